@@ -8,11 +8,17 @@ outputs) over the batch, inputs already resident in HBM.  With --gpus N every ra
 block of episodes and the ranks all-gather the chosen (action, cost) over RCCL.  The per-rank batch is
 the SAME for every N (weak scaling, 4096 unless --episodes says otherwise), so the points of a scaling
 curve differ in nothing but the rank count; BASELINE configs[3] (65536 episodes over 8 GPUs = 8192 per
-rank) is timed as well in every multi-rank run and reported under "config4_shard" (its one-GPU
+rank) is timed as well in every multi-rank --full run and reported under "config4_shard" (its one-GPU
 counterpart is `--episodes 8192`).
 
 Launch: `python bench.py --gpus N` starts the N ranks itself (one process per GPU); under
 torchrun (WORLD_SIZE set) it joins as one rank.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line.  Everything else -- the seed-median sweep,
+the pipelined figure, configs[3]'s shard in multi-rank runs, the `secondary` workloads, the CPU baseline with its parity
+check against the oracle and the fp64 / issue figures built on it, the combined tick's PyTorch-ROCm actor leg -- runs only
+with --full.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64, finite: see dump_outputs), for
+comparing two builds output for output: the inputs are seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -30,6 +36,7 @@ FP64_VALU_PEAK_TFLOPS = 78.6   # fp64 vector peak
 # "stale": true wherever it quotes such a counter and the running library was built from other sources.
 MEASURED_CANDIDATES = [os.path.join(REPO, "profiles", r, "measured.json") for r in ("r6", "r5", "r4", "r3")]
 MEASURED = next((m for m in MEASURED_CANDIDATES if os.path.exists(m)), MEASURED_CANDIDATES[0])
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
 
 
 def parse_args():
@@ -44,6 +51,11 @@ def parse_args():
                          "RL+MPC combined controller (configs/combined_medium_1.json) with the reference's pretrained ddpg_medium1 actor; episodes: batched merge "
                          "environments with configs/train_moderate_1.json's traffic under that controller (BASELINE configs[4] as a labelled "
                          "throughput demo: the reference has no counterpart)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, run everything else the benchmark measures and checks "
+                    "(seed-median sweep, pipelined figure, configs[3]'s shard, secondary workloads, CPU baseline + parity against the oracle, "
+                    "fp64 / issue figures, the combined tick's PyTorch-ROCm actor leg); the options below select parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float64; non-finite entries as 0.0 with <name>_nonfinite.npy codes; a seeded sample of the episodes if over 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` object of the headline line (the reference's own lattice, st.do_st_control and "
                     "the combined controller's tick, each a short timed run in the same process after the headline loop)")
@@ -51,7 +63,40 @@ def parse_args():
                     "output buffers each; 0/1 = skip); the headline value is always one batch at a time")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall-clock target per CPU solver (heap, layered) of the cpu_baseline sample")
     ap.add_argument("--seeds", type=str, default="1000,1,2,3,4", help="state-generator seeds of the seed-median figure (h40a21 / default workloads, one GPU); '' = skip")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(path, arrays):
+    """Writes every array as <path>/<name>.npy in float64 (exact for the int32 outputs).  The files hold finite numbers only: some outputs are
+    non-finite by definition (path_dist is NaN past best_t, a statistic that does not apply is NaN), so each floating-point output is written
+    with 0.0 in those places and comes with <name>_nonfinite.npy, 0 finite / 1 NaN / 2 +inf / 3 -inf per entry -- together exactly what the
+    caller received.  All arrays share the episode axis; over DUMP_LIMIT_BYTES in all, each keeps the same fixed, seeded sample of episodes,
+    whose indices go to sample_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    files = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        if np.issubdtype(v.dtype, np.floating):
+            code = np.select([np.isnan(v), v == np.inf, v == -np.inf], [1.0, 2.0, 3.0], 0.0)
+            files[k] = np.where(code == 0.0, v, 0.0).astype(np.float64)
+            files[k + "_nonfinite"] = code
+        else:
+            files[k] = v.astype(np.float64)
+    arrays = files
+    budget = DUMP_LIMIT_BYTES - 128 * (len(arrays) + 1)       # 128 B: the .npy header of each file
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        n = next(iter(arrays.values())).shape[0]
+        m = int(budget // (total // n + 8))
+        rows = np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def cpu_info():
@@ -193,8 +238,8 @@ def secondary_workloads(args, dev, local_rank, np, torch, pkg, _capi, synth):
     from rl_mpc_lanemerging_amd import combined_bench
     import copy
     a2 = copy.copy(args)
-    a2.episodes, a2.steps, a2.warmup, a2.no_cpu_baseline = n, steps, warm, True
-    cb = combined_bench.run(a2, 0, 1, dev, None)
+    a2.episodes, a2.steps, a2.warmup, a2.no_cpu_baseline, a2.dump_outputs = n, steps, warm, True, None
+    cb, _ = combined_bench.run(a2, 0, 1, dev, None)
     out["combined_tick"] = {"metric": cb["metric"], "value": cb["value"], "unit": cb["unit"], "ms_per_step": cb["ms_per_step"], "episodes": n, "steps": steps,
                             "actor": cb["config"]["actor"], "decisions": cb["decisions"],
                             "controller_solves_per_decision": cb["config"]["controller_solves_per_decision"],
@@ -232,15 +277,17 @@ def run(args):
 
     if args.workload == "combined":
         from rl_mpc_lanemerging_amd import combined_bench
-        out = combined_bench.run(args, rank, world, dev, dist)
+        out, arrays = combined_bench.run(args, rank, world, dev, dist)
     elif args.workload == "episodes":
         from rl_mpc_lanemerging_amd import episodes_bench
-        out = episodes_bench.run(args, rank, world, dev, dist)
+        out, arrays = episodes_bench.run(args, rank, world, dev, dist)
     else:
-        out = run_solver(args, rank, world, local_rank, dev, dist, np, torch, pkg, _capi, sharding, synth)
+        out, arrays = run_solver(args, rank, world, local_rank, dev, dist, np, torch, pkg, _capi, sharding, synth)
 
     if use_dist:
         dist.destroy_process_group()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, arrays)
     # RCCL prints a version banner through C stdio: flush it first so that the JSON line is the last line of stdout
     import ctypes
     try:
@@ -333,6 +380,13 @@ def run_solver(args, rank, world, local_rank, dev, dist, np, torch, pkg, _capi, 
         # every rank must hold every rank's (action, cost): check this rank's own rows of the gathered buffer
         own = gathered[rank * n:(rank + 1) * n]
         assert torch.equal(own[:, 0].to(torch.int32), d_path[:, 1]) and torch.equal(own[:, 1], d_cost), "gather mismatch"
+    arrays = None
+    if args.dump_outputs:       # what the last timed step returned to its caller (the untimed step below recomputes the same bits)
+        arrays = {"path_idx": d_path, "best_t": d_bt, "cost": d_cost}
+        arrays.update({"speed": d_speed, "fine": d_fine, "fine_len": d_fine_len} if control else {"path_dist": d_pd, "crash": d_crash})
+        if use_dist:
+            arrays["action_cost"] = d_ac
+        arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
 
     step()                      # one untimed step outside the profiling window to read the tier statistics
     torch.cuda.synchronize()
@@ -371,21 +425,21 @@ def run_solver(args, rank, world, local_rank, dev, dist, np, torch, pkg, _capi, 
     # the headline batch is one draw of the state generator; the step time depends on the draw (its longest searches): median over seeds
     seed_median = None
     seeds = [int(x) for x in args.seeds.split(",") if x.strip()] if args.seeds else []
-    if seeds and not use_dist and not control:
+    if args.full and seeds and not use_dist and not control:
         per_seed = {}
         for sd in seeds:
             per_seed[sd] = n * args.steps / (elapsed if sd == 1000 + rank else timed_other_batch(n, sd))
         seed_median = {"seeds": seeds, "solves_per_s": {str(k_): v_ for k_, v_ in per_seed.items()},
                        "value_seed_median": float(np.median(list(per_seed.values()))), "min": min(per_seed.values()), "max": max(per_seed.values())}
-    # BASELINE configs[3]: 65536 episodes over 8 GPUs = 8192 per rank, timed in every multi-rank run next to the curve's own per-rank batch
+    # BASELINE configs[3]: 65536 episodes over 8 GPUs = 8192 per rank, timed in every multi-rank --full run next to the curve's own per-rank batch
     config4 = None
-    if use_dist and not control and n != 8192:
+    if args.full and use_dist and not control and n != 8192:
         el4 = timed_other_batch(8192, 2000 + rank)
         config4 = {"episodes_per_gpu": 8192, "episodes_total": 8192 * world, "value": 8192 * world * args.steps / el4, "unit": "solves/s",
                    "ms_per_step": el4 / args.steps * 1e3, "note": "BASELINE configs[3] is this with 8 ranks (65536 episodes); not the headline, whose per-rank batch is the same for every N"}
 
     pipelined = None
-    if args.pipelined > 1 and not use_dist and not control:
+    if args.full and args.pipelined > 1 and not use_dist and not control:
         # serving pattern: consecutive batches on separate streams / contexts / output buffers, so that one batch's tail (its
         # last long searches, its wide-window launch) overlaps the next batch's start.  Reported next to the headline, never as it.
         S_ = args.pipelined
@@ -475,7 +529,7 @@ def run_solver(args, rank, world, local_rank, dev, dist, np, torch, pkg, _capi, 
         out["stages"] = {"lattice_search_ms": prof["solve_ms"] / max(prof["launches"], 1),
                          "qp_resampling_ms": ms_per_step - prof["solve_ms"] / max(prof["launches"], 1),
                          "note": "lattice search from HIP events inside the library; QP = step time minus that"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_secondary and args.workload == "h40a21" and args.episodes in (0, 4096):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_secondary and args.workload == "h40a21" and args.episodes in (0, 4096):
         # the other configs, witnessed by the same run (after the timed headline loop; nothing of the headline depends on it)
         c0 = time.perf_counter()
         try:
@@ -484,7 +538,7 @@ def run_solver(args, rank, world, local_rank, dev, dist, np, torch, pkg, _capi, 
         finally:
             pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
             pkg.apply_overrides(pkg.SYNTHETIC_H40A21)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import st_oracle as orc
         op = orc.OrcParams.from_dict(params.as_dict())
         base, counts, _ = cpu_baseline(orc, op, ego, kc, ox, ov, args.cpu_seconds)
@@ -562,7 +616,7 @@ def run_solver(args, rank, world, local_rank, dev, dist, np, torch, pkg, _capi, 
                             "stale": measured_stale,
                             "source": "%s (rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU ..., scripts/profile_gpu.sh; taken from library sources %s), kernel time of this run"
                                       % (measured_rel, measured.get("csrc_hash"))}
-    return out
+    return out, arrays
 
 
 def _spawned(local_rank, args, port):

@@ -78,11 +78,13 @@ def run(args, rank, world, dev, dist):
             el = float(t.item())
         return el, d_
 
-    # BASELINE configs[2] words the actor as "on PyTorch-ROCm": timed that way too, next to the fused kernel the package uses by default
-    elapsed_torch, d_torch = timed("torch")
+    # BASELINE configs[2] words the actor as "on PyTorch-ROCm": timed that way too (--full), next to the fused kernel the package uses by default
+    d_torch = None
+    if args.full:
+        elapsed_torch, d_torch = timed("torch")
     ctx.combined_counts(reset=True)
     elapsed, d = timed("hip")
-    same_decisions = int((d["reason"] != d_torch["reason"]).sum().item())
+    arrays = {k: v.cpu().numpy() for k, v in d.items()} if args.dump_outputs else None
     reason = d["reason"].cpu().numpy()
     decisions, control_solves = ctx.combined_counts()
     out = {"metric": "combined RL+MPC controller ticks/sec (configs/combined_medium_1.json, pretrained ddpg_medium1 actor)",
@@ -94,13 +96,14 @@ def run(args, rank, world, dev, dist):
                                   "re-sampling for the states whose decision hands control over, decision"
                                   % (n, max(int(S.ROLLOUT_LENGTH), 1), _capi.num_t(params), _capi.num_s(params, 0.0)),
                       "episodes_per_gpu": n, "actor": COMBINED_MEDIUM_1_ACTOR, "controller_solves_per_decision": control_solves / max(decisions, 1)},
-           "actor_on_pytorch_rocm": {"value": n * world * args.steps / elapsed_torch, "unit": "ticks/s", "ms_per_step": elapsed_torch / args.steps * 1e3,
-                                     "note": "same tick with the network as three rocBLAS GEMMs + elementwise kernels on PyTorch-ROCm (inputs from k_policy_features)",
-                                     "decisions_that_differ_from_the_fused_kernel": same_decisions},
            "library": {"backend": _capi.backend_info()},
            "decisions": {"policy_kept": int((reason == 0).sum()), "crash_predicted": int((reason == 1).sum()), "too_fast": int((reason == 2).sum()),
                          "probe_rejected": int((reason == 3).sum()), "st_better": int((reason == 4).sum())}}
+    if d_torch is not None:
+        out["actor_on_pytorch_rocm"] = {"value": n * world * args.steps / elapsed_torch, "unit": "ticks/s", "ms_per_step": elapsed_torch / args.steps * 1e3,
+                                        "note": "same tick with the network as three rocBLAS GEMMs + elementwise kernels on PyTorch-ROCm (inputs from k_policy_features)",
+                                        "decisions_that_differ_from_the_fused_kernel": int((d["reason"] != d_torch["reason"]).sum().item())}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["parity_note"] = ("decisions with this actor are pinned by the suite (test_actor.py) against golden_combined_real.npz (the reference's do_combined_control with the same "
                               "network); the decision logic by test_combined.py; this workload has no CPU baseline leg")
-    return out
+    return out, arrays

@@ -60,4 +60,4 @@ def run(args, rank, world, dev, dist):
                                    % (n, max(int(S.ROLLOUT_LENGTH), 1), _capi.num_t(r.params), _capi.num_s(r.params, 0.0), S.BASE_TRAFFIC_INTERVAL, S.OTHER_CAR_SPEED),
                        "episodes_per_gpu": n, "note": "BASELINE configs[4] has no counterpart in the reference (its training never calls the solver, SURVEY R7): demo only"},
             "environments_still_running_at_end": running, "ticks_per_environment": int(r.ticks_done), "untimed_ticks_before": PRE_TICKS,
-            "takeover_share": float(np.nanmean(res["percent_st"]))}
+            "takeover_share": float(np.nanmean(res["percent_st"]))}, (res if args.dump_outputs else None)

@@ -4,7 +4,7 @@
 # stages:
 #   tests[=<pytest -k expression>]            pytest -m gpu (all, or the selected tests)
 #   smoke                                     __graft_entry__.smoke()
-#   bench[=<bench.py args, '+' for spaces>]   one bench.py line -> bench_<i>.json
+#   bench[=<bench.py args, '+' for spaces>]   one `bench.py --full` line -> bench_<i>.json
 #   sweep=<n>/<seeds>/<lib|->/<spec>[/<spec>...]   scripts/lab/sweep.py with STMPC_LIB=variants/libstmpc_<lib>.so ('-' = the product build);
 #                                             a spec is tag:ENV=V;ENV=V  (use ',' inside seeds, '+' for spaces)
 #   trace[=<bench args>]                      rocprofv3 --kernel-trace --stats of a short bench run -> trace_<i>/
@@ -29,7 +29,7 @@ for stage in "$@"; do
     smoke)
       timeout 300 python __graft_entry__.py smoke > $O/smoke_$i.log 2>&1; echo "[$stage] rc=$? $(tail -1 $O/smoke_$i.log)";;
     bench)
-      timeout 900 python bench.py $arg_sp > $O/bench_$i.json 2> $O/bench_$i.err; rc=$?
+      timeout 900 python bench.py --full $arg_sp > $O/bench_$i.json 2> $O/bench_$i.err; rc=$?
       echo "[$stage] rc=$rc $(python - $O/bench_$i.json <<'PY'
 import json,sys
 try:

@@ -326,7 +326,7 @@ def test_bench_forced_rccl_single_rank():
     import json, subprocess, sys
     env = dict(os.environ, STMPC_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"),
-                          "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--episodes", "512"], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--episodes", "512"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and "all_gather" in line["config"]["collective"] and line["value"] > 0
