@@ -18,6 +18,8 @@
  *                                network stays the caller's; everything around it runs here)
  *   stmpc_policy_features_device <- dqn.get_state_vector_from_base_state  dqn.py:389-446 (+ the float32 cast and TimeFeature input of ddpg.py:41,84)
  *   stmpc_actor_eval_device   <- DDPGAgent.get_control                ddpg.py:83-87 (state vector + the pretrained policy network, one launch)
+ *   stmpc_env_*               <- merge_gym.JerkEnv / ContinuousJerkEnv / AccelerationEnv  merge_gym.py:15-221 with the rewards of
+ *                                dqn.get_reward_function (dqn.py:449-563, rl.py:168-174), batched on the SUMO-free world (stmpc_sim_*)
  *   stmpc_ego_s               <- control.get_ego_s                   control.py:373-380
  *   stmpc_num_s / stmpc_num_t <- the np.arange sizes at st.py:31-32
  *
@@ -72,7 +74,8 @@
 extern "C" {
 #endif
 
-#define STMPC_ABI_VERSION 6   /* bumped whenever an exported signature, a struct layout or the accepted values of a field change (6: stmpc_sim_cfg.yield_overlap must be 2); see stmpc_abi_version() */
+#define STMPC_ABI_VERSION 7   /* bumped whenever an exported signature, a struct layout or the accepted values of a field change (6: stmpc_sim_cfg.yield_overlap must be 2;
+                                 7: the vector environment stmpc_env_*); see stmpc_abi_version() */
 
 #define STMPC_OK        0
 #define STMPC_EINVAL   -1   /* bad argument (NULL, size, Kmax/H/S out of range) */
@@ -445,6 +448,85 @@ int stmpc_sim_read(stmpc_ctx *ctx, int N, int32_t *status, int32_t *ticks, doubl
 /* status [N] into a DEVICE array, asynchronously on `stream`: lets a controller loop mask its own per-environment statistics to the
  * environments that are still running without a host round trip. */
 int stmpc_sim_status_device(stmpc_ctx *ctx, int N, int32_t *d_status, void *stream);
+
+/*
+ * Vector environment: the reference's gym environments (merge_gym.py) for N environments of the world above, stepped in lock-step on the device.
+ * One step = the env's action handling -> stmpc_sim_step_device's kernel, unchanged -> reward, terminated / truncated, observation, and for the
+ * environments that finished on this tick their final observation and statistics and (autoreset) the reset to their next episode.
+ *   stmpc_env_reset_device  stmpc_sim_init_device(sim_cfg) + every environment back to episode 0 (episode 0 IS that sim_init); copies the discrete
+ *                           action table (HOST pointer) to the device and synchronises on `stream` for it; d_obs [N][obs_stride] float32 may be NULL
+ *   stmpc_env_step_device   asynchronous, no host synchronisation.  d_action: fp64 [N] jerks (STMPC_ENV_CONTINUOUS_JERK, not clipped to the action Box:
+ *                           the reference does not clip either) or int32 [N] indices into action_values (discrete modes; an index out of range
+ *                           leaves that environment's speed unchanged for the tick and makes the next stmpc_check_error return STMPC_EINVAL).
+ *                           Outputs: d_obs [N][obs_stride] float32 (dqn.get_state_vector_from_base_state of the new state, dqn.py:389-446, without
+ *                           the TimeFeature input; zeros after a crash or an arrival, merge_gym.py:109,114; with autoreset the start state of the
+ *                           next episode where one ended), d_reward [N] fp64 (the reward function + the invalid-action reward, merge_gym.py:110-135),
+ *                           d_terminated / d_truncated [N] uint8 (status 1 arrived or 2 crashed / status 3 out of time); where an episode ended:
+ *                           d_final_obs [N][obs_stride] (the observation the reference returns for that step) and d_final_stats
+ *                           [N][STMPC_ENV_NSTAT] (acc[STMPC_SIM_NACC] as stmpc_sim_read, status, ticks, return of the episode) -- rows of the other
+ *                           environments are left as they were; either may be NULL.  Without autoreset a finished environment idles: reward 0,
+ *                           both flags 0, observation as on its last step.
+ *                           Episode j >= 1 of environment e starts as environment e of stmpc_sim_init_device with seed stmpc_env_episode_seed(seed, j)
+ *                           (every field but the draw counter, which starts j * 2^16 further on for j < 2^16 and at an offset taken from the
+ *                           episode seed after that: the traffic after the reset is drawn from the run's
+ *                           seed by the unchanged world step).  The reset state is the world's start state, not the reference's 20 s warm-up
+ *                           (merge_gym.py:142-150).
+ *   stmpc_env_reward_device the reward function alone for arbitrary batched states (replay buffers): ego4 [N][4] x, y, v, a; k [N]; other_x [N][Kmax]
+ *                           front to back (Kmax <= 64; other_v / other_a are not read and may be NULL); jerk [N]; crashed / arrived [N] int32 (may be NULL)
+ *   stmpc_env_drain         host copies of the statistics rows of the episodes finished since the last drain or reset ([n_rows][STMPC_ENV_LOG_COLS]: the
+ *                           d_final_stats row, environment, episode index; in completion order); synchronises.  The context keeps at most
+ *                           log_capacity rows; *n_dropped counts the ones it had to drop
+ *   stmpc_env_episode_ticks_device  ticks of each environment's current episode (0 right after a reset; a DDPG agent's TimeFeature input) into a
+ *                           DEVICE int32 [N] array, asynchronously on `stream` (one device-to-device copy)
+ *   A context holds one world: stmpc_sim_init_device on it ends the environment (its step entry then returns STMPC_EINVAL until the next
+ *   stmpc_env_reset_device), and the action_mode of every step must be the one of the reset (else STMPC_EINVAL).
+ *   stmpc_env_episode_seed  host only: the seed of episode `episode` (0: `seed` itself; else splitmix64 of seed + episode * 0x9E3779B97F4A7C15)
+ * Exactness: the action handling, rewards and observations are the reference's expressions in its operation order, except that its x ** 2
+ * (a libm pow call, not correctly rounded in glibc >= 2.28) is the correctly rounded x * x here.
+ */
+#define STMPC_ENV_CONTINUOUS_JERK 0  /* ContinuousJerkEnv, "sumo-jerk-continuous-v0" (merge_gym.py:217-227) */
+#define STMPC_ENV_JERK            1  /* JerkEnv, "sumo-jerk-v0" (merge_gym.py:99-100: action_values = JERK_VALUES_DQN) */
+#define STMPC_ENV_ACCELERATION    2  /* AccelerationEnv, "sumo-accel-v0" (merge_gym.py:187-214: action_values = ACCELERATION_VALUES_DQN) */
+#define STMPC_REWARD_CONTINUOUS   0  /* dqn.continuous_reward        dqn.py:463-505 */
+#define STMPC_REWARD_SLOTTED      1  /* rl.slotted_reward            rl.py:168-174 */
+#define STMPC_REWARD_SLOTTED_JERK 2  /* dqn.slotted_reward_with_jerk dqn.py:557-563 */
+#define STMPC_REWARD_ST           3  /* dqn.st_reward                dqn.py:508-554 */
+#define STMPC_ENV_MAX_ACTIONS 256
+#define STMPC_ENV_NSTAT 15
+#define STMPC_ENV_LOG_COLS 17
+typedef struct stmpc_env_cfg {
+    int32_t action_mode;             /* STMPC_ENV_* (Settings.GYM_ENVIRONMENT, config.py:12) */
+    int32_t reward_function;         /* STMPC_REWARD_* (Settings.REWARD_FUNCTION, config.py:59; dqn.get_reward_function, dqn.py:449-460) */
+    double tick_length;              /* Settings.TICK_LENGTH */
+    double crash_reward, success_reward, time_reward;            /* Settings.CRASH_REWARD, SUCCESS_REWARD, TIME_REWARD (config.py:62-64) */
+    double wt_smooth, wt_safe, wt_efficient;                     /* Settings.WT_SMOOTH, WT_SAFE, WT_EFFICIENT (config.py:66-68) */
+    double alt_v_weight, alt_a_weight, alt_j_weight, alt_d_weight; /* Settings.ALT_*_WEIGHT (config.py:73-76) */
+    double min_follow_distance;      /* Settings.MIN_FOLLOW_DISTANCE (config.py:71) */
+    double desired_speed;            /* Settings.DESIRED_SPEED (config.py:94) */
+    double car_length;               /* Settings.CAR_LENGTH */
+    double invalid_action_penalty;   /* Settings.INVALID_ACTION_PENALTY (config.py:140; merge_gym.py:25) */
+    double minimum_negative_jerk, maximum_positive_jerk;         /* Settings.MINIMUM_NEGATIVE_JERK, MAXIMUM_POSITIVE_JERK */
+    double max_negative_acceleration, max_positive_acceleration; /* Settings.MAX_NEGATIVE_ACCELERATION, MAX_POSITIVE_ACCELERATION */
+    double max_speed;                /* Settings.MAX_SPEED */
+    const double *action_values;     /* HOST [n_action_values]: JERK_VALUES_DQN / ACCELERATION_VALUES_DQN (config.py:114-115) in index order; copied by
+                                        stmpc_env_reset_device (unused by STMPC_ENV_CONTINUOUS_JERK) */
+    int32_t n_action_values;
+    int32_t autoreset;               /* 1: an environment whose episode ended starts its next one in the same step */
+    int32_t log_capacity;            /* episode statistics rows kept between drains (0: 16 N) */
+    int32_t reserved0;
+    const stmpc_policy_features_cfg *features;  /* the observation (time_feature must be 0) */
+} stmpc_env_cfg;
+int stmpc_env_reset_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfg, const stmpc_env_cfg *env_cfg, int N, float *d_obs,
+                           int obs_stride, void *stream);
+int stmpc_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfg, const stmpc_env_cfg *env_cfg, int N, const void *d_action,
+                          float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs,
+                          double *d_final_stats, void *stream);
+int stmpc_env_reward_device(stmpc_ctx *ctx, const stmpc_env_cfg *env_cfg, int N, int Kmax, const double *d_ego4, const int32_t *d_k, const double *d_ox,
+                            const double *d_ov, const double *d_oa, const double *d_jerk, const int32_t *d_crashed, const int32_t *d_arrived,
+                            double *d_reward, void *stream);
+int stmpc_env_drain(stmpc_ctx *ctx, int max_rows, double *rows, int64_t *n_rows, int64_t *n_dropped);
+int stmpc_env_episode_ticks_device(stmpc_ctx *ctx, int N, int32_t *d_ticks, void *stream);
+uint64_t stmpc_env_episode_seed(uint64_t seed, uint32_t episode);
 
 /* Device arithmetic probe used by the parity tests: out[i] = a[i] op b[i] evaluated on the GPU
  * with the kernels' compile flags. op: 0 div, 1 sqrt(a), 2 mul, 3 add, 4 fma(a,a,b*b), 5 the five-operation

@@ -110,6 +110,36 @@ class SimCfg(C.Structure):
         return self
 
 
+class EnvCfg(C.Structure):
+    """``stmpc_env_cfg`` (include/stmpc.h): action mode, reward function and the reference's reward / action settings (merge_gym.py, dqn.py:449-563)."""
+    _fields_ = [("action_mode", C.c_int32), ("reward_function", C.c_int32), ("tick_length", C.c_double), ("crash_reward", C.c_double),
+                ("success_reward", C.c_double), ("time_reward", C.c_double), ("wt_smooth", C.c_double), ("wt_safe", C.c_double), ("wt_efficient", C.c_double),
+                ("alt_v_weight", C.c_double), ("alt_a_weight", C.c_double), ("alt_j_weight", C.c_double), ("alt_d_weight", C.c_double),
+                ("min_follow_distance", C.c_double), ("desired_speed", C.c_double), ("car_length", C.c_double), ("invalid_action_penalty", C.c_double),
+                ("minimum_negative_jerk", C.c_double), ("maximum_positive_jerk", C.c_double), ("max_negative_acceleration", C.c_double),
+                ("max_positive_acceleration", C.c_double), ("max_speed", C.c_double), ("action_values", C.POINTER(C.c_double)), ("n_action_values", C.c_int32),
+                ("autoreset", C.c_int32), ("log_capacity", C.c_int32), ("reserved0", C.c_int32), ("features", C.POINTER(FeaturesCfg))]
+
+    @classmethod
+    def from_settings(cls, S, action_mode, reward_function, action_values=None, autoreset=True, log_capacity=0):
+        """``action_mode`` / ``reward_function``: the STMPC_ENV_* / STMPC_REWARD_* codes; ``action_values``: the discrete action table in index order.
+        The arrays it points to are kept alive by this object."""
+        c = cls(action_mode=int(action_mode), reward_function=int(reward_function), tick_length=S.TICK_LENGTH, crash_reward=S.CRASH_REWARD,
+                success_reward=S.SUCCESS_REWARD, time_reward=S.TIME_REWARD, wt_smooth=S.WT_SMOOTH, wt_safe=S.WT_SAFE, wt_efficient=S.WT_EFFICIENT,
+                alt_v_weight=S.ALT_V_WEIGHT, alt_a_weight=S.ALT_A_WEIGHT, alt_j_weight=S.ALT_J_WEIGHT, alt_d_weight=S.ALT_D_WEIGHT,
+                min_follow_distance=S.MIN_FOLLOW_DISTANCE, desired_speed=S.DESIRED_SPEED, car_length=S.CAR_LENGTH,
+                invalid_action_penalty=S.INVALID_ACTION_PENALTY, minimum_negative_jerk=S.MINIMUM_NEGATIVE_JERK, maximum_positive_jerk=S.MAXIMUM_POSITIVE_JERK,
+                max_negative_acceleration=S.MAX_NEGATIVE_ACCELERATION, max_positive_acceleration=S.MAX_POSITIVE_ACCELERATION, max_speed=S.MAX_SPEED,
+                autoreset=int(bool(autoreset)), log_capacity=int(log_capacity))
+        c._features = FeaturesCfg.from_settings(S, time_feature=False)
+        c.features = C.pointer(c._features)
+        if action_values is not None:
+            c._actions = np.ascontiguousarray(action_values, dtype=np.float64)
+            c.action_values = c._actions.ctypes.data_as(C.POINTER(C.c_double))
+            c.n_action_values = int(c._actions.size)
+        return c
+
+
 class ProfileTotals(C.Structure):
     _fields_ = [("launches", C.c_int64), ("episodes", C.c_int64), ("solve_ms", C.c_double), ("dp_kernel_ms", C.c_double)]
 
@@ -126,9 +156,14 @@ EXPORTS = (
     "stmpc_abi_version", "stmpc_check_error", "stmpc_predict_batch_acc", "stmpc_sim_status_device",
     "stmpc_policy_features_device", "stmpc_policy_features_len", "stmpc_combined_counts", "stmpc_solve_batch_device_ac",
     "stmpc_actor_create", "stmpc_actor_destroy", "stmpc_actor_eval_device",
+    "stmpc_env_reset_device", "stmpc_env_step_device", "stmpc_env_reward_device", "stmpc_env_drain", "stmpc_env_episode_seed",
+    "stmpc_env_episode_ticks_device",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
-ABI_VERSION = 6     # STMPC_ABI_VERSION of include/stmpc.h this binding was written against
+ENV_CONTINUOUS_JERK, ENV_JERK, ENV_ACCELERATION = 0, 1, 2                                 # STMPC_ENV_*
+REWARD_CONTINUOUS, REWARD_SLOTTED, REWARD_SLOTTED_JERK, REWARD_ST = 0, 1, 2, 3             # STMPC_REWARD_*
+ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
+ABI_VERSION = 7     # STMPC_ABI_VERSION of include/stmpc.h this binding was written against
 
 QP_NMAX = 64        # STMPC_QP_NMAX
 QP_MAXITERS = 10    # STMPC_QP_MAXITERS (solvers.options['maxiters'], st.py:17)
@@ -210,6 +245,14 @@ def load():
     lib.stmpc_finer_fit_batch.argtypes = [vp, pp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, dp, ip, dp, dp, dp,
                                           C.c_int, dp, ip, ip]
     lib.stmpc_st_control_batch.argtypes = [vp, pp, C.c_double, C.c_int, C.c_int, dp, ip, dp, dp, dp, ip, ip, dp, dp, ip]
+    ep = C.POINTER(EnvCfg)
+    lib.stmpc_env_reset_device.argtypes = [vp, pp, sp, ep, C.c_int, vp, C.c_int, vp]
+    lib.stmpc_env_step_device.argtypes = [vp, pp, sp, ep, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.stmpc_env_reward_device.argtypes = [vp, ep, C.c_int, C.c_int] + [vp] * 9 + [vp]
+    lib.stmpc_env_drain.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.stmpc_env_episode_ticks_device.argtypes = [vp, C.c_int, vp, vp]
+    lib.stmpc_env_episode_seed.argtypes = [C.c_uint64, C.c_uint32]
+    lib.stmpc_env_episode_seed.restype = C.c_uint64
     lib.stmpc_st_control_batch_device.argtypes = [vp, pp, C.c_double, C.c_int, C.c_int] + [vp] * 10 + [vp]
     _lib = lib
     return lib
@@ -249,6 +292,11 @@ def fastdiv2_check(d):
     zl = C.c_double(0.0)
     ok = load().stmpc_fastdiv2_check(float(d), C.byref(zl))
     return bool(ok), zl.value
+
+
+def env_episode_seed(seed, episode):
+    """``stmpc_env_episode_seed``: the seed episode ``episode`` of an environment starts from (host only)."""
+    return int(load().stmpc_env_episode_seed(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(episode))))
 
 
 def backend_info():
@@ -505,6 +553,29 @@ class Context:
     def sim_status_device(self, N, d_status, stream=0):
         """Environment status words into a device int32 array (asynchronous): 0 running, 1 arrived, 2 crashed, 3 out of time."""
         self._chk(self._lib.stmpc_sim_status_device(self._h, int(N), d_status, stream))
+
+    # -- vector environment (stmpc_env_*) ---------------------------------------------------------------
+    def env_reset(self, params, sim_cfg, env_cfg, N, d_obs, obs_stride, stream=0):
+        self._chk(self._lib.stmpc_env_reset_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), int(N), d_obs, int(obs_stride), stream))
+
+    def env_step(self, params, sim_cfg, env_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs=0, d_final_stats=0, stream=0):
+        self._chk(self._lib.stmpc_env_step_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), int(N), d_action, d_obs, int(obs_stride),
+                                                  d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream))
+
+    def env_reward(self, env_cfg, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed=0, d_arrived=0, d_reward=0, stream=0):
+        self._chk(self._lib.stmpc_env_reward_device(self._h, C.byref(env_cfg), int(N), int(Kmax), d_ego4, d_k, d_ox, 0, 0, d_jerk, d_crashed, d_arrived,
+                                                    d_reward, stream))
+
+    def env_episode_ticks(self, N, d_ticks, stream=0):
+        """Ticks of each environment's current episode into a device int32 [N] array (asynchronous)."""
+        self._chk(self._lib.stmpc_env_episode_ticks_device(self._h, int(N), d_ticks, stream))
+
+    def env_drain(self, capacity):
+        """(rows [n][ENV_LOG_COLS], dropped): the episodes finished since the last drain (synchronises)."""
+        rows = np.zeros((max(int(capacity), 1), ENV_LOG_COLS))
+        n, dropped = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.stmpc_env_drain(self._h, int(capacity), _dptr(rows), C.byref(n), C.byref(dropped)))
+        return rows[:n.value], int(dropped.value)
 
     def check_error(self):
         """Synchronise and raise what kernels of earlier (asynchronous) calls on this context flagged; see ``stmpc_check_error``."""

@@ -2,7 +2,8 @@
 
 Mirrors ``config.py:7-170`` of the reference for exactly the attributes that reach the
 ST ("MPC") hot path (``config.py:30-37, 94-110, 143, 145-154``); everything else in the
-reference's ``Settings`` (RL training, logging, SUMO) is outside this package's scope.
+reference's ``Settings`` (RL training, logging, SUMO) is outside this package's scope -- except the gym environment, its reward
+functions and actions (``config.py:12, 42-44, 51-55, 59-76, 81, 114-115, 140``), which ``vec_env.MergeVecEnv`` reads.
 ``load_from_file`` keeps the reference's semantics (``config.py:161-170``): every key of
 the JSON file is set as a class attribute, so the shipped experiment configs
 (``configs/*.json``) load unchanged.
@@ -11,6 +12,9 @@ import json
 
 
 class Settings:
+    # Task (config.py:12): the gym environment a learner trains on (vec_env.MergeVecEnv)
+    GYM_ENVIRONMENT = "sumo-jerk-continuous-v0"
+
     # Simulation (config.py:30-37)
     TICK_LENGTH = 0.2
     MAX_POSITIVE_ACCELERATION = 4.5
@@ -19,6 +23,40 @@ class Settings:
     MAXIMUM_POSITIVE_JERK = 5.0
     MAX_SPEED = 30
     CAR_LENGTH = 5.0
+
+    # Simple traffic distribution (config.py:42-44) and random start speed (config.py:51-55): the world of episodes.py / vec_env.py
+    VARY_TRAFFIC_START_TIMES = True
+    BASE_TRAFFIC_INTERVAL = 1.2
+    OTHER_CAR_SPEED = 7.0
+    START_SPEED = 15
+    RANDOMIZE_START_SPEED = True
+    START_SPEED_VARIANCE = 5
+    MIN_START_SPEED = 5
+    MAX_START_SPEED = 25
+
+    # Reward functions (config.py:59-76; dqn.get_reward_function, dqn.py:449-460)
+    REWARD_FUNCTION = "Continuous"           # "Continuous" or "Slotted" or "ST" or "Slotted Jerk"
+    CRASH_REWARD = -10
+    SUCCESS_REWARD = 10
+    TIME_REWARD = -0.1
+    WT_SMOOTH = 0.1
+    WT_SAFE = 0.1
+    WT_EFFICIENT = 0.01
+    DESIRED_TTC = 3
+    MIN_FOLLOW_DISTANCE = 3
+    ALT_V_WEIGHT = 0.0001
+    ALT_A_WEIGHT = 0.01
+    ALT_J_WEIGHT = 0.05  # Also used for slotted reward + jerk
+    ALT_D_WEIGHT = 0.05
+
+    # Episode length in seconds (config.py:81; merge_gym.py:24)
+    MAX_EPISODE_LENGTH = 100
+
+    # Discrete actions of the gym environments (config.py:114-115) and their invalid-action penalty (config.py:140)
+    JERK_VALUES_DQN = {0: -5, 1: -2.5, 2: 0, 3: 2.5, 4: 5}
+    ACCELERATION_VALUES_DQN = {0: -6.0, 1: -5.5, 2: -5.0, 3: -4.5, 4: -4.0, 5: -3.0, 6: -2.5, 7: -2.0, 8: -1.0, 9: -0.5, 10: 0.0, 11: 0.5, 12: 1.0, 13: 1.5,
+                               14: 2.0, 15: 2.5, 16: 3.0, 17: 3.5, 18: 4.0, 19: 4.5}
+    INVALID_ACTION_PENALTY = 0.0
 
     # S-T solver and continuous reward (config.py:94)
     DESIRED_SPEED = 30.0

@@ -6,6 +6,7 @@
 #include "stmpc_cc_kernels.hpp"
 #include "stmpc_nj_kernels.hpp"
 #include "stmpc_actor_kernels.hpp"
+#include "stmpc_env_kernels.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -138,6 +139,9 @@ struct stmpc_ctx {
     // batched episode simulator (stmpc_sim_*)
     DevBuf sim_ego, sim_nveh, sim_vx, sim_vv, sim_va, sim_vc, sim_delay, sim_status, sim_ticks, sim_rng, sim_acc, sim_route;
     int sim_N = 0, sim_route_n = 0;
+    // vector environment on the simulator (stmpc_env_*)
+    DevBuf env_ep, env_prev_a, env_pjerk, env_inv, env_ret, env_cmd, env_live, env_vx, env_vv, env_va, env_k, env_log, env_log_n, env_actions;
+    int env_N = 0, env_n_actions = 0, env_log_cap = 0, env_mode = -1;    // (env_N = 0: no environment; a plain stmpc_sim_init_device invalidates it)
     DevBuf f_seq, f_len, f_v0, f_a0, f_bac, f_out, f_olen, f_iters, f_speed;   // finer_fit / st_control staging
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     stmpc_stats stats{};
@@ -210,7 +214,8 @@ struct stmpc_ctx {
                                                 // in a row and ends the step; over 16 state seeds (1.05, 1.3, 4) has the same median and no 5.4-5.8 ms outliers
     int retire_cus = 0, retire_at = 75;   // STMPC_RETIRE_CUS=k, STMPC_RETIRE_AT=percent of N: k compute units leave the first launch once fewer than that many tasks are left (see SolveArgs::cu_tab)
     DevBuf cu_tab;
-    DevBuf sticky;                 // [2] error flags that outlive a call: [0] solver internal error, [1] QP re-sampling refused a path (read and cleared by stmpc_check_error)
+    DevBuf sticky;                 // [3] error flags that outlive a call: [0] solver internal error, [1] QP re-sampling refused a path, [2] a discrete env action out of range
+                                   // (read and cleared by stmpc_check_error)
     hipStream_t main_masked = nullptr, aux_reserved = nullptr;
     hipEvent_t ev_join0 = nullptr, ev_join_r = nullptr;
 };
@@ -325,7 +330,7 @@ int stmpc_create(stmpc_ctx **out, int device) {
         if (hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess) c->aux_stream = nullptr;
     }
     if (!c->aux_stream) c->overlap = 0;          // no side stream: the tiers simply run one after the other
-    if (c->sticky.ensure(2 * sizeof(unsigned)) || hipMemset(c->sticky.p, 0, 2 * sizeof(unsigned)) != hipSuccess) { stmpc_destroy(c); return fail(STMPC_ENOMEM, "device allocation failed"); }
+    if (c->sticky.ensure(3 * sizeof(unsigned)) || hipMemset(c->sticky.p, 0, 3 * sizeof(unsigned)) != hipSuccess) { stmpc_destroy(c); return fail(STMPC_ENOMEM, "device allocation failed"); }
     if (const char *w = getenv("STMPC_TUBE")) { int v = atoi(w); if (v >= 0 && v <= 4096) c->tube_w = v; }
     if (const char *w = getenv("STMPC_PRIO")) { int v = atoi(w); if (v >= 0) c->prio_thr = v; }
     if (const char *w = getenv("STMPC_PRIO_MODE")) c->prio_mode = atoi(w);
@@ -369,7 +374,8 @@ void stmpc_destroy(stmpc_ctx *c) {
                      &c->ckpt, &c->pool_bp, &c->resume_t, &c->phase_prof, &c->prio_key, &c->cc_live, &c->cc_hist_len, &c->cc_crash_pred, &c->cc_have_test, &c->cc_sel, &c->cc_rollout_s, &c->cc_test_ego,
                      &c->cc_test_ox, &c->cc_test_ov, &c->cc_probe_ego, &c->cc_probe_ox, &c->cc_probe_ov, &c->cc_path, &c->cc_bt, &c->cc_cost, &c->cc_pcrash, &c->cc_speed,
                      &c->cc_fine, &c->cc_fine_len, &c->cc_err, &c->sim_ego, &c->sim_nveh, &c->sim_vx, &c->sim_vv, &c->sim_va, &c->sim_vc, &c->sim_delay, &c->sim_status, &c->sim_ticks,
-                     &c->sim_rng, &c->sim_acc, &c->sim_route, &c->f_seq, &c->f_len, &c->f_v0, &c->f_a0, &c->f_bac, &c->f_out, &c->f_olen, &c->f_iters, &c->f_speed,
+                     &c->sim_rng, &c->sim_acc, &c->sim_route, &c->env_ep, &c->env_prev_a, &c->env_pjerk, &c->env_inv, &c->env_ret, &c->env_cmd, &c->env_live,
+                     &c->env_vx, &c->env_vv, &c->env_va, &c->env_k, &c->env_log, &c->env_log_n, &c->env_actions, &c->f_seq, &c->f_len, &c->f_v0, &c->f_a0, &c->f_bac, &c->f_out, &c->f_olen, &c->f_iters, &c->f_speed,
                      &c->cc_sel_idx, &c->cc_sel_count, &c->cc_c_ego, &c->cc_c_k, &c->cc_c_ox, &c->cc_c_ov, &c->cc_c_speed, &c->cc_c_fine, &c->cc_c_fine_len};
     for (DevBuf *b : all) b->release();
     if (c->cc_host_count) (void)hipHostFree(c->cc_host_count);
@@ -1179,15 +1185,16 @@ int stmpc_check_error(stmpc_ctx *c) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
-    unsigned flags[2] = {0, 0}, cur = 0;
+    unsigned flags[3] = {0, 0, 0}, cur = 0;
     HIPCHK(hipMemcpy(flags, c->sticky.p, sizeof flags, hipMemcpyDeviceToHost));
     if (c->counters.p) HIPCHK(hipMemcpy(&cur, (const unsigned *)c->counters.p + STMPC_CNT_ERR, sizeof cur, hipMemcpyDeviceToHost));
-    if (flags[0] || flags[1] || cur) {
+    if (flags[0] || flags[1] || flags[2] || cur) {
         HIPCHK(hipMemset(c->sticky.p, 0, sizeof flags));
         if (cur) HIPCHK(hipMemset((unsigned *)c->counters.p + STMPC_CNT_ERR, 0, sizeof cur));
     }
     if (flags[0] || cur) return fail(STMPC_EINTERNAL, "solver error flag set on device (an episode of an earlier batch may not have been solved)");
     if (flags[1]) return fail(STMPC_EINVAL, "finer_fit: a fine grid longer than STMPC_QP_NMAX samples is not supported (the commanded speed of that state is not valid)");
+    if (flags[2]) return fail(STMPC_EINVAL, "stmpc_env_step_device: a discrete action index out of range (that environment kept its speed for the tick)");
     return STMPC_OK;
 }
 
@@ -1864,6 +1871,7 @@ int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *str
     if ((rc = c->sim_rng.ensure((size_t)N * 4))) return rc;
     if ((rc = c->sim_acc.ensure((size_t)N * sim::NACC * 8))) return rc;
     c->sim_N = N;
+    c->env_N = 0;                  // (the vector environment's bookkeeping no longer describes this world; stmpc_env_reset_device sets it again)
     c->sim_route_n = 0;
     if (g->ego_route_xy && g->ego_route_n >= 2) {
         const int n = g->ego_route_n;
@@ -1930,6 +1938,151 @@ int stmpc_sim_read(stmpc_ctx *c, int N, int32_t *status, int32_t *ticks, double 
     if (ticks) HIPCHK(hipMemcpy(ticks, c->sim_ticks.p, (size_t)N * 4, hipMemcpyDeviceToHost));
     if (acc) HIPCHK(hipMemcpy(acc, c->sim_acc.p, (size_t)N * sim::NACC * 8, hipMemcpyDeviceToHost));
     if (ego4) HIPCHK(hipMemcpy(ego4, c->sim_ego.p, (size_t)N * 32, hipMemcpyDeviceToHost));
+    return STMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- vector environment on the simulator (stmpc_env_*): the reference's gym environments, merge_gym.py ----
+namespace {
+int make_envcfg(const stmpc_env_cfg *g, env::ECfg *c) {
+    if (!g) return fail(STMPC_EINVAL, "env cfg is NULL");
+    if (!g->features) return fail(STMPC_EINVAL, "env cfg: features is NULL");
+    const stmpc_policy_features_cfg *f = g->features;
+    if (f->time_feature) return fail(STMPC_EINVAL, "env cfg: the observation has no time feature (TimeFeature wraps the agent, not the env)");
+    if (f->cars_ahead < 0 || f->cars_behind < 0 || f->cars_ahead > STMPC_KMAX_LIMIT || f->cars_behind > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "cars_ahead / cars_behind out of range");
+    if (f->normalize && (!(f->max_speed > 0) || !(f->sensor_radius > 0))) return fail(STMPC_EINVAL, "max_speed and sensor_radius must be positive");
+    if (g->action_mode < STMPC_ENV_CONTINUOUS_JERK || g->action_mode > STMPC_ENV_ACCELERATION) return fail(STMPC_EINVAL, "env cfg: unknown action_mode");
+    if (g->reward_function < STMPC_REWARD_CONTINUOUS || g->reward_function > STMPC_REWARD_ST) return fail(STMPC_EINVAL, "env cfg: unknown reward_function");
+    if (!(g->tick_length > 0)) return fail(STMPC_EINVAL, "env cfg: tick_length must be positive");
+    memset(c, 0, sizeof *c);
+    c->tick = g->tick_length; c->crash_r = g->crash_reward; c->success_r = g->success_reward; c->time_r = g->time_reward;
+    c->wt_smooth = g->wt_smooth; c->wt_safe = g->wt_safe; c->wt_eff = g->wt_efficient;
+    c->alt_v = g->alt_v_weight; c->alt_a = g->alt_a_weight; c->alt_j = g->alt_j_weight; c->alt_d = g->alt_d_weight;
+    c->min_follow = g->min_follow_distance; c->desired_speed = g->desired_speed; c->car_length = g->car_length;
+    c->penalty = g->invalid_action_penalty; c->j_min = g->minimum_negative_jerk; c->j_max = g->maximum_positive_jerk;
+    c->a_min = g->max_negative_acceleration; c->a_max = g->max_positive_acceleration; c->v_max = g->max_speed;
+    c->mode = g->action_mode; c->reward = g->reward_function; c->autoreset = g->autoreset != 0;
+    c->f.max_speed = f->max_speed; c->f.sensor_radius = f->sensor_radius; c->f.time_scale = (float)f->time_scale;
+    c->f.cars_ahead = f->cars_ahead; c->f.cars_behind = f->cars_behind; c->f.use_accel = f->use_acceleration != 0; c->f.use_speed_diff = f->use_speed_difference != 0;
+    c->f.normalize = f->normalize != 0; c->f.time_feature = 0;
+    c->obs_len = stmpc_policy_features_len(f);
+    return STMPC_OK;
+}
+env::EState env_state(stmpc_ctx *c) {
+    return env::EState{c->env_ep.as<int>(), c->env_prev_a.as<double>(), c->env_pjerk.as<double>(), c->env_inv.as<double>(), c->env_ret.as<double>(),
+                       c->env_cmd.as<double>(), c->env_live.as<int>(), c->env_vx.as<double>(), c->env_vv.as<double>(), c->env_va.as<double>(), c->env_k.as<int>(),
+                       c->env_log.as<double>(), c->env_log_n.as<unsigned>(), c->sticky.as<unsigned>() + 2};
+}
+}  // namespace
+
+extern "C" {
+
+uint64_t stmpc_env_episode_seed(uint64_t seed, uint32_t episode) { return env::episode_seed(seed, episode); }
+
+int stmpc_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, float *d_obs, int obs_stride, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (!p) return fail(STMPC_EINVAL, "params is NULL");
+    env::ECfg e;
+    int rc = make_envcfg(ec, &e);
+    if (rc) return rc;
+    if (d_obs && obs_stride < e.obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
+    if (ec->action_mode != STMPC_ENV_CONTINUOUS_JERK && (!ec->action_values || ec->n_action_values < 1 || ec->n_action_values > STMPC_ENV_MAX_ACTIONS))
+        return fail(STMPC_EINVAL, "a discrete env needs 1..STMPC_ENV_MAX_ACTIONS action_values");
+    if (ec->log_capacity < 0) return fail(STMPC_EINVAL, "log_capacity must not be negative");
+    if ((rc = stmpc_sim_init_device(c, g, N, stream))) return rc;
+    const size_t n = (size_t)N, KS = sim::KS;
+    if ((rc = c->env_ep.ensure(n * 4)) || (rc = c->env_prev_a.ensure(n * 8)) || (rc = c->env_pjerk.ensure(n * 8)) || (rc = c->env_inv.ensure(n * 8)) ||
+        (rc = c->env_ret.ensure(n * 8)) || (rc = c->env_cmd.ensure(n * 8)) || (rc = c->env_live.ensure(n * 4)) || (rc = c->env_vx.ensure(n * KS * 8)) ||
+        (rc = c->env_vv.ensure(n * KS * 8)) || (rc = c->env_va.ensure(n * KS * 8)) || (rc = c->env_k.ensure(n * 4)) || (rc = c->env_log_n.ensure(4)))
+        return rc;
+    const int cap = ec->log_capacity ? ec->log_capacity : 16 * N;
+    if ((rc = c->env_log.ensure((size_t)cap * env::NLOG * 8))) return rc;
+    c->env_log_cap = cap;
+    c->env_n_actions = 0;
+    if (ec->action_mode != STMPC_ENV_CONTINUOUS_JERK) {
+        if ((rc = c->env_actions.ensure((size_t)ec->n_action_values * 8))) return rc;
+        HIPCHK(hipMemcpyAsync(c->env_actions.p, ec->action_values, (size_t)ec->n_action_values * 8, hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));       // (the table is the caller's host memory)
+        c->env_n_actions = ec->n_action_values;
+    }
+    HIPCHK(hipMemsetAsync(c->env_log_n.p, 0, 4, (hipStream_t)stream));
+    c->env_N = N;
+    c->env_mode = ec->action_mode;
+    sim::Cfg sc;
+    if ((rc = make_simcfg(g, &sc))) return rc;
+    sim_route_of(c, &sc);
+    e.seed = sc.seed; e.log_cap = cap; e.n_actions = c->env_n_actions; e.actions = c->env_actions.as<double>();
+    hipLaunchKernelGGL(env::k_env_reset, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, sc, N, sim_state(c), env_state(c), d_obs, obs_stride);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
+                          double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (N != c->env_N || N != c->sim_N || N < 1) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device");
+    if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    env::ECfg e;
+    sim::Cfg sc;
+    DevP dp;
+    int rc = make_envcfg(ec, &e);
+    if (rc) return rc;
+    if (obs_stride < e.obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
+    if (e.mode != c->env_mode) return fail(STMPC_EINVAL, "env_cfg.action_mode differs from the one the context was reset with (stmpc_env_reset_device)");
+    if ((rc = make_simcfg(g, &sc))) return rc;
+    sim_route_of(c, &sc);
+    if ((rc = make_devp(p, &dp))) return rc;
+    e.seed = sc.seed; e.log_cap = c->env_log_cap; e.n_actions = c->env_n_actions; e.actions = c->env_actions.as<double>();
+    HIPCHK(hipSetDevice(c->device));
+    const dim3 grid((N + 63) / 64), block(64);
+    const sim::State s = sim_state(c);
+    const env::EState es = env_state(c);
+    hipLaunchKernelGGL(env::k_env_act, grid, block, 0, (hipStream_t)stream, e, N, s, es, d_action);
+    hipLaunchKernelGGL(sim::k_sim_step, grid, block, 0, (hipStream_t)stream, dp, sc, N, s, (const double *)es.cmd, p->crash_min_s);
+    hipLaunchKernelGGL(env::k_env_post, grid, block, 0, (hipStream_t)stream, e, sc, N, s, es, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_env_reward_device(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, int Kmax, const double *d_ego4, const int32_t *d_k, const double *d_ox, const double *d_ov,
+                            const double *d_oa, const double *d_jerk, const int32_t *d_crashed, const int32_t *d_arrived, double *d_reward, void *stream) {
+    (void)d_ov; (void)d_oa;        // (no reward function reads the other vehicles' speeds or accelerations)
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    env::ECfg e;
+    int rc = make_envcfg(ec, &e);
+    if (rc) return rc;
+    if (N < 0 || Kmax < 0 || Kmax > sim::KS) return fail(STMPC_EINVAL, "N or Kmax out of range (Kmax <= 64)");
+    if (N == 0) return STMPC_OK;
+    if (!d_ego4 || !d_k || !d_jerk || !d_reward || (Kmax > 0 && !d_ox)) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(env::k_env_reward, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed, d_arrived, d_reward);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_env_drain(stmpc_ctx *c, int max_rows, double *rows, int64_t *n_rows, int64_t *n_dropped) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (!n_rows || (max_rows > 0 && !rows)) return fail(STMPC_EINVAL, "NULL host pointer");
+    if (c->env_N < 1) return fail(STMPC_EINVAL, "no environment in this context (stmpc_env_reset_device)");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned cnt = 0;
+    HIPCHK(hipMemcpy(&cnt, c->env_log_n.p, 4, hipMemcpyDeviceToHost));
+    const int64_t kept = cnt < (unsigned)c->env_log_cap ? (int64_t)cnt : (int64_t)c->env_log_cap;
+    const int64_t take = kept < (int64_t)(max_rows > 0 ? max_rows : 0) ? kept : (int64_t)(max_rows > 0 ? max_rows : 0);
+    if (take) HIPCHK(hipMemcpy(rows, c->env_log.p, (size_t)take * env::NLOG * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(c->env_log_n.p, 0, 4));
+    *n_rows = take;
+    if (n_dropped) *n_dropped = (int64_t)cnt - take;
+    return STMPC_OK;
+}
+
+int stmpc_env_episode_ticks_device(stmpc_ctx *c, int N, int32_t *d_ticks, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (N != c->env_N || N < 1 || !d_ticks) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device, or NULL pointer");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(d_ticks, c->sim_ticks.p, (size_t)N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return STMPC_OK;
 }
 

@@ -329,9 +329,10 @@ __device__ __forceinline__ double krauss_follow(const Cfg &c, double gap, double
 // end at x = 1.5, and the ego's lane differs in x extent from its length by 0.2 %: the x coordinate itself, which is also what the planner
 // compares with the vehicles' (prediction.py:78)
 __device__ __forceinline__ double ego_lane_pos(double x, double /*y*/) { return x; }
-__global__ void __launch_bounds__(64) k_sim_init(Cfg c, int N, State s) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
+// Environment e of k_sim_init with `seed` in place of c.seed (the per-environment reset of stmpc_env_step_device starts episode j from here).
+__device__ __forceinline__ void sim_init_env(const Cfg &c_, const State &s, int e, unsigned long long seed) {
+    Cfg c = c_;
+    c.seed = seed;
     unsigned ctr = 0;
     // highway traffic in its stationary state (what the reference gets from its warm-up ticks, control.py:255-258): every vehicle at its desired
     // speed, spaced by the insertion intervals; an insertion that is not yet safe is postponed, as SUMO does
@@ -357,6 +358,11 @@ __global__ void __launch_bounds__(64) k_sim_init(Cfg c, int N, State s) {
     s.status[e] = 0; s.ticks[e] = 0; s.rng[e] = ctr;
     for (int q = 0; q < NACC; ++q) s.acc[(size_t)e * NACC + q] = 0.0;
     s.acc[(size_t)e * NACC + 5] = 1e300;
+}
+__global__ void __launch_bounds__(64) k_sim_init(Cfg c, int N, State s) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    sim_init_env(c, s, e, c.seed);
 }
 // The planner's view of each environment (HighwayState.from_sumo, prediction.py:112-142): the vehicles within the sensor radius of the ego (plane
 // distance; the highway lane runs at y = -1.6), front to back, and the ego with its s coordinate.

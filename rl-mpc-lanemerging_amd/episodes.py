@@ -112,23 +112,31 @@ class EpisodeRunner:
     def result(self):
         status, ticks, acc, ego4 = self.ctx.sim_read(self.n)
         self.ctx.check_error()
-        samples = np.maximum(acc[:, 4], 1.0)
-        # mean |jerk| as the reference reports it: its jerk history holds a 0 for the first tick (control.py:284-287) and the mean is taken
-        # over all ticks (stats.py:60) -- n samples, not n - 1 jerk terms
-        out = {"crashed": (status == 2).astype(np.float64), "merged": (status == 1).astype(np.float64), "timed_out": (status == 3).astype(np.float64),
-               "mean_speed": acc[:, 0] / samples, "max_speed": acc[:, 1], "mean_abs_jerk": acc[:, 2] / samples,
-               "closest_distance": np.where(acc[:, 7] > 0, acc[:, 5], np.nan), "mean_closest_distance": np.where(acc[:, 7] > 0, acc[:, 6] / np.maximum(acc[:, 7], 1.0), np.nan),
-               "time_taken": ticks * self.tick_length, "ticks": ticks, "status": status, "ego4": ego4}
-        out["time_to_merge"] = np.where(status == 1, out["time_taken"], np.nan)
-        # the reference's "disruption" columns (stats.py:64-68): deceleration of the nearest vehicle behind the ego, per controlled tick past MERGE_POINT_X
-        have = acc[:, 10] > 0
-        out["mean_disruption"] = np.where(have, acc[:, 8] / np.maximum(acc[:, 10], 1.0), np.nan)
-        out["max_disruption"] = np.where(have, acc[:, 9], np.nan)
-        out["total_disruption"] = np.where(have, acc[:, 8] * self.tick_length, np.nan)
-        out["disruption_time"] = np.where(have, acc[:, 11] * self.tick_length, np.nan)
+        out = stats_columns(status, ticks, acc, self.tick_length)
+        out["ego4"] = ego4
         if self.controller == "combined":
             out["percent_st"] = (self.takeovers / self.torch.clamp(self.controlled, min=1.0)).cpu().numpy()
         return out
+
+
+def stats_columns(status, ticks, acc, tick_length):
+    """The per-episode columns of the reference's stats report from the world's statistics (``stmpc_sim_read``: status, ticks,
+    acc [n][STMPC_SIM_NACC]); used by ``EpisodeRunner.result`` and ``vec_env.MergeVecEnv.drain_episode_stats``."""
+    samples = np.maximum(acc[:, 4], 1.0)
+    # mean |jerk| as the reference reports it: its jerk history holds a 0 for the first tick (control.py:284-287) and the mean is taken
+    # over all ticks (stats.py:60) -- n samples, not n - 1 jerk terms
+    out = {"crashed": (status == 2).astype(np.float64), "merged": (status == 1).astype(np.float64), "timed_out": (status == 3).astype(np.float64),
+           "mean_speed": acc[:, 0] / samples, "max_speed": acc[:, 1], "mean_abs_jerk": acc[:, 2] / samples,
+           "closest_distance": np.where(acc[:, 7] > 0, acc[:, 5], np.nan), "mean_closest_distance": np.where(acc[:, 7] > 0, acc[:, 6] / np.maximum(acc[:, 7], 1.0), np.nan),
+           "time_taken": ticks * tick_length, "ticks": ticks, "status": status}
+    out["time_to_merge"] = np.where(status == 1, out["time_taken"], np.nan)
+    # the reference's "disruption" columns (stats.py:64-68): deceleration of the nearest vehicle behind the ego, per controlled tick past MERGE_POINT_X
+    have = acc[:, 10] > 0
+    out["mean_disruption"] = np.where(have, acc[:, 8] / np.maximum(acc[:, 10], 1.0), np.nan)
+    out["max_disruption"] = np.where(have, acc[:, 9], np.nan)
+    out["total_disruption"] = np.where(have, acc[:, 8] * tick_length, np.nan)
+    out["disruption_time"] = np.where(have, acc[:, 11] * tick_length, np.nan)
+    return out
 
 
 def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, check_every=16, max_ticks=None):

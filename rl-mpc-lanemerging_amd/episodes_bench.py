@@ -8,6 +8,8 @@ train_moderate_1.json's traffic (BASE_TRAFFIC_INTERVAL 1.2 s, OTHER_CAR_SPEED 11
 combined RL + MPC controller (policy rollout, feasibility probe solve, controller solve + QP re-sampling, decision,
 ``combined.decide_batch_device``) with the reference's pretrained actor for that traffic (``runs/ddpg_moderate1_extended``, ``actor.DDPGActor``) in place of a learner.  A step = one simulator tick of
 every environment; the value is environment steps per second.
+The environment side a learner trains on is ``vec_env.MergeVecEnv`` (the reference's gym environments with their rewards on this world;
+``scripts/env_bench.py`` measures its env-steps/s); this workload keeps measuring the controller-driven episodes.
 """
 import time
 

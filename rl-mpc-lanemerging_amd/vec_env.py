@@ -1,0 +1,179 @@
+"""Batched on-device RL training environment for the merge world: the reference's gym environments (merge_gym.py: ``sumo-jerk-continuous-v0``
+= ContinuousJerkEnv, ``sumo-jerk-v0`` = JerkEnv, ``sumo-accel-v0`` = AccelerationEnv) with the rewards of ``dqn.get_reward_function``
+(dqn.py:449-563, rl.py:168-174), for ``n`` environments of the SUMO-free world (episodes.py) stepped in lock-step on one GPU.
+
+``MergeVecEnv`` follows the call shape of a gym / gymnasium vector env (neither is imported): ``reset() -> obs``,
+``step(action) -> obs, reward, terminated, truncated, info``, all torch device tensors; ``step`` never synchronises with the host.
+Finished environments start their next episode in the same step (``autoreset``); ``info["final_observation"]`` / ``info["final_stats"]``
+hold what the finished episode returned in the rows where ``terminated | truncated``.  ``drain_episode_stats()`` is the one sync point.
+
+Differences from the reference, by design: the reset state is the world's start state (the traffic in its stationary state, the ego at the
+ramp's start), not the reference's 20 s warm-up plus one tick (merge_gym.py:142-150) -- as ``episodes.EpisodeRunner`` starts; the observation
+has no TimeFeature input (that wraps the agent, not the env: ddpg.py:41); the world is a restatement, not SUMO, so
+whole-episode outcomes are not the reference's, while rewards, actions and observations are pinned to it.
+"""
+import weakref
+
+import numpy as np
+
+from . import _capi, episodes
+from .config import Settings
+
+ENV_IDS = {"sumo-jerk-continuous-v0": _capi.ENV_CONTINUOUS_JERK, "sumo-jerk-v0": _capi.ENV_JERK, "sumo-accel-v0": _capi.ENV_ACCELERATION}
+REWARD_IDS = {"Continuous": _capi.REWARD_CONTINUOUS, "Slotted": _capi.REWARD_SLOTTED, "Slotted Jerk": _capi.REWARD_SLOTTED_JERK, "ST": _capi.REWARD_ST}
+_M64 = 0xFFFFFFFFFFFFFFFF
+_owners = weakref.WeakKeyDictionary()       # context -> the MergeVecEnv whose world it holds (a context holds one world)
+
+
+def episode_seed(seed, episode):
+    """Seed of episode ``episode`` of an environment in a run seeded ``seed`` (``stmpc_env_episode_seed``; 0: the seed itself)."""
+    if episode == 0:
+        return int(seed) & _M64
+    z = (int(seed) + 0x9E3779B97F4A7C15 * int(episode)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def env_cfg(env_id=None, reward=None, autoreset=True, S=Settings, log_capacity=0):
+    """``stmpc_env_cfg`` for ``env_id`` / ``reward`` (default: Settings.GYM_ENVIRONMENT / Settings.REWARD_FUNCTION); ValueError for unknown names."""
+    env_id = S.GYM_ENVIRONMENT if env_id is None else env_id
+    reward = S.REWARD_FUNCTION if reward is None else reward
+    if env_id not in ENV_IDS:
+        raise ValueError("Invalid gym environment {} (one of {})".format(env_id, ", ".join(ENV_IDS)))
+    if reward not in REWARD_IDS:
+        raise ValueError("Invalid reward function {} specified in settings.".format(reward))        # dqn.get_reward_function, dqn.py:460
+    table = None
+    if env_id == "sumo-jerk-v0":
+        table = [S.JERK_VALUES_DQN[i] for i in range(len(S.JERK_VALUES_DQN))]
+    elif env_id == "sumo-accel-v0":
+        table = [S.ACCELERATION_VALUES_DQN[i] for i in range(len(S.ACCELERATION_VALUES_DQN))]
+    return _capi.EnvCfg.from_settings(S, ENV_IDS[env_id], REWARD_IDS[reward], table, autoreset, log_capacity)
+
+
+def observation_bounds(S=Settings):
+    """(low, high) of JerkEnv's observation space, merge_gym.py:41-79."""
+    n_cars = S.CARS_AHEAD + S.CARS_BEHIND
+    dim = (4 if S.USE_ACCELERATION_OF_OTHER_CARS else 3) * n_cars + 4
+    lows, highs = np.zeros(dim), np.zeros(dim)
+    if S.NORMALIZE_VECTOR_INPUT:
+        lows -= 1
+        highs += 1
+    else:
+        for i in range(n_cars):
+            if S.USE_ACCELERATION_OF_OTHER_CARS:
+                lows[4 * i:4 * i + 4] = (-9, -S.MAX_SPEED, -300, 0)
+                highs[4 * i:4 * i + 4] = (6, S.MAX_SPEED + 1E-5, 300, 1)
+            else:
+                lows[3 * i:3 * i + 3] = (-S.MAX_SPEED, -300, 0)
+                highs[3 * i:3 * i + 3] = (S.MAX_SPEED + 1E-5, 300, 1)
+        lows[-4:] = (0, S.MAX_NEGATIVE_ACCELERATION - 1E-5, -250, -10)
+        highs[-4:] = (S.MAX_SPEED + 1E-5, S.MAX_POSITIVE_ACCELERATION + 1E-5, 250, 100)
+    return lows, highs
+
+
+class MergeVecEnv:
+    """``n`` merge environments on the device.  ``env_id``: "sumo-jerk-continuous-v0" (actions: fp64 jerks [n], not clipped to the Box, as the
+    reference does not clip them), "sumo-jerk-v0" or "sumo-accel-v0" (actions: int indices [n]); ``reward``: "Continuous", "Slotted",
+    "Slotted Jerk" or "ST".  Settings are read at construction (Settings.MAX_EPISODE_LENGTH, the traffic, the reward weights, ...).
+    ``ctx``: the ``_capi.Context`` that holds the world (default: a context of its own).  A context holds one world: a second env reset on it,
+    or an ``EpisodeRunner`` started on it, ends this one -- its next ``step`` raises instead of stepping the other's world.
+    Kernels run on the current torch stream of the call."""
+
+    def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0):
+        import torch
+        self.torch = torch
+        self.env_id = Settings.GYM_ENVIRONMENT if env_id is None else env_id
+        self.reward_name = Settings.REWARD_FUNCTION if reward is None else reward
+        self.cfg = env_cfg(self.env_id, self.reward_name, autoreset, Settings, log_capacity)         # (raises ValueError first)
+        self.n, self.seed, self.autoreset = int(n), int(seed), bool(autoreset)
+        if self.n < 1:
+            raise ValueError("n must be positive")
+        self.ctx = ctx if ctx is not None else _capi.Context(-1)
+        self.params = _capi.Params.from_settings(Settings)
+        self.sim_cfg = episodes.sim_cfg(seed, float(Settings.MAX_EPISODE_LENGTH))
+        self.log_capacity = int(log_capacity) if log_capacity else 16 * self.n
+        self.obs_dim = (4 if Settings.USE_ACCELERATION_OF_OTHER_CARS else 3) * (Settings.CARS_AHEAD + Settings.CARS_BEHIND) + 4
+        self.observation_low, self.observation_high = observation_bounds(Settings)
+        self.continuous = self.env_id == "sumo-jerk-continuous-v0"
+        if self.continuous:             # spaces.Box(MINIMUM_NEGATIVE_JERK, MAXIMUM_POSITIVE_JERK, shape=(1,)), merge_gym.py:222-224
+            self.action_space = {"type": "Box", "low": float(Settings.MINIMUM_NEGATIVE_JERK), "high": float(Settings.MAXIMUM_POSITIVE_JERK), "shape": (1,)}
+        else:                           # spaces.Discrete(len(...)), merge_gym.py:80,190
+            self.action_space = {"type": "Discrete", "n": int(self.cfg.n_action_values)}
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
+        self._obs = [z(self.n, self.obs_dim, dtype=torch.float32) for _ in range(2)]      # double-buffered: a learner may keep the previous step's tensor
+        self._final_obs = z(self.n, self.obs_dim, dtype=torch.float32)
+        self._reward, self._final_stats = z(self.n), z(self.n, _capi.ENV_NSTAT)
+        self._term, self._trunc = z(self.n, dtype=torch.bool), z(self.n, dtype=torch.bool)
+        self._cur = 0
+        self._ticks = z(self.n, dtype=torch.int32)
+        self._reset_done = False
+
+    def reset(self):
+        """Every environment back to episode 0 (``stmpc_env_reset_device``): the observations of the start states [n][obs_dim] float32."""
+        self._cur = 0
+        obs = self._obs[0]
+        self.ctx.env_reset(self.params, self.sim_cfg, self.cfg, self.n, obs.data_ptr(), self.obs_dim, self._stream())
+        _owners[self.ctx] = self
+        self._reset_done = True
+        return obs
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    @property
+    def episode_ticks(self):
+        """Ticks of each environment's current episode, int32 [n] on the device (0 right after a reset; e.g. a TimeFeature input: 0.001 x this).
+        One device-to-device copy of the world's counter on the current stream; the tensor is overwritten by the next read."""
+        self.ctx.env_episode_ticks(self.n, self._ticks.data_ptr(), self._stream())
+        return self._ticks
+
+    def _action_tensor(self, action):
+        torch = self.torch
+        want = torch.float64 if self.continuous else torch.int32
+        a = torch.as_tensor(action, device=self.device)
+        if a.dtype != want:
+            a = a.to(want)
+        a = a.reshape(self.n)
+        return a if a.is_contiguous() else a.contiguous()
+
+    def step(self, action):
+        """One tick of every environment; no host synchronisation.  Returns (obs, reward, terminated, truncated, info) as device tensors;
+        info: final_observation [n][obs_dim], final_stats [n][15] (world statistics as episodes.EpisodeRunner reads them, status, ticks, return),
+        episode_return [n] (= final_stats[:, 14]) and status [n] (= final_stats[:, 12]) -- valid where terminated | truncated."""
+        if not self._reset_done:
+            raise RuntimeError("call reset() before step()")
+        if _owners.get(self.ctx) is not self:
+            raise RuntimeError("another MergeVecEnv was reset on this env's context since its own reset(): a context holds one world")
+        a = self._action_tensor(action)
+        self._cur ^= 1
+        obs = self._obs[self._cur]
+        self.ctx.env_step(self.params, self.sim_cfg, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
+                          self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(), self._stream())
+        self._last_action = a                                # (kept alive until the kernels have read it)
+        info = {"final_observation": self._final_obs, "final_stats": self._final_stats, "episode_return": self._final_stats[:, _capi.ENV_NSTAT - 1],
+                "status": self._final_stats[:, _capi.SIM_NACC]}
+        return obs, self._reward, self._term, self._trunc, info
+
+    def check_error(self):
+        """Raise what the kernels flagged (an action index out of range); synchronises."""
+        self.ctx.check_error()
+
+    def drain_episode_stats(self):
+        """The episodes finished since the last drain (or reset), as the columns of ``episodes.EpisodeRunner.result()`` plus ``env``,
+        ``episode`` and ``episode_return``, ordered by (env, episode).  Synchronises; raises if device-side errors were flagged, and
+        RuntimeError if more episodes finished than the log holds (``log_capacity``, default 16 n: drain more often)."""
+        rows, dropped = self.ctx.env_drain(self.log_capacity)
+        self.ctx.check_error()
+        if dropped:
+            raise RuntimeError("%d finished episodes were dropped: drain_episode_stats() more often or raise log_capacity" % dropped)
+        order = np.lexsort((rows[:, _capi.ENV_NSTAT + 1], rows[:, _capi.ENV_NSTAT]))
+        rows = rows[order]
+        out = episodes.stats_columns(rows[:, _capi.SIM_NACC].astype(np.int32), rows[:, _capi.SIM_NACC + 1].astype(np.int32), rows[:, :_capi.SIM_NACC],
+                                     Settings.TICK_LENGTH)
+        out["episode_return"] = rows[:, _capi.ENV_NSTAT - 1]
+        out["env"] = rows[:, _capi.ENV_NSTAT].astype(np.int64)
+        out["episode"] = rows[:, _capi.ENV_NSTAT + 1].astype(np.int64)
+        return out
