@@ -74,8 +74,8 @@
 extern "C" {
 #endif
 
-#define STMPC_ABI_VERSION 7   /* bumped whenever an exported signature, a struct layout or the accepted values of a field change (6: stmpc_sim_cfg.yield_overlap must be 2;
-                                 7: the vector environment stmpc_env_*); see stmpc_abi_version() */
+#define STMPC_ABI_VERSION 8   /* bumped whenever an exported signature, a struct layout or the accepted values of a field change (6: stmpc_sim_cfg.yield_overlap must be 2;
+                                 7: the vector environment stmpc_env_*; 8: the DDPG learner stmpc_ddpg_*); see stmpc_abi_version() */
 
 #define STMPC_OK        0
 #define STMPC_EINVAL   -1   /* bad argument (NULL, size, Kmax/H/S out of range) */
@@ -527,6 +527,85 @@ int stmpc_env_reward_device(stmpc_ctx *ctx, const stmpc_env_cfg *env_cfg, int N,
 int stmpc_env_drain(stmpc_ctx *ctx, int max_rows, double *rows, int64_t *n_rows, int64_t *n_dropped);
 int stmpc_env_episode_ticks_device(stmpc_ctx *ctx, int N, int32_t *d_ticks, void *stream);
 uint64_t stmpc_env_episode_seed(uint64_t seed, uint32_t episode);
+
+/*
+ * DDPG learner on the device, next to the vector environment: the reference's TRAIN_DDPG (ddpg.py:44-80: the `all` library's ddpg preset), restated --
+ * the library is absent from the reference checkout, so parity with it is unpinned; the network shapes are those of the reference's checkpoints:
+ * actor (n_obs + 1) -> h1 -> ReLU -> h2 -> ReLU -> 1 -> tanh * tanh_scale + tanh_mean, critic (n_obs + 2) -> h1 -> ReLU -> h2 -> ReLU -> 1, float32.
+ * Input n_obs of both is the time feature time_scale * ticks; the critic's last input is the action.  Per update, on a minibatch of `batch` replay rows
+ * (s, a, r, s', mask) drawn uniformly with replacement from the filled part of the ring:
+ *   y = r + gamma * mask * Q_target(s', pi_target(s'));  critic: Adam step on mean((Q(s, a) - y)^2);  actor: Adam step on -mean(Q(s, pi(s))) with the
+ *   critic after its step;  both targets: theta_target <- (1 - tau) theta_target + tau theta.
+ * Every entry with a `stream` is asynchronous and never synchronises with the host: cursors, counters and Adam's state live on the device, and the
+ * launch sequence depends on (batch, N, shapes) alone, so act -> stmpc_env_step_device -> push -> updates may be captured as one single-stream graph.
+ *   create          seeded parameters are the caller's business: all parameters start at zero until set_params
+ *   set / get_params  HOST float32, one slot at a time: STMPC_DDPG_ACTOR, _ACTOR_TARGET, _ACTOR_M, _ACTOR_V (Adam's moments), STMPC_DDPG_CRITIC, ...;
+ *                   a slot is the net's tensors one after the other, row-major as torch stores them: W0 [h1][n_in] | b0 [h1] | W1 [h2][h1] | b1 [h2] |
+ *                   W2 [h2] | b2 [1], n_in = n_obs + 1 (actor) or n_obs + 2 (critic); `count` must be that length.  Synchronise.
+ *   set / get_state   HOST: counters int64 [STMPC_DDPG_NCOUNTERS] (ring cursor, fill, updates done, noisy acting calls, frames pushed, 0, 0, 0) and Adam's
+ *                   running beta powers float32 [4] (actor beta1^t, beta2^t, critic beta1^t, beta2^t).  With the eight slots: a checkpoint (the replay
+ *                   ring's contents are not part of it).  Synchronise.
+ *   push_device     one environment step into the ring (N <= capacity rows at the cursor, which wraps): d_obs / d_next_obs / d_final_obs [N][obs_stride]
+ *                   float32, d_ticks / d_next_ticks [N] int32 (the ticks the observation was made at), d_action / d_reward [N] fp64, d_terminated /
+ *                   d_truncated [N] uint8.  Where an episode ended, s' is the d_final_obs row (if given) at ticks + 1; elsewhere d_next_obs at d_next_ticks
+ *                   (NULL: ticks + 1).  mask = 0 where terminated, 1 otherwise (a truncation bootstraps).  Rows are stored as float32 [STMPC_DDPG_ROW]:
+ *                   [0, 32) s, time feature, action, zeros; [32, 64) s', time feature, zeros; [64] reward; [65] mask
+ *   act_device      d_action [N] fp64 = clip(pi(obs, time feature) + noise_std * gauss, action_low, action_high); noise = 0: the greedy action.  gauss is
+ *                   Box-Muller on two 24-bit draws of the hash stmpc_ddpg_noise restates, keyed by (seed, noisy acting calls so far, row); d_debug (may be
+ *                   NULL) uint32 [N][4]: the two draws, the bits of the float32 gauss, the bits of the float32 greedy action
+ *   update_device   n_updates updates with the critic's / the actor's learning rate lr_q / lr_pi; does nothing (on the device) until more than
+ *                   replay_start frames have been pushed.  Minibatch row r of update u is ring row stmpc_ddpg_sample_index of (seed, u, r, fill)
+ *   grads_device    debug: the gradients of both losses on the minibatch of the current update index into d_grad_actor / d_grad_critic (DEVICE float32,
+ *                   slot layout), nothing applied, no replay_start gate; both against the current, un-stepped critic
+ *   stats_device    d_out DEVICE fp64 [4]: critic loss and mean Q(s, a) of the last minibatch, fill, updates done
+ *   replay_read     debug, HOST: `count` ring rows from row `first` ([count][STMPC_DDPG_ROW]); synchronises.  gather_device: the minibatch of the current
+ *                   update index, DEVICE [batch][STMPC_DDPG_ROW]
+ *   sample_index, noise   host only, no learner: the generator.  noise returns the standard normal in fp64 and the two draws
+ */
+#define STMPC_DDPG_ROW 68
+#define STMPC_DDPG_NCOUNTERS 8
+#define STMPC_DDPG_ACTOR 0
+#define STMPC_DDPG_ACTOR_TARGET 1
+#define STMPC_DDPG_ACTOR_M 2
+#define STMPC_DDPG_ACTOR_V 3
+#define STMPC_DDPG_CRITIC 4
+#define STMPC_DDPG_CRITIC_TARGET 5
+#define STMPC_DDPG_CRITIC_M 6
+#define STMPC_DDPG_CRITIC_V 7
+typedef struct stmpc_ddpg_cfg {
+    int32_t n_obs;                   /* observation entries (20 for the shipped settings; <= 30) */
+    int32_t h1, h2;                  /* hidden widths (400, 300; <= 1024) */
+    int32_t batch;                   /* minibatch rows B, 16 ... 8192 (100) */
+    int32_t capacity;                /* replay rows */
+    int32_t reserved0;
+    int64_t replay_start;            /* updates start once MORE than this many frames were pushed (5000); < capacity */
+    uint64_t seed;                   /* of the minibatch indices and the exploration noise */
+    double gamma, tau;               /* 0.99, 0.005 */
+    double beta1, beta2, eps;        /* Adam: 0.9, 0.999, 1e-8 */
+    double time_scale;               /* time feature = time_scale * ticks (0.001) */
+    double tanh_scale, tanh_mean;    /* the actor's squash: half the action Box's width, its centre */
+    double noise_std;                /* exploration noise (0.1 * tanh_scale) */
+    double action_low, action_high;  /* the action Box */
+} stmpc_ddpg_cfg;
+typedef struct stmpc_ddpg stmpc_ddpg;
+int  stmpc_ddpg_create(stmpc_ctx *ctx, const stmpc_ddpg_cfg *cfg, stmpc_ddpg **out);
+void stmpc_ddpg_destroy(stmpc_ddpg *learner);
+int  stmpc_ddpg_set_params(stmpc_ddpg *learner, int slot, const float *values, int64_t count);
+int  stmpc_ddpg_get_params(stmpc_ddpg *learner, int slot, float *values, int64_t count);
+int  stmpc_ddpg_set_state(stmpc_ddpg *learner, const int64_t *counters, const float *beta_pow);
+int  stmpc_ddpg_get_state(stmpc_ddpg *learner, int64_t *counters, float *beta_pow);
+int  stmpc_ddpg_push_device(stmpc_ddpg *learner, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                            const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward,
+                            const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream);
+int  stmpc_ddpg_act_device(stmpc_ddpg *learner, int N, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action,
+                           uint32_t *d_debug, void *stream);
+int  stmpc_ddpg_update_device(stmpc_ddpg *learner, int n_updates, double lr_q, double lr_pi, void *stream);
+int  stmpc_ddpg_grads_device(stmpc_ddpg *learner, float *d_grad_actor, float *d_grad_critic, void *stream);
+int  stmpc_ddpg_stats_device(stmpc_ddpg *learner, double *d_out, void *stream);
+int  stmpc_ddpg_replay_read(stmpc_ddpg *learner, int64_t first, int64_t count, float *rows);
+int  stmpc_ddpg_gather_device(stmpc_ddpg *learner, float *d_rows, void *stream);
+uint64_t stmpc_ddpg_sample_index(uint64_t seed, uint64_t update, uint32_t row, uint64_t fill);
+double stmpc_ddpg_noise(uint64_t seed, uint64_t call, uint32_t row, uint32_t *draw1, uint32_t *draw2);
 
 /* Device arithmetic probe used by the parity tests: out[i] = a[i] op b[i] evaluated on the GPU
  * with the kernels' compile flags. op: 0 div, 1 sqrt(a), 2 mul, 3 add, 4 fma(a,a,b*b), 5 the five-operation

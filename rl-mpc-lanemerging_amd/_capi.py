@@ -140,6 +140,14 @@ class EnvCfg(C.Structure):
         return c
 
 
+class DDPGCfg(C.Structure):
+    """``stmpc_ddpg_cfg`` (include/stmpc.h): shapes, replay size and the constants of the DDPG update (defaults: the ``all`` preset's)."""
+    _fields_ = [("n_obs", C.c_int32), ("h1", C.c_int32), ("h2", C.c_int32), ("batch", C.c_int32), ("capacity", C.c_int32), ("reserved0", C.c_int32),
+                ("replay_start", C.c_int64), ("seed", C.c_uint64), ("gamma", C.c_double), ("tau", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("time_scale", C.c_double), ("tanh_scale", C.c_double), ("tanh_mean", C.c_double), ("noise_std", C.c_double),
+                ("action_low", C.c_double), ("action_high", C.c_double)]
+
+
 class ProfileTotals(C.Structure):
     _fields_ = [("launches", C.c_int64), ("episodes", C.c_int64), ("solve_ms", C.c_double), ("dp_kernel_ms", C.c_double)]
 
@@ -158,12 +166,17 @@ EXPORTS = (
     "stmpc_actor_create", "stmpc_actor_destroy", "stmpc_actor_eval_device",
     "stmpc_env_reset_device", "stmpc_env_step_device", "stmpc_env_reward_device", "stmpc_env_drain", "stmpc_env_episode_seed",
     "stmpc_env_episode_ticks_device",
+    "stmpc_ddpg_create", "stmpc_ddpg_destroy", "stmpc_ddpg_set_params", "stmpc_ddpg_get_params", "stmpc_ddpg_set_state", "stmpc_ddpg_get_state",
+    "stmpc_ddpg_push_device", "stmpc_ddpg_act_device", "stmpc_ddpg_update_device", "stmpc_ddpg_grads_device", "stmpc_ddpg_stats_device",
+    "stmpc_ddpg_replay_read", "stmpc_ddpg_gather_device", "stmpc_ddpg_sample_index", "stmpc_ddpg_noise",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
 ENV_CONTINUOUS_JERK, ENV_JERK, ENV_ACCELERATION = 0, 1, 2                                 # STMPC_ENV_*
 REWARD_CONTINUOUS, REWARD_SLOTTED, REWARD_SLOTTED_JERK, REWARD_ST = 0, 1, 2, 3             # STMPC_REWARD_*
 ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
-ABI_VERSION = 7     # STMPC_ABI_VERSION of include/stmpc.h this binding was written against
+DDPG_ROW, DDPG_NCOUNTERS = 68, 8      # STMPC_DDPG_ROW, STMPC_DDPG_NCOUNTERS
+DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
+ABI_VERSION = 8     # STMPC_ABI_VERSION of include/stmpc.h this binding was written against
 
 QP_NMAX = 64        # STMPC_QP_NMAX
 QP_MAXITERS = 10    # STMPC_QP_MAXITERS (solvers.options['maxiters'], st.py:17)
@@ -254,6 +267,25 @@ def load():
     lib.stmpc_env_episode_seed.argtypes = [C.c_uint64, C.c_uint32]
     lib.stmpc_env_episode_seed.restype = C.c_uint64
     lib.stmpc_st_control_batch_device.argtypes = [vp, pp, C.c_double, C.c_int, C.c_int] + [vp] * 10 + [vp]
+    i64p, u32p = C.POINTER(C.c_int64), C.POINTER(C.c_uint32)
+    lib.stmpc_ddpg_create.argtypes = [vp, C.POINTER(DDPGCfg), C.POINTER(vp)]
+    lib.stmpc_ddpg_destroy.argtypes = [vp]
+    lib.stmpc_ddpg_destroy.restype = None
+    lib.stmpc_ddpg_set_params.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_ddpg_get_params.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_ddpg_set_state.argtypes = [vp, i64p, fp]
+    lib.stmpc_ddpg_get_state.argtypes = [vp, i64p, fp]
+    lib.stmpc_ddpg_push_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 6 + [vp]
+    lib.stmpc_ddpg_act_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    lib.stmpc_ddpg_update_device.argtypes = [vp, C.c_int, C.c_double, C.c_double, vp]
+    lib.stmpc_ddpg_grads_device.argtypes = [vp, vp, vp, vp]
+    lib.stmpc_ddpg_stats_device.argtypes = [vp, vp, vp]
+    lib.stmpc_ddpg_replay_read.argtypes = [vp, C.c_int64, C.c_int64, fp]
+    lib.stmpc_ddpg_gather_device.argtypes = [vp, vp, vp]
+    lib.stmpc_ddpg_sample_index.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64]
+    lib.stmpc_ddpg_sample_index.restype = C.c_uint64
+    lib.stmpc_ddpg_noise.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, u32p, u32p]
+    lib.stmpc_ddpg_noise.restype = C.c_double
     _lib = lib
     return lib
 
@@ -292,6 +324,18 @@ def fastdiv2_check(d):
     zl = C.c_double(0.0)
     ok = load().stmpc_fastdiv2_check(float(d), C.byref(zl))
     return bool(ok), zl.value
+
+
+def ddpg_sample_index(seed, update, row, fill):
+    """``stmpc_ddpg_sample_index``: the ring row minibatch row ``row`` of update ``update`` reads (host only)."""
+    return int(load().stmpc_ddpg_sample_index(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(update)), C.c_uint32(int(row)), C.c_uint64(int(fill))))
+
+
+def ddpg_noise(seed, call, row):
+    """``stmpc_ddpg_noise``: (standard normal in fp64, draw 1, draw 2) of row ``row`` in noisy acting call ``call`` (host only)."""
+    u1, u2 = C.c_uint32(0), C.c_uint32(0)
+    g = load().stmpc_ddpg_noise(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(call)), C.c_uint32(int(row)), C.byref(u1), C.byref(u2))
+    return float(g), int(u1.value), int(u2.value)
 
 
 def env_episode_seed(seed, episode):
@@ -553,6 +597,60 @@ class Context:
     def sim_status_device(self, N, d_status, stream=0):
         """Environment status words into a device int32 array (asynchronous): 0 running, 1 arrived, 2 crashed, 3 out of time."""
         self._chk(self._lib.stmpc_sim_status_device(self._h, int(N), d_status, stream))
+
+    # -- DDPG learner (stmpc_ddpg_*): the handle belongs to this context's device ------------------------
+    def ddpg_create(self, cfg):
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_ddpg_create(self._h, C.byref(cfg), C.byref(h)))
+        return h
+
+    def ddpg_destroy(self, handle):
+        self._lib.stmpc_ddpg_destroy(handle)
+
+    def ddpg_set_params(self, handle, slot, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        self._chk(self._lib.stmpc_ddpg_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+
+    def ddpg_get_params(self, handle, slot, count):
+        flat = np.empty(int(count), dtype=np.float32)
+        self._chk(self._lib.stmpc_ddpg_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        return flat
+
+    def ddpg_set_state(self, handle, counters, beta_pow):
+        cn = np.ascontiguousarray(counters, dtype=np.int64)
+        bp = np.ascontiguousarray(beta_pow, dtype=np.float32)
+        assert cn.size == DDPG_NCOUNTERS and bp.size == 4
+        self._chk(self._lib.stmpc_ddpg_set_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def ddpg_get_state(self, handle):
+        """(counters int64 [8]: cursor, fill, updates, noisy acting calls, frames, ...; Adam's beta powers float32 [4]); synchronises."""
+        cn, bp = np.zeros(DDPG_NCOUNTERS, dtype=np.int64), np.zeros(4, dtype=np.float32)
+        self._chk(self._lib.stmpc_ddpg_get_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
+        return cn, bp
+
+    def ddpg_push(self, handle, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated, stream=0):
+        self._chk(self._lib.stmpc_ddpg_push_device(handle, int(N), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_ticks, d_next_ticks, d_action, d_reward,
+                                                   d_terminated, d_truncated, stream))
+
+    def ddpg_act(self, handle, N, d_obs, obs_stride, d_ticks, noise, d_action, d_debug=0, stream=0):
+        self._chk(self._lib.stmpc_ddpg_act_device(handle, int(N), d_obs, int(obs_stride), d_ticks, int(bool(noise)), d_action, d_debug, stream))
+
+    def ddpg_update(self, handle, n_updates, lr_q, lr_pi, stream=0):
+        self._chk(self._lib.stmpc_ddpg_update_device(handle, int(n_updates), float(lr_q), float(lr_pi), stream))
+
+    def ddpg_grads(self, handle, d_grad_actor, d_grad_critic, stream=0):
+        self._chk(self._lib.stmpc_ddpg_grads_device(handle, d_grad_actor, d_grad_critic, stream))
+
+    def ddpg_stats(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_ddpg_stats_device(handle, d_out, stream))
+
+    def ddpg_replay_read(self, handle, first, count):
+        rows = np.empty((int(count), DDPG_ROW), dtype=np.float32)
+        self._chk(self._lib.stmpc_ddpg_replay_read(handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
+        return rows
+
+    def ddpg_gather(self, handle, d_rows, stream=0):
+        self._chk(self._lib.stmpc_ddpg_gather_device(handle, d_rows, stream))
 
     # -- vector environment (stmpc_env_*) ---------------------------------------------------------------
     def env_reset(self, params, sim_cfg, env_cfg, N, d_obs, obs_stride, stream=0):

@@ -58,6 +58,9 @@ class Settings:
                                14: 2.0, 15: 2.5, 16: 3.0, 17: 3.5, 18: 4.0, 19: 4.5}
     INVALID_ACTION_PENALTY = 0.0
 
+    # Learner (config.py:122; the train configs set it): Adam's learning rate of both DDPG networks (learner.DDPGConfig)
+    LEARNING_RATE = 2e-4
+
     # S-T solver and continuous reward (config.py:94)
     DESIRED_SPEED = 30.0
 

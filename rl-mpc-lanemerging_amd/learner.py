@@ -1,0 +1,365 @@
+"""DDPG learner on the device, next to ``vec_env.MergeVecEnv``: the reference's ``TRAIN_DDPG`` (ddpg.py:44-80: the ``all`` library's ``ddpg``
+preset on ``sumo-jerk-continuous-v0``), whose product is the ``policy.pt`` / ``q.pt`` pairs under ``pretrained_models/``.
+
+``DDPGLearner`` holds a replay ring filled from the env's step tensors, the actor and critic with their targets and Adam state, and runs the
+update as six HIP launches (``csrc/stmpc_ddpg_kernels.hpp``); acting, pushing and updating never synchronise with the host.  ``export_actor``
+writes the ``.npz`` that ``actor.load_weights`` / ``actor.DDPGActor`` / the combined controller read.
+
+The ``all`` library (0.5.3, requirements.txt:10) is absent from the reference checkout: the update below restates its published DDPG with the
+preset's documented constants as defaults (``DDPGConfig``); parity with the library itself is unpinned.  The network shapes are the reference's
+own checkpoints': actor 21 -> 400 -> ReLU -> 300 -> ReLU -> 1 -> tanh * scale + mean, critic 22 -> 400 -> ReLU -> 300 -> ReLU -> 1 (20 observation
+entries, the time feature 0.001 x ticks, the action).
+
+Per update on a minibatch (s, a, r, s', mask), s including the time feature:
+  1. y = r + gamma * mask * Q_target(s', pi_target(s')); mask = 0 where the episode terminated (a truncation keeps 1, s' = final_observation)
+  2. critic: Adam step on mean((Q(s, a) - y)^2)
+  3. actor: Adam step on -mean(Q(s, pi(s))) with the critic after step 2
+  4. theta_target <- (1 - tau) theta_target + tau theta, both nets
+
+Host twins (the suite's yardsticks, in the style of ``rewards.py``): ``update_host`` (torch autograd, float64 or float32), ``adam_host`` (numpy
+float32 in the kernel's operation order), ``sample_indices_host``, ``noise_host``.
+"""
+import math
+
+import numpy as np
+
+from . import _capi, actor as _actor
+from .config import Settings
+
+TENSORS = ("w0", "b0", "w1", "b1", "w2", "b2")
+_M64 = 0xFFFFFFFFFFFFFFFF
+_G = 0x9E3779B97F4A7C15
+NOISE_STREAM = 0x6E6F697365
+TWO_PI_F32 = float(np.float32(6.2831855))
+
+
+class DDPGConfig:
+    """The constants of the update; defaults are the ``all`` ddpg preset's as its documentation gives them (``lr``: Settings.LEARNING_RATE)."""
+
+    def __init__(self, n_obs=20, h1=400, h2=300, batch=100, capacity=1000000, replay_start=5000, gamma=0.99, tau=0.005, lr_q=None, lr_pi=None,
+                 beta1=0.9, beta2=0.999, eps=1e-8, time_scale=0.001, tanh_scale=None, tanh_mean=None, noise=0.1, action_low=None, action_high=None):
+        lo = float(Settings.MINIMUM_NEGATIVE_JERK) if action_low is None else float(action_low)
+        hi = float(Settings.MAXIMUM_POSITIVE_JERK) if action_high is None else float(action_high)
+        self.n_obs, self.h1, self.h2, self.batch, self.capacity, self.replay_start = int(n_obs), int(h1), int(h2), int(batch), int(capacity), int(replay_start)
+        self.gamma, self.tau, self.beta1, self.beta2, self.eps, self.time_scale = float(gamma), float(tau), float(beta1), float(beta2), float(eps), float(time_scale)
+        self.lr_q = float(Settings.LEARNING_RATE if lr_q is None else lr_q)
+        self.lr_pi = float(Settings.LEARNING_RATE if lr_pi is None else lr_pi)
+        self.action_low, self.action_high = lo, hi
+        self.tanh_scale = (hi - lo) / 2 if tanh_scale is None else float(tanh_scale)
+        self.tanh_mean = (hi + lo) / 2 if tanh_mean is None else float(tanh_mean)
+        self.noise_std = float(noise) * self.tanh_scale              # N(0, noise * tanh_scale), clipped to the Box
+
+    def to_c(self, seed):
+        return _capi.DDPGCfg(n_obs=self.n_obs, h1=self.h1, h2=self.h2, batch=self.batch, capacity=self.capacity, replay_start=self.replay_start,
+                             seed=int(seed) & _M64, gamma=self.gamma, tau=self.tau, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
+                             time_scale=self.time_scale, tanh_scale=self.tanh_scale, tanh_mean=self.tanh_mean, noise_std=self.noise_std,
+                             action_low=self.action_low, action_high=self.action_high)
+
+
+# ---- the generator (host twins of dg_hash / stmpc_ddpg_sample_index / stmpc_ddpg_noise) ------------------------------------------------------
+def _mix(z):
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def hash3(seed, a, b):
+    """splitmix64 of (seed, a, b): two rounds of the generator ``vec_env.episode_seed`` uses."""
+    return _mix((_mix((int(seed) + _G * (int(a) + 1)) & _M64) + _G * (int(b) + 1)) & _M64)
+
+
+def sample_indices_host(seed, update, batch, fill):
+    """Ring rows of the ``batch`` minibatch rows of update ``update`` with ``fill`` rows filled: uniform, with replacement (int64 [batch])."""
+    return np.array([hash3(seed, update, r) % int(fill) for r in range(int(batch))], dtype=np.int64)
+
+
+def noise_host(seed, call, n):
+    """Noisy acting call ``call``, rows 0 .. n-1: (draw1, draw2, gauss) -- the two 24-bit draws (uint32) and Box-Muller on them in float64,
+    cos taken at the float32 product 2 pi x draw2 / 2^24 the kernel forms."""
+    u1, u2 = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    for e in range(n):
+        h = hash3((int(seed) & _M64) ^ NOISE_STREAM, call, e)
+        u1[e], u2[e] = h >> 40, (h >> 8) & 0xFFFFFF
+    f1 = (u1.astype(np.float64) + 1.0) * 2.0 ** -24
+    theta = (np.float32(TWO_PI_F32) * (u2.astype(np.float32) * np.float32(2.0 ** -24))).astype(np.float64)
+    return u1, u2, np.sqrt(-2.0 * np.log(f1)) * np.cos(theta)
+
+
+# ---- parameters --------------------------------------------------------------------------------------------------------------------------------
+def flatten(net):
+    """{w0, b0, w1, b1, w2, b2} -> the C-ABI's slot layout (float32)."""
+    return np.concatenate([np.asarray(net[k], dtype=np.float32).reshape(-1) for k in TENSORS])
+
+
+def unflatten(flat, n_in, h1, h2):
+    shapes = ((h1, n_in), (h1,), (h2, h1), (h2,), (1, h2), (1,))
+    out, o = {}, 0
+    for k, sh in zip(TENSORS, shapes):
+        n = int(np.prod(sh))
+        out[k] = np.array(flat[o:o + n]).reshape(sh)
+        o += n
+    assert o == len(flat)
+    return out
+
+
+def init_net(n_in, h1, h2, rng):
+    """torch's nn.Linear initialisation (uniform +-1/sqrt(fan_in) for weight and bias), the last layer zero (the ``all`` library's Linear0)."""
+    u = lambda fan_in, *sh: rng.uniform(-1.0 / math.sqrt(fan_in), 1.0 / math.sqrt(fan_in), size=sh).astype(np.float32)
+    return {"w0": u(n_in, h1, n_in), "b0": u(n_in, h1), "w1": u(h1, h2, h1), "b1": u(h1, h2), "w2": np.zeros((1, h2), np.float32), "b2": np.zeros(1, np.float32)}
+
+
+def zeros_like_net(net):
+    return {k: np.zeros_like(np.asarray(net[k], dtype=np.float32)) for k in TENSORS}
+
+
+def new_params(actor_net, critic_net):
+    """The learner's whole parameter state for given online nets: targets = copies, Adam moments zero, beta powers 1, no updates."""
+    cp = lambda n: {k: np.array(n[k], dtype=np.float32) for k in TENSORS}
+    return {"actor": cp(actor_net), "actor_target": cp(actor_net), "actor_m": zeros_like_net(actor_net), "actor_v": zeros_like_net(actor_net),
+            "critic": cp(critic_net), "critic_target": cp(critic_net), "critic_m": zeros_like_net(critic_net), "critic_v": zeros_like_net(critic_net),
+            "beta_pow": np.ones(4, dtype=np.float32), "updates": 0}
+
+
+def batch_from_rows(rows, n_obs):
+    """Replay rows [B][68] -> the minibatch dict update_host takes (s, s2 include the time feature)."""
+    ns = n_obs + 1
+    return {"s": rows[:, :ns], "a": rows[:, ns], "s2": rows[:, 32:32 + ns], "r": rows[:, 64], "mask": rows[:, 65]}
+
+
+# ---- the update on the host ------------------------------------------------------------------------------------------------------------------
+def _mlp(t, x):
+    import torch
+    h = torch.relu(x @ t["w0"].T + t["b0"])
+    h = torch.relu(h @ t["w1"].T + t["b1"])
+    return (h @ t["w2"].T + t["b2"])[:, 0]
+
+
+def update_host(params, batch, cfg, dtype="float64", lr_q=None, lr_pi=None, grads_only=False):
+    """One update (steps 1-4 of the module text) in torch with autograd, every tensor in ``dtype`` ("float64" or "float32").
+    ``params``: as ``new_params`` / ``DDPGLearner.state_dict()["params"]``; returns the new one (numpy arrays of ``dtype``) and a dict with
+    ``critic_loss``, ``mean_q``, ``grad_critic``, ``grad_actor``.  ``grads_only``: nothing is applied and BOTH gradients are taken against the
+    current critic (``stmpc_ddpg_grads_device``'s mode)."""
+    import torch
+    td = getattr(torch, dtype)
+    T = lambda a: torch.tensor(np.asarray(a), dtype=td)
+    P = {slot: {k: T(params[slot][k]) for k in TENSORS} for slot in _capi.DDPG_SLOTS}
+    s, a, r, s2, mask = (T(batch[k]) for k in ("s", "a", "r", "s2", "mask"))
+    scale, mean = cfg.tanh_scale, cfg.tanh_mean
+    lr = {"critic": cfg.lr_q if lr_q is None else lr_q, "actor": cfg.lr_pi if lr_pi is None else lr_pi}
+    t = int(params["updates"]) + 1
+
+    def adam(name, grads):
+        bc1, bc2 = 1.0 - cfg.beta1 ** t, 1.0 - cfg.beta2 ** t
+        for k in TENSORS:
+            g, m, v = grads[k], P[name + "_m"][k], P[name + "_v"][k]
+            m = cfg.beta1 * m + (1 - cfg.beta1) * g
+            v = cfg.beta2 * v + (1 - cfg.beta2) * g * g
+            P[name + "_m"][k], P[name + "_v"][k] = m, v
+            P[name][k] = P[name][k] - (lr[name] / bc1) * m / (v.sqrt() / math.sqrt(bc2) + cfg.eps)
+            P[name + "_target"][k] = (1 - cfg.tau) * P[name + "_target"][k] + cfg.tau * P[name][k]
+
+    with torch.no_grad():
+        a2 = torch.tanh(_mlp(P["actor_target"], s2)) * scale + mean
+        y = r + cfg.gamma * mask * _mlp(P["critic_target"], torch.cat([s2, a2[:, None]], 1))
+    crit = {k: P["critic"][k].clone().requires_grad_(True) for k in TENSORS}
+    q = _mlp(crit, torch.cat([s, a[:, None]], 1))
+    loss = ((q - y) ** 2).mean()
+    gq = dict(zip(TENSORS, torch.autograd.grad(loss, [crit[k] for k in TENSORS])))
+    if not grads_only:
+        adam("critic", gq)
+    act = {k: P["actor"][k].clone().requires_grad_(True) for k in TENSORS}
+    pa = torch.tanh(_mlp(act, s)) * scale + mean
+    aloss = -_mlp(P["critic"], torch.cat([s, pa[:, None]], 1)).mean()
+    gp = dict(zip(TENSORS, torch.autograd.grad(aloss, [act[k] for k in TENSORS])))
+    if not grads_only:
+        adam("actor", gp)
+    out = {slot: {k: P[slot][k].detach().numpy() for k in TENSORS} for slot in _capi.DDPG_SLOTS}
+    out["beta_pow"] = np.array(params["beta_pow"], dtype=np.float32) * (1 if grads_only else np.array([cfg.beta1, cfg.beta2] * 2, dtype=np.float32))
+    out["updates"] = int(params["updates"]) + (0 if grads_only else 1)
+    info = {"critic_loss": float(loss.detach()), "mean_q": float(q.detach().mean()), "grad_critic": {k: gq[k].numpy() for k in TENSORS},
+            "grad_actor": {k: gp[k].numpy() for k in TENSORS}}
+    return out, info
+
+
+def adam_host(w, g, m, v, wt, beta_pow, lr, cfg):
+    """``k_ddpg_adam`` for one tensor (or one flat slot) in numpy float32, operation for operation: returns (w, m, v, wt, beta_pow) after the step.
+    ``beta_pow``: float32 (beta1^(t-1), beta2^(t-1)), the running products the device keeps."""
+    f = np.float32
+    w, g, m, v, wt = (np.asarray(x, dtype=f) for x in (w, g, m, v, wt))
+    b1, b2, tau, eps = f(cfg.beta1), f(cfg.beta2), f(cfg.tau), f(cfg.eps)
+    omb1, omb2, omtau = f(1) - b1, f(1) - b2, f(1) - tau
+    pw1, pw2 = f(beta_pow[0]) * b1, f(beta_pow[1]) * b2
+    step = f(lr) / (f(1) - pw1)
+    bc2s = np.sqrt(f(1) - pw2)
+    m = b1 * m + omb1 * g
+    v = b2 * v + omb2 * (g * g)
+    denom = np.sqrt(v) / bc2s + eps
+    w = w - step * (m / denom)
+    wt = omtau * wt + tau * w
+    return w, m, v, wt, np.array([pw1, pw2], dtype=f)
+
+
+# ---- the learner -------------------------------------------------------------------------------------------------------------------------------
+class DDPGLearner:
+    """``env_or_dims``: a ``MergeVecEnv`` (continuous-jerk; its context, observation width and action Box are taken over) or the observation width.
+    ``cfg``: ``DDPGConfig`` (None: the defaults); ``seed``: of the initialisation, the minibatch indices and the exploration noise;
+    ``init``: None (torch's nn.Linear initialisation, last layers zero), the name of a shipped actor ("medium1": that actor, a fresh critic), or a
+    dict ``{"actor": net, "critic": net}`` of numpy tensors."""
+
+    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None):
+        import torch
+        self.torch = torch
+        env = None if isinstance(env_or_dims, int) else env_or_dims
+        if env is not None and not env.continuous:
+            raise ValueError("DDPG needs the continuous action space (sumo-jerk-continuous-v0)")
+        self.cfg = cfg if cfg is not None else DDPGConfig(n_obs=env.obs_dim if env is not None else int(env_or_dims))
+        n_obs = env.obs_dim if env is not None else int(env_or_dims)
+        if self.cfg.n_obs != n_obs:
+            raise ValueError("cfg.n_obs is %d, the observation has %d entries" % (self.cfg.n_obs, n_obs))
+        self.ctx = ctx if ctx is not None else (env.ctx if env is not None else _capi.Context(-1))
+        self.seed = int(seed)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.handle = self.ctx.ddpg_create(self.cfg.to_c(seed))
+        c = self.cfg
+        rng = np.random.default_rng(self.seed)
+        if isinstance(init, dict):
+            a_net, q_net = init["actor"], init["critic"]
+        else:
+            a_net, q_net = init_net(c.n_obs + 1, c.h1, c.h2, rng), init_net(c.n_obs + 2, c.h1, c.h2, rng)
+            if init is not None:
+                w = _actor.load_weights(init)
+                if abs(w["tanh_scale"] - c.tanh_scale) > 0 or abs(w["tanh_mean"] - c.tanh_mean) > 0:
+                    raise ValueError("the shipped actor's squash is not this action Box's")
+                a_net = {k: w[k] for k in TENSORS}
+        self._lens = {"actor": flatten(a_net).size, "critic": flatten(q_net).size}
+        if self._lens["actor"] != (c.n_obs + 2) * c.h1 + (c.h1 + 2) * c.h2 + 1:
+            raise ValueError("the actor's tensors do not have the shape %d -> %d -> %d -> 1" % (c.n_obs + 1, c.h1, c.h2))
+        self.load_state_dict({"params": new_params(a_net, q_net), "counters": None})
+        z = lambda *sh, dtype=torch.float64: torch.zeros(sh, dtype=dtype, device=self.device)
+        self._stats = z(4)
+        self._actions = {}
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                self.ctx.ddpg_destroy(self.handle)
+            except Exception:
+                pass
+            self.handle = None
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    # -- acting / replay / update: asynchronous ---------------------------------------------------------------------------------------------
+    def act(self, obs, ticks, noise=True, debug=None):
+        """Actions fp64 [n] for observations float32 [n][n_obs] and episode ticks int32 [n] (``MergeVecEnv.episode_ticks``): the actor's output,
+        plus N(0, cfg.noise_std) exploration noise if ``noise``, clipped to the action Box.  The returned tensor is reused by the next call
+        with the same n.  ``debug``: uint32 [n][4] device tensor for the draws (debugging)."""
+        n = obs.shape[0]
+        out = self._actions.get(n)
+        if out is None:
+            out = self._actions[n] = self.torch.empty(n, dtype=self.torch.float64, device=self.device)
+        assert obs.dtype == self.torch.float32 and ticks.dtype == self.torch.int32 and obs.stride(1) == 1
+        self.ctx.ddpg_act(self.handle, n, obs.data_ptr(), obs.stride(0), ticks.data_ptr(), noise, out.data_ptr(), debug.data_ptr() if debug is not None else 0,
+                          self._stream())
+        return out
+
+    def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
+        """One env step into the replay ring: ``obs`` / ``ticks`` as given to ``act``, ``action`` fp64 [n], and what ``env.step`` returned
+        (``final_obs = info["final_observation"]``).  Where an episode ended, s' is the final observation at ticks + 1."""
+        torch = self.torch
+        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == reward.dtype == torch.float64 and ticks.dtype == torch.int32
+        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
+        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+        self.ctx.ddpg_push(self.handle, obs.shape[0], obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0, obs.stride(0),
+                           ticks.data_ptr(), next_ticks.data_ptr() if next_ticks is not None else 0, action.data_ptr(), reward.data_ptr(),
+                           terminated.data_ptr(), truncated.data_ptr(), self._stream())
+
+    def update(self, n=1, lr_q=None, lr_pi=None):
+        """``n`` updates (each: critic step, actor step, both Polyak updates); on the device nothing happens until more than cfg.replay_start
+        frames were pushed.  ``lr_q`` / ``lr_pi``: this call's learning rates (a schedule is the caller's; default cfg's)."""
+        self.ctx.ddpg_update(self.handle, n, self.cfg.lr_q if lr_q is None else lr_q, self.cfg.lr_pi if lr_pi is None else lr_pi, self._stream())
+
+    def grads(self):
+        """Debug: (actor gradient, critic gradient) on the current update index's minibatch as dicts of numpy tensors; nothing applied; synchronises."""
+        torch, c = self.torch, self.cfg
+        ga = torch.empty(self._lens["actor"], dtype=torch.float32, device=self.device)
+        gq = torch.empty(self._lens["critic"], dtype=torch.float32, device=self.device)
+        self.ctx.ddpg_grads(self.handle, ga.data_ptr(), gq.data_ptr(), self._stream())
+        return unflatten(ga.cpu().numpy(), c.n_obs + 1, c.h1, c.h2), unflatten(gq.cpu().numpy(), c.n_obs + 2, c.h1, c.h2)
+
+    def minibatch(self):
+        """Debug: the replay rows [batch][68] the next update will read (numpy); synchronises."""
+        rows = self.torch.empty(self.cfg.batch, _capi.DDPG_ROW, dtype=self.torch.float32, device=self.device)
+        self.ctx.ddpg_gather(self.handle, rows.data_ptr(), self._stream())
+        return rows.cpu().numpy()
+
+    def stats_device(self):
+        """fp64 [4] device tensor: critic loss and mean Q of the last minibatch, fill, updates done (asynchronous)."""
+        self.ctx.ddpg_stats(self.handle, self._stats.data_ptr(), self._stream())
+        return self._stats
+
+    def stats(self):
+        """The same as a dict; synchronises."""
+        s = self.stats_device().cpu().numpy()
+        return {"critic_loss": float(s[0]), "mean_q": float(s[1]), "fill": int(s[2]), "updates": int(s[3])}
+
+    # -- state ------------------------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """{"params": the eight slots as dicts of numpy tensors + beta_pow + updates, "counters": int64 [8]}; the replay ring is not part of it."""
+        c = self.cfg
+        cn, bp = self.ctx.ddpg_get_state(self.handle)
+        params = {}
+        for i, slot in enumerate(_capi.DDPG_SLOTS):
+            which = "critic" if i >= 4 else "actor"
+            params[slot] = unflatten(self.ctx.ddpg_get_params(self.handle, i, self._lens[which]), c.n_obs + (2 if i >= 4 else 1), c.h1, c.h2)
+        params["beta_pow"], params["updates"] = bp, int(cn[2])
+        return {"params": params, "counters": cn}
+
+    def load_state_dict(self, sd):
+        """The inverse; ``counters`` None: only the update count and Adam's beta powers are set (the replay's cursor and fill stay)."""
+        p = sd["params"]
+        for i, slot in enumerate(_capi.DDPG_SLOTS):
+            self.ctx.ddpg_set_params(self.handle, i, flatten(p[slot]))
+        cn = sd.get("counters")
+        if cn is None:
+            cn, _ = self.ctx.ddpg_get_state(self.handle)
+            cn[2] = int(p["updates"])
+        self.ctx.ddpg_set_state(self.handle, cn, p["beta_pow"])
+
+    def export_actor(self, path):
+        """Write the online actor as the ``.npz`` ``actor.load_weights`` reads (w0 ... b2 float32, tanh_scale, tanh_mean)."""
+        c = self.cfg
+        net = unflatten(self.ctx.ddpg_get_params(self.handle, 0, self._lens["actor"]), c.n_obs + 1, c.h1, c.h2)
+        write_actor(path, net, c.tanh_scale, c.tanh_mean)
+        return path
+
+
+def write_actor(path, net, tanh_scale, tanh_mean):
+    """The file format of ``actor.load_weights`` for a net {w0, b0, w1, b1, w2, b2}."""
+    with open(path, "wb") as fh:
+        np.savez_compressed(fh, **{k: np.asarray(net[k], dtype=np.float32) for k in TENSORS}, tanh_scale=np.float64(tanh_scale), tanh_mean=np.float64(tanh_mean))
+
+
+def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_schedule=None):
+    """The loop of the reference's ``DDPGAgent.train`` on the device: act with noise -> env.step -> push -> ``updates_per_step`` updates, until
+    ``frames`` transitions were collected (rounded up to whole steps of env.n).  Synchronises only every ``drain_every`` steps, to drain the
+    finished episodes' statistics.  ``lr_schedule(step, steps) -> (lr_q, lr_pi)``: e.g. the preset's cosine schedule, computed on the host.
+    Returns {"steps", "frames", "episodes", "mean_return" (of the drained episodes), "returns" (array)}."""
+    steps = -(-int(frames) // env.n)
+    obs = env.reset()
+    returns = []
+    for i in range(steps):
+        ticks = env.episode_ticks.clone()
+        action = learner.act(obs, ticks, noise=True)
+        next_obs, reward, term, trunc, info = env.step(action)
+        learner.push(obs, ticks, action, reward, next_obs, term, trunc, final_obs=info["final_observation"])
+        if updates_per_step:
+            lr_q, lr_pi = lr_schedule(i, steps) if lr_schedule is not None else (None, None)
+            learner.update(updates_per_step, lr_q, lr_pi)
+        obs = next_obs
+        if (i + 1) % drain_every == 0 or i + 1 == steps:
+            returns.append(env.drain_episode_stats()["episode_return"])
+    returns = np.concatenate(returns) if returns else np.zeros(0)
+    return {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
+            "returns": returns}
