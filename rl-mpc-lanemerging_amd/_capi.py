@@ -302,6 +302,19 @@ def _u8ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
+def _batch_states(ego, k_count, other_x, other_v):
+    """Host batch entries' states as contiguous arrays: ``(ego[N,5], k_count[N], other_x[N,Kmax], other_v[N,Kmax], N, Kmax)``, Kmax from ``other_x``."""
+    ego = np.ascontiguousarray(ego, dtype=np.float64)
+    k_count = np.ascontiguousarray(k_count, dtype=np.int32)
+    N = ego.shape[0]
+    if ego.ndim != 2 or ego.shape[1] != 5:
+        raise ValueError("ego must be [N,5] (x, y, v, a, start_s)")
+    other_x = np.ascontiguousarray(other_x, dtype=np.float64)
+    other_v = np.ascontiguousarray(other_v, dtype=np.float64)
+    Kmax = other_x.shape[1] if other_x.ndim == 2 else (other_x.size // N if N else 0)
+    return ego, k_count, other_x.reshape(N, Kmax), other_v.reshape(N, Kmax), N, Kmax
+
+
 def ego_s(x, y):
     """control.get_ego_s evaluated by the library's host helper (same libm as CPython)."""
     return load().stmpc_ego_s(float(x), float(y))
@@ -381,16 +394,7 @@ class Context:
 
     # -- batched solve, host numpy arrays --------------------------------------------------
     def solve_batch(self, params, ego, k_count, other_x, other_v, want_dist=True):
-        ego = np.ascontiguousarray(ego, dtype=np.float64)
-        k_count = np.ascontiguousarray(k_count, dtype=np.int32)
-        N = ego.shape[0]
-        if ego.ndim != 2 or ego.shape[1] != 5:
-            raise ValueError("ego must be [N,5] (x, y, v, a, start_s)")
-        other_x = np.ascontiguousarray(other_x, dtype=np.float64)
-        other_v = np.ascontiguousarray(other_v, dtype=np.float64)
-        Kmax = other_x.shape[1] if other_x.ndim == 2 else (other_x.size // N if N else 0)
-        other_x = other_x.reshape(N, Kmax)
-        other_v = other_v.reshape(N, Kmax)
+        ego, k_count, other_x, other_v, N, Kmax = _batch_states(ego, k_count, other_x, other_v)
         H = num_t(params)
         path = np.empty((N, H), dtype=np.int32)
         best_t = np.empty(N, dtype=np.int32)
@@ -433,16 +437,7 @@ class Context:
     # -- st.do_st_control, batched (host arrays) ---------------------------------------------------
     def st_control_batch(self, params, tick_length, ego, k_count, other_x, other_v, want_paths=False):
         """Returns a dict: ``speed[N]``, ``best_t[N]`` and, with ``want_paths``, ``path_idx``, ``cost``, ``fine``, ``fine_len``."""
-        ego = np.ascontiguousarray(ego, dtype=np.float64)
-        k_count = np.ascontiguousarray(k_count, dtype=np.int32)
-        N = ego.shape[0]
-        if ego.ndim != 2 or ego.shape[1] != 5:
-            raise ValueError("ego must be [N,5] (x, y, v, a, start_s)")
-        other_x = np.ascontiguousarray(other_x, dtype=np.float64)
-        other_v = np.ascontiguousarray(other_v, dtype=np.float64)
-        Kmax = other_x.shape[1] if other_x.ndim == 2 else (other_x.size // N if N else 0)
-        other_x = other_x.reshape(N, Kmax)
-        other_v = other_v.reshape(N, Kmax)
+        ego, k_count, other_x, other_v, N, Kmax = _batch_states(ego, k_count, other_x, other_v)
         H = num_t(params)
         speed = np.zeros(N, dtype=np.float64)
         best_t = np.zeros(N, dtype=np.int32)

@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "stmpc.h"
@@ -36,13 +37,24 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
                         std::string(#expr) + ": " + hipGetErrorString(_e));                        \
     } while (0)
 
+// returns the status of an entry's step when it is not STMPC_OK
+#define TRY(expr)                                                                                  \
+    do {                                                                                           \
+        if (const int _rc = (expr)) return _rc;                                                    \
+    } while (0)
+
 // libm pow through a volatile pointer so clang cannot fold pow(x,2.0)/pow(x,3.0): the reference's
 // Python evaluates float**int with libm pow (control.py:38) and Cython's dt**3 likewise (st_cy.pyx:49).
 double (*volatile host_pow)(double, double) = pow;
 
+// A device allocation that only grows; freed on destruction (on the current device: the destroy entries select the owner's first).
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return STMPC_OK;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -55,6 +67,32 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *)p; }
 };
+
+// host -> device staging: the buffer grows to count elements, then the copy
+template <class T> int upload(DevBuf &b, const T *host, size_t count) {
+    TRY(b.ensure(count * sizeof(T)));
+    HIPCHK(hipMemcpy(b.p, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return STMPC_OK;
+}
+// device -> host; a NULL host pointer is an output the caller did not ask for
+template <class T> int download(T *host, const DevBuf &b, size_t count) {
+    if (host) HIPCHK(hipMemcpy(host, b.p, count * sizeof(T), hipMemcpyDeviceToHost));
+    return STMPC_OK;
+}
+
+// the kernels' vehicle capacity (template argument KMAX): f(std::integral_constant<int, 8, 16 or 32>), the smallest that holds Kalloc
+template <class F> void with_kmax(int Kalloc, F &&f) {
+    if (Kalloc <= 8) f(std::integral_constant<int, 8>{});
+    else if (Kalloc <= 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 32>{});
+}
+
+// argument checks of the host batch entries: the batch's shape, then each state's vehicle count
+int check_batch(int N, int Kmax) { return N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT ? fail(STMPC_EINVAL, "N or Kmax out of range") : STMPC_OK; }
+int check_counts(int N, int Kmax, const int32_t *k) {
+    for (int i = 0; i < N; ++i) if (k[i] < 0 || k[i] > Kmax) return fail(STMPC_EINVAL, "k_count[i] outside [0, Kmax]");
+    return STMPC_OK;
+}
 
 int next_pow2(int v) { int w = 1; while (w < v) w <<= 1; return w; }
 
@@ -127,23 +165,74 @@ struct stmpc_ctx {
     // scratch
     DevBuf tab_edge, tab_win, tab_nact, tab_nums, counters, lists, ubound, proxy, order, gscratch, bp_tier[STMPC_MAX_TIERS];
     // staging for the host-pointer API
-    DevBuf s_ego, s_k, s_ox, s_ov, s_path, s_bt, s_cost, s_pd, s_crash, s_misc0, s_misc1, s_misc2, s_misc3;
+    struct Staging {
+        DevBuf ego, k, ox, ov, path, bt, cost, pd, crash, misc0, misc1, misc2, misc3;
+        DevBuf f_seq, f_len, f_v0, f_a0, f_bac, f_out, f_olen, f_iters, f_speed;   // finer_fit / st_control
+        // a host batch's states: ego [N][ego_w] (a buffer of [N][5]), k [N], other vehicles [N][Kmax] (buffers for at least one)
+        int states(int N, int Kmax, const double *ego_h, int ego_w, const int32_t *k_h, const double *ox_h, const double *ov_h) {
+            const size_t n = (size_t)N, Kalloc = Kmax > 0 ? Kmax : 1;
+            TRY(ego.ensure(n * 5 * 8)); TRY(k.ensure(n * 4)); TRY(ox.ensure(n * Kalloc * 8)); TRY(ov.ensure(n * Kalloc * 8));
+            TRY(upload(ego, ego_h, n * ego_w));
+            TRY(upload(k, k_h, n));
+            if (Kmax > 0) { TRY(upload(ox, ox_h, n * Kmax)); TRY(upload(ov, ov_h, n * Kmax)); }
+            return STMPC_OK;
+        }
+    } s;
     DevBuf ckpt, pool_bp, resume_t, phase_prof, prio_key;
     int pool_cap_override = 0;     // STMPC_POOL=n: checkpoint pool entries (tests: a tiny pool must only cost speed)
     // combined controller (stmpc_rollout_step_device / stmpc_combined_decide_device): rollout bookkeeping and probe / controller outputs
-    DevBuf cc_live, cc_hist_len, cc_crash_pred, cc_have_test, cc_sel, cc_rollout_s, cc_test_ego, cc_test_ox, cc_test_ov, cc_probe_ego, cc_probe_ox, cc_probe_ov,
-        cc_path, cc_bt, cc_cost, cc_pcrash, cc_speed, cc_fine, cc_fine_len, cc_err,
-        cc_sel_idx, cc_sel_count, cc_c_ego, cc_c_k, cc_c_ox, cc_c_ov, cc_c_speed, cc_c_fine, cc_c_fine_len;      // sparse controller solve: the states that need st.do_st_control
-    int cc_N = 0, cc_K = 0, cc_R = 0;
-    int *cc_host_count = nullptr;  // pinned host word for the number of those states
-    int64_t cc_ticks = 0, cc_control_solves = 0;      // decisions taken / controller solves run for them (stmpc_combined_counts)
+    struct Combined {
+        DevBuf live, hist_len, crash_pred, have_test, sel, rollout_s, test_ego, test_ox, test_ov, probe_ego, probe_ox, probe_ov,
+            path, bt, cost, pcrash, speed, fine, fine_len,
+            sel_idx, sel_count, c_ego, c_k, c_ox, c_ov, c_speed, c_fine, c_fine_len;      // sparse controller solve: the states that need st.do_st_control
+        int N = 0, K = 0, R = 0;
+        int *host_count = nullptr;  // pinned host word for the number of those states
+        int64_t ticks = 0, control_solves = 0;      // decisions taken / controller solves run for them (stmpc_combined_counts)
+        int ensure(int n_, int k_, int r_) {        // the rollout's bookkeeping (step 1)
+            const size_t n = (size_t)n_;
+            TRY(live.ensure(n * 4)); TRY(hist_len.ensure(n * 4)); TRY(crash_pred.ensure(n * 4)); TRY(have_test.ensure(n * 4)); TRY(sel.ensure(n * 8));
+            TRY(rollout_s.ensure(n * (r_ + 1) * 8)); TRY(test_ego.ensure(n * 4 * 8)); TRY(test_ox.ensure(n * k_ * 8)); TRY(test_ov.ensure(n * k_ * 8));
+            N = n_; K = k_; R = r_;
+            return STMPC_OK;
+        }
+        CCState state() const {
+            return CCState{live.as<int>(), hist_len.as<int>(), crash_pred.as<int>(), have_test.as<int>(), sel.as<double>(), rollout_s.as<double>(),
+                           test_ego.as<double>(), test_ox.as<double>(), test_ov.as<double>()};
+        }
+    } cc;
     // batched episode simulator (stmpc_sim_*)
-    DevBuf sim_ego, sim_nveh, sim_vx, sim_vv, sim_va, sim_vc, sim_delay, sim_status, sim_ticks, sim_rng, sim_acc, sim_route;
-    int sim_N = 0, sim_route_n = 0;
+    struct Sim {
+        DevBuf ego, nveh, vx, vv, va, vc, delay, status, ticks, rng, acc, route;
+        int N = 0, route_n = 0;
+        int ensure(int n_) {
+            const size_t n = (size_t)n_, KS = sim::KS;
+            TRY(ego.ensure(n * 4 * 8)); TRY(nveh.ensure(n * 4)); TRY(vx.ensure(n * KS * 8)); TRY(vv.ensure(n * KS * 8)); TRY(va.ensure(n * KS * 8));
+            TRY(vc.ensure(n * KS * 8)); TRY(delay.ensure(n * 8)); TRY(status.ensure(n * 4)); TRY(ticks.ensure(n * 4)); TRY(rng.ensure(n * 4));
+            TRY(acc.ensure(n * sim::NACC * 8));
+            return STMPC_OK;
+        }
+        sim::State state() const {
+            return sim::State{ego.as<double>(), nveh.as<int>(), vx.as<double>(), vv.as<double>(), va.as<double>(), vc.as<double>(), delay.as<double>(),
+                              status.as<int>(), ticks.as<int>(), rng.as<unsigned>(), acc.as<double>()};
+        }
+    } sim;
     // vector environment on the simulator (stmpc_env_*)
-    DevBuf env_ep, env_prev_a, env_pjerk, env_inv, env_ret, env_cmd, env_live, env_vx, env_vv, env_va, env_k, env_log, env_log_n, env_actions;
-    int env_N = 0, env_n_actions = 0, env_log_cap = 0, env_mode = -1;    // (env_N = 0: no environment; a plain stmpc_sim_init_device invalidates it)
-    DevBuf f_seq, f_len, f_v0, f_a0, f_bac, f_out, f_olen, f_iters, f_speed;   // finer_fit / st_control staging
+    struct Env {
+        DevBuf ep, prev_a, pjerk, inv, ret, cmd, live, vx, vv, va, k, log, log_n, actions;
+        int N = 0, n_actions = 0, log_cap = 0, mode = -1;    // (N = 0: no environment; a plain stmpc_sim_init_device invalidates it)
+        int ensure(int n_, int cap) {
+            const size_t n = (size_t)n_, KS = sim::KS;
+            TRY(ep.ensure(n * 4)); TRY(prev_a.ensure(n * 8)); TRY(pjerk.ensure(n * 8)); TRY(inv.ensure(n * 8)); TRY(ret.ensure(n * 8)); TRY(cmd.ensure(n * 8));
+            TRY(live.ensure(n * 4)); TRY(vx.ensure(n * KS * 8)); TRY(vv.ensure(n * KS * 8)); TRY(va.ensure(n * KS * 8)); TRY(k.ensure(n * 4)); TRY(log_n.ensure(4));
+            TRY(log.ensure((size_t)cap * env::NLOG * 8));
+            log_cap = cap;
+            return STMPC_OK;
+        }
+        env::EState state(unsigned *err) const {
+            return env::EState{ep.as<int>(), prev_a.as<double>(), pjerk.as<double>(), inv.as<double>(), ret.as<double>(), cmd.as<double>(), live.as<int>(),
+                               vx.as<double>(), vv.as<double>(), va.as<double>(), k.as<int>(), log.as<double>(), log_n.as<unsigned>(), err};
+        }
+    } env;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     stmpc_stats stats{};
     bool stats_pending = false;
@@ -367,19 +456,8 @@ int stmpc_create(stmpc_ctx **out, int device) {
 
 void stmpc_destroy(stmpc_ctx *c) {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    for (auto &g : c->guides) g.dev.release();
-    DevBuf *all[] = {&c->guide_cells, &c->sticky, &c->cu_tab, &c->tab_edge, &c->tab_win, &c->tab_nact, &c->tab_nums, &c->counters, &c->lists, &c->ubound, &c->proxy, &c->order, &c->bp_tier[0],
-                     &c->bp_tier[1], &c->bp_tier[2], &c->bp_tier[3], &c->bp_tier[4], &c->bp_tier[5], &c->gscratch, &c->s_ego, &c->s_k, &c->s_ox, &c->s_ov, &c->s_path, &c->s_bt, &c->s_cost,
-                     &c->s_pd, &c->s_crash, &c->s_misc0, &c->s_misc1, &c->s_misc2, &c->s_misc3,
-                     &c->ckpt, &c->pool_bp, &c->resume_t, &c->phase_prof, &c->prio_key, &c->cc_live, &c->cc_hist_len, &c->cc_crash_pred, &c->cc_have_test, &c->cc_sel, &c->cc_rollout_s, &c->cc_test_ego,
-                     &c->cc_test_ox, &c->cc_test_ov, &c->cc_probe_ego, &c->cc_probe_ox, &c->cc_probe_ov, &c->cc_path, &c->cc_bt, &c->cc_cost, &c->cc_pcrash, &c->cc_speed,
-                     &c->cc_fine, &c->cc_fine_len, &c->cc_err, &c->sim_ego, &c->sim_nveh, &c->sim_vx, &c->sim_vv, &c->sim_va, &c->sim_vc, &c->sim_delay, &c->sim_status, &c->sim_ticks,
-                     &c->sim_rng, &c->sim_acc, &c->sim_route, &c->env_ep, &c->env_prev_a, &c->env_pjerk, &c->env_inv, &c->env_ret, &c->env_cmd, &c->env_live,
-                     &c->env_vx, &c->env_vv, &c->env_va, &c->env_k, &c->env_log, &c->env_log_n, &c->env_actions, &c->f_seq, &c->f_len, &c->f_v0, &c->f_a0, &c->f_bac, &c->f_out, &c->f_olen, &c->f_iters, &c->f_speed,
-                     &c->cc_sel_idx, &c->cc_sel_count, &c->cc_c_ego, &c->cc_c_k, &c->cc_c_ox, &c->cc_c_ov, &c->cc_c_speed, &c->cc_c_fine, &c->cc_c_fine_len};
-    for (DevBuf *b : all) b->release();
-    if (c->cc_host_count) (void)hipHostFree(c->cc_host_count);
+    (void)hipSetDevice(c->device);       // (the device buffers are freed by their destructors, on this device)
+    if (c->cc.host_count) (void)hipHostFree(c->cc.host_count);
     if (c->h_overflow) (void)hipHostFree(c->h_overflow);
     if (c->main_masked) (void)hipStreamDestroy(c->main_masked);
     if (c->aux_reserved) (void)hipStreamDestroy(c->aux_reserved);
@@ -596,8 +674,7 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     DevP dp;
-    int rc = make_devp(p, &dp);
-    if (rc) return rc;
+    TRY(make_devp(p, &dp));
     const int H = dp.H;
     const int S_nom = stmpc_num_s(p, 0.0);
     if (S_nom < 2 || S_nom + 2 > STMPC_S_LIMIT) return fail(STMPC_EINVAL, "number of position cells out of range");
@@ -611,15 +688,15 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     const bool fastdiv = c->allow_fastdiv && fastdiv_ok(dp.dt) && fastdiv_ok(dp.dt2) && fastdiv_ok(dp.dt3) && c->fd2_ok;
 
     // scratch
-    if ((rc = c->tab_edge.ensure((size_t)N * H * Kalloc * 2 * sizeof(double)))) return rc;
-    if ((rc = c->tab_win.ensure((size_t)N * H * Kalloc * 2 * sizeof(int)))) return rc;
-    if ((rc = c->tab_nact.ensure((size_t)N * H * sizeof(int)))) return rc;
-    if ((rc = c->tab_nums.ensure((size_t)N * sizeof(int)))) return rc;
-    if (!c->counters.p) { if ((rc = c->counters.ensure(64 * sizeof(unsigned)))) return rc; HIPCHK(hipMemsetAsync(c->counters.p, 0, 64 * sizeof(unsigned), st)); }
-    if ((rc = c->lists.ensure((size_t)STMPC_MAX_TIERS * N * sizeof(int)))) return rc;
-    if ((rc = c->ubound.ensure((size_t)N * sizeof(u64)))) return rc;
-    if ((rc = c->proxy.ensure((size_t)N * sizeof(unsigned)))) return rc;
-    if ((rc = c->order.ensure((size_t)N * sizeof(int)))) return rc;
+    TRY(c->tab_edge.ensure((size_t)N * H * Kalloc * 2 * sizeof(double)));
+    TRY(c->tab_win.ensure((size_t)N * H * Kalloc * 2 * sizeof(int)));
+    TRY(c->tab_nact.ensure((size_t)N * H * sizeof(int)));
+    TRY(c->tab_nums.ensure((size_t)N * sizeof(int)));
+    if (!c->counters.p) { TRY(c->counters.ensure(64 * sizeof(unsigned))); HIPCHK(hipMemsetAsync(c->counters.p, 0, 64 * sizeof(unsigned), st)); }
+    TRY(c->lists.ensure((size_t)STMPC_MAX_TIERS * N * sizeof(int)));
+    TRY(c->ubound.ensure((size_t)N * sizeof(u64)));
+    TRY(c->proxy.ensure((size_t)N * sizeof(unsigned)));
+    TRY(c->order.ensure((size_t)N * sizeof(int)));
 
     // widest fan-out the dynamics allow (st_cy.pyx:65-93): acceleration- or jerk-limited window, +2 for rounding
     const double fan_acc = (dp.a_max - dp.a_min) * dp.dt2 / dp.ds, fan_jerk = (dp.j_max - dp.j_min) * dp.dt3 / dp.ds;
@@ -714,10 +791,10 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
         }
     }
     for (int k = 0; k < nt; ++k)                 // back-pointers of a tier: per resident workgroup
-        if ((rc = c->bp_tier[k].ensure((size_t)tierGrid[k] * H * tierW[k] * bp_elem))) return rc;
+        TRY(c->bp_tier[k].ensure((size_t)tierGrid[k] * H * tierW[k] * bp_elem));
     c->last_resume_refused = resume_wanted && !resume;
     int *resume_t = resume ? c->resume_t.as<int>() : nullptr;
-    if (need_hbm_tier && (rc = c->gscratch.ensure((size_t)tierGrid[nt - 1] * ((size_t)Wg * STMPC_CELL_BYTES + STMPC_LIST_SLACK + (size_t)Wg * 8)))) return rc;
+    if (need_hbm_tier) TRY(c->gscratch.ensure((size_t)tierGrid[nt - 1] * ((size_t)Wg * STMPC_CELL_BYTES + STMPC_LIST_SLACK + (size_t)Wg * 8)));
 
     CarTab tab{c->tab_edge.as<double>(), c->tab_win.as<int>(), c->tab_nact.as<int>(), c->tab_nums.as<int>()};
     unsigned *counters = c->counters.as<unsigned>();
@@ -748,7 +825,7 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     const bool split = prune_on && !c->two_phase && c->split && N >= 2 * tierGrid[0];
     unsigned *proxy0 = split ? c->proxy.as<unsigned>() : nullptr;
     const bool heavy_first = split && c->heavy_first;
-    if (heavy_first && (rc = c->prio_key.ensure((size_t)N))) return rc;
+    if (heavy_first) TRY(c->prio_key.ensure((size_t)N));
     unsigned char *prio_key = heavy_first ? c->prio_key.as<unsigned char>() : nullptr;
     const unsigned char *g_tab = nullptr; u16 *g_cells = nullptr; int g_imax = 0, g_D = 0;
     if (prune_on && c->tube_w > 0) {
@@ -769,19 +846,20 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
             }
             slot->ok = build_guide_table(dp, slot->host, slot->imax, slot->D);
             if (slot->ok) {
-                if ((rc = slot->dev.ensure(slot->host.size()))) return rc;
+                TRY(slot->dev.ensure(slot->host.size()));
                 HIPCHK(hipMemcpyAsync(slot->dev.p, slot->host.data(), slot->host.size(), hipMemcpyHostToDevice, st));
             }
             memcpy(slot->key, key, sizeof key);
             slot->valid = true;                 // (only after the upload has been queued successfully)
         }
         slot->last_use = ++c->guide_clock;
-        if (slot->ok) { if ((rc = c->guide_cells.ensure((size_t)N * H * sizeof(u16)))) return rc; g_tab = slot->dev.as<unsigned char>(); g_cells = c->guide_cells.as<u16>(); g_imax = slot->imax; g_D = slot->D; }
+        if (slot->ok) { TRY(c->guide_cells.ensure((size_t)N * H * sizeof(u16))); g_tab = slot->dev.as<unsigned char>(); g_cells = c->guide_cells.as<u16>(); g_imax = slot->imax; g_D = slot->D; }
     }
     HIPCHK(hipEventRecord(e0, st));
-    if (Kalloc <= 8) launch_predict<8>(dp, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, c->ubound.as<u64>(), queue1, proxy0, resume_t, prio_key, st, c->sticky.as<unsigned>(), g_tab, g_imax, g_D, g_cells);
-    else if (Kalloc <= 16) launch_predict<16>(dp, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, c->ubound.as<u64>(), queue1, proxy0, resume_t, prio_key, st, c->sticky.as<unsigned>(), g_tab, g_imax, g_D, g_cells);
-    else launch_predict<32>(dp, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, c->ubound.as<u64>(), queue1, proxy0, resume_t, prio_key, st, c->sticky.as<unsigned>(), g_tab, g_imax, g_D, g_cells);
+    with_kmax(Kalloc, [&](auto km) {
+        launch_predict<decltype(km)::value>(dp, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, c->ubound.as<u64>(), queue1, proxy0, resume_t, prio_key, st,
+                                            c->sticky.as<unsigned>(), g_tab, g_imax, g_D, g_cells);
+    });
 
     SolveArgs a;
     memset(&a, 0, sizeof a);
@@ -816,7 +894,7 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     a.gsh_max = c->gsh_max;
     a.zl_dt = c->fd2_zl[0]; a.zl_dt2 = c->fd2_zl[1]; a.zl_dt3 = c->fd2_zl[2];
 #ifdef STMPC_PHASE_PROF
-    if ((rc = c->phase_prof.ensure(4 * STMPC_NPH * sizeof(unsigned long long)))) return rc;
+    TRY(c->phase_prof.ensure(4 * STMPC_NPH * sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(c->phase_prof.p, 0, 4 * STMPC_NPH * sizeof(unsigned long long), st));
     a.phase_prof = c->phase_prof.as<unsigned long long>();
 #endif
@@ -830,7 +908,7 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     a.host_overflow = c->d_overflow;
 
     if (overlap && split && c->retire_cus > 0 && c->retire_cus < c->num_cu) {
-        if ((rc = c->cu_tab.ensure(1025 * sizeof(unsigned)))) return rc;
+        TRY(c->cu_tab.ensure(1025 * sizeof(unsigned)));
         HIPCHK(hipMemsetAsync(c->cu_tab.p, 0, 1025 * sizeof(unsigned), st));
         a.cu_tab = c->cu_tab.as<unsigned>(); a.retire_from = c->num_cu - c->retire_cus; a.retire_left = (long long)N * c->retire_at / 100;
     }
@@ -922,18 +1000,18 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
 
     if (heavy_first) hipLaunchKernelGGL(k_order8, dim3(1), dim3(1024), 0, st, N, (const unsigned char *)prio_key, c->order.as<int>());
     if (two_phase) {                                           // bound every episode, order them heaviest-first
-        if ((rc = launch_tier(0, 1, false))) return rc;
+        TRY(launch_tier(0, 1, false));
         hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, N, (const unsigned *)c->proxy.as<unsigned>(), c->order.as<int>());
     }
     for (int k = 0; k < nt; ++k) {
         if (reserve && k == 0) HIPCHK(hipStreamWaitEvent(c->main_masked, c->ev_fork, 0));
-        if ((rc = launch_tier(k, two_phase ? 2 : 0, false))) return rc;
+        TRY(launch_tier(k, two_phase ? 2 : 0, false));
         if (reserve && k == 0) {
             // the reserved units host second-window workgroups from the start of the step; the masked streams partition the device, so
             // these consumers may always wait for the queue (they cannot be holding a unit a producer needs)
             HIPCHK(hipEventRecord(c->ev_join0, c->main_masked));
             HIPCHK(hipStreamWaitEvent(c->aux_reserved, c->ev_fork, 0));
-            if ((rc = launch_tier(1, 0, true, true))) return rc;
+            TRY(launch_tier(1, 0, true, true));
             HIPCHK(hipEventRecord(c->ev_join_r, c->aux_reserved));
             HIPCHK(hipStreamWaitEvent(st, c->ev_join0, 0));
             HIPCHK(hipStreamWaitEvent(st, c->ev_join_r, 0));
@@ -943,7 +1021,7 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
             // tier 0's persistent workgroups begin to leave CUs.  The main stream then waits for it, and the ordinary
             // launch of tier 1 that follows picks up whatever it left (normally nothing).
             HIPCHK(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-            if ((rc = launch_tier(1, 0, true))) return rc;
+            TRY(launch_tier(1, 0, true));
             HIPCHK(hipEventRecord(c->ev_join, c->aux_stream));
             HIPCHK(hipStreamWaitEvent(st, c->ev_join, 0));
         }
@@ -1029,43 +1107,25 @@ int stmpc_solve_batch(stmpc_ctx *c, const stmpc_params *p, int N, int Kmax, cons
                       const double *ox, const double *ov, int32_t *path, int32_t *bt, double *cost, double *pd,
                       int32_t *crash) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "N or Kmax out of range");
+    TRY(check_batch(N, Kmax));
     if (N == 0) return STMPC_OK;
     if (!ego || !k || !path || !bt || !cost) return fail(STMPC_EINVAL, "NULL host pointer");
     if (Kmax > 0 && (!ox || !ov)) return fail(STMPC_EINVAL, "NULL host pointer (other_x/other_v)");
-    for (int i = 0; i < N; ++i) if (k[i] < 0 || k[i] > Kmax) return fail(STMPC_EINVAL, "k_count[i] outside [0, Kmax]");
+    TRY(check_counts(N, Kmax, k));
     HIPCHK(hipSetDevice(c->device));
     int H = stmpc_num_t(p);
     if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
-    int rc;
-    const int Kalloc = Kmax > 0 ? Kmax : 1;
-    if ((rc = c->s_ego.ensure((size_t)N * 5 * 8))) return rc;
-    if ((rc = c->s_k.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->s_ox.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->s_ov.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->s_path.ensure((size_t)N * H * 4))) return rc;
-    if ((rc = c->s_bt.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->s_cost.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->s_pd.ensure((size_t)N * H * 8))) return rc;
-    if ((rc = c->s_crash.ensure((size_t)N * 4))) return rc;
-    HIPCHK(hipMemcpy(c->s_ego.p, ego, (size_t)N * 5 * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->s_k.p, k, (size_t)N * 4, hipMemcpyHostToDevice));
-    if (Kmax > 0) {
-        HIPCHK(hipMemcpy(c->s_ox.p, ox, (size_t)N * Kmax * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->s_ov.p, ov, (size_t)N * Kmax * 8, hipMemcpyHostToDevice));
-    }
-    rc = stmpc_solve_batch_device(c, p, N, Kmax, c->s_ego.as<double>(), c->s_k.as<int32_t>(), c->s_ox.as<double>(),
-                                  c->s_ov.as<double>(), c->s_path.as<int32_t>(), c->s_bt.as<int32_t>(),
-                                  c->s_cost.as<double>(), c->s_pd.as<double>(), c->s_crash.as<int32_t>(), nullptr);
-    if (rc) return rc;
+    auto &s = c->s;
+    const size_t n = (size_t)N;
+    TRY(s.path.ensure(n * H * 4)); TRY(s.bt.ensure(n * 4)); TRY(s.cost.ensure(n * 8)); TRY(s.pd.ensure(n * H * 8)); TRY(s.crash.ensure(n * 4));
+    TRY(s.states(N, Kmax, ego, 5, k, ox, ov));
+    TRY(stmpc_solve_batch_device(c, p, N, Kmax, s.ego.as<double>(), s.k.as<int32_t>(), s.ox.as<double>(), s.ov.as<double>(), s.path.as<int32_t>(),
+                                 s.bt.as<int32_t>(), s.cost.as<double>(), s.pd.as<double>(), s.crash.as<int32_t>(), nullptr));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(path, c->s_path.p, (size_t)N * H * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(bt, c->s_bt.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cost, c->s_cost.p, (size_t)N * 8, hipMemcpyDeviceToHost));
-    if (pd) HIPCHK(hipMemcpy(pd, c->s_pd.p, (size_t)N * H * 8, hipMemcpyDeviceToHost));
-    if (crash) HIPCHK(hipMemcpy(crash, c->s_crash.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    stmpc_stats s;
-    return stmpc_get_stats(c, &s);
+    TRY(download(path, s.path, n * H)); TRY(download(bt, s.bt, n)); TRY(download(cost, s.cost, n));
+    TRY(download(pd, s.pd, n * H)); TRY(download(crash, s.crash, n));
+    stmpc_stats st;
+    return stmpc_get_stats(c, &st);
 }
 
 int stmpc_solve_grid(stmpc_ctx *c, const uint8_t *obstacles, const double *s_values, int S, const double *t_values,
@@ -1086,34 +1146,29 @@ int stmpc_solve_grid(stmpc_ctx *c, const uint8_t *obstacles, const double *s_val
     dp.d_w = d_w; dp.v_w = v_w; dp.a_w = a_w; dp.j_w = j_w; dp.v_des = v_des; dp.v_max = v_max; dp.a_min = a_min;
     dp.a_max = a_max; dp.j_min = j_min; dp.j_max = j_max; dp.min_allowed = min_allowed;
     dp.crash_dist_thr = -1.0; dp.H = H;
-    int rc;
+    auto &s = c->s;
     const size_t cells = (size_t)H * S;
-    if ((rc = c->s_misc0.ensure(cells))) return rc;
-    if ((rc = c->s_misc1.ensure(cells * 8))) return rc;
-    if ((rc = c->s_misc2.ensure((size_t)S * 8))) return rc;
-    if ((rc = c->s_misc3.ensure((size_t)H * 8))) return rc;
-    if ((rc = c->counters.ensure(64 * sizeof(unsigned)))) return rc;
+    TRY(s.misc3.ensure((size_t)H * 8));
+    TRY(c->counters.ensure(64 * sizeof(unsigned)));
     const int Wg = next_pow2(S + 2 + 128);
-    if ((rc = c->gscratch.ensure((size_t)Wg * STMPC_CELL_BYTES + STMPC_LIST_SLACK + (size_t)Wg * 8))) return rc;
-    if ((rc = c->bp_tier[STMPC_MAX_TIERS - 1].ensure((size_t)H * Wg * sizeof(u16)))) return rc;
-    HIPCHK(hipMemcpy(c->s_misc0.p, obstacles, cells, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->s_misc1.p, distances, cells * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->s_misc2.p, s_values, (size_t)S * 8, hipMemcpyHostToDevice));
-    if ((rc = latch_solver_error(c))) return rc;          // an earlier asynchronous call's flag survives the reset below
+    TRY(c->gscratch.ensure((size_t)Wg * STMPC_CELL_BYTES + STMPC_LIST_SLACK + (size_t)Wg * 8));
+    TRY(c->bp_tier[STMPC_MAX_TIERS - 1].ensure((size_t)H * Wg * sizeof(u16)));
+    TRY(upload(s.misc0, obstacles, cells)); TRY(upload(s.misc1, distances, cells)); TRY(upload(s.misc2, s_values, (size_t)S));
+    TRY(latch_solver_error(c));          // an earlier asynchronous call's flag survives the reset below
     HIPCHK(hipMemset(c->counters.p, 0, 64 * sizeof(unsigned)));
     SolveArgs a;
     memset(&a, 0, sizeof a);
     a.p = dp; a.N = 1; a.Kmax = 1; a.W = Wg; a.PW = Wg; a.last_tier = 1;
     for (int i = 0; i < 3; ++i) a.retry_mult[i] = c->retry_mult[i];
     a.bound_infl = c->bound_infl; a.last_infl = c->last_infl;
-    a.obstacles = c->s_misc0.as<uint8_t>(); a.distances = c->s_misc1.as<double>(); a.s_values = c->s_misc2.as<double>();
+    a.obstacles = s.misc0.as<uint8_t>(); a.distances = s.misc1.as<double>(); a.s_values = s.misc2.as<double>();
     a.S_grid = S; a.v0_grid = v0; a.a0_grid = a0; a.gsh_max = c->gsh_max;
     a.bp = c->bp_tier[STMPC_MAX_TIERS - 1].as<u16>(); a.gscratch = c->gscratch.as<unsigned char>(); a.counters = c->counters.as<unsigned>();
-    a.s_sequence = c->s_misc3.as<double>();
+    a.s_sequence = s.misc3.as<double>();
     hipLaunchKernelGGL((k_solve<false, true, false, 0, 16, true>), dim3(1), dim3(256), ((stmpc_chunk_ints(Wg) * sizeof(int) + 15) & ~(size_t)15) + 16, nullptr, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(s_sequence_out, c->s_misc3.p, (size_t)H * 8, hipMemcpyDeviceToHost));
+    TRY(download(s_sequence_out, s.misc3, (size_t)H));
     unsigned cnt[64];
     HIPCHK(hipMemcpy(cnt, c->counters.p, sizeof cnt, hipMemcpyDeviceToHost));
     if (cnt[STMPC_CNT_ERR]) {
@@ -1130,46 +1185,33 @@ int stmpc_build_grid(stmpc_ctx *c, const stmpc_params *p, const double *state5, 
     if (k < 0 || k > STMPC_KMAX_LIMIT || (k > 0 && (!ox || !ov))) return fail(STMPC_EINVAL, "bad vehicle count / arrays");
     HIPCHK(hipSetDevice(c->device));
     DevP dp;
-    int rc = make_devp(p, &dp);
-    if (rc) return rc;
+    TRY(make_devp(p, &dp));
     const int H = dp.H;
     const double start_s = state5[4];
     const int S = stmpc_num_s(p, start_s);
     if (S < 2 || S > STMPC_S_LIMIT) return fail(STMPC_EINVAL, "number of position cells out of range");
     const int Kalloc = k > 0 ? k : 1;
-    if ((rc = c->tab_edge.ensure((size_t)H * Kalloc * 2 * 8))) return rc;
-    if ((rc = c->tab_win.ensure((size_t)H * Kalloc * 2 * 4))) return rc;
-    if ((rc = c->tab_nact.ensure((size_t)H * 4))) return rc;
-    if ((rc = c->tab_nums.ensure(4))) return rc;
-    if ((rc = c->counters.ensure(64 * sizeof(unsigned)))) return rc;
-    if ((rc = c->s_ego.ensure(5 * 8))) return rc;
-    if ((rc = c->s_k.ensure(4))) return rc;
-    if ((rc = c->s_ox.ensure((size_t)Kalloc * 8))) return rc;
-    if ((rc = c->s_ov.ensure((size_t)Kalloc * 8))) return rc;
+    auto &s = c->s;
+    TRY(c->tab_edge.ensure((size_t)H * Kalloc * 2 * 8));
+    TRY(c->tab_win.ensure((size_t)H * Kalloc * 2 * 4));
+    TRY(c->tab_nact.ensure((size_t)H * 4));
+    TRY(c->tab_nums.ensure(4));
+    TRY(c->counters.ensure(64 * sizeof(unsigned)));
     const size_t cells = (size_t)H * S;
-    if ((rc = c->s_misc0.ensure(cells))) return rc;
-    if ((rc = c->s_misc1.ensure(cells * 8))) return rc;
-    if ((rc = c->s_misc2.ensure((size_t)S * 8))) return rc;
-    HIPCHK(hipMemcpy(c->s_ego.p, state5, 5 * 8, hipMemcpyHostToDevice));
-    int32_t kk = k;
-    HIPCHK(hipMemcpy(c->s_k.p, &kk, 4, hipMemcpyHostToDevice));
-    if (k > 0) {
-        HIPCHK(hipMemcpy(c->s_ox.p, ox, (size_t)k * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->s_ov.p, ov, (size_t)k * 8, hipMemcpyHostToDevice));
-    }
+    TRY(s.misc0.ensure(cells)); TRY(s.misc1.ensure(cells * 8)); TRY(s.misc2.ensure((size_t)S * 8));
+    const int32_t kk = k;
+    TRY(s.states(1, k, state5, 5, &kk, ox, ov));
     CarTab tab{c->tab_edge.as<double>(), c->tab_win.as<int>(), c->tab_nact.as<int>(), c->tab_nums.as<int>()};
     unsigned *counters = c->counters.as<unsigned>();
-    if (Kalloc <= 8) launch_predict<8>(dp, 1, Kalloc, c->s_ego.as<double>(), c->s_k.as<int>(), c->s_ox.as<double>(), c->s_ov.as<double>(), tab, counters, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->sticky.as<unsigned>());
-    else if (Kalloc <= 16) launch_predict<16>(dp, 1, Kalloc, c->s_ego.as<double>(), c->s_k.as<int>(), c->s_ox.as<double>(), c->s_ov.as<double>(), tab, counters, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->sticky.as<unsigned>());
-    else launch_predict<32>(dp, 1, Kalloc, c->s_ego.as<double>(), c->s_k.as<int>(), c->s_ox.as<double>(), c->s_ov.as<double>(), tab, counters, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->sticky.as<unsigned>());
+    with_kmax(Kalloc, [&](auto km) {
+        launch_predict<decltype(km)::value>(dp, 1, Kalloc, s.ego.as<double>(), s.k.as<int>(), s.ox.as<double>(), s.ov.as<double>(), tab, counters, nullptr, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, c->sticky.as<unsigned>());
+    });
     dim3 grid((S + 255) / 256, H);
-    hipLaunchKernelGGL(k_build_grid, grid, dim3(256), 0, nullptr, dp, tab, Kalloc, start_s, S, c->s_misc0.as<uint8_t>(),
-                       c->s_misc1.as<double>(), c->s_misc2.as<double>());
+    hipLaunchKernelGGL(k_build_grid, grid, dim3(256), 0, nullptr, dp, tab, Kalloc, start_s, S, s.misc0.as<uint8_t>(), s.misc1.as<double>(), s.misc2.as<double>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(obstacles, c->s_misc0.p, cells, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(distances, c->s_misc1.p, cells * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(s_values, c->s_misc2.p, (size_t)S * 8, hipMemcpyDeviceToHost));
+    TRY(download(obstacles, s.misc0, cells)); TRY(download(distances, s.misc1, cells)); TRY(download(s_values, s.misc2, (size_t)S));
     host_t_values(p, H, t_values);
     return STMPC_OK;
 }
@@ -1207,49 +1249,28 @@ int stmpc_predict_batch_acc(stmpc_ctx *c, const stmpc_params *p, int mode, int N
     if (N == 0) return STMPC_OK;
     if (!ego4 || !k || !ego4_out || !crashed || (mode == 0 && !sel)) return fail(STMPC_EINVAL, "NULL host pointer");
     if (Kmax > 0 && (!ox || !ov || !ox_out || !ov_out)) return fail(STMPC_EINVAL, "NULL host pointer (vehicles)");
-    for (int i = 0; i < N; ++i) if (k[i] < 0 || k[i] > Kmax) return fail(STMPC_EINVAL, "k_count[i] outside [0, Kmax]");
+    TRY(check_counts(N, Kmax, k));
     HIPCHK(hipSetDevice(c->device));
     DevP dp;
-    int rc = make_devp(p, &dp);
-    if (rc) return rc;
+    TRY(make_devp(p, &dp));
     const int Kalloc = Kmax > 0 ? Kmax : 1;
-    if ((rc = c->s_ego.ensure((size_t)N * 5 * 8))) return rc;
-    if ((rc = c->s_k.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->s_ox.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->s_ov.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->s_misc0.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->s_misc1.ensure((size_t)N * 4 * 8))) return rc;
-    if ((rc = c->s_misc2.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->s_misc3.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->s_crash.ensure((size_t)N * 4))) return rc;
-    if (oa_out && (rc = c->s_pd.ensure((size_t)N * Kalloc * 8))) return rc;
-    if (oa_out) HIPCHK(hipMemset(c->s_pd.p, 0, (size_t)N * Kalloc * 8));
-    HIPCHK(hipMemcpy(c->s_ego.p, ego4, (size_t)N * 4 * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->s_k.p, k, (size_t)N * 4, hipMemcpyHostToDevice));
-    if (Kmax > 0) {
-        HIPCHK(hipMemcpy(c->s_ox.p, ox, (size_t)N * Kmax * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->s_ov.p, ov, (size_t)N * Kmax * 8, hipMemcpyHostToDevice));
-    }
-    if (mode == 0) HIPCHK(hipMemcpy(c->s_misc0.p, sel, (size_t)N * 8, hipMemcpyHostToDevice));
-    int blocks = (N + 63) / 64;
-#define STMPC_LAUNCH_STEP(KM)                                                                                         \
-    hipLaunchKernelGGL(k_predict_step<KM>, dim3(blocks), dim3(64), 0, nullptr, dp, mode, N, Kalloc, c->s_ego.as<double>(), \
-                       c->s_k.as<int>(), c->s_ox.as<double>(), c->s_ov.as<double>(), c->s_misc0.as<double>(), dt, mcd,   \
-                       c->s_misc1.as<double>(), c->s_misc2.as<double>(), c->s_misc3.as<double>(), c->s_crash.as<int>(), \
-                       oa_out ? c->s_pd.as<double>() : (double *)nullptr)
-    if (Kalloc <= 8) STMPC_LAUNCH_STEP(8);
-    else if (Kalloc <= 16) STMPC_LAUNCH_STEP(16);
-    else STMPC_LAUNCH_STEP(32);
-#undef STMPC_LAUNCH_STEP
+    auto &s = c->s;
+    const size_t n = (size_t)N;
+    TRY(s.misc0.ensure(n * 8)); TRY(s.misc1.ensure(n * 4 * 8)); TRY(s.misc2.ensure(n * Kalloc * 8)); TRY(s.misc3.ensure(n * Kalloc * 8)); TRY(s.crash.ensure(n * 4));
+    if (oa_out) { TRY(s.pd.ensure(n * Kalloc * 8)); HIPCHK(hipMemset(s.pd.p, 0, n * Kalloc * 8)); }
+    TRY(s.states(N, Kmax, ego4, 4, k, ox, ov));
+    if (mode == 0) TRY(upload(s.misc0, sel, n));
+    with_kmax(Kalloc, [&](auto km) {
+        hipLaunchKernelGGL(k_predict_step<decltype(km)::value>, dim3((N + 63) / 64), dim3(64), 0, nullptr, dp, mode, N, Kalloc, s.ego.as<double>(), s.k.as<int>(),
+                           s.ox.as<double>(), s.ov.as<double>(), s.misc0.as<double>(), dt, mcd, s.misc1.as<double>(), s.misc2.as<double>(), s.misc3.as<double>(),
+                           s.crash.as<int>(), oa_out ? s.pd.as<double>() : (double *)nullptr);
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(ego4_out, c->s_misc1.p, (size_t)N * 4 * 8, hipMemcpyDeviceToHost));
-    if (Kmax > 0) {
-        HIPCHK(hipMemcpy(ox_out, c->s_misc2.p, (size_t)N * Kmax * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ov_out, c->s_misc3.p, (size_t)N * Kmax * 8, hipMemcpyDeviceToHost));
-    }
-    HIPCHK(hipMemcpy(crashed, c->s_crash.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (oa_out && Kmax > 0) HIPCHK(hipMemcpy(oa_out, c->s_pd.p, (size_t)N * Kmax * 8, hipMemcpyDeviceToHost));
+    TRY(download(ego4_out, s.misc1, n * 4));
+    if (Kmax > 0) { TRY(download(ox_out, s.misc2, n * Kmax)); TRY(download(ov_out, s.misc3, n * Kmax)); }
+    TRY(download(crashed, s.crash, n));
+    if (Kmax > 0) TRY(download(oa_out, s.pd, n * Kmax));
     return STMPC_OK;
 }
 
@@ -1264,18 +1285,14 @@ int stmpc_probe_arith(stmpc_ctx *c, int op, const double *a, const double *b, do
     if (!c || !a || !out || n < 0) return fail(STMPC_EINVAL, "bad argument");
     if (n == 0) return STMPC_OK;
     HIPCHK(hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->s_misc0.ensure((size_t)n * 8))) return rc;
-    if ((rc = c->s_misc1.ensure((size_t)n * 8))) return rc;
-    if ((rc = c->s_misc2.ensure((size_t)n * 8))) return rc;
-    HIPCHK(hipMemcpy(c->s_misc0.p, a, (size_t)n * 8, hipMemcpyHostToDevice));
-    if (b) HIPCHK(hipMemcpy(c->s_misc1.p, b, (size_t)n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_probe, dim3((n + 255) / 256), dim3(256), 0, nullptr, op, c->s_misc0.as<double>(),
-                       b ? c->s_misc1.as<double>() : nullptr, c->s_misc2.as<double>(), n);
+    auto &s = c->s;
+    TRY(s.misc1.ensure((size_t)n * 8)); TRY(s.misc2.ensure((size_t)n * 8));
+    TRY(upload(s.misc0, a, (size_t)n));
+    if (b) TRY(upload(s.misc1, b, (size_t)n));
+    hipLaunchKernelGGL(k_probe, dim3((n + 255) / 256), dim3(256), 0, nullptr, op, s.misc0.as<double>(), b ? s.misc1.as<double>() : nullptr, s.misc2.as<double>(), n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, c->s_misc2.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return STMPC_OK;
+    return download(out, s.misc2, (size_t)n);
 }
 
 }  // extern "C"
@@ -1329,35 +1346,22 @@ int stmpc_finer_fit_batch(stmpc_ctx *c, const stmpc_params *p, double dt, double
     for (int i = 0; i < N; ++i) if (len[i] < 1 || len[i] > Hs) return fail(STMPC_EINVAL, "len[i] outside [1, Hs]");
     FFArgs a;
     memset(&a, 0, sizeof a);
-    int rc = make_ffconst(p, dt, cdt, maxiters, &a.k);
-    if (rc) return rc;
+    TRY(make_ffconst(p, dt, cdt, maxiters, &a.k));
     HIPCHK(hipSetDevice(c->device));
-    if ((rc = c->f_seq.ensure((size_t)N * Hs * 8))) return rc;
-    if ((rc = c->f_len.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->f_v0.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->f_a0.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->f_out.ensure((size_t)N * n_max * 8))) return rc;
-    if ((rc = c->f_olen.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->f_iters.ensure((size_t)N * 4))) return rc;
-    HIPCHK(hipMemcpy(c->f_seq.p, s_seq, (size_t)N * Hs * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->f_len.p, len, (size_t)N * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->f_v0.p, v0, (size_t)N * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->f_a0.p, a0, (size_t)N * 8, hipMemcpyHostToDevice));
-    if (bac) {
-        if ((rc = c->f_bac.ensure((size_t)N * 32))) return rc;
-        HIPCHK(hipMemcpy(c->f_bac.p, bac, (size_t)N * 32, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemset(c->f_out.p, 0, (size_t)N * n_max * 8));
+    auto &s = c->s;
+    const size_t n = (size_t)N;
+    TRY(s.f_out.ensure(n * n_max * 8)); TRY(s.f_olen.ensure(n * 4)); TRY(s.f_iters.ensure(n * 4));
+    TRY(upload(s.f_seq, s_seq, n * Hs)); TRY(upload(s.f_len, len, n)); TRY(upload(s.f_v0, v0, n)); TRY(upload(s.f_a0, a0, n));
+    if (bac) TRY(upload(s.f_bac, bac, n * 4));
+    HIPCHK(hipMemset(s.f_out.p, 0, n * n_max * 8));
     a.N = N; a.Hs = Hs; a.n_max = n_max; a.use_qp = 1;
-    a.s_seq = c->f_seq.as<double>(); a.len = c->f_len.as<int>(); a.v0 = c->f_v0.as<double>(); a.a0 = c->f_a0.as<double>();
-    a.bac = bac ? c->f_bac.as<double>() : nullptr;
-    a.out = c->f_out.as<double>(); a.out_len = c->f_olen.as<int>(); a.iters = c->f_iters.as<int>();
+    a.s_seq = s.f_seq.as<double>(); a.len = s.f_len.as<int>(); a.v0 = s.f_v0.as<double>(); a.a0 = s.f_a0.as<double>();
+    a.bac = bac ? s.f_bac.as<double>() : nullptr;
+    a.out = s.f_out.as<double>(); a.out_len = s.f_olen.as<int>(); a.iters = s.f_iters.as<int>();
     launch_finer_fit(a, bac != nullptr, ff_group_width(Hs, dt, cdt), nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, c->f_out.p, (size_t)N * n_max * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_len, c->f_olen.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (iters) HIPCHK(hipMemcpy(iters, c->f_iters.p, (size_t)N * 4, hipMemcpyDeviceToHost));
+    TRY(download(out, s.f_out, n * n_max)); TRY(download(out_len, s.f_olen, n)); TRY(download(iters, s.f_iters, n));
     return STMPC_OK;
 }
 
@@ -1370,15 +1374,14 @@ static int st_control_device(stmpc_ctx *c, const stmpc_params *p, double tick, i
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (N == 0) return STMPC_OK;
     if (!d_speed) return fail(STMPC_EINVAL, "NULL device pointer (speed)");
-    int rc = stmpc_solve_batch_device(c, p, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, nullptr, nullptr, stream);
-    if (rc) return rc;
+    TRY(stmpc_solve_batch_device(c, p, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, nullptr, nullptr, stream));
     FFArgs a;
     memset(&a, 0, sizeof a);
     const int H = stmpc_num_t(p);
     double tv[STMPC_MAXH];
     host_t_values(p, H, tv);
     // finer_fit is called with (TICK_LENGTH, T_DISCRETIZATION) = the settings, not the arange spacing (st.py:771-772)
-    if ((rc = make_ffconst(p, tick, p->dt, c->qp_maxiters, &a.k))) return rc;
+    TRY(make_ffconst(p, tick, p->dt, c->qp_maxiters, &a.k));
     a.N = N; a.Hs = H; a.n_max = STMPC_QP_NMAX; a.use_qp = (tick < p->dt) ? 1 : 0;
     a.path_idx = d_path; a.best_t = d_bt; a.ego = d_ego; a.ds = p->ds;
     a.out = d_fine; a.out_len = d_fine_len; a.speed = d_speed;
@@ -1401,46 +1404,27 @@ int stmpc_st_control_batch(stmpc_ctx *c, const stmpc_params *p, double tick, int
                            const int32_t *k, const double *ox, const double *ov, double *speed, int32_t *bt,
                            int32_t *path, double *cost, double *fine, int32_t *fine_len) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "N or Kmax out of range");
+    TRY(check_batch(N, Kmax));
     if (N == 0) return STMPC_OK;
     if (!ego || !k || !speed || !bt) return fail(STMPC_EINVAL, "NULL host pointer");
     if (Kmax > 0 && (!ox || !ov)) return fail(STMPC_EINVAL, "NULL host pointer (other_x/other_v)");
-    for (int i = 0; i < N; ++i) if (k[i] < 0 || k[i] > Kmax) return fail(STMPC_EINVAL, "k_count[i] outside [0, Kmax]");
+    TRY(check_counts(N, Kmax, k));
     HIPCHK(hipSetDevice(c->device));
     const int H = stmpc_num_t(p);
     if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
-    int rc;
-    const int Kalloc = Kmax > 0 ? Kmax : 1;
-    if ((rc = c->s_ego.ensure((size_t)N * 5 * 8))) return rc;
-    if ((rc = c->s_k.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->s_ox.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->s_ov.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->s_path.ensure((size_t)N * H * 4))) return rc;
-    if ((rc = c->s_bt.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->s_cost.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->f_speed.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->f_out.ensure((size_t)N * STMPC_QP_NMAX * 8))) return rc;
-    if ((rc = c->f_olen.ensure((size_t)N * 4))) return rc;
-    HIPCHK(hipMemcpy(c->s_ego.p, ego, (size_t)N * 5 * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->s_k.p, k, (size_t)N * 4, hipMemcpyHostToDevice));
-    if (Kmax > 0) {
-        HIPCHK(hipMemcpy(c->s_ox.p, ox, (size_t)N * Kmax * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->s_ov.p, ov, (size_t)N * Kmax * 8, hipMemcpyHostToDevice));
-    }
-    if (fine) HIPCHK(hipMemset(c->f_out.p, 0, (size_t)N * STMPC_QP_NMAX * 8));
-    rc = stmpc_st_control_batch_device(c, p, tick, N, Kmax, c->s_ego.as<double>(), c->s_k.as<int32_t>(), c->s_ox.as<double>(),
-                                       c->s_ov.as<double>(), c->s_path.as<int32_t>(), c->s_bt.as<int32_t>(), c->s_cost.as<double>(),
-                                       c->f_speed.as<double>(), c->f_out.as<double>(), c->f_olen.as<int>(), nullptr);
-    if (rc) return rc;
+    auto &s = c->s;
+    const size_t n = (size_t)N;
+    TRY(s.path.ensure(n * H * 4)); TRY(s.bt.ensure(n * 4)); TRY(s.cost.ensure(n * 8));
+    TRY(s.f_speed.ensure(n * 8)); TRY(s.f_out.ensure(n * STMPC_QP_NMAX * 8)); TRY(s.f_olen.ensure(n * 4));
+    TRY(s.states(N, Kmax, ego, 5, k, ox, ov));
+    if (fine) HIPCHK(hipMemset(s.f_out.p, 0, n * STMPC_QP_NMAX * 8));
+    TRY(stmpc_st_control_batch_device(c, p, tick, N, Kmax, s.ego.as<double>(), s.k.as<int32_t>(), s.ox.as<double>(), s.ov.as<double>(), s.path.as<int32_t>(),
+                                      s.bt.as<int32_t>(), s.cost.as<double>(), s.f_speed.as<double>(), s.f_out.as<double>(), s.f_olen.as<int>(), nullptr));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(speed, c->f_speed.p, (size_t)N * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(bt, c->s_bt.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (path) HIPCHK(hipMemcpy(path, c->s_path.p, (size_t)N * H * 4, hipMemcpyDeviceToHost));
-    if (cost) HIPCHK(hipMemcpy(cost, c->s_cost.p, (size_t)N * 8, hipMemcpyDeviceToHost));
-    if (fine) HIPCHK(hipMemcpy(fine, c->f_out.p, (size_t)N * STMPC_QP_NMAX * 8, hipMemcpyDeviceToHost));
-    if (fine_len) HIPCHK(hipMemcpy(fine_len, c->f_olen.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    stmpc_stats s;
-    if ((rc = stmpc_get_stats(c, &s))) return rc;
+    TRY(download(speed, s.f_speed, n)); TRY(download(bt, s.bt, n)); TRY(download(path, s.path, n * H)); TRY(download(cost, s.cost, n));
+    TRY(download(fine, s.f_out, n * STMPC_QP_NMAX)); TRY(download(fine_len, s.f_olen, n));
+    stmpc_stats st;
+    TRY(stmpc_get_stats(c, &st));
     // (this entry is synchronous: a refused re-sampling is its own error, not left for a later stmpc_check_error)
     unsigned refused = 0;
     HIPCHK(hipMemcpy(&refused, c->sticky.as<unsigned>() + 1, sizeof refused, hipMemcpyDeviceToHost));
@@ -1466,23 +1450,24 @@ int make_ccfg(const stmpc_params *p, const stmpc_combined_cfg *g, CCfg *c) {
     if (c->rollout_length > STMPC_ROLLOUT_LIMIT) return fail(STMPC_EINVAL, "rollout_length above STMPC_ROLLOUT_LIMIT");
     return STMPC_OK;
 }
-int cc_ensure(stmpc_ctx *c, int N, int K, int R) {
-    int rc;
-    if ((rc = c->cc_live.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->cc_hist_len.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->cc_crash_pred.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->cc_have_test.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->cc_sel.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->cc_rollout_s.ensure((size_t)N * (R + 1) * 8))) return rc;
-    if ((rc = c->cc_test_ego.ensure((size_t)N * 4 * 8))) return rc;
-    if ((rc = c->cc_test_ox.ensure((size_t)N * K * 8))) return rc;
-    if ((rc = c->cc_test_ov.ensure((size_t)N * K * 8))) return rc;
-    c->cc_N = N; c->cc_K = K; c->cc_R = R;
+// the policy's state vector: checked and converted (stmpc_policy_features_device, stmpc_actor_eval_device, the environment's observation)
+int make_featcfg(const stmpc_policy_features_cfg *f, FeatCfg *fc) {
+    if (f->cars_ahead < 0 || f->cars_behind < 0 || f->cars_ahead > STMPC_KMAX_LIMIT || f->cars_behind > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "cars_ahead / cars_behind out of range");
+    if (f->normalize && (!(f->max_speed > 0) || !(f->sensor_radius > 0))) return fail(STMPC_EINVAL, "max_speed and sensor_radius must be positive");
+    memset(fc, 0, sizeof *fc);
+    fc->max_speed = f->max_speed; fc->sensor_radius = f->sensor_radius; fc->time_scale = (float)f->time_scale;
+    fc->cars_ahead = f->cars_ahead; fc->cars_behind = f->cars_behind; fc->use_accel = f->use_acceleration != 0; fc->use_speed_diff = f->use_speed_difference != 0;
+    fc->normalize = f->normalize != 0; fc->time_feature = f->time_feature != 0;
     return STMPC_OK;
 }
-CCState cc_state(stmpc_ctx *c) {
-    return CCState{c->cc_live.as<int>(), c->cc_hist_len.as<int>(), c->cc_crash_pred.as<int>(), c->cc_have_test.as<int>(), c->cc_sel.as<double>(),
-                   c->cc_rollout_s.as<double>(), c->cc_test_ego.as<double>(), c->cc_test_ox.as<double>(), c->cc_test_ov.as<double>()};
+// later rollout steps: only states whose rollout is still going on are evaluated by the reference (dqn.py:129-133); *live = NULL at step 1
+int rollout_live(const stmpc_ctx *c, int N, int step, const int **live) {
+    *live = nullptr;
+    if (step > 1) {
+        if (c->cc.N != N) return fail(STMPC_EINVAL, "step > 1 without a rollout of this size in the context (stmpc_rollout_step_device)");
+        *live = c->cc.live.as<int>();
+    }
+    return STMPC_OK;
 }
 }  // namespace
 
@@ -1498,17 +1483,16 @@ int stmpc_rollout_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_c
     if (Kmax > 0 && (!d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
     HIPCHK(hipSetDevice(c->device));
     DevP dp; CCfg cc;
-    int rc = make_devp(p, &dp);
-    if (rc) return rc;
-    if ((rc = make_ccfg(p, g, &cc))) return rc;
+    TRY(make_devp(p, &dp));
+    TRY(make_ccfg(p, g, &cc));
     const int Kalloc = Kmax > 0 ? Kmax : 1;
-    if (step == 1) { if ((rc = cc_ensure(c, N, Kalloc, cc.rollout_length))) return rc; }
-    else if (c->cc_N != N || c->cc_K != Kalloc || c->cc_R != cc.rollout_length) return fail(STMPC_EINVAL, "rollout step > 1 does not continue the rollout begun with step 1");
-    CCState st = cc_state(c);
-    const int blocks = (N + 63) / 64;
-#define STMPC_RS(KM) hipLaunchKernelGGL(k_rollout_step<KM>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dp, cc, N, Kalloc, step, d_ego5_start, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_action, st)
-    if (Kalloc <= 8) STMPC_RS(8); else if (Kalloc <= 16) STMPC_RS(16); else STMPC_RS(32);
-#undef STMPC_RS
+    if (step == 1) TRY(c->cc.ensure(N, Kalloc, cc.rollout_length));
+    else if (c->cc.N != N || c->cc.K != Kalloc || c->cc.R != cc.rollout_length) return fail(STMPC_EINVAL, "rollout step > 1 does not continue the rollout begun with step 1");
+    CCState st = c->cc.state();
+    with_kmax(Kalloc, [&](auto km) {
+        hipLaunchKernelGGL(k_rollout_step<decltype(km)::value>, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, dp, cc, N, Kalloc, step, d_ego5_start, d_cur_ego4,
+                           d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_action, st);
+    });
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
@@ -1518,24 +1502,16 @@ int stmpc_policy_features_device(stmpc_ctx *c, const stmpc_policy_features_cfg *
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (!f) return fail(STMPC_EINVAL, "features cfg is NULL");
     if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT || step < 1) return fail(STMPC_EINVAL, "N, Kmax or step out of range");
-    if (f->cars_ahead < 0 || f->cars_behind < 0 || f->cars_ahead > STMPC_KMAX_LIMIT || f->cars_behind > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "cars_ahead / cars_behind out of range");
-    const int len = stmpc_policy_features_len(f);
-    if (feat_stride < len) return fail(STMPC_EINVAL, "feat_stride is shorter than the feature vector");
-    if (f->normalize && (!(f->max_speed > 0) || !(f->sensor_radius > 0))) return fail(STMPC_EINVAL, "max_speed and sensor_radius must be positive");
+    FeatCfg fc;
+    TRY(make_featcfg(f, &fc));
+    if (feat_stride < stmpc_policy_features_len(f)) return fail(STMPC_EINVAL, "feat_stride is shorter than the feature vector");
     if (N == 0) return STMPC_OK;
     if (!d_cur_ego4 || !d_k || !d_feat) return fail(STMPC_EINVAL, "NULL device pointer");
     if (Kmax > 0 && (!d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
     if (f->time_feature && !d_evals) return fail(STMPC_EINVAL, "time_feature needs the evaluation counters");
-    const int *live = nullptr;
-    if (step > 1) {                // later rollout steps: only states whose rollout is still going on are evaluated by the reference (dqn.py:129-133)
-        if (c->cc_N != N) return fail(STMPC_EINVAL, "step > 1 without a rollout of this size in the context (stmpc_rollout_step_device)");
-        live = c->cc_live.as<int>();
-    }
+    const int *live;
+    TRY(rollout_live(c, N, step, &live));
     HIPCHK(hipSetDevice(c->device));
-    FeatCfg fc;
-    fc.max_speed = f->max_speed; fc.sensor_radius = f->sensor_radius; fc.time_scale = (float)f->time_scale;
-    fc.cars_ahead = f->cars_ahead; fc.cars_behind = f->cars_behind; fc.use_accel = f->use_acceleration != 0; fc.use_speed_diff = f->use_speed_difference != 0;
-    fc.normalize = f->normalize != 0; fc.time_feature = f->time_feature != 0;
     hipLaunchKernelGGL(k_policy_features, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, fc, N, Kmax, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live,
                        d_evals, d_feat, feat_stride);
     HIPCHK(hipGetLastError());
@@ -1571,12 +1547,7 @@ std::vector<float> pack_layer(const float *W, int rows, int cols, int rows_p, in
                 }
     return out;
 }
-int upload(DevBuf &b, const std::vector<float> &v) {
-    int rc = b.ensure(v.size() * sizeof(float));
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(b.p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-    return STMPC_OK;
-}
+int upload(DevBuf &b, const std::vector<float> &v) { return upload(b, v.data(), v.size()); }
 }  // namespace
 
 extern "C" {
@@ -1620,7 +1591,6 @@ int stmpc_actor_create(stmpc_ctx *c, int n_in, int h1, int h2, const float *w0, 
 void stmpc_actor_destroy(stmpc_actor *a) {
     if (!a) return;
     (void)hipSetDevice(a->device);
-    a->p0.release(); a->b0.release(); a->p1.release(); a->b1.release(); a->w2.release();
     delete a;
 }
 
@@ -1630,24 +1600,17 @@ int stmpc_actor_eval_device(stmpc_ctx *c, const stmpc_actor *a, const stmpc_poli
     if (!c || !a || !f) return fail(STMPC_EINVAL, "NULL argument");
     if (a->device != c->device) return fail(STMPC_EINVAL, "actor and context are on different devices");
     if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT || step < 1) return fail(STMPC_EINVAL, "N, Kmax or step out of range");
-    if (f->cars_ahead < 0 || f->cars_behind < 0 || f->cars_ahead > STMPC_KMAX_LIMIT || f->cars_behind > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "cars_ahead / cars_behind out of range");
+    FeatCfg fc;
+    TRY(make_featcfg(f, &fc));
     if (stmpc_policy_features_len(f) != a->dev.n_in) return fail(STMPC_EINVAL, "the actor's input width is not the length of this state vector");
     if (d_feat && feat_stride < a->dev.n_in) return fail(STMPC_EINVAL, "feat_stride is shorter than the feature vector");
-    if (f->normalize && (!(f->max_speed > 0) || !(f->sensor_radius > 0))) return fail(STMPC_EINVAL, "max_speed and sensor_radius must be positive");
     if (N == 0) return STMPC_OK;
     if (!d_cur_ego4 || !d_k || !d_jerk) return fail(STMPC_EINVAL, "NULL device pointer");
     if (Kmax > 0 && (!d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
     if (f->time_feature && !d_evals) return fail(STMPC_EINVAL, "time_feature needs the evaluation counters");
-    const int *live = nullptr;
-    if (step > 1) {
-        if (c->cc_N != N) return fail(STMPC_EINVAL, "step > 1 without a rollout of this size in the context (stmpc_rollout_step_device)");
-        live = c->cc_live.as<int>();
-    }
+    const int *live;
+    TRY(rollout_live(c, N, step, &live));
     HIPCHK(hipSetDevice(c->device));
-    FeatCfg fc;
-    fc.max_speed = f->max_speed; fc.sensor_radius = f->sensor_radius; fc.time_scale = (float)f->time_scale;
-    fc.cars_ahead = f->cars_ahead; fc.cars_behind = f->cars_behind; fc.use_accel = f->use_acceleration != 0; fc.use_speed_diff = f->use_speed_difference != 0;
-    fc.normalize = f->normalize != 0; fc.time_feature = f->time_feature != 0;
     hipLaunchKernelGGL(k_actor_eval, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), a->lds, (hipStream_t)stream, fc, a->dev, N, Kmax, d_cur_ego4, d_k, d_cur_ox, d_cur_ov,
                        d_cur_oa, live, d_evals, d_feat, feat_stride, d_jerk);
     HIPCHK(hipGetLastError());
@@ -1656,9 +1619,9 @@ int stmpc_actor_eval_device(stmpc_ctx *c, const stmpc_actor *a, const stmpc_poli
 
 int stmpc_combined_counts(stmpc_ctx *c, int64_t *decisions, int64_t *control_solves, int reset) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (decisions) *decisions = c->cc_ticks;
-    if (control_solves) *control_solves = c->cc_control_solves;
-    if (reset) { c->cc_ticks = 0; c->cc_control_solves = 0; }
+    if (decisions) *decisions = c->cc.ticks;
+    if (control_solves) *control_solves = c->cc.control_solves;
+    if (reset) { c->cc.ticks = 0; c->cc.control_solves = 0; }
     return STMPC_OK;
 }
 
@@ -1668,83 +1631,72 @@ int stmpc_combined_decide_device(stmpc_ctx *c, const stmpc_params *p, const stmp
                                  const int32_t *d_last_choice_rl, int32_t *d_takeover, int32_t *d_reason, double *d_speed, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (!p || !g) return fail(STMPC_EINVAL, "NULL parameter struct");
-    if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "N or Kmax out of range");
+    TRY(check_batch(N, Kmax));
     if (N == 0) return STMPC_OK;
     if (!d_ego5_start || !d_k || !d_cur_ego4 || !d_first_action || !d_takeover || !d_reason || !d_speed) return fail(STMPC_EINVAL, "NULL device pointer");
     if (Kmax > 0 && (!d_ox_start || !d_ov_start || !d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
     HIPCHK(hipSetDevice(c->device));
     CCfg cc;
-    int rc = make_ccfg(p, g, &cc);
-    if (rc) return rc;
+    TRY(make_ccfg(p, g, &cc));
     const int Kalloc = Kmax > 0 ? Kmax : 1;
-    if (c->cc_N != N || c->cc_K != Kalloc || c->cc_R != cc.rollout_length) return fail(STMPC_EINVAL, "no rollout of this shape in the context (call stmpc_rollout_step_device first)");
+    auto &b = c->cc;
+    if (b.N != N || b.K != Kalloc || b.R != cc.rollout_length) return fail(STMPC_EINVAL, "no rollout of this shape in the context (call stmpc_rollout_step_device first)");
     const int H = stmpc_num_t(p);
     if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
     hipStream_t st_ = (hipStream_t)stream;
-    if ((rc = c->cc_probe_ego.ensure((size_t)N * 5 * 8))) return rc;
-    if ((rc = c->cc_probe_ox.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->cc_probe_ov.ensure((size_t)N * Kalloc * 8))) return rc;
-    if ((rc = c->cc_path.ensure((size_t)N * H * 4))) return rc;
-    if ((rc = c->cc_bt.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->cc_cost.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->cc_pcrash.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->cc_speed.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->cc_fine.ensure((size_t)N * STMPC_QP_NMAX * 8))) return rc;
-    if ((rc = c->cc_fine_len.ensure((size_t)N * 4))) return rc;
-    CCState st = cc_state(c);
+    const size_t n = (size_t)N;
+    TRY(b.probe_ego.ensure(n * 5 * 8)); TRY(b.probe_ox.ensure(n * Kalloc * 8)); TRY(b.probe_ov.ensure(n * Kalloc * 8));
+    TRY(b.path.ensure(n * H * 4)); TRY(b.bt.ensure(n * 4)); TRY(b.cost.ensure(n * 8)); TRY(b.pcrash.ensure(n * 4));
+    TRY(b.speed.ensure(n * 8)); TRY(b.fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(b.fine_len.ensure(n * 4));
+    CCState st = b.state();
     const int blocks = (N + 63) / 64;
-    HIPCHK(hipMemsetAsync(c->cc_pcrash.p, 0, (size_t)N * 4, st_));
+    HIPCHK(hipMemsetAsync(b.pcrash.p, 0, n * 4, st_));
     // 1. feasibility probe of the rolled-out state (st.test_guaranteed_crash_from_state, dqn.py:152): one batched solve
     if (cc.test_rollout_state) {
-        hipLaunchKernelGGL(k_cc_probe_state, dim3(blocks), dim3(64), 0, st_, N, Kalloc, Kmax, d_k, d_cur_ego4, d_cur_ox, d_cur_ov, st, c->cc_probe_ego.as<double>(),
-                           c->cc_probe_ox.as<double>(), c->cc_probe_ov.as<double>());
-        if ((rc = stmpc_solve_batch_device(c, p, N, Kmax, c->cc_probe_ego.as<double>(), d_k, c->cc_probe_ox.as<double>(), c->cc_probe_ov.as<double>(),
-                                           c->cc_path.as<int32_t>(), c->cc_bt.as<int32_t>(), c->cc_cost.as<double>(), nullptr, c->cc_pcrash.as<int32_t>(), stream))) return rc;
+        hipLaunchKernelGGL(k_cc_probe_state, dim3(blocks), dim3(64), 0, st_, N, Kalloc, Kmax, d_k, d_cur_ego4, d_cur_ox, d_cur_ov, st, b.probe_ego.as<double>(),
+                           b.probe_ox.as<double>(), b.probe_ov.as<double>());
+        TRY(stmpc_solve_batch_device(c, p, N, Kmax, b.probe_ego.as<double>(), d_k, b.probe_ox.as<double>(), b.probe_ov.as<double>(), b.path.as<int32_t>(),
+                                     b.bt.as<int32_t>(), b.cost.as<double>(), nullptr, b.pcrash.as<int32_t>(), stream));
     }
     // 2. the controller on the start state (st.do_st_control; also the path of the strictly-better comparison, dqn.py:157-164)
-    HIPCHK(hipMemsetAsync(c->cc_fine.p, 0, (size_t)N * STMPC_QP_NMAX * 8, st_));
-    c->cc_ticks += N;
+    HIPCHK(hipMemsetAsync(b.fine.p, 0, n * STMPC_QP_NMAX * 8, st_));
+    b.ticks += N;
     if (g->sparse_control && !cc.strictly_better) {
         // The reference solves the start state only when a branch of dqn.py:144-155 hands control over (2-5 % of the ticks under the shipped
         // configs); here: ordered compaction of those states, ONE host round trip for their number, the controller on the compact batch, scatter.
-        if ((rc = c->cc_sel_idx.ensure((size_t)N * 4))) return rc;
-        if ((rc = c->cc_sel_count.ensure(4))) return rc;
-        if (!c->cc_host_count) HIPCHK(hipHostMalloc((void **)&c->cc_host_count, 4, hipHostMallocDefault));
-        HIPCHK(hipMemsetAsync(c->cc_speed.p, 0xFF, (size_t)N * 8, st_));            // NaN: no controller command exists for a state the policy keeps
-        HIPCHK(hipMemsetAsync(c->cc_fine_len.p, 0, (size_t)N * 4, st_));
-        hipLaunchKernelGGL(k_cc_select, dim3(1), dim3(1024), 0, st_, cc, N, st, (const int *)c->cc_pcrash.as<int>(), c->cc_sel_idx.as<int>(), c->cc_sel_count.as<int>());
-        HIPCHK(hipMemcpyAsync(c->cc_host_count, c->cc_sel_count.p, 4, hipMemcpyDeviceToHost, st_));
+        TRY(b.sel_idx.ensure(n * 4)); TRY(b.sel_count.ensure(4));
+        if (!b.host_count) HIPCHK(hipHostMalloc((void **)&b.host_count, 4, hipHostMallocDefault));
+        HIPCHK(hipMemsetAsync(b.speed.p, 0xFF, n * 8, st_));            // NaN: no controller command exists for a state the policy keeps
+        HIPCHK(hipMemsetAsync(b.fine_len.p, 0, n * 4, st_));
+        hipLaunchKernelGGL(k_cc_select, dim3(1), dim3(1024), 0, st_, cc, N, st, (const int *)b.pcrash.as<int>(), b.sel_idx.as<int>(), b.sel_count.as<int>());
+        HIPCHK(hipMemcpyAsync(b.host_count, b.sel_count.p, 4, hipMemcpyDeviceToHost, st_));
         HIPCHK(hipStreamSynchronize(st_));
-        const int M = *c->cc_host_count;
+        const int M = *b.host_count;
         if (M < 0 || M > N) return fail(STMPC_EINTERNAL, "combined controller: selection count out of range");
-        c->cc_control_solves += M;
+        b.control_solves += M;
         if (M > 0) {
-            if ((rc = c->cc_c_ego.ensure((size_t)M * 5 * 8))) return rc;
-            if ((rc = c->cc_c_k.ensure((size_t)M * 4))) return rc;
-            if ((rc = c->cc_c_ox.ensure((size_t)M * Kalloc * 8))) return rc;
-            if ((rc = c->cc_c_ov.ensure((size_t)M * Kalloc * 8))) return rc;
-            if ((rc = c->cc_c_speed.ensure((size_t)M * 8))) return rc;
-            if ((rc = c->cc_c_fine.ensure((size_t)M * STMPC_QP_NMAX * 8))) return rc;
-            if ((rc = c->cc_c_fine_len.ensure((size_t)M * 4))) return rc;
+            const size_t m = (size_t)M;
+            TRY(b.c_ego.ensure(m * 5 * 8)); TRY(b.c_k.ensure(m * 4)); TRY(b.c_ox.ensure(m * Kalloc * 8)); TRY(b.c_ov.ensure(m * Kalloc * 8));
+            TRY(b.c_speed.ensure(m * 8)); TRY(b.c_fine.ensure(m * STMPC_QP_NMAX * 8)); TRY(b.c_fine_len.ensure(m * 4));
             const int mb = (M + 63) / 64;
-            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kmax, (const int *)c->cc_sel_idx.as<int>(), d_ego5_start, d_k, d_ox_start, d_ov_start,
-                               c->cc_c_ego.as<double>(), c->cc_c_k.as<int>(), c->cc_c_ox.as<double>(), c->cc_c_ov.as<double>());
-            HIPCHK(hipMemsetAsync(c->cc_c_fine.p, 0, (size_t)M * STMPC_QP_NMAX * 8, st_));
-            if ((rc = st_control_device(c, p, g->tick_length, M, Kalloc, c->cc_c_ego.as<double>(), c->cc_c_k.as<int32_t>(), c->cc_c_ox.as<double>(), c->cc_c_ov.as<double>(),
-                                        c->cc_path.as<int32_t>(), c->cc_bt.as<int32_t>(), c->cc_cost.as<double>(), c->cc_c_speed.as<double>(), c->cc_c_fine.as<double>(),
-                                        c->cc_c_fine_len.as<int32_t>(), stream, nullptr))) return rc;
-            hipLaunchKernelGGL(k_cc_scatter, dim3(mb), dim3(64), 0, st_, M, (const int *)c->cc_sel_idx.as<int>(), (const double *)c->cc_c_speed.as<double>(),
-                               (const double *)c->cc_c_fine.as<double>(), (const int *)c->cc_c_fine_len.as<int>(), STMPC_QP_NMAX, c->cc_speed.as<double>(),
-                               c->cc_fine.as<double>(), c->cc_fine_len.as<int>());
+            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kmax, (const int *)b.sel_idx.as<int>(), d_ego5_start, d_k, d_ox_start, d_ov_start,
+                               b.c_ego.as<double>(), b.c_k.as<int>(), b.c_ox.as<double>(), b.c_ov.as<double>());
+            HIPCHK(hipMemsetAsync(b.c_fine.p, 0, m * STMPC_QP_NMAX * 8, st_));
+            TRY(st_control_device(c, p, g->tick_length, M, Kalloc, b.c_ego.as<double>(), b.c_k.as<int32_t>(), b.c_ox.as<double>(), b.c_ov.as<double>(),
+                                  b.path.as<int32_t>(), b.bt.as<int32_t>(), b.cost.as<double>(), b.c_speed.as<double>(), b.c_fine.as<double>(),
+                                  b.c_fine_len.as<int32_t>(), stream, nullptr));
+            hipLaunchKernelGGL(k_cc_scatter, dim3(mb), dim3(64), 0, st_, M, (const int *)b.sel_idx.as<int>(), (const double *)b.c_speed.as<double>(),
+                               (const double *)b.c_fine.as<double>(), (const int *)b.c_fine_len.as<int>(), STMPC_QP_NMAX, b.speed.as<double>(),
+                               b.fine.as<double>(), b.fine_len.as<int>());
         }
     } else {
-        c->cc_control_solves += N;
-        if ((rc = st_control_device(c, p, g->tick_length, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start, c->cc_path.as<int32_t>(), c->cc_bt.as<int32_t>(),
-                                    c->cc_cost.as<double>(), c->cc_speed.as<double>(), c->cc_fine.as<double>(), c->cc_fine_len.as<int32_t>(), stream, nullptr))) return rc;
+        b.control_solves += N;
+        TRY(st_control_device(c, p, g->tick_length, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start, b.path.as<int32_t>(), b.bt.as<int32_t>(),
+                              b.cost.as<double>(), b.speed.as<double>(), b.fine.as<double>(), b.fine_len.as<int32_t>(), stream, nullptr));
     }
     // 3. the decision
-    hipLaunchKernelGGL(k_cc_decide, dim3(blocks), dim3(64), 0, st_, cc, N, d_ego5_start, d_first_action, d_last_choice_rl, st, (const int *)c->cc_pcrash.as<int>(),
-                       (const double *)c->cc_speed.as<double>(), (const double *)c->cc_fine.as<double>(), (const int *)c->cc_fine_len.as<int>(), STMPC_QP_NMAX,
+    hipLaunchKernelGGL(k_cc_decide, dim3(blocks), dim3(64), 0, st_, cc, N, d_ego5_start, d_first_action, d_last_choice_rl, st, (const int *)b.pcrash.as<int>(),
+                       (const double *)b.speed.as<double>(), (const double *)b.fine.as<double>(), (const int *)b.fine_len.as<int>(), STMPC_QP_NMAX,
                        d_takeover, d_reason, d_speed, c->sticky.as<unsigned>() + 1);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -1754,23 +1706,19 @@ int stmpc_combined_read_state(stmpc_ctx *c, int N, int32_t *live, int32_t *hist_
                               int32_t *have_test, double *test_ego4, double *test_ox, double *test_ov, int32_t *probe_crash, double *st_speed,
                               double *fine, int32_t *fine_len) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->cc_N) return fail(STMPC_EINVAL, "no rollout of this size in the context");
+    const auto &b = c->cc;
+    if (N != b.N) return fail(STMPC_EINVAL, "no rollout of this size in the context");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
-    const size_t K = c->cc_K, R1 = c->cc_R + 1;
-    if (live) HIPCHK(hipMemcpy(live, c->cc_live.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (hist_len) HIPCHK(hipMemcpy(hist_len, c->cc_hist_len.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (crash_pred) HIPCHK(hipMemcpy(crash_pred, c->cc_crash_pred.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (sel_speed) HIPCHK(hipMemcpy(sel_speed, c->cc_sel.p, (size_t)N * 8, hipMemcpyDeviceToHost));
-    if (rollout_s) HIPCHK(hipMemcpy(rollout_s, c->cc_rollout_s.p, (size_t)N * R1 * 8, hipMemcpyDeviceToHost));
-    if (have_test) HIPCHK(hipMemcpy(have_test, c->cc_have_test.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (test_ego4) HIPCHK(hipMemcpy(test_ego4, c->cc_test_ego.p, (size_t)N * 4 * 8, hipMemcpyDeviceToHost));
-    if (test_ox) HIPCHK(hipMemcpy(test_ox, c->cc_test_ox.p, (size_t)N * K * 8, hipMemcpyDeviceToHost));
-    if (test_ov) HIPCHK(hipMemcpy(test_ov, c->cc_test_ov.p, (size_t)N * K * 8, hipMemcpyDeviceToHost));
-    if (probe_crash && c->cc_pcrash.p) HIPCHK(hipMemcpy(probe_crash, c->cc_pcrash.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (st_speed && c->cc_speed.p) HIPCHK(hipMemcpy(st_speed, c->cc_speed.p, (size_t)N * 8, hipMemcpyDeviceToHost));
-    if (fine && c->cc_fine.p) HIPCHK(hipMemcpy(fine, c->cc_fine.p, (size_t)N * STMPC_QP_NMAX * 8, hipMemcpyDeviceToHost));
-    if (fine_len && c->cc_fine_len.p) HIPCHK(hipMemcpy(fine_len, c->cc_fine_len.p, (size_t)N * 4, hipMemcpyDeviceToHost));
+    const size_t n = (size_t)N, K = b.K, R1 = b.R + 1;
+    TRY(download(live, b.live, n)); TRY(download(hist_len, b.hist_len, n)); TRY(download(crash_pred, b.crash_pred, n)); TRY(download(sel_speed, b.sel, n));
+    TRY(download(rollout_s, b.rollout_s, n * R1)); TRY(download(have_test, b.have_test, n)); TRY(download(test_ego4, b.test_ego, n * 4));
+    TRY(download(test_ox, b.test_ox, n * K)); TRY(download(test_ov, b.test_ov, n * K));
+    // (the decision's buffers exist once stmpc_combined_decide_device has run)
+    if (b.pcrash.p) TRY(download(probe_crash, b.pcrash, n));
+    if (b.speed.p) TRY(download(st_speed, b.speed, n));
+    if (b.fine.p) TRY(download(fine, b.fine, n * STMPC_QP_NMAX));
+    if (b.fine_len.p) TRY(download(fine_len, b.fine_len, n));
     return stmpc_check_error(c);         // (device already synchronised: just the flags)
 }
 
@@ -1785,36 +1733,28 @@ int stmpc_solve_grid_no_jerk(stmpc_ctx *c, int variant, const uint8_t *obstacles
     if (t_values[1] - t_values[0] == 0.0) return fail(STMPC_EINVAL, "float division by zero (delta_t == 0)");
     if (s_values[1] - s_values[0] == 0.0) return fail(STMPC_EINVAL, "float division by zero (delta_s == 0)");
     HIPCHK(hipSetDevice(c->device));
-    int rc;
+    auto &s = c->s;
     const size_t cells = (size_t)H * S, states = variant ? cells * S : cells;
     size_t cap = states * 8;
     if (cap < ((size_t)1 << 20)) cap = (size_t)1 << 20;
     if (cap > ((size_t)1 << 25)) cap = (size_t)1 << 25;               // 32 M entries = 768 MB at most
-    if ((rc = c->s_misc0.ensure(cells))) return rc;
-    if ((rc = c->s_misc1.ensure(cells * 8))) return rc;
-    if ((rc = c->s_misc2.ensure((size_t)S * 8))) return rc;
-    if ((rc = c->s_misc3.ensure((size_t)H * 8 + 16))) return rc;
-    if ((rc = c->s_pd.ensure(states))) return rc;
-    if ((rc = c->s_path.ensure(states * 4))) return rc;
-    if ((rc = c->gscratch.ensure(cap * sizeof(NjItem)))) return rc;
-    HIPCHK(hipMemcpy(c->s_misc0.p, obstacles, cells, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->s_misc1.p, distances, cells * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->s_misc2.p, s_values, (size_t)S * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(c->s_pd.p, 0, states));
-    HIPCHK(hipMemset(c->s_path.p, 0, states * 4));
+    TRY(s.misc3.ensure((size_t)H * 8 + 16)); TRY(s.pd.ensure(states)); TRY(s.path.ensure(states * 4)); TRY(c->gscratch.ensure(cap * sizeof(NjItem)));
+    TRY(upload(s.misc0, obstacles, cells)); TRY(upload(s.misc1, distances, cells)); TRY(upload(s.misc2, s_values, (size_t)S));
+    HIPCHK(hipMemset(s.pd.p, 0, states));
+    HIPCHK(hipMemset(s.path.p, 0, states * 4));
     NjArgs a;
     memset(&a, 0, sizeof a);
     a.triple = variant; a.S = S; a.H = H; a.v0 = ego_start_speed;
-    a.obstacles = c->s_misc0.as<uint8_t>(); a.distances = c->s_misc1.as<double>(); a.s_values = c->s_misc2.as<double>();
+    a.obstacles = s.misc0.as<uint8_t>(); a.distances = s.misc1.as<double>(); a.s_values = s.misc2.as<double>();
     a.dt = t_values[1] - t_values[0];
-    a.enc = c->s_pd.as<uint8_t>(); a.prev = c->s_path.as<int>(); a.heap = c->gscratch.as<NjItem>(); a.cap = cap;
-    a.s_sequence = c->s_misc3.as<double>(); a.status = (int *)(c->s_misc3.as<double>() + H);
+    a.enc = s.pd.as<uint8_t>(); a.prev = s.path.as<int>(); a.heap = c->gscratch.as<NjItem>(); a.cap = cap;
+    a.s_sequence = s.misc3.as<double>(); a.status = (int *)(s.misc3.as<double>() + H);
     hipLaunchKernelGGL(k_nojerk, dim3(1), dim3(64), 0, nullptr, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     int status = 0;
-    HIPCHK(hipMemcpy(s_sequence_out, c->s_misc3.p, (size_t)H * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&status, (char *)c->s_misc3.p + (size_t)H * 8, 4, hipMemcpyDeviceToHost));
+    TRY(download(s_sequence_out, s.misc3, (size_t)H));
+    HIPCHK(hipMemcpy(&status, (char *)s.misc3.p + (size_t)H * 8, 4, hipMemcpyDeviceToHost));
     if (status == 1) return fail(STMPC_ENOMEM, "no-jerk solver: heap capacity exceeded");
     if (status == 2) return fail(STMPC_EINVAL, "index out of bounds: the first layer's reachable cells leave the grid (IndexError in the reference)");
     return STMPC_OK;
@@ -1842,11 +1782,7 @@ int make_simcfg(const stmpc_sim_cfg *g, sim::Cfg *c) {
     return STMPC_OK;
 }
 void sim_route_of(stmpc_ctx *c, sim::Cfg *sc) {
-    if (c->sim_route_n >= 2) { sc->route = c->sim_route.as<double>(); sc->route_n = c->sim_route_n; }
-}
-sim::State sim_state(stmpc_ctx *c) {
-    return sim::State{c->sim_ego.as<double>(), c->sim_nveh.as<int>(), c->sim_vx.as<double>(), c->sim_vv.as<double>(), c->sim_va.as<double>(), c->sim_vc.as<double>(), c->sim_delay.as<double>(),
-                      c->sim_status.as<int>(), c->sim_ticks.as<int>(), c->sim_rng.as<unsigned>(), c->sim_acc.as<double>()};
+    if (c->sim.route_n >= 2) { sc->route = c->sim.route.as<double>(); sc->route_n = c->sim.route_n; }
 }
 }  // namespace
 
@@ -1856,24 +1792,12 @@ int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *str
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
     sim::Cfg sc;
-    int rc = make_simcfg(g, &sc);
-    if (rc) return rc;
+    TRY(make_simcfg(g, &sc));
     HIPCHK(hipSetDevice(c->device));
-    const size_t KS = sim::KS;
-    if ((rc = c->sim_ego.ensure((size_t)N * 4 * 8))) return rc;
-    if ((rc = c->sim_nveh.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->sim_vx.ensure((size_t)N * KS * 8))) return rc;
-    if ((rc = c->sim_vv.ensure((size_t)N * KS * 8))) return rc;
-    if ((rc = c->sim_va.ensure((size_t)N * KS * 8))) return rc;
-    if ((rc = c->sim_vc.ensure((size_t)N * KS * 8))) return rc;
-    if ((rc = c->sim_delay.ensure((size_t)N * 8))) return rc;
-    if ((rc = c->sim_status.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->sim_ticks.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->sim_rng.ensure((size_t)N * 4))) return rc;
-    if ((rc = c->sim_acc.ensure((size_t)N * sim::NACC * 8))) return rc;
-    c->sim_N = N;
-    c->env_N = 0;                  // (the vector environment's bookkeeping no longer describes this world; stmpc_env_reset_device sets it again)
-    c->sim_route_n = 0;
+    TRY(c->sim.ensure(N));
+    c->sim.N = N;
+    c->env.N = 0;                  // (the vector environment's bookkeeping no longer describes this world; stmpc_env_reset_device sets it again)
+    c->sim.route_n = 0;
     if (g->ego_route_xy && g->ego_route_n >= 2) {
         const int n = g->ego_route_n;
         if (n > 4096) return fail(STMPC_EINVAL, "ego_route_n out of range (at most 4096 points)");
@@ -1882,63 +1806,60 @@ int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *str
             xy[i] = g->ego_route_xy[2 * i]; xy[n + i] = g->ego_route_xy[2 * i + 1];
             if (i && !(xy[i] > xy[i - 1])) return fail(STMPC_EINVAL, "ego_route_xy: x must be strictly increasing");
         }
-        if ((rc = c->sim_route.ensure(xy.size() * 8))) return rc;
-        HIPCHK(hipMemcpyAsync(c->sim_route.p, xy.data(), xy.size() * 8, hipMemcpyHostToDevice, (hipStream_t)stream));
+        TRY(c->sim.route.ensure(xy.size() * 8));
+        HIPCHK(hipMemcpyAsync(c->sim.route.p, xy.data(), xy.size() * 8, hipMemcpyHostToDevice, (hipStream_t)stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));       // (xy is a local)
-        c->sim_route_n = n;
+        c->sim.route_n = n;
     }
     sim_route_of(c, &sc);
-    hipLaunchKernelGGL(sim::k_sim_init, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, sc, N, sim_state(c));
+    hipLaunchKernelGGL(sim::k_sim_init, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, sc, N, c->sim.state());
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
 int stmpc_sim_view_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, int Kmax, double *d_ego5, int32_t *d_k, double *d_ox, double *d_ov, double *d_oa, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->sim_N || Kmax < 1 || Kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or Kmax out of range");
+    if (N != c->sim.N || Kmax < 1 || Kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or Kmax out of range");
     if (!d_ego5 || !d_k || !d_ox || !d_ov) return fail(STMPC_EINVAL, "NULL device pointer");
     sim::Cfg sc;
-    int rc = make_simcfg(g, &sc);
-    if (rc) return rc;
+    TRY(make_simcfg(g, &sc));
     sim_route_of(c, &sc);
     HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(sim::k_sim_view, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, sc, N, Kmax, sim_state(c), d_ego5, d_k, d_ox, d_ov, d_oa);
+    hipLaunchKernelGGL(sim::k_sim_view, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, sc, N, Kmax, c->sim.state(), d_ego5, d_k, d_ox, d_ov, d_oa);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
 int stmpc_sim_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, int N, const double *d_cmd_speed, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->sim_N || !d_cmd_speed) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or NULL device pointer");
+    if (N != c->sim.N || !d_cmd_speed) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or NULL device pointer");
     sim::Cfg sc;
     DevP dp;
-    int rc = make_simcfg(g, &sc);
-    if (rc) return rc;
+    TRY(make_simcfg(g, &sc));
     sim_route_of(c, &sc);
-    if ((rc = make_devp(p, &dp))) return rc;
+    TRY(make_devp(p, &dp));
     HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(sim::k_sim_step, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, dp, sc, N, sim_state(c), d_cmd_speed, p->crash_min_s);
+    hipLaunchKernelGGL(sim::k_sim_step, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, dp, sc, N, c->sim.state(), d_cmd_speed, p->crash_min_s);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
 int stmpc_sim_status_device(stmpc_ctx *c, int N, int32_t *d_status, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->sim_N || !d_status) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or NULL pointer");
+    if (N != c->sim.N || !d_status) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or NULL pointer");
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(d_status, c->sim_status.p, (size_t)N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(d_status, c->sim.status.p, (size_t)N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return STMPC_OK;
 }
 
 int stmpc_sim_read(stmpc_ctx *c, int N, int32_t *status, int32_t *ticks, double *acc, double *ego4) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->sim_N) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device");
+    if (N != c->sim.N) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
-    if (status) HIPCHK(hipMemcpy(status, c->sim_status.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (ticks) HIPCHK(hipMemcpy(ticks, c->sim_ticks.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (acc) HIPCHK(hipMemcpy(acc, c->sim_acc.p, (size_t)N * sim::NACC * 8, hipMemcpyDeviceToHost));
-    if (ego4) HIPCHK(hipMemcpy(ego4, c->sim_ego.p, (size_t)N * 32, hipMemcpyDeviceToHost));
+    const size_t n = (size_t)N;
+    TRY(download(status, c->sim.status, n)); TRY(download(ticks, c->sim.ticks, n)); TRY(download(acc, c->sim.acc, n * sim::NACC));
+    TRY(download(ego4, c->sim.ego, n * 4));
     return STMPC_OK;
 }
 
@@ -1951,8 +1872,8 @@ int make_envcfg(const stmpc_env_cfg *g, env::ECfg *c) {
     if (!g->features) return fail(STMPC_EINVAL, "env cfg: features is NULL");
     const stmpc_policy_features_cfg *f = g->features;
     if (f->time_feature) return fail(STMPC_EINVAL, "env cfg: the observation has no time feature (TimeFeature wraps the agent, not the env)");
-    if (f->cars_ahead < 0 || f->cars_behind < 0 || f->cars_ahead > STMPC_KMAX_LIMIT || f->cars_behind > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "cars_ahead / cars_behind out of range");
-    if (f->normalize && (!(f->max_speed > 0) || !(f->sensor_radius > 0))) return fail(STMPC_EINVAL, "max_speed and sensor_radius must be positive");
+    FeatCfg fc;
+    TRY(make_featcfg(f, &fc));
     if (g->action_mode < STMPC_ENV_CONTINUOUS_JERK || g->action_mode > STMPC_ENV_ACCELERATION) return fail(STMPC_EINVAL, "env cfg: unknown action_mode");
     if (g->reward_function < STMPC_REWARD_CONTINUOUS || g->reward_function > STMPC_REWARD_ST) return fail(STMPC_EINVAL, "env cfg: unknown reward_function");
     if (!(g->tick_length > 0)) return fail(STMPC_EINVAL, "env cfg: tick_length must be positive");
@@ -1964,17 +1885,11 @@ int make_envcfg(const stmpc_env_cfg *g, env::ECfg *c) {
     c->penalty = g->invalid_action_penalty; c->j_min = g->minimum_negative_jerk; c->j_max = g->maximum_positive_jerk;
     c->a_min = g->max_negative_acceleration; c->a_max = g->max_positive_acceleration; c->v_max = g->max_speed;
     c->mode = g->action_mode; c->reward = g->reward_function; c->autoreset = g->autoreset != 0;
-    c->f.max_speed = f->max_speed; c->f.sensor_radius = f->sensor_radius; c->f.time_scale = (float)f->time_scale;
-    c->f.cars_ahead = f->cars_ahead; c->f.cars_behind = f->cars_behind; c->f.use_accel = f->use_acceleration != 0; c->f.use_speed_diff = f->use_speed_difference != 0;
-    c->f.normalize = f->normalize != 0; c->f.time_feature = 0;
+    c->f = fc;                                   // (time_feature = 0: refused above)
     c->obs_len = stmpc_policy_features_len(f);
     return STMPC_OK;
 }
-env::EState env_state(stmpc_ctx *c) {
-    return env::EState{c->env_ep.as<int>(), c->env_prev_a.as<double>(), c->env_pjerk.as<double>(), c->env_inv.as<double>(), c->env_ret.as<double>(),
-                       c->env_cmd.as<double>(), c->env_live.as<int>(), c->env_vx.as<double>(), c->env_vv.as<double>(), c->env_va.as<double>(), c->env_k.as<int>(),
-                       c->env_log.as<double>(), c->env_log_n.as<unsigned>(), c->sticky.as<unsigned>() + 2};
-}
+env::EState env_state(stmpc_ctx *c) { return c->env.state(c->sticky.as<unsigned>() + 2); }
 }  // namespace
 
 extern "C" {
@@ -1985,36 +1900,30 @@ int stmpc_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (!p) return fail(STMPC_EINVAL, "params is NULL");
     env::ECfg e;
-    int rc = make_envcfg(ec, &e);
-    if (rc) return rc;
+    TRY(make_envcfg(ec, &e));
     if (d_obs && obs_stride < e.obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
     if (ec->action_mode != STMPC_ENV_CONTINUOUS_JERK && (!ec->action_values || ec->n_action_values < 1 || ec->n_action_values > STMPC_ENV_MAX_ACTIONS))
         return fail(STMPC_EINVAL, "a discrete env needs 1..STMPC_ENV_MAX_ACTIONS action_values");
     if (ec->log_capacity < 0) return fail(STMPC_EINVAL, "log_capacity must not be negative");
-    if ((rc = stmpc_sim_init_device(c, g, N, stream))) return rc;
-    const size_t n = (size_t)N, KS = sim::KS;
-    if ((rc = c->env_ep.ensure(n * 4)) || (rc = c->env_prev_a.ensure(n * 8)) || (rc = c->env_pjerk.ensure(n * 8)) || (rc = c->env_inv.ensure(n * 8)) ||
-        (rc = c->env_ret.ensure(n * 8)) || (rc = c->env_cmd.ensure(n * 8)) || (rc = c->env_live.ensure(n * 4)) || (rc = c->env_vx.ensure(n * KS * 8)) ||
-        (rc = c->env_vv.ensure(n * KS * 8)) || (rc = c->env_va.ensure(n * KS * 8)) || (rc = c->env_k.ensure(n * 4)) || (rc = c->env_log_n.ensure(4)))
-        return rc;
+    TRY(stmpc_sim_init_device(c, g, N, stream));
+    auto &v = c->env;
     const int cap = ec->log_capacity ? ec->log_capacity : 16 * N;
-    if ((rc = c->env_log.ensure((size_t)cap * env::NLOG * 8))) return rc;
-    c->env_log_cap = cap;
-    c->env_n_actions = 0;
+    TRY(v.ensure(N, cap));
+    v.n_actions = 0;
     if (ec->action_mode != STMPC_ENV_CONTINUOUS_JERK) {
-        if ((rc = c->env_actions.ensure((size_t)ec->n_action_values * 8))) return rc;
-        HIPCHK(hipMemcpyAsync(c->env_actions.p, ec->action_values, (size_t)ec->n_action_values * 8, hipMemcpyHostToDevice, (hipStream_t)stream));
+        TRY(v.actions.ensure((size_t)ec->n_action_values * 8));
+        HIPCHK(hipMemcpyAsync(v.actions.p, ec->action_values, (size_t)ec->n_action_values * 8, hipMemcpyHostToDevice, (hipStream_t)stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));       // (the table is the caller's host memory)
-        c->env_n_actions = ec->n_action_values;
+        v.n_actions = ec->n_action_values;
     }
-    HIPCHK(hipMemsetAsync(c->env_log_n.p, 0, 4, (hipStream_t)stream));
-    c->env_N = N;
-    c->env_mode = ec->action_mode;
+    HIPCHK(hipMemsetAsync(v.log_n.p, 0, 4, (hipStream_t)stream));
+    v.N = N;
+    v.mode = ec->action_mode;
     sim::Cfg sc;
-    if ((rc = make_simcfg(g, &sc))) return rc;
+    TRY(make_simcfg(g, &sc));
     sim_route_of(c, &sc);
-    e.seed = sc.seed; e.log_cap = cap; e.n_actions = c->env_n_actions; e.actions = c->env_actions.as<double>();
-    hipLaunchKernelGGL(env::k_env_reset, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, sc, N, sim_state(c), env_state(c), d_obs, obs_stride);
+    e.seed = sc.seed; e.log_cap = cap; e.n_actions = v.n_actions; e.actions = v.actions.as<double>();
+    hipLaunchKernelGGL(env::k_env_reset, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, sc, N, c->sim.state(), env_state(c), d_obs, obs_stride);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
@@ -2022,22 +1931,21 @@ int stmpc_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_
 int stmpc_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
                           double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->env_N || N != c->sim_N || N < 1) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device");
+    if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device");
     if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     env::ECfg e;
     sim::Cfg sc;
     DevP dp;
-    int rc = make_envcfg(ec, &e);
-    if (rc) return rc;
+    TRY(make_envcfg(ec, &e));
     if (obs_stride < e.obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
-    if (e.mode != c->env_mode) return fail(STMPC_EINVAL, "env_cfg.action_mode differs from the one the context was reset with (stmpc_env_reset_device)");
-    if ((rc = make_simcfg(g, &sc))) return rc;
+    if (e.mode != c->env.mode) return fail(STMPC_EINVAL, "env_cfg.action_mode differs from the one the context was reset with (stmpc_env_reset_device)");
+    TRY(make_simcfg(g, &sc));
     sim_route_of(c, &sc);
-    if ((rc = make_devp(p, &dp))) return rc;
-    e.seed = sc.seed; e.log_cap = c->env_log_cap; e.n_actions = c->env_n_actions; e.actions = c->env_actions.as<double>();
+    TRY(make_devp(p, &dp));
+    e.seed = sc.seed; e.log_cap = c->env.log_cap; e.n_actions = c->env.n_actions; e.actions = c->env.actions.as<double>();
     HIPCHK(hipSetDevice(c->device));
     const dim3 grid((N + 63) / 64), block(64);
-    const sim::State s = sim_state(c);
+    const sim::State s = c->sim.state();
     const env::EState es = env_state(c);
     hipLaunchKernelGGL(env::k_env_act, grid, block, 0, (hipStream_t)stream, e, N, s, es, d_action);
     hipLaunchKernelGGL(sim::k_sim_step, grid, block, 0, (hipStream_t)stream, dp, sc, N, s, (const double *)es.cmd, p->crash_min_s);
@@ -2051,8 +1959,7 @@ int stmpc_env_reward_device(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, int Km
     (void)d_ov; (void)d_oa;        // (no reward function reads the other vehicles' speeds or accelerations)
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     env::ECfg e;
-    int rc = make_envcfg(ec, &e);
-    if (rc) return rc;
+    TRY(make_envcfg(ec, &e));
     if (N < 0 || Kmax < 0 || Kmax > sim::KS) return fail(STMPC_EINVAL, "N or Kmax out of range (Kmax <= 64)");
     if (N == 0) return STMPC_OK;
     if (!d_ego4 || !d_k || !d_jerk || !d_reward || (Kmax > 0 && !d_ox)) return fail(STMPC_EINVAL, "NULL device pointer");
@@ -2065,15 +1972,15 @@ int stmpc_env_reward_device(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, int Km
 int stmpc_env_drain(stmpc_ctx *c, int max_rows, double *rows, int64_t *n_rows, int64_t *n_dropped) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (!n_rows || (max_rows > 0 && !rows)) return fail(STMPC_EINVAL, "NULL host pointer");
-    if (c->env_N < 1) return fail(STMPC_EINVAL, "no environment in this context (stmpc_env_reset_device)");
+    if (c->env.N < 1) return fail(STMPC_EINVAL, "no environment in this context (stmpc_env_reset_device)");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
     unsigned cnt = 0;
-    HIPCHK(hipMemcpy(&cnt, c->env_log_n.p, 4, hipMemcpyDeviceToHost));
-    const int64_t kept = cnt < (unsigned)c->env_log_cap ? (int64_t)cnt : (int64_t)c->env_log_cap;
+    TRY(download(&cnt, c->env.log_n, 1));
+    const int64_t kept = cnt < (unsigned)c->env.log_cap ? (int64_t)cnt : (int64_t)c->env.log_cap;
     const int64_t take = kept < (int64_t)(max_rows > 0 ? max_rows : 0) ? kept : (int64_t)(max_rows > 0 ? max_rows : 0);
-    if (take) HIPCHK(hipMemcpy(rows, c->env_log.p, (size_t)take * env::NLOG * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(c->env_log_n.p, 0, 4));
+    if (take) TRY(download(rows, c->env.log, (size_t)take * env::NLOG));
+    HIPCHK(hipMemset(c->env.log_n.p, 0, 4));
     *n_rows = take;
     if (n_dropped) *n_dropped = (int64_t)cnt - take;
     return STMPC_OK;
@@ -2081,9 +1988,9 @@ int stmpc_env_drain(stmpc_ctx *c, int max_rows, double *rows, int64_t *n_rows, i
 
 int stmpc_env_episode_ticks_device(stmpc_ctx *c, int N, int32_t *d_ticks, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->env_N || N < 1 || !d_ticks) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device, or NULL pointer");
+    if (N != c->env.N || N < 1 || !d_ticks) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device, or NULL pointer");
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(d_ticks, c->sim_ticks.p, (size_t)N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(d_ticks, c->sim.ticks.p, (size_t)N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return STMPC_OK;
 }
 
@@ -2094,7 +2001,7 @@ struct stmpc_ddpg {
     int device = 0;
     stmpc_ddpg_cfg cfg{};
     DdpgDev dev{};
-    DevBuf netbuf[2][13], ring, cnt, tick, ws[7], stage;
+    DevBuf netbuf[2][13], ring, cnt, tick, ws[7];
     int h1p = 0, h2p = 0, np = 0, Bp = 0;
     size_t lds = 0;
     int n_in(int which) const { return cfg.n_obs + 1 + which; }
@@ -2103,8 +2010,7 @@ struct stmpc_ddpg {
 
 namespace {
 int ddpg_zero(DevBuf &b, size_t bytes) {
-    int rc = b.ensure(bytes);
-    if (rc) return rc;
+    TRY(b.ensure(bytes));
     HIPCHK(hipMemset(b.p, 0, bytes));
     return STMPC_OK;
 }
@@ -2194,9 +2100,6 @@ int stmpc_ddpg_create(stmpc_ctx *c, const stmpc_ddpg_cfg *g, stmpc_ddpg **out) {
 void stmpc_ddpg_destroy(stmpc_ddpg *l) {
     if (!l) return;
     (void)hipSetDevice(l->device);
-    for (auto &row : l->netbuf) for (auto &b : row) b.release();
-    for (auto &b : l->ws) b.release();
-    l->ring.release(); l->cnt.release(); l->tick.release(); l->stage.release();
     delete l;
 }
 

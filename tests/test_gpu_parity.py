@@ -698,3 +698,49 @@ def test_narrow_lattice_side_launch_follows_the_previous_batch(restore_settings,
     _check(half, {k_: v_[:700] for k_, v_ in ref.items()}, _capi.num_t(p))
     _check(st.solve_arrays(ego, kc, ox, ov, p, ctx), ref, _capi.num_t(p))
     ctx.close()
+
+
+def test_context_actor_learner_free_their_device_memory(restore_settings):
+    """Nine cycles of a context's life (a solve at N = 4096, an actor, an env reset and step, a DDPG learner, then close) through the C-ABI:
+    after one warm-up cycle, the eight that follow give back their device memory -- together they lose less than a quarter of one cycle's
+    footprint (the drop in free memory while its objects are alive); a buffer that one of the destroy calls missed would lose about eight."""
+    import torch
+    import rl_mpc_lanemerging_amd as pkg
+    from rl_mpc_lanemerging_amd import _capi, episodes, synth, vec_env
+    S = pkg.Settings
+    p, n, n_env = _capi.Params.from_settings(S), 4096, 1024
+    ego, kc, ox, ov = synth.generate_states(n, k=6, kmax=8, seed=1000)
+    sim, env = episodes.sim_cfg(0, float(S.MAX_EPISODE_LENGTH)), vec_env.env_cfg("sumo-jerk-continuous-v0", "Continuous", True, S)
+    n_obs = (4 if S.USE_ACCELERATION_OF_OTHER_CARS else 3) * (S.CARS_AHEAD + S.CARS_BEHIND) + 4
+    rng = np.random.default_rng(0)
+    w = dict(w0=rng.normal(size=(64, n_obs)), b0=np.zeros(64), w1=rng.normal(size=(64, 64)), b1=np.zeros(64), w2=rng.normal(size=64), b2=np.zeros(1),
+             tanh_scale=1.0, tanh_mean=0.0)
+    ddpg = _capi.DDPGCfg(n_obs=n_obs, h1=400, h2=300, batch=100, capacity=100000, replay_start=1000, seed=1, gamma=0.99, tau=0.005, beta1=0.9, beta2=0.999,
+                         eps=1e-8, time_scale=0.001, tanh_scale=1.0, tanh_mean=0.0, noise_std=0.1, action_low=-1.0, action_high=1.0)
+    z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device="cuda")
+    obs, action, reward, term, trunc = z(n_env, n_obs, dtype=torch.float32), z(n_env), z(n_env), z(n_env, dtype=torch.uint8), z(n_env, dtype=torch.uint8)
+
+    def cycle():
+        ctx = _capi.Context(0)
+        ctx.solve_batch(p, ego, kc, ox, ov)
+        ctx.actor_destroy(ctx.actor_create(w))
+        ctx.env_reset(p, sim, env, n_env, obs.data_ptr(), n_obs)
+        ctx.env_step(p, sim, env, n_env, action.data_ptr(), obs.data_ptr(), n_obs, reward.data_ptr(), term.data_ptr(), trunc.data_ptr())
+        learner = ctx.ddpg_create(ddpg)
+        torch.cuda.synchronize()
+        alive = torch.cuda.mem_get_info()[0]
+        ctx.ddpg_destroy(learner)
+        ctx.close()
+        return alive
+
+    cycle()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    footprint = free0 - cycle()
+    for _ in range(7):
+        cycle()
+    torch.cuda.synchronize()
+    lost = free0 - torch.cuda.mem_get_info()[0]
+    print("footprint %d bytes, lost over 8 cycles %d bytes" % (footprint, lost))
+    assert footprint > 0
+    assert lost < footprint / 4
