@@ -20,7 +20,10 @@
  *   stmpc_actor_eval_device   <- DDPGAgent.get_control                ddpg.py:83-87 (state vector + the pretrained policy network, one launch)
  *   stmpc_env_*               <- merge_gym.JerkEnv / ContinuousJerkEnv / AccelerationEnv  merge_gym.py:15-221 with the rewards of
  *                                dqn.get_reward_function (dqn.py:449-563, rl.py:168-174), batched on the SUMO-free world (stmpc_sim_*)
- *   stmpc_ego_s               <- control.get_ego_s                   control.py:373-380
+ *   stmpc_rec_*               <- the per-tick histories of control.run_episode (control.py:247-254, 280-289), the position bins of
+ *                                stats.StatsAggregator (stats.py:33-52) and RLAgent.plot_st_proportion (dqn.py:101-115, 215-226), and the
+ *                                crash dump of st.evaluate_st_and_dump_crash (st.py:822-824, stats.py:75-77)
+ *   stmpc_ego_s               <- control.get_ego_s                  control.py:373-380
  *   stmpc_num_s / stmpc_num_t <- the np.arange sizes at st.py:31-32
  *
  * Plain pointers and sizes only; no torch / numpy types.  All floating point is
@@ -606,6 +609,53 @@ int  stmpc_ddpg_replay_read(stmpc_ddpg *learner, int64_t first, int64_t count, f
 int  stmpc_ddpg_gather_device(stmpc_ddpg *learner, float *d_rows, void *stream);
 uint64_t stmpc_ddpg_sample_index(uint64_t seed, uint64_t update, uint32_t row, uint64_t fill);
 double stmpc_ddpg_noise(uint64_t seed, uint64_t call, uint32_t row, uint32_t *draw1, uint32_t *draw2);
+
+/*
+ * Episode flight recorder on the device, next to the world (stmpc_sim_*): the per-tick histories the reference's evaluation keeps and what it
+ * bins over the ego's position, for N environments in lock-step, with nothing crossing to the host until it is read.  (Additive: new entries
+ * only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)
+ *   stmpc_rec_create / destroy / reset   <- the history lists of control.run_episode (control.py:247-254) and StatsAggregator.__init__'s
+ *                           bins / counts / jerks / speeds (stats.py:33-41).  N environments, Kmax view slots, a ring of `depth` (1 ...
+ *                           STMPC_REC_MAX_DEPTH) records per environment, n_edges (2 ... STMPC_REC_MAX_EDGES) finite, strictly increasing bin edges
+ *                           (HOST pointer, copied; the reference's are np.arange(-220, 61, 20)), tick_length = Settings.TICK_LENGTH.  The recorder follows
+ *                           ONE episode per environment of the context's world as it is at create / reset: after another stmpc_sim_init_device on the
+ *                           context every entry returns STMPC_EINVAL until stmpc_rec_reset (which needs the world's N to be the recorder's and zeroes
+ *                           everything; asynchronous on `stream`).  The per-environment resets of the vector environment (stmpc_env_step_device with
+ *                           autoreset) are not followed.  Destroy the recorder before its context.
+ *   stmpc_rec_tick_device <- state_history.append / position_history / speed_history / acceleration_history / jerk_history of control.py:280-289 and
+ *                           takeover_history of dqn.py:144-200, plus add_episode_stats' binning (stats.py:44-52) and combined_stats_callback /
+ *                           plot_st_proportion (dqn.py:101-115, 215-226).  Call it once per world tick, between the controller and
+ *                           stmpc_sim_step_device, with the view arrays the controller consumed (the state BEFORE control, as the reference appends
+ *                           it) and the commanded speeds; d_oa and d_takeover (int32 [N]) may be NULL (recorded as 0).  For every environment whose
+ *                           status is 0: one record into ring slot (world tick mod depth) and the tick added to the environment's accumulators; an
+ *                           environment that has finished is not touched again, so its last min(ticks, depth) records are the run-up to its end.
+ *                           Record = [STMPC_REC_HDR + 3 Kmax] fp64: world tick, ego x, y, v, a, s, k, commanded speed, takeover, jerk, then other_x
+ *                           [Kmax], other_v [Kmax], other_a [Kmax].  jerk is jerk_history's entry: 0 for an environment's first record, else
+ *                           (a - a of the previous record) / tick_length.  Accumulators per environment and bin, STMPC_REC_NQ quantities:
+ *                             0 count, 1 takeover count   np.histogram's rule: edge[b] <= x < edge[b+1], last bin closed on the right, outside dropped
+ *                             2 sum |jerk|, 3 sum |v|     the loop of stats.py:48-52: the first b with x <= edge[b+1]; x below the first edge -> bin 0
+ *                                                         (beyond the last edge the reference's loop fails with an IndexError; dropped here)
+ *                           then two totals: ticks with takeover != 0, recorded ticks (percent st solver = their quotient, dqn.py:113).
+ *                           Asynchronous, no atomics; within an environment sums are formed in tick order.
+ *   stmpc_rec_reduce_device the accumulators summed over the environments into the recorder (and d_out, DEVICE fp64 [STMPC_REC_NQ * (n_edges - 1) + 2],
+ *                           if not NULL): row q * (n_edges - 1) + b, then the two totals.  One workgroup per row, a fixed summation tree whose
+ *                           shape depends on N alone: equal inputs give equal bits.  Asynchronous
+ *   stmpc_rec_read          host copies (synchronises; any pointer may be NULL): ring [N][depth][STMPC_REC_HDR + 3 Kmax] in chronological order with
+ *                           length [N] valid records each (the rest zero), acc_env [STMPC_REC_NQ * (n_edges - 1) + 2][N], acc_reduced (reduced by this
+ *                           call), status [N] of the world
+ */
+#define STMPC_REC_HDR 10
+#define STMPC_REC_NQ 4
+#define STMPC_REC_MAX_DEPTH 64
+#define STMPC_REC_MAX_EDGES 32
+typedef struct stmpc_rec stmpc_rec;
+int  stmpc_rec_create(stmpc_ctx *ctx, int N, int Kmax, int depth, double tick_length, const double *edges, int n_edges, stmpc_rec **out);
+void stmpc_rec_destroy(stmpc_rec *rec);
+int  stmpc_rec_reset(stmpc_rec *rec, void *stream);
+int  stmpc_rec_tick_device(stmpc_rec *rec, int N, int Kmax, const double *d_ego5, const int32_t *d_k, const double *d_ox, const double *d_ov,
+                           const double *d_oa, const double *d_cmd_speed, const int32_t *d_takeover, void *stream);
+int  stmpc_rec_reduce_device(stmpc_rec *rec, double *d_out, void *stream);
+int  stmpc_rec_read(stmpc_rec *rec, double *ring, int32_t *length, double *acc_env, double *acc_reduced, int32_t *status);
 
 /* Device arithmetic probe used by the parity tests: out[i] = a[i] op b[i] evaluated on the GPU
  * with the kernels' compile flags. op: 0 div, 1 sqrt(a), 2 mul, 3 add, 4 fma(a,a,b*b), 5 the five-operation

@@ -169,6 +169,7 @@ EXPORTS = (
     "stmpc_ddpg_create", "stmpc_ddpg_destroy", "stmpc_ddpg_set_params", "stmpc_ddpg_get_params", "stmpc_ddpg_set_state", "stmpc_ddpg_get_state",
     "stmpc_ddpg_push_device", "stmpc_ddpg_act_device", "stmpc_ddpg_update_device", "stmpc_ddpg_grads_device", "stmpc_ddpg_stats_device",
     "stmpc_ddpg_replay_read", "stmpc_ddpg_gather_device", "stmpc_ddpg_sample_index", "stmpc_ddpg_noise",
+    "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
 ENV_CONTINUOUS_JERK, ENV_JERK, ENV_ACCELERATION = 0, 1, 2                                 # STMPC_ENV_*
@@ -176,6 +177,9 @@ REWARD_CONTINUOUS, REWARD_SLOTTED, REWARD_SLOTTED_JERK, REWARD_ST = 0, 1, 2, 3  
 ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
 DDPG_ROW, DDPG_NCOUNTERS = 68, 8      # STMPC_DDPG_ROW, STMPC_DDPG_NCOUNTERS
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
+REC_HDR, REC_NQ, REC_MAX_DEPTH, REC_MAX_EDGES = 10, 4, 64, 32      # STMPC_REC_HDR, STMPC_REC_NQ, STMPC_REC_MAX_DEPTH, STMPC_REC_MAX_EDGES
+REC_COLUMNS = ("tick", "x", "y", "v", "a", "s", "k", "cmd", "takeover", "jerk")      # the first STMPC_REC_HDR columns of a record
+REC_QUANTITIES = ("count", "takeover_count", "sum_abs_jerk", "sum_abs_speed")        # the STMPC_REC_NQ binned quantities, in row order
 ABI_VERSION = 8     # STMPC_ABI_VERSION of include/stmpc.h this binding was written against
 
 QP_NMAX = 64        # STMPC_QP_NMAX
@@ -286,6 +290,13 @@ def load():
     lib.stmpc_ddpg_sample_index.restype = C.c_uint64
     lib.stmpc_ddpg_noise.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, u32p, u32p]
     lib.stmpc_ddpg_noise.restype = C.c_double
+    lib.stmpc_rec_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_int, C.POINTER(vp)]
+    lib.stmpc_rec_destroy.argtypes = [vp]
+    lib.stmpc_rec_destroy.restype = None
+    lib.stmpc_rec_reset.argtypes = [vp, vp]
+    lib.stmpc_rec_tick_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 7 + [vp]
+    lib.stmpc_rec_reduce_device.argtypes = [vp, vp, vp]
+    lib.stmpc_rec_read.argtypes = [vp, dp, ip, dp, dp, ip]
     _lib = lib
     return lib
 
@@ -646,6 +657,36 @@ class Context:
 
     def ddpg_gather(self, handle, d_rows, stream=0):
         self._chk(self._lib.stmpc_ddpg_gather_device(handle, d_rows, stream))
+
+    # -- episode flight recorder (stmpc_rec_*): the handle follows this context's world ------------------------
+    def rec_create(self, N, Kmax, depth, tick_length, edges):
+        """A recorder of ``depth`` records per environment with the given bin edges for this context's world (``stmpc_rec_create``)."""
+        edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_rec_create(self._h, int(N), int(Kmax), int(depth), float(tick_length), _dptr(edges), int(edges.size), C.byref(h)))
+        return h
+
+    def rec_destroy(self, handle):
+        self._lib.stmpc_rec_destroy(handle)
+
+    def rec_reset(self, handle, stream=0):
+        self._chk(self._lib.stmpc_rec_reset(handle, stream))
+
+    def rec_tick(self, handle, N, Kmax, d_ego5, d_k, d_ox, d_ov, d_oa, d_cmd_speed, d_takeover=0, stream=0):
+        """One record + the bin accumulators for every running environment; between the controller and ``sim_step`` (asynchronous)."""
+        self._chk(self._lib.stmpc_rec_tick_device(handle, int(N), int(Kmax), d_ego5, d_k, d_ox, d_ov, d_oa or None, d_cmd_speed, d_takeover or None, stream))
+
+    def rec_reduce(self, handle, d_out=0, stream=0):
+        self._chk(self._lib.stmpc_rec_reduce_device(handle, d_out or None, stream))
+
+    def rec_read(self, handle, N, Kmax, depth, n_edges, want_ring=True):
+        """Host copies (synchronises): dict of ``ring`` [N][depth][REC_HDR + 3 Kmax] in chronological order, ``length`` [N], ``acc_env``
+        [REC_NQ * (n_edges - 1) + 2][N], ``acc_reduced`` and the world's ``status`` [N]."""
+        rows = REC_NQ * (int(n_edges) - 1) + 2
+        out = {"ring": np.zeros((N, depth, REC_HDR + 3 * Kmax)) if want_ring else None, "length": np.zeros(N, np.int32), "acc_env": np.zeros((rows, N)),
+               "acc_reduced": np.zeros(rows), "status": np.zeros(N, np.int32)}
+        self._chk(self._lib.stmpc_rec_read(handle, _dptr(out["ring"]), _iptr(out["length"]), _dptr(out["acc_env"]), _dptr(out["acc_reduced"]), _iptr(out["status"])))
+        return out
 
     # -- vector environment (stmpc_env_*) ---------------------------------------------------------------
     def env_reset(self, params, sim_cfg, env_cfg, N, d_obs, obs_stride, stream=0):

@@ -8,6 +8,7 @@
 #include "stmpc_actor_kernels.hpp"
 #include "stmpc_env_kernels.hpp"
 #include "stmpc_ddpg_kernels.hpp"
+#include "stmpc_rec_kernels.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -204,6 +205,7 @@ struct stmpc_ctx {
     struct Sim {
         DevBuf ego, nveh, vx, vv, va, vc, delay, status, ticks, rng, acc, route;
         int N = 0, route_n = 0;
+        int64_t generation = 0;    // stmpc_sim_init_device calls so far (a recorder bound to an earlier world refuses to go on)
         int ensure(int n_) {
             const size_t n = (size_t)n_, KS = sim::KS;
             TRY(ego.ensure(n * 4 * 8)); TRY(nveh.ensure(n * 4)); TRY(vx.ensure(n * KS * 8)); TRY(vv.ensure(n * KS * 8)); TRY(va.ensure(n * KS * 8));
@@ -1796,7 +1798,8 @@ int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *str
     HIPCHK(hipSetDevice(c->device));
     TRY(c->sim.ensure(N));
     c->sim.N = N;
-    c->env.N = 0;                  // (the vector environment's bookkeeping no longer describes this world; stmpc_env_reset_device sets it again)
+    ++c->sim.generation;
+    c->env.N = 0;                 // (the vector environment's bookkeeping no longer describes this world; stmpc_env_reset_device sets it again)
     c->sim.route_n = 0;
     if (g->ego_route_xy && g->ego_route_n >= 2) {
         const int n = g->ego_route_n;
@@ -2250,6 +2253,141 @@ double stmpc_ddpg_noise(uint64_t seed, uint64_t call, uint32_t row, uint32_t *dr
     const double f1 = ((double)u1 + 1.0) * 5.9604644775390625e-8;
     const volatile float theta = 6.2831855f * ((float)u2 * 5.9604644775390625e-8f);      // the float32 product the kernel forms
     return sqrt(-2.0 * log(f1)) * cos((double)theta);
+}
+
+}  // extern "C"
+
+// ---- episode flight recorder (stmpc_rec_*): per-tick rings and position-binned accumulators; kernels in stmpc_rec_kernels.hpp ----------------------
+struct stmpc_rec {
+    stmpc_ctx *ctx = nullptr;
+    int device = 0;
+    rec::Cfg cfg{};
+    DevBuf ring, nrec, last_tick, prev_a, acc, red;
+    int64_t generation = -1;       // the world (stmpc_ctx::Sim::generation) the recorder follows; -1: none yet (stmpc_rec_reset)
+    rec::State state() const { return rec::State{ring.as<double>(), nrec.as<int>(), last_tick.as<int>(), prev_a.as<double>(), acc.as<double>(), red.as<double>()}; }
+    size_t ring_len() const { return (size_t)cfg.N * cfg.T * rec::row_width(cfg.Kmax); }
+    size_t acc_len() const { return (size_t)rec::acc_rows(cfg.n_edges) * cfg.N; }
+};
+
+namespace {
+// the recorder follows the world it was reset on: same context, same N, no stmpc_sim_init_device since
+int rec_bound(const stmpc_rec *r) {
+    if (!r) return fail(STMPC_EINVAL, "recorder is NULL");
+    if (r->cfg.N != r->ctx->sim.N || r->generation != r->ctx->sim.generation)
+        return fail(STMPC_EINVAL, "the recorder's world was re-initialised (or has another N) since stmpc_rec_reset");
+    return STMPC_OK;
+}
+void rec_launch_reduce(const stmpc_rec *r, hipStream_t st) {
+    hipLaunchKernelGGL(rec::k_rec_reduce, dim3(rec::acc_rows(r->cfg.n_edges)), dim3(rec::THREADS), 0, st, r->cfg.N, (const double *)r->acc.p, r->red.as<double>());
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_rec_create(stmpc_ctx *c, int N, int Kmax, int depth, double tick_length, const double *edges, int n_edges, stmpc_rec **out) {
+    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (N < 1 || Kmax < 1 || Kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "recorder: N or Kmax out of range");
+    if (depth < 1 || depth > STMPC_REC_MAX_DEPTH) return fail(STMPC_EINVAL, "recorder: the ring depth must be in 1 ... STMPC_REC_MAX_DEPTH");
+    if (!edges || n_edges < 2 || n_edges > STMPC_REC_MAX_EDGES) return fail(STMPC_EINVAL, "recorder: 2 ... STMPC_REC_MAX_EDGES bin edges");
+    if (!(tick_length > 0)) return fail(STMPC_EINVAL, "recorder: tick_length must be positive");
+    for (int i = 0; i < n_edges; ++i)
+        if (!(fabs(edges[i]) < 1e300) || (i && !(edges[i] > edges[i - 1]))) return fail(STMPC_EINVAL, "recorder: bin edges must be finite and strictly increasing");
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_rec *r = new stmpc_rec();
+    r->ctx = c; r->device = c->device;
+    r->cfg.N = N; r->cfg.Kmax = Kmax; r->cfg.T = depth; r->cfg.n_edges = n_edges; r->cfg.tick = tick_length;
+    for (int i = 0; i < n_edges; ++i) r->cfg.edges[i] = edges[i];
+    const size_t n = (size_t)N;
+    int rc = r->ring.ensure(r->ring_len() * 8);
+    if (!rc) rc = r->nrec.ensure(n * 4);
+    if (!rc) rc = r->last_tick.ensure(n * 4);
+    if (!rc) rc = r->prev_a.ensure(n * 8);
+    if (!rc) rc = r->acc.ensure(r->acc_len() * 8);
+    if (!rc) rc = r->red.ensure((size_t)rec::acc_rows(n_edges) * 8);
+    if (!rc && c->sim.N == N) rc = stmpc_rec_reset(r, nullptr);      // (a world of this size exists: follow it from here)
+    if (rc) { delete r; return rc; }
+    *out = r;
+    return STMPC_OK;
+}
+
+void stmpc_rec_destroy(stmpc_rec *r) {
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    delete r;
+}
+
+int stmpc_rec_reset(stmpc_rec *r, void *stream) {
+    if (!r) return fail(STMPC_EINVAL, "recorder is NULL");
+    if (r->cfg.N != r->ctx->sim.N) return fail(STMPC_EINVAL, "recorder: N does not match stmpc_sim_init_device");
+    HIPCHK(hipSetDevice(r->ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)r->cfg.N;
+    HIPCHK(hipMemsetAsync(r->ring.p, 0, r->ring_len() * 8, st));
+    HIPCHK(hipMemsetAsync(r->nrec.p, 0, n * 4, st));
+    HIPCHK(hipMemsetAsync(r->last_tick.p, 0, n * 4, st));
+    HIPCHK(hipMemsetAsync(r->prev_a.p, 0, n * 8, st));
+    HIPCHK(hipMemsetAsync(r->acc.p, 0, r->acc_len() * 8, st));
+    HIPCHK(hipMemsetAsync(r->red.p, 0, (size_t)rec::acc_rows(r->cfg.n_edges) * 8, st));
+    r->generation = r->ctx->sim.generation;
+    return STMPC_OK;
+}
+
+int stmpc_rec_tick_device(stmpc_rec *r, int N, int Kmax, const double *d_ego5, const int32_t *d_k, const double *d_ox, const double *d_ov, const double *d_oa,
+                          const double *d_cmd_speed, const int32_t *d_takeover, void *stream) {
+    TRY(rec_bound(r));
+    if (N != r->cfg.N || Kmax != r->cfg.Kmax) return fail(STMPC_EINVAL, "recorder: N or Kmax differ from stmpc_rec_create's");
+    if (!d_ego5 || !d_k || !d_ox || !d_ov || !d_cmd_speed) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(r->ctx->device));
+    const sim::State s = r->ctx->sim.state();
+    hipLaunchKernelGGL(rec::k_rec_tick, dim3((N + rec::G - 1) / rec::G), dim3(rec::THREADS), 0, (hipStream_t)stream, r->cfg, r->state(), (const int *)s.status,
+                       (const int *)s.ticks, d_ego5, d_k, d_ox, d_ov, d_oa, d_cmd_speed, d_takeover);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_rec_reduce_device(stmpc_rec *r, double *d_out, void *stream) {
+    TRY(rec_bound(r));
+    HIPCHK(hipSetDevice(r->ctx->device));
+    rec_launch_reduce(r, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    if (d_out) HIPCHK(hipMemcpyAsync(d_out, r->red.p, (size_t)rec::acc_rows(r->cfg.n_edges) * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return STMPC_OK;
+}
+
+int stmpc_rec_read(stmpc_rec *r, double *ring, int32_t *length, double *acc_env, double *acc_reduced, int32_t *status) {
+    TRY(rec_bound(r));
+    HIPCHK(hipSetDevice(r->ctx->device));
+    HIPCHK(hipDeviceSynchronize());
+    const int N = r->cfg.N, T = r->cfg.T, W = rec::row_width(r->cfg.Kmax);
+    const size_t n = (size_t)N;
+    if (ring || length) {
+        std::vector<int32_t> nrec(n), last(n);
+        TRY(download(nrec.data(), r->nrec, n)); TRY(download(last.data(), r->last_tick, n));
+        std::vector<double> raw;
+        if (ring) { raw.resize(r->ring_len()); TRY(download(raw.data(), r->ring, raw.size())); }
+        for (int e = 0; e < N; ++e) {
+            const int len = nrec[e] < T ? nrec[e] : T;
+            if (length) length[e] = len;
+            if (!ring) continue;
+            double *dst = ring + (size_t)e * T * W;
+            // chronological order: the newest record sits in slot last % T, the ones before it in the slots before that (the world's tick counts up by one per record)
+            for (int i = 0; i < len; ++i) {
+                const int slot = ((last[e] - (len - 1 - i)) % T + T) % T;
+                memcpy(dst + (size_t)i * W, raw.data() + ((size_t)e * T + slot) * W, (size_t)W * 8);
+            }
+            if (len < T) memset(dst + (size_t)len * W, 0, (size_t)(T - len) * W * 8);
+        }
+    }
+    TRY(download(acc_env, r->acc, r->acc_len()));
+    if (acc_reduced) {
+        rec_launch_reduce(r, nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+        TRY(download(acc_reduced, r->red, (size_t)rec::acc_rows(r->cfg.n_edges)));
+    }
+    TRY(download(status, r->ctx->sim.status, n));
+    return STMPC_OK;
 }
 
 }  // extern "C"

@@ -53,9 +53,15 @@ def sim_cfg(seed=0, max_episode_length=100.0, route="lane"):
 
 class EpisodeRunner:
     """N merge episodes stepped in lock-step on the device, one ``tick()`` at a time (``run_episodes`` drives it to the end;
-    ``bench.py --workload episodes`` times its ticks)."""
+    ``bench.py --workload episodes`` times its ticks).
 
-    def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0):
+    ``record``: None (the tick is the plain sequence view -> controller -> step) or a ``report.RecorderConfig``: every tick then also feeds the
+    on-device flight recorder (``stmpc_rec_*``) between the controller and the step, and ``result()`` gains ``out["report"]`` (``report.Report``:
+    the reference's report row with standard errors, the position profiles, the recorded run-up of every environment).  The recorder follows
+    ONE episode per environment -- this runner's -- and is bound to the world this constructor initialises; ``vec_env.MergeVecEnv``'s autoreset
+    is not recorded."""
+
+    def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, record=None):
         import torch
         self.torch = torch
         if controller not in ("st", "combined"):
@@ -78,6 +84,12 @@ class EpisodeRunner:
         self.d_status = z(n, dtype=torch.int32)
         self.ticks_done = 0
         self.ctx.sim_init(self.cfg, n)
+        self.recorder = None
+        if record is not None:
+            from . import report
+            if not isinstance(record, report.RecorderConfig):
+                raise ValueError("record must be None or a report.RecorderConfig (the recorder follows one episode per environment: this runner's), not %r" % (record,))
+            self.recorder = report.Recorder(self.ctx, n, kmax, record, self.tick_length)
 
     def tick(self):
         """Planner view -> controller -> world step for every environment (finished environments idle)."""
@@ -100,6 +112,9 @@ class EpisodeRunner:
             self.takeovers += d["takeover"].to(torch.float64) * running
             self.controlled += running
             self.last_rl = (d["takeover"] == 0).to(torch.int32)
+        if self.recorder is not None:
+            # the state before control, as the reference appends it to state_history (control.py:280-289), with this tick's command
+            self.recorder.tick(n, kmax, self.d_ego5, self.d_k, self.d_ox, self.d_ov, self.d_oa, cmd, d["takeover"] if self.controller == "combined" else None)
         ctx.sim_step(self.params, self.cfg, n, cmd.data_ptr())
         self.ticks_done += 1
 
@@ -116,6 +131,9 @@ class EpisodeRunner:
         out["ego4"] = ego4
         if self.controller == "combined":
             out["percent_st"] = (self.takeovers / self.torch.clamp(self.controlled, min=1.0)).cpu().numpy()
+        if self.recorder is not None:
+            from . import report
+            out["report"] = report.Report.from_result(out, self.recorder.read())
         return out
 
 
@@ -139,15 +157,16 @@ def stats_columns(status, ticks, acc, tick_length):
     return out
 
 
-def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, check_every=16, max_ticks=None):
+def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, check_every=16, max_ticks=None, record=None):
     """Run ``n`` merge episodes to the end (or for ``max_ticks`` ticks); returns the per-episode columns of the reference's stats report
     (``crashed``, ``merged``, ``mean_speed``, ``max_speed``, ``mean_abs_jerk``, ``closest_distance``, ``mean_closest_distance``,
     ``time_taken``, ``time_to_merge`` (NaN unless merged)) plus ``ticks``, ``status`` (0 still running), ``ego4`` and ``percent_st``
     (combined controller only).
 
     controller: "st" = ``st.do_st_control`` every tick (TASK "ST"); "combined" = ``do_combined_control`` with ``policy``
-    (see ``combined.decide_batch_device``)."""
-    r = EpisodeRunner(n, seed, controller, policy, ctx, kmax, max_episode_length)
+    (see ``combined.decide_batch_device``).  record: None, or a ``report.RecorderConfig`` -- the result then holds ``report`` (``report.Report``),
+    see ``EpisodeRunner``."""
+    r = EpisodeRunner(n, seed, controller, policy, ctx, kmax, max_episode_length, record)
     limit = r.cfg.max_ticks + 1 if max_ticks is None else min(int(max_ticks), r.cfg.max_ticks + 1)
     for tick in range(limit):
         r.tick()
@@ -158,4 +177,4 @@ def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max
 
 def summary(stats):
     """Column means as the reference's report rows hold them (stats.py:145-158)."""
-    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4")}
+    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4", "report")}

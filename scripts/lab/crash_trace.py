@@ -1,29 +1,21 @@
-"""Trace of one environment of the batched episodes up to its crash (analysis tool).  usage: crash_trace.py <interval> <seed> <n> <env>"""
+"""Run-up of environments of the batched episodes to their end, from the on-device flight recorder (analysis tool): the whole batch runs without a
+per-tick synchronisation, the environments are chosen afterwards.
+usage: crash_trace.py <interval> <seed> <n> [env ...]      (no env: every crashed environment; the table is the last 25 recorded ticks of each)"""
 import sys; sys.path.insert(0, '.')
-import numpy as np, torch
+import numpy as np
 import rl_mpc_lanemerging_amd as pkg
-from rl_mpc_lanemerging_amd import episodes, _capi
-from rl_mpc_lanemerging_amd.config import Settings
-interval, seed, n, env = float(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
+from rl_mpc_lanemerging_amd import episodes, report, _capi
+interval, seed, n = float(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
+envs = [int(a) for a in sys.argv[4:]]
 pkg.apply_overrides(pkg.REFERENCE_DEFAULT); pkg.apply_overrides(dict(BASE_TRAFFIC_INTERVAL=interval, OTHER_CAR_SPEED=7.0))
-ctx = _capi.default_context(); params = _capi.Params.from_settings(Settings); cfg = episodes.sim_cfg(seed, 100.0)
-dev = torch.device("cuda", 0); kmax = 32; H = _capi.num_t(params)
-z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=dev)
-d_ego5, d_k, d_ox, d_ov = z(n, 5), z(n, dt=torch.int32), z(n, kmax), z(n, kmax)
-d_path, d_bt, d_cost, d_speed, d_fine, d_fl = z(n, H, dt=torch.int32), z(n, dt=torch.int32), z(n), z(n), z(n, _capi.QP_NMAX), z(n, dt=torch.int32)
-ctx.sim_init(cfg, n)
-rows = []
-for tick in range(cfg.max_ticks + 1):
-    ctx.sim_view(cfg, n, kmax, d_ego5.data_ptr(), d_k.data_ptr(), d_ox.data_ptr(), d_ov.data_ptr())
-    ctx.st_control_batch_device(params, Settings.TICK_LENGTH, n, kmax, d_ego5.data_ptr(), d_k.data_ptr(), d_ox.data_ptr(), d_ov.data_ptr(), d_path.data_ptr(), d_bt.data_ptr(),
-                                d_cost.data_ptr(), d_speed.data_ptr(), d_fine.data_ptr(), d_fl.data_ptr(), 0)
-    torch.cuda.synchronize()
-    k = int(d_k[env]); e5 = d_ego5[env].cpu().numpy(); ox = d_ox[env, :k].cpu().numpy(); ov = d_ov[env, :k].cpu().numpy()
-    rows.append((tick, e5.copy(), ox.copy(), ov.copy(), float(d_speed[env]), int(d_bt[env]), int(d_fl[env])))
-    ctx.sim_step(params, cfg, n, d_speed.data_ptr())
-    status, _, _, _ = ctx.sim_read(n)
-    if status[env] != 0:
-        print("status", status[env], "at tick", tick); break
-for tick, e5, ox, ov, cmd, bt, fl in rows[-25:]:
-    near = sorted(zip(ox - e5[0], ov), key=lambda q: abs(q[0]))[:4]
-    print("t %3d ego x %.2f y %.2f v %.2f a %.2f s %.2f | cmd %.2f best_t %d fine_len %d | nearest dx,v: %s" % (tick, e5[0], e5[1], e5[2], e5[3], e5[4], cmd, bt, fl, " ".join("(%.1f,%.1f)" % q for q in sorted(near))))
+res = episodes.run_episodes(n, seed=seed, controller="st", kmax=32, record=report.RecorderConfig(depth=25))
+rep = res["report"]
+traces = [t for t in rep.traces() if t.env in envs] if envs else rep.crashed_traces()
+print("status counts", {s: int((res["status"] == s).sum()) for s in (0, 1, 2, 3)}, "| traces of", [t.env for t in traces])
+for tr in traces:
+    print("env", tr.env, "status", tr.status, "at tick", int(res["ticks"][tr.env]) - 1)
+    again = report.replay(tr)          # best_t and the re-sampled path's length are not recorded: solved again from the recorded states
+    for s, bt, fl in zip(tr, again["best_t"], again["fine_len"]):
+        e5 = s["ego5"]
+        near = sorted(zip(s["other_x"] - e5[0], s["other_v"]), key=lambda q: abs(q[0]))[:4]
+        print("t %3d ego x %.2f y %.2f v %.2f a %.2f s %.2f | cmd %.2f best_t %d fine_len %d | nearest dx,v: %s" % (s["tick"], e5[0], e5[1], e5[2], e5[3], e5[4], s["cmd"], bt, fl, " ".join("(%.1f,%.1f)" % q for q in sorted(near))))
