@@ -611,6 +611,39 @@ uint64_t stmpc_ddpg_sample_index(uint64_t seed, uint64_t update, uint32_t row, u
 double stmpc_ddpg_noise(uint64_t seed, uint64_t call, uint32_t row, uint32_t *draw1, uint32_t *draw2);
 
 /*
+ * A population of DDPG learners: P independent learners of the section above -- each its own replay ring, networks, Adam state, counters, seed and
+ * constants -- sharing one vector environment and advancing with ONE launch per kernel.  The reference trains its agents as one TRAIN_DDPG run
+ * (ddpg.py:44-80) per seed: the train_{traffic_type}_{seed}.json configs and the ddpg_*{1,2,...} checkpoints of pretrained_models/README.md; one
+ * learner's update occupies a few workgroups of the device, and the members of a population fill the rest.  Member m owns rows
+ * [m * n_per_member, (m + 1) * n_per_member) of the step tensors.  Members do not interact, and every member is bit-identical to a lone
+ * stmpc_ddpg with its cfg given its slice: the noise and the minibatch indices are keyed by the member's seed, its own counters and the row LOCAL
+ * to its slice.  (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)
+ *   pop_create      P = 1 ... STMPC_DDPG_POP_MAX configs that share n_obs, h1, h2, batch and capacity (the launch shapes are common); seed, replay_start,
+ *                   gamma, tau, the betas, eps, noise_std, the squash and the action Box may differ per member
+ *   pop_member      the m-th member as a BORROWED learner handle, valid until pop_destroy (never stmpc_ddpg_destroy it): set / get_params, set /
+ *                   get_state, replay_read, grads_device, gather_device -- and the single-learner act / push / update -- work on it as on a lone learner
+ *   pop_act_device / pop_push_device   stmpc_ddpg_act_device / stmpc_ddpg_push_device on tensors of P * n_per_member rows, 1 <= n_per_member <= capacity;
+ *                   d_debug [P * n_per_member][4].  A member's noisy-acting counter, cursor, fill and frames are its own
+ *   pop_update_device   n_updates updates of every member in six launches each; lr_q / lr_pi: HOST fp64 [n_lr], n_lr = P, member m's learning rates
+ *                   (they travel as kernel arguments: no copy, no synchronisation, capturable).  A member whose replay_start gate is still shut
+ *                   skips its update while the others proceed
+ *   pop_stats_device    d_out DEVICE fp64 [P][4]: stmpc_ddpg_stats_device's four numbers per member
+ */
+#define STMPC_DDPG_POP_MAX 64
+typedef struct stmpc_ddpg_pop stmpc_ddpg_pop;
+int  stmpc_ddpg_pop_create(stmpc_ctx *ctx, const stmpc_ddpg_cfg *cfgs, int P, stmpc_ddpg_pop **out);
+void stmpc_ddpg_pop_destroy(stmpc_ddpg_pop *pop);
+int  stmpc_ddpg_pop_size(const stmpc_ddpg_pop *pop);
+stmpc_ddpg *stmpc_ddpg_pop_member(stmpc_ddpg_pop *pop, int m);
+int  stmpc_ddpg_pop_act_device(stmpc_ddpg_pop *pop, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise,
+                               double *d_action, uint32_t *d_debug, void *stream);
+int  stmpc_ddpg_pop_push_device(stmpc_ddpg_pop *pop, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs,
+                                int obs_stride, const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward,
+                                const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream);
+int  stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *pop, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream);
+int  stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *pop, double *d_out, void *stream);
+
+/*
  * Episode flight recorder on the device, next to the world (stmpc_sim_*): the per-tick histories the reference's evaluation keeps and what it
  * bins over the ego's position, for N environments in lock-step, with nothing crossing to the host until it is read.  (Additive: new entries
  * only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)

@@ -169,6 +169,8 @@ EXPORTS = (
     "stmpc_ddpg_create", "stmpc_ddpg_destroy", "stmpc_ddpg_set_params", "stmpc_ddpg_get_params", "stmpc_ddpg_set_state", "stmpc_ddpg_get_state",
     "stmpc_ddpg_push_device", "stmpc_ddpg_act_device", "stmpc_ddpg_update_device", "stmpc_ddpg_grads_device", "stmpc_ddpg_stats_device",
     "stmpc_ddpg_replay_read", "stmpc_ddpg_gather_device", "stmpc_ddpg_sample_index", "stmpc_ddpg_noise",
+    "stmpc_ddpg_pop_create", "stmpc_ddpg_pop_destroy", "stmpc_ddpg_pop_size", "stmpc_ddpg_pop_member", "stmpc_ddpg_pop_act_device",
+    "stmpc_ddpg_pop_push_device", "stmpc_ddpg_pop_update_device", "stmpc_ddpg_pop_stats_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
@@ -176,6 +178,7 @@ ENV_CONTINUOUS_JERK, ENV_JERK, ENV_ACCELERATION = 0, 1, 2                       
 REWARD_CONTINUOUS, REWARD_SLOTTED, REWARD_SLOTTED_JERK, REWARD_ST = 0, 1, 2, 3             # STMPC_REWARD_*
 ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
 DDPG_ROW, DDPG_NCOUNTERS = 68, 8      # STMPC_DDPG_ROW, STMPC_DDPG_NCOUNTERS
+DDPG_POP_MAX = 64                     # STMPC_DDPG_POP_MAX
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
 REC_HDR, REC_NQ, REC_MAX_DEPTH, REC_MAX_EDGES = 10, 4, 64, 32      # STMPC_REC_HDR, STMPC_REC_NQ, STMPC_REC_MAX_DEPTH, STMPC_REC_MAX_EDGES
 REC_COLUMNS = ("tick", "x", "y", "v", "a", "s", "k", "cmd", "takeover", "jerk")      # the first STMPC_REC_HDR columns of a record
@@ -290,6 +293,16 @@ def load():
     lib.stmpc_ddpg_sample_index.restype = C.c_uint64
     lib.stmpc_ddpg_noise.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, u32p, u32p]
     lib.stmpc_ddpg_noise.restype = C.c_double
+    lib.stmpc_ddpg_pop_create.argtypes = [vp, C.POINTER(DDPGCfg), C.c_int, C.POINTER(vp)]
+    lib.stmpc_ddpg_pop_destroy.argtypes = [vp]
+    lib.stmpc_ddpg_pop_destroy.restype = None
+    lib.stmpc_ddpg_pop_size.argtypes = [vp]
+    lib.stmpc_ddpg_pop_member.argtypes = [vp, C.c_int]
+    lib.stmpc_ddpg_pop_member.restype = vp
+    lib.stmpc_ddpg_pop_act_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    lib.stmpc_ddpg_pop_push_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 6 + [vp]
+    lib.stmpc_ddpg_pop_update_device.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, vp]
+    lib.stmpc_ddpg_pop_stats_device.argtypes = [vp, vp, vp]
     lib.stmpc_rec_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_int, C.POINTER(vp)]
     lib.stmpc_rec_destroy.argtypes = [vp]
     lib.stmpc_rec_destroy.restype = None
@@ -657,6 +670,45 @@ class Context:
 
     def ddpg_gather(self, handle, d_rows, stream=0):
         self._chk(self._lib.stmpc_ddpg_gather_device(handle, d_rows, stream))
+
+    # -- DDPG population (stmpc_ddpg_pop_*): P learners, one launch per kernel ------------------------
+    def ddpg_pop_create(self, cfgs):
+        """``cfgs``: a sequence of ``DDPGCfg``; the library checks the member count and that the launch shapes are common."""
+        arr = (DDPGCfg * len(cfgs))(*cfgs)
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_ddpg_pop_create(self._h, arr, len(cfgs), C.byref(h)))
+        return h
+
+    def ddpg_pop_destroy(self, handle):
+        self._lib.stmpc_ddpg_pop_destroy(handle)
+
+    def ddpg_pop_size(self, handle):
+        return int(self._lib.stmpc_ddpg_pop_size(handle))
+
+    def ddpg_pop_member(self, handle, m):
+        """The m-th member as a borrowed ``stmpc_ddpg`` handle for the ``ddpg_*`` methods above (never ``ddpg_destroy`` it)."""
+        h = self._lib.stmpc_ddpg_pop_member(handle, int(m))
+        if not h:
+            self._chk(STMPC_EINVAL)
+        return C.c_void_p(h)
+
+    def ddpg_pop_act(self, handle, n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug=0, stream=0):
+        self._chk(self._lib.stmpc_ddpg_pop_act_device(handle, int(n_per_member), d_obs, int(obs_stride), d_ticks, int(bool(noise)), d_action, d_debug, stream))
+
+    def ddpg_pop_push(self, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated,
+                      stream=0):
+        self._chk(self._lib.stmpc_ddpg_pop_push_device(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_ticks, d_next_ticks, d_action,
+                                                       d_reward, d_terminated, d_truncated, stream))
+
+    def ddpg_pop_update(self, handle, n_updates, lr_q, lr_pi, stream=0):
+        """``lr_q`` / ``lr_pi``: one learning rate per member (the library checks the lengths)."""
+        lq, lp = np.ascontiguousarray(lr_q, dtype=np.float64).reshape(-1), np.ascontiguousarray(lr_pi, dtype=np.float64).reshape(-1)
+        if lq.size != lp.size:
+            raise ValueError("lr_q has %d entries, lr_pi %d" % (lq.size, lp.size))
+        self._chk(self._lib.stmpc_ddpg_pop_update_device(handle, int(n_updates), _dptr(lq), _dptr(lp), int(lq.size), stream))
+
+    def ddpg_pop_stats(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_ddpg_pop_stats_device(handle, d_out, stream))
 
     # -- episode flight recorder (stmpc_rec_*): the handle follows this context's world ------------------------
     def rec_create(self, N, Kmax, depth, tick_length, edges):

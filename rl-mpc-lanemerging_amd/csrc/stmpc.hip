@@ -8,6 +8,7 @@
 #include "stmpc_actor_kernels.hpp"
 #include "stmpc_env_kernels.hpp"
 #include "stmpc_ddpg_kernels.hpp"
+#include "stmpc_ddpg_pop_kernels.hpp"
 #include "stmpc_rec_kernels.hpp"
 
 #include <math.h>
@@ -2253,6 +2254,136 @@ double stmpc_ddpg_noise(uint64_t seed, uint64_t call, uint32_t row, uint32_t *dr
     const double f1 = ((double)u1 + 1.0) * 5.9604644775390625e-8;
     const volatile float theta = 6.2831855f * ((float)u2 * 5.9604644775390625e-8f);      // the float32 product the kernel forms
     return sqrt(-2.0 * log(f1)) * cos((double)theta);
+}
+
+}  // extern "C"
+
+// ---- DDPG population (stmpc_ddpg_pop_*): P learners of the section above, one launch per kernel; kernels in stmpc_ddpg_pop_kernels.hpp ------------
+struct stmpc_ddpg_pop {
+    int device = 0;
+    std::vector<stmpc_ddpg *> members;      // owned; made by stmpc_ddpg_create, so every single-learner entry works on a borrowed member
+    DevBuf table;                           // DdpgDev [P]: the members' structs (their pointers and constants never change after create)
+    int P() const { return (int)members.size(); }
+    const DdpgDev *dev() const { return table.as<DdpgDev>(); }
+};
+
+static_assert(DG_POP_MAX == STMPC_DDPG_POP_MAX, "DdpgLr holds one learning rate per possible member");
+
+namespace {
+int ddpg_pop_lrs(const stmpc_ddpg_pop *p, const double *lr, DdpgLr &out) {
+    for (int m = 0; m < p->P(); ++m) {
+        if (!(lr[m] >= 0)) return fail(STMPC_EINVAL, "a member's learning rate is negative");
+        out.lr[m] = (float)lr[m];
+    }
+    return STMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_ddpg_pop_create(stmpc_ctx *c, const stmpc_ddpg_cfg *cfgs, int P, stmpc_ddpg_pop **out) {
+    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (P < 1 || P > DG_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
+    if (!cfgs) return fail(STMPC_EINVAL, "NULL argument");
+    for (int m = 1; m < P; ++m)
+        if (cfgs[m].n_obs != cfgs[0].n_obs || cfgs[m].h1 != cfgs[0].h1 || cfgs[m].h2 != cfgs[0].h2 || cfgs[m].batch != cfgs[0].batch || cfgs[m].capacity != cfgs[0].capacity)
+            return fail(STMPC_EINVAL, "the members of a population share n_obs, h1, h2, batch and capacity (member " + std::to_string(m) + " differs from member 0)");
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_ddpg_pop *p = new stmpc_ddpg_pop();
+    p->device = c->device;
+    int rc = STMPC_OK;
+    std::vector<DdpgDev> host;
+    for (int m = 0; m < P && !rc; ++m) {
+        stmpc_ddpg *l = nullptr;
+        rc = stmpc_ddpg_create(c, cfgs + m, &l);
+        if (!rc) { p->members.push_back(l); host.push_back(l->dev); }
+    }
+    if (!rc) rc = p->table.ensure(host.size() * sizeof(DdpgDev));
+    if (!rc && hipMemcpy(p->table.p, host.data(), host.size() * sizeof(DdpgDev), hipMemcpyHostToDevice) != hipSuccess) rc = fail(STMPC_EHIP, "hipMemcpy of the member table failed");
+    const size_t lds = rc ? 0 : p->members[0]->lds;
+    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_critic_fwd_pop, lds);
+    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_actor_fwd_pop, lds);
+    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_act_pop, lds);
+    if (rc) { stmpc_ddpg_pop_destroy(p); return rc; }
+    *out = p;
+    return STMPC_OK;
+}
+
+void stmpc_ddpg_pop_destroy(stmpc_ddpg_pop *p) {
+    if (!p) return;
+    for (stmpc_ddpg *l : p->members) stmpc_ddpg_destroy(l);
+    (void)hipSetDevice(p->device);
+    delete p;
+}
+
+int stmpc_ddpg_pop_size(const stmpc_ddpg_pop *p) { return p ? p->P() : 0; }
+
+stmpc_ddpg *stmpc_ddpg_pop_member(stmpc_ddpg_pop *p, int m) {
+    if (!p || m < 0 || m >= p->P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
+    return p->members[m];
+}
+
+int stmpc_ddpg_pop_act_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action,
+                              uint32_t *d_debug, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    const stmpc_ddpg *l0 = p->members[0];
+    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
+        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
+    if (!d_obs || !d_ticks || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(p->device));
+    hipLaunchKernelGGL(k_ddpg_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, p->P()), dim3(AT_THREADS), l0->lds, (hipStream_t)stream, p->dev(), n_per_member, d_obs,
+                       obs_stride, d_ticks, noise != 0, d_action, d_debug);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_ddpg_pop_push_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                               const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated,
+                               const uint8_t *d_truncated, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    const stmpc_ddpg *l0 = p->members[0];
+    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
+        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
+    if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(p->device));
+    const long long items = (long long)n_per_member * DG_ROW;       // per member: stmpc_ddpg_push_device's block count
+    const int blocks = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_replay_push_pop, dim3(blocks, p->P()), dim3(256), 0, (hipStream_t)stream, p->dev(), n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride,
+                       d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *p, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream) {
+    if (!p || !lr_q || !lr_pi) return fail(STMPC_EINVAL, "NULL argument");
+    if (n_lr != p->P()) return fail(STMPC_EINVAL, "the learning-rate arrays have " + std::to_string(n_lr) + " entries, the population " + std::to_string(p->P()) + " members");
+    if (n_updates < 0) return fail(STMPC_EINVAL, "n_updates is negative");
+    DdpgLr lq{}, lp{};
+    TRY(ddpg_pop_lrs(p, lr_q, lq));
+    TRY(ddpg_pop_lrs(p, lr_pi, lp));
+    HIPCHK(hipSetDevice(p->device));
+    const stmpc_ddpg *l = p->members[0];
+    const int P = p->P(), tiles = l->Bp / AT_TM, t1 = l->h2p / 16, t0 = l->h1p / 16, jobs = t1 * t0 + 2 * t0 + t1 + t0 + t1 + 1, ablocks = (l->np + 255) / 256;
+    hipStream_t st = (hipStream_t)stream;
+    for (int u = 0; u < n_updates; ++u) {                            // stmpc_ddpg_update_device's six launches, each over the members
+        hipLaunchKernelGGL(k_ddpg_critic_fwd_pop, dim3(tiles, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
+        hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 1, l->Bp, 1);
+        hipLaunchKernelGGL(k_ddpg_adam_pop, dim3(ablocks, P), dim3(256), 0, st, p->dev(), 1, lq, 0, 0, 1);
+        hipLaunchKernelGGL(k_ddpg_actor_fwd_pop, dim3(tiles, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
+        hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 0, l->Bp, 1);
+        hipLaunchKernelGGL(k_ddpg_adam_pop, dim3(ablocks, P), dim3(256), 0, st, p->dev(), 0, lp, 0, 1, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *p, double *d_out, void *stream) {
+    if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(p->device));
+    hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->members[0]->cfg.batch, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
 }
 
 }  // extern "C"

@@ -81,9 +81,11 @@ __device__ __forceinline__ bool dg_last_block(unsigned int *ticket, unsigned int
 }
 
 // ---- replay ---------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_replay_push(DdpgDev L, int N, const float *__restrict__ obs, const float *__restrict__ next_obs, const float *__restrict__ final_obs,
-                                                     int obs_stride, const int *__restrict__ ticks, const int *__restrict__ next_ticks, const double *__restrict__ action,
-                                                     const double *__restrict__ reward, const unsigned char *__restrict__ term, const unsigned char *__restrict__ trunc) {
+// (every kernel's body is a __device__ function of the learner's struct: the single-learner entry passes its by-value argument, the population
+// entry of stmpc_ddpg_pop_kernels.hpp the member blockIdx.y selects)
+__device__ __forceinline__ void ddpg_push_body(const DdpgDev &L, int N, const float *__restrict__ obs, const float *__restrict__ next_obs, const float *__restrict__ final_obs,
+                                               int obs_stride, const int *__restrict__ ticks, const int *__restrict__ next_ticks, const double *__restrict__ action,
+                                               const double *__restrict__ reward, const unsigned char *__restrict__ term, const unsigned char *__restrict__ trunc) {
     const long long cursor = L.cnt[DG_CURSOR], fill = L.cnt[DG_FILL], frames = L.cnt[DG_FRAMES];
     const int ns = L.n_obs + 1;
     for (long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x; x < (long long)N * DG_ROW; x += (long long)gridDim.x * blockDim.x) {
@@ -105,6 +107,11 @@ __global__ void __launch_bounds__(256) k_replay_push(DdpgDev L, int N, const flo
         L.cnt[DG_FILL] = fill + N < L.capacity ? fill + N : L.capacity;
         L.cnt[DG_FRAMES] = frames + N;
     }
+}
+__global__ void __launch_bounds__(256) k_replay_push(DdpgDev L, int N, const float *__restrict__ obs, const float *__restrict__ next_obs, const float *__restrict__ final_obs,
+                                                     int obs_stride, const int *__restrict__ ticks, const int *__restrict__ next_ticks, const double *__restrict__ action,
+                                                     const double *__restrict__ reward, const unsigned char *__restrict__ term, const unsigned char *__restrict__ trunc) {
+    ddpg_push_body(L, N, obs, next_obs, final_obs, obs_stride, ticks, next_ticks, action, reward, term, trunc);
 }
 
 // the minibatch of the current update index, gathered: out [B][DG_ROW] (tests and diagnostics; the update gathers in its first kernel)
@@ -200,8 +207,7 @@ __device__ __forceinline__ bool ddpg_gate(const DdpgDev &L, int gate) {
 }
 
 // ---- critic pass ------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(AT_THREADS) k_ddpg_critic_fwd(DdpgDev L, int B, int gate) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+__device__ __forceinline__ void ddpg_critic_fwd_body(const DdpgDev &L, int B, int gate, unsigned char *dg_smem) {
     if (!ddpg_gate(L, gate)) return;
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, L.h2p);
     const int tid = threadIdx.x, r0 = blockIdx.x * AT_TM, ns = L.n_obs + 1;
@@ -265,10 +271,13 @@ __global__ void __launch_bounds__(AT_THREADS) k_ddpg_critic_fwd(DdpgDev L, int B
     __syncthreads();
     ddpg_store_tile(T.H1, T.h1_ld, L.aD1 + (size_t)r0 * L.h1p, L.h1p);
 }
+__global__ void __launch_bounds__(AT_THREADS) k_ddpg_critic_fwd(DdpgDev L, int B, int gate) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    ddpg_critic_fwd_body(L, B, gate, dg_smem);
+}
 
 // ---- actor pass -------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(AT_THREADS) k_ddpg_actor_fwd(DdpgDev L, int B, int gate) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+__device__ __forceinline__ void ddpg_actor_fwd_body(const DdpgDev &L, int B, int gate, unsigned char *dg_smem) {
     if (!ddpg_gate(L, gate)) return;
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, L.h2p);
     const int tid = threadIdx.x, r0 = blockIdx.x * AT_TM, ns = L.n_obs + 1;
@@ -330,12 +339,15 @@ __global__ void __launch_bounds__(AT_THREADS) k_ddpg_actor_fwd(DdpgDev L, int B,
     __syncthreads();
     ddpg_store_tile(T.H1, T.h1_ld, L.aD1 + (size_t)r0 * L.h1p, L.h1p);
 }
+__global__ void __launch_bounds__(AT_THREADS) k_ddpg_actor_fwd(DdpgDev L, int B, int gate) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    ddpg_actor_fwd_body(L, B, gate, dg_smem);
+}
 
 // ---- weight gradients ---------------------------------------------------------------------------------------------------------------------------
 // One workgroup per 16 x 16 tile of out[i][j] = sum_b Lm[b][i] * Rm[b][j]; an operand with ld = 0 is a vector broadcast over its 16 columns
 // (ones: the bias gradients; dz: the last layer's).  Jobs in blockIdx order: dW1, dW0, db1, db0, dW2, db2.
-__global__ void __launch_bounds__(64 * DG_WG_WAVES) k_ddpg_wgrad(DdpgDev L, int which, int Bp, int gate) {
-    __shared__ double part_s[DG_WG_WAVES][256];
+__device__ __forceinline__ void ddpg_wgrad_body(const DdpgDev &L, int which, int Bp, int gate, double (*part_s)[256]) {
     if (!ddpg_gate(L, gate)) return;
     const DdpgNet &net = which ? L.q : L.pi;
     const int t1 = L.h2p >> 4, t0 = L.h1p >> 4;
@@ -378,13 +390,17 @@ __global__ void __launch_bounds__(64 * DG_WG_WAVES) k_ddpg_wgrad(DdpgDev L, int 
         else if (i == 0 && (!Rone || jj == 0)) out[j0 + jj] = s;
     }
 }
+__global__ void __launch_bounds__(64 * DG_WG_WAVES) k_ddpg_wgrad(DdpgDev L, int which, int Bp, int gate) {
+    __shared__ double part_s[DG_WG_WAVES][256];
+    ddpg_wgrad_body(L, which, Bp, gate, part_s);
+}
 
 // ---- Adam + Polyak + re-pack ----------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ size_t dg_packed_index(int n, int k, int kblocks) {
     return ((((size_t)(n >> 4) * kblocks + (k >> 4)) * 64) + (n & 15) + 16 * ((k & 15) >> 2)) * 4 + (k & 3);
 }
 // mode 0: Adam step with learning rate lr, Polyak, re-pack; mode 1: re-pack only (after stmpc_ddpg_set_params).  bump: this launch ends an update.
-__global__ void __launch_bounds__(256) k_ddpg_adam(DdpgDev L, int which, float lr, int mode, int bump, int gate) {
+__device__ __forceinline__ void ddpg_adam_body(const DdpgDev &L, int which, float lr, int mode, int bump, int gate) {
     if (mode == 0 && !ddpg_gate(L, gate)) return;
     const DdpgNet &net = which ? L.q : L.pi;
     const int np = dg_nparam(L.h1p, L.h2p), ow1 = dg_o_w1(L.h1p), ob1 = dg_o_b1(L.h1p, L.h2p), ob0 = dg_o_b0(L.h1p);
@@ -418,6 +434,7 @@ __global__ void __launch_bounds__(256) k_ddpg_adam(DdpgDev L, int which, float l
         if (bump) L.cnt[DG_UPDATES] = upd + 1;
     }
 }
+__global__ void __launch_bounds__(256) k_ddpg_adam(DdpgDev L, int which, float lr, int mode, int bump, int gate) { ddpg_adam_body(L, which, lr, mode, bump, gate); }
 
 // padded parameter layout -> the tensors one after the other, row-major, unpadded: W0 [h1][n_in] | b0 | W1 [h2][h1] | b1 | W2 [h2] | b2
 __global__ void k_ddpg_unpad(DdpgDev L, int n_in, const float *__restrict__ src, float *__restrict__ dst) {
@@ -435,7 +452,7 @@ __global__ void k_ddpg_unpad(DdpgDev L, int n_in, const float *__restrict__ src,
 }
 
 // last critic loss, mean Q of the last minibatch, fill, updates -> out [4] fp64; one workgroup, 64 strided partial sums in fp64, added by a butterfly: a fixed order
-__global__ void __launch_bounds__(64) k_ddpg_stats(DdpgDev L, int B, double *out) {
+__device__ __forceinline__ void ddpg_stats_body(const DdpgDev &L, int B, double *out) {
     const int lane = threadIdx.x;
     double sl = 0.0, sq = 0.0;
     for (int r = lane; r < B; r += 64) { sl += (double)L.arow[2 * r]; sq += (double)L.arow[2 * r + 1]; }
@@ -445,13 +462,13 @@ __global__ void __launch_bounds__(64) k_ddpg_stats(DdpgDev L, int B, double *out
         out[2] = (double)L.cnt[DG_FILL]; out[3] = (double)L.cnt[DG_UPDATES];
     }
 }
+__global__ void __launch_bounds__(64) k_ddpg_stats(DdpgDev L, int B, double *out) { ddpg_stats_body(L, B, out); }
 
 // ---- acting -------------------------------------------------------------------------------------------------------------------------------------
 // action [N] fp64 = clip(pi(obs, time_scale * ticks) + noise_std * gauss); gauss: Box-Muller on two 24-bit draws of splitmix64(seed ^ stream, acting call, env).
 // dbg (may be null) uint32 [N][4]: the two draws, the bits of the float32 gaussian, the bits of the float32 greedy action.
-__global__ void __launch_bounds__(AT_THREADS) k_ddpg_act(DdpgDev L, int N, const float *__restrict__ obs, int obs_stride, const int *__restrict__ ticks, int noise,
-                                                         double *__restrict__ action, unsigned int *__restrict__ dbg) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+__device__ __forceinline__ void ddpg_act_body(const DdpgDev &L, int N, const float *__restrict__ obs, int obs_stride, const int *__restrict__ ticks, int noise,
+                                              double *__restrict__ action, unsigned int *__restrict__ dbg, unsigned char *dg_smem) {
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, L.h2p);
     const int tid = threadIdx.x, e0 = blockIdx.x * AT_TM;
     const long long acts = L.cnt[DG_ACTS];
@@ -487,6 +504,11 @@ __global__ void __launch_bounds__(AT_THREADS) k_ddpg_act(DdpgDev L, int N, const
     }
     __syncthreads();
     if (noise && tid == 0 && dg_last_block(L.tick + DG_T_ACT, gridDim.x)) L.cnt[DG_ACTS] = acts + 1;
+}
+__global__ void __launch_bounds__(AT_THREADS) k_ddpg_act(DdpgDev L, int N, const float *__restrict__ obs, int obs_stride, const int *__restrict__ ticks, int noise,
+                                                         double *__restrict__ action, unsigned int *__restrict__ dbg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    ddpg_act_body(L, N, obs, obs_stride, ticks, noise, action, dbg, dg_smem);
 }
 
 }  // namespace stmpc

@@ -3,7 +3,9 @@ preset on ``sumo-jerk-continuous-v0``), whose product is the ``policy.pt`` / ``q
 
 ``DDPGLearner`` holds a replay ring filled from the env's step tensors, the actor and critic with their targets and Adam state, and runs the
 update as six HIP launches (``csrc/stmpc_ddpg_kernels.hpp``); acting, pushing and updating never synchronise with the host.  ``export_actor``
-writes the ``.npz`` that ``actor.load_weights`` / ``actor.DDPGActor`` / the combined controller read.
+writes the ``.npz`` that ``actor.load_weights`` / ``actor.DDPGActor`` / the combined controller read.  ``DDPGPopulation`` is P such learners
+on slices of one env, advanced with one launch per kernel (``csrc/stmpc_ddpg_pop_kernels.hpp``): the reference's per-seed runs
+(``train_{traffic_type}_{seed}.json``, pretrained_models/README.md) side by side, each member bit-identical to the run it would have had alone.
 
 The ``all`` library (0.5.3, requirements.txt:10) is absent from the reference checkout: the update below restates its published DDPG with the
 preset's documented constants as defaults (``DDPGConfig``); parity with the library itself is unpinned.  The network shapes are the reference's
@@ -219,7 +221,7 @@ class DDPGLearner:
         self.ctx = ctx if ctx is not None else (env.ctx if env is not None else _capi.Context(-1))
         self.seed = int(seed)
         self.device = torch.device("cuda", torch.cuda.current_device())
-        self.handle = self.ctx.ddpg_create(self.cfg.to_c(seed))
+        self.handle = self._make_handle()
         c = self.cfg
         rng = np.random.default_rng(self.seed)
         if isinstance(init, dict):
@@ -238,6 +240,9 @@ class DDPGLearner:
         z = lambda *sh, dtype=torch.float64: torch.zeros(sh, dtype=dtype, device=self.device)
         self._stats = z(4)
         self._actions = {}
+
+    def _make_handle(self):
+        return self.ctx.ddpg_create(self.cfg.to_c(self.seed))
 
     def __del__(self):
         if getattr(self, "handle", None) is not None:
@@ -335,6 +340,123 @@ class DDPGLearner:
         return path
 
 
+class _PopulationMember(DDPGLearner):
+    """One member of a ``DDPGPopulation`` as a ``DDPGLearner``: the handle is borrowed from the population (``stmpc_ddpg_pop_member``), which
+    outlives it; everything else -- the seeded initialisation included -- is the lone learner's code."""
+
+    def __init__(self, population, m, env, cfg, seed, init):
+        self._population, self._borrowed = population, population.ctx.ddpg_pop_member(population.handle, m)
+        super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
+
+    def _make_handle(self):
+        return self._borrowed
+
+    def __del__(self):
+        self.handle = None                                          # the population destroys its members
+
+
+class DDPGPopulation:
+    """P independent DDPG learners on one ``MergeVecEnv``, advanced together: one launch per kernel instead of one per member and kernel
+    (``csrc/stmpc_ddpg_pop_kernels.hpp``).  The reference trains one agent per ``train_{traffic_type}_{seed}.json`` config, a ``TRAIN_DDPG`` run
+    (ddpg.py:44-80) each, and compares them (pretrained_models/README.md); a population is those runs side by side on one device.
+
+    ``cfgs``: a list of ``DDPGConfig`` or ``(cfg, P)``; the members share n_obs, h1, h2, batch and capacity and may differ in everything else.
+    ``env.n`` must be ``P * n_per_member``: member m owns environments [m * n_per_member, (m + 1) * n_per_member).  ``seeds``: one per member
+    (None: 0 .. P-1); ``init``: as ``DDPGLearner``'s, for every member, or a list of P.  Member m starts exactly as
+    ``DDPGLearner(seed=seeds[m], init=...)`` does and stays bit-identical to that learner driven on its slice alone.
+    ``act`` / ``push`` / ``update`` / ``stats_device`` / ``stats`` are ``DDPGLearner``'s on the whole env's tensors; ``member(m)`` is a
+    ``DDPGLearner`` view (``state_dict``, ``load_state_dict``, ``export_actor``, ``grads``, ``minibatch``)."""
+
+    def __init__(self, env, cfgs, seeds=None, init=None, ctx=None):
+        if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], DDPGConfig):
+            cfgs = [cfgs[0]] * int(cfgs[1])
+        self.cfgs = list(cfgs)
+        P = self.P = len(self.cfgs)
+        if not env.continuous:
+            raise ValueError("DDPG needs the continuous action space (sumo-jerk-continuous-v0)")
+        # (a member count outside 1 ... DDPG_POP_MAX is the library's to refuse)
+        if 1 <= P <= _capi.DDPG_POP_MAX and env.n % P:
+            raise ValueError("env.n = %d is not a multiple of the population's %d members" % (env.n, P))
+        self.seeds = list(range(P)) if seeds is None else [int(x) for x in seeds]
+        inits = list(init) if isinstance(init, (list, tuple)) else [init] * P
+        if len(self.seeds) != P or len(inits) != P:
+            raise ValueError("seeds and init (if a list) have one entry per member")
+        for c in self.cfgs:
+            if c.n_obs != env.obs_dim:
+                raise ValueError("cfg.n_obs is %d, the observation has %d entries" % (c.n_obs, env.obs_dim))
+        import torch
+        self.torch = torch
+        self.env_n, self.n_per_member = env.n, (env.n // P if P >= 1 else 0)
+        self.ctx = ctx if ctx is not None else env.ctx
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.handle = self.ctx.ddpg_pop_create([c.to_c(s) for c, s in zip(self.cfgs, self.seeds)])
+        self._members = [_PopulationMember(self, m, env, self.cfgs[m], self.seeds[m], inits[m]) for m in range(P)]
+        self._lr_q, self._lr_pi = np.array([c.lr_q for c in self.cfgs]), np.array([c.lr_pi for c in self.cfgs])
+        self._stats = torch.zeros(P, 4, dtype=torch.float64, device=self.device)
+        self._actions = torch.empty(env.n, dtype=torch.float64, device=self.device)
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                self.ctx.ddpg_pop_destroy(self.handle)
+            except Exception:
+                pass
+            self.handle = None
+
+    def __len__(self):
+        return self.P
+
+    def member(self, m):
+        return self._members[m]
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _rows(self, t):
+        if t.shape[0] != self.env_n:
+            raise ValueError("%d rows given, the population's env has %d" % (t.shape[0], self.env_n))
+
+    def act(self, obs, ticks, noise=True, debug=None):
+        """``DDPGLearner.act`` for all members: row e is acted on by member e // n_per_member.  The returned tensor is reused by the next call."""
+        self._rows(obs)
+        assert obs.dtype == self.torch.float32 and ticks.dtype == self.torch.int32 and obs.stride(1) == 1
+        self.ctx.ddpg_pop_act(self.handle, self.n_per_member, obs.data_ptr(), obs.stride(0), ticks.data_ptr(), noise, self._actions.data_ptr(),
+                              debug.data_ptr() if debug is not None else 0, self._stream())
+        return self._actions
+
+    def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
+        """``DDPGLearner.push`` for all members: each member's slice of the step goes into its own ring."""
+        torch = self.torch
+        self._rows(obs)
+        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == reward.dtype == torch.float64 and ticks.dtype == torch.int32
+        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
+        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+        self.ctx.ddpg_pop_push(self.handle, self.n_per_member, obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0,
+                               obs.stride(0), ticks.data_ptr(), next_ticks.data_ptr() if next_ticks is not None else 0, action.data_ptr(), reward.data_ptr(),
+                               terminated.data_ptr(), truncated.data_ptr(), self._stream())
+
+    def _lr(self, lr, default):
+        if lr is None:
+            return default
+        lr = np.asarray(lr, dtype=np.float64)
+        return np.full(self.P, float(lr)) if lr.ndim == 0 else lr       # (the library checks a given array's length)
+
+    def update(self, n=1, lr_q=None, lr_pi=None):
+        """``n`` updates of every member, six launches each; a member whose replay_start gate is still shut skips its own.  ``lr_q`` / ``lr_pi``:
+        a scalar or one value per member (default: each member's cfg's)."""
+        self.ctx.ddpg_pop_update(self.handle, n, self._lr(lr_q, self._lr_q), self._lr(lr_pi, self._lr_pi), self._stream())
+
+    def stats_device(self):
+        """fp64 [P][4] device tensor: per member, critic loss and mean Q of the last minibatch, fill, updates done (asynchronous)."""
+        self.ctx.ddpg_pop_stats(self.handle, self._stats.data_ptr(), self._stream())
+        return self._stats
+
+    def stats(self):
+        """The same as a dict of arrays of length P; synchronises."""
+        s = self.stats_device().cpu().numpy()
+        return {"critic_loss": s[:, 0].copy(), "mean_q": s[:, 1].copy(), "fill": s[:, 2].astype(np.int64), "updates": s[:, 3].astype(np.int64)}
+
+
 def write_actor(path, net, tanh_scale, tanh_mean):
     """The file format of ``actor.load_weights`` for a net {w0, b0, w1, b1, w2, b2}."""
     with open(path, "wb") as fh:
@@ -345,10 +467,12 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
     """The loop of the reference's ``DDPGAgent.train`` on the device: act with noise -> env.step -> push -> ``updates_per_step`` updates, until
     ``frames`` transitions were collected (rounded up to whole steps of env.n).  Synchronises only every ``drain_every`` steps, to drain the
     finished episodes' statistics.  ``lr_schedule(step, steps) -> (lr_q, lr_pi)``: e.g. the preset's cosine schedule, computed on the host.
-    Returns {"steps", "frames", "episodes", "mean_return" (of the drained episodes), "returns" (array)}."""
+    Returns {"steps", "frames", "episodes", "mean_return" (of the drained episodes), "returns" (array)}.
+    ``learner`` may be a ``DDPGPopulation`` (the schedule may then return per-member arrays); the result then also carries
+    ``member_returns``: the drained returns of each member's environments, a list of P arrays."""
     steps = -(-int(frames) // env.n)
     obs = env.reset()
-    returns = []
+    returns, envs = [], []
     for i in range(steps):
         ticks = env.episode_ticks.clone()
         action = learner.act(obs, ticks, noise=True)
@@ -359,7 +483,13 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
             learner.update(updates_per_step, lr_q, lr_pi)
         obs = next_obs
         if (i + 1) % drain_every == 0 or i + 1 == steps:
-            returns.append(env.drain_episode_stats()["episode_return"])
+            drained = env.drain_episode_stats()
+            returns.append(drained["episode_return"])
+            envs.append(drained["env"])
     returns = np.concatenate(returns) if returns else np.zeros(0)
-    return {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
-            "returns": returns}
+    out = {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
+           "returns": returns}
+    if isinstance(learner, DDPGPopulation):
+        owner = (np.concatenate(envs) if envs else np.zeros(0, dtype=np.int64)) // learner.n_per_member
+        out["member_returns"] = [returns[owner == m] for m in range(learner.P)]
+    return out
