@@ -18,6 +18,8 @@
  *                                network stays the caller's; everything around it runs here)
  *   stmpc_policy_features_device <- dqn.get_state_vector_from_base_state  dqn.py:389-446 (+ the float32 cast and TimeFeature input of ddpg.py:41,84)
  *   stmpc_actor_eval_device   <- DDPGAgent.get_control                ddpg.py:83-87 (state vector + the pretrained policy network, one launch)
+ *   stmpc_actor_view_ddpg     <- the closing `evaluate` of ddpg.train_ddpg_all_with_lr_drop (the model just trained, evaluated where it lies)
+ *   stmpc_actor_pop_*         <- DDPGAgent.load + get_control for several MODEL_NAMEs (ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json), one launch
  *   stmpc_env_*               <- merge_gym.JerkEnv / ContinuousJerkEnv / AccelerationEnv  merge_gym.py:15-221 with the rewards of
  *                                dqn.get_reward_function (dqn.py:449-563, rl.py:168-174), batched on the SUMO-free world (stmpc_sim_*)
  *   stmpc_rec_*               <- the per-tick histories of control.run_episode (control.py:247-254, 280-289), the position bins of
@@ -642,6 +644,34 @@ int  stmpc_ddpg_pop_push_device(stmpc_ddpg_pop *pop, int n_per_member, const flo
                                 const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream);
 int  stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *pop, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream);
 int  stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *pop, double *d_out, void *stream);
+
+/*
+ * Actors straight from learners, and a population of actors evaluated in one launch.  The reference's workflow ends a training with an evaluation
+ * of the model it trained (ddpg.train_ddpg_all_with_lr_drop's closing `evaluate`, ddpg.py:96-117) and publishes a matrix of EVALUATE_COMBINED_DDPG runs, one per
+ * MODEL_NAME (DDPGAgent.load + get_control, ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json, experiment_data/saved_data.csv).  (Additive: new
+ * entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)
+ *   stmpc_actor_view_ddpg   a BORROWED actor whose tensors ALIAS the learner's online (target = 0) or target (target = 1) actor: the learner keeps both
+ *                   packed for the kernel after every update, so no copy is made, and the output bias is read through a pointer at every evaluation.
+ *                   An evaluation ordered after an update ON THE SAME STREAM sees the updated weights; across streams the order is the caller's to
+ *                   establish.  The arithmetic is stmpc_actor_eval_device's float32 chain and tanhf, as for the learner's exported file -- not
+ *                   stmpc_ddpg_act_device's fp64 output dot.  Valid until the learner is destroyed: destroy the view first, with stmpc_actor_destroy,
+ *                   which frees nothing the learner owns.  Works on handles lent by stmpc_ddpg_pop_member; stmpc_actor_eval_device takes a view like
+ *                   any actor, from any context on the learner's device.
+ *   stmpc_actor_pop_create  P = 1 ... STMPC_DDPG_POP_MAX actors (created or views) that share n_in, the padded hidden widths and the context's device
+ *                   (one launch shape, one LDS size), else STMPC_EINVAL; the squash may differ per member.  The members stay the caller's and must
+ *                   outlive the population, which holds a device table of their descriptions.
+ *   stmpc_actor_pop_eval_device   stmpc_actor_eval_device on arrays of P * n_per_member rows: member m evaluates rows [m * n_per_member, (m + 1) *
+ *                   n_per_member), bit-identical to stmpc_actor_eval_device with that member on that slice; same argument checks (step > 1 needs a
+ *                   rollout of P * n_per_member states in the context).
+ */
+typedef struct stmpc_actor_pop stmpc_actor_pop;
+int  stmpc_actor_view_ddpg(stmpc_ddpg *learner, int target, stmpc_actor **out);
+int  stmpc_actor_pop_create(stmpc_ctx *ctx, const stmpc_actor *const *actors, int P, stmpc_actor_pop **out);
+void stmpc_actor_pop_destroy(stmpc_actor_pop *pop);
+int  stmpc_actor_pop_size(const stmpc_actor_pop *pop);
+int  stmpc_actor_pop_eval_device(stmpc_ctx *ctx, const stmpc_actor_pop *pop, const stmpc_policy_features_cfg *cfg, int n_per_member, int Kmax, int step,
+                                 const double *d_cur_ego4, const int32_t *d_k_count, const double *d_cur_other_x, const double *d_cur_other_v,
+                                 const double *d_cur_other_a, int32_t *d_evals, float *d_feat, int feat_stride, double *d_jerk, void *stream);
 
 /*
  * Episode flight recorder on the device, next to the world (stmpc_sim_*): the per-tick histories the reference's evaluation keeps and what it

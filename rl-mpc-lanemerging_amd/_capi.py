@@ -164,6 +164,7 @@ EXPORTS = (
     "stmpc_abi_version", "stmpc_check_error", "stmpc_predict_batch_acc", "stmpc_sim_status_device",
     "stmpc_policy_features_device", "stmpc_policy_features_len", "stmpc_combined_counts", "stmpc_solve_batch_device_ac",
     "stmpc_actor_create", "stmpc_actor_destroy", "stmpc_actor_eval_device",
+    "stmpc_actor_view_ddpg", "stmpc_actor_pop_create", "stmpc_actor_pop_destroy", "stmpc_actor_pop_size", "stmpc_actor_pop_eval_device",
     "stmpc_env_reset_device", "stmpc_env_step_device", "stmpc_env_reward_device", "stmpc_env_drain", "stmpc_env_episode_seed",
     "stmpc_env_episode_ticks_device",
     "stmpc_ddpg_create", "stmpc_ddpg_destroy", "stmpc_ddpg_set_params", "stmpc_ddpg_get_params", "stmpc_ddpg_set_state", "stmpc_ddpg_get_state",
@@ -303,6 +304,12 @@ def load():
     lib.stmpc_ddpg_pop_push_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 6 + [vp]
     lib.stmpc_ddpg_pop_update_device.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, vp]
     lib.stmpc_ddpg_pop_stats_device.argtypes = [vp, vp, vp]
+    lib.stmpc_actor_view_ddpg.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    lib.stmpc_actor_pop_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
+    lib.stmpc_actor_pop_destroy.argtypes = [vp]
+    lib.stmpc_actor_pop_destroy.restype = None
+    lib.stmpc_actor_pop_size.argtypes = [vp]
+    lib.stmpc_actor_pop_eval_device.argtypes = [vp, vp, C.POINTER(FeaturesCfg), C.c_int, C.c_int, C.c_int] + [vp] * 7 + [C.c_int, vp, vp]
     lib.stmpc_rec_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_int, C.POINTER(vp)]
     lib.stmpc_rec_destroy.argtypes = [vp]
     lib.stmpc_rec_destroy.restype = None
@@ -596,6 +603,32 @@ class Context:
         """One launch: state vectors + the packed network -> proposed jerk [N] fp64 (``stmpc_actor_eval_device``)."""
         self._chk(self._lib.stmpc_actor_eval_device(self._h, handle, C.byref(fcfg), int(N), int(Kmax), int(step), d_cur_ego4, d_k, d_cur_ox, d_cur_ov,
                                                     d_cur_oa, d_evals, d_feat, int(feat_stride), d_jerk, stream))
+
+    # -- actors from learners, and a population of actors (stmpc_actor_view_ddpg, stmpc_actor_pop_*) -------------
+    def actor_view_ddpg(self, learner_handle, target=False):
+        """A borrowed actor aliasing the learner's online (or target) actor: no copy; ``actor_destroy`` it before the learner goes."""
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_actor_view_ddpg(learner_handle, int(bool(target)), C.byref(h)))
+        return h
+
+    def actor_pop_create(self, handles):
+        """``handles``: a sequence of actor handles (created or views); the library checks the member count and that the shapes are common."""
+        arr = (C.c_void_p * len(handles))(*handles)
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_actor_pop_create(self._h, arr, len(handles), C.byref(h)))
+        return h
+
+    def actor_pop_destroy(self, handle):
+        self._lib.stmpc_actor_pop_destroy(handle)
+
+    def actor_pop_size(self, handle):
+        return int(self._lib.stmpc_actor_pop_size(handle))
+
+    def actor_pop_eval_device(self, handle, fcfg, n_per_member, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_evals, d_feat, feat_stride, d_jerk,
+                              stream=0):
+        """One launch for all members, member m on rows [m * n_per_member, (m + 1) * n_per_member) (``stmpc_actor_pop_eval_device``)."""
+        self._chk(self._lib.stmpc_actor_pop_eval_device(self._h, handle, C.byref(fcfg), int(n_per_member), int(Kmax), int(step), d_cur_ego4, d_k, d_cur_ox,
+                                                        d_cur_ov, d_cur_oa, d_evals, d_feat, int(feat_stride), d_jerk, stream))
 
     def combined_counts(self, reset=False):
         """(decisions taken, controller solves run for them) since the last reset."""

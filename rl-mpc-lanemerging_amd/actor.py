@@ -125,7 +125,38 @@ class DDPGActor:
         self.feat = torch.empty(self.n, self.flen, dtype=torch.float32, device=dev)
         self.jerk = torch.empty(self.n, dtype=torch.float64, device=dev)
         self.keep_features = False                # hip engine: also write the input vectors to ``self.feat`` (parity checks)
+        self.shape = (int(w["w0"].shape[1]), int(w["w0"].shape[0]), int(w["w1"].shape[0]))      # n_in, h1, h2
         self.handle = ctx.actor_create(w) if engine == "hip" else None
+
+    @classmethod
+    def from_learner(cls, learner, n, ctx, S, target=False, time_feature=True):
+        """A zero-copy VIEW of a ``learner.DDPGLearner``'s online (``target=True``: target) actor (``stmpc_actor_view_ddpg``; hip engine only):
+        the learner keeps both packed for the kernel after every update, so nothing is exported, written or uploaded, and an evaluation queued
+        after an update on the same stream sees the updated weights (across streams the order is the caller's).  The arithmetic is the fused
+        kernel's float32 chain, as for the learner's exported file.  The view holds the learner, so the learner cannot be collected first."""
+        import torch
+        self = cls.__new__(cls)
+        self.torch, self.ctx, self.n, self.engine, self.dtype = torch, ctx, int(n), "hip", torch.float32
+        self.learner, self.target = learner, bool(target)
+        self.name = "view of %r (%s actor)" % (learner, "target" if target else "online")
+        c = learner.cfg
+        self.scale, self.mean, self.shape = c.tanh_scale, c.tanh_mean, (c.n_obs + 1, c.h1, c.h2)
+        self._buffers(S, time_feature, learner.device)
+        self.handle = ctx.actor_view_ddpg(learner.handle, target)
+        return self
+
+    def _buffers(self, S, time_feature, dev):
+        torch = self.torch
+        self.fcfg = _capi.FeaturesCfg.from_settings(S, time_feature=True)
+        if not time_feature:
+            self.fcfg.time_scale = 0.0
+        self.flen = (self.fcfg.cars_ahead + self.fcfg.cars_behind) * (4 if self.fcfg.use_acceleration else 3) + 5
+        if self.flen != self.shape[0]:
+            raise ValueError("the actor takes %d inputs, the state vector of these settings has %d" % (self.shape[0], self.flen))
+        self.evals = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.feat = torch.empty(self.n, self.flen, dtype=torch.float32, device=dev)
+        self.jerk = torch.empty(self.n, dtype=torch.float64, device=dev)
+        self.keep_features = False
 
     def __del__(self):
         if getattr(self, "handle", None) is not None:
@@ -143,9 +174,7 @@ class DDPGActor:
 
     def _check_rows(self, cur_ego4, k, cur_ox, cur_ov, cur_oa):
         # the kernels are launched for self.n states and write self.jerk / self.feat / self.evals of that length
-        for name, t_ in (("cur_ego4", cur_ego4), ("k", k), ("cur_ox", cur_ox), ("cur_ov", cur_ov), ("cur_oa", cur_oa)):
-            if t_ is not None and t_.shape[0] != self.n:
-                raise ValueError("%s has %d rows, this actor was built for %d states" % (name, t_.shape[0], self.n))
+        _check_rows(self.n, cur_ego4, k, cur_ox, cur_ov, cur_oa)
 
     def features(self, step, cur_ego4, k, cur_ox, cur_ov, cur_oa, stream=None):
         torch = self.torch
@@ -173,6 +202,88 @@ class DDPGActor:
         with self.torch.no_grad():
             feat = self.features(step, cur_ego4, k, cur_ox, cur_ov, cur_oa)
             return self.forward(feat).to(self.torch.float64)
+
+
+def _check_rows(n, cur_ego4, k, cur_ox, cur_ov, cur_oa):
+    for name, t_ in (("cur_ego4", cur_ego4), ("k", k), ("cur_ox", cur_ox), ("cur_ov", cur_ov), ("cur_oa", cur_oa)):
+        if t_ is not None and t_.shape[0] != n:
+            raise ValueError("%s has %d rows, this actor was built for %d states" % (name, t_.shape[0], n))
+
+
+class ActorPopulation:
+    """P actors, each on its own slice of one batch, evaluated in ONE launch (``k_actor_eval_pop``, csrc/stmpc_actor_pop_kernels.hpp): the
+    reference's per-model ``EVALUATE_COMBINED_DDPG`` runs (``DDPGAgent.load`` + ``get_control`` for the MODEL_NAME of each
+    ``configs/combined_<traffic>_{1,2,3}.json``) side by side, and the evaluation ``train_ddpg_all_with_lr_drop`` ends with, for every member
+    of a trained population at once.
+
+    ``members``: a list whose items are shipped names or ``.npz`` paths, ``learner.DDPGLearner``s (a zero-copy view each, see
+    ``DDPGActor.from_learner``) or existing hip-engine ``DDPGActor``s; or a ``learner.DDPGPopulation`` (one view per member).  The members share the
+    network's shape; the squash may differ.  Member m evaluates rows [m * n_per_member, (m + 1) * n_per_member) and is bit-identical to a lone
+    ``DDPGActor`` on that slice.  Same call signature as ``DDPGActor``: ``combined.decide_batch_device`` and ``episodes.EpisodeRunner`` take it as
+    they are (the runner then reports per member).  In a runner the members face different environments of one world: identically distributed
+    episodes, not common random numbers."""
+
+    def __init__(self, members, n_per_member, ctx, S, time_feature=True):
+        import torch
+        self.torch, self.ctx = torch, ctx
+        if hasattr(members, "member") and hasattr(members, "P"):                 # a learner.DDPGPopulation
+            members = [members.member(m) for m in range(members.P)]
+        members = list(members)
+        if not 1 <= len(members) <= _capi.DDPG_POP_MAX:
+            raise ValueError("a population has 1 ... %d members, not %d" % (_capi.DDPG_POP_MAX, len(members)))
+        self.P, self.n_per_member = len(members), int(n_per_member)
+        if self.n_per_member < 1:
+            raise ValueError("n_per_member must be positive")
+        self.n = self.P * self.n_per_member
+        self.members = []
+        for item in members:
+            if isinstance(item, DDPGActor):
+                if item.engine != "hip":
+                    raise ValueError("a population evaluates hip-engine actors, not %r" % (item.engine,))
+                a = item
+            elif isinstance(item, (str, os.PathLike)):
+                a = DDPGActor(os.fspath(item), 1, ctx, S, time_feature=time_feature)      # (its own row buffers stay unused: the population has them)
+            elif hasattr(item, "export_actor") and hasattr(item, "handle"):     # a learner.DDPGLearner
+                a = DDPGActor.from_learner(item, 1, ctx, S, time_feature=time_feature)
+            else:
+                raise ValueError("a member is a shipped name, an .npz path, a DDPGLearner or a DDPGActor, not %r" % (item,))
+            self.members.append(a)
+        pad = lambda sh: (sh[0], (sh[1] + 15) & ~15, (sh[2] + 15) & ~15)
+        for m, a in enumerate(self.members):
+            if pad(a.shape) != pad(self.members[0].shape):
+                raise ValueError("member %d is %d -> %d -> %d -> 1, member 0 is %d -> %d -> %d -> 1: one launch needs one shape" % ((m,) + a.shape + self.members[0].shape))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.fcfg = _capi.FeaturesCfg.from_settings(S, time_feature=True)
+        if not time_feature:
+            self.fcfg.time_scale = 0.0
+        self.flen = self.members[0].flen
+        self.evals = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.feat = torch.empty(self.n, self.flen, dtype=torch.float32, device=dev)
+        self.jerk = torch.empty(self.n, dtype=torch.float64, device=dev)
+        self.keep_features = False
+        self.handle = ctx.actor_pop_create([a.handle for a in self.members])
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                self.ctx.actor_pop_destroy(self.handle)
+            except Exception:
+                pass
+            self.handle = None
+
+    def reset(self, mask=None):
+        if mask is None:
+            self.evals.zero_()
+        else:
+            self.evals.masked_fill_(mask, 0)
+
+    def __call__(self, step, cur_ego4, k, cur_ox, cur_ov, cur_oa):
+        _check_rows(self.n, cur_ego4, k, cur_ox, cur_ov, cur_oa)
+        stream = self.torch.cuda.current_stream().cuda_stream
+        self.ctx.actor_pop_eval_device(self.handle, self.fcfg, self.n_per_member, cur_ox.shape[1], step, cur_ego4.data_ptr(), k.data_ptr(), cur_ox.data_ptr(),
+                                       cur_ov.data_ptr(), cur_oa.data_ptr() if cur_oa is not None else 0, self.evals.data_ptr(),
+                                       self.feat.data_ptr() if self.keep_features else 0, self.flen, self.jerk.data_ptr(), stream)
+        return self.jerk
 
 
 def forward_host(w, feat, dtype=np.float32):

@@ -9,6 +9,7 @@
 #include "stmpc_env_kernels.hpp"
 #include "stmpc_ddpg_kernels.hpp"
 #include "stmpc_ddpg_pop_kernels.hpp"
+#include "stmpc_actor_pop_kernels.hpp"
 #include "stmpc_rec_kernels.hpp"
 
 #include <math.h>
@@ -1531,7 +1532,7 @@ int stmpc_policy_features_len(const stmpc_policy_features_cfg *f) {
 // ---- the policy network itself (optional: the caller may keep it in its own framework and only use stmpc_policy_features_device) ----
 struct stmpc_actor {
     int device = 0;
-    DevBuf p0, b0, p1, b1, w2;
+    DevBuf p0, b0, p1, b1, w2, b2;      // empty for a view (stmpc_actor_view_ddpg): dev then points into the learner's arrays
     ActorDev dev{};
     size_t lds = 0;
 };
@@ -1551,6 +1552,38 @@ std::vector<float> pack_layer(const float *W, int rows, int cols, int rows_p, in
     return out;
 }
 int upload(DevBuf &b, const std::vector<float> &v) { return upload(b, v.data(), v.size()); }
+size_t actor_lds_bytes(int h1p, int h2p) { return ((size_t)AT_TM * AT_KIN + (size_t)AT_TM * (h1p + 4) + (size_t)AT_TM * (h2p + 4)) * sizeof(float); }
+// dynamic LDS of k_actor_eval (which = 0) / k_actor_eval_pop (1)
+// (the attribute belongs to the kernel, not to an actor: only ever raised, so that a narrower actor created later does not take the
+// dynamic LDS away from a wider one that is still in use)
+int actor_raise_lds(int which, int device, size_t lds) {
+    static size_t actor_lds_max[2][16] = {{0}};
+    size_t &lds_max = actor_lds_max[which][(unsigned)device & 15u];
+    if (lds > 48 * 1024 && lds > lds_max) {
+        const void *fn = which ? (const void *)k_actor_eval_pop : (const void *)k_actor_eval;
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(STMPC_EHIP, which ? "hipFuncSetAttribute(k_actor_eval_pop, dynamic LDS) failed" : "hipFuncSetAttribute(k_actor_eval, dynamic LDS) failed");
+        }
+        lds_max = lds;
+    }
+    return STMPC_OK;
+}
+// the argument checks stmpc_actor_eval_device and stmpc_actor_pop_eval_device share; N: all rows of the call
+int actor_eval_checks(const stmpc_ctx *c, int device, int n_in, const stmpc_policy_features_cfg *f, int N, int Kmax, int step, const double *d_cur_ego4,
+                      const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov, const int32_t *d_evals, const float *d_feat, int feat_stride,
+                      const double *d_jerk, FeatCfg *fc) {
+    if (device != c->device) return fail(STMPC_EINVAL, "actor and context are on different devices");
+    if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT || step < 1) return fail(STMPC_EINVAL, "N, Kmax or step out of range");
+    TRY(make_featcfg(f, fc));
+    if (stmpc_policy_features_len(f) != n_in) return fail(STMPC_EINVAL, "the actor's input width is not the length of this state vector");
+    if (d_feat && feat_stride < n_in) return fail(STMPC_EINVAL, "feat_stride is shorter than the feature vector");
+    if (N == 0) return STMPC_OK;
+    if (!d_cur_ego4 || !d_k || !d_jerk) return fail(STMPC_EINVAL, "NULL device pointer");
+    if (Kmax > 0 && (!d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
+    if (f->time_feature && !d_evals) return fail(STMPC_EINVAL, "time_feature needs the evaluation counters");
+    return STMPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1563,30 +1596,19 @@ int stmpc_actor_create(stmpc_ctx *c, int n_in, int h1, int h2, const float *w0, 
     if (n_in < 1 || n_in > AT_KIN || h1 < 1 || h1 > 1024 || h2 < 1 || h2 > 1024) return fail(STMPC_EINVAL, "actor shape out of range (n_in <= 32, hidden widths <= 1024)");
     HIPCHK(hipSetDevice(c->device));
     const int h1p = (h1 + 15) & ~15, h2p = (h2 + 15) & ~15;
-    const size_t lds = ((size_t)AT_TM * AT_KIN + (size_t)AT_TM * (h1p + 4) + (size_t)AT_TM * (h2p + 4)) * sizeof(float);
+    const size_t lds = actor_lds_bytes(h1p, h2p);
     if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, "actor too wide for one workgroup's LDS");
     stmpc_actor *a = new stmpc_actor();
     a->device = c->device; a->lds = lds;
-    std::vector<float> vb0(h1p, 0.f), vb1(h2p, 0.f), vw2(h2p, 0.f);
+    std::vector<float> vb0(h1p, 0.f), vb1(h2p, 0.f), vw2(h2p, 0.f), vb2(1, b2[0]);
     for (int i = 0; i < h1; ++i) vb0[i] = b0[i];
     for (int i = 0; i < h2; ++i) { vb1[i] = b1[i]; vw2[i] = w2[i]; }
     int rc;
     if ((rc = upload(a->p0, pack_layer(w0, h1, n_in, h1p, AT_KIN))) || (rc = upload(a->b0, vb0)) || (rc = upload(a->p1, pack_layer(w1, h2, h1, h2p, h1p))) ||
-        (rc = upload(a->b1, vb1)) || (rc = upload(a->w2, vw2))) { stmpc_actor_destroy(a); return rc; }
+        (rc = upload(a->b1, vb1)) || (rc = upload(a->w2, vw2)) || (rc = upload(a->b2, vb2))) { stmpc_actor_destroy(a); return rc; }
     a->dev.p0 = a->p0.as<float>(); a->dev.b0 = a->b0.as<float>(); a->dev.p1 = a->p1.as<float>(); a->dev.b1 = a->b1.as<float>(); a->dev.w2 = a->w2.as<float>();
-    a->dev.b2 = b2[0]; a->dev.scale = (float)tanh_scale; a->dev.mean = (float)tanh_mean; a->dev.n_in = n_in; a->dev.h1p = h1p; a->dev.h2p = h2p;
-    // (the attribute belongs to the kernel, not to this actor: only ever raised, so that a narrower actor created later does not take the
-    // dynamic LDS away from a wider one that is still in use)
-    static size_t actor_lds_max[16] = {0};
-    size_t &lds_max = actor_lds_max[(unsigned)c->device & 15u];
-    if (lds > 48 * 1024 && lds > lds_max) {
-        if (hipFuncSetAttribute((const void *)k_actor_eval, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();
-            stmpc_actor_destroy(a);
-            return fail(STMPC_EHIP, "hipFuncSetAttribute(k_actor_eval, dynamic LDS) failed");
-        }
-        lds_max = lds;
-    }
+    a->dev.b2p = a->b2.as<float>(); a->dev.scale = (float)tanh_scale; a->dev.mean = (float)tanh_mean; a->dev.n_in = n_in; a->dev.h1p = h1p; a->dev.h2p = h2p;
+    if ((rc = actor_raise_lds(0, c->device, lds))) { stmpc_actor_destroy(a); return rc; }
     *out = a;
     return STMPC_OK;
 }
@@ -1601,16 +1623,9 @@ int stmpc_actor_eval_device(stmpc_ctx *c, const stmpc_actor *a, const stmpc_poli
                             const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa, int32_t *d_evals, float *d_feat,
                             int feat_stride, double *d_jerk, void *stream) {
     if (!c || !a || !f) return fail(STMPC_EINVAL, "NULL argument");
-    if (a->device != c->device) return fail(STMPC_EINVAL, "actor and context are on different devices");
-    if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT || step < 1) return fail(STMPC_EINVAL, "N, Kmax or step out of range");
     FeatCfg fc;
-    TRY(make_featcfg(f, &fc));
-    if (stmpc_policy_features_len(f) != a->dev.n_in) return fail(STMPC_EINVAL, "the actor's input width is not the length of this state vector");
-    if (d_feat && feat_stride < a->dev.n_in) return fail(STMPC_EINVAL, "feat_stride is shorter than the feature vector");
+    TRY(actor_eval_checks(c, a->device, a->dev.n_in, f, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_evals, d_feat, feat_stride, d_jerk, &fc));
     if (N == 0) return STMPC_OK;
-    if (!d_cur_ego4 || !d_k || !d_jerk) return fail(STMPC_EINVAL, "NULL device pointer");
-    if (Kmax > 0 && (!d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
-    if (f->time_feature && !d_evals) return fail(STMPC_EINVAL, "time_feature needs the evaluation counters");
     const int *live;
     TRY(rollout_live(c, N, step, &live));
     HIPCHK(hipSetDevice(c->device));
@@ -2382,6 +2397,90 @@ int stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *p, double *d_out, void *stream) 
     if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(p->device));
     hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->members[0]->cfg.batch, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- actors from learners, and a population of actors (stmpc_actor_view_ddpg, stmpc_actor_pop_*); kernel in stmpc_actor_pop_kernels.hpp -----------
+struct stmpc_actor_pop {
+    int device = 0;
+    DevBuf table;                           // ActorDev [P]: the members' structs (a view's pointers are fixed for its learner's lifetime)
+    int P = 0, n_in = 0;
+    size_t lds = 0;
+    const ActorDev *dev() const { return table.as<ActorDev>(); }
+};
+
+extern "C" {
+
+int stmpc_actor_view_ddpg(stmpc_ddpg *l, int target, stmpc_actor **out) {
+    if (!l || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (target != 0 && target != 1) return fail(STMPC_EINVAL, "target must be 0 (online actor) or 1 (target actor)");
+    // k_ddpg_adam keeps both actors packed in actor_layer's lane order; biases and the last layer are read in place in the padded parameter array
+    const DdpgNet &pi = l->dev.pi;
+    const float *w = target ? pi.wt : pi.w;
+    HIPCHK(hipSetDevice(l->device));
+    stmpc_actor *a = new stmpc_actor();     // owns no buffer: destroying it frees nothing of the learner's
+    a->device = l->device; a->lds = actor_lds_bytes(l->h1p, l->h2p);
+    a->dev.p0 = target ? pi.t0 : pi.p0; a->dev.b0 = w + dg_o_b0(l->h1p);
+    a->dev.p1 = target ? pi.t1 : pi.p1; a->dev.b1 = w + dg_o_b1(l->h1p, l->h2p);
+    a->dev.w2 = w + dg_o_w2(l->h1p, l->h2p); a->dev.b2p = w + dg_o_b2(l->h1p, l->h2p);
+    a->dev.scale = l->dev.scale; a->dev.mean = l->dev.mean; a->dev.n_in = pi.n_in; a->dev.h1p = l->h1p; a->dev.h2p = l->h2p;
+    const int rc = actor_raise_lds(0, l->device, a->lds);
+    if (rc) { stmpc_actor_destroy(a); return rc; }
+    *out = a;
+    return STMPC_OK;
+}
+
+int stmpc_actor_pop_create(stmpc_ctx *c, const stmpc_actor *const *actors, int P, stmpc_actor_pop **out) {
+    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (P < 1 || P > STMPC_DDPG_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
+    if (!actors) return fail(STMPC_EINVAL, "NULL argument");
+    std::vector<ActorDev> host;
+    for (int m = 0; m < P; ++m) {
+        const stmpc_actor *a = actors[m];
+        if (!a) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " is NULL");
+        if (a->device != c->device) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " and the context are on different devices");
+        if (a->dev.n_in != actors[0]->dev.n_in || a->dev.h1p != actors[0]->dev.h1p || a->dev.h2p != actors[0]->dev.h2p)
+            return fail(STMPC_EINVAL, "the members of a population share n_in and the padded hidden widths (member " + std::to_string(m) + " differs from member 0)");
+        host.push_back(a->dev);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_actor_pop *p = new stmpc_actor_pop();
+    p->device = c->device; p->P = P; p->n_in = host[0].n_in; p->lds = actors[0]->lds;
+    int rc = p->table.ensure(host.size() * sizeof(ActorDev));
+    if (!rc && hipMemcpy(p->table.p, host.data(), host.size() * sizeof(ActorDev), hipMemcpyHostToDevice) != hipSuccess) rc = fail(STMPC_EHIP, "hipMemcpy of the member table failed");
+    if (!rc) rc = actor_raise_lds(1, c->device, p->lds);
+    if (rc) { stmpc_actor_pop_destroy(p); return rc; }
+    *out = p;
+    return STMPC_OK;
+}
+
+void stmpc_actor_pop_destroy(stmpc_actor_pop *p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    delete p;
+}
+
+int stmpc_actor_pop_size(const stmpc_actor_pop *p) { return p ? p->P : 0; }
+
+int stmpc_actor_pop_eval_device(stmpc_ctx *c, const stmpc_actor_pop *p, const stmpc_policy_features_cfg *f, int n_per_member, int Kmax, int step,
+                                const double *d_cur_ego4, const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa,
+                                int32_t *d_evals, float *d_feat, int feat_stride, double *d_jerk, void *stream) {
+    if (!c || !p || !f) return fail(STMPC_EINVAL, "NULL argument");
+    if (n_per_member < 0 || (long long)n_per_member * p->P > 0x7fffffffLL) return fail(STMPC_EINVAL, "n_per_member out of range");
+    const int N = n_per_member * p->P;
+    FeatCfg fc;
+    TRY(actor_eval_checks(c, p->device, p->n_in, f, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_evals, d_feat, feat_stride, d_jerk, &fc));
+    if (N == 0) return STMPC_OK;
+    const int *live;
+    TRY(rollout_live(c, N, step, &live));
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_actor_eval_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, p->P), dim3(AT_THREADS), p->lds, (hipStream_t)stream, fc, p->dev(), n_per_member, Kmax,
+                       d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, d_evals, d_feat, feat_stride, d_jerk);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }

@@ -25,7 +25,8 @@ struct ActorDev {                   // device pointers + shape of one packed act
     const float *p0, *b0;           // [h1p / 16][AT_KIN / 16][64][4], [h1p]
     const float *p1, *b1;           // [h2p / 16][h1p / 16][64][4], [h2p]
     const float *w2;                // [h2p]
-    float b2, scale, mean;
+    const float *b2p;               // [1]: the output bias, read where it lives (a view of a learner's actor sees every update; stmpc_actor_view_ddpg)
+    float scale, mean;
     int n_in, h1p, h2p;             // h1p, h2p: hidden widths padded to multiples of 16 (pad weights and biases are zero)
 };
 
@@ -75,18 +76,21 @@ __device__ __forceinline__ void actor_layer(const float *in, int in_ld, int kp, 
 }
 
 // feat_out (may be null): the input vectors as the network saw them, [N][feat_stride]; jerk_out [N] fp64.
-__global__ void __launch_bounds__(AT_THREADS) k_actor_eval(FeatCfg f, ActorDev A, int N, int Kmax, const double *__restrict__ ego4, const int *__restrict__ k_count,
-                                                           const double *__restrict__ ox, const double *__restrict__ ov, const double *__restrict__ oa,
-                                                           const int *__restrict__ live, int *evals, float *feat_out, int feat_stride, double *jerk_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char at_smem[];
+// The evaluation of rows [row0 + 16 blockIdx.x, + 16) with actor A, as far as row0 + rows: row0 = 0 and rows = N for a lone actor; a member of a
+// population (stmpc_actor_pop_kernels.hpp) has its slice's first row and length here.  The state arrays, evals, live, feat_out and jerk_out are
+// indexed by the global row.
+__device__ __forceinline__ void actor_eval_body(const FeatCfg &f, const ActorDev &A, int row0, int rows, int Kmax, const double *__restrict__ ego4,
+                                                const int *__restrict__ k_count, const double *__restrict__ ox, const double *__restrict__ ov,
+                                                const double *__restrict__ oa, const int *__restrict__ live, int *evals, float *feat_out, int feat_stride,
+                                                double *jerk_out, unsigned char *at_smem) {
     const int h1_ld = A.h1p + 4, h2_ld = A.h2p + 4;                 // (+4 floats: rows start 16 B apart modulo the banks)
     float *X = (float *)at_smem;                                   // [AT_TM][AT_KIN]
     float *H1 = X + AT_TM * AT_KIN;                                // [AT_TM][h1_ld]
     float *H2 = H1 + (size_t)AT_TM * h1_ld;                        // [AT_TM][h2_ld]
-    const int tid = threadIdx.x, e0 = blockIdx.x * AT_TM;
+    const int tid = threadIdx.x, l0 = blockIdx.x * AT_TM, e0 = row0 + l0;
     for (int x = tid; x < AT_TM * AT_KIN; x += blockDim.x) X[x] = 0.f;
     __syncthreads();
-    if (tid < AT_TM && e0 + tid < N) {
+    if (tid < AT_TM && l0 + tid < rows) {
         const int e = e0 + tid;
         dev_policy_features(f, e, Kmax, ego4, k_count, ox, ov, oa, live, evals, X + tid * AT_KIN);
         if (feat_out) for (int q = 0; q < A.n_in; ++q) feat_out[(size_t)e * feat_stride + q] = X[tid * AT_KIN + q];
@@ -101,7 +105,14 @@ __global__ void __launch_bounds__(AT_THREADS) k_actor_eval(FeatCfg f, ActorDev A
     float s = 0.f;
     for (int n = part; n < A.h2p; n += 32) s = __builtin_fmaf(H2[(size_t)row * h2_ld + n], A.w2[n], s);
     s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8); s += __shfl_xor(s, 16);
-    if (part == 0 && e0 + row < N) jerk_out[e0 + row] = (double)(tanhf(s + A.b2) * A.scale + A.mean);
+    if (part == 0 && l0 + row < rows) jerk_out[e0 + row] = (double)(tanhf(s + *A.b2p) * A.scale + A.mean);
+}
+
+__global__ void __launch_bounds__(AT_THREADS) k_actor_eval(FeatCfg f, ActorDev A, int N, int Kmax, const double *__restrict__ ego4, const int *__restrict__ k_count,
+                                                           const double *__restrict__ ox, const double *__restrict__ ov, const double *__restrict__ oa,
+                                                           const int *__restrict__ live, int *evals, float *feat_out, int feat_stride, double *jerk_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char at_smem[];
+    actor_eval_body(f, A, 0, N, Kmax, ego4, k_count, ox, ov, oa, live, evals, feat_out, feat_stride, jerk_out, at_smem);
 }
 
 }  // namespace stmpc

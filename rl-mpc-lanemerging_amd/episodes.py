@@ -59,7 +59,11 @@ class EpisodeRunner:
     on-device flight recorder (``stmpc_rec_*``) between the controller and the step, and ``result()`` gains ``out["report"]`` (``report.Report``:
     the reference's report row with standard errors, the position profiles, the recorded run-up of every environment).  The recorder follows
     ONE episode per environment -- this runner's -- and is bound to the world this constructor initialises; ``vec_env.MergeVecEnv``'s autoreset
-    is not recorded."""
+    is not recorded.
+
+    ``policy`` may be an ``actor.ActorPopulation`` (anything with a ``P`` attribute): member m then drives environments
+    [m * n_per_member, (m + 1) * n_per_member), ``n`` must be ``policy.n``, and ``result()`` gains ``out["member"]`` (see ``summary_by_member``,
+    ``report.Report.by_member``).  The members' environments are different draws of one world, not common random numbers."""
 
     def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, record=None):
         import torch
@@ -67,6 +71,8 @@ class EpisodeRunner:
         if controller not in ("st", "combined"):
             # (the policy alone -- TASK EVALUATE_DDPG -- is not on the solver's path: SURVEY section 2 marks ddpg.py out of scope; removed in round 6)
             raise ValueError("controller must be 'st' or 'combined', not %r" % (controller,))
+        if hasattr(policy, "P") and int(n) != policy.n:
+            raise ValueError("n = %d, the population of policies was built for %d x %d = %d environments" % (n, policy.P, policy.n_per_member, policy.n))
         self.n, self.kmax, self.controller, self.policy = int(n), int(kmax), controller, policy
         self.ctx = ctx or _capi.default_context()
         self.params = _capi.Params.from_settings(Settings)
@@ -131,6 +137,8 @@ class EpisodeRunner:
         out["ego4"] = ego4
         if self.controller == "combined":
             out["percent_st"] = (self.takeovers / self.torch.clamp(self.controlled, min=1.0)).cpu().numpy()
+        if hasattr(self.policy, "P"):
+            out["member"] = np.arange(self.n) // self.policy.n_per_member
         if self.recorder is not None:
             from . import report
             out["report"] = report.Report.from_result(out, self.recorder.read())
@@ -177,4 +185,14 @@ def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max
 
 def summary(stats):
     """Column means as the reference's report rows hold them (stats.py:145-158)."""
-    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4", "report")}
+    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4", "report", "member")}
+
+
+def summary_by_member(stats, P):
+    """``summary`` of each member's environments: P dicts, member m from rows [m * n / P, (m + 1) * n / P) of every column (the result of a run
+    whose policy was an ``actor.ActorPopulation`` of P members)."""
+    n = len(stats["status"])
+    if P < 1 or n % P:
+        raise ValueError("%d environments do not split into %d members" % (n, P))
+    npm = n // P
+    return [summary({k: v[m * npm:(m + 1) * npm] for k, v in stats.items() if k != "report"}) for m in range(P)]

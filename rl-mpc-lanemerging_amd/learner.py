@@ -493,3 +493,20 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
         owner = (np.concatenate(envs) if envs else np.zeros(0, dtype=np.int64)) // learner.n_per_member
         out["member_returns"] = [returns[owner == m] for m in range(learner.P)]
     return out
+
+
+def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None):
+    """The reference's per-model ``EVALUATE_COMBINED_DDPG`` -- and the evaluation ``train_ddpg_all_with_lr_drop`` (ddpg.py:96-117) ends with -- for
+    every member at once: ``n_per_member`` merge episodes per member under the combined controller, in ONE run of P * n_per_member environments
+    whose policy is an ``actor.ActorPopulation``.  ``source``: a ``DDPGPopulation`` or a ``DDPGLearner`` (zero-copy views of the weights as they
+    are on the device: nothing is exported or uploaded), or a list as ``ActorPopulation`` takes (names, paths, learners, actors).
+    ``ctx``: the evaluation's context; by default a new one, because a context holds one world and the training env has its own.
+    Returns ``{"stats": run_episodes' columns + "member", "by_member": P summary rows, "reports": P ``report.Report``s (None without ``record``)}``.
+    The members' episodes are different draws of one world (identically distributed, not common random numbers)."""
+    from . import episodes
+    ctx = ctx if ctx is not None else _capi.Context(-1)
+    members = source if isinstance(source, (DDPGPopulation, list, tuple)) else [source]
+    pop = _actor.ActorPopulation(members, n_per_member, ctx, Settings)
+    stats = episodes.run_episodes(pop.n, seed=seed, controller="combined", policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record)
+    rep = stats.get("report")
+    return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P), "reports": rep.by_member(pop.P) if rep is not None else None}

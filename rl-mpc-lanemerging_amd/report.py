@@ -156,6 +156,22 @@ def columns_from_histories(per_episode_histories, tick_length=None):
     return out
 
 
+def reduce_rows_host(acc, threads=256):
+    """Host twin of ``k_rec_reduce`` for ``acc`` [rows][n]: per row, ``threads`` partial sums (environment e goes to partial e % threads, in index
+    order), then the fixed halving tree.  The order depends on n alone, so this gives the bits the device's reduction has for n environments."""
+    acc = np.asarray(acc, dtype=np.float64)
+    rows, n = acc.shape
+    part = np.zeros((rows, threads))
+    for e0 in range(0, n, threads):
+        chunk = acc[:, e0:e0 + threads]
+        part[:, :chunk.shape[1]] += chunk
+    w = threads // 2
+    while w > 0:
+        part[:, :w] += part[:, w:2 * w]
+        w //= 2
+    return part[:, 0].copy()
+
+
 def sem(values):
     """``scipy.stats.sem`` in numpy: std(ddof=1) / sqrt(n) (NaN for fewer than two values, as scipy returns)."""
     a = np.asarray(values, dtype=np.float64)
@@ -188,6 +204,26 @@ class Report:
         prof = {"counts": q("count"), "takeover_counts": q("takeover_count"), "jerks": q("sum_abs_jerk"), "speeds": q("sum_abs_speed"), "bins": recorded["bins"].copy()}
         cols = {k: v for k, v in result.items() if k not in ("ego4", "report")}
         return cls(cols, prof, recorded)
+
+    def by_member(self, P):
+        """P ``Report``s, member m's from environments [m * n / P, (m + 1) * n / P): its columns, rings and per-environment accumulators, and the
+        profiles summed from the latter in the order the recorder's own reduction has for that many environments (``reduce_rows_host``) -- what a
+        recorder of the member's environments alone would hold.  For a run whose policy was an ``actor.ActorPopulation`` of P members
+        (the reference: one report row per evaluated model, experiment_data/saved_data.csv).  ``P = 1``: this report itself."""
+        r = self._need_recorded()
+        n = len(r["status"])
+        if P < 1 or n % P:
+            raise ValueError("%d environments do not split into %d members" % (n, P))
+        if P == 1:
+            return [self]
+        npm, nb, out = n // P, len(r["bins"]) - 1, []
+        for m in range(P):
+            sl = slice(m * npm, (m + 1) * npm)
+            acc = np.ascontiguousarray(r["acc_env"][:, sl])
+            rec = {"ring": r["ring"][sl].copy() if r["ring"] is not None else None, "length": r["length"][sl].copy(), "acc_env": acc,
+                   "acc_reduced": reduce_rows_host(acc), "status": r["status"][sl].copy(), "bins": r["bins"].copy(), "kmax": r["kmax"]}
+            out.append(Report.from_result({k: v[sl] for k, v in self.columns.items()}, rec))
+        return out
 
     @classmethod
     def from_histories(cls, per_episode_histories, edges=DEFAULT_BINS, tick_length=None):

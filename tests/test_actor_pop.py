@@ -1,0 +1,512 @@
+"""A population of actors evaluated in one launch, and actors that are views of learners' weights (actor.ActorPopulation,
+actor.DDPGActor.from_learner, csrc/stmpc_actor_pop_kernels.hpp, stmpc_actor_view_ddpg / stmpc_actor_pop_* of include/stmpc.h), with the
+per-member split of the runner's results and of the report (episodes.summary_by_member, report.Report.by_member, learner.evaluate_members).
+
+CPU: header / library / binding agree on the six new entries; the per-member summaries and reports equal those of each slice alone.
+GPU: everything at the shipped 21-400-300-1 shape with 3 members of 24 rows (24 is not a multiple of the 16-row tile: every member has a
+masked tail, and a tile that wrongly spanned two members would mix weights at rows 24-31) and Kmax = 16.  A member equals a lone ``DDPGActor``
+on its slice, a view equals the actor loaded from the learner's export, a run under a population equals the runs of its members -- all bit for
+bit: the population runs the lone actor's own arithmetic, so no tolerance appears anywhere.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import REPO, load_golden
+from test_combined import _apply_settings
+
+NAMES = ("low1", "medium1", "fast1")
+P, N_PER, KMAX = 3, 24, 16
+N = P * N_PER
+NEW = ("stmpc_actor_view_ddpg", "stmpc_actor_pop_create", "stmpc_actor_pop_destroy", "stmpc_actor_pop_size", "stmpc_actor_pop_eval_device")
+_cache = {}
+
+
+def _capi():
+    import rl_mpc_lanemerging_amd as pkg
+    if pkg.build.needs_build():
+        pkg.build.build()
+    from rl_mpc_lanemerging_amd import _capi
+    return _capi
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def _same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------------------------------
+def test_header_library_and_binding_agree_on_the_new_entries():
+    capi = _capi()
+    lib = capi.load()
+    header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
+    declared = {name: args for name, args in re.findall(r"\b(stmpc_actor_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}
+    assert set(declared) == {"stmpc_actor_create", "stmpc_actor_destroy", "stmpc_actor_eval_device"} | set(NEW)
+    assert set(NEW) <= set(capi.EXPORTS)
+    for name in NEW:
+        fn = getattr(lib, name)                                   # (AttributeError: the library does not export it)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(declared[name].split(",")), name
+    assert "typedef struct stmpc_actor_pop stmpc_actor_pop;" in header
+    assert capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8 and "#define STMPC_ABI_VERSION 8" in header
+    # refusals that come before the device is touched
+    import ctypes
+    h = ctypes.c_void_p()
+    assert lib.stmpc_actor_view_ddpg(None, 0, ctypes.byref(h)) == capi.STMPC_EINVAL
+    assert lib.stmpc_actor_pop_create(None, None, 1, ctypes.byref(h)) == capi.STMPC_EINVAL
+    assert lib.stmpc_actor_pop_size(None) == 0
+
+
+def _synthetic_stats(n, seed):
+    rng = np.random.default_rng(seed)
+    status = rng.integers(1, 4, n).astype(np.int32)
+    st = {"status": status, "ticks": rng.integers(20, 200, n).astype(np.int32), "ego4": rng.normal(size=(n, 4)),
+          "crashed": (status == 2).astype(np.float64), "merged": (status == 1).astype(np.float64), "mean_speed": rng.uniform(5, 20, n),
+          "mean_abs_jerk": rng.uniform(0, 2, n), "closest_distance": np.where(rng.random(n) < 0.2, np.nan, rng.uniform(3, 50, n)),
+          "percent_st": rng.random(n), "member": np.arange(n) // (n // P)}
+    st["time_to_merge"] = np.where(status == 1, st["ticks"] * 0.2, np.nan)
+    return st
+
+
+def test_summary_by_member_is_the_summary_of_each_slice():
+    _capi()
+    from rl_mpc_lanemerging_amd import episodes
+    st = _synthetic_stats(N, 1)
+    st["report"] = object()                                       # (never looked at)
+    rows = episodes.summary_by_member(st, P)
+    assert len(rows) == P
+    for m, row in enumerate(rows):
+        want = episodes.summary({k: v[m * N_PER:(m + 1) * N_PER] for k, v in st.items() if k != "report"})
+        assert set(row) == set(want) and "member" not in row and "ego4" not in row and "mean_speed" in row
+        for k in want:
+            assert _same_bits(np.float64(row[k]), np.float64(want[k])), (m, k)
+    assert rows[0]["mean_speed"] != rows[1]["mean_speed"]
+    assert episodes.summary_by_member(st, 1)[0] == episodes.summary(st)
+    with pytest.raises(ValueError):
+        episodes.summary_by_member(st, 5)
+
+
+def _synthetic_episodes(n, seed):
+    """``episode_stats`` dicts as control.run_episode returns them: an approach along x with a few takeovers; merged / crashed / timed out mixed,
+    some without a closest-vehicle or disruption sample."""
+    rng = np.random.default_rng(seed)
+    eps = []
+    for e in range(n):
+        L = int(rng.integers(3, 60))
+        xs = np.cumsum(rng.uniform(0.5, 6.0, L)) - 215.0
+        kind = e % 3
+        have = rng.random() < 0.8 or kind == 0
+        eps.append({"position_history": [(float(x), 0.0) for x in xs], "speed_history": [float(v) for v in rng.uniform(0.0, 20.0, L)],
+                    "jerk_history": [0.0] + [float(j) for j in rng.normal(0.0, 1.0, L - 1)],
+                    "closest_vehicle_history": [float(d) for d in rng.uniform(3.0, 60.0, L)] if have else [],
+                    "disruption_history": [float(d) for d in np.maximum(rng.normal(0.0, 1.0, L // 2), 0.0)] if have else [],
+                    "takeover_history": [bool(t) for t in rng.random(L) < 0.1], "crashed": kind == 1, "merged": kind == 0,
+                    "simulation_time_taken": 0.2 * L})
+    return eps
+
+
+def _report_from_twins(eps, bins):
+    """A ``Report`` as ``EpisodeRunner.result()`` builds it, with the recorder's host copies assembled from the host twins: one accumulator column per
+    episode (``bin_profiles_host`` on it alone, then its takeover and tick totals), reduced in the recorder's order."""
+    from rl_mpc_lanemerging_amd import report
+    cols = report.columns_from_histories(eps)
+    cols["status"] = np.array([1 if ep["merged"] else 2 if ep["crashed"] else 3 for ep in eps], dtype=np.int32)
+    acc = np.zeros((4 * (len(bins) - 1) + 2, len(eps)))
+    for e, ep in enumerate(eps):
+        xs = [p[0] for p in ep["position_history"]]
+        p = report.bin_profiles_host(xs, ep["jerk_history"], ep["speed_history"], ep["takeover_history"], bins)
+        acc[:, e] = np.concatenate([p["counts"], p["takeover_counts"], p["jerks"], p["speeds"], [float(sum(ep["takeover_history"])), float(len(xs))]])
+    rec = {"ring": None, "length": np.array([min(len(ep["position_history"]), 8) for ep in eps], np.int32), "acc_env": acc,
+           "acc_reduced": report.reduce_rows_host(acc), "status": cols["status"].copy(), "bins": np.asarray(bins, np.float64), "kmax": KMAX}
+    return report.Report.from_result(cols, rec)
+
+
+def test_report_by_member_is_the_report_of_each_slice():
+    _capi()
+    from rl_mpc_lanemerging_amd import report
+    eps = _synthetic_episodes(3 * 8, 2)
+    whole = _report_from_twins(eps, report.DEFAULT_BINS)
+    parts = whole.by_member(3)
+    assert len(parts) == 3
+    for m, part in enumerate(parts):
+        want = _report_from_twins(eps[8 * m:8 * m + 8], report.DEFAULT_BINS)
+        assert set(part.columns) == set(want.columns)
+        for k in want.columns:
+            assert _same_bits(part.columns[k], want.columns[k]), (m, k)
+        pp, pw = part.profiles(), want.profiles()
+        for k in ("counts", "takeover_counts", "jerks", "speeds", "avg_jerks", "avg_speeds", "st_proportion", "bins"):
+            assert _same_bits(pp[k], pw[k]), (m, k)
+        assert pp["counts"].sum() == sum(len(ep["position_history"]) for ep in eps[8 * m:8 * m + 8])      # every x lies inside the bins
+        for k in ("acc_env", "acc_reduced", "length", "status"):
+            assert _same_bits(part._rec[k], want._rec[k]), (m, k)
+        assert _same_bits(part.percent_st(), want.percent_st())
+        lp, lw = part.lists(), want.lists()
+        assert set(lp) == set(lw)
+        for k in lw:
+            assert _same_bits(lp[k], lw[k]), (m, k)
+        ap, aw, sp, sw = part.averages(), want.averages(), part.stds(), want.stds()
+        for k in aw:
+            assert _same_bits(np.float64(ap[k]), np.float64(aw[k])), (m, k)
+            assert (np.isnan(sp[k]) and np.isnan(sw[k])) or abs(sp[k] - sw[k]) <= 1e-12, (m, k)
+    assert not np.array_equal(parts[0].profiles()["jerks"], parts[1].profiles()["jerks"])
+    assert np.array_equal(sum(p.profiles()["counts"] for p in parts), whole.profiles()["counts"])
+    assert whole.by_member(1) == [whole] and whole.by_member(1)[0] is whole
+    with pytest.raises(ValueError):
+        whole.by_member(5)
+    with pytest.raises(ValueError):                               # a report without a recorder has no per-environment accumulators
+        report.Report.from_histories(eps).by_member(3)
+
+
+def test_reduce_rows_host_has_the_recorders_order():
+    """k_rec_reduce: thread t adds environments t, t + 256, ... in order, then the halving tree over the 256 partial sums."""
+    _capi()
+    from rl_mpc_lanemerging_amd import report
+    rng = np.random.default_rng(3)
+    for n in (1, 24, 256, 700):
+        acc = rng.uniform(0.0, 1e3, (5, n))
+        part = np.zeros((5, 256))
+        for e in range(n):
+            part[:, e % 256] = part[:, e % 256] + acc[:, e]
+        w = 128
+        while w:
+            for t in range(w):
+                part[:, t] = part[:, t] + part[:, t + w]
+            w //= 2
+        assert _same_bits(report.reduce_rows_host(acc), part[:, 0].copy()), n
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------------------------------
+def _settings():
+    g = load_golden("golden_combined_real.npz")
+    pkg = _apply_settings(g)
+    return g, pkg.Settings
+
+
+def _states(g, dev, same=False):
+    """72 states of the golden, vehicle slots padded from 8 to Kmax = 16: per member 18 of its first states and, spread over both tiles of the
+    member's slice, 6 whose rollout the reference ended after the first step (so that step 2 meets rows that are no longer live).
+    ``same``: member 0's 24 states, three times."""
+    import torch
+    short = np.nonzero(g["n_evals"] == 1)[0]
+    assert len(short) >= 6 * P
+    rows = np.arange(N)
+    for m in range(P):
+        rows[m * N_PER + np.array([3, 9, 15, 16, 20, 23])] = short[6 * m:6 * m + 6]
+    if same:
+        rows = np.tile(rows[:N_PER], P)
+    pad = lambda a: np.concatenate([a[rows], np.zeros((N, KMAX - a.shape[1]))], axis=1)
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    return {"ego5": t(g["ego"][rows]), "ego4": t(g["ego"][rows][:, :4]), "k": t(g["k_count"][rows]), "ox": t(pad(g["other_x"])), "ov": t(pad(g["other_v"])),
+            "oa": t(pad(g["other_a"])), "evals0": t(g["evals0"][rows])}
+
+
+def _two_steps(ctx, S, policy, st, rows):
+    """Evaluate ``policy`` on ``rows`` of the states at step 1, roll those rows out one step with its jerks, evaluate at step 2 (only the rows whose
+    rollout goes on are evaluated then).  Returns the policy's jerk, input vectors and counters after each step, as numpy."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi as capi
+    params, ccfg = capi.Params.from_settings(S), capi.CombinedCfg.from_settings(S)
+    cur = {k: st[k][rows].clone().contiguous() for k in ("ego4", "ox", "ov", "oa")}
+    ego5, k = st["ego5"][rows].contiguous(), st["k"][rows].contiguous()
+    n = ego5.shape[0]
+    policy.keep_features = True
+    policy.evals.copy_(st["evals0"][rows])
+    policy.feat.fill_(-7.0)
+    policy.jerk.fill_(-7.0)
+    out = []
+    for step in (1, 2):
+        jerk = policy(step, cur["ego4"], k, cur["ox"], cur["ov"], cur["oa"])
+        torch.cuda.synchronize()
+        out.append({"jerk": jerk.cpu().numpy().copy(), "feat": policy.feat.cpu().numpy().copy(), "evals": policy.evals.cpu().numpy().copy()})
+        if step == 1:
+            ctx.rollout_step_device(params, ccfg, n, KMAX, 1, ego5.data_ptr(), cur["ego4"].data_ptr(), k.data_ptr(), cur["ox"].data_ptr(), cur["ov"].data_ptr(),
+                                    cur["oa"].data_ptr(), jerk.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    ctx.check_error()
+    return out
+
+
+def _assert_steps_equal(got, want, label):
+    for step, (a, b) in enumerate(zip(got, want), 1):
+        for key in ("jerk", "feat", "evals"):
+            assert _same_bits(a[key], b[key]), (label, "step", step, key)
+
+
+def _slice_steps(steps, sl):
+    return [{k: v[sl] for k, v in s.items()} for s in steps]
+
+
+@pytest.mark.gpu
+def test_gpu_members_are_lone_actors(gpu_ctx, restore_settings):
+    import torch
+    from rl_mpc_lanemerging_amd import actor
+    g, S = _settings()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    st = _states(g, dev)
+    pop = actor.ActorPopulation(list(NAMES), N_PER, gpu_ctx, S)
+    assert (pop.P, pop.n_per_member, pop.n) == (P, N_PER, N) and gpu_ctx.actor_pop_size(pop.handle) == P
+    assert pop.evals.shape == (N,) and pop.feat.shape == (N, 21) and pop.jerk.shape == (N,)
+    got = _two_steps(gpu_ctx, S, pop, st, slice(0, N))
+    assert (got[1]["evals"] - got[0]["evals"]).min() == 0 < (got[1]["evals"] - got[0]["evals"]).max()      # step 2 met ended rollouts and live ones
+    for m, name in enumerate(NAMES):
+        sl = slice(m * N_PER, (m + 1) * N_PER)
+        lone = actor.DDPGActor(name, N_PER, gpu_ctx, S, dev)
+        _assert_steps_equal(_slice_steps(got, sl), _two_steps(gpu_ctx, S, lone, st, sl), name)
+    assert np.abs(got[0]["jerk"]).max() <= 5.0 and got[0]["jerk"].std() > 0.1
+    # every member reads its own row of the table: the same 24 states give three different answers
+    same = _states(g, dev, same=True)
+    pop.evals.copy_(same["evals0"])
+    j = pop(1, same["ego4"], same["k"], same["ox"], same["ov"], same["oa"]).cpu().numpy().reshape(P, N_PER)
+    f = pop.feat.cpu().numpy().reshape(P, N_PER, 21)
+    assert _same_bits(f[0], f[1]) and _same_bits(f[0], f[2])
+    assert (j[0] != j[1]).any() and (j[1] != j[2]).any() and (j[0] != j[2]).any()
+    assert ((j[0] != j[1]) & (j[1] != j[2]) & (j[0] != j[2])).mean() > 0.5          # (differently trained actors: not a few borderline rows)
+    # a population of one is the actor
+    one = actor.ActorPopulation(["medium1"], N_PER, gpu_ctx, S)
+    lone = actor.DDPGActor("medium1", N_PER, gpu_ctx, S, dev)
+    _assert_steps_equal(_two_steps(gpu_ctx, S, one, st, slice(0, N_PER)), _two_steps(gpu_ctx, S, lone, st, slice(0, N_PER)), "P = 1")
+    # existing actors as members: borrowed, the population's table points at them
+    mixed = actor.ActorPopulation([lone, "fast1", actor.weights_path("low1")], N_PER, gpu_ctx, S)
+    assert mixed.members[0] is lone
+    jm = mixed(1, st["ego4"], st["k"], st["ox"], st["ov"], st["oa"]).cpu().numpy()
+    assert np.isfinite(jm).all() and np.abs(jm).max() <= 5.0
+
+
+def _nonzero_last_layers(L, seed):
+    """A fresh learner's last layers are zero (every jerk 0, every gradient behind it 0): give both nets and their targets non-zero ones."""
+    sd = L.state_dict()
+    for i, slot in enumerate(("actor", "actor_target", "critic", "critic_target")):
+        r = np.random.default_rng(seed + i // 2)                   # a target starts as a copy of its net
+        sd["params"][slot]["w2"] = r.normal(0, 0.05, (1, L.cfg.h2)).astype(np.float32)
+        sd["params"][slot]["b2"] = r.normal(0, 0.05, 1).astype(np.float32)
+    L.load_state_dict({"params": sd["params"], "counters": None})
+
+
+def _eval(ctx, S, policy, st):
+    return _two_steps(ctx, S, policy, st, slice(0, N_PER))
+
+
+@pytest.mark.gpu
+def test_gpu_a_view_is_the_export_without_the_copy(gpu_ctx, restore_settings, tmp_path):
+    import torch
+    from rl_mpc_lanemerging_amd import actor, learner
+    g, S = _settings()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    st = _states(g, dev)
+    L = learner.DDPGLearner(20, learner.DDPGConfig(batch=16, capacity=200, replay_start=0), seed=3)
+    _nonzero_last_layers(L, 40)
+    view = actor.DDPGActor.from_learner(L, N_PER, gpu_ctx, S)
+    assert view.learner is L and view.engine == "hip"
+    before = _eval(gpu_ctx, S, view, st)
+    _assert_steps_equal(before, _eval(gpu_ctx, S, actor.DDPGActor(L.export_actor(str(tmp_path / "a0.npz")), N_PER, gpu_ctx, S, dev), st), "fresh learner")
+    assert np.abs(before[0]["jerk"]).max() > 1e-3
+    b2_before = L.state_dict()["params"]["actor"]["b2"].copy()
+    rng = np.random.default_rng(41)
+    t = lambda a: torch.as_tensor(a, device=dev)
+    obs, nobs = t(rng.normal(0, 0.5, (64, 20)).astype(np.float32)), t(rng.normal(0, 0.5, (64, 20)).astype(np.float32))
+    L.push(obs, t(rng.integers(0, 100, 64).astype(np.int32)), t(rng.uniform(-5, 5, 64)), t(rng.normal(0, 1, 64)), nobs, t(rng.random(64) < 0.1), t(np.zeros(64, bool)))
+    L.update(3, lr_q=1e-3, lr_pi=1e-3)
+    after = _eval(gpu_ctx, S, view, st)                            # the SAME view object, evaluated after the updates on the same stream
+    assert L.stats()["updates"] == 3
+    _assert_steps_equal(after, _eval(gpu_ctx, S, actor.DDPGActor(L.export_actor(str(tmp_path / "a3.npz")), N_PER, gpu_ctx, S, dev), st), "after 3 updates")
+    assert (after[0]["jerk"] != before[0]["jerk"]).any()
+    sd = L.state_dict()["params"]
+    assert sd["actor"]["b2"][0] != b2_before[0]                    # (the output bias moved too: a host snapshot of it would have shown above)
+    tview = actor.DDPGActor.from_learner(L, N_PER, gpu_ctx, S, target=True)
+    learner.write_actor(str(tmp_path / "t3.npz"), sd["actor_target"], L.cfg.tanh_scale, L.cfg.tanh_mean)
+    tgt = _eval(gpu_ctx, S, tview, st)
+    _assert_steps_equal(tgt, _eval(gpu_ctx, S, actor.DDPGActor(str(tmp_path / "t3.npz"), N_PER, gpu_ctx, S, dev), st), "target actor")
+    assert (tgt[0]["jerk"] != after[0]["jerk"]).any()
+
+
+def _trained_population(gpu_ctx):
+    """Three learners with different seeds on one env of 72, two updates each; computed once, then only read."""
+    if "pop" in _cache:
+        return _cache["pop"]
+    import torch
+    import rl_mpc_lanemerging_amd as pkg
+    from rl_mpc_lanemerging_amd import learner, vec_env
+    snap = pkg.Settings.snapshot()
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    env = vec_env.MergeVecEnv(N, env_id="sumo-jerk-continuous-v0", seed=7, ctx=gpu_ctx)
+    cfg = learner.DDPGConfig(n_obs=20, batch=16, capacity=200, replay_start=0, lr_q=1e-3, lr_pi=1e-3)
+    pop = learner.DDPGPopulation(env, (cfg, P), seeds=[11, 12, 13])
+    for m in range(P):
+        _nonzero_last_layers(pop.member(m), 50 + 2 * m)
+    obs = env.reset()
+    for _ in range(2):
+        ticks = env.episode_ticks.clone()
+        action = pop.act(obs, ticks, noise=True).clone()
+        nobs, r, term, trunc, info = env.step(action)
+        pop.push(obs, ticks, action, r, nobs, term, trunc, final_obs=info["final_observation"])
+        pop.update(1)
+        obs = nobs
+    torch.cuda.synchronize()
+    env.check_error()
+    assert list(pop.stats()["updates"]) == [2] * P
+    pkg.Settings.restore(snap)
+    _cache["pop"] = pop
+    return pop
+
+
+@pytest.mark.gpu
+def test_gpu_views_of_a_learner_population(gpu_ctx, restore_settings, tmp_path):
+    import torch
+    from rl_mpc_lanemerging_amd import actor
+    pop = _trained_population(gpu_ctx)
+    g, S = _settings()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    st = _states(g, dev)
+    views = actor.ActorPopulation(pop, N_PER, gpu_ctx, S)
+    assert views.P == P and all(views.members[m].learner is pop.member(m) for m in range(P))
+    got = _two_steps(gpu_ctx, S, views, st, slice(0, N))
+    for m in range(P):
+        sl = slice(m * N_PER, (m + 1) * N_PER)
+        exported = actor.DDPGActor(pop.member(m).export_actor(str(tmp_path / ("m%d.npz" % m))), N_PER, gpu_ctx, S, dev)
+        _assert_steps_equal(_slice_steps(got, sl), _two_steps(gpu_ctx, S, exported, st, sl), "member %d" % m)
+    same = _states(g, dev, same=True)
+    views.evals.copy_(same["evals0"])
+    j = views(1, same["ego4"], same["k"], same["ox"], same["ov"], same["oa"]).cpu().numpy().reshape(P, N_PER)
+    assert (j[0] != j[1]).any() and (j[1] != j[2]).any()
+
+
+def _episode_settings():
+    import rl_mpc_lanemerging_amd as pkg
+    from rl_mpc_lanemerging_amd import combined_bench
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
+    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1_TRAFFIC)
+    return pkg.Settings
+
+
+def _episode_runs(gpu_ctx):
+    """The three 40-tick runs of 72 environments, with a recorder; computed once, then only read."""
+    if "runs" in _cache:
+        return _cache["runs"]
+    from rl_mpc_lanemerging_amd import actor, episodes, report
+    S = _episode_settings()
+    runs = {}
+    for label, make in (("lone", lambda: actor.DDPGActor("medium1", N, gpu_ctx, S)), ("thrice", lambda: actor.ActorPopulation(["medium1"] * P, N_PER, gpu_ctx, S)),
+                        ("mixed", lambda: actor.ActorPopulation(list(NAMES), N_PER, gpu_ctx, S))):
+        runs[label] = episodes.run_episodes(N, seed=21, controller="combined", policy=make(), ctx=gpu_ctx, kmax=KMAX, max_ticks=40,
+                                            record=report.RecorderConfig(depth=8))
+    _cache["runs"] = runs
+    return runs
+
+
+@pytest.mark.gpu
+def test_gpu_episodes_under_a_population(gpu_ctx, restore_settings):
+    from rl_mpc_lanemerging_amd import report
+    runs = _episode_runs(gpu_ctx)
+    lone, thrice, mixed = runs["lone"], runs["thrice"], runs["mixed"]
+    assert "member" not in lone
+    for run in (thrice, mixed):
+        assert np.array_equal(run["member"], [0] * N_PER + [1] * N_PER + [2] * N_PER)
+    columns = [k for k in lone if k != "report"]
+    assert "ego4" in columns and "percent_st" in columns and set(thrice) == set(lone) | {"member"}
+    mid = slice(N_PER, 2 * N_PER)
+    for k in columns:
+        assert _same_bits(thrice[k], lone[k]), k                                   # three times the same actor = that actor on all rows
+        assert _same_bits(mixed[k][mid], lone[k][mid]), k                          # the member that is the same actor meets the same environments
+    assert lone["ticks"].max() == 40 and (lone["ego4"][:, 2] > 0).any()
+    outer = np.r_[0:N_PER, 2 * N_PER:N]
+    assert (mixed["ego4"][outer] != lone["ego4"][outer]).any()                     # the other members drive differently
+    rm, rl = mixed["report"].by_member(P)[1], lone["report"].by_member(P)[1]
+    for k in ("ring", "length", "acc_env", "acc_reduced", "status"):
+        assert _same_bits(rm._rec[k], rl._rec[k]), k
+    assert set(rm.columns) == set(rl.columns) | {"member"}
+    for k in rl.columns:
+        assert _same_bits(rm.columns[k], rl.columns[k]), k
+    for k, v in rl.profiles().items():
+        assert _same_bits(rm.profiles()[k], v), k
+    assert (rm.columns["member"] == 1).all() and rl.profiles()["counts"].sum() == rl._rec["acc_env"][-1].sum() >= 40
+    # the recorder's own reduction over all 72 environments has the order of its host twin
+    assert _same_bits(lone["report"]._rec["acc_reduced"], report.reduce_rows_host(lone["report"]._rec["acc_env"]))
+    assert not _same_bits(mixed["report"].by_member(P)[0]._rec["ring"], lone["report"].by_member(P)[0]._rec["ring"])
+
+
+@pytest.mark.gpu
+def test_gpu_evaluate_members(gpu_ctx, restore_settings):
+    from rl_mpc_lanemerging_amd import _capi as capi, actor, episodes, learner, report
+    pop = _trained_population(gpu_ctx)
+    S = _episode_settings()
+    length = 39 * S.TICK_LENGTH + 0.5 * S.TICK_LENGTH            # max_ticks = 39: the run is 40 ticks
+    out = learner.evaluate_members(pop, N_PER, seed=5, kmax=KMAX, max_episode_length=length, record=report.RecorderConfig(depth=8))
+    assert set(out) == {"stats", "by_member", "reports"} and len(out["by_member"]) == P and len(out["reports"]) == P
+    # (the world's own tick count stops at max_ticks = 39, where an episode is out of time; the runner's loop makes max_ticks + 1 = 40 ticks)
+    assert out["stats"]["ticks"].max() == 39 and np.array_equal(out["stats"]["member"], np.arange(N) // N_PER)
+    ctx = capi.Context(-1)
+    views = actor.ActorPopulation(pop, N_PER, ctx, S)
+    r = episodes.EpisodeRunner(N, seed=5, controller="combined", policy=views, ctx=ctx, kmax=KMAX, max_episode_length=length)
+    assert r.cfg.max_ticks == 39
+    for _ in range(40):
+        r.tick()
+    assert r.ticks_done == 40
+    want = episodes.summary_by_member(r.result(), P)
+    for m in range(P):
+        assert set(out["by_member"][m]) == set(want[m])
+        for k, v in want[m].items():
+            assert _same_bits(np.float64(out["by_member"][m][k]), np.float64(v)), (m, k)
+        assert out["reports"][m].profiles()["counts"].sum() == out["stats"]["ticks"][m * N_PER:(m + 1) * N_PER].sum()
+    assert out["by_member"][0]["mean_speed"] != out["by_member"][1]["mean_speed"]
+    assert learner.evaluate_members(pop.member(0), N_PER, seed=5, kmax=KMAX, max_episode_length=2 * S.TICK_LENGTH)["reports"] is None
+
+
+@pytest.mark.gpu
+def test_gpu_refusals(gpu_ctx, restore_settings):
+    """None of these launches a kernel: every refusal comes from a check before the launch."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi as capi, actor, episodes, learner
+    g, S = _settings()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    st = _states(g, dev)
+    narrow = learner.DDPGLearner(20, learner.DDPGConfig(h1=64, h2=48, batch=16, capacity=200, replay_start=0), seed=1)
+    shipped = actor.DDPGActor("medium1", N_PER, gpu_ctx, S, dev)
+    with pytest.raises(ValueError, match="one launch needs one shape"):
+        actor.ActorPopulation(["medium1", narrow], N_PER, gpu_ctx, S)
+    nview = actor.DDPGActor.from_learner(narrow, N_PER, gpu_ctx, S)
+    with pytest.raises(capi.StmpcError) as err:                    # the library's own check
+        gpu_ctx.actor_pop_create([shipped.handle, nview.handle])
+    assert err.value.code == capi.STMPC_EINVAL
+    for handles in ([], [shipped.handle] * (capi.DDPG_POP_MAX + 1)):
+        with pytest.raises(capi.StmpcError) as err:
+            gpu_ctx.actor_pop_create(handles)
+        assert err.value.code == capi.STMPC_EINVAL
+    full = gpu_ctx.actor_pop_create([shipped.handle] * capi.DDPG_POP_MAX)
+    assert gpu_ctx.actor_pop_size(full) == capi.DDPG_POP_MAX
+    gpu_ctx.actor_pop_destroy(full)
+    for members in ([], ["medium1"] * (capi.DDPG_POP_MAX + 1)):
+        with pytest.raises(ValueError, match="1 ... 64 members"):
+            actor.ActorPopulation(members, N_PER, gpu_ctx, S)
+    with pytest.raises(ValueError):
+        actor.ActorPopulation([3.5], N_PER, gpu_ctx, S)
+    with pytest.raises(ValueError, match="hip-engine"):
+        actor.ActorPopulation([actor.DDPGActor("medium1", N_PER, gpu_ctx, S, dev, engine="torch")], N_PER, gpu_ctx, S)
+    pop = actor.ActorPopulation(list(NAMES), N_PER, gpu_ctx, S)
+    pop.jerk.fill_(-7.0)
+    with pytest.raises(ValueError, match="has 71 rows"):
+        pop(1, st["ego4"][:71], st["k"], st["ox"], st["ov"], st["oa"])
+    with pytest.raises(ValueError, match="has 24 rows"):
+        pop(1, st["ego4"], st["k"], st["ox"][:N_PER], st["ov"], st["oa"])
+    fc = capi.FeaturesCfg.from_settings(S, time_feature=False)     # 20 inputs: not these actors' width
+    args = (st["ego4"].data_ptr(), st["k"].data_ptr(), st["ox"].data_ptr(), st["ov"].data_ptr(), st["oa"].data_ptr(), pop.evals.data_ptr(), 0, 21, pop.jerk.data_ptr(), 0)
+    with pytest.raises(capi.StmpcError):
+        gpu_ctx.actor_pop_eval_device(pop.handle, fc, N_PER, KMAX, 1, *args)
+    with pytest.raises(capi.StmpcError):                           # step 2 without a rollout of 72 states in the context
+        capi.Context(-1).actor_pop_eval_device(pop.handle, pop.fcfg, N_PER, KMAX, 2, *args)
+    with pytest.raises(capi.StmpcError):
+        gpu_ctx.actor_pop_eval_device(pop.handle, pop.fcfg, N_PER, capi.KMAX_LIMIT + 1, 1, *args)
+    with pytest.raises(capi.StmpcError):                           # the time feature needs its counters
+        gpu_ctx.actor_pop_eval_device(pop.handle, pop.fcfg, N_PER, KMAX, 1, *(args[:5] + (0,) + args[6:]))
+    torch.cuda.synchronize()
+    assert (pop.jerk == -7.0).all()                                # nothing ran
+    _episode_settings()
+    with pytest.raises(ValueError, match="built for 3 x 24 = 72 environments"):
+        episodes.EpisodeRunner(N + 1, controller="combined", policy=pop, ctx=gpu_ctx, kmax=KMAX)
+    with pytest.raises(ValueError, match="built for 3 x 24 = 72 environments"):
+        episodes.run_episodes(N_PER, controller="combined", policy=pop, ctx=gpu_ctx, kmax=KMAX)
