@@ -674,6 +674,39 @@ int  stmpc_actor_pop_eval_device(stmpc_ctx *ctx, const stmpc_actor_pop *pop, con
                                  const double *d_cur_other_a, int32_t *d_evals, float *d_feat, int feat_stride, double *d_jerk, void *stream);
 
 /*
+ * Traffic groups: the world of a context split into G groups of n_per_group consecutive environments, each with its own stmpc_sim_cfg, stepped, viewed,
+ * recorded, used as a vector environment and reset in the launches of an ungrouped world.  The reference's experiment matrix varies along this axis: its
+ * configs/{train,combined,cross,ddpg}_*.json differ in BASE_TRAFFIC_INTERVAL and OTHER_CAR_SPEED -- the highway flow control.py:215-226 inserts -- and each
+ * is one process with one merge_gym.py environment.  (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)
+ * Group g of a grouped world is, bit for bit, the lone world of n_per_group environments made from cfgs[g]: environment `local` of the group draws
+ * as environment `local` of that world (its seed, its episode seeds and counter windows) and lives at row g * n_per_group + local of every array.
+ *   May differ between groups: other_car_speed, base_traffic_interval, vary_traffic_start_times, speed_dev, seed, start_speed, start_speed_std,
+ *                   min_start_speed, max_start_speed, randomize_start_speed, max_ticks.
+ *   Must be equal (else STMPC_EINVAL naming the field): tick_length, spawn_x, despawn_x, ego_start_x, ego_start_y, arrive_x, sensor_radius, the veh_*
+ *                   vehicle type, disruption_min_s, yield_overlap and the route (the context keeps one device copy, from cfgs[0]; the others point to
+ *                   equal points, or are NULL alike).  Two groups with the same seed see common random numbers; nothing else couples groups.
+ *   stmpc_sim_init_groups_device   validates every cfg, uploads the table (synchronises on `stream` for it), sets the world's size to G * n_per_group
+ *                   and initialises it; G = 1 ... STMPC_SIM_GROUPS_MAX, n_per_group >= 1.  Ends the environment as stmpc_sim_init_device does;
+ *                   stmpc_sim_init_device on the context ends the grouping.  A refused call changes nothing.
+ *   stmpc_sim_step_groups_device   stmpc_sim_step_device for a grouped world: takes no cfgs (the context's table is read on the device; no copy, no
+ *                   synchronisation).  N must be G * n_per_group.  STMPC_EINVAL on a world without groups -- and the plain stmpc_sim_step_device /
+ *                   stmpc_env_step_device return STMPC_EINVAL on a grouped world, which they would step with one cfg.  stmpc_sim_view_device (any
+ *                   group's cfg: it reads sensor_radius), stmpc_sim_read, stmpc_sim_status_device and the recorder serve a grouped world unchanged.
+ *   stmpc_env_reset_groups_device / stmpc_env_step_groups_device   stmpc_env_reset_device / stmpc_env_step_device on a grouped world; an episode log
+ *                   row's environment column holds the global row.  The autoreset re-initialises an environment with its own group's cfg.
+ *   stmpc_sim_groups   the current split (0, 0: an ungrouped world)
+ */
+#define STMPC_SIM_GROUPS_MAX 64
+int stmpc_sim_init_groups_device(stmpc_ctx *ctx, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream);
+int stmpc_sim_step_groups_device(stmpc_ctx *ctx, const stmpc_params *p, int N, const double *d_cmd_speed, void *stream);
+int stmpc_sim_groups(stmpc_ctx *ctx, int *G, int *n_per_group);
+int stmpc_env_reset_groups_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *cfgs, int G, int n_per_group, const stmpc_env_cfg *env_cfg,
+                                  float *d_obs, int obs_stride, void *stream);
+int stmpc_env_step_groups_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_env_cfg *env_cfg, int N, const void *d_action, float *d_obs,
+                                 int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats,
+                                 void *stream);
+
+/*
  * Episode flight recorder on the device, next to the world (stmpc_sim_*): the per-tick histories the reference's evaluation keeps and what it
  * bins over the ego's position, for N environments in lock-step, with nothing crossing to the host until it is read.  (Additive: new entries
  * only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)

@@ -110,6 +110,26 @@ class SimCfg(C.Structure):
         return self
 
 
+class SimCfgTable:
+    """A contiguous ``stmpc_sim_cfg[G]`` for the traffic-group entries, from a sequence of ``SimCfg`` (kept alive with their routes); indexing gives
+    the caller's ``SimCfg`` objects."""
+
+    def __init__(self, cfgs):
+        self.cfgs = list(cfgs)
+        self.array = (SimCfg * max(len(self.cfgs), 1))()
+        for i, c in enumerate(self.cfgs):
+            C.memmove(C.byref(self.array, i * C.sizeof(SimCfg)), C.byref(c), C.sizeof(SimCfg))
+
+    def __len__(self):
+        return len(self.cfgs)
+
+    def __getitem__(self, i):
+        return self.cfgs[i]
+
+    def __iter__(self):
+        return iter(self.cfgs)
+
+
 class EnvCfg(C.Structure):
     """``stmpc_env_cfg`` (include/stmpc.h): action mode, reward function and the reference's reward / action settings (merge_gym.py, dqn.py:449-563)."""
     _fields_ = [("action_mode", C.c_int32), ("reward_function", C.c_int32), ("tick_length", C.c_double), ("crash_reward", C.c_double),
@@ -167,6 +187,7 @@ EXPORTS = (
     "stmpc_actor_view_ddpg", "stmpc_actor_pop_create", "stmpc_actor_pop_destroy", "stmpc_actor_pop_size", "stmpc_actor_pop_eval_device",
     "stmpc_env_reset_device", "stmpc_env_step_device", "stmpc_env_reward_device", "stmpc_env_drain", "stmpc_env_episode_seed",
     "stmpc_env_episode_ticks_device",
+    "stmpc_sim_init_groups_device", "stmpc_sim_step_groups_device", "stmpc_sim_groups", "stmpc_env_reset_groups_device", "stmpc_env_step_groups_device",
     "stmpc_ddpg_create", "stmpc_ddpg_destroy", "stmpc_ddpg_set_params", "stmpc_ddpg_get_params", "stmpc_ddpg_set_state", "stmpc_ddpg_get_state",
     "stmpc_ddpg_push_device", "stmpc_ddpg_act_device", "stmpc_ddpg_update_device", "stmpc_ddpg_grads_device", "stmpc_ddpg_stats_device",
     "stmpc_ddpg_replay_read", "stmpc_ddpg_gather_device", "stmpc_ddpg_sample_index", "stmpc_ddpg_noise",
@@ -180,6 +201,7 @@ REWARD_CONTINUOUS, REWARD_SLOTTED, REWARD_SLOTTED_JERK, REWARD_ST = 0, 1, 2, 3  
 ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
 DDPG_ROW, DDPG_NCOUNTERS = 68, 8      # STMPC_DDPG_ROW, STMPC_DDPG_NCOUNTERS
 DDPG_POP_MAX = 64                     # STMPC_DDPG_POP_MAX
+SIM_GROUPS_MAX = 64                   # STMPC_SIM_GROUPS_MAX
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
 REC_HDR, REC_NQ, REC_MAX_DEPTH, REC_MAX_EDGES = 10, 4, 64, 32      # STMPC_REC_HDR, STMPC_REC_NQ, STMPC_REC_MAX_DEPTH, STMPC_REC_MAX_EDGES
 REC_COLUMNS = ("tick", "x", "y", "v", "a", "s", "k", "cmd", "takeover", "jerk")      # the first STMPC_REC_HDR columns of a record
@@ -272,6 +294,11 @@ def load():
     lib.stmpc_env_reward_device.argtypes = [vp, ep, C.c_int, C.c_int] + [vp] * 9 + [vp]
     lib.stmpc_env_drain.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.stmpc_env_episode_ticks_device.argtypes = [vp, C.c_int, vp, vp]
+    lib.stmpc_sim_init_groups_device.argtypes = [vp, sp, C.c_int, C.c_int, vp]
+    lib.stmpc_sim_step_groups_device.argtypes = [vp, pp, C.c_int, vp, vp]
+    lib.stmpc_sim_groups.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.stmpc_env_reset_groups_device.argtypes = [vp, pp, sp, C.c_int, C.c_int, ep, vp, C.c_int, vp]
+    lib.stmpc_env_step_groups_device.argtypes = [vp, pp, ep, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.stmpc_env_episode_seed.argtypes = [C.c_uint64, C.c_uint32]
     lib.stmpc_env_episode_seed.restype = C.c_uint64
     lib.stmpc_st_control_batch_device.argtypes = [vp, pp, C.c_double, C.c_int, C.c_int] + [vp] * 10 + [vp]
@@ -646,6 +673,20 @@ class Context:
     def sim_step(self, params, cfg, N, d_cmd_speed, stream=0):
         self._chk(self._lib.stmpc_sim_step_device(self._h, C.byref(params), C.byref(cfg), int(N), d_cmd_speed, stream))
 
+    def sim_init_groups(self, cfgs, n_per_group, stream=0):
+        """``stmpc_sim_init_groups_device``: ``cfgs`` is a ``SimCfgTable`` (or a sequence of ``SimCfg``), one per traffic group."""
+        t = cfgs if isinstance(cfgs, SimCfgTable) else SimCfgTable(cfgs)
+        self._chk(self._lib.stmpc_sim_init_groups_device(self._h, t.array, len(t), int(n_per_group), stream))
+
+    def sim_step_groups(self, params, N, d_cmd_speed, stream=0):
+        self._chk(self._lib.stmpc_sim_step_groups_device(self._h, C.byref(params), int(N), d_cmd_speed, stream))
+
+    def sim_groups(self):
+        """(G, n_per_group) of the context's world; (0, 0) for an ungrouped one."""
+        g, n = C.c_int(0), C.c_int(0)
+        self._chk(self._lib.stmpc_sim_groups(self._h, C.byref(g), C.byref(n)))
+        return g.value, n.value
+
     def sim_status_device(self, N, d_status, stream=0):
         """Environment status words into a device int32 array (asynchronous): 0 running, 1 arrived, 2 crashed, 3 out of time."""
         self._chk(self._lib.stmpc_sim_status_device(self._h, int(N), d_status, stream))
@@ -780,6 +821,14 @@ class Context:
     def env_step(self, params, sim_cfg, env_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs=0, d_final_stats=0, stream=0):
         self._chk(self._lib.stmpc_env_step_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), int(N), d_action, d_obs, int(obs_stride),
                                                   d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream))
+
+    def env_reset_groups(self, params, cfgs, n_per_group, env_cfg, d_obs, obs_stride, stream=0):
+        t = cfgs if isinstance(cfgs, SimCfgTable) else SimCfgTable(cfgs)
+        self._chk(self._lib.stmpc_env_reset_groups_device(self._h, C.byref(params), t.array, len(t), int(n_per_group), C.byref(env_cfg), d_obs, int(obs_stride), stream))
+
+    def env_step_groups(self, params, env_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs=0, d_final_stats=0, stream=0):
+        self._chk(self._lib.stmpc_env_step_groups_device(self._h, C.byref(params), C.byref(env_cfg), int(N), d_action, d_obs, int(obs_stride), d_reward, d_terminated,
+                                                         d_truncated, d_final_obs, d_final_stats, stream))
 
     def env_reward(self, env_cfg, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed=0, d_arrived=0, d_reward=0, stream=0):
         self._chk(self._lib.stmpc_env_reward_device(self._h, C.byref(env_cfg), int(N), int(Kmax), d_ego4, d_k, d_ox, 0, 0, d_jerk, d_crashed, d_arrived,

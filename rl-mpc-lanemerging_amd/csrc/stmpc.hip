@@ -11,6 +11,7 @@
 #include "stmpc_ddpg_pop_kernels.hpp"
 #include "stmpc_actor_pop_kernels.hpp"
 #include "stmpc_rec_kernels.hpp"
+#include "stmpc_sim_groups_kernels.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -205,8 +206,9 @@ struct stmpc_ctx {
     } cc;
     // batched episode simulator (stmpc_sim_*)
     struct Sim {
-        DevBuf ego, nveh, vx, vv, va, vc, delay, status, ticks, rng, acc, route;
+        DevBuf ego, nveh, vx, vv, va, vc, delay, status, ticks, rng, acc, route, groups;
         int N = 0, route_n = 0;
+        int G = 0, n_per_group = 0;   // traffic groups (stmpc_sim_init_groups_device): `groups` holds G sim::Cfg; 0, 0 = an ungrouped world
         int64_t generation = 0;    // stmpc_sim_init_device calls so far (a recorder bound to an earlier world refuses to go on)
         int ensure(int n_) {
             const size_t n = (size_t)n_, KS = sim::KS;
@@ -1802,20 +1804,8 @@ int make_simcfg(const stmpc_sim_cfg *g, sim::Cfg *c) {
 void sim_route_of(stmpc_ctx *c, sim::Cfg *sc) {
     if (c->sim.route_n >= 2) { sc->route = c->sim.route.as<double>(); sc->route_n = c->sim.route_n; }
 }
-}  // namespace
-
-extern "C" {
-
-int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *stream) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
-    sim::Cfg sc;
-    TRY(make_simcfg(g, &sc));
-    HIPCHK(hipSetDevice(c->device));
-    TRY(c->sim.ensure(N));
-    c->sim.N = N;
-    ++c->sim.generation;
-    c->env.N = 0;                 // (the vector environment's bookkeeping no longer describes this world; stmpc_env_reset_device sets it again)
+// the context's device copy of g's route (x then y), or none
+int sim_route_upload(stmpc_ctx *c, const stmpc_sim_cfg *g, void *stream) {
     c->sim.route_n = 0;
     if (g->ego_route_xy && g->ego_route_n >= 2) {
         const int n = g->ego_route_n;
@@ -1830,6 +1820,60 @@ int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *str
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));       // (xy is a local)
         c->sim.route_n = n;
     }
+    return STMPC_OK;
+}
+// Traffic groups: every cfg valid, and equal in what the shared kernels (k_sim_view, k_env_act), the one route and the one vehicle type read.
+// Changes nothing; `out` receives the G kernel cfgs without their route.
+int check_groups(const stmpc_sim_cfg *cfgs, int G, int n_per_group, std::vector<sim::Cfg> *out) {
+    if (!cfgs) return fail(STMPC_EINVAL, "sim cfgs is NULL");
+    if (G < 1 || G > STMPC_SIM_GROUPS_MAX) return fail(STMPC_EINVAL, "G must be 1 ... STMPC_SIM_GROUPS_MAX (64) traffic groups");
+    if (n_per_group < 1) return fail(STMPC_EINVAL, "n_per_group must be positive");
+    if ((int64_t)G * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, "G * n_per_group out of range");
+    out->resize((size_t)G);
+    for (int g = 0; g < G; ++g) TRY(make_simcfg(&cfgs[g], &(*out)[g]));
+    const stmpc_sim_cfg &a = cfgs[0];
+    if (a.ego_route_xy && a.ego_route_n >= 2) {
+        if (a.ego_route_n > 4096) return fail(STMPC_EINVAL, "ego_route_n out of range (at most 4096 points)");
+        for (int i = 1; i < a.ego_route_n; ++i)
+            if (!(a.ego_route_xy[2 * i] > a.ego_route_xy[2 * i - 2])) return fail(STMPC_EINVAL, "ego_route_xy: x must be strictly increasing");
+    }
+    const int route_a = a.ego_route_xy && a.ego_route_n >= 2 ? a.ego_route_n : 0;
+    for (int g = 1; g < G; ++g) {
+        const stmpc_sim_cfg &b = cfgs[g];
+#define SAME(field) if (!(a.field == b.field)) return fail(STMPC_EINVAL, "traffic groups must share " #field " (it differs in group " + std::to_string(g) + ")")
+        SAME(tick_length); SAME(spawn_x); SAME(despawn_x); SAME(ego_start_x); SAME(ego_start_y); SAME(arrive_x); SAME(sensor_radius);
+        SAME(veh_accel); SAME(veh_decel); SAME(veh_min_gap); SAME(veh_tau); SAME(veh_emergency_decel); SAME(veh_length); SAME(veh_width);
+        SAME(disruption_min_s); SAME(yield_overlap);
+#undef SAME
+        const int route_b = b.ego_route_xy && b.ego_route_n >= 2 ? b.ego_route_n : 0;
+        if (route_a != route_b || (route_a && a.ego_route_xy != b.ego_route_xy && memcmp(a.ego_route_xy, b.ego_route_xy, (size_t)route_a * 16) != 0))
+            return fail(STMPC_EINVAL, "traffic groups must share ego_route_xy (it differs in group " + std::to_string(g) + ": equal points, or NULL alike)");
+    }
+    return STMPC_OK;
+}
+// the checks every grouped step entry starts with
+int check_grouped_world(stmpc_ctx *c, int N) {
+    if (c->sim.G < 1) return fail(STMPC_EINVAL, "the world has no traffic groups (stmpc_sim_init_groups_device): use the plain step entry");
+    if (N != c->sim.N) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_groups_device (G * n_per_group)");
+    return STMPC_OK;
+}
+const char *const GROUPED_WORLD = "the world has traffic groups (stmpc_sim_init_groups_device): one cfg would step every group; use the grouped step entry";
+}  // namespace
+
+extern "C" {
+
+int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
+    sim::Cfg sc;
+    TRY(make_simcfg(g, &sc));
+    HIPCHK(hipSetDevice(c->device));
+    TRY(c->sim.ensure(N));
+    c->sim.N = N;
+    ++c->sim.generation;
+    c->env.N = 0;                 // (the vector environment's bookkeeping no longer describes this world; stmpc_env_reset_device sets it again)
+    c->sim.G = 0; c->sim.n_per_group = 0;      // (nor does the table of traffic groups)
+    TRY(sim_route_upload(c, g, stream));
     sim_route_of(c, &sc);
     hipLaunchKernelGGL(sim::k_sim_init, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, sc, N, c->sim.state());
     HIPCHK(hipGetLastError());
@@ -1852,6 +1896,7 @@ int stmpc_sim_view_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, int Kmax,
 int stmpc_sim_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, int N, const double *d_cmd_speed, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (N != c->sim.N || !d_cmd_speed) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or NULL device pointer");
+    if (c->sim.G) return fail(STMPC_EINVAL, GROUPED_WORLD);
     sim::Cfg sc;
     DevP dp;
     TRY(make_simcfg(g, &sc));
@@ -1860,6 +1905,48 @@ int stmpc_sim_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_c
     HIPCHK(hipSetDevice(c->device));
     hipLaunchKernelGGL(sim::k_sim_step, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, dp, sc, N, c->sim.state(), d_cmd_speed, p->crash_min_s);
     HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_sim_init_groups_device(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    std::vector<sim::Cfg> table;
+    TRY(check_groups(cfgs, G, n_per_group, &table));
+    const int N = G * n_per_group;
+    HIPCHK(hipSetDevice(c->device));
+    TRY(c->sim.ensure(N));
+    TRY(c->sim.groups.ensure(table.size() * sizeof(sim::Cfg)));
+    c->sim.N = N;
+    ++c->sim.generation;
+    c->env.N = 0;
+    c->sim.G = 0; c->sim.n_per_group = 0;
+    TRY(sim_route_upload(c, &cfgs[0], stream));
+    for (auto &sc : table) sim_route_of(c, &sc);
+    HIPCHK(hipMemcpyAsync(c->sim.groups.p, table.data(), table.size() * sizeof(sim::Cfg), hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));           // (table is a local; the step entries read the device copy and take no cfgs)
+    c->sim.G = G; c->sim.n_per_group = n_per_group;
+    hipLaunchKernelGGL(sim::k_sim_init_groups, dim3((n_per_group + 63) / 64, G), dim3(64), 0, (hipStream_t)stream, c->sim.groups.as<sim::Cfg>(), n_per_group, c->sim.state());
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_sim_step_groups_device(stmpc_ctx *c, const stmpc_params *p, int N, const double *d_cmd_speed, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(check_grouped_world(c, N));
+    if (!d_cmd_speed) return fail(STMPC_EINVAL, "NULL device pointer");
+    DevP dp;
+    TRY(make_devp(p, &dp));
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(sim::k_sim_step_groups, dim3((c->sim.n_per_group + 63) / 64, c->sim.G), dim3(64), 0, (hipStream_t)stream, dp, c->sim.groups.as<sim::Cfg>(),
+                       c->sim.n_per_group, c->sim.state(), d_cmd_speed, p->crash_min_s);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_sim_groups(stmpc_ctx *c, int *G, int *n_per_group) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (G) *G = c->sim.G;
+    if (n_per_group) *n_per_group = c->sim.n_per_group;
     return STMPC_OK;
 }
 
@@ -1909,22 +1996,19 @@ int make_envcfg(const stmpc_env_cfg *g, env::ECfg *c) {
     return STMPC_OK;
 }
 env::EState env_state(stmpc_ctx *c) { return c->env.state(c->sticky.as<unsigned>() + 2); }
-}  // namespace
-
-extern "C" {
-
-uint64_t stmpc_env_episode_seed(uint64_t seed, uint32_t episode) { return env::episode_seed(seed, episode); }
-
-int stmpc_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, float *d_obs, int obs_stride, void *stream) {
+// argument checks of the reset entries (nothing changes before they pass)
+int env_reset_check(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, const float *d_obs, int obs_stride, env::ECfg *e) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (!p) return fail(STMPC_EINVAL, "params is NULL");
-    env::ECfg e;
-    TRY(make_envcfg(ec, &e));
-    if (d_obs && obs_stride < e.obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
+    TRY(make_envcfg(ec, e));
+    if (d_obs && obs_stride < e->obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
     if (ec->action_mode != STMPC_ENV_CONTINUOUS_JERK && (!ec->action_values || ec->n_action_values < 1 || ec->n_action_values > STMPC_ENV_MAX_ACTIONS))
         return fail(STMPC_EINVAL, "a discrete env needs 1..STMPC_ENV_MAX_ACTIONS action_values");
     if (ec->log_capacity < 0) return fail(STMPC_EINVAL, "log_capacity must not be negative");
-    TRY(stmpc_sim_init_device(c, g, N, stream));
+    return STMPC_OK;
+}
+// the environment's bookkeeping for the world of N environments just initialised: buffers, the action table, an empty log
+int env_reset_begin(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, env::ECfg *e, void *stream) {
     auto &v = c->env;
     const int cap = ec->log_capacity ? ec->log_capacity : 16 * N;
     TRY(v.ensure(N, cap));
@@ -1938,11 +2022,65 @@ int stmpc_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_
     HIPCHK(hipMemsetAsync(v.log_n.p, 0, 4, (hipStream_t)stream));
     v.N = N;
     v.mode = ec->action_mode;
+    e->log_cap = cap; e->n_actions = v.n_actions; e->actions = v.actions.as<double>();
+    return STMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+uint64_t stmpc_env_episode_seed(uint64_t seed, uint32_t episode) { return env::episode_seed(seed, episode); }
+
+int stmpc_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, float *d_obs, int obs_stride, void *stream) {
+    env::ECfg e;
+    TRY(env_reset_check(c, p, ec, d_obs, obs_stride, &e));
+    TRY(stmpc_sim_init_device(c, g, N, stream));
+    TRY(env_reset_begin(c, ec, N, &e, stream));
     sim::Cfg sc;
     TRY(make_simcfg(g, &sc));
     sim_route_of(c, &sc);
-    e.seed = sc.seed; e.log_cap = cap; e.n_actions = v.n_actions; e.actions = v.actions.as<double>();
+    e.seed = sc.seed;
     hipLaunchKernelGGL(env::k_env_reset, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, sc, N, c->sim.state(), env_state(c), d_obs, obs_stride);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_env_reset_groups_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *cfgs, int G, int n_per_group, const stmpc_env_cfg *ec, float *d_obs,
+                                  int obs_stride, void *stream) {
+    env::ECfg e;
+    TRY(env_reset_check(c, p, ec, d_obs, obs_stride, &e));
+    TRY(stmpc_sim_init_groups_device(c, cfgs, G, n_per_group, stream));
+    TRY(env_reset_begin(c, ec, G * n_per_group, &e, stream));
+    e.seed = 0;                                  // (unused: a group's environments take their seed from the group's cfg)
+    hipLaunchKernelGGL(env::k_env_reset_groups, dim3((n_per_group + 63) / 64, G), dim3(64), 0, (hipStream_t)stream, e, c->sim.groups.as<sim::Cfg>(), n_per_group,
+                       c->sim.state(), env_state(c), d_obs, obs_stride);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_env_step_groups_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
+                                 double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(check_grouped_world(c, N));
+    if (N != c->env.N) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_groups_device");
+    if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    env::ECfg e;
+    DevP dp;
+    TRY(make_envcfg(ec, &e));
+    if (obs_stride < e.obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
+    if (e.mode != c->env.mode) return fail(STMPC_EINVAL, "env_cfg.action_mode differs from the one the context was reset with (stmpc_env_reset_groups_device)");
+    TRY(make_devp(p, &dp));
+    e.seed = 0; e.log_cap = c->env.log_cap; e.n_actions = c->env.n_actions; e.actions = c->env.actions.as<double>();
+    HIPCHK(hipSetDevice(c->device));
+    const int npg = c->sim.n_per_group;
+    const dim3 grid((N + 63) / 64), ggrid((npg + 63) / 64, c->sim.G), block(64);
+    const sim::State s = c->sim.state();
+    const env::EState es = env_state(c);
+    const sim::Cfg *groups = c->sim.groups.as<sim::Cfg>();
+    hipLaunchKernelGGL(env::k_env_act, grid, block, 0, (hipStream_t)stream, e, N, s, es, d_action);
+    hipLaunchKernelGGL(sim::k_sim_step_groups, ggrid, block, 0, (hipStream_t)stream, dp, groups, npg, s, (const double *)es.cmd, p->crash_min_s);
+    hipLaunchKernelGGL(env::k_env_post_groups, ggrid, block, 0, (hipStream_t)stream, e, groups, npg, s, es, d_obs, obs_stride, d_reward, d_terminated, d_truncated,
+                       d_final_obs, d_final_stats);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
@@ -1951,6 +2089,7 @@ int stmpc_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_c
                           double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device");
+    if (c->sim.G) return fail(STMPC_EINVAL, GROUPED_WORLD);
     if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     env::ECfg e;
     sim::Cfg sc;

@@ -359,10 +359,17 @@ __device__ __forceinline__ void sim_init_env(const Cfg &c_, const State &s, int 
     for (int q = 0; q < NACC; ++q) s.acc[(size_t)e * NACC + q] = 0.0;
     s.acc[(size_t)e * NACC + 5] = 1e300;
 }
-__global__ void __launch_bounds__(64) k_sim_init(Cfg c, int N, State s) {
+// k_sim_init's body for the N environments `s` points at (the grouped entry of stmpc_sim_groups_kernels.hpp runs it on a group's slice and cfg)
+__device__ __forceinline__ void sim_init_body(const Cfg &c, int N, const State &s) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     sim_init_env(c, s, e, c.seed);
+}
+__global__ void __launch_bounds__(64) k_sim_init(Cfg c, int N, State s) { sim_init_body(c, N, s); }
+// `s` moved on by `off` environments: rows [off, ...) of every array (a traffic group's slice of a grouped world)
+__device__ __forceinline__ State state_slice(const State &s, size_t off) {
+    return State{s.ego4 + off * 4, s.nveh + off, s.vx + off * KS, s.vv + off * KS, s.va + off * KS, s.vc + off * KS, s.delay + off, s.status + off, s.ticks + off,
+                 s.rng + off, s.acc + off * NACC};
 }
 // The planner's view of each environment (HighwayState.from_sumo, prediction.py:112-142): the vehicles within the sensor radius of the ego (plane
 // distance; the highway lane runs at y = -1.6), front to back, and the ego with its s coordinate.
@@ -382,8 +389,8 @@ __global__ void __launch_bounds__(64) k_sim_view(Cfg c, int N, int Kmax, State s
     for (int i = k; i < Kmax; ++i) { ox[(size_t)e * Kmax + i] = 0.0; ov[(size_t)e * Kmax + i] = 0.0; if (oa) oa[(size_t)e * Kmax + i] = 0.0; }
     k_count[e] = k;
 }
-// One simulator tick with the commanded ego speed.
-__global__ void __launch_bounds__(64) k_sim_step(DevP p, Cfg c, int N, State s, const double *__restrict__ cmd_speed, double crash_min_s) {
+// One simulator tick with the commanded ego speed: k_sim_step's body for the N environments `s` and `cmd_speed` point at.
+__device__ __forceinline__ void sim_step_body(const DevP &p, const Cfg &c, int N, const State &s, const double *__restrict__ cmd_speed, double crash_min_s) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N || s.status[e] != 0) return;
     const double dt = c.tick;
@@ -506,6 +513,9 @@ __global__ void __launch_bounds__(64) k_sim_step(DevP p, Cfg c, int N, State s, 
     if (px >= c.arrive_x) s.status[e] = 1;
     else if (crashed) s.status[e] = 2;
     else if (tk + 1 >= c.max_ticks) s.status[e] = 3;
+}
+__global__ void __launch_bounds__(64) k_sim_step(DevP p, Cfg c, int N, State s, const double *__restrict__ cmd_speed, double crash_min_s) {
+    sim_step_body(p, c, N, s, cmd_speed, crash_min_s);
 }
 }  // namespace sim
 }  // namespace stmpc

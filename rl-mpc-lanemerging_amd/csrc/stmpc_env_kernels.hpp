@@ -205,10 +205,18 @@ __global__ void __launch_bounds__(64) k_env_act(ECfg c, int N, sim::State s, ESt
     es.cmd[e] = cmd; es.pjerk[e] = pjerk; es.inv[e] = inv;
 }
 
-// JerkEnv.step after control.step() (merge_gym.py:102-140), then the vector env's bookkeeping.
-__global__ void __launch_bounds__(64) k_env_post(ECfg c, sim::Cfg sc, int N, sim::State s, EState es, float *__restrict__ obs, int obs_stride, double *__restrict__ rew,
-                                                 unsigned char *__restrict__ term, unsigned char *__restrict__ trunc, float *__restrict__ final_obs,
-                                                 double *__restrict__ final_stats) {
+// `es` moved on by `off` environments (a traffic group's slice); the episode log, its counter and the error word stay the world's
+__device__ __forceinline__ EState estate_slice(const EState &es, size_t off) {
+    return EState{es.episode + off, es.prev_a + off, es.pjerk + off, es.inv + off, es.ret + off, es.cmd + off, es.live + off, es.vx + off * sim::KS,
+                  es.vv + off * sim::KS, es.va + off * sim::KS, es.k + off, es.log, es.log_n, es.err};
+}
+
+// JerkEnv.step after control.step() (merge_gym.py:102-140), then the vector env's bookkeeping: k_env_post's body for the N environments the state
+// and step arrays point at.  `seed`: the run's seed of these environments (ECfg::seed; a traffic group's own); `row0`: the world's row of
+// environment 0 (the environment column of a log row holds row0 + e).
+__device__ __forceinline__ void env_post_body(const ECfg &c, const sim::Cfg &sc, unsigned long long seed, int row0, int N, const sim::State &s, const EState &es,
+                                              float *__restrict__ obs, int obs_stride, double *__restrict__ rew, unsigned char *__restrict__ term,
+                                              unsigned char *__restrict__ trunc, float *__restrict__ final_obs, double *__restrict__ final_stats) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     const int status = s.status[e];
@@ -249,23 +257,31 @@ __global__ void __launch_bounds__(64) k_env_post(ECfg c, sim::Cfg sc, int N, sim
     if (slot < (unsigned)c.log_cap) {
         double *lg = es.log + (size_t)slot * NLOG;
         for (int q = 0; q < sim::NACC; ++q) lg[q] = acc[q];
-        lg[sim::NACC] = (double)status; lg[sim::NACC + 1] = (double)s.ticks[e]; lg[sim::NACC + 2] = ret; lg[NSTAT] = (double)e; lg[NSTAT + 1] = (double)ep;
+        lg[sim::NACC] = (double)status; lg[sim::NACC + 1] = (double)s.ticks[e]; lg[sim::NACC + 2] = ret; lg[NSTAT] = (double)(row0 + e); lg[NSTAT + 1] = (double)ep;
     }
     if (!c.autoreset) { es.ret[e] = ret; return; }
     const unsigned j = (unsigned)ep + 1u;
-    const unsigned long long ep_seed = episode_seed(c.seed, j);
+    const unsigned long long ep_seed = episode_seed(seed, j);
     sim::sim_init_env(sc, s, e, ep_seed);
     s.rng[e] = episode_ctr(s.rng[e], j, ep_seed);
     es.episode[e] = (int)j; es.prev_a[e] = 0.0; es.ret[e] = 0.0;          // JerkEnv.reset (merge_gym.py:142-161)
     env_obs(c, sc, s, es, e, row);
 }
+__global__ void __launch_bounds__(64) k_env_post(ECfg c, sim::Cfg sc, int N, sim::State s, EState es, float *__restrict__ obs, int obs_stride, double *__restrict__ rew,
+                                                 unsigned char *__restrict__ term, unsigned char *__restrict__ trunc, float *__restrict__ final_obs,
+                                                 double *__restrict__ final_stats) {
+    env_post_body(c, sc, c.seed, 0, N, s, es, obs, obs_stride, rew, term, trunc, final_obs, final_stats);
+}
 
 // Observation of every environment's current state and a fresh episode bookkeeping (stmpc_env_reset_device, after k_sim_init).
-__global__ void __launch_bounds__(64) k_env_reset(ECfg c, sim::Cfg sc, int N, sim::State s, EState es, float *__restrict__ obs, int obs_stride) {
+__device__ __forceinline__ void env_reset_body(const ECfg &c, const sim::Cfg &sc, int N, const sim::State &s, const EState &es, float *__restrict__ obs, int obs_stride) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     es.episode[e] = 0; es.prev_a[e] = 0.0; es.ret[e] = 0.0; es.pjerk[e] = 0.0; es.inv[e] = 0.0; es.live[e] = 1;
     if (obs) env_obs(c, sc, s, es, e, obs + (size_t)e * obs_stride);
+}
+__global__ void __launch_bounds__(64) k_env_reset(ECfg c, sim::Cfg sc, int N, sim::State s, EState es, float *__restrict__ obs, int obs_stride) {
+    env_reset_body(c, sc, N, s, es, obs, obs_stride);
 }
 
 // The reward for arbitrary batched states (stmpc_env_reward_device): ego4 [N][4], other_x [N][Kmax] front to back, k [N].

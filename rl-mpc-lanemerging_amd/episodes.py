@@ -33,12 +33,28 @@ def ego_start_position(route="lane"):
     return x0 + EGO_START_ARC * ux, y0 + EGO_START_ARC * uy
 
 
-def sim_cfg(seed=0, max_episode_length=100.0, route="lane"):
+# The traffic types of the reference's experiment matrix (configs/{st,train,combined,cross,ddpg}_*.json differ in these two fields; "heavy" and
+# "slow" are what the cross configs call the default traffic next to a medium / moderate network).
+TRAFFIC_TYPES = {
+    "low": {"BASE_TRAFFIC_INTERVAL": 2.4, "OTHER_CAR_SPEED": 7.0},
+    "medium": {"BASE_TRAFFIC_INTERVAL": 1.8, "OTHER_CAR_SPEED": 7.0},
+    "default": {"BASE_TRAFFIC_INTERVAL": 1.2, "OTHER_CAR_SPEED": 7.0},
+    "moderate": {"BASE_TRAFFIC_INTERVAL": 1.2, "OTHER_CAR_SPEED": 11.0},
+    "fast": {"BASE_TRAFFIC_INTERVAL": 1.2, "OTHER_CAR_SPEED": 15.0},
+    "heavy": {"BASE_TRAFFIC_INTERVAL": 1.2, "OTHER_CAR_SPEED": 7.0},
+    "slow": {"BASE_TRAFFIC_INTERVAL": 1.2, "OTHER_CAR_SPEED": 7.0},
+}
+_TRAFFIC_KEYS = ("BASE_TRAFFIC_INTERVAL", "OTHER_CAR_SPEED", "VARY_TRAFFIC_START_TIMES", "seed")
+
+
+def sim_cfg(seed=0, max_episode_length=100.0, route="lane", overrides=None):
     """``route``: "lane" (default) = the ego follows the centre line of its lanes in the reference's network (``scenario.py``; TraCI reports those
-    positions), None = the straight lines the planner assumes (prediction.py:46-59; the world of rounds 3-4, kept for the mechanics test)."""
+    positions), None = the straight lines the planner assumes (prediction.py:46-59; the world of rounds 3-4, kept for the mechanics test).
+    ``overrides``: a dict of setting names that take precedence over ``Settings`` for this cfg (``sim_cfgs``: a traffic group's own values)."""
     S = Settings
     ex, ey = ego_start_position(route)
-    g = lambda name, default: getattr(S, name, default)
+    ov = overrides or {}
+    g = lambda name, default: ov[name] if name in ov else getattr(S, name, default)
     return _capi.SimCfg(tick_length=S.TICK_LENGTH, other_car_speed=g("OTHER_CAR_SPEED", 7.0), base_traffic_interval=g("BASE_TRAFFIC_INTERVAL", 1.2),
                         spawn_x=SPAWN_X, despawn_x=DESPAWN_X, ego_start_x=ex, ego_start_y=ey, arrive_x=ARRIVE_X, sensor_radius=g("SENSOR_RADIUS", 125.0),
                         start_speed=g("START_SPEED", 15.0), start_speed_std=g("START_SPEED_VARIANCE", 5.0), min_start_speed=g("MIN_START_SPEED", 5.0),
@@ -49,6 +65,55 @@ def sim_cfg(seed=0, max_episode_length=100.0, route="lane"):
                         randomize_start_speed=int(bool(g("RANDOMIZE_START_SPEED", True))), max_ticks=int(max_episode_length / S.TICK_LENGTH),
                         yield_overlap=2,          # (the one junction rule, include/stmpc.h)
                         seed=int(seed), disruption_min_s=float(g("MERGE_POINT_X", -50.0))).set_route(np.stack(scenario.lane_polyline()[:2], axis=1) if route == "lane" else None)
+
+
+def traffic_settings(entry):
+    """One traffic group as a dict of settings: ``entry`` is a name of ``TRAFFIC_TYPES`` or a dict with BASE_TRAFFIC_INTERVAL and OTHER_CAR_SPEED
+    (and optionally VARY_TRAFFIC_START_TIMES and a ``seed``); ValueError for anything else."""
+    if isinstance(entry, str):
+        if entry not in TRAFFIC_TYPES:
+            raise ValueError("unknown traffic type %r (one of %s)" % (entry, ", ".join(TRAFFIC_TYPES)))
+        return dict(TRAFFIC_TYPES[entry])
+    if not isinstance(entry, dict) or "BASE_TRAFFIC_INTERVAL" not in entry or "OTHER_CAR_SPEED" not in entry:
+        raise ValueError("a traffic group is a name of TRAFFIC_TYPES or a dict with BASE_TRAFFIC_INTERVAL and OTHER_CAR_SPEED, not %r" % (entry,))
+    unknown = [k for k in entry if k not in _TRAFFIC_KEYS]
+    if unknown:
+        raise ValueError("a traffic group may set %s, not %s" % (", ".join(_TRAFFIC_KEYS), ", ".join(map(str, unknown))))
+    return dict(entry)
+
+
+def sim_cfgs(traffic, seed=0, max_episode_length=100.0, route="lane"):
+    """One ``SimCfg`` per traffic group (a ``_capi.SimCfgTable`` for ``stmpc_sim_init_groups_device``): ``traffic`` is a list of names of
+    ``TRAFFIC_TYPES`` or of dicts (``traffic_settings``).  Every cfg comes from ``sim_cfg``'s code path with the group's values in place of the
+    global ``Settings``', which are read for everything else and never written.
+
+    Seeds: group g's is its own ``seed`` entry if it has one, else ``vec_env.episode_seed(seed, g)`` -- ``seed`` itself for group 0 (a one-group
+    world is the plain world of that seed), splitmix64 of ``seed + g * 0x9E3779B97F4A7C15`` for the others, so groups are different draws.  Give two
+    groups the same ``seed`` entry for common random numbers."""
+    from . import vec_env
+    groups = [traffic_settings(t) for t in traffic]
+    if not groups:
+        raise ValueError("traffic must name at least one group")
+    cfgs = []
+    for gi, t in enumerate(groups):
+        gseed = int(t.pop("seed")) if "seed" in t else vec_env.episode_seed(seed, gi)
+        cfgs.append(sim_cfg(gseed, max_episode_length, route, overrides=t))
+    return _capi.SimCfgTable(cfgs)
+
+
+def _check_traffic(n, traffic, policy):
+    """(G, n_per_group) for ``n`` environments in the groups of ``traffic``; ValueError when they do not split or do not coincide with the
+    members of a population ``policy``.  Touches no device."""
+    G = len(traffic)
+    if G < 1 or G > _capi.SIM_GROUPS_MAX:
+        raise ValueError("traffic must name 1 ... %d groups, not %d" % (_capi.SIM_GROUPS_MAX, G))
+    if int(n) < G or int(n) % G:
+        raise ValueError("n = %d environments do not split into %d traffic groups of equal size" % (n, G))
+    npg = int(n) // G
+    if hasattr(policy, "P") and (policy.P != G or policy.n_per_member != npg):
+        raise ValueError("the population has %d members of %d environments, the traffic %d groups of %d: cell c pairs member c with traffic c, so they must coincide"
+                         % (policy.P, policy.n_per_member, G, npg))
+    return G, npg
 
 
 class EpisodeRunner:
@@ -63,9 +128,14 @@ class EpisodeRunner:
 
     ``policy`` may be an ``actor.ActorPopulation`` (anything with a ``P`` attribute): member m then drives environments
     [m * n_per_member, (m + 1) * n_per_member), ``n`` must be ``policy.n``, and ``result()`` gains ``out["member"]`` (see ``summary_by_member``,
-    ``report.Report.by_member``).  The members' environments are different draws of one world, not common random numbers."""
+    ``report.Report.by_member``).  The members' environments are different draws of one world, not common random numbers.
 
-    def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, record=None):
+    ``traffic``: None (one world from the global ``Settings``) or a list as ``sim_cfgs`` takes: the world then has ``G = len(traffic)`` traffic
+    groups of ``n / G`` consecutive environments (``stmpc_sim_init_groups_device``), group g bit-identical to a lone runner of ``n / G``
+    environments with that traffic and group g's seed, and ``result()`` gains ``out["traffic_group"]``.  With a population policy too, its P
+    must be G and its ``n_per_member`` the group size: cell c pairs member c with traffic c (``cross_matrix`` builds a models x traffic grid)."""
+
+    def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, record=None, traffic=None):
         import torch
         self.torch = torch
         if controller not in ("st", "combined"):
@@ -73,10 +143,14 @@ class EpisodeRunner:
             raise ValueError("controller must be 'st' or 'combined', not %r" % (controller,))
         if hasattr(policy, "P") and int(n) != policy.n:
             raise ValueError("n = %d, the population of policies was built for %d x %d = %d environments" % (n, policy.P, policy.n_per_member, policy.n))
+        self.traffic = list(traffic) if traffic is not None else None
+        self.G, self.n_per_group = _check_traffic(n, self.traffic, policy) if self.traffic is not None else (0, 0)
         self.n, self.kmax, self.controller, self.policy = int(n), int(kmax), controller, policy
+        self.cfgs = sim_cfgs(self.traffic, seed, max_episode_length) if self.traffic is not None else None
         self.ctx = ctx or _capi.default_context()
         self.params = _capi.Params.from_settings(Settings)
-        self.cfg = sim_cfg(seed, max_episode_length)
+        self.cfg = self.cfgs[0] if self.cfgs is not None else sim_cfg(seed, max_episode_length)      # (what the view reads is equal across groups)
+        self.max_ticks = max(c.max_ticks for c in self.cfgs) if self.cfgs is not None else self.cfg.max_ticks
         self.tick_length = Settings.TICK_LENGTH
         dev = torch.device("cuda", torch.cuda.current_device())
         H = _capi.num_t(self.params)
@@ -89,7 +163,10 @@ class EpisodeRunner:
         self.last_rl = torch.ones(n, dtype=torch.int32, device=dev)
         self.d_status = z(n, dtype=torch.int32)
         self.ticks_done = 0
-        self.ctx.sim_init(self.cfg, n)
+        if self.cfgs is not None:
+            self.ctx.sim_init_groups(self.cfgs, self.n_per_group)
+        else:
+            self.ctx.sim_init(self.cfg, n)
         self.recorder = None
         if record is not None:
             from . import report
@@ -121,7 +198,10 @@ class EpisodeRunner:
         if self.recorder is not None:
             # the state before control, as the reference appends it to state_history (control.py:280-289), with this tick's command
             self.recorder.tick(n, kmax, self.d_ego5, self.d_k, self.d_ox, self.d_ov, self.d_oa, cmd, d["takeover"] if self.controller == "combined" else None)
-        ctx.sim_step(self.params, self.cfg, n, cmd.data_ptr())
+        if self.cfgs is not None:
+            ctx.sim_step_groups(self.params, n, cmd.data_ptr())
+        else:
+            ctx.sim_step(self.params, self.cfg, n, cmd.data_ptr())
         self.ticks_done += 1
 
     def status(self):
@@ -139,6 +219,8 @@ class EpisodeRunner:
             out["percent_st"] = (self.takeovers / self.torch.clamp(self.controlled, min=1.0)).cpu().numpy()
         if hasattr(self.policy, "P"):
             out["member"] = np.arange(self.n) // self.policy.n_per_member
+        if self.cfgs is not None:
+            out["traffic_group"] = np.arange(self.n) // self.n_per_group
         if self.recorder is not None:
             from . import report
             out["report"] = report.Report.from_result(out, self.recorder.read())
@@ -165,7 +247,7 @@ def stats_columns(status, ticks, acc, tick_length):
     return out
 
 
-def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, check_every=16, max_ticks=None, record=None):
+def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, check_every=16, max_ticks=None, record=None, traffic=None):
     """Run ``n`` merge episodes to the end (or for ``max_ticks`` ticks); returns the per-episode columns of the reference's stats report
     (``crashed``, ``merged``, ``mean_speed``, ``max_speed``, ``mean_abs_jerk``, ``closest_distance``, ``mean_closest_distance``,
     ``time_taken``, ``time_to_merge`` (NaN unless merged)) plus ``ticks``, ``status`` (0 still running), ``ego4`` and ``percent_st``
@@ -173,9 +255,9 @@ def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max
 
     controller: "st" = ``st.do_st_control`` every tick (TASK "ST"); "combined" = ``do_combined_control`` with ``policy``
     (see ``combined.decide_batch_device``).  record: None, or a ``report.RecorderConfig`` -- the result then holds ``report`` (``report.Report``),
-    see ``EpisodeRunner``."""
-    r = EpisodeRunner(n, seed, controller, policy, ctx, kmax, max_episode_length, record)
-    limit = r.cfg.max_ticks + 1 if max_ticks is None else min(int(max_ticks), r.cfg.max_ticks + 1)
+    see ``EpisodeRunner``.  traffic: None, or the traffic groups of ``EpisodeRunner``; the tick limit is then the largest group's ``max_ticks + 1``."""
+    r = EpisodeRunner(n, seed, controller, policy, ctx, kmax, max_episode_length, record, traffic)
+    limit = r.max_ticks + 1 if max_ticks is None else min(int(max_ticks), r.max_ticks + 1)
     for tick in range(limit):
         r.tick()
         if tick % check_every == check_every - 1 and (r.status() != 0).all():
@@ -185,7 +267,7 @@ def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max
 
 def summary(stats):
     """Column means as the reference's report rows hold them (stats.py:145-158)."""
-    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4", "report", "member")}
+    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4", "report", "member", "traffic_group")}
 
 
 def summary_by_member(stats, P):
@@ -196,3 +278,42 @@ def summary_by_member(stats, P):
         raise ValueError("%d environments do not split into %d members" % (n, P))
     npm = n // P
     return [summary({k: v[m * npm:(m + 1) * npm] for k, v in stats.items() if k != "report"}) for m in range(P)]
+
+
+def summary_by_group(stats, G):
+    """``summary`` of each traffic group's environments: G dicts, group g from rows [g * n / G, (g + 1) * n / G) of every column (the result of a
+    run with ``traffic``)."""
+    n = len(stats["status"])
+    if G < 1 or n % G:
+        raise ValueError("%d environments do not split into %d traffic groups" % (n, G))
+    npg = n // G
+    return [summary({k: v[g * npg:(g + 1) * npg] for k, v in stats.items() if k != "report"}) for g in range(G)]
+
+
+def cross_matrix(models, traffic, n_per_cell, seed=0, ctx=None, kmax=16, max_episode_length=100.0, record=None, max_ticks=None, check_every=16):
+    """The reference's ``combined_{traffic}_{seed}`` diagonal and ``cross_{traffic_1}_network_{traffic_2}_traffic_{seed}`` off-diagonals in ONE run:
+    every model of ``models`` (as ``actor.ActorPopulation`` takes them: shipped names, paths, learners, actors) under the combined controller on
+    every traffic group of ``traffic`` (as ``sim_cfgs`` takes them), ``n_per_cell`` episodes each.  Cell c = i * len(traffic) + j (row-major) pairs
+    model i with traffic j: the population repeats each member len(traffic) times, the traffic list is tiled len(models) times, and the cells are
+    the groups of one runner (cell c's default seed is ``vec_env.episode_seed(seed, c)``).
+    Returns ``{"matrix": [len(models)][len(traffic)] ``summary`` dicts, "stats": the raw result (with ``member`` = cell and ``traffic_group`` =
+    cell), "models": [...], "traffic": [...]}``."""
+    from . import actor
+    models, traffic = list(models), list(traffic)
+    M, T = len(models), len(traffic)
+    if M < 1 or T < 1:
+        raise ValueError("cross_matrix needs at least one model and one traffic group")
+    if int(n_per_cell) < 1:
+        raise ValueError("n_per_cell must be positive")
+    if M * T > _capi.SIM_GROUPS_MAX:
+        raise ValueError("%d models x %d traffic groups = %d cells, at most %d fit one run" % (M, T, M * T, _capi.SIM_GROUPS_MAX))
+    cell_traffic = [traffic_settings(t) for t in traffic] * M          # (validates the names before anything is built)
+    ctx = ctx if ctx is not None else _capi.default_context()
+    # (a shipped name or a path is loaded once and its actor repeated along its row)
+    loaded = [actor.DDPGActor(os.fspath(m), 1, ctx, Settings) if isinstance(m, (str, os.PathLike)) else m for m in models]
+    cell_models = [m for m in loaded for _ in range(T)]
+    pop = actor.ActorPopulation(cell_models, int(n_per_cell), ctx, Settings)
+    stats = run_episodes(pop.n, seed=seed, controller="combined", policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, check_every=check_every,
+                         max_ticks=max_ticks, record=record, traffic=cell_traffic)
+    cells = summary_by_group(stats, M * T)
+    return {"matrix": [[cells[i * T + j] for j in range(T)] for i in range(M)], "stats": stats, "models": models, "traffic": traffic}

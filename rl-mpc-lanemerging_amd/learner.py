@@ -365,7 +365,11 @@ class DDPGPopulation:
     (None: 0 .. P-1); ``init``: as ``DDPGLearner``'s, for every member, or a list of P.  Member m starts exactly as
     ``DDPGLearner(seed=seeds[m], init=...)`` does and stays bit-identical to that learner driven on its slice alone.
     ``act`` / ``push`` / ``update`` / ``stats_device`` / ``stats`` are ``DDPGLearner``'s on the whole env's tensors; ``member(m)`` is a
-    ``DDPGLearner`` view (``state_dict``, ``load_state_dict``, ``export_actor``, ``grads``, ``minibatch``)."""
+    ``DDPGLearner`` view (``state_dict``, ``load_state_dict``, ``export_actor``, ``grads``, ``minibatch``).
+
+    ``env`` may have traffic groups (``MergeVecEnv(traffic=[...])``) when there are as many as members: member m then trains on traffic m -- the
+    reference's ``train_{traffic}_{seed}.json`` runs for several traffic types in one launch sequence -- and stays bit-identical to a lone
+    learner on a lone env of that traffic."""
 
     def __init__(self, env, cfgs, seeds=None, init=None, ctx=None):
         if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], DDPGConfig):
@@ -377,6 +381,9 @@ class DDPGPopulation:
         # (a member count outside 1 ... DDPG_POP_MAX is the library's to refuse)
         if 1 <= P <= _capi.DDPG_POP_MAX and env.n % P:
             raise ValueError("env.n = %d is not a multiple of the population's %d members" % (env.n, P))
+        if getattr(env, "sim_cfgs", None) is not None and env.G != P:
+            # (equal sizes: G == P makes group m's environments member m's)
+            raise ValueError("the env has %d traffic groups, the population %d members: member m trains on traffic m, so they must coincide" % (env.G, P))
         self.seeds = list(range(P)) if seeds is None else [int(x) for x in seeds]
         inits = list(init) if isinstance(init, (list, tuple)) else [init] * P
         if len(self.seeds) != P or len(inits) != P:
@@ -495,18 +502,24 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
     return out
 
 
-def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None):
+def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None):
     """The reference's per-model ``EVALUATE_COMBINED_DDPG`` -- and the evaluation ``train_ddpg_all_with_lr_drop`` (ddpg.py:96-117) ends with -- for
     every member at once: ``n_per_member`` merge episodes per member under the combined controller, in ONE run of P * n_per_member environments
     whose policy is an ``actor.ActorPopulation``.  ``source``: a ``DDPGPopulation`` or a ``DDPGLearner`` (zero-copy views of the weights as they
     are on the device: nothing is exported or uploaded), or a list as ``ActorPopulation`` takes (names, paths, learners, actors).
     ``ctx``: the evaluation's context; by default a new one, because a context holds one world and the training env has its own.
     Returns ``{"stats": run_episodes' columns + "member", "by_member": P summary rows, "reports": P ``report.Report``s (None without ``record``)}``.
-    The members' episodes are different draws of one world (identically distributed, not common random numbers)."""
+    The members' episodes are different draws of one world (identically distributed, not common random numbers).
+    ``traffic``: None, or one traffic group per member (as ``episodes.sim_cfgs`` takes them): member m is evaluated on traffic m, and its report
+    row carries that traffic's TRAFFIC_DESCRIPTION."""
     from . import episodes
-    ctx = ctx if ctx is not None else _capi.Context(-1)
     members = source if isinstance(source, (DDPGPopulation, list, tuple)) else [source]
+    if traffic is not None and len(traffic) != len(members):
+        raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), len(members)))
+    ctx = ctx if ctx is not None else _capi.Context(-1)
     pop = _actor.ActorPopulation(members, n_per_member, ctx, Settings)
-    stats = episodes.run_episodes(pop.n, seed=seed, controller="combined", policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record)
+    stats = episodes.run_episodes(pop.n, seed=seed, controller="combined", policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
+                                  traffic=traffic)
     rep = stats.get("report")
-    return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P), "reports": rep.by_member(pop.P) if rep is not None else None}
+    return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),
+            "reports": rep.by_member(pop.P, traffic) if rep is not None else None}

@@ -194,6 +194,7 @@ class Report:
         self.columns = {k: np.asarray(v) for k, v in columns.items()}
         self._profiles = profiles                   # counts, jerks, speeds, takeover_counts, bins
         self._rec = recorded                        # Recorder.read(), or None
+        self.traffic = None                         # the traffic group this report's episodes ran on (by_group / by_member), or None: the global Settings'
 
     @classmethod
     def from_result(cls, result, recorded):
@@ -205,17 +206,34 @@ class Report:
         cols = {k: v for k, v in result.items() if k not in ("ego4", "report")}
         return cls(cols, prof, recorded)
 
-    def by_member(self, P):
+    def by_group(self, G, traffic):
+        """G ``Report``s, group g's from environments [g * n / G, (g + 1) * n / G) of a run with traffic groups (``by_member``'s split), each with
+        the TRAFFIC_DESCRIPTION of its own group in ``row()``.  ``traffic``: the G groups as the runner took them."""
+        if traffic is None or len(traffic) != G:
+            raise ValueError("by_group needs the run's %d traffic groups" % G)
+        return self.by_member(G, traffic)
+
+    def by_member(self, P, traffic=None):
         """P ``Report``s, member m's from environments [m * n / P, (m + 1) * n / P): its columns, rings and per-environment accumulators, and the
         profiles summed from the latter in the order the recorder's own reduction has for that many environments (``reduce_rows_host``) -- what a
         recorder of the member's environments alone would hold.  For a run whose policy was an ``actor.ActorPopulation`` of P members
-        (the reference: one report row per evaluated model, experiment_data/saved_data.csv).  ``P = 1``: this report itself."""
+        (the reference: one report row per evaluated model, experiment_data/saved_data.csv).  ``P = 1``: this report itself.
+        ``traffic``: None, or the P traffic groups the members ran on (``episodes.traffic_settings`` entries): part m's ``row()`` then describes
+        traffic m instead of the global ``Settings``'."""
+        from . import episodes
         r = self._need_recorded()
         n = len(r["status"])
         if P < 1 or n % P:
             raise ValueError("%d environments do not split into %d members" % (n, P))
+        if traffic is not None and len(traffic) != P:
+            raise ValueError("%d traffic groups for %d parts" % (len(traffic), P))
+        groups = [episodes.traffic_settings(t) for t in traffic] if traffic is not None else None
         if P == 1:
-            return [self]
+            if groups is None:
+                return [self]
+            one = Report(self.columns, self._profiles, self._rec)
+            one.traffic = groups[0]
+            return [one]
         npm, nb, out = n // P, len(r["bins"]) - 1, []
         for m in range(P):
             sl = slice(m * npm, (m + 1) * npm)
@@ -223,6 +241,8 @@ class Report:
             rec = {"ring": r["ring"][sl].copy() if r["ring"] is not None else None, "length": r["length"][sl].copy(), "acc_env": acc,
                    "acc_reduced": reduce_rows_host(acc), "status": r["status"][sl].copy(), "bins": r["bins"].copy(), "kmax": r["kmax"]}
             out.append(Report.from_result({k: v[sl] for k, v in self.columns.items()}, rec))
+            if groups is not None:
+                out[-1].traffic = groups[m]
         return out
 
     @classmethod
@@ -277,7 +297,8 @@ class Report:
             cols[name] = avg[name]
             cols[name + "_std"] = std[name]
         S = Settings
-        g = lambda name, default: getattr(S, name, default)
+        t = self.traffic or {}
+        g = lambda name, default: t[name] if name in t else getattr(S, name, default)
         cols["ST_DESCRIPTION"] = "st-{}-{}-{}-{}-{}-{}-{}-{}".format(S.V_WEIGHT, S.A_WEIGHT, S.J_WEIGHT, S.A_WEIGHT, S.MIN_ALLOWED_DISTANCE, S.CRASH_MIN_S,
                                                                      S.START_UNCERTAINTY, S.UNCERTAINTY_PER_SECOND)
         cols["TRAFFIC_DESCRIPTION"] = "uniform-{}-{}-{}".format(g("OTHER_CAR_SPEED", 7.0), g("BASE_TRAFFIC_INTERVAL", 1.2),

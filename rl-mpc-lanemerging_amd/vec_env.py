@@ -78,9 +78,13 @@ class MergeVecEnv:
     "Slotted Jerk" or "ST".  Settings are read at construction (Settings.MAX_EPISODE_LENGTH, the traffic, the reward weights, ...).
     ``ctx``: the ``_capi.Context`` that holds the world (default: a context of its own).  A context holds one world: a second env reset on it,
     or an ``EpisodeRunner`` started on it, ends this one -- its next ``step`` raises instead of stepping the other's world.
-    Kernels run on the current torch stream of the call."""
+    Kernels run on the current torch stream of the call.
 
-    def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0):
+    ``traffic``: None, or a list as ``episodes.sim_cfgs`` takes: ``G = len(traffic)`` traffic groups of ``n / G`` consecutive environments
+    (``stmpc_env_reset_groups_device`` / ``stmpc_env_step_groups_device``, the launches of an ungrouped env), group g bit-identical -- through
+    every autoreset -- to a lone ``MergeVecEnv`` of ``n / G`` environments with that traffic and group g's seed (``episodes.sim_cfgs``)."""
+
+    def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, traffic=None):
         import torch
         self.torch = torch
         self.env_id = Settings.GYM_ENVIRONMENT if env_id is None else env_id
@@ -89,9 +93,12 @@ class MergeVecEnv:
         self.n, self.seed, self.autoreset = int(n), int(seed), bool(autoreset)
         if self.n < 1:
             raise ValueError("n must be positive")
+        self.traffic = list(traffic) if traffic is not None else None
+        self.G, self.n_per_group = episodes._check_traffic(self.n, self.traffic, None) if self.traffic is not None else (0, 0)
+        self.sim_cfgs = episodes.sim_cfgs(self.traffic, seed, float(Settings.MAX_EPISODE_LENGTH)) if self.traffic is not None else None
         self.ctx = ctx if ctx is not None else _capi.Context(-1)
         self.params = _capi.Params.from_settings(Settings)
-        self.sim_cfg = episodes.sim_cfg(seed, float(Settings.MAX_EPISODE_LENGTH))
+        self.sim_cfg = self.sim_cfgs[0] if self.sim_cfgs is not None else episodes.sim_cfg(seed, float(Settings.MAX_EPISODE_LENGTH))
         self.log_capacity = int(log_capacity) if log_capacity else 16 * self.n
         self.obs_dim = (4 if Settings.USE_ACCELERATION_OF_OTHER_CARS else 3) * (Settings.CARS_AHEAD + Settings.CARS_BEHIND) + 4
         self.observation_low, self.observation_high = observation_bounds(Settings)
@@ -115,7 +122,10 @@ class MergeVecEnv:
         """Every environment back to episode 0 (``stmpc_env_reset_device``): the observations of the start states [n][obs_dim] float32."""
         self._cur = 0
         obs = self._obs[0]
-        self.ctx.env_reset(self.params, self.sim_cfg, self.cfg, self.n, obs.data_ptr(), self.obs_dim, self._stream())
+        if self.sim_cfgs is not None:
+            self.ctx.env_reset_groups(self.params, self.sim_cfgs, self.n_per_group, self.cfg, obs.data_ptr(), self.obs_dim, self._stream())
+        else:
+            self.ctx.env_reset(self.params, self.sim_cfg, self.cfg, self.n, obs.data_ptr(), self.obs_dim, self._stream())
         _owners[self.ctx] = self
         self._reset_done = True
         return obs
@@ -150,8 +160,12 @@ class MergeVecEnv:
         a = self._action_tensor(action)
         self._cur ^= 1
         obs = self._obs[self._cur]
-        self.ctx.env_step(self.params, self.sim_cfg, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
-                          self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(), self._stream())
+        if self.sim_cfgs is not None:
+            self.ctx.env_step_groups(self.params, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
+                                     self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(), self._stream())
+        else:
+            self.ctx.env_step(self.params, self.sim_cfg, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
+                              self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(), self._stream())
         self._last_action = a                                # (kept alive until the kernels have read it)
         info = {"final_observation": self._final_obs, "final_stats": self._final_stats, "episode_return": self._final_stats[:, _capi.ENV_NSTAT - 1],
                 "status": self._final_stats[:, _capi.SIM_NACC]}
@@ -163,7 +177,7 @@ class MergeVecEnv:
 
     def drain_episode_stats(self):
         """The episodes finished since the last drain (or reset), as the columns of ``episodes.EpisodeRunner.result()`` plus ``env``,
-        ``episode`` and ``episode_return``, ordered by (env, episode).  Synchronises; raises if device-side errors were flagged, and
+        ``episode``, ``episode_return`` and ``traffic_group`` (``env // n_per_group``; 0 without traffic groups), ordered by (env, episode).  Synchronises; raises if device-side errors were flagged, and
         RuntimeError if more episodes finished than the log holds (``log_capacity``, default 16 n: drain more often)."""
         rows, dropped = self.ctx.env_drain(self.log_capacity)
         self.ctx.check_error()
@@ -176,4 +190,5 @@ class MergeVecEnv:
         out["episode_return"] = rows[:, _capi.ENV_NSTAT - 1]
         out["env"] = rows[:, _capi.ENV_NSTAT].astype(np.int64)
         out["episode"] = rows[:, _capi.ENV_NSTAT + 1].astype(np.int64)
+        out["traffic_group"] = out["env"] // self.n_per_group if self.sim_cfgs is not None else np.zeros(len(rows), dtype=np.int64)
         return out

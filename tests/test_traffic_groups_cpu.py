@@ -1,0 +1,149 @@
+"""Traffic groups, host side (episodes.TRAFFIC_TYPES / sim_cfgs / cross_matrix, the traffic arguments of EpisodeRunner and MergeVecEnv, the
+stmpc_sim_*_groups_* / stmpc_env_*_groups_* entries of include/stmpc.h).  No GPU: the table against its fixture, ``sim_cfgs`` leaves the global
+Settings alone and gives the documented seeds, header / library / binding agree, and every shape mismatch is a ValueError raised before a
+context is made or asked for anything.
+"""
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, REPO
+
+
+def _pkg():
+    import rl_mpc_lanemerging_amd as pkg
+    if pkg.build.needs_build():
+        pkg.build.build()
+    return pkg
+
+
+class _NoDevice:
+    """A context that must not be asked for anything."""
+
+    def __getattr__(self, name):
+        raise AssertionError("the device was touched (%s)" % name)
+
+
+def test_traffic_types_are_the_reference_matrix():
+    _pkg()
+    from rl_mpc_lanemerging_amd import episodes
+    want = json.load(open(os.path.join(GOLDEN, "traffic_types.json")))
+    assert episodes.TRAFFIC_TYPES == want
+    assert set(want) == {"low", "medium", "default", "moderate", "fast", "heavy", "slow"}
+    assert want["heavy"] == want["slow"] == want["default"]
+    assert len({(v["BASE_TRAFFIC_INTERVAL"], v["OTHER_CAR_SPEED"]) for v in want.values()}) == 5
+
+
+def test_header_library_and_binding_agree_on_the_group_entries():
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import _capi as capi
+    lib = capi.load()
+    header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
+    names = {"stmpc_sim_init_groups_device", "stmpc_sim_step_groups_device", "stmpc_sim_groups", "stmpc_env_reset_groups_device", "stmpc_env_step_groups_device"}
+    declared = {name: args for name, args in re.findall(r"\b(stmpc_(?:sim|env)_[a-z_0-9]*groups[a-z_0-9]*)\s*\(([^)]*)\)\s*;", header)}
+    assert set(declared) == names and names <= set(capi.EXPORTS)
+    for name, args in declared.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(args.split(",")), name
+    assert "#define STMPC_SIM_GROUPS_MAX %d" % capi.SIM_GROUPS_MAX in header and capi.SIM_GROUPS_MAX == 64
+    assert capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8 and "#define STMPC_ABI_VERSION 8" in header
+
+
+def test_sim_cfgs_leaves_settings_alone_and_seeds_as_documented(restore_settings):
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import _capi as capi, episodes, vec_env
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    before = pkg.Settings.snapshot()
+    traffic = ["low", "default", "fast", {"BASE_TRAFFIC_INTERVAL": 1.5, "OTHER_CAR_SPEED": 9.0, "VARY_TRAFFIC_START_TIMES": False, "seed": 99}]
+    table = episodes.sim_cfgs(traffic, seed=5, max_episode_length=20.0)
+    assert pkg.Settings.snapshot() == before
+    assert isinstance(table, capi.SimCfgTable) and len(table) == 4
+    plain = episodes.sim_cfg(5, 20.0)
+    assert pkg.Settings.snapshot() == before
+    for g, (interval, speed, vary) in enumerate([(2.4, 7.0, 1), (1.2, 7.0, 1), (1.2, 15.0, 1), (1.5, 9.0, 0)]):
+        for c in (table[g], table.array[g]):                       # the caller's object and the row the library reads
+            assert (c.base_traffic_interval, c.other_car_speed, c.vary_traffic_start_times) == (interval, speed, vary), g
+            assert c.max_ticks == plain.max_ticks and c.ego_route_n == plain.ego_route_n and c.ego_route_n >= 2
+            for name, _ in capi.SimCfg._fields_:
+                if name not in ("base_traffic_interval", "other_car_speed", "vary_traffic_start_times", "seed", "ego_route_xy"):
+                    assert getattr(c, name) == getattr(plain, name), (g, name)
+            assert np.array_equal(np.ctypeslib.as_array(c.ego_route_xy, (c.ego_route_n, 2)), np.ctypeslib.as_array(plain.ego_route_xy, (plain.ego_route_n, 2)))
+    # group g's default seed: vec_env.episode_seed(seed, g) -- the seed itself for group 0, splitmix64 of seed + g * golden gamma after it
+    assert [table[g].seed for g in range(4)] == [5, vec_env.episode_seed(5, 1), vec_env.episode_seed(5, 2), 99]
+    assert table[1].seed == capi.env_episode_seed(5, 1) and table[1].seed not in (5, 6)
+    # a one-group table of the default traffic is the plain cfg, field for field
+    one = episodes.sim_cfgs(["default"], seed=5, max_episode_length=20.0)[0]
+    for name, _ in capi.SimCfg._fields_:
+        if name != "ego_route_xy":
+            assert getattr(one, name) == getattr(plain, name), name
+    # the global Settings still decide everything a group does not set
+    pkg.Settings.SENSOR_RADIUS = 80.0
+    assert episodes.sim_cfgs(["fast"])[0].sensor_radius == 80.0
+    with pytest.raises(ValueError, match="unknown traffic type 'rush'"):
+        episodes.sim_cfgs(["low", "rush"])
+    with pytest.raises(ValueError, match="BASE_TRAFFIC_INTERVAL and OTHER_CAR_SPEED"):
+        episodes.sim_cfgs([{"OTHER_CAR_SPEED": 7.0}])
+    with pytest.raises(ValueError, match="not TICK_LENGTH"):
+        episodes.sim_cfgs([{"BASE_TRAFFIC_INTERVAL": 1.2, "OTHER_CAR_SPEED": 7.0, "TICK_LENGTH": 0.1}])
+    with pytest.raises(ValueError, match="at least one"):
+        episodes.sim_cfgs([])
+
+
+def test_mismatched_shapes_are_refused_before_any_context(restore_settings):
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import episodes, learner, report, vec_env
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    three = ["low", "default", "fast"]
+
+    class Pop:                                                     # what EpisodeRunner reads of an actor.ActorPopulation
+        def __init__(self, P, npm):
+            self.P, self.n_per_member, self.n = P, npm, P * npm
+    nodev = _NoDevice()
+    with pytest.raises(ValueError, match="70 environments do not split into 3 traffic groups"):
+        episodes.EpisodeRunner(70, ctx=nodev, traffic=three)
+    with pytest.raises(ValueError, match="2 members of 36 environments, the traffic 3 groups of 24"):
+        episodes.EpisodeRunner(72, controller="combined", policy=Pop(2, 36), ctx=nodev, traffic=three)
+    with pytest.raises(ValueError, match="3 members of 24 environments, the traffic 2 groups of 36"):
+        episodes.run_episodes(72, controller="combined", policy=Pop(3, 24), ctx=nodev, traffic=["low", "fast"])
+    with pytest.raises(ValueError, match="unknown traffic type"):
+        episodes.EpisodeRunner(72, ctx=nodev, traffic=["low", "default", "quick"])
+    with pytest.raises(ValueError, match="1 ... 64 groups, not 65"):
+        episodes.EpisodeRunner(130, ctx=nodev, traffic=["low"] * 65)
+    with pytest.raises(ValueError, match="do not split into 3 traffic groups"):
+        vec_env.MergeVecEnv(70, env_id="sumo-jerk-continuous-v0", ctx=nodev, traffic=three)
+    # cross_matrix: nothing is loaded or created for a matrix that cannot run
+    with pytest.raises(ValueError, match="unknown traffic type"):
+        episodes.cross_matrix(["low1"], ["low", "quick"], 24, ctx=nodev)
+    with pytest.raises(ValueError, match="n_per_cell must be positive"):
+        episodes.cross_matrix(["low1"], ["low"], 0, ctx=nodev)
+    with pytest.raises(ValueError, match="9 models x 8 traffic groups = 72 cells, at most 64"):
+        episodes.cross_matrix(["low1"] * 9, ["low"] * 8, 24, ctx=nodev)
+    with pytest.raises(ValueError, match="at least one model"):
+        episodes.cross_matrix([], ["low"], 24, ctx=nodev)
+    # a population on an env whose traffic groups are not its members
+    class Env:
+        n, obs_dim, continuous, sim_cfgs, G = 72, 20, True, object(), 3
+
+        @property
+        def ctx(self):
+            raise AssertionError("the device was touched")
+    cfg = learner.DDPGConfig(n_obs=20, batch=16, capacity=200, replay_start=0)
+    with pytest.raises(ValueError, match="3 traffic groups, the population 2 members"):
+        learner.DDPGPopulation(Env(), (cfg, 2))
+    with pytest.raises(ValueError, match="3 traffic groups for 2 members"):
+        learner.evaluate_members(["low1", "fast1"], 24, ctx=nodev, traffic=three)
+    # summaries and reports split by group
+    stats = {"status": np.array([1, 1, 2, 2, 1, 2]), "ticks": np.arange(6), "merged": np.array([1.0, 1, 0, 0, 1, 0]), "traffic_group": np.arange(6) // 2}
+    by = episodes.summary_by_group(stats, 3)
+    assert [b["merged"] for b in by] == [1.0, 0.0, 0.5] and "traffic_group" not in by[0]
+    with pytest.raises(ValueError, match="do not split into 4 traffic groups"):
+        episodes.summary_by_group(stats, 4)
+    rep = report.Report({"merged": np.ones(4)}, None, {"status": np.zeros(4)})
+    with pytest.raises(ValueError, match="needs the run's 2 traffic groups"):
+        rep.by_group(2, None)
+    with pytest.raises(ValueError, match="needs the run's 2 traffic groups"):
+        rep.by_group(2, three)
