@@ -707,6 +707,46 @@ int stmpc_env_step_groups_device(stmpc_ctx *ctx, const stmpc_params *p, const st
                                  void *stream);
 
 /*
+ * Controller groups: one batch of the combined controller split into C groups of n_per_group consecutive states, each with its own stmpc_combined_cfg,
+ * rolled out and decided in the launches of a lone batch.  The reference compares the combined controller's own settings one process per cell:
+ * main.do_grid_search_combined (main.py:62-81) sweeps ROLLOUT_LENGTH x ST_TEST_ROLLOUTS x TEST_ROLLOUT_STATE, its combined_*b configs flip
+ * CHECK_ROLLOUT_CRASH, LIMIT_DQN_SPEED, TEST_ST_STRICTLY_BETTER and REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED.  (Additive: new entries only, no
+ * signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)
+ * Group g of a grouped batch is, bit for bit, the lone batch of n_per_group states under cfgs[g]: decisions, commands, the cur_* arrays, the rollout
+ * bookkeeping and -- through the evaluation mask below -- the policy's evaluation counters.
+ *   May differ between groups: rollout_length, st_test_rollouts, check_rollout_crash, limit_dqn_speed, test_rollout_state, test_st_strictly_better,
+ *                   remember_last_choice.  Must be equal (else STMPC_EINVAL naming the field): tick_length, stop_x, sparse_control.
+ *   stmpc_combined_groups_set     validates every cfg (a rollout_length above STMPC_ROLLOUT_LIMIT in any group is refused), uploads the table and the
+ *                   static list of the rows whose group has test_rollout_state set (synchronous copies, once); C = 1 ... STMPC_SIM_GROUPS_MAX,
+ *                   n_per_group >= 1.  Ends a grouped rollout that is under way.  A refused call changes nothing.
+ *   stmpc_combined_groups_clear   ends the grouping (and a grouped rollout that is under way).
+ *   stmpc_rollout_step_groups_device   stmpc_rollout_step_device without a cfg: the context's table is read on the device, so a step copies nothing.  N
+ *                   must be C * n_per_group.  Call it for step = 1 .. Rmax, the largest group's max(rollout_length, 1): a step past a group's own
+ *                   length leaves that group's rows untouched.  rollout_s has row stride Rmax + 1 for every group (stmpc_combined_read_state:
+ *                   [N][Rmax + 1]; a group's history ends at its own length + 1).  While the context's rollout is a grouped one, the policy entries
+ *                   (stmpc_policy_features_device, stmpc_actor_eval_device, stmpc_actor_pop_eval_device) count an evaluation at step > 1 only for
+ *                   the rows that are live AND whose group has that step -- a lone batch of R steps asks its policy at steps 1 .. R only; `live`
+ *                   itself (stmpc_combined_read_state) keeps its meaning.
+ *   stmpc_combined_decide_groups_device   stmpc_combined_decide_device for a grouped rollout.  The feasibility probe solves only the rows of the groups
+ *                   that test (gathered through the static list: no round trip; a group that does not test can never latch a solver error for its rows).
+ *                   With sparse_control the controller is solved for the rows whose own group's branches hand control over (one round trip, as the
+ *                   plain entry) -- unless ANY group sets test_st_strictly_better: one such group makes the whole run dense (every row is solved;
+ *                   same decisions and commands either way, as stmpc_combined_cfg states).
+ *   The plain stmpc_rollout_step_device / stmpc_combined_decide_device ignore the table and behave as without one.  STMPC_EINVAL before any launch,
+ *   changing nothing: a grouped step or decide with no table set; N != C * n_per_group; a grouped decide after a plain rollout or a plain decide after a
+ *   grouped rollout; step > 1 that does not continue a grouped rollout of this shape.
+ */
+int stmpc_combined_groups_set(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_combined_cfg *cfgs, int C, int n_per_group);
+int stmpc_combined_groups_clear(stmpc_ctx *ctx);
+int stmpc_rollout_step_groups_device(stmpc_ctx *ctx, const stmpc_params *p, int N, int Kmax, int step, const double *d_ego5_start, double *d_cur_ego4,
+                                     const int32_t *d_k_count, double *d_cur_other_x, double *d_cur_other_v, double *d_cur_other_a,
+                                     const double *d_action, void *stream);
+int stmpc_combined_decide_groups_device(stmpc_ctx *ctx, const stmpc_params *p, int N, int Kmax, const double *d_ego5_start, const int32_t *d_k_count,
+                                        const double *d_other_x_start, const double *d_other_v_start, const double *d_cur_ego4,
+                                        const double *d_cur_other_x, const double *d_cur_other_v, const double *d_first_action,
+                                        const int32_t *d_last_choice_rl, int32_t *d_takeover, int32_t *d_reason, double *d_speed, void *stream);
+
+/*
  * Episode flight recorder on the device, next to the world (stmpc_sim_*): the per-tick histories the reference's evaluation keeps and what it
  * bins over the ego's position, for N environments in lock-step, with nothing crossing to the host until it is read.  (Additive: new entries
  * only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)

@@ -193,6 +193,7 @@ EXPORTS = (
     "stmpc_ddpg_replay_read", "stmpc_ddpg_gather_device", "stmpc_ddpg_sample_index", "stmpc_ddpg_noise",
     "stmpc_ddpg_pop_create", "stmpc_ddpg_pop_destroy", "stmpc_ddpg_pop_size", "stmpc_ddpg_pop_member", "stmpc_ddpg_pop_act_device",
     "stmpc_ddpg_pop_push_device", "stmpc_ddpg_pop_update_device", "stmpc_ddpg_pop_stats_device",
+    "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
@@ -269,6 +270,10 @@ def load():
     cp = C.POINTER(CombinedCfg)
     lib.stmpc_rollout_step_device.argtypes = [vp, pp, cp, C.c_int, C.c_int, C.c_int] + [vp] * 7 + [vp]
     lib.stmpc_combined_decide_device.argtypes = [vp, pp, cp, C.c_int, C.c_int] + [vp] * 12 + [vp]
+    lib.stmpc_combined_groups_set.argtypes = [vp, pp, cp, C.c_int, C.c_int]
+    lib.stmpc_combined_groups_clear.argtypes = [vp]
+    lib.stmpc_rollout_step_groups_device.argtypes = [vp, pp, C.c_int, C.c_int, C.c_int] + [vp] * 7 + [vp]
+    lib.stmpc_combined_decide_groups_device.argtypes = [vp, pp, C.c_int, C.c_int] + [vp] * 12 + [vp]
     sp = C.POINTER(SimCfg)
     lib.stmpc_policy_features_len.argtypes = [C.POINTER(FeaturesCfg)]
     lib.stmpc_policy_features_device.argtypes = [vp, C.POINTER(FeaturesCfg), C.c_int, C.c_int, C.c_int] + [vp] * 7 + [C.c_int, vp]
@@ -606,6 +611,30 @@ class Context:
         self._chk(self._lib.stmpc_combined_decide_device(self._h, C.byref(params), C.byref(cfg), int(N), int(Kmax), d_ego5_start, d_k, d_ox_start,
                                                          d_ov_start, d_cur_ego4, d_cur_ox, d_cur_ov, d_first_action, d_last_choice_rl,
                                                          d_takeover, d_reason, d_speed, stream))
+
+    # -- controller groups (stmpc_combined_groups_*; see include/stmpc.h) --
+    def combined_groups_set(self, params, cfgs, n_per_group):
+        """``stmpc_combined_groups_set``: ``cfgs`` is a sequence of ``CombinedCfg``, one per controller group."""
+        cfgs = list(cfgs)
+        arr = (CombinedCfg * max(len(cfgs), 1))()
+        for i, c in enumerate(cfgs):
+            C.memmove(C.byref(arr, i * C.sizeof(CombinedCfg)), C.byref(c), C.sizeof(CombinedCfg))
+        self._control_groups_key = None       # (combined.ControlGroups.ensure_set's note of the table the context holds)
+        self._chk(self._lib.stmpc_combined_groups_set(self._h, C.byref(params), arr, len(cfgs), int(n_per_group)))
+
+    def combined_groups_clear(self):
+        self._control_groups_key = None
+        self._chk(self._lib.stmpc_combined_groups_clear(self._h))
+
+    def rollout_step_groups_device(self, params, N, Kmax, step, d_ego5_start, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_action, stream=0):
+        self._chk(self._lib.stmpc_rollout_step_groups_device(self._h, C.byref(params), int(N), int(Kmax), int(step), d_ego5_start, d_cur_ego4,
+                                                             d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_action, stream))
+
+    def combined_decide_groups_device(self, params, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start, d_cur_ego4, d_cur_ox, d_cur_ov,
+                                      d_first_action, d_last_choice_rl, d_takeover, d_reason, d_speed, stream=0):
+        self._chk(self._lib.stmpc_combined_decide_groups_device(self._h, C.byref(params), int(N), int(Kmax), d_ego5_start, d_k, d_ox_start,
+                                                                d_ov_start, d_cur_ego4, d_cur_ox, d_cur_ov, d_first_action, d_last_choice_rl,
+                                                                d_takeover, d_reason, d_speed, stream))
 
     def policy_features_device(self, fcfg, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_evals, d_feat, feat_stride, stream=0):
         """The policy's float32 input vectors (dqn.get_state_vector_from_base_state + TimeFeature) into ``d_feat`` [N][feat_stride]."""

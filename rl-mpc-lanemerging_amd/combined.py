@@ -30,6 +30,78 @@ REASON_NAMES = {REASON_RL: "rl", REASON_CRASH: "crash predicted", REASON_SPEED: 
                 REASON_ROLLOUT: "st solver not happy with rollout state", REASON_ST_BETTER: "st path deemed better"}
 
 
+#: the settings of ``do_combined_control`` a controller group may set (the reference's ``Settings`` names)
+CONTROL_KEYS = ("ROLLOUT_LENGTH", "ST_TEST_ROLLOUTS", "TEST_ROLLOUT_STATE", "CHECK_ROLLOUT_CRASH", "LIMIT_DQN_SPEED", "TEST_ST_STRICTLY_BETTER",
+                "REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED")
+CONTROL_GROUPS_MAX = _capi.SIM_GROUPS_MAX
+
+
+class _Overlay:
+    """``Settings`` with a group's own values in front of it (read-only: nothing is written anywhere)."""
+
+    def __init__(self, base, values):
+        self._base, self._values = base, values
+
+    def __getattr__(self, name):
+        values = object.__getattribute__(self, "_values")
+        if name in values:
+            return values[name]
+        return getattr(object.__getattribute__(self, "_base"), name)
+
+
+def control_cfgs(control, sparse_control=False):
+    """One ``CombinedCfg`` per controller group: ``control`` is a list of dicts keyed by ``CONTROL_KEYS`` (any other key: ValueError).  Every cfg
+    comes from ``CombinedCfg.from_settings``' code path with the group's values in place of the global ``Settings``', which are read for
+    everything else and never written."""
+    cfgs = []
+    for g, entry in enumerate(control):
+        if not isinstance(entry, dict):
+            raise ValueError("controller group %d is %r, not a dict of %s" % (g, entry, ", ".join(CONTROL_KEYS)))
+        unknown = [k for k in entry if k not in CONTROL_KEYS]
+        if unknown:
+            raise ValueError("a controller group may set %s, not %s" % (", ".join(CONTROL_KEYS), ", ".join(map(str, unknown))))
+        cfgs.append(_capi.CombinedCfg.from_settings(_Overlay(Settings, dict(entry)), sparse_control=sparse_control))
+    if not cfgs:
+        raise ValueError("control must name at least one group")
+    return cfgs
+
+
+class ControlGroups:
+    """C controller groups of ``n_per_group`` consecutive states for ``decide_batch_device`` (``stmpc_combined_groups_set``): ``cfgs`` is a list of
+    ``CombinedCfg`` (``control_cfgs``).  Group g is bit-identical to a lone ``decide_batch_device`` of its slice under ``cfgs[g]``."""
+
+    def __init__(self, cfgs, n_per_group):
+        self.cfgs = list(cfgs)
+        self.C, self.n_per_group = len(self.cfgs), int(n_per_group)
+        if self.C < 1 or self.C > CONTROL_GROUPS_MAX:
+            raise ValueError("control must name 1 ... %d groups, not %d" % (CONTROL_GROUPS_MAX, self.C))
+        if self.n_per_group < 1:
+            raise ValueError("n_per_group must be positive")
+        self.n = self.C * self.n_per_group
+        self.rollout_length = max(max(int(c.rollout_length), 1) for c in self.cfgs)       # Rmax: the steps of a grouped rollout
+        self.key = (b"".join(bytes(c) for c in self.cfgs), self.n_per_group)
+
+    def ensure_set(self, ctx, params):
+        """Set the context's table unless it already holds this one (under these params)."""
+        key = self.key + (bytes(params),)
+        if getattr(ctx, "_control_groups_key", None) != key:
+            ctx._control_groups_key = None
+            ctx.combined_groups_set(params, self.cfgs, self.n_per_group)
+            ctx._control_groups_key = key
+
+
+def grid_search_cells():
+    """The valid cells of the reference's ``main.do_grid_search_combined`` (main.py:62-81), in its order, as dicts for ``control_cfgs``: the product
+    ROLLOUT_LENGTH x ST_TEST_ROLLOUTS x TEST_ROLLOUT_STATE less the cells its three skip rules drop (13 cells; pinned by the suite's fixture combined_grid.json)."""
+    import itertools
+    cells = []
+    for R, T, test in itertools.product([3, 5, 10, 20], [2, 5, 10], [True, False]):
+        if (not test and T != 2) or (R == 1 and T != 2) or T > R:
+            continue
+        cells.append({"ROLLOUT_LENGTH": R, "ST_TEST_ROLLOUTS": T, "TEST_ROLLOUT_STATE": test})
+    return cells
+
+
 def _unpack(ego4, k, ox, ov, oa, i):
     kk = int(k[i])
     return HighwayState((float(ego4[i, 0]), float(ego4[i, 1])), float(ego4[i, 2]), float(ego4[i, 3]),
@@ -45,9 +117,17 @@ def decide_batch_device(ctx, params, cfg, d_ego5, d_k, d_ox, d_ov, policy, d_las
     ``policy(step, cur_ego4, k, cur_ox, cur_ov, cur_oa) -> jerk[N]`` (fp64 device tensor) is the caller's network; it is asked once
     per rollout step for every episode (entries of episodes whose rollout has ended are ignored, dqn.py:129-141).  Returns device
     tensors ``takeover``, ``reason`` (REASON_*), ``speed`` (the command) and ``first_action``; the rollout bookkeeping stays in the
-    context (``ctx.combined_read_state``)."""
+    context (``ctx.combined_read_state``).
+
+    ``cfg`` may be a ``ControlGroups``: the states are then C groups of ``n_per_group`` rows, each under its own cfg; the rollout runs for the longest
+    group's length (``cfg.rollout_length``, also the ``rollout_length`` to read the state with) and a group's rows rest after their own."""
     import torch
     n, K = d_ego5.shape[0], d_ox.shape[1]
+    groups = cfg if isinstance(cfg, ControlGroups) else None
+    if groups is not None:
+        if n != groups.n:
+            raise ValueError("%d states, the controller groups are %d x %d = %d" % (n, groups.C, groups.n_per_group, groups.n))
+        groups.ensure_set(ctx, params)
     cur_ego4 = d_ego5[:, :4].clone().contiguous()      # (a copy: with one row the slice is already contiguous and would alias the start state)
     cur_ox, cur_ov = d_ox.clone(), d_ov.clone()
     cur_oa = d_oa.clone() if d_oa is not None else torch.zeros_like(d_ox)
@@ -56,15 +136,24 @@ def decide_batch_device(ctx, params, cfg, d_ego5, d_k, d_ox, d_ov, policy, d_las
         action = policy(step, cur_ego4, d_k, cur_ox, cur_ov, cur_oa).to(torch.float64).contiguous()
         if step == 1:
             first_action = action.clone()
-        ctx.rollout_step_device(params, cfg, n, K, step, d_ego5.data_ptr(), cur_ego4.data_ptr(), d_k.data_ptr(), cur_ox.data_ptr(),
-                                cur_ov.data_ptr(), cur_oa.data_ptr(), action.data_ptr(), stream)
+        if groups is not None:
+            ctx.rollout_step_groups_device(params, n, K, step, d_ego5.data_ptr(), cur_ego4.data_ptr(), d_k.data_ptr(), cur_ox.data_ptr(),
+                                           cur_ov.data_ptr(), cur_oa.data_ptr(), action.data_ptr(), stream)
+        else:
+            ctx.rollout_step_device(params, cfg, n, K, step, d_ego5.data_ptr(), cur_ego4.data_ptr(), d_k.data_ptr(), cur_ox.data_ptr(),
+                                    cur_ov.data_ptr(), cur_oa.data_ptr(), action.data_ptr(), stream)
     takeover = torch.empty(n, dtype=torch.int32, device=d_ego5.device)
     reason = torch.empty(n, dtype=torch.int32, device=d_ego5.device)
     speed = torch.empty(n, dtype=torch.float64, device=d_ego5.device)
-    ctx.combined_decide_device(params, cfg, n, K, d_ego5.data_ptr(), d_k.data_ptr(), d_ox.data_ptr(), d_ov.data_ptr(), cur_ego4.data_ptr(),
-                               cur_ox.data_ptr(), cur_ov.data_ptr(), first_action.data_ptr(),
-                               d_last_choice_rl.data_ptr() if d_last_choice_rl is not None else 0,
-                               takeover.data_ptr(), reason.data_ptr(), speed.data_ptr(), stream)
+    last = d_last_choice_rl.data_ptr() if d_last_choice_rl is not None else 0
+    if groups is not None:
+        ctx.combined_decide_groups_device(params, n, K, d_ego5.data_ptr(), d_k.data_ptr(), d_ox.data_ptr(), d_ov.data_ptr(), cur_ego4.data_ptr(),
+                                          cur_ox.data_ptr(), cur_ov.data_ptr(), first_action.data_ptr(), last, takeover.data_ptr(), reason.data_ptr(),
+                                          speed.data_ptr(), stream)
+    else:
+        ctx.combined_decide_device(params, cfg, n, K, d_ego5.data_ptr(), d_k.data_ptr(), d_ox.data_ptr(), d_ov.data_ptr(), cur_ego4.data_ptr(),
+                                   cur_ox.data_ptr(), cur_ov.data_ptr(), first_action.data_ptr(), last,
+                                   takeover.data_ptr(), reason.data_ptr(), speed.data_ptr(), stream)
     return {"takeover": takeover, "reason": reason, "speed": speed, "first_action": first_action,
             "cur_ego4": cur_ego4, "cur_ox": cur_ox, "cur_ov": cur_ov, "cur_oa": cur_oa}      # the last rolled-out state of every episode
 

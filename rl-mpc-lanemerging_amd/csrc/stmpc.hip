@@ -12,6 +12,7 @@
 #include "stmpc_actor_pop_kernels.hpp"
 #include "stmpc_rec_kernels.hpp"
 #include "stmpc_sim_groups_kernels.hpp"
+#include "stmpc_cc_groups_kernels.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -190,6 +191,13 @@ struct stmpc_ctx {
             path, bt, cost, pcrash, speed, fine, fine_len,
             sel_idx, sel_count, c_ego, c_k, c_ox, c_ov, c_speed, c_fine, c_fine_len;      // sparse controller solve: the states that need st.do_st_control
         int N = 0, K = 0, R = 0;
+        // controller groups (stmpc_combined_groups_set): `groups` holds C CCfg; C = 0: no table.  `grouped`: the rollout in the context was begun by
+        // stmpc_rollout_step_groups_device (R is then the largest group's rollout_length, the row stride of rollout_s less one)
+        DevBuf groups, ask, test_idx, c_pcrash;
+        std::vector<CCfg> table;
+        int C = 0, n_per_group = 0, Rmax = 0, n_test = 0, any_strict = 0, sparse = 0;
+        double tick = 0;
+        bool grouped = false;
         int *host_count = nullptr;  // pinned host word for the number of those states
         int64_t ticks = 0, control_solves = 0;      // decisions taken / controller solves run for them (stmpc_combined_counts)
         int ensure(int n_, int k_, int r_) {        // the rollout's bookkeeping (step 1)
@@ -1471,7 +1479,7 @@ int rollout_live(const stmpc_ctx *c, int N, int step, const int **live) {
     *live = nullptr;
     if (step > 1) {
         if (c->cc.N != N) return fail(STMPC_EINVAL, "step > 1 without a rollout of this size in the context (stmpc_rollout_step_device)");
-        *live = c->cc.live.as<int>();
+        *live = c->cc.grouped ? c->cc.ask.as<int>() : c->cc.live.as<int>();      // (a grouped rollout: not past the row's own group's last step either)
     }
     return STMPC_OK;
 }
@@ -1492,8 +1500,8 @@ int stmpc_rollout_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_c
     TRY(make_devp(p, &dp));
     TRY(make_ccfg(p, g, &cc));
     const int Kalloc = Kmax > 0 ? Kmax : 1;
-    if (step == 1) TRY(c->cc.ensure(N, Kalloc, cc.rollout_length));
-    else if (c->cc.N != N || c->cc.K != Kalloc || c->cc.R != cc.rollout_length) return fail(STMPC_EINVAL, "rollout step > 1 does not continue the rollout begun with step 1");
+    if (step == 1) { TRY(c->cc.ensure(N, Kalloc, cc.rollout_length)); c->cc.grouped = false; }
+    else if (c->cc.grouped || c->cc.N != N || c->cc.K != Kalloc || c->cc.R != cc.rollout_length) return fail(STMPC_EINVAL, "rollout step > 1 does not continue the rollout begun with step 1");
     CCState st = c->cc.state();
     with_kmax(Kalloc, [&](auto km) {
         hipLaunchKernelGGL(k_rollout_step<decltype(km)::value>, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, dp, cc, N, Kalloc, step, d_ego5_start, d_cur_ego4,
@@ -1660,7 +1668,7 @@ int stmpc_combined_decide_device(stmpc_ctx *c, const stmpc_params *p, const stmp
     TRY(make_ccfg(p, g, &cc));
     const int Kalloc = Kmax > 0 ? Kmax : 1;
     auto &b = c->cc;
-    if (b.N != N || b.K != Kalloc || b.R != cc.rollout_length) return fail(STMPC_EINVAL, "no rollout of this shape in the context (call stmpc_rollout_step_device first)");
+    if (b.grouped || b.N != N || b.K != Kalloc || b.R != cc.rollout_length) return fail(STMPC_EINVAL, "no rollout of this shape in the context (call stmpc_rollout_step_device first)");
     const int H = stmpc_num_t(p);
     if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
     hipStream_t st_ = (hipStream_t)stream;
@@ -1718,6 +1726,166 @@ int stmpc_combined_decide_device(stmpc_ctx *c, const stmpc_params *p, const stmp
     hipLaunchKernelGGL(k_cc_decide, dim3(blocks), dim3(64), 0, st_, cc, N, d_ego5_start, d_first_action, d_last_choice_rl, st, (const int *)b.pcrash.as<int>(),
                        (const double *)b.speed.as<double>(), (const double *)b.fine.as<double>(), (const int *)b.fine_len.as<int>(), STMPC_QP_NMAX,
                        d_takeover, d_reason, d_speed, c->sticky.as<unsigned>() + 1);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+// ---- controller groups (stmpc_cc_groups_kernels.hpp) ----
+int stmpc_combined_groups_set(stmpc_ctx *c, const stmpc_params *p, const stmpc_combined_cfg *cfgs, int C, int n_per_group) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (!p || !cfgs) return fail(STMPC_EINVAL, "params / combined cfgs is NULL");
+    if (C < 1 || C > STMPC_SIM_GROUPS_MAX) return fail(STMPC_EINVAL, "C must be 1 ... STMPC_SIM_GROUPS_MAX (64) controller groups");
+    if (n_per_group < 1) return fail(STMPC_EINVAL, "n_per_group must be positive");
+    if ((int64_t)C * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, "C * n_per_group out of range");
+    std::vector<CCfg> table((size_t)C);
+    for (int g = 0; g < C; ++g) TRY(make_ccfg(p, &cfgs[g], &table[g]));
+    for (int g = 1; g < C; ++g) {
+#define SAME(field) if (!(cfgs[0].field == cfgs[g].field)) return fail(STMPC_EINVAL, "controller groups must share " #field " (it differs in group " + std::to_string(g) + ")")
+        SAME(tick_length); SAME(stop_x); SAME(sparse_control);
+#undef SAME
+    }
+    // the rows of the groups that probe their rolled-out state: a static list, so a tick needs no round trip to gather them
+    std::vector<int> test_rows;
+    int Rmax = 1, any_strict = 0;
+    for (int g = 0; g < C; ++g) {
+        Rmax = table[g].rollout_length > Rmax ? table[g].rollout_length : Rmax;
+        any_strict |= table[g].strictly_better != 0;
+        if (table[g].test_rollout_state) for (int e = 0; e < n_per_group; ++e) test_rows.push_back(g * n_per_group + e);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    auto &b = c->cc;
+    TRY(b.groups.ensure(table.size() * sizeof(CCfg)));
+    TRY(b.test_idx.ensure((test_rows.size() + 1) * 4));
+    if (b.grouped) { b.grouped = false; b.N = 0; }       // (a grouped rollout of the former table cannot be continued or decided)
+    b.C = 0;
+    HIPCHK(hipMemcpy(b.groups.p, table.data(), table.size() * sizeof(CCfg), hipMemcpyHostToDevice));      // (synchronous: table and test_rows are locals)
+    if (!test_rows.empty()) HIPCHK(hipMemcpy(b.test_idx.p, test_rows.data(), test_rows.size() * 4, hipMemcpyHostToDevice));
+    b.table = std::move(table);
+    b.C = C; b.n_per_group = n_per_group; b.Rmax = Rmax; b.n_test = (int)test_rows.size(); b.any_strict = any_strict;
+    b.sparse = cfgs[0].sparse_control != 0; b.tick = cfgs[0].tick_length;
+    return STMPC_OK;
+}
+
+int stmpc_combined_groups_clear(stmpc_ctx *c) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    auto &b = c->cc;
+    if (b.grouped) { b.grouped = false; b.N = 0; }
+    b.C = 0; b.n_per_group = 0; b.Rmax = 0; b.n_test = 0; b.any_strict = 0; b.table.clear();
+    return STMPC_OK;
+}
+
+int stmpc_rollout_step_groups_device(stmpc_ctx *c, const stmpc_params *p, int N, int Kmax, int step, const double *d_ego5_start, double *d_cur_ego4,
+                                     const int32_t *d_k, double *d_cur_ox, double *d_cur_ov, double *d_cur_oa, const double *d_action, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT || step < 1) return fail(STMPC_EINVAL, "N, Kmax or step out of range");
+    auto &b = c->cc;
+    if (b.C < 1) return fail(STMPC_EINVAL, "the context has no controller groups (stmpc_combined_groups_set): use the plain rollout entry");
+    if ((int64_t)N != (int64_t)b.C * b.n_per_group) return fail(STMPC_EINVAL, "N does not match stmpc_combined_groups_set (C * n_per_group)");
+    if (!d_ego5_start || !d_cur_ego4 || !d_k || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    if (Kmax > 0 && (!d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
+    DevP dp;
+    TRY(make_devp(p, &dp));
+    const int Kalloc = Kmax > 0 ? Kmax : 1;
+    if (step > 1 && (!b.grouped || b.N != N || b.K != Kalloc || b.R != b.Rmax)) return fail(STMPC_EINVAL, "rollout step > 1 does not continue the grouped rollout begun with step 1");
+    HIPCHK(hipSetDevice(c->device));
+    if (step == 1) {
+        TRY(b.ask.ensure((size_t)N * 4));
+        TRY(b.ensure(N, Kalloc, b.Rmax));
+        b.grouped = true;
+    }
+    CCState st = b.state();
+    with_kmax(Kalloc, [&](auto km) {
+        hipLaunchKernelGGL(k_rollout_step_groups<decltype(km)::value>, dim3((b.n_per_group + 63) / 64, b.C), dim3(64), 0, (hipStream_t)stream, dp,
+                           (const CCfg *)b.groups.as<CCfg>(), b.n_per_group, Kalloc, step, b.Rmax + 1, d_ego5_start, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_action,
+                           st, b.ask.as<int>());
+    });
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_combined_decide_groups_device(stmpc_ctx *c, const stmpc_params *p, int N, int Kmax, const double *d_ego5_start, const int32_t *d_k,
+                                        const double *d_ox_start, const double *d_ov_start, const double *d_cur_ego4, const double *d_cur_ox,
+                                        const double *d_cur_ov, const double *d_first_action, const int32_t *d_last_choice_rl, int32_t *d_takeover,
+                                        int32_t *d_reason, double *d_speed, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (!p) return fail(STMPC_EINVAL, "NULL parameter struct");
+    TRY(check_batch(N, Kmax));
+    auto &b = c->cc;
+    if (b.C < 1) return fail(STMPC_EINVAL, "the context has no controller groups (stmpc_combined_groups_set): use the plain decide entry");
+    if ((int64_t)N != (int64_t)b.C * b.n_per_group) return fail(STMPC_EINVAL, "N does not match stmpc_combined_groups_set (C * n_per_group)");
+    if (!d_ego5_start || !d_k || !d_cur_ego4 || !d_first_action || !d_takeover || !d_reason || !d_speed) return fail(STMPC_EINVAL, "NULL device pointer");
+    if (Kmax > 0 && (!d_ox_start || !d_ov_start || !d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
+    const int Kalloc = Kmax > 0 ? Kmax : 1;
+    if (!b.grouped || b.N != N || b.K != Kalloc || b.R != b.Rmax) return fail(STMPC_EINVAL, "no grouped rollout of this shape in the context (call stmpc_rollout_step_groups_device first)");
+    const int H = stmpc_num_t(p);
+    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st_ = (hipStream_t)stream;
+    const size_t n = (size_t)N;
+    TRY(b.probe_ego.ensure(n * 5 * 8)); TRY(b.probe_ox.ensure(n * Kalloc * 8)); TRY(b.probe_ov.ensure(n * Kalloc * 8));
+    TRY(b.path.ensure(n * H * 4)); TRY(b.bt.ensure(n * 4)); TRY(b.cost.ensure(n * 8)); TRY(b.pcrash.ensure(n * 4));
+    TRY(b.speed.ensure(n * 8)); TRY(b.fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(b.fine_len.ensure(n * 4));
+    // (the compact batches of both gathers, sized once for all rows: no allocation between the launches of a tick)
+    TRY(b.c_ego.ensure(n * 5 * 8)); TRY(b.c_k.ensure(n * 4)); TRY(b.c_ox.ensure(n * Kalloc * 8)); TRY(b.c_ov.ensure(n * Kalloc * 8)); TRY(b.c_pcrash.ensure(n * 4));
+    TRY(b.c_speed.ensure(n * 8)); TRY(b.c_fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(b.c_fine_len.ensure(n * 4));
+    CCState st = b.state();
+    const CCfg *groups = b.groups.as<CCfg>();
+    const int npg = b.n_per_group, blocks = (N + 63) / 64;
+    const dim3 ggrid((npg + 63) / 64, b.C);
+    HIPCHK(hipMemsetAsync(b.pcrash.p, 0, n * 4, st_));
+    // 1. feasibility probe, only for the rows of the groups that test (a lone run of a group that does not never calls the solver for them)
+    if (b.n_test > 0) {
+        hipLaunchKernelGGL(k_cc_probe_state, dim3(blocks), dim3(64), 0, st_, N, Kalloc, Kmax, d_k, d_cur_ego4, d_cur_ox, d_cur_ov, st, b.probe_ego.as<double>(),
+                           b.probe_ox.as<double>(), b.probe_ov.as<double>());
+        if (b.n_test == N) {
+            TRY(stmpc_solve_batch_device(c, p, N, Kmax, b.probe_ego.as<double>(), d_k, b.probe_ox.as<double>(), b.probe_ov.as<double>(), b.path.as<int32_t>(),
+                                         b.bt.as<int32_t>(), b.cost.as<double>(), nullptr, b.pcrash.as<int32_t>(), stream));
+        } else {
+            const int M = b.n_test, mb = (M + 63) / 64;
+            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kalloc, (const int *)b.test_idx.as<int>(), (const double *)b.probe_ego.as<double>(), d_k,
+                               (const double *)b.probe_ox.as<double>(), (const double *)b.probe_ov.as<double>(), b.c_ego.as<double>(), b.c_k.as<int>(),
+                               b.c_ox.as<double>(), b.c_ov.as<double>());
+            TRY(stmpc_solve_batch_device(c, p, M, Kalloc, b.c_ego.as<double>(), b.c_k.as<int32_t>(), b.c_ox.as<double>(), b.c_ov.as<double>(), b.path.as<int32_t>(),
+                                         b.bt.as<int32_t>(), b.cost.as<double>(), nullptr, b.c_pcrash.as<int32_t>(), stream));
+            hipLaunchKernelGGL(k_cc_scatter_flag, dim3(mb), dim3(64), 0, st_, M, (const int *)b.test_idx.as<int>(), (const int *)b.c_pcrash.as<int>(), b.pcrash.as<int>());
+        }
+    }
+    // 2. the controller on the start state: sparse as the plain entry unless a group compares paths (then every row's path is needed: the run is dense)
+    HIPCHK(hipMemsetAsync(b.fine.p, 0, n * STMPC_QP_NMAX * 8, st_));
+    b.ticks += N;
+    if (b.sparse && !b.any_strict) {
+        TRY(b.sel_idx.ensure(n * 4)); TRY(b.sel_count.ensure(4));
+        if (!b.host_count) HIPCHK(hipHostMalloc((void **)&b.host_count, 4, hipHostMallocDefault));
+        HIPCHK(hipMemsetAsync(b.speed.p, 0xFF, n * 8, st_));
+        HIPCHK(hipMemsetAsync(b.fine_len.p, 0, n * 4, st_));
+        hipLaunchKernelGGL(k_cc_select_groups, dim3(1), dim3(1024), 0, st_, groups, npg, N, st, (const int *)b.pcrash.as<int>(), b.sel_idx.as<int>(), b.sel_count.as<int>());
+        HIPCHK(hipMemcpyAsync(b.host_count, b.sel_count.p, 4, hipMemcpyDeviceToHost, st_));
+        HIPCHK(hipStreamSynchronize(st_));
+        const int M = *b.host_count;
+        if (M < 0 || M > N) return fail(STMPC_EINTERNAL, "combined controller: selection count out of range");
+        b.control_solves += M;
+        if (M > 0) {
+            const size_t m = (size_t)M;
+            const int mb = (M + 63) / 64;
+            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kmax, (const int *)b.sel_idx.as<int>(), d_ego5_start, d_k, d_ox_start, d_ov_start,
+                               b.c_ego.as<double>(), b.c_k.as<int>(), b.c_ox.as<double>(), b.c_ov.as<double>());
+            HIPCHK(hipMemsetAsync(b.c_fine.p, 0, m * STMPC_QP_NMAX * 8, st_));
+            TRY(st_control_device(c, p, b.tick, M, Kalloc, b.c_ego.as<double>(), b.c_k.as<int32_t>(), b.c_ox.as<double>(), b.c_ov.as<double>(),
+                                  b.path.as<int32_t>(), b.bt.as<int32_t>(), b.cost.as<double>(), b.c_speed.as<double>(), b.c_fine.as<double>(),
+                                  b.c_fine_len.as<int32_t>(), stream, nullptr));
+            hipLaunchKernelGGL(k_cc_scatter, dim3(mb), dim3(64), 0, st_, M, (const int *)b.sel_idx.as<int>(), (const double *)b.c_speed.as<double>(),
+                               (const double *)b.c_fine.as<double>(), (const int *)b.c_fine_len.as<int>(), STMPC_QP_NMAX, b.speed.as<double>(),
+                               b.fine.as<double>(), b.fine_len.as<int>());
+        }
+    } else {
+        b.control_solves += N;
+        TRY(st_control_device(c, p, b.tick, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start, b.path.as<int32_t>(), b.bt.as<int32_t>(),
+                              b.cost.as<double>(), b.speed.as<double>(), b.fine.as<double>(), b.fine_len.as<int32_t>(), stream, nullptr));
+    }
+    // 3. the decision
+    hipLaunchKernelGGL(k_cc_decide_groups, ggrid, dim3(64), 0, st_, groups, npg, b.Rmax + 1, d_ego5_start, d_first_action, d_last_choice_rl, st,
+                       (const int *)b.pcrash.as<int>(), (const double *)b.speed.as<double>(), (const double *)b.fine.as<double>(), (const int *)b.fine_len.as<int>(),
+                       STMPC_QP_NMAX, d_takeover, d_reason, d_speed, c->sticky.as<unsigned>() + 1);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }

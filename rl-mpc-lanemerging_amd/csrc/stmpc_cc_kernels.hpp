@@ -46,17 +46,25 @@ struct CCState {              // per-context bookkeeping of one rollout (device 
     double *test_ego4, *test_ox, *test_ov;      // [N][4], [N][Kmax], [N][Kmax]
 };
 
-// One rollout step, dqn.py:129-141.  step is 1-based; step 1 also resets the bookkeeping.
+// `s` moved on by `off` rows: rows [off, ...) of every array (a controller group's slice, stmpc_cc_groups_kernels.hpp); rs = row stride of rollout_s
+__device__ __forceinline__ CCState cc_state_slice(const CCState &s, size_t off, int rs, int Kmax) {
+    return CCState{s.live + off, s.hist_len + off, s.crash_pred + off, s.have_test + off, s.sel_speed + off, s.rollout_s + off * rs,
+                   s.test_ego4 + off * 4, s.test_ox + off * Kmax, s.test_ov + off * Kmax};
+}
+
+// One rollout step, dqn.py:129-141, for the N rows the arrays point at: k_rollout_step's body (the grouped entry of stmpc_cc_groups_kernels.hpp
+// runs it on a group's slice and cfg).  step is 1-based; step 1 also resets the bookkeeping.  rs: row stride of rollout_s (rollout_length + 1 for a
+// lone batch, the largest group's for a grouped one; the history's bound stays this cfg's own).  A step past the cfg's rollout_length touches nothing.
 template <int KMAX>
-__global__ void __launch_bounds__(64) k_rollout_step(DevP p, CCfg c, int N, int Kmax, int step, const double *__restrict__ ego5_start,
-                                                     double *ego4, const int *__restrict__ k_count, double *ox, double *ov, double *oa,
-                                                     const double *__restrict__ action, CCState st) {
+__device__ __forceinline__ void rollout_step_body(const DevP &p, const CCfg &c, int N, int Kmax, int step, int rs, const double *__restrict__ ego5_start,
+                                                  double *ego4, const int *__restrict__ k_count, double *ox, double *ov, double *oa,
+                                                  const double *__restrict__ action, const CCState &st) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
+    if (e >= N || step > c.rollout_length) return;
     const int R1 = c.rollout_length + 1;
     if (step == 1) {
         st.live[e] = 1; st.hist_len[e] = 1; st.crash_pred[e] = 0; st.have_test[e] = 0; st.sel_speed[e] = 0.0;
-        st.rollout_s[(size_t)e * R1] = ego5_start[(size_t)e * 5 + 4];          // control.get_ego_s(start_state.ego_position), dqn.py:121
+        st.rollout_s[(size_t)e * rs] = ego5_start[(size_t)e * 5 + 4];          // control.get_ego_s(start_state.ego_position), dqn.py:121
     }
     if (!st.live[e]) return;
     DState<KMAX> s;
@@ -90,8 +98,14 @@ __global__ void __launch_bounds__(64) k_rollout_step(DevP p, CCfg c, int N, int 
         st.have_test[e] = 1;
     }
     const int hl = st.hist_len[e];
-    if (hl < R1) { st.rollout_s[(size_t)e * R1 + hl] = dev_ego_s(s.ex, s.ey); st.hist_len[e] = hl + 1; }     // dqn.py:139
+    if (hl < R1) { st.rollout_s[(size_t)e * rs + hl] = dev_ego_s(s.ex, s.ey); st.hist_len[e] = hl + 1; }     // dqn.py:139
     st.live[e] = (!cr && !(s.ex > c.stop_x)) ? 1 : 0;                          // loop condition + dqn.py:140-141
+}
+template <int KMAX>
+__global__ void __launch_bounds__(64) k_rollout_step(DevP p, CCfg c, int N, int Kmax, int step, const double *__restrict__ ego5_start,
+                                                     double *ego4, const int *__restrict__ k_count, double *ox, double *ov, double *oa,
+                                                     const double *__restrict__ action, CCState st) {
+    rollout_step_body<KMAX>(p, c, N, Kmax, step, c.rollout_length + 1, ego5_start, ego4, k_count, ox, ov, oa, action, st);
 }
 
 // Probe state of the episodes whose rollout ended before step ST_TEST_ROLLOUTS (dqn.py:142-143), as the 5-column state
@@ -116,13 +130,13 @@ __global__ void __launch_bounds__(64) k_cc_probe_state(int N, int Kmax /* row st
 
 // The decision, dqn.py:144-200.  probe_crash = st.test_guaranteed_crash_from_state(test_state); st_speed / fine / fine_len =
 // st.do_st_control's command and (trimmed, re-sampled) path for the START state.
-__global__ void __launch_bounds__(64) k_cc_decide(CCfg c, int N, const double *__restrict__ ego5_start, const double *__restrict__ first_action,
-                                                  const int *__restrict__ last_choice_rl, CCState st, const int *__restrict__ probe_crash,
-                                                  const double *__restrict__ st_speed, const double *__restrict__ fine, const int *__restrict__ fine_len,
-                                                  int fine_stride, int *takeover, int *reason_out, double *speed_out, unsigned *err) {
+// k_cc_decide's body for the N rows the arrays point at; rs: row stride of rollout_s.
+__device__ __forceinline__ void cc_decide_body(const CCfg &c, int N, int rs, const double *__restrict__ ego5_start, const double *__restrict__ first_action,
+                                               const int *__restrict__ last_choice_rl, const CCState &st, const int *__restrict__ probe_crash,
+                                               const double *__restrict__ st_speed, const double *__restrict__ fine, const int *__restrict__ fine_len,
+                                               int fine_stride, int *takeover, int *reason_out, double *speed_out, unsigned *err) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
-    const int R1 = c.rollout_length + 1;
     const double v0 = ego5_start[(size_t)e * 5 + 2], a0 = ego5_start[(size_t)e * 5 + 3];
     int reason = CC_RL;
     double speed = dev_speed_from_jerk(c, v0, a0, first_action[e]);            // control.set_ego_jerk(first_action), control.py:174-178
@@ -135,7 +149,7 @@ __global__ void __launch_bounds__(64) k_cc_decide(CCfg c, int N, const double *_
         else if (m > 1) {                                                      // dqn.py:167-169: a single point = nothing to compare
             const int hl = st.hist_len[e];
             const int ml = m < hl ? m : hl;
-            const double *fs = fine + (size_t)e * fine_stride, *hs = st.rollout_s + (size_t)e * R1;
+            const double *fs = fine + (size_t)e * fine_stride, *hs = st.rollout_s + (size_t)e * rs;
             const double st_jerk = dev_mean_abs_jerk(fs, ml, v0, a0, c.tick), rl_jerk = dev_mean_abs_jerk(hs, ml, v0, a0, c.tick);
             const double st_dist = fs[ml - 1] - fs[0], rl_dist = hs[ml - 1] - hs[0];
             const bool last_rl = last_choice_rl ? last_choice_rl[e] != 0 : true;
@@ -152,6 +166,13 @@ __global__ void __launch_bounds__(64) k_cc_decide(CCfg c, int N, const double *_
     takeover[e] = reason != CC_RL;
     reason_out[e] = reason;
     speed_out[e] = speed;
+}
+__global__ void __launch_bounds__(64) k_cc_decide(CCfg c, int N, const double *__restrict__ ego5_start, const double *__restrict__ first_action,
+                                                  const int *__restrict__ last_choice_rl, CCState st, const int *__restrict__ probe_crash,
+                                                  const double *__restrict__ st_speed, const double *__restrict__ fine, const int *__restrict__ fine_len,
+                                                  int fine_stride, int *takeover, int *reason_out, double *speed_out, unsigned *err) {
+    cc_decide_body(c, N, c.rollout_length + 1, ego5_start, first_action, last_choice_rl, st, probe_crash, st_speed, fine, fine_len, fine_stride, takeover, reason_out,
+                   speed_out, err);
 }
 
 // The policy's input vector for N states: dqn.get_state_vector_from_base_state (dqn.py:389-446), then what the reference's RL library does
@@ -209,7 +230,13 @@ __global__ void __launch_bounds__(64) k_policy_features(FeatCfg f, int N, int Km
 
 // Ordered list of the states whose decision needs st.do_st_control(start_state) (dqn.py:144-155; every branch but the
 // strictly-better comparison, which needs the controller's path for every state).  One workgroup, block-wide ordered compaction.
-__global__ void __launch_bounds__(1024) k_cc_select(CCfg c, int N, CCState st, const int *__restrict__ probe_crash, int *sel_idx, int *sel_count) {
+// does row e's decision call the controller?  (the first three branches of cc_decide_body)
+__device__ __forceinline__ bool cc_needs_control(const CCfg &c, const CCState &st, const int *__restrict__ probe_crash, int e) {
+    return (c.check_rollout_crash && st.crash_pred[e]) || (c.limit_speed && st.sel_speed[e] > c.desired_speed) || (c.test_rollout_state && probe_crash[e]);
+}
+// k_cc_select's body; cfg_of(e): the cfg of row e
+template <class CfgOf>
+__device__ __forceinline__ void cc_select_body(CfgOf cfg_of, int N, const CCState &st, const int *__restrict__ probe_crash, int *sel_idx, int *sel_count) {
     __shared__ int wsum[16];
     __shared__ int base;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -218,7 +245,7 @@ __global__ void __launch_bounds__(1024) k_cc_select(CCfg c, int N, CCState st, c
     for (int start = 0; start < N; start += 1024) {
         const int e = start + tid;
         bool need = false;
-        if (e < N) need = (c.check_rollout_crash && st.crash_pred[e]) || (c.limit_speed && st.sel_speed[e] > c.desired_speed) || (c.test_rollout_state && probe_crash[e]);
+        if (e < N) need = cc_needs_control(cfg_of(e), st, probe_crash, e);
         const unsigned long long b = __ballot(need);
         if (lane == 0) wsum[w] = __popcll(b);
         __syncthreads();
@@ -230,6 +257,9 @@ __global__ void __launch_bounds__(1024) k_cc_select(CCfg c, int N, CCState st, c
         __syncthreads();
     }
     if (tid == 0) *sel_count = base;
+}
+__global__ void __launch_bounds__(1024) k_cc_select(CCfg c, int N, CCState st, const int *__restrict__ probe_crash, int *sel_idx, int *sel_count) {
+    cc_select_body([&](int) -> const CCfg & { return c; }, N, st, probe_crash, sel_idx, sel_count);
 }
 __global__ void __launch_bounds__(64) k_cc_gather(int M, int Kmax, int Kcopy, const int *__restrict__ sel_idx, const double *__restrict__ ego5, const int *__restrict__ k_count,
                                                   const double *__restrict__ ox, const double *__restrict__ ov, double *c_ego5, int *c_k, double *c_ox, double *c_ov) {

@@ -116,6 +116,24 @@ def _check_traffic(n, traffic, policy):
     return G, npg
 
 
+def _check_control(n, control, traffic, policy):
+    """(C, n_per_cell) for ``n`` environments in the controller groups of ``control``; ValueError when they do not split or do not coincide with
+    the traffic groups or the members of a population ``policy`` (cell c pairs member c, traffic c and control c).  Touches no device."""
+    from . import combined
+    C = len(control)
+    if C < 1 or C > combined.CONTROL_GROUPS_MAX:
+        raise ValueError("control must name 1 ... %d groups, not %d" % (combined.CONTROL_GROUPS_MAX, C))
+    if int(n) < C or int(n) % C:
+        raise ValueError("n = %d environments do not split into %d controller groups of equal size" % (n, C))
+    npc = int(n) // C
+    if traffic is not None and len(traffic) != C:
+        raise ValueError("the traffic has %d groups, the control %d: cell c pairs traffic c with control c, so they must coincide" % (len(traffic), C))
+    if hasattr(policy, "P") and (policy.P != C or policy.n_per_member != npc):
+        raise ValueError("the population has %d members of %d environments, the control %d groups of %d: cell c pairs member c with control c, so they must coincide"
+                         % (policy.P, policy.n_per_member, C, npc))
+    return C, npc
+
+
 class EpisodeRunner:
     """N merge episodes stepped in lock-step on the device, one ``tick()`` at a time (``run_episodes`` drives it to the end;
     ``bench.py --workload episodes`` times its ticks).
@@ -133,9 +151,16 @@ class EpisodeRunner:
     ``traffic``: None (one world from the global ``Settings``) or a list as ``sim_cfgs`` takes: the world then has ``G = len(traffic)`` traffic
     groups of ``n / G`` consecutive environments (``stmpc_sim_init_groups_device``), group g bit-identical to a lone runner of ``n / G``
     environments with that traffic and group g's seed, and ``result()`` gains ``out["traffic_group"]``.  With a population policy too, its P
-    must be G and its ``n_per_member`` the group size: cell c pairs member c with traffic c (``cross_matrix`` builds a models x traffic grid)."""
+    must be G and its ``n_per_member`` the group size: cell c pairs member c with traffic c (``cross_matrix`` builds a models x traffic grid).
 
-    def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, record=None, traffic=None):
+    ``control`` (combined controller only): None (one ``CombinedCfg`` from the global ``Settings``) or a list of dicts as ``combined.control_cfgs``
+    takes: the environments are then ``C = len(control)`` controller groups of ``n / C`` consecutive environments, group c decided under its own
+    settings (``stmpc_combined_groups_set``) and bit-identical to a lone runner of ``n / C`` environments with ``control=[control[c]]``, and
+    ``result()`` gains ``out["control_group"]``.  With ``traffic`` and / or a population policy too, cell c pairs member c, traffic c and
+    control c: the counts and slice sizes must coincide.  Give the traffic groups one ``seed`` for common random numbers across the cells
+    (``grid_search_combined``)."""
+
+    def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, record=None, traffic=None, control=None):
         import torch
         self.torch = torch
         if controller not in ("st", "combined"):
@@ -144,6 +169,10 @@ class EpisodeRunner:
         if hasattr(policy, "P") and int(n) != policy.n:
             raise ValueError("n = %d, the population of policies was built for %d x %d = %d environments" % (n, policy.P, policy.n_per_member, policy.n))
         self.traffic = list(traffic) if traffic is not None else None
+        self.control = list(control) if control is not None else None
+        if self.control is not None and controller != "combined":
+            raise ValueError("control groups are settings of the combined controller, not of %r" % (controller,))
+        self.C, self.n_per_cell = _check_control(n, self.control, self.traffic, policy) if self.control is not None else (0, 0)
         self.G, self.n_per_group = _check_traffic(n, self.traffic, policy) if self.traffic is not None else (0, 0)
         self.n, self.kmax, self.controller, self.policy = int(n), int(kmax), controller, policy
         self.cfgs = sim_cfgs(self.traffic, seed, max_episode_length) if self.traffic is not None else None
@@ -159,6 +188,9 @@ class EpisodeRunner:
         self.d_path, self.d_bt, self.d_cost, self.d_speed = z(n, H, dtype=torch.int32), z(n, dtype=torch.int32), z(n), z(n)
         self.d_fine, self.d_fine_len = z(n, _capi.QP_NMAX), z(n, dtype=torch.int32)
         self.ccfg = _capi.CombinedCfg.from_settings(Settings, sparse_control=True) if controller == "combined" else None      # (a tick ends with a host-side status check anyway)
+        if self.control is not None:
+            from . import combined
+            self.ccfg = combined.ControlGroups(combined.control_cfgs(self.control, sparse_control=True), self.n_per_cell)
         self.takeovers, self.controlled = z(n), z(n)
         self.last_rl = torch.ones(n, dtype=torch.int32, device=dev)
         self.d_status = z(n, dtype=torch.int32)
@@ -221,6 +253,8 @@ class EpisodeRunner:
             out["member"] = np.arange(self.n) // self.policy.n_per_member
         if self.cfgs is not None:
             out["traffic_group"] = np.arange(self.n) // self.n_per_group
+        if self.control is not None:
+            out["control_group"] = np.arange(self.n) // self.n_per_cell
         if self.recorder is not None:
             from . import report
             out["report"] = report.Report.from_result(out, self.recorder.read())
@@ -247,7 +281,8 @@ def stats_columns(status, ticks, acc, tick_length):
     return out
 
 
-def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, check_every=16, max_ticks=None, record=None, traffic=None):
+def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, check_every=16, max_ticks=None, record=None, traffic=None,
+                 control=None):
     """Run ``n`` merge episodes to the end (or for ``max_ticks`` ticks); returns the per-episode columns of the reference's stats report
     (``crashed``, ``merged``, ``mean_speed``, ``max_speed``, ``mean_abs_jerk``, ``closest_distance``, ``mean_closest_distance``,
     ``time_taken``, ``time_to_merge`` (NaN unless merged)) plus ``ticks``, ``status`` (0 still running), ``ego4`` and ``percent_st``
@@ -255,8 +290,9 @@ def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max
 
     controller: "st" = ``st.do_st_control`` every tick (TASK "ST"); "combined" = ``do_combined_control`` with ``policy``
     (see ``combined.decide_batch_device``).  record: None, or a ``report.RecorderConfig`` -- the result then holds ``report`` (``report.Report``),
-    see ``EpisodeRunner``.  traffic: None, or the traffic groups of ``EpisodeRunner``; the tick limit is then the largest group's ``max_ticks + 1``."""
-    r = EpisodeRunner(n, seed, controller, policy, ctx, kmax, max_episode_length, record, traffic)
+    see ``EpisodeRunner``.  traffic: None, or the traffic groups of ``EpisodeRunner``; the tick limit is then the largest group's ``max_ticks + 1``.
+    control: None, or the controller groups of ``EpisodeRunner``."""
+    r = EpisodeRunner(n, seed, controller, policy, ctx, kmax, max_episode_length, record, traffic, control)
     limit = r.max_ticks + 1 if max_ticks is None else min(int(max_ticks), r.max_ticks + 1)
     for tick in range(limit):
         r.tick()
@@ -267,7 +303,7 @@ def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max
 
 def summary(stats):
     """Column means as the reference's report rows hold them (stats.py:145-158)."""
-    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4", "report", "member", "traffic_group")}
+    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4", "report", "member", "traffic_group", "control_group")}
 
 
 def summary_by_member(stats, P):
@@ -288,6 +324,45 @@ def summary_by_group(stats, G):
         raise ValueError("%d environments do not split into %d traffic groups" % (n, G))
     npg = n // G
     return [summary({k: v[g * npg:(g + 1) * npg] for k, v in stats.items() if k != "report"}) for g in range(G)]
+
+
+def summary_by_control(stats, C):
+    """``summary`` of each controller group's environments: C dicts, group c from rows [c * n / C, (c + 1) * n / C) of every column (the result of a
+    run with ``control``)."""
+    n = len(stats["status"])
+    if C < 1 or n % C:
+        raise ValueError("%d environments do not split into %d controller groups" % (n, C))
+    npc = n // C
+    return [summary({k: v[c * npc:(c + 1) * npc] for k, v in stats.items() if k != "report"}) for c in range(C)]
+
+
+def grid_search_combined(model, traffic, n_per_cell, cells=None, seed=0, common_random_numbers=True, ctx=None, kmax=16, max_episode_length=100.0, record=None,
+                         max_ticks=None, check_every=16):
+    """The reference's ``main.do_grid_search_combined`` (main.py:62-81: one ``EVALUATE_COMBINED_DDPG`` process per cell) in ONE run: ``model`` (as
+    ``actor.ActorPopulation`` takes a member) under the combined controller on the traffic type ``traffic`` (as ``sim_cfgs`` takes one group), once
+    per cell of ``cells`` (default ``combined.grid_search_cells()``; dicts as ``combined.control_cfgs`` takes them), ``n_per_cell`` episodes each.
+    ``common_random_numbers``: every cell's traffic group gets the same seed (``seed``), so all cells face the same traffic draws and start
+    speeds and differ by the controller alone -- something one process per cell cannot give; False: cell c's seed is
+    ``vec_env.episode_seed(seed, c)``.
+    Returns ``{"cells": [{"settings": cell, "summary": ``summary`` dict}, ...], "stats": the raw result}``."""
+    from . import actor, combined
+    cells = [dict(c) for c in (cells if cells is not None else combined.grid_search_cells())]
+    C = len(cells)
+    if C < 1 or C > combined.CONTROL_GROUPS_MAX:
+        raise ValueError("control must name 1 ... %d groups, not %d" % (combined.CONTROL_GROUPS_MAX, C))
+    if int(n_per_cell) < 1:
+        raise ValueError("n_per_cell must be positive")
+    combined.control_cfgs(cells)                                        # (validates the keys before anything is built)
+    t = traffic_settings(traffic)
+    if common_random_numbers:
+        t["seed"] = int(seed)
+    ctx = ctx if ctx is not None else _capi.default_context()
+    one = actor.DDPGActor(os.fspath(model), 1, ctx, Settings) if isinstance(model, (str, os.PathLike)) else model
+    pop = actor.ActorPopulation([one] * C, int(n_per_cell), ctx, Settings)
+    stats = run_episodes(pop.n, seed=seed, controller="combined", policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, check_every=check_every,
+                         max_ticks=max_ticks, record=record, traffic=[dict(t) for _ in range(C)], control=cells)
+    by = summary_by_control(stats, C)
+    return {"cells": [{"settings": cells[c], "summary": by[c]} for c in range(C)], "stats": stats}
 
 
 def cross_matrix(models, traffic, n_per_cell, seed=0, ctx=None, kmax=16, max_episode_length=100.0, record=None, max_ticks=None, check_every=16):

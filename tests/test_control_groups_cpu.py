@@ -1,0 +1,144 @@
+"""Controller groups, host side (combined.control_cfgs / ControlGroups / grid_search_cells, the ``control`` argument of episodes.EpisodeRunner and
+episodes.grid_search_combined, the stmpc_combined_groups_* / stmpc_*_groups_device entries of include/stmpc.h).  No GPU: the cells of the grid search
+against the fixture recorded from the reference's own loop, ``control_cfgs`` leaves the global Settings alone, header / library / binding agree, and
+every shape mismatch is a ValueError raised before a context is made or asked for anything.
+"""
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, REPO
+
+ENTRIES = {"stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device"}
+
+
+def _pkg():
+    import rl_mpc_lanemerging_amd as pkg
+    if pkg.build.needs_build():
+        pkg.build.build()
+    return pkg
+
+
+class _NoDevice:
+    """A context that must not be asked for anything."""
+
+    def __getattr__(self, name):
+        raise AssertionError("the device was touched (%s)" % name)
+
+
+def test_grid_search_cells_are_the_reference_loop():
+    _pkg()
+    from rl_mpc_lanemerging_amd import combined
+    want = json.load(open(os.path.join(GOLDEN, "combined_grid.json")))
+    assert want["keys"] == ["ROLLOUT_LENGTH", "ST_TEST_ROLLOUTS", "TEST_ROLLOUT_STATE"]
+    cells = combined.grid_search_cells()
+    assert cells == want["cells"] and len(cells) == 13
+    assert all(type(c["TEST_ROLLOUT_STATE"]) is bool and type(c["ROLLOUT_LENGTH"]) is int for c in cells)
+    # the three skip rules of main.py:75-80, on the fixture itself
+    for c in want["cells"]:
+        assert c["ST_TEST_ROLLOUTS"] <= c["ROLLOUT_LENGTH"] and (c["TEST_ROLLOUT_STATE"] or c["ST_TEST_ROLLOUTS"] == 2)
+    assert len({tuple(sorted(c.items())) for c in cells}) == 13 and len(cells) <= combined.CONTROL_GROUPS_MAX
+
+
+def test_header_library_and_binding_agree_on_the_control_group_entries():
+    _pkg()
+    from rl_mpc_lanemerging_amd import _capi as capi
+    lib = capi.load()
+    header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
+    declared = {name: args for name, args in re.findall(r"\bint (stmpc_(?:combined|rollout)_[a-z_0-9]*groups[a-z_0-9]*)\s*\(([^)]*)\)\s*;", header)}
+    assert set(declared) == ENTRIES and ENTRIES <= set(capi.EXPORTS)
+    for name, args in declared.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(args.split(",")), name
+    assert capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8 and "#define STMPC_ABI_VERSION 8" in header
+    for method in ("combined_groups_set", "combined_groups_clear", "rollout_step_groups_device", "combined_decide_groups_device"):
+        assert callable(getattr(capi.Context, method))
+
+
+def test_control_cfgs_leaves_settings_alone_and_rejects_unknown_keys(restore_settings):
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import _capi as capi, combined
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    pkg.Settings.ROLLOUT_LENGTH, pkg.Settings.ST_TEST_ROLLOUTS, pkg.Settings.TEST_ROLLOUT_STATE, pkg.Settings.CHECK_ROLLOUT_CRASH = 5, 5, True, True
+    before = pkg.Settings.snapshot()
+    control = [{"ROLLOUT_LENGTH": 3, "ST_TEST_ROLLOUTS": 2}, {"TEST_ROLLOUT_STATE": False, "LIMIT_DQN_SPEED": True}, {},
+               {"TEST_ST_STRICTLY_BETTER": True, "REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED": True, "CHECK_ROLLOUT_CRASH": False}]
+    cfgs = combined.control_cfgs(control, sparse_control=True)
+    assert pkg.Settings.snapshot() == before
+    plain = capi.CombinedCfg.from_settings(pkg.Settings, sparse_control=True)
+    fields = [n for n, _ in capi.CombinedCfg._fields_]
+    as_dict = lambda c: {n: getattr(c, n) for n in fields}
+    assert as_dict(cfgs[2]) == as_dict(plain)                                       # an empty group is the global Settings' cfg, field for field
+    assert as_dict(cfgs[0]) == dict(as_dict(plain), rollout_length=3, st_test_rollouts=2)
+    assert as_dict(cfgs[1]) == dict(as_dict(plain), test_rollout_state=0, limit_dqn_speed=1)
+    assert as_dict(cfgs[3]) == dict(as_dict(plain), test_st_strictly_better=1, remember_last_choice=1, check_rollout_crash=0)
+    assert all(c.sparse_control == 1 for c in cfgs) and combined.control_cfgs([{}])[0].sparse_control == 0
+    # the global Settings still decide everything a group does not set
+    pkg.Settings.STOP_X = 40
+    assert combined.control_cfgs([{"ROLLOUT_LENGTH": 3}])[0].stop_x == 40.0
+    with pytest.raises(ValueError, match="not TICK_LENGTH"):
+        combined.control_cfgs([{"ROLLOUT_LENGTH": 3, "TICK_LENGTH": 0.1}])
+    with pytest.raises(ValueError, match="not STOP_X, V_WEIGHT"):
+        combined.control_cfgs([{}, {"STOP_X": 1, "V_WEIGHT": 2}])
+    with pytest.raises(ValueError, match="at least one"):
+        combined.control_cfgs([])
+    with pytest.raises(ValueError, match="not a dict"):
+        combined.control_cfgs(["default"])
+    groups = combined.ControlGroups(cfgs, 24)
+    assert (groups.C, groups.n_per_group, groups.n, groups.rollout_length) == (4, 24, 96, 5)
+    assert combined.ControlGroups(combined.control_cfgs(combined.grid_search_cells()), 7).rollout_length == 20
+    with pytest.raises(ValueError, match="1 ... 64 groups, not 65"):
+        combined.ControlGroups(cfgs[:1] * 65, 24)
+    with pytest.raises(ValueError, match="1 ... 64 groups, not 0"):
+        combined.ControlGroups([], 24)
+    with pytest.raises(ValueError, match="n_per_group must be positive"):
+        combined.ControlGroups(cfgs, 0)
+
+
+def test_mismatched_shapes_are_refused_before_any_context(restore_settings):
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import episodes
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    three = [{"ROLLOUT_LENGTH": 3}, {"ROLLOUT_LENGTH": 5}, {"TEST_ROLLOUT_STATE": False}]
+
+    class Pop:                                                     # what EpisodeRunner reads of an actor.ActorPopulation
+        def __init__(self, P, npm):
+            self.P, self.n_per_member, self.n = P, npm, P * npm
+    nodev = _NoDevice()
+    # n does not split into the cells
+    with pytest.raises(ValueError, match="70 environments do not split into 3 controller groups"):
+        episodes.EpisodeRunner(70, controller="combined", ctx=nodev, control=three)
+    with pytest.raises(ValueError, match="do not split into 3 controller groups"):
+        episodes.run_episodes(2, controller="combined", ctx=nodev, control=three)
+    # C, G and P do not coincide
+    with pytest.raises(ValueError, match="the traffic has 2 groups, the control 3"):
+        episodes.EpisodeRunner(72, controller="combined", ctx=nodev, traffic=["low", "fast"], control=three)
+    with pytest.raises(ValueError, match="2 members of 36 environments, the control 3 groups of 24"):
+        episodes.EpisodeRunner(72, controller="combined", policy=Pop(2, 36), ctx=nodev, control=three)
+    with pytest.raises(ValueError, match="2 members of 36 environments, the .* 3 groups of 24: .* must coincide"):
+        episodes.EpisodeRunner(72, controller="combined", policy=Pop(2, 36), ctx=nodev, traffic=["low", "default", "fast"], control=three)
+    # C outside 1 ... 64
+    with pytest.raises(ValueError, match="1 ... 64 groups, not 65"):
+        episodes.EpisodeRunner(130, controller="combined", ctx=nodev, control=[{}] * 65)
+    with pytest.raises(ValueError, match="1 ... 64 groups, not 0"):
+        episodes.EpisodeRunner(24, controller="combined", ctx=nodev, control=[])
+    with pytest.raises(ValueError, match="1 ... 64 groups, not 65"):
+        episodes.grid_search_combined("medium1", "medium", 4, cells=[{}] * 65, ctx=nodev)
+    # settings of the combined controller only, and only its own
+    with pytest.raises(ValueError, match="not of 'st'"):
+        episodes.EpisodeRunner(72, controller="st", ctx=nodev, control=three)
+    with pytest.raises(ValueError, match="not V_WEIGHT"):
+        episodes.grid_search_combined("medium1", "medium", 4, cells=[{"V_WEIGHT": 1.0}], ctx=nodev)
+    with pytest.raises(ValueError, match="unknown traffic type"):
+        episodes.grid_search_combined("medium1", "rush", 4, ctx=nodev)
+    with pytest.raises(ValueError, match="n_per_cell must be positive"):
+        episodes.grid_search_combined("medium1", "medium", 0, ctx=nodev)
+    # summaries split by controller group
+    stats = {"status": np.array([1, 1, 2, 2, 1, 2]), "ticks": np.arange(6), "merged": np.array([1.0, 1, 0, 0, 1, 0]), "control_group": np.arange(6) // 2}
+    by = episodes.summary_by_control(stats, 3)
+    assert [b["merged"] for b in by] == [1.0, 0.0, 0.5] and "control_group" not in by[0]
+    with pytest.raises(ValueError, match="do not split into 4 controller groups"):
+        episodes.summary_by_control(stats, 4)
