@@ -16,6 +16,8 @@
  *   stmpc_st_control_batch[_device] <- st.do_st_control              st.py:757-783 applied to N independent states
  *   stmpc_rollout_step_device / stmpc_combined_decide_device <- dqn.RLAgent.do_combined_control  dqn.py:117-200 (the policy
  *                                network stays the caller's; everything around it runs here)
+ *   stmpc_first_step[_device] <- st.do_conditional_st_based_on_first_step  st.py:805-814 (one predictor step, the feasibility probe, the controller on takeover)
+ *   stmpc_speed_from_jerk_device <- control.get_ego_speed_from_jerk   control.py:160-171
  *   stmpc_policy_features_device <- dqn.get_state_vector_from_base_state  dqn.py:389-446 (+ the float32 cast and TimeFeature input of ddpg.py:41,84)
  *   stmpc_actor_eval_device   <- DDPGAgent.get_control                ddpg.py:83-87 (state vector + the pretrained policy network, one launch)
  *   stmpc_actor_view_ddpg     <- the closing `evaluate` of ddpg.train_ddpg_all_with_lr_drop (the model just trained, evaluated where it lies)
@@ -40,7 +42,7 @@
  * wide-lattice solve with a set of dynamics / cost parameters builds a small table on the host (a few ms; its upload is queued on the call's
  * stream, so that call cannot be captured in a hipGraph) -- the context keeps the tables of the four most recent parameter sets, so alternating
  * sets neither rebuild nor wait, and only a fifth set waits for the device (hipDeviceSynchronize) before it replaces the least recently used;
- * and stmpc_combined_decide_device with sparse_control (one integer comes back to the host, see stmpc_combined_cfg).
+ * and stmpc_combined_decide_device / stmpc_first_step_device with sparse_control (one integer comes back to the host, see stmpc_combined_cfg).
  * Environment knobs (STMPC_*) are read once, in stmpc_create.
  * Scratch: back-pointers (one byte per lattice cell of a window and time layer -- the distance to the predecessor -- when no step of the dynamics
  * exceeds 255 cells, else two) live per RESIDENT workgroup (84 MB for the first window's 1024 workgroups at H = 40).  Only a search that overflows
@@ -792,6 +794,51 @@ int  stmpc_rec_tick_device(stmpc_rec *rec, int N, int Kmax, const double *d_ego5
                            const double *d_oa, const double *d_cmd_speed, const int32_t *d_takeover, void *stream);
 int  stmpc_rec_reduce_device(stmpc_rec *rec, double *d_out, void *stream);
 int  stmpc_rec_read(stmpc_rec *rec, double *ring, int32_t *length, double *acc_env, double *acc_reduced, int32_t *status);
+
+/*
+ * First-step shield controller, st.do_conditional_st_based_on_first_step(state, start_speed) (st.py:805-814), for N independent states: the
+ * reference's cheaper way to put the solver behind a proposed command -- ONE predictor step and at most two solves per tick, where the combined
+ * controller rolls out ROLLOUT_LENGTH policy evaluations.  (Additive: new entries only, no signature or struct of ABI 8 changes, so
+ * STMPC_ABI_VERSION stays 8.)  It is not a stmpc_combined_cfg: the step predicts with predict_step_with_ego's DEFAULT min_crash_distance
+ * (prediction.py:46) while the probe keeps COMBINATION_MIN_DISTANCE - CAR_LENGTH (st.py:800; p->comb_min_dist feeds both in the combined controller),
+ * nothing stops at STOP_X, and the proposal is a speed, not a jerk.
+ *   stmpc_first_step_device    <- st.py:805-814.  DEVICE pointers, states as stmpc_solve_batch_device takes them (ego5 [N][5], k [N], other_x / other_v
+ *                       [N][Kmax]) plus start_speed [N].  Per state: next_state, crashed = predict_step_with_ego(start_speed, tick_length,
+ *                       min_crash_distance) (st.py:806; laid out as the solver's state, start_s of the predicted position from the device map of
+ *                       control.get_ego_s), crash_guaranteed = st.test_guaranteed_crash_from_state(next_state) (st.py:807: one batched solve over all
+ *                       states -- the reference too asks before it looks at `crashed`), then cmd_speed = st.do_st_control(state) where crashed or
+ *                       crash_guaranteed (st.py:808-811), else start_speed itself, bit for bit (st.py:813-814).  Outputs: cmd_speed [N], takeover [N]
+ *                       (0 / 1), reason [N]: 0 the proposed speed, 1 the step crashed, 2 a crash is guaranteed afterwards (both: 1, the order of the
+ *                       reference's `or`).  d_other_a may be NULL and is not read: the predictor takes no accelerations (prediction.py:75-97); the
+ *                       argument completes the planner's view (stmpc_sim_view_device) for the caller's convenience.  Asynchronous on `stream` unless
+ *                       sparse_control.  A controller path that cannot be re-sampled latches STMPC_EINVAL for stmpc_check_error only where that command
+ *                       is used, as in stmpc_combined_decide_device.
+ *   stmpc_first_step           the same for HOST pointers: stages, runs, copies back, synchronous (like stmpc_st_control_batch; a latched error is this
+ *                       call's).  Optional outputs (any may be NULL) are the intermediate results: crashed [N], crash_guaranteed [N] (the probe's
+ *                       verdict for EVERY state, crashed ones included), and the predicted state next_ego [N][5], next_other_x / next_other_v [N][Kmax].
+ *   stmpc_first_step_counts    totals of stmpc_first_step_device on this context since the last reset: states decided, states taken over (counted on the
+ *                       device by the deciding kernel; reading them synchronises), controller solves run (= takeovers with sparse_control, else =
+ *                       decisions).  The combined controller's stmpc_combined_counts are not touched.
+ *   stmpc_speed_from_jerk_device   <- control.get_ego_speed_from_jerk (control.py:160-171) for N states: the acceleration ego5[.][3] + jerk * tick_length
+ *                       clamped to [p->a_min, p->a_max], the speed ego5[.][2] + that * tick_length clamped to [0, p->v_max] -- the function the combined
+ *                       rollout applies inside its step kernel, on its own, so that a policy's jerk becomes this controller's proposal.  DEVICE
+ *                       pointers, asynchronous.
+ */
+typedef struct stmpc_first_step_cfg {
+    double tick_length;        /* Settings.TICK_LENGTH */
+    double min_crash_distance; /* predict_step_with_ego's default, 5 (prediction.py:46) */
+    int    sparse_control;     /* as stmpc_combined_cfg: 1 = solve st.do_st_control only for the taken-over states (ONE host round trip for their number; not
+                                  capturable in a hipGraph), 0 = for all states, fully asynchronous.  Same outputs either way. */
+} stmpc_first_step_cfg;
+int stmpc_first_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_first_step_cfg *cfg, int N, int Kmax, const double *d_ego5,
+                            const int32_t *d_k_count, const double *d_other_x, const double *d_other_v, const double *d_other_a /* may be NULL */,
+                            const double *d_start_speed, double *d_cmd_speed, int32_t *d_takeover, int32_t *d_reason, void *stream);
+int stmpc_first_step(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_first_step_cfg *cfg, int N, int Kmax, const double *ego, const int32_t *k_count,
+                     const double *other_x, const double *other_v, const double *start_speed, double *cmd_speed, int32_t *takeover, int32_t *reason,
+                     int32_t *crashed, int32_t *crash_guaranteed, double *next_ego, double *next_other_x, double *next_other_v);
+int stmpc_first_step_counts(stmpc_ctx *ctx, int64_t *decisions, int64_t *takeovers, int64_t *control_solves, int reset);
+int stmpc_speed_from_jerk_device(stmpc_ctx *ctx, const stmpc_params *p, double tick_length, int N, const double *d_ego5, const double *d_jerk,
+                                 double *d_speed, void *stream);
 
 /* Device arithmetic probe used by the parity tests: out[i] = a[i] op b[i] evaluated on the GPU
  * with the kernels' compile flags. op: 0 div, 1 sqrt(a), 2 mul, 3 add, 4 fma(a,a,b*b), 5 the five-operation

@@ -69,6 +69,20 @@ class CombinedCfg(C.Structure):
                    remember_last_choice=int(bool(getattr(S, "REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED", False))))
 
 
+class FirstStepCfg(C.Structure):
+    """``stmpc_first_step_cfg`` (include/stmpc.h): what st.do_conditional_st_based_on_first_step (st.py:805-814) reads besides the solver's settings."""
+    _fields_ = [("tick_length", C.c_double), ("min_crash_distance", C.c_double), ("sparse_control", C.c_int)]
+
+    #: the default of HighwayState.predict_step_with_ego's min_crash_distance (prediction.py:46): st.py:806 passes none
+    MIN_CRASH_DISTANCE = 5.0
+
+    @classmethod
+    def from_settings(cls, S, sparse_control=False):
+        """``sparse_control`` as ``CombinedCfg.from_settings`` takes it: False keeps ``stmpc_first_step_device`` asynchronous and solves the controller
+        for every state, True only for the taken-over ones at the price of one host round trip."""
+        return cls(tick_length=S.TICK_LENGTH, min_crash_distance=cls.MIN_CRASH_DISTANCE, sparse_control=int(bool(sparse_control)))
+
+
 class FeaturesCfg(C.Structure):
     """``stmpc_policy_features_cfg`` (include/stmpc.h): the flags of dqn.get_state_vector_from_base_state (+ the TimeFeature input of ddpg.py:41)."""
     _fields_ = [("max_speed", C.c_double), ("sensor_radius", C.c_double), ("time_scale", C.c_double), ("cars_ahead", C.c_int32), ("cars_behind", C.c_int32),
@@ -195,6 +209,7 @@ EXPORTS = (
     "stmpc_ddpg_pop_push_device", "stmpc_ddpg_pop_update_device", "stmpc_ddpg_pop_stats_device",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
+    "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
 ENV_CONTINUOUS_JERK, ENV_JERK, ENV_ACCELERATION = 0, 1, 2                                 # STMPC_ENV_*
@@ -349,6 +364,11 @@ def load():
     lib.stmpc_rec_tick_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 7 + [vp]
     lib.stmpc_rec_reduce_device.argtypes = [vp, vp, vp]
     lib.stmpc_rec_read.argtypes = [vp, dp, ip, dp, dp, ip]
+    fsp = C.POINTER(FirstStepCfg)
+    lib.stmpc_first_step_device.argtypes = [vp, pp, fsp, C.c_int, C.c_int] + [vp] * 9 + [vp]
+    lib.stmpc_first_step.argtypes = [vp, pp, fsp, C.c_int, C.c_int, dp, ip, dp, dp, dp, dp, ip, ip, ip, ip, dp, dp, dp]
+    lib.stmpc_first_step_counts.argtypes = [vp, i64p, i64p, i64p, C.c_int]
+    lib.stmpc_speed_from_jerk_device.argtypes = [vp, pp, C.c_double, C.c_int, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -691,6 +711,38 @@ class Context:
         a, b = C.c_int64(0), C.c_int64(0)
         self._chk(self._lib.stmpc_combined_counts(self._h, C.byref(a), C.byref(b), int(bool(reset))))
         return int(a.value), int(b.value)
+
+    # -- first-step shield controller (stmpc_first_step*; see include/stmpc.h) ------------------------------
+    def first_step_device(self, params, cfg, N, Kmax, d_ego5, d_k, d_ox, d_ov, d_oa, d_start_speed, d_cmd_speed, d_takeover, d_reason, stream=0):
+        self._chk(self._lib.stmpc_first_step_device(self._h, C.byref(params), C.byref(cfg), int(N), int(Kmax), d_ego5, d_k, d_ox, d_ov, d_oa or None,
+                                                    d_start_speed, d_cmd_speed, d_takeover, d_reason, stream or None))
+
+    def first_step(self, params, cfg, ego, k_count, other_x, other_v, start_speed, want_state=True):
+        """``stmpc_first_step`` on host arrays.  Returns a dict: ``cmd_speed``, ``takeover``, ``reason`` and, with ``want_state``, ``crashed``,
+        ``crash_guaranteed`` (the probe's verdict for every state) and the predicted state ``next_ego`` [N][5], ``next_other_x``, ``next_other_v``."""
+        ego, k_count, other_x, other_v, N, Kmax = _batch_states(ego, k_count, other_x, other_v)
+        start_speed = np.ascontiguousarray(start_speed, dtype=np.float64).reshape(-1)
+        if start_speed.size != N:
+            raise ValueError("start_speed has %d entries for %d states" % (start_speed.size, N))
+        out = {"cmd_speed": np.zeros(N), "takeover": np.zeros(N, np.int32), "reason": np.zeros(N, np.int32)}
+        ext = {"crashed": np.zeros(N, np.int32), "crash_guaranteed": np.zeros(N, np.int32), "next_ego": np.zeros((N, 5)), "next_other_x": np.zeros((N, Kmax)),
+               "next_other_v": np.zeros((N, Kmax))} if want_state else {}
+        self._chk(self._lib.stmpc_first_step(self._h, C.byref(params), C.byref(cfg), N, Kmax, _dptr(ego), _iptr(k_count), _dptr(other_x) if Kmax else None,
+                                             _dptr(other_v) if Kmax else None, _dptr(start_speed), _dptr(out["cmd_speed"]), _iptr(out["takeover"]),
+                                             _iptr(out["reason"]), _iptr(ext.get("crashed")), _iptr(ext.get("crash_guaranteed")), _dptr(ext.get("next_ego")),
+                                             _dptr(ext.get("next_other_x")) if Kmax else None, _dptr(ext.get("next_other_v")) if Kmax else None))
+        out.update(ext)
+        return out
+
+    def first_step_counts(self, reset=False):
+        """(states decided, states taken over, controller solves run for them) since the last reset; synchronises."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.stmpc_first_step_counts(self._h, C.byref(a), C.byref(b), C.byref(c), int(bool(reset))))
+        return int(a.value), int(b.value), int(c.value)
+
+    def speed_from_jerk_device(self, params, tick_length, N, d_ego5, d_jerk, d_speed, stream=0):
+        """control.get_ego_speed_from_jerk for N states on the device (``stmpc_speed_from_jerk_device``)."""
+        self._chk(self._lib.stmpc_speed_from_jerk_device(self._h, C.byref(params), float(tick_length), int(N), d_ego5, d_jerk, d_speed, stream or None))
 
     # -- batched episode simulator --------------------------------------------------------------
     def sim_init(self, cfg, N, stream=0):

@@ -13,6 +13,7 @@
 #include "stmpc_rec_kernels.hpp"
 #include "stmpc_sim_groups_kernels.hpp"
 #include "stmpc_cc_groups_kernels.hpp"
+#include "stmpc_fs_kernels.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -212,6 +213,14 @@ struct stmpc_ctx {
                            test_ego.as<double>(), test_ox.as<double>(), test_ov.as<double>()};
         }
     } cc;
+    // first-step shield controller (stmpc_first_step_device): the predicted states, the probe's and the controller's outputs
+    struct FirstStep {
+        DevBuf next_ego, next_ox, next_ov, crashed, pcrash, path, bt, cost, speed, fine, fine_len, takeovers,
+            sel_idx, sel_count, c_ego, c_k, c_ox, c_ov, c_speed, c_fine, c_fine_len;      // sparse controller solve, as Combined's
+        int N = 0, K = 0;           // shape of the last call (stmpc_first_step reads the predicted states back)
+        int *host_count = nullptr;  // pinned host word for the number of taken-over states
+        int64_t decisions = 0, control_solves = 0;      // stmpc_first_step_counts (the takeovers are counted on the device: `takeovers`, one 64-bit word)
+    } fs;
     // batched episode simulator (stmpc_sim_*)
     struct Sim {
         DevBuf ego, nveh, vx, vv, va, vc, delay, status, ticks, rng, acc, route, groups;
@@ -472,6 +481,7 @@ void stmpc_destroy(stmpc_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);       // (the device buffers are freed by their destructors, on this device)
     if (c->cc.host_count) (void)hipHostFree(c->cc.host_count);
+    if (c->fs.host_count) (void)hipHostFree(c->fs.host_count);
     if (c->h_overflow) (void)hipHostFree(c->h_overflow);
     if (c->main_masked) (void)hipStreamDestroy(c->main_masked);
     if (c->aux_reserved) (void)hipStreamDestroy(c->aux_reserved);
@@ -1945,6 +1955,150 @@ int stmpc_solve_grid_no_jerk(stmpc_ctx *c, int variant, const uint8_t *obstacles
     HIPCHK(hipMemcpy(&status, (char *)s.misc3.p + (size_t)H * 8, 4, hipMemcpyDeviceToHost));
     if (status == 1) return fail(STMPC_ENOMEM, "no-jerk solver: heap capacity exceeded");
     if (status == 2) return fail(STMPC_EINVAL, "index out of bounds: the first layer's reachable cells leave the grid (IndexError in the reference)");
+    return STMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- first-step shield controller (stmpc_fs_kernels.hpp): st.do_conditional_st_based_on_first_step, st.py:805-814 ----
+extern "C" {
+
+int stmpc_first_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_first_step_cfg *g, int N, int Kmax, const double *d_ego5, const int32_t *d_k,
+                            const double *d_ox, const double *d_ov, const double *d_oa, const double *d_start_speed, double *d_cmd_speed, int32_t *d_takeover,
+                            int32_t *d_reason, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (!p || !g) return fail(STMPC_EINVAL, "NULL parameter struct");
+    if (!(g->tick_length > 0)) return fail(STMPC_EINVAL, "tick_length must be positive");
+    if (!(g->min_crash_distance >= 0)) return fail(STMPC_EINVAL, "min_crash_distance must not be negative");
+    TRY(check_batch(N, Kmax));
+    if (N == 0) return STMPC_OK;
+    if (!d_ego5 || !d_k || !d_start_speed || !d_cmd_speed || !d_takeover || !d_reason) return fail(STMPC_EINVAL, "NULL device pointer");
+    if (Kmax > 0 && (!d_ox || !d_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
+    (void)d_oa;                          // (prediction.py:75-97 reads no accelerations: the argument completes the planner's view, nothing more)
+    HIPCHK(hipSetDevice(c->device));
+    DevP dp;
+    TRY(make_devp(p, &dp));
+    const int H = stmpc_num_t(p);
+    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
+    const int Kalloc = Kmax > 0 ? Kmax : 1;
+    hipStream_t st_ = (hipStream_t)stream;
+    const size_t n = (size_t)N;
+    auto &b = c->fs;
+    TRY(b.next_ego.ensure(n * 5 * 8)); TRY(b.next_ox.ensure(n * Kalloc * 8)); TRY(b.next_ov.ensure(n * Kalloc * 8)); TRY(b.crashed.ensure(n * 4));
+    TRY(b.pcrash.ensure(n * 4)); TRY(b.path.ensure(n * H * 4)); TRY(b.bt.ensure(n * 4)); TRY(b.cost.ensure(n * 8));
+    TRY(b.speed.ensure(n * 8)); TRY(b.fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(b.fine_len.ensure(n * 4));
+    if (!b.takeovers.p) { TRY(b.takeovers.ensure(8)); HIPCHK(hipMemset(b.takeovers.p, 0, 8)); }
+    b.N = N; b.K = Kalloc;
+    const int blocks = (N + 63) / 64;
+    // 1. one predictor step with the proposed speed, laid out as the probe's state (st.py:806)
+    with_kmax(Kalloc, [&](auto km) {
+        hipLaunchKernelGGL(k_fs_step<decltype(km)::value>, dim3(blocks), dim3(64), 0, st_, dp, g->tick_length, g->min_crash_distance, N, Kmax, d_ego5, d_k, d_ox, d_ov,
+                           d_start_speed, b.crashed.as<int>(), b.next_ego.as<double>(), b.next_ox.as<double>(), b.next_ov.as<double>());
+    });
+    HIPCHK(hipGetLastError());
+    // 2. st.test_guaranteed_crash_from_state(next_state), st.py:807: one batched solve (the reference asks before it looks at `crashed`, so every state is solved)
+    TRY(stmpc_solve_batch_device(c, p, N, Kmax, b.next_ego.as<double>(), d_k, b.next_ox.as<double>(), b.next_ov.as<double>(), b.path.as<int32_t>(),
+                                 b.bt.as<int32_t>(), b.cost.as<double>(), nullptr, b.pcrash.as<int32_t>(), stream));
+    // 3. st.do_st_control(state) of the START state, st.py:811
+    b.decisions += N;
+    if (g->sparse_control) {
+        // only for the states st.py:808 hands over: ordered compaction, ONE host round trip for their number, the controller on the compact batch, scatter
+        TRY(b.sel_idx.ensure(n * 4)); TRY(b.sel_count.ensure(4));
+        if (!b.host_count) HIPCHK(hipHostMalloc((void **)&b.host_count, 4, hipHostMallocDefault));
+        HIPCHK(hipMemsetAsync(b.speed.p, 0xFF, n * 8, st_));            // NaN: no controller command exists for a state that keeps the proposed speed
+        HIPCHK(hipMemsetAsync(b.fine_len.p, 0, n * 4, st_));
+        hipLaunchKernelGGL(k_fs_select, dim3(1), dim3(1024), 0, st_, N, (const int *)b.crashed.as<int>(), (const int *)b.pcrash.as<int>(), b.sel_idx.as<int>(),
+                           b.sel_count.as<int>());
+        HIPCHK(hipMemcpyAsync(b.host_count, b.sel_count.p, 4, hipMemcpyDeviceToHost, st_));
+        HIPCHK(hipStreamSynchronize(st_));
+        const int M = *b.host_count;
+        if (M < 0 || M > N) return fail(STMPC_EINTERNAL, "first-step controller: selection count out of range");
+        b.control_solves += M;
+        if (M > 0) {
+            const size_t m = (size_t)M;
+            TRY(b.c_ego.ensure(m * 5 * 8)); TRY(b.c_k.ensure(m * 4)); TRY(b.c_ox.ensure(m * Kalloc * 8)); TRY(b.c_ov.ensure(m * Kalloc * 8));
+            TRY(b.c_speed.ensure(m * 8)); TRY(b.c_fine.ensure(m * STMPC_QP_NMAX * 8)); TRY(b.c_fine_len.ensure(m * 4));
+            const int mb = (M + 63) / 64;
+            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kmax, (const int *)b.sel_idx.as<int>(), d_ego5, d_k, d_ox, d_ov,
+                               b.c_ego.as<double>(), b.c_k.as<int>(), b.c_ox.as<double>(), b.c_ov.as<double>());
+            HIPCHK(hipMemsetAsync(b.c_fine.p, 0, m * STMPC_QP_NMAX * 8, st_));
+            TRY(st_control_device(c, p, g->tick_length, M, Kalloc, b.c_ego.as<double>(), b.c_k.as<int32_t>(), b.c_ox.as<double>(), b.c_ov.as<double>(),
+                                  b.path.as<int32_t>(), b.bt.as<int32_t>(), b.cost.as<double>(), b.c_speed.as<double>(), b.c_fine.as<double>(),
+                                  b.c_fine_len.as<int32_t>(), stream, nullptr));
+            hipLaunchKernelGGL(k_cc_scatter, dim3(mb), dim3(64), 0, st_, M, (const int *)b.sel_idx.as<int>(), (const double *)b.c_speed.as<double>(),
+                               (const double *)b.c_fine.as<double>(), (const int *)b.c_fine_len.as<int>(), STMPC_QP_NMAX, b.speed.as<double>(),
+                               b.fine.as<double>(), b.fine_len.as<int>());
+        }
+    } else {
+        b.control_solves += N;
+        HIPCHK(hipMemsetAsync(b.fine.p, 0, n * STMPC_QP_NMAX * 8, st_));
+        TRY(st_control_device(c, p, g->tick_length, N, Kmax, d_ego5, d_k, d_ox, d_ov, b.path.as<int32_t>(), b.bt.as<int32_t>(), b.cost.as<double>(),
+                              b.speed.as<double>(), b.fine.as<double>(), b.fine_len.as<int32_t>(), stream, nullptr));
+    }
+    // 4. the choice, st.py:808-814
+    hipLaunchKernelGGL(k_fs_decide, dim3(blocks), dim3(64), 0, st_, N, d_start_speed, (const int *)b.crashed.as<int>(), (const int *)b.pcrash.as<int>(),
+                       (const double *)b.speed.as<double>(), (const int *)b.fine_len.as<int>(), d_cmd_speed, d_takeover, d_reason,
+                       b.takeovers.as<unsigned long long>(), c->sticky.as<unsigned>() + 1);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_first_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_first_step_cfg *g, int N, int Kmax, const double *ego, const int32_t *k, const double *ox,
+                     const double *ov, const double *start_speed, double *cmd_speed, int32_t *takeover, int32_t *reason, int32_t *crashed,
+                     int32_t *crash_guaranteed, double *next_ego, double *next_ox, double *next_ov) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(check_batch(N, Kmax));
+    if (N == 0) return STMPC_OK;
+    if (!ego || !k || !start_speed || !cmd_speed || !takeover || !reason) return fail(STMPC_EINVAL, "NULL host pointer");
+    if (Kmax > 0 && (!ox || !ov)) return fail(STMPC_EINVAL, "NULL host pointer (other_x/other_v)");
+    TRY(check_counts(N, Kmax, k));
+    HIPCHK(hipSetDevice(c->device));
+    auto &s = c->s;
+    const size_t n = (size_t)N;
+    TRY(s.states(N, Kmax, ego, 5, k, ox, ov));
+    TRY(upload(s.misc0, start_speed, n));
+    TRY(s.misc1.ensure(n * 8)); TRY(s.misc2.ensure(n * 4)); TRY(s.misc3.ensure(n * 4));
+    TRY(stmpc_first_step_device(c, p, g, N, Kmax, s.ego.as<double>(), s.k.as<int32_t>(), s.ox.as<double>(), s.ov.as<double>(), nullptr, s.misc0.as<double>(),
+                                s.misc1.as<double>(), s.misc2.as<int32_t>(), s.misc3.as<int32_t>(), nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    const auto &b = c->fs;
+    TRY(download(cmd_speed, s.misc1, n)); TRY(download(takeover, s.misc2, n)); TRY(download(reason, s.misc3, n));
+    TRY(download(crashed, b.crashed, n)); TRY(download(crash_guaranteed, b.pcrash, n)); TRY(download(next_ego, b.next_ego, n * 5));
+    if (Kmax > 0) { TRY(download(next_ox, b.next_ox, n * Kmax)); TRY(download(next_ov, b.next_ov, n * Kmax)); }
+    return stmpc_check_error(c);         // (this entry is synchronous: what its kernels flagged is its own error)
+}
+
+int stmpc_first_step_counts(stmpc_ctx *c, int64_t *decisions, int64_t *takeovers, int64_t *control_solves, int reset) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    auto &b = c->fs;
+    unsigned long long t = 0;
+    if (b.takeovers.p) {
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(&t, b.takeovers.p, sizeof t, hipMemcpyDeviceToHost));
+        if (reset) HIPCHK(hipMemset(b.takeovers.p, 0, sizeof t));
+    }
+    if (decisions) *decisions = b.decisions;
+    if (takeovers) *takeovers = (int64_t)t;
+    if (control_solves) *control_solves = b.control_solves;
+    if (reset) { b.decisions = 0; b.control_solves = 0; }
+    return STMPC_OK;
+}
+
+int stmpc_speed_from_jerk_device(stmpc_ctx *c, const stmpc_params *p, double tick_length, int N, const double *d_ego5, const double *d_jerk, double *d_speed,
+                                 void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (!p) return fail(STMPC_EINVAL, "params is NULL");
+    if (!(tick_length > 0)) return fail(STMPC_EINVAL, "tick_length must be positive");
+    if (N < 0) return fail(STMPC_EINVAL, "N out of range");
+    if (N == 0) return STMPC_OK;
+    if (!d_ego5 || !d_jerk || !d_speed) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c->device));
+    CCfg cc;
+    memset(&cc, 0, sizeof cc);
+    cc.tick = tick_length; cc.a_max = p->a_max; cc.a_min = p->a_min; cc.v_max = p->v_max;
+    hipLaunchKernelGGL(k_fs_speed_from_jerk, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, cc, N, d_ego5, d_jerk, d_speed);
+    HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 

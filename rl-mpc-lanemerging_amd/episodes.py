@@ -5,8 +5,8 @@
 The world restates the SUMO scenario the reference configures (Krauss vehicles of the "simple traffic distribution", the ego under
 speed mode 22; see ``stmpc_sim_*`` in include/stmpc.h) but is not SUMO: results are comparable with the reference's reported numbers
 (experiment_data/saved_data.csv) as DISTRIBUTIONS only.  Every tick is: planner view ->
-controller (``st.do_st_control`` for all environments in one launch, or the combined controller) -> world step; nothing but a
-periodic "all finished?" flag crosses to the host.
+controller (``st.do_st_control`` for all environments in one launch, the combined controller, or the first-step shield controller of
+``first_step.py``) -> world step; nothing but a periodic "all finished?" flag crosses to the host.
 """
 import os
 
@@ -158,20 +158,26 @@ class EpisodeRunner:
     settings (``stmpc_combined_groups_set``) and bit-identical to a lone runner of ``n / C`` environments with ``control=[control[c]]``, and
     ``result()`` gains ``out["control_group"]``.  With ``traffic`` and / or a population policy too, cell c pairs member c, traffic c and
     control c: the counts and slice sizes must coincide.  Give the traffic groups one ``seed`` for common random numbers across the cells
-    (``grid_search_combined``)."""
+    (``grid_search_combined``).
+
+    ``controller="first_step"``: ``st.do_conditional_st_based_on_first_step`` (st.py:805-814, ``first_step.py``) behind ``policy`` -- per tick the
+    view, ONE policy evaluation, ``control.get_ego_speed_from_jerk`` of its jerk, ``stmpc_first_step_device``, the world step.  ``policy`` (an actor or
+    a population) and ``traffic`` work as for "combined"; ``control`` is refused (its keys are settings of the combined controller)."""
 
     def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, record=None, traffic=None, control=None):
         import torch
         self.torch = torch
-        if controller not in ("st", "combined"):
+        if controller not in ("st", "combined", "first_step"):
             # (the policy alone -- TASK EVALUATE_DDPG -- is not on the solver's path: SURVEY section 2 marks ddpg.py out of scope; removed in round 6)
-            raise ValueError("controller must be 'st' or 'combined', not %r" % (controller,))
+            raise ValueError("controller must be 'st', 'combined' or 'first_step', not %r" % (controller,))
         if hasattr(policy, "P") and int(n) != policy.n:
             raise ValueError("n = %d, the population of policies was built for %d x %d = %d environments" % (n, policy.P, policy.n_per_member, policy.n))
         self.traffic = list(traffic) if traffic is not None else None
         self.control = list(control) if control is not None else None
         if self.control is not None and controller != "combined":
             raise ValueError("control groups are settings of the combined controller, not of %r" % (controller,))
+        if controller == "first_step" and policy is None:
+            raise ValueError("the first-step controller shields a policy's proposal: give one (an actor.DDPGActor or an actor.ActorPopulation)")
         self.C, self.n_per_cell = _check_control(n, self.control, self.traffic, policy) if self.control is not None else (0, 0)
         self.G, self.n_per_group = _check_traffic(n, self.traffic, policy) if self.traffic is not None else (0, 0)
         self.n, self.kmax, self.controller, self.policy = int(n), int(kmax), controller, policy
@@ -191,6 +197,11 @@ class EpisodeRunner:
         if self.control is not None:
             from . import combined
             self.ccfg = combined.ControlGroups(combined.control_cfgs(self.control, sparse_control=True), self.n_per_cell)
+        self.fs = None
+        if controller == "first_step":
+            from . import first_step
+            self.fs = first_step.FirstStepController(n, self.ctx, self.params, sparse_control=True)      # (sparse for the reason above)
+            self.cur_ego4 = z(n, 4)
         self.takeovers, self.controlled = z(n), z(n)
         self.last_rl = torch.ones(n, dtype=torch.int32, device=dev)
         self.d_status = z(n, dtype=torch.int32)
@@ -218,7 +229,12 @@ class EpisodeRunner:
                                         self.d_fine_len.data_ptr(), 0)
             cmd = self.d_speed
         else:
-            d = combined.decide_batch_device(ctx, self.params, self.ccfg, self.d_ego5, self.d_k, self.d_ox, self.d_ov, self.policy, self.last_rl, d_oa=self.d_oa)
+            if self.controller == "first_step":
+                self.cur_ego4.copy_(self.d_ego5[:, :4])
+                jerk = self.policy(1, self.cur_ego4, self.d_k, self.d_ox, self.d_ov, self.d_oa).to(torch.float64).contiguous()
+                d = self.fs.decide_jerk(self.d_ego5, self.d_k, self.d_ox, self.d_ov, jerk, self.d_oa)
+            else:
+                d = combined.decide_batch_device(ctx, self.params, self.ccfg, self.d_ego5, self.d_k, self.d_ox, self.d_ov, self.policy, self.last_rl, d_oa=self.d_oa)
             cmd = d["speed"]
             # per-episode takeover share (the reference's stats count the ticks of the episode itself): finished environments keep
             # returning their final state from sim_view, their repeated decisions must not be counted
@@ -229,7 +245,7 @@ class EpisodeRunner:
             self.last_rl = (d["takeover"] == 0).to(torch.int32)
         if self.recorder is not None:
             # the state before control, as the reference appends it to state_history (control.py:280-289), with this tick's command
-            self.recorder.tick(n, kmax, self.d_ego5, self.d_k, self.d_ox, self.d_ov, self.d_oa, cmd, d["takeover"] if self.controller == "combined" else None)
+            self.recorder.tick(n, kmax, self.d_ego5, self.d_k, self.d_ox, self.d_ov, self.d_oa, cmd, d["takeover"] if self.controller != "st" else None)
         if self.cfgs is not None:
             ctx.sim_step_groups(self.params, n, cmd.data_ptr())
         else:
@@ -247,7 +263,7 @@ class EpisodeRunner:
         self.ctx.check_error()
         out = stats_columns(status, ticks, acc, self.tick_length)
         out["ego4"] = ego4
-        if self.controller == "combined":
+        if self.controller != "st":
             out["percent_st"] = (self.takeovers / self.torch.clamp(self.controlled, min=1.0)).cpu().numpy()
         if hasattr(self.policy, "P"):
             out["member"] = np.arange(self.n) // self.policy.n_per_member
@@ -286,10 +302,10 @@ def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max
     """Run ``n`` merge episodes to the end (or for ``max_ticks`` ticks); returns the per-episode columns of the reference's stats report
     (``crashed``, ``merged``, ``mean_speed``, ``max_speed``, ``mean_abs_jerk``, ``closest_distance``, ``mean_closest_distance``,
     ``time_taken``, ``time_to_merge`` (NaN unless merged)) plus ``ticks``, ``status`` (0 still running), ``ego4`` and ``percent_st``
-    (combined controller only).
+    (the controllers that shield a policy only).
 
     controller: "st" = ``st.do_st_control`` every tick (TASK "ST"); "combined" = ``do_combined_control`` with ``policy``
-    (see ``combined.decide_batch_device``).  record: None, or a ``report.RecorderConfig`` -- the result then holds ``report`` (``report.Report``),
+    (see ``combined.decide_batch_device``); "first_step" = ``do_conditional_st_based_on_first_step`` behind ``policy`` (``first_step.py``).  record: None, or a ``report.RecorderConfig`` -- the result then holds ``report`` (``report.Report``),
     see ``EpisodeRunner``.  traffic: None, or the traffic groups of ``EpisodeRunner``; the tick limit is then the largest group's ``max_ticks + 1``.
     control: None, or the controller groups of ``EpisodeRunner``."""
     r = EpisodeRunner(n, seed, controller, policy, ctx, kmax, max_episode_length, record, traffic, control)
@@ -365,17 +381,21 @@ def grid_search_combined(model, traffic, n_per_cell, cells=None, seed=0, common_
     return {"cells": [{"settings": cells[c], "summary": by[c]} for c in range(C)], "stats": stats}
 
 
-def cross_matrix(models, traffic, n_per_cell, seed=0, ctx=None, kmax=16, max_episode_length=100.0, record=None, max_ticks=None, check_every=16):
+def cross_matrix(models, traffic, n_per_cell, seed=0, ctx=None, kmax=16, max_episode_length=100.0, record=None, max_ticks=None, check_every=16,
+                 controller="combined"):
     """The reference's ``combined_{traffic}_{seed}`` diagonal and ``cross_{traffic_1}_network_{traffic_2}_traffic_{seed}`` off-diagonals in ONE run:
     every model of ``models`` (as ``actor.ActorPopulation`` takes them: shipped names, paths, learners, actors) under the combined controller on
     every traffic group of ``traffic`` (as ``sim_cfgs`` takes them), ``n_per_cell`` episodes each.  Cell c = i * len(traffic) + j (row-major) pairs
     model i with traffic j: the population repeats each member len(traffic) times, the traffic list is tiled len(models) times, and the cells are
-    the groups of one runner (cell c's default seed is ``vec_env.episode_seed(seed, c)``).
+    the groups of one runner (cell c's default seed is ``vec_env.episode_seed(seed, c)``).  ``controller``: "combined" or "first_step" -- the same
+    worlds, actors and report under the other shield.
     Returns ``{"matrix": [len(models)][len(traffic)] ``summary`` dicts, "stats": the raw result (with ``member`` = cell and ``traffic_group`` =
     cell), "models": [...], "traffic": [...]}``."""
     from . import actor
     models, traffic = list(models), list(traffic)
     M, T = len(models), len(traffic)
+    if controller not in ("combined", "first_step"):
+        raise ValueError("cross_matrix runs models under 'combined' or 'first_step', not %r" % (controller,))
     if M < 1 or T < 1:
         raise ValueError("cross_matrix needs at least one model and one traffic group")
     if int(n_per_cell) < 1:
@@ -388,7 +408,7 @@ def cross_matrix(models, traffic, n_per_cell, seed=0, ctx=None, kmax=16, max_epi
     loaded = [actor.DDPGActor(os.fspath(m), 1, ctx, Settings) if isinstance(m, (str, os.PathLike)) else m for m in models]
     cell_models = [m for m in loaded for _ in range(T)]
     pop = actor.ActorPopulation(cell_models, int(n_per_cell), ctx, Settings)
-    stats = run_episodes(pop.n, seed=seed, controller="combined", policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, check_every=check_every,
+    stats = run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, check_every=check_every,
                          max_ticks=max_ticks, record=record, traffic=cell_traffic)
     cells = summary_by_group(stats, M * T)
     return {"matrix": [[cells[i * T + j] for j in range(T)] for i in range(M)], "stats": stats, "models": models, "traffic": traffic}

@@ -502,7 +502,7 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
     return out
 
 
-def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None):
+def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):
     """The reference's per-model ``EVALUATE_COMBINED_DDPG`` -- and the evaluation ``train_ddpg_all_with_lr_drop`` (ddpg.py:96-117) ends with -- for
     every member at once: ``n_per_member`` merge episodes per member under the combined controller, in ONE run of P * n_per_member environments
     whose policy is an ``actor.ActorPopulation``.  ``source``: a ``DDPGPopulation`` or a ``DDPGLearner`` (zero-copy views of the weights as they
@@ -511,14 +511,16 @@ def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=1
     Returns ``{"stats": run_episodes' columns + "member", "by_member": P summary rows, "reports": P ``report.Report``s (None without ``record``)}``.
     The members' episodes are different draws of one world (identically distributed, not common random numbers).
     ``traffic``: None, or one traffic group per member (as ``episodes.sim_cfgs`` takes them): member m is evaluated on traffic m, and its report
-    row carries that traffic's TRAFFIC_DESCRIPTION."""
+    row carries that traffic's TRAFFIC_DESCRIPTION.  ``controller``: "combined", or "first_step" for the one-step shield of ``first_step.py``."""
     from . import episodes
+    if controller not in ("combined", "first_step"):
+        raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
     members = source if isinstance(source, (DDPGPopulation, list, tuple)) else [source]
     if traffic is not None and len(traffic) != len(members):
         raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), len(members)))
     ctx = ctx if ctx is not None else _capi.Context(-1)
     pop = _actor.ActorPopulation(members, n_per_member, ctx, Settings)
-    stats = episodes.run_episodes(pop.n, seed=seed, controller="combined", policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
+    stats = episodes.run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
                                   traffic=traffic)
     rep = stats.get("report")
     return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),

@@ -1,0 +1,138 @@
+"""First-step shield controller, host side (first_step.py, the ``controller="first_step"`` argument of episodes.EpisodeRunner, the stmpc_first_step* /
+stmpc_speed_from_jerk_device entries of include/stmpc.h, the fixture recorded from the reference's own st.do_conditional_st_based_on_first_step).
+No GPU: header / library / binding agree on the entries and the cfg's layout, ``FirstStepCfg.from_settings`` reads what the reference reads, the fixture
+populates every branch as its generator promises, and the arguments the controller cannot take are refused before a context is asked for anything.
+"""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import REPO, load_golden
+
+ENTRIES = {"stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device"}
+
+
+def _pkg():
+    import rl_mpc_lanemerging_amd as pkg
+    if pkg.build.needs_build():
+        pkg.build.build()
+    return pkg
+
+
+class _NoDevice:
+    """A context that must not be asked for anything."""
+
+    def __getattr__(self, name):
+        raise AssertionError("the device was touched (%s)" % name)
+
+
+def test_header_library_and_binding_agree_on_the_first_step_entries():
+    _pkg()
+    from rl_mpc_lanemerging_amd import _capi as capi
+    lib = capi.load()
+    header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
+    header = re.sub(r"/\*.*?\*/", " ", header)
+    declared = {name: args for name, args in re.findall(r"\bint (stmpc_(?:first_step|speed_from_jerk)[a-z_0-9]*)\s*\(([^)]*)\)\s*;", header)}
+    assert set(declared) == ENTRIES and ENTRIES <= set(capi.EXPORTS)
+    for name, args in declared.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(args.split(",")), name
+    assert capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8 and "#define STMPC_ABI_VERSION 8" in header
+    for method in ("first_step_device", "first_step", "first_step_counts", "speed_from_jerk_device"):
+        assert callable(getattr(capi.Context, method))
+    # the cfg, field for field: names, order, C types, offsets, size
+    body = re.search(r"typedef struct stmpc_first_step_cfg \{(.*?)\} stmpc_first_step_cfg;", header).group(1)
+    fields = [tuple(f.split()) for f in body.split(";") if f.strip()]
+    assert fields == [("double", "tick_length"), ("double", "min_crash_distance"), ("int", "sparse_control")]
+    ctype = {"double": C.c_double, "int": C.c_int}
+    assert [(n, t) for n, t in capi.FirstStepCfg._fields_] == [(n, ctype[t]) for t, n in fields]
+    assert [getattr(capi.FirstStepCfg, n).offset for n, _ in capi.FirstStepCfg._fields_] == [0, 8, 16] and C.sizeof(capi.FirstStepCfg) == 24
+
+
+def test_cfg_from_settings(restore_settings):
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import _capi as capi, first_step
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    assert first_step.FirstStepCfg is capi.FirstStepCfg
+    c = capi.FirstStepCfg.from_settings(pkg.Settings)
+    # st.py:806 passes delta_t = TICK_LENGTH and no min_crash_distance: the predictor's default, 5 (prediction.py:46), whatever COMBINATION_MIN_DISTANCE is
+    assert (c.tick_length, c.min_crash_distance, c.sparse_control) == (pkg.Settings.TICK_LENGTH, 5.0, 0)
+    pkg.Settings.TICK_LENGTH, pkg.Settings.COMBINATION_MIN_DISTANCE = 0.1, 7.5
+    c = capi.FirstStepCfg.from_settings(pkg.Settings, sparse_control=True)
+    assert (c.tick_length, c.min_crash_distance, c.sparse_control) == (0.1, 5.0, 1)
+    assert (first_step.REASON_PROPOSED, first_step.REASON_CRASHED, first_step.REASON_GUARANTEED) == (0, 1, 2)
+    # the host twin of stmpc_speed_from_jerk_device: control.py:160-171, clamps included
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    S = pkg.Settings
+    t = S.TICK_LENGTH
+    assert first_step.get_ego_speed_from_jerk(10.0, 0.5, 1.0) == 10.0 + (0.5 + 1.0 * t) * t
+    assert first_step.get_ego_speed_from_jerk(10.0, S.MAX_POSITIVE_ACCELERATION, 5.0) == 10.0 + S.MAX_POSITIVE_ACCELERATION * t
+    assert first_step.get_ego_speed_from_jerk(10.0, S.MAX_NEGATIVE_ACCELERATION, -5.0) == 10.0 + S.MAX_NEGATIVE_ACCELERATION * t
+    assert first_step.get_ego_speed_from_jerk(0.1, S.MAX_NEGATIVE_ACCELERATION, -5.0) == 0
+    assert first_step.get_ego_speed_from_jerk(S.MAX_SPEED, 2.0, 5.0) == S.MAX_SPEED
+
+
+def test_fixture_populates_every_branch():
+    g = load_golden("golden_first_step.npz")
+    n = g["ego"].shape[0]
+    for key, shape in (("ego", (n, 5)), ("next_ego", (n, 5)), ("other_x", (n, 8)), ("other_v", (n, 8)), ("next_other_x", (n, 8)), ("next_other_v", (n, 8)),
+                       ("k_count", (n,)), ("start_speed", (n,)), ("jerk", (n,)), ("crashed", (n,)), ("crash_guaranteed", (n,)), ("branch", (n,))):
+        assert g[key].shape == shape, key
+    crashed, guaranteed = g["crashed"] != 0, g["crash_guaranteed"] != 0
+    assert int(crashed.sum()) >= 20 and int((guaranteed & ~crashed).sum()) >= 20 and int((~guaranteed & ~crashed).sum()) >= 100
+    assert (int(crashed.sum()), int((guaranteed & ~crashed).sum()), int((~guaranteed & ~crashed).sum())) == (59, 23, 1538)      # the generator's docstring
+    # the branch is the reference's `crashed or crash_guaranteed`, the step's crash first
+    assert np.array_equal(g["branch"], np.where(crashed, 1, np.where(guaranteed, 2, 0)))
+    # three proposed speeds per state, jerk -5 and +5 among them, each the host function of (speed, acceleration, jerk)
+    assert n % 3 == 0 and np.array_equal(g["ego"][0::3], g["ego"][1::3]) and np.array_equal(g["ego"][0::3], g["ego"][2::3])
+    assert np.all(g["jerk"][1::3] == -5.0) and np.all(g["jerk"][2::3] == 5.0)
+    assert int(g["n_from_combined_real"]) == 720
+    real = load_golden("golden_combined_real.npz")
+    assert np.array_equal(g["ego"][0:720:3], real["ego"][:240]) and np.array_equal(g["jerk"][0:720:3], real["jerks"][:240, 0])
+    assert np.array_equal(g["next_ego"][:, 2], g["start_speed"])              # the predicted state's speed is the proposed one (prediction.py:105)
+    assert os.path.getsize(os.path.join(REPO, "tests", "golden", "golden_first_step.npz")) < 512 * 1024
+
+
+def test_fixture_speeds_are_the_host_function(restore_settings):
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import combined_bench, first_step
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
+    g = load_golden("golden_first_step.npz")
+    for key, val in zip(g["setting_keys"], g["setting_vals"]):
+        assert float(getattr(pkg.Settings, str(key))) == float(val), key
+    want = [first_step.get_ego_speed_from_jerk(float(v), float(a), float(j)) for v, a, j in zip(g["ego"][:, 2], g["ego"][:, 3], g["jerk"])]
+    assert np.array_equal(np.array(want, dtype=np.float64), g["start_speed"])
+
+
+def test_arguments_the_controller_cannot_take_are_refused_before_any_context(restore_settings):
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import episodes, learner
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+
+    class Pop:                                                     # what EpisodeRunner reads of an actor.ActorPopulation
+        def __init__(self, P, npm):
+            self.P, self.n_per_member, self.n = P, npm, P * npm
+    nodev = _NoDevice()
+    # control groups are the combined controller's settings
+    with pytest.raises(ValueError, match="not of 'first_step'"):
+        episodes.EpisodeRunner(48, controller="first_step", policy=Pop(2, 24), ctx=nodev, control=[{"ROLLOUT_LENGTH": 3}, {}])
+    with pytest.raises(ValueError, match="not of 'first_step'"):
+        episodes.run_episodes(48, controller="first_step", policy=Pop(1, 48), ctx=nodev, control=[{}])
+    # it shields a policy: there must be one
+    with pytest.raises(ValueError, match="shields a policy"):
+        episodes.EpisodeRunner(48, controller="first_step", ctx=nodev)
+    # the population and traffic checks are those of the combined controller
+    with pytest.raises(ValueError, match="built for 2 x 24 = 48"):
+        episodes.EpisodeRunner(50, controller="first_step", policy=Pop(2, 24), ctx=nodev)
+    with pytest.raises(ValueError, match="2 members of 24 environments, the traffic 3 groups of 16"):
+        episodes.EpisodeRunner(48, controller="first_step", policy=Pop(2, 24), ctx=nodev, traffic=["low", "medium", "fast"])
+    with pytest.raises(ValueError, match="'st', 'combined' or 'first_step'"):
+        episodes.EpisodeRunner(48, controller="second_step", ctx=nodev)
+    with pytest.raises(ValueError, match="'combined' or 'first_step', not 'st'"):
+        episodes.cross_matrix(["medium1"], ["medium"], 4, ctx=nodev, controller="st")
+    with pytest.raises(ValueError, match="'combined' or 'first_step', not 'st'"):
+        learner.evaluate_members(["medium1"], 4, ctx=nodev, controller="st")
