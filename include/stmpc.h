@@ -749,6 +749,50 @@ int stmpc_combined_decide_groups_device(stmpc_ctx *ctx, const stmpc_params *p, i
                                         const int32_t *d_last_choice_rl, int32_t *d_takeover, int32_t *d_reason, double *d_speed, void *stream);
 
 /*
+ * Solver groups: one batch of the ST solver split into G groups of n_per_group consecutive states, each solved under its own stmpc_params, in the
+ * launches of one batch (state i belongs to group i / n_per_group).  The reference tunes the solver along exactly this axis, one process per cell:
+ * main.do_grid_search_st (main.py:43-59) runs TASK "ST" over the product of V_WEIGHT, A_WEIGHT, J_WEIGHT, D_WEIGHT, MIN_ALLOWED_DISTANCE and
+ * CRASH_MIN_S (288 cells).  (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)
+ * Every output row of group g is, bit for bit, the row of a lone call with n_per_group states under groups[g]: path_idx, best_t, cost, path_dist, crash,
+ * action_cost, and for the control entry speed, fine and fine_len.  The scheduling statistics of stmpc_stats describe the grouped batch as a whole.
+ *   May differ between groups: d_w, v_w, a_w, j_w, min_allowed, crash_min_s.  Every other field must be equal (else STMPC_EINVAL naming the field,
+ *                   before any launch): the lattice, the limits, the uncertainty settings, the predictor constants, comb_min_dist.
+ *   G = 1 ... STMPC_SOLVER_GROUPS_MAX, n_per_group >= 1, N == G * n_per_group (else STMPC_EINVAL).  G = 1 gives the results of the ungrouped entry.
+ *   stmpc_solve_batch_groups_device   stmpc_solve_batch_device_ac (main.py:43-59 over it) with a table of G parameter sets (HOST pointer; its device copy
+ *                   is kept while the next call brings an equal table, and replacing it synchronises with the device once).
+ *   stmpc_solve_batch_groups          its host-pointer form, as stmpc_solve_batch (action_cost [N][2] may be NULL).
+ *   stmpc_st_control_groups_device    stmpc_st_control_batch_device (st.do_st_control, main.py:43-59 over it): the grouped solve, then the re-sampling,
+ *                   which reads none of the six fields.
+ *   stmpc_solver_groups_sim_step_device   stmpc_sim_step_groups_device (main.py:43-59 over the world step) with the closest-distance statistics of traffic
+ *                   group g gated by groups[g].crash_min_s, so that a cell's statistics are those of a lone world under its own CRASH_MIN_S.  The world
+ *                   must have traffic groups and the solver groups must coincide with them (same G and n_per_group: cell c pairs traffic c with
+ *                   solver c).
+ *   stmpc_solver_groups_sim_init_device   stmpc_sim_init_groups_device (main.py:43-59: the world of the whole grid) for G = 1 ... STMPC_SOLVER_GROUPS_MAX
+ *                   cells, one traffic group per cell (cfgs[c]: the cell's traffic and seed; the same seed everywhere gives every cell the same
+ *                   draws), so that the whole grid is one world.  Everything that serves a world of traffic groups serves it.
+ * A grouped call with a table the context has not seen synchronises with the device to replace its copy: such a call cannot be captured in a graph
+ * (a repeat with an equal table copies nothing and can).
+ * The grouped solve runs one fixed schedule: no staged vehicle table, no checkpoint / resume between the windows.  It honours STMPC_TIERS, STMPC_NW,
+ * STMPC_PEN_CELLS, STMPC_PRUNE, STMPC_FASTDIV, STMPC_OVERLAP, STMPC_SIDE_GRID, STMPC_SPLIT, STMPC_TWO_PHASE, STMPC_HEAVY_FIRST, STMPC_BAND, STMPC_BAND_CAP,
+ * STMPC_BAND2_MULT, STMPC_BAND_DENSE, STMPC_TUBE, STMPC_TUBE_DENSE, STMPC_BOUND_INFL, STMPC_LAST_INFL, STMPC_RETRY, STMPC_GSH, STMPC_BP16 and
+ * STMPC_FORCE_GENERAL, STMPC_WAVES_PER_CU, STMPC_LDS_HEADROOM, STMPC_CU_RESERVE, STMPC_RETIRE_CUS and STMPC_RETIRE_AT.  Without effect on it:
+ * STMPC_STAGE_TAB, STMPC_RESUME, STMPC_POOL, STMPC_RETRY_MOVE, STMPC_PRIO and STMPC_PRIO_MODE (all read only by the checkpointing kernels, which the
+ * grouped path does not launch).
+ */
+#define STMPC_SOLVER_GROUPS_MAX 512
+int stmpc_solve_batch_groups_device(stmpc_ctx *ctx, const stmpc_params *groups, int G, int n_per_group, int N, int Kmax, const double *d_ego,
+                                    const int32_t *d_k_count, const double *d_other_x, const double *d_other_v, int32_t *d_path_idx, int32_t *d_best_t,
+                                    double *d_cost, double *d_path_dist, int32_t *d_crash, double *d_action_cost, void *stream);
+int stmpc_solve_batch_groups(stmpc_ctx *ctx, const stmpc_params *groups, int G, int n_per_group, int N, int Kmax, const double *ego, const int32_t *k_count,
+                             const double *other_x, const double *other_v, int32_t *path_idx, int32_t *best_t, double *cost, double *path_dist,
+                             int32_t *crash, double *action_cost);
+int stmpc_st_control_groups_device(stmpc_ctx *ctx, const stmpc_params *groups, int G, int n_per_group, double tick_length, int N, int Kmax,
+                                   const double *d_ego, const int32_t *d_k_count, const double *d_other_x, const double *d_other_v, int32_t *d_path_idx,
+                                   int32_t *d_best_t, double *d_cost, double *d_speed, double *d_fine, int32_t *d_fine_len, void *stream);
+int stmpc_solver_groups_sim_step_device(stmpc_ctx *ctx, const stmpc_params *groups, int G, int n_per_group, int N, const double *d_cmd_speed, void *stream);
+int stmpc_solver_groups_sim_init_device(stmpc_ctx *ctx, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream);
+
+/*
  * Episode flight recorder on the device, next to the world (stmpc_sim_*): the per-tick histories the reference's evaluation keeps and what it
  * bins over the ego's position, for N environments in lock-step, with nothing crossing to the host until it is read.  (Additive: new entries
  * only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)

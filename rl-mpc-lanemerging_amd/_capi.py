@@ -45,6 +45,23 @@ class Params(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ParamsTable:
+    """A contiguous ``stmpc_params[G]`` for the solver-group entries, from a sequence of ``Params`` (copied); indexing gives the copies."""
+
+    def __init__(self, params):
+        self.params = [Params.from_buffer_copy(bytes(p)) for p in params]
+        self.array = (Params * max(len(self.params), 1))(*self.params)
+
+    def __len__(self):
+        return len(self.params)
+
+    def __getitem__(self, i):
+        return self.params[i]
+
+    def __iter__(self):
+        return iter(self.params)
+
+
 class Stats(C.Structure):
     _fields_ = [("episodes", C.c_int64), ("fast_path", C.c_int64), ("fallback", C.c_int64), ("hbm_tier", C.c_int64),
                 ("retries", C.c_int64), ("nodes_exact", C.c_int64), ("nodes_bound", C.c_int64),
@@ -210,6 +227,8 @@ EXPORTS = (
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
+    "stmpc_solve_batch_groups_device", "stmpc_solve_batch_groups", "stmpc_st_control_groups_device", "stmpc_solver_groups_sim_step_device",
+    "stmpc_solver_groups_sim_init_device",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
 ENV_CONTINUOUS_JERK, ENV_JERK, ENV_ACCELERATION = 0, 1, 2                                 # STMPC_ENV_*
@@ -218,6 +237,7 @@ ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
 DDPG_ROW, DDPG_NCOUNTERS = 68, 8      # STMPC_DDPG_ROW, STMPC_DDPG_NCOUNTERS
 DDPG_POP_MAX = 64                     # STMPC_DDPG_POP_MAX
 SIM_GROUPS_MAX = 64                   # STMPC_SIM_GROUPS_MAX
+SOLVER_GROUPS_MAX = 512               # STMPC_SOLVER_GROUPS_MAX
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
 REC_HDR, REC_NQ, REC_MAX_DEPTH, REC_MAX_EDGES = 10, 4, 64, 32      # STMPC_REC_HDR, STMPC_REC_NQ, STMPC_REC_MAX_DEPTH, STMPC_REC_MAX_EDGES
 REC_COLUMNS = ("tick", "x", "y", "v", "a", "s", "k", "cmd", "takeover", "jerk")      # the first STMPC_REC_HDR columns of a record
@@ -273,6 +293,11 @@ def load():
     lib.stmpc_solve_batch_device_ac.argtypes = [vp, pp, C.c_int, C.c_int] + [vp] * 10 + [vp]
     lib.stmpc_solve_batch.argtypes = [vp, pp, C.c_int, C.c_int, dp, ip, dp, dp, ip, ip, dp, dp, ip]
     lib.stmpc_get_stats.argtypes = [vp, C.POINTER(Stats)]
+    lib.stmpc_solve_batch_groups_device.argtypes = [vp, pp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 10 + [vp]
+    lib.stmpc_solve_batch_groups.argtypes = [vp, pp, C.c_int, C.c_int, C.c_int, C.c_int, dp, ip, dp, dp, ip, ip, dp, dp, ip, dp]
+    lib.stmpc_st_control_groups_device.argtypes = [vp, pp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [vp] * 10 + [vp]
+    lib.stmpc_solver_groups_sim_step_device.argtypes = [vp, pp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.stmpc_solver_groups_sim_init_device.argtypes = [vp, C.POINTER(SimCfg), C.c_int, C.c_int, vp]
     lib.stmpc_solve_grid.argtypes = [vp, u8p, dp, C.c_int, dp, C.c_int, C.c_double, C.c_double, dp] + [C.c_double] * 11 + [dp]
     lib.stmpc_solve_grid_no_jerk.argtypes = [vp, C.c_int, u8p, dp, C.c_int, dp, C.c_int, C.c_double, dp, dp]
     lib.stmpc_build_grid.argtypes = [vp, pp, dp, C.c_int, dp, dp, u8p, dp, dp, dp]
@@ -542,6 +567,45 @@ class Context:
         self._chk(self._lib.stmpc_st_control_batch_device(self._h, C.byref(params), float(tick_length), int(N), int(Kmax),
                                                           d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, d_speed,
                                                           d_fine or None, d_fine_len or None, stream or None))
+
+    # -- solver groups (main.py:43-59): G parameter sets in the launches of one batch ------------------
+    @staticmethod
+    def _table(groups):
+        return groups if isinstance(groups, ParamsTable) else ParamsTable(groups)
+
+    def solve_batch_groups(self, groups, n_per_group, ego, k_count, other_x, other_v):
+        """``stmpc_solve_batch_groups``: state i is solved under ``groups[i // n_per_group]`` (a ``ParamsTable`` or a sequence of ``Params``).
+        Returns a dict with ``path_idx``, ``best_t``, ``cost``, ``path_dist``, ``crash`` and ``action_cost[N, 2]``."""
+        t = self._table(groups)
+        ego, k_count, other_x, other_v, N, Kmax = _batch_states(ego, k_count, other_x, other_v)
+        H = max(num_t(t.array[0]), 1) if len(t) else 1        # (an empty or unusable table is refused by the library, not here)
+        path, best_t, cost = np.empty((N, H), dtype=np.int32), np.empty(N, dtype=np.int32), np.empty(N, dtype=np.float64)
+        pdist, crash, ac = np.empty((N, H), dtype=np.float64), np.empty(N, dtype=np.int32), np.empty((N, 2), dtype=np.float64)
+        self._chk(self._lib.stmpc_solve_batch_groups(self._h, t.array, len(t), int(n_per_group), N, Kmax, _dptr(ego), _iptr(k_count),
+                                                     _dptr(other_x) if Kmax else None, _dptr(other_v) if Kmax else None,
+                                                     _iptr(path), _iptr(best_t), _dptr(cost), _dptr(pdist), _iptr(crash), _dptr(ac)))
+        return {"path_idx": path, "best_t": best_t, "cost": cost, "path_dist": pdist, "crash": crash, "action_cost": ac}
+
+    def solve_batch_groups_device(self, groups, n_per_group, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, d_pd=0, d_crash=0, d_action_cost=0, stream=0):
+        t = self._table(groups)
+        self._chk(self._lib.stmpc_solve_batch_groups_device(self._h, t.array, len(t), int(n_per_group), int(N), int(Kmax), d_ego, d_k, d_ox, d_ov, d_path,
+                                                            d_bt, d_cost, d_pd or None, d_crash or None, d_action_cost or None, stream or None))
+
+    def st_control_groups_device(self, groups, n_per_group, tick_length, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, d_speed, d_fine=0,
+                                 d_fine_len=0, stream=0):
+        t = self._table(groups)
+        self._chk(self._lib.stmpc_st_control_groups_device(self._h, t.array, len(t), int(n_per_group), float(tick_length), int(N), int(Kmax), d_ego, d_k,
+                                                           d_ox, d_ov, d_path, d_bt, d_cost, d_speed, d_fine or None, d_fine_len or None, stream or None))
+
+    def sim_init_solver_groups(self, cfgs, n_per_group, stream=0):
+        """``stmpc_solver_groups_sim_init_device``: ``sim_init_groups`` for up to ``SOLVER_GROUPS_MAX`` cells, one traffic group per cell."""
+        t = cfgs if isinstance(cfgs, SimCfgTable) else SimCfgTable(cfgs)
+        self._chk(self._lib.stmpc_solver_groups_sim_init_device(self._h, t.array, len(t), int(n_per_group), stream))
+
+    def sim_step_solver_groups(self, groups, n_per_group, N, d_cmd_speed, stream=0):
+        """``stmpc_solver_groups_sim_step_device``: the grouped world step with traffic group g's closest-distance gate at ``groups[g].crash_min_s``."""
+        t = self._table(groups)
+        self._chk(self._lib.stmpc_solver_groups_sim_step_device(self._h, t.array, len(t), int(n_per_group), int(N), d_cmd_speed, stream))
 
     def profile_begin(self):
         self._chk(self._lib.stmpc_profile(self._h, 1, None))

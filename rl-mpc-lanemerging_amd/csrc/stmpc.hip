@@ -14,6 +14,7 @@
 #include "stmpc_sim_groups_kernels.hpp"
 #include "stmpc_cc_groups_kernels.hpp"
 #include "stmpc_fs_kernels.hpp"
+#include "stmpc_solver_groups_kernels.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -313,6 +314,14 @@ struct stmpc_ctx {
     struct GuideSlot { double key[12] = {0}; bool valid = false, ok = false; int imax = 0, D = 0; std::vector<unsigned char> host; DevBuf dev; uint64_t last_use = 0; };
     GuideSlot guides[4]; uint64_t guide_clock = 0;
     DevBuf guide_cells;
+    // solver groups: the device copy of the last grouped call's table (kept while the next call's table is equal), its guide tables, one after another,
+    // and the groups' crash_min_s for the grouped world step
+    struct SolverGroupsDev {
+        DevBuf table, guide, crash_min_s;
+        std::vector<GroupP> host;          // what `table` holds
+        std::vector<double> host_cms;      // what `crash_min_s` holds
+        bool want_guide = false, guide_ok = false; int guide_imax = 0, guide_D = 0;
+    } sg;
     int prio_thr = 32000;          // STMPC_PRIO=t (0 = off): an overflowing search with more than t (layers left x nodes of the saved layer) ahead of it is served first
                                    // by the second window (SolveArgs::prio_thr): 4.60 -> 4.46 ms over 12 seeds at N = 4096, flat from 25000 to 35000
     int prio_mode = 0;             // STMPC_PRIO_MODE (experiment: which estimate prio_thr is compared with)
@@ -601,6 +610,40 @@ int make_devp(const stmpc_params *p, DevP *d) {
     return STMPC_OK;
 }
 
+// Solver groups (main.py:43-59): the DevP of every group, after checking that the groups differ in nothing but d_w, v_w, a_w, j_w, min_allowed and
+// crash_min_s.  Changes nothing; touches no device.
+int check_solver_groups(const stmpc_params *groups, int G, int n_per_group, std::vector<GroupP> *out) {
+    if (!groups) return fail(STMPC_EINVAL, "solver groups is NULL");
+    if (G < 1 || G > STMPC_SOLVER_GROUPS_MAX) return fail(STMPC_EINVAL, "G must be 1 ... STMPC_SOLVER_GROUPS_MAX (512) solver groups");
+    if (n_per_group < 1) return fail(STMPC_EINVAL, "n_per_group must be positive");
+    if ((int64_t)G * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, "G * n_per_group out of range");
+    const stmpc_params &a = groups[0];
+    for (int g = 1; g < G; ++g) {
+        const stmpc_params &b = groups[g];
+#define SAME(field) if (!(a.field == b.field)) return fail(STMPC_EINVAL, "solver groups must share " #field " (it differs in group " + std::to_string(g) + \
+                                                                         "): only d_w, v_w, a_w, j_w, min_allowed and crash_min_s may differ")
+        SAME(future_s); SAME(ds); SAME(dt); SAME(future_t); SAME(start_unc); SAME(unc_per_s); SAME(v_des); SAME(v_max); SAME(a_min); SAME(a_max);
+        SAME(j_min); SAME(j_max); SAME(car_length); SAME(max_pred_decel); SAME(follow_gap); SAME(react_thr); SAME(crash_thr); SAME(comb_min_dist);
+#undef SAME
+    }
+    if (out) {
+        out->resize((size_t)G);
+        for (int g = 0; g < G; ++g) {
+            GroupP &gp = (*out)[g];
+            memset(&gp, 0, sizeof gp);
+            if (g == 0) TRY(make_devp(&groups[0], &gp.p));
+            else {
+                // (the shared fields are equal, so are the values make_devp derives from them: the bisections are not repeated per group)
+                gp.p = (*out)[0].p;
+                gp.p.d_w = groups[g].d_w; gp.p.v_w = groups[g].v_w; gp.p.a_w = groups[g].a_w; gp.p.j_w = groups[g].j_w;
+                gp.p.min_allowed = groups[g].min_allowed;
+                gp.p.obst_min_s = groups[g].crash_min_s - groups[g].min_allowed;
+            }
+        }
+    }
+    return STMPC_OK;
+}
+
 
 // Table of the guided bounding attempt (SolveArgs::guide_tab): the optimal step sequence of the OBSTACLE-FREE problem from every lattice state
 // (i1 = cells covered in the last layer, d = i1 - cells covered in the layer before), by backward dynamic programming over the true state
@@ -677,6 +720,23 @@ void launch_predict(const DevP &dp, int N, int Kmax, const double *ego, const in
                        guide_tab, guide_imax, guide_D, guide, 0);
 }
 
+template <int KMAX>
+void launch_predict_groups(const DevP &dp, GroupTab gt, int N, int Kmax, const double *ego, const int *k, const double *ox, const double *ov,
+                           CarTab tab, unsigned *counters, u64 *ubound, int *queue1, unsigned *proxy0, int *resume_t, unsigned char *prio_key, hipStream_t st,
+                           unsigned *sticky, const unsigned char *guide_tab, int guide_imax, int guide_D, u16 *guide) {
+    constexpr int E = PredShape<KMAX>::E;
+    int blocks = (N + E - 1) / E;
+    hipLaunchKernelGGL(grouped::k_predict<KMAX>, dim3(blocks), dim3(128), 0, st, dp, gt, N, Kmax, ego, k, ox, ov, tab, counters, ubound, queue1, proxy0, resume_t, prio_key,
+                       sticky, guide_tab, guide_imax, guide_D, guide, 0);
+}
+
+// the groups of a grouped solve: the table as check_solver_groups made it (band, band2_mult and guide_off are filled in by solve_device)
+struct SolverGroupsHost { std::vector<GroupP> table; int n_per_group = 0; };
+
+int solve_device(stmpc_ctx *c, const stmpc_params *p, SolverGroupsHost *sg, int N, int Kmax, const double *d_ego,
+                 const int32_t *d_k, const double *d_ox, const double *d_ov, int32_t *d_path,
+                 int32_t *d_bt, double *d_cost, double *d_pd, int32_t *d_crash, double *d_action_cost, void *stream);
+
 }  // namespace
 
 extern "C" {
@@ -690,6 +750,19 @@ int stmpc_solve_batch_device(stmpc_ctx *c, const stmpc_params *p, int N, int Kma
 int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int Kmax, const double *d_ego,
                                 const int32_t *d_k, const double *d_ox, const double *d_ov, int32_t *d_path,
                                 int32_t *d_bt, double *d_cost, double *d_pd, int32_t *d_crash, double *d_action_cost, void *stream) {
+    return solve_device(c, p, nullptr, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, d_pd, d_crash, d_action_cost, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The batched solve behind every solver entry.  sg: null, or the groups of a grouped call (p is then groups[0], read for the shared fields): k_predict and
+// the k_solve launches are replaced by the kernels of namespace grouped on one fixed set of shapes (no staged vehicle table, no checkpoint / resume); every decision
+// below depends on fields the groups share.
+int solve_device(stmpc_ctx *c, const stmpc_params *p, SolverGroupsHost *sg, int N, int Kmax, const double *d_ego,
+                 const int32_t *d_k, const double *d_ox, const double *d_ov, int32_t *d_path,
+                 int32_t *d_bt, double *d_cost, double *d_pd, int32_t *d_crash, double *d_action_cost, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "N or Kmax out of range");
     if (N == 0) return STMPC_OK;
@@ -727,7 +800,7 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     const double fan_bound = (fan_acc < fan_jerk ? fan_acc : fan_jerk) + 2.0;
     const bool small_fan = fan_bound <= 9.0;
     // the scalar-register vehicle table costs ~48 SGPRs/VGPRs: only with the small-fan kernel (the wide one would spill)
-    const bool stage_tab = c->allow_stage_tab && small_fan && Kalloc <= 8 && stmpc_tab_bytes(H, 8) <= 4096;
+    const bool stage_tab = !sg && c->allow_stage_tab && small_fan && Kalloc <= 8 && stmpc_tab_bytes(H, 8) <= 4096;
 
     // tiers: LDS windows in increasing size, then one HBM-scratch tier whose window covers every cell
     const int Wg = next_pow2(S_nom + 2 + 128);   // covers every cell plus the 64-cell alignment slack
@@ -789,7 +862,7 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     if (pool_cap > N) pool_cap = N;
     if (pool_cap > (1 << 22)) pool_cap = 1 << 22;            // (the entry number shares a word with the layer)
     const size_t pool_bytes = (size_t)pool_cap * ((size_t)H * tierW[0] * bp_elem + ckpt_stride);
-    bool resume = c->resume && prune_on && !small_fan && !stage_tab && nt >= 2 && tierLds[0] && tierLds[1];      // (compiled for the wide-fan kernels only)
+    bool resume = !sg && c->resume && prune_on && !small_fan && !stage_tab && nt >= 2 && tierLds[0] && tierLds[1];      // (compiled for the wide-fan kernels only)
     if (resume && c->pool_bp.cap + c->ckpt.cap < pool_bytes) {
         // a growing request: only while it is at most a quarter of what the device has free right now (a process shared with torch / RCCL).
         // A request that was turned down is priced again every 64th call: memory another tenant held at that moment may be free by now.
@@ -801,7 +874,7 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
             else c->resume_refused_for = 0;
         }
     }
-    const bool resume_wanted = c->resume && prune_on && !small_fan && !stage_tab && nt >= 2 && tierLds[0] && tierLds[1];
+    const bool resume_wanted = !sg && c->resume && prune_on && !small_fan && !stage_tab && nt >= 2 && tierLds[0] && tierLds[1];
     // reserved compute units (experiment, STMPC_CU_RESERVE): the first window's persistent grid covers the remaining units only
     const bool reserve_cfg = c->cu_reserve > 0 && prune_on && nt >= 2 && tierLds[0] && tierLds[1] && !c->two_phase;
     if (reserve_cfg) tierGrid[0] = tierGrid[0] / c->num_cu * (c->num_cu - c->cu_reserve);
@@ -852,7 +925,62 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     if (heavy_first) TRY(c->prio_key.ensure((size_t)N));
     unsigned char *prio_key = heavy_first ? c->prio_key.as<unsigned char>() : nullptr;
     const unsigned char *g_tab = nullptr; u16 *g_cells = nullptr; int g_imax = 0, g_D = 0;
-    if (prune_on && c->tube_w > 0) {
+    // band of the bounding pre-pass and the factor of its second attempt, from a parameter set's weights (see SolveArgs::band below)
+    auto band_for = [&](const DevP &d, double *band, double *band2_mult) {
+        const double band_nominal = fmax(1.0, 0.5 * d.v_w * d.v_des * d.v_des);
+        *band = c->band_override > 0 ? c->band_override : (c->band_cap > 0 ? 8.0 * band_nominal : band_nominal);
+        *band2_mult = c->band2_mult > 0 ? c->band2_mult : (c->band_cap > 0 && c->band_override <= 0 ? 4.0 : 5.0);
+        if (c->band2_mult <= 0 && c->band_cap > 0) {
+            const double dv = fmax(d.v_des, d.v_max - d.v_des), da = fmax(fabs(d.a_min), fabs(d.a_max)), dj = fmax(fabs(d.j_min), fabs(d.j_max));
+            const double step_max = d.v_w * dv * dv + d.a_w * da * da + d.j_w * dj * dj;      // dearest single step, penalties aside
+            if (step_max > 0 && *band * *band2_mult > 0.7 * step_max) *band2_mult = fmax(1.0, 0.7 * step_max / *band);
+        }
+    };
+    GroupTab gtab{nullptr, 0};
+    if (sg) {
+        // The groups' table: per group the DevP, the band of its own weights and the offset of its own guide table (one table per distinct
+        // (v_w, a_w, j_w), built on the host and stored one after another).  The device copies are kept while the next call brings an equal table;
+        // replacing them waits for the device first (kernels of earlier calls may still read them).
+        const bool want_guide = prune_on && c->tube_w > 0;
+        for (auto &gp : sg->table) { band_for(gp.p, &gp.band, &gp.band2_mult); gp.guide_off = -1; }
+        const bool same = c->sg.host.size() == sg->table.size() && [&] {
+            for (size_t g = 0; g < sg->table.size(); ++g) {
+                GroupP x = c->sg.host[g]; x.guide_off = -1;
+                if (memcmp(&x, &sg->table[g], sizeof x) != 0) return false;
+            }
+            return true;
+        }();
+        if (!same || c->sg.want_guide != want_guide) {
+            std::vector<unsigned char> all;
+            std::vector<int> built;                          // groups whose table is in `all`
+            bool ok = want_guide;
+            int imax = 0, D = 0;
+            for (size_t g = 0; g < sg->table.size() && ok; ++g) {
+                GroupP &gp = sg->table[g];
+                for (int b : built)
+                    if (sg->table[b].p.v_w == gp.p.v_w && sg->table[b].p.a_w == gp.p.a_w && sg->table[b].p.j_w == gp.p.j_w) { gp.guide_off = sg->table[b].guide_off; break; }
+                if (gp.guide_off >= 0) continue;
+                std::vector<unsigned char> one;
+                ok = build_guide_table(gp.p, one, imax, D);
+                if (!ok) break;
+                gp.guide_off = (long long)all.size();
+                all.insert(all.end(), one.begin(), one.end());
+                built.push_back((int)g);
+            }
+            if (!ok) for (auto &gp : sg->table) gp.guide_off = 0;
+            HIPCHK(hipDeviceSynchronize());
+            c->sg.host.clear();
+            TRY(upload(c->sg.table, sg->table.data(), sg->table.size()));
+            if (ok) TRY(upload(c->sg.guide, all.data(), all.size()));
+            c->sg.want_guide = want_guide; c->sg.guide_ok = ok; c->sg.guide_imax = imax; c->sg.guide_D = D;
+            c->sg.host = sg->table;
+        }
+        gtab.groups = c->sg.table.as<GroupP>(); gtab.n_per_group = sg->n_per_group;
+        if (want_guide && c->sg.guide_ok) {
+            TRY(c->guide_cells.ensure((size_t)N * H * sizeof(u16)));
+            g_tab = c->sg.guide.as<unsigned char>(); g_cells = c->guide_cells.as<u16>(); g_imax = c->sg.guide_imax; g_D = c->sg.guide_D;
+        }
+    } else if (prune_on && c->tube_w > 0) {
         // guided bounding attempt: the table depends on the dynamics and the cost weights only; rebuilt when they change (a few ms on the host)
         const double key[12] = {dp.ds, dp.dt, dp.v_w, dp.a_w, dp.j_w, dp.v_des, dp.v_max, dp.a_min, dp.a_max, dp.j_min, dp.j_max, (double)H};
         stmpc_ctx::GuideSlot *slot = nullptr;
@@ -881,8 +1009,10 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     }
     HIPCHK(hipEventRecord(e0, st));
     with_kmax(Kalloc, [&](auto km) {
-        launch_predict<decltype(km)::value>(dp, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, c->ubound.as<u64>(), queue1, proxy0, resume_t, prio_key, st,
-                                            c->sticky.as<unsigned>(), g_tab, g_imax, g_D, g_cells);
+        if (sg) launch_predict_groups<decltype(km)::value>(dp, gtab, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, c->ubound.as<u64>(), queue1, proxy0, resume_t,
+                                                           prio_key, st, c->sticky.as<unsigned>(), g_tab, g_imax, g_D, g_cells);
+        else launch_predict<decltype(km)::value>(dp, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, c->ubound.as<u64>(), queue1, proxy0, resume_t, prio_key, st,
+                                                 c->sticky.as<unsigned>(), g_tab, g_imax, g_D, g_cells);
     });
 
     SolveArgs a;
@@ -896,17 +1026,10 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     // more than band_cap nodes (dp_pass): wide where few alternatives exist, beam-like where many do -- 15 % fewer
     // expanded nodes in total than the best fixed band (sweeps on the H=40 workload: fixed 60..1200, capped 225..8000 x
     // 150..550).  Any value is safe (the exact pass re-checks); it only trades pre-pass work for tightness of the bound.
-    const double band_nominal = fmax(1.0, 0.5 * dp.v_w * dp.v_des * dp.v_des);
-    a.band = c->band_override > 0 ? c->band_override : (c->band_cap > 0 ? 8.0 * band_nominal : band_nominal);
+    band_for(dp, &a.band, &a.band2_mult);
     // second attempt (penalty zone allowed): a wider band, but kept well below the cost of one worst-case step
     // (j_w * j_max^2 ~ 12 k on the benchmark lattice): a band that admits those steps keeps everything, and single
     // episodes then take several times longer (measured cliff at 44x the nominal band; 32x is used)
-    a.band2_mult = c->band2_mult > 0 ? c->band2_mult : (c->band_cap > 0 && c->band_override <= 0 ? 4.0 : 5.0);
-    if (c->band2_mult <= 0 && c->band_cap > 0) {
-        const double dv = fmax(dp.v_des, dp.v_max - dp.v_des), da = fmax(fabs(dp.a_min), fabs(dp.a_max)), dj = fmax(fabs(dp.j_min), fabs(dp.j_max));
-        const double step_max = dp.v_w * dv * dv + dp.a_w * da * da + dp.j_w * dj * dj;      // dearest single step, penalties aside
-        if (step_max > 0 && a.band * a.band2_mult > 0.7 * step_max) a.band2_mult = fmax(1.0, 0.7 * step_max / a.band);
-    }
     a.band_cap = c->band_cap;
     for (int i = 0; i < 3; ++i) a.retry_mult[i] = c->retry_mult[i];
     a.bound_infl = c->bound_infl; a.last_infl = c->last_infl;
@@ -959,6 +1082,35 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
         const bool std_shape2 = tierNW[k] == 8 && tierW[k] == 8192 && tierPW[k] == 4096;
         const int side_g = (side && !on_reserved && side_grid_auto > 0 && side_grid_auto < tierGrid[k]) ? side_grid_auto : tierGrid[k];
         const dim3 grid(on_reserved ? (tierGrid[k] / c->num_cu > 0 ? tierGrid[k] / c->num_cu : 1) * c->cu_reserve : side_g), block(64 * tierNW[k]);
+#ifndef STMPC_FAN1
+#define STMPC_FAN1 8        /* candidate slots per barrier pair of the wide-lattice kernels outside the standard second window (128 VGPRs); 7 / 11 / 12 measured in round 5, 12 again in round 6 */
+#endif
+        if (sg) {
+            // the grouped family: first window in its standard shape, any other LDS window and the HBM window in the general shape
+            SolveArgsG ag;
+            memset(&ag, 0, sizeof ag);
+            static_cast<SolveArgs &>(ag) = a;
+            ag.g = gtab;
+#define STMPC_LAUNCH_G(L, FD, FM, SG, NWX_)                                                                   \
+            do {                                                                                              \
+                if (lds > 48 * 1024)                                                                          \
+                    HIPCHK(hipFuncSetAttribute((const void *)grouped::k_solve<L, false, FD, 0, FM, SG, 0, NWX_>, \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
+                hipLaunchKernelGGL((grouped::k_solve<L, false, FD, 0, FM, SG, 0, NWX_>), grid, block, lds, lst, ag); \
+            } while (0)
+#define STMPC_LAUNCH_GS(FD, FM)                                                                               \
+            do {                                                                                              \
+                if (!tierLds[k]) STMPC_LAUNCH_G(false, false, FM, true, STMPC_MAXWAVES);                      \
+                else if (a.last_tier) STMPC_LAUNCH_G(true, FD, FM, true, STMPC_MAXWAVES);                     \
+                else if (std_shape) STMPC_LAUNCH_G(true, FD, FM, false, 4);                                   \
+                else STMPC_LAUNCH_G(true, FD, FM, false, STMPC_MAXWAVES);                                     \
+            } while (0)
+            if (small_fan) { if (fastdiv) STMPC_LAUNCH_GS(true, 9); else STMPC_LAUNCH_GS(false, 9); }
+            else { if (fastdiv) STMPC_LAUNCH_GS(true, STMPC_FAN1); else STMPC_LAUNCH_GS(false, STMPC_FAN1); }
+#undef STMPC_LAUNCH_GS
+#undef STMPC_LAUNCH_G
+            return STMPC_OK;
+        }
 #define STMPC_LAUNCH_R(L, FD, KT_, FM, SG, RS)                                                                \
         do {                                                                                                  \
             if (lds > 48 * 1024)                                                                              \
@@ -981,9 +1133,6 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
             hipLaunchKernelGGL((k_solve<L, false, FD, KT_, FM, SG, RS, 88>), grid, block, lds, lst, a);       \
         } while (0)
-#ifndef STMPC_FAN1
-#define STMPC_FAN1 8        /* candidate slots per barrier pair of the wide-lattice kernels outside the standard second window (128 VGPRs); 7 / 11 / 12 measured in round 5, 12 again in round 6 */
-#endif
 #ifndef STMPC_FAN88
 #define STMPC_FAN88 24      /* candidate slots per barrier pair in the standard second window (it has the registers: 256 VGPRs); 12 / 16 / 21 / 24 measured, EXPERIMENTS.md */
 #endif
@@ -1059,6 +1208,10 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
     if (c->profiling) { c->acc_launches += 1; c->acc_episodes += N; }
     return STMPC_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int stmpc_get_stats(stmpc_ctx *c, stmpc_stats *out) {
     if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
@@ -1394,11 +1547,12 @@ int stmpc_finer_fit_batch(stmpc_ctx *c, const stmpc_params *p, double dt, double
 static int st_control_device(stmpc_ctx *c, const stmpc_params *p, double tick, int N, int Kmax, const double *d_ego,
                              const int32_t *d_k, const double *d_ox, const double *d_ov, int32_t *d_path,
                              int32_t *d_bt, double *d_cost, double *d_speed, double *d_fine, int32_t *d_fine_len,
-                             void *stream, unsigned *refused) {
+                             void *stream, unsigned *refused, SolverGroupsHost *sg = nullptr) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (N == 0) return STMPC_OK;
     if (!d_speed) return fail(STMPC_EINVAL, "NULL device pointer (speed)");
-    TRY(stmpc_solve_batch_device(c, p, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, nullptr, nullptr, stream));
+    // (with solver groups: the re-sampling below reads none of the fields the groups may differ in -- FFConst holds limits, tick and car length only)
+    TRY(solve_device(c, p, sg, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, nullptr, nullptr, nullptr, stream));
     FFArgs a;
     memset(&a, 0, sizeof a);
     const int H = stmpc_num_t(p);
@@ -1457,6 +1611,60 @@ int stmpc_st_control_batch(stmpc_ctx *c, const stmpc_params *p, double tick, int
         return fail(STMPC_EINVAL, "finer_fit: a fine grid longer than STMPC_QP_NMAX samples is not supported (speed = NaN, fine_len = -1 for those states)");
     }
     return STMPC_OK;
+}
+
+// ---- solver groups (main.py:43-59, do_grid_search_st): G parameter sets in the launches of one batch ----
+namespace {
+int solver_groups_of(const stmpc_params *groups, int G, int n_per_group, int N, SolverGroupsHost *sg) {
+    TRY(check_solver_groups(groups, G, n_per_group, &sg->table));
+    if ((int64_t)N != (int64_t)G * n_per_group) return fail(STMPC_EINVAL, "N must be G * n_per_group");
+    sg->n_per_group = n_per_group;
+    return STMPC_OK;
+}
+}  // namespace
+
+int stmpc_solve_batch_groups_device(stmpc_ctx *c, const stmpc_params *groups, int G, int n_per_group, int N, int Kmax, const double *d_ego, const int32_t *d_k,
+                                    const double *d_ox, const double *d_ov, int32_t *d_path, int32_t *d_bt, double *d_cost, double *d_pd, int32_t *d_crash,
+                                    double *d_action_cost, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    SolverGroupsHost sg;
+    TRY(solver_groups_of(groups, G, n_per_group, N, &sg));
+    return solve_device(c, &groups[0], &sg, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, d_pd, d_crash, d_action_cost, stream);
+}
+
+int stmpc_solve_batch_groups(stmpc_ctx *c, const stmpc_params *groups, int G, int n_per_group, int N, int Kmax, const double *ego, const int32_t *k,
+                             const double *ox, const double *ov, int32_t *path, int32_t *bt, double *cost, double *pd, int32_t *crash, double *action_cost) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    SolverGroupsHost sg;
+    TRY(solver_groups_of(groups, G, n_per_group, N, &sg));
+    TRY(check_batch(N, Kmax));
+    if (!ego || !k || !path || !bt || !cost) return fail(STMPC_EINVAL, "NULL host pointer");
+    if (Kmax > 0 && (!ox || !ov)) return fail(STMPC_EINVAL, "NULL host pointer (other_x/other_v)");
+    TRY(check_counts(N, Kmax, k));
+    HIPCHK(hipSetDevice(c->device));
+    const int H = sg.table[0].p.H;
+    auto &s = c->s;
+    const size_t n = (size_t)N;
+    TRY(s.path.ensure(n * H * 4)); TRY(s.bt.ensure(n * 4)); TRY(s.cost.ensure(n * 8)); TRY(s.pd.ensure(n * H * 8)); TRY(s.crash.ensure(n * 4));
+    TRY(s.f_out.ensure(n * 2 * 8));               // (the action_cost rows)
+    TRY(s.states(N, Kmax, ego, 5, k, ox, ov));
+    TRY(solve_device(c, &groups[0], &sg, N, Kmax, s.ego.as<double>(), s.k.as<int32_t>(), s.ox.as<double>(), s.ov.as<double>(), s.path.as<int32_t>(),
+                     s.bt.as<int32_t>(), s.cost.as<double>(), s.pd.as<double>(), s.crash.as<int32_t>(), action_cost ? s.f_out.as<double>() : nullptr, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    TRY(download(path, s.path, n * H)); TRY(download(bt, s.bt, n)); TRY(download(cost, s.cost, n));
+    TRY(download(pd, s.pd, n * H)); TRY(download(crash, s.crash, n)); TRY(download(action_cost, s.f_out, n * 2));
+    stmpc_stats st;
+    return stmpc_get_stats(c, &st);
+}
+
+int stmpc_st_control_groups_device(stmpc_ctx *c, const stmpc_params *groups, int G, int n_per_group, double tick, int N, int Kmax, const double *d_ego,
+                                   const int32_t *d_k, const double *d_ox, const double *d_ov, int32_t *d_path, int32_t *d_bt, double *d_cost,
+                                   double *d_speed, double *d_fine, int32_t *d_fine_len, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    SolverGroupsHost sg;
+    TRY(solver_groups_of(groups, G, n_per_group, N, &sg));
+    return st_control_device(c, &groups[0], tick, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, d_speed, d_fine, d_fine_len, stream,
+                             c->sticky.as<unsigned>() + 1, &sg);
 }
 
 }  // extern "C"
@@ -2146,9 +2354,10 @@ int sim_route_upload(stmpc_ctx *c, const stmpc_sim_cfg *g, void *stream) {
 }
 // Traffic groups: every cfg valid, and equal in what the shared kernels (k_sim_view, k_env_act), the one route and the one vehicle type read.
 // Changes nothing; `out` receives the G kernel cfgs without their route.
-int check_groups(const stmpc_sim_cfg *cfgs, int G, int n_per_group, std::vector<sim::Cfg> *out) {
+int check_groups(const stmpc_sim_cfg *cfgs, int G, int n_per_group, std::vector<sim::Cfg> *out, int G_max = STMPC_SIM_GROUPS_MAX) {
     if (!cfgs) return fail(STMPC_EINVAL, "sim cfgs is NULL");
-    if (G < 1 || G > STMPC_SIM_GROUPS_MAX) return fail(STMPC_EINVAL, "G must be 1 ... STMPC_SIM_GROUPS_MAX (64) traffic groups");
+    if (G < 1 || G > G_max)
+        return fail(STMPC_EINVAL, G_max == STMPC_SIM_GROUPS_MAX ? "G must be 1 ... STMPC_SIM_GROUPS_MAX (64) traffic groups" : "G must be 1 ... STMPC_SOLVER_GROUPS_MAX (512) cells");
     if (n_per_group < 1) return fail(STMPC_EINVAL, "n_per_group must be positive");
     if ((int64_t)G * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, "G * n_per_group out of range");
     out->resize((size_t)G);
@@ -2179,6 +2388,7 @@ int check_grouped_world(stmpc_ctx *c, int N) {
     if (N != c->sim.N) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_groups_device (G * n_per_group)");
     return STMPC_OK;
 }
+int sim_init_groups(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream, int G_max);
 const char *const GROUPED_WORLD = "the world has traffic groups (stmpc_sim_init_groups_device): one cfg would step every group; use the grouped step entry";
 }  // namespace
 
@@ -2231,9 +2441,21 @@ int stmpc_sim_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_c
 }
 
 int stmpc_sim_init_groups_device(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream) {
+    return sim_init_groups(c, cfgs, G, n_per_group, stream, STMPC_SIM_GROUPS_MAX);
+}
+
+// (the world of a solver-groups run: one traffic group per cell of the grid, so the table may hold as many groups as the solver's)
+int stmpc_solver_groups_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream) {
+    return sim_init_groups(c, cfgs, G, n_per_group, stream, STMPC_SOLVER_GROUPS_MAX);
+}
+
+}  // extern "C"
+
+namespace {
+int sim_init_groups(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream, int G_max) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     std::vector<sim::Cfg> table;
-    TRY(check_groups(cfgs, G, n_per_group, &table));
+    TRY(check_groups(cfgs, G, n_per_group, &table, G_max));
     const int N = G * n_per_group;
     HIPCHK(hipSetDevice(c->device));
     TRY(c->sim.ensure(N));
@@ -2252,6 +2474,10 @@ int stmpc_sim_init_groups_device(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G,
     return STMPC_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
 int stmpc_sim_step_groups_device(stmpc_ctx *c, const stmpc_params *p, int N, const double *d_cmd_speed, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     TRY(check_grouped_world(c, N));
@@ -2261,6 +2487,30 @@ int stmpc_sim_step_groups_device(stmpc_ctx *c, const stmpc_params *p, int N, con
     HIPCHK(hipSetDevice(c->device));
     hipLaunchKernelGGL(sim::k_sim_step_groups, dim3((c->sim.n_per_group + 63) / 64, c->sim.G), dim3(64), 0, (hipStream_t)stream, dp, c->sim.groups.as<sim::Cfg>(),
                        c->sim.n_per_group, c->sim.state(), d_cmd_speed, p->crash_min_s);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_solver_groups_sim_step_device(stmpc_ctx *c, const stmpc_params *groups, int G, int n_per_group, int N, const double *d_cmd_speed, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(check_solver_groups(groups, G, n_per_group, nullptr));
+    TRY(check_grouped_world(c, N));
+    if (G != c->sim.G || n_per_group != c->sim.n_per_group)
+        return fail(STMPC_EINVAL, "the solver groups must coincide with the world's traffic groups (cell c pairs traffic c with solver c): G and n_per_group differ");
+    if (!d_cmd_speed) return fail(STMPC_EINVAL, "NULL device pointer");
+    DevP dp;
+    TRY(make_devp(&groups[0], &dp));          // (the step reads the limits only: shared fields)
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<double> cms((size_t)G);
+    for (int g = 0; g < G; ++g) cms[g] = groups[g].crash_min_s;
+    if (cms != c->sg.host_cms) {                  // (once per runner: the table is kept while the next step brings equal values)
+        HIPCHK(hipDeviceSynchronize());
+        c->sg.host_cms.clear();
+        TRY(upload(c->sg.crash_min_s, cms.data(), cms.size()));
+        c->sg.host_cms = cms;
+    }
+    hipLaunchKernelGGL(sim::k_sim_step_solver_groups, dim3((n_per_group + 63) / 64, G), dim3(64), 0, (hipStream_t)stream, dp, c->sim.groups.as<sim::Cfg>(), n_per_group,
+                       c->sim.state(), d_cmd_speed, c->sg.crash_min_s.as<double>());
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }

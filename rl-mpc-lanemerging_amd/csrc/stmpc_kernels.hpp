@@ -28,7 +28,22 @@
 //               in the second.
 //
 // Everything is fp64 and compiled with -ffp-contract=off: one IEEE op per reference op.
-#pragma once
+//
+// Solver groups (stmpc_solver_groups_kernels.hpp) compile k_predict and the k_solve family a SECOND time, in namespace stmpc::grouped, by including this
+// file again with STMPC_KERNELS_GROUPED_PASS defined: only the two sections marked "both passes" are seen then, and the STMPC_G_* macros below select
+// where an episode's parameters come from.  In the first pass they expand to the plain expressions the production kernels have always had (a.p, a.band,
+// p.obst_min_s, ...), so those kernels are compiled from the same tokens as before.
+#if defined(STMPC_KERNELS_GROUPED_PASS) || !defined(STMPC_KERNELS_HPP)
+#ifndef STMPC_KERNELS_GROUPED_PASS
+#define STMPC_KERNELS_HPP
+#define STMPC_G_ARGS SolveArgs              /* argument struct of the solve kernels */
+#define STMPC_G_P(a, e) a.p                 /* DevP of episode e */
+#define STMPC_G_BAND(a, e) a.band
+#define STMPC_G_BAND2(a, e) a.band2_mult
+#define STMPC_G_PRED_ARG                    /* extra kernel argument of k_predict */
+#define STMPC_G_PRED_GUIDE(e) guide_tab     /* table of the guided attempt for episode e */
+#define STMPC_G_PRED_OBST_MIN_S(e) p.obst_min_s
+#define STMPC_G_PRED_MIN_ALLOWED(e) p.min_allowed
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -314,8 +329,10 @@ __device__ __forceinline__ double left_neighbour(double v, int lane) {
         return __shfl(v, lane > 0 ? lane - 1 : 0, 64);
 }
 
+#endif  // first pass only
+// ---- both passes: k_predict
 template <int KMAX>
-__global__ void __launch_bounds__(128) k_predict(DevP p, int N, int Kmax, const double *__restrict__ ego,
+__global__ void __launch_bounds__(128) k_predict(DevP p, STMPC_G_PRED_ARG int N, int Kmax, const double *__restrict__ ego,
                                                  const int *__restrict__ k_count,
                                                  const double *__restrict__ other_x,
                                                  const double *__restrict__ other_v, CarTab tab,
@@ -397,7 +414,7 @@ __global__ void __launch_bounds__(128) k_predict(DevP p, int N, int Kmax, const 
             int d = i1 - i2; d = d < -guide_D ? -guide_D : (d > guide_D ? guide_D : d);
             if (i1 - d < 0) d = i1;
             if (i1 - d > guide_imax) d = i1 - guide_imax;
-            grow = guide_tab + ((size_t)i1 * (2 * guide_D + 1) + (size_t)(d + guide_D)) * (size_t)(p.H - 1);
+            grow = STMPC_G_PRED_GUIDE(e0 + el0) + ((size_t)i1 * (2 * guide_D + 1) + (size_t)(d + guide_D)) * (size_t)(p.H - 1);
             g_ok = true;
         }
         if (prio_key && wr && c == 0) {
@@ -533,7 +550,7 @@ __global__ void __launch_bounds__(128) k_predict(DevP p, int N, int Kmax, const 
             const double dl = (st_s + p.ds) - st_s;
             const double o = xs_l[el][tt][c] - (-51.0);                            // control.py:388-389
             const bool inb = tin && c < ke;
-            const bool below = inb && o < p.obst_min_s;                            // st.py:46-47 break: this vehicle and every later one
+            const bool below = inb && o < STMPC_G_PRED_OBST_MIN_S(e);                            // st.py:46-47 break: this vehicle and every later one
             const u64 bm = (__ballot(below) >> grp) & gmask;
             const bool stop = (bm & ((2ull << c) - 1ull)) != 0ull;
             const bool valid = inb && !stop && !(o > s_last + p.car_length);       // st.py:48-49 continue
@@ -557,7 +574,7 @@ __global__ void __launch_bounds__(128) k_predict(DevP p, int N, int Kmax, const 
                     const int gc = gcell_l[el][tt];
                     const double g_sn = st_s + (double)gc * dl;
                     const double gd = __builtin_fmin(fabs(g_sn - front), fabs(g_sn - back));
-                    if ((gc >= imin && gc < imax) || gd < p.min_allowed) bad[el] = true;
+                    if ((gc >= imin && gc < imax) || gd < STMPC_G_PRED_MIN_ALLOWED(e)) bad[el] = true;
                 }
             }
             if (tin && c == 0) {
@@ -582,6 +599,7 @@ __global__ void __launch_bounds__(128) k_predict(DevP p, int N, int Kmax, const 
     }
 }
 
+#ifndef STMPC_KERNELS_GROUPED_PASS
 // One-step prediction exposed through the C-ABI (stmpc_predict_batch).
 template <int KMAX>
 __global__ void __launch_bounds__(64) k_predict_step(DevP p, int mode, int N, int Kmax,
@@ -785,6 +803,19 @@ struct Mem {
     }
 };
 
+// Solver groups: one batch of G groups of n_per_group consecutive episodes, each under its own parameters from a device table (row episode / n_per_group).
+struct GroupP {
+    DevP p;
+    double band, band2_mult;    // SolveArgs::band / ::band2_mult of this group's weights
+    long long guide_off;        // where this group's table of the guided attempt starts in k_predict's guide_tab (bytes)
+};
+struct GroupTab { const GroupP *__restrict__ groups; int n_per_group; };
+// SolveArgs of a grouped launch: a.p holds what every group shares (any group's DevP serves)
+struct SolveArgsG : SolveArgs { GroupTab g; };
+// (the episode of a solve workgroup is uniform: said so that the group's row is addressed from scalar registers)
+__device__ __forceinline__ const GroupP &group_of(const SolveArgsG &a, int e) { return a.g.groups[__builtin_amdgcn_readfirstlane(e) / a.g.n_per_group]; }
+#endif  // first pass only
+// ---- both passes: the lattice DP, from the per-episode constants to k_solve
 // Per-episode constants shared by the passes of one solve.
 struct Ep {
     double start_s, s1, delta, v0, a0;
@@ -905,11 +936,11 @@ template <int NWX> struct WgShape {
     static constexpr int W = (NWX == 4) ? 2048 : 8192, PW = (NWX == 4) ? 1024 : 4096;
 };
 template <bool USE_LDS, bool GRID, bool FASTDIV, int KT, int MODE, int FANMAX, bool S1GEN, int RES = 0, int NWX = STMPC_MAXWAVES>
-__device__ int dp_pass(const SolveArgs &a, const Ep &ep, WgShared &sh, u64 *cost, unsigned *hist, double *pen,
+__device__ int dp_pass(const STMPC_G_ARGS &a, const Ep &ep, WgShared &sh, u64 *cost, unsigned *hist, double *pen,
                        u16 *list, int *chunk_cnt, const double *ltab_e, const int *ltab_w, const int *ltab_n,
                        u64 ubits, double band, bool hardsoft, PassOut &out, const int t_start = 0, const int tube_w = 0) {
     typedef Mem<USE_LDS> M;
-    const DevP &p = a.p;
+    const DevP &p = STMPC_G_P(a, ep.e);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -1657,9 +1688,9 @@ __device__ int dp_pass(const SolveArgs &a, const Ep &ep, WgShared &sh, u64 *cost
 // its bound the reference's own cost in most episodes.
 // cells: [2][256] u64, penf: [256] float (LDS).  sh.path holds the guide.  Returns true with out.best_bits / out.nodes set if a complete path was found.
 template <bool FASTDIV, bool S1GEN>
-__device__ __forceinline__ bool tube_pass(const SolveArgs &a, const Ep &ep, WgShared &sh, u64 *cells, float *penf, PassOut &out) {
+__device__ __forceinline__ bool tube_pass(const STMPC_G_ARGS &a, const Ep &ep, WgShared &sh, u64 *cells, float *penf, PassOut &out) {
     typedef Mem<true> M;
-    const DevP &p = a.p;
+    const DevP &p = STMPC_G_P(a, ep.e);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int H = p.H, S = ep.S, e = __builtin_amdgcn_readfirstlane(ep.e), w = a.tube_w, TW = 2 * w + 1;
     const double start_s = ep.start_s, delta = ep.delta, dt = p.dt;
@@ -1674,8 +1705,8 @@ __device__ __forceinline__ bool tube_pass(const SolveArgs &a, const Ep &ep, WgSh
     const double K = nk.K, invK = nk.invK;
     const bool quad = nk.ok;
     const float Kf = (float)K, stepf = (float)delta;
-    const float bandf = (float)a.band;
-    const double rad = quad ? (double)__builtin_amdgcn_sqrtf((float)(a.band * invK)) : 0.0;       // (the band is constant here: a tube layer never exceeds band_cap nodes)
+    const float bandf = (float)STMPC_G_BAND(a, ep.e);
+    const double rad = quad ? (double)__builtin_amdgcn_sqrtf((float)(STMPC_G_BAND(a, ep.e) * invK)) : 0.0;       // (the band is constant here: a tube layer never exceeds band_cap nodes)
     u64 *cur = cells, *nxt = cells + 256;
     M::barrier();                        // previous users of the arrays are done
     M::st64(&cur[tid], (tid == w) ? 0ull : INF_BITS);          // layer 0: cell 0 (the guide's cell of layer 0) at cost 0, no history
@@ -1821,9 +1852,9 @@ __device__ __forceinline__ bool tube_pass(const SolveArgs &a, const Ep &ep, WgSh
 #define STMPC_BAND_W 1536
 #define STMPC_BAND_SLOTS (STMPC_BAND_W / 256)
 template <bool FASTDIV, bool S1GEN>
-__device__ __forceinline__ int band_pass(const SolveArgs &a, const Ep &ep, WgShared &sh, unsigned char *lds /* >= 30 KB */, const double band, const bool hardsoft, PassOut &out) {
+__device__ __forceinline__ int band_pass(const STMPC_G_ARGS &a, const Ep &ep, WgShared &sh, unsigned char *lds /* >= 30 KB */, const double band, const bool hardsoft, PassOut &out) {
     typedef Mem<true> M;
-    const DevP &p = a.p;
+    const DevP &p = STMPC_G_P(a, ep.e);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int H = p.H, S = ep.S, e = __builtin_amdgcn_readfirstlane(ep.e);      // (uniform by construction; said so that the vehicle rows are fetched by scalar loads)
     const double start_s = ep.start_s, delta = ep.delta, dt = p.dt;
@@ -2010,9 +2041,9 @@ __device__ __forceinline__ int band_pass(const SolveArgs &a, const Ep &ep, WgSha
 
 // Solve one episode with one workgroup.  Returns 0 ok, 1 window overflow (workgroup-uniform).
 template <bool USE_LDS, bool GRID, bool FASTDIV, int KT, int FANMAX, bool S1GEN, int RES = 0, int NWX = STMPC_MAXWAVES>
-__device__ int solve_episode(const SolveArgs &a, int e, int slot, WgShared &sh, u64 *cost, unsigned *hist,
+__device__ int solve_episode(const STMPC_G_ARGS &a, int e, int slot, WgShared &sh, u64 *cost, unsigned *hist,
                              double *pen, u16 *list, int *chunk_cnt, double *ltab_e, int *ltab_w, int *ltab_n, const int phase) {
-    const DevP &p = a.p;
+    const DevP &p = STMPC_G_P(a, e);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int W = WgShape<NWX>::fixed ? WgShape<NWX>::W : a.W, WM = W - 1;
@@ -2098,7 +2129,7 @@ __device__ int solve_episode(const SolveArgs &a, int e, int slot, WgShared &sh, 
             for (int att = guided ? -1 : 0; att < 2 && ubits == INF_BITS; ++att) {
                 if constexpr (USE_LDS && NWX == 4 && FANMAX != 9) {
                     if (att >= 0 && a.band_dense) {
-                        const int rb = band_pass<FASTDIV, S1GEN>(a, ep, sh, (unsigned char *)cost, att == 0 ? a.band : a.band * a.band2_mult, att == 0, out);
+                        const int rb = band_pass<FASTDIV, S1GEN>(a, ep, sh, (unsigned char *)cost, att == 0 ? STMPC_G_BAND(a, e) : STMPC_G_BAND(a, e) * STMPC_G_BAND2(a, e), att == 0, out);
                         bn += out.nodes;
                         if (rb == 0) { ubits = out.best_bits; break; }
                         if (rb == 1) continue;             // no complete path under this band: next attempt
@@ -2106,7 +2137,7 @@ __device__ int solve_episode(const SolveArgs &a, int e, int slot, WgShared &sh, 
                     }
                 }
                 rc = dp_pass<USE_LDS, GRID, FASTDIV, KT, PASS_BOUND, FANMAX, S1GEN, 0, NWX>(a, ep, sh, cost, hist, pen, list, chunk_cnt, ltab_e, ltab_w, ltab_n, INF_BITS,
-                                                                                   att <= 0 ? a.band : a.band * a.band2_mult, att <= 0, out, 0, att < 0 ? a.tube_w : 0);
+                                                                                   att <= 0 ? STMPC_G_BAND(a, e) : STMPC_G_BAND(a, e) * STMPC_G_BAND2(a, e), att <= 0, out, 0, att < 0 ? a.tube_w : 0);
                 bn += out.nodes;
                 if (rc != 0) { if (att < 0) { rc = 0; continue; } break; }      // (a tube that does not fit the window: go on with the ordinary attempts)
                 if (out.best_t == H - 1) { ubits = out.best_bits; if (att < 0 && tid == 0) atomicAdd(&a.counters[STMPC_CNT_GUIDED], 1u); break; }
@@ -2282,7 +2313,7 @@ __host__ __device__ inline size_t stmpc_tab_bytes(int H, int KT) { return (size_
 // Persistent kernel: workgroups of NW waves pull episodes until the tier's queue is drained.
 template <bool USE_LDS, bool GRID, bool FASTDIV, int KT, int FANMAX, bool S1GEN, int RES = 0, int NWX = STMPC_MAXWAVES>
 // (the standard second window -- NWX 88: eight waves, 147 KB of LDS -- is alone on its compute unit, two waves per SIMD: it may use 256 VGPRs)
-__global__ void __launch_bounds__(512, ((FANMAX <= 12 && NWX != 88) ? STMPC_MIN_WAVES : 2)) k_solve(SolveArgs a) {
+__global__ void __launch_bounds__(512, ((FANMAX <= 12 && NWX != 88) ? STMPC_MIN_WAVES : 2)) k_solve(STMPC_G_ARGS a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ WgShared sh;
     const int tid = threadIdx.x;
@@ -2424,6 +2455,7 @@ __global__ void __launch_bounds__(512, ((FANMAX <= 12 && NWX != 88) ? STMPC_MIN_
     }
 }
 
+#ifndef STMPC_KERNELS_GROUPED_PASS
 // Heaviest-first order of the episodes for the exact phase (LPT): counting sort of the work estimates into
 // 64 logarithmic buckets, one workgroup.
 __global__ void __launch_bounds__(1024) k_order(int N, const unsigned *__restrict__ proxy, int *__restrict__ order) {
@@ -2501,3 +2533,5 @@ __global__ void k_probe(int op, const double *a, const double *b, double *out, i
 }
 
 }  // namespace stmpc
+#endif  // first pass only
+#endif  // STMPC_KERNELS_HPP

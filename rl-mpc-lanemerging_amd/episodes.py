@@ -101,12 +101,14 @@ def sim_cfgs(traffic, seed=0, max_episode_length=100.0, route="lane"):
     return _capi.SimCfgTable(cfgs)
 
 
-def _check_traffic(n, traffic, policy):
+def _check_traffic(n, traffic, policy, g_max=None):
     """(G, n_per_group) for ``n`` environments in the groups of ``traffic``; ValueError when they do not split or do not coincide with the
-    members of a population ``policy``.  Touches no device."""
+    members of a population ``policy``.  ``g_max``: the most groups the world takes (default ``SIM_GROUPS_MAX``; a solver-groups run:
+    ``SOLVER_GROUPS_MAX``).  Touches no device."""
     G = len(traffic)
-    if G < 1 or G > _capi.SIM_GROUPS_MAX:
-        raise ValueError("traffic must name 1 ... %d groups, not %d" % (_capi.SIM_GROUPS_MAX, G))
+    g_max = _capi.SIM_GROUPS_MAX if g_max is None else g_max
+    if G < 1 or G > g_max:
+        raise ValueError("traffic must name 1 ... %d groups, not %d" % (g_max, G))
     if int(n) < G or int(n) % G:
         raise ValueError("n = %d environments do not split into %d traffic groups of equal size" % (n, G))
     npg = int(n) // G
@@ -132,6 +134,21 @@ def _check_control(n, control, traffic, policy):
         raise ValueError("the population has %d members of %d environments, the control %d groups of %d: cell c pairs member c with control c, so they must coincide"
                          % (policy.P, policy.n_per_member, C, npc))
     return C, npc
+
+
+def _check_solver(n, solver, traffic, controller):
+    """(G, n_per_cell) for ``n`` environments in the solver groups of ``solver``; ValueError when the controller is not "st", when they do not split,
+    or when they do not coincide with the traffic groups (cell c pairs traffic c with solver c).  Touches no device."""
+    if controller != "st":
+        raise ValueError("solver groups are settings of the ST controller, not of %r" % (controller,))
+    G = len(solver)
+    if G < 1 or G > _capi.SOLVER_GROUPS_MAX:
+        raise ValueError("solver must name 1 ... %d groups, not %d" % (_capi.SOLVER_GROUPS_MAX, G))
+    if int(n) < G or int(n) % G:
+        raise ValueError("n = %d environments do not split into %d solver groups of equal size" % (n, G))
+    if traffic is not None and len(traffic) != G:
+        raise ValueError("the traffic has %d groups, the solver %d: cell c pairs traffic c with solver c, so they must coincide" % (len(traffic), G))
+    return G, int(n) // G
 
 
 class EpisodeRunner:
@@ -160,11 +177,23 @@ class EpisodeRunner:
     control c: the counts and slice sizes must coincide.  Give the traffic groups one ``seed`` for common random numbers across the cells
     (``grid_search_combined``).
 
+    ``solver`` (ST controller only): None (one ``Params`` from the global ``Settings``) or a list of dicts as ``st.param_cfgs`` takes: the environments
+    are then ``len(solver)`` solver groups of equal size, group g controlled under its own V/A/J/D_WEIGHT, MIN_ALLOWED_DISTANCE and CRASH_MIN_S
+    (``stmpc_st_control_groups_device``) and its closest-distance statistics gated by its own CRASH_MIN_S
+    (``stmpc_solver_groups_sim_step_device``), bit-identical to a lone runner of that many environments with ``Settings`` set to the cell; ``result()``
+    gains ``out["solver_group"]``.  With ``traffic`` too, cell c pairs traffic c with solver c and the counts must coincide; without it every cell
+    gets the default traffic under ``vec_env.episode_seed(seed, c)``.  Give the traffic groups one ``seed`` for common random numbers
+    (``grid_search_st``).  Up to ``_capi.SOLVER_GROUPS_MAX`` (512) cells fit one runner (``stmpc_solver_groups_sim_init_device``).  The world of
+    such a run always has one traffic group per cell, so ``result()`` holds ``out["traffic_group"]`` (equal to ``solver_group``) even when no
+    ``traffic`` was given; with ``record``, the report's settings text (``ST_DESCRIPTION``) is the global ``Settings``', not a cell's -- take a
+    cell's settings from ``solver[c]``.
+
     ``controller="first_step"``: ``st.do_conditional_st_based_on_first_step`` (st.py:805-814, ``first_step.py``) behind ``policy`` -- per tick the
     view, ONE policy evaluation, ``control.get_ego_speed_from_jerk`` of its jerk, ``stmpc_first_step_device``, the world step.  ``policy`` (an actor or
     a population) and ``traffic`` work as for "combined"; ``control`` is refused (its keys are settings of the combined controller)."""
 
-    def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, record=None, traffic=None, control=None):
+    def __init__(self, n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, record=None, traffic=None, control=None,
+                 solver=None):
         import torch
         self.torch = torch
         if controller not in ("st", "combined", "first_step"):
@@ -174,12 +203,22 @@ class EpisodeRunner:
             raise ValueError("n = %d, the population of policies was built for %d x %d = %d environments" % (n, policy.P, policy.n_per_member, policy.n))
         self.traffic = list(traffic) if traffic is not None else None
         self.control = list(control) if control is not None else None
+        self.solver = [dict(c) for c in solver] if solver is not None else None
+        self.solver_params = None
+        if self.solver is not None:
+            from . import st
+            self.n_solver, self.n_per_solver = _check_solver(n, self.solver, self.traffic, controller)
+            self.solver_params = st.param_cfgs(self.solver)
+            if self.traffic is None:               # (the grouped step serves a world of traffic groups: one per cell, of the default traffic)
+                self.traffic = [{"BASE_TRAFFIC_INTERVAL": getattr(Settings, "BASE_TRAFFIC_INTERVAL", 1.2), "OTHER_CAR_SPEED": getattr(Settings, "OTHER_CAR_SPEED", 7.0)}
+                                for _ in self.solver]
         if self.control is not None and controller != "combined":
             raise ValueError("control groups are settings of the combined controller, not of %r" % (controller,))
         if controller == "first_step" and policy is None:
             raise ValueError("the first-step controller shields a policy's proposal: give one (an actor.DDPGActor or an actor.ActorPopulation)")
         self.C, self.n_per_cell = _check_control(n, self.control, self.traffic, policy) if self.control is not None else (0, 0)
-        self.G, self.n_per_group = _check_traffic(n, self.traffic, policy) if self.traffic is not None else (0, 0)
+        self.G, self.n_per_group = (_check_traffic(n, self.traffic, policy, _capi.SOLVER_GROUPS_MAX if self.solver is not None else None)
+                                    if self.traffic is not None else (0, 0))
         self.n, self.kmax, self.controller, self.policy = int(n), int(kmax), controller, policy
         self.cfgs = sim_cfgs(self.traffic, seed, max_episode_length) if self.traffic is not None else None
         self.ctx = ctx or _capi.default_context()
@@ -206,7 +245,9 @@ class EpisodeRunner:
         self.last_rl = torch.ones(n, dtype=torch.int32, device=dev)
         self.d_status = z(n, dtype=torch.int32)
         self.ticks_done = 0
-        if self.cfgs is not None:
+        if self.solver is not None:
+            self.ctx.sim_init_solver_groups(self.cfgs, self.n_per_group)          # (one traffic group per cell: up to SOLVER_GROUPS_MAX of them)
+        elif self.cfgs is not None:
             self.ctx.sim_init_groups(self.cfgs, self.n_per_group)
         else:
             self.ctx.sim_init(self.cfg, n)
@@ -224,9 +265,14 @@ class EpisodeRunner:
         ctx.sim_view(self.cfg, n, kmax, self.d_ego5.data_ptr(), self.d_k.data_ptr(), self.d_ox.data_ptr(), self.d_ov.data_ptr(),
                      self.d_oa.data_ptr() if self.controller != "st" else 0)
         if self.controller == "st":
-            ctx.st_control_batch_device(self.params, self.tick_length, n, kmax, self.d_ego5.data_ptr(), self.d_k.data_ptr(), self.d_ox.data_ptr(), self.d_ov.data_ptr(),
-                                        self.d_path.data_ptr(), self.d_bt.data_ptr(), self.d_cost.data_ptr(), self.d_speed.data_ptr(), self.d_fine.data_ptr(),
-                                        self.d_fine_len.data_ptr(), 0)
+            if self.solver_params is not None:
+                ctx.st_control_groups_device(self.solver_params, self.n_per_solver, self.tick_length, n, kmax, self.d_ego5.data_ptr(), self.d_k.data_ptr(),
+                                             self.d_ox.data_ptr(), self.d_ov.data_ptr(), self.d_path.data_ptr(), self.d_bt.data_ptr(), self.d_cost.data_ptr(),
+                                             self.d_speed.data_ptr(), self.d_fine.data_ptr(), self.d_fine_len.data_ptr(), 0)
+            else:
+                ctx.st_control_batch_device(self.params, self.tick_length, n, kmax, self.d_ego5.data_ptr(), self.d_k.data_ptr(), self.d_ox.data_ptr(),
+                                            self.d_ov.data_ptr(), self.d_path.data_ptr(), self.d_bt.data_ptr(), self.d_cost.data_ptr(), self.d_speed.data_ptr(),
+                                            self.d_fine.data_ptr(), self.d_fine_len.data_ptr(), 0)
             cmd = self.d_speed
         else:
             if self.controller == "first_step":
@@ -246,7 +292,9 @@ class EpisodeRunner:
         if self.recorder is not None:
             # the state before control, as the reference appends it to state_history (control.py:280-289), with this tick's command
             self.recorder.tick(n, kmax, self.d_ego5, self.d_k, self.d_ox, self.d_ov, self.d_oa, cmd, d["takeover"] if self.controller != "st" else None)
-        if self.cfgs is not None:
+        if self.solver_params is not None:
+            ctx.sim_step_solver_groups(self.solver_params, self.n_per_solver, n, cmd.data_ptr())
+        elif self.cfgs is not None:
             ctx.sim_step_groups(self.params, n, cmd.data_ptr())
         else:
             ctx.sim_step(self.params, self.cfg, n, cmd.data_ptr())
@@ -271,6 +319,8 @@ class EpisodeRunner:
             out["traffic_group"] = np.arange(self.n) // self.n_per_group
         if self.control is not None:
             out["control_group"] = np.arange(self.n) // self.n_per_cell
+        if self.solver is not None:
+            out["solver_group"] = np.arange(self.n) // self.n_per_solver
         if self.recorder is not None:
             from . import report
             out["report"] = report.Report.from_result(out, self.recorder.read())
@@ -298,7 +348,7 @@ def stats_columns(status, ticks, acc, tick_length):
 
 
 def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max_episode_length=100.0, check_every=16, max_ticks=None, record=None, traffic=None,
-                 control=None):
+                 control=None, solver=None):
     """Run ``n`` merge episodes to the end (or for ``max_ticks`` ticks); returns the per-episode columns of the reference's stats report
     (``crashed``, ``merged``, ``mean_speed``, ``max_speed``, ``mean_abs_jerk``, ``closest_distance``, ``mean_closest_distance``,
     ``time_taken``, ``time_to_merge`` (NaN unless merged)) plus ``ticks``, ``status`` (0 still running), ``ego4`` and ``percent_st``
@@ -307,8 +357,8 @@ def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max
     controller: "st" = ``st.do_st_control`` every tick (TASK "ST"); "combined" = ``do_combined_control`` with ``policy``
     (see ``combined.decide_batch_device``); "first_step" = ``do_conditional_st_based_on_first_step`` behind ``policy`` (``first_step.py``).  record: None, or a ``report.RecorderConfig`` -- the result then holds ``report`` (``report.Report``),
     see ``EpisodeRunner``.  traffic: None, or the traffic groups of ``EpisodeRunner``; the tick limit is then the largest group's ``max_ticks + 1``.
-    control: None, or the controller groups of ``EpisodeRunner``."""
-    r = EpisodeRunner(n, seed, controller, policy, ctx, kmax, max_episode_length, record, traffic, control)
+    control: None, or the controller groups of ``EpisodeRunner``.  solver: None, or the solver groups of ``EpisodeRunner``."""
+    r = EpisodeRunner(n, seed, controller, policy, ctx, kmax, max_episode_length, record, traffic, control, solver)
     limit = r.max_ticks + 1 if max_ticks is None else min(int(max_ticks), r.max_ticks + 1)
     for tick in range(limit):
         r.tick()
@@ -319,7 +369,7 @@ def run_episodes(n, seed=0, controller="st", policy=None, ctx=None, kmax=32, max
 
 def summary(stats):
     """Column means as the reference's report rows hold them (stats.py:145-158)."""
-    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4", "report", "member", "traffic_group", "control_group")}
+    return {k: float(np.nanmean(v)) for k, v in stats.items() if k not in ("ticks", "status", "ego4", "report", "member", "traffic_group", "control_group", "solver_group")}
 
 
 def summary_by_member(stats, P):
@@ -350,6 +400,39 @@ def summary_by_control(stats, C):
         raise ValueError("%d environments do not split into %d controller groups" % (n, C))
     npc = n // C
     return [summary({k: v[c * npc:(c + 1) * npc] for k, v in stats.items() if k != "report"}) for c in range(C)]
+
+
+def summary_by_solver(stats, G):
+    """``summary`` of each solver group's environments: G dicts, group g from rows [g * n / G, (g + 1) * n / G) of every column (the result of a
+    run with ``solver``)."""
+    n = len(stats["status"])
+    if G < 1 or n % G:
+        raise ValueError("%d environments do not split into %d solver groups" % (n, G))
+    npg = n // G
+    return [summary({k: v[g * npg:(g + 1) * npg] for k, v in stats.items() if k != "report"}) for g in range(G)]
+
+
+def grid_search_st(n_per_cell, seed=0, traffic=None, cells=None, common_random_numbers=True, ctx=None, kmax=16, max_episode_length=100.0, max_ticks=None,
+                   check_every=16, record=None):
+    """The reference's ``main.do_grid_search_st`` (main.py:43-59: one TASK "ST" process per cell) in ONE run: the ST controller on the traffic type
+    ``traffic`` (as ``sim_cfgs`` takes one group; default: the traffic of ``Settings``), once per cell of ``cells`` (default ``st.grid_search_cells()``,
+    288 dicts as ``st.param_cfgs`` takes them), ``n_per_cell`` episodes each, every cell a solver group and a traffic group of one runner.
+    ``common_random_numbers``: every cell's traffic group gets the same seed (``seed``), so all cells face the same traffic draws and start speeds
+    and differ by the solver's settings alone; False: cell c's seed is ``vec_env.episode_seed(seed, c)``.
+    Returns ``{"cells": [{"settings": cell, "summary": ``summary`` dict}, ...], "stats": the raw result}``."""
+    from . import st, vec_env
+    cells = [dict(c) for c in (cells if cells is not None else st.grid_search_cells())]
+    if int(n_per_cell) < 1:
+        raise ValueError("n_per_cell must be positive")
+    st.param_cfgs(cells)                                                # (validates the keys and the count before anything is built)
+    base = traffic_settings(traffic) if traffic is not None else {"BASE_TRAFFIC_INTERVAL": getattr(Settings, "BASE_TRAFFIC_INTERVAL", 1.2),
+                                                                   "OTHER_CAR_SPEED": getattr(Settings, "OTHER_CAR_SPEED", 7.0)}
+    cell_traffic = [dict(base, seed=int(seed) if common_random_numbers else vec_env.episode_seed(seed, c)) for c in range(len(cells))]
+    ctx = ctx if ctx is not None else _capi.default_context()
+    stats = run_episodes(len(cells) * int(n_per_cell), seed=seed, controller="st", ctx=ctx, kmax=kmax, max_episode_length=max_episode_length,
+                         check_every=check_every, max_ticks=max_ticks, record=record, traffic=cell_traffic, solver=cells)
+    by = summary_by_solver(stats, len(cells))
+    return {"cells": [{"settings": cells[c], "summary": by[c]} for c in range(len(cells))], "stats": stats}
 
 
 def grid_search_combined(model, traffic, n_per_cell, cells=None, seed=0, common_random_numbers=True, ctx=None, kmax=16, max_episode_length=100.0, record=None,

@@ -26,6 +26,48 @@ from .config import Settings
 from .prediction import HighwayState, pack_states  # noqa: F401  (re-export)
 
 
+# Solver groups: the settings main.do_grid_search_st sweeps (main.py:43-59), and the stmpc_params field each one sets
+SOLVER_GROUP_KEYS = {"V_WEIGHT": "v_w", "A_WEIGHT": "a_w", "J_WEIGHT": "j_w", "D_WEIGHT": "d_w", "MIN_ALLOWED_DISTANCE": "min_allowed",
+                     "CRASH_MIN_S": "crash_min_s"}
+SOLVER_GROUPS_MAX = _capi.SOLVER_GROUPS_MAX
+
+
+def param_cfgs(cells, S=Settings):
+    """One ``Params`` per solver group (a ``_capi.ParamsTable`` for the ``stmpc_*_groups`` entries): ``cells`` is a list of dicts, each setting any of
+    ``V_WEIGHT``, ``A_WEIGHT``, ``J_WEIGHT``, ``D_WEIGHT``, ``MIN_ALLOWED_DISTANCE`` and ``CRASH_MIN_S`` over ``S`` (the global ``Settings``, which is
+    read and never written).  ValueError for any other key, for an empty list and for more than ``SOLVER_GROUPS_MAX`` cells."""
+    cells = list(cells)
+    if not 1 <= len(cells) <= SOLVER_GROUPS_MAX:
+        raise ValueError("solver must name 1 ... %d groups, not %d" % (SOLVER_GROUPS_MAX, len(cells)))
+    table = []
+    for cell in cells:
+        if not isinstance(cell, dict):
+            raise ValueError("a solver group is a dict of settings, not %r" % (cell,))
+        unknown = [k for k in cell if k not in SOLVER_GROUP_KEYS]
+        if unknown:
+            raise ValueError("a solver group may set %s, not %s" % (", ".join(SOLVER_GROUP_KEYS), ", ".join(map(str, unknown))))
+        p = _capi.Params.from_settings(S)
+        for key, value in cell.items():
+            setattr(p, SOLVER_GROUP_KEYS[key], float(value))
+        table.append(p)
+    return _capi.ParamsTable(table)
+
+
+def grid_search_cells():
+    """The 288 cells of ``main.do_grid_search_st`` (main.py:43-59) as dicts, in the order of its ``itertools.product`` over ``search_grid``."""
+    import itertools
+    grid = {"V_WEIGHT": [0.5, 1.0], "A_WEIGHT": [0.0, 10.0], "J_WEIGHT": [0.0, 10.0, 50.0], "D_WEIGHT": [0.0, 10.0, 100.0, 1000.0],
+            "MIN_ALLOWED_DISTANCE": [5, 6], "CRASH_MIN_S": [10, 15, 20]}
+    return [dict(zip(grid, values)) for values in itertools.product(*grid.values())]
+
+
+def solve_arrays_groups(groups, n_per_group, ego, k_count, other_x, other_v, ctx=None):
+    """``solve_arrays`` with solver groups: state i under ``groups[i // n_per_group]`` (a ``param_cfgs`` table).  Returns ``solve_arrays``' dict plus
+    ``action_cost[N, 2]``."""
+    ctx = ctx or _capi.default_context()
+    return ctx.solve_batch_groups(groups, n_per_group, ego, k_count, other_x, other_v)
+
+
 def get_range_index(min_s, delta_s, s):
     # st.py:20-22
     return int((s - min_s) / delta_s)
