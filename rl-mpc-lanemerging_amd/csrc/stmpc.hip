@@ -187,11 +187,32 @@ struct stmpc_ctx {
     } s;
     DevBuf ckpt, pool_bp, resume_t, phase_prof, prio_key;
     int pool_cap_override = 0;     // STMPC_POOL=n: checkpoint pool entries (tests: a tiny pool must only cost speed)
-    // combined controller (stmpc_rollout_step_device / stmpc_combined_decide_device): rollout bookkeeping and probe / controller outputs
+    // What a shield controller keeps of "st.do_st_control of the start states" (shield_control): the controller's outputs for its N rows, with the probe's
+    // verdicts, and for the sparse solve the compact batch of the rows that need the controller.  One per controller: each is read back after its call.
+    struct ShieldBufs {
+        DevBuf path, bt, cost, pcrash, speed, fine, fine_len,
+            sel_idx, sel_count, c_ego, c_k, c_ox, c_ov, c_speed, c_fine, c_fine_len;
+        int *host_count = nullptr;  // pinned host word for the number of selected rows
+        ~ShieldBufs() { if (host_count) (void)hipHostFree(host_count); }      // (on the current device, as DevBuf)
+        int ensure(int N, int H) {
+            const size_t n = (size_t)N;
+            TRY(path.ensure(n * H * 4)); TRY(bt.ensure(n * 4)); TRY(cost.ensure(n * 8)); TRY(pcrash.ensure(n * 4));
+            TRY(speed.ensure(n * 8)); TRY(fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(fine_len.ensure(n * 4));
+            return STMPC_OK;
+        }
+        // the selection and the compact batch, sized once for all rows: no allocation between the launches of a tick
+        int ensure_compact(int N, int Kalloc) {
+            const size_t n = (size_t)N;
+            TRY(sel_idx.ensure(n * 4)); TRY(sel_count.ensure(4));
+            TRY(c_ego.ensure(n * 5 * 8)); TRY(c_k.ensure(n * 4)); TRY(c_ox.ensure(n * Kalloc * 8)); TRY(c_ov.ensure(n * Kalloc * 8));
+            TRY(c_speed.ensure(n * 8)); TRY(c_fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(c_fine_len.ensure(n * 4));
+            return STMPC_OK;
+        }
+    };
+    // combined controller (stmpc_rollout_step_device / stmpc_combined_decide_device): rollout bookkeeping, the probe's states, the controller's outputs
     struct Combined {
-        DevBuf live, hist_len, crash_pred, have_test, sel, rollout_s, test_ego, test_ox, test_ov, probe_ego, probe_ox, probe_ov,
-            path, bt, cost, pcrash, speed, fine, fine_len,
-            sel_idx, sel_count, c_ego, c_k, c_ox, c_ov, c_speed, c_fine, c_fine_len;      // sparse controller solve: the states that need st.do_st_control
+        DevBuf live, hist_len, crash_pred, have_test, sel, rollout_s, test_ego, test_ox, test_ov, probe_ego, probe_ox, probe_ov;
+        ShieldBufs sh;
         int N = 0, K = 0, R = 0;
         // controller groups (stmpc_combined_groups_set): `groups` holds C CCfg; C = 0: no table.  `grouped`: the rollout in the context was begun by
         // stmpc_rollout_step_groups_device (R is then the largest group's rollout_length, the row stride of rollout_s less one)
@@ -200,7 +221,6 @@ struct stmpc_ctx {
         int C = 0, n_per_group = 0, Rmax = 0, n_test = 0, any_strict = 0, sparse = 0;
         double tick = 0;
         bool grouped = false;
-        int *host_count = nullptr;  // pinned host word for the number of those states
         int64_t ticks = 0, control_solves = 0;      // decisions taken / controller solves run for them (stmpc_combined_counts)
         int ensure(int n_, int k_, int r_) {        // the rollout's bookkeeping (step 1)
             const size_t n = (size_t)n_;
@@ -213,13 +233,13 @@ struct stmpc_ctx {
             return CCState{live.as<int>(), hist_len.as<int>(), crash_pred.as<int>(), have_test.as<int>(), sel.as<double>(), rollout_s.as<double>(),
                            test_ego.as<double>(), test_ox.as<double>(), test_ov.as<double>()};
         }
+        void drop_grouped() { if (grouped) { grouped = false; N = 0; } }       // (a grouped rollout of a former table cannot be continued or decided)
     } cc;
     // first-step shield controller (stmpc_first_step_device): the predicted states, the probe's and the controller's outputs
     struct FirstStep {
-        DevBuf next_ego, next_ox, next_ov, crashed, pcrash, path, bt, cost, speed, fine, fine_len, takeovers,
-            sel_idx, sel_count, c_ego, c_k, c_ox, c_ov, c_speed, c_fine, c_fine_len;      // sparse controller solve, as Combined's
+        DevBuf next_ego, next_ox, next_ov, crashed, takeovers;
+        ShieldBufs sh;
         int N = 0, K = 0;           // shape of the last call (stmpc_first_step reads the predicted states back)
-        int *host_count = nullptr;  // pinned host word for the number of taken-over states
         int64_t decisions = 0, control_solves = 0;      // stmpc_first_step_counts (the takeovers are counted on the device: `takeovers`, one 64-bit word)
     } fs;
     // batched episode simulator (stmpc_sim_*)
@@ -489,8 +509,6 @@ int stmpc_create(stmpc_ctx **out, int device) {
 void stmpc_destroy(stmpc_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);       // (the device buffers are freed by their destructors, on this device)
-    if (c->cc.host_count) (void)hipHostFree(c->cc.host_count);
-    if (c->fs.host_count) (void)hipHostFree(c->fs.host_count);
     if (c->h_overflow) (void)hipHostFree(c->h_overflow);
     if (c->main_masked) (void)hipStreamDestroy(c->main_masked);
     if (c->aux_reserved) (void)hipStreamDestroy(c->aux_reserved);
@@ -579,11 +597,30 @@ double q_smallest_sqrt_ge(double m) {
     return q;
 }
 
+// the lattice's time layers: the range every kernel is built for, and a parameter set's count
+bool bad_layers(int H) { return H < 2 || H > STMPC_H_LIMIT; }
+int num_layers(const stmpc_params *p, int *H) {
+    *H = stmpc_num_t(p);
+    return bad_layers(*H) ? fail(STMPC_EINVAL, "number of time layers must be in [2, 64]") : STMPC_OK;
+}
+
+// How the host-pointer batch entries open: the batch's shape, the state arrays (`outs`: the entry's own required outputs are all there), each state's
+// vehicle count, the context's device.  An empty batch passes untouched: the entry returns at once.
+int host_batch_begin(stmpc_ctx *c, int N, int Kmax, const double *ego, const int32_t *k, const double *ox, const double *ov, bool outs) {
+    TRY(check_batch(N, Kmax));
+    if (N == 0) return STMPC_OK;
+    if (!ego || !k || !outs) return fail(STMPC_EINVAL, "NULL host pointer");
+    if (Kmax > 0 && (!ox || !ov)) return fail(STMPC_EINVAL, "NULL host pointer (other_x/other_v)");
+    TRY(check_counts(N, Kmax, k));
+    HIPCHK(hipSetDevice(c->device));
+    return STMPC_OK;
+}
+
 int make_devp(const stmpc_params *p, DevP *d) {
     if (!p) return fail(STMPC_EINVAL, "params is NULL");
     if (!(p->ds > 0) || !(p->dt > 0)) return fail(STMPC_EINVAL, "ds and dt must be positive");
-    int H = stmpc_num_t(p);
-    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
+    int H;
+    TRY(num_layers(p, &H));
     memset(d, 0, sizeof *d);
     d->future_s = p->future_s; d->ds = p->ds;
     double tv[STMPC_MAXH];
@@ -1284,14 +1321,10 @@ int stmpc_solve_batch(stmpc_ctx *c, const stmpc_params *p, int N, int Kmax, cons
                       const double *ox, const double *ov, int32_t *path, int32_t *bt, double *cost, double *pd,
                       int32_t *crash) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    TRY(check_batch(N, Kmax));
+    TRY(host_batch_begin(c, N, Kmax, ego, k, ox, ov, path && bt && cost));
     if (N == 0) return STMPC_OK;
-    if (!ego || !k || !path || !bt || !cost) return fail(STMPC_EINVAL, "NULL host pointer");
-    if (Kmax > 0 && (!ox || !ov)) return fail(STMPC_EINVAL, "NULL host pointer (other_x/other_v)");
-    TRY(check_counts(N, Kmax, k));
-    HIPCHK(hipSetDevice(c->device));
-    int H = stmpc_num_t(p);
-    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
+    int H;
+    TRY(num_layers(p, &H));
     auto &s = c->s;
     const size_t n = (size_t)N;
     TRY(s.path.ensure(n * H * 4)); TRY(s.bt.ensure(n * 4)); TRY(s.cost.ensure(n * 8)); TRY(s.pd.ensure(n * H * 8)); TRY(s.crash.ensure(n * 4));
@@ -1311,7 +1344,7 @@ int stmpc_solve_grid(stmpc_ctx *c, const uint8_t *obstacles, const double *s_val
                      double min_allowed, double *s_sequence_out) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (!obstacles || !s_values || !t_values || !distances || !s_sequence_out) return fail(STMPC_EINVAL, "NULL host pointer");
-    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "num_t must be in [2, 64]");
+    if (bad_layers(H)) return fail(STMPC_EINVAL, "num_t must be in [2, 64]");
     if (S < 2 || S > STMPC_S_LIMIT) return fail(STMPC_EINVAL, "num_s must be in [2, 65000]");
     HIPCHK(hipSetDevice(c->device));
     DevP dp;
@@ -1582,14 +1615,10 @@ int stmpc_st_control_batch(stmpc_ctx *c, const stmpc_params *p, double tick, int
                            const int32_t *k, const double *ox, const double *ov, double *speed, int32_t *bt,
                            int32_t *path, double *cost, double *fine, int32_t *fine_len) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    TRY(check_batch(N, Kmax));
+    TRY(host_batch_begin(c, N, Kmax, ego, k, ox, ov, speed && bt));
     if (N == 0) return STMPC_OK;
-    if (!ego || !k || !speed || !bt) return fail(STMPC_EINVAL, "NULL host pointer");
-    if (Kmax > 0 && (!ox || !ov)) return fail(STMPC_EINVAL, "NULL host pointer (other_x/other_v)");
-    TRY(check_counts(N, Kmax, k));
-    HIPCHK(hipSetDevice(c->device));
-    const int H = stmpc_num_t(p);
-    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
+    int H;
+    TRY(num_layers(p, &H));
     auto &s = c->s;
     const size_t n = (size_t)N;
     TRY(s.path.ensure(n * H * 4)); TRY(s.bt.ensure(n * 4)); TRY(s.cost.ensure(n * 8));
@@ -1637,11 +1666,7 @@ int stmpc_solve_batch_groups(stmpc_ctx *c, const stmpc_params *groups, int G, in
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     SolverGroupsHost sg;
     TRY(solver_groups_of(groups, G, n_per_group, N, &sg));
-    TRY(check_batch(N, Kmax));
-    if (!ego || !k || !path || !bt || !cost) return fail(STMPC_EINVAL, "NULL host pointer");
-    if (Kmax > 0 && (!ox || !ov)) return fail(STMPC_EINVAL, "NULL host pointer (other_x/other_v)");
-    TRY(check_counts(N, Kmax, k));
-    HIPCHK(hipSetDevice(c->device));
+    TRY(host_batch_begin(c, N, Kmax, ego, k, ox, ov, path && bt && cost));       // (N = G * n_per_group >= 1)
     const int H = sg.table[0].p.H;
     auto &s = c->s;
     const size_t n = (size_t)N;
@@ -1701,6 +1726,93 @@ int rollout_live(const stmpc_ctx *c, int N, int step, const int **live) {
     }
     return STMPC_OK;
 }
+// pointer checks of the two rollout step entries
+int rollout_step_ptrs(int Kmax, const double *d_ego5_start, const double *d_cur_ego4, const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov,
+                      const double *d_action) {
+    if (!d_ego5_start || !d_cur_ego4 || !d_k || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    if (Kmax > 0 && (!d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
+    return STMPC_OK;
+}
+
+// The shield controllers' step "st.do_st_control of the start states": the commands into b.speed / b.fine / b.fine_len (paths into b.path, b.bt, b.cost).
+// Dense: every row, fully asynchronous.  Sparse: the reference solves the start state only where control is handed over (dqn.py:144-155, st.py:808: a few
+// per cent of the ticks), so `select(sel_idx, sel_count)` launches the caller's ordered compaction of those rows, ONE host round trip fetches their number M,
+// the controller runs on the compact batch and the commands are scattered back; a row that keeps its proposal has speed NaN and fine_len 0.  b.fine is
+// the caller's to zero if its decide kernel reads it; `solves` is its control_solves counter, `who` its name in the error text.
+template <class Select>
+int shield_control(stmpc_ctx *c, const stmpc_params *p, double tick, int N, int Kmax, const double *d_ego5, const int32_t *d_k, const double *d_ox,
+                   const double *d_ov, stmpc_ctx::ShieldBufs &b, hipStream_t st_, bool sparse, Select &&select, int64_t &solves, const char *who) {
+    if (!sparse) {
+        solves += N;
+        return st_control_device(c, p, tick, N, Kmax, d_ego5, d_k, d_ox, d_ov, b.path.as<int32_t>(), b.bt.as<int32_t>(), b.cost.as<double>(), b.speed.as<double>(),
+                                 b.fine.as<double>(), b.fine_len.as<int32_t>(), st_, nullptr);
+    }
+    const size_t n = (size_t)N;
+    const int Kalloc = Kmax > 0 ? Kmax : 1;
+    if (!b.host_count) HIPCHK(hipHostMalloc((void **)&b.host_count, 4, hipHostMallocDefault));
+    HIPCHK(hipMemsetAsync(b.speed.p, 0xFF, n * 8, st_));            // NaN: no controller command exists for a row that keeps its proposal
+    HIPCHK(hipMemsetAsync(b.fine_len.p, 0, n * 4, st_));
+    select(b.sel_idx.as<int>(), b.sel_count.as<int>());
+    HIPCHK(hipMemcpyAsync(b.host_count, b.sel_count.p, 4, hipMemcpyDeviceToHost, st_));
+    HIPCHK(hipStreamSynchronize(st_));
+    const int M = *b.host_count;
+    if (M < 0 || M > N) return fail(STMPC_EINTERNAL, std::string(who) + ": selection count out of range");
+    solves += M;
+    if (M == 0) return STMPC_OK;
+    const int mb = (M + 63) / 64;
+    hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kmax, (const int *)b.sel_idx.as<int>(), d_ego5, d_k, d_ox, d_ov, b.c_ego.as<double>(),
+                       b.c_k.as<int>(), b.c_ox.as<double>(), b.c_ov.as<double>());
+    HIPCHK(hipMemsetAsync(b.c_fine.p, 0, (size_t)M * STMPC_QP_NMAX * 8, st_));
+    TRY(st_control_device(c, p, tick, M, Kalloc, b.c_ego.as<double>(), b.c_k.as<int32_t>(), b.c_ox.as<double>(), b.c_ov.as<double>(), b.path.as<int32_t>(),
+                          b.bt.as<int32_t>(), b.cost.as<double>(), b.c_speed.as<double>(), b.c_fine.as<double>(), b.c_fine_len.as<int32_t>(), st_, nullptr));
+    hipLaunchKernelGGL(k_cc_scatter, dim3(mb), dim3(64), 0, st_, M, (const int *)b.sel_idx.as<int>(), (const double *)b.c_speed.as<double>(),
+                       (const double *)b.c_fine.as<double>(), (const int *)b.c_fine_len.as<int>(), STMPC_QP_NMAX, b.speed.as<double>(), b.fine.as<double>(),
+                       b.fine_len.as<int>());
+    return STMPC_OK;
+}
+
+// A tick of the combined controller once the entry has checked its arguments and the rollout in the context: probe, controller, decision.  `n_test`: the
+// rows that probe their rolled-out state -- none, all, or those of the context's static list test_idx (controller groups).  `select` is shield_control's,
+// `decide()` launches the entry's decide kernel on what the two steps left in c->cc.sh.
+template <class Select, class Decide>
+int combined_decide(stmpc_ctx *c, const stmpc_params *p, int H, double tick, bool sparse, int n_test, int N, int Kmax, const double *d_ego5_start,
+                    const int32_t *d_k, const double *d_ox_start, const double *d_ov_start, const double *d_cur_ego4, const double *d_cur_ox,
+                    const double *d_cur_ov, hipStream_t st_, Select &&select, Decide &&decide) {
+    auto &b = c->cc;
+    auto &o = b.sh;
+    const size_t n = (size_t)N;
+    const int Kalloc = Kmax > 0 ? Kmax : 1;
+    TRY(b.probe_ego.ensure(n * 5 * 8)); TRY(b.probe_ox.ensure(n * Kalloc * 8)); TRY(b.probe_ov.ensure(n * Kalloc * 8));
+    TRY(o.ensure(N, H));
+    if (sparse) TRY(o.ensure_compact(N, Kalloc));
+    HIPCHK(hipMemsetAsync(o.pcrash.p, 0, n * 4, st_));
+    // 1. feasibility probe of the rolled-out state (st.test_guaranteed_crash_from_state, dqn.py:152): one batched solve, of the rows that test only (a lone
+    //    run of a group that does not test never calls the solver for them)
+    if (n_test > 0) {
+        hipLaunchKernelGGL(k_cc_probe_state, dim3((N + 63) / 64), dim3(64), 0, st_, N, Kalloc, Kmax, d_k, d_cur_ego4, d_cur_ox, d_cur_ov, b.state(),
+                           b.probe_ego.as<double>(), b.probe_ox.as<double>(), b.probe_ov.as<double>());
+        if (n_test == N) {
+            TRY(stmpc_solve_batch_device(c, p, N, Kmax, b.probe_ego.as<double>(), d_k, b.probe_ox.as<double>(), b.probe_ov.as<double>(), o.path.as<int32_t>(),
+                                         o.bt.as<int32_t>(), o.cost.as<double>(), nullptr, o.pcrash.as<int32_t>(), st_));
+        } else {
+            const int M = n_test, mb = (M + 63) / 64;
+            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kalloc, (const int *)b.test_idx.as<int>(), (const double *)b.probe_ego.as<double>(), d_k,
+                               (const double *)b.probe_ox.as<double>(), (const double *)b.probe_ov.as<double>(), o.c_ego.as<double>(), o.c_k.as<int>(),
+                               o.c_ox.as<double>(), o.c_ov.as<double>());
+            TRY(stmpc_solve_batch_device(c, p, M, Kalloc, o.c_ego.as<double>(), o.c_k.as<int32_t>(), o.c_ox.as<double>(), o.c_ov.as<double>(), o.path.as<int32_t>(),
+                                         o.bt.as<int32_t>(), o.cost.as<double>(), nullptr, b.c_pcrash.as<int32_t>(), st_));
+            hipLaunchKernelGGL(k_cc_scatter_flag, dim3(mb), dim3(64), 0, st_, M, (const int *)b.test_idx.as<int>(), (const int *)b.c_pcrash.as<int>(), o.pcrash.as<int>());
+        }
+    }
+    // 2. the controller on the start state (st.do_st_control; also the path of the strictly-better comparison, dqn.py:157-164, which needs every row's)
+    HIPCHK(hipMemsetAsync(o.fine.p, 0, n * STMPC_QP_NMAX * 8, st_));          // (k_cc_decide* read the fine path)
+    b.ticks += N;
+    TRY(shield_control(c, p, tick, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start, o, st_, sparse, select, b.control_solves, "combined controller"));
+    // 3. the decision
+    decide();
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1711,8 +1823,7 @@ int stmpc_rollout_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_c
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT || step < 1) return fail(STMPC_EINVAL, "N, Kmax or step out of range");
     if (N == 0) return STMPC_OK;
-    if (!d_ego5_start || !d_cur_ego4 || !d_k || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    if (Kmax > 0 && (!d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
+    TRY(rollout_step_ptrs(Kmax, d_ego5_start, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_action));
     HIPCHK(hipSetDevice(c->device));
     DevP dp; CCfg cc;
     TRY(make_devp(p, &dp));
@@ -1887,65 +1998,23 @@ int stmpc_combined_decide_device(stmpc_ctx *c, const stmpc_params *p, const stmp
     const int Kalloc = Kmax > 0 ? Kmax : 1;
     auto &b = c->cc;
     if (b.grouped || b.N != N || b.K != Kalloc || b.R != cc.rollout_length) return fail(STMPC_EINVAL, "no rollout of this shape in the context (call stmpc_rollout_step_device first)");
-    const int H = stmpc_num_t(p);
-    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
+    int H;
+    TRY(num_layers(p, &H));
     hipStream_t st_ = (hipStream_t)stream;
-    const size_t n = (size_t)N;
-    TRY(b.probe_ego.ensure(n * 5 * 8)); TRY(b.probe_ox.ensure(n * Kalloc * 8)); TRY(b.probe_ov.ensure(n * Kalloc * 8));
-    TRY(b.path.ensure(n * H * 4)); TRY(b.bt.ensure(n * 4)); TRY(b.cost.ensure(n * 8)); TRY(b.pcrash.ensure(n * 4));
-    TRY(b.speed.ensure(n * 8)); TRY(b.fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(b.fine_len.ensure(n * 4));
-    CCState st = b.state();
-    const int blocks = (N + 63) / 64;
-    HIPCHK(hipMemsetAsync(b.pcrash.p, 0, n * 4, st_));
-    // 1. feasibility probe of the rolled-out state (st.test_guaranteed_crash_from_state, dqn.py:152): one batched solve
-    if (cc.test_rollout_state) {
-        hipLaunchKernelGGL(k_cc_probe_state, dim3(blocks), dim3(64), 0, st_, N, Kalloc, Kmax, d_k, d_cur_ego4, d_cur_ox, d_cur_ov, st, b.probe_ego.as<double>(),
-                           b.probe_ox.as<double>(), b.probe_ov.as<double>());
-        TRY(stmpc_solve_batch_device(c, p, N, Kmax, b.probe_ego.as<double>(), d_k, b.probe_ox.as<double>(), b.probe_ov.as<double>(), b.path.as<int32_t>(),
-                                     b.bt.as<int32_t>(), b.cost.as<double>(), nullptr, b.pcrash.as<int32_t>(), stream));
-    }
-    // 2. the controller on the start state (st.do_st_control; also the path of the strictly-better comparison, dqn.py:157-164)
-    HIPCHK(hipMemsetAsync(b.fine.p, 0, n * STMPC_QP_NMAX * 8, st_));
-    b.ticks += N;
-    if (g->sparse_control && !cc.strictly_better) {
-        // The reference solves the start state only when a branch of dqn.py:144-155 hands control over (2-5 % of the ticks under the shipped
-        // configs); here: ordered compaction of those states, ONE host round trip for their number, the controller on the compact batch, scatter.
-        TRY(b.sel_idx.ensure(n * 4)); TRY(b.sel_count.ensure(4));
-        if (!b.host_count) HIPCHK(hipHostMalloc((void **)&b.host_count, 4, hipHostMallocDefault));
-        HIPCHK(hipMemsetAsync(b.speed.p, 0xFF, n * 8, st_));            // NaN: no controller command exists for a state the policy keeps
-        HIPCHK(hipMemsetAsync(b.fine_len.p, 0, n * 4, st_));
-        hipLaunchKernelGGL(k_cc_select, dim3(1), dim3(1024), 0, st_, cc, N, st, (const int *)b.pcrash.as<int>(), b.sel_idx.as<int>(), b.sel_count.as<int>());
-        HIPCHK(hipMemcpyAsync(b.host_count, b.sel_count.p, 4, hipMemcpyDeviceToHost, st_));
-        HIPCHK(hipStreamSynchronize(st_));
-        const int M = *b.host_count;
-        if (M < 0 || M > N) return fail(STMPC_EINTERNAL, "combined controller: selection count out of range");
-        b.control_solves += M;
-        if (M > 0) {
-            const size_t m = (size_t)M;
-            TRY(b.c_ego.ensure(m * 5 * 8)); TRY(b.c_k.ensure(m * 4)); TRY(b.c_ox.ensure(m * Kalloc * 8)); TRY(b.c_ov.ensure(m * Kalloc * 8));
-            TRY(b.c_speed.ensure(m * 8)); TRY(b.c_fine.ensure(m * STMPC_QP_NMAX * 8)); TRY(b.c_fine_len.ensure(m * 4));
-            const int mb = (M + 63) / 64;
-            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kmax, (const int *)b.sel_idx.as<int>(), d_ego5_start, d_k, d_ox_start, d_ov_start,
-                               b.c_ego.as<double>(), b.c_k.as<int>(), b.c_ox.as<double>(), b.c_ov.as<double>());
-            HIPCHK(hipMemsetAsync(b.c_fine.p, 0, m * STMPC_QP_NMAX * 8, st_));
-            TRY(st_control_device(c, p, g->tick_length, M, Kalloc, b.c_ego.as<double>(), b.c_k.as<int32_t>(), b.c_ox.as<double>(), b.c_ov.as<double>(),
-                                  b.path.as<int32_t>(), b.bt.as<int32_t>(), b.cost.as<double>(), b.c_speed.as<double>(), b.c_fine.as<double>(),
-                                  b.c_fine_len.as<int32_t>(), stream, nullptr));
-            hipLaunchKernelGGL(k_cc_scatter, dim3(mb), dim3(64), 0, st_, M, (const int *)b.sel_idx.as<int>(), (const double *)b.c_speed.as<double>(),
-                               (const double *)b.c_fine.as<double>(), (const int *)b.c_fine_len.as<int>(), STMPC_QP_NMAX, b.speed.as<double>(),
-                               b.fine.as<double>(), b.fine_len.as<int>());
-        }
-    } else {
-        b.control_solves += N;
-        TRY(st_control_device(c, p, g->tick_length, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start, b.path.as<int32_t>(), b.bt.as<int32_t>(),
-                              b.cost.as<double>(), b.speed.as<double>(), b.fine.as<double>(), b.fine_len.as<int32_t>(), stream, nullptr));
-    }
-    // 3. the decision
-    hipLaunchKernelGGL(k_cc_decide, dim3(blocks), dim3(64), 0, st_, cc, N, d_ego5_start, d_first_action, d_last_choice_rl, st, (const int *)b.pcrash.as<int>(),
-                       (const double *)b.speed.as<double>(), (const double *)b.fine.as<double>(), (const int *)b.fine_len.as<int>(), STMPC_QP_NMAX,
-                       d_takeover, d_reason, d_speed, c->sticky.as<unsigned>() + 1);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    const CCState st = b.state();
+    const auto &o = b.sh;
+    // (sparse: not with the strictly-better comparison, which needs every row's path)
+    return combined_decide(
+        c, p, H, g->tick_length, g->sparse_control && !cc.strictly_better, cc.test_rollout_state ? N : 0, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start,
+        d_cur_ego4, d_cur_ox, d_cur_ov, st_,
+        [&](int *sel_idx, int *sel_count) {
+            hipLaunchKernelGGL(k_cc_select, dim3(1), dim3(1024), 0, st_, cc, N, st, (const int *)o.pcrash.as<int>(), sel_idx, sel_count);
+        },
+        [&] {
+            hipLaunchKernelGGL(k_cc_decide, dim3((N + 63) / 64), dim3(64), 0, st_, cc, N, d_ego5_start, d_first_action, d_last_choice_rl, st,
+                               (const int *)o.pcrash.as<int>(), (const double *)o.speed.as<double>(), (const double *)o.fine.as<double>(),
+                               (const int *)o.fine_len.as<int>(), STMPC_QP_NMAX, d_takeover, d_reason, d_speed, c->sticky.as<unsigned>() + 1);
+        });
 }
 
 // ---- controller groups (stmpc_cc_groups_kernels.hpp) ----
@@ -1974,7 +2043,7 @@ int stmpc_combined_groups_set(stmpc_ctx *c, const stmpc_params *p, const stmpc_c
     auto &b = c->cc;
     TRY(b.groups.ensure(table.size() * sizeof(CCfg)));
     TRY(b.test_idx.ensure((test_rows.size() + 1) * 4));
-    if (b.grouped) { b.grouped = false; b.N = 0; }       // (a grouped rollout of the former table cannot be continued or decided)
+    b.drop_grouped();
     b.C = 0;
     HIPCHK(hipMemcpy(b.groups.p, table.data(), table.size() * sizeof(CCfg), hipMemcpyHostToDevice));      // (synchronous: table and test_rows are locals)
     if (!test_rows.empty()) HIPCHK(hipMemcpy(b.test_idx.p, test_rows.data(), test_rows.size() * 4, hipMemcpyHostToDevice));
@@ -1987,7 +2056,7 @@ int stmpc_combined_groups_set(stmpc_ctx *c, const stmpc_params *p, const stmpc_c
 int stmpc_combined_groups_clear(stmpc_ctx *c) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     auto &b = c->cc;
-    if (b.grouped) { b.grouped = false; b.N = 0; }
+    b.drop_grouped();
     b.C = 0; b.n_per_group = 0; b.Rmax = 0; b.n_test = 0; b.any_strict = 0; b.table.clear();
     return STMPC_OK;
 }
@@ -1999,8 +2068,7 @@ int stmpc_rollout_step_groups_device(stmpc_ctx *c, const stmpc_params *p, int N,
     auto &b = c->cc;
     if (b.C < 1) return fail(STMPC_EINVAL, "the context has no controller groups (stmpc_combined_groups_set): use the plain rollout entry");
     if ((int64_t)N != (int64_t)b.C * b.n_per_group) return fail(STMPC_EINVAL, "N does not match stmpc_combined_groups_set (C * n_per_group)");
-    if (!d_ego5_start || !d_cur_ego4 || !d_k || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    if (Kmax > 0 && (!d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
+    TRY(rollout_step_ptrs(Kmax, d_ego5_start, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_action));
     DevP dp;
     TRY(make_devp(p, &dp));
     const int Kalloc = Kmax > 0 ? Kmax : 1;
@@ -2035,77 +2103,27 @@ int stmpc_combined_decide_groups_device(stmpc_ctx *c, const stmpc_params *p, int
     if (Kmax > 0 && (!d_ox_start || !d_ov_start || !d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
     const int Kalloc = Kmax > 0 ? Kmax : 1;
     if (!b.grouped || b.N != N || b.K != Kalloc || b.R != b.Rmax) return fail(STMPC_EINVAL, "no grouped rollout of this shape in the context (call stmpc_rollout_step_groups_device first)");
-    const int H = stmpc_num_t(p);
-    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
+    int H;
+    TRY(num_layers(p, &H));
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st_ = (hipStream_t)stream;
-    const size_t n = (size_t)N;
-    TRY(b.probe_ego.ensure(n * 5 * 8)); TRY(b.probe_ox.ensure(n * Kalloc * 8)); TRY(b.probe_ov.ensure(n * Kalloc * 8));
-    TRY(b.path.ensure(n * H * 4)); TRY(b.bt.ensure(n * 4)); TRY(b.cost.ensure(n * 8)); TRY(b.pcrash.ensure(n * 4));
-    TRY(b.speed.ensure(n * 8)); TRY(b.fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(b.fine_len.ensure(n * 4));
-    // (the compact batches of both gathers, sized once for all rows: no allocation between the launches of a tick)
-    TRY(b.c_ego.ensure(n * 5 * 8)); TRY(b.c_k.ensure(n * 4)); TRY(b.c_ox.ensure(n * Kalloc * 8)); TRY(b.c_ov.ensure(n * Kalloc * 8)); TRY(b.c_pcrash.ensure(n * 4));
-    TRY(b.c_speed.ensure(n * 8)); TRY(b.c_fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(b.c_fine_len.ensure(n * 4));
-    CCState st = b.state();
+    auto &o = b.sh;
+    // (the compact batch serves the probe's gather too, so it exists in a dense run as well)
+    TRY(o.ensure_compact(N, Kalloc)); TRY(b.c_pcrash.ensure((size_t)N * 4));
+    const CCState st = b.state();
     const CCfg *groups = b.groups.as<CCfg>();
-    const int npg = b.n_per_group, blocks = (N + 63) / 64;
-    const dim3 ggrid((npg + 63) / 64, b.C);
-    HIPCHK(hipMemsetAsync(b.pcrash.p, 0, n * 4, st_));
-    // 1. feasibility probe, only for the rows of the groups that test (a lone run of a group that does not never calls the solver for them)
-    if (b.n_test > 0) {
-        hipLaunchKernelGGL(k_cc_probe_state, dim3(blocks), dim3(64), 0, st_, N, Kalloc, Kmax, d_k, d_cur_ego4, d_cur_ox, d_cur_ov, st, b.probe_ego.as<double>(),
-                           b.probe_ox.as<double>(), b.probe_ov.as<double>());
-        if (b.n_test == N) {
-            TRY(stmpc_solve_batch_device(c, p, N, Kmax, b.probe_ego.as<double>(), d_k, b.probe_ox.as<double>(), b.probe_ov.as<double>(), b.path.as<int32_t>(),
-                                         b.bt.as<int32_t>(), b.cost.as<double>(), nullptr, b.pcrash.as<int32_t>(), stream));
-        } else {
-            const int M = b.n_test, mb = (M + 63) / 64;
-            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kalloc, (const int *)b.test_idx.as<int>(), (const double *)b.probe_ego.as<double>(), d_k,
-                               (const double *)b.probe_ox.as<double>(), (const double *)b.probe_ov.as<double>(), b.c_ego.as<double>(), b.c_k.as<int>(),
-                               b.c_ox.as<double>(), b.c_ov.as<double>());
-            TRY(stmpc_solve_batch_device(c, p, M, Kalloc, b.c_ego.as<double>(), b.c_k.as<int32_t>(), b.c_ox.as<double>(), b.c_ov.as<double>(), b.path.as<int32_t>(),
-                                         b.bt.as<int32_t>(), b.cost.as<double>(), nullptr, b.c_pcrash.as<int32_t>(), stream));
-            hipLaunchKernelGGL(k_cc_scatter_flag, dim3(mb), dim3(64), 0, st_, M, (const int *)b.test_idx.as<int>(), (const int *)b.c_pcrash.as<int>(), b.pcrash.as<int>());
-        }
-    }
-    // 2. the controller on the start state: sparse as the plain entry unless a group compares paths (then every row's path is needed: the run is dense)
-    HIPCHK(hipMemsetAsync(b.fine.p, 0, n * STMPC_QP_NMAX * 8, st_));
-    b.ticks += N;
-    if (b.sparse && !b.any_strict) {
-        TRY(b.sel_idx.ensure(n * 4)); TRY(b.sel_count.ensure(4));
-        if (!b.host_count) HIPCHK(hipHostMalloc((void **)&b.host_count, 4, hipHostMallocDefault));
-        HIPCHK(hipMemsetAsync(b.speed.p, 0xFF, n * 8, st_));
-        HIPCHK(hipMemsetAsync(b.fine_len.p, 0, n * 4, st_));
-        hipLaunchKernelGGL(k_cc_select_groups, dim3(1), dim3(1024), 0, st_, groups, npg, N, st, (const int *)b.pcrash.as<int>(), b.sel_idx.as<int>(), b.sel_count.as<int>());
-        HIPCHK(hipMemcpyAsync(b.host_count, b.sel_count.p, 4, hipMemcpyDeviceToHost, st_));
-        HIPCHK(hipStreamSynchronize(st_));
-        const int M = *b.host_count;
-        if (M < 0 || M > N) return fail(STMPC_EINTERNAL, "combined controller: selection count out of range");
-        b.control_solves += M;
-        if (M > 0) {
-            const size_t m = (size_t)M;
-            const int mb = (M + 63) / 64;
-            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kmax, (const int *)b.sel_idx.as<int>(), d_ego5_start, d_k, d_ox_start, d_ov_start,
-                               b.c_ego.as<double>(), b.c_k.as<int>(), b.c_ox.as<double>(), b.c_ov.as<double>());
-            HIPCHK(hipMemsetAsync(b.c_fine.p, 0, m * STMPC_QP_NMAX * 8, st_));
-            TRY(st_control_device(c, p, b.tick, M, Kalloc, b.c_ego.as<double>(), b.c_k.as<int32_t>(), b.c_ox.as<double>(), b.c_ov.as<double>(),
-                                  b.path.as<int32_t>(), b.bt.as<int32_t>(), b.cost.as<double>(), b.c_speed.as<double>(), b.c_fine.as<double>(),
-                                  b.c_fine_len.as<int32_t>(), stream, nullptr));
-            hipLaunchKernelGGL(k_cc_scatter, dim3(mb), dim3(64), 0, st_, M, (const int *)b.sel_idx.as<int>(), (const double *)b.c_speed.as<double>(),
-                               (const double *)b.c_fine.as<double>(), (const int *)b.c_fine_len.as<int>(), STMPC_QP_NMAX, b.speed.as<double>(),
-                               b.fine.as<double>(), b.fine_len.as<int>());
-        }
-    } else {
-        b.control_solves += N;
-        TRY(st_control_device(c, p, b.tick, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start, b.path.as<int32_t>(), b.bt.as<int32_t>(),
-                              b.cost.as<double>(), b.speed.as<double>(), b.fine.as<double>(), b.fine_len.as<int32_t>(), stream, nullptr));
-    }
-    // 3. the decision
-    hipLaunchKernelGGL(k_cc_decide_groups, ggrid, dim3(64), 0, st_, groups, npg, b.Rmax + 1, d_ego5_start, d_first_action, d_last_choice_rl, st,
-                       (const int *)b.pcrash.as<int>(), (const double *)b.speed.as<double>(), (const double *)b.fine.as<double>(), (const int *)b.fine_len.as<int>(),
-                       STMPC_QP_NMAX, d_takeover, d_reason, d_speed, c->sticky.as<unsigned>() + 1);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    const int npg = b.n_per_group;
+    // (sparse as the plain entry unless a group compares paths: then every row's path is needed and the run is dense)
+    return combined_decide(
+        c, p, H, b.tick, b.sparse && !b.any_strict, b.n_test, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start, d_cur_ego4, d_cur_ox, d_cur_ov, st_,
+        [&](int *sel_idx, int *sel_count) {
+            hipLaunchKernelGGL(k_cc_select_groups, dim3(1), dim3(1024), 0, st_, groups, npg, N, st, (const int *)o.pcrash.as<int>(), sel_idx, sel_count);
+        },
+        [&] {
+            hipLaunchKernelGGL(k_cc_decide_groups, dim3((npg + 63) / 64, b.C), dim3(64), 0, st_, groups, npg, b.Rmax + 1, d_ego5_start, d_first_action,
+                               d_last_choice_rl, st, (const int *)o.pcrash.as<int>(), (const double *)o.speed.as<double>(), (const double *)o.fine.as<double>(),
+                               (const int *)o.fine_len.as<int>(), STMPC_QP_NMAX, d_takeover, d_reason, d_speed, c->sticky.as<unsigned>() + 1);
+        });
 }
 
 int stmpc_combined_read_state(stmpc_ctx *c, int N, int32_t *live, int32_t *hist_len, int32_t *crash_pred, double *sel_speed, double *rollout_s,
@@ -2121,10 +2139,10 @@ int stmpc_combined_read_state(stmpc_ctx *c, int N, int32_t *live, int32_t *hist_
     TRY(download(rollout_s, b.rollout_s, n * R1)); TRY(download(have_test, b.have_test, n)); TRY(download(test_ego4, b.test_ego, n * 4));
     TRY(download(test_ox, b.test_ox, n * K)); TRY(download(test_ov, b.test_ov, n * K));
     // (the decision's buffers exist once stmpc_combined_decide_device has run)
-    if (b.pcrash.p) TRY(download(probe_crash, b.pcrash, n));
-    if (b.speed.p) TRY(download(st_speed, b.speed, n));
-    if (b.fine.p) TRY(download(fine, b.fine, n * STMPC_QP_NMAX));
-    if (b.fine_len.p) TRY(download(fine_len, b.fine_len, n));
+    if (b.sh.pcrash.p) TRY(download(probe_crash, b.sh.pcrash, n));
+    if (b.sh.speed.p) TRY(download(st_speed, b.sh.speed, n));
+    if (b.sh.fine.p) TRY(download(fine, b.sh.fine, n * STMPC_QP_NMAX));
+    if (b.sh.fine_len.p) TRY(download(fine_len, b.sh.fine_len, n));
     return stmpc_check_error(c);         // (device already synchronised: just the flags)
 }
 
@@ -2133,7 +2151,7 @@ int stmpc_solve_grid_no_jerk(stmpc_ctx *c, int variant, const uint8_t *obstacles
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (variant != 0 && variant != 1) return fail(STMPC_EINVAL, "variant must be 0 (no_jerk_fast) or 1 (no_jerk_djikstra)");
     if (!obstacles || !s_values || !t_values || !distances || !s_sequence_out) return fail(STMPC_EINVAL, "NULL host pointer");
-    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "num_t must be in [2, 64]");
+    if (bad_layers(H)) return fail(STMPC_EINVAL, "num_t must be in [2, 64]");
     if (S < 2 || S > STMPC_S_LIMIT) return fail(STMPC_EINVAL, "num_s must be in [2, 65000]");
     if (variant == 1 && (size_t)H * S * S > ((size_t)1 << 28)) return fail(STMPC_EINVAL, "no_jerk_djikstra keeps H*S*S node flags: lattice too large (H*S*S > 2^28)");
     if (t_values[1] - t_values[0] == 0.0) return fail(STMPC_EINVAL, "float division by zero (delta_t == 0)");
@@ -2186,15 +2204,15 @@ int stmpc_first_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_fir
     HIPCHK(hipSetDevice(c->device));
     DevP dp;
     TRY(make_devp(p, &dp));
-    const int H = stmpc_num_t(p);
-    if (H < 2 || H > STMPC_H_LIMIT) return fail(STMPC_EINVAL, "number of time layers must be in [2, 64]");
+    const int H = dp.H;
     const int Kalloc = Kmax > 0 ? Kmax : 1;
     hipStream_t st_ = (hipStream_t)stream;
     const size_t n = (size_t)N;
     auto &b = c->fs;
+    auto &o = b.sh;
     TRY(b.next_ego.ensure(n * 5 * 8)); TRY(b.next_ox.ensure(n * Kalloc * 8)); TRY(b.next_ov.ensure(n * Kalloc * 8)); TRY(b.crashed.ensure(n * 4));
-    TRY(b.pcrash.ensure(n * 4)); TRY(b.path.ensure(n * H * 4)); TRY(b.bt.ensure(n * 4)); TRY(b.cost.ensure(n * 8));
-    TRY(b.speed.ensure(n * 8)); TRY(b.fine.ensure(n * STMPC_QP_NMAX * 8)); TRY(b.fine_len.ensure(n * 4));
+    TRY(o.ensure(N, H));
+    if (g->sparse_control) TRY(o.ensure_compact(N, Kalloc));
     if (!b.takeovers.p) { TRY(b.takeovers.ensure(8)); HIPCHK(hipMemset(b.takeovers.p, 0, 8)); }
     b.N = N; b.K = Kalloc;
     const int blocks = (N + 63) / 64;
@@ -2205,47 +2223,21 @@ int stmpc_first_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_fir
     });
     HIPCHK(hipGetLastError());
     // 2. st.test_guaranteed_crash_from_state(next_state), st.py:807: one batched solve (the reference asks before it looks at `crashed`, so every state is solved)
-    TRY(stmpc_solve_batch_device(c, p, N, Kmax, b.next_ego.as<double>(), d_k, b.next_ox.as<double>(), b.next_ov.as<double>(), b.path.as<int32_t>(),
-                                 b.bt.as<int32_t>(), b.cost.as<double>(), nullptr, b.pcrash.as<int32_t>(), stream));
-    // 3. st.do_st_control(state) of the START state, st.py:811
+    TRY(stmpc_solve_batch_device(c, p, N, Kmax, b.next_ego.as<double>(), d_k, b.next_ox.as<double>(), b.next_ov.as<double>(), o.path.as<int32_t>(),
+                                 o.bt.as<int32_t>(), o.cost.as<double>(), nullptr, o.pcrash.as<int32_t>(), stream));
+    // 3. st.do_st_control(state) of the START state, st.py:811; sparse: only for the states st.py:808 hands over.  k_fs_decide reads no fine path, so only
+    //    the dense run, which fills every row's, clears them first
     b.decisions += N;
-    if (g->sparse_control) {
-        // only for the states st.py:808 hands over: ordered compaction, ONE host round trip for their number, the controller on the compact batch, scatter
-        TRY(b.sel_idx.ensure(n * 4)); TRY(b.sel_count.ensure(4));
-        if (!b.host_count) HIPCHK(hipHostMalloc((void **)&b.host_count, 4, hipHostMallocDefault));
-        HIPCHK(hipMemsetAsync(b.speed.p, 0xFF, n * 8, st_));            // NaN: no controller command exists for a state that keeps the proposed speed
-        HIPCHK(hipMemsetAsync(b.fine_len.p, 0, n * 4, st_));
-        hipLaunchKernelGGL(k_fs_select, dim3(1), dim3(1024), 0, st_, N, (const int *)b.crashed.as<int>(), (const int *)b.pcrash.as<int>(), b.sel_idx.as<int>(),
-                           b.sel_count.as<int>());
-        HIPCHK(hipMemcpyAsync(b.host_count, b.sel_count.p, 4, hipMemcpyDeviceToHost, st_));
-        HIPCHK(hipStreamSynchronize(st_));
-        const int M = *b.host_count;
-        if (M < 0 || M > N) return fail(STMPC_EINTERNAL, "first-step controller: selection count out of range");
-        b.control_solves += M;
-        if (M > 0) {
-            const size_t m = (size_t)M;
-            TRY(b.c_ego.ensure(m * 5 * 8)); TRY(b.c_k.ensure(m * 4)); TRY(b.c_ox.ensure(m * Kalloc * 8)); TRY(b.c_ov.ensure(m * Kalloc * 8));
-            TRY(b.c_speed.ensure(m * 8)); TRY(b.c_fine.ensure(m * STMPC_QP_NMAX * 8)); TRY(b.c_fine_len.ensure(m * 4));
-            const int mb = (M + 63) / 64;
-            hipLaunchKernelGGL(k_cc_gather, dim3(mb), dim3(64), 0, st_, M, Kalloc, Kmax, (const int *)b.sel_idx.as<int>(), d_ego5, d_k, d_ox, d_ov,
-                               b.c_ego.as<double>(), b.c_k.as<int>(), b.c_ox.as<double>(), b.c_ov.as<double>());
-            HIPCHK(hipMemsetAsync(b.c_fine.p, 0, m * STMPC_QP_NMAX * 8, st_));
-            TRY(st_control_device(c, p, g->tick_length, M, Kalloc, b.c_ego.as<double>(), b.c_k.as<int32_t>(), b.c_ox.as<double>(), b.c_ov.as<double>(),
-                                  b.path.as<int32_t>(), b.bt.as<int32_t>(), b.cost.as<double>(), b.c_speed.as<double>(), b.c_fine.as<double>(),
-                                  b.c_fine_len.as<int32_t>(), stream, nullptr));
-            hipLaunchKernelGGL(k_cc_scatter, dim3(mb), dim3(64), 0, st_, M, (const int *)b.sel_idx.as<int>(), (const double *)b.c_speed.as<double>(),
-                               (const double *)b.c_fine.as<double>(), (const int *)b.c_fine_len.as<int>(), STMPC_QP_NMAX, b.speed.as<double>(),
-                               b.fine.as<double>(), b.fine_len.as<int>());
-        }
-    } else {
-        b.control_solves += N;
-        HIPCHK(hipMemsetAsync(b.fine.p, 0, n * STMPC_QP_NMAX * 8, st_));
-        TRY(st_control_device(c, p, g->tick_length, N, Kmax, d_ego5, d_k, d_ox, d_ov, b.path.as<int32_t>(), b.bt.as<int32_t>(), b.cost.as<double>(),
-                              b.speed.as<double>(), b.fine.as<double>(), b.fine_len.as<int32_t>(), stream, nullptr));
-    }
+    if (!g->sparse_control) HIPCHK(hipMemsetAsync(o.fine.p, 0, n * STMPC_QP_NMAX * 8, st_));
+    TRY(shield_control(
+        c, p, g->tick_length, N, Kmax, d_ego5, d_k, d_ox, d_ov, o, st_, g->sparse_control != 0,
+        [&](int *sel_idx, int *sel_count) {
+            hipLaunchKernelGGL(k_fs_select, dim3(1), dim3(1024), 0, st_, N, (const int *)b.crashed.as<int>(), (const int *)o.pcrash.as<int>(), sel_idx, sel_count);
+        },
+        b.control_solves, "first-step controller"));
     // 4. the choice, st.py:808-814
-    hipLaunchKernelGGL(k_fs_decide, dim3(blocks), dim3(64), 0, st_, N, d_start_speed, (const int *)b.crashed.as<int>(), (const int *)b.pcrash.as<int>(),
-                       (const double *)b.speed.as<double>(), (const int *)b.fine_len.as<int>(), d_cmd_speed, d_takeover, d_reason,
+    hipLaunchKernelGGL(k_fs_decide, dim3(blocks), dim3(64), 0, st_, N, d_start_speed, (const int *)b.crashed.as<int>(), (const int *)o.pcrash.as<int>(),
+                       (const double *)o.speed.as<double>(), (const int *)o.fine_len.as<int>(), d_cmd_speed, d_takeover, d_reason,
                        b.takeovers.as<unsigned long long>(), c->sticky.as<unsigned>() + 1);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -2255,12 +2247,8 @@ int stmpc_first_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_first_step
                      const double *ov, const double *start_speed, double *cmd_speed, int32_t *takeover, int32_t *reason, int32_t *crashed,
                      int32_t *crash_guaranteed, double *next_ego, double *next_ox, double *next_ov) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    TRY(check_batch(N, Kmax));
+    TRY(host_batch_begin(c, N, Kmax, ego, k, ox, ov, start_speed && cmd_speed && takeover && reason));
     if (N == 0) return STMPC_OK;
-    if (!ego || !k || !start_speed || !cmd_speed || !takeover || !reason) return fail(STMPC_EINVAL, "NULL host pointer");
-    if (Kmax > 0 && (!ox || !ov)) return fail(STMPC_EINVAL, "NULL host pointer (other_x/other_v)");
-    TRY(check_counts(N, Kmax, k));
-    HIPCHK(hipSetDevice(c->device));
     auto &s = c->s;
     const size_t n = (size_t)N;
     TRY(s.states(N, Kmax, ego, 5, k, ox, ov));
@@ -2271,7 +2259,7 @@ int stmpc_first_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_first_step
     HIPCHK(hipDeviceSynchronize());
     const auto &b = c->fs;
     TRY(download(cmd_speed, s.misc1, n)); TRY(download(takeover, s.misc2, n)); TRY(download(reason, s.misc3, n));
-    TRY(download(crashed, b.crashed, n)); TRY(download(crash_guaranteed, b.pcrash, n)); TRY(download(next_ego, b.next_ego, n * 5));
+    TRY(download(crashed, b.crashed, n)); TRY(download(crash_guaranteed, b.sh.pcrash, n)); TRY(download(next_ego, b.next_ego, n * 5));
     if (Kmax > 0) { TRY(download(next_ox, b.next_ox, n * Kmax)); TRY(download(next_ov, b.next_ov, n * Kmax)); }
     return stmpc_check_error(c);         // (this entry is synchronous: what its kernels flagged is its own error)
 }
@@ -2597,6 +2585,15 @@ int env_reset_begin(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, env::ECfg *e, 
     e->log_cap = cap; e->n_actions = v.n_actions; e->actions = v.actions.as<double>();
     return STMPC_OK;
 }
+// the step entries, after their own checks of N and of their pointers: the env cfg against the environment in the context (`reset_entry` made it), which
+// then completes the ECfg (but for the seed)
+int env_step_begin(const stmpc_ctx *c, const stmpc_env_cfg *ec, int obs_stride, const char *reset_entry, env::ECfg *e) {
+    TRY(make_envcfg(ec, e));
+    if (obs_stride < e->obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
+    if (e->mode != c->env.mode) return fail(STMPC_EINVAL, std::string("env_cfg.action_mode differs from the one the context was reset with (") + reset_entry + ")");
+    e->log_cap = c->env.log_cap; e->n_actions = c->env.n_actions; e->actions = c->env.actions.as<double>();
+    return STMPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2638,11 +2635,9 @@ int stmpc_env_step_groups_device(stmpc_ctx *c, const stmpc_params *p, const stmp
     if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     env::ECfg e;
     DevP dp;
-    TRY(make_envcfg(ec, &e));
-    if (obs_stride < e.obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
-    if (e.mode != c->env.mode) return fail(STMPC_EINVAL, "env_cfg.action_mode differs from the one the context was reset with (stmpc_env_reset_groups_device)");
+    TRY(env_step_begin(c, ec, obs_stride, "stmpc_env_reset_groups_device", &e));
     TRY(make_devp(p, &dp));
-    e.seed = 0; e.log_cap = c->env.log_cap; e.n_actions = c->env.n_actions; e.actions = c->env.actions.as<double>();
+    e.seed = 0;
     HIPCHK(hipSetDevice(c->device));
     const int npg = c->sim.n_per_group;
     const dim3 grid((N + 63) / 64), ggrid((npg + 63) / 64, c->sim.G), block(64);
@@ -2666,13 +2661,11 @@ int stmpc_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_c
     env::ECfg e;
     sim::Cfg sc;
     DevP dp;
-    TRY(make_envcfg(ec, &e));
-    if (obs_stride < e.obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
-    if (e.mode != c->env.mode) return fail(STMPC_EINVAL, "env_cfg.action_mode differs from the one the context was reset with (stmpc_env_reset_device)");
+    TRY(env_step_begin(c, ec, obs_stride, "stmpc_env_reset_device", &e));
     TRY(make_simcfg(g, &sc));
     sim_route_of(c, &sc);
     TRY(make_devp(p, &dp));
-    e.seed = sc.seed; e.log_cap = c->env.log_cap; e.n_actions = c->env.n_actions; e.actions = c->env.actions.as<double>();
+    e.seed = sc.seed;
     HIPCHK(hipSetDevice(c->device));
     const dim3 grid((N + 63) / 64), block(64);
     const sim::State s = c->sim.state();

@@ -225,3 +225,51 @@ def test_gpu_combined_without_vehicles_and_probe_state_fallback(gpu_ctx, restore
     d = combined.decide_batch(near_end, stub_policy, gpu_ctx)
     ts = d["test_states"][0]
     assert ts is not None and ts.ego_position[0] > pkg.Settings.STOP_X and len(ts.other_xs) == 2 and len(d["rollout_s"][0]) == 2
+
+
+@pytest.mark.gpu
+def test_gpu_sparse_controller_solve_none_all_and_one_taken(gpu_ctx, restore_settings):
+    """The plain entry's sparse controller solve at its edges, on rows picked by the reference's own decisions: 64 states it leaves to the policy (nothing
+    selected: no controller launch at all), up to 64 it takes over (everything selected) and a single taken-over state.  Decisions and commands are the
+    dense run's bit for bit, the counters give the number of solves, and a controller command exists exactly for the rows that were taken over."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, combined
+    from rl_mpc_lanemerging_amd.prediction import pack_states
+    g = load_golden("golden_combined.npz")
+    kept, taken = np.nonzero(g["reason"] == 0)[0], np.nonzero(g["reason"] != 0)[0]
+    assert len(kept) > 0 and len(taken) > 0
+    S = _apply_settings(g).Settings
+    states = _states_from(g, g["ego"].shape[0])
+    params = _capi.Params.from_settings(S)
+    R = max(int(S.ROLLOUT_LENGTH), 1)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for rows in (kept[:64], taken[:64], taken[:1]):
+        sub = [states[i] for i in rows]
+        n, M = len(sub), int((g["reason"][rows] != 0).sum())
+        ego5, k, ox, ov = pack_states(sub)
+        K = ox.shape[1]
+        d_ego5, d_k, d_ox, d_ov = (torch.as_tensor(a, device=dev) for a in (ego5, k, ox, ov))
+
+        def policy(step, cur_ego4, d_k_, cur_ox, cur_ov, cur_oa):       # the stand-in policy on the host, asked as decide_batch asks it
+            live = np.ones(n, bool) if step == 1 else gpu_ctx.combined_read_state(n, K, R, after_decide=False)["live"].astype(bool)
+            e4, xo, vo, ao = cur_ego4.cpu().numpy(), cur_ox.cpu().numpy(), cur_ov.cpu().numpy(), cur_oa.cpu().numpy()
+            act = np.zeros(n)
+            for j in np.nonzero(live)[0]:
+                act[j] = stub_policy(combined._unpack(e4, k, xo, vo, ao, j))
+            return torch.as_tensor(act, device=dev)
+
+        res = {}
+        for sparse in (False, True):
+            gpu_ctx.combined_counts(reset=True)
+            d = combined.decide_batch_device(gpu_ctx, params, _capi.CombinedCfg.from_settings(S, sparse_control=sparse), d_ego5, d_k, d_ox, d_ov, policy, None,
+                                             torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            gpu_ctx.check_error()
+            res[sparse] = {q: d[q].cpu().numpy() for q in ("takeover", "reason", "speed")}
+            assert gpu_ctx.combined_counts() == (n, M if sparse else n)
+        st_speed = gpu_ctx.combined_read_state(n, K, R)["st_speed"]         # (of the sparse run, the last one)
+        assert np.array_equal(res[True]["reason"], g["reason"][rows])
+        for q in ("takeover", "reason"):
+            assert np.array_equal(res[True][q], res[False][q]), (n, M, q)
+        assert np.array_equal(res[True]["speed"].view(np.uint64), res[False]["speed"].view(np.uint64)), (n, M)
+        assert np.array_equal(np.isnan(st_speed), g["reason"][rows] == 0), (n, M)
