@@ -884,6 +884,45 @@ int stmpc_first_step_counts(stmpc_ctx *ctx, int64_t *decisions, int64_t *takeove
 int stmpc_speed_from_jerk_device(stmpc_ctx *ctx, const stmpc_params *p, double tick_length, int N, const double *d_ego5, const double *d_jerk,
                                  double *d_speed, void *stream);
 
+/*
+ * Reward groups: one vector environment split into R groups of n_per_reward_group consecutive environments, each rewarded under its own stmpc_env_cfg, in
+ * the launches of a lone env (three per step).  The reference treats the reward as a per-run setting and compares rewards one TRAIN_DDPG run per setting:
+ * dqn.get_reward_function and the four functions it picks (dqn.py:449-563, rl.py:168-174), the weights every file under its configs/ overrides, and the
+ * env's INVALID_ACTION_PENALTY and action handling (merge_gym.py:25,83-140).  (Additive: new entries only, no signature or struct of ABI 8 changes, so
+ * STMPC_ABI_VERSION stays 8.)
+ * Rows [r * n_per_reward_group, (r + 1) * n_per_reward_group) of a grouped env are, bit for bit and through every autoreset, those rows of the env reset
+ * through the plain entries with env_cfgs[r] -- observations, rewards, terminated / truncated, final observation and statistics, log rows, returns.  On a
+ * world of traffic groups cell c pairs traffic c with reward c, so group r is the lone env of n_per_reward_group environments made from sim_cfgs[r] and
+ * env_cfgs[r]; an ungrouped world is one world of R * n_per_reward_group environments whatever the rewards (the reward never feeds back into the world).
+ *   May differ between groups: reward_function, crash_reward, success_reward, time_reward, wt_smooth, wt_safe, wt_efficient, alt_v_weight, alt_a_weight,
+ *                   alt_j_weight, alt_d_weight, min_follow_distance, desired_speed (the reward's use of it), invalid_action_penalty.
+ *   Must be equal (else STMPC_EINVAL naming the field): action_mode, action_values and n_action_values, tick_length, minimum_negative_jerk,
+ *                   maximum_positive_jerk, max_negative_acceleration, max_positive_acceleration, max_speed, car_length, autoreset, log_capacity, features
+ *                   (equal contents, or the same pointer).
+ *   stmpc_reward_groups_env_reset_device (dqn.py:449-563, rl.py:168-174, merge_gym.py:25,83-140)   stmpc_env_reset_device / stmpc_env_reset_groups_device
+ *                   with a table of R = 1 ... STMPC_ENV_REWARD_GROUPS_MAX env cfgs: validates everything, initialises the world -- G = 0: an ungrouped
+ *                   world of R * n_per_reward_group environments from sim_cfgs[0]; G >= 1: traffic groups, where R must equal G and n_per_reward_group
+ *                   n_per_traffic_group --, uploads the table (synchronises on `stream` for it) and resets every environment.  A refused call changes
+ *                   nothing.  stmpc_sim_init_device / stmpc_sim_init_groups_device on the context end the env and its grouping.
+ *   stmpc_reward_groups_env_step_device (dqn.py:449-563, rl.py:168-174, merge_gym.py:25,83-140)   stmpc_env_step_device on such an env, for either kind
+ *                   of world: the arguments of stmpc_env_step_groups_device.  The context's table is read on the device (no copy, no synchronisation);
+ *                   env_cfg supplies the shared fields, its reward fields are not read.  STMPC_EINVAL on an env without reward groups -- and the plain
+ *                   stmpc_env_step_device / stmpc_env_step_groups_device return STMPC_EINVAL on an env with them, which they would reward with one cfg.
+ *   stmpc_reward_groups_env_reward_device (dqn.py:449-563, rl.py:168-174, merge_gym.py:25,83-140)   stmpc_env_reward_device with the context's table: state
+ *                   e is rewarded under group e / n_per_reward_group; N <= R * n_per_reward_group.
+ *   stmpc_reward_groups_split (dqn.py:449-563, rl.py:168-174, merge_gym.py:25,83-140)   the current split (0, 0: one reward for every environment, or no env)
+ */
+#define STMPC_ENV_REWARD_GROUPS_MAX 64
+int stmpc_reward_groups_env_reset_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int G, int n_per_traffic_group,
+                                         const stmpc_env_cfg *env_cfgs, int R, int n_per_reward_group, float *d_obs, int obs_stride, void *stream);
+int stmpc_reward_groups_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_env_cfg *env_cfg, int N, const void *d_action, float *d_obs,
+                                        int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs,
+                                        double *d_final_stats, void *stream);
+int stmpc_reward_groups_env_reward_device(stmpc_ctx *ctx, const stmpc_env_cfg *env_cfg, int N, int Kmax, const double *d_ego4, const int32_t *d_k,
+                                          const double *d_ox, const double *d_ov, const double *d_oa, const double *d_jerk, const int32_t *d_crashed,
+                                          const int32_t *d_arrived, double *d_reward, void *stream);
+int stmpc_reward_groups_split(stmpc_ctx *ctx, int *R, int *n_per_group);
+
 /* Device arithmetic probe used by the parity tests: out[i] = a[i] op b[i] evaluated on the GPU
  * with the kernels' compile flags. op: 0 div, 1 sqrt(a), 2 mul, 3 add, 4 fma(a,a,b*b), 5 the five-operation
  * quotient a/b of the FASTDIV kernels, 6 their two-operation quotient a/b.  HOST pointers. */

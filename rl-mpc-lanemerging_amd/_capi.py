@@ -191,6 +191,26 @@ class EnvCfg(C.Structure):
         return c
 
 
+class EnvCfgTable:
+    """A contiguous ``stmpc_env_cfg[R]`` for the reward-group entries, from a sequence of ``EnvCfg`` (kept alive with their action tables and
+    feature cfgs); indexing gives the caller's ``EnvCfg`` objects."""
+
+    def __init__(self, cfgs):
+        self.cfgs = list(cfgs)
+        self.array = (EnvCfg * max(len(self.cfgs), 1))()
+        for i, c in enumerate(self.cfgs):
+            C.memmove(C.byref(self.array, i * C.sizeof(EnvCfg)), C.byref(c), C.sizeof(EnvCfg))
+
+    def __len__(self):
+        return len(self.cfgs)
+
+    def __getitem__(self, i):
+        return self.cfgs[i]
+
+    def __iter__(self):
+        return iter(self.cfgs)
+
+
 class DDPGCfg(C.Structure):
     """``stmpc_ddpg_cfg`` (include/stmpc.h): shapes, replay size and the constants of the DDPG update (defaults: the ``all`` preset's)."""
     _fields_ = [("n_obs", C.c_int32), ("h1", C.c_int32), ("h2", C.c_int32), ("batch", C.c_int32), ("capacity", C.c_int32), ("reserved0", C.c_int32),
@@ -229,6 +249,7 @@ EXPORTS = (
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
     "stmpc_solve_batch_groups_device", "stmpc_solve_batch_groups", "stmpc_st_control_groups_device", "stmpc_solver_groups_sim_step_device",
     "stmpc_solver_groups_sim_init_device",
+    "stmpc_reward_groups_env_reset_device", "stmpc_reward_groups_env_step_device", "stmpc_reward_groups_env_reward_device", "stmpc_reward_groups_split",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
 ENV_CONTINUOUS_JERK, ENV_JERK, ENV_ACCELERATION = 0, 1, 2                                 # STMPC_ENV_*
@@ -238,6 +259,7 @@ DDPG_ROW, DDPG_NCOUNTERS = 68, 8      # STMPC_DDPG_ROW, STMPC_DDPG_NCOUNTERS
 DDPG_POP_MAX = 64                     # STMPC_DDPG_POP_MAX
 SIM_GROUPS_MAX = 64                   # STMPC_SIM_GROUPS_MAX
 SOLVER_GROUPS_MAX = 512               # STMPC_SOLVER_GROUPS_MAX
+ENV_REWARD_GROUPS_MAX = 64            # STMPC_ENV_REWARD_GROUPS_MAX
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
 REC_HDR, REC_NQ, REC_MAX_DEPTH, REC_MAX_EDGES = 10, 4, 64, 32      # STMPC_REC_HDR, STMPC_REC_NQ, STMPC_REC_MAX_DEPTH, STMPC_REC_MAX_EDGES
 REC_COLUMNS = ("tick", "x", "y", "v", "a", "s", "k", "cmd", "takeover", "jerk")      # the first STMPC_REC_HDR columns of a record
@@ -344,6 +366,10 @@ def load():
     lib.stmpc_sim_groups.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.stmpc_env_reset_groups_device.argtypes = [vp, pp, sp, C.c_int, C.c_int, ep, vp, C.c_int, vp]
     lib.stmpc_env_step_groups_device.argtypes = [vp, pp, ep, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.stmpc_reward_groups_env_reset_device.argtypes = [vp, pp, sp, C.c_int, C.c_int, ep, C.c_int, C.c_int, vp, C.c_int, vp]
+    lib.stmpc_reward_groups_env_step_device.argtypes = [vp, pp, ep, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.stmpc_reward_groups_env_reward_device.argtypes = [vp, ep, C.c_int, C.c_int] + [vp] * 9 + [vp]
+    lib.stmpc_reward_groups_split.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.stmpc_env_episode_seed.argtypes = [C.c_uint64, C.c_uint32]
     lib.stmpc_env_episode_seed.restype = C.c_uint64
     lib.stmpc_st_control_batch_device.argtypes = [vp, pp, C.c_double, C.c_int, C.c_int] + [vp] * 10 + [vp]
@@ -978,6 +1004,34 @@ class Context:
     def env_reward(self, env_cfg, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed=0, d_arrived=0, d_reward=0, stream=0):
         self._chk(self._lib.stmpc_env_reward_device(self._h, C.byref(env_cfg), int(N), int(Kmax), d_ego4, d_k, d_ox, 0, 0, d_jerk, d_crashed, d_arrived,
                                                     d_reward, stream))
+
+    def env_reset_reward_groups(self, params, sim_cfgs, n_per_traffic_group, env_cfgs, n_per_reward_group, d_obs, obs_stride, stream=0):
+        """``stmpc_reward_groups_env_reset_device``: ``env_cfgs`` is an ``EnvCfgTable`` (or a sequence of ``EnvCfg``), one per reward group;
+        ``sim_cfgs`` is one ``SimCfg`` (an ungrouped world, ``n_per_traffic_group`` unused) or a ``SimCfgTable`` / sequence (traffic groups)."""
+        e = env_cfgs if isinstance(env_cfgs, EnvCfgTable) else EnvCfgTable(env_cfgs)
+        if isinstance(sim_cfgs, SimCfg):
+            sims, G = C.byref(sim_cfgs), 0
+        else:
+            t = sim_cfgs if isinstance(sim_cfgs, SimCfgTable) else SimCfgTable(sim_cfgs)
+            sims, G = t.array, len(t)
+        self._chk(self._lib.stmpc_reward_groups_env_reset_device(self._h, C.byref(params), sims, G, int(n_per_traffic_group), e.array, len(e),
+                                                                 int(n_per_reward_group), d_obs, int(obs_stride), stream))
+
+    def env_step_reward_groups(self, params, env_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs=0, d_final_stats=0,
+                               stream=0):
+        self._chk(self._lib.stmpc_reward_groups_env_step_device(self._h, C.byref(params), C.byref(env_cfg), int(N), d_action, d_obs, int(obs_stride), d_reward,
+                                                                d_terminated, d_truncated, d_final_obs, d_final_stats, stream))
+
+    def env_reward_reward_groups(self, env_cfg, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed=0, d_arrived=0, d_reward=0, stream=0):
+        """``stmpc_reward_groups_env_reward_device``: state e is rewarded under reward group ``e // n_per_reward_group`` of the context's env."""
+        self._chk(self._lib.stmpc_reward_groups_env_reward_device(self._h, C.byref(env_cfg), int(N), int(Kmax), d_ego4, d_k, d_ox, 0, 0, d_jerk, d_crashed,
+                                                                  d_arrived, d_reward, stream))
+
+    def env_reward_groups(self):
+        """(R, n_per_reward_group) of the context's env; (0, 0) without reward groups."""
+        r, n = C.c_int(0), C.c_int(0)
+        self._chk(self._lib.stmpc_reward_groups_split(self._h, C.byref(r), C.byref(n)))
+        return r.value, n.value
 
     def env_episode_ticks(self, N, d_ticks, stream=0):
         """Ticks of each environment's current episode into a device int32 [N] array (asynchronous)."""

@@ -15,6 +15,7 @@
 #include "stmpc_cc_groups_kernels.hpp"
 #include "stmpc_fs_kernels.hpp"
 #include "stmpc_solver_groups_kernels.hpp"
+#include "stmpc_env_groups_kernels.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -262,8 +263,11 @@ struct stmpc_ctx {
     } sim;
     // vector environment on the simulator (stmpc_env_*)
     struct Env {
-        DevBuf ep, prev_a, pjerk, inv, ret, cmd, live, vx, vv, va, k, log, log_n, actions;
+        DevBuf ep, prev_a, pjerk, inv, ret, cmd, live, vx, vv, va, k, log, log_n, actions, rtab;
         int N = 0, n_actions = 0, log_cap = 0, mode = -1;    // (N = 0: no environment; a plain stmpc_sim_init_device invalidates it)
+        int R = 0, n_per_rg = 0;      // reward groups (stmpc_reward_groups_env_reset_device): `rtab` holds R env::RewardRow; 0, 0 = one reward for all
+        sim::Cfg rg_sc{};             // the ungrouped world of an env with reward groups (its step entry takes no sim cfg)
+        env::RewardTab reward_tab() const { return env::RewardTab{rtab.as<env::RewardRow>(), n_per_rg}; }
         int ensure(int n_, int cap) {
             const size_t n = (size_t)n_, KS = sim::KS;
             TRY(ep.ensure(n * 4)); TRY(prev_a.ensure(n * 8)); TRY(pjerk.ensure(n * 8)); TRY(inv.ensure(n * 8)); TRY(ret.ensure(n * 8)); TRY(cmd.ensure(n * 8));
@@ -2378,6 +2382,7 @@ int check_grouped_world(stmpc_ctx *c, int N) {
 }
 int sim_init_groups(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream, int G_max);
 const char *const GROUPED_WORLD = "the world has traffic groups (stmpc_sim_init_groups_device): one cfg would step every group; use the grouped step entry";
+const char *const REWARD_GROUPED_ENV = "the env has reward groups (stmpc_reward_groups_env_reset_device): one cfg would reward every group; use stmpc_reward_groups_env_step_device";
 }  // namespace
 
 extern "C" {
@@ -2392,6 +2397,7 @@ int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *str
     c->sim.N = N;
     ++c->sim.generation;
     c->env.N = 0;                 // (the vector environment's bookkeeping no longer describes this world; stmpc_env_reset_device sets it again)
+    c->env.R = 0; c->env.n_per_rg = 0;
     c->sim.G = 0; c->sim.n_per_group = 0;      // (nor does the table of traffic groups)
     TRY(sim_route_upload(c, g, stream));
     sim_route_of(c, &sc);
@@ -2451,6 +2457,7 @@ int sim_init_groups(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_gr
     c->sim.N = N;
     ++c->sim.generation;
     c->env.N = 0;
+    c->env.R = 0; c->env.n_per_rg = 0;
     c->sim.G = 0; c->sim.n_per_group = 0;
     TRY(sim_route_upload(c, &cfgs[0], stream));
     for (auto &sc : table) sim_route_of(c, &sc);
@@ -2632,6 +2639,7 @@ int stmpc_env_step_groups_device(stmpc_ctx *c, const stmpc_params *p, const stmp
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     TRY(check_grouped_world(c, N));
     if (N != c->env.N) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_groups_device");
+    if (c->env.R) return fail(STMPC_EINVAL, REWARD_GROUPED_ENV);
     if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     env::ECfg e;
     DevP dp;
@@ -2657,6 +2665,7 @@ int stmpc_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_c
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device");
     if (c->sim.G) return fail(STMPC_EINVAL, GROUPED_WORLD);
+    if (c->env.R) return fail(STMPC_EINVAL, REWARD_GROUPED_ENV);
     if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     env::ECfg e;
     sim::Cfg sc;
@@ -2714,6 +2723,150 @@ int stmpc_env_episode_ticks_device(stmpc_ctx *c, int N, int32_t *d_ticks, void *
     if (N != c->env.N || N < 1 || !d_ticks) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device, or NULL pointer");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(d_ticks, c->sim.ticks.p, (size_t)N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return STMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- reward groups (stmpc_reward_groups_*): kernels in stmpc_env_groups_kernels.hpp ----
+// The reference's per-run reward settings (dqn.py:449-563, rl.py:168-174, merge_gym.py:25,83-140) as a group axis of one vector environment.
+namespace {
+// Every cfg valid, and equal in what the shared ECfg, the one action table, the one log and the one observation hold.  Changes nothing; `rows` receives
+// the R table rows.
+int check_reward_groups(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *cfgs, int R, int n_per_group, const float *d_obs, int obs_stride,
+                        std::vector<env::RewardRow> *rows, env::ECfg *shared) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (!cfgs) return fail(STMPC_EINVAL, "env cfgs is NULL");
+    if (R < 1 || R > STMPC_ENV_REWARD_GROUPS_MAX) return fail(STMPC_EINVAL, "R must be 1 ... STMPC_ENV_REWARD_GROUPS_MAX (64) reward groups");
+    if (n_per_group < 1) return fail(STMPC_EINVAL, "n_per_reward_group must be positive");
+    if ((int64_t)R * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, "R * n_per_reward_group out of range");
+    rows->resize((size_t)R);
+    for (int r = 0; r < R; ++r) {
+        env::ECfg e;
+        TRY(env_reset_check(c, p, &cfgs[r], d_obs, obs_stride, &e));
+        if (r == 0) *shared = e;
+        (*rows)[r] = env::RewardRow{e.crash_r, e.success_r, e.time_r, e.wt_smooth, e.wt_safe, e.wt_eff, e.alt_v, e.alt_a, e.alt_j, e.alt_d, e.min_follow,
+                                    e.desired_speed, e.penalty, e.reward, 0};
+    }
+    const stmpc_env_cfg &a = cfgs[0];
+    for (int r = 1; r < R; ++r) {
+        const stmpc_env_cfg &b = cfgs[r];
+#define SAME(field) if (!(a.field == b.field)) return fail(STMPC_EINVAL, "reward groups must share " #field " (it differs in group " + std::to_string(r) + ")")
+        SAME(action_mode); SAME(n_action_values); SAME(tick_length); SAME(minimum_negative_jerk); SAME(maximum_positive_jerk); SAME(max_negative_acceleration);
+        SAME(max_positive_acceleration); SAME(max_speed); SAME(car_length); SAME(autoreset); SAME(log_capacity);
+#undef SAME
+        if (a.action_mode != STMPC_ENV_CONTINUOUS_JERK && a.action_values != b.action_values &&
+            memcmp(a.action_values, b.action_values, (size_t)a.n_action_values * 8) != 0)
+            return fail(STMPC_EINVAL, "reward groups must share action_values (they differ in group " + std::to_string(r) + ")");
+        if (a.features != b.features && memcmp(a.features, b.features, sizeof *a.features) != 0)
+            return fail(STMPC_EINVAL, "reward groups must share features (they differ in group " + std::to_string(r) + ")");
+    }
+    return STMPC_OK;
+}
+// the checks every reward-groups step or reward entry starts with
+int check_reward_grouped_env(const stmpc_ctx *c) {
+    if (c->env.N < 1 || c->env.R < 1)
+        return fail(STMPC_EINVAL, "the env has no reward groups (stmpc_reward_groups_env_reset_device): use the plain or the traffic-groups step entry");
+    return STMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_reward_groups_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int G, int n_per_traffic_group,
+                                         const stmpc_env_cfg *env_cfgs, int R, int n_per_reward_group, float *d_obs, int obs_stride, void *stream) {
+    std::vector<env::RewardRow> rows;
+    std::vector<sim::Cfg> world;
+    env::ECfg e;
+    TRY(check_reward_groups(c, p, env_cfgs, R, n_per_reward_group, d_obs, obs_stride, &rows, &e));
+    const int N = R * n_per_reward_group;
+    if (G < 0) return fail(STMPC_EINVAL, "G must not be negative (0: an ungrouped world from sim_cfgs[0])");
+    TRY(check_groups(sim_cfgs, G ? G : 1, G ? n_per_traffic_group : N, &world));          // (G = 0: the one cfg and its route, as a table of one)
+    if (G && (G != R || n_per_traffic_group != n_per_reward_group))
+        return fail(STMPC_EINVAL, "the reward groups must coincide with the world's traffic groups (cell c pairs traffic c with reward c): R must equal G and "
+                                  "n_per_reward_group n_per_traffic_group");
+    HIPCHK(hipSetDevice(c->device));
+    TRY(c->env.rtab.ensure((size_t)STMPC_ENV_REWARD_GROUPS_MAX * sizeof(env::RewardRow)));   // (its full size once: never reallocated under a running kernel)
+    // nothing has changed so far
+    if (G) { TRY(stmpc_sim_init_groups_device(c, sim_cfgs, G, n_per_traffic_group, stream)); }
+    else { TRY(stmpc_sim_init_device(c, &sim_cfgs[0], N, stream)); }
+    TRY(env_reset_begin(c, &env_cfgs[0], N, &e, stream));
+    HIPCHK(hipMemcpyAsync(c->env.rtab.p, rows.data(), rows.size() * sizeof(env::RewardRow), hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));           // (rows is a local; the step entries read the device copy)
+    c->env.R = R; c->env.n_per_rg = n_per_reward_group;
+    if (G) {
+        e.seed = 0;
+        hipLaunchKernelGGL(env::k_env_reset_groups, dim3((n_per_traffic_group + 63) / 64, G), dim3(64), 0, (hipStream_t)stream, e, c->sim.groups.as<sim::Cfg>(),
+                           n_per_traffic_group, c->sim.state(), env_state(c), d_obs, obs_stride);
+    } else {
+        sim::Cfg sc = world[0];
+        sim_route_of(c, &sc);
+        c->env.rg_sc = sc;
+        e.seed = sc.seed;
+        hipLaunchKernelGGL(env::k_env_reset, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, sc, N, c->sim.state(), env_state(c), d_obs, obs_stride);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_reward_groups_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
+                                        double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(check_reward_grouped_env(c));
+    if (N != c->env.N || N != c->sim.N) return fail(STMPC_EINVAL, "N does not match stmpc_reward_groups_env_reset_device (R * n_per_reward_group)");
+    if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    env::ECfg e;
+    DevP dp;
+    TRY(env_step_begin(c, ec, obs_stride, "stmpc_reward_groups_env_reset_device", &e));
+    TRY(make_devp(p, &dp));
+    HIPCHK(hipSetDevice(c->device));
+    const dim3 grid((N + 63) / 64), block(64);
+    const sim::State s = c->sim.state();
+    const env::EState es = env_state(c);
+    const env::RewardTab tab = c->env.reward_tab();
+    hipLaunchKernelGGL(env::k_env_act_rg, grid, block, 0, (hipStream_t)stream, e, tab, N, s, es, d_action);
+    if (c->sim.G) {
+        const int npg = c->sim.n_per_group;
+        const dim3 ggrid((npg + 63) / 64, c->sim.G);
+        const sim::Cfg *groups = c->sim.groups.as<sim::Cfg>();
+        e.seed = 0;
+        hipLaunchKernelGGL(sim::k_sim_step_groups, ggrid, block, 0, (hipStream_t)stream, dp, groups, npg, s, (const double *)es.cmd, p->crash_min_s);
+        hipLaunchKernelGGL(env::k_env_post_rg_groups, ggrid, block, 0, (hipStream_t)stream, e, tab, groups, npg, s, es, d_obs, obs_stride, d_reward, d_terminated,
+                           d_truncated, d_final_obs, d_final_stats);
+    } else {
+        const sim::Cfg sc = c->env.rg_sc;
+        e.seed = sc.seed;
+        hipLaunchKernelGGL(sim::k_sim_step, grid, block, 0, (hipStream_t)stream, dp, sc, N, s, (const double *)es.cmd, p->crash_min_s);
+        hipLaunchKernelGGL(env::k_env_post_rg, grid, block, 0, (hipStream_t)stream, e, tab, sc, N, s, es, d_obs, obs_stride, d_reward, d_terminated, d_truncated,
+                           d_final_obs, d_final_stats);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_reward_groups_env_reward_device(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, int Kmax, const double *d_ego4, const int32_t *d_k, const double *d_ox,
+                                          const double *d_ov, const double *d_oa, const double *d_jerk, const int32_t *d_crashed, const int32_t *d_arrived,
+                                          double *d_reward, void *stream) {
+    (void)d_ov; (void)d_oa;
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(check_reward_grouped_env(c));
+    env::ECfg e;
+    TRY(make_envcfg(ec, &e));
+    if (N < 0 || N > c->env.N || Kmax < 0 || Kmax > sim::KS) return fail(STMPC_EINVAL, "N or Kmax out of range (N <= R * n_per_reward_group, Kmax <= 64)");
+    if (N == 0) return STMPC_OK;
+    if (!d_ego4 || !d_k || !d_jerk || !d_reward || (Kmax > 0 && !d_ox)) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(env::k_env_reward_rg, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, c->env.reward_tab(), N, Kmax, d_ego4, d_k, d_ox, d_jerk,
+                       d_crashed, d_arrived, d_reward);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_reward_groups_split(stmpc_ctx *c, int *R, int *n_per_group) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    const bool on = c->env.N >= 1;
+    if (R) *R = on ? c->env.R : 0;
+    if (n_per_group) *n_per_group = on ? c->env.n_per_rg : 0;
     return STMPC_OK;
 }
 

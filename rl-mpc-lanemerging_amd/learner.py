@@ -369,7 +369,13 @@ class DDPGPopulation:
 
     ``env`` may have traffic groups (``MergeVecEnv(traffic=[...])``) when there are as many as members: member m then trains on traffic m -- the
     reference's ``train_{traffic}_{seed}.json`` runs for several traffic types in one launch sequence -- and stays bit-identical to a lone
-    learner on a lone env of that traffic."""
+    learner on a lone env of that traffic.
+
+    ``env`` may have reward groups (``MergeVecEnv(rewards=[...])``) when there are as many as members (``env.R == P``, so that
+    ``n_per_member == env.n_per_reward_group``): member m's slice is reward group m, so member m trains under reward m -- the reference's
+    reward-shaping comparison, one ``TRAIN_DDPG`` run per config, in one launch sequence -- and stays bit-identical to a lone learner fed that
+    slice of the lone env made under reward m.  Nothing else changes: the population reads the env's reward tensor row by row.
+    ``evaluate_members`` / ``episodes.summary_by_member`` then compare the policies the rewards produced on one common report."""
 
     def __init__(self, env, cfgs, seeds=None, init=None, ctx=None):
         if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], DDPGConfig):
@@ -384,6 +390,9 @@ class DDPGPopulation:
         if getattr(env, "sim_cfgs", None) is not None and env.G != P:
             # (equal sizes: G == P makes group m's environments member m's)
             raise ValueError("the env has %d traffic groups, the population %d members: member m trains on traffic m, so they must coincide" % (env.G, P))
+        if getattr(env, "R", 0) and env.R != P:
+            # (equal sizes: R == P makes reward group m's environments member m's, n_per_member == n_per_reward_group)
+            raise ValueError("the env has %d reward groups, the population %d members: member m trains under reward m, so they must coincide" % (env.R, P))
         self.seeds = list(range(P)) if seeds is None else [int(x) for x in seeds]
         inits = list(init) if isinstance(init, (list, tuple)) else [init] * P
         if len(self.seeds) != P or len(inits) != P:

@@ -51,6 +51,42 @@ def env_cfg(env_id=None, reward=None, autoreset=True, S=Settings, log_capacity=0
     return _capi.EnvCfg.from_settings(S, ENV_IDS[env_id], REWARD_IDS[reward], table, autoreset, log_capacity)
 
 
+#: what a reward group may set: ``REWARD_FUNCTION`` and these ``Settings`` names -> the ``stmpc_env_cfg`` fields that may differ between reward groups
+REWARD_GROUP_KEYS = {"CRASH_REWARD": "crash_reward", "SUCCESS_REWARD": "success_reward", "TIME_REWARD": "time_reward", "WT_SMOOTH": "wt_smooth",
+                     "WT_SAFE": "wt_safe", "WT_EFFICIENT": "wt_efficient", "ALT_V_WEIGHT": "alt_v_weight", "ALT_A_WEIGHT": "alt_a_weight",
+                     "ALT_J_WEIGHT": "alt_j_weight", "ALT_D_WEIGHT": "alt_d_weight", "MIN_FOLLOW_DISTANCE": "min_follow_distance",
+                     "DESIRED_SPEED": "desired_speed", "INVALID_ACTION_PENALTY": "invalid_action_penalty"}
+
+
+def reward_cfgs(rewards, env_id=None, autoreset=True, S=Settings, log_capacity=0):
+    """One ``stmpc_env_cfg`` per reward group (a ``_capi.EnvCfgTable`` for the ``stmpc_reward_groups_*`` entries): ``rewards`` is a list of
+    dicts, each setting ``REWARD_FUNCTION`` and any of ``REWARD_GROUP_KEYS`` over ``S`` (the global ``Settings``, which is read and never
+    written) -- what the reference's configs/*.json override per run (dqn.py:449-460, merge_gym.py:25).  Everything else -- the env, its action
+    table, the tick, the limits, autoreset, the log, the observation -- is ``S``'s for every group.  ValueError for any other key, an unknown
+    reward function, an empty list and more than ``ENV_REWARD_GROUPS_MAX`` groups."""
+    rewards = list(rewards)
+    if not 1 <= len(rewards) <= _capi.ENV_REWARD_GROUPS_MAX:
+        raise ValueError("rewards must name 1 ... %d groups, not %d" % (_capi.ENV_REWARD_GROUPS_MAX, len(rewards)))
+    table = []
+    for group in rewards:
+        if not isinstance(group, dict):
+            raise ValueError("a reward group is a dict of settings, not %r" % (group,))
+        unknown = [k for k in group if k != "REWARD_FUNCTION" and k not in REWARD_GROUP_KEYS]
+        if unknown:
+            raise ValueError("a reward group may set REWARD_FUNCTION, %s, not %s" % (", ".join(REWARD_GROUP_KEYS), ", ".join(map(str, unknown))))
+        c = env_cfg(env_id, group.get("REWARD_FUNCTION"), autoreset, S, log_capacity)
+        for key, value in group.items():
+            if key != "REWARD_FUNCTION":
+                setattr(c, REWARD_GROUP_KEYS[key], float(value))
+        table.append(c)
+    return _capi.EnvCfgTable(table)
+
+
+def reward_settings(group, S=Settings):
+    """``S`` overlaid with one reward group's dict: a class to hand to the ``rewards.py`` twins as ``S=``."""
+    return type("RewardGroupSettings", (S,), dict(group))
+
+
 def observation_bounds(S=Settings):
     """(low, high) of JerkEnv's observation space, merge_gym.py:41-79."""
     n_cars = S.CARS_AHEAD + S.CARS_BEHIND
@@ -82,9 +118,19 @@ class MergeVecEnv:
 
     ``traffic``: None, or a list as ``episodes.sim_cfgs`` takes: ``G = len(traffic)`` traffic groups of ``n / G`` consecutive environments
     (``stmpc_env_reset_groups_device`` / ``stmpc_env_step_groups_device``, the launches of an ungrouped env), group g bit-identical -- through
-    every autoreset -- to a lone ``MergeVecEnv`` of ``n / G`` environments with that traffic and group g's seed (``episodes.sim_cfgs``)."""
+    every autoreset -- to a lone ``MergeVecEnv`` of ``n / G`` environments with that traffic and group g's seed (``episodes.sim_cfgs``).
 
-    def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, traffic=None):
+    ``rewards``: None, or a list as ``reward_cfgs`` takes: ``R = len(rewards)`` reward groups of ``n / R`` consecutive environments, each rewarded
+    under its own reward function and weights (``stmpc_reward_groups_env_reset_device`` / ``stmpc_reward_groups_env_step_device``, the three
+    launches of a lone env) -- the reward-shaping sweep the reference runs as one ``TRAIN_DDPG`` per config.  Rows
+    ``[r * n / R, (r + 1) * n / R)`` are bit-identical -- through every autoreset -- to those rows of the lone ``MergeVecEnv`` made with group r's
+    values in the Settings.  With ``traffic`` too the counts must coincide (cell c pairs traffic c with reward c) and group r is the lone env of
+    ``n / R`` environments with that traffic and that reward; without it the world is one world of ``n`` environments whatever the rewards (pass
+    ``traffic=[t] * R`` for R copies of one lone world under R rewards: common random numbers).  ``reward`` is then ignored;
+    ``reward_names`` lists the groups' functions.  A ``learner.DDPGPopulation`` of R members trains member m under reward m, and
+    ``learner.evaluate_members`` / ``episodes.summary_by_member`` compare the resulting policies on one common report."""
+
+    def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, traffic=None, rewards=None):
         import torch
         self.torch = torch
         self.env_id = Settings.GYM_ENVIRONMENT if env_id is None else env_id
@@ -96,6 +142,17 @@ class MergeVecEnv:
         self.traffic = list(traffic) if traffic is not None else None
         self.G, self.n_per_group = episodes._check_traffic(self.n, self.traffic, None) if self.traffic is not None else (0, 0)
         self.sim_cfgs = episodes.sim_cfgs(self.traffic, seed, float(Settings.MAX_EPISODE_LENGTH)) if self.traffic is not None else None
+        self.rewards = [dict(r) for r in rewards] if rewards is not None else None
+        self.reward_cfgs = reward_cfgs(self.rewards, self.env_id, autoreset, Settings, log_capacity) if self.rewards is not None else None
+        self.R = len(self.rewards) if self.rewards is not None else 0
+        if self.R and self.n % self.R:
+            raise ValueError("n = %d environments do not divide into %d reward groups of equal size" % (self.n, self.R))
+        self.n_per_reward_group = self.n // self.R if self.R else 0
+        if self.R and self.traffic is not None and self.R != self.G:
+            raise ValueError("the env has %d traffic groups and %d reward groups: cell c pairs traffic c with reward c, so they must coincide" % (self.G, self.R))
+        self.reward_names = [r.get("REWARD_FUNCTION", Settings.REWARD_FUNCTION) for r in self.rewards] if self.R else [self.reward_name]
+        if self.R:
+            self.cfg = self.reward_cfgs[0]                   # (the shared fields: what the step entry reads of it)
         self.ctx = ctx if ctx is not None else _capi.Context(-1)
         self.params = _capi.Params.from_settings(Settings)
         self.sim_cfg = self.sim_cfgs[0] if self.sim_cfgs is not None else episodes.sim_cfg(seed, float(Settings.MAX_EPISODE_LENGTH))
@@ -122,7 +179,10 @@ class MergeVecEnv:
         """Every environment back to episode 0 (``stmpc_env_reset_device``): the observations of the start states [n][obs_dim] float32."""
         self._cur = 0
         obs = self._obs[0]
-        if self.sim_cfgs is not None:
+        if self.R:
+            self.ctx.env_reset_reward_groups(self.params, self.sim_cfgs if self.sim_cfgs is not None else self.sim_cfg, self.n_per_group, self.reward_cfgs,
+                                             self.n_per_reward_group, obs.data_ptr(), self.obs_dim, self._stream())
+        elif self.sim_cfgs is not None:
             self.ctx.env_reset_groups(self.params, self.sim_cfgs, self.n_per_group, self.cfg, obs.data_ptr(), self.obs_dim, self._stream())
         else:
             self.ctx.env_reset(self.params, self.sim_cfg, self.cfg, self.n, obs.data_ptr(), self.obs_dim, self._stream())
@@ -160,7 +220,11 @@ class MergeVecEnv:
         a = self._action_tensor(action)
         self._cur ^= 1
         obs = self._obs[self._cur]
-        if self.sim_cfgs is not None:
+        if self.R:
+            self.ctx.env_step_reward_groups(self.params, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
+                                            self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(),
+                                            self._stream())
+        elif self.sim_cfgs is not None:
             self.ctx.env_step_groups(self.params, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
                                      self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(), self._stream())
         else:
@@ -177,7 +241,8 @@ class MergeVecEnv:
 
     def drain_episode_stats(self):
         """The episodes finished since the last drain (or reset), as the columns of ``episodes.EpisodeRunner.result()`` plus ``env``,
-        ``episode``, ``episode_return`` and ``traffic_group`` (``env // n_per_group``; 0 without traffic groups), ordered by (env, episode).  Synchronises; raises if device-side errors were flagged, and
+        ``episode``, ``episode_return``, ``traffic_group`` (``env // n_per_group``; 0 without traffic groups) and ``reward_group``
+        (``env // n_per_reward_group``; 0 without reward groups), ordered by (env, episode).  Synchronises; raises if device-side errors were flagged, and
         RuntimeError if more episodes finished than the log holds (``log_capacity``, default 16 n: drain more often)."""
         rows, dropped = self.ctx.env_drain(self.log_capacity)
         self.ctx.check_error()
@@ -191,4 +256,5 @@ class MergeVecEnv:
         out["env"] = rows[:, _capi.ENV_NSTAT].astype(np.int64)
         out["episode"] = rows[:, _capi.ENV_NSTAT + 1].astype(np.int64)
         out["traffic_group"] = out["env"] // self.n_per_group if self.sim_cfgs is not None else np.zeros(len(rows), dtype=np.int64)
+        out["reward_group"] = out["env"] // self.n_per_reward_group if self.R else np.zeros(len(rows), dtype=np.int64)
         return out
