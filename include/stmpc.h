@@ -923,6 +923,46 @@ int stmpc_reward_groups_env_reward_device(stmpc_ctx *ctx, const stmpc_env_cfg *e
                                           const int32_t *d_arrived, double *d_reward, void *stream);
 int stmpc_reward_groups_split(stmpc_ctx *ctx, int *R, int *n_per_group);
 
+/*
+ * Shielded vector environment: stmpc_env_step_device behind the first-step shield, st.do_conditional_st_based_on_first_step (st.py:805-814), without
+ * leaving the device -- the loop a policy is DEPLOYED in (episodes: controller "first_step"), for training.  The env's action is a proposal; the shield
+ * decides what is executed, and the step tells the learner what that was and how often it was overruled.  (Additive: new entries only, no signature or
+ * struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)
+ * One step, on `stream`: the env's action handling + the planner's view of the current state at row stride kmax (what stmpc_sim_view_device writes) + the
+ * proposed speed (the speed stmpc_env_step_device would command; a finished environment proposes what its action would command from its last state, as
+ * the episode runner does, and an action index out of range proposes the current speed), in one
+ * kernel -> the body of stmpc_first_step_device on that view and proposal (the context's stmpc_first_step_counts advance) -> where the shield took over a
+ * running environment: the commanded speed becomes the shield's, the projected jerk becomes (clip((cmd - v) / tick, a_min, a_max) - previous_acceleration)
+ * / tick (AccelerationEnv._do_action's third branch, merge_gym.py:208-212, of the executed speed) and takeover_penalty * tick_length is added to the tick's
+ * invalid-action reward -> the world step and the reward / observation / autoreset kernel of stmpc_env_step_device, unchanged.  The step equals, bit for
+ * bit, that composition made from the public entries by a caller.
+ *   stmpc_shield_env_reset_device   stmpc_env_reset_device + the context's shield buffers (view, proposal, decision, per-environment takeover counters,
+ *                       zeroed) and the first-step controller's for either value of fs.sparse_control, sized here: the step allocates none of them.  STMPC_EINVAL
+ *                       (before anything changes) for kmax outside 1 ... STMPC_KMAX_LIMIT and for a takeover_penalty that is negative or not finite.
+ *   stmpc_shield_env_step_device    the arguments of stmpc_env_step_device, then d_takeover uint8 [N], d_reason int32 [N] (stmpc_first_step_device's codes),
+ *                       d_executed_jerk fp64 [N] (the projected jerk after the shield), d_executed_action fp64 [N] (STMPC_ENV_CONTINUOUS_JERK only, may be
+ *                       NULL; must be NULL for a discrete env, whose index is not rewritten: the action's own bits where the proposal stood, else
+ *                       d_executed_jerk clipped to [minimum_negative_jerk, maximum_positive_jerk]), d_takeover_ticks int32 [N] (takeovers of the
+ *                       environment's current episode up to and including this tick: in the rows where the step reports terminated | truncated, the
+ *                       finished episode's).  A finished environment (no autoreset) gets takeover 0, reason 0, executed_jerk 0 and keeps its count.
+ *                       Asynchronous with fs.sparse_control = 0; with 1 it makes the one host round trip of stmpc_first_step_device.  STMPC_EINVAL if the
+ *                       context's environment was not reset through stmpc_shield_env_reset_device, N differs from the reset, the world has traffic groups
+ *                       or the env reward groups, kmax is out of range or differs from the reset's.  The plain stmpc_env_step_device stays legal on such
+ *                       an env: it is the unshielded step.
+ */
+typedef struct stmpc_shield_env_cfg {
+    stmpc_first_step_cfg fs;     /* tick_length, min_crash_distance, sparse_control: as stmpc_first_step_device */
+    double takeover_penalty;     /* added to the tick's reward as takeover_penalty * tick_length where the shield took over (0: none) */
+    int32_t kmax;                /* row stride of the planner view handed to the shield, 1 ... STMPC_KMAX_LIMIT (the solver's vehicles per state) */
+    int32_t reserved0;
+} stmpc_shield_env_cfg;
+int stmpc_shield_env_reset_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfg, const stmpc_env_cfg *env_cfg,
+                                  const stmpc_shield_env_cfg *shield_cfg, int N, float *d_obs, int obs_stride, void *stream);
+int stmpc_shield_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfg, const stmpc_env_cfg *env_cfg,
+                                 const stmpc_shield_env_cfg *shield_cfg, int N, const void *d_action, float *d_obs, int obs_stride, double *d_reward,
+                                 uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, uint8_t *d_takeover,
+                                 int32_t *d_reason, double *d_executed_jerk, double *d_executed_action, int32_t *d_takeover_ticks, void *stream);
+
 /* Device arithmetic probe used by the parity tests: out[i] = a[i] op b[i] evaluated on the GPU
  * with the kernels' compile flags. op: 0 div, 1 sqrt(a), 2 mul, 3 add, 4 fma(a,a,b*b), 5 the five-operation
  * quotient a/b of the FASTDIV kernels, 6 their two-operation quotient a/b.  HOST pointers. */

@@ -100,6 +100,16 @@ class FirstStepCfg(C.Structure):
         return cls(tick_length=S.TICK_LENGTH, min_crash_distance=cls.MIN_CRASH_DISTANCE, sparse_control=int(bool(sparse_control)))
 
 
+class ShieldEnvCfg(C.Structure):
+    """``stmpc_shield_env_cfg`` (include/stmpc.h): the first-step shield of the shielded vector environment, the takeover penalty and the row stride
+    of the planner's view handed to the shield."""
+    _fields_ = [("fs", FirstStepCfg), ("takeover_penalty", C.c_double), ("kmax", C.c_int32), ("reserved0", C.c_int32)]
+
+    @classmethod
+    def from_settings(cls, S, sparse_control=False, takeover_penalty=0.0, kmax=32):
+        return cls(fs=FirstStepCfg.from_settings(S, sparse_control=sparse_control), takeover_penalty=float(takeover_penalty), kmax=int(kmax))
+
+
 class FeaturesCfg(C.Structure):
     """``stmpc_policy_features_cfg`` (include/stmpc.h): the flags of dqn.get_state_vector_from_base_state (+ the TimeFeature input of ddpg.py:41)."""
     _fields_ = [("max_speed", C.c_double), ("sensor_radius", C.c_double), ("time_scale", C.c_double), ("cars_ahead", C.c_int32), ("cars_behind", C.c_int32),
@@ -250,8 +260,10 @@ EXPORTS = (
     "stmpc_solve_batch_groups_device", "stmpc_solve_batch_groups", "stmpc_st_control_groups_device", "stmpc_solver_groups_sim_step_device",
     "stmpc_solver_groups_sim_init_device",
     "stmpc_reward_groups_env_reset_device", "stmpc_reward_groups_env_step_device", "stmpc_reward_groups_env_reward_device", "stmpc_reward_groups_split",
+    "stmpc_shield_env_reset_device", "stmpc_shield_env_step_device",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
+KMAX_LIMIT = 32      # STMPC_KMAX_LIMIT
 ENV_CONTINUOUS_JERK, ENV_JERK, ENV_ACCELERATION = 0, 1, 2                                 # STMPC_ENV_*
 REWARD_CONTINUOUS, REWARD_SLOTTED, REWARD_SLOTTED_JERK, REWARD_ST = 0, 1, 2, 3             # STMPC_REWARD_*
 ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
@@ -420,6 +432,9 @@ def load():
     lib.stmpc_first_step.argtypes = [vp, pp, fsp, C.c_int, C.c_int, dp, ip, dp, dp, dp, dp, ip, ip, ip, ip, dp, dp, dp]
     lib.stmpc_first_step_counts.argtypes = [vp, i64p, i64p, i64p, C.c_int]
     lib.stmpc_speed_from_jerk_device.argtypes = [vp, pp, C.c_double, C.c_int, vp, vp, vp, vp]
+    shp = C.POINTER(ShieldEnvCfg)
+    lib.stmpc_shield_env_reset_device.argtypes = [vp, pp, sp, ep, shp, C.c_int, vp, C.c_int, vp]
+    lib.stmpc_shield_env_step_device.argtypes = [vp, pp, sp, ep, shp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -1000,6 +1015,18 @@ class Context:
     def env_step_groups(self, params, env_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs=0, d_final_stats=0, stream=0):
         self._chk(self._lib.stmpc_env_step_groups_device(self._h, C.byref(params), C.byref(env_cfg), int(N), d_action, d_obs, int(obs_stride), d_reward, d_terminated,
                                                          d_truncated, d_final_obs, d_final_stats, stream))
+
+    # -- shielded vector environment (stmpc_shield_env_*; see include/stmpc.h) -------------------------------
+    def shield_env_reset(self, params, sim_cfg, env_cfg, shield_cfg, N, d_obs, obs_stride, stream=0):
+        self._chk(self._lib.stmpc_shield_env_reset_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), C.byref(shield_cfg), int(N), d_obs,
+                                                          int(obs_stride), stream))
+
+    def shield_env_step(self, params, sim_cfg, env_cfg, shield_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs,
+                        d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks, stream=0):
+        """``stmpc_shield_env_step_device``; ``d_executed_action``: 0 for a discrete env."""
+        self._chk(self._lib.stmpc_shield_env_step_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), C.byref(shield_cfg), int(N), d_action,
+                                                         d_obs, int(obs_stride), d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, d_takeover,
+                                                         d_reason, d_executed_jerk, d_executed_action or None, d_takeover_ticks, stream))
 
     def env_reward(self, env_cfg, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed=0, d_arrived=0, d_reward=0, stream=0):
         self._chk(self._lib.stmpc_env_reward_device(self._h, C.byref(env_cfg), int(N), int(Kmax), d_ego4, d_k, d_ox, 0, 0, d_jerk, d_crashed, d_arrived,

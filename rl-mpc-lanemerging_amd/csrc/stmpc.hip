@@ -16,6 +16,7 @@
 #include "stmpc_fs_kernels.hpp"
 #include "stmpc_solver_groups_kernels.hpp"
 #include "stmpc_env_groups_kernels.hpp"
+#include "stmpc_shield_env_kernels.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -281,6 +282,20 @@ struct stmpc_ctx {
                                vx.as<double>(), vv.as<double>(), va.as<double>(), k.as<int>(), log.as<double>(), log_n.as<unsigned>(), err};
         }
     } env;
+    // shielded vector environment (stmpc_shield_env_*): the planner's view and the proposal handed to the first-step shield, its decision, and the
+    // takeovers of each environment's current episode with the episode they were counted in.  Valid while `generation` is the world's
+    struct ShieldEnv {
+        DevBuf ego5, k, ox, ov, proposal, speed, takeover, reason, count, tag;
+        int N = 0, kmax = 0;
+        int64_t generation = -1;
+        int ensure(int n_, int kmax_) {
+            const size_t n = (size_t)n_;
+            TRY(ego5.ensure(n * 5 * 8)); TRY(k.ensure(n * 4)); TRY(ox.ensure(n * kmax_ * 8)); TRY(ov.ensure(n * kmax_ * 8)); TRY(proposal.ensure(n * 8));
+            TRY(speed.ensure(n * 8)); TRY(takeover.ensure(n * 4)); TRY(reason.ensure(n * 4)); TRY(count.ensure(n * 4)); TRY(tag.ensure(n * 4));
+            return STMPC_OK;
+        }
+        env::ShieldView view() const { return env::ShieldView{ego5.as<double>(), k.as<int>(), ox.as<double>(), ov.as<double>(), proposal.as<double>()}; }
+    } shield;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     stmpc_stats stats{};
     bool stats_pending = false;
@@ -2191,20 +2206,28 @@ int stmpc_solve_grid_no_jerk(stmpc_ctx *c, int variant, const uint8_t *obstacles
 }  // extern "C"
 
 // ---- first-step shield controller (stmpc_fs_kernels.hpp): st.do_conditional_st_based_on_first_step, st.py:805-814 ----
-extern "C" {
-
-int stmpc_first_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_first_step_cfg *g, int N, int Kmax, const double *d_ego5, const int32_t *d_k,
-                            const double *d_ox, const double *d_ov, const double *d_oa, const double *d_start_speed, double *d_cmd_speed, int32_t *d_takeover,
-                            int32_t *d_reason, void *stream) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+namespace {
+// the checks of stmpc_first_step_device's cfg and batch shape (the shielded env's entries make them too, before anything changes)
+int first_step_check(const stmpc_params *p, const stmpc_first_step_cfg *g, int N, int Kmax) {
     if (!p || !g) return fail(STMPC_EINVAL, "NULL parameter struct");
     if (!(g->tick_length > 0)) return fail(STMPC_EINVAL, "tick_length must be positive");
     if (!(g->min_crash_distance >= 0)) return fail(STMPC_EINVAL, "min_crash_distance must not be negative");
-    TRY(check_batch(N, Kmax));
-    if (N == 0) return STMPC_OK;
-    if (!d_ego5 || !d_k || !d_start_speed || !d_cmd_speed || !d_takeover || !d_reason) return fail(STMPC_EINVAL, "NULL device pointer");
-    if (Kmax > 0 && (!d_ox || !d_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
-    (void)d_oa;                          // (prediction.py:75-97 reads no accelerations: the argument completes the planner's view, nothing more)
+    return check_batch(N, Kmax);
+}
+// the controller's buffers for N states of Kalloc vehicle slots and H layers (grow-only: a no-op once they hold the shape)
+int first_step_ensure(stmpc_ctx *c, int N, int Kalloc, int H, bool sparse) {
+    const size_t n = (size_t)N;
+    auto &b = c->fs;
+    TRY(b.next_ego.ensure(n * 5 * 8)); TRY(b.next_ox.ensure(n * Kalloc * 8)); TRY(b.next_ov.ensure(n * Kalloc * 8)); TRY(b.crashed.ensure(n * 4));
+    TRY(b.sh.ensure(N, H));
+    if (sparse) TRY(b.sh.ensure_compact(N, Kalloc));
+    if (!b.takeovers.p) { TRY(b.takeovers.ensure(8)); HIPCHK(hipMemset(b.takeovers.p, 0, 8)); }
+    return STMPC_OK;
+}
+// stmpc_first_step_device after its argument checks (N >= 1): the entry's body, shared with stmpc_shield_env_step_device
+int first_step_run(stmpc_ctx *c, const stmpc_params *p, const stmpc_first_step_cfg *g, int N, int Kmax, const double *d_ego5, const int32_t *d_k,
+                   const double *d_ox, const double *d_ov, const double *d_start_speed, double *d_cmd_speed, int32_t *d_takeover, int32_t *d_reason,
+                   void *stream) {
     HIPCHK(hipSetDevice(c->device));
     DevP dp;
     TRY(make_devp(p, &dp));
@@ -2214,10 +2237,7 @@ int stmpc_first_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_fir
     const size_t n = (size_t)N;
     auto &b = c->fs;
     auto &o = b.sh;
-    TRY(b.next_ego.ensure(n * 5 * 8)); TRY(b.next_ox.ensure(n * Kalloc * 8)); TRY(b.next_ov.ensure(n * Kalloc * 8)); TRY(b.crashed.ensure(n * 4));
-    TRY(o.ensure(N, H));
-    if (g->sparse_control) TRY(o.ensure_compact(N, Kalloc));
-    if (!b.takeovers.p) { TRY(b.takeovers.ensure(8)); HIPCHK(hipMemset(b.takeovers.p, 0, 8)); }
+    TRY(first_step_ensure(c, N, Kalloc, H, g->sparse_control != 0));
     b.N = N; b.K = Kalloc;
     const int blocks = (N + 63) / 64;
     // 1. one predictor step with the proposed speed, laid out as the probe's state (st.py:806)
@@ -2245,6 +2265,21 @@ int stmpc_first_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_fir
                        b.takeovers.as<unsigned long long>(), c->sticky.as<unsigned>() + 1);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_first_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_first_step_cfg *g, int N, int Kmax, const double *d_ego5, const int32_t *d_k,
+                            const double *d_ox, const double *d_ov, const double *d_oa, const double *d_start_speed, double *d_cmd_speed, int32_t *d_takeover,
+                            int32_t *d_reason, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(first_step_check(p, g, N, Kmax));
+    if (N == 0) return STMPC_OK;
+    if (!d_ego5 || !d_k || !d_start_speed || !d_cmd_speed || !d_takeover || !d_reason) return fail(STMPC_EINVAL, "NULL device pointer");
+    if (Kmax > 0 && (!d_ox || !d_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
+    (void)d_oa;                          // (prediction.py:75-97 reads no accelerations: the argument completes the planner's view, nothing more)
+    return first_step_run(c, p, g, N, Kmax, d_ego5, d_k, d_ox, d_ov, d_start_speed, d_cmd_speed, d_takeover, d_reason, stream);
 }
 
 int stmpc_first_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_first_step_cfg *g, int N, int Kmax, const double *ego, const int32_t *k, const double *ox,
@@ -2867,6 +2902,86 @@ int stmpc_reward_groups_split(stmpc_ctx *c, int *R, int *n_per_group) {
     const bool on = c->env.N >= 1;
     if (R) *R = on ? c->env.R : 0;
     if (n_per_group) *n_per_group = on ? c->env.n_per_rg : 0;
+    return STMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- shielded vector environment (stmpc_shield_env_*): kernels in stmpc_shield_env_kernels.hpp ----
+// The env step behind st.do_conditional_st_based_on_first_step (st.py:805-814): the action is a proposal, the shield decides what is executed.
+namespace {
+int shield_cfg_check(const stmpc_params *p, const stmpc_shield_env_cfg *sh, int N) {
+    if (!sh) return fail(STMPC_EINVAL, "shield cfg is NULL");
+    if (sh->kmax < 1 || sh->kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "shield cfg: kmax must be 1 ... STMPC_KMAX_LIMIT (32), the solver's vehicles per state");
+    if (!(sh->takeover_penalty >= 0) || !(sh->takeover_penalty <= 1.7976931348623157e308)) return fail(STMPC_EINVAL, "shield cfg: takeover_penalty must be finite and not negative");
+    return first_step_check(p, &sh->fs, N, sh->kmax);
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_shield_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N,
+                                  float *d_obs, int obs_stride, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(shield_cfg_check(p, sh, N));
+    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
+    DevP dp;
+    TRY(make_devp(p, &dp));
+    HIPCHK(hipSetDevice(c->device));
+    auto &v = c->shield;                         // (a world initialised below outdates an earlier shielded env by its generation)
+    TRY(stmpc_env_reset_device(c, p, g, ec, N, d_obs, obs_stride, stream));
+    TRY(v.ensure(N, sh->kmax));
+    TRY(first_step_ensure(c, N, sh->kmax, dp.H, true));       // (the sparse solve's compact batch too: a step may set fs.sparse_control either way)
+    HIPCHK(hipMemsetAsync(v.count.p, 0, (size_t)N * 4, (hipStream_t)stream));
+    HIPCHK(hipMemsetAsync(v.tag.p, 0, (size_t)N * 4, (hipStream_t)stream));
+    v.N = N; v.kmax = sh->kmax; v.generation = c->sim.generation;
+    return STMPC_OK;
+}
+
+int stmpc_shield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N,
+                                 const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
+                                 float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk,
+                                 double *d_executed_action, int32_t *d_takeover_ticks, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, "N does not match stmpc_shield_env_reset_device");
+    if (c->sim.G) return fail(STMPC_EINVAL, "the world has traffic groups: the shielded env step serves an ungrouped world only");
+    if (c->env.R) return fail(STMPC_EINVAL, "the env has reward groups: the shielded env step serves one reward only");
+    const auto &v = c->shield;
+    if (v.N != N || v.generation != c->sim.generation)
+        return fail(STMPC_EINVAL, "the environment in this context was not reset through stmpc_shield_env_reset_device");
+    TRY(shield_cfg_check(p, sh, N));
+    if (sh->kmax != v.kmax) return fail(STMPC_EINVAL, "shield cfg: kmax differs from the one the context was reset with (stmpc_shield_env_reset_device)");
+    if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    if (!d_takeover || !d_reason || !d_executed_jerk || !d_takeover_ticks) return fail(STMPC_EINVAL, "NULL device pointer (shield outputs)");
+    env::ECfg e;
+    sim::Cfg sc;
+    DevP dp;
+    TRY(env_step_begin(c, ec, obs_stride, "stmpc_shield_env_reset_device", &e));
+    if (d_executed_action && e.mode != env::ACT_CONTINUOUS_JERK)
+        return fail(STMPC_EINVAL, "d_executed_action is the continuous env's (a discrete index is not rewritten): pass NULL");
+    TRY(make_simcfg(g, &sc));
+    sim_route_of(c, &sc);
+    TRY(make_devp(p, &dp));
+    e.seed = sc.seed;
+    HIPCHK(hipSetDevice(c->device));
+    const dim3 grid((N + 63) / 64), block(64);
+    hipStream_t st_ = (hipStream_t)stream;
+    const sim::State s = c->sim.state();
+    const env::EState es = env_state(c);
+    const env::ShieldView w = v.view();
+    // 1. action handling, the planner's view, the proposal
+    hipLaunchKernelGGL(env::k_shield_env_pre, grid, block, 0, st_, e, sc, N, v.kmax, s, es, d_action, w);
+    HIPCHK(hipGetLastError());
+    // 2. st.do_conditional_st_based_on_first_step on that view and proposal: stmpc_first_step_device's body
+    TRY(first_step_run(c, p, &sh->fs, N, v.kmax, w.ego5, w.k, w.ox, w.ov, w.proposal, v.speed.as<double>(), v.takeover.as<int32_t>(), v.reason.as<int32_t>(), stream));
+    // 3. what is executed, and what the learner is told
+    hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, sh->takeover_penalty, N, s, es, d_action, (const double *)v.speed.as<double>(),
+                       (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), d_takeover, d_reason,
+                       d_executed_jerk, d_executed_action, d_takeover_ticks);
+    // 4. the world step and the env's reward / observation / autoreset, as stmpc_env_step_device launches them
+    hipLaunchKernelGGL(sim::k_sim_step, grid, block, 0, st_, dp, sc, N, s, (const double *)es.cmd, p->crash_min_s);
+    hipLaunchKernelGGL(env::k_env_post, grid, block, 0, st_, e, sc, N, s, es, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats);
+    HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 

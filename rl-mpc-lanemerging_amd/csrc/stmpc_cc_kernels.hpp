@@ -403,9 +403,8 @@ __device__ __forceinline__ State state_slice(const State &s, size_t off) {
 }
 // The planner's view of each environment (HighwayState.from_sumo, prediction.py:112-142): the vehicles within the sensor radius of the ego (plane
 // distance; the highway lane runs at y = -1.6), front to back, and the ego with its s coordinate.
-__global__ void __launch_bounds__(64) k_sim_view(Cfg c, int N, int Kmax, State s, double *ego5, int *k_count, double *ox, double *ov, double *oa) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
+// k_sim_view's body for environment e (e < N: the caller has checked its bounds); the shielded env step (stmpc_shield_env_kernels.hpp) calls it too.
+__device__ __forceinline__ void sim_view_env(const Cfg &c, int Kmax, const State &s, int e, double *ego5, int *k_count, double *ox, double *ov, double *oa) {
     const double ex = s.ego4[e * 4 + 0], ey = s.ego4[e * 4 + 1];
     for (int q = 0; q < 4; ++q) ego5[(size_t)e * 5 + q] = s.ego4[e * 4 + q];
     ego5[(size_t)e * 5 + 4] = dev_ego_s(ex, ey);
@@ -418,6 +417,11 @@ __global__ void __launch_bounds__(64) k_sim_view(Cfg c, int N, int Kmax, State s
     }
     for (int i = k; i < Kmax; ++i) { ox[(size_t)e * Kmax + i] = 0.0; ov[(size_t)e * Kmax + i] = 0.0; if (oa) oa[(size_t)e * Kmax + i] = 0.0; }
     k_count[e] = k;
+}
+__global__ void __launch_bounds__(64) k_sim_view(Cfg c, int N, int Kmax, State s, double *ego5, int *k_count, double *ox, double *ov, double *oa) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    sim_view_env(c, Kmax, s, e, ego5, k_count, ox, ov, oa);
 }
 // One simulator tick with the commanded ego speed: k_sim_step's body for the N environments `s` and `cmd_speed` point at.
 __device__ __forceinline__ void sim_step_body(const DevP &p, const Cfg &c, int N, const State &s, const double *__restrict__ cmd_speed, double crash_min_s) {

@@ -479,21 +479,37 @@ def write_actor(path, net, tanh_scale, tanh_mean):
         np.savez_compressed(fh, **{k: np.asarray(net[k], dtype=np.float32) for k in TENSORS}, tanh_scale=np.float64(tanh_scale), tanh_mean=np.float64(tanh_mean))
 
 
-def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_schedule=None):
+def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_schedule=None, executed_actions=False):
     """The loop of the reference's ``DDPGAgent.train`` on the device: act with noise -> env.step -> push -> ``updates_per_step`` updates, until
     ``frames`` transitions were collected (rounded up to whole steps of env.n).  Synchronises only every ``drain_every`` steps, to drain the
     finished episodes' statistics.  ``lr_schedule(step, steps) -> (lr_q, lr_pi)``: e.g. the preset's cosine schedule, computed on the host.
     Returns {"steps", "frames", "episodes", "mean_return" (of the drained episodes), "returns" (array)}.
     ``learner`` may be a ``DDPGPopulation`` (the schedule may then return per-member arrays); the result then also carries
-    ``member_returns``: the drained returns of each member's environments, a list of P arrays."""
+    ``member_returns``: the drained returns of each member's environments, a list of P arrays.
+    On a shielded env (``MergeVecEnv(shield="first_step")``) the result's ``takeover_share`` is the share of the live ticks on which the shield
+    overruled the action (summed on the device, read at the drains; 0.0 on an unshielded env), and ``executed_actions=True`` (continuous env only,
+    else ValueError) pushes ``info["executed_action"]`` -- what the shield let through or put in the action's place -- instead of the action."""
+    shielded = getattr(env, "shield", None) is not None
+    if executed_actions and not (shielded and env.continuous):
+        raise ValueError("executed_actions=True needs a shielded continuous env (MergeVecEnv(env_id='sumo-jerk-continuous-v0', shield='first_step'))")
     steps = -(-int(frames) // env.n)
     obs = env.reset()
     returns, envs = [], []
+    if shielded:
+        torch = env.torch
+        taken, lived = torch.zeros((), dtype=torch.int64, device=env.device), torch.zeros((), dtype=torch.int64, device=env.device)
+        alive = torch.ones(env.n, dtype=torch.bool, device=env.device)       # (without autoreset a finished environment idles: not a live tick)
+    takeover_ticks = live_ticks = 0
     for i in range(steps):
         ticks = env.episode_ticks.clone()
         action = learner.act(obs, ticks, noise=True)
         next_obs, reward, term, trunc, info = env.step(action)
-        learner.push(obs, ticks, action, reward, next_obs, term, trunc, final_obs=info["final_observation"])
+        learner.push(obs, ticks, info["executed_action"] if executed_actions else action, reward, next_obs, term, trunc, final_obs=info["final_observation"])
+        if shielded:
+            taken += info["takeover"].sum()
+            lived += alive.sum()
+            if not env.autoreset:
+                alive &= ~(term | trunc)
         if updates_per_step:
             lr_q, lr_pi = lr_schedule(i, steps) if lr_schedule is not None else (None, None)
             learner.update(updates_per_step, lr_q, lr_pi)
@@ -502,9 +518,11 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
             drained = env.drain_episode_stats()
             returns.append(drained["episode_return"])
             envs.append(drained["env"])
+            if shielded:
+                takeover_ticks, live_ticks = int(taken.item()), int(lived.item())
     returns = np.concatenate(returns) if returns else np.zeros(0)
     out = {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
-           "returns": returns}
+           "returns": returns, "takeover_share": takeover_ticks / live_ticks if live_ticks else 0.0}
     if isinstance(learner, DDPGPopulation):
         owner = (np.concatenate(envs) if envs else np.zeros(0, dtype=np.int64)) // learner.n_per_member
         out["member_returns"] = [returns[owner == m] for m in range(learner.P)]

@@ -3,7 +3,8 @@
 (dqn.py:449-563, rl.py:168-174), for ``n`` environments of the SUMO-free world (episodes.py) stepped in lock-step on one GPU.
 
 ``MergeVecEnv`` follows the call shape of a gym / gymnasium vector env (neither is imported): ``reset() -> obs``,
-``step(action) -> obs, reward, terminated, truncated, info``, all torch device tensors; ``step`` never synchronises with the host.
+``step(action) -> obs, reward, terminated, truncated, info``, all torch device tensors; ``step`` never synchronises with the host
+(one exception, by request: ``shield_sparse=True``, see ``MergeVecEnv``).
 Finished environments start their next episode in the same step (``autoreset``); ``info["final_observation"]`` / ``info["final_stats"]``
 hold what the finished episode returned in the rows where ``terminated | truncated``.  ``drain_episode_stats()`` is the one sync point.
 
@@ -128,9 +129,39 @@ class MergeVecEnv:
     ``n / R`` environments with that traffic and that reward; without it the world is one world of ``n`` environments whatever the rewards (pass
     ``traffic=[t] * R`` for R copies of one lone world under R rewards: common random numbers).  ``reward`` is then ignored;
     ``reward_names`` lists the groups' functions.  A ``learner.DDPGPopulation`` of R members trains member m under reward m, and
-    ``learner.evaluate_members`` / ``episodes.summary_by_member`` compare the resulting policies on one common report."""
+    ``learner.evaluate_members`` / ``episodes.summary_by_member`` compare the resulting policies on one common report.
 
-    def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, traffic=None, rewards=None):
+    ``shield``: None (every action is executed as it is: today's env on every path) or "first_step": every step runs behind the first-step shield,
+    ``st.do_conditional_st_based_on_first_step`` (st.py:805-814, ``first_step.py``), on the device (``stmpc_shield_env_reset_device`` /
+    ``stmpc_shield_env_step_device``) -- the closed loop ``episodes.EpisodeRunner(controller="first_step")`` deploys a policy in.  The action is a
+    proposal: where one predictor step with it crashes, or no feasible path is left after it, ``st.do_st_control``'s speed is executed instead, and
+    ``info`` tells the learner: ``takeover`` (bool [n]), ``reason`` (int32 [n], ``first_step.REASON_*``), ``executed_jerk`` (fp64 [n]: the projected jerk
+    of what was executed), ``executed_action`` (the continuous env only: the action where it stood, else ``executed_jerk`` clipped to the Box) and
+    ``takeover_ticks`` (int32 [n]: takeovers of the environment's current episode up to this tick; the finished episode's where ``terminated |
+    truncated``).  ``takeover_penalty`` (>= 0) is added to the reward as ``takeover_penalty * TICK_LENGTH`` on a takeover tick; ``shield_kmax``: the row
+    stride of the planner's view the shield sees (``EpisodeRunner``'s ``kmax``; 1 ... 32, the solver's limit).  ``shield_sparse=False`` solves the controller for every environment and
+    keeps ``step`` free of host synchronisation; ``shield_sparse=True`` solves it for the taken-over ones only, and ``step`` then DOES synchronise: one
+    integer, their number, crosses to the host every step.  Same outputs either way.  ``shield_counts()`` reads the shield's totals.  Out of scope,
+    refused with a ValueError: a shield together with ``traffic`` or ``rewards`` groups."""
+
+    SHIELDS = ("first_step",)
+
+    def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, traffic=None, rewards=None, shield=None,
+                 shield_sparse=False, takeover_penalty=0.0, shield_kmax=32):
+        self.shield = shield
+        if shield is not None:                                   # (before any device call)
+            if shield not in self.SHIELDS:
+                raise ValueError("unknown shield %r (None or one of %s)" % (shield, ", ".join(self.SHIELDS)))
+            if traffic is not None or rewards is not None:
+                raise ValueError("a shielded env with traffic or reward groups is out of scope: the shielded step serves one ungrouped world under one reward")
+            try:
+                penalty = float(takeover_penalty)                # (a Python or numpy number, a 0-d array or tensor)
+            except (TypeError, ValueError):
+                raise ValueError("takeover_penalty must be a number, not %r" % (takeover_penalty,))
+            if not (np.isfinite(penalty) and penalty >= 0):
+                raise ValueError("takeover_penalty must be finite and not negative, not %r" % (takeover_penalty,))
+            if not 1 <= int(shield_kmax) <= _capi.KMAX_LIMIT:
+                raise ValueError("shield_kmax must be 1 ... %d (the solver's vehicles per state), not %r" % (_capi.KMAX_LIMIT, shield_kmax))
         import torch
         self.torch = torch
         self.env_id = Settings.GYM_ENVIRONMENT if env_id is None else env_id
@@ -174,12 +205,21 @@ class MergeVecEnv:
         self._cur = 0
         self._ticks = z(self.n, dtype=torch.int32)
         self._reset_done = False
+        self.shield_cfg = None
+        if shield is not None:
+            self.shield_cfg = _capi.ShieldEnvCfg.from_settings(Settings, shield_sparse, float(takeover_penalty), shield_kmax)
+            self._takeover, self._reason = z(self.n, dtype=torch.bool), z(self.n, dtype=torch.int32)
+            self._exec_jerk, self._takeover_ticks = z(self.n), z(self.n, dtype=torch.int32)
+            self._exec_action = z(self.n) if self.continuous else None
 
     def reset(self):
-        """Every environment back to episode 0 (``stmpc_env_reset_device``): the observations of the start states [n][obs_dim] float32."""
+        """Every environment back to episode 0 (``stmpc_env_reset_device``, or the reset entry of the env's traffic groups, reward groups or shield):
+        the observations of the start states [n][obs_dim] float32."""
         self._cur = 0
         obs = self._obs[0]
-        if self.R:
+        if self.shield_cfg is not None:
+            self.ctx.shield_env_reset(self.params, self.sim_cfg, self.cfg, self.shield_cfg, self.n, obs.data_ptr(), self.obs_dim, self._stream())
+        elif self.R:
             self.ctx.env_reset_reward_groups(self.params, self.sim_cfgs if self.sim_cfgs is not None else self.sim_cfg, self.n_per_group, self.reward_cfgs,
                                              self.n_per_reward_group, obs.data_ptr(), self.obs_dim, self._stream())
         elif self.sim_cfgs is not None:
@@ -210,9 +250,10 @@ class MergeVecEnv:
         return a if a.is_contiguous() else a.contiguous()
 
     def step(self, action):
-        """One tick of every environment; no host synchronisation.  Returns (obs, reward, terminated, truncated, info) as device tensors;
+        """One tick of every environment; no host synchronisation (but with ``shield_sparse=True``).  Returns (obs, reward, terminated, truncated, info) as device tensors;
         info: final_observation [n][obs_dim], final_stats [n][15] (world statistics as episodes.EpisodeRunner reads them, status, ticks, return),
-        episode_return [n] (= final_stats[:, 14]) and status [n] (= final_stats[:, 12]) -- valid where terminated | truncated."""
+        episode_return [n] (= final_stats[:, 14]) and status [n] (= final_stats[:, 12]) -- valid where terminated | truncated.  A shielded env adds
+        takeover, reason, executed_jerk, executed_action (continuous env) and takeover_ticks, valid in every row (see the class)."""
         if not self._reset_done:
             raise RuntimeError("call reset() before step()")
         if _owners.get(self.ctx) is not self:
@@ -220,7 +261,12 @@ class MergeVecEnv:
         a = self._action_tensor(action)
         self._cur ^= 1
         obs = self._obs[self._cur]
-        if self.R:
+        if self.shield_cfg is not None:
+            self.ctx.shield_env_step(self.params, self.sim_cfg, self.cfg, self.shield_cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim,
+                                     self._reward.data_ptr(), self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(),
+                                     self._final_stats.data_ptr(), self._takeover.data_ptr(), self._reason.data_ptr(), self._exec_jerk.data_ptr(),
+                                     self._exec_action.data_ptr() if self._exec_action is not None else 0, self._takeover_ticks.data_ptr(), self._stream())
+        elif self.R:
             self.ctx.env_step_reward_groups(self.params, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
                                             self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(),
                                             self._stream())
@@ -233,7 +279,18 @@ class MergeVecEnv:
         self._last_action = a                                # (kept alive until the kernels have read it)
         info = {"final_observation": self._final_obs, "final_stats": self._final_stats, "episode_return": self._final_stats[:, _capi.ENV_NSTAT - 1],
                 "status": self._final_stats[:, _capi.SIM_NACC]}
+        if self.shield_cfg is not None:
+            info.update(takeover=self._takeover, reason=self._reason, executed_jerk=self._exec_jerk, takeover_ticks=self._takeover_ticks)
+            if self._exec_action is not None:
+                info["executed_action"] = self._exec_action
         return obs, self._reward, self._term, self._trunc, info
+
+    def shield_counts(self, reset=False):
+        """(states decided, states taken over, controller solves) of the shield on this env's context since the last reset of the counts
+        (``stmpc_first_step_counts``: finished environments of a run without autoreset are decided too, and count); synchronises."""
+        if self.shield_cfg is None:
+            raise RuntimeError("this env has no shield")
+        return self.ctx.first_step_counts(reset)
 
     def check_error(self):
         """Raise what the kernels flagged (an action index out of range); synchronises."""

@@ -1,0 +1,419 @@
+"""The shielded vector environment on the GPU (csrc/stmpc_shield_env_kernels.hpp; stmpc_shield_env_* of include/stmpc.h; the ``shield`` arguments of
+vec_env.MergeVecEnv; ``executed_actions`` of learner.train_ddpg): the fused step equals the composition of the pinned public pieces, bit for bit.
+
+Shape unless stated: n = 96 (a full 64-thread workgroup and a partial one), "sumo-jerk-continuous-v0", the "default" traffic (1.2 s headway),
+shield_kmax = 32.  Every shielded run is recorded once (``_record``) and shared by the tests that need it."""
+import numpy as np
+import pytest
+
+N, KMAX, SEED, ACT_SEED = 96, 32, 7, 11
+_cache = {}
+
+
+def _pkg():
+    import rl_mpc_lanemerging_amd as pkg
+    if pkg.build.needs_build():
+        pkg.build.build()
+    return pkg
+
+
+def _settings():
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import combined_bench, episodes
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
+    pkg.apply_overrides(episodes.TRAFFIC_TYPES["default"])
+    return pkg.Settings
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+
+
+def _same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+
+
+def _actions(env, rng, n):
+    if env.continuous:
+        return rng.uniform(env.action_space["low"], env.action_space["high"], n)
+    return rng.integers(0, env.action_space["n"], n).astype(np.int32)
+
+
+KEYS = ("obs", "reward", "term", "trunc", "takeover", "reason", "executed_jerk", "executed_action", "takeover_ticks", "final_stats")
+
+
+def _record(env_id="sumo-jerk-continuous-v0", n=N, ticks=150, shield="first_step", sparse=False, penalty=0.0, autoreset=False, world=True, actions=None,
+            expect_error=False):
+    """One run of a MergeVecEnv on a context of its own under the seeded actions: every output of every tick (host copies), the world after every tick
+    (``world``) and the shield's counts.  Cached: a reference is computed once and never changed."""
+    key = (env_id, n, ticks, shield, sparse, penalty, autoreset, world, None if actions is None else hash(np.ascontiguousarray(actions).tobytes()))
+    if key in _cache:
+        return _cache[key]
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, vec_env
+    _settings()
+    ctx = _capi.Context(-1)
+    kw = dict(shield=shield, shield_sparse=sparse, takeover_penalty=penalty, shield_kmax=KMAX) if shield else {}
+    env = vec_env.MergeVecEnv(n, env_id=env_id, seed=SEED, reward="Continuous", autoreset=autoreset, ctx=ctx, **kw)
+    if shield:
+        env.shield_counts(reset=True)
+    out = {k: [] for k in KEYS + ("action", "status", "sim_ticks", "acc", "ego4")}
+    out["obs0"] = env.reset().cpu().numpy().copy()
+    rng = np.random.default_rng(ACT_SEED)
+    for t in range(ticks):
+        act = actions[t] if actions is not None else _actions(env, rng, n)
+        obs, r, term, trunc, info = env.step(torch.as_tensor(act, device="cuda"))
+        out["action"].append(act)
+        for k, v in (("obs", obs), ("reward", r), ("term", term), ("trunc", trunc), ("final_stats", info["final_stats"])):
+            out[k].append(v.cpu().numpy().copy())
+        for k in ("takeover", "reason", "executed_jerk", "executed_action", "takeover_ticks"):
+            if k in info:
+                out[k].append(info[k].cpu().numpy().copy())
+        if world:
+            for k, v in zip(("status", "sim_ticks", "acc", "ego4"), ctx.sim_read(n)):
+                out[k].append(v.copy())
+    out = {k: (np.stack(v) if isinstance(v, list) and v else v) for k, v in out.items()}
+    out["info_keys"] = set(info)
+    out["counts"] = env.shield_counts() if shield else None
+    if expect_error:                                      # (an action index out of range was among the actions)
+        with pytest.raises(_capi.StmpcError):
+            env.check_error()
+        out["drained"] = None
+    else:
+        out["drained"] = env.drain_episode_stats()
+        env.check_error()
+    ctx.close()
+    _cache[key] = out
+    return out
+
+
+def _compose(rec, env_id, penalty=0.0, check=("world", "obs", "reward", "flags", "shield", "executed_jerk")):
+    """The recorded shielded run's ticks made again on a second context from the public pieces (DESIGN section 11's construction with the shield in
+    the middle): sim_view -> the proposal (speed_from_jerk_device for the continuous env, the rewards.py twin's command for the discrete ones) ->
+    FirstStepController.decide (dense) -> stmpc_sim_step_device with the decided speeds -> stmpc_env_reward_device + policy_features_device + the
+    action-handling twins.  A finished environment proposes what its action would command from its last state, as the runner does, so the
+    composition's takeovers over ALL rows (``all_takeovers``) are the context's count.  An index out of range proposes the current speed.  Asserts bit
+    equality on the live rows of every tick; returns what the run exercised."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, episodes, first_step, rewards, vec_env
+    S = _settings()
+    n, ticks = rec["action"].shape[1], rec["action"].shape[0]
+    continuous = env_id == "sumo-jerk-continuous-v0"
+    ctx = _capi.Context(-1)
+    cfg = episodes.sim_cfg(SEED, float(S.MAX_EPISODE_LENGTH))
+    ecfg = vec_env.env_cfg(env_id, "Continuous", autoreset=False)
+    params = _capi.Params.from_settings(S)
+    fcfg = _capi.FeaturesCfg.from_settings(S, time_feature=False)
+    fs = first_step.FirstStepController(n, ctx, params, sparse_control=False)
+    ctx.sim_init(cfg, n)
+    dev = lambda a, dtype=None: torch.as_tensor(np.ascontiguousarray(a), device="cuda", dtype=dtype)
+    z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device="cuda")
+    ego5, kb, oxb, ovb, oab, feat, rew = z(n, 5), z(n, dtype=torch.int32), z(n, KMAX), z(n, KMAX), z(n, KMAX), z(n, 20, dtype=torch.float32), z(n)
+    tick = float(S.TICK_LENGTH)
+    a_min, a_max, j_min, j_max = float(S.MAX_NEGATIVE_ACCELERATION), float(S.MAX_POSITIVE_ACCELERATION), float(S.MINIMUM_NEGATIVE_JERK), float(S.MAXIMUM_POSITIVE_JERK)
+
+    def view():
+        ctx.sim_view(cfg, n, KMAX, ego5.data_ptr(), kb.data_ptr(), oxb.data_ptr(), ovb.data_ptr(), oab.data_ptr())
+
+    view()
+    e4 = ego5[:, :4].contiguous()
+    ctx.policy_features_device(fcfg, n, KMAX, 1, e4.data_ptr(), kb.data_ptr(), oxb.data_ptr(), ovb.data_ptr(), oab.data_ptr(), 0, feat.data_ptr(), 20)
+    assert _same(rec["obs0"], feat.cpu().numpy())
+    prev_a, count = np.zeros(n), np.zeros(n, np.int32)
+    seen = {"takeovers": 0, "all_takeovers": 0, "dead_decisions": 0, "accepted": 0, "ended_taken": 0, "ended": 0, "penalised": 0}
+    n_actions = None if continuous else int(ecfg.n_action_values)
+    for t in range(ticks):
+        live = ctx.sim_read(n)[0] == 0
+        e5 = ego5.cpu().numpy()
+        assert int(kb.max()) < KMAX                       # (the shield's view and the env's own, which has no cut, hold the same vehicles)
+        act = rec["action"][t]
+        cmd_tw, pj, inv = np.zeros(n), np.zeros(n), np.zeros(n)
+        for i in range(n):
+            if not continuous and not 0 <= int(act[i]) < n_actions:
+                cmd_tw[i] = e5[i, 2]                      # (keeps its speed: k_sim_step's reading of k_env_act's NaN command)
+                continue
+            cmd_tw[i], pj[i], inv[i] = rewards.handle_action(env_id, float(e5[i, 2]), float(e5[i, 3]), float(prev_a[i]), float(act[i]) if continuous else int(act[i]))
+        if continuous:
+            d_act = dev(act, torch.float64)
+            prop = first_step.speed_from_jerk_device(ctx, params, tick, ego5, d_act)
+            assert _same(prop.cpu().numpy(), cmd_tw)
+        else:
+            prop = dev(cmd_tw)
+        d = fs.decide(ego5, kb, oxb, ovb, prop)
+        cmd, take, reason = d["speed"].cpu().numpy(), d["takeover"].cpu().numpy() != 0, d["reason"].cpu().numpy()
+        ctx.sim_step(params, cfg, n, d["speed"].data_ptr())
+        status, sim_ticks, acc, ego4 = ctx.sim_read(n)
+        if "world" in check:
+            for name, got, want in (("status", rec["status"][t], status), ("ticks", rec["sim_ticks"][t], sim_ticks), ("acc", rec["acc"][t], acc), ("ego", rec["ego4"][t], ego4)):
+                assert _same(got[live], want[live]), (name, t)
+        # what was executed: the formula of k_shield_env_apply in float64, in its operation order
+        ex_jerk = np.where(take, (np.clip((cmd - e5[:, 2]) / tick, a_min, a_max) - prev_a) / tick, pj)
+        inv = np.where(take, inv + penalty * tick, inv)
+        count += (take & live).astype(np.int32)
+        view()
+        e4 = ego5[:, :4].contiguous()
+        ctx.policy_features_device(fcfg, n, KMAX, 1, e4.data_ptr(), kb.data_ptr(), oxb.data_ptr(), ovb.data_ptr(), oab.data_ptr(), 0, feat.data_ptr(), 20)
+        crashed, arrived = status == 2, status == 1
+        ended = crashed | arrived
+        jerk = np.where(ended, ex_jerk, (ego4[:, 3] - prev_a) / tick)
+        d_jerk, d_cr, d_ar = dev(jerk), dev(crashed.astype(np.int32)), dev(arrived.astype(np.int32))       # (kept alive until the kernel has read them)
+        ctx.env_reward(ecfg, n, KMAX, e4.data_ptr(), kb.data_ptr(), oxb.data_ptr(), d_jerk.data_ptr(), d_cr.data_ptr(), d_ar.data_ptr(), rew.data_ptr())
+        want_r = rew.cpu().numpy() + inv
+        want_obs = np.where(ended[:, None], np.float32(0), feat.cpu().numpy())
+        if "shield" in check:
+            assert _same(rec["takeover"][t][live], take[live]) and _same(rec["reason"][t][live], reason[live]), t
+            assert _same(rec["takeover_ticks"][t][live], count[live]), t
+            assert not rec["takeover"][t][~live].any() and not rec["reason"][t][~live].any() and not rec["executed_jerk"][t][~live].any(), t
+        if "executed_jerk" in check:
+            assert _same(rec["executed_jerk"][t][live], ex_jerk[live]), t
+            if continuous:
+                assert _same(rec["executed_action"][t][live], np.where(take, np.clip(ex_jerk, j_min, j_max), act)[live]), t
+        if "reward" in check:
+            assert _same(rec["reward"][t][live], want_r[live]), t
+        if "obs" in check:
+            assert _same(rec["obs"][t][live], want_obs[live]), t
+        if "flags" in check:
+            assert _same(rec["term"][t][live], ended[live]) and _same(rec["trunc"][t][live], (status == 3)[live]), t
+            assert not rec["term"][t][~live].any() and not rec["trunc"][t][~live].any() and not rec["reward"][t][~live].any(), t
+        seen["takeovers"] += int((take & live).sum())
+        seen["all_takeovers"] += int(take.sum())
+        seen["dead_decisions"] += int((~live).sum())
+        seen["accepted"] += int((~take & live).sum())
+        seen["ended"] += int((live & (status != 0)).sum())
+        seen["ended_taken"] += int((live & ended & take).sum())
+        seen["penalised"] += int((live & (inv != 0)).sum())
+        running = status == 0
+        prev_a = np.where(live & running, ego4[:, 3], prev_a)
+    ctx.check_error()
+    ctx.close()
+    return seen
+
+
+@pytest.mark.gpu
+def test_gpu_step_is_the_composition_bit_for_bit(restore_settings):
+    """150 ticks of uniform jerks in the Box, world seed 7, action seed 11.  That run, on an MI355X: 1378 takeovers and 12250 accepted proposals on
+    live rows, 33 environments end, 17 of them (crash or arrival) on a tick on which they were taken over -- the corrected projected jerk; 772 decisions
+    fall on finished rows, and over all rows the composition counts 1852 takeovers, the context's own count."""
+    rec = _record()
+    seen = _compose(rec, "sumo-jerk-continuous-v0")
+    print("shield env composition:", seen, "counts", rec["counts"])
+    assert seen["takeovers"] >= 1 and seen["accepted"] >= 1, seen
+    assert seen["ended_taken"] >= 1, seen
+    assert rec["info_keys"] >= {"takeover", "reason", "executed_jerk", "executed_action", "takeover_ticks"}
+    decisions, takeovers, solves = rec["counts"]
+    assert decisions == solves == 150 * N
+    # the context's count covers the finished rows too: they propose their action's speed (with their current speed this run counts 2038, not 1852)
+    assert takeovers == seen["all_takeovers"] and seen["dead_decisions"] > 500, (takeovers, seen)
+
+
+@pytest.mark.gpu
+def test_gpu_env_follows_the_first_step_runner(gpu_ctx, restore_settings):
+    """A pretrained actor's jerks through the shielded env end every episode exactly where EpisodeRunner(controller="first_step") ends it."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, actor, combined_bench, episodes, vec_env
+    S = _settings()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    name = combined_bench.COMBINED_MEDIUM_1_ACTOR
+    ctx_r = _capi.Context(-1)
+    runner = episodes.EpisodeRunner(N, seed=SEED, controller="first_step", policy=actor.DDPGActor(name, N, ctx_r, S, dev), ctx=ctx_r, kmax=KMAX,
+                                    max_episode_length=float(S.MAX_EPISODE_LENGTH))
+    ctx_r.first_step_counts(reset=True)
+    ctx = _capi.Context(-1)
+    env = vec_env.MergeVecEnv(N, seed=SEED, reward="Continuous", autoreset=False, ctx=ctx, shield="first_step", shield_sparse=True, shield_kmax=KMAX)
+    env.shield_counts(reset=True)
+    env.reset()
+    pol = actor.DDPGActor(name, N, ctx, S, dev)
+    z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
+    ego5, k, ox, ov, oa = z(N, 5), z(N, dtype=torch.int32), z(N, KMAX), z(N, KMAX), z(N, KMAX)
+    ticks = 0
+    for t in range(500):
+        runner.tick()
+        ctx.sim_view(env.sim_cfg, N, KMAX, ego5.data_ptr(), k.data_ptr(), ox.data_ptr(), ov.data_ptr(), oa.data_ptr())       # the shield's own view
+        jerk = pol(1, ego5[:, :4].contiguous(), k, ox, ov, oa).to(torch.float64).contiguous()
+        env.step(jerk)
+        ticks += 1
+        if ticks % 10 == 0 and (runner.status() != 0).all():
+            break
+    want, got = ctx_r.sim_read(N), ctx.sim_read(N)
+    for name_, a, b in zip(("status", "ticks", "acc", "ego"), got, want):
+        assert _same(a, b), name_
+    assert (want[0] != 0).all() or ticks == 500
+    dr, tr, _ = ctx_r.first_step_counts()
+    de, te, _ = env.shield_counts()
+    print("shield env vs runner: ticks", ticks, "runner counts", (dr, tr), "env counts", (de, te))
+    assert (de, te) == (dr, tr)
+    env.check_error()
+    ctx.close()
+    ctx_r.close()
+
+
+@pytest.mark.gpu
+def test_gpu_sparse_equals_dense(restore_settings):
+    dense = _record()
+    sparse = _record(ticks=100, sparse=True, actions=dense["action"][:100])
+    for k in KEYS + ("status", "sim_ticks", "acc", "ego4"):
+        assert _same(sparse[k], dense[k][:100]), k
+    d, t, solves = sparse["counts"]
+    assert d == 100 * N and solves == t and t >= 1
+    assert dense["counts"][2] == dense["counts"][0] == 150 * N
+
+
+@pytest.mark.gpu
+def test_gpu_no_takeover_is_todays_env_and_the_penalty_is_exact(restore_settings):
+    S = _settings()
+    shielded = _record()
+    plain = _record(shield=None, actions=shielded["action"])
+    assert not plain["info_keys"] & {"takeover", "reason", "executed_jerk", "executed_action", "takeover_ticks"}
+    taken_before = np.cumsum(shielded["takeover"], axis=0) - shielded["takeover"] > 0          # [t][e]: a takeover on an earlier tick
+    clean = ~(taken_before | shielded["takeover"])                                              # up to the row's first takeover
+    assert clean.sum() > 1000 and (~clean).sum() > 100
+    for k in ("reward", "term", "trunc"):
+        assert _same(shielded[k][clean], plain[k][clean]), k
+    assert _same(shielded["obs"][clean], plain["obs"][clean])
+    stood = ~shielded["takeover"]
+    assert _same(shielded["executed_action"][stood], shielded["action"][stood])
+    # the takeover penalty: the world does not read the reward, so the run is the same run and only the reward moves
+    fined = _record(penalty=0.7, actions=shielded["action"])
+    for k in ("status", "sim_ticks", "acc", "ego4", "obs", "term", "trunc", "takeover", "reason", "executed_jerk", "executed_action", "takeover_ticks"):
+        assert _same(fined[k], shielded[k]), k
+    take = shielded["takeover"]
+    assert _same(fined["reward"][~take], shielded["reward"][~take])
+    # INVALID_ACTION_PENALTY is 0 in these settings, so inv = 0 and reward = base + inv: the kernel's sums are 0 + 0.7 * tick, then base + that
+    assert S.INVALID_ACTION_PENALTY == 0.0
+    inv = 0.0 + 0.7 * float(S.TICK_LENGTH)
+    assert take.sum() >= 1 and _same(fined["reward"][take], shielded["reward"][take] + inv)
+    assert (fined["reward"][take] != shielded["reward"][take]).all()
+    _compose(fined, "sumo-jerk-continuous-v0", penalty=0.7, check=("reward",))              # and against the pieces, in the kernel's order
+
+
+@pytest.mark.gpu
+def test_gpu_autoreset_counters_and_fewer_crashes(restore_settings):
+    n, ticks = 1024, 400
+    a = _record(n=n, ticks=ticks, autoreset=True, world=False)
+    done = a["term"] | a["trunc"]
+    count = np.zeros(n, np.int32)
+    ends = 0
+    for t in range(ticks):
+        count += a["takeover"][t]
+        assert _same(a["takeover_ticks"][t], count), t                 # (every row is live with autoreset)
+        ends += int(done[t].sum())
+        count[done[t]] = 0                                             # restarts with the next episode
+    assert ends > n and (a["takeover_ticks"][done] > 0).any() and (a["takeover_ticks"][done] == 0).any()
+    dr = a["drained"]
+    assert len(dr["env"]) == ends and np.isfinite(dr["episode_return"]).all()
+    b = _record(n=n, ticks=ticks, shield=None, autoreset=True, world=False, actions=a["action"])
+    crashed_a, crashed_b = int(dr["crashed"].sum()), int(b["drained"]["crashed"].sum())
+    print("crashed episodes: shielded %d of %d, unshielded %d of %d; takeover share %.4f"
+          % (crashed_a, ends, crashed_b, len(b["drained"]["env"]), a["takeover"].mean()))
+    assert crashed_a <= crashed_b
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_id", ["sumo-jerk-v0", "sumo-accel-v0"])
+def test_gpu_discrete_envs(env_id, restore_settings):
+    rec = _record(env_id=env_id, ticks=60)
+    assert "executed_action" not in rec["info_keys"] and rec["executed_action"] == []
+    seen = _compose(rec, env_id, check=("world", "reward", "shield"))
+    print("shield env composition,", env_id, seen)
+    assert rec["counts"][1] == seen["all_takeovers"], (rec["counts"], seen)         # (finished rows propose their action's speed here too)
+    # one index out of range in a live row: the error word is latched, the row proposes and -- unless the shield objects -- keeps its speed, which the
+    # composition with exactly that proposal pins through the world's state after the step; nothing turns NaN
+    act = np.zeros((1, N), np.int32)
+    act[0, 70] = 20 if env_id == "sumo-accel-v0" else 5
+    bad = _record(env_id=env_id, ticks=1, actions=act, expect_error=True)
+    _compose(bad, env_id, check=("world", "reward", "shield"))
+    for k in ("obs", "reward", "executed_jerk", "acc", "ego4"):
+        assert np.isfinite(bad[k]).all(), k
+    assert bad["executed_jerk"][0, 70] == 0.0 or bad["takeover"][0, 70]
+
+
+@pytest.mark.gpu
+def test_gpu_step_entry_refusals_and_the_plain_step_stays_legal(restore_settings):
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, vec_env
+    _settings()
+    n = N
+
+    def step(env, ctx=None, n_=n, shield_cfg=None, executed_action=None):
+        """env's shielded step through the raw entry with one argument changed"""
+        a = torch.zeros(n, dtype=torch.float64 if env.continuous else torch.int32, device="cuda")
+        ea = env._exec_action.data_ptr() if env._exec_action is not None else 0
+        (ctx or env.ctx).shield_env_step(env.params, env.sim_cfg, env.cfg, shield_cfg or env.shield_cfg, n_, a.data_ptr(), env._obs[1].data_ptr(), env.obs_dim,
+                                         env._reward.data_ptr(), env._term.data_ptr(), env._trunc.data_ptr(), env._final_obs.data_ptr(),
+                                         env._final_stats.data_ptr(), env._takeover.data_ptr(), env._reason.data_ptr(), env._exec_jerk.data_ptr(),
+                                         ea if executed_action is None else executed_action, env._takeover_ticks.data_ptr())
+        torch.cuda.synchronize()
+    mk = lambda **kw: vec_env.MergeVecEnv(n, seed=SEED, reward="Continuous", autoreset=False, ctx=_capi.Context(-1), **kw)
+    shielded, plain = mk(shield="first_step", shield_kmax=KMAX), mk()
+    shielded.reset()
+    plain.reset()
+    with pytest.raises(_capi.StmpcError, match="stmpc_shield_env_reset_device"):      # a context reset through the plain entry
+        step(shielded, ctx=plain.ctx)
+    with pytest.raises(_capi.StmpcError, match="N does not match"):
+        step(shielded, n_=n - 1)
+    other = _capi.ShieldEnvCfg.from_buffer_copy(shielded.shield_cfg)
+    other.kmax = 16
+    with pytest.raises(_capi.StmpcError, match="kmax differs"):
+        step(shielded, shield_cfg=other)
+    other.kmax = 33
+    with pytest.raises(_capi.StmpcError, match="kmax must be"):
+        step(shielded, shield_cfg=other)
+    discrete = mk(env_id="sumo-jerk-v0", shield="first_step", shield_kmax=KMAX)
+    discrete.reset()
+    with pytest.raises(_capi.StmpcError, match="d_executed_action"):
+        step(discrete, executed_action=discrete._exec_jerk.data_ptr())
+    step(shielded)                                           # none of the refusals changed anything: the step still runs
+    step(discrete)
+    # a plain stmpc_env_step_device on a shield-reset context is the unshielded step
+    fresh = mk(shield="first_step", shield_kmax=KMAX)
+    fresh.reset()
+    act = torch.as_tensor(np.random.default_rng(ACT_SEED).uniform(-5, 5, n), device="cuda")
+    o = torch.zeros_like(fresh._obs[1])
+    fresh.ctx.env_step(fresh.params, fresh.sim_cfg, fresh.cfg, n, act.data_ptr(), o.data_ptr(), fresh.obs_dim, fresh._reward.data_ptr(), fresh._term.data_ptr(),
+                       fresh._trunc.data_ptr())
+    want = plain.step(act)
+    assert _same(o.cpu().numpy(), want[0].cpu().numpy()) and _same(fresh._reward.cpu().numpy(), want[1].cpu().numpy())
+    for a, b in zip(fresh.ctx.sim_read(n), plain.ctx.sim_read(n)):
+        assert _same(a, b)
+    step(fresh)                                              # ... and the shielded step goes on after it
+    for e in (shielded, plain, discrete, fresh):
+        e.check_error()
+        e.ctx.close()
+
+
+def _flat(d, prefix=""):
+    out = {}
+    for k, v in d.items():
+        if isinstance(v, dict):
+            out.update(_flat(v, prefix + str(k) + "."))
+        else:
+            out[prefix + str(k)] = np.asarray(v).copy()
+    return out
+
+
+@pytest.mark.gpu
+def test_gpu_training_smoke_on_executed_actions(restore_settings):
+    from rl_mpc_lanemerging_amd import _capi, learner, vec_env
+    n = 256
+
+    def run():
+        _settings()
+        ctx = _capi.Context(-1)
+        env = vec_env.MergeVecEnv(n, seed=SEED, reward="Continuous", ctx=ctx, shield="first_step", shield_kmax=KMAX)
+        L = learner.DDPGLearner(env, learner.DDPGConfig(n_obs=env.obs_dim, capacity=8 * n, replay_start=n), seed=3)
+        res = learner.train_ddpg(env, L, frames=4 * n, executed_actions=True, drain_every=2)
+        env.check_error()
+        state = _flat(L.state_dict())
+        assert L.stats()["updates"] >= 1
+        ctx.close()
+        return res, state
+    r1, s1 = run()
+    r2, s2 = run()
+    assert r1["steps"] == 4 and (r1["episodes"] == 0 or np.isfinite(r1["mean_return"]))
+    assert 0.0 <= r1["takeover_share"] <= 1.0 and r1["takeover_share"] == r2["takeover_share"]
+    assert set(s1) == set(s2)
+    for k in s1:
+        assert _same(s1[k], s2[k]), k
