@@ -2361,23 +2361,38 @@ int make_simcfg(const stmpc_sim_cfg *g, sim::Cfg *c) {
 void sim_route_of(stmpc_ctx *c, sim::Cfg *sc) {
     if (c->sim.route_n >= 2) { sc->route = c->sim.route.as<double>(); sc->route_n = c->sim.route_n; }
 }
-// the context's device copy of g's route (x then y), or none
+// g's route, if it has one: at most 4096 points, x strictly increasing.  Changes nothing
+int route_check(const stmpc_sim_cfg *g) {
+    if (!g->ego_route_xy || g->ego_route_n < 2) return STMPC_OK;
+    if (g->ego_route_n > 4096) return fail(STMPC_EINVAL, "ego_route_n out of range (at most 4096 points)");
+    for (int i = 1; i < g->ego_route_n; ++i)
+        if (!(g->ego_route_xy[2 * i] > g->ego_route_xy[2 * i - 2])) return fail(STMPC_EINVAL, "ego_route_xy: x must be strictly increasing");
+    return STMPC_OK;
+}
+// the context's device copy of g's route (x then y), or none; the route has passed route_check
 int sim_route_upload(stmpc_ctx *c, const stmpc_sim_cfg *g, void *stream) {
     c->sim.route_n = 0;
     if (g->ego_route_xy && g->ego_route_n >= 2) {
         const int n = g->ego_route_n;
-        if (n > 4096) return fail(STMPC_EINVAL, "ego_route_n out of range (at most 4096 points)");
         std::vector<double> xy((size_t)2 * n);
-        for (int i = 0; i < n; ++i) {
-            xy[i] = g->ego_route_xy[2 * i]; xy[n + i] = g->ego_route_xy[2 * i + 1];
-            if (i && !(xy[i] > xy[i - 1])) return fail(STMPC_EINVAL, "ego_route_xy: x must be strictly increasing");
-        }
+        for (int i = 0; i < n; ++i) { xy[i] = g->ego_route_xy[2 * i]; xy[n + i] = g->ego_route_xy[2 * i + 1]; }
         TRY(c->sim.route.ensure(xy.size() * 8));
         HIPCHK(hipMemcpyAsync(c->sim.route.p, xy.data(), xy.size() * 8, hipMemcpyHostToDevice, (hipStream_t)stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));       // (xy is a local)
         c->sim.route_n = n;
     }
     return STMPC_OK;
+}
+// A new world of N environments takes the context over (the init entries, after their checks): its buffers and g's route.  The vector environment's
+// bookkeeping, its reward groups and the table of traffic groups no longer describe this world (the entries that made them set them again), and what
+// is bound to the former world's generation (a recorder, a shielded env) is outdated.
+int sim_world_begin(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *stream) {
+    TRY(c->sim.ensure(N));
+    c->sim.N = N;
+    ++c->sim.generation;
+    c->env.N = 0; c->env.R = 0; c->env.n_per_rg = 0;
+    c->sim.G = 0; c->sim.n_per_group = 0;
+    return sim_route_upload(c, g, stream);
 }
 // Traffic groups: every cfg valid, and equal in what the shared kernels (k_sim_view, k_env_act), the one route and the one vehicle type read.
 // Changes nothing; `out` receives the G kernel cfgs without their route.
@@ -2390,11 +2405,7 @@ int check_groups(const stmpc_sim_cfg *cfgs, int G, int n_per_group, std::vector<
     out->resize((size_t)G);
     for (int g = 0; g < G; ++g) TRY(make_simcfg(&cfgs[g], &(*out)[g]));
     const stmpc_sim_cfg &a = cfgs[0];
-    if (a.ego_route_xy && a.ego_route_n >= 2) {
-        if (a.ego_route_n > 4096) return fail(STMPC_EINVAL, "ego_route_n out of range (at most 4096 points)");
-        for (int i = 1; i < a.ego_route_n; ++i)
-            if (!(a.ego_route_xy[2 * i] > a.ego_route_xy[2 * i - 2])) return fail(STMPC_EINVAL, "ego_route_xy: x must be strictly increasing");
-    }
+    TRY(route_check(&a));
     const int route_a = a.ego_route_xy && a.ego_route_n >= 2 ? a.ego_route_n : 0;
     for (int g = 1; g < G; ++g) {
         const stmpc_sim_cfg &b = cfgs[g];
@@ -2409,9 +2420,10 @@ int check_groups(const stmpc_sim_cfg *cfgs, int G, int n_per_group, std::vector<
     }
     return STMPC_OK;
 }
-// the checks every grouped step entry starts with
+const char *const UNGROUPED_WORLD = "the world has no traffic groups (stmpc_sim_init_groups_device): use the plain step entry";
+// the checks every grouped world step entry starts with
 int check_grouped_world(stmpc_ctx *c, int N) {
-    if (c->sim.G < 1) return fail(STMPC_EINVAL, "the world has no traffic groups (stmpc_sim_init_groups_device): use the plain step entry");
+    if (c->sim.G < 1) return fail(STMPC_EINVAL, UNGROUPED_WORLD);
     if (N != c->sim.N) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_groups_device (G * n_per_group)");
     return STMPC_OK;
 }
@@ -2427,14 +2439,9 @@ int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *str
     if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
     sim::Cfg sc;
     TRY(make_simcfg(g, &sc));
+    TRY(route_check(g));
     HIPCHK(hipSetDevice(c->device));
-    TRY(c->sim.ensure(N));
-    c->sim.N = N;
-    ++c->sim.generation;
-    c->env.N = 0;                 // (the vector environment's bookkeeping no longer describes this world; stmpc_env_reset_device sets it again)
-    c->env.R = 0; c->env.n_per_rg = 0;
-    c->sim.G = 0; c->sim.n_per_group = 0;      // (nor does the table of traffic groups)
-    TRY(sim_route_upload(c, g, stream));
+    TRY(sim_world_begin(c, g, N, stream));
     sim_route_of(c, &sc);
     hipLaunchKernelGGL(sim::k_sim_init, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, sc, N, c->sim.state());
     HIPCHK(hipGetLastError());
@@ -2487,14 +2494,8 @@ int sim_init_groups(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_gr
     TRY(check_groups(cfgs, G, n_per_group, &table, G_max));
     const int N = G * n_per_group;
     HIPCHK(hipSetDevice(c->device));
-    TRY(c->sim.ensure(N));
     TRY(c->sim.groups.ensure(table.size() * sizeof(sim::Cfg)));
-    c->sim.N = N;
-    ++c->sim.generation;
-    c->env.N = 0;
-    c->env.R = 0; c->env.n_per_rg = 0;
-    c->sim.G = 0; c->sim.n_per_group = 0;
-    TRY(sim_route_upload(c, &cfgs[0], stream));
+    TRY(sim_world_begin(c, &cfgs[0], N, stream));
     for (auto &sc : table) sim_route_of(c, &sc);
     HIPCHK(hipMemcpyAsync(c->sim.groups.p, table.data(), table.size() * sizeof(sim::Cfg), hipMemcpyHostToDevice, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));           // (table is a local; the step entries read the device copy and take no cfgs)
@@ -2627,8 +2628,7 @@ int env_reset_begin(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, env::ECfg *e, 
     e->log_cap = cap; e->n_actions = v.n_actions; e->actions = v.actions.as<double>();
     return STMPC_OK;
 }
-// the step entries, after their own checks of N and of their pointers: the env cfg against the environment in the context (`reset_entry` made it), which
-// then completes the ECfg (but for the seed)
+// the env cfg of a step against the environment in the context (`reset_entry` made it), which then completes the ECfg (but for the seed)
 int env_step_begin(const stmpc_ctx *c, const stmpc_env_cfg *ec, int obs_stride, const char *reset_entry, env::ECfg *e) {
     TRY(make_envcfg(ec, e));
     if (obs_stride < e->obs_len) return fail(STMPC_EINVAL, "obs_stride is shorter than the observation");
@@ -2636,136 +2636,7 @@ int env_step_begin(const stmpc_ctx *c, const stmpc_env_cfg *ec, int obs_stride, 
     e->log_cap = c->env.log_cap; e->n_actions = c->env.n_actions; e->actions = c->env.actions.as<double>();
     return STMPC_OK;
 }
-}  // namespace
 
-extern "C" {
-
-uint64_t stmpc_env_episode_seed(uint64_t seed, uint32_t episode) { return env::episode_seed(seed, episode); }
-
-int stmpc_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, float *d_obs, int obs_stride, void *stream) {
-    env::ECfg e;
-    TRY(env_reset_check(c, p, ec, d_obs, obs_stride, &e));
-    TRY(stmpc_sim_init_device(c, g, N, stream));
-    TRY(env_reset_begin(c, ec, N, &e, stream));
-    sim::Cfg sc;
-    TRY(make_simcfg(g, &sc));
-    sim_route_of(c, &sc);
-    e.seed = sc.seed;
-    hipLaunchKernelGGL(env::k_env_reset, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, sc, N, c->sim.state(), env_state(c), d_obs, obs_stride);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_env_reset_groups_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *cfgs, int G, int n_per_group, const stmpc_env_cfg *ec, float *d_obs,
-                                  int obs_stride, void *stream) {
-    env::ECfg e;
-    TRY(env_reset_check(c, p, ec, d_obs, obs_stride, &e));
-    TRY(stmpc_sim_init_groups_device(c, cfgs, G, n_per_group, stream));
-    TRY(env_reset_begin(c, ec, G * n_per_group, &e, stream));
-    e.seed = 0;                                  // (unused: a group's environments take their seed from the group's cfg)
-    hipLaunchKernelGGL(env::k_env_reset_groups, dim3((n_per_group + 63) / 64, G), dim3(64), 0, (hipStream_t)stream, e, c->sim.groups.as<sim::Cfg>(), n_per_group,
-                       c->sim.state(), env_state(c), d_obs, obs_stride);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_env_step_groups_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
-                                 double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    TRY(check_grouped_world(c, N));
-    if (N != c->env.N) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_groups_device");
-    if (c->env.R) return fail(STMPC_EINVAL, REWARD_GROUPED_ENV);
-    if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    env::ECfg e;
-    DevP dp;
-    TRY(env_step_begin(c, ec, obs_stride, "stmpc_env_reset_groups_device", &e));
-    TRY(make_devp(p, &dp));
-    e.seed = 0;
-    HIPCHK(hipSetDevice(c->device));
-    const int npg = c->sim.n_per_group;
-    const dim3 grid((N + 63) / 64), ggrid((npg + 63) / 64, c->sim.G), block(64);
-    const sim::State s = c->sim.state();
-    const env::EState es = env_state(c);
-    const sim::Cfg *groups = c->sim.groups.as<sim::Cfg>();
-    hipLaunchKernelGGL(env::k_env_act, grid, block, 0, (hipStream_t)stream, e, N, s, es, d_action);
-    hipLaunchKernelGGL(sim::k_sim_step_groups, ggrid, block, 0, (hipStream_t)stream, dp, groups, npg, s, (const double *)es.cmd, p->crash_min_s);
-    hipLaunchKernelGGL(env::k_env_post_groups, ggrid, block, 0, (hipStream_t)stream, e, groups, npg, s, es, d_obs, obs_stride, d_reward, d_terminated, d_truncated,
-                       d_final_obs, d_final_stats);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
-                          double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device");
-    if (c->sim.G) return fail(STMPC_EINVAL, GROUPED_WORLD);
-    if (c->env.R) return fail(STMPC_EINVAL, REWARD_GROUPED_ENV);
-    if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    env::ECfg e;
-    sim::Cfg sc;
-    DevP dp;
-    TRY(env_step_begin(c, ec, obs_stride, "stmpc_env_reset_device", &e));
-    TRY(make_simcfg(g, &sc));
-    sim_route_of(c, &sc);
-    TRY(make_devp(p, &dp));
-    e.seed = sc.seed;
-    HIPCHK(hipSetDevice(c->device));
-    const dim3 grid((N + 63) / 64), block(64);
-    const sim::State s = c->sim.state();
-    const env::EState es = env_state(c);
-    hipLaunchKernelGGL(env::k_env_act, grid, block, 0, (hipStream_t)stream, e, N, s, es, d_action);
-    hipLaunchKernelGGL(sim::k_sim_step, grid, block, 0, (hipStream_t)stream, dp, sc, N, s, (const double *)es.cmd, p->crash_min_s);
-    hipLaunchKernelGGL(env::k_env_post, grid, block, 0, (hipStream_t)stream, e, sc, N, s, es, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_env_reward_device(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, int Kmax, const double *d_ego4, const int32_t *d_k, const double *d_ox, const double *d_ov,
-                            const double *d_oa, const double *d_jerk, const int32_t *d_crashed, const int32_t *d_arrived, double *d_reward, void *stream) {
-    (void)d_ov; (void)d_oa;        // (no reward function reads the other vehicles' speeds or accelerations)
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    env::ECfg e;
-    TRY(make_envcfg(ec, &e));
-    if (N < 0 || Kmax < 0 || Kmax > sim::KS) return fail(STMPC_EINVAL, "N or Kmax out of range (Kmax <= 64)");
-    if (N == 0) return STMPC_OK;
-    if (!d_ego4 || !d_k || !d_jerk || !d_reward || (Kmax > 0 && !d_ox)) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(env::k_env_reward, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed, d_arrived, d_reward);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_env_drain(stmpc_ctx *c, int max_rows, double *rows, int64_t *n_rows, int64_t *n_dropped) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (!n_rows || (max_rows > 0 && !rows)) return fail(STMPC_EINVAL, "NULL host pointer");
-    if (c->env.N < 1) return fail(STMPC_EINVAL, "no environment in this context (stmpc_env_reset_device)");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipDeviceSynchronize());
-    unsigned cnt = 0;
-    TRY(download(&cnt, c->env.log_n, 1));
-    const int64_t kept = cnt < (unsigned)c->env.log_cap ? (int64_t)cnt : (int64_t)c->env.log_cap;
-    const int64_t take = kept < (int64_t)(max_rows > 0 ? max_rows : 0) ? kept : (int64_t)(max_rows > 0 ? max_rows : 0);
-    if (take) TRY(download(rows, c->env.log, (size_t)take * env::NLOG));
-    HIPCHK(hipMemset(c->env.log_n.p, 0, 4));
-    *n_rows = take;
-    if (n_dropped) *n_dropped = (int64_t)cnt - take;
-    return STMPC_OK;
-}
-
-int stmpc_env_episode_ticks_device(stmpc_ctx *c, int N, int32_t *d_ticks, void *stream) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->env.N || N < 1 || !d_ticks) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device, or NULL pointer");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(d_ticks, c->sim.ticks.p, (size_t)N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return STMPC_OK;
-}
-
-}  // extern "C"
-
-// ---- reward groups (stmpc_reward_groups_*): kernels in stmpc_env_groups_kernels.hpp ----
-// The reference's per-run reward settings (dqn.py:449-563, rl.py:168-174, merge_gym.py:25,83-140) as a group axis of one vector environment.
-namespace {
 // Every cfg valid, and equal in what the shared ECfg, the one action table, the one log and the one observation hold.  Changes nothing; `rows` receives
 // the R table rows.
 int check_reward_groups(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *cfgs, int R, int n_per_group, const float *d_obs, int obs_stride,
@@ -2798,16 +2669,204 @@ int check_reward_groups(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg
     }
     return STMPC_OK;
 }
-// the checks every reward-groups step or reward entry starts with
-int check_reward_grouped_env(const stmpc_ctx *c) {
-    if (c->env.N < 1 || c->env.R < 1)
-        return fail(STMPC_EINVAL, "the env has no reward groups (stmpc_reward_groups_env_reset_device): use the plain or the traffic-groups step entry");
+// the shielded env's cfg (its reset and its step)
+int shield_cfg_check(const stmpc_params *p, const stmpc_shield_env_cfg *sh, int N) {
+    if (!sh) return fail(STMPC_EINVAL, "shield cfg is NULL");
+    if (sh->kmax < 1 || sh->kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "shield cfg: kmax must be 1 ... STMPC_KMAX_LIMIT (32), the solver's vehicles per state");
+    if (!(sh->takeover_penalty >= 0) || !(sh->takeover_penalty <= 1.7976931348623157e308)) return fail(STMPC_EINVAL, "shield cfg: takeover_penalty must be finite and not negative");
+    return first_step_check(p, &sh->fs, N, sh->kmax);
+}
+
+// ---- one reset, one step and one reward body behind the plain, traffic-groups, reward-groups and shielded entries ----
+// Which env shapes an entry serves: a shape the context has and the entry refuses, or lacks and the entry requires, is STMPC_EINVAL.
+enum Need { REFUSED, EITHER, REQUIRED };
+struct EnvEntry {
+    const char *reset_entry;                 // the reset entry that makes this entry's env (for messages)
+    Need traffic_groups, reward_groups, shield;
+};
+const EnvEntry PLAIN_ENV{"stmpc_env_reset_device", REFUSED, REFUSED, EITHER};       // (on a shield-reset context: the unshielded step)
+const EnvEntry TRAFFIC_GROUPS_ENV{"stmpc_env_reset_groups_device", REQUIRED, REFUSED, EITHER};
+const EnvEntry REWARD_GROUPS_ENV{"stmpc_reward_groups_env_reset_device", EITHER, REQUIRED, EITHER};
+const EnvEntry SHIELD_ENV{"stmpc_shield_env_reset_device", REFUSED, REFUSED, REQUIRED};
+
+int env_shape_check(const stmpc_ctx *c, const EnvEntry &who) {
+    const auto &v = c->shield;
+    const struct { bool has; Need need; const char *refused, *missing; } shapes[] = {
+        {c->sim.G > 0, who.traffic_groups, GROUPED_WORLD, UNGROUPED_WORLD},
+        {c->env.N >= 1 && c->env.R >= 1, who.reward_groups, REWARD_GROUPED_ENV,
+         "the env has no reward groups (stmpc_reward_groups_env_reset_device): use the plain or the traffic-groups step entry"},
+        {c->env.N >= 1 && v.N == c->env.N && v.generation == c->sim.generation, who.shield, "",
+         "the environment in this context was not reset through stmpc_shield_env_reset_device"},
+    };
+    for (const auto &sh : shapes) {
+        if (sh.has && sh.need == REFUSED) return fail(STMPC_EINVAL, sh.refused);
+        if (!sh.has && sh.need == REQUIRED) return fail(STMPC_EINVAL, sh.missing);
+    }
+    return STMPC_OK;
+}
+
+// Reset.  The world is the lone sim_cfgs[0] with N environments (G = 0) or G traffic groups; the reward is the lone env_cfgs[0] (R = 0) or R reward groups
+// (`rows`: their table, checked by the caller with `e`, the shared cfg).  The caller has made every check of the env's arguments; the world inits make
+// theirs before they change anything.
+int env_reset(stmpc_ctx *c, const stmpc_sim_cfg *sim_cfgs, int G, int n_per_group, int N, const stmpc_env_cfg *env_cfgs, int R, int n_per_rg,
+              const std::vector<env::RewardRow> &rows, env::ECfg e, float *d_obs, int obs_stride, void *stream) {
+    if (G) { TRY(sim_init_groups(c, sim_cfgs, G, n_per_group, stream, STMPC_SIM_GROUPS_MAX)); }
+    else { TRY(stmpc_sim_init_device(c, sim_cfgs, N, stream)); }
+    N = c->sim.N;
+    TRY(env_reset_begin(c, env_cfgs, N, &e, stream));
+    if (R) {
+        HIPCHK(hipMemcpyAsync(c->env.rtab.p, rows.data(), rows.size() * sizeof(env::RewardRow), hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));       // (rows is the caller's local; the step entries read the device copy)
+        c->env.R = R; c->env.n_per_rg = n_per_rg;
+    }
+    if (G) {
+        e.seed = 0;                              // (unused: a group's environments take their seed from the group's cfg)
+        hipLaunchKernelGGL(env::k_env_reset_groups, dim3((n_per_group + 63) / 64, G), dim3(64), 0, (hipStream_t)stream, e, c->sim.groups.as<sim::Cfg>(), n_per_group,
+                           c->sim.state(), env_state(c), d_obs, obs_stride);
+    } else {
+        sim::Cfg sc;
+        TRY(make_simcfg(sim_cfgs, &sc));
+        sim_route_of(c, &sc);
+        if (R) c->env.rg_sc = sc;                // (the reward-groups step takes no sim cfg)
+        e.seed = sc.seed;
+        hipLaunchKernelGGL(env::k_env_reset, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, sc, N, c->sim.state(), env_state(c), d_obs, obs_stride);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+struct StepOut {                             // the tail every step entry takes
+    const void *action;
+    float *obs;
+    int obs_stride;
+    double *reward;
+    uint8_t *terminated, *truncated;
+    float *final_obs;
+    double *final_stats;
+    void *stream;
+};
+struct ShieldStep {                          // what the shielded step takes on top
+    const stmpc_shield_env_cfg *cfg;
+    uint8_t *takeover;
+    int32_t *reason;
+    double *executed_jerk, *executed_action;
+    int32_t *takeover_ticks;
+};
+
+// the world step and the env's reward / observation / autoreset: `lone` is the cfg of an ungrouped world, NULL for the context's traffic groups
+void env_world_step(stmpc_ctx *c, const DevP &dp, double crash_min_s, const env::ECfg &e, const sim::Cfg *lone, bool reward_groups, const StepOut &o) {
+    const int N = c->sim.N, npg = c->sim.n_per_group;
+    const dim3 grid = lone ? dim3((N + 63) / 64) : dim3((npg + 63) / 64, c->sim.G), block(64);
+    hipStream_t st_ = (hipStream_t)o.stream;
+    const sim::State s = c->sim.state();
+    const env::EState es = env_state(c);
+    const env::RewardTab tab = c->env.reward_tab();
+    const sim::Cfg *groups = c->sim.groups.as<sim::Cfg>();
+    if (lone) hipLaunchKernelGGL(sim::k_sim_step, grid, block, 0, st_, dp, *lone, N, s, (const double *)es.cmd, crash_min_s);
+    else hipLaunchKernelGGL(sim::k_sim_step_groups, grid, block, 0, st_, dp, groups, npg, s, (const double *)es.cmd, crash_min_s);
+#define POST(kernel, ...) hipLaunchKernelGGL(env::kernel, grid, block, 0, st_, e, __VA_ARGS__, s, es, o.obs, o.obs_stride, o.reward, o.terminated, o.truncated, o.final_obs, o.final_stats)
+    if (lone && reward_groups) POST(k_env_post_rg, tab, *lone, N);
+    else if (lone) POST(k_env_post, *lone, N);
+    else if (reward_groups) POST(k_env_post_rg_groups, tab, groups, npg);
+    else POST(k_env_post_groups, groups, npg);
+#undef POST
+}
+
+// Step.  `g`: the cfg of a lone world (NULL: the entry takes none); `sh`: the shielded step's arguments, or NULL.
+int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const EnvEntry &who, const StepOut &o,
+             const ShieldStep *sh = nullptr) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(env_shape_check(c, who));
+    if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, std::string("N does not match ") + who.reset_entry);
+    const auto &v = c->shield;
+    if (sh) {
+        TRY(shield_cfg_check(p, sh->cfg, N));
+        if (sh->cfg->kmax != v.kmax) return fail(STMPC_EINVAL, "shield cfg: kmax differs from the one the context was reset with (stmpc_shield_env_reset_device)");
+    }
+    if (!o.action || !o.obs || !o.reward || !o.terminated || !o.truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    if (sh && (!sh->takeover || !sh->reason || !sh->executed_jerk || !sh->takeover_ticks)) return fail(STMPC_EINVAL, "NULL device pointer (shield outputs)");
+    env::ECfg e;
+    sim::Cfg sc;
+    DevP dp;
+    TRY(env_step_begin(c, ec, o.obs_stride, who.reset_entry, &e));
+    if (sh && sh->executed_action && e.mode != env::ACT_CONTINUOUS_JERK)
+        return fail(STMPC_EINVAL, "d_executed_action is the continuous env's (a discrete index is not rewritten): pass NULL");
+    // the world: one cfg -- the caller's, or the one an ungrouped reward-groups reset kept -- or the context's table of traffic groups
+    const bool grouped = c->sim.G > 0, reward_groups = who.reward_groups == REQUIRED;
+    if (!grouped && reward_groups) sc = c->env.rg_sc;
+    else if (!grouped) { TRY(make_simcfg(g, &sc)); sim_route_of(c, &sc); }
+    TRY(make_devp(p, &dp));
+    e.seed = grouped ? 0 : sc.seed;
+    HIPCHK(hipSetDevice(c->device));
+    const dim3 grid((N + 63) / 64), block(64);
+    hipStream_t st_ = (hipStream_t)o.stream;
+    const sim::State s = c->sim.state();
+    const env::EState es = env_state(c);
+    // the action stage: the command of every live environment
+    if (sh) {
+        const env::ShieldView w = v.view();
+        // 1. action handling, the planner's view, the proposal
+        hipLaunchKernelGGL(env::k_shield_env_pre, grid, block, 0, st_, e, sc, N, v.kmax, s, es, o.action, w);
+        HIPCHK(hipGetLastError());
+        // 2. st.do_conditional_st_based_on_first_step on that view and proposal: stmpc_first_step_device's body
+        TRY(first_step_run(c, p, &sh->cfg->fs, N, v.kmax, w.ego5, w.k, w.ox, w.ov, w.proposal, v.speed.as<double>(), v.takeover.as<int32_t>(), v.reason.as<int32_t>(),
+                           o.stream));
+        // 3. what is executed, and what the learner is told
+        hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, sh->cfg->takeover_penalty, N, s, es, o.action, (const double *)v.speed.as<double>(),
+                           (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), sh->takeover, sh->reason,
+                           sh->executed_jerk, sh->executed_action, sh->takeover_ticks);
+    } else if (reward_groups) {
+        hipLaunchKernelGGL(env::k_env_act_rg, grid, block, 0, st_, e, c->env.reward_tab(), N, s, es, o.action);
+    } else {
+        hipLaunchKernelGGL(env::k_env_act, grid, block, 0, st_, e, N, s, es, o.action);
+    }
+    env_world_step(c, dp, p->crash_min_s, e, grouped ? nullptr : &sc, reward_groups, o);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+// Reward of arbitrary batched states: under the one cfg, or (`reward_groups`) state e under reward group e / n_per_reward_group of the context's env.
+int env_reward(stmpc_ctx *c, bool reward_groups, const stmpc_env_cfg *ec, int N, int Kmax, const double *d_ego4, const int32_t *d_k, const double *d_ox,
+               const double *d_jerk, const int32_t *d_crashed, const int32_t *d_arrived, double *d_reward, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (reward_groups) TRY(env_shape_check(c, REWARD_GROUPS_ENV));
+    env::ECfg e;
+    TRY(make_envcfg(ec, &e));
+    if (N < 0 || (reward_groups && N > c->env.N) || Kmax < 0 || Kmax > sim::KS)
+        return fail(STMPC_EINVAL, "N or Kmax out of range (Kmax <= 64; with reward groups N <= R * n_per_reward_group)");
+    if (N == 0) return STMPC_OK;
+    if (!d_ego4 || !d_k || !d_jerk || !d_reward || (Kmax > 0 && !d_ox)) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c->device));
+    const dim3 grid((N + 63) / 64), block(64);
+    if (reward_groups)
+        hipLaunchKernelGGL(env::k_env_reward_rg, grid, block, 0, (hipStream_t)stream, e, c->env.reward_tab(), N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed, d_arrived,
+                           d_reward);
+    else hipLaunchKernelGGL(env::k_env_reward, grid, block, 0, (hipStream_t)stream, e, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed, d_arrived, d_reward);
+    HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 }  // namespace
 
 extern "C" {
 
+uint64_t stmpc_env_episode_seed(uint64_t seed, uint32_t episode) { return env::episode_seed(seed, episode); }
+
+int stmpc_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, float *d_obs, int obs_stride, void *stream) {
+    env::ECfg e;
+    TRY(env_reset_check(c, p, ec, d_obs, obs_stride, &e));
+    return env_reset(c, g, 0, 0, N, ec, 0, 0, {}, e, d_obs, obs_stride, stream);
+}
+
+int stmpc_env_reset_groups_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *cfgs, int G, int n_per_group, const stmpc_env_cfg *ec, float *d_obs,
+                                  int obs_stride, void *stream) {
+    env::ECfg e;
+    TRY(env_reset_check(c, p, ec, d_obs, obs_stride, &e));
+    std::vector<sim::Cfg> world;
+    TRY(check_groups(cfgs, G, n_per_group, &world));
+    return env_reset(c, cfgs, G, n_per_group, 0, ec, 0, 0, {}, e, d_obs, obs_stride, stream);
+}
+
+// The reference's per-run reward settings (dqn.py:449-563, rl.py:168-174, merge_gym.py:25,83-140) as a group axis of one vector environment.
 int stmpc_reward_groups_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int G, int n_per_traffic_group,
                                          const stmpc_env_cfg *env_cfgs, int R, int n_per_reward_group, float *d_obs, int obs_stride, void *stream) {
     std::vector<env::RewardRow> rows;
@@ -2822,104 +2881,10 @@ int stmpc_reward_groups_env_reset_device(stmpc_ctx *c, const stmpc_params *p, co
                                   "n_per_reward_group n_per_traffic_group");
     HIPCHK(hipSetDevice(c->device));
     TRY(c->env.rtab.ensure((size_t)STMPC_ENV_REWARD_GROUPS_MAX * sizeof(env::RewardRow)));   // (its full size once: never reallocated under a running kernel)
-    // nothing has changed so far
-    if (G) { TRY(stmpc_sim_init_groups_device(c, sim_cfgs, G, n_per_traffic_group, stream)); }
-    else { TRY(stmpc_sim_init_device(c, &sim_cfgs[0], N, stream)); }
-    TRY(env_reset_begin(c, &env_cfgs[0], N, &e, stream));
-    HIPCHK(hipMemcpyAsync(c->env.rtab.p, rows.data(), rows.size() * sizeof(env::RewardRow), hipMemcpyHostToDevice, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));           // (rows is a local; the step entries read the device copy)
-    c->env.R = R; c->env.n_per_rg = n_per_reward_group;
-    if (G) {
-        e.seed = 0;
-        hipLaunchKernelGGL(env::k_env_reset_groups, dim3((n_per_traffic_group + 63) / 64, G), dim3(64), 0, (hipStream_t)stream, e, c->sim.groups.as<sim::Cfg>(),
-                           n_per_traffic_group, c->sim.state(), env_state(c), d_obs, obs_stride);
-    } else {
-        sim::Cfg sc = world[0];
-        sim_route_of(c, &sc);
-        c->env.rg_sc = sc;
-        e.seed = sc.seed;
-        hipLaunchKernelGGL(env::k_env_reset, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, sc, N, c->sim.state(), env_state(c), d_obs, obs_stride);
-    }
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    return env_reset(c, sim_cfgs, G, n_per_traffic_group, N, env_cfgs, R, n_per_reward_group, rows, e, d_obs, obs_stride, stream);
 }
 
-int stmpc_reward_groups_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
-                                        double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    TRY(check_reward_grouped_env(c));
-    if (N != c->env.N || N != c->sim.N) return fail(STMPC_EINVAL, "N does not match stmpc_reward_groups_env_reset_device (R * n_per_reward_group)");
-    if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    env::ECfg e;
-    DevP dp;
-    TRY(env_step_begin(c, ec, obs_stride, "stmpc_reward_groups_env_reset_device", &e));
-    TRY(make_devp(p, &dp));
-    HIPCHK(hipSetDevice(c->device));
-    const dim3 grid((N + 63) / 64), block(64);
-    const sim::State s = c->sim.state();
-    const env::EState es = env_state(c);
-    const env::RewardTab tab = c->env.reward_tab();
-    hipLaunchKernelGGL(env::k_env_act_rg, grid, block, 0, (hipStream_t)stream, e, tab, N, s, es, d_action);
-    if (c->sim.G) {
-        const int npg = c->sim.n_per_group;
-        const dim3 ggrid((npg + 63) / 64, c->sim.G);
-        const sim::Cfg *groups = c->sim.groups.as<sim::Cfg>();
-        e.seed = 0;
-        hipLaunchKernelGGL(sim::k_sim_step_groups, ggrid, block, 0, (hipStream_t)stream, dp, groups, npg, s, (const double *)es.cmd, p->crash_min_s);
-        hipLaunchKernelGGL(env::k_env_post_rg_groups, ggrid, block, 0, (hipStream_t)stream, e, tab, groups, npg, s, es, d_obs, obs_stride, d_reward, d_terminated,
-                           d_truncated, d_final_obs, d_final_stats);
-    } else {
-        const sim::Cfg sc = c->env.rg_sc;
-        e.seed = sc.seed;
-        hipLaunchKernelGGL(sim::k_sim_step, grid, block, 0, (hipStream_t)stream, dp, sc, N, s, (const double *)es.cmd, p->crash_min_s);
-        hipLaunchKernelGGL(env::k_env_post_rg, grid, block, 0, (hipStream_t)stream, e, tab, sc, N, s, es, d_obs, obs_stride, d_reward, d_terminated, d_truncated,
-                           d_final_obs, d_final_stats);
-    }
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_reward_groups_env_reward_device(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, int Kmax, const double *d_ego4, const int32_t *d_k, const double *d_ox,
-                                          const double *d_ov, const double *d_oa, const double *d_jerk, const int32_t *d_crashed, const int32_t *d_arrived,
-                                          double *d_reward, void *stream) {
-    (void)d_ov; (void)d_oa;
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    TRY(check_reward_grouped_env(c));
-    env::ECfg e;
-    TRY(make_envcfg(ec, &e));
-    if (N < 0 || N > c->env.N || Kmax < 0 || Kmax > sim::KS) return fail(STMPC_EINVAL, "N or Kmax out of range (N <= R * n_per_reward_group, Kmax <= 64)");
-    if (N == 0) return STMPC_OK;
-    if (!d_ego4 || !d_k || !d_jerk || !d_reward || (Kmax > 0 && !d_ox)) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(env::k_env_reward_rg, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, c->env.reward_tab(), N, Kmax, d_ego4, d_k, d_ox, d_jerk,
-                       d_crashed, d_arrived, d_reward);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_reward_groups_split(stmpc_ctx *c, int *R, int *n_per_group) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    const bool on = c->env.N >= 1;
-    if (R) *R = on ? c->env.R : 0;
-    if (n_per_group) *n_per_group = on ? c->env.n_per_rg : 0;
-    return STMPC_OK;
-}
-
-}  // extern "C"
-
-// ---- shielded vector environment (stmpc_shield_env_*): kernels in stmpc_shield_env_kernels.hpp ----
-// The env step behind st.do_conditional_st_based_on_first_step (st.py:805-814): the action is a proposal, the shield decides what is executed.
-namespace {
-int shield_cfg_check(const stmpc_params *p, const stmpc_shield_env_cfg *sh, int N) {
-    if (!sh) return fail(STMPC_EINVAL, "shield cfg is NULL");
-    if (sh->kmax < 1 || sh->kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "shield cfg: kmax must be 1 ... STMPC_KMAX_LIMIT (32), the solver's vehicles per state");
-    if (!(sh->takeover_penalty >= 0) || !(sh->takeover_penalty <= 1.7976931348623157e308)) return fail(STMPC_EINVAL, "shield cfg: takeover_penalty must be finite and not negative");
-    return first_step_check(p, &sh->fs, N, sh->kmax);
-}
-}  // namespace
-
-extern "C" {
-
+// The env behind st.do_conditional_st_based_on_first_step (st.py:805-814): the plain reset, then the shield's buffers and zeroed counters.
 int stmpc_shield_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N,
                                   float *d_obs, int obs_stride, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
@@ -2938,50 +2903,72 @@ int stmpc_shield_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stm
     return STMPC_OK;
 }
 
+int stmpc_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
+                          double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
+    return env_step(c, p, g, ec, N, PLAIN_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream});
+}
+
+int stmpc_env_step_groups_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
+                                 double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
+    return env_step(c, p, nullptr, ec, N, TRAFFIC_GROUPS_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream});
+}
+
+int stmpc_reward_groups_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
+                                        double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, void *stream) {
+    return env_step(c, p, nullptr, ec, N, REWARD_GROUPS_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream});
+}
+
 int stmpc_shield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N,
                                  const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
                                  float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk,
                                  double *d_executed_action, int32_t *d_takeover_ticks, void *stream) {
+    const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    return env_step(c, p, g, ec, N, SHIELD_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, &shield);
+}
+
+int stmpc_env_reward_device(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, int Kmax, const double *d_ego4, const int32_t *d_k, const double *d_ox, const double *d_ov,
+                            const double *d_oa, const double *d_jerk, const int32_t *d_crashed, const int32_t *d_arrived, double *d_reward, void *stream) {
+    (void)d_ov; (void)d_oa;        // (no reward function reads the other vehicles' speeds or accelerations)
+    return env_reward(c, false, ec, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed, d_arrived, d_reward, stream);
+}
+
+int stmpc_reward_groups_env_reward_device(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, int Kmax, const double *d_ego4, const int32_t *d_k, const double *d_ox,
+                                          const double *d_ov, const double *d_oa, const double *d_jerk, const int32_t *d_crashed, const int32_t *d_arrived,
+                                          double *d_reward, void *stream) {
+    (void)d_ov; (void)d_oa;
+    return env_reward(c, true, ec, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed, d_arrived, d_reward, stream);
+}
+
+int stmpc_env_drain(stmpc_ctx *c, int max_rows, double *rows, int64_t *n_rows, int64_t *n_dropped) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, "N does not match stmpc_shield_env_reset_device");
-    if (c->sim.G) return fail(STMPC_EINVAL, "the world has traffic groups: the shielded env step serves an ungrouped world only");
-    if (c->env.R) return fail(STMPC_EINVAL, "the env has reward groups: the shielded env step serves one reward only");
-    const auto &v = c->shield;
-    if (v.N != N || v.generation != c->sim.generation)
-        return fail(STMPC_EINVAL, "the environment in this context was not reset through stmpc_shield_env_reset_device");
-    TRY(shield_cfg_check(p, sh, N));
-    if (sh->kmax != v.kmax) return fail(STMPC_EINVAL, "shield cfg: kmax differs from the one the context was reset with (stmpc_shield_env_reset_device)");
-    if (!d_action || !d_obs || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    if (!d_takeover || !d_reason || !d_executed_jerk || !d_takeover_ticks) return fail(STMPC_EINVAL, "NULL device pointer (shield outputs)");
-    env::ECfg e;
-    sim::Cfg sc;
-    DevP dp;
-    TRY(env_step_begin(c, ec, obs_stride, "stmpc_shield_env_reset_device", &e));
-    if (d_executed_action && e.mode != env::ACT_CONTINUOUS_JERK)
-        return fail(STMPC_EINVAL, "d_executed_action is the continuous env's (a discrete index is not rewritten): pass NULL");
-    TRY(make_simcfg(g, &sc));
-    sim_route_of(c, &sc);
-    TRY(make_devp(p, &dp));
-    e.seed = sc.seed;
+    if (!n_rows || (max_rows > 0 && !rows)) return fail(STMPC_EINVAL, "NULL host pointer");
+    if (c->env.N < 1) return fail(STMPC_EINVAL, "no environment in this context (stmpc_env_reset_device)");
     HIPCHK(hipSetDevice(c->device));
-    const dim3 grid((N + 63) / 64), block(64);
-    hipStream_t st_ = (hipStream_t)stream;
-    const sim::State s = c->sim.state();
-    const env::EState es = env_state(c);
-    const env::ShieldView w = v.view();
-    // 1. action handling, the planner's view, the proposal
-    hipLaunchKernelGGL(env::k_shield_env_pre, grid, block, 0, st_, e, sc, N, v.kmax, s, es, d_action, w);
-    HIPCHK(hipGetLastError());
-    // 2. st.do_conditional_st_based_on_first_step on that view and proposal: stmpc_first_step_device's body
-    TRY(first_step_run(c, p, &sh->fs, N, v.kmax, w.ego5, w.k, w.ox, w.ov, w.proposal, v.speed.as<double>(), v.takeover.as<int32_t>(), v.reason.as<int32_t>(), stream));
-    // 3. what is executed, and what the learner is told
-    hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, sh->takeover_penalty, N, s, es, d_action, (const double *)v.speed.as<double>(),
-                       (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), d_takeover, d_reason,
-                       d_executed_jerk, d_executed_action, d_takeover_ticks);
-    // 4. the world step and the env's reward / observation / autoreset, as stmpc_env_step_device launches them
-    hipLaunchKernelGGL(sim::k_sim_step, grid, block, 0, st_, dp, sc, N, s, (const double *)es.cmd, p->crash_min_s);
-    hipLaunchKernelGGL(env::k_env_post, grid, block, 0, st_, e, sc, N, s, es, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats);
-    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    unsigned cnt = 0;
+    TRY(download(&cnt, c->env.log_n, 1));
+    const int64_t kept = cnt < (unsigned)c->env.log_cap ? (int64_t)cnt : (int64_t)c->env.log_cap;
+    const int64_t take = kept < (int64_t)(max_rows > 0 ? max_rows : 0) ? kept : (int64_t)(max_rows > 0 ? max_rows : 0);
+    if (take) TRY(download(rows, c->env.log, (size_t)take * env::NLOG));
+    HIPCHK(hipMemset(c->env.log_n.p, 0, 4));
+    *n_rows = take;
+    if (n_dropped) *n_dropped = (int64_t)cnt - take;
+    return STMPC_OK;
+}
+
+int stmpc_env_episode_ticks_device(stmpc_ctx *c, int N, int32_t *d_ticks, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    if (N != c->env.N || N < 1 || !d_ticks) return fail(STMPC_EINVAL, "N does not match stmpc_env_reset_device, or NULL pointer");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(d_ticks, c->sim.ticks.p, (size_t)N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return STMPC_OK;
+}
+
+int stmpc_reward_groups_split(stmpc_ctx *c, int *R, int *n_per_group) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    const bool on = c->env.N >= 1;
+    if (R) *R = on ? c->env.R : 0;
+    if (n_per_group) *n_per_group = on ? c->env.n_per_rg : 0;
     return STMPC_OK;
 }
 

@@ -3,7 +3,7 @@
 // one of four functions, every file under its configs/ overrides their weights, merge_gym.py:25 adds INVALID_ACTION_PENALTY -- and compares rewards by
 // one TRAIN_DDPG run per setting; here the envs of several settings are stepped side by side.
 //
-// Every kernel is the arithmetic of its lone twin in stmpc_env_kernels.hpp (env_post_body, reward, handle_jerk, handle_acceleration -- called, not copied)
+// Every kernel is the arithmetic of its lone twin in stmpc_env_kernels.hpp (env_act_body, env_post_body, reward -- called, not copied)
 // on an ECfg whose reward fields come from row e / n_per_group of a device table of RewardRow, e the environment's row in the world:
 //   k_env_act_rg          k_env_act with the row's invalid-action penalty;
 //   k_env_post_rg         k_env_post (an ungrouped world);
@@ -42,7 +42,7 @@ __device__ __forceinline__ ECfg cfg_of_row(const ECfg &c, const RewardTab &t, in
     return o;
 }
 
-// k_env_act's dispatch with the penalty of the environment's reward group (the only field of the action handling that may differ)
+// k_env_act with the penalty of the environment's reward group (the only field of the action handling that may differ)
 __global__ void __launch_bounds__(64) k_env_act_rg(ECfg c, RewardTab tab, int N, sim::State s, EState es, const void *__restrict__ action) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
@@ -50,22 +50,7 @@ __global__ void __launch_bounds__(64) k_env_act_rg(ECfg c, RewardTab tab, int N,
     es.live[e] = live;
     if (!live) return;
     c.penalty = tab.rows[e / tab.n_per_group].penalty;
-    const double v = s.ego4[e * 4 + 2], a = s.ego4[e * 4 + 3], prev_a = es.prev_a[e];
-    double pjerk = 0.0, inv = 0.0, cmd;
-    if (c.mode == ACT_CONTINUOUS_JERK) {
-        cmd = handle_jerk(c, v, a, prev_a, ((const double *)action)[e], pjerk, inv);
-    } else {
-        const int idx = ((const int *)action)[e];
-        if (idx < 0 || idx >= c.n_actions) {
-            es.err[0] = 1u;
-            cmd = __builtin_nan("");
-        } else if (c.mode == ACT_JERK) {
-            cmd = handle_jerk(c, v, a, prev_a, c.actions[idx], pjerk, inv);
-        } else {
-            cmd = handle_acceleration(c, v, a, prev_a, c.actions[idx], pjerk, inv);
-        }
-    }
-    es.cmd[e] = cmd; es.pjerk[e] = pjerk; es.inv[e] = inv;
+    env_act_body(c, e, s, es, action);
 }
 
 __global__ void __launch_bounds__(64) k_env_post_rg(ECfg c, RewardTab tab, sim::Cfg sc, int N, sim::State s, EState es, float *__restrict__ obs, int obs_stride,

@@ -181,28 +181,40 @@ __device__ __forceinline__ void env_obs(const ECfg &c, const sim::Cfg &sc, const
     dev_policy_features(c.f, e, sim::KS, s.ego4, es.k, es.vx, es.vv, es.va, nullptr, nullptr, row);
 }
 
+// The env's action handling for environment e of the arrays `action` points at (ContinuousJerkEnv / JerkEnv / AccelerationEnv._do_action, merge_gym.py:83-100,
+// 193-221): a continuous jerk (not clipped to the Box: the reference does not either), or an index into the table of jerks or of accelerations.  The one
+// dispatch of k_env_act, k_env_act_rg and k_shield_env_pre.  Returns "the index is out of range": cmd is then left to the caller, pjerk and inv are 0.
+__device__ __forceinline__ bool handle_action(const ECfg &c, const void *__restrict__ action, int e, double v, double a, double prev_a, double &cmd, double &pjerk,
+                                              double &inv) {
+    pjerk = 0.0; inv = 0.0;
+    if (c.mode == ACT_CONTINUOUS_JERK) {
+        cmd = handle_jerk(c, v, a, prev_a, ((const double *)action)[e], pjerk, inv);
+        return false;
+    }
+    const int idx = ((const int *)action)[e];
+    if (idx < 0 || idx >= c.n_actions) return true;
+    if (c.mode == ACT_JERK) cmd = handle_jerk(c, v, a, prev_a, c.actions[idx], pjerk, inv);
+    else cmd = handle_acceleration(c, v, a, prev_a, c.actions[idx], pjerk, inv);
+    return false;
+}
+
+// k_env_act's body with the cfg of environment e (the reward groups' kernel passes the group's penalty in it)
+__device__ __forceinline__ void env_act_body(const ECfg &c, int e, const sim::State &s, const EState &es, const void *__restrict__ action) {
+    const double v = s.ego4[e * 4 + 2], a = s.ego4[e * 4 + 3], prev_a = es.prev_a[e];
+    double pjerk, inv, cmd;
+    if (handle_action(c, action, e, v, a, prev_a, cmd, pjerk, inv)) {
+        es.err[0] = 1u;                                                    // (reported by stmpc_check_error; the ego keeps its speed)
+        cmd = __builtin_nan("");
+    }
+    es.cmd[e] = cmd; es.pjerk[e] = pjerk; es.inv[e] = inv;
+}
 __global__ void __launch_bounds__(64) k_env_act(ECfg c, int N, sim::State s, EState es, const void *__restrict__ action) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     const int live = s.status[e] == 0;
     es.live[e] = live;
     if (!live) return;                                                     // (k_sim_step idles finished environments)
-    const double v = s.ego4[e * 4 + 2], a = s.ego4[e * 4 + 3], prev_a = es.prev_a[e];
-    double pjerk = 0.0, inv = 0.0, cmd;
-    if (c.mode == ACT_CONTINUOUS_JERK) {
-        cmd = handle_jerk(c, v, a, prev_a, ((const double *)action)[e], pjerk, inv);       // not clipped to the Box: the reference does not either
-    } else {
-        const int idx = ((const int *)action)[e];
-        if (idx < 0 || idx >= c.n_actions) {
-            es.err[0] = 1u;                                                // (reported by stmpc_check_error; the ego keeps its speed)
-            cmd = __builtin_nan("");
-        } else if (c.mode == ACT_JERK) {
-            cmd = handle_jerk(c, v, a, prev_a, c.actions[idx], pjerk, inv);
-        } else {
-            cmd = handle_acceleration(c, v, a, prev_a, c.actions[idx], pjerk, inv);
-        }
-    }
-    es.cmd[e] = cmd; es.pjerk[e] = pjerk; es.inv[e] = inv;
+    env_act_body(c, e, s, es, action);
 }
 
 // `es` moved on by `off` environments (a traffic group's slice); the episode log, its counter and the error word stay the world's

@@ -24,7 +24,7 @@ struct ShieldView {                         // device arrays: the planner's view
     double *proposal;                       // [N] the proposed speed
 };
 
-// k_env_act's dispatch (restated, as k_env_act_rg restates it) + the shield's view and proposal.  A finished environment gets the view k_sim_view
+// k_env_act's dispatch (handle_action, called) + the shield's view and proposal.  A finished environment gets the view k_sim_view
 // gives it and proposes the speed its action would command from that state -- what episodes.EpisodeRunner(controller="first_step") proposes for a
 // finished environment, so that the context's stmpc_first_step_counts are the runner's row for row -- while its step state is left alone, as
 // k_env_act leaves it.  An index out of range latches the error word as k_env_act does (a running environment's only) and proposes -- and
@@ -37,19 +37,10 @@ __global__ void __launch_bounds__(64) k_shield_env_pre(ECfg c, sim::Cfg sc, int 
     const int live = s.status[e] == 0;
     es.live[e] = live;
     const double v = s.ego4[e * 4 + 2], a = s.ego4[e * 4 + 3], prev_a = es.prev_a[e];
-    double pjerk = 0.0, inv = 0.0, cmd;
-    if (c.mode == ACT_CONTINUOUS_JERK) {
-        cmd = handle_jerk(c, v, a, prev_a, ((const double *)action)[e], pjerk, inv);
-    } else {
-        const int idx = ((const int *)action)[e];
-        if (idx < 0 || idx >= c.n_actions) {
-            if (live) es.err[0] = 1u;
-            cmd = v;
-        } else if (c.mode == ACT_JERK) {
-            cmd = handle_jerk(c, v, a, prev_a, c.actions[idx], pjerk, inv);
-        } else {
-            cmd = handle_acceleration(c, v, a, prev_a, c.actions[idx], pjerk, inv);
-        }
+    double pjerk, inv, cmd;
+    if (handle_action(c, action, e, v, a, prev_a, cmd, pjerk, inv)) {
+        if (live) es.err[0] = 1u;
+        cmd = v;
     }
     w.proposal[e] = cmd;
     if (!live) return;                                                     // (k_sim_step idles finished environments)

@@ -13,6 +13,7 @@ ramp's start), not the reference's 20 s warm-up plus one tick (merge_gym.py:142-
 has no TimeFeature input (that wraps the agent, not the env: ddpg.py:41); the world is a restatement, not SUMO, so
 whole-episode outcomes are not the reference's, while rewards, actions and observations are pinned to it.
 """
+import functools
 import weakref
 
 import numpy as np
@@ -211,21 +212,28 @@ class MergeVecEnv:
             self._takeover, self._reason = z(self.n, dtype=torch.bool), z(self.n, dtype=torch.int32)
             self._exec_jerk, self._takeover_ticks = z(self.n), z(self.n, dtype=torch.int32)
             self._exec_action = z(self.n) if self.continuous else None
+        # the env's reset and step entry, bound to their leading arguments: reset(d_obs, obs_stride, stream) and step(d_action, d_obs, ..., stream)
+        bind, c = functools.partial, self.ctx
+        if shield is not None:
+            self._reset = bind(c.shield_env_reset, self.params, self.sim_cfg, self.cfg, self.shield_cfg, self.n)
+            self._step = bind(c.shield_env_step, self.params, self.sim_cfg, self.cfg, self.shield_cfg, self.n)
+        elif self.R:
+            self._reset = bind(c.env_reset_reward_groups, self.params, self.sim_cfgs if self.sim_cfgs is not None else self.sim_cfg, self.n_per_group,
+                               self.reward_cfgs, self.n_per_reward_group)
+            self._step = bind(c.env_step_reward_groups, self.params, self.cfg, self.n)
+        elif self.sim_cfgs is not None:
+            self._reset = bind(c.env_reset_groups, self.params, self.sim_cfgs, self.n_per_group, self.cfg)
+            self._step = bind(c.env_step_groups, self.params, self.cfg, self.n)
+        else:
+            self._reset = bind(c.env_reset, self.params, self.sim_cfg, self.cfg, self.n)
+            self._step = bind(c.env_step, self.params, self.sim_cfg, self.cfg, self.n)
 
     def reset(self):
         """Every environment back to episode 0 (``stmpc_env_reset_device``, or the reset entry of the env's traffic groups, reward groups or shield):
         the observations of the start states [n][obs_dim] float32."""
         self._cur = 0
         obs = self._obs[0]
-        if self.shield_cfg is not None:
-            self.ctx.shield_env_reset(self.params, self.sim_cfg, self.cfg, self.shield_cfg, self.n, obs.data_ptr(), self.obs_dim, self._stream())
-        elif self.R:
-            self.ctx.env_reset_reward_groups(self.params, self.sim_cfgs if self.sim_cfgs is not None else self.sim_cfg, self.n_per_group, self.reward_cfgs,
-                                             self.n_per_reward_group, obs.data_ptr(), self.obs_dim, self._stream())
-        elif self.sim_cfgs is not None:
-            self.ctx.env_reset_groups(self.params, self.sim_cfgs, self.n_per_group, self.cfg, obs.data_ptr(), self.obs_dim, self._stream())
-        else:
-            self.ctx.env_reset(self.params, self.sim_cfg, self.cfg, self.n, obs.data_ptr(), self.obs_dim, self._stream())
+        self._reset(obs.data_ptr(), self.obs_dim, self._stream())
         _owners[self.ctx] = self
         self._reset_done = True
         return obs
@@ -261,21 +269,12 @@ class MergeVecEnv:
         a = self._action_tensor(action)
         self._cur ^= 1
         obs = self._obs[self._cur]
+        shield_out = ()
         if self.shield_cfg is not None:
-            self.ctx.shield_env_step(self.params, self.sim_cfg, self.cfg, self.shield_cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim,
-                                     self._reward.data_ptr(), self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(),
-                                     self._final_stats.data_ptr(), self._takeover.data_ptr(), self._reason.data_ptr(), self._exec_jerk.data_ptr(),
-                                     self._exec_action.data_ptr() if self._exec_action is not None else 0, self._takeover_ticks.data_ptr(), self._stream())
-        elif self.R:
-            self.ctx.env_step_reward_groups(self.params, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
-                                            self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(),
-                                            self._stream())
-        elif self.sim_cfgs is not None:
-            self.ctx.env_step_groups(self.params, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
-                                     self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(), self._stream())
-        else:
-            self.ctx.env_step(self.params, self.sim_cfg, self.cfg, self.n, a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(),
-                              self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(), self._final_stats.data_ptr(), self._stream())
+            shield_out = (self._takeover.data_ptr(), self._reason.data_ptr(), self._exec_jerk.data_ptr(),
+                          self._exec_action.data_ptr() if self._exec_action is not None else 0, self._takeover_ticks.data_ptr())
+        self._step(a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(), self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(),
+                   self._final_stats.data_ptr(), *shield_out, self._stream())
         self._last_action = a                                # (kept alive until the kernels have read it)
         info = {"final_observation": self._final_obs, "final_stats": self._final_stats, "episode_return": self._final_stats[:, _capi.ENV_NSTAT - 1],
                 "status": self._final_stats[:, _capi.SIM_NACC]}
