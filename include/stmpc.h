@@ -413,7 +413,8 @@ int stmpc_combined_read_state(stmpc_ctx *ctx, int N, int32_t *live, int32_t *his
  * It is not SUMO: episode statistics compare with the reference's reports as distributions only.
  *   stmpc_sim_init_device   traffic in its stationary state, ego at the ramp start with control.get_ego_start_speed's draw
  *   stmpc_sim_view_device   planner inputs of every environment (the layout stmpc_solve_batch_device takes; vehicles within the
- *                           sensor radius, front to back; other_a may be NULL)
+ *                           sensor radius, front to back; other_a may be NULL).  Kmax: 1 ... 64, the world's vehicle slots per environment --
+ *                           the solver's entries take rows of at most STMPC_KMAX_LIMIT; wider rows show the whole world (tests/test_sim_world.py)
  *   stmpc_sim_step_device   one tick with the commanded speeds (limited by the vehicle's acceleration limits); finished environments idle
  *   stmpc_sim_read          host copies: status [N] (0 running, 1 arrived = "merged", 2 crashed, 3 out of time), ticks [N], acc [N][STMPC_SIM_NACC] =
  *                           sum of speeds, max speed, sum |jerk|, (internal), samples, closest distance past CRASH_MIN_S, sum and count of those

@@ -2450,7 +2450,8 @@ int stmpc_sim_init_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *str
 
 int stmpc_sim_view_device(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, int Kmax, double *d_ego5, int32_t *d_k, double *d_ox, double *d_ov, double *d_oa, void *stream) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    if (N != c->sim.N || Kmax < 1 || Kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or Kmax out of range");
+    // (up to the world's vehicle slots: rows wider than STMPC_KMAX_LIMIT show the whole world to a test; the solver's entries take at most that limit)
+    if (N != c->sim.N || Kmax < 1 || Kmax > sim::KS) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or Kmax out of range");
     if (!d_ego5 || !d_k || !d_ox || !d_ov) return fail(STMPC_EINVAL, "NULL device pointer");
     sim::Cfg sc;
     TRY(make_simcfg(g, &sc));
