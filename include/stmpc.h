@@ -964,6 +964,45 @@ int stmpc_shield_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const st
                                  uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, uint8_t *d_takeover,
                                  int32_t *d_reason, double *d_executed_jerk, double *d_executed_action, int32_t *d_takeover_ticks, void *stream);
 
+/*
+ * Traffic mix: one ungrouped vector environment of N environments in which every episode draws its own traffic type -- domain randomisation at the
+ * episode boundary, the autoreset included.  The reference trains one policy per traffic type (configs/train_{low,medium,default,moderate,fast}_*.json
+ * differ in BASE_TRAFFIC_INTERVAL and OTHER_CAR_SPEED, control.py:215-226) and its cross_* configs measure such a policy on another type; a mixed env
+ * lets one learner meet all of them in every row.  (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)
+ * The rule: episode j of environment e runs under type t(e, j) = the first t with u < cum[t], where u is the world's generator (splitmix64, 53 bits)
+ * of (mix_seed, e) keyed by the episode index j in place of the draw counter, and cum is the running sum of weights / sum(weights), formed once on the
+ * host in fp64, left to right, and set to exactly 1.0 from the last type of positive weight on (a type of weight 0 is never drawn).  The draw takes
+ * nothing from the world's own draw counter: episode j starts from the start state of the lone world made from sim_cfgs[t(e, j)], environment e, seed
+ * stmpc_env_episode_seed(seed, j), with the counter offset the plain env gives episode j.  So every episode is, bit for bit, episode j of row e of the
+ * env reset through stmpc_env_reset_device with sim_cfgs[t(e, j)] when it receives the same actions, and a mix of T = 1 is that env.
+ *   May differ between types: base_traffic_interval, other_car_speed, vary_traffic_start_times.
+ *   Must be equal (else STMPC_EINVAL naming the field): every other field of stmpc_sim_cfg, the seed included (a mixed world has one seed) and the
+ *                   route (equal points, or NULL alike).
+ *   stmpc_traffic_mix_env_reset_device   stmpc_env_reset_device with a table of T = 1 ... STMPC_TRAFFIC_MIX_MAX sim cfgs and their weights (each finite
+ *                   and >= 0, positive sum): validates everything, uploads the table (synchronises on `stream` for it; the table and the
+ *                   per-environment types are sized here to their maximum and never reallocated under a running kernel), draws t(e, 0) and
+ *                   resets every environment under it.  d_traffic_type (int32 [N], may be NULL) receives t(e, 0).  A refused call changes nothing.
+ *                   stmpc_sim_init_device / stmpc_sim_init_groups_device and every other reset entry end the mix.
+ *   stmpc_traffic_mix_env_step_device    stmpc_env_step_device on such an env: the arguments of stmpc_env_step_groups_device (the context keeps the
+ *                   world's cfgs), then d_traffic_type int32 [N] (the type of the episode the row is in after this step) and d_final_traffic_type
+ *                   int32 [N] (where terminated | truncated: the type of the episode that just ended; elsewhere the current type).  The finishing
+ *                   episode's reward, final observation, statistics and log row are made under its own type, the next episode's start state and
+ *                   its observation under the type drawn for it.  Three launches, no copy, no synchronisation.  STMPC_EINVAL -- and nothing changes
+ *                   -- on an env that was not reset through stmpc_traffic_mix_env_reset_device or whose N differs; every other env step entry and
+ *                   stmpc_sim_step_device return STMPC_EINVAL on a mixed env, which they would step under one cfg.  A log row holds its environment
+ *                   and episode index, so its type is stmpc_traffic_mix_draw of them: the log has no column for it.
+ *   stmpc_traffic_mix_draw               the rule on the host: t(env, episode) for cum[0 .. T) as above (no context; -1 for cum NULL or T outside
+ *                   1 ... STMPC_TRAFFIC_MIX_MAX).
+ */
+#define STMPC_TRAFFIC_MIX_MAX 64
+int stmpc_traffic_mix_env_reset_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int T, const double *weights,
+                                       uint64_t mix_seed, const stmpc_env_cfg *env_cfg, int N, float *d_obs, int obs_stride, int32_t *d_traffic_type,
+                                       void *stream);
+int stmpc_traffic_mix_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_env_cfg *env_cfg, int N, const void *d_action, float *d_obs,
+                                      int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs,
+                                      double *d_final_stats, int32_t *d_traffic_type, int32_t *d_final_traffic_type, void *stream);
+int stmpc_traffic_mix_draw(uint64_t mix_seed, int env, uint32_t episode, const double *cum, int T);
+
 /* Device arithmetic probe used by the parity tests: out[i] = a[i] op b[i] evaluated on the GPU
  * with the kernels' compile flags. op: 0 div, 1 sqrt(a), 2 mul, 3 add, 4 fma(a,a,b*b), 5 the five-operation
  * quotient a/b of the FASTDIV kernels, 6 their two-operation quotient a/b.  HOST pointers. */

@@ -261,6 +261,7 @@ EXPORTS = (
     "stmpc_solver_groups_sim_init_device",
     "stmpc_reward_groups_env_reset_device", "stmpc_reward_groups_env_step_device", "stmpc_reward_groups_env_reward_device", "stmpc_reward_groups_split",
     "stmpc_shield_env_reset_device", "stmpc_shield_env_step_device",
+    "stmpc_traffic_mix_env_reset_device", "stmpc_traffic_mix_env_step_device", "stmpc_traffic_mix_draw",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
 KMAX_LIMIT = 32      # STMPC_KMAX_LIMIT
@@ -272,6 +273,7 @@ DDPG_POP_MAX = 64                     # STMPC_DDPG_POP_MAX
 SIM_GROUPS_MAX = 64                   # STMPC_SIM_GROUPS_MAX
 SOLVER_GROUPS_MAX = 512               # STMPC_SOLVER_GROUPS_MAX
 ENV_REWARD_GROUPS_MAX = 64            # STMPC_ENV_REWARD_GROUPS_MAX
+TRAFFIC_MIX_MAX = 64                  # STMPC_TRAFFIC_MIX_MAX
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
 REC_HDR, REC_NQ, REC_MAX_DEPTH, REC_MAX_EDGES = 10, 4, 64, 32      # STMPC_REC_HDR, STMPC_REC_NQ, STMPC_REC_MAX_DEPTH, STMPC_REC_MAX_EDGES
 REC_COLUMNS = ("tick", "x", "y", "v", "a", "s", "k", "cmd", "takeover", "jerk")      # the first STMPC_REC_HDR columns of a record
@@ -435,6 +437,9 @@ def load():
     shp = C.POINTER(ShieldEnvCfg)
     lib.stmpc_shield_env_reset_device.argtypes = [vp, pp, sp, ep, shp, C.c_int, vp, C.c_int, vp]
     lib.stmpc_shield_env_step_device.argtypes = [vp, pp, sp, ep, shp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.stmpc_traffic_mix_env_reset_device.argtypes = [vp, pp, sp, C.c_int, dp, C.c_uint64, ep, C.c_int, vp, C.c_int, vp, vp]
+    lib.stmpc_traffic_mix_env_step_device.argtypes = [vp, pp, ep, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.stmpc_traffic_mix_draw.argtypes = [C.c_uint64, C.c_int, C.c_uint32, dp, C.c_int]
     _lib = lib
     return lib
 
@@ -503,6 +508,12 @@ def ddpg_noise(seed, call, row):
 def env_episode_seed(seed, episode):
     """``stmpc_env_episode_seed``: the seed episode ``episode`` of an environment starts from (host only)."""
     return int(load().stmpc_env_episode_seed(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(episode))))
+
+
+def traffic_mix_draw(mix_seed, env, episode, cum):
+    """``stmpc_traffic_mix_draw``: the traffic type of episode ``episode`` of environment ``env`` under the cumulative weights ``cum`` (host only)."""
+    cum = np.ascontiguousarray(cum, dtype=np.float64)
+    return int(load().stmpc_traffic_mix_draw(C.c_uint64(int(mix_seed) & 0xFFFFFFFFFFFFFFFF), int(env), C.c_uint32(int(episode)), _dptr(cum), int(cum.size)))
 
 
 def backend_info():
@@ -1027,6 +1038,22 @@ class Context:
         self._chk(self._lib.stmpc_shield_env_step_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), C.byref(shield_cfg), int(N), d_action,
                                                          d_obs, int(obs_stride), d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, d_takeover,
                                                          d_reason, d_executed_jerk, d_executed_action or None, d_takeover_ticks, stream))
+
+    # -- traffic mix (stmpc_traffic_mix_*; see include/stmpc.h) ---------------------------------------------------
+    def traffic_mix_env_reset(self, params, sim_cfgs, weights, mix_seed, env_cfg, N, d_obs, obs_stride, d_traffic_type=0, stream=0):
+        """``stmpc_traffic_mix_env_reset_device``: ``sim_cfgs`` is a ``SimCfgTable`` (or a sequence of ``SimCfg``), one per traffic type, ``weights``
+        one number per type."""
+        t = sim_cfgs if isinstance(sim_cfgs, SimCfgTable) else SimCfgTable(sim_cfgs)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != len(t):
+            raise ValueError("%d weights for %d traffic types" % (w.size, len(t)))
+        self._chk(self._lib.stmpc_traffic_mix_env_reset_device(self._h, C.byref(params), t.array, len(t), _dptr(w), C.c_uint64(int(mix_seed) & 0xFFFFFFFFFFFFFFFF),
+                                                               C.byref(env_cfg), int(N), d_obs, int(obs_stride), d_traffic_type or None, stream))
+
+    def traffic_mix_env_step(self, params, env_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats,
+                             d_traffic_type, d_final_traffic_type, stream=0):
+        self._chk(self._lib.stmpc_traffic_mix_env_step_device(self._h, C.byref(params), C.byref(env_cfg), int(N), d_action, d_obs, int(obs_stride), d_reward,
+                                                              d_terminated, d_truncated, d_final_obs, d_final_stats, d_traffic_type, d_final_traffic_type, stream))
 
     def env_reward(self, env_cfg, N, Kmax, d_ego4, d_k, d_ox, d_jerk, d_crashed=0, d_arrived=0, d_reward=0, stream=0):
         self._chk(self._lib.stmpc_env_reward_device(self._h, C.byref(env_cfg), int(N), int(Kmax), d_ego4, d_k, d_ox, 0, 0, d_jerk, d_crashed, d_arrived,

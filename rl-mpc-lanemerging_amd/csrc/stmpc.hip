@@ -17,6 +17,7 @@
 #include "stmpc_solver_groups_kernels.hpp"
 #include "stmpc_env_groups_kernels.hpp"
 #include "stmpc_shield_env_kernels.hpp"
+#include "stmpc_traffic_mix_kernels.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -264,11 +265,17 @@ struct stmpc_ctx {
     } sim;
     // vector environment on the simulator (stmpc_env_*)
     struct Env {
-        DevBuf ep, prev_a, pjerk, inv, ret, cmd, live, vx, vv, va, k, log, log_n, actions, rtab;
+        DevBuf ep, prev_a, pjerk, inv, ret, cmd, live, vx, vv, va, k, log, log_n, actions, rtab, mix_rows, mix_cum, mix_type;
         int N = 0, n_actions = 0, log_cap = 0, mode = -1;    // (N = 0: no environment; a plain stmpc_sim_init_device invalidates it)
         int R = 0, n_per_rg = 0;      // reward groups (stmpc_reward_groups_env_reset_device): `rtab` holds R env::RewardRow; 0, 0 = one reward for all
         sim::Cfg rg_sc{};             // the ungrouped world of an env with reward groups (its step entry takes no sim cfg)
         env::RewardTab reward_tab() const { return env::RewardTab{rtab.as<env::RewardRow>(), n_per_rg}; }
+        // traffic mix (stmpc_traffic_mix_env_reset_device): `mix_rows` / `mix_cum` hold T env::TrafficRow / cumulative weights, `mix_type` the type of
+        // each environment's current episode; T = 0: no mix.  `mix_sc`: what the types share (the mix step takes no sim cfg)
+        int T = 0;
+        unsigned long long mix_seed = 0;
+        sim::Cfg mix_sc{};
+        env::TrafficMix traffic_mix() const { return env::TrafficMix{mix_rows.as<env::TrafficRow>(), mix_cum.as<double>(), mix_type.as<int>(), T, mix_seed}; }
         int ensure(int n_, int cap) {
             const size_t n = (size_t)n_, KS = sim::KS;
             TRY(ep.ensure(n * 4)); TRY(prev_a.ensure(n * 8)); TRY(pjerk.ensure(n * 8)); TRY(inv.ensure(n * 8)); TRY(ret.ensure(n * 8)); TRY(cmd.ensure(n * 8));
@@ -2390,7 +2397,7 @@ int sim_world_begin(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *stream) {
     TRY(c->sim.ensure(N));
     c->sim.N = N;
     ++c->sim.generation;
-    c->env.N = 0; c->env.R = 0; c->env.n_per_rg = 0;
+    c->env.N = 0; c->env.R = 0; c->env.n_per_rg = 0; c->env.T = 0;
     c->sim.G = 0; c->sim.n_per_group = 0;
     return sim_route_upload(c, g, stream);
 }
@@ -2429,6 +2436,7 @@ int check_grouped_world(stmpc_ctx *c, int N) {
 }
 int sim_init_groups(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream, int G_max);
 const char *const GROUPED_WORLD = "the world has traffic groups (stmpc_sim_init_groups_device): one cfg would step every group; use the grouped step entry";
+const char *const MIXED_ENV = "the env has a traffic mix (stmpc_traffic_mix_env_reset_device): one cfg would step every type; use stmpc_traffic_mix_env_step_device";
 const char *const REWARD_GROUPED_ENV = "the env has reward groups (stmpc_reward_groups_env_reset_device): one cfg would reward every group; use stmpc_reward_groups_env_step_device";
 }  // namespace
 
@@ -2466,6 +2474,7 @@ int stmpc_sim_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_c
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (N != c->sim.N || !d_cmd_speed) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or NULL device pointer");
     if (c->sim.G) return fail(STMPC_EINVAL, GROUPED_WORLD);
+    if (c->env.N >= 1 && c->env.T >= 1) return fail(STMPC_EINVAL, MIXED_ENV);
     sim::Cfg sc;
     DevP dp;
     TRY(make_simcfg(g, &sc));
@@ -2670,6 +2679,45 @@ int check_reward_groups(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg
     }
     return STMPC_OK;
 }
+struct MixReset {                            // what stmpc_traffic_mix_env_reset_device adds to a reset
+    std::vector<env::TrafficRow> rows;       // one per type
+    std::vector<double> cum;                 // the cumulative normalised weights
+    unsigned long long seed;
+    int32_t *d_type;                         // may be NULL
+};
+// The traffic mix: every cfg valid and equal in everything but the three traffic fields, the weights finite, not negative and of positive sum.  Changes
+// nothing; `out` receives the table rows and the cumulative weights (the rule of include/stmpc.h: left to right in fp64, 1.0 from the last positive weight on).
+int check_traffic_mix(const stmpc_sim_cfg *cfgs, int T, const double *weights, int N, MixReset *out) {
+    if (!cfgs) return fail(STMPC_EINVAL, "sim cfgs is NULL");
+    if (!weights) return fail(STMPC_EINVAL, "weights is NULL");
+    if (T < 1 || T > STMPC_TRAFFIC_MIX_MAX) return fail(STMPC_EINVAL, "T must be 1 ... STMPC_TRAFFIC_MIX_MAX (64) traffic types");
+    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
+    std::vector<sim::Cfg> table;
+    TRY(check_groups(cfgs, T, 1, &table));                   // (every cfg valid; the fields traffic groups must share, and the route)
+    const stmpc_sim_cfg &a = cfgs[0];
+    for (int t = 1; t < T; ++t) {
+        const stmpc_sim_cfg &b = cfgs[t];
+#define SAME(field) if (!(a.field == b.field)) return fail(STMPC_EINVAL, "traffic types must share " #field " (it differs in type " + std::to_string(t) + ")")
+        SAME(seed); SAME(start_speed); SAME(start_speed_std); SAME(min_start_speed); SAME(max_start_speed); SAME(speed_dev); SAME(randomize_start_speed); SAME(max_ticks);
+#undef SAME
+    }
+    double sum = 0.0;
+    int last = -1;
+    for (int t = 0; t < T; ++t) {
+        if (!(weights[t] >= 0.0) || !(weights[t] <= 1.7976931348623157e308)) return fail(STMPC_EINVAL, "weights must be finite and not negative (type " + std::to_string(t) + ")");
+        sum += weights[t];
+        if (weights[t] > 0.0) last = t;
+    }
+    if (!(sum > 0.0) || !(sum <= 1.7976931348623157e308)) return fail(STMPC_EINVAL, "weights must have a positive, finite sum");
+    out->rows.resize((size_t)T); out->cum.resize((size_t)T);
+    double run = 0.0;
+    for (int t = 0; t < T; ++t) {
+        run += weights[t] / sum;
+        out->cum[t] = t >= last ? 1.0 : run;
+        out->rows[t] = env::TrafficRow{table[t].base_interval, table[t].other_speed, table[t].vary_interval, 0};
+    }
+    return STMPC_OK;
+}
 // the shielded env's cfg (its reset and its step)
 int shield_cfg_check(const stmpc_params *p, const stmpc_shield_env_cfg *sh, int N) {
     if (!sh) return fail(STMPC_EINVAL, "shield cfg is NULL");
@@ -2683,12 +2731,13 @@ int shield_cfg_check(const stmpc_params *p, const stmpc_shield_env_cfg *sh, int 
 enum Need { REFUSED, EITHER, REQUIRED };
 struct EnvEntry {
     const char *reset_entry;                 // the reset entry that makes this entry's env (for messages)
-    Need traffic_groups, reward_groups, shield;
+    Need traffic_groups, reward_groups, shield, traffic_mix;
 };
-const EnvEntry PLAIN_ENV{"stmpc_env_reset_device", REFUSED, REFUSED, EITHER};       // (on a shield-reset context: the unshielded step)
-const EnvEntry TRAFFIC_GROUPS_ENV{"stmpc_env_reset_groups_device", REQUIRED, REFUSED, EITHER};
-const EnvEntry REWARD_GROUPS_ENV{"stmpc_reward_groups_env_reset_device", EITHER, REQUIRED, EITHER};
-const EnvEntry SHIELD_ENV{"stmpc_shield_env_reset_device", REFUSED, REFUSED, REQUIRED};
+const EnvEntry PLAIN_ENV{"stmpc_env_reset_device", REFUSED, REFUSED, EITHER, REFUSED};       // (on a shield-reset context: the unshielded step)
+const EnvEntry TRAFFIC_GROUPS_ENV{"stmpc_env_reset_groups_device", REQUIRED, REFUSED, EITHER, REFUSED};
+const EnvEntry REWARD_GROUPS_ENV{"stmpc_reward_groups_env_reset_device", EITHER, REQUIRED, EITHER, REFUSED};
+const EnvEntry SHIELD_ENV{"stmpc_shield_env_reset_device", REFUSED, REFUSED, REQUIRED, REFUSED};
+const EnvEntry TRAFFIC_MIX_ENV{"stmpc_traffic_mix_env_reset_device", REFUSED, REFUSED, REFUSED, REQUIRED};
 
 int env_shape_check(const stmpc_ctx *c, const EnvEntry &who) {
     const auto &v = c->shield;
@@ -2696,8 +2745,9 @@ int env_shape_check(const stmpc_ctx *c, const EnvEntry &who) {
         {c->sim.G > 0, who.traffic_groups, GROUPED_WORLD, UNGROUPED_WORLD},
         {c->env.N >= 1 && c->env.R >= 1, who.reward_groups, REWARD_GROUPED_ENV,
          "the env has no reward groups (stmpc_reward_groups_env_reset_device): use the plain or the traffic-groups step entry"},
-        {c->env.N >= 1 && v.N == c->env.N && v.generation == c->sim.generation, who.shield, "",
+        {c->env.N >= 1 && v.N == c->env.N && v.generation == c->sim.generation, who.shield, "the env was reset through stmpc_shield_env_reset_device: the traffic mix does not run behind the shield",
          "the environment in this context was not reset through stmpc_shield_env_reset_device"},
+        {c->env.N >= 1 && c->env.T >= 1, who.traffic_mix, MIXED_ENV, "the environment in this context was not reset through stmpc_traffic_mix_env_reset_device"},
     };
     for (const auto &sh : shapes) {
         if (sh.has && sh.need == REFUSED) return fail(STMPC_EINVAL, sh.refused);
@@ -2709,12 +2759,29 @@ int env_shape_check(const stmpc_ctx *c, const EnvEntry &who) {
 // Reset.  The world is the lone sim_cfgs[0] with N environments (G = 0) or G traffic groups; the reward is the lone env_cfgs[0] (R = 0) or R reward groups
 // (`rows`: their table, checked by the caller with `e`, the shared cfg).  The caller has made every check of the env's arguments; the world inits make
 // theirs before they change anything.
+// `mix`: NULL, or the traffic mix of an ungrouped world under one reward (checked by the caller; sim_cfgs[0] then carries what the types share).
 int env_reset(stmpc_ctx *c, const stmpc_sim_cfg *sim_cfgs, int G, int n_per_group, int N, const stmpc_env_cfg *env_cfgs, int R, int n_per_rg,
-              const std::vector<env::RewardRow> &rows, env::ECfg e, float *d_obs, int obs_stride, void *stream) {
+              const std::vector<env::RewardRow> &rows, env::ECfg e, float *d_obs, int obs_stride, void *stream, const MixReset *mix = nullptr) {
     if (G) { TRY(sim_init_groups(c, sim_cfgs, G, n_per_group, stream, STMPC_SIM_GROUPS_MAX)); }
+    else if (mix) { TRY(sim_world_begin(c, sim_cfgs, N, stream)); }          // (no k_sim_init: k_env_reset_mix starts each environment under its own type)
     else { TRY(stmpc_sim_init_device(c, sim_cfgs, N, stream)); }
     N = c->sim.N;
     TRY(env_reset_begin(c, env_cfgs, N, &e, stream));
+    if (mix) {
+        auto &v = c->env;
+        HIPCHK(hipMemcpyAsync(v.mix_rows.p, mix->rows.data(), mix->rows.size() * sizeof(env::TrafficRow), hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIPCHK(hipMemcpyAsync(v.mix_cum.p, mix->cum.data(), mix->cum.size() * 8, hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));       // (the caller's locals; the step entry reads the device copies)
+        sim::Cfg sc;
+        TRY(make_simcfg(sim_cfgs, &sc));
+        sim_route_of(c, &sc);
+        v.T = (int)mix->rows.size(); v.mix_seed = mix->seed; v.mix_sc = sc;
+        e.seed = sc.seed;
+        hipLaunchKernelGGL(env::k_env_reset_mix, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, sc, v.traffic_mix(), N, c->sim.state(), env_state(c), d_obs,
+                           obs_stride, mix->d_type);
+        HIPCHK(hipGetLastError());
+        return STMPC_OK;
+    }
     if (R) {
         HIPCHK(hipMemcpyAsync(c->env.rtab.p, rows.data(), rows.size() * sizeof(env::RewardRow), hipMemcpyHostToDevice, (hipStream_t)stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));       // (rows is the caller's local; the step entries read the device copy)
@@ -2746,6 +2813,9 @@ struct StepOut {                             // the tail every step entry takes
     double *final_stats;
     void *stream;
 };
+struct MixStep {                             // what the traffic-mix step takes on top
+    int32_t *traffic_type, *final_traffic_type;
+};
 struct ShieldStep {                          // what the shielded step takes on top
     const stmpc_shield_env_cfg *cfg;
     uint8_t *takeover;
@@ -2755,7 +2825,9 @@ struct ShieldStep {                          // what the shielded step takes on 
 };
 
 // the world step and the env's reward / observation / autoreset: `lone` is the cfg of an ungrouped world, NULL for the context's traffic groups
-void env_world_step(stmpc_ctx *c, const DevP &dp, double crash_min_s, const env::ECfg &e, const sim::Cfg *lone, bool reward_groups, const StepOut &o) {
+// (`mix`: the world is the context's traffic mix, `lone` what its types share)
+void env_world_step(stmpc_ctx *c, const DevP &dp, double crash_min_s, const env::ECfg &e, const sim::Cfg *lone, bool reward_groups, const StepOut &o,
+                    const MixStep *mix = nullptr) {
     const int N = c->sim.N, npg = c->sim.n_per_group;
     const dim3 grid = lone ? dim3((N + 63) / 64) : dim3((npg + 63) / 64, c->sim.G), block(64);
     hipStream_t st_ = (hipStream_t)o.stream;
@@ -2763,6 +2835,13 @@ void env_world_step(stmpc_ctx *c, const DevP &dp, double crash_min_s, const env:
     const env::EState es = env_state(c);
     const env::RewardTab tab = c->env.reward_tab();
     const sim::Cfg *groups = c->sim.groups.as<sim::Cfg>();
+    if (mix) {
+        const env::TrafficMix m = c->env.traffic_mix();
+        hipLaunchKernelGGL(env::k_sim_step_mix, grid, block, 0, st_, dp, *lone, m, N, s, (const double *)es.cmd, crash_min_s);
+        hipLaunchKernelGGL(env::k_env_post_mix, grid, block, 0, st_, e, *lone, m, N, s, es, o.obs, o.obs_stride, o.reward, o.terminated, o.truncated, o.final_obs,
+                           o.final_stats, mix->traffic_type, mix->final_traffic_type);
+        return;
+    }
     if (lone) hipLaunchKernelGGL(sim::k_sim_step, grid, block, 0, st_, dp, *lone, N, s, (const double *)es.cmd, crash_min_s);
     else hipLaunchKernelGGL(sim::k_sim_step_groups, grid, block, 0, st_, dp, groups, npg, s, (const double *)es.cmd, crash_min_s);
 #define POST(kernel, ...) hipLaunchKernelGGL(env::kernel, grid, block, 0, st_, e, __VA_ARGS__, s, es, o.obs, o.obs_stride, o.reward, o.terminated, o.truncated, o.final_obs, o.final_stats)
@@ -2775,7 +2854,7 @@ void env_world_step(stmpc_ctx *c, const DevP &dp, double crash_min_s, const env:
 
 // Step.  `g`: the cfg of a lone world (NULL: the entry takes none); `sh`: the shielded step's arguments, or NULL.
 int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const EnvEntry &who, const StepOut &o,
-             const ShieldStep *sh = nullptr) {
+             const ShieldStep *sh = nullptr, const MixStep *mix = nullptr) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     TRY(env_shape_check(c, who));
     if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, std::string("N does not match ") + who.reset_entry);
@@ -2786,6 +2865,7 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
     }
     if (!o.action || !o.obs || !o.reward || !o.terminated || !o.truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     if (sh && (!sh->takeover || !sh->reason || !sh->executed_jerk || !sh->takeover_ticks)) return fail(STMPC_EINVAL, "NULL device pointer (shield outputs)");
+    if (mix && (!mix->traffic_type || !mix->final_traffic_type)) return fail(STMPC_EINVAL, "NULL device pointer (traffic type outputs)");
     env::ECfg e;
     sim::Cfg sc;
     DevP dp;
@@ -2795,6 +2875,7 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
     // the world: one cfg -- the caller's, or the one an ungrouped reward-groups reset kept -- or the context's table of traffic groups
     const bool grouped = c->sim.G > 0, reward_groups = who.reward_groups == REQUIRED;
     if (!grouped && reward_groups) sc = c->env.rg_sc;
+    else if (mix) sc = c->env.mix_sc;
     else if (!grouped) { TRY(make_simcfg(g, &sc)); sim_route_of(c, &sc); }
     TRY(make_devp(p, &dp));
     e.seed = grouped ? 0 : sc.seed;
@@ -2821,7 +2902,7 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
     } else {
         hipLaunchKernelGGL(env::k_env_act, grid, block, 0, st_, e, N, s, es, o.action);
     }
-    env_world_step(c, dp, p->crash_min_s, e, grouped ? nullptr : &sc, reward_groups, o);
+    env_world_step(c, dp, p->crash_min_s, e, grouped ? nullptr : &sc, reward_groups, o, mix);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
@@ -2925,6 +3006,35 @@ int stmpc_shield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmp
                                  double *d_executed_action, int32_t *d_takeover_ticks, void *stream) {
     const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
     return env_step(c, p, g, ec, N, SHIELD_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, &shield);
+}
+
+// Domain randomisation over the reference's traffic types (configs/train_*_*.json, control.py:215-226) at the episode boundary.
+int stmpc_traffic_mix_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int T, const double *weights, uint64_t mix_seed,
+                                       const stmpc_env_cfg *ec, int N, float *d_obs, int obs_stride, int32_t *d_traffic_type, void *stream) {
+    env::ECfg e;
+    TRY(env_reset_check(c, p, ec, d_obs, obs_stride, &e));
+    MixReset mix;
+    TRY(check_traffic_mix(sim_cfgs, T, weights, N, &mix));
+    mix.seed = mix_seed; mix.d_type = d_traffic_type;
+    HIPCHK(hipSetDevice(c->device));
+    auto &v = c->env;                            // (their full size once: never reallocated under a running kernel while N does not grow)
+    TRY(v.mix_rows.ensure((size_t)STMPC_TRAFFIC_MIX_MAX * sizeof(env::TrafficRow)));
+    TRY(v.mix_cum.ensure((size_t)STMPC_TRAFFIC_MIX_MAX * 8));
+    TRY(v.mix_type.ensure((size_t)N * 4));
+    return env_reset(c, sim_cfgs, 0, 0, N, ec, 0, 0, {}, e, d_obs, obs_stride, stream, &mix);
+}
+
+int stmpc_traffic_mix_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
+                                      double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats,
+                                      int32_t *d_traffic_type, int32_t *d_final_traffic_type, void *stream) {
+    const MixStep mix{d_traffic_type, d_final_traffic_type};
+    return env_step(c, p, nullptr, ec, N, TRAFFIC_MIX_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream},
+                    nullptr, &mix);
+}
+
+int stmpc_traffic_mix_draw(uint64_t mix_seed, int env_index, uint32_t episode, const double *cum, int T) {
+    if (!cum || T < 1 || T > STMPC_TRAFFIC_MIX_MAX) return -1;
+    return env::mix_draw(mix_seed, env_index, episode, cum, T);
 }
 
 int stmpc_env_reward_device(stmpc_ctx *c, const stmpc_env_cfg *ec, int N, int Kmax, const double *d_ego4, const int32_t *d_k, const double *d_ox, const double *d_ov,

@@ -321,7 +321,7 @@ struct State {                     // device arrays
     double *acc;                   // [N][NACC]: sum speed, max speed, sum |jerk|, previous acceleration, samples, min gap (s > CRASH_MIN_S), sum gap, gap samples,
                                    //            disruption (deceleration of the nearest vehicle behind, s > disruption_min_s): sum, max, samples, non-zero samples
 };
-__device__ __forceinline__ double uniform01(unsigned long long seed, int env, unsigned &ctr) {
+__host__ __device__ __forceinline__ double uniform01(unsigned long long seed, int env, unsigned &ctr) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)env * 0x100000001ull + (unsigned long long)(ctr++) + 1ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;      // splitmix64
     return (double)(z >> 11) * (1.0 / 9007199254740992.0);

@@ -226,17 +226,20 @@ __device__ __forceinline__ EState estate_slice(const EState &es, size_t off) {
 // JerkEnv.step after control.step() (merge_gym.py:102-140), then the vector env's bookkeeping: k_env_post's body for the N environments the state
 // and step arrays point at.  `seed`: the run's seed of these environments (ECfg::seed; a traffic group's own); `row0`: the world's row of
 // environment 0 (the environment column of a log row holds row0 + e).
-__device__ __forceinline__ void env_post_body(const ECfg &c, const sim::Cfg &sc, unsigned long long seed, int row0, int N, const sim::State &s, const EState &es,
-                                              float *__restrict__ obs, int obs_stride, double *__restrict__ rew, unsigned char *__restrict__ term,
-                                              unsigned char *__restrict__ trunc, float *__restrict__ final_obs, double *__restrict__ final_stats) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
+//
+// The body in its two halves, split where the next episode begins (the traffic mix of stmpc_traffic_mix_kernels.hpp draws the next episode's cfg between
+// them; every other kernel runs both under its one cfg through env_post_body).  env_post_tick: environment e's tick under the cfg of the episode it is
+// in -- the view, the reward, the flags, the observation and, where the episode ended, its final observation, statistics row and log row.  Returns
+// "the episode ended and autoreset is on": the caller then starts the next episode with env_post_autoreset.
+__device__ __forceinline__ bool env_post_tick(const ECfg &c, const sim::Cfg &sc, int row0, int e, const sim::State &s, const EState &es, float *__restrict__ obs,
+                                              int obs_stride, double *__restrict__ rew, unsigned char *__restrict__ term, unsigned char *__restrict__ trunc,
+                                              float *__restrict__ final_obs, double *__restrict__ final_stats) {
     const int status = s.status[e];
     float *row = obs + (size_t)e * obs_stride;
     if (!es.live[e]) {                                                     // finished before this tick (autoreset off): idles
         if (status == 3) env_obs(c, sc, s, es, e, row); else for (int q = 0; q < c.obs_len; ++q) row[q] = 0.0f;
         rew[e] = 0.0; term[e] = 0; trunc[e] = 0;
-        return;
+        return false;
     }
     const bool crashed = status == 2, arrived = status == 1;
     const double ex = s.ego4[e * 4 + 0], ey = s.ego4[e * 4 + 1], ev = s.ego4[e * 4 + 2], ea = s.ego4[e * 4 + 3];
@@ -255,7 +258,7 @@ __device__ __forceinline__ void env_post_body(const ECfg &c, const sim::Cfg &sc,
     rew[e] = r;
     term[e] = crashed || arrived;
     trunc[e] = status == 3;
-    if (status == 0) { es.ret[e] = ret; return; }
+    if (status == 0) { es.ret[e] = ret; return false; }
     // the episode ended on this tick
     if (final_obs) { float *fo = final_obs + (size_t)e * obs_stride; for (int q = 0; q < c.obs_len; ++q) fo[q] = row[q]; }
     const double *acc = s.acc + (size_t)e * sim::NACC;
@@ -271,13 +274,27 @@ __device__ __forceinline__ void env_post_body(const ECfg &c, const sim::Cfg &sc,
         for (int q = 0; q < sim::NACC; ++q) lg[q] = acc[q];
         lg[sim::NACC] = (double)status; lg[sim::NACC + 1] = (double)s.ticks[e]; lg[sim::NACC + 2] = ret; lg[NSTAT] = (double)(row0 + e); lg[NSTAT + 1] = (double)ep;
     }
-    if (!c.autoreset) { es.ret[e] = ret; return; }
-    const unsigned j = (unsigned)ep + 1u;
+    if (!c.autoreset) { es.ret[e] = ret; return false; }
+    return true;
+}
+// The autoreset of environment e, whose episode es.episode[e] has just ended: episode j = es.episode[e] + 1 starts from sim_init_env under `sc` -- the
+// NEXT episode's cfg -- and episode_seed(seed, j), and its start state is observed into the environment's observation row.
+__device__ __forceinline__ void env_post_autoreset(const ECfg &c, const sim::Cfg &sc, unsigned long long seed, int e, const sim::State &s, const EState &es,
+                                                   float *__restrict__ row) {
+    const unsigned j = (unsigned)es.episode[e] + 1u;
     const unsigned long long ep_seed = episode_seed(seed, j);
     sim::sim_init_env(sc, s, e, ep_seed);
     s.rng[e] = episode_ctr(s.rng[e], j, ep_seed);
     es.episode[e] = (int)j; es.prev_a[e] = 0.0; es.ret[e] = 0.0;          // JerkEnv.reset (merge_gym.py:142-161)
     env_obs(c, sc, s, es, e, row);
+}
+__device__ __forceinline__ void env_post_body(const ECfg &c, const sim::Cfg &sc, unsigned long long seed, int row0, int N, const sim::State &s, const EState &es,
+                                              float *__restrict__ obs, int obs_stride, double *__restrict__ rew, unsigned char *__restrict__ term,
+                                              unsigned char *__restrict__ trunc, float *__restrict__ final_obs, double *__restrict__ final_stats) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    if (env_post_tick(c, sc, row0, e, s, es, obs, obs_stride, rew, term, trunc, final_obs, final_stats))
+        env_post_autoreset(c, sc, seed, e, s, es, obs + (size_t)e * obs_stride);
 }
 __global__ void __launch_bounds__(64) k_env_post(ECfg c, sim::Cfg sc, int N, sim::State s, EState es, float *__restrict__ obs, int obs_stride, double *__restrict__ rew,
                                                  unsigned char *__restrict__ term, unsigned char *__restrict__ trunc, float *__restrict__ final_obs,

@@ -101,6 +101,19 @@ def sim_cfgs(traffic, seed=0, max_episode_length=100.0, route="lane"):
     return _capi.SimCfgTable(cfgs)
 
 
+def traffic_mix_cfgs(traffic_mix, seed=0, max_episode_length=100.0, route="lane"):
+    """One ``SimCfg`` per traffic type of a traffic mix (a ``_capi.SimCfgTable`` for ``stmpc_traffic_mix_env_reset_device``): ``traffic_mix`` is a list
+    of what ``traffic_settings`` takes.  Every cfg comes from ``sim_cfg``'s code path under the one ``seed`` -- a mixed world is one world, so an entry
+    that sets its own ``seed`` is a ValueError, as is an empty list and one of more than ``TRAFFIC_MIX_MAX`` types.  Touches no device."""
+    types = [traffic_settings(t) for t in traffic_mix]
+    if not 1 <= len(types) <= _capi.TRAFFIC_MIX_MAX:
+        raise ValueError("traffic_mix must name 1 ... %d traffic types, not %d" % (_capi.TRAFFIC_MIX_MAX, len(types)))
+    for ti, t in enumerate(types):
+        if "seed" in t:
+            raise ValueError("a traffic mix has one seed (the env's): type %d must not set its own" % ti)
+    return _capi.SimCfgTable([sim_cfg(seed, max_episode_length, route, overrides=t) for t in types])
+
+
 def _check_traffic(n, traffic, policy, g_max=None):
     """(G, n_per_group) for ``n`` environments in the groups of ``traffic``; ValueError when they do not split or do not coincide with the
     members of a population ``policy``.  ``g_max``: the most groups the world takes (default ``SIM_GROUPS_MAX``; a solver-groups run:

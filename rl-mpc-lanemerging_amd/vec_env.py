@@ -37,6 +37,47 @@ def episode_seed(seed, episode):
     return z ^ (z >> 31)
 
 
+def traffic_mix_cum(weights):
+    """The cumulative weights of a traffic mix as ``stmpc_traffic_mix_env_reset_device`` forms them: the running sum of ``w / sum(w)`` in fp64, left to
+    right, and exactly 1.0 from the last type of positive weight on -- so ``cum[-1] == 1.0`` and a type of weight 0 is never drawn, wherever it stands.
+    A list of floats.  ValueError unless there are 1 ... ``TRAFFIC_MIX_MAX`` weights, each finite and >= 0, with a positive (finite) sum."""
+    try:
+        w = [float(x) for x in weights]
+    except (TypeError, ValueError):
+        raise ValueError("mix_weights must be a sequence of numbers, not %r" % (weights,))
+    if not 1 <= len(w) <= _capi.TRAFFIC_MIX_MAX:
+        raise ValueError("a traffic mix has 1 ... %d weights, not %d" % (_capi.TRAFFIC_MIX_MAX, len(w)))
+    total, last = 0.0, -1
+    for t, x in enumerate(w):
+        if not (x >= 0.0 and x != float("inf")):
+            raise ValueError("mix_weights must be finite and not negative, not %r (type %d)" % (x, t))
+        total += x                               # (an explicit loop: the built-in sum() of floats is compensated, the C entry's is not)
+        if x > 0.0:
+            last = t
+    if not (total > 0.0 and total != float("inf")):
+        raise ValueError("mix_weights must have a positive, finite sum")
+    cum, run = [], 0.0
+    for t, x in enumerate(w):
+        run += x / total
+        cum.append(1.0 if t >= last else run)
+    return cum
+
+
+def traffic_mix_draw(mix_seed, env, episode, cum):
+    """The traffic type of episode ``episode`` of environment ``env`` in a mix seeded ``mix_seed`` (``stmpc_traffic_mix_draw`` and the kernels, in
+    Python integers): the first t with ``u < cum[t]``, u = the world's ``uniform01(mix_seed, env, ctr=episode)`` -- splitmix64 of
+    ``mix_seed + gamma * (env * (2**32 + 1) + episode + 1)``, its top 53 bits over 2**53."""
+    z = (int(mix_seed) + 0x9E3779B97F4A7C15 * (int(env) * 0x100000001 + (int(episode) & 0xFFFFFFFF) + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    z ^= z >> 31
+    u = (z >> 11) * (1.0 / 9007199254740992.0)
+    t = 0
+    while t < len(cum) - 1 and not u < cum[t]:
+        t += 1
+    return t
+
+
 def env_cfg(env_id=None, reward=None, autoreset=True, S=Settings, log_capacity=0):
     """``stmpc_env_cfg`` for ``env_id`` / ``reward`` (default: Settings.GYM_ENVIRONMENT / Settings.REWARD_FUNCTION); ValueError for unknown names."""
     env_id = S.GYM_ENVIRONMENT if env_id is None else env_id
@@ -143,9 +184,19 @@ class MergeVecEnv:
     stride of the planner's view the shield sees (``EpisodeRunner``'s ``kmax``; 1 ... 32, the solver's limit).  ``shield_sparse=False`` solves the controller for every environment and
     keeps ``step`` free of host synchronisation; ``shield_sparse=True`` solves it for the taken-over ones only, and ``step`` then DOES synchronise: one
     integer, their number, crosses to the host every step.  Same outputs either way.  ``shield_counts()`` reads the shield's totals.  Out of scope,
-    refused with a ValueError: a shield together with ``traffic`` or ``rewards`` groups."""
+    refused with a ValueError: a shield together with ``traffic`` or ``rewards`` groups.
+
+    ``traffic_mix`` (with ``mix_weights``, ``mix_seed``; keyword-only): every episode draws its own traffic type -- the call then returns a
+    ``TrafficMixVecEnv``, see there."""
 
     SHIELDS = ("first_step",)
+
+    def __new__(cls, *args, **kwargs):
+        # ``MergeVecEnv(..., traffic_mix=[...], mix_weights=None, mix_seed=None)`` makes a ``TrafficMixVecEnv``, whose constructor takes these three
+        # keyword-only arguments after this class's own (which stay as they are)
+        if cls is MergeVecEnv and any(k in kwargs for k in ("traffic_mix", "mix_weights", "mix_seed")):
+            return object.__new__(TrafficMixVecEnv)
+        return object.__new__(cls)
 
     def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, traffic=None, rewards=None, shield=None,
                  shield_sparse=False, takeover_penalty=0.0, shield_kmax=32):
@@ -313,4 +364,94 @@ class MergeVecEnv:
         out["episode"] = rows[:, _capi.ENV_NSTAT + 1].astype(np.int64)
         out["traffic_group"] = out["env"] // self.n_per_group if self.sim_cfgs is not None else np.zeros(len(rows), dtype=np.int64)
         out["reward_group"] = out["env"] // self.n_per_reward_group if self.R else np.zeros(len(rows), dtype=np.int64)
+        return out
+
+
+class TrafficMixVecEnv(MergeVecEnv):
+    """``MergeVecEnv`` whose every episode draws its own traffic type: domain randomisation at the episode boundary, the autoreset included, on the
+    device (``stmpc_traffic_mix_env_reset_device`` / ``stmpc_traffic_mix_env_step_device``, the three launches of a lone env).  Made by
+    ``MergeVecEnv(..., traffic_mix=..., mix_weights=..., mix_seed=...)`` as well as by its own name; with ``traffic_mix=None`` it is the plain env.
+
+    ``traffic_mix``: a list as ``episodes.traffic_settings`` takes -- names of ``episodes.TRAFFIC_TYPES`` or dicts of BASE_TRAFFIC_INTERVAL,
+    OTHER_CAR_SPEED and optionally VARY_TRAFFIC_START_TIMES; 1 ... ``_capi.TRAFFIC_MIX_MAX`` types; a ``seed`` key is a ValueError (one world, one
+    seed).  ``mix_weights``: one number per type, each finite and >= 0 with a positive sum (default: uniform).  ``mix_seed``: default
+    ``episode_seed(seed, 2**31 - 1)``, so that the type draws are not the world's draws.
+
+    The world is one ungrouped world of ``n`` environments.  Episode j of environment e runs under type ``traffic_mix_draw(mix_seed, e, j, mix_cum)``
+    and is, bit for bit, episode j of row e of the lone ``MergeVecEnv(n, traffic=[that type], seed=seed)`` when it receives the same actions: the draw
+    takes nothing from the world's draw counter.  The finishing episode's reward, final observation, statistics and log row are its own type's; the
+    observation returned for the row is the next episode's start state under the type drawn for it.  ``step`` adds ``info["traffic_type"]`` (int32 [n]:
+    the type of the episode the row is in after the step) and ``info["final_traffic_type"]`` (where ``terminated | truncated``: the type of the
+    episode that ended; elsewhere the current type), device tensors, no host synchronisation.  ``traffic_type`` reads the current types,
+    ``drain_episode_stats`` adds a ``traffic_type`` column (``traffic_of_log``), ``summary_by_traffic`` condenses it per type.
+    ``learner.train_ddpg`` and ``learner.DDPGPopulation`` train on it as on any env.  Out of scope, refused with a ValueError before any device call:
+    a mix together with ``traffic`` groups, ``rewards`` groups or a ``shield``."""
+
+    def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, traffic=None, rewards=None, shield=None,
+                 shield_sparse=False, takeover_penalty=0.0, shield_kmax=32, *, traffic_mix=None, mix_weights=None, mix_seed=None):
+        self.traffic_mix = None
+        if traffic_mix is None:
+            if mix_weights is not None or mix_seed is not None:
+                raise ValueError("mix_weights and mix_seed belong to a traffic_mix: none was given")
+            super().__init__(n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic, rewards, shield, shield_sparse, takeover_penalty, shield_kmax)
+            return
+        if traffic is not None or rewards is not None or shield is not None:         # (before any device call)
+            raise ValueError("a traffic mix with traffic groups, reward groups or a shield is out of scope: the mixed step serves one ungrouped world "
+                             "under one reward, unshielded")
+        mix = list(traffic_mix)
+        mix_cfgs = episodes.traffic_mix_cfgs(mix, seed, float(Settings.MAX_EPISODE_LENGTH))
+        weights = [1.0] * len(mix) if mix_weights is None else list(mix_weights)
+        if len(weights) != len(mix):
+            raise ValueError("mix_weights has %d entries for %d traffic types" % (len(weights), len(mix)))
+        cum = traffic_mix_cum(weights)
+        super().__init__(n, env_id, seed, reward, autoreset, ctx, log_capacity)
+        self.traffic_mix, self.mix_cfgs, self.T = mix, mix_cfgs, len(mix)
+        self.mix_weights, self.mix_cum = [float(w) for w in weights], cum
+        self.mix_seed = episode_seed(seed, 2 ** 31 - 1) if mix_seed is None else int(mix_seed) & _M64
+        self._type = self.torch.zeros(self.n, dtype=self.torch.int32, device=self.device)
+        self._final_type = self.torch.zeros(self.n, dtype=self.torch.int32, device=self.device)
+        c = self.ctx
+        self._reset = lambda d_obs, obs_stride, stream: c.traffic_mix_env_reset(self.params, self.mix_cfgs, self.mix_weights, self.mix_seed, self.cfg, self.n,
+                                                                                d_obs, obs_stride, self._type.data_ptr(), stream)
+        self._step = lambda *a: c.traffic_mix_env_step(self.params, self.cfg, self.n, *a[:-1], self._type.data_ptr(), self._final_type.data_ptr(), a[-1])
+
+    @property
+    def traffic_type(self):
+        """The traffic type of the episode each environment is in, int32 [n] on the device (the tensor of ``info["traffic_type"]``)."""
+        self._need_mix()
+        return self._type
+
+    def _need_mix(self):
+        if self.traffic_mix is None:
+            raise RuntimeError("this env has no traffic mix")
+
+    def step(self, action):
+        out = super().step(action)
+        if self.traffic_mix is not None:
+            out[4].update(traffic_type=self._type, final_traffic_type=self._final_type)
+        return out
+
+    def traffic_of_log(self, rows):
+        """The traffic type of each drained episode (``rows``: what ``drain_episode_stats`` returns, or any dict with ``env`` and ``episode``
+        columns), int64 [len]: host arithmetic on the two columns through ``traffic_mix_draw`` -- the log has no column for it."""
+        self._need_mix()
+        return np.array([traffic_mix_draw(self.mix_seed, int(e), int(j), self.mix_cum) for e, j in zip(rows["env"], rows["episode"])], dtype=np.int64)
+
+    def summary_by_traffic(self, rows):
+        """One dict per traffic type for drained episodes ``rows``: ``episodes`` (their number), the ``merged``, ``crashed`` and ``timed_out`` shares,
+        ``mean_ticks`` and ``mean_return`` (NaN for a type without episodes)."""
+        types = self.traffic_of_log(rows)
+        out = []
+        for t in range(self.T):
+            m = types == t
+            k = int(m.sum())
+            mean = lambda col: float(np.mean(np.asarray(rows[col], dtype=np.float64)[m])) if k else float("nan")
+            out.append({"episodes": k, "merged": mean("merged"), "crashed": mean("crashed"), "timed_out": mean("timed_out"), "mean_ticks": mean("ticks"),
+                        "mean_return": mean("episode_return")})
+        return out
+
+    def drain_episode_stats(self):
+        out = super().drain_episode_stats()
+        if self.traffic_mix is not None:
+            out["traffic_type"] = self.traffic_of_log(out)
         return out

@@ -1,0 +1,339 @@
+"""The traffic mix on the GPU (csrc/stmpc_traffic_mix_kernels.hpp; the stmpc_traffic_mix_* entries of include/stmpc.h; the ``traffic_mix`` argument
+of vec_env.MergeVecEnv; learner.train_ddpg on such an env).
+
+The contract: episode j of environment e of a mixed env is, bit for bit, episode j of row e of the LONE env of the type
+``traffic_mix_draw(mix_seed, e, j)`` -- ``MergeVecEnv(n, traffic=[type], seed=seed)``, the path a user had before -- when it receives the same
+actions.  Every comparison is on the raw bits; there is no tolerance anywhere.
+
+The setup all tests share: N = 96 (one full wavefront and a partial one), traffic_mix = ["low", "default", "fast"] with uniform weights, world seed 7,
+episodes of at most 50 ticks, and an action that is a fixed hash of (environment, tick of its episode) mapped into the Box, so that equal episodes
+receive equal actions whatever else the env has been through.  The 50 ticks are 20 s at TICK_LENGTH 0.4: at the reference's 0.2 s no ego covers the
+265 m to its arrival position through the traffic within 50 ticks, so no episode could end "arrived", which the second test requires (the world's
+host twin gives 0 arrivals among 616 episodes of the mixed run at 0.2 s, and 17 among 939 at 0.4 s).  A third of the environments push (crashes), a
+third hold their speed (arrivals), a third brake (out of time).
+"""
+import numpy as np
+import pytest
+
+N, SEED, STEPS = 96, 7, 300
+MIX = ["low", "default", "fast"]
+TICK, EPISODE_S, MAX_TICKS = 0.4, 20.0, 50
+CONT, DISC = "sumo-jerk-continuous-v0", "sumo-jerk-v0"
+KEYS = ("obs", "reward", "terminated", "truncated", "final_observation", "final_stats", "ticks")
+_M64 = (1 << 64) - 1
+_cache = {}
+
+
+def _pkg():
+    import rl_mpc_lanemerging_amd as pkg
+    if pkg.build.needs_build():
+        pkg.build.build()
+    return pkg
+
+
+def _hash01(e, tick):
+    z = (0x9E3779B97F4A7C15 * (e * 1000003 + tick + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    z ^= z >> 31
+    return (z >> 11) / 9007199254740992.0
+
+
+def _action_table(env_id):
+    """[N][MAX_TICKS + 1]: the action of environment e at tick k of its episode.  Continuous: a jerk inside the Box [-5, 5]; discrete: an index
+    into JERK_VALUES_DQN (-5, -2.5, 0, 2.5, 5)."""
+    if env_id not in _cache:
+        centre, width = (4.0, 0.0, -3.0), (1.5, 0.6, 1.5)
+        jerk = np.array([[min(max(centre[e % 3] + (2.0 * _hash01(e, k) - 1.0) * width[e % 3], -5.0), 5.0) for k in range(MAX_TICKS + 1)] for e in range(N)])
+        _cache[env_id] = jerk if env_id == CONT else np.clip(np.rint(jerk / 2.5) + 2, 0, 4).astype(np.int32)
+    return _cache[env_id]
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+
+
+def _same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+
+
+def _settings():
+    pkg = _pkg()
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    pkg.apply_overrides({"MAX_EPISODE_LENGTH": EPISODE_S, "TICK_LENGTH": TICK})
+    return pkg
+
+
+def _make(ctx, env_id=CONT, autoreset=True, n=N, **kwargs):
+    _settings()
+    from rl_mpc_lanemerging_amd import vec_env
+    return vec_env.MergeVecEnv(n, env_id=env_id, seed=SEED, ctx=ctx, autoreset=autoreset, log_capacity=256 * n, **kwargs)
+
+
+def _step_hashed(env, table):
+    import torch
+    ticks = env.episode_ticks.cpu().numpy()
+    return env.step(torch.as_tensor(table[np.arange(env.n), np.minimum(ticks, MAX_TICKS)], device=env.device))
+
+
+def _run(ctx, key, steps, env_id=CONT, autoreset=True, **kwargs):
+    """reset + ``steps`` hashed steps: every tensor ``step`` returns stacked over the steps, the episode index of each row after each step, the
+    drained log.  Computed once per key, then only read."""
+    if key in _cache and _cache[key]["steps"] >= steps:
+        return _cache[key]
+    import torch
+    env = _make(ctx, env_id, autoreset, **kwargs)
+    mixed = kwargs.get("traffic_mix") is not None
+    table = _action_table(env_id)
+    out = {"obs0": env.reset().clone().cpu().numpy(), "steps": steps, "env": env}
+    if mixed:
+        out["type0"] = env.traffic_type.cpu().numpy().copy()
+    rec = {k: [] for k in KEYS + (("traffic_type", "final_traffic_type") if mixed else ())}
+    for _ in range(steps):
+        obs, rew, term, trunc, info = _step_hashed(env, table)
+        vals = [obs, rew, term, trunc, info["final_observation"], info["final_stats"], env.episode_ticks]
+        if mixed:
+            vals += [info["traffic_type"], info["final_traffic_type"]]
+        for k, v in zip(rec, vals):
+            rec[k].append(v.clone())
+    out.update({k: torch.stack(v).cpu().numpy() for k, v in rec.items()})
+    done = out["terminated"] | out["truncated"]
+    out["done"] = done
+    out["episode"] = np.cumsum(done, axis=0) if autoreset else np.zeros_like(done, dtype=np.int64)       # of each row after each step
+    out["log"] = env.drain_episode_stats()
+    env.check_error()
+    _cache[key] = out
+    return out
+
+
+def _episodes(run):
+    """{(e, j): the record of finished episode j of row e}: the observation it started from, every later observation of it, its final observation,
+    rewards, flags and statistics row."""
+    eps = {}
+    for e in range(N):
+        start, s0, j = run["obs0"][e], 0, 0
+        for s in np.flatnonzero(run["done"][:, e]):
+            eps[(e, j)] = {"start": start, "obs": run["obs"][s0:s, e], "final_observation": run["final_observation"][s, e], "reward": run["reward"][s0:s + 1, e],
+                           "terminated": run["terminated"][s0:s + 1, e], "truncated": run["truncated"][s0:s + 1, e], "final_stats": run["final_stats"][s, e],
+                           "ticks": run["ticks"][s0:s, e], "end_step": int(s)}
+            start, s0, j = run["obs"][s, e], s + 1, j + 1
+    return eps
+
+
+def _log_rows(log):
+    cols = [k for k in sorted(log) if k not in ("traffic_type", "traffic_group", "reward_group")]
+    return {(int(e), int(j)): np.array([log[k][i] for k in cols], dtype=np.float64).tobytes() for i, (e, j) in enumerate(zip(log["env"], log["episode"]))}
+
+
+def _mixed(gpu_ctx):
+    return _run(gpu_ctx, "mixed", STEPS, traffic_mix=MIX)
+
+
+def _twin_types(env, episode):
+    from rl_mpc_lanemerging_amd import vec_env
+    return np.array([vec_env.traffic_mix_draw(env.mix_seed, e, int(j), env.mix_cum) for e, j in enumerate(episode)], dtype=np.int32)
+
+
+# ---- 1: one type is the plain env -------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_id", [CONT, DISC])
+def test_gpu_a_mix_of_one_type_is_the_plain_env(gpu_ctx, restore_settings, env_id):
+    mixed = _run(gpu_ctx, ("one", env_id), STEPS, env_id, traffic_mix=["default"])
+    lone = _run(gpu_ctx, ("lone", "default", env_id), STEPS, env_id, traffic=["default"])
+    for k in KEYS + ("obs0",):
+        assert _same(mixed[k], lone[k][:STEPS] if k != "obs0" else lone[k]), (env_id, k)
+    assert mixed["done"].sum() > N and (mixed["episode"][-1] >= 2).all()                                  # (every row through autoresets)
+    assert (mixed["traffic_type"] == 0).all() and (mixed["final_traffic_type"] == 0).all() and (mixed["type0"] == 0).all()
+    lone_eps = _episodes(lone)                                  # (the lone run may be a longer one another test made: its first STEPS steps)
+    lone_log = {k: v for k, v in _log_rows(lone["log"]).items() if lone_eps[k]["end_step"] < STEPS}
+    assert _log_rows(mixed["log"]) == lone_log and len(lone_log) == mixed["done"].sum()
+
+
+# ---- 2: every episode is the lone env's episode ---------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_every_mixed_episode_is_the_lone_envs_episode(gpu_ctx, restore_settings):
+    from rl_mpc_lanemerging_amd import vec_env
+    mixed = _mixed(gpu_ctx)
+    env = mixed["env"]
+    mine, mlog = _episodes(mixed), _log_rows(mixed["log"])
+    assert len(mine) == mixed["done"].sum() == len(mlog) and set(mine) == set(mlog)
+    j_max = max(j for _, j in mine)
+    lone_steps = (j_max + 1) * (MAX_TICKS + 1)
+    lones = [_run(gpu_ctx, ("lone", t, CONT), lone_steps, traffic=[t]) for t in MIX]
+    theirs = [(_episodes(r), _log_rows(r["log"])) for r in lones]
+    per_type, status_seen, types_of_row = [0] * len(MIX), set(), [set() for _ in range(N)]
+    for (e, j), ep in sorted(mine.items()):
+        t = vec_env.traffic_mix_draw(env.mix_seed, e, j, env.mix_cum)
+        assert mixed["final_traffic_type"][ep["end_step"], e] == t
+        eps, log = theirs[t]
+        assert (e, j) in eps and (e, j) in log, ("episode %d of row %d did not finish in the lone env of %s" % (j, e, MIX[t]))
+        for k in ("start", "obs", "final_observation", "reward", "terminated", "truncated", "final_stats", "ticks"):
+            assert _same(ep[k], eps[(e, j)][k]), (e, j, MIX[t], k)
+        assert mlog[(e, j)] == log[(e, j)], (e, j, MIX[t], "log row")
+        per_type[t] += 1
+        types_of_row[e].add(t)
+        status_seen.add(int(ep["final_stats"][12]))
+    # conditions on the run, so that it cannot pass trivially
+    print("episodes per type", per_type, "rows with two or more types", sum(len(s) >= 2 for s in types_of_row), "statuses", sorted(status_seen), "j_max", j_max)
+    assert min(per_type) >= 20, per_type
+    assert sum(len(s) >= 2 for s in types_of_row) >= N // 2
+    assert {1, 2, 3} <= status_seen, status_seen
+    # the types differ where it matters: the lone envs of two types do not tell the same story
+    assert not _same(lones[0]["obs"][:STEPS], lones[2]["obs"][:STEPS]) and not _same(lones[0]["obs0"], lones[2]["obs0"])
+
+
+# ---- 3: the outputs tell the truth ----------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_the_type_outputs_are_the_twins_draws(gpu_ctx, restore_settings):
+    mixed = _mixed(gpu_ctx)
+    env = mixed["env"]
+    from rl_mpc_lanemerging_amd import vec_env
+    assert env.mix_seed == vec_env.episode_seed(SEED, 2 ** 31 - 1)
+    assert np.array_equal(mixed["type0"], _twin_types(env, np.zeros(N, dtype=np.int64)))
+    before = np.zeros(N, dtype=np.int64)
+    for s in range(STEPS):
+        after = mixed["episode"][s]
+        assert np.array_equal(mixed["traffic_type"][s], _twin_types(env, after)), s
+        assert np.array_equal(mixed["final_traffic_type"][s], _twin_types(env, before)), s      # (ending rows: the type the episode started with)
+        before = after
+    assert len(set(mixed["traffic_type"].ravel().tolist())) == len(MIX)
+    log = mixed["log"]
+    ends = {(e, j): ep["end_step"] for (e, j), ep in _episodes(mixed).items()}
+    recorded = np.array([mixed["final_traffic_type"][ends[(int(e), int(j))], int(e)] for e, j in zip(log["env"], log["episode"])])
+    assert np.array_equal(env.traffic_of_log(log), recorded) and np.array_equal(log["traffic_type"], recorded)
+    summary = env.summary_by_traffic(log)
+    assert len(summary) == len(MIX) and sum(row["episodes"] for row in summary) == len(log["env"]) == mixed["done"].sum()
+    for t, row in enumerate(summary):
+        m = recorded == t
+        assert row["episodes"] == m.sum() and row["merged"] == log["merged"][m].mean() and row["mean_return"] == log["episode_return"][m].mean()
+        assert abs(row["merged"] + row["crashed"] + row["timed_out"] - 1.0) < 1e-12 and row["mean_ticks"] == log["ticks"][m].mean()
+
+
+# ---- 4: without autoreset -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_without_autoreset_a_finished_row_keeps_its_type_and_state(gpu_ctx, restore_settings):
+    steps = MAX_TICKS + 10
+    mixed = _run(gpu_ctx, "mixed-once", steps, autoreset=False, traffic_mix=MIX)
+    env = mixed["env"]
+    t0 = _twin_types(env, np.zeros(N, dtype=np.int64))
+    assert np.array_equal(mixed["type0"], t0) and (mixed["traffic_type"] == t0).all() and (mixed["final_traffic_type"] == t0).all()
+    assert (mixed["done"].sum(axis=0) == 1).all() and len(mixed["log"]["env"]) == N and (mixed["log"]["episode"] == 0).all()
+    assert len(set(t0.tolist())) == len(MIX)
+    for t, name in enumerate(MIX):
+        lone = _run(gpu_ctx, ("lone-once", name), steps, autoreset=False, traffic=[name])
+        rows = t0 == t
+        for k in KEYS:
+            assert _same(mixed[k][:, rows], lone[k][:, rows]), (name, k)
+        assert _same(mixed["obs0"][rows], lone["obs0"][rows])
+    # after its end a row idles as the plain env's does: no reward, no flag, its tick counter and its type stay
+    last = mixed["done"].argmax(axis=0)
+    for e in range(N):
+        tail = slice(last[e] + 1, steps)
+        assert not mixed["reward"][tail, e].any() and not mixed["done"][tail, e].any() and (mixed["ticks"][tail, e] == mixed["ticks"][last[e], e]).all()
+
+
+# ---- 5: the shape table ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_the_mix_entries_serve_a_mix_context_only(gpu_ctx, restore_settings):
+    import torch
+    from rl_mpc_lanemerging_amd import _capi
+    pkg = _settings()
+    other = _capi.Context(-1)
+    env, twin = _make(gpu_ctx, traffic_mix=MIX), _make(other, traffic_mix=MIX)
+    table = _action_table(CONT)
+    env.reset(), twin.reset()
+    for _ in range(3):
+        a, b = _step_hashed(env, table), _step_hashed(twin, table)
+    ctx, n = gpu_ctx, N
+    z = lambda dtype, *shape: torch.zeros((n,) + shape, dtype=dtype, device="cuda")
+    scratch = (z(torch.float32, env.obs_dim), z(torch.float64), z(torch.bool), z(torch.bool), z(torch.float32, env.obs_dim), z(torch.float64, _capi.ENV_NSTAT))
+    action = torch.zeros(n, dtype=torch.float64, device="cuda")
+    out = (action.data_ptr(), scratch[0].data_ptr(), env.obs_dim) + tuple(t.data_ptr() for t in scratch[1:])
+    kmax = 8
+    shield_cfg = _capi.ShieldEnvCfg.from_settings(pkg.Settings, False, 0.0, kmax)
+    extra = [z(torch.bool), z(torch.int32), z(torch.float64), z(torch.float64), z(torch.int32)]
+    existing = {"plain": lambda: ctx.env_step(env.params, env.mix_cfgs[1], env.cfg, n, *out),
+                "traffic_groups": lambda: ctx.env_step_groups(env.params, env.cfg, n, *out),
+                "reward_groups": lambda: ctx.env_step_reward_groups(env.params, env.cfg, n, *out),
+                "shield": lambda: ctx.shield_env_step(env.params, env.mix_cfgs[1], env.cfg, shield_cfg, n, *out, *(t.data_ptr() for t in extra)),
+                "sim_step": lambda: ctx.sim_step(env.params, env.mix_cfgs[1], n, action.data_ptr())}
+    types_before = env.traffic_type.clone()
+    for name, call in existing.items():
+        before = ctx.sim_read(n)
+        with pytest.raises(_capi.StmpcError) as err:
+            call()
+        assert err.value.code == _capi.STMPC_EINVAL, name
+        for x, y in zip(before, ctx.sim_read(n)):
+            assert x.tobytes() == y.tobytes(), name
+    assert all(not t.any() for t in scratch) and torch.equal(env.traffic_type, types_before)
+    # N mismatch and NULL type outputs: refused, nothing moves
+    types = (env._type.data_ptr(), env._final_type.data_ptr())
+    before = ctx.sim_read(n)
+    for bad in (lambda: ctx.traffic_mix_env_step(env.params, env.cfg, n - 1, *out, *types), lambda: ctx.traffic_mix_env_step(env.params, env.cfg, n, *out, types[0], None)):
+        with pytest.raises(_capi.StmpcError) as err:
+            bad()
+        assert err.value.code == _capi.STMPC_EINVAL
+    for x, y in zip(before, ctx.sim_read(n)):
+        assert x.tobytes() == y.tobytes()
+    # the next mixed steps are those of the untouched twin
+    for _ in range(MAX_TICKS + 5):
+        a, b = _step_hashed(env, table), _step_hashed(twin, table)
+        for x, y in zip(a[:4] + tuple(a[4][k] for k in sorted(a[4])), b[:4] + tuple(b[4][k] for k in sorted(b[4]))):
+            assert _same(x.cpu().numpy(), y.cpu().numpy())
+    env.check_error(), twin.check_error()
+    assert _log_rows(env.drain_episode_stats()) == _log_rows(twin.drain_episode_stats())
+    # the mix step on a plain, grouped, reward-grouped and shield-reset context; a bad table at the reset
+    m = 8
+    rewards = [{"REWARD_FUNCTION": "Continuous"}, {"REWARD_FUNCTION": "ST"}]
+    mt = torch.zeros(m, dtype=torch.int32, device="cuda")
+    for kwargs in ({}, {"traffic": ["low", "fast"]}, {"rewards": rewards}, {"traffic": ["low", "fast"], "rewards": rewards}, {"shield": "first_step", "shield_kmax": kmax}):
+        plain = _make(other, n=m, **kwargs)
+        plain.reset()
+        before = other.sim_read(m)
+        with pytest.raises(_capi.StmpcError) as err:
+            other.traffic_mix_env_step(plain.params, plain.cfg, m, action.data_ptr(), plain._obs[1].data_ptr(), plain.obs_dim, plain._reward.data_ptr(),
+                                       plain._term.data_ptr(), plain._trunc.data_ptr(), plain._final_obs.data_ptr(), plain._final_stats.data_ptr(), mt.data_ptr(), mt.data_ptr())
+        assert err.value.code == _capi.STMPC_EINVAL, kwargs
+        for x, y in zip(before, other.sim_read(m)):
+            assert x.tobytes() == y.tobytes(), kwargs
+        plain.step(torch.zeros(m, dtype=torch.float64, device="cuda"))                     # (its own step still runs)
+        other.check_error()
+    from rl_mpc_lanemerging_amd import episodes
+    cfgs = episodes.traffic_mix_cfgs(MIX, SEED, EPISODE_S)
+    obs = torch.zeros(m, env.obs_dim, dtype=torch.float32, device="cuda")
+    reset = lambda table, w: other.traffic_mix_env_reset(plain.params, table, w, 1, plain.cfg, m, obs.data_ptr(), env.obs_dim)
+    cfgs.cfgs[2].seed = 8                                       # (a second seed: by hand, the Python layer refuses it earlier)
+    for table, w in ((_capi.SimCfgTable(cfgs.cfgs), (1, 1, 1)), (cfgs.cfgs[:2], (1, -1)), (cfgs.cfgs[:2], (0, 0)), (cfgs.cfgs[:2], (1, float("nan"))),
+                     (cfgs.cfgs[:1] * 65, [1.0] * 65)):
+        before = other.sim_read(m)
+        with pytest.raises(_capi.StmpcError) as err:
+            reset(table, w)
+        assert err.value.code == _capi.STMPC_EINVAL
+        for x, y in zip(before, other.sim_read(m)):
+            assert x.tobytes() == y.tobytes()
+    reset(cfgs.cfgs[:2], (0, 1))                                # (and a good one is taken: every row the second type)
+    assert not obs.eq(0).all()
+
+
+# ---- 6: it trains ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_train_ddpg_runs_on_a_mixed_env_and_repeats(gpu_ctx, restore_settings):
+    from rl_mpc_lanemerging_amd import learner
+
+    def once():
+        env = _make(gpu_ctx, traffic_mix=MIX)
+        env.reset()
+        cfg = learner.DDPGConfig(n_obs=env.obs_dim, capacity=16 * N, replay_start=192)
+        agent = learner.DDPGLearner(env, cfg, seed=3)
+        result = learner.train_ddpg(env, agent, frames=192 + 4 * N, drain_every=4)
+        return result, agent.state_dict(), env.traffic_type.cpu().numpy().copy()
+
+    (r1, s1, t1), (r2, s2, t2) = once(), once()
+    assert r1["frames"] >= 192 + 4 * N and s1["params"]["updates"] > 0
+    for slot in ("actor", "critic", "actor_target", "critic_target"):
+        for k, v in s1["params"][slot].items():
+            assert np.isfinite(v).all(), (slot, k)
+            assert _same(v, s2["params"][slot][k]), (slot, k)
+    assert np.array_equal(s1["counters"], s2["counters"]) and np.array_equal(t1, t2) and _same(np.asarray(r1["returns"]), np.asarray(r2["returns"]))
