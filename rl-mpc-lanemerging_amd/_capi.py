@@ -45,21 +45,37 @@ class Params(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-class ParamsTable:
-    """A contiguous ``stmpc_params[G]`` for the solver-group entries, from a sequence of ``Params`` (copied); indexing gives the copies."""
+class CfgTable:
+    """A contiguous ctypes array ``ELEM[G]`` for the group entries, from a sequence of ``ELEM``.  With ``COPY`` the rows are private copies and
+    indexing gives the copies; without it the caller's objects are kept alive (with the arrays they point to) and indexing gives them back."""
+    ELEM, COPY = None, False
 
-    def __init__(self, params):
-        self.params = [Params.from_buffer_copy(bytes(p)) for p in params]
-        self.array = (Params * max(len(self.params), 1))(*self.params)
+    def __init__(self, rows):
+        E = self.ELEM
+        self.rows = [E.from_buffer_copy(bytes(r)) for r in rows] if self.COPY else list(rows)
+        self.array = (E * max(len(self.rows), 1))()
+        for i, r in enumerate(self.rows):
+            C.memmove(C.byref(self.array, i * C.sizeof(E)), C.byref(r), C.sizeof(E))
+
+    @classmethod
+    def of(cls, x):
+        """``x`` itself if it is such a table already, else a table of the sequence ``x``."""
+        return x if isinstance(x, cls) else cls(x)
 
     def __len__(self):
-        return len(self.params)
+        return len(self.rows)
 
     def __getitem__(self, i):
-        return self.params[i]
+        return self.rows[i]
 
     def __iter__(self):
-        return iter(self.params)
+        return iter(self.rows)
+
+
+class ParamsTable(CfgTable):
+    """A contiguous ``stmpc_params[G]`` for the solver-group entries, from a sequence of ``Params`` (copied); indexing gives the copies."""
+    ELEM, COPY = Params, True
+    params = property(lambda self: self.rows)
 
 
 class Stats(C.Structure):
@@ -151,24 +167,11 @@ class SimCfg(C.Structure):
         return self
 
 
-class SimCfgTable:
+class SimCfgTable(CfgTable):
     """A contiguous ``stmpc_sim_cfg[G]`` for the traffic-group entries, from a sequence of ``SimCfg`` (kept alive with their routes); indexing gives
     the caller's ``SimCfg`` objects."""
-
-    def __init__(self, cfgs):
-        self.cfgs = list(cfgs)
-        self.array = (SimCfg * max(len(self.cfgs), 1))()
-        for i, c in enumerate(self.cfgs):
-            C.memmove(C.byref(self.array, i * C.sizeof(SimCfg)), C.byref(c), C.sizeof(SimCfg))
-
-    def __len__(self):
-        return len(self.cfgs)
-
-    def __getitem__(self, i):
-        return self.cfgs[i]
-
-    def __iter__(self):
-        return iter(self.cfgs)
+    ELEM = SimCfg
+    cfgs = property(lambda self: self.rows)
 
 
 class EnvCfg(C.Structure):
@@ -201,24 +204,11 @@ class EnvCfg(C.Structure):
         return c
 
 
-class EnvCfgTable:
+class EnvCfgTable(CfgTable):
     """A contiguous ``stmpc_env_cfg[R]`` for the reward-group entries, from a sequence of ``EnvCfg`` (kept alive with their action tables and
     feature cfgs); indexing gives the caller's ``EnvCfg`` objects."""
-
-    def __init__(self, cfgs):
-        self.cfgs = list(cfgs)
-        self.array = (EnvCfg * max(len(self.cfgs), 1))()
-        for i, c in enumerate(self.cfgs):
-            C.memmove(C.byref(self.array, i * C.sizeof(EnvCfg)), C.byref(c), C.sizeof(EnvCfg))
-
-    def __len__(self):
-        return len(self.cfgs)
-
-    def __getitem__(self, i):
-        return self.cfgs[i]
-
-    def __iter__(self):
-        return iter(self.cfgs)
+    ELEM = EnvCfg
+    cfgs = property(lambda self: self.rows)
 
 
 class DDPGCfg(C.Structure):
@@ -621,14 +611,10 @@ class Context:
                                                           d_fine or None, d_fine_len or None, stream or None))
 
     # -- solver groups (main.py:43-59): G parameter sets in the launches of one batch ------------------
-    @staticmethod
-    def _table(groups):
-        return groups if isinstance(groups, ParamsTable) else ParamsTable(groups)
-
     def solve_batch_groups(self, groups, n_per_group, ego, k_count, other_x, other_v):
         """``stmpc_solve_batch_groups``: state i is solved under ``groups[i // n_per_group]`` (a ``ParamsTable`` or a sequence of ``Params``).
         Returns a dict with ``path_idx``, ``best_t``, ``cost``, ``path_dist``, ``crash`` and ``action_cost[N, 2]``."""
-        t = self._table(groups)
+        t = ParamsTable.of(groups)
         ego, k_count, other_x, other_v, N, Kmax = _batch_states(ego, k_count, other_x, other_v)
         H = max(num_t(t.array[0]), 1) if len(t) else 1        # (an empty or unusable table is refused by the library, not here)
         path, best_t, cost = np.empty((N, H), dtype=np.int32), np.empty(N, dtype=np.int32), np.empty(N, dtype=np.float64)
@@ -639,24 +625,24 @@ class Context:
         return {"path_idx": path, "best_t": best_t, "cost": cost, "path_dist": pdist, "crash": crash, "action_cost": ac}
 
     def solve_batch_groups_device(self, groups, n_per_group, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, d_pd=0, d_crash=0, d_action_cost=0, stream=0):
-        t = self._table(groups)
+        t = ParamsTable.of(groups)
         self._chk(self._lib.stmpc_solve_batch_groups_device(self._h, t.array, len(t), int(n_per_group), int(N), int(Kmax), d_ego, d_k, d_ox, d_ov, d_path,
                                                             d_bt, d_cost, d_pd or None, d_crash or None, d_action_cost or None, stream or None))
 
     def st_control_groups_device(self, groups, n_per_group, tick_length, N, Kmax, d_ego, d_k, d_ox, d_ov, d_path, d_bt, d_cost, d_speed, d_fine=0,
                                  d_fine_len=0, stream=0):
-        t = self._table(groups)
+        t = ParamsTable.of(groups)
         self._chk(self._lib.stmpc_st_control_groups_device(self._h, t.array, len(t), int(n_per_group), float(tick_length), int(N), int(Kmax), d_ego, d_k,
                                                            d_ox, d_ov, d_path, d_bt, d_cost, d_speed, d_fine or None, d_fine_len or None, stream or None))
 
     def sim_init_solver_groups(self, cfgs, n_per_group, stream=0):
         """``stmpc_solver_groups_sim_init_device``: ``sim_init_groups`` for up to ``SOLVER_GROUPS_MAX`` cells, one traffic group per cell."""
-        t = cfgs if isinstance(cfgs, SimCfgTable) else SimCfgTable(cfgs)
+        t = SimCfgTable.of(cfgs)
         self._chk(self._lib.stmpc_solver_groups_sim_init_device(self._h, t.array, len(t), int(n_per_group), stream))
 
     def sim_step_solver_groups(self, groups, n_per_group, N, d_cmd_speed, stream=0):
         """``stmpc_solver_groups_sim_step_device``: the grouped world step with traffic group g's closest-distance gate at ``groups[g].crash_min_s``."""
-        t = self._table(groups)
+        t = ParamsTable.of(groups)
         self._chk(self._lib.stmpc_solver_groups_sim_step_device(self._h, t.array, len(t), int(n_per_group), int(N), d_cmd_speed, stream))
 
     def profile_begin(self):
@@ -872,7 +858,7 @@ class Context:
 
     def sim_init_groups(self, cfgs, n_per_group, stream=0):
         """``stmpc_sim_init_groups_device``: ``cfgs`` is a ``SimCfgTable`` (or a sequence of ``SimCfg``), one per traffic group."""
-        t = cfgs if isinstance(cfgs, SimCfgTable) else SimCfgTable(cfgs)
+        t = SimCfgTable.of(cfgs)
         self._chk(self._lib.stmpc_sim_init_groups_device(self._h, t.array, len(t), int(n_per_group), stream))
 
     def sim_step_groups(self, params, N, d_cmd_speed, stream=0):
@@ -1020,7 +1006,7 @@ class Context:
                                                   d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream))
 
     def env_reset_groups(self, params, cfgs, n_per_group, env_cfg, d_obs, obs_stride, stream=0):
-        t = cfgs if isinstance(cfgs, SimCfgTable) else SimCfgTable(cfgs)
+        t = SimCfgTable.of(cfgs)
         self._chk(self._lib.stmpc_env_reset_groups_device(self._h, C.byref(params), t.array, len(t), int(n_per_group), C.byref(env_cfg), d_obs, int(obs_stride), stream))
 
     def env_step_groups(self, params, env_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs=0, d_final_stats=0, stream=0):
@@ -1043,7 +1029,7 @@ class Context:
     def traffic_mix_env_reset(self, params, sim_cfgs, weights, mix_seed, env_cfg, N, d_obs, obs_stride, d_traffic_type=0, stream=0):
         """``stmpc_traffic_mix_env_reset_device``: ``sim_cfgs`` is a ``SimCfgTable`` (or a sequence of ``SimCfg``), one per traffic type, ``weights``
         one number per type."""
-        t = sim_cfgs if isinstance(sim_cfgs, SimCfgTable) else SimCfgTable(sim_cfgs)
+        t = SimCfgTable.of(sim_cfgs)
         w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
         if w.size != len(t):
             raise ValueError("%d weights for %d traffic types" % (w.size, len(t)))
@@ -1062,11 +1048,11 @@ class Context:
     def env_reset_reward_groups(self, params, sim_cfgs, n_per_traffic_group, env_cfgs, n_per_reward_group, d_obs, obs_stride, stream=0):
         """``stmpc_reward_groups_env_reset_device``: ``env_cfgs`` is an ``EnvCfgTable`` (or a sequence of ``EnvCfg``), one per reward group;
         ``sim_cfgs`` is one ``SimCfg`` (an ungrouped world, ``n_per_traffic_group`` unused) or a ``SimCfgTable`` / sequence (traffic groups)."""
-        e = env_cfgs if isinstance(env_cfgs, EnvCfgTable) else EnvCfgTable(env_cfgs)
+        e = EnvCfgTable.of(env_cfgs)
         if isinstance(sim_cfgs, SimCfg):
             sims, G = C.byref(sim_cfgs), 0
         else:
-            t = sim_cfgs if isinstance(sim_cfgs, SimCfgTable) else SimCfgTable(sim_cfgs)
+            t = SimCfgTable.of(sim_cfgs)
             sims, G = t.array, len(t)
         self._chk(self._lib.stmpc_reward_groups_env_reset_device(self._h, C.byref(params), sims, G, int(n_per_traffic_group), e.array, len(e),
                                                                  int(n_per_reward_group), d_obs, int(obs_stride), stream))

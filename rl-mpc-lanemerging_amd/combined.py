@@ -10,7 +10,7 @@ proposed action through the traffic predictor (``predict_step_with_ego`` with
 """
 import numpy as np
 
-from . import _capi
+from . import _capi, groups as _groups
 from . import control
 from . import st
 from .config import Settings
@@ -73,8 +73,7 @@ class ControlGroups:
     def __init__(self, cfgs, n_per_group):
         self.cfgs = list(cfgs)
         self.C, self.n_per_group = len(self.cfgs), int(n_per_group)
-        if self.C < 1 or self.C > CONTROL_GROUPS_MAX:
-            raise ValueError("control must name 1 ... %d groups, not %d" % (CONTROL_GROUPS_MAX, self.C))
+        _groups.within(self.C, CONTROL_GROUPS_MAX, "control")
         if self.n_per_group < 1:
             raise ValueError("n_per_group must be positive")
         self.n = self.C * self.n_per_group

@@ -104,6 +104,25 @@ int check_counts(int N, int Kmax, const int32_t *k) {
     return STMPC_OK;
 }
 
+// the count checks every group entry starts with; `range` is the whole first message (it names the limit), `letter` and `per` the two arguments
+int check_group_counts(int count, int n_per_group, int max, const char *range, const char *letter = "G", const char *per = "n_per_group") {
+    if (count < 1 || count > max) return fail(STMPC_EINVAL, range);
+    if (n_per_group < 1) return fail(STMPC_EINVAL, std::string(per) + " must be positive");
+    if ((int64_t)count * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, std::string(letter) + " * " + per + " out of range");
+    return STMPC_OK;
+}
+// "`what` must share `field` (it differs in `unit` i)`tail`": SHARED(field) compares that field of `a` (unit 0's struct) and `b` (unit i's), with a
+// `const Share share` in scope
+struct Share {
+    const char *what, *unit;
+    int i;
+    const char *tail;
+    std::string differs(const char *field) const { return std::string(what) + " must share " + field + " (it differs in " + unit + " " + std::to_string(i) + ")" + tail; }
+};
+#define SHARED(field) if (!(a.field == b.field)) return fail(STMPC_EINVAL, share.differs(#field))
+// two host arrays hold the same n bytes: one array, or equal contents
+bool same_bytes(const void *p, const void *q, size_t n) { return p == q || memcmp(p, q, n) == 0; }
+
 int next_pow2(int v) { int w = 1; while (w < v) w <<= 1; return w; }
 
 // divc<true> needs RN(1/d) to be usable by Markstein's theorem: excludes divisors whose significand is all ones
@@ -677,17 +696,13 @@ int make_devp(const stmpc_params *p, DevP *d) {
 // crash_min_s.  Changes nothing; touches no device.
 int check_solver_groups(const stmpc_params *groups, int G, int n_per_group, std::vector<GroupP> *out) {
     if (!groups) return fail(STMPC_EINVAL, "solver groups is NULL");
-    if (G < 1 || G > STMPC_SOLVER_GROUPS_MAX) return fail(STMPC_EINVAL, "G must be 1 ... STMPC_SOLVER_GROUPS_MAX (512) solver groups");
-    if (n_per_group < 1) return fail(STMPC_EINVAL, "n_per_group must be positive");
-    if ((int64_t)G * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, "G * n_per_group out of range");
+    TRY(check_group_counts(G, n_per_group, STMPC_SOLVER_GROUPS_MAX, "G must be 1 ... STMPC_SOLVER_GROUPS_MAX (512) solver groups"));
     const stmpc_params &a = groups[0];
     for (int g = 1; g < G; ++g) {
         const stmpc_params &b = groups[g];
-#define SAME(field) if (!(a.field == b.field)) return fail(STMPC_EINVAL, "solver groups must share " #field " (it differs in group " + std::to_string(g) + \
-                                                                         "): only d_w, v_w, a_w, j_w, min_allowed and crash_min_s may differ")
-        SAME(future_s); SAME(ds); SAME(dt); SAME(future_t); SAME(start_unc); SAME(unc_per_s); SAME(v_des); SAME(v_max); SAME(a_min); SAME(a_max);
-        SAME(j_min); SAME(j_max); SAME(car_length); SAME(max_pred_decel); SAME(follow_gap); SAME(react_thr); SAME(crash_thr); SAME(comb_min_dist);
-#undef SAME
+        const Share share{"solver groups", "group", g, ": only d_w, v_w, a_w, j_w, min_allowed and crash_min_s may differ"};
+        SHARED(future_s); SHARED(ds); SHARED(dt); SHARED(future_t); SHARED(start_unc); SHARED(unc_per_s); SHARED(v_des); SHARED(v_max); SHARED(a_min); SHARED(a_max);
+        SHARED(j_min); SHARED(j_max); SHARED(car_length); SHARED(max_pred_decel); SHARED(follow_gap); SHARED(react_thr); SHARED(crash_thr); SHARED(comb_min_dist);
     }
     if (out) {
         out->resize((size_t)G);
@@ -2047,15 +2062,13 @@ int stmpc_combined_decide_device(stmpc_ctx *c, const stmpc_params *p, const stmp
 int stmpc_combined_groups_set(stmpc_ctx *c, const stmpc_params *p, const stmpc_combined_cfg *cfgs, int C, int n_per_group) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (!p || !cfgs) return fail(STMPC_EINVAL, "params / combined cfgs is NULL");
-    if (C < 1 || C > STMPC_SIM_GROUPS_MAX) return fail(STMPC_EINVAL, "C must be 1 ... STMPC_SIM_GROUPS_MAX (64) controller groups");
-    if (n_per_group < 1) return fail(STMPC_EINVAL, "n_per_group must be positive");
-    if ((int64_t)C * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, "C * n_per_group out of range");
+    TRY(check_group_counts(C, n_per_group, STMPC_SIM_GROUPS_MAX, "C must be 1 ... STMPC_SIM_GROUPS_MAX (64) controller groups", "C"));
     std::vector<CCfg> table((size_t)C);
     for (int g = 0; g < C; ++g) TRY(make_ccfg(p, &cfgs[g], &table[g]));
     for (int g = 1; g < C; ++g) {
-#define SAME(field) if (!(cfgs[0].field == cfgs[g].field)) return fail(STMPC_EINVAL, "controller groups must share " #field " (it differs in group " + std::to_string(g) + ")")
-        SAME(tick_length); SAME(stop_x); SAME(sparse_control);
-#undef SAME
+        const stmpc_combined_cfg &a = cfgs[0], &b = cfgs[g];
+        const Share share{"controller groups", "group", g, ""};
+        SHARED(tick_length); SHARED(stop_x); SHARED(sparse_control);
     }
     // the rows of the groups that probe their rolled-out state: a static list, so a tick needs no round trip to gather them
     std::vector<int> test_rows;
@@ -2405,10 +2418,8 @@ int sim_world_begin(stmpc_ctx *c, const stmpc_sim_cfg *g, int N, void *stream) {
 // Changes nothing; `out` receives the G kernel cfgs without their route.
 int check_groups(const stmpc_sim_cfg *cfgs, int G, int n_per_group, std::vector<sim::Cfg> *out, int G_max = STMPC_SIM_GROUPS_MAX) {
     if (!cfgs) return fail(STMPC_EINVAL, "sim cfgs is NULL");
-    if (G < 1 || G > G_max)
-        return fail(STMPC_EINVAL, G_max == STMPC_SIM_GROUPS_MAX ? "G must be 1 ... STMPC_SIM_GROUPS_MAX (64) traffic groups" : "G must be 1 ... STMPC_SOLVER_GROUPS_MAX (512) cells");
-    if (n_per_group < 1) return fail(STMPC_EINVAL, "n_per_group must be positive");
-    if ((int64_t)G * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, "G * n_per_group out of range");
+    TRY(check_group_counts(G, n_per_group, G_max,
+                           G_max == STMPC_SIM_GROUPS_MAX ? "G must be 1 ... STMPC_SIM_GROUPS_MAX (64) traffic groups" : "G must be 1 ... STMPC_SOLVER_GROUPS_MAX (512) cells"));
     out->resize((size_t)G);
     for (int g = 0; g < G; ++g) TRY(make_simcfg(&cfgs[g], &(*out)[g]));
     const stmpc_sim_cfg &a = cfgs[0];
@@ -2416,13 +2427,12 @@ int check_groups(const stmpc_sim_cfg *cfgs, int G, int n_per_group, std::vector<
     const int route_a = a.ego_route_xy && a.ego_route_n >= 2 ? a.ego_route_n : 0;
     for (int g = 1; g < G; ++g) {
         const stmpc_sim_cfg &b = cfgs[g];
-#define SAME(field) if (!(a.field == b.field)) return fail(STMPC_EINVAL, "traffic groups must share " #field " (it differs in group " + std::to_string(g) + ")")
-        SAME(tick_length); SAME(spawn_x); SAME(despawn_x); SAME(ego_start_x); SAME(ego_start_y); SAME(arrive_x); SAME(sensor_radius);
-        SAME(veh_accel); SAME(veh_decel); SAME(veh_min_gap); SAME(veh_tau); SAME(veh_emergency_decel); SAME(veh_length); SAME(veh_width);
-        SAME(disruption_min_s); SAME(yield_overlap);
-#undef SAME
+        const Share share{"traffic groups", "group", g, ""};
+        SHARED(tick_length); SHARED(spawn_x); SHARED(despawn_x); SHARED(ego_start_x); SHARED(ego_start_y); SHARED(arrive_x); SHARED(sensor_radius);
+        SHARED(veh_accel); SHARED(veh_decel); SHARED(veh_min_gap); SHARED(veh_tau); SHARED(veh_emergency_decel); SHARED(veh_length); SHARED(veh_width);
+        SHARED(disruption_min_s); SHARED(yield_overlap);
         const int route_b = b.ego_route_xy && b.ego_route_n >= 2 ? b.ego_route_n : 0;
-        if (route_a != route_b || (route_a && a.ego_route_xy != b.ego_route_xy && memcmp(a.ego_route_xy, b.ego_route_xy, (size_t)route_a * 16) != 0))
+        if (route_a != route_b || (route_a && !same_bytes(a.ego_route_xy, b.ego_route_xy, (size_t)route_a * 16)))
             return fail(STMPC_EINVAL, "traffic groups must share ego_route_xy (it differs in group " + std::to_string(g) + ": equal points, or NULL alike)");
     }
     return STMPC_OK;
@@ -2653,9 +2663,7 @@ int check_reward_groups(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg
                         std::vector<env::RewardRow> *rows, env::ECfg *shared) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     if (!cfgs) return fail(STMPC_EINVAL, "env cfgs is NULL");
-    if (R < 1 || R > STMPC_ENV_REWARD_GROUPS_MAX) return fail(STMPC_EINVAL, "R must be 1 ... STMPC_ENV_REWARD_GROUPS_MAX (64) reward groups");
-    if (n_per_group < 1) return fail(STMPC_EINVAL, "n_per_reward_group must be positive");
-    if ((int64_t)R * n_per_group > INT32_MAX) return fail(STMPC_EINVAL, "R * n_per_reward_group out of range");
+    TRY(check_group_counts(R, n_per_group, STMPC_ENV_REWARD_GROUPS_MAX, "R must be 1 ... STMPC_ENV_REWARD_GROUPS_MAX (64) reward groups", "R", "n_per_reward_group"));
     rows->resize((size_t)R);
     for (int r = 0; r < R; ++r) {
         env::ECfg e;
@@ -2667,14 +2675,12 @@ int check_reward_groups(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg
     const stmpc_env_cfg &a = cfgs[0];
     for (int r = 1; r < R; ++r) {
         const stmpc_env_cfg &b = cfgs[r];
-#define SAME(field) if (!(a.field == b.field)) return fail(STMPC_EINVAL, "reward groups must share " #field " (it differs in group " + std::to_string(r) + ")")
-        SAME(action_mode); SAME(n_action_values); SAME(tick_length); SAME(minimum_negative_jerk); SAME(maximum_positive_jerk); SAME(max_negative_acceleration);
-        SAME(max_positive_acceleration); SAME(max_speed); SAME(car_length); SAME(autoreset); SAME(log_capacity);
-#undef SAME
-        if (a.action_mode != STMPC_ENV_CONTINUOUS_JERK && a.action_values != b.action_values &&
-            memcmp(a.action_values, b.action_values, (size_t)a.n_action_values * 8) != 0)
+        const Share share{"reward groups", "group", r, ""};
+        SHARED(action_mode); SHARED(n_action_values); SHARED(tick_length); SHARED(minimum_negative_jerk); SHARED(maximum_positive_jerk); SHARED(max_negative_acceleration);
+        SHARED(max_positive_acceleration); SHARED(max_speed); SHARED(car_length); SHARED(autoreset); SHARED(log_capacity);
+        if (a.action_mode != STMPC_ENV_CONTINUOUS_JERK && !same_bytes(a.action_values, b.action_values, (size_t)a.n_action_values * 8))
             return fail(STMPC_EINVAL, "reward groups must share action_values (they differ in group " + std::to_string(r) + ")");
-        if (a.features != b.features && memcmp(a.features, b.features, sizeof *a.features) != 0)
+        if (!same_bytes(a.features, b.features, sizeof *a.features))
             return fail(STMPC_EINVAL, "reward groups must share features (they differ in group " + std::to_string(r) + ")");
     }
     return STMPC_OK;
@@ -2697,9 +2703,8 @@ int check_traffic_mix(const stmpc_sim_cfg *cfgs, int T, const double *weights, i
     const stmpc_sim_cfg &a = cfgs[0];
     for (int t = 1; t < T; ++t) {
         const stmpc_sim_cfg &b = cfgs[t];
-#define SAME(field) if (!(a.field == b.field)) return fail(STMPC_EINVAL, "traffic types must share " #field " (it differs in type " + std::to_string(t) + ")")
-        SAME(seed); SAME(start_speed); SAME(start_speed_std); SAME(min_start_speed); SAME(max_start_speed); SAME(speed_dev); SAME(randomize_start_speed); SAME(max_ticks);
-#undef SAME
+        const Share share{"traffic types", "type", t, ""};
+        SHARED(seed); SHARED(start_speed); SHARED(start_speed_std); SHARED(min_start_speed); SHARED(max_start_speed); SHARED(speed_dev); SHARED(randomize_start_speed); SHARED(max_ticks);
     }
     double sum = 0.0;
     int last = -1;

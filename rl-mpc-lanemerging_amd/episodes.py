@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from . import _capi, scenario, synth
+from . import _capi, groups, scenario, synth
 from .config import Settings
 
 # scenario constants of the reference's SUMO network and episode runner
@@ -106,8 +106,7 @@ def traffic_mix_cfgs(traffic_mix, seed=0, max_episode_length=100.0, route="lane"
     of what ``traffic_settings`` takes.  Every cfg comes from ``sim_cfg``'s code path under the one ``seed`` -- a mixed world is one world, so an entry
     that sets its own ``seed`` is a ValueError, as is an empty list and one of more than ``TRAFFIC_MIX_MAX`` types.  Touches no device."""
     types = [traffic_settings(t) for t in traffic_mix]
-    if not 1 <= len(types) <= _capi.TRAFFIC_MIX_MAX:
-        raise ValueError("traffic_mix must name 1 ... %d traffic types, not %d" % (_capi.TRAFFIC_MIX_MAX, len(types)))
+    groups.within(len(types), _capi.TRAFFIC_MIX_MAX, "traffic_mix", "traffic types")
     for ti, t in enumerate(types):
         if "seed" in t:
             raise ValueError("a traffic mix has one seed (the env's): type %d must not set its own" % ti)
@@ -118,16 +117,8 @@ def _check_traffic(n, traffic, policy, g_max=None):
     """(G, n_per_group) for ``n`` environments in the groups of ``traffic``; ValueError when they do not split or do not coincide with the
     members of a population ``policy``.  ``g_max``: the most groups the world takes (default ``SIM_GROUPS_MAX``; a solver-groups run:
     ``SOLVER_GROUPS_MAX``).  Touches no device."""
-    G = len(traffic)
-    g_max = _capi.SIM_GROUPS_MAX if g_max is None else g_max
-    if G < 1 or G > g_max:
-        raise ValueError("traffic must name 1 ... %d groups, not %d" % (g_max, G))
-    if int(n) < G or int(n) % G:
-        raise ValueError("n = %d environments do not split into %d traffic groups of equal size" % (n, G))
-    npg = int(n) // G
-    if hasattr(policy, "P") and (policy.P != G or policy.n_per_member != npg):
-        raise ValueError("the population has %d members of %d environments, the traffic %d groups of %d: cell c pairs member c with traffic c, so they must coincide"
-                         % (policy.P, policy.n_per_member, G, npg))
+    G, npg = groups.split(n, len(traffic), _capi.SIM_GROUPS_MAX if g_max is None else g_max, "traffic")
+    groups.coincide("traffic", G, npg, policy=policy)
     return G, npg
 
 
@@ -135,17 +126,8 @@ def _check_control(n, control, traffic, policy):
     """(C, n_per_cell) for ``n`` environments in the controller groups of ``control``; ValueError when they do not split or do not coincide with
     the traffic groups or the members of a population ``policy`` (cell c pairs member c, traffic c and control c).  Touches no device."""
     from . import combined
-    C = len(control)
-    if C < 1 or C > combined.CONTROL_GROUPS_MAX:
-        raise ValueError("control must name 1 ... %d groups, not %d" % (combined.CONTROL_GROUPS_MAX, C))
-    if int(n) < C or int(n) % C:
-        raise ValueError("n = %d environments do not split into %d controller groups of equal size" % (n, C))
-    npc = int(n) // C
-    if traffic is not None and len(traffic) != C:
-        raise ValueError("the traffic has %d groups, the control %d: cell c pairs traffic c with control c, so they must coincide" % (len(traffic), C))
-    if hasattr(policy, "P") and (policy.P != C or policy.n_per_member != npc):
-        raise ValueError("the population has %d members of %d environments, the control %d groups of %d: cell c pairs member c with control c, so they must coincide"
-                         % (policy.P, policy.n_per_member, C, npc))
+    C, npc = groups.split(n, len(control), combined.CONTROL_GROUPS_MAX, "control", "controller")
+    groups.coincide("control", C, npc, traffic, policy)
     return C, npc
 
 
@@ -154,14 +136,9 @@ def _check_solver(n, solver, traffic, controller):
     or when they do not coincide with the traffic groups (cell c pairs traffic c with solver c).  Touches no device."""
     if controller != "st":
         raise ValueError("solver groups are settings of the ST controller, not of %r" % (controller,))
-    G = len(solver)
-    if G < 1 or G > _capi.SOLVER_GROUPS_MAX:
-        raise ValueError("solver must name 1 ... %d groups, not %d" % (_capi.SOLVER_GROUPS_MAX, G))
-    if int(n) < G or int(n) % G:
-        raise ValueError("n = %d environments do not split into %d solver groups of equal size" % (n, G))
-    if traffic is not None and len(traffic) != G:
-        raise ValueError("the traffic has %d groups, the solver %d: cell c pairs traffic c with solver c, so they must coincide" % (len(traffic), G))
-    return G, int(n) // G
+    G, npg = groups.split(n, len(solver), _capi.SOLVER_GROUPS_MAX, "solver")
+    groups.coincide("solver", G, npg, traffic)
+    return G, npg
 
 
 class EpisodeRunner:
@@ -388,41 +365,22 @@ def summary(stats):
 def summary_by_member(stats, P):
     """``summary`` of each member's environments: P dicts, member m from rows [m * n / P, (m + 1) * n / P) of every column (the result of a run
     whose policy was an ``actor.ActorPopulation`` of P members)."""
-    n = len(stats["status"])
-    if P < 1 or n % P:
-        raise ValueError("%d environments do not split into %d members" % (n, P))
-    npm = n // P
-    return [summary({k: v[m * npm:(m + 1) * npm] for k, v in stats.items() if k != "report"}) for m in range(P)]
+    return groups.summary_by(stats, P, "members")
 
 
 def summary_by_group(stats, G):
-    """``summary`` of each traffic group's environments: G dicts, group g from rows [g * n / G, (g + 1) * n / G) of every column (the result of a
-    run with ``traffic``)."""
-    n = len(stats["status"])
-    if G < 1 or n % G:
-        raise ValueError("%d environments do not split into %d traffic groups" % (n, G))
-    npg = n // G
-    return [summary({k: v[g * npg:(g + 1) * npg] for k, v in stats.items() if k != "report"}) for g in range(G)]
+    """``summary_by_member`` for the G traffic groups of a run with ``traffic``."""
+    return groups.summary_by(stats, G, "traffic groups")
 
 
 def summary_by_control(stats, C):
-    """``summary`` of each controller group's environments: C dicts, group c from rows [c * n / C, (c + 1) * n / C) of every column (the result of a
-    run with ``control``)."""
-    n = len(stats["status"])
-    if C < 1 or n % C:
-        raise ValueError("%d environments do not split into %d controller groups" % (n, C))
-    npc = n // C
-    return [summary({k: v[c * npc:(c + 1) * npc] for k, v in stats.items() if k != "report"}) for c in range(C)]
+    """``summary_by_member`` for the C controller groups of a run with ``control``."""
+    return groups.summary_by(stats, C, "controller groups")
 
 
 def summary_by_solver(stats, G):
-    """``summary`` of each solver group's environments: G dicts, group g from rows [g * n / G, (g + 1) * n / G) of every column (the result of a
-    run with ``solver``)."""
-    n = len(stats["status"])
-    if G < 1 or n % G:
-        raise ValueError("%d environments do not split into %d solver groups" % (n, G))
-    npg = n // G
-    return [summary({k: v[g * npg:(g + 1) * npg] for k, v in stats.items() if k != "report"}) for g in range(G)]
+    """``summary_by_member`` for the G solver groups of a run with ``solver``."""
+    return groups.summary_by(stats, G, "solver groups")
 
 
 def grid_search_st(n_per_cell, seed=0, traffic=None, cells=None, common_random_numbers=True, ctx=None, kmax=16, max_episode_length=100.0, max_ticks=None,
@@ -459,9 +417,7 @@ def grid_search_combined(model, traffic, n_per_cell, cells=None, seed=0, common_
     Returns ``{"cells": [{"settings": cell, "summary": ``summary`` dict}, ...], "stats": the raw result}``."""
     from . import actor, combined
     cells = [dict(c) for c in (cells if cells is not None else combined.grid_search_cells())]
-    C = len(cells)
-    if C < 1 or C > combined.CONTROL_GROUPS_MAX:
-        raise ValueError("control must name 1 ... %d groups, not %d" % (combined.CONTROL_GROUPS_MAX, C))
+    C = groups.within(len(cells), combined.CONTROL_GROUPS_MAX, "control")
     if int(n_per_cell) < 1:
         raise ValueError("n_per_cell must be positive")
     combined.control_cfgs(cells)                                        # (validates the keys before anything is built)

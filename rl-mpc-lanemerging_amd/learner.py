@@ -26,6 +26,7 @@ import math
 import numpy as np
 
 from . import _capi, actor as _actor
+from .groups import splitmix64
 from .config import Settings
 
 TENSORS = ("w0", "b0", "w1", "b1", "w2", "b2")
@@ -59,15 +60,9 @@ class DDPGConfig:
 
 
 # ---- the generator (host twins of dg_hash / stmpc_ddpg_sample_index / stmpc_ddpg_noise) ------------------------------------------------------
-def _mix(z):
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
-
-
 def hash3(seed, a, b):
     """splitmix64 of (seed, a, b): two rounds of the generator ``vec_env.episode_seed`` uses."""
-    return _mix((_mix((int(seed) + _G * (int(a) + 1)) & _M64) + _G * (int(b) + 1)) & _M64)
+    return splitmix64((splitmix64((int(seed) + _G * (int(a) + 1)) & _M64) + _G * (int(b) + 1)) & _M64)
 
 
 def sample_indices_host(seed, update, batch, fill):

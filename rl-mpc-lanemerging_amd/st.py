@@ -20,7 +20,7 @@ CPU implementation.
 """
 import numpy as np
 
-from . import _capi
+from . import _capi, groups
 from . import control
 from .config import Settings
 from .prediction import HighwayState, pack_states  # noqa: F401  (re-export)
@@ -37,8 +37,7 @@ def param_cfgs(cells, S=Settings):
     ``V_WEIGHT``, ``A_WEIGHT``, ``J_WEIGHT``, ``D_WEIGHT``, ``MIN_ALLOWED_DISTANCE`` and ``CRASH_MIN_S`` over ``S`` (the global ``Settings``, which is
     read and never written).  ValueError for any other key, for an empty list and for more than ``SOLVER_GROUPS_MAX`` cells."""
     cells = list(cells)
-    if not 1 <= len(cells) <= SOLVER_GROUPS_MAX:
-        raise ValueError("solver must name 1 ... %d groups, not %d" % (SOLVER_GROUPS_MAX, len(cells)))
+    groups.within(len(cells), SOLVER_GROUPS_MAX, "solver")
     table = []
     for cell in cells:
         if not isinstance(cell, dict):

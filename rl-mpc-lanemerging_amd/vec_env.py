@@ -18,7 +18,7 @@ import weakref
 
 import numpy as np
 
-from . import _capi, episodes
+from . import _capi, episodes, groups
 from .config import Settings
 
 ENV_IDS = {"sumo-jerk-continuous-v0": _capi.ENV_CONTINUOUS_JERK, "sumo-jerk-v0": _capi.ENV_JERK, "sumo-accel-v0": _capi.ENV_ACCELERATION}
@@ -31,10 +31,7 @@ def episode_seed(seed, episode):
     """Seed of episode ``episode`` of an environment in a run seeded ``seed`` (``stmpc_env_episode_seed``; 0: the seed itself)."""
     if episode == 0:
         return int(seed) & _M64
-    z = (int(seed) + 0x9E3779B97F4A7C15 * int(episode)) & _M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
+    return groups.splitmix64((int(seed) + 0x9E3779B97F4A7C15 * int(episode)) & _M64)
 
 
 def traffic_mix_cum(weights):
@@ -67,10 +64,7 @@ def traffic_mix_draw(mix_seed, env, episode, cum):
     """The traffic type of episode ``episode`` of environment ``env`` in a mix seeded ``mix_seed`` (``stmpc_traffic_mix_draw`` and the kernels, in
     Python integers): the first t with ``u < cum[t]``, u = the world's ``uniform01(mix_seed, env, ctr=episode)`` -- splitmix64 of
     ``mix_seed + gamma * (env * (2**32 + 1) + episode + 1)``, its top 53 bits over 2**53."""
-    z = (int(mix_seed) + 0x9E3779B97F4A7C15 * (int(env) * 0x100000001 + (int(episode) & 0xFFFFFFFF) + 1)) & _M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    z ^= z >> 31
+    z = groups.splitmix64((int(mix_seed) + 0x9E3779B97F4A7C15 * (int(env) * 0x100000001 + (int(episode) & 0xFFFFFFFF) + 1)) & _M64)
     u = (z >> 11) * (1.0 / 9007199254740992.0)
     t = 0
     while t < len(cum) - 1 and not u < cum[t]:
@@ -108,8 +102,7 @@ def reward_cfgs(rewards, env_id=None, autoreset=True, S=Settings, log_capacity=0
     table, the tick, the limits, autoreset, the log, the observation -- is ``S``'s for every group.  ValueError for any other key, an unknown
     reward function, an empty list and more than ``ENV_REWARD_GROUPS_MAX`` groups."""
     rewards = list(rewards)
-    if not 1 <= len(rewards) <= _capi.ENV_REWARD_GROUPS_MAX:
-        raise ValueError("rewards must name 1 ... %d groups, not %d" % (_capi.ENV_REWARD_GROUPS_MAX, len(rewards)))
+    groups.within(len(rewards), _capi.ENV_REWARD_GROUPS_MAX, "rewards")
     table = []
     for group in rewards:
         if not isinstance(group, dict):

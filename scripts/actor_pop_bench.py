@@ -18,26 +18,11 @@ import sys
 import tempfile
 import time
 
+from _timing import timed
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-WINDOW = 20
 KMAX = 16
-
-
-def timed(fn, steps, warmup, torch):
-    for _ in range(warmup):
-        fn()
-    total, done = 0.0, 0
-    while done < steps:
-        w = min(WINDOW, steps - done)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(w):
-            fn()
-        torch.cuda.synchronize()
-        total += time.perf_counter() - t0
-        done += w
-    return total / steps
 
 
 def tables(result):

@@ -6,38 +6,14 @@ import argparse
 import json
 import os
 import sys
-import time
+
+from _timing import WINDOW, timed
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 TRAIN_MODERATE_1 = {"REWARD_FUNCTION": "Slotted Jerk", "ALT_J_WEIGHT": 0.1, "OTHER_CAR_SPEED": 11.0, "BASE_TRAFFIC_INTERVAL": 1.2, "CRASH_MIN_S": 20,
                     "CRASH_REWARD": -10, "SUCCESS_REWARD": 10, "TIME_REWARD": -0.1}
-
-
-WINDOW = 20
-
-
-def timed(fn, steps, warmup, torch, before_window=None, after_window=None):
-    """Seconds per call of fn, timed in windows of WINDOW calls with a synchronisation at both ends of each (the same for every leg);
-    before_window / after_window run outside the timed region."""
-    for _ in range(warmup):
-        fn()
-    total, done = 0.0, 0
-    while done < steps:
-        w = min(WINDOW, steps - done)
-        if before_window:
-            before_window()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(w):
-            fn()
-        torch.cuda.synchronize()
-        total += time.perf_counter() - t0
-        if after_window:
-            after_window()
-        done += w
-    return total / steps
 
 
 def main():

@@ -16,31 +16,12 @@ import argparse
 import json
 import os
 import sys
-import time
+
+from _timing import WINDOW, timed
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-WINDOW = 20
 KMAX = 32
-
-
-def timed(fn, steps, warmup, torch, between=None):
-    """Seconds per call of ``fn``; ``between``: untimed work before every window (keeps a world that ``fn`` only reads moving)."""
-    for _ in range(warmup):
-        fn()
-    total, done = 0.0, 0
-    while done < steps:
-        w = min(WINDOW, steps - done)
-        if between is not None:
-            between()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(w):
-            fn()
-        torch.cuda.synchronize()
-        total += time.perf_counter() - t0
-        done += w
-    return total / steps
 
 
 def crash_shares(vec_env, np, torch, n=1024, ticks=400, seed=7, act_seed=11):
@@ -118,7 +99,7 @@ def main():
         rounds["a_dense"].append(timed(lambda: dense.step(act()), args.steps, args.warmup, torch))
         rounds["b_sparse"].append(timed(lambda: sparse.step(act()), args.steps, args.warmup, torch))
         rounds["c_plain"].append(timed(both_step, args.steps, args.warmup, torch) / 2)          # (two equal env steps per call)
-        rounds["d_pieces"].append(timed(pieces, args.steps, args.warmup, torch, between=advance))
+        rounds["d_pieces"].append(timed(pieces, args.steps, args.warmup, torch, before_window=advance))
         rounds["c_plus_d"].append(timed(step_and_pieces, args.steps, args.warmup, torch))       # (holds a second env step: subtract c_plain)
     for e in (dense, sparse, plain, twin):
         e.check_error()

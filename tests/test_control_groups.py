@@ -19,6 +19,7 @@ import pytest
 
 from conftest import load_golden
 from test_combined import _apply_settings
+from stmpc_testlib import bits as _bits, same as _same
 
 NPG, KMAX = 24, 16
 IDX = [90, 128, 131, 165, 241, 101, 108, 144, 187, 202, 123, 167, 291, 297, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9]
@@ -50,18 +51,6 @@ def _lone_ctx(i):
     if i not in _ctxs:
         _ctxs[i] = _capi.Context(-1)
     return _ctxs[i]
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype.kind == "f":
-        return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-    return a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _run(ctx, control, grouped, sparse=False, ticks=1):

@@ -7,24 +7,16 @@ Parity is with the reference's own ``st.do_conditional_st_based_on_first_step`` 
 anywhere.  The fixture batch is run ONCE (dense and sparse) and shared; the subsets (N = 1, 64, 65) are compared with its rows -- states are
 independent, so a row's outputs do not depend on the batch it is solved in.
 """
-import contextlib
-
 import numpy as np
 import pytest
 
 from conftest import load_golden
+from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same, settings_of as _settings_of
 
 KMAX = 16
 TICKS = 30
 GROUP_TICKS = 100       # the population / traffic test runs until egos are in the merge zone, where the shield takes over (30 ticks end on the ramp)
 _cache = {}
-
-
-def _pkg():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    return pkg
 
 
 def _settings():
@@ -33,18 +25,6 @@ def _settings():
     pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
     pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
     return pkg.Settings
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype.kind == "f":
-        return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-    return a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _pad(a):
@@ -259,17 +239,6 @@ def test_gpu_combined_runner_is_unchanged(gpu_ctx, restore_settings):
     assert set(got) == set(want)
     for key, val in want.items():
         assert _same(got[key], val), key
-
-
-@contextlib.contextmanager
-def _settings_of(group):
-    pkg = _pkg()
-    snap = pkg.Settings.snapshot()
-    pkg.apply_overrides({k: v for k, v in group.items() if k != "seed"})
-    try:
-        yield
-    finally:
-        pkg.Settings.restore(snap)
 
 
 @pytest.mark.gpu

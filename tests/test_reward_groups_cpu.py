@@ -9,6 +9,7 @@ import re
 import pytest
 
 from conftest import REPO
+from stmpc_testlib import pkg as _pkg
 
 MAY_DIFFER = ("reward_function", "crash_reward", "success_reward", "time_reward", "wt_smooth", "wt_safe", "wt_efficient", "alt_v_weight", "alt_a_weight",
               "alt_j_weight", "alt_d_weight", "min_follow_distance", "desired_speed", "invalid_action_penalty")
@@ -16,13 +17,6 @@ MUST_BE_EQUAL = ("action_mode", "tick_length", "car_length", "minimum_negative_j
                  "max_positive_acceleration", "max_speed", "n_action_values", "autoreset", "log_capacity")
 ENTRIES = {"stmpc_reward_groups_env_reset_device": 11, "stmpc_reward_groups_env_step_device": 13, "stmpc_reward_groups_env_reward_device": 14,
            "stmpc_reward_groups_split": 3}
-
-
-def _pkg():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    return pkg
 
 
 class _NoDevice:

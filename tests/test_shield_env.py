@@ -6,15 +6,10 @@ shield_kmax = 32.  Every shielded run is recorded once (``_record``) and shared 
 import numpy as np
 import pytest
 
+from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same
+
 N, KMAX, SEED, ACT_SEED = 96, 32, 7, 11
 _cache = {}
-
-
-def _pkg():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    return pkg
 
 
 def _settings():
@@ -24,16 +19,6 @@ def _settings():
     pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
     pkg.apply_overrides(episodes.TRAFFIC_TYPES["default"])
     return pkg.Settings
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _actions(env, rng, n):

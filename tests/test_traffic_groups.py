@@ -7,10 +7,10 @@ path a user had before groups existed.  The shape is the smallest that can go wr
 n_per_group = 24 (no multiple of the 64-lane workgroup: every group has a masked tail, and a workgroup that spanned groups would mix cfgs from row
 24 on), Kmax = 16.  No tolerance anywhere.
 """
-import contextlib
-
 import numpy as np
 import pytest
+
+from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same, settings_of as _settings_of, linit as _linit
 
 NPG, G, KMAX, TICKS = 24, 3, 16, 40
 N = G * NPG
@@ -18,40 +18,9 @@ NAMES, SEEDS = ("low", "default", "fast"), (31, 32, 33)
 _cache = {}
 
 
-def _pkg():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    return pkg
-
-
 def _traffic(names=NAMES, seeds=SEEDS):
     from rl_mpc_lanemerging_amd import episodes
     return [dict(episodes.TRAFFIC_TYPES[t], seed=s) for t, s in zip(names, seeds)]
-
-
-@contextlib.contextmanager
-def _settings_of(group):
-    """The global Settings with one traffic group's values: how a lone world of that traffic is made through the plain entries."""
-    pkg = _pkg()
-    snap = pkg.Settings.snapshot()
-    pkg.apply_overrides({k: v for k, v in group.items() if k != "seed"})
-    try:
-        yield
-    finally:
-        pkg.Settings.restore(snap)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype.kind == "f":
-        return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-    return a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _sl(g):
@@ -218,15 +187,6 @@ def _lcfg(m):
     from rl_mpc_lanemerging_amd import learner
     return learner.DDPGConfig(n_obs=20, batch=BATCH, capacity=CAP, replay_start=REPLAY_START[m], gamma=GAMMA[m], tau=TAU[m], noise=NOISE[m], lr_q=LR_Q[m],
                               lr_pi=LR_PI[m])
-
-
-def _linit(m):
-    from rl_mpc_lanemerging_amd import learner
-    rng = np.random.default_rng(100 + m)
-    a_net, q_net = learner.init_net(21, 400, 300, rng), learner.init_net(22, 400, 300, rng)
-    a_net["w2"] = rng.normal(0, 0.05, (1, 300)).astype(np.float32)
-    q_net["w2"] = rng.normal(0, 0.05, (1, 300)).astype(np.float32)
-    return {"actor": a_net, "critic": q_net}
 
 
 def _train(env, L, lr_q, lr_pi):

@@ -12,13 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, REPO
-
-
-def _pkg():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    return pkg
+from stmpc_testlib import pkg as _pkg
 
 
 class _NoDevice:

@@ -15,6 +15,8 @@ third hold their speed (arrivals), a third brake (out of time).
 import numpy as np
 import pytest
 
+from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same
+
 N, SEED, STEPS = 96, 7, 300
 MIX = ["low", "default", "fast"]
 TICK, EPISODE_S, MAX_TICKS = 0.4, 20.0, 50
@@ -22,13 +24,6 @@ CONT, DISC = "sumo-jerk-continuous-v0", "sumo-jerk-v0"
 KEYS = ("obs", "reward", "terminated", "truncated", "final_observation", "final_stats", "ticks")
 _M64 = (1 << 64) - 1
 _cache = {}
-
-
-def _pkg():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    return pkg
 
 
 def _hash01(e, tick):
@@ -47,16 +42,6 @@ def _action_table(env_id):
         jerk = np.array([[min(max(centre[e % 3] + (2.0 * _hash01(e, k) - 1.0) * width[e % 3], -5.0), 5.0) for k in range(MAX_TICKS + 1)] for e in range(N)])
         _cache[env_id] = jerk if env_id == CONT else np.clip(np.rint(jerk / 2.5) + 2, 0, 4).astype(np.int32)
     return _cache[env_id]
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _settings():

@@ -11,15 +11,9 @@ import re
 import pytest
 
 from conftest import REPO
+from stmpc_testlib import pkg as _pkg
 
 ENTRIES = {"stmpc_traffic_mix_env_reset_device": 12, "stmpc_traffic_mix_env_step_device": 15, "stmpc_traffic_mix_draw": 5}
-
-
-def _pkg():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    return pkg
 
 
 class _NoDevice:
