@@ -18,6 +18,7 @@
 #include "stmpc_env_groups_kernels.hpp"
 #include "stmpc_shield_env_kernels.hpp"
 #include "stmpc_traffic_mix_kernels.hpp"
+#include "stmpc_solve_plan.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -123,8 +124,6 @@ struct Share {
 // two host arrays hold the same n bytes: one array, or equal contents
 bool same_bytes(const void *p, const void *q, size_t n) { return p == q || memcmp(p, q, n) == 0; }
 
-int next_pow2(int v) { int w = 1; while (w < v) w <<= 1; return w; }
-
 // divc<true> needs RN(1/d) to be usable by Markstein's theorem: excludes divisors whose significand is all ones
 bool fastdiv_ok(double d) {
     uint64_t b; memcpy(&b, &d, 8);
@@ -191,8 +190,6 @@ struct stmpc_ctx {
     int device = 0;
     int num_cu = 256;
     int lds_per_block = 65536;
-    // scratch
-    DevBuf tab_edge, tab_win, tab_nact, tab_nums, counters, lists, ubound, proxy, order, gscratch, bp_tier[STMPC_MAX_TIERS];
     // staging for the host-pointer API
     struct Staging {
         DevBuf ego, k, ox, ov, path, bt, cost, pd, crash, misc0, misc1, misc2, misc3;
@@ -207,8 +204,6 @@ struct stmpc_ctx {
             return STMPC_OK;
         }
     } s;
-    DevBuf ckpt, pool_bp, resume_t, phase_prof, prio_key;
-    int pool_cap_override = 0;     // STMPC_POOL=n: checkpoint pool entries (tests: a tiny pool must only cost speed)
     // What a shield controller keeps of "st.do_st_control of the start states" (shield_control): the controller's outputs for its N rows, with the probe's
     // verdicts, and for the sparse solve the compact batch of the rows that need the controller.  One per controller: each is read back after its call.
     struct ShieldBufs {
@@ -322,89 +317,48 @@ struct stmpc_ctx {
         }
         env::ShieldView view() const { return env::ShieldView{ego5.as<double>(), k.as<int>(), ox.as<double>(), ov.as<double>(), proposal.as<double>()}; }
     } shield;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+    // the batched ST solver (solve_device and the entries on top of it)
+    struct Solver {
+        plan::SolveKnobs knobs;        // the STMPC_* settings (stmpc_create)
+        DevBuf tab_edge, tab_win, tab_nact, tab_nums, counters, lists, ubound, proxy, order, gscratch, bp_tier[STMPC_MAX_TIERS], resume_t, phase_prof, prio_key, cu_tab;   // scratch
+        // checkpoint pool, and what the quarter-of-free-memory rule remembers
+        DevBuf ckpt, pool_bp;
+        unsigned resume_refused_calls = 0;
+        bool last_resume_refused = false;   // the last batch wanted checkpoint / resume and did not get it (stmpc_stats::resume_refused)
+        size_t resume_refused_for = 0; // back-pointer bytes of the last request the quarter-of-free-memory rule turned down (not asked again until the request changes)
+        // guide tables, one per parameter set (dynamics + cost weights), least recently used replaced: a caller that alternates parameter sets
+        // (two controllers on one context) neither rebuilds nor waits
+        struct GuideSlot { double key[12] = {0}; bool valid = false, ok = false; int imax = 0, D = 0; std::vector<unsigned char> host; DevBuf dev; uint64_t last_use = 0; };
+        GuideSlot guides[4]; uint64_t guide_clock = 0;
+        DevBuf guide_cells;
+        // solver groups: the device copy of the last grouped call's table (kept while the next call's table is equal), its guide tables, one after another,
+        // and the groups' crash_min_s for the grouped world step
+        struct SolverGroupsDev {
+            DevBuf table, guide, crash_min_s;
+            std::vector<GroupP> host;          // what `table` holds
+            std::vector<double> host_cms;      // what `crash_min_s` holds
+            bool want_guide = false, guide_ok = false; int guide_imax = 0, guide_D = 0;
+        } sg;
+        double fd2_dt = 0, fd2_dt2 = 0, fd2_dt3 = 0, fd2_zl[3] = {0, 0, 0}; bool fd2_ok = false;      // fastdiv2_ok results for the current dt
+        // the side stream and the CU-masked pair of STMPC_CU_RESERVE, with the events that fork from and join the caller's stream
+        hipStream_t aux_stream = nullptr, main_masked = nullptr, aux_reserved = nullptr;
+        hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join0 = nullptr, ev_join_r = nullptr;
+        int *h_overflow = nullptr, *d_overflow = nullptr;   // mapped pinned words the batch's last launch stores (plan::SolveHistory::overflow)
+        int last_nt = 0;
+        bool last_has_hbm = true;
+        int64_t last_hbm_tier_count = 0;    // episodes the last batch whose statistics were read sent to the clean-up tier
+        hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+        // profiling pool: one (begin, dp-begin, dp-end, end) event quad per launch while enabled
+        bool profiling = false;
+        std::vector<hipEvent_t> pool;
+        size_t pool_used = 0;          // events used (multiple of 4)
+        double acc_solve_ms = 0, acc_dp_ms = 0;
+        int64_t acc_launches = 0, acc_fallback = 0, acc_episodes = 0;
+    } solver;
     stmpc_stats stats{};
     bool stats_pending = false;
-    // profiling pool: one (begin, dp-begin, dp-end, end) event quad per launch while enabled
-    bool profiling = false;
-    std::vector<hipEvent_t> pool;
-    size_t pool_used = 0;          // events used (multiple of 4)
-    double acc_solve_ms = 0, acc_dp_ms = 0;
-    int64_t acc_launches = 0, acc_fallback = 0, acc_episodes = 0;
-    int lds_tier_W[STMPC_MAX_TIERS] = {2048, 4096, 8192, 0, 0, 0};   // LDS windows (cells), increasing
-    int n_lds_tiers = 0;          // 0 = automatic: {2048, smallest window covering every cell (<= 8192)}
-    int pen_cells[STMPC_MAX_TIERS] = {0, 0, 0, 0, 0, 0};   // STMPC_PEN_CELLS="a,b,c": penalty-buffer cells per LDS tier (0 = min(W, 4096))
-    int max_waves_per_cu = 16;
-    int lds_headroom = 1024;       // STMPC_LDS_HEADROOM: bytes added to a workgroup's dynamic LDS when counting workgroups per CU
-    int waves_override = 0;       // STMPC_NW=n or "a,b,c": waves per workgroup (episode), all tiers or per LDS tier
-    int waves_tier[STMPC_MAX_TIERS] = {0, 0, 0, 0, 0, 0};
-    bool tiers_from_env = false;
-    bool allow_fastdiv = true;
-    double fd2_dt = 0, fd2_dt2 = 0, fd2_dt3 = 0, fd2_zl[3] = {0, 0, 0}; bool fd2_ok = false;      // fastdiv2_ok results for the current dt
-    int prune = -1;               // -1 auto (bounded search only when the fan-out is large), 0 off, 1 on
-    double band_override = 0.0;
-    int band_dense = 1;            // STMPC_BAND_DENSE=0/1: dense ordinary bounding attempts (band_pass)
-    int tube_dense = 1;            // STMPC_TUBE_DENSE=0/1: dense guided attempt (tube_pass)
-    int band_cap = 450;            // STMPC_BAND_CAP: nodes per layer the pre-pass steers its band towards (0 = fixed band); 300 until the pre-pass moved to
-                                   // packed single precision (round 3): with candidates at a fifth of their former cost a wider pre-pass pays for itself in
-                                   // tighter bounds (10 state seeds at N=4096: 375-600 all within 2 % of each other and 5 % ahead of 300)
-    double band2_mult = 0.0;       // STMPC_BAND2_MULT (0 = default: 4 with the node cap, 5 with a fixed band)
-    bool force_general = false;    // STMPC_FORCE_GENERAL=1 (tests)
-    bool two_phase = false;        // STMPC_TWO_PHASE=1: bound all episodes first, then solve heaviest-first (measured 6 % slower at N=4096)
-    bool allow_stage_tab = false;  // STMPC_STAGE_TAB=1: stage the vehicle table in LDS + scalar registers (costs the 4th workgroup per CU)
-    int last_nt = 0;
-    bool last_has_hbm = true;
-    // STMPC_OVERLAP=0/1: start the second LDS tier on its own stream while the first is still running (see k_solve)
-    bool resume = true;            // STMPC_RESUME=0/1: the wider window continues a checkpointed exact pass instead of starting over
-    bool heavy_first = false;      // STMPC_HEAVY_FIRST=1: split tasks are handed out slow starters first (measured: 6.76-6.82 vs 6.81-6.82 ms at N=4096, 13.0 vs 12.2 ms at N=8192 -- long searches side by side slow each other down; off)
-    int gsh_max = 4;               // STMPC_GSH=0..4: lanes per source of sparse layers, log2 (0 = one lane per source)
-    bool split = true;             // STMPC_SPLIT=0/1: bounding and exact pass of an episode are separate tasks of the first launch (-4 % at N=4096)
-    int overlap = -1;              // -1 auto: with the bounded (wide fan-out) search, where overflow is common
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // STMPC_CU_RESERVE=n (multiple of 8, experiment): n compute units are kept out of the first window's launch and host the second
-    // window's workgroups from the start of the step (CU-masked streams); 0 = off
-    int cu_reserve = 0;
-    int side_grid = 0;             // STMPC_SIDE_GRID=n: workgroups of the second window's side launch (0 = automatic: the tier's full grid with the bounded
-                                   // search, 32 on the narrow lattice where a handful of episodes overflow)
-    int *h_overflow = nullptr, *d_overflow = nullptr;   // mapped pinned word: episodes that overflowed the first window in the batch before this one (stored by the
-                                   // batch's last launch straight into host memory -- no copy, no stall --, read, possibly one batch late, when the next one
-                                   // is set up): the narrow lattice starts its second window alongside the first only when there was something for it to do
-    double last_infl = 1.005;      // STMPC_LAST_INFL: the exact pass's candidate filter lets terminals up to this factor above the bound through (SolveArgs::last_infl); 1 = off
-    double bound_infl = 1.00002;   // STMPC_BOUND_INFL: factor on a bounding pass's single-precision path cost (>= 1.00002, the rounding of that total)
-    int qp_maxiters = STMPC_QP_MAXITERS;   // STMPC_QP_ITERS (experiment: the iteration cap of st.do_st_control's QP; the reference's is 10, st.py:17)
-    int tube_w = 96;               // STMPC_TUBE=w: half-width (cells) of the guided bounding attempt, 0 = off (see SolveArgs::guide_tab)
-    // guide tables, one per parameter set (dynamics + cost weights), least recently used replaced: a caller that alternates parameter sets
-    // (two controllers on one context) neither rebuilds nor waits
-    struct GuideSlot { double key[12] = {0}; bool valid = false, ok = false; int imax = 0, D = 0; std::vector<unsigned char> host; DevBuf dev; uint64_t last_use = 0; };
-    GuideSlot guides[4]; uint64_t guide_clock = 0;
-    DevBuf guide_cells;
-    // solver groups: the device copy of the last grouped call's table (kept while the next call's table is equal), its guide tables, one after another,
-    // and the groups' crash_min_s for the grouped world step
-    struct SolverGroupsDev {
-        DevBuf table, guide, crash_min_s;
-        std::vector<GroupP> host;          // what `table` holds
-        std::vector<double> host_cms;      // what `crash_min_s` holds
-        bool want_guide = false, guide_ok = false; int guide_imax = 0, guide_D = 0;
-    } sg;
-    int prio_thr = 32000;          // STMPC_PRIO=t (0 = off): an overflowing search with more than t (layers left x nodes of the saved layer) ahead of it is served first
-                                   // by the second window (SolveArgs::prio_thr): 4.60 -> 4.46 ms over 12 seeds at N = 4096, flat from 25000 to 35000
-    int prio_mode = 0;             // STMPC_PRIO_MODE (experiment: which estimate prio_thr is compared with)
-    bool bp16 = false;             // STMPC_BP16=1: two-byte back-pointers even where one byte would do
-    unsigned resume_refused_calls = 0;
-    bool last_resume_refused = false;   // the last batch wanted checkpoint / resume and did not get it (stmpc_stats::resume_refused)
-    int64_t last_hbm_tier_count = 0;    // episodes the last batch whose statistics were read sent to the clean-up tier
-    size_t resume_refused_for = 0; // back-pointer bytes of the last request the quarter-of-free-memory rule turned down (not asked again until the request changes)
-    int retry_move = 0;            // STMPC_RETRY_MOVE=k: see SolveArgs::retry_move
-    double retry_mult[3] = {1.05, 1.3, 4.0};    // STMPC_RETRY="a,b,c": growth of a bound that turned out to be below the reference's terminal cost.  Round 2 grew gently
-                                                // (1.02, 1.08, 1.3): most failures need less than 0.2 %, but the rare search that fails twice is three ever larger passes
-                                                // in a row and ends the step; over 16 state seeds (1.05, 1.3, 4) has the same median and no 5.4-5.8 ms outliers
-    int retire_cus = 0, retire_at = 75;   // STMPC_RETIRE_CUS=k, STMPC_RETIRE_AT=percent of N: k compute units leave the first launch once fewer than that many tasks are left (see SolveArgs::cu_tab)
-    DevBuf cu_tab;
     DevBuf sticky;                 // [3] error flags that outlive a call: [0] solver internal error, [1] QP re-sampling refused a path, [2] a discrete env action out of range
                                    // (read and cleared by stmpc_check_error)
-    hipStream_t main_masked = nullptr, aux_reserved = nullptr;
-    hipEvent_t ev_join0 = nullptr, ev_join_r = nullptr;
 };
 
 extern "C" {
@@ -447,103 +401,41 @@ int stmpc_create(stmpc_ctx **out, int device) {
         c->num_cu = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
         c->lds_per_block = (int)pr.sharedMemPerBlock;
     }
-    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        hipEventCreate(&c->ev2) != hipSuccess || hipEventCreate(&c->ev3) != hipSuccess) {
+    stmpc_ctx::Solver &sv = c->solver;
+    if (hipEventCreate(&sv.ev0) != hipSuccess || hipEventCreate(&sv.ev1) != hipSuccess ||
+        hipEventCreate(&sv.ev2) != hipSuccess || hipEventCreate(&sv.ev3) != hipSuccess) {
         delete c;
         return fail(STMPC_EHIP, "hipEventCreate failed");
     }
-    // experiment knobs: STMPC_TIERS="512,2048" (LDS windows), STMPC_WAVES_PER_CU, STMPC_FASTDIV=0
-    if (const char *w = getenv("STMPC_TIERS")) {
-        int n = 0; const char *q = w;
-        while (*q && n < STMPC_MAX_TIERS - 1) {
-            int v = atoi(q);
-            if (v >= 64 && v <= 8192 && (v & (v - 1)) == 0 && (n == 0 || v > c->lds_tier_W[n - 1])) c->lds_tier_W[n++] = v;
-            while (*q && *q != ',') ++q;
-            if (*q == ',') ++q;
-        }
-        if (n > 0) c->n_lds_tiers = n;
-        c->tiers_from_env = n > 0;
-    }
-    if (const char *w = getenv("STMPC_WAVES_PER_CU")) { int v = atoi(w); if (v >= 1 && v <= 32) c->max_waves_per_cu = v; }
-    if (const char *w = getenv("STMPC_LDS_HEADROOM")) { int v = atoi(w); if (v >= 600 && v <= 8192) c->lds_headroom = v; }
-    if (const char *w = getenv("STMPC_PEN_CELLS")) {
-        int n = 0; const char *q = w;
-        while (*q && n < STMPC_MAX_TIERS) {
-            int v = atoi(q);
-            if (v >= 128 && v <= 8192 && (v & (v - 1)) == 0) c->pen_cells[n] = v;
-            ++n;
-            while (*q && *q != ',') ++q;
-            if (*q == ',') ++q;
-        }
-    }
-    if (const char *w = getenv("STMPC_NW")) {
-        if (strchr(w, ',')) {
-            int n = 0; const char *q = w;
-            while (*q && n < STMPC_MAX_TIERS) {
-                int v = atoi(q);
-                if (v >= 1 && v <= STMPC_MAXWAVES) c->waves_tier[n] = v;
-                ++n;
-                while (*q && *q != ',') ++q;
-                if (*q == ',') ++q;
-            }
-        } else { int v = atoi(w); if (v >= 1 && v <= STMPC_MAXWAVES) c->waves_override = v; }
-    }
-    if (const char *w = getenv("STMPC_FASTDIV")) c->allow_fastdiv = atoi(w) != 0;
-    if (const char *w = getenv("STMPC_PRUNE")) c->prune = atoi(w) != 0 ? 1 : 0;
-    if (const char *w = getenv("STMPC_BAND")) c->band_override = atof(w);
-    if (const char *w = getenv("STMPC_FORCE_GENERAL")) c->force_general = atoi(w) != 0;
-    if (const char *w = getenv("STMPC_TWO_PHASE")) c->two_phase = atoi(w) != 0;
-    if (const char *w = getenv("STMPC_BAND2_MULT")) { double v = atof(w); if (v >= 1.0) c->band2_mult = v; }
-    if (const char *w = getenv("STMPC_STAGE_TAB")) c->allow_stage_tab = atoi(w) != 0;
-    if (const char *w = getenv("STMPC_OVERLAP")) c->overlap = atoi(w) != 0 ? 1 : 0;
-    if (const char *w = getenv("STMPC_BAND_DENSE")) c->band_dense = atoi(w) != 0;
-    if (const char *w = getenv("STMPC_TUBE_DENSE")) c->tube_dense = atoi(w) != 0;
-    if (const char *w = getenv("STMPC_BAND_CAP")) { int v = atoi(w); if (v >= 0) c->band_cap = v; }
-    if (const char *w = getenv("STMPC_SPLIT")) c->split = atoi(w) != 0;
-    if (const char *w = getenv("STMPC_HEAVY_FIRST")) c->heavy_first = atoi(w) != 0;
-    if (const char *w = getenv("STMPC_GSH")) { int v = atoi(w); if (v >= 0 && v <= 4) c->gsh_max = v; }
-    if (const char *w = getenv("STMPC_RESUME")) c->resume = atoi(w) != 0;
-    if (const char *w = getenv("STMPC_LAST_INFL")) { double v = atof(w); if (v >= 1.0 && v <= 4.0) c->last_infl = v; }
-    if (const char *w = getenv("STMPC_BOUND_INFL")) { double v = atof(w); if (v >= 1.00002 && v <= 2.0) c->bound_infl = v; }
-    if (const char *w = getenv("STMPC_POOL")) { int v = atoi(w); if (v >= 1) c->pool_cap_override = v; }
-    if (const char *w = getenv("STMPC_QP_ITERS")) { int v = atoi(w); if (v >= 0 && v <= 1000) c->qp_maxiters = v; }
+    sv.knobs = plan::SolveKnobs::from_env();
     // the side stream gets the highest priority: priority levels have their own hardware queues, so its launch
     // cannot end up queued behind the main stream's in a process that owns many streams (torch + RCCL)
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    if (hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, prio_greatest) != hipSuccess) {
+    if (hipStreamCreateWithPriority(&sv.aux_stream, hipStreamNonBlocking, prio_greatest) != hipSuccess) {
         (void)hipGetLastError();
-        c->aux_stream = nullptr;
-        if (hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess) c->aux_stream = nullptr;
+        sv.aux_stream = nullptr;
+        if (hipStreamCreateWithFlags(&sv.aux_stream, hipStreamNonBlocking) != hipSuccess) sv.aux_stream = nullptr;
     }
-    if (!c->aux_stream) c->overlap = 0;          // no side stream: the tiers simply run one after the other
+    if (!sv.aux_stream) sv.knobs.overlap = 0;          // no side stream: the tiers simply run one after the other
     if (c->sticky.ensure(3 * sizeof(unsigned)) || hipMemset(c->sticky.p, 0, 3 * sizeof(unsigned)) != hipSuccess) { stmpc_destroy(c); return fail(STMPC_ENOMEM, "device allocation failed"); }
-    if (const char *w = getenv("STMPC_TUBE")) { int v = atoi(w); if (v >= 0 && v <= 4096) c->tube_w = v; }
-    if (const char *w = getenv("STMPC_PRIO")) { int v = atoi(w); if (v >= 0) c->prio_thr = v; }
-    if (const char *w = getenv("STMPC_PRIO_MODE")) c->prio_mode = atoi(w);
-    if (getenv("STMPC_BP16")) c->bp16 = true;
-    if (const char *w = getenv("STMPC_RETRY_MOVE")) { int v = atoi(w); if (v >= 0 && v <= 4) c->retry_move = v; }
-    if (const char *w = getenv("STMPC_RETRY")) { double x[3]; if (sscanf(w, "%lf,%lf,%lf", &x[0], &x[1], &x[2]) == 3 && x[0] > 1.0 && x[1] > 1.0 && x[2] > 1.0) for (int i = 0; i < 3; ++i) c->retry_mult[i] = x[i]; }
-    if (const char *w = getenv("STMPC_RETIRE_CUS")) { int v = atoi(w); if (v >= 0 && v < 256) c->retire_cus = v; }
-    if (const char *w = getenv("STMPC_RETIRE_AT")) { int v = atoi(w); if (v >= 1 && v <= 200) c->retire_at = v; }
-    if (const char *w = getenv("STMPC_SIDE_GRID")) { int v = atoi(w); if (v >= 1) c->side_grid = v; }
-    if (const char *w = getenv("STMPC_CU_RESERVE")) {
+    if (const int v = sv.knobs.cu_reserve) {
         // Reserved compute units: bit 32a + a + 8j (a = 0..7, j < n/8) of the CU mask.  Whether the driver numbers the mask bits
         // XCD by XCD or round-robin over the XCDs, every XCD gives up n/8 units and keeps the rest (a queue whose mask leaves an XCD
         // without units would never get the workgroups the dispatcher assigns to that XCD).
-        int v = atoi(w);
-        if (c->aux_stream && v >= 8 && v <= 128 && v % 8 == 0 && c->num_cu == 256) {
+        sv.knobs.cu_reserve = 0;
+        if (sv.aux_stream && c->num_cu == 256) {
             uint32_t res[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rest[8];
             for (int a = 0; a < 8; ++a) for (int j = 0; j < v / 8; ++j) { const int bit = 32 * a + ((a + 8 * j) & 31); res[bit >> 5] |= 1u << (bit & 31); }
             for (int i = 0; i < 8; ++i) rest[i] = ~res[i];
-            if (hipExtStreamCreateWithCUMask(&c->main_masked, 8, rest) == hipSuccess && hipExtStreamCreateWithCUMask(&c->aux_reserved, 8, res) == hipSuccess &&
-                hipEventCreateWithFlags(&c->ev_join0, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_join_r, hipEventDisableTiming) == hipSuccess)
-                c->cu_reserve = v;
+            if (hipExtStreamCreateWithCUMask(&sv.main_masked, 8, rest) == hipSuccess && hipExtStreamCreateWithCUMask(&sv.aux_reserved, 8, res) == hipSuccess &&
+                hipEventCreateWithFlags(&sv.ev_join0, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&sv.ev_join_r, hipEventDisableTiming) == hipSuccess)
+                sv.knobs.cu_reserve = v;
             else (void)hipGetLastError();
         }
     }
-    if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
+    if (hipEventCreateWithFlags(&sv.ev_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&sv.ev_join, hipEventDisableTiming) != hipSuccess) {
         stmpc_destroy(c);
         return fail(STMPC_EHIP, "stream/event creation failed");
     }
@@ -554,19 +446,20 @@ int stmpc_create(stmpc_ctx **out, int device) {
 void stmpc_destroy(stmpc_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);       // (the device buffers are freed by their destructors, on this device)
-    if (c->h_overflow) (void)hipHostFree(c->h_overflow);
-    if (c->main_masked) (void)hipStreamDestroy(c->main_masked);
-    if (c->aux_reserved) (void)hipStreamDestroy(c->aux_reserved);
-    if (c->ev_join0) (void)hipEventDestroy(c->ev_join0);
-    if (c->ev_join_r) (void)hipEventDestroy(c->ev_join_r);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->ev2) (void)hipEventDestroy(c->ev2);
-    if (c->ev3) (void)hipEventDestroy(c->ev3);
-    for (hipEvent_t ev : c->pool) (void)hipEventDestroy(ev);
+    stmpc_ctx::Solver &sv = c->solver;
+    if (sv.h_overflow) (void)hipHostFree(sv.h_overflow);
+    if (sv.main_masked) (void)hipStreamDestroy(sv.main_masked);
+    if (sv.aux_reserved) (void)hipStreamDestroy(sv.aux_reserved);
+    if (sv.ev_join0) (void)hipEventDestroy(sv.ev_join0);
+    if (sv.ev_join_r) (void)hipEventDestroy(sv.ev_join_r);
+    if (sv.ev_fork) (void)hipEventDestroy(sv.ev_fork);
+    if (sv.ev_join) (void)hipEventDestroy(sv.ev_join);
+    if (sv.aux_stream) (void)hipStreamDestroy(sv.aux_stream);
+    if (sv.ev0) (void)hipEventDestroy(sv.ev0);
+    if (sv.ev1) (void)hipEventDestroy(sv.ev1);
+    if (sv.ev2) (void)hipEventDestroy(sv.ev2);
+    if (sv.ev3) (void)hipEventDestroy(sv.ev3);
+    for (hipEvent_t ev : sv.pool) (void)hipEventDestroy(ev);
     delete c;
 }
 
@@ -780,10 +673,10 @@ bool build_guide_table(const DevP &dp, std::vector<unsigned char> &tab, int &ima
 // Synchronous entries that reuse the counters: an error flag raised by an earlier asynchronous solve and not yet seen by
 // stmpc_get_stats / stmpc_check_error is moved to the context's sticky word first (k_predict does the same on the device).
 int latch_solver_error(stmpc_ctx *c) {
-    if (!c->counters.p) return STMPC_OK;
+    if (!c->solver.counters.p) return STMPC_OK;
     HIPCHK(hipDeviceSynchronize());
     unsigned cur = 0;
-    HIPCHK(hipMemcpy(&cur, (const unsigned *)c->counters.p + STMPC_CNT_ERR, sizeof cur, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&cur, (const unsigned *)c->solver.counters.p + STMPC_CNT_ERR, sizeof cur, hipMemcpyDeviceToHost));
     if (cur) { const unsigned one = 1u; HIPCHK(hipMemcpy(c->sticky.p, &one, sizeof one, hipMemcpyHostToDevice)); }
     return STMPC_OK;
 }
@@ -835,9 +728,132 @@ int stmpc_solve_batch_device_ac(stmpc_ctx *c, const stmpc_params *p, int N, int 
 
 namespace {
 
-// The batched solve behind every solver entry.  sg: null, or the groups of a grouped call (p is then groups[0], read for the shared fields): k_predict and
-// the k_solve launches are replaced by the kernels of namespace grouped on one fixed set of shapes (no staged vehicle table, no checkpoint / resume); every decision
-// below depends on fields the groups share.
+// ---- one k_solve launch ------------------------------------------------------------------------------------------------------------------
+struct SolveLaunch { dim3 grid, block; size_t lds; hipStream_t stream; const SolveArgs &a; const GroupTab *g; };
+
+// f(std::true_type or std::false_type)
+template <class F> int with_flag(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// one instantiation: compiled when plan::variant_built lists it, refused otherwise
+template <bool G, bool L, bool FD, int KT, int FM, bool SG, int RS, int NWX>
+int launch_instance(const SolveLaunch &l) {
+    if constexpr (!plan::variant_built(plan::KernelVariant{L, FD, KT, FM, SG, RS, NWX, G})) return fail(STMPC_EINTERNAL, "k_solve: no such kernel variant");
+    else if constexpr (G) {
+        SolveArgsG ag;
+        memset(&ag, 0, sizeof ag);
+        static_cast<SolveArgs &>(ag) = l.a;
+        ag.g = *l.g;
+        if (l.lds > 48 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void *)grouped::k_solve<L, false, FD, KT, FM, SG, RS, NWX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+        hipLaunchKernelGGL((grouped::k_solve<L, false, FD, KT, FM, SG, RS, NWX>), l.grid, l.block, l.lds, l.stream, ag);
+        return STMPC_OK;
+    } else {
+        if (l.lds > 48 * 1024)
+            HIPCHK(hipFuncSetAttribute((const void *)k_solve<L, false, FD, KT, FM, SG, RS, NWX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+        hipLaunchKernelGGL((k_solve<L, false, FD, KT, FM, SG, RS, NWX>), l.grid, l.block, l.lds, l.stream, l.a);
+        return STMPC_OK;
+    }
+}
+
+// RES and NWX of a variant whose other arguments are constants by now (FM: 9 or STMPC_FAN1; the 88 shape swaps in STMPC_FAN88)
+template <bool G, bool L, bool FD, int KT, int FM, bool SG>
+int launch_res_nwx(const plan::KernelVariant &v, const SolveLaunch &l) {
+    constexpr int NW = STMPC_MAXWAVES;
+    if (v.res == 0 && v.nwx == NW) return launch_instance<G, L, FD, KT, FM, SG, 0, NW>(l);
+    if (v.res == 0 && v.nwx == 4) return launch_instance<G, L, FD, KT, FM, SG, 0, 4>(l);
+    if (v.res == 1 && v.nwx == NW) return launch_instance<G, L, FD, KT, FM, SG, 1, NW>(l);
+    if (v.res == 1 && v.nwx == 4) return launch_instance<G, L, FD, KT, FM, SG, 1, 4>(l);
+    if (v.res == 2 && v.nwx == NW) return launch_instance<G, L, FD, KT, FM, SG, 2, NW>(l);
+    if (v.res == 2 && v.nwx == 88) return launch_instance<G, L, FD, KT, STMPC_FAN88, SG, 2, 88>(l);
+    return fail(STMPC_EINTERNAL, "k_solve: no such kernel variant");
+}
+
+// The k_solve instantiation of a variant: raises its dynamic LDS limit where the launch needs more than 48 KB, and launches it.
+int launch_k_solve(const plan::KernelVariant &v, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveArgs &a, const GroupTab *g) {
+    if (!plan::variant_built(v) || (v.grouped && !g)) return fail(STMPC_EINTERNAL, "k_solve: no such kernel variant");
+    const SolveLaunch l{grid, block, lds, stream, a, g};
+    return with_flag(v.grouped, [&](auto G) { return with_flag(v.use_lds, [&](auto L) { return with_flag(v.fastdiv, [&](auto FD) {
+           return with_flag(v.kt == 8, [&](auto KT8) { return with_flag(v.fanmax == 9, [&](auto F9) { return with_flag(v.s1gen, [&](auto SG) {
+               return launch_res_nwx<decltype(G)::value, decltype(L)::value, decltype(FD)::value, decltype(KT8)::value ? 8 : 0,
+                                     decltype(F9)::value ? 9 : STMPC_FAN1, decltype(SG)::value>(v, l); }); }); }); }); }); });
+}
+
+// ---- guide tables of the guided bounding attempt (SolveArgs::guide_tab) ------------------------------------------------------------------------
+struct Guide { const unsigned char *tab = nullptr; int imax = 0, D = 0; };
+
+// One parameter set: the table depends on the dynamics and the cost weights only; rebuilt when they change (a few ms on the host)
+int guide_for_params(stmpc_ctx::Solver &sv, const DevP &dp, hipStream_t st, Guide *out) {
+    const double key[12] = {dp.ds, dp.dt, dp.v_w, dp.a_w, dp.j_w, dp.v_des, dp.v_max, dp.a_min, dp.a_max, dp.j_min, dp.j_max, (double)dp.H};
+    stmpc_ctx::Solver::GuideSlot *slot = nullptr;
+    for (auto &g : sv.guides) if (g.valid && memcmp(key, g.key, sizeof key) == 0) { slot = &g; break; }
+    if (!slot) {
+        // A parameter set not seen before (or replaced since): build its table on the host (a few ms) and queue the upload on THIS call's
+        // stream, ahead of the kernels that read it.  Nothing waits for the device unless a table has to be replaced (a fifth parameter set):
+        // kernels of earlier calls may still read the one that goes.
+        for (auto &g : sv.guides) if (!g.valid) { slot = &g; break; }
+        if (!slot) {
+            slot = &sv.guides[0];
+            for (auto &g : sv.guides) if (g.last_use < slot->last_use) slot = &g;
+            slot->valid = false;
+            HIPCHK(hipDeviceSynchronize());
+        }
+        slot->ok = build_guide_table(dp, slot->host, slot->imax, slot->D);
+        if (slot->ok) {
+            TRY(slot->dev.ensure(slot->host.size()));
+            HIPCHK(hipMemcpyAsync(slot->dev.p, slot->host.data(), slot->host.size(), hipMemcpyHostToDevice, st));
+        }
+        memcpy(slot->key, key, sizeof key);
+        slot->valid = true;                 // (only after the upload has been queued successfully)
+    }
+    slot->last_use = ++sv.guide_clock;
+    if (slot->ok) *out = Guide{slot->dev.as<unsigned char>(), slot->imax, slot->D};
+    return STMPC_OK;
+}
+
+// The groups' table: per group the DevP, the band of its own weights and the offset of its own guide table (one table per distinct
+// (v_w, a_w, j_w), built on the host and stored one after another).  The device copies are kept while the next call brings an equal table;
+// replacing them waits for the device first (kernels of earlier calls may still read them).
+int guide_for_groups(stmpc_ctx::Solver &sv, const plan::SolvePlan &pl, SolverGroupsHost *sg, GroupTab *gtab, Guide *out) {
+    for (auto &gp : sg->table) { plan::band_for(pl.k, gp.p, &gp.band, &gp.band2_mult); gp.guide_off = -1; }
+    const bool same = sv.sg.host.size() == sg->table.size() && [&] {
+        for (size_t g = 0; g < sg->table.size(); ++g) {
+            GroupP x = sv.sg.host[g]; x.guide_off = -1;
+            if (memcmp(&x, &sg->table[g], sizeof x) != 0) return false;
+        }
+        return true;
+    }();
+    if (!same || sv.sg.want_guide != pl.guided) {
+        std::vector<unsigned char> all;
+        std::vector<int> built;                          // groups whose table is in `all`
+        bool ok = pl.guided;
+        int imax = 0, D = 0;
+        for (size_t g = 0; g < sg->table.size() && ok; ++g) {
+            GroupP &gp = sg->table[g];
+            for (int b : built)
+                if (sg->table[b].p.v_w == gp.p.v_w && sg->table[b].p.a_w == gp.p.a_w && sg->table[b].p.j_w == gp.p.j_w) { gp.guide_off = sg->table[b].guide_off; break; }
+            if (gp.guide_off >= 0) continue;
+            std::vector<unsigned char> one;
+            ok = build_guide_table(gp.p, one, imax, D);
+            if (!ok) break;
+            gp.guide_off = (long long)all.size();
+            all.insert(all.end(), one.begin(), one.end());
+            built.push_back((int)g);
+        }
+        if (!ok) for (auto &gp : sg->table) gp.guide_off = 0;
+        HIPCHK(hipDeviceSynchronize());
+        sv.sg.host.clear();
+        TRY(upload(sv.sg.table, sg->table.data(), sg->table.size()));
+        if (ok) TRY(upload(sv.sg.guide, all.data(), all.size()));
+        sv.sg.want_guide = pl.guided; sv.sg.guide_ok = ok; sv.sg.guide_imax = imax; sv.sg.guide_D = D;
+        sv.sg.host = sg->table;
+    }
+    gtab->groups = sv.sg.table.as<GroupP>(); gtab->n_per_group = sg->n_per_group;
+    if (pl.guided && sv.sg.guide_ok) *out = Guide{sv.sg.guide.as<unsigned char>(), sv.sg.guide_imax, sv.sg.guide_D};
+    return STMPC_OK;
+}
+
+// The batched solve behind every solver entry: carries out plan::plan_solve's plan.  sg: null, or the groups of a grouped call (p is then groups[0],
+// read for the shared fields): k_predict and the k_solve launches are replaced by the kernels of namespace grouped.
 int solve_device(stmpc_ctx *c, const stmpc_params *p, SolverGroupsHost *sg, int N, int Kmax, const double *d_ego,
                  const int32_t *d_k, const double *d_ox, const double *d_ov, int32_t *d_path,
                  int32_t *d_bt, double *d_cost, double *d_pd, int32_t *d_crash, double *d_action_cost, void *stream) {
@@ -848,442 +864,167 @@ int solve_device(stmpc_ctx *c, const stmpc_params *p, SolverGroupsHost *sg, int 
     if (Kmax > 0 && (!d_ox || !d_ov)) return fail(STMPC_EINVAL, "NULL device pointer (other_x/other_v)");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
+    stmpc_ctx::Solver &sv = c->solver;
     DevP dp;
     TRY(make_devp(p, &dp));
     const int H = dp.H;
     const int S_nom = stmpc_num_s(p, 0.0);
     if (S_nom < 2 || S_nom + 2 > STMPC_S_LIMIT) return fail(STMPC_EINVAL, "number of position cells out of range");
-    const int Kalloc = Kmax > 0 ? Kmax : 1;
     // FASTDIV kernels: Markstein's five-operation quotient for the lattice step (per-episode value), the two-operation one for
     // dt, dt^2, dt^3 once each of them has passed fastdiv2_ok (cached per context: the check costs a few hundred divisions)
-    if (c->fd2_dt != dp.dt || c->fd2_dt2 != dp.dt2 || c->fd2_dt3 != dp.dt3) {
-        c->fd2_dt = dp.dt; c->fd2_dt2 = dp.dt2; c->fd2_dt3 = dp.dt3;
-        c->fd2_ok = fastdiv2_ok(dp.dt, &c->fd2_zl[0]) && fastdiv2_ok(dp.dt2, &c->fd2_zl[1]) && fastdiv2_ok(dp.dt3, &c->fd2_zl[2]);
+    if (sv.fd2_dt != dp.dt || sv.fd2_dt2 != dp.dt2 || sv.fd2_dt3 != dp.dt3) {
+        sv.fd2_dt = dp.dt; sv.fd2_dt2 = dp.dt2; sv.fd2_dt3 = dp.dt3;
+        sv.fd2_ok = fastdiv2_ok(dp.dt, &sv.fd2_zl[0]) && fastdiv2_ok(dp.dt2, &sv.fd2_zl[1]) && fastdiv2_ok(dp.dt3, &sv.fd2_zl[2]);
     }
-    const bool fastdiv = c->allow_fastdiv && fastdiv_ok(dp.dt) && fastdiv_ok(dp.dt2) && fastdiv_ok(dp.dt3) && c->fd2_ok;
+    plan::SolveHistory hist;
+    if (sv.h_overflow) { hist.overflow[0] = sv.h_overflow[0]; hist.overflow[1] = sv.h_overflow[1]; }
+    hist.last_has_hbm = sv.last_has_hbm; hist.last_hbm_tier_count = sv.last_hbm_tier_count;
+    hist.fastdiv_proven = fastdiv_ok(dp.dt) && fastdiv_ok(dp.dt2) && fastdiv_ok(dp.dt3) && sv.fd2_ok;
+    const plan::SolvePlan pl = plan::plan_solve(sv.knobs, plan::DeviceShape{c->num_cu, c->lds_per_block}, dp, N, Kmax, sg != nullptr, hist);
+    const int Kalloc = pl.Kalloc, nt = pl.nt;
 
     // scratch
-    TRY(c->tab_edge.ensure((size_t)N * H * Kalloc * 2 * sizeof(double)));
-    TRY(c->tab_win.ensure((size_t)N * H * Kalloc * 2 * sizeof(int)));
-    TRY(c->tab_nact.ensure((size_t)N * H * sizeof(int)));
-    TRY(c->tab_nums.ensure((size_t)N * sizeof(int)));
-    if (!c->counters.p) { TRY(c->counters.ensure(64 * sizeof(unsigned))); HIPCHK(hipMemsetAsync(c->counters.p, 0, 64 * sizeof(unsigned), st)); }
-    TRY(c->lists.ensure((size_t)STMPC_MAX_TIERS * N * sizeof(int)));
-    TRY(c->ubound.ensure((size_t)N * sizeof(u64)));
-    TRY(c->proxy.ensure((size_t)N * sizeof(unsigned)));
-    TRY(c->order.ensure((size_t)N * sizeof(int)));
+    TRY(sv.tab_edge.ensure((size_t)N * H * Kalloc * 2 * sizeof(double)));
+    TRY(sv.tab_win.ensure((size_t)N * H * Kalloc * 2 * sizeof(int)));
+    TRY(sv.tab_nact.ensure((size_t)N * H * sizeof(int)));
+    TRY(sv.tab_nums.ensure((size_t)N * sizeof(int)));
+    if (!sv.counters.p) { TRY(sv.counters.ensure(64 * sizeof(unsigned))); HIPCHK(hipMemsetAsync(sv.counters.p, 0, 64 * sizeof(unsigned), st)); }
+    TRY(sv.lists.ensure((size_t)STMPC_MAX_TIERS * N * sizeof(int)));
+    TRY(sv.ubound.ensure((size_t)N * sizeof(u64)));
+    TRY(sv.proxy.ensure((size_t)N * sizeof(unsigned)));
+    TRY(sv.order.ensure((size_t)N * sizeof(int)));
 
-    // widest fan-out the dynamics allow (st_cy.pyx:65-93): acceleration- or jerk-limited window, +2 for rounding
-    const double fan_acc = (dp.a_max - dp.a_min) * dp.dt2 / dp.ds, fan_jerk = (dp.j_max - dp.j_min) * dp.dt3 / dp.ds;
-    const double fan_bound = (fan_acc < fan_jerk ? fan_acc : fan_jerk) + 2.0;
-    const bool small_fan = fan_bound <= 9.0;
-    // the scalar-register vehicle table costs ~48 SGPRs/VGPRs: only with the small-fan kernel (the wide one would spill)
-    const bool stage_tab = !sg && c->allow_stage_tab && small_fan && Kalloc <= 8 && stmpc_tab_bytes(H, 8) <= 4096;
-
-    // tiers: LDS windows in increasing size, then one HBM-scratch tier whose window covers every cell
-    const int Wg = next_pow2(S_nom + 2 + 128);   // covers every cell plus the 64-cell alignment slack
-    int tierW[STMPC_MAX_TIERS]; int tierPW[STMPC_MAX_TIERS]; bool tierLds[STMPC_MAX_TIERS]; int tierGrid[STMPC_MAX_TIERS]; int tierNW[STMPC_MAX_TIERS];
-    size_t tierLdsBytes[STMPC_MAX_TIERS];
-    int nt = 0;
-    int auto_W[2] = {2048, Wg < 8192 ? Wg : 8192};
-    int n_auto = 2;
-    if (auto_W[1] <= auto_W[0]) { auto_W[0] = auto_W[1]; n_auto = 1; }      // one window already covers the lattice
-    const int n_lds = c->tiers_from_env ? c->n_lds_tiers : n_auto;
-    for (int k = 0; k < n_lds && nt < STMPC_MAX_TIERS - 1; ++k) {
-        int W = c->tiers_from_env ? c->lds_tier_W[k] : auto_W[k];
-        if (W > Wg && nt > 0) break;
-        const int nw = c->waves_tier[k] > 0 ? c->waves_tier[k] : (c->waves_override > 0 ? c->waves_override : (W <= 2048 ? 4 : 8));
-        // penalty buffer: 1024 cells for the first (4-wave) tier -- with the 14 B/cell arrays that is 38 KB per
-        // workgroup, i.e. 4 workgroups = 16 waves per CU -- and up to 4096 cells for the wider tiers
-        int PW = c->pen_cells[k] > 0 ? c->pen_cells[k] : (k == 0 && W <= 2048 ? 1024 : 4096);
-        if (PW > W) PW = W;
-        const size_t lds = (size_t)W * STMPC_CELL_BYTES + STMPC_LIST_SLACK + (size_t)PW * 8 + ((stmpc_chunk_ints(W) * sizeof(int) + 15) & ~(size_t)15) +
-                           stmpc_tab_bytes(H, stage_tab ? 8 : 0);
-        if (lds + 2048 > (size_t)c->lds_per_block) break;
-        tierW[nt] = W; tierPW[nt] = PW; tierLds[nt] = true; tierLdsBytes[nt] = lds;
-        tierNW[nt] = nw;
-        int per_cu = (int)((size_t)(c->lds_per_block) / (lds + c->lds_headroom));      // (+ the kernel's static LDS and allocation granularity)
-        int by_waves = c->max_waves_per_cu / tierNW[nt];
-        if (per_cu > by_waves) per_cu = by_waves;
-        if (per_cu < 1) per_cu = 1;
-        tierGrid[nt] = c->num_cu * per_cu;
-        ++nt;
-    }
-    // an LDS tier whose window covers every cell cannot overflow: the HBM-scratch tier is only needed beyond that
-    const bool need_hbm_tier = (nt == 0) || tierW[nt - 1] < Wg || tierPW[nt - 1] < tierW[nt - 1];
-    if (need_hbm_tier) {
-        // Clean-up launch: when the last LDS window already covers every cell, the only episodes that can reach this tier are those whose
-        // lattice is not start + n*delta (the LDS kernels are compiled for that form) and rounds whose 64 sources' targets do not fit the
-        // penalty buffer -- none in 4096 x 16 benchmark batches.  The launch then exists for correctness only and is sized accordingly: a
-        // full persistent grid costs 13 us per step to start and leave on an empty queue (and its spill prologue writes 9 MB), 16 workgroups 3.
-        const bool cleanup_only = nt > 0 && tierW[nt - 1] >= Wg && !c->tiers_from_env && !c->force_general;
-        tierW[nt] = Wg; tierPW[nt] = Wg; tierLds[nt] = false; tierNW[nt] = c->waves_override > 0 ? c->waves_override : 8;
-        tierLdsBytes[nt] = ((stmpc_chunk_ints(Wg) * sizeof(int) + 15) & ~(size_t)15) + 16;
-        // (a batch that sent more than a handful of episodes there -- e.g. identical reset states whose second lattice point is not start + step --
-        // gets the full grid from the next step on)
-        // (the count comes from a mapped host word the batch's last launch stores itself, [1] of h_overflow: a caller that never reads statistics --
-        // EpisodeRunner, decide_batch_device -- gets the full grid as well)
-        const int64_t sent_last = c->h_overflow && c->last_has_hbm ? (int64_t)c->h_overflow[1] : 0;
-        tierGrid[nt] = (cleanup_only && c->last_hbm_tier_count <= 16 && sent_last <= 16) ? 16 : c->num_cu * (c->max_waves_per_cu / tierNW[nt] > 0 ? c->max_waves_per_cu / tierNW[nt] : 1); ++nt;
-    }
-    const int prune_on = c->prune < 0 ? (small_fan ? 0 : 1) : c->prune;
-    // checkpoint / resume across the first two LDS windows (SolveArgs::ckpt, ::pool_bp): a search that cannot build a layer in the first window
-    // saves that layer and the back-pointer rows written so far in an entry of a pool and continues in the second window from there.
-    // back-pointers: one byte (distance to the predecessor) when no step of the dynamics exceeds 255 cells, else two (its cell)
-    const bool bp_rel8 = ceil(dp.v_max * dp.dt / dp.ds) + 4.0 <= 255.0 && !c->bp16;
-    const size_t bp_elem = bp_rel8 ? 1 : sizeof(u16);
-    const size_t ckpt_stride = 16 + (size_t)tierW[0] * 12;
-    // Pool: an eighth of the batch (5 % of the benchmark's searches overflow), at least 256 entries, of H x W0 back-pointers + one saved layer
-    // (104 KB at H = 40): 53 MB for 4096 episodes, 0.85 GB for 65536 -- round 4 kept both for EVERY episode (0.43 GB / 6.9 GB).  A search that
-    // finds the pool exhausted starts over in the wider window (stmpc_stats::pool_exhausted counts them).
-    int pool_cap = c->pool_cap_override > 0 ? c->pool_cap_override : (N / 8 > 256 ? N / 8 : 256);
-    if (pool_cap > N) pool_cap = N;
-    if (pool_cap > (1 << 22)) pool_cap = 1 << 22;            // (the entry number shares a word with the layer)
-    const size_t pool_bytes = (size_t)pool_cap * ((size_t)H * tierW[0] * bp_elem + ckpt_stride);
-    bool resume = !sg && c->resume && prune_on && !small_fan && !stage_tab && nt >= 2 && tierLds[0] && tierLds[1];      // (compiled for the wide-fan kernels only)
-    if (resume && c->pool_bp.cap + c->ckpt.cap < pool_bytes) {
+    // the checkpoint pool: the plan wants it, the device's memory decides
+    bool resume = pl.resume_wanted;
+    if (resume && sv.pool_bp.cap + sv.ckpt.cap < pl.pool_bytes) {
         // a growing request: only while it is at most a quarter of what the device has free right now (a process shared with torch / RCCL).
         // A request that was turned down is priced again every 64th call: memory another tenant held at that moment may be free by now.
-        if (c->resume_refused_for == pool_bytes && (++c->resume_refused_calls & 63) != 0) resume = false;
+        if (sv.resume_refused_for == pl.pool_bytes && (++sv.resume_refused_calls & 63) != 0) resume = false;
         else {
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-            if (pool_bytes > (free_b + c->pool_bp.cap + c->ckpt.cap) / 4) { resume = false; c->resume_refused_for = pool_bytes; }
-            else c->resume_refused_for = 0;
+            if (pl.pool_bytes > (free_b + sv.pool_bp.cap + sv.ckpt.cap) / 4) { resume = false; sv.resume_refused_for = pl.pool_bytes; }
+            else sv.resume_refused_for = 0;
         }
     }
-    const bool resume_wanted = !sg && c->resume && prune_on && !small_fan && !stage_tab && nt >= 2 && tierLds[0] && tierLds[1];
-    // reserved compute units (experiment, STMPC_CU_RESERVE): the first window's persistent grid covers the remaining units only
-    const bool reserve_cfg = c->cu_reserve > 0 && prune_on && nt >= 2 && tierLds[0] && tierLds[1] && !c->two_phase;
-    if (reserve_cfg) tierGrid[0] = tierGrid[0] / c->num_cu * (c->num_cu - c->cu_reserve);
-    for (int k = 0; k < nt; ++k) if (tierGrid[k] > N) tierGrid[k] = N;
     if (resume) {
-        // the pool: if the device cannot spare it, overflowing searches restart in the wider window instead of continuing
-        if (c->pool_bp.ensure((size_t)pool_cap * H * tierW[0] * bp_elem) || c->ckpt.ensure((size_t)pool_cap * ckpt_stride) || c->resume_t.ensure((size_t)N * sizeof(int))) {
+        // if the device cannot spare it, overflowing searches restart in the wider window instead of continuing
+        if (sv.pool_bp.ensure((size_t)pl.pool_cap * H * pl.tier[0].W * pl.bp_elem) || sv.ckpt.ensure((size_t)pl.pool_cap * pl.ckpt_stride) || sv.resume_t.ensure((size_t)N * sizeof(int))) {
             (void)hipGetLastError();
-            c->pool_bp.release(); c->ckpt.release();
+            sv.pool_bp.release(); sv.ckpt.release();
             resume = false;
         }
     }
     for (int k = 0; k < nt; ++k)                 // back-pointers of a tier: per resident workgroup
-        TRY(c->bp_tier[k].ensure((size_t)tierGrid[k] * H * tierW[k] * bp_elem));
-    c->last_resume_refused = resume_wanted && !resume;
-    int *resume_t = resume ? c->resume_t.as<int>() : nullptr;
-    if (need_hbm_tier) TRY(c->gscratch.ensure((size_t)tierGrid[nt - 1] * ((size_t)Wg * STMPC_CELL_BYTES + STMPC_LIST_SLACK + (size_t)Wg * 8)));
+        TRY(sv.bp_tier[k].ensure((size_t)pl.tier[k].grid * H * pl.tier[k].W * pl.bp_elem));
+    sv.last_resume_refused = pl.resume_wanted && !resume;
+    int *resume_t = resume ? sv.resume_t.as<int>() : nullptr;
+    if (pl.need_hbm_tier) TRY(sv.gscratch.ensure((size_t)pl.tier[nt - 1].grid * ((size_t)pl.Wg * STMPC_CELL_BYTES + STMPC_LIST_SLACK + (size_t)pl.Wg * 8)));
 
-    CarTab tab{c->tab_edge.as<double>(), c->tab_win.as<int>(), c->tab_nact.as<int>(), c->tab_nums.as<int>()};
-    unsigned *counters = c->counters.as<unsigned>();
+    CarTab tab{sv.tab_edge.as<double>(), sv.tab_win.as<int>(), sv.tab_nact.as<int>(), sv.tab_nums.as<int>()};
+    unsigned *counters = sv.counters.as<unsigned>();
 
-    hipEvent_t e0 = c->ev0, e1 = c->ev1, e2 = c->ev2, e3 = c->ev3;
-    if (c->profiling) {
-        if (c->pool_used + 4 > c->pool.size()) {
-            for (int i = 0; i < 4; ++i) { hipEvent_t ev; HIPCHK(hipEventCreate(&ev)); c->pool.push_back(ev); }
+    hipEvent_t e0 = sv.ev0, e1 = sv.ev1, e2 = sv.ev2, e3 = sv.ev3;
+    if (sv.profiling) {
+        if (sv.pool_used + 4 > sv.pool.size()) {
+            for (int i = 0; i < 4; ++i) { hipEvent_t ev; HIPCHK(hipEventCreate(&ev)); sv.pool.push_back(ev); }
         }
-        e0 = c->pool[c->pool_used]; e1 = c->pool[c->pool_used + 1]; e2 = c->pool[c->pool_used + 2]; e3 = c->pool[c->pool_used + 3];
-        c->pool_used += 4;
+        e0 = sv.pool[sv.pool_used]; e1 = sv.pool[sv.pool_used + 1]; e2 = sv.pool[sv.pool_used + 2]; e3 = sv.pool[sv.pool_used + 3];
+        sv.pool_used += 4;
     }
-    // second LDS tier started alongside the first (see k_solve): only where overflow is common enough to pay for the
-    // extra launch, and not with the two-phase schedule (its first launch of tier 0 only bounds)
-    // (narrow lattice, round 5: three of 4096 benchmark states overflow the first window; run after the first launch they cost one search's latency,
-    // 0.14 of a 1.0 ms step; alongside it, on a small grid, they are done when it ends -- but a side launch that finds nothing to do costs 40 us of
-    // stream hand-overs, so it is started only when the previous batch on this context overflowed)
-    if (!c->h_overflow) {
-        HIPCHK(hipHostMalloc((void **)&c->h_overflow, 2 * sizeof(int), hipHostMallocMapped)); c->h_overflow[0] = 0; c->h_overflow[1] = 0;
-        HIPCHK(hipHostGetDevicePointer((void **)&c->d_overflow, c->h_overflow, 0));
+    if (!sv.h_overflow) {
+        HIPCHK(hipHostMalloc((void **)&sv.h_overflow, 2 * sizeof(int), hipHostMallocMapped)); sv.h_overflow[0] = 0; sv.h_overflow[1] = 0;
+        HIPCHK(hipHostGetDevicePointer((void **)&sv.d_overflow, sv.h_overflow, 0));
     }
-    const bool overlap_auto = prune_on != 0 || (small_fan && *c->h_overflow > 0);
-    const bool overlap = nt >= 2 && tierLds[1] && !(prune_on && c->two_phase) && N > tierGrid[0] &&
-                         (c->overlap < 0 ? overlap_auto : c->overlap != 0);
-    const int side_grid_auto = c->side_grid > 0 ? c->side_grid : (small_fan ? 32 : 0);
-    const bool reserve = reserve_cfg && overlap;
-    int *queue1 = overlap ? c->lists.as<int>() + (size_t)N : nullptr;
-    const bool split = prune_on && !c->two_phase && c->split && N >= 2 * tierGrid[0];
-    unsigned *proxy0 = split ? c->proxy.as<unsigned>() : nullptr;
-    const bool heavy_first = split && c->heavy_first;
-    if (heavy_first) TRY(c->prio_key.ensure((size_t)N));
-    unsigned char *prio_key = heavy_first ? c->prio_key.as<unsigned char>() : nullptr;
-    const unsigned char *g_tab = nullptr; u16 *g_cells = nullptr; int g_imax = 0, g_D = 0;
-    // band of the bounding pre-pass and the factor of its second attempt, from a parameter set's weights (see SolveArgs::band below)
-    auto band_for = [&](const DevP &d, double *band, double *band2_mult) {
-        const double band_nominal = fmax(1.0, 0.5 * d.v_w * d.v_des * d.v_des);
-        *band = c->band_override > 0 ? c->band_override : (c->band_cap > 0 ? 8.0 * band_nominal : band_nominal);
-        *band2_mult = c->band2_mult > 0 ? c->band2_mult : (c->band_cap > 0 && c->band_override <= 0 ? 4.0 : 5.0);
-        if (c->band2_mult <= 0 && c->band_cap > 0) {
-            const double dv = fmax(d.v_des, d.v_max - d.v_des), da = fmax(fabs(d.a_min), fabs(d.a_max)), dj = fmax(fabs(d.j_min), fabs(d.j_max));
-            const double step_max = d.v_w * dv * dv + d.a_w * da * da + d.j_w * dj * dj;      // dearest single step, penalties aside
-            if (step_max > 0 && *band * *band2_mult > 0.7 * step_max) *band2_mult = fmax(1.0, 0.7 * step_max / *band);
-        }
-    };
+    int *queue1 = pl.overlap ? sv.lists.as<int>() + (size_t)N : nullptr;
+    unsigned *proxy0 = pl.split ? sv.proxy.as<unsigned>() : nullptr;
+    if (pl.heavy_first) TRY(sv.prio_key.ensure((size_t)N));
+    unsigned char *prio_key = pl.heavy_first ? sv.prio_key.as<unsigned char>() : nullptr;
+    Guide guide;
     GroupTab gtab{nullptr, 0};
-    if (sg) {
-        // The groups' table: per group the DevP, the band of its own weights and the offset of its own guide table (one table per distinct
-        // (v_w, a_w, j_w), built on the host and stored one after another).  The device copies are kept while the next call brings an equal table;
-        // replacing them waits for the device first (kernels of earlier calls may still read them).
-        const bool want_guide = prune_on && c->tube_w > 0;
-        for (auto &gp : sg->table) { band_for(gp.p, &gp.band, &gp.band2_mult); gp.guide_off = -1; }
-        const bool same = c->sg.host.size() == sg->table.size() && [&] {
-            for (size_t g = 0; g < sg->table.size(); ++g) {
-                GroupP x = c->sg.host[g]; x.guide_off = -1;
-                if (memcmp(&x, &sg->table[g], sizeof x) != 0) return false;
-            }
-            return true;
-        }();
-        if (!same || c->sg.want_guide != want_guide) {
-            std::vector<unsigned char> all;
-            std::vector<int> built;                          // groups whose table is in `all`
-            bool ok = want_guide;
-            int imax = 0, D = 0;
-            for (size_t g = 0; g < sg->table.size() && ok; ++g) {
-                GroupP &gp = sg->table[g];
-                for (int b : built)
-                    if (sg->table[b].p.v_w == gp.p.v_w && sg->table[b].p.a_w == gp.p.a_w && sg->table[b].p.j_w == gp.p.j_w) { gp.guide_off = sg->table[b].guide_off; break; }
-                if (gp.guide_off >= 0) continue;
-                std::vector<unsigned char> one;
-                ok = build_guide_table(gp.p, one, imax, D);
-                if (!ok) break;
-                gp.guide_off = (long long)all.size();
-                all.insert(all.end(), one.begin(), one.end());
-                built.push_back((int)g);
-            }
-            if (!ok) for (auto &gp : sg->table) gp.guide_off = 0;
-            HIPCHK(hipDeviceSynchronize());
-            c->sg.host.clear();
-            TRY(upload(c->sg.table, sg->table.data(), sg->table.size()));
-            if (ok) TRY(upload(c->sg.guide, all.data(), all.size()));
-            c->sg.want_guide = want_guide; c->sg.guide_ok = ok; c->sg.guide_imax = imax; c->sg.guide_D = D;
-            c->sg.host = sg->table;
-        }
-        gtab.groups = c->sg.table.as<GroupP>(); gtab.n_per_group = sg->n_per_group;
-        if (want_guide && c->sg.guide_ok) {
-            TRY(c->guide_cells.ensure((size_t)N * H * sizeof(u16)));
-            g_tab = c->sg.guide.as<unsigned char>(); g_cells = c->guide_cells.as<u16>(); g_imax = c->sg.guide_imax; g_D = c->sg.guide_D;
-        }
-    } else if (prune_on && c->tube_w > 0) {
-        // guided bounding attempt: the table depends on the dynamics and the cost weights only; rebuilt when they change (a few ms on the host)
-        const double key[12] = {dp.ds, dp.dt, dp.v_w, dp.a_w, dp.j_w, dp.v_des, dp.v_max, dp.a_min, dp.a_max, dp.j_min, dp.j_max, (double)H};
-        stmpc_ctx::GuideSlot *slot = nullptr;
-        for (auto &g : c->guides) if (g.valid && memcmp(key, g.key, sizeof key) == 0) { slot = &g; break; }
-        if (!slot) {
-            // A parameter set not seen before (or replaced since): build its table on the host (a few ms) and queue the upload on THIS call's
-            // stream, ahead of the kernels that read it.  Nothing waits for the device unless a table has to be replaced (a fifth parameter set):
-            // kernels of earlier calls may still read the one that goes.
-            for (auto &g : c->guides) if (!g.valid) { slot = &g; break; }
-            if (!slot) {
-                slot = &c->guides[0];
-                for (auto &g : c->guides) if (g.last_use < slot->last_use) slot = &g;
-                slot->valid = false;
-                HIPCHK(hipDeviceSynchronize());
-            }
-            slot->ok = build_guide_table(dp, slot->host, slot->imax, slot->D);
-            if (slot->ok) {
-                TRY(slot->dev.ensure(slot->host.size()));
-                HIPCHK(hipMemcpyAsync(slot->dev.p, slot->host.data(), slot->host.size(), hipMemcpyHostToDevice, st));
-            }
-            memcpy(slot->key, key, sizeof key);
-            slot->valid = true;                 // (only after the upload has been queued successfully)
-        }
-        slot->last_use = ++c->guide_clock;
-        if (slot->ok) { TRY(c->guide_cells.ensure((size_t)N * H * sizeof(u16))); g_tab = slot->dev.as<unsigned char>(); g_cells = c->guide_cells.as<u16>(); g_imax = slot->imax; g_D = slot->D; }
-    }
+    if (sg) TRY(guide_for_groups(sv, pl, sg, &gtab, &guide));
+    else if (pl.guided) TRY(guide_for_params(sv, dp, st, &guide));
+    u16 *g_cells = nullptr;
+    if (guide.tab) { TRY(sv.guide_cells.ensure((size_t)N * H * sizeof(u16))); g_cells = sv.guide_cells.as<u16>(); }
     HIPCHK(hipEventRecord(e0, st));
     with_kmax(Kalloc, [&](auto km) {
-        if (sg) launch_predict_groups<decltype(km)::value>(dp, gtab, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, c->ubound.as<u64>(), queue1, proxy0, resume_t,
-                                                           prio_key, st, c->sticky.as<unsigned>(), g_tab, g_imax, g_D, g_cells);
-        else launch_predict<decltype(km)::value>(dp, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, c->ubound.as<u64>(), queue1, proxy0, resume_t, prio_key, st,
-                                                 c->sticky.as<unsigned>(), g_tab, g_imax, g_D, g_cells);
+        if (sg) launch_predict_groups<decltype(km)::value>(dp, gtab, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, sv.ubound.as<u64>(), queue1, proxy0, resume_t,
+                                                           prio_key, st, c->sticky.as<unsigned>(), guide.tab, guide.imax, guide.D, g_cells);
+        else launch_predict<decltype(km)::value>(dp, N, Kalloc, d_ego, d_k, d_ox, d_ov, tab, counters, sv.ubound.as<u64>(), queue1, proxy0, resume_t, prio_key, st,
+                                                 c->sticky.as<unsigned>(), guide.tab, guide.imax, guide.D, g_cells);
     });
 
     SolveArgs a;
     memset(&a, 0, sizeof a);
     a.p = dp; a.N = N; a.Kmax = Kalloc;
     a.ego = d_ego; a.tab = tab;
-    a.counters = counters; a.lists = c->lists.as<int>(); a.ubound = c->ubound.as<u64>();
-    a.prune = prune_on;
-    // band of the bounding pre-pass.  Nominal: half the per-step cost of standing still (225 with the reference's
-    // weights).  With the node cap (default) the pass starts from 8x that and narrows the band whenever a layer expands
-    // more than band_cap nodes (dp_pass): wide where few alternatives exist, beam-like where many do -- 15 % fewer
-    // expanded nodes in total than the best fixed band (sweeps on the H=40 workload: fixed 60..1200, capped 225..8000 x
-    // 150..550).  Any value is safe (the exact pass re-checks); it only trades pre-pass work for tightness of the bound.
-    band_for(dp, &a.band, &a.band2_mult);
-    // second attempt (penalty zone allowed): a wider band, but kept well below the cost of one worst-case step
-    // (j_w * j_max^2 ~ 12 k on the benchmark lattice): a band that admits those steps keeps everything, and single
-    // episodes then take several times longer (measured cliff at 44x the nominal band; 32x is used)
-    a.band_cap = c->band_cap;
-    for (int i = 0; i < 3; ++i) a.retry_mult[i] = c->retry_mult[i];
-    a.bound_infl = c->bound_infl; a.last_infl = c->last_infl;
-    a.guide = g_cells; a.tube_w = c->tube_w; a.tube_dense = c->tube_dense; a.band_dense = c->band_dense;
-    a.retry_move = resume ? c->retry_move : 0;
-    a.prio_thr = c->prio_thr; a.prio_mode = c->prio_mode;
-    a.bp_rel8 = bp_rel8 ? 1 : 0;
-    a.force_general = c->force_general ? 1 : 0;
-    a.gsh_max = c->gsh_max;
-    a.zl_dt = c->fd2_zl[0]; a.zl_dt2 = c->fd2_zl[1]; a.zl_dt3 = c->fd2_zl[2];
+    a.counters = counters; a.lists = sv.lists.as<int>(); a.ubound = sv.ubound.as<u64>();
+    a.prune = pl.prune_on;
+    a.band = pl.band; a.band2_mult = pl.band2_mult;
+    a.band_cap = pl.k.band_cap;
+    for (int i = 0; i < 3; ++i) a.retry_mult[i] = pl.k.retry_mult[i];
+    a.bound_infl = pl.k.bound_infl; a.last_infl = pl.k.last_infl;
+    a.guide = g_cells; a.tube_w = pl.k.tube_w; a.tube_dense = pl.k.tube_dense; a.band_dense = pl.k.band_dense;
+    a.retry_move = resume ? pl.k.retry_move : 0;
+    a.prio_thr = pl.k.prio_thr; a.prio_mode = pl.k.prio_mode;
+    a.bp_rel8 = pl.bp_rel8 ? 1 : 0;
+    a.force_general = pl.k.force_general ? 1 : 0;
+    a.gsh_max = pl.k.gsh_max;
+    a.zl_dt = sv.fd2_zl[0]; a.zl_dt2 = sv.fd2_zl[1]; a.zl_dt3 = sv.fd2_zl[2];
 #ifdef STMPC_PHASE_PROF
-    TRY(c->phase_prof.ensure(4 * STMPC_NPH * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(c->phase_prof.p, 0, 4 * STMPC_NPH * sizeof(unsigned long long), st));
-    a.phase_prof = c->phase_prof.as<unsigned long long>();
+    TRY(sv.phase_prof.ensure(4 * STMPC_NPH * sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(sv.phase_prof.p, 0, 4 * STMPC_NPH * sizeof(unsigned long long), st));
+    a.phase_prof = sv.phase_prof.as<unsigned long long>();
 #endif
-    a.ckpt = resume ? c->ckpt.as<unsigned char>() : nullptr; a.ckpt_stride = ckpt_stride; a.resume_t = resume_t;
-    a.pool_bp = resume ? c->pool_bp.as<unsigned char>() : nullptr; a.pool_cap = resume ? pool_cap : 0;
-    a.W0 = tierW[0];
-    a.maxshift = (int)ceil(dp.v_max * dp.dt / dp.ds) + 2 + 66;     // st_cy.pyx:65-93: v <= v_max; + interval rounding to 64-cell blocks
-    a.proxy = c->proxy.as<unsigned>();
-    const bool two_phase = a.prune && c->two_phase;      // bound all episodes first, then solve them heaviest-first
+    a.ckpt = resume ? sv.ckpt.as<unsigned char>() : nullptr; a.ckpt_stride = pl.ckpt_stride; a.resume_t = resume_t;
+    a.pool_bp = resume ? sv.pool_bp.as<unsigned char>() : nullptr; a.pool_cap = resume ? pl.pool_cap : 0;
+    a.W0 = pl.tier[0].W;
+    a.maxshift = pl.maxshift;
+    a.proxy = sv.proxy.as<unsigned>();
     a.path_idx = d_path; a.best_t = d_bt; a.cost = d_cost; a.path_dist = d_pd; a.crash = d_crash; a.action_cost = d_action_cost;
-    a.host_overflow = c->d_overflow;
-
-    if (overlap && split && c->retire_cus > 0 && c->retire_cus < c->num_cu) {
-        TRY(c->cu_tab.ensure(1025 * sizeof(unsigned)));
-        HIPCHK(hipMemsetAsync(c->cu_tab.p, 0, 1025 * sizeof(unsigned), st));
-        a.cu_tab = c->cu_tab.as<unsigned>(); a.retire_from = c->num_cu - c->retire_cus; a.retire_left = (long long)N * c->retire_at / 100;
+    a.host_overflow = sv.d_overflow;
+    if (pl.retire) {
+        TRY(sv.cu_tab.ensure(1025 * sizeof(unsigned)));
+        HIPCHK(hipMemsetAsync(sv.cu_tab.p, 0, 1025 * sizeof(unsigned), st));
+        a.cu_tab = sv.cu_tab.as<unsigned>(); a.retire_from = pl.retire_from; a.retire_left = pl.retire_left;
     }
     HIPCHK(hipEventRecord(e1, st));
-    if (overlap) HIPCHK(hipEventRecord(c->ev_fork, st));      // the vehicle table and the preset queue are ready
+    if (pl.overlap) HIPCHK(hipEventRecord(sv.ev_fork, st));      // the vehicle table and the preset queue are ready
 
-    // one launch of tier k: phase 0 = bound + exact, 1 = bounding pre-passes only, 2 = exact with the stored bounds;
-    // side = on the side stream, consuming tier 0's overflow queue while tier 0 is still running
-    auto launch_tier = [&](int k, int phase, bool side, bool on_reserved = false) -> int {
-        hipStream_t lst = side ? (on_reserved ? c->aux_reserved : c->aux_stream) : ((reserve && k == 0) ? c->main_masked : st);
-        a.concurrent = side ? 1 : 0;
-        a.always_wait = on_reserved ? 1 : 0;
-        a.split = (split && k == 0) ? 1 : 0;
-        a.feeds_concurrent = (overlap && k == 0) ? 1 : 0;
-        a.prev_grid = side ? tierGrid[0] : 0;
-        a.wait_ticks = side ? 20000000ull : 0ull;             // 0.2 s of the 100 MHz clock
-        a.phase = phase;
-        a.order = ((phase == 2 || heavy_first) && k == 0) ? c->order.as<int>() : nullptr;
-        a.W = tierW[k]; a.PW = tierPW[k]; a.tier = k; a.last_tier = (k == nt - 1);
-        a.bp = c->bp_tier[k].as<u16>();
-        a.gscratch = tierLds[k] ? nullptr : c->gscratch.as<unsigned char>();
-        const size_t lds = tierLdsBytes[k];
-        const bool std_shape = tierNW[k] == 4 && tierW[k] == 2048 && tierPW[k] == 1024;      // the kernels compiled with these as constants
-        const bool std_shape2 = tierNW[k] == 8 && tierW[k] == 8192 && tierPW[k] == 4096;
-        const int side_g = (side && !on_reserved && side_grid_auto > 0 && side_grid_auto < tierGrid[k]) ? side_grid_auto : tierGrid[k];
-        const dim3 grid(on_reserved ? (tierGrid[k] / c->num_cu > 0 ? tierGrid[k] / c->num_cu : 1) * c->cu_reserve : side_g), block(64 * tierNW[k]);
-#ifndef STMPC_FAN1
-#define STMPC_FAN1 8        /* candidate slots per barrier pair of the wide-lattice kernels outside the standard second window (128 VGPRs); 7 / 11 / 12 measured in round 5, 12 again in round 6 */
-#endif
-        if (sg) {
-            // the grouped family: first window in its standard shape, any other LDS window and the HBM window in the general shape
-            SolveArgsG ag;
-            memset(&ag, 0, sizeof ag);
-            static_cast<SolveArgs &>(ag) = a;
-            ag.g = gtab;
-#define STMPC_LAUNCH_G(L, FD, FM, SG, NWX_)                                                                   \
-            do {                                                                                              \
-                if (lds > 48 * 1024)                                                                          \
-                    HIPCHK(hipFuncSetAttribute((const void *)grouped::k_solve<L, false, FD, 0, FM, SG, 0, NWX_>, \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
-                hipLaunchKernelGGL((grouped::k_solve<L, false, FD, 0, FM, SG, 0, NWX_>), grid, block, lds, lst, ag); \
-            } while (0)
-#define STMPC_LAUNCH_GS(FD, FM)                                                                               \
-            do {                                                                                              \
-                if (!tierLds[k]) STMPC_LAUNCH_G(false, false, FM, true, STMPC_MAXWAVES);                      \
-                else if (a.last_tier) STMPC_LAUNCH_G(true, FD, FM, true, STMPC_MAXWAVES);                     \
-                else if (std_shape) STMPC_LAUNCH_G(true, FD, FM, false, 4);                                   \
-                else STMPC_LAUNCH_G(true, FD, FM, false, STMPC_MAXWAVES);                                     \
-            } while (0)
-            if (small_fan) { if (fastdiv) STMPC_LAUNCH_GS(true, 9); else STMPC_LAUNCH_GS(false, 9); }
-            else { if (fastdiv) STMPC_LAUNCH_GS(true, STMPC_FAN1); else STMPC_LAUNCH_GS(false, STMPC_FAN1); }
-#undef STMPC_LAUNCH_GS
-#undef STMPC_LAUNCH_G
-            return STMPC_OK;
+    // the schedule, step by step: wait, launch, record
+    auto stream_of = [&](plan::Stream s) { return s == plan::Stream::Side ? sv.aux_stream : s == plan::Stream::Masked ? sv.main_masked : s == plan::Stream::Reserved ? sv.aux_reserved : st; };
+    auto event_of = [&](plan::Event e) { return e == plan::Event::Fork ? sv.ev_fork : e == plan::Event::Join ? sv.ev_join : e == plan::Event::Join0 ? sv.ev_join0 : e == plan::Event::JoinR ? sv.ev_join_r : e2; };
+    for (int i = 0; i < pl.n_steps; ++i) {
+        const plan::PlanStep &s = pl.steps[i];
+        hipStream_t lst = stream_of(s.stream);
+        if (s.wait != plan::Event::None) HIPCHK(hipStreamWaitEvent(lst, event_of(s.wait), 0));
+        if (s.op == plan::Op::Order8) hipLaunchKernelGGL(k_order8, dim3(1), dim3(1024), 0, lst, N, (const unsigned char *)prio_key, sv.order.as<int>());
+        else if (s.op == plan::Op::Order) hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, lst, N, (const unsigned *)sv.proxy.as<unsigned>(), sv.order.as<int>());
+        else if (s.op == plan::Op::Solve) {
+            // side = on the side (or reserved) stream, consuming tier 0's overflow queue while tier 0 is still running
+            const plan::PlanTier &t = pl.tier[s.tier];
+            const bool side = s.stream == plan::Stream::Side || s.stream == plan::Stream::Reserved;
+            a.concurrent = side ? 1 : 0;
+            a.always_wait = s.stream == plan::Stream::Reserved ? 1 : 0;
+            a.split = (pl.split && s.tier == 0) ? 1 : 0;
+            a.feeds_concurrent = (pl.overlap && s.tier == 0) ? 1 : 0;
+            a.prev_grid = side ? pl.tier[0].grid : 0;
+            a.wait_ticks = side ? 20000000ull : 0ull;             // 0.2 s of the 100 MHz clock
+            a.phase = s.phase;
+            a.order = ((s.phase == 2 || pl.heavy_first) && s.tier == 0) ? sv.order.as<int>() : nullptr;
+            a.W = t.W; a.PW = t.PW; a.tier = s.tier; a.last_tier = (s.tier == nt - 1);
+            a.bp = sv.bp_tier[s.tier].as<u16>();
+            a.gscratch = t.lds ? nullptr : sv.gscratch.as<unsigned char>();
+            TRY(launch_k_solve(resume ? t.variant_resume : t.variant, dim3(s.grid), dim3(64 * t.waves), t.lds_bytes, lst, a, sg ? &gtab : nullptr));
         }
-#define STMPC_LAUNCH_R(L, FD, KT_, FM, SG, RS)                                                                \
-        do {                                                                                                  \
-            if (lds > 48 * 1024)                                                                              \
-                HIPCHK(hipFuncSetAttribute((const void *)k_solve<L, false, FD, KT_, FM, SG, RS>,              \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
-            hipLaunchKernelGGL((k_solve<L, false, FD, KT_, FM, SG, RS>), grid, block, lds, lst, a);           \
-        } while (0)
-        // (the first window's four-wave workgroups: list segments searched with 3 compares instead of 7)
-#define STMPC_LAUNCH_R4(L, FD, KT_, FM, SG, RS)                                                               \
-        do {                                                                                                  \
-            if (lds > 48 * 1024)                                                                              \
-                HIPCHK(hipFuncSetAttribute((const void *)k_solve<L, false, FD, KT_, FM, SG, RS, 4>,           \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
-            hipLaunchKernelGGL((k_solve<L, false, FD, KT_, FM, SG, RS, 4>), grid, block, lds, lst, a);        \
-        } while (0)
-#define STMPC_LAUNCH_R88(L, FD, KT_, FM, SG, RS)                                                              \
-        do {                                                                                                  \
-            if (lds > 48 * 1024)                                                                              \
-                HIPCHK(hipFuncSetAttribute((const void *)k_solve<L, false, FD, KT_, FM, SG, RS, 88>,          \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
-            hipLaunchKernelGGL((k_solve<L, false, FD, KT_, FM, SG, RS, 88>), grid, block, lds, lst, a);       \
-        } while (0)
-#ifndef STMPC_FAN88
-#define STMPC_FAN88 24      /* candidate slots per barrier pair in the standard second window (it has the registers: 256 VGPRs); 12 / 16 / 21 / 24 measured, EXPERIMENTS.md */
-#endif
-#define STMPC_LAUNCH_R0(L, FD, KT_, FM, SG)                                                                   \
-        do {                                                                                                  \
-            if constexpr (L) { if (std_shape) STMPC_LAUNCH_R4(L, FD, KT_, FM, SG, 0); else STMPC_LAUNCH_R(L, FD, KT_, FM, SG, 0); } \
-            else STMPC_LAUNCH_R(L, FD, KT_, FM, SG, 0);                                                       \
-        } while (0)
-        // checkpointing variants only where they are used: the first window saves, the second continues
-#define STMPC_LAUNCH_S(L, FD, KT_, FM, SG)                                                                    \
-        do {                                                                                                  \
-            if constexpr (L && FM == STMPC_FAN1 && KT_ == 0) {                                                        \
-                if (resume && k == 0 && std_shape) STMPC_LAUNCH_R4(L, FD, KT_, FM, SG, 1);               \
-                else if (resume && k == 0) STMPC_LAUNCH_R(L, FD, KT_, FM, SG, 1);                             \
-                else if (resume && k == 1 && std_shape2) STMPC_LAUNCH_R88(L, FD, KT_, STMPC_FAN88, SG, 2);    \
-                else if (resume && k == 1) STMPC_LAUNCH_R(L, FD, KT_, FM, SG, 2);                             \
-                else STMPC_LAUNCH_R0(L, FD, KT_, FM, SG);                                                     \
-            } else STMPC_LAUNCH_R0(L, FD, KT_, FM, SG);                                                       \
-        } while (0)
-        // only the last tier carries the general lattice-coordinate form (see solve_episode)
-#define STMPC_LAUNCH(L, FD, KT_, FM) do { if (a.last_tier) STMPC_LAUNCH_S(L, FD, KT_, FM, true); else STMPC_LAUNCH_S(L, FD, KT_, FM, false); } while (0)
-#define STMPC_LAUNCH_FM(L, FD, KT_) do { if (small_fan) STMPC_LAUNCH(L, FD, KT_, 9); else STMPC_LAUNCH(L, FD, KT_, STMPC_FAN1); } while (0)
-        if (tierLds[k]) {
-            if (stage_tab) { if (fastdiv) STMPC_LAUNCH_FM(true, true, 8); else STMPC_LAUNCH_FM(true, false, 8); }
-            else { if (fastdiv) STMPC_LAUNCH_FM(true, true, 0); else STMPC_LAUNCH_FM(true, false, 0); }
-        } else {
-            if (fastdiv) STMPC_LAUNCH_FM(false, true, 0); else STMPC_LAUNCH_FM(false, false, 0);
-        }
-#undef STMPC_LAUNCH_FM
-#undef STMPC_LAUNCH
-#undef STMPC_LAUNCH_S
-#undef STMPC_LAUNCH_R
-#undef STMPC_LAUNCH_R4
-#undef STMPC_LAUNCH_R88
-#undef STMPC_LAUNCH_R0
-        return STMPC_OK;
-    };
-
-    if (heavy_first) hipLaunchKernelGGL(k_order8, dim3(1), dim3(1024), 0, st, N, (const unsigned char *)prio_key, c->order.as<int>());
-    if (two_phase) {                                           // bound every episode, order them heaviest-first
-        TRY(launch_tier(0, 1, false));
-        hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, N, (const unsigned *)c->proxy.as<unsigned>(), c->order.as<int>());
-    }
-    for (int k = 0; k < nt; ++k) {
-        if (reserve && k == 0) HIPCHK(hipStreamWaitEvent(c->main_masked, c->ev_fork, 0));
-        TRY(launch_tier(k, two_phase ? 2 : 0, false));
-        if (reserve && k == 0) {
-            // the reserved units host second-window workgroups from the start of the step; the masked streams partition the device, so
-            // these consumers may always wait for the queue (they cannot be holding a unit a producer needs)
-            HIPCHK(hipEventRecord(c->ev_join0, c->main_masked));
-            HIPCHK(hipStreamWaitEvent(c->aux_reserved, c->ev_fork, 0));
-            TRY(launch_tier(1, 0, true, true));
-            HIPCHK(hipEventRecord(c->ev_join_r, c->aux_reserved));
-            HIPCHK(hipStreamWaitEvent(st, c->ev_join0, 0));
-            HIPCHK(hipStreamWaitEvent(st, c->ev_join_r, 0));
-        }
-        if (overlap && k == 0) {
-            // tier 1 alongside tier 0: queued on the side stream behind the predictor only; its workgroups start when
-            // tier 0's persistent workgroups begin to leave CUs.  The main stream then waits for it, and the ordinary
-            // launch of tier 1 that follows picks up whatever it left (normally nothing).
-            HIPCHK(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-            TRY(launch_tier(1, 0, true));
-            HIPCHK(hipEventRecord(c->ev_join, c->aux_stream));
-            HIPCHK(hipStreamWaitEvent(st, c->ev_join, 0));
-        }
-        if ((need_hbm_tier && k == nt - 2) || (!need_hbm_tier && k == nt - 1) || nt == 1) HIPCHK(hipEventRecord(e2, st));   // after the last LDS tier
+        if (s.record != plan::Event::None) HIPCHK(hipEventRecord(event_of(s.record), lst));
     }
     HIPCHK(hipEventRecord(e3, st));
     HIPCHK(hipGetLastError());
     c->stats.episodes = N;
-    c->last_nt = nt; c->last_has_hbm = need_hbm_tier;
-    c->stats_pending = !c->profiling;
-    if (c->profiling) { c->acc_launches += 1; c->acc_episodes += N; }
+    sv.last_nt = nt; sv.last_has_hbm = pl.need_hbm_tier;
+    c->stats_pending = !sv.profiling;
+    if (sv.profiling) { sv.acc_launches += 1; sv.acc_episodes += N; }
     return STMPC_OK;
 }
 
@@ -1295,25 +1036,25 @@ int stmpc_get_stats(stmpc_ctx *c, stmpc_stats *out) {
     if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(c->device));
     if (c->stats_pending) {
-        HIPCHK(hipEventSynchronize(c->ev3));
+        HIPCHK(hipEventSynchronize(c->solver.ev3));
         unsigned cnt[64];
-        HIPCHK(hipMemcpy(cnt, c->counters.p, sizeof cnt, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cnt, c->solver.counters.p, sizeof cnt, hipMemcpyDeviceToHost));
         float ms_all = 0.f, ms_dp = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms_all, c->ev0, c->ev3));
-        HIPCHK(hipEventElapsedTime(&ms_dp, c->ev1, c->ev2));
+        HIPCHK(hipEventElapsedTime(&ms_all, c->solver.ev0, c->solver.ev3));
+        HIPCHK(hipEventElapsedTime(&ms_dp, c->solver.ev1, c->solver.ev2));
 #ifdef STMPC_PHASE_PROF
         if (const char *f = getenv("STMPC_PHASE_DUMP")) {
             unsigned long long pp[4 * STMPC_NPH];
-            HIPCHK(hipMemcpy(pp, c->phase_prof.p, sizeof pp, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(pp, c->solver.phase_prof.p, sizeof pp, hipMemcpyDeviceToHost));
             FILE *fp = fopen(f, "w");
             if (fp) { for (int m = 0; m < 4; ++m) { for (int k = 0; k < STMPC_NPH; ++k) fprintf(fp, "%llu ", pp[m * STMPC_NPH + k]); fprintf(fp, "\n"); } fclose(fp); }
         }
 #endif
         c->stats.fallback = cnt[4];                       // episodes that overflowed the first LDS window
-        c->stats.hbm_tier = (c->last_has_hbm && c->last_nt >= 2) ? cnt[4 * (c->last_nt - 1)] : 0;
+        c->stats.hbm_tier = (c->solver.last_has_hbm && c->solver.last_nt >= 2) ? cnt[4 * (c->solver.last_nt - 1)] : 0;
         c->stats.fast_path = c->stats.episodes - cnt[4];
-        c->last_hbm_tier_count = c->stats.hbm_tier;
-        c->stats.resume_refused = c->last_resume_refused ? 1 : 0;
+        c->solver.last_hbm_tier_count = c->stats.hbm_tier;
+        c->stats.resume_refused = c->solver.last_resume_refused ? 1 : 0;
         c->stats.pool_exhausted = cnt[STMPC_CNT_POOL_FULL];
         c->stats.retries = cnt[STMPC_CNT_RETRY];
         c->stats.guided = cnt[STMPC_CNT_GUIDED];
@@ -1324,7 +1065,7 @@ int stmpc_get_stats(stmpc_ctx *c, stmpc_stats *out) {
         c->stats_pending = false;
         if (cnt[STMPC_CNT_ERR]) {
             // reported here, once: cleared so that the next k_predict does not latch it again and blame a later batch
-            HIPCHK(hipMemset((unsigned *)c->counters.p + STMPC_CNT_ERR, 0, sizeof(unsigned)));
+            HIPCHK(hipMemset((unsigned *)c->solver.counters.p + STMPC_CNT_ERR, 0, sizeof(unsigned)));
             *out = c->stats;
             return fail(STMPC_EINTERNAL, "solver error flag set on device");
         }
@@ -1337,23 +1078,23 @@ int stmpc_profile(stmpc_ctx *c, int enable, stmpc_profile_totals *out) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     HIPCHK(hipSetDevice(c->device));
     if (enable) {
-        c->profiling = true; c->pool_used = 0;
-        c->acc_solve_ms = c->acc_dp_ms = 0; c->acc_launches = c->acc_fallback = c->acc_episodes = 0;
+        c->solver.profiling = true; c->solver.pool_used = 0;
+        c->solver.acc_solve_ms = c->solver.acc_dp_ms = 0; c->solver.acc_launches = c->solver.acc_fallback = c->solver.acc_episodes = 0;
         return STMPC_OK;
     }
     // disable: drain the pool
-    for (size_t i = 0; i + 3 < c->pool_used; i += 4) {
-        HIPCHK(hipEventSynchronize(c->pool[i + 3]));
+    for (size_t i = 0; i + 3 < c->solver.pool_used; i += 4) {
+        HIPCHK(hipEventSynchronize(c->solver.pool[i + 3]));
         float a = 0.f, b = 0.f;
-        HIPCHK(hipEventElapsedTime(&a, c->pool[i], c->pool[i + 3]));
-        HIPCHK(hipEventElapsedTime(&b, c->pool[i + 1], c->pool[i + 2]));
-        c->acc_solve_ms += a; c->acc_dp_ms += b;
+        HIPCHK(hipEventElapsedTime(&a, c->solver.pool[i], c->solver.pool[i + 3]));
+        HIPCHK(hipEventElapsedTime(&b, c->solver.pool[i + 1], c->solver.pool[i + 2]));
+        c->solver.acc_solve_ms += a; c->solver.acc_dp_ms += b;
     }
-    c->pool_used = 0;
-    c->profiling = false;
+    c->solver.pool_used = 0;
+    c->solver.profiling = false;
     if (out) {
-        out->launches = c->acc_launches; out->episodes = c->acc_episodes;
-        out->solve_ms = c->acc_solve_ms; out->dp_kernel_ms = c->acc_dp_ms;
+        out->launches = c->solver.acc_launches; out->episodes = c->solver.acc_episodes;
+        out->solve_ms = c->solver.acc_solve_ms; out->dp_kernel_ms = c->solver.acc_dp_ms;
     }
     return STMPC_OK;
 }
@@ -1400,30 +1141,30 @@ int stmpc_solve_grid(stmpc_ctx *c, const uint8_t *obstacles, const double *s_val
     auto &s = c->s;
     const size_t cells = (size_t)H * S;
     TRY(s.misc3.ensure((size_t)H * 8));
-    TRY(c->counters.ensure(64 * sizeof(unsigned)));
-    const int Wg = next_pow2(S + 2 + 128);
-    TRY(c->gscratch.ensure((size_t)Wg * STMPC_CELL_BYTES + STMPC_LIST_SLACK + (size_t)Wg * 8));
-    TRY(c->bp_tier[STMPC_MAX_TIERS - 1].ensure((size_t)H * Wg * sizeof(u16)));
+    TRY(c->solver.counters.ensure(64 * sizeof(unsigned)));
+    const int Wg = plan::next_pow2(S + 2 + 128);
+    TRY(c->solver.gscratch.ensure((size_t)Wg * STMPC_CELL_BYTES + STMPC_LIST_SLACK + (size_t)Wg * 8));
+    TRY(c->solver.bp_tier[STMPC_MAX_TIERS - 1].ensure((size_t)H * Wg * sizeof(u16)));
     TRY(upload(s.misc0, obstacles, cells)); TRY(upload(s.misc1, distances, cells)); TRY(upload(s.misc2, s_values, (size_t)S));
     TRY(latch_solver_error(c));          // an earlier asynchronous call's flag survives the reset below
-    HIPCHK(hipMemset(c->counters.p, 0, 64 * sizeof(unsigned)));
+    HIPCHK(hipMemset(c->solver.counters.p, 0, 64 * sizeof(unsigned)));
     SolveArgs a;
     memset(&a, 0, sizeof a);
     a.p = dp; a.N = 1; a.Kmax = 1; a.W = Wg; a.PW = Wg; a.last_tier = 1;
-    for (int i = 0; i < 3; ++i) a.retry_mult[i] = c->retry_mult[i];
-    a.bound_infl = c->bound_infl; a.last_infl = c->last_infl;
+    for (int i = 0; i < 3; ++i) a.retry_mult[i] = c->solver.knobs.retry_mult[i];
+    a.bound_infl = c->solver.knobs.bound_infl; a.last_infl = c->solver.knobs.last_infl;
     a.obstacles = s.misc0.as<uint8_t>(); a.distances = s.misc1.as<double>(); a.s_values = s.misc2.as<double>();
-    a.S_grid = S; a.v0_grid = v0; a.a0_grid = a0; a.gsh_max = c->gsh_max;
-    a.bp = c->bp_tier[STMPC_MAX_TIERS - 1].as<u16>(); a.gscratch = c->gscratch.as<unsigned char>(); a.counters = c->counters.as<unsigned>();
+    a.S_grid = S; a.v0_grid = v0; a.a0_grid = a0; a.gsh_max = c->solver.knobs.gsh_max;
+    a.bp = c->solver.bp_tier[STMPC_MAX_TIERS - 1].as<u16>(); a.gscratch = c->solver.gscratch.as<unsigned char>(); a.counters = c->solver.counters.as<unsigned>();
     a.s_sequence = s.misc3.as<double>();
     hipLaunchKernelGGL((k_solve<false, true, false, 0, 16, true>), dim3(1), dim3(256), ((stmpc_chunk_ints(Wg) * sizeof(int) + 15) & ~(size_t)15) + 16, nullptr, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     TRY(download(s_sequence_out, s.misc3, (size_t)H));
     unsigned cnt[64];
-    HIPCHK(hipMemcpy(cnt, c->counters.p, sizeof cnt, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cnt, c->solver.counters.p, sizeof cnt, hipMemcpyDeviceToHost));
     if (cnt[STMPC_CNT_ERR]) {
-        HIPCHK(hipMemset((unsigned *)c->counters.p + STMPC_CNT_ERR, 0, sizeof(unsigned)));
+        HIPCHK(hipMemset((unsigned *)c->solver.counters.p + STMPC_CNT_ERR, 0, sizeof(unsigned)));
         return fail(STMPC_EINTERNAL, "grid solver reported a window overflow");
     }
     return STMPC_OK;
@@ -1443,17 +1184,17 @@ int stmpc_build_grid(stmpc_ctx *c, const stmpc_params *p, const double *state5, 
     if (S < 2 || S > STMPC_S_LIMIT) return fail(STMPC_EINVAL, "number of position cells out of range");
     const int Kalloc = k > 0 ? k : 1;
     auto &s = c->s;
-    TRY(c->tab_edge.ensure((size_t)H * Kalloc * 2 * 8));
-    TRY(c->tab_win.ensure((size_t)H * Kalloc * 2 * 4));
-    TRY(c->tab_nact.ensure((size_t)H * 4));
-    TRY(c->tab_nums.ensure(4));
-    TRY(c->counters.ensure(64 * sizeof(unsigned)));
+    TRY(c->solver.tab_edge.ensure((size_t)H * Kalloc * 2 * 8));
+    TRY(c->solver.tab_win.ensure((size_t)H * Kalloc * 2 * 4));
+    TRY(c->solver.tab_nact.ensure((size_t)H * 4));
+    TRY(c->solver.tab_nums.ensure(4));
+    TRY(c->solver.counters.ensure(64 * sizeof(unsigned)));
     const size_t cells = (size_t)H * S;
     TRY(s.misc0.ensure(cells)); TRY(s.misc1.ensure(cells * 8)); TRY(s.misc2.ensure((size_t)S * 8));
     const int32_t kk = k;
     TRY(s.states(1, k, state5, 5, &kk, ox, ov));
-    CarTab tab{c->tab_edge.as<double>(), c->tab_win.as<int>(), c->tab_nact.as<int>(), c->tab_nums.as<int>()};
-    unsigned *counters = c->counters.as<unsigned>();
+    CarTab tab{c->solver.tab_edge.as<double>(), c->solver.tab_win.as<int>(), c->solver.tab_nact.as<int>(), c->solver.tab_nums.as<int>()};
+    unsigned *counters = c->solver.counters.as<unsigned>();
     with_kmax(Kalloc, [&](auto km) {
         launch_predict<decltype(km)::value>(dp, 1, Kalloc, s.ego.as<double>(), s.k.as<int>(), s.ox.as<double>(), s.ov.as<double>(), tab, counters, nullptr, nullptr,
                                             nullptr, nullptr, nullptr, nullptr, c->sticky.as<unsigned>());
@@ -1481,10 +1222,10 @@ int stmpc_check_error(stmpc_ctx *c) {
     HIPCHK(hipDeviceSynchronize());
     unsigned flags[3] = {0, 0, 0}, cur = 0;
     HIPCHK(hipMemcpy(flags, c->sticky.p, sizeof flags, hipMemcpyDeviceToHost));
-    if (c->counters.p) HIPCHK(hipMemcpy(&cur, (const unsigned *)c->counters.p + STMPC_CNT_ERR, sizeof cur, hipMemcpyDeviceToHost));
+    if (c->solver.counters.p) HIPCHK(hipMemcpy(&cur, (const unsigned *)c->solver.counters.p + STMPC_CNT_ERR, sizeof cur, hipMemcpyDeviceToHost));
     if (flags[0] || flags[1] || flags[2] || cur) {
         HIPCHK(hipMemset(c->sticky.p, 0, sizeof flags));
-        if (cur) HIPCHK(hipMemset((unsigned *)c->counters.p + STMPC_CNT_ERR, 0, sizeof cur));
+        if (cur) HIPCHK(hipMemset((unsigned *)c->solver.counters.p + STMPC_CNT_ERR, 0, sizeof cur));
     }
     if (flags[0] || cur) return fail(STMPC_EINTERNAL, "solver error flag set on device (an episode of an earlier batch may not have been solved)");
     if (flags[1]) return fail(STMPC_EINVAL, "finer_fit: a fine grid longer than STMPC_QP_NMAX samples is not supported (the commanded speed of that state is not valid)");
@@ -1633,7 +1374,7 @@ static int st_control_device(stmpc_ctx *c, const stmpc_params *p, double tick, i
     double tv[STMPC_MAXH];
     host_t_values(p, H, tv);
     // finer_fit is called with (TICK_LENGTH, T_DISCRETIZATION) = the settings, not the arange spacing (st.py:771-772)
-    TRY(make_ffconst(p, tick, p->dt, c->qp_maxiters, &a.k));
+    TRY(make_ffconst(p, tick, p->dt, c->solver.knobs.qp_maxiters, &a.k));
     a.N = N; a.Hs = H; a.n_max = STMPC_QP_NMAX; a.use_qp = (tick < p->dt) ? 1 : 0;
     a.path_idx = d_path; a.best_t = d_bt; a.ego = d_ego; a.ds = p->ds;
     a.out = d_fine; a.out_len = d_fine_len; a.speed = d_speed;
@@ -2201,7 +1942,7 @@ int stmpc_solve_grid_no_jerk(stmpc_ctx *c, int variant, const uint8_t *obstacles
     size_t cap = states * 8;
     if (cap < ((size_t)1 << 20)) cap = (size_t)1 << 20;
     if (cap > ((size_t)1 << 25)) cap = (size_t)1 << 25;               // 32 M entries = 768 MB at most
-    TRY(s.misc3.ensure((size_t)H * 8 + 16)); TRY(s.pd.ensure(states)); TRY(s.path.ensure(states * 4)); TRY(c->gscratch.ensure(cap * sizeof(NjItem)));
+    TRY(s.misc3.ensure((size_t)H * 8 + 16)); TRY(s.pd.ensure(states)); TRY(s.path.ensure(states * 4)); TRY(c->solver.gscratch.ensure(cap * sizeof(NjItem)));
     TRY(upload(s.misc0, obstacles, cells)); TRY(upload(s.misc1, distances, cells)); TRY(upload(s.misc2, s_values, (size_t)S));
     HIPCHK(hipMemset(s.pd.p, 0, states));
     HIPCHK(hipMemset(s.path.p, 0, states * 4));
@@ -2210,7 +1951,7 @@ int stmpc_solve_grid_no_jerk(stmpc_ctx *c, int variant, const uint8_t *obstacles
     a.triple = variant; a.S = S; a.H = H; a.v0 = ego_start_speed;
     a.obstacles = s.misc0.as<uint8_t>(); a.distances = s.misc1.as<double>(); a.s_values = s.misc2.as<double>();
     a.dt = t_values[1] - t_values[0];
-    a.enc = s.pd.as<uint8_t>(); a.prev = s.path.as<int>(); a.heap = c->gscratch.as<NjItem>(); a.cap = cap;
+    a.enc = s.pd.as<uint8_t>(); a.prev = s.path.as<int>(); a.heap = c->solver.gscratch.as<NjItem>(); a.cap = cap;
     a.s_sequence = s.misc3.as<double>(); a.status = (int *)(s.misc3.as<double>() + H);
     hipLaunchKernelGGL(k_nojerk, dim3(1), dim3(64), 0, nullptr, a);
     HIPCHK(hipGetLastError());
@@ -2554,14 +2295,14 @@ int stmpc_solver_groups_sim_step_device(stmpc_ctx *c, const stmpc_params *groups
     HIPCHK(hipSetDevice(c->device));
     std::vector<double> cms((size_t)G);
     for (int g = 0; g < G; ++g) cms[g] = groups[g].crash_min_s;
-    if (cms != c->sg.host_cms) {                  // (once per runner: the table is kept while the next step brings equal values)
+    if (cms != c->solver.sg.host_cms) {                  // (once per runner: the table is kept while the next step brings equal values)
         HIPCHK(hipDeviceSynchronize());
-        c->sg.host_cms.clear();
-        TRY(upload(c->sg.crash_min_s, cms.data(), cms.size()));
-        c->sg.host_cms = cms;
+        c->solver.sg.host_cms.clear();
+        TRY(upload(c->solver.sg.crash_min_s, cms.data(), cms.size()));
+        c->solver.sg.host_cms = cms;
     }
     hipLaunchKernelGGL(sim::k_sim_step_solver_groups, dim3((n_per_group + 63) / 64, G), dim3(64), 0, (hipStream_t)stream, dp, c->sim.groups.as<sim::Cfg>(), n_per_group,
-                       c->sim.state(), d_cmd_speed, c->sg.crash_min_s.as<double>());
+                       c->sim.state(), d_cmd_speed, c->solver.sg.crash_min_s.as<double>());
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
