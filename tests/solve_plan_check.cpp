@@ -1,11 +1,14 @@
 // Prints the launch plan of one batched solve (csrc/stmpc_solve_plan.hpp) -- host code only, for tests/test_solve_plan_cpu.py.
 // usage: solve_plan_check num_cu lds_per_block N Kmax grouped fastdiv_proven H future_s ds dt dt2 dt3 v_w a_w j_w v_des v_max a_min a_max j_min j_max
 //        solve_plan_check variants        (every instantiation variant_built lists, one name per line)
+//        solve_plan_check reachable num_cu lds_per_block H future_s ... j_max      (every variant some setting of the knobs that choose kernels launches
+//                                         on that lattice, built or not, one name per line -- for tests/test_solver_variants_cpu.py)
 // The settings come from the STMPC_* environment, as in stmpc_create.  History is a fresh context's; the checkpoint pool is taken as granted
 // wherever the plan wants it (a fresh context on a device with memory to spare).
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <set>
 #include <string>
 
 #include "stmpc_solve_plan.hpp"
@@ -49,6 +52,39 @@ static std::string render(const SolvePlan &p) {
     return out;
 }
 
+// The knobs that decide which kernels a solve launches, swept in-process: windows, waves per workgroup, staged table, division, resume, bounded
+// search and penalty-buffer cells, lone and grouped, with and without vehicles and past the staged table's eight, at N below and above one
+// workgroup per compute unit.  (The other knobs reach the kernels as arguments, or move grids and streams.)
+static std::set<std::string> reachable(const DeviceShape &dev, const Params &dp) {
+    static const int tiers[][4] = {{0}, {1, 64}, {2, 256, 512}, {2, 512, 2048}, {3, 64, 128, 256}, {2, 2048, 8192}};
+    static const int waves[][3] = {{0, 0, 0}, {4, 0, 0}, {8, 0, 0}, {0, 8, 4}, {0, 4, 8}};      // {STMPC_NW=n, or "a,b"}
+    static const int pens[] = {0, 256, 512};
+    std::set<std::string> met;
+    for (const auto &tw : tiers) for (const auto &nw : waves) for (int pen : pens) for (int bits = 0; bits < 16; ++bits) for (int prune = -1; prune <= 1; ++prune) {
+        SolveKnobs k;
+        k.max_waves_per_cu = 4;
+        if (tw[0] > 0) { k.n_lds_tiers = tw[0]; k.tiers_from_env = true; for (int i = 0; i < tw[0]; ++i) k.lds_tier_W[i] = tw[1 + i]; }
+        k.waves_override = nw[0]; k.waves_tier[0] = nw[1]; k.waves_tier[1] = nw[2];
+        k.pen_cells[0] = k.pen_cells[1] = pen;
+        k.allow_stage_tab = (bits & 1) != 0; k.resume = (bits & 2) != 0; k.prune = prune;
+        SolveHistory hist;
+        hist.fastdiv_proven = (bits & 4) != 0;
+        const bool grouped = (bits & 8) != 0;
+        for (int N : {200, 600, 4096}) for (int Kmax : {0, 8, 9}) {
+            const SolvePlan p = plan_solve(k, dev, dp, N, Kmax, grouped, hist);
+            for (int i = 0; i < p.n_steps; ++i)
+                if (p.steps[i].op == Op::Solve) met.insert(name_of(p.resume_wanted ? p.tier[p.steps[i].tier].variant_resume : p.tier[p.steps[i].tier].variant));
+        }
+    }
+    return met;
+}
+
+static void read_params(char **argv, Params *dp) {
+    dp->H = atoi(argv[0]);
+    double *f[] = {&dp->future_s, &dp->ds, &dp->dt, &dp->dt2, &dp->dt3, &dp->v_w, &dp->a_w, &dp->j_w, &dp->v_des, &dp->v_max, &dp->a_min, &dp->a_max, &dp->j_min, &dp->j_max};
+    for (int i = 0; i < 14; ++i) *f[i] = strtod(argv[1 + i], nullptr);
+}
+
 int main(int argc, char **argv) {
     if (argc == 2 && std::string(argv[1]) == "variants") {
         const int fans[] = {9, STMPC_FAN1, STMPC_FAN88}, nwxs[] = {4, STMPC_MAXWAVES, 88};
@@ -59,6 +95,12 @@ int main(int argc, char **argv) {
         }
         return 0;
     }
+    if (argc == 19 && std::string(argv[1]) == "reachable") {
+        Params dp;
+        read_params(argv + 4, &dp);
+        for (const std::string &name : reachable(DeviceShape{atoi(argv[2]), atoi(argv[3])}, dp)) puts(name.c_str());
+        return 0;
+    }
     if (argc != 22) { fprintf(stderr, "solve_plan_check: 21 arguments expected, %d given\n", argc - 1); return 2; }
     const DeviceShape dev{atoi(argv[1]), atoi(argv[2])};
     const int N = atoi(argv[3]), Kmax = atoi(argv[4]);
@@ -66,9 +108,7 @@ int main(int argc, char **argv) {
     SolveHistory hist;
     hist.fastdiv_proven = atoi(argv[6]) != 0;
     Params dp;
-    dp.H = atoi(argv[7]);
-    double *f[] = {&dp.future_s, &dp.ds, &dp.dt, &dp.dt2, &dp.dt3, &dp.v_w, &dp.a_w, &dp.j_w, &dp.v_des, &dp.v_max, &dp.a_min, &dp.a_max, &dp.j_min, &dp.j_max};
-    for (int i = 0; i < 14; ++i) *f[i] = strtod(argv[8 + i], nullptr);
+    read_params(argv + 7, &dp);
     const SolveKnobs knobs = SolveKnobs::from_env();
     const std::string once = render(plan_solve(knobs, dev, dp, N, Kmax, grouped, hist)), twice = render(plan_solve(knobs, dev, dp, N, Kmax, grouped, hist));
     fputs(once.c_str(), stdout);

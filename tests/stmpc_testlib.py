@@ -1,8 +1,15 @@
 """Helpers the suite's modules share (plain functions: no fixtures, no hooks).  Import what a module needs, e.g.
 ``from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same``."""
 import contextlib
+import math
+import os
+import shutil
+import struct
+import subprocess
 
 import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def pkg():
@@ -47,3 +54,42 @@ def linit(m):
     a_net["w2"] = rng.normal(0, 0.05, (1, 300)).astype(np.float32)
     q_net["w2"] = rng.normal(0, 0.05, (1, 300)).astype(np.float32)
     return {"actor": a_net, "critic": q_net}
+
+
+def build_plan_checker(directory):
+    """tests/solve_plan_check.cpp (the solver's launch plan, host code only) compiled into ``directory``; the program's path."""
+    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = os.path.join(str(directory), "solve_plan_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(REPO, "include"), "-I" + os.path.join(REPO, "rl-mpc-lanemerging_amd", "csrc"),
+                    os.path.join(REPO, "tests", "solve_plan_check.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def plan_args(p, H):
+    """The plan checker's arguments for one parameter set (a dict of stmpc_params' fields): H and DevP's fields as make_devp derives them."""
+    dt = (0.0 + p["dt"]) - 0.0
+    assert H == int(math.ceil((p["future_t"] + p["dt"]) / p["dt"]))
+    args = [H, p["future_s"], p["ds"], dt, dt * dt, math.pow(dt, 3.0), p["v_w"], p["a_w"], p["j_w"], p["v_des"], p["v_max"], p["a_min"], p["a_max"], p["j_min"], p["j_max"]]
+    return [repr(float(a)) if isinstance(a, float) else str(a) for a in args]
+
+
+def plan_of(exe, inputs):
+    """The checker's output lines for one solve call: ``inputs`` as profiles/solver/launch_plan_parent.json records them (device shape, N, Kmax,
+    grouped, fastdiv_proven, H, params, knobs); the knobs go through the environment."""
+    args = [str(inputs[k]) for k in ("num_cu", "lds_per_block", "N", "Kmax")] + [str(int(inputs["grouped"])), str(int(inputs["fastdiv_proven"]))]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("STMPC_")}
+    env.update(inputs["knobs"])
+    out = subprocess.run([exe] + args + plan_args(inputs["params"][0], inputs["H"]), env=env, check=True, capture_output=True, text=True).stdout
+    return out.splitlines()
+
+
+def fastdiv_proven(dt):
+    """What solve_device finds for a time step: dt, dt^2 and dt^3 pass fastdiv_ok (a significand that is not all ones, restated here) and the
+    library's fastdiv2_ok."""
+    from rl_mpc_lanemerging_amd import _capi
+    dt = (0.0 + dt) - 0.0
+
+    def fastdiv_ok(d):
+        return 1e-100 < d < 1e100 and struct.unpack("<Q", struct.pack("<d", d))[0] & 0xFFFFFFFFFFFFF != 0xFFFFFFFFFFFFF
+    return all(fastdiv_ok(d) and _capi.fastdiv2_check(d)[0] for d in (dt, dt * dt, math.pow(dt, 3.0)))

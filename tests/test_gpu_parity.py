@@ -200,7 +200,8 @@ def test_h40a21_matches_oracle_seeded(gpu_ctx, restore_settings):
     (dict(MAX_SPEED=12, DESIRED_SPEED=10.0, V_WEIGHT=0.0, A_WEIGHT=0.0, J_WEIGHT=0.0), 6, 8),                # only the gap term: many ties
 ])
 def test_other_parameter_sets_match_oracle(over, k, kmax, gpu_ctx, restore_settings):
-    """Kernel variants selected by the parameters (wide/narrow fan-out, staged/unstaged vehicle table, K > 8)."""
+    """Kernel variants selected by the parameters (wide / narrow fan-out, K <= 8 and K > 8, many ties).  The staged vehicle table is not among them: it
+    is off unless STMPC_STAGE_TAB=1 is set -- tests/test_solver_variants.py runs it."""
     import rl_mpc_lanemerging_amd as pkg
     from rl_mpc_lanemerging_amd import _capi, st, synth
     from oracle import st_oracle as orc

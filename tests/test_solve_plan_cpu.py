@@ -4,12 +4,12 @@ profiles/solver/launch_plan_parent.json holds, for eight solve calls (wide and n
 no resume, small windows, staged table, solver groups), the inputs and every k_solve launch of the commit before the plan existed: kernel name, workgroups,
 block, dynamic LDS bytes, in order.  tests/solve_plan_check.cpp prints plan_solve's answer for the same inputs; the two must be equal."""
 import json
-import math
 import os
-import shutil
 import subprocess
 
 import pytest
+
+from stmpc_testlib import build_plan_checker, plan_of
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECORD = json.load(open(os.path.join(REPO, "profiles", "solver", "launch_plan_parent.json")))["cases"]
@@ -17,26 +17,7 @@ RECORD = json.load(open(os.path.join(REPO, "profiles", "solver", "launch_plan_pa
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("solve_plan") / "solve_plan_check")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(REPO, "include"), "-I" + os.path.join(REPO, "rl-mpc-lanemerging_amd", "csrc"),
-                    os.path.join(REPO, "tests", "solve_plan_check.cpp"), "-o", exe], check=True)
-    return exe
-
-
-def plan_of(exe, inputs):
-    """The checker's output lines for a recorded case: DevP's fields as make_devp derives them, the knobs through the environment."""
-    p = inputs["params"][0]
-    dt = (0.0 + p["dt"]) - 0.0
-    H = int(math.ceil((p["future_t"] + p["dt"]) / p["dt"]))
-    assert H == inputs["H"]
-    args = [inputs["num_cu"], inputs["lds_per_block"], inputs["N"], inputs["Kmax"], int(inputs["grouped"]), int(inputs["fastdiv_proven"]), H,
-            p["future_s"], p["ds"], dt, dt * dt, math.pow(dt, 3.0), p["v_w"], p["a_w"], p["j_w"], p["v_des"], p["v_max"], p["a_min"], p["a_max"], p["j_min"], p["j_max"]]
-    env = {k: v for k, v in os.environ.items() if not k.startswith("STMPC_")}
-    env.update(inputs["knobs"])
-    out = subprocess.run([exe] + [repr(float(a)) if isinstance(a, float) else str(a) for a in args], env=env, check=True, capture_output=True, text=True).stdout
-    return out.splitlines()
+    return build_plan_checker(tmp_path_factory.mktemp("solve_plan"))
 
 
 @pytest.mark.parametrize("case", RECORD, ids=lambda c: "case%d" % c["case"])
