@@ -1003,6 +1003,58 @@ int stmpc_traffic_mix_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, con
                                       double *d_final_stats, int32_t *d_traffic_type, int32_t *d_final_traffic_type, void *stream);
 int stmpc_traffic_mix_draw(uint64_t mix_seed, int env, uint32_t episode, const double *cum, int T);
 
+/*
+ * Combined-controller shield for the vector environment: stmpc_env_step_device behind dqn.RLAgent.do_combined_control (dqn.py:117-200), the controller
+ * the reference deploys and evaluates (EVALUATE_COMBINED_DDPG; episodes: controller "combined"), without leaving the device -- for training.  The env's
+ * action is the FIRST action of do_combined_control (the reference's agent.get_control(state)); rollout steps 2 ... L ask `actor` on the device, the
+ * decision rules of dqn.py:144-200 choose what is executed, and the step reports it as stmpc_shield_env_step_device does.  (Additive: new entries only,
+ * no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)
+ * One step, on `stream`: the env's action handling + the planner's view of the current state at row stride kmax WITH the other vehicles' accelerations
+ * (what stmpc_sim_view_device writes), into the start rows and the rollout's current rows + first_action = the action's jerk + the rollout's time
+ * counter, in one kernel -> for step = 1 ... max(rollout_length, 1): from step 2 on the body of stmpc_actor_eval_device on the current rows with the
+ * shield's counter, then the body of stmpc_rollout_step_device -> the body of stmpc_combined_decide_device (probe solve, controller solve, decision; the
+ * context's stmpc_combined_counts advance) -> where the decision took over a running environment: the executed speed, projected jerk and takeover
+ * penalty exactly as stmpc_shield_env_step_device applies them -> the world step and the reward / observation / autoreset kernel of
+ * stmpc_env_step_device, unchanged.  The step equals, bit for bit, that composition made from the public entries by a caller.
+ * The rollout's time counter (what the actor's TimeFeature input reads at rollout step s >= 2, stmpc_policy_features_device's d_evals):
+ *   rollout_time 0 ("env")       it starts every tick at episode ticks + 1, so step s reads time_scale x (ticks + s - 1): the value a policy acting in
+ *                                this env (one evaluation per tick, time = the episode's ticks) would read s - 1 ticks later.
+ *   rollout_time 1 ("deployed")  a running count of ALL policy evaluations of the environment's current episode -- this tick's proposal counts one, every
+ *                                rollout step s >= 2 whose rollout is still going on one more -- the reference's TimeFeature under do_combined_control.
+ *                                It restarts when the environment's episode index moves on (autoreset); a finished environment keeps counting.
+ *   stmpc_cshield_env_reset_device   stmpc_env_reset_device + every buffer of the step (start and current rows, first action, counter, decision,
+ *                       per-environment takeover counters, zeroed; the combined controller's and, for either value of cc.sparse_control, the sparse
+ *                       solve's), sized here: the step allocates none.  STMPC_EINVAL (before anything changes) unless env_cfg->action_mode is
+ *                       STMPC_ENV_CONTINUOUS_JERK (the rollout policy is a continuous actor), cc.remember_last_choice is 0, kmax is 1 ...
+ *                       STMPC_KMAX_LIMIT, takeover_penalty finite and >= 0, rollout_time 0 or 1, and actor (created, or a stmpc_actor_view_ddpg view) is on
+ *                       the context's device with n_in = stmpc_policy_features_len(&features).
+ *   stmpc_cshield_env_step_device    the arguments of stmpc_env_step_device, the cfg and the actor, then the four per-tick outputs of
+ *                       stmpc_shield_env_step_device with `reason` in the combined controller's codes 0-4 (stmpc_combined_decide_device);
+ *                       d_executed_action may be NULL.  A finished environment (no autoreset) proposes from its last state and is decided as the
+ *                       episode runner decides it, gets takeover 0, reason 0, executed_jerk 0 and keeps its step state.  Asynchronous with
+ *                       cc.sparse_control = 0; with 1 it makes the one host round trip of stmpc_combined_decide_device.  STMPC_EINVAL -- and nothing
+ *                       changes -- if the context's environment was not reset through stmpc_cshield_env_reset_device, N, kmax, rollout_time or the
+ *                       rollout length differ from the reset's, or the world has traffic groups, the env reward groups or a traffic mix.  Every other env
+ *                       step entry and stmpc_sim_step_device return STMPC_EINVAL on such an env: they would execute the proposal unprotected.
+ *   stmpc_cshield_env_evals_device   d_evals int32 [N]: the count the NEXT step's proposal is evaluated at (stmpc_policy_features_device's d_evals for
+ *                       a policy that acts in this env): the episode's ticks under rollout_time 0, the running count under 1 (0 in a new episode).
+ */
+typedef struct stmpc_cshield_env_cfg {
+    stmpc_combined_cfg cc;               /* as stmpc_combined_decide_device; remember_last_choice must be 0 (the env keeps no takeover history per episode) */
+    stmpc_policy_features_cfg features;  /* the rollout actor's input (time_feature as the actor was built) */
+    double takeover_penalty;             /* added to the tick's reward as takeover_penalty * tick_length where the controller took over (>= 0, finite) */
+    int32_t kmax;                        /* row stride of the planner view, 1 ... STMPC_KMAX_LIMIT */
+    int32_t rollout_time;                /* 0 "env", 1 "deployed" (above) */
+} stmpc_cshield_env_cfg;
+int stmpc_cshield_env_reset_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfg, const stmpc_env_cfg *env_cfg,
+                                   const stmpc_cshield_env_cfg *shield_cfg, const stmpc_actor *actor, int N, float *d_obs, int obs_stride, void *stream);
+int stmpc_cshield_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfg, const stmpc_env_cfg *env_cfg,
+                                  const stmpc_cshield_env_cfg *shield_cfg, const stmpc_actor *actor, int N, const void *d_action, float *d_obs,
+                                  int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats,
+                                  uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk, double *d_executed_action, int32_t *d_takeover_ticks,
+                                  void *stream);
+int stmpc_cshield_env_evals_device(stmpc_ctx *ctx, int N, int32_t *d_evals, void *stream);
+
 /* Device arithmetic probe used by the parity tests: out[i] = a[i] op b[i] evaluated on the GPU
  * with the kernels' compile flags. op: 0 div, 1 sqrt(a), 2 mul, 3 add, 4 fma(a,a,b*b), 5 the five-operation
  * quotient a/b of the FASTDIV kernels, 6 their two-operation quotient a/b.  HOST pointers. */

@@ -140,6 +140,24 @@ class FeaturesCfg(C.Structure):
                    time_feature=int(bool(time_feature)))
 
 
+class CShieldEnvCfg(C.Structure):
+    """``stmpc_cshield_env_cfg`` (include/stmpc.h): the combined controller behind the vector environment -- its flags, the rollout actor's input, the
+    takeover penalty, the row stride of the planner's view and the rule of the rollout's time counter."""
+    _fields_ = [("cc", CombinedCfg), ("features", FeaturesCfg), ("takeover_penalty", C.c_double), ("kmax", C.c_int32), ("rollout_time", C.c_int32)]
+
+    ROLLOUT_TIMES = {"env": 0, "deployed": 1}
+
+    @classmethod
+    def from_settings(cls, S, sparse_control=False, takeover_penalty=0.0, kmax=32, rollout_time="env", features=None):
+        """``S``: the ``Settings`` (or an overlay of them) ``do_combined_control`` reads; ``features``: the rollout actor's ``FeaturesCfg`` (default:
+        ``FeaturesCfg.from_settings(S)``, the time feature on); ``rollout_time``: "env" or "deployed" (ValueError otherwise)."""
+        if rollout_time not in cls.ROLLOUT_TIMES:
+            raise ValueError("rollout_time must be one of %s, not %r" % (", ".join(map(repr, cls.ROLLOUT_TIMES)), rollout_time))
+        f = FeaturesCfg.from_buffer_copy(features) if features is not None else FeaturesCfg.from_settings(S)
+        return cls(cc=CombinedCfg.from_settings(S, sparse_control=sparse_control), features=f, takeover_penalty=float(takeover_penalty), kmax=int(kmax),
+                   rollout_time=cls.ROLLOUT_TIMES[rollout_time])
+
+
 class SimCfg(C.Structure):
     """``stmpc_sim_cfg`` (include/stmpc.h): scenario constants of the batched SUMO-free episode runner."""
     _fields_ = [("tick_length", C.c_double), ("other_car_speed", C.c_double), ("base_traffic_interval", C.c_double), ("spawn_x", C.c_double),
@@ -252,6 +270,7 @@ EXPORTS = (
     "stmpc_reward_groups_env_reset_device", "stmpc_reward_groups_env_step_device", "stmpc_reward_groups_env_reward_device", "stmpc_reward_groups_split",
     "stmpc_shield_env_reset_device", "stmpc_shield_env_step_device",
     "stmpc_traffic_mix_env_reset_device", "stmpc_traffic_mix_env_step_device", "stmpc_traffic_mix_draw",
+    "stmpc_cshield_env_reset_device", "stmpc_cshield_env_step_device", "stmpc_cshield_env_evals_device",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
 KMAX_LIMIT = 32      # STMPC_KMAX_LIMIT
@@ -430,6 +449,10 @@ def load():
     lib.stmpc_traffic_mix_env_reset_device.argtypes = [vp, pp, sp, C.c_int, dp, C.c_uint64, ep, C.c_int, vp, C.c_int, vp, vp]
     lib.stmpc_traffic_mix_env_step_device.argtypes = [vp, pp, ep, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.stmpc_traffic_mix_draw.argtypes = [C.c_uint64, C.c_int, C.c_uint32, dp, C.c_int]
+    csp = C.POINTER(CShieldEnvCfg)
+    lib.stmpc_cshield_env_reset_device.argtypes = [vp, pp, sp, ep, csp, vp, C.c_int, vp, C.c_int, vp]
+    lib.stmpc_cshield_env_step_device.argtypes = [vp, pp, sp, ep, csp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.stmpc_cshield_env_evals_device.argtypes = [vp, C.c_int, vp, vp]
     _lib = lib
     return lib
 
@@ -1024,6 +1047,23 @@ class Context:
         self._chk(self._lib.stmpc_shield_env_step_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), C.byref(shield_cfg), int(N), d_action,
                                                          d_obs, int(obs_stride), d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, d_takeover,
                                                          d_reason, d_executed_jerk, d_executed_action or None, d_takeover_ticks, stream))
+
+    # -- vector environment behind the combined controller (stmpc_cshield_env_*; see include/stmpc.h) --------------
+    def cshield_env_reset(self, params, sim_cfg, env_cfg, shield_cfg, actor, N, d_obs, obs_stride, stream=0):
+        """``stmpc_cshield_env_reset_device``; ``actor``: an actor handle (``actor_create`` or ``actor_view_ddpg``)."""
+        self._chk(self._lib.stmpc_cshield_env_reset_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), C.byref(shield_cfg), actor, int(N), d_obs,
+                                                           int(obs_stride), stream))
+
+    def cshield_env_step(self, params, sim_cfg, env_cfg, shield_cfg, actor, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs,
+                         d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks, stream=0):
+        """``stmpc_cshield_env_step_device``; ``d_executed_action`` may be 0."""
+        self._chk(self._lib.stmpc_cshield_env_step_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), C.byref(shield_cfg), actor, int(N), d_action,
+                                                          d_obs, int(obs_stride), d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, d_takeover,
+                                                          d_reason, d_executed_jerk, d_executed_action or None, d_takeover_ticks, stream))
+
+    def cshield_env_evals(self, N, d_evals, stream=0):
+        """``stmpc_cshield_env_evals_device``: the count the next step's proposal is evaluated at, int32 [N] on the device."""
+        self._chk(self._lib.stmpc_cshield_env_evals_device(self._h, int(N), d_evals, stream))
 
     # -- traffic mix (stmpc_traffic_mix_*; see include/stmpc.h) ---------------------------------------------------
     def traffic_mix_env_reset(self, params, sim_cfgs, weights, mix_seed, env_cfg, N, d_obs, obs_stride, d_traffic_type=0, stream=0):

@@ -17,6 +17,7 @@
 #include "stmpc_solver_groups_kernels.hpp"
 #include "stmpc_env_groups_kernels.hpp"
 #include "stmpc_shield_env_kernels.hpp"
+#include "stmpc_cshield_env_kernels.hpp"
 #include "stmpc_traffic_mix_kernels.hpp"
 #include "stmpc_solve_plan.hpp"
 
@@ -317,6 +318,26 @@ struct stmpc_ctx {
         }
         env::ShieldView view() const { return env::ShieldView{ego5.as<double>(), k.as<int>(), ox.as<double>(), ov.as<double>(), proposal.as<double>()}; }
     } shield;
+    // vector environment behind the combined controller (stmpc_cshield_env_*): the start and current rows of the rollout, the first action, the rollout
+    // actor's time counter with the episode it was counted in, the decision, and the takeovers of each environment's current episode with theirs.  Valid
+    // while `generation` is the world's; kmax, rollout_time and L (the rollout length) are the reset's
+    struct CShieldEnv {
+        DevBuf ego5, k, ox, ov, cur_ego4, cur_ox, cur_ov, cur_oa, first_action, jerk, evals, evals_tag, speed, takeover, reason, count, tag;
+        int N = 0, kmax = 0, rollout_time = 0, L = 0;
+        int64_t generation = -1;
+        int ensure(int n_, int kmax_) {
+            const size_t n = (size_t)n_, row = n * kmax_ * 8;
+            TRY(ego5.ensure(n * 5 * 8)); TRY(k.ensure(n * 4)); TRY(ox.ensure(row)); TRY(ov.ensure(row)); TRY(cur_ego4.ensure(n * 4 * 8)); TRY(cur_ox.ensure(row));
+            TRY(cur_ov.ensure(row)); TRY(cur_oa.ensure(row)); TRY(first_action.ensure(n * 8)); TRY(jerk.ensure(n * 8)); TRY(evals.ensure(n * 4));
+            TRY(evals_tag.ensure(n * 4)); TRY(speed.ensure(n * 8)); TRY(takeover.ensure(n * 4)); TRY(reason.ensure(n * 4)); TRY(count.ensure(n * 4));
+            TRY(tag.ensure(n * 4));
+            return STMPC_OK;
+        }
+        env::CShieldView view() const {
+            return env::CShieldView{ego5.as<double>(), k.as<int>(), ox.as<double>(), ov.as<double>(), cur_ego4.as<double>(), cur_ox.as<double>(), cur_ov.as<double>(),
+                                    cur_oa.as<double>(), first_action.as<double>(), evals.as<int>(), evals_tag.as<int>()};
+        }
+    } cshield;
     // the batched ST solver (solve_device and the entries on top of it)
     struct Solver {
         plan::SolveKnobs knobs;        // the STMPC_* settings (stmpc_create)
@@ -1508,6 +1529,11 @@ int rollout_live(const stmpc_ctx *c, int N, int step, const int **live) {
     }
     return STMPC_OK;
 }
+int rollout_step_run(stmpc_ctx *c, const stmpc_params *p, const stmpc_combined_cfg *g, int N, int Kmax, int step, const double *d_ego5_start, double *d_cur_ego4,
+                     const int32_t *d_k, double *d_cur_ox, double *d_cur_ov, double *d_cur_oa, const double *d_action, void *stream);
+int combined_decide_run(stmpc_ctx *c, const stmpc_params *p, const stmpc_combined_cfg *g, int N, int Kmax, const double *d_ego5_start, const int32_t *d_k,
+                        const double *d_ox_start, const double *d_ov_start, const double *d_cur_ego4, const double *d_cur_ox, const double *d_cur_ov,
+                        const double *d_first_action, const int32_t *d_last_choice_rl, int32_t *d_takeover, int32_t *d_reason, double *d_speed, void *stream);
 // pointer checks of the two rollout step entries
 int rollout_step_ptrs(int Kmax, const double *d_ego5_start, const double *d_cur_ego4, const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov,
                       const double *d_action) {
@@ -1553,6 +1579,16 @@ int shield_control(stmpc_ctx *c, const stmpc_params *p, double tick, int N, int 
     return STMPC_OK;
 }
 
+// the decision's buffers for N states of Kalloc vehicle slots and H layers (grow-only: a no-op once they hold the shape)
+int combined_ensure(stmpc_ctx *c, int N, int Kalloc, int H, bool sparse) {
+    const size_t n = (size_t)N;
+    auto &b = c->cc;
+    TRY(b.probe_ego.ensure(n * 5 * 8)); TRY(b.probe_ox.ensure(n * Kalloc * 8)); TRY(b.probe_ov.ensure(n * Kalloc * 8));
+    TRY(b.sh.ensure(N, H));
+    if (sparse) TRY(b.sh.ensure_compact(N, Kalloc));
+    return STMPC_OK;
+}
+
 // A tick of the combined controller once the entry has checked its arguments and the rollout in the context: probe, controller, decision.  `n_test`: the
 // rows that probe their rolled-out state -- none, all, or those of the context's static list test_idx (controller groups).  `select` is shield_control's,
 // `decide()` launches the entry's decide kernel on what the two steps left in c->cc.sh.
@@ -1564,9 +1600,7 @@ int combined_decide(stmpc_ctx *c, const stmpc_params *p, int H, double tick, boo
     auto &o = b.sh;
     const size_t n = (size_t)N;
     const int Kalloc = Kmax > 0 ? Kmax : 1;
-    TRY(b.probe_ego.ensure(n * 5 * 8)); TRY(b.probe_ox.ensure(n * Kalloc * 8)); TRY(b.probe_ov.ensure(n * Kalloc * 8));
-    TRY(o.ensure(N, H));
-    if (sparse) TRY(o.ensure_compact(N, Kalloc));
+    TRY(combined_ensure(c, N, Kalloc, H, sparse));
     HIPCHK(hipMemsetAsync(o.pcrash.p, 0, n * 4, st_));
     // 1. feasibility probe of the rolled-out state (st.test_guaranteed_crash_from_state, dqn.py:152): one batched solve, of the rows that test only (a lone
     //    run of a group that does not test never calls the solver for them)
@@ -1606,6 +1640,15 @@ int stmpc_rollout_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_c
     if (N < 0 || Kmax < 0 || Kmax > STMPC_KMAX_LIMIT || step < 1) return fail(STMPC_EINVAL, "N, Kmax or step out of range");
     if (N == 0) return STMPC_OK;
     TRY(rollout_step_ptrs(Kmax, d_ego5_start, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_action));
+    return rollout_step_run(c, p, g, N, Kmax, step, d_ego5_start, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_action, stream);
+}
+
+}  // extern "C"
+
+namespace {
+// stmpc_rollout_step_device after its argument checks (N >= 1): the entry's body, shared with stmpc_cshield_env_step_device
+int rollout_step_run(stmpc_ctx *c, const stmpc_params *p, const stmpc_combined_cfg *g, int N, int Kmax, int step, const double *d_ego5_start, double *d_cur_ego4,
+                     const int32_t *d_k, double *d_cur_ox, double *d_cur_ov, double *d_cur_oa, const double *d_action, void *stream) {
     HIPCHK(hipSetDevice(c->device));
     DevP dp; CCfg cc;
     TRY(make_devp(p, &dp));
@@ -1621,6 +1664,9 @@ int stmpc_rollout_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_c
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int stmpc_policy_features_device(stmpc_ctx *c, const stmpc_policy_features_cfg *f, int N, int Kmax, int step, const double *d_cur_ego4, const int32_t *d_k,
                                  const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa, int32_t *d_evals, float *d_feat, int feat_stride, void *stream) {
@@ -1705,6 +1751,18 @@ int actor_eval_checks(const stmpc_ctx *c, int device, int n_in, const stmpc_poli
     if (f->time_feature && !d_evals) return fail(STMPC_EINVAL, "time_feature needs the evaluation counters");
     return STMPC_OK;
 }
+// stmpc_actor_eval_device after its argument checks (N >= 1): the entry's body, shared with stmpc_cshield_env_step_device
+int actor_eval_run(stmpc_ctx *c, const stmpc_actor *a, const FeatCfg &fc, int N, int Kmax, int step, const double *d_cur_ego4, const int32_t *d_k,
+                   const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa, int32_t *d_evals, float *d_feat, int feat_stride, double *d_jerk,
+                   void *stream) {
+    const int *live;
+    TRY(rollout_live(c, N, step, &live));
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_actor_eval, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), a->lds, (hipStream_t)stream, fc, a->dev, N, Kmax, d_cur_ego4, d_k, d_cur_ox, d_cur_ov,
+                       d_cur_oa, live, d_evals, d_feat, feat_stride, d_jerk);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1747,13 +1805,7 @@ int stmpc_actor_eval_device(stmpc_ctx *c, const stmpc_actor *a, const stmpc_poli
     FeatCfg fc;
     TRY(actor_eval_checks(c, a->device, a->dev.n_in, f, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_evals, d_feat, feat_stride, d_jerk, &fc));
     if (N == 0) return STMPC_OK;
-    const int *live;
-    TRY(rollout_live(c, N, step, &live));
-    HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_actor_eval, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), a->lds, (hipStream_t)stream, fc, a->dev, N, Kmax, d_cur_ego4, d_k, d_cur_ox, d_cur_ov,
-                       d_cur_oa, live, d_evals, d_feat, feat_stride, d_jerk);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    return actor_eval_run(c, a, fc, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_evals, d_feat, feat_stride, d_jerk, stream);
 }
 
 int stmpc_combined_counts(stmpc_ctx *c, int64_t *decisions, int64_t *control_solves, int reset) {
@@ -1774,6 +1826,17 @@ int stmpc_combined_decide_device(stmpc_ctx *c, const stmpc_params *p, const stmp
     if (N == 0) return STMPC_OK;
     if (!d_ego5_start || !d_k || !d_cur_ego4 || !d_first_action || !d_takeover || !d_reason || !d_speed) return fail(STMPC_EINVAL, "NULL device pointer");
     if (Kmax > 0 && (!d_ox_start || !d_ov_start || !d_cur_ox || !d_cur_ov)) return fail(STMPC_EINVAL, "NULL device pointer (vehicles)");
+    return combined_decide_run(c, p, g, N, Kmax, d_ego5_start, d_k, d_ox_start, d_ov_start, d_cur_ego4, d_cur_ox, d_cur_ov, d_first_action, d_last_choice_rl,
+                               d_takeover, d_reason, d_speed, stream);
+}
+
+}  // extern "C"
+
+namespace {
+// stmpc_combined_decide_device after its argument checks (N >= 1): the entry's body, shared with stmpc_cshield_env_step_device
+int combined_decide_run(stmpc_ctx *c, const stmpc_params *p, const stmpc_combined_cfg *g, int N, int Kmax, const double *d_ego5_start, const int32_t *d_k,
+                        const double *d_ox_start, const double *d_ov_start, const double *d_cur_ego4, const double *d_cur_ox, const double *d_cur_ov,
+                        const double *d_first_action, const int32_t *d_last_choice_rl, int32_t *d_takeover, int32_t *d_reason, double *d_speed, void *stream) {
     HIPCHK(hipSetDevice(c->device));
     CCfg cc;
     TRY(make_ccfg(p, g, &cc));
@@ -1798,6 +1861,9 @@ int stmpc_combined_decide_device(stmpc_ctx *c, const stmpc_params *p, const stmp
                                (const int *)o.fine_len.as<int>(), STMPC_QP_NMAX, d_takeover, d_reason, d_speed, c->sticky.as<unsigned>() + 1);
         });
 }
+}  // namespace
+
+extern "C" {
 
 // ---- controller groups (stmpc_cc_groups_kernels.hpp) ----
 int stmpc_combined_groups_set(stmpc_ctx *c, const stmpc_params *p, const stmpc_combined_cfg *cfgs, int C, int n_per_group) {
@@ -2188,6 +2254,8 @@ int check_grouped_world(stmpc_ctx *c, int N) {
 int sim_init_groups(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_group, void *stream, int G_max);
 const char *const GROUPED_WORLD = "the world has traffic groups (stmpc_sim_init_groups_device): one cfg would step every group; use the grouped step entry";
 const char *const MIXED_ENV = "the env has a traffic mix (stmpc_traffic_mix_env_reset_device): one cfg would step every type; use stmpc_traffic_mix_env_step_device";
+const char *const CSHIELD_ENV = "the env runs behind the combined controller (stmpc_cshield_env_reset_device): this entry would execute the proposal unprotected; use stmpc_cshield_env_step_device";
+bool has_cshield_env(const stmpc_ctx *c) { return c->env.N >= 1 && c->cshield.N == c->env.N && c->cshield.generation == c->sim.generation; }
 const char *const REWARD_GROUPED_ENV = "the env has reward groups (stmpc_reward_groups_env_reset_device): one cfg would reward every group; use stmpc_reward_groups_env_step_device";
 }  // namespace
 
@@ -2226,6 +2294,7 @@ int stmpc_sim_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_c
     if (N != c->sim.N || !d_cmd_speed) return fail(STMPC_EINVAL, "N does not match stmpc_sim_init_device, or NULL device pointer");
     if (c->sim.G) return fail(STMPC_EINVAL, GROUPED_WORLD);
     if (c->env.N >= 1 && c->env.T >= 1) return fail(STMPC_EINVAL, MIXED_ENV);
+    if (has_cshield_env(c)) return fail(STMPC_EINVAL, CSHIELD_ENV);
     sim::Cfg sc;
     DevP dp;
     TRY(make_simcfg(g, &sc));
@@ -2472,18 +2541,35 @@ int shield_cfg_check(const stmpc_params *p, const stmpc_shield_env_cfg *sh, int 
     return first_step_check(p, &sh->fs, N, sh->kmax);
 }
 
+// the combined-shield env's cfg and actor (its reset and its step): `cc`, `fc` receive the kernels' forms
+int cshield_cfg_check(const stmpc_ctx *c, const stmpc_params *p, const stmpc_cshield_env_cfg *sh, const stmpc_actor *a, int N, CCfg *cc, FeatCfg *fc) {
+    if (!sh) return fail(STMPC_EINVAL, "combined shield cfg is NULL");
+    if (!a) return fail(STMPC_EINVAL, "combined shield: actor is NULL");
+    if (sh->kmax < 1 || sh->kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "combined shield cfg: kmax must be 1 ... STMPC_KMAX_LIMIT (32), the solver's vehicles per state");
+    if (!(sh->takeover_penalty >= 0) || !(sh->takeover_penalty <= 1.7976931348623157e308))
+        return fail(STMPC_EINVAL, "combined shield cfg: takeover_penalty must be finite and not negative");
+    if (sh->rollout_time != env::ROLLOUT_TIME_ENV && sh->rollout_time != env::ROLLOUT_TIME_DEPLOYED)
+        return fail(STMPC_EINVAL, "combined shield cfg: rollout_time must be 0 (env) or 1 (deployed)");
+    TRY(make_ccfg(p, &sh->cc, cc));
+    if (cc->remember_last) return fail(STMPC_EINVAL, "combined shield cfg: remember_last_choice must be 0 (the env keeps no takeover history per episode)");
+    TRY(check_batch(N, sh->kmax));
+    // (stmpc_actor_eval_device's checks of an empty batch: the device, the features, the actor's input width; the rows are the context's own)
+    return actor_eval_checks(c, a->device, a->dev.n_in, &sh->features, 0, sh->kmax, 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, fc);
+}
+
 // ---- one reset, one step and one reward body behind the plain, traffic-groups, reward-groups and shielded entries ----
 // Which env shapes an entry serves: a shape the context has and the entry refuses, or lacks and the entry requires, is STMPC_EINVAL.
 enum Need { REFUSED, EITHER, REQUIRED };
 struct EnvEntry {
     const char *reset_entry;                 // the reset entry that makes this entry's env (for messages)
-    Need traffic_groups, reward_groups, shield, traffic_mix;
+    Need traffic_groups, reward_groups, shield, traffic_mix, cshield;
 };
-const EnvEntry PLAIN_ENV{"stmpc_env_reset_device", REFUSED, REFUSED, EITHER, REFUSED};       // (on a shield-reset context: the unshielded step)
-const EnvEntry TRAFFIC_GROUPS_ENV{"stmpc_env_reset_groups_device", REQUIRED, REFUSED, EITHER, REFUSED};
-const EnvEntry REWARD_GROUPS_ENV{"stmpc_reward_groups_env_reset_device", EITHER, REQUIRED, EITHER, REFUSED};
-const EnvEntry SHIELD_ENV{"stmpc_shield_env_reset_device", REFUSED, REFUSED, REQUIRED, REFUSED};
-const EnvEntry TRAFFIC_MIX_ENV{"stmpc_traffic_mix_env_reset_device", REFUSED, REFUSED, REFUSED, REQUIRED};
+const EnvEntry PLAIN_ENV{"stmpc_env_reset_device", REFUSED, REFUSED, EITHER, REFUSED, REFUSED};       // (on a shield-reset context: the unshielded step)
+const EnvEntry TRAFFIC_GROUPS_ENV{"stmpc_env_reset_groups_device", REQUIRED, REFUSED, EITHER, REFUSED, REFUSED};
+const EnvEntry REWARD_GROUPS_ENV{"stmpc_reward_groups_env_reset_device", EITHER, REQUIRED, EITHER, REFUSED, REFUSED};
+const EnvEntry SHIELD_ENV{"stmpc_shield_env_reset_device", REFUSED, REFUSED, REQUIRED, REFUSED, REFUSED};
+const EnvEntry TRAFFIC_MIX_ENV{"stmpc_traffic_mix_env_reset_device", REFUSED, REFUSED, REFUSED, REQUIRED, REFUSED};
+const EnvEntry CSHIELD_ENV_ENTRY{"stmpc_cshield_env_reset_device", REFUSED, REFUSED, REFUSED, REFUSED, REQUIRED};
 
 int env_shape_check(const stmpc_ctx *c, const EnvEntry &who) {
     const auto &v = c->shield;
@@ -2494,6 +2580,7 @@ int env_shape_check(const stmpc_ctx *c, const EnvEntry &who) {
         {c->env.N >= 1 && v.N == c->env.N && v.generation == c->sim.generation, who.shield, "the env was reset through stmpc_shield_env_reset_device: the traffic mix does not run behind the shield",
          "the environment in this context was not reset through stmpc_shield_env_reset_device"},
         {c->env.N >= 1 && c->env.T >= 1, who.traffic_mix, MIXED_ENV, "the environment in this context was not reset through stmpc_traffic_mix_env_reset_device"},
+        {has_cshield_env(c), who.cshield, CSHIELD_ENV, "the environment in this context was not reset through stmpc_cshield_env_reset_device"},
     };
     for (const auto &sh : shapes) {
         if (sh.has && sh.need == REFUSED) return fail(STMPC_EINVAL, sh.refused);
@@ -2562,6 +2649,10 @@ struct StepOut {                             // the tail every step entry takes
 struct MixStep {                             // what the traffic-mix step takes on top
     int32_t *traffic_type, *final_traffic_type;
 };
+struct CShieldStep {                         // what the combined-shield step takes on top of ShieldStep's outputs (ShieldStep::cfg is then NULL)
+    const stmpc_cshield_env_cfg *cfg;
+    const stmpc_actor *actor;
+};
 struct ShieldStep {                          // what the shielded step takes on top
     const stmpc_shield_env_cfg *cfg;
     uint8_t *takeover;
@@ -2600,12 +2691,19 @@ void env_world_step(stmpc_ctx *c, const DevP &dp, double crash_min_s, const env:
 
 // Step.  `g`: the cfg of a lone world (NULL: the entry takes none); `sh`: the shielded step's arguments, or NULL.
 int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const EnvEntry &who, const StepOut &o,
-             const ShieldStep *sh = nullptr, const MixStep *mix = nullptr) {
+             const ShieldStep *sh = nullptr, const MixStep *mix = nullptr, const CShieldStep *cs = nullptr) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     TRY(env_shape_check(c, who));
     if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, std::string("N does not match ") + who.reset_entry);
     const auto &v = c->shield;
-    if (sh) {
+    const auto &u = c->cshield;
+    CCfg cs_cc;
+    FeatCfg cs_fc;
+    if (cs) {
+        TRY(cshield_cfg_check(c, p, cs->cfg, cs->actor, N, &cs_cc, &cs_fc));
+        if (cs->cfg->kmax != u.kmax || cs->cfg->rollout_time != u.rollout_time || cs_cc.rollout_length != u.L)
+            return fail(STMPC_EINVAL, "combined shield cfg: kmax, rollout_time or the rollout length differs from the one the context was reset with (stmpc_cshield_env_reset_device)");
+    } else if (sh) {
         TRY(shield_cfg_check(p, sh->cfg, N));
         if (sh->cfg->kmax != v.kmax) return fail(STMPC_EINVAL, "shield cfg: kmax differs from the one the context was reset with (stmpc_shield_env_reset_device)");
     }
@@ -2618,6 +2716,7 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
     TRY(env_step_begin(c, ec, o.obs_stride, who.reset_entry, &e));
     if (sh && sh->executed_action && e.mode != env::ACT_CONTINUOUS_JERK)
         return fail(STMPC_EINVAL, "d_executed_action is the continuous env's (a discrete index is not rewritten): pass NULL");
+    if (cs && e.mode != env::ACT_CONTINUOUS_JERK) return fail(STMPC_EINVAL, "the combined shield serves STMPC_ENV_CONTINUOUS_JERK only (the rollout policy is a continuous actor)");
     // the world: one cfg -- the caller's, or the one an ungrouped reward-groups reset kept -- or the context's table of traffic groups
     const bool grouped = c->sim.G > 0, reward_groups = who.reward_groups == REQUIRED;
     if (!grouped && reward_groups) sc = c->env.rg_sc;
@@ -2631,7 +2730,27 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
     const sim::State s = c->sim.state();
     const env::EState es = env_state(c);
     // the action stage: the command of every live environment
-    if (sh) {
+    if (cs) {
+        const env::CShieldView w = u.view();
+        const stmpc_combined_cfg *g = &cs->cfg->cc;
+        // 1. action handling, the planner's view into the start and the current rows, the first action, the rollout's time counter
+        hipLaunchKernelGGL(env::k_cshield_env_pre, grid, block, 0, st_, e, sc, N, u.kmax, u.rollout_time, s, es, o.action, w);
+        HIPCHK(hipGetLastError());
+        // 2. dqn.RLAgent.do_combined_control on that view: the bodies of stmpc_actor_eval_device (steps 2 ... L), stmpc_rollout_step_device and
+        //    stmpc_combined_decide_device
+        for (int step = 1; step <= cs_cc.rollout_length; ++step) {
+            if (step > 1)
+                TRY(actor_eval_run(c, cs->actor, cs_fc, N, u.kmax, step, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, w.evals, nullptr, 0, u.jerk.as<double>(), o.stream));
+            TRY(rollout_step_run(c, p, g, N, u.kmax, step, w.ego5, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, step > 1 ? u.jerk.as<double>() : w.first_action,
+                                 o.stream));
+        }
+        TRY(combined_decide_run(c, p, g, N, u.kmax, w.ego5, w.k, w.ox, w.ov, w.cur_ego4, w.cur_ox, w.cur_ov, w.first_action, nullptr, u.takeover.as<int32_t>(),
+                                u.reason.as<int32_t>(), u.speed.as<double>(), o.stream));
+        // 3. what is executed, and what the learner is told: the first-step shield's rule, unchanged
+        hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, cs->cfg->takeover_penalty, N, s, es, o.action, (const double *)u.speed.as<double>(),
+                           (const int *)u.takeover.as<int>(), (const int *)u.reason.as<int>(), u.count.as<int>(), u.tag.as<int>(), sh->takeover, sh->reason,
+                           sh->executed_jerk, sh->executed_action, sh->takeover_ticks);
+    } else if (sh) {
         const env::ShieldView w = v.view();
         // 1. action handling, the planner's view, the proposal
         hipLaunchKernelGGL(env::k_shield_env_pre, grid, block, 0, st_, e, sc, N, v.kmax, s, es, o.action, w);
@@ -2752,6 +2871,51 @@ int stmpc_shield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmp
                                  double *d_executed_action, int32_t *d_takeover_ticks, void *stream) {
     const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
     return env_step(c, p, g, ec, N, SHIELD_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, &shield);
+}
+
+// The env behind dqn.RLAgent.do_combined_control (dqn.py:117-200): the plain reset, then every buffer of the step and zeroed counters.
+int stmpc_cshield_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_cshield_env_cfg *sh,
+                                   const stmpc_actor *actor, int N, float *d_obs, int obs_stride, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    CCfg cc;
+    FeatCfg fc;
+    TRY(cshield_cfg_check(c, p, sh, actor, N, &cc, &fc));
+    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
+    if (!ec) return fail(STMPC_EINVAL, "env cfg is NULL");
+    if (ec->action_mode != STMPC_ENV_CONTINUOUS_JERK)
+        return fail(STMPC_EINVAL, "the combined shield serves STMPC_ENV_CONTINUOUS_JERK only (the rollout policy is a continuous actor)");
+    DevP dp;
+    TRY(make_devp(p, &dp));
+    HIPCHK(hipSetDevice(c->device));
+    auto &u = c->cshield;                        // (a world initialised below outdates an earlier combined-shield env by its generation)
+    TRY(stmpc_env_reset_device(c, p, g, ec, N, d_obs, obs_stride, stream));
+    TRY(u.ensure(N, sh->kmax));
+    TRY(c->cc.ensure(N, sh->kmax, cc.rollout_length));
+    TRY(combined_ensure(c, N, sh->kmax, dp.H, true));         // (the sparse solve's compact batch too: a step may set cc.sparse_control either way)
+    for (DevBuf *b : {&u.evals, &u.evals_tag, &u.count, &u.tag}) HIPCHK(hipMemsetAsync(b->p, 0, (size_t)N * 4, (hipStream_t)stream));
+    u.N = N; u.kmax = sh->kmax; u.rollout_time = sh->rollout_time; u.L = cc.rollout_length; u.generation = c->sim.generation;
+    return STMPC_OK;
+}
+
+int stmpc_cshield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_cshield_env_cfg *sh,
+                                  const stmpc_actor *actor, int N, const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated,
+                                  uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason,
+                                  double *d_executed_jerk, double *d_executed_action, int32_t *d_takeover_ticks, void *stream) {
+    const ShieldStep out{nullptr, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    const CShieldStep cs{sh, actor};
+    return env_step(c, p, g, ec, N, CSHIELD_ENV_ENTRY, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, &out,
+                    nullptr, &cs);
+}
+
+int stmpc_cshield_env_evals_device(stmpc_ctx *c, int N, int32_t *d_evals, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(env_shape_check(c, CSHIELD_ENV_ENTRY));
+    if (N != c->env.N || !d_evals) return fail(STMPC_EINVAL, "N does not match stmpc_cshield_env_reset_device, or NULL device pointer");
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(env::k_cshield_env_evals, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, N, c->cshield.rollout_time, c->sim.state(), env_state(c),
+                       c->cshield.view(), d_evals);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
 }
 
 // Domain randomisation over the reference's traffic types (configs/train_*_*.json, control.py:215-226) at the episode boundary.

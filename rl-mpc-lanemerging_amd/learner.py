@@ -481,12 +481,13 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
     Returns {"steps", "frames", "episodes", "mean_return" (of the drained episodes), "returns" (array)}.
     ``learner`` may be a ``DDPGPopulation`` (the schedule may then return per-member arrays); the result then also carries
     ``member_returns``: the drained returns of each member's environments, a list of P arrays.
-    On a shielded env (``MergeVecEnv(shield="first_step")``) the result's ``takeover_share`` is the share of the live ticks on which the shield
+    On a shielded env (``MergeVecEnv(shield="first_step")``, ``vec_env.CombinedShieldVecEnv``) the result's ``takeover_share`` is the share of the live ticks on which the shield
     overruled the action (summed on the device, read at the drains; 0.0 on an unshielded env), and ``executed_actions=True`` (continuous env only,
     else ValueError) pushes ``info["executed_action"]`` -- what the shield let through or put in the action's place -- instead of the action."""
     shielded = getattr(env, "shield", None) is not None
     if executed_actions and not (shielded and env.continuous):
-        raise ValueError("executed_actions=True needs a shielded continuous env (MergeVecEnv(env_id='sumo-jerk-continuous-v0', shield='first_step'))")
+        raise ValueError("executed_actions=True needs a shielded continuous env (MergeVecEnv(env_id='sumo-jerk-continuous-v0', shield='first_step') or a "
+                         "CombinedShieldVecEnv)")
     steps = -(-int(frames) // env.n)
     obs = env.reset()
     returns, envs = [], []

@@ -448,3 +448,81 @@ class TrafficMixVecEnv(MergeVecEnv):
         if self.traffic_mix is not None:
             out["traffic_type"] = self.traffic_of_log(out)
         return out
+
+
+class CombinedShieldVecEnv(MergeVecEnv):
+    """``MergeVecEnv`` whose every step runs behind the combined RL + ST controller, ``dqn.RLAgent.do_combined_control`` (dqn.py:117-200) -- the
+    controller the reference deploys and evaluates (``EVALUATE_COMBINED_DDPG``, ``episodes.EpisodeRunner(controller="combined")``) -- on the device
+    (``stmpc_cshield_env_reset_device`` / ``stmpc_cshield_env_step_device``), so that a policy trains in the closed loop it is deployed in.  A class of
+    its own: ``MergeVecEnv(shield=...)`` stays the first-step shield's.
+
+    The action handed to ``step`` is the controller's first action (the reference's ``agent.get_control(state)``); rollout steps 2 ... ROLLOUT_LENGTH ask
+    ``policy`` on the device, the feasibility probe and the decision rules choose between the action and ``st.do_st_control``, and ``info`` reports what
+    was executed with the first-step shield's keys: ``takeover``, ``reason`` (``combined.REASON_*``), ``executed_jerk``, ``executed_action``,
+    ``takeover_ticks``.  ``env.shield == "combined"``, so ``learner.train_ddpg`` runs on it as on a shielded env, ``executed_actions=True`` included.
+
+    ``policy``: a lone hip-engine ``actor.DDPGActor`` of ``n`` rows on the env's context (``ctx`` defaults to the actor's): pretrained, or
+    ``DDPGActor.from_learner(learner, n, ctx, S, target=...)`` -- a zero-copy view, so the rollouts of a step queued after ``learner.update`` on the same
+    stream see the updated weights: the learner's own current actor does the rollouts.  The env keeps it alive; its ``evals`` are not used.
+    ``rollout_time``: what the actor's time feature reads at rollout step s >= 2.  "env": ``(episode ticks + s - 1) * time_scale``, the value
+    ``learner.act`` would give that many ticks later; "deployed": a running count of all policy evaluations of the episode, the reference's
+    ``TimeFeature`` under ``do_combined_control`` (``rollout_evals`` reads the count the next proposal is evaluated at).
+    ``control``: a dict of ``combined.CONTROL_KEYS`` overlaid on ``Settings``, as ``combined.control_cfgs`` takes one cell.
+    ``shield_sparse``, ``takeover_penalty``, ``shield_kmax``: as ``MergeVecEnv`` takes them.  ``shield_counts()`` reads ``(decisions, controller solves)``.
+
+    Refused with a ValueError before any device call: a discrete env id, ``REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED`` true (the env keeps no
+    takeover history), an ``actor.ActorPopulation`` or anything else that is no hip-engine ``DDPGActor``, an actor of another ``n`` or context, and a
+    bad ``rollout_time``, ``takeover_penalty`` or ``shield_kmax``.  Out of scope: traffic groups, reward groups and the traffic mix behind this shield."""
+
+    def __init__(self, n, policy, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, *, rollout_time="env", shield_sparse=False,
+                 takeover_penalty=0.0, shield_kmax=32, control=None):
+        from . import actor as _actor, combined
+        env_id_ = Settings.GYM_ENVIRONMENT if env_id is None else env_id
+        if env_id_ not in ENV_IDS:
+            raise ValueError("Invalid gym environment {} (one of {})".format(env_id_, ", ".join(ENV_IDS)))
+        if env_id_ != "sumo-jerk-continuous-v0":
+            raise ValueError("the combined shield serves 'sumo-jerk-continuous-v0' only (the rollout policy is a continuous actor), not %r" % (env_id_,))
+        if isinstance(policy, _actor.ActorPopulation):
+            raise ValueError("an ActorPopulation behind the combined shield is out of scope: policy is one actor.DDPGActor")
+        if not isinstance(policy, _actor.DDPGActor) or getattr(policy, "engine", None) != "hip" or getattr(policy, "handle", None) is None:
+            raise ValueError("policy must be a hip-engine actor.DDPGActor (pretrained, or DDPGActor.from_learner), not %r" % (policy,))
+        if int(n) < 1 or policy.n != int(n):
+            raise ValueError("the actor was built for %d rows, the env has n = %r" % (policy.n, n))
+        if ctx is not None and policy.ctx is not ctx:
+            raise ValueError("the actor lives on another context than the env's: build it on ctx (or leave ctx=None to take the actor's)")
+        if rollout_time not in _capi.CShieldEnvCfg.ROLLOUT_TIMES:
+            raise ValueError("rollout_time must be 'env' or 'deployed', not %r" % (rollout_time,))
+        try:
+            penalty = float(takeover_penalty)
+        except (TypeError, ValueError):
+            raise ValueError("takeover_penalty must be a number, not %r" % (takeover_penalty,))
+        if not (np.isfinite(penalty) and penalty >= 0):
+            raise ValueError("takeover_penalty must be finite and not negative, not %r" % (takeover_penalty,))
+        if not 1 <= int(shield_kmax) <= _capi.KMAX_LIMIT:
+            raise ValueError("shield_kmax must be 1 ... %d (the solver's vehicles per state), not %r" % (_capi.KMAX_LIMIT, shield_kmax))
+        self.control = dict(control) if control is not None else {}
+        combined.control_cfgs([self.control])                               # (ValueError for a key that is no setting of do_combined_control)
+        cfg = _capi.CShieldEnvCfg.from_settings(combined._Overlay(Settings, self.control), shield_sparse, penalty, shield_kmax, rollout_time, policy.fcfg)
+        if cfg.cc.remember_last_choice:
+            raise ValueError("REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED is out of scope behind the combined shield: the env keeps no takeover history")
+        super().__init__(n, env_id_, seed, reward, autoreset, policy.ctx, log_capacity)
+        self.shield, self.policy, self.rollout_time, self.shield_cfg = "combined", policy, rollout_time, cfg
+        z = lambda dtype: self.torch.zeros(self.n, dtype=dtype, device=self.device)
+        self._takeover, self._reason = z(self.torch.bool), z(self.torch.int32)
+        self._exec_jerk, self._exec_action, self._takeover_ticks = z(self.torch.float64), z(self.torch.float64), z(self.torch.int32)
+        self._evals = z(self.torch.int32)
+        bind, c = functools.partial, self.ctx
+        self._reset = bind(c.cshield_env_reset, self.params, self.sim_cfg, self.cfg, cfg, policy.handle, self.n)
+        self._step = bind(c.cshield_env_step, self.params, self.sim_cfg, self.cfg, cfg, policy.handle, self.n)
+
+    @property
+    def rollout_evals(self):
+        """The count the next step's proposal is evaluated at, int32 [n] on the device (``stmpc_cshield_env_evals_device``): the episode's ticks under
+        ``rollout_time="env"``, the episode's policy evaluations so far under "deployed" -- the ``evals`` to hand to an actor that proposes the action."""
+        self.ctx.cshield_env_evals(self.n, self._evals.data_ptr(), self._stream())
+        return self._evals
+
+    def shield_counts(self, reset=False):
+        """(states decided, controller solves run for them) on this env's context since the last reset of the counts (``stmpc_combined_counts``:
+        finished environments of a run without autoreset are decided too, and count; equal unless ``shield_sparse``)."""
+        return self.ctx.combined_counts(reset)
