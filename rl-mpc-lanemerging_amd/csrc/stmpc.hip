@@ -752,51 +752,46 @@ namespace {
 // ---- one k_solve launch ------------------------------------------------------------------------------------------------------------------
 struct SolveLaunch { dim3 grid, block; size_t lds; hipStream_t stream; const SolveArgs &a; const GroupTab *g; };
 
-// f(std::true_type or std::false_type)
-template <class F> int with_flag(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+int no_such_variant() { return fail(STMPC_EINTERNAL, "k_solve: no such kernel variant"); }
 
-// one instantiation: compiled when plan::variant_built lists it, refused otherwise
+// f(std::integral_constant of the one of Vs that x equals); refused when it equals none
+template <auto... Vs, class X, class F> int with_value(X x, F &&f) {
+    int rc = STMPC_OK;
+    const bool found = ((x == Vs && ((rc = f(std::integral_constant<decltype(Vs), Vs>{})), true)) || ...);
+    return found ? rc : no_such_variant();
+}
+
+// one instantiation: compiled when plan::variant_built lists it, refused otherwise.  Raises the kernel's dynamic LDS limit where the launch needs
+// more than 48 KB, and launches it.
 template <bool G, bool L, bool FD, int KT, int FM, bool SG, int RS, int NWX>
 int launch_instance(const SolveLaunch &l) {
-    if constexpr (!plan::variant_built(plan::KernelVariant{L, FD, KT, FM, SG, RS, NWX, G})) return fail(STMPC_EINTERNAL, "k_solve: no such kernel variant");
-    else if constexpr (G) {
-        SolveArgsG ag;
-        memset(&ag, 0, sizeof ag);
-        static_cast<SolveArgs &>(ag) = l.a;
-        ag.g = *l.g;
-        if (l.lds > 48 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)grouped::k_solve<L, false, FD, KT, FM, SG, RS, NWX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
-        hipLaunchKernelGGL((grouped::k_solve<L, false, FD, KT, FM, SG, RS, NWX>), l.grid, l.block, l.lds, l.stream, ag);
-        return STMPC_OK;
-    } else {
-        if (l.lds > 48 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)k_solve<L, false, FD, KT, FM, SG, RS, NWX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
-        hipLaunchKernelGGL((k_solve<L, false, FD, KT, FM, SG, RS, NWX>), l.grid, l.block, l.lds, l.stream, l.a);
-        return STMPC_OK;
+    if constexpr (!plan::variant_built(plan::KernelVariant{L, FD, KT, FM, SG, RS, NWX, G})) return no_such_variant();
+    else {
+        const auto launch = [&l](auto *kernel, const auto &args) -> int {
+            if (l.lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+            hipLaunchKernelGGL(kernel, l.grid, l.block, l.lds, l.stream, args);
+            return STMPC_OK;
+        };
+        if constexpr (G) {
+            SolveArgsG ag;
+            memset(&ag, 0, sizeof ag);
+            static_cast<SolveArgs &>(ag) = l.a;
+            ag.g = *l.g;
+            return launch(grouped::k_solve<L, false, FD, KT, FM, SG, RS, NWX>, ag);
+        } else return launch(k_solve<L, false, FD, KT, FM, SG, RS, NWX>, l.a);
     }
 }
 
-// RES and NWX of a variant whose other arguments are constants by now (FM: 9 or STMPC_FAN1; the 88 shape swaps in STMPC_FAN88)
-template <bool G, bool L, bool FD, int KT, int FM, bool SG>
-int launch_res_nwx(const plan::KernelVariant &v, const SolveLaunch &l) {
-    constexpr int NW = STMPC_MAXWAVES;
-    if (v.res == 0 && v.nwx == NW) return launch_instance<G, L, FD, KT, FM, SG, 0, NW>(l);
-    if (v.res == 0 && v.nwx == 4) return launch_instance<G, L, FD, KT, FM, SG, 0, 4>(l);
-    if (v.res == 1 && v.nwx == NW) return launch_instance<G, L, FD, KT, FM, SG, 1, NW>(l);
-    if (v.res == 1 && v.nwx == 4) return launch_instance<G, L, FD, KT, FM, SG, 1, 4>(l);
-    if (v.res == 2 && v.nwx == NW) return launch_instance<G, L, FD, KT, FM, SG, 2, NW>(l);
-    if (v.res == 2 && v.nwx == 88) return launch_instance<G, L, FD, KT, STMPC_FAN88, SG, 2, 88>(l);
-    return fail(STMPC_EINTERNAL, "k_solve: no such kernel variant");
-}
-
-// The k_solve instantiation of a variant: raises its dynamic LDS limit where the launch needs more than 48 KB, and launches it.
+// The k_solve instantiation of a variant, each template argument picked from the values it takes in some instantiation.
 int launch_k_solve(const plan::KernelVariant &v, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SolveArgs &a, const GroupTab *g) {
-    if (!plan::variant_built(v) || (v.grouped && !g)) return fail(STMPC_EINTERNAL, "k_solve: no such kernel variant");
+    if (!plan::variant_built(v) || (v.grouped && !g)) return no_such_variant();
     const SolveLaunch l{grid, block, lds, stream, a, g};
-    return with_flag(v.grouped, [&](auto G) { return with_flag(v.use_lds, [&](auto L) { return with_flag(v.fastdiv, [&](auto FD) {
-           return with_flag(v.kt == 8, [&](auto KT8) { return with_flag(v.fanmax == 9, [&](auto F9) { return with_flag(v.s1gen, [&](auto SG) {
-               return launch_res_nwx<decltype(G)::value, decltype(L)::value, decltype(FD)::value, decltype(KT8)::value ? 8 : 0,
-                                     decltype(F9)::value ? 9 : STMPC_FAN1, decltype(SG)::value>(v, l); }); }); }); }); }); });
+    return with_value<false, true>(v.grouped, [&](auto G) { return with_value<false, true>(v.use_lds, [&](auto L) {
+           return with_value<false, true>(v.fastdiv, [&](auto FD) { return with_value<0, 8>(v.kt, [&](auto KT) {
+           return with_value<9, STMPC_FAN1, STMPC_FAN88>(v.fanmax, [&](auto FM) { return with_value<false, true>(v.s1gen, [&](auto SG) {
+           return with_value<0, 1, 2>(v.res, [&](auto RS) { return with_value<4, STMPC_MAXWAVES, 88>(v.nwx, [&](auto NWX) {
+               return launch_instance<decltype(G)::value, decltype(L)::value, decltype(FD)::value, decltype(KT)::value, decltype(FM)::value,
+                                      decltype(SG)::value, decltype(RS)::value, decltype(NWX)::value>(l); }); }); }); }); }); }); }); });
 }
 
 // ---- guide tables of the guided bounding attempt (SolveArgs::guide_tab) ------------------------------------------------------------------------

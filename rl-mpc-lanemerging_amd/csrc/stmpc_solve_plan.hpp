@@ -161,17 +161,19 @@ struct SolveHistory {
 // The template arguments of one k_solve instantiation (GRID is false in every batched launch); grouped: the kernel of namespace grouped
 struct KernelVariant { bool use_lds, fastdiv; int kt, fanmax; bool s1gen; int res, nwx; bool grouped; };
 
-// The instantiations the library is built with -- launch_k_solve (stmpc.hip) compiles exactly these and refuses any other.  Pruned on purpose:
-// checkpointing (RES 1 saves, 2 continues) only for the wide-fan LDS kernels without a staged table, the 88 shape (second window alone on its
-// unit) only with STMPC_FAN88 slots, four-wave list search (NWX 4) only in LDS windows; the grouped family is the first window in its standard
-// shape, any other LDS window and the HBM window (ordinary division) in the general shape.
+// The instantiations the library is built with: exactly what plan_solve can store in a PlanTier -- launch_k_solve (stmpc.hip) compiles these and
+// refuses any other.  46: 32 lone, 14 grouped.
 constexpr bool variant_built(const KernelVariant &v) {
     const bool fan = v.fanmax == 9 || v.fanmax == STMPC_FAN1, full = v.nwx == STMPC_MAXWAVES;
-    if (v.grouped) return v.kt == 0 && v.res == 0 && fan && (v.use_lds ? (full || (v.nwx == 4 && !v.s1gen)) : (full && !v.fastdiv && v.s1gen));
-    if (v.res == 0) return fan && (v.kt == 0 || (v.kt == 8 && v.use_lds)) && (full || (v.nwx == 4 && v.use_lds));
-    if (!v.use_lds || v.kt != 0) return false;
-    if (v.res == 1) return v.fanmax == STMPC_FAN1 && (full || v.nwx == 4);
-    return v.res == 2 && ((v.fanmax == STMPC_FAN1 && full) || (v.fanmax == STMPC_FAN88 && v.nwx == 88));
+    // the HBM window is the last tier, and S1GEN is `last`; it has no staged table, no checkpoints and eight-wave lists (grouped: ordinary division)
+    if (!v.use_lds) return v.s1gen && fan && full && v.kt == 0 && v.res == 0 && !(v.grouped && v.fastdiv);
+    // the four-wave shape is W 2048 / PW 1024 and the 88 shape W 8192 / PW 4096: a penalty buffer below the window, so a tier always follows
+    if ((v.nwx == 4 || v.nwx == 88) && v.s1gen) return false;
+    if (v.res == 0) return fan && (full || v.nwx == 4) && (v.kt == 0 || (v.kt == 8 && v.fanmax == 9 && !v.grouped));      // stage_tab requires small_fan
+    // checkpointing (resume_wanted): lone, the wide fan, no staged table, the first two of at least two LDS windows
+    if (v.grouped || v.kt != 0) return false;
+    if (v.res == 1) return v.fanmax == STMPC_FAN1 && (full || v.nwx == 4) && !v.s1gen;      // the window that saves is tier 0 of two: never the last
+    return v.res == 2 && ((v.fanmax == STMPC_FAN1 && full) || (v.fanmax == STMPC_FAN88 && v.nwx == 88));       // the 88 shape alone has STMPC_FAN88 slots
 }
 
 struct PlanTier {
@@ -349,7 +351,7 @@ SolvePlan plan_solve(const SolveKnobs &k, const DeviceShape &dev, const P &dp, i
         }
         if (t.lds && std_shape) v.nwx = 4;
         t.variant = t.variant_resume = v;
-        if (t.lds && fm == STMPC_FAN1 && v.kt == 0 && i <= 1) {
+        if (two_lds && fm == STMPC_FAN1 && v.kt == 0 && i <= 1) {       // (a lone LDS window never checkpoints: the two coincide)
             KernelVariant &r = t.variant_resume;
             r.res = i + 1;
             if (i == 1) { r.nwx = STMPC_MAXWAVES; if (std_shape2) { r.fanmax = STMPC_FAN88; r.nwx = 88; } }

@@ -33,7 +33,7 @@ def main():
                                                            r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]"), r.get("LDS Size [bytes/block]")))
     s = "\n".join(lines) + "\n"
     if out:
-        open(out, "w").write("# hipcc " + " ".join(b.HIPCC_FLAGS + extra) + " -Rpass-analysis=kernel-resource-usage\n# k_solve<USE_LDS, GRID, FASTDIV, KT, FANMAX, S1GEN, RES>\n" + s)
+        open(out, "w").write("# hipcc " + " ".join(b.HIPCC_FLAGS + extra) + " -Rpass-analysis=kernel-resource-usage\n# k_solve<USE_LDS, GRID, FASTDIV, KT, FANMAX, S1GEN, RES, NWX>\n" + s)
     sys.stdout.write(s)
 
 if __name__ == "__main__":

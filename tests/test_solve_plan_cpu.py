@@ -51,8 +51,7 @@ def test_record_covers_the_plan_flags():
 
 def test_variant_list_is_the_librarys(checker):
     """variant_built (the list the dispatch compiles from, and DESIGN.md section 4 tabulates) names exactly the batched k_solve kernels of the library:
-    the rows of profiles/solver/resource_usage_plan.txt, less stmpc_solve_grid's one GRID kernel."""
+    the rows of profiles/solver/resource_usage_variants.txt, less stmpc_solve_grid's one GRID kernel."""
     listed = subprocess.run([checker, "variants"], check=True, capture_output=True, text=True).stdout.split("\n")[:-1]
-    rows = [l[:88].rstrip() for l in open(os.path.join(REPO, "profiles", "solver", "resource_usage_plan.txt")) if "k_solve<" in l and not l.startswith("#")]
-    built = [r[:r.index(">") + 1] for r in rows if not r.startswith("k_solve<false, true,")]
-    assert len(listed) == len(set(listed)) == 70 and sorted(listed) == sorted(built)
+    rows = [l for l in open(os.path.join(REPO, "profiles", "solver", "resource_usage_variants.txt")) if "k_solve<" in l and not l.startswith(("#", "k_solve<false, true,"))]
+    assert len(listed) == len(set(listed)) == 46 and sorted(listed) == sorted(r[:r.index(">") + 1] for r in rows)

@@ -1,9 +1,8 @@
-"""Which of the library's 70 k_solve instantiations a GPU test launches, and which of them it hands work -- answered on a CPU, from the pure launch
+"""Which of the library's 46 k_solve instantiations a GPU test launches, and which of them it hands work -- answered on a CPU, from the pure launch
 plan (csrc/stmpc_solve_plan.hpp through tests/solve_plan_check.cpp) of every case of tests/solver_variant_cases.py on an MI355X's shape.
 
-Every built variant is either launched and given work by a named case, or listed in EXPECTED_UNREACHABLE with the reason no setting of the knobs
-reaches it; the checker's `reachable` sweep over the knobs that choose kernels guards that list.  profiles/solver/variant_coverage.txt is the
-printed table, and must equal the computation."""
+The variants launched and given work by the named cases are exactly the variants built; the checker's `reachable` sweep over the knobs that choose
+kernels guards the rules variant_built prunes by.  profiles/solver/variant_coverage.txt is the printed table, and must equal the computation."""
 import os
 import subprocess
 
@@ -14,24 +13,6 @@ from conftest import REPO
 from stmpc_testlib import build_plan_checker, fastdiv_proven, pkg as _pkg, plan_args, plan_of
 
 COVERAGE = os.path.join(REPO, "profiles", "solver", "variant_coverage.txt")
-V = svc.variant
-
-# Built, but launched under no setting: variant_built lists the kernels by family, plan_solve picks fewer.  One reason per entry.
-EXPECTED_UNREACHABLE = {}
-for fd in (0, 1):
-    for fan in (9, 8):
-        EXPECTED_UNREACHABLE[V(0, fd, 0, fan, 0, 0, 8)] = "the HBM window is always the last tier, so S1GEN=false never occurs there"
-        for kt in (0, 8):
-            if (kt, fan) != (8, 8):
-                EXPECTED_UNREACHABLE[V(1, fd, kt, fan, 1, 0, 4)] = "the four-wave shape's penalty buffer (1024) is smaller than its window (2048), so a tier always follows it: never S1GEN"
-    for s1 in (0, 1):
-        for nwx in (4, 8):
-            EXPECTED_UNREACHABLE[V(1, fd, 8, 8, s1, 0, nwx)] = "the staged table (KT=8) needs the small fan"
-    for nwx in (4, 8):
-        EXPECTED_UNREACHABLE[V(1, fd, 0, 8, 1, 1, nwx)] = "a window that checkpoints (RES=1) is the first of two: never the last tier, and a lone LDS window never checkpoints"
-    EXPECTED_UNREACHABLE[V(1, fd, 0, 24, 1, 2, 88)] = "the 88 shape's penalty buffer (4096) is smaller than its window (8192), so the HBM tier always follows it: never S1GEN"
-del fd, fan, kt, s1, nwx
-assert len(EXPECTED_UNREACHABLE) == 24
 
 
 @pytest.fixture(scope="module")
@@ -121,13 +102,10 @@ def _label(names):
 def render(cov, built):
     lines = ["# k_solve variants by the cases of tests/solver_variant_cases.py: variant | cases that launch it | cases that give it work",
              "# ([test]: a setting another GPU test runs).  Written by tests/test_solver_variants_cpu.py from the launch plan on %d compute units with" % svc.DEVICE["num_cu"],
-             "# %d B of LDS; unreachable: built, but launched under no setting of the knobs (the reason follows)." % svc.DEVICE["lds_per_block"]]
+             "# %d B of LDS." % svc.DEVICE["lds_per_block"]]
     for v in sorted(built):
-        if v in EXPECTED_UNREACHABLE:
-            lines.append("%s | unreachable | %s" % (v, EXPECTED_UNREACHABLE[v]))
-        else:
-            c = cov.get(v, {"launch": [], "work": []})
-            lines.append("%s | %s | %s" % (v, " ".join(_label(c["launch"])) or "-", " ".join(_label(c["work"])) or "-"))
+        c = cov.get(v, {"launch": [], "work": []})
+        lines.append("%s | %s | %s" % (v, " ".join(_label(c["launch"])) or "-", " ".join(_label(c["work"])) or "-"))
     return "\n".join(lines) + "\n"
 
 
@@ -168,19 +146,17 @@ def test_case_launches_what_it_claims(checker, case):
         assert name in worked, "%s launches %s but no condition of it proves the kernel saw an episode" % (case["name"], name)
 
 
-def test_every_built_variant_is_run_or_known_unreachable(checker, coverage):
+def test_every_built_variant_is_run(checker, coverage):
+    """built == launched and given work by a named case, 46 of them: no kernel the library holds goes unexercised, and none is launched that it lacks."""
     built = _built(checker)
-    assert len(built) == 70 and set(EXPECTED_UNREACHABLE) <= set(built)
-    launched = set(coverage)
-    assert launched <= set(built)
-    assert launched == set(built) - set(EXPECTED_UNREACHABLE), (sorted(set(built) - set(EXPECTED_UNREACHABLE) - launched), sorted(launched & set(EXPECTED_UNREACHABLE)))
-    idle = sorted(v for v in launched if not coverage[v]["work"])
-    assert not idle, "launched, but no case's conditions prove they saw an episode: %s" % idle
+    assert len(built) == len(set(built)) == 46
+    worked = {v for v, c in coverage.items() if c["work"]}
+    assert worked == set(coverage) == set(built), (sorted(set(built) - worked), sorted(set(coverage) - set(built)))
 
 
 def test_reachable_sweep_finds_nothing_new(checker, coverage):
     """The checker's sweep of the knobs that choose kernels (windows, waves, staged table, division, resume, bounded search, penalty cells, lone and
-    grouped, N below and above the grid, Kmax 0 / 8 / 9) over the table's lattices: nothing it meets is unbuilt, listed as unreachable, or uncovered."""
+    grouped, N below and above the grid, Kmax 0 / 8 / 9) over the table's lattices: nothing it meets is unbuilt (one of variant_built's rules would be wrong) or uncovered."""
     built = set(_built(checker))
     met = set()
     for lattice in svc.LATTICES:
@@ -189,7 +165,6 @@ def test_reachable_sweep_finds_nothing_new(checker, coverage):
         met |= {l for l in out.split("\n") if l}
     assert len(met) > 30
     assert met <= built, sorted(met - built)
-    assert not met & set(EXPECTED_UNREACHABLE), sorted(met & set(EXPECTED_UNREACHABLE))
     assert met <= {v for v, c in coverage.items() if c["work"]}, sorted(met - {v for v, c in coverage.items() if c["work"]})
 
 
