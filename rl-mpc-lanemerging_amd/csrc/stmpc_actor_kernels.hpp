@@ -108,11 +108,13 @@ __device__ __forceinline__ void actor_eval_body(const FeatCfg &f, const ActorDev
     if (part == 0 && l0 + row < rows) jerk_out[e0 + row] = (double)(tanhf(s + *A.b2p) * A.scale + A.mean);
 }
 
+#ifdef STMPC_UNIT_CONTROL        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(AT_THREADS) k_actor_eval(FeatCfg f, ActorDev A, int N, int Kmax, const double *__restrict__ ego4, const int *__restrict__ k_count,
                                                            const double *__restrict__ ox, const double *__restrict__ ov, const double *__restrict__ oa,
                                                            const int *__restrict__ live, int *evals, float *feat_out, int feat_stride, double *jerk_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char at_smem[];
     actor_eval_body(f, A, 0, N, Kmax, ego4, k_count, ox, ov, oa, live, evals, feat_out, feat_stride, jerk_out, at_smem);
 }
+#endif
 
 }  // namespace stmpc

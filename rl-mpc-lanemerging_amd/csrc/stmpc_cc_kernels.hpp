@@ -108,6 +108,7 @@ __global__ void __launch_bounds__(64) k_rollout_step(DevP p, CCfg c, int N, int 
     rollout_step_body<KMAX>(p, c, N, Kmax, step, c.rollout_length + 1, ego5_start, ego4, k_count, ox, ov, oa, action, st);
 }
 
+#ifdef STMPC_UNIT_CONTROL        // (the kernels of the unit that launches them)
 // Probe state of the episodes whose rollout ended before step ST_TEST_ROLLOUTS (dqn.py:142-143), as the 5-column state
 // the solver takes (start_s of the probe state from the device map of control.get_ego_s).
 __global__ void __launch_bounds__(64) k_cc_probe_state(int N, int Kmax /* row stride */, int Kcopy /* vehicles per row the caller's arrays hold (0: none, pointers may be null) */,
@@ -127,6 +128,7 @@ __global__ void __launch_bounds__(64) k_cc_probe_state(int N, int Kmax /* row st
         probe_ox[(size_t)e * Kmax + i] = x; probe_ov[(size_t)e * Kmax + i] = v;
     }
 }
+#endif
 
 // The decision, dqn.py:144-200.  probe_crash = st.test_guaranteed_crash_from_state(test_state); st_speed / fine / fine_len =
 // st.do_st_control's command and (trimmed, re-sampled) path for the START state.
@@ -167,6 +169,7 @@ __device__ __forceinline__ void cc_decide_body(const CCfg &c, int N, int rs, con
     reason_out[e] = reason;
     speed_out[e] = speed;
 }
+#ifdef STMPC_UNIT_CONTROL        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(64) k_cc_decide(CCfg c, int N, const double *__restrict__ ego5_start, const double *__restrict__ first_action,
                                                   const int *__restrict__ last_choice_rl, CCState st, const int *__restrict__ probe_crash,
                                                   const double *__restrict__ st_speed, const double *__restrict__ fine, const int *__restrict__ fine_len,
@@ -174,6 +177,7 @@ __global__ void __launch_bounds__(64) k_cc_decide(CCfg c, int N, const double *_
     cc_decide_body(c, N, c.rollout_length + 1, ego5_start, first_action, last_choice_rl, st, probe_crash, st_speed, fine, fine_len, fine_stride, takeover, reason_out,
                    speed_out, err);
 }
+#endif
 
 // The policy's input vector for N states: dqn.get_state_vector_from_base_state (dqn.py:389-446), then what the reference's RL library does
 // between that function and the network in DDPGAgent.get_control (ddpg.py:83-87) -- GymEnvironment._make_state's cast to the observation
@@ -220,6 +224,7 @@ __device__ __forceinline__ void dev_policy_features(const FeatCfg &f, int e, int
         if (!live || live[e]) evals[e] = n + 1;                               // only the states whose rollout goes on ask the policy again (dqn.py:129-133)
     }
 }
+#ifdef STMPC_UNIT_CONTROL        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(64) k_policy_features(FeatCfg f, int N, int Kmax, const double *__restrict__ ego4, const int *__restrict__ k_count,
                                                         const double *__restrict__ ox, const double *__restrict__ ov, const double *__restrict__ oa,
                                                         const int *__restrict__ live, int *evals, float *feat, int stride) {
@@ -227,6 +232,7 @@ __global__ void __launch_bounds__(64) k_policy_features(FeatCfg f, int N, int Km
     if (e >= N) return;
     dev_policy_features(f, e, Kmax, ego4, k_count, ox, ov, oa, live, evals, feat + (size_t)e * stride);
 }
+#endif
 
 // Ordered list of the states whose decision needs st.do_st_control(start_state) (dqn.py:144-155; every branch but the
 // strictly-better comparison, which needs the controller's path for every state).  One workgroup, block-wide ordered compaction.
@@ -258,6 +264,7 @@ __device__ __forceinline__ void cc_select_body(CfgOf cfg_of, int N, const CCStat
     }
     if (tid == 0) *sel_count = base;
 }
+#ifdef STMPC_UNIT_CONTROL        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(1024) k_cc_select(CCfg c, int N, CCState st, const int *__restrict__ probe_crash, int *sel_idx, int *sel_count) {
     cc_select_body([&](int) -> const CCfg & { return c; }, N, st, probe_crash, sel_idx, sel_count);
 }
@@ -282,6 +289,7 @@ __global__ void __launch_bounds__(64) k_cc_scatter(int M, const int *__restrict_
     fine_len[e] = c_fine_len[j];
     for (int q = 0; q < fine_stride; ++q) fine[(size_t)e * fine_stride + q] = c_fine[(size_t)j * fine_stride + q];
 }
+#endif
 
 // ------------------------------------------------------------------------------------------------------------------
 // SUMO-free batched merge episodes (stands in for control.run_episode / control.step,
@@ -395,7 +403,9 @@ __device__ __forceinline__ void sim_init_body(const Cfg &c, int N, const State &
     if (e >= N) return;
     sim_init_env(c, s, e, c.seed);
 }
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(64) k_sim_init(Cfg c, int N, State s) { sim_init_body(c, N, s); }
+#endif
 // `s` moved on by `off` environments: rows [off, ...) of every array (a traffic group's slice of a grouped world)
 __device__ __forceinline__ State state_slice(const State &s, size_t off) {
     return State{s.ego4 + off * 4, s.nveh + off, s.vx + off * KS, s.vv + off * KS, s.va + off * KS, s.vc + off * KS, s.delay + off, s.status + off, s.ticks + off,
@@ -418,11 +428,13 @@ __device__ __forceinline__ void sim_view_env(const Cfg &c, int Kmax, const State
     for (int i = k; i < Kmax; ++i) { ox[(size_t)e * Kmax + i] = 0.0; ov[(size_t)e * Kmax + i] = 0.0; if (oa) oa[(size_t)e * Kmax + i] = 0.0; }
     k_count[e] = k;
 }
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(64) k_sim_view(Cfg c, int N, int Kmax, State s, double *ego5, int *k_count, double *ox, double *ov, double *oa) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     sim_view_env(c, Kmax, s, e, ego5, k_count, ox, ov, oa);
 }
+#endif
 // One simulator tick with the commanded ego speed: k_sim_step's body for the N environments `s` and `cmd_speed` point at.
 __device__ __forceinline__ void sim_step_body(const DevP &p, const Cfg &c, int N, const State &s, const double *__restrict__ cmd_speed, double crash_min_s) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -548,8 +560,10 @@ __device__ __forceinline__ void sim_step_body(const DevP &p, const Cfg &c, int N
     else if (crashed) s.status[e] = 2;
     else if (tk + 1 >= c.max_ticks) s.status[e] = 3;
 }
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(64) k_sim_step(DevP p, Cfg c, int N, State s, const double *__restrict__ cmd_speed, double crash_min_s) {
     sim_step_body(p, c, N, s, cmd_speed, crash_min_s);
 }
+#endif
 }  // namespace sim
 }  // namespace stmpc

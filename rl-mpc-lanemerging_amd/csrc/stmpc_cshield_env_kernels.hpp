@@ -37,6 +37,7 @@ __device__ __forceinline__ int cshield_evals_now(int rollout_time, const sim::St
     return w.evals_tag[e] == es.episode[e] ? w.evals[e] : 0;
 }
 
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 // k_env_act's dispatch (handle_action, called) + the controller's view, first action and time counter.  A finished environment gets the view
 // k_sim_view gives it and proposes its action from that state -- what episodes.EpisodeRunner(controller="combined") decides for a finished
 // environment -- while its step state is left alone, as k_env_act leaves it.  (Continuous jerks only: handle_action cannot refuse one.)
@@ -66,6 +67,7 @@ __global__ void __launch_bounds__(64) k_cshield_env_evals(int N, int rollout_tim
     if (e >= N) return;
     out[e] = cshield_evals_now(rollout_time, s, es, w, e);
 }
+#endif
 
 }  // namespace env
 }  // namespace stmpc

@@ -42,6 +42,7 @@ __device__ __forceinline__ ECfg cfg_of_row(const ECfg &c, const RewardTab &t, in
     return o;
 }
 
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 // k_env_act with the penalty of the environment's reward group (the only field of the action handling that may differ)
 __global__ void __launch_bounds__(64) k_env_act_rg(ECfg c, RewardTab tab, int N, sim::State s, EState es, const void *__restrict__ action) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -87,6 +88,7 @@ __global__ void __launch_bounds__(64) k_env_reward_rg(ECfg c, RewardTab tab, int
     out[e] = reward(ce, ego4[(size_t)e * 4 + 0], ego4[(size_t)e * 4 + 1], ego4[(size_t)e * 4 + 2], ego4[(size_t)e * 4 + 3], ox + (size_t)e * Kmax, n, jerk[e],
                     crashed && crashed[e] != 0, arrived && arrived[e] != 0);
 }
+#endif
 
 }  // namespace env
 }  // namespace stmpc

@@ -208,6 +208,7 @@ __device__ __forceinline__ void env_act_body(const ECfg &c, int e, const sim::St
     }
     es.cmd[e] = cmd; es.pjerk[e] = pjerk; es.inv[e] = inv;
 }
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(64) k_env_act(ECfg c, int N, sim::State s, EState es, const void *__restrict__ action) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
@@ -216,6 +217,7 @@ __global__ void __launch_bounds__(64) k_env_act(ECfg c, int N, sim::State s, ESt
     if (!live) return;                                                     // (k_sim_step idles finished environments)
     env_act_body(c, e, s, es, action);
 }
+#endif
 
 // `es` moved on by `off` environments (a traffic group's slice); the episode log, its counter and the error word stay the world's
 __device__ __forceinline__ EState estate_slice(const EState &es, size_t off) {
@@ -296,11 +298,13 @@ __device__ __forceinline__ void env_post_body(const ECfg &c, const sim::Cfg &sc,
     if (env_post_tick(c, sc, row0, e, s, es, obs, obs_stride, rew, term, trunc, final_obs, final_stats))
         env_post_autoreset(c, sc, seed, e, s, es, obs + (size_t)e * obs_stride);
 }
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(64) k_env_post(ECfg c, sim::Cfg sc, int N, sim::State s, EState es, float *__restrict__ obs, int obs_stride, double *__restrict__ rew,
                                                  unsigned char *__restrict__ term, unsigned char *__restrict__ trunc, float *__restrict__ final_obs,
                                                  double *__restrict__ final_stats) {
     env_post_body(c, sc, c.seed, 0, N, s, es, obs, obs_stride, rew, term, trunc, final_obs, final_stats);
 }
+#endif
 
 // Observation of every environment's current state and a fresh episode bookkeeping (stmpc_env_reset_device, after k_sim_init).
 __device__ __forceinline__ void env_reset_body(const ECfg &c, const sim::Cfg &sc, int N, const sim::State &s, const EState &es, float *__restrict__ obs, int obs_stride) {
@@ -309,10 +313,13 @@ __device__ __forceinline__ void env_reset_body(const ECfg &c, const sim::Cfg &sc
     es.episode[e] = 0; es.prev_a[e] = 0.0; es.ret[e] = 0.0; es.pjerk[e] = 0.0; es.inv[e] = 0.0; es.live[e] = 1;
     if (obs) env_obs(c, sc, s, es, e, obs + (size_t)e * obs_stride);
 }
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(64) k_env_reset(ECfg c, sim::Cfg sc, int N, sim::State s, EState es, float *__restrict__ obs, int obs_stride) {
     env_reset_body(c, sc, N, s, es, obs, obs_stride);
 }
+#endif
 
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 // The reward for arbitrary batched states (stmpc_env_reward_device): ego4 [N][4], other_x [N][Kmax] front to back, k [N].
 __global__ void __launch_bounds__(64) k_env_reward(ECfg c, int N, int Kmax, const double *__restrict__ ego4, const int *__restrict__ k, const double *__restrict__ ox,
                                                    const double *__restrict__ jerk, const int *__restrict__ crashed, const int *__restrict__ arrived, double *__restrict__ out) {
@@ -323,6 +330,7 @@ __global__ void __launch_bounds__(64) k_env_reward(ECfg c, int N, int Kmax, cons
     out[e] = reward(c, ego4[(size_t)e * 4 + 0], ego4[(size_t)e * 4 + 1], ego4[(size_t)e * 4 + 2], ego4[(size_t)e * 4 + 3], ox + (size_t)e * Kmax, n, jerk[e],
                     crashed && crashed[e] != 0, arrived && arrived[e] != 0);
 }
+#endif
 
 }  // namespace env
 }  // namespace stmpc

@@ -670,7 +670,7 @@ __device__ __forceinline__ double divc(double x, double d, double r) {
 // x / d for one of the launch's CONSTANT divisors (dt, dt^2, dt^3) in two operations: zh = RN(1/d), zl = RN(1/d - zh).
 // fma(x, zh, RN(x*zl)) equals x/d to 2^-105 relative before its rounding, i.e. it is RN(x/d) unless x/d lies within 2^-52 ulp
 // of a midpoint; for a given d only a few dozen significands x can come that close, and the host tries every one of them
-// (fastdiv2_ok in stmpc.hip; the argument and its exhaustive replay in small formats: tests/div2_check.py).
+// (fastdiv2_ok in stmpc_solver.hip; the argument and its exhaustive replay in small formats: tests/div2_check.py).
 // A divisor that fails the check, or was not checked, never gets here: FASTDIV is then false and x / d is used.
 template <bool FASTDIV>
 __device__ __forceinline__ double divk(double x, double d, double zh, double zl) {
@@ -759,7 +759,7 @@ struct SolveArgs {
     int prio_mode;         // (experiment: which estimate prio_thr is compared with)
     int prio_thr;          // first window: an overflowing search with more than this much left (layers x nodes) joins the front class of the next queue; 0 = off
     int retry_move;        // first window: after this many failed exact passes of an episode the next one runs in the second window (0 = never)
-    double bound_infl;     // a bounding pass's single-precision total times this is the bound (its rounding alone needs 1.00002; see stmpc.hip)
+    double bound_infl;     // a bounding pass's single-precision total times this is the bound (its rounding alone needs 1.00002; see stmpc_solve_plan.hpp)
     double last_infl;      // exact pass: factor on the bound in the candidate filter of the step INTO the last layer (>= 1; see dp_pass, vmin_bits)
     double retry_mult[3];  // growth of a bound that turned out to be below the reference's terminal cost: first, second, third repeat (then unbounded)
     unsigned *cu_tab;      // null = off
@@ -2456,6 +2456,7 @@ __global__ void __launch_bounds__(512, ((FANMAX <= 12 && NWX != 88) ? STMPC_MIN_
 }
 
 #ifndef STMPC_KERNELS_GROUPED_PASS
+#ifdef STMPC_UNIT_SOLVER        // (the kernels of the unit that launches them)
 // Heaviest-first order of the episodes for the exact phase (LPT): counting sort of the work estimates into
 // 64 logarithmic buckets, one workgroup.
 __global__ void __launch_bounds__(1024) k_order(int N, const unsigned *__restrict__ proxy, int *__restrict__ order) {
@@ -2531,6 +2532,7 @@ __global__ void k_probe(int op, const double *a, const double *b, double *out, i
     }
     out[i] = r;
 }
+#endif
 
 }  // namespace stmpc
 #endif  // first pass only

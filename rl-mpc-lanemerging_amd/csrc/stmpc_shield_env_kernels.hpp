@@ -24,6 +24,7 @@ struct ShieldView {                         // device arrays: the planner's view
     double *proposal;                       // [N] the proposed speed
 };
 
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 // k_env_act's dispatch (handle_action, called) + the shield's view and proposal.  A finished environment gets the view k_sim_view
 // gives it and proposes the speed its action would command from that state -- what episodes.EpisodeRunner(controller="first_step") proposes for a
 // finished environment, so that the context's stmpc_first_step_counts are the runner's row for row -- while its step state is left alone, as
@@ -84,6 +85,7 @@ __global__ void __launch_bounds__(64) k_shield_env_apply(ECfg c, double takeover
     if (exec_action) exec_action[e] = take ? clip(pjerk, c.j_min, c.j_max) : ((const double *)action)[e];
     takeover_ticks[e] = cnt;
 }
+#endif
 
 }  // namespace env
 }  // namespace stmpc

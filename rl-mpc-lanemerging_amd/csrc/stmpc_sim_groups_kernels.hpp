@@ -18,6 +18,7 @@
 namespace stmpc {
 namespace sim {
 
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 __global__ void __launch_bounds__(64) k_sim_init_groups(const Cfg *__restrict__ groups, int n_per_group, State s) {
     const Cfg c = groups[blockIdx.y];
     sim_init_body(c, n_per_group, state_slice(s, (size_t)blockIdx.y * n_per_group));
@@ -29,11 +30,13 @@ __global__ void __launch_bounds__(64) k_sim_step_groups(DevP p, const Cfg *__res
     const size_t off = (size_t)blockIdx.y * n_per_group;
     sim_step_body(p, c, n_per_group, state_slice(s, off), cmd_speed + off, crash_min_s);
 }
+#endif
 
 }  // namespace sim
 
 namespace env {
 
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 // obs, rew, term, trunc, final_obs and final_stats have G * n_per_group rows
 __global__ void __launch_bounds__(64) k_env_post_groups(ECfg c, const sim::Cfg *__restrict__ groups, int n_per_group, sim::State s, EState es, float *__restrict__ obs,
                                                         int obs_stride, double *__restrict__ rew, unsigned char *__restrict__ term, unsigned char *__restrict__ trunc,
@@ -51,6 +54,7 @@ __global__ void __launch_bounds__(64) k_env_reset_groups(ECfg c, const sim::Cfg 
     const size_t off = (size_t)blockIdx.y * n_per_group;
     env_reset_body(c, sc, n_per_group, sim::state_slice(s, off), estate_slice(es, off), obs ? obs + off * obs_stride : nullptr, obs_stride);
 }
+#endif
 
 }  // namespace env
 }  // namespace stmpc

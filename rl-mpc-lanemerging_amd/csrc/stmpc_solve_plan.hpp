@@ -1,7 +1,7 @@
 // stmpc_solve_plan.hpp -- what one batched solve launches, decided in plain C++ before anything touches the device.
 // plan_solve() is a pure function of the settings (SolveKnobs), the device's shape, the parameter set and the batch's shape: which windows (tiers)
 // there are, their grids and LDS bytes, which k_solve instantiation serves each (KernelVariant), and the order of the launches with their streams
-// and events (SolvePlan::steps).  solve_device() in stmpc.hip carries a plan out; tests/solve_plan_check.cpp prints one on a CPU.
+// and events (SolvePlan::steps).  solve_device() in stmpc_solver.hip carries a plan out; tests/solve_plan_check.cpp prints one on a CPU.
 // No HIP here: the parameter set is any struct with DevP's fields (stmpc_kernels.hpp).
 #ifndef STMPC_SOLVE_PLAN_HPP
 #define STMPC_SOLVE_PLAN_HPP
@@ -161,7 +161,7 @@ struct SolveHistory {
 // The template arguments of one k_solve instantiation (GRID is false in every batched launch); grouped: the kernel of namespace grouped
 struct KernelVariant { bool use_lds, fastdiv; int kt, fanmax; bool s1gen; int res, nwx; bool grouped; };
 
-// The instantiations the library is built with: exactly what plan_solve can store in a PlanTier -- launch_k_solve (stmpc.hip) compiles these and
+// The instantiations the library is built with: exactly what plan_solve can store in a PlanTier -- launch_k_solve (stmpc_solver.hip) compiles these and
 // refuses any other.  46: 32 lone, 14 grouped.
 constexpr bool variant_built(const KernelVariant &v) {
     const bool fan = v.fanmax == 9 || v.fanmax == STMPC_FAN1, full = v.nwx == STMPC_MAXWAVES;

@@ -43,6 +43,7 @@ namespace stmpc {
 
 namespace sim {
 
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 // k_sim_step_groups with the closest-distance gate (es > crash_min_s) of the traffic group's own solver group: crash_min_s[blockIdx.y]
 __global__ void __launch_bounds__(64) k_sim_step_solver_groups(DevP p, const Cfg *__restrict__ groups, int n_per_group, State s, const double *__restrict__ cmd_speed,
                                                                const double *__restrict__ crash_min_s) {
@@ -50,6 +51,7 @@ __global__ void __launch_bounds__(64) k_sim_step_solver_groups(DevP p, const Cfg
     const size_t off = (size_t)blockIdx.y * n_per_group;
     sim_step_body(p, c, n_per_group, state_slice(s, off), cmd_speed + off, crash_min_s[blockIdx.y]);
 }
+#endif
 
 }  // namespace sim
 }  // namespace stmpc

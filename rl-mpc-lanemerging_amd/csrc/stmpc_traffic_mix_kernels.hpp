@@ -55,6 +55,7 @@ __device__ __forceinline__ sim::Cfg cfg_of_type(const sim::Cfg &c, const Traffic
     return o;
 }
 
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
 // Episode 0 of every environment: its type, k_sim_init's work under that type's cfg, then k_env_reset's.  traffic_type may be NULL.
 __global__ void __launch_bounds__(64) k_env_reset_mix(ECfg c, sim::Cfg sc, TrafficMix m, int N, sim::State s, EState es, float *__restrict__ obs, int obs_stride,
                                                       int *__restrict__ traffic_type) {
@@ -95,6 +96,7 @@ __global__ void __launch_bounds__(64) k_env_post_mix(ECfg c, sim::Cfg sc, Traffi
     traffic_type[e] = next;
     final_traffic_type[e] = t;
 }
+#endif
 
 }  // namespace env
 }  // namespace stmpc

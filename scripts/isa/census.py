@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ISA census of one kernel of csrc/stmpc.hip (gfx950 assembly from `hipcc --cuda-device-only -S`).
+"""ISA census of one kernel of a unit of csrc/ (stmpc_solver.hip for k_solve) (gfx950 assembly from `hipcc --cuda-device-only -S`).
 usage: scripts/isa/census.py <stmpc.s> <substring of the mangled kernel name> [--blocks]
 Prints the kernel's resource footer, and per loop depth the instruction count, the spill moves (v_readlane / v_writelane that implement
 SGPR spills, scratch_ loads / stores that implement VGPR spills) -- the evidence that spills sit outside the hot loops -- and, with

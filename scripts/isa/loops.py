@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Loop tree of one kernel of csrc/stmpc.hip with the spill traffic of every loop's OWN blocks (sub-loops excluded).
+"""Loop tree of one kernel of a unit of csrc/ (stmpc_solver.hip for k_solve) with the spill traffic of every loop's OWN blocks (sub-loops excluded).
 usage: scripts/isa/loops.py <stmpc.s> <substring of the mangled kernel name>
 For each loop: depth, header, parent, instructions / v_readlane+v_writelane (SGPR spill moves) / scratch_ (VGPR spill) / barriers in the
 blocks that belong to this loop and to none of its sub-loops, and markers that identify the loop in the source:

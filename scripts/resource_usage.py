@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compile csrc/stmpc.hip with -Rpass-analysis=kernel-resource-usage and print one row per kernel
+"""Compile the units of csrc/ (build.UNITS) with -Rpass-analysis=kernel-resource-usage and print one row per kernel
 (registers, spills, scratch, occupancy, static LDS).  Usage: scripts/resource_usage.py [out.txt] [extra hipcc flags...]"""
 import os, re, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,9 +10,9 @@ def main():
     out = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else None
     extra = [a for a in sys.argv[1:] if a.startswith("-")]
     b = pkg.build
-    cmd = [b.find_hipcc()] + b.HIPCC_FLAGS + extra + ["-I" + os.path.join(REPO, "include"), os.path.join(b.CSRC, "stmpc.hip"),
+    cmd = [b.find_hipcc()] + b.HIPCC_FLAGS + extra + ["-I" + os.path.join(REPO, "include")] + [b.unit_source(u) for u in b.UNITS] + [
            "-o", "/tmp/libstmpc_ru.so", "-Rpass-analysis=kernel-resource-usage"]
-    txt = subprocess.run(cmd, capture_output=True, text=True).stderr
+    txt = subprocess.run(cmd, capture_output=True, text=True).stderr      # (a kernel is compiled in one unit only: one row per kernel)
     rows, cur = [], None
     for line in txt.splitlines():
         m = re.search(r"remark:\s+(.*?)\s*\[-Rpass", line)

@@ -7,7 +7,7 @@ midpoint of two adjacent floats.  For p-bit mantissas X (of x) and D (odd part o
 them; verify() runs the actual two-operation sequence on every one of them (and their neighbours).  This file is the
 prototype and the self-test of that argument (test infrastructure: only tests/ import it): toy_exhaustive() replays it in a 10..12-bit floating-point format where ALL
 (X, D) pairs can be tried, and checks that every failing pair is among the candidates.  The product's C++ twin is
-fastdiv2_ok() in stmpc.hip.  (Brisebarre & Muller, "Correctly rounded multiplication by arbitrary precision constants",
+fastdiv2_ok() in stmpc_solver.hip.  (Brisebarre & Muller, "Correctly rounded multiplication by arbitrary precision constants",
 IEEE TC 2008, give the general theory; only the elementary bound above is used here.)"""
 from fractions import Fraction
 import math, random, sys

@@ -1,4 +1,4 @@
-"""Two-operation division by dt, dt^2, dt^3 (divk in stmpc_kernels.hpp; host check fastdiv2_ok in stmpc.hip): the argument is
+"""Two-operation division by dt, dt^2, dt^3 (divk in stmpc_kernels.hpp; host check fastdiv2_ok in stmpc_solver.hip): the argument is
 replayed exhaustively in small floating-point formats, the library's check is compared with an exact-arithmetic prototype
 (tests/div2_check.py), and on the GPU the sequence is run on exactly the inputs that come closest to a rounding
 boundary -- for divisors that pass the check and for one that does not."""
