@@ -1055,6 +1055,62 @@ int stmpc_cshield_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const s
                                   void *stream);
 int stmpc_cshield_env_evals_device(stmpc_ctx *ctx, int N, int32_t *d_evals, void *stream);
 
+/*
+ * First-step shield for grouped and mixed-traffic vector environments: stmpc_shield_env_step_device in front of the env's group axes -- traffic groups
+ * (the reference's traffic types, configs/train_*_*.json, control.py:215-226), reward groups (its per-run reward settings, dqn.py:449-563,
+ * merge_gym.py:25) and the traffic mix -- so that the per-traffic-type training matrix, a reward-shaping sweep and a mixed-traffic policy train in
+ * the closed loop of st.do_conditional_st_based_on_first_step (st.py:805-814).  (Additive: new entries only, no signature or struct of ABI 8 changes,
+ * so STMPC_ABI_VERSION stays 8.)
+ * Nothing in the shield reads the traffic type or the reward.  One step is the lone shielded step, in as many launches: the action stage with the
+ * world cfg of the environment's traffic group or of its episode's traffic type and the invalid-action penalty of its reward group -> the body of
+ * stmpc_first_step_device on all N rows (the context's stmpc_first_step_counts advance by N) -> the takeover branch of
+ * stmpc_shield_env_step_device under the takeover penalty of the environment's group -> the world step and the reward / observation / autoreset
+ * kernel of the env's shape (stmpc_env_step_groups_device's, stmpc_reward_groups_env_step_device's, stmpc_traffic_mix_env_step_device's).  Rows of
+ * group g are, bit for bit and through every autoreset, the rows of the lone env reset through stmpc_shield_env_reset_device with group g's sim cfg,
+ * reward settings and takeover penalty; an episode of the shielded mix is the lone shielded env's episode of the drawn type.
+ * The takeover penalties belong to the RESET: takeover_penalties is a host array of P values, P = the number of groups (G, or R), or 1 (one value for
+ * every group), or P = 0 (takeover_penalties may be NULL): shield_cfg->takeover_penalty for every group.  Each finite and >= 0.  The step entries
+ * check shield_cfg->takeover_penalty as the lone step does and do not read it further: they apply the reset's table.  The mix has no groups: its
+ * reset takes shield_cfg->takeover_penalty.
+ *   stmpc_shield_traffic_groups_env_reset_device / stmpc_shield_traffic_groups_env_step_device
+ *                       stmpc_env_reset_groups_device / stmpc_env_step_groups_device behind the shield.
+ *   stmpc_shield_reward_groups_env_reset_device / stmpc_shield_reward_groups_env_step_device
+ *                       stmpc_reward_groups_env_reset_device / stmpc_reward_groups_env_step_device behind the shield: G = 0 (an ungrouped world from
+ *                       sim_cfgs[0]) or G == R traffic groups that coincide with the reward groups.
+ *   stmpc_shield_traffic_mix_env_reset_device / stmpc_shield_traffic_mix_env_step_device
+ *                       stmpc_traffic_mix_env_reset_device / stmpc_traffic_mix_env_step_device behind the shield; the step's d_traffic_type and
+ *                       d_final_traffic_type follow the shield's outputs.
+ * Each reset takes the arguments of its unshielded twin with shield_cfg (and the penalties) after the env cfgs; each step the arguments of its twin
+ * with shield_cfg after env_cfg, then the five outputs of stmpc_shield_env_step_device (d_executed_action NULL for a discrete env).  Every argument
+ * check of a reset -- the twin's and stmpc_shield_env_reset_device's -- runs before anything changes; the shield's buffers and the penalty table are
+ * sized by the reset (the upload synchronises on `stream`), the step allocates nothing.  A step returns STMPC_EINVAL -- before its first launch, the
+ * world as it was -- on a context that was not reset through its own reset entry, for another N, and for a kmax that is out of range or not the
+ * reset's.  Every other env step entry and the lone stmpc_shield_env_step_device return STMPC_EINVAL on such an env: unlike the lone shielded env,
+ * whose unshielded step stmpc_env_step_device stays legal, a shielded env with groups or a mix has no unshielded step.
+ */
+int stmpc_shield_traffic_groups_env_reset_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *cfgs, int G, int n_per_group,
+                                         const stmpc_env_cfg *env_cfg, const stmpc_shield_env_cfg *shield_cfg, const double *takeover_penalties, int P,
+                                         float *d_obs, int obs_stride, void *stream);
+int stmpc_shield_traffic_groups_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_env_cfg *env_cfg, const stmpc_shield_env_cfg *shield_cfg, int N,
+                                        const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
+                                        float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk,
+                                        double *d_executed_action, int32_t *d_takeover_ticks, void *stream);
+int stmpc_shield_reward_groups_env_reset_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int G, int n_per_traffic_group,
+                                                const stmpc_env_cfg *env_cfgs, int R, int n_per_reward_group, const stmpc_shield_env_cfg *shield_cfg,
+                                                const double *takeover_penalties, int P, float *d_obs, int obs_stride, void *stream);
+int stmpc_shield_reward_groups_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_env_cfg *env_cfg, const stmpc_shield_env_cfg *shield_cfg,
+                                               int N, const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated,
+                                               uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason,
+                                               double *d_executed_jerk, double *d_executed_action, int32_t *d_takeover_ticks, void *stream);
+int stmpc_shield_traffic_mix_env_reset_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int T, const double *weights,
+                                              uint64_t mix_seed, const stmpc_env_cfg *env_cfg, const stmpc_shield_env_cfg *shield_cfg, int N, float *d_obs,
+                                              int obs_stride, int32_t *d_traffic_type, void *stream);
+int stmpc_shield_traffic_mix_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_env_cfg *env_cfg, const stmpc_shield_env_cfg *shield_cfg,
+                                             int N, const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated,
+                                             uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason,
+                                             double *d_executed_jerk, double *d_executed_action, int32_t *d_takeover_ticks, int32_t *d_traffic_type,
+                                             int32_t *d_final_traffic_type, void *stream);
+
 /* Device arithmetic probe used by the parity tests: out[i] = a[i] op b[i] evaluated on the GPU
  * with the kernels' compile flags. op: 0 div, 1 sqrt(a), 2 mul, 3 add, 4 fma(a,a,b*b), 5 the five-operation
  * quotient a/b of the FASTDIV kernels, 6 their two-operation quotient a/b.  HOST pointers. */

@@ -271,6 +271,9 @@ EXPORTS = (
     "stmpc_shield_env_reset_device", "stmpc_shield_env_step_device",
     "stmpc_traffic_mix_env_reset_device", "stmpc_traffic_mix_env_step_device", "stmpc_traffic_mix_draw",
     "stmpc_cshield_env_reset_device", "stmpc_cshield_env_step_device", "stmpc_cshield_env_evals_device",
+    "stmpc_shield_traffic_groups_env_reset_device", "stmpc_shield_traffic_groups_env_step_device",
+    "stmpc_shield_reward_groups_env_reset_device", "stmpc_shield_reward_groups_env_step_device",
+    "stmpc_shield_traffic_mix_env_reset_device", "stmpc_shield_traffic_mix_env_step_device",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
 KMAX_LIMIT = 32      # STMPC_KMAX_LIMIT
@@ -453,6 +456,13 @@ def load():
     lib.stmpc_cshield_env_reset_device.argtypes = [vp, pp, sp, ep, csp, vp, C.c_int, vp, C.c_int, vp]
     lib.stmpc_cshield_env_step_device.argtypes = [vp, pp, sp, ep, csp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.stmpc_cshield_env_evals_device.argtypes = [vp, C.c_int, vp, vp]
+    shield_step = [vp, pp, ep, shp, C.c_int, vp, vp, C.c_int] + [vp] * 10         # ctx ... N, d_action, d_obs, obs_stride, the step's and the shield's outputs
+    lib.stmpc_shield_traffic_groups_env_reset_device.argtypes = [vp, pp, sp, C.c_int, C.c_int, ep, shp, dp, C.c_int, vp, C.c_int, vp]
+    lib.stmpc_shield_traffic_groups_env_step_device.argtypes = shield_step + [vp]
+    lib.stmpc_shield_reward_groups_env_reset_device.argtypes = [vp, pp, sp, C.c_int, C.c_int, ep, C.c_int, C.c_int, shp, dp, C.c_int, vp, C.c_int, vp]
+    lib.stmpc_shield_reward_groups_env_step_device.argtypes = shield_step + [vp]
+    lib.stmpc_shield_traffic_mix_env_reset_device.argtypes = [vp, pp, sp, C.c_int, dp, C.c_uint64, ep, shp, C.c_int, vp, C.c_int, vp, vp]
+    lib.stmpc_shield_traffic_mix_env_step_device.argtypes = shield_step + [vp, vp, vp]
     _lib = lib
     return lib
 
@@ -1064,6 +1074,72 @@ class Context:
     def cshield_env_evals(self, N, d_evals, stream=0):
         """``stmpc_cshield_env_evals_device``: the count the next step's proposal is evaluated at, int32 [N] on the device."""
         self._chk(self._lib.stmpc_cshield_env_evals_device(self._h, int(N), d_evals, stream))
+
+    # -- first-step shield on traffic groups, reward groups and the traffic mix (stmpc_shield_*groups* / stmpc_shield_traffic_mix_*; see include/stmpc.h) ----
+    @staticmethod
+    def _penalties(takeover_penalties):
+        """(pointer, P) of a reset's ``takeover_penalties``: None -> (NULL, 0), the shield cfg's penalty for every group."""
+        if takeover_penalties is None:
+            return None, 0, None
+        w = np.ascontiguousarray(takeover_penalties, dtype=np.float64).reshape(-1)
+        return _dptr(w), int(w.size), w
+
+    def shield_env_reset_groups(self, params, cfgs, n_per_group, env_cfg, shield_cfg, takeover_penalties, d_obs, obs_stride, stream=0):
+        """``stmpc_shield_traffic_groups_env_reset_device``; ``takeover_penalties``: None, or 1 or G numbers."""
+        t = SimCfgTable.of(cfgs)
+        ptr, P, keep = self._penalties(takeover_penalties)
+        self._chk(self._lib.stmpc_shield_traffic_groups_env_reset_device(self._h, C.byref(params), t.array, len(t), int(n_per_group), C.byref(env_cfg), C.byref(shield_cfg),
+                                                                 ptr, P, d_obs, int(obs_stride), stream))
+
+    def shield_env_reset_reward_groups(self, params, sim_cfgs, n_per_traffic_group, env_cfgs, n_per_reward_group, shield_cfg, takeover_penalties, d_obs,
+                                       obs_stride, stream=0):
+        """``stmpc_shield_reward_groups_env_reset_device``; ``sim_cfgs`` and ``env_cfgs`` as ``env_reset_reward_groups`` takes them."""
+        e = EnvCfgTable.of(env_cfgs)
+        if isinstance(sim_cfgs, SimCfg):
+            sims, G = C.byref(sim_cfgs), 0
+        else:
+            t = SimCfgTable.of(sim_cfgs)
+            sims, G = t.array, len(t)
+        ptr, P, keep = self._penalties(takeover_penalties)
+        self._chk(self._lib.stmpc_shield_reward_groups_env_reset_device(self._h, C.byref(params), sims, G, int(n_per_traffic_group), e.array, len(e),
+                                                                        int(n_per_reward_group), C.byref(shield_cfg), ptr, P, d_obs, int(obs_stride), stream))
+
+    def shield_traffic_mix_env_reset(self, params, sim_cfgs, weights, mix_seed, env_cfg, shield_cfg, N, d_obs, obs_stride, d_traffic_type=0, stream=0):
+        """``stmpc_shield_traffic_mix_env_reset_device``; ``sim_cfgs`` and ``weights`` as ``traffic_mix_env_reset`` takes them."""
+        t = SimCfgTable.of(sim_cfgs)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != len(t):
+            raise ValueError("%d weights for %d traffic types" % (w.size, len(t)))
+        self._chk(self._lib.stmpc_shield_traffic_mix_env_reset_device(self._h, C.byref(params), t.array, len(t), _dptr(w), C.c_uint64(int(mix_seed) & 0xFFFFFFFFFFFFFFFF),
+                                                                      C.byref(env_cfg), C.byref(shield_cfg), int(N), d_obs, int(obs_stride), d_traffic_type or None,
+                                                                      stream))
+
+    def _shield_groups_step(self, entry, params, env_cfg, shield_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs,
+                            d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks, *tail):
+        self._chk(entry(self._h, C.byref(params), C.byref(env_cfg), C.byref(shield_cfg), int(N), d_action, d_obs, int(obs_stride), d_reward, d_terminated,
+                        d_truncated, d_final_obs, d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action or None, d_takeover_ticks, *tail))
+
+    def shield_env_step_groups(self, params, env_cfg, shield_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs,
+                               d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks, stream=0):
+        """``stmpc_shield_traffic_groups_env_step_device``; ``d_executed_action``: 0 for a discrete env."""
+        self._shield_groups_step(self._lib.stmpc_shield_traffic_groups_env_step_device, params, env_cfg, shield_cfg, N, d_action, d_obs, obs_stride, d_reward,
+                                 d_terminated, d_truncated, d_final_obs, d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action,
+                                 d_takeover_ticks, stream)
+
+    def shield_env_step_reward_groups(self, params, env_cfg, shield_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs,
+                                      d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks, stream=0):
+        """``stmpc_shield_reward_groups_env_step_device``."""
+        self._shield_groups_step(self._lib.stmpc_shield_reward_groups_env_step_device, params, env_cfg, shield_cfg, N, d_action, d_obs, obs_stride, d_reward,
+                                 d_terminated, d_truncated, d_final_obs, d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action,
+                                 d_takeover_ticks, stream)
+
+    def shield_traffic_mix_env_step(self, params, env_cfg, shield_cfg, N, d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs,
+                                    d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks, d_traffic_type,
+                                    d_final_traffic_type, stream=0):
+        """``stmpc_shield_traffic_mix_env_step_device``."""
+        self._shield_groups_step(self._lib.stmpc_shield_traffic_mix_env_step_device, params, env_cfg, shield_cfg, N, d_action, d_obs, obs_stride, d_reward,
+                                 d_terminated, d_truncated, d_final_obs, d_final_stats, d_takeover, d_reason, d_executed_jerk, d_executed_action,
+                                 d_takeover_ticks, d_traffic_type, d_final_traffic_type, stream)
 
     # -- traffic mix (stmpc_traffic_mix_*; see include/stmpc.h) ---------------------------------------------------
     def traffic_mix_env_reset(self, params, sim_cfgs, weights, mix_seed, env_cfg, N, d_obs, obs_stride, d_traffic_type=0, stream=0):

@@ -1085,6 +1085,7 @@ int sim_init_groups(stmpc_ctx *c, const stmpc_sim_cfg *cfgs, int G, int n_per_gr
 const char *const GROUPED_WORLD = "the world has traffic groups (stmpc_sim_init_groups_device): one cfg would step every group; use the grouped step entry";
 const char *const MIXED_ENV = "the env has a traffic mix (stmpc_traffic_mix_env_reset_device): one cfg would step every type; use stmpc_traffic_mix_env_step_device";
 const char *const CSHIELD_ENV = "the env runs behind the combined controller (stmpc_cshield_env_reset_device): this entry would execute the proposal unprotected; use stmpc_cshield_env_step_device";
+const char *const SHIELDED_ENV = "the env runs behind the first-step shield (a stmpc_shield_*_reset_device entry): this entry would execute the proposal unprotected; use the shielded step entry of the env's groups";
 bool has_cshield_env(const stmpc_ctx *c) { return c->env.N >= 1 && c->cshield.N == c->env.N && c->cshield.generation == c->sim.generation; }
 const char *const REWARD_GROUPED_ENV = "the env has reward groups (stmpc_reward_groups_env_reset_device): one cfg would reward every group; use stmpc_reward_groups_env_step_device";
 }  // namespace
@@ -1346,6 +1347,66 @@ int shield_cfg_check(const stmpc_params *p, const stmpc_shield_env_cfg *sh, int 
     if (!(sh->takeover_penalty >= 0) || !(sh->takeover_penalty <= 1.7976931348623157e308)) return fail(STMPC_EINVAL, "shield cfg: takeover_penalty must be finite and not negative");
     return first_step_check(p, &sh->fs, N, sh->kmax);
 }
+// The checks of a shielded reset (nothing changes).  `count`: 0 for the lone shielded env, whose step takes sh->takeover_penalty by value (no table); else the
+// env's groups (1 for the traffic mix), and `table` receives the takeover penalties the step reads: the P = 1 or P = count values of
+// `penalties`, or (P = 0) the one sh->takeover_penalty.
+struct ShieldReset {
+    std::vector<double> table;
+    int N = 0, H = 0;
+};
+int shield_reset_check(stmpc_ctx *c, const stmpc_params *p, const stmpc_shield_env_cfg *sh, int N, const double *penalties, int P, int count, ShieldReset *r) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    TRY(shield_cfg_check(p, sh, N));
+    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
+    DevP dp;
+    TRY(make_devp(p, &dp));
+    r->N = N; r->H = dp.H;
+    if (!count) return STMPC_OK;
+    if (P < 0 || (P > 0 && !penalties) || (P != 0 && P != 1 && P != count))
+        return fail(STMPC_EINVAL, "takeover_penalties: P must be 0 (shield_cfg's takeover_penalty for every group), 1 or the number of groups (" + std::to_string(count) + ")");
+    r->table.assign(penalties, penalties + P);
+    if (!P) r->table.push_back(sh->takeover_penalty);
+    for (size_t i = 0; i < r->table.size(); ++i)
+        if (!(r->table[i] >= 0) || !(r->table[i] <= 1.7976931348623157e308))
+            return fail(STMPC_EINVAL, "takeover_penalties must be finite and not negative (group " + std::to_string(i) + ")");
+    return STMPC_OK;
+}
+// ... and what follows the env's reset: the shield's buffers (view, proposal, decision, counters, zeroed), the first-step controller's, the penalty table
+int shield_reset_finish(stmpc_ctx *c, const stmpc_shield_env_cfg *sh, const ShieldReset &r, void *stream) {
+    auto &v = c->shield;                         // (the world initialised by the env's reset has outdated an earlier shielded env by its generation)
+    const int N = r.N;
+    TRY(v.ensure(N, sh->kmax));
+    TRY(first_step_ensure(c, N, sh->kmax, r.H, true));        // (the sparse solve's compact batch too: a step may set fs.sparse_control either way)
+    HIPCHK(hipMemsetAsync(v.count.p, 0, (size_t)N * 4, (hipStream_t)stream));
+    HIPCHK(hipMemsetAsync(v.tag.p, 0, (size_t)N * 4, (hipStream_t)stream));
+    v.P = 0; v.n_per_penalty = 0;
+    if (!r.table.empty()) {
+        TRY(v.penalty.ensure((size_t)STMPC_SIM_GROUPS_MAX * 8));      // (its full size once: never reallocated under a running kernel)
+        HIPCHK(hipMemcpyAsync(v.penalty.p, r.table.data(), r.table.size() * 8, hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));       // (the table is the caller's local; the step reads the device copy)
+        v.P = (int)r.table.size(); v.n_per_penalty = N / v.P;
+    }
+    v.N = N; v.kmax = sh->kmax; v.generation = c->sim.generation;
+    return STMPC_OK;
+}
+// the checks of a reward-groups reset (nothing changes): the table rows, the shared cfg, N = R * n_per_reward_group
+struct RewardGroupsReset {
+    std::vector<env::RewardRow> rows;
+    env::ECfg e;
+    int N = 0;
+};
+int reward_groups_reset_check(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int G, int n_per_traffic_group, const stmpc_env_cfg *env_cfgs,
+                              int R, int n_per_reward_group, const float *d_obs, int obs_stride, RewardGroupsReset *rg) {
+    std::vector<sim::Cfg> world;
+    TRY(check_reward_groups(c, p, env_cfgs, R, n_per_reward_group, d_obs, obs_stride, &rg->rows, &rg->e));
+    rg->N = R * n_per_reward_group;
+    if (G < 0) return fail(STMPC_EINVAL, "G must not be negative (0: an ungrouped world from sim_cfgs[0])");
+    TRY(check_groups(sim_cfgs, G ? G : 1, G ? n_per_traffic_group : rg->N, &world));       // (G = 0: the one cfg and its route, as a table of one)
+    if (G && (G != R || n_per_traffic_group != n_per_reward_group))
+        return fail(STMPC_EINVAL, "the reward groups must coincide with the world's traffic groups (cell c pairs traffic c with reward c): R must equal G and "
+                                  "n_per_reward_group n_per_traffic_group");
+    return STMPC_OK;
+}
 
 // the combined-shield env's cfg and actor (its reset and its step): `cc`, `fc` receive the kernels' forms
 int cshield_cfg_check(const stmpc_ctx *c, const stmpc_params *p, const stmpc_cshield_env_cfg *sh, const stmpc_actor *a, int N, CCfg *cc, FeatCfg *fc) {
@@ -1371,11 +1432,15 @@ struct EnvEntry {
     Need traffic_groups, reward_groups, shield, traffic_mix, cshield;
 };
 const EnvEntry PLAIN_ENV{"stmpc_env_reset_device", REFUSED, REFUSED, EITHER, REFUSED, REFUSED};       // (on a shield-reset context: the unshielded step)
-const EnvEntry TRAFFIC_GROUPS_ENV{"stmpc_env_reset_groups_device", REQUIRED, REFUSED, EITHER, REFUSED, REFUSED};
-const EnvEntry REWARD_GROUPS_ENV{"stmpc_reward_groups_env_reset_device", EITHER, REQUIRED, EITHER, REFUSED, REFUSED};
+// (the unshielded grouped entries refuse a shielded env: only the lone shielded env, whose world takes one cfg, has an unshielded step)
+const EnvEntry TRAFFIC_GROUPS_ENV{"stmpc_env_reset_groups_device", REQUIRED, REFUSED, REFUSED, REFUSED, REFUSED};
+const EnvEntry REWARD_GROUPS_ENV{"stmpc_reward_groups_env_reset_device", EITHER, REQUIRED, REFUSED, REFUSED, REFUSED};
 const EnvEntry SHIELD_ENV{"stmpc_shield_env_reset_device", REFUSED, REFUSED, REQUIRED, REFUSED, REFUSED};
 const EnvEntry TRAFFIC_MIX_ENV{"stmpc_traffic_mix_env_reset_device", REFUSED, REFUSED, REFUSED, REQUIRED, REFUSED};
 const EnvEntry CSHIELD_ENV_ENTRY{"stmpc_cshield_env_reset_device", REFUSED, REFUSED, REFUSED, REFUSED, REQUIRED};
+const EnvEntry SHIELD_TRAFFIC_GROUPS_ENV{"stmpc_shield_traffic_groups_env_reset_device", REQUIRED, REFUSED, REQUIRED, REFUSED, REFUSED};
+const EnvEntry SHIELD_REWARD_GROUPS_ENV{"stmpc_shield_reward_groups_env_reset_device", EITHER, REQUIRED, REQUIRED, REFUSED, REFUSED};
+const EnvEntry SHIELD_TRAFFIC_MIX_ENV{"stmpc_shield_traffic_mix_env_reset_device", REFUSED, REFUSED, REQUIRED, REQUIRED, REFUSED};
 
 int env_shape_check(const stmpc_ctx *c, const EnvEntry &who) {
     const auto &v = c->shield;
@@ -1383,8 +1448,8 @@ int env_shape_check(const stmpc_ctx *c, const EnvEntry &who) {
         {c->sim.G > 0, who.traffic_groups, GROUPED_WORLD, UNGROUPED_WORLD},
         {c->env.N >= 1 && c->env.R >= 1, who.reward_groups, REWARD_GROUPED_ENV,
          "the env has no reward groups (stmpc_reward_groups_env_reset_device): use the plain or the traffic-groups step entry"},
-        {c->env.N >= 1 && v.N == c->env.N && v.generation == c->sim.generation, who.shield, "the env was reset through stmpc_shield_env_reset_device: the traffic mix does not run behind the shield",
-         "the environment in this context was not reset through stmpc_shield_env_reset_device"},
+        {c->env.N >= 1 && v.N == c->env.N && v.generation == c->sim.generation, who.shield, SHIELDED_ENV,
+         "the environment in this context was not reset through stmpc_shield_env_reset_device or a shielded reset entry of its groups"},
         {c->env.N >= 1 && c->env.T >= 1, who.traffic_mix, MIXED_ENV, "the environment in this context was not reset through stmpc_traffic_mix_env_reset_device"},
         {has_cshield_env(c), who.cshield, CSHIELD_ENV, "the environment in this context was not reset through stmpc_cshield_env_reset_device"},
     };
@@ -1511,7 +1576,7 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
             return fail(STMPC_EINVAL, "combined shield cfg: kmax, rollout_time or the rollout length differs from the one the context was reset with (stmpc_cshield_env_reset_device)");
     } else if (sh) {
         TRY(shield_cfg_check(p, sh->cfg, N));
-        if (sh->cfg->kmax != v.kmax) return fail(STMPC_EINVAL, "shield cfg: kmax differs from the one the context was reset with (stmpc_shield_env_reset_device)");
+        if (sh->cfg->kmax != v.kmax) return fail(STMPC_EINVAL, std::string("shield cfg: kmax differs from the one the context was reset with (") + who.reset_entry + ")");
     }
     if (!o.action || !o.obs || !o.reward || !o.terminated || !o.truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     if (sh && (!sh->takeover || !sh->reason || !sh->executed_jerk || !sh->takeover_ticks)) return fail(STMPC_EINVAL, "NULL device pointer (shield outputs)");
@@ -1525,6 +1590,8 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
     if (cs && e.mode != env::ACT_CONTINUOUS_JERK) return fail(STMPC_EINVAL, "the combined shield serves STMPC_ENV_CONTINUOUS_JERK only (the rollout policy is a continuous actor)");
     // the world: one cfg -- the caller's, or the one an ungrouped reward-groups reset kept -- or the context's table of traffic groups
     const bool grouped = c->sim.G > 0, reward_groups = who.reward_groups == REQUIRED;
+    if (sh && !cs && (grouped || reward_groups || mix) && (v.P < 1 || (int64_t)v.P * v.n_per_penalty != N))         // (what k_shield_env_apply_groups indexes)
+        return fail(STMPC_EINVAL, std::string("the context holds no takeover penalty table for this env (") + who.reset_entry + ")");
     if (!grouped && reward_groups) sc = c->env.rg_sc;
     else if (mix) sc = c->env.mix_sc;
     else if (!grouped) { TRY(make_simcfg(g, &sc)); sim_route_of(c, &sc); }
@@ -1558,16 +1625,28 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
                            sh->executed_jerk, sh->executed_action, sh->takeover_ticks);
     } else if (sh) {
         const env::ShieldView w = v.view();
-        // 1. action handling, the planner's view, the proposal
-        hipLaunchKernelGGL(env::k_shield_env_pre, grid, block, 0, st_, e, sc, N, v.kmax, s, es, o.action, w);
+        const bool lone = !grouped && !reward_groups && !mix;
+        const sim::Cfg *groups = c->sim.groups.as<sim::Cfg>();
+        // 1. action handling, the planner's view, the proposal: the lone kernel, or the form of the env's groups (one launch either way)
+        if (lone) hipLaunchKernelGGL(env::k_shield_env_pre, grid, block, 0, st_, e, sc, N, v.kmax, s, es, o.action, w);
+        else if (mix) hipLaunchKernelGGL(env::k_shield_env_pre_mix, grid, block, 0, st_, e, sc, c->env.traffic_mix(), N, v.kmax, s, es, o.action, w);
+        else if (grouped && reward_groups)
+            hipLaunchKernelGGL(env::k_shield_env_pre_rg_groups, grid, block, 0, st_, e, c->env.reward_tab(), groups, N, v.kmax, s, es, o.action, w);
+        else if (grouped) hipLaunchKernelGGL(env::k_shield_env_pre_groups, grid, block, 0, st_, e, groups, c->sim.n_per_group, N, v.kmax, s, es, o.action, w);
+        else hipLaunchKernelGGL(env::k_shield_env_pre_rg, grid, block, 0, st_, e, c->env.reward_tab(), sc, N, v.kmax, s, es, o.action, w);
         HIPCHK(hipGetLastError());
-        // 2. st.do_conditional_st_based_on_first_step on that view and proposal: stmpc_first_step_device's body
+        // 2. st.do_conditional_st_based_on_first_step on that view and proposal: stmpc_first_step_device's body, on all N rows whatever their group
         TRY(first_step_run(c, p, &sh->cfg->fs, N, v.kmax, w.ego5, w.k, w.ox, w.ov, w.proposal, v.speed.as<double>(), v.takeover.as<int32_t>(), v.reason.as<int32_t>(),
                            o.stream));
-        // 3. what is executed, and what the learner is told
-        hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, sh->cfg->takeover_penalty, N, s, es, o.action, (const double *)v.speed.as<double>(),
-                           (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), sh->takeover, sh->reason,
-                           sh->executed_jerk, sh->executed_action, sh->takeover_ticks);
+        // 3. what is executed, and what the learner is told (with groups: under the penalty of the environment's row of the reset's table)
+        if (lone)
+            hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, sh->cfg->takeover_penalty, N, s, es, o.action, (const double *)v.speed.as<double>(),
+                               (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), sh->takeover, sh->reason,
+                               sh->executed_jerk, sh->executed_action, sh->takeover_ticks);
+        else
+            hipLaunchKernelGGL(env::k_shield_env_apply_groups, grid, block, 0, st_, e, v.penalty_tab(), N, s, es, o.action, (const double *)v.speed.as<double>(),
+                               (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), sh->takeover, sh->reason,
+                               sh->executed_jerk, sh->executed_action, sh->takeover_ticks);
     } else if (reward_groups) {
         hipLaunchKernelGGL(env::k_env_act_rg, grid, block, 0, st_, e, c->env.reward_tab(), N, s, es, o.action);
     } else {
@@ -1622,38 +1701,51 @@ int stmpc_env_reset_groups_device(stmpc_ctx *c, const stmpc_params *p, const stm
 // The reference's per-run reward settings (dqn.py:449-563, rl.py:168-174, merge_gym.py:25,83-140) as a group axis of one vector environment.
 int stmpc_reward_groups_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int G, int n_per_traffic_group,
                                          const stmpc_env_cfg *env_cfgs, int R, int n_per_reward_group, float *d_obs, int obs_stride, void *stream) {
-    std::vector<env::RewardRow> rows;
-    std::vector<sim::Cfg> world;
-    env::ECfg e;
-    TRY(check_reward_groups(c, p, env_cfgs, R, n_per_reward_group, d_obs, obs_stride, &rows, &e));
-    const int N = R * n_per_reward_group;
-    if (G < 0) return fail(STMPC_EINVAL, "G must not be negative (0: an ungrouped world from sim_cfgs[0])");
-    TRY(check_groups(sim_cfgs, G ? G : 1, G ? n_per_traffic_group : N, &world));          // (G = 0: the one cfg and its route, as a table of one)
-    if (G && (G != R || n_per_traffic_group != n_per_reward_group))
-        return fail(STMPC_EINVAL, "the reward groups must coincide with the world's traffic groups (cell c pairs traffic c with reward c): R must equal G and "
-                                  "n_per_reward_group n_per_traffic_group");
+    RewardGroupsReset rg;
+    TRY(reward_groups_reset_check(c, p, sim_cfgs, G, n_per_traffic_group, env_cfgs, R, n_per_reward_group, d_obs, obs_stride, &rg));
     HIPCHK(hipSetDevice(c->device));
     TRY(c->env.rtab.ensure((size_t)STMPC_ENV_REWARD_GROUPS_MAX * sizeof(env::RewardRow)));   // (its full size once: never reallocated under a running kernel)
-    return env_reset(c, sim_cfgs, G, n_per_traffic_group, N, env_cfgs, R, n_per_reward_group, rows, e, d_obs, obs_stride, stream);
+    return env_reset(c, sim_cfgs, G, n_per_traffic_group, rg.N, env_cfgs, R, n_per_reward_group, rg.rows, rg.e, d_obs, obs_stride, stream);
 }
 
 // The env behind st.do_conditional_st_based_on_first_step (st.py:805-814): the plain reset, then the shield's buffers and zeroed counters.
 int stmpc_shield_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N,
                                   float *d_obs, int obs_stride, void *stream) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    TRY(shield_cfg_check(p, sh, N));
-    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
-    DevP dp;
-    TRY(make_devp(p, &dp));
+    ShieldReset r;
+    TRY(shield_reset_check(c, p, sh, N, nullptr, 0, 0, &r));
     HIPCHK(hipSetDevice(c->device));
-    auto &v = c->shield;                         // (a world initialised below outdates an earlier shielded env by its generation)
     TRY(stmpc_env_reset_device(c, p, g, ec, N, d_obs, obs_stride, stream));
-    TRY(v.ensure(N, sh->kmax));
-    TRY(first_step_ensure(c, N, sh->kmax, dp.H, true));       // (the sparse solve's compact batch too: a step may set fs.sparse_control either way)
-    HIPCHK(hipMemsetAsync(v.count.p, 0, (size_t)N * 4, (hipStream_t)stream));
-    HIPCHK(hipMemsetAsync(v.tag.p, 0, (size_t)N * 4, (hipStream_t)stream));
-    v.N = N; v.kmax = sh->kmax; v.generation = c->sim.generation;
-    return STMPC_OK;
+    return shield_reset_finish(c, sh, r, stream);
+}
+
+// st.do_conditional_st_based_on_first_step (st.py:805-814) in front of the traffic-type axis of the reference's experiments (configs/train_*_*.json,
+// control.py:215-226): the traffic-groups reset, then the shield's buffers, zeroed counters and the groups' takeover penalties.
+int stmpc_shield_traffic_groups_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *cfgs, int G, int n_per_group, const stmpc_env_cfg *ec,
+                                         const stmpc_shield_env_cfg *sh, const double *takeover_penalties, int P, float *d_obs, int obs_stride, void *stream) {
+    env::ECfg e;
+    TRY(env_reset_check(c, p, ec, d_obs, obs_stride, &e));
+    std::vector<sim::Cfg> world;
+    TRY(check_groups(cfgs, G, n_per_group, &world));
+    ShieldReset r;
+    TRY(shield_reset_check(c, p, sh, G * n_per_group, takeover_penalties, P, G, &r));
+    HIPCHK(hipSetDevice(c->device));
+    TRY(env_reset(c, cfgs, G, n_per_group, 0, ec, 0, 0, {}, e, d_obs, obs_stride, stream));
+    return shield_reset_finish(c, sh, r, stream);
+}
+
+// ... in front of the reference's per-run reward settings (dqn.py:449-563, rl.py:168-174, merge_gym.py:25,83-140): the reward-groups reset (an ungrouped
+// world, G = 0, or traffic groups that coincide with the reward groups), then the shield's part.
+int stmpc_shield_reward_groups_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int G, int n_per_traffic_group,
+                                                const stmpc_env_cfg *env_cfgs, int R, int n_per_reward_group, const stmpc_shield_env_cfg *sh,
+                                                const double *takeover_penalties, int P, float *d_obs, int obs_stride, void *stream) {
+    RewardGroupsReset rg;
+    TRY(reward_groups_reset_check(c, p, sim_cfgs, G, n_per_traffic_group, env_cfgs, R, n_per_reward_group, d_obs, obs_stride, &rg));
+    ShieldReset r;
+    TRY(shield_reset_check(c, p, sh, rg.N, takeover_penalties, P, R, &r));
+    HIPCHK(hipSetDevice(c->device));
+    TRY(c->env.rtab.ensure((size_t)STMPC_ENV_REWARD_GROUPS_MAX * sizeof(env::RewardRow)));
+    TRY(env_reset(c, sim_cfgs, G, n_per_traffic_group, rg.N, env_cfgs, R, n_per_reward_group, rg.rows, rg.e, d_obs, obs_stride, stream));
+    return shield_reset_finish(c, sh, r, stream);
 }
 
 int stmpc_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const void *d_action, float *d_obs, int obs_stride,
@@ -1746,6 +1838,57 @@ int stmpc_traffic_mix_env_step_device(stmpc_ctx *c, const stmpc_params *p, const
     const MixStep mix{d_traffic_type, d_final_traffic_type};
     return env_step(c, p, nullptr, ec, N, TRAFFIC_MIX_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream},
                     nullptr, &mix);
+}
+
+// ... in front of the traffic mix (one policy across the types of configs/train_*_*.json): the mix's reset, then the shield's part; one takeover penalty,
+// shield_cfg's, for every row.
+int stmpc_shield_traffic_mix_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *sim_cfgs, int T, const double *weights, uint64_t mix_seed,
+                                              const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N, float *d_obs, int obs_stride, int32_t *d_traffic_type,
+                                              void *stream) {
+    env::ECfg e;
+    TRY(env_reset_check(c, p, ec, d_obs, obs_stride, &e));
+    MixReset mix;
+    TRY(check_traffic_mix(sim_cfgs, T, weights, N, &mix));
+    mix.seed = mix_seed; mix.d_type = d_traffic_type;
+    ShieldReset r;
+    TRY(shield_reset_check(c, p, sh, N, nullptr, 0, 1, &r));
+    HIPCHK(hipSetDevice(c->device));
+    auto &v = c->env;
+    TRY(v.mix_rows.ensure((size_t)STMPC_TRAFFIC_MIX_MAX * sizeof(env::TrafficRow)));
+    TRY(v.mix_cum.ensure((size_t)STMPC_TRAFFIC_MIX_MAX * 8));
+    TRY(v.mix_type.ensure((size_t)N * 4));
+    TRY(env_reset(c, sim_cfgs, 0, 0, N, ec, 0, 0, {}, e, d_obs, obs_stride, stream, &mix));
+    return shield_reset_finish(c, sh, r, stream);
+}
+
+// The shielded step (st.py:805-814 in front of merge_gym.py:83-140) of an env with traffic groups, reward groups or a traffic mix: thin entries over env_step.
+int stmpc_shield_traffic_groups_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N, const void *d_action,
+                                        float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs,
+                                        double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk, double *d_executed_action,
+                                        int32_t *d_takeover_ticks, void *stream) {
+    const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    return env_step(c, p, nullptr, ec, N, SHIELD_TRAFFIC_GROUPS_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream},
+                    &shield);
+}
+
+int stmpc_shield_reward_groups_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N,
+                                               const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
+                                               float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk,
+                                               double *d_executed_action, int32_t *d_takeover_ticks, void *stream) {
+    const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    return env_step(c, p, nullptr, ec, N, SHIELD_REWARD_GROUPS_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream},
+                    &shield);
+}
+
+int stmpc_shield_traffic_mix_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N,
+                                             const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
+                                             float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk,
+                                             double *d_executed_action, int32_t *d_takeover_ticks, int32_t *d_traffic_type, int32_t *d_final_traffic_type,
+                                             void *stream) {
+    const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    const MixStep mix{d_traffic_type, d_final_traffic_type};
+    return env_step(c, p, nullptr, ec, N, SHIELD_TRAFFIC_MIX_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream},
+                    &shield, &mix);
 }
 
 int stmpc_traffic_mix_draw(uint64_t mix_seed, int env_index, uint32_t episode, const double *cum, int T) {

@@ -13,6 +13,7 @@
 #include "stmpc_shield_env_kernels.hpp"
 #include "stmpc_cshield_env_kernels.hpp"
 #include "stmpc_traffic_mix_kernels.hpp"
+#include "stmpc_shield_groups_kernels.hpp"
 #include "stmpc_solve_plan.hpp"
 
 #include <math.h>
@@ -232,11 +233,14 @@ struct stmpc_ctx {
         }
     } env;
     // shielded vector environment (stmpc_shield_env_*): the planner's view and the proposal handed to the first-step shield, its decision, and the
-    // takeovers of each environment's current episode with the episode they were counted in.  Valid while `generation` is the world's
+    // takeovers of each environment's current episode with the episode they were counted in.  Valid while `generation` is the world's.
+    // `penalty`: the takeover penalties of a shielded env with groups or a traffic mix (stmpc_shield_traffic_groups_env_reset_device and its kin), P values for
+    // n_per_penalty consecutive environments each; P = 0: the lone shielded env, whose step takes its penalty by value
     struct ShieldEnv {
-        DevBuf ego5, k, ox, ov, proposal, speed, takeover, reason, count, tag;
-        int N = 0, kmax = 0;
+        DevBuf ego5, k, ox, ov, proposal, speed, takeover, reason, count, tag, penalty;
+        int N = 0, kmax = 0, P = 0, n_per_penalty = 0;
         int64_t generation = -1;
+        env::PenaltyTab penalty_tab() const { return env::PenaltyTab{penalty.as<double>(), n_per_penalty}; }
         int ensure(int n_, int kmax_) {
             const size_t n = (size_t)n_;
             TRY(ego5.ensure(n * 5 * 8)); TRY(k.ensure(n * 4)); TRY(ox.ensure(n * kmax_ * 8)); TRY(ov.ensure(n * kmax_ * 8)); TRY(proposal.ensure(n * 8));

@@ -24,16 +24,15 @@ struct ShieldView {                         // device arrays: the planner's view
     double *proposal;                       // [N] the proposed speed
 };
 
-#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
-// k_env_act's dispatch (handle_action, called) + the shield's view and proposal.  A finished environment gets the view k_sim_view
+// k_env_act's dispatch (handle_action, called) + the shield's view and proposal, for environment e (e < N: the caller has checked its bounds) under
+// the env cfg `c` and the world cfg `sc` of that environment -- the body of k_shield_env_pre and of its grouped forms
+// (stmpc_shield_groups_kernels.hpp).  A finished environment gets the view k_sim_view
 // gives it and proposes the speed its action would command from that state -- what episodes.EpisodeRunner(controller="first_step") proposes for a
 // finished environment, so that the context's stmpc_first_step_counts are the runner's row for row -- while its step state is left alone, as
 // k_env_act leaves it.  An index out of range latches the error word as k_env_act does (a running environment's only) and proposes -- and
 // commands -- the current speed, which is what sim::k_sim_step makes of k_env_act's NaN command, so that no NaN reaches the predictor or the solver.
-__global__ void __launch_bounds__(64) k_shield_env_pre(ECfg c, sim::Cfg sc, int N, int kmax, sim::State s, EState es, const void *__restrict__ action,
-                                                       ShieldView w) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
+__device__ __forceinline__ void shield_env_pre_body(const ECfg &c, const sim::Cfg &sc, int e, int kmax, const sim::State &s, const EState &es,
+                                                    const void *__restrict__ action, const ShieldView &w) {
     sim::sim_view_env(sc, kmax, s, e, w.ego5, w.k, w.ox, w.ov, nullptr);
     const int live = s.status[e] == 0;
     es.live[e] = live;
@@ -48,18 +47,17 @@ __global__ void __launch_bounds__(64) k_shield_env_pre(ECfg c, sim::Cfg sc, int 
     es.cmd[e] = cmd; es.pjerk[e] = pjerk; es.inv[e] = inv;
 }
 
-// After the shield's decision (sh_*: k_fs_decide's outputs for the N rows).  Where it took over a live environment: the command becomes the
+// After the shield's decision (sh_*: k_fs_decide's outputs for the N rows), for environment e (e < N) -- the body of k_shield_env_apply and of
+// k_shield_env_apply_groups.  Where it took over a live environment: the command becomes the
 // shield's speed, the projected jerk that of the executed speed -- the third branch of AccelerationEnv._do_action (merge_gym.py:208-212) in
 // exactly this operation order -- and the tick's invalid-action reward grows by takeover_penalty * tick.  count / tag: the takeovers of the
 // environment's current episode and the episode they were counted in; the count restarts when es.episode[e] has moved on (k_env_post's autoreset),
 // so the value written on the tick an episode ends is still that episode's.  exec_action may be NULL (discrete envs: the index is not rewritten).
-__global__ void __launch_bounds__(64) k_shield_env_apply(ECfg c, double takeover_penalty, int N, sim::State s, EState es, const void *__restrict__ action,
-                                                         const double *__restrict__ sh_speed, const int *__restrict__ sh_takeover,
-                                                         const int *__restrict__ sh_reason, int *count, int *tag, unsigned char *__restrict__ takeover,
-                                                         int *__restrict__ reason, double *__restrict__ exec_jerk, double *__restrict__ exec_action,
-                                                         int *__restrict__ takeover_ticks) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
+__device__ __forceinline__ void shield_env_apply_body(const ECfg &c, double takeover_penalty, int e, const sim::State &s, const EState &es,
+                                                      const void *__restrict__ action, const double *__restrict__ sh_speed,
+                                                      const int *__restrict__ sh_takeover, const int *__restrict__ sh_reason, int *count, int *tag,
+                                                      unsigned char *__restrict__ takeover, int *__restrict__ reason, double *__restrict__ exec_jerk,
+                                                      double *__restrict__ exec_action, int *__restrict__ takeover_ticks) {
     const int ep = es.episode[e];
     int cnt = tag[e] == ep ? count[e] : 0;
     if (!es.live[e]) {                                                     // finished before this tick: nothing is executed, nothing is counted
@@ -84,6 +82,24 @@ __global__ void __launch_bounds__(64) k_shield_env_apply(ECfg c, double takeover
     exec_jerk[e] = pjerk;
     if (exec_action) exec_action[e] = take ? clip(pjerk, c.j_min, c.j_max) : ((const double *)action)[e];
     takeover_ticks[e] = cnt;
+}
+
+#ifdef STMPC_UNIT_ENV        // (the kernels of the unit that launches them)
+__global__ void __launch_bounds__(64) k_shield_env_pre(ECfg c, sim::Cfg sc, int N, int kmax, sim::State s, EState es, const void *__restrict__ action,
+                                                       ShieldView w) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    shield_env_pre_body(c, sc, e, kmax, s, es, action, w);
+}
+
+__global__ void __launch_bounds__(64) k_shield_env_apply(ECfg c, double takeover_penalty, int N, sim::State s, EState es, const void *__restrict__ action,
+                                                         const double *__restrict__ sh_speed, const int *__restrict__ sh_takeover,
+                                                         const int *__restrict__ sh_reason, int *count, int *tag, unsigned char *__restrict__ takeover,
+                                                         int *__restrict__ reason, double *__restrict__ exec_jerk, double *__restrict__ exec_action,
+                                                         int *__restrict__ takeover_ticks) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    shield_env_apply_body(c, takeover_penalty, e, s, es, action, sh_speed, sh_takeover, sh_reason, count, tag, takeover, reason, exec_jerk, exec_action, takeover_ticks);
 }
 #endif
 

@@ -176,8 +176,8 @@ class MergeVecEnv:
     truncated``).  ``takeover_penalty`` (>= 0) is added to the reward as ``takeover_penalty * TICK_LENGTH`` on a takeover tick; ``shield_kmax``: the row
     stride of the planner's view the shield sees (``EpisodeRunner``'s ``kmax``; 1 ... 32, the solver's limit).  ``shield_sparse=False`` solves the controller for every environment and
     keeps ``step`` free of host synchronisation; ``shield_sparse=True`` solves it for the taken-over ones only, and ``step`` then DOES synchronise: one
-    integer, their number, crosses to the host every step.  Same outputs either way.  ``shield_counts()`` reads the shield's totals.  Out of scope,
-    refused with a ValueError: a shield together with ``traffic`` or ``rewards`` groups.
+    integer, their number, crosses to the host every step.  Same outputs either way.  ``shield_counts()`` reads the shield's totals.  Refused
+    with a ValueError here: a shield together with ``traffic`` or ``rewards`` groups -- that env is a class of its own, ``GroupedShieldVecEnv``.
 
     ``traffic_mix`` (with ``mix_weights``, ``mix_seed``; keyword-only): every episode draws its own traffic type -- the call then returns a
     ``TrafficMixVecEnv``, see there."""
@@ -526,3 +526,110 @@ class CombinedShieldVecEnv(MergeVecEnv):
         """(states decided, controller solves run for them) on this env's context since the last reset of the counts (``stmpc_combined_counts``:
         finished environments of a run without autoreset are decided too, and count; equal unless ``shield_sparse``)."""
         return self.ctx.combined_counts(reset)
+
+
+class GroupedShieldVecEnv(TrafficMixVecEnv):
+    """The first-step shield of ``MergeVecEnv(shield="first_step")`` in front of the env's group axes: ``traffic`` groups, ``rewards`` groups (on an
+    ungrouped world, or with as many traffic groups) or a ``traffic_mix`` -- the per-traffic-type training matrix, a reward-shaping sweep or a
+    mixed-traffic policy trained in the closed loop of ``st.do_conditional_st_based_on_first_step`` (st.py:805-814), on the device
+    (``stmpc_shield_traffic_groups_env_reset_device``, ``stmpc_shield_reward_groups_env_reset_device``, ``stmpc_shield_traffic_mix_env_reset_device`` and their
+    step entries: the launches of the lone shielded step).  A class of its own: ``MergeVecEnv`` keeps refusing a shield together with groups or a mix.
+
+    ``traffic``, ``rewards``, ``traffic_mix`` / ``mix_weights`` / ``mix_seed``: as ``MergeVecEnv`` and ``TrafficMixVecEnv`` take them; at least one
+    of the three must be given, and the mix goes with neither kind of groups (ValueError).  ``takeover_penalty``: one number for every group, or one per
+    group (G, or R without traffic groups; the mix takes one number); each finite and >= 0.  ``shield_sparse``, ``shield_kmax``: as ``MergeVecEnv``.
+
+    The rows of group g are bit-identical -- through every autoreset -- to the lone ``MergeVecEnv(n / G, shield="first_step")`` made with group g's
+    traffic, reward settings and takeover penalty; an episode of the shielded mix is the lone shielded env's episode of the drawn type.  ``step``'s
+    ``info`` has the shielded env's keys (``takeover``, ``reason``, ``executed_jerk``, ``executed_action`` for the continuous env, ``takeover_ticks``)
+    and, with a mix, ``traffic_type`` / ``final_traffic_type``.  ``env.shield == "first_step"``: ``learner.train_ddpg`` runs on it as on the lone
+    shielded env, ``executed_actions=True`` included, and a ``learner.DDPGPopulation`` of one member per group trains member m behind the shield on
+    group m.  ``takeover_share()`` and ``summary_by_group(rows)`` report per group (per traffic type for the mix)."""
+
+    def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, *, traffic=None, rewards=None, traffic_mix=None,
+                 mix_weights=None, mix_seed=None, shield_sparse=False, takeover_penalty=0.0, shield_kmax=32):
+        if traffic is None and rewards is None and traffic_mix is None:                   # (every check before any device call)
+            raise ValueError("a GroupedShieldVecEnv needs traffic groups, reward groups or a traffic_mix: the lone shielded env is MergeVecEnv(shield='first_step')")
+        traffic = list(traffic) if traffic is not None else None
+        rewards = list(rewards) if rewards is not None else None
+        count = len(traffic) if traffic is not None else len(rewards) if rewards is not None else 1
+        try:
+            penalties = [float(x) for x in np.asarray(takeover_penalty, dtype=np.float64).reshape(-1)]
+        except (TypeError, ValueError):
+            raise ValueError("takeover_penalty must be a number or one number per group, not %r" % (takeover_penalty,))
+        if len(penalties) not in (1, count):
+            raise ValueError("takeover_penalty has %d values for %d groups: one number, or one per group" % (len(penalties), count))
+        if not all(np.isfinite(x) and x >= 0 for x in penalties):
+            raise ValueError("takeover_penalty must be finite and not negative, not %r" % (takeover_penalty,))
+        if not 1 <= int(shield_kmax) <= _capi.KMAX_LIMIT:
+            raise ValueError("shield_kmax must be 1 ... %d (the solver's vehicles per state), not %r" % (_capi.KMAX_LIMIT, shield_kmax))
+        super().__init__(n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic, rewards, traffic_mix=traffic_mix, mix_weights=mix_weights,
+                         mix_seed=mix_seed)
+        torch = self.torch
+        self.shield, self.takeover_penalties = "first_step", penalties
+        # (the cfg's own penalty is what the lone shielded step reads; the grouped step reads the reset's table)
+        self.shield_cfg = _capi.ShieldEnvCfg.from_settings(Settings, shield_sparse, penalties[0], shield_kmax)
+        z = lambda dtype: torch.zeros(self.n, dtype=dtype, device=self.device)
+        self._takeover, self._reason = z(torch.bool), z(torch.int32)
+        self._exec_jerk, self._takeover_ticks = z(torch.float64), z(torch.int32)
+        self._exec_action = z(torch.float64) if self.continuous else None
+        bind, c = functools.partial, self.ctx
+        if self.traffic_mix is not None:
+            self.n_groups = self.T
+            self._group_of_row = None                            # (the type the tick ran under: info["final_traffic_type"])
+            self._reset = lambda d_obs, obs_stride, stream: c.shield_traffic_mix_env_reset(self.params, self.mix_cfgs, self.mix_weights, self.mix_seed, self.cfg,
+                                                                                           self.shield_cfg, self.n, d_obs, obs_stride, self._type.data_ptr(), stream)
+            self._step = lambda *a: c.shield_traffic_mix_env_step(self.params, self.cfg, self.shield_cfg, self.n, *a[:-1], self._type.data_ptr(),
+                                                                  self._final_type.data_ptr(), a[-1])
+        else:
+            self.n_groups = self.R or self.G
+            self._group_of_row = torch.arange(self.n, device=self.device) // (self.n // self.n_groups)
+            if self.R:
+                self._reset = bind(c.shield_env_reset_reward_groups, self.params, self.sim_cfgs if self.sim_cfgs is not None else self.sim_cfg, self.n_per_group,
+                                   self.reward_cfgs, self.n_per_reward_group, self.shield_cfg, penalties)
+                self._step = bind(c.shield_env_step_reward_groups, self.params, self.cfg, self.shield_cfg, self.n)
+            else:
+                self._reset = bind(c.shield_env_reset_groups, self.params, self.sim_cfgs, self.n_per_group, self.cfg, self.shield_cfg, penalties)
+                self._step = bind(c.shield_env_step_groups, self.params, self.cfg, self.shield_cfg, self.n)
+        self._taken = torch.zeros(self.n_groups, dtype=torch.int64, device=self.device)
+        self._lived = torch.zeros(self.n_groups, dtype=torch.int64, device=self.device)
+        self._alive = torch.ones(self.n, dtype=torch.bool, device=self.device)
+
+    def reset(self):
+        obs = super().reset()
+        self._taken.zero_(), self._lived.zero_(), self._alive.fill_(True)
+        return obs
+
+    def step(self, action):
+        out = super().step(action)
+        group = self._group_of_row if self._group_of_row is not None else self._final_type.to(self.torch.int64)
+        self._taken.index_add_(0, group, self._takeover.to(self.torch.int64))         # (device sums: no host synchronisation)
+        self._lived.index_add_(0, group, self._alive.to(self.torch.int64))
+        if not self.autoreset:
+            self._alive &= ~(out[2] | out[3])                    # (a finished environment idles: not a live tick)
+        return out
+
+    def takeover_share(self):
+        """Per group (per traffic type for the mix): the share of the live ticks since ``reset()`` on which the shield overruled the action, a list of
+        floats (NaN for a type no tick ran under); synchronises."""
+        taken, lived = self._taken.cpu().numpy(), self._lived.cpu().numpy()
+        return [float(t) / float(l) if l else float("nan") for t, l in zip(taken, lived)]
+
+    def summary_by_group(self, rows):
+        """One dict per group for drained episodes ``rows`` (``drain_episode_stats``): ``episodes``, the ``merged``, ``crashed`` and ``timed_out``
+        shares, ``mean_ticks``, ``mean_return`` (NaN for a group without episodes) and ``takeover_share`` (of the group's live ticks since ``reset()``).
+        The groups are the reward groups, else the traffic groups, else the mix's traffic types."""
+        if self.traffic_mix is not None:
+            out = self.summary_by_traffic(rows)
+        else:
+            owner = np.asarray(rows["env"], dtype=np.int64) // (self.n // self.n_groups)
+            out = []
+            for g in range(self.n_groups):
+                m = owner == g
+                k = int(m.sum())
+                mean = lambda col: float(np.mean(np.asarray(rows[col], dtype=np.float64)[m])) if k else float("nan")
+                out.append({"episodes": k, "merged": mean("merged"), "crashed": mean("crashed"), "timed_out": mean("timed_out"), "mean_ticks": mean("ticks"),
+                            "mean_return": mean("episode_return")})
+        for d, share in zip(out, self.takeover_share()):
+            d["takeover_share"] = share
+        return out
