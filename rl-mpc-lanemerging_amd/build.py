@@ -3,9 +3,9 @@
 The library is the product's only compute path; importing the package does not build
 anything, and every solver entry fails loudly if the library or a GPU is missing.
 
-The host code is several translation units (``UNITS``: the solver, and the rest of the C-ABI): each is compiled to an object
-under ``build/``, in parallel, and one link step makes the library.  Only the units whose sources
-changed are compiled again.
+The host code is three translation units (``UNITS``: the solver; the core with the context, the controllers, the episode world and
+the vector env; the learners): each is compiled to an object under ``build/``, in parallel, and one link step makes the library.
+Only the units whose sources changed are compiled again (and the core, which carries the ``src=`` stamp).
 """
 import os
 import shutil
@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libstmpc.so")
 STMPC_H = os.path.join(REPO_ROOT, "include", "stmpc.h")
 
 # csrc/<unit>.hip, the longest compile first.  CORE_UNIT carries the src= stamp of stmpc_backend_info.
-UNITS = ["stmpc_solver", "stmpc"]
+UNITS = ["stmpc_solver", "stmpc", "stmpc_learner"]
 CORE_UNIT = "stmpc"
 
 HIPCC_FLAGS = [

@@ -1,14 +1,14 @@
-// stmpc.hip -- C-ABI (include/stmpc.h) over the gfx950 kernels in stmpc_kernels.hpp.
+// stmpc.hip -- the core of the C-ABI (include/stmpc.h): the context and the host helpers, the controllers on top of the solver (stmpc_solver.hip),
+// the episode world, the vector env and the flight recorder.  The learners are stmpc_learner.hip; what they call here is declared in stmpc_host.hpp.
 // Host side: context, device buffers, launch sequencing on the caller's HIP stream.
 // No CPU fallback: every compute entry needs a HIP device.
+// (The world and the env stay in this unit with the controllers: their observation kernels are optimised together with k_policy_features and k_actor_eval,
+// whose feature code they share, and come out different in a module without them.)
 #define STMPC_UNIT_CONTROL      // (this unit launches the kernels of the controllers and of the episode world)
 #define STMPC_UNIT_ENV
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ff_kernels.hpp"
 #include "stmpc_nj_kernels.hpp"
-#include "stmpc_ddpg_kernels.hpp"
-#include "stmpc_ddpg_pop_kernels.hpp"
-#include "stmpc_actor_pop_kernels.hpp"
 #include "stmpc_rec_kernels.hpp"
 #include "stmpc_sim_groups_kernels.hpp"
 #include "stmpc_cc_groups_kernels.hpp"
@@ -352,6 +352,9 @@ int make_featcfg(const stmpc_policy_features_cfg *f, FeatCfg *fc) {
     fc->normalize = f->normalize != 0; fc->time_feature = f->time_feature != 0;
     return STMPC_OK;
 }
+}  // namespace
+
+// (declared in stmpc_host.hpp: the actor population of stmpc_learner.hip asks too)
 // later rollout steps: only states whose rollout is still going on are evaluated by the reference (dqn.py:129-133); *live = NULL at step 1
 int rollout_live(const stmpc_ctx *c, int N, int step, const int **live) {
     *live = nullptr;
@@ -361,6 +364,8 @@ int rollout_live(const stmpc_ctx *c, int N, int step, const int **live) {
     }
     return STMPC_OK;
 }
+
+namespace {
 // pointer checks of the two rollout step entries
 int rollout_step_ptrs(int Kmax, const double *d_ego5_start, const double *d_cur_ego4, const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov,
                       const double *d_action) {
@@ -547,13 +552,7 @@ int stmpc_policy_features_len(const stmpc_policy_features_cfg *f) {
 }  // extern "C"
 
 // ---- the policy network itself (optional: the caller may keep it in its own framework and only use stmpc_policy_features_device) ----
-struct stmpc_actor {
-    int device = 0;
-    DevBuf p0, b0, p1, b1, w2, b2;      // empty for a view (stmpc_actor_view_ddpg): dev then points into the learner's arrays
-    ActorDev dev{};
-    size_t lds = 0;
-};
-
+// (struct stmpc_actor: stmpc_host.hpp, with the declarations of what stmpc_learner.hip calls of this section)
 namespace {
 // [column tile][k block][lane = j + 16 kk][4]: W[n0 + j][k0 + 4 kk + s], zero outside [rows) x [cols)
 std::vector<float> pack_layer(const float *W, int rows, int cols, int rows_p, int cols_p) {
@@ -569,6 +568,8 @@ std::vector<float> pack_layer(const float *W, int rows, int cols, int rows_p, in
     return out;
 }
 int upload(DevBuf &b, const std::vector<float> &v) { return upload(b, v.data(), v.size()); }
+}  // namespace
+
 size_t actor_lds_bytes(int h1p, int h2p) { return ((size_t)AT_TM * AT_KIN + (size_t)AT_TM * (h1p + 4) + (size_t)AT_TM * (h2p + 4)) * sizeof(float); }
 // dynamic LDS of k_actor_eval (which = 0) / k_actor_eval_pop (1)
 // (the attribute belongs to the kernel, not to an actor: only ever raised, so that a narrower actor created later does not take the
@@ -601,6 +602,8 @@ int actor_eval_checks(const stmpc_ctx *c, int device, int n_in, const stmpc_poli
     if (f->time_feature && !d_evals) return fail(STMPC_EINVAL, "time_feature needs the evaluation counters");
     return STMPC_OK;
 }
+
+namespace {
 // stmpc_actor_eval_device after its argument checks (N >= 1): the entry's body, shared with stmpc_cshield_env_step_device
 int actor_eval_run(stmpc_ctx *c, const stmpc_actor *a, const FeatCfg &fc, int N, int Kmax, int step, const double *d_cur_ego4, const int32_t *d_k,
                    const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa, int32_t *d_evals, float *d_feat, int feat_stride, double *d_jerk,
@@ -1939,478 +1942,6 @@ int stmpc_reward_groups_split(stmpc_ctx *c, int *R, int *n_per_group) {
     const bool on = c->env.N >= 1;
     if (R) *R = on ? c->env.R : 0;
     if (n_per_group) *n_per_group = on ? c->env.n_per_rg : 0;
-    return STMPC_OK;
-}
-
-}  // extern "C"
-
-// ---- DDPG learner (stmpc_ddpg_*): replay ring, fused update, acting; kernels in stmpc_ddpg_kernels.hpp -------------------------------------------
-struct stmpc_ddpg {
-    int device = 0;
-    stmpc_ddpg_cfg cfg{};
-    DdpgDev dev{};
-    DevBuf netbuf[2][13], ring, cnt, tick, ws[7];
-    int h1p = 0, h2p = 0, np = 0, Bp = 0;
-    size_t lds = 0;
-    int n_in(int which) const { return cfg.n_obs + 1 + which; }
-    int64_t slot_len(int which) const { const int64_t n = n_in(which); return (int64_t)cfg.h1 * n + cfg.h1 + (int64_t)cfg.h2 * cfg.h1 + cfg.h2 + cfg.h2 + 1; }
-};
-
-namespace {
-int ddpg_zero(DevBuf &b, size_t bytes) {
-    TRY(b.ensure(bytes));
-    HIPCHK(hipMemset(b.p, 0, bytes));
-    return STMPC_OK;
-}
-float *ddpg_slot_ptr(stmpc_ddpg *l, int slot) {
-    const DdpgNet &n = slot >= 4 ? l->dev.q : l->dev.pi;
-    switch (slot & 3) { case 0: return n.w; case 1: return n.wt; case 2: return n.m; default: return n.v; }
-}
-// slot layout (unpadded) <-> padded layout, on the host
-void ddpg_pad(const stmpc_ddpg *l, int n_in, const float *flat, std::vector<float> &pad, bool to_pad, float *flat_out) {
-    const int h1 = l->cfg.h1, h2 = l->cfg.h2, h1p = l->h1p, h2p = l->h2p;
-    size_t i = 0;
-    auto item = [&](size_t p) { if (to_pad) pad[p] = flat[i]; else flat_out[i] = pad[p]; ++i; };
-    for (int n = 0; n < h1; ++n) for (int k = 0; k < n_in; ++k) item((size_t)n * AT_KIN + k);
-    for (int n = 0; n < h1; ++n) item((size_t)dg_o_b0(h1p) + n);
-    for (int n = 0; n < h2; ++n) for (int k = 0; k < h1; ++k) item((size_t)dg_o_w1(h1p) + (size_t)n * h1p + k);
-    for (int n = 0; n < h2; ++n) item((size_t)dg_o_b1(h1p, h2p) + n);
-    for (int n = 0; n < h2; ++n) item((size_t)dg_o_w2(h1p, h2p) + n);
-    item((size_t)dg_o_b2(h1p, h2p));
-}
-int ddpg_set_lds(const void *fn, size_t lds) {
-    if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(STMPC_EHIP, "hipFuncSetAttribute(dynamic LDS) failed for a DDPG kernel");
-    }
-    return STMPC_OK;
-}
-void ddpg_launch_grads(stmpc_ddpg *l, int which, int gate, hipStream_t st) {
-    const int tiles = l->Bp / AT_TM, t1 = l->h2p / 16, t0 = l->h1p / 16;
-    if (which) hipLaunchKernelGGL(k_ddpg_critic_fwd, dim3(tiles), dim3(AT_THREADS), l->lds, st, l->dev, l->cfg.batch, gate);
-    else hipLaunchKernelGGL(k_ddpg_actor_fwd, dim3(tiles), dim3(AT_THREADS), l->lds, st, l->dev, l->cfg.batch, gate);
-    hipLaunchKernelGGL(k_ddpg_wgrad, dim3(t1 * t0 + 2 * t0 + t1 + t0 + t1 + 1), dim3(64 * DG_WG_WAVES), 0, st, l->dev, which, l->Bp, gate);
-}
-void ddpg_launch_adam(stmpc_ddpg *l, int which, float lr, int mode, int bump, hipStream_t st) {
-    hipLaunchKernelGGL(k_ddpg_adam, dim3((l->np + 255) / 256), dim3(256), 0, st, l->dev, which, lr, mode, bump, 1);
-}
-}  // namespace
-
-extern "C" {
-
-int stmpc_ddpg_create(stmpc_ctx *c, const stmpc_ddpg_cfg *g, stmpc_ddpg **out) {
-    if (!c || !g || !out) return fail(STMPC_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (g->n_obs < 1 || g->n_obs > AT_KIN - 2 || g->h1 < 1 || g->h1 > 1024 || g->h2 < 1 || g->h2 > 1024) return fail(STMPC_EINVAL, "DDPG network shape out of range (n_obs <= 30, hidden widths <= 1024)");
-    if (g->batch < 16 || g->batch > 8192) return fail(STMPC_EINVAL, "batch must be in 16 ... 8192");
-    if (g->capacity < 1 || g->replay_start < 0 || g->replay_start >= g->capacity) return fail(STMPC_EINVAL, "capacity must be positive and replay_start below it");
-    if (!(g->gamma >= 0) || !(g->tau >= 0 && g->tau <= 1) || !(g->beta1 >= 0 && g->beta1 < 1) || !(g->beta2 >= 0 && g->beta2 < 1) || !(g->eps > 0) ||
-        !(g->noise_std >= 0) || !(g->action_low <= g->action_high)) return fail(STMPC_EINVAL, "DDPG constants out of range");
-    HIPCHK(hipSetDevice(c->device));
-    stmpc_ddpg *l = new stmpc_ddpg();
-    l->device = c->device; l->cfg = *g;
-    const int h1p = l->h1p = (g->h1 + 15) & ~15, h2p = l->h2p = (g->h2 + 15) & ~15;
-    const int np = l->np = dg_nparam(h1p, h2p), Bp = l->Bp = (g->batch + 15) & ~15;
-    l->lds = ddpg_tile_bytes(h1p, h2p);
-    if (l->lds + 1024 > (size_t)c->lds_per_block) { delete l; return fail(STMPC_EINVAL, "DDPG networks too wide for one workgroup's LDS"); }
-    DdpgDev &d = l->dev;
-    int rc = 0;
-    for (int w = 0; w < 2 && !rc; ++w) {
-        DdpgNet &n = w ? d.q : d.pi;
-        float **ptr[13] = {&n.w, &n.wt, &n.m, &n.v, &n.g, &n.p0, &n.p1, &n.p1t, &n.t0, &n.t1, &n.bpow, nullptr, nullptr};
-        const size_t len[11] = {(size_t)np, (size_t)np, (size_t)np, (size_t)np, (size_t)np, (size_t)h1p * AT_KIN, (size_t)h2p * h1p, (size_t)h2p * h1p,
-                                (size_t)h1p * AT_KIN, (size_t)h2p * h1p, 4};
-        for (int i = 0; i < 11 && !rc; ++i) { rc = ddpg_zero(l->netbuf[w][i], len[i] * sizeof(float)); *ptr[i] = l->netbuf[w][i].as<float>(); }
-        n.n_in = l->n_in(w);
-    }
-    const size_t wlen[7] = {(size_t)Bp * AT_KIN, (size_t)Bp * h1p, (size_t)Bp * h2p, (size_t)Bp * h2p, (size_t)Bp * h1p, (size_t)Bp, (size_t)Bp * 2};
-    float **wptr[7] = {&d.aX, &d.aH1, &d.aH2, &d.aD2, &d.aD1, &d.adz, &d.arow};
-    for (int i = 0; i < 7 && !rc; ++i) { rc = ddpg_zero(l->ws[i], wlen[i] * sizeof(float)); *wptr[i] = l->ws[i].as<float>(); }
-    if (!rc) rc = ddpg_zero(l->ring, (size_t)g->capacity * DG_ROW * sizeof(float));
-    if (!rc) rc = ddpg_zero(l->cnt, DG_NCNT * sizeof(long long));
-    if (!rc) rc = ddpg_zero(l->tick, DG_NTICK * sizeof(unsigned int));
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_critic_fwd, l->lds);
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_actor_fwd, l->lds);
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_act, l->lds);
-    if (rc) { stmpc_ddpg_destroy(l); return rc; }
-    d.ring = l->ring.as<float>(); d.cnt = l->cnt.as<long long>(); d.tick = l->tick.as<unsigned int>();
-    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = g->h2; d.h1p = h1p; d.h2p = h2p; d.capacity = g->capacity; d.replay_start = g->replay_start; d.seed = g->seed;
-    d.gamma = (float)g->gamma; d.tau = (float)g->tau; d.beta1 = (float)g->beta1; d.beta2 = (float)g->beta2;
-    d.omb1 = 1.0f - d.beta1; d.omb2 = 1.0f - d.beta2; d.omtau = 1.0f - d.tau; d.eps = (float)g->eps; d.time_scale = (float)g->time_scale;
-    d.scale = (float)g->tanh_scale; d.mean = (float)g->tanh_mean; d.noise_std = (float)g->noise_std; d.a_low = (float)g->action_low; d.a_high = (float)g->action_high;
-    const float one[4] = {1.f, 1.f, 0.f, 0.f};                       // beta^0
-    HIPCHK(hipMemcpy(d.pi.bpow, one, sizeof one, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.q.bpow, one, sizeof one, hipMemcpyHostToDevice));
-    *out = l;
-    return STMPC_OK;
-}
-
-void stmpc_ddpg_destroy(stmpc_ddpg *l) {
-    if (!l) return;
-    (void)hipSetDevice(l->device);
-    delete l;
-}
-
-int stmpc_ddpg_set_params(stmpc_ddpg *l, int slot, const float *values, int64_t count) {
-    if (!l || !values || slot < 0 || slot > 7) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
-    const int which = slot >= 4;
-    if (count != l->slot_len(which)) return fail(STMPC_EINVAL, "count is not the length of this slot");
-    HIPCHK(hipSetDevice(l->device));
-    std::vector<float> pad((size_t)l->np, 0.f);
-    ddpg_pad(l, l->n_in(which), values, pad, true, nullptr);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(ddpg_slot_ptr(l, slot), pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
-    if ((slot & 3) < 2) {                                            // the packed copies follow the parameters
-        ddpg_launch_adam(l, which, 0.f, 1, 0, (hipStream_t)0);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-    }
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_get_params(stmpc_ddpg *l, int slot, float *values, int64_t count) {
-    if (!l || !values || slot < 0 || slot > 7) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
-    const int which = slot >= 4;
-    if (count != l->slot_len(which)) return fail(STMPC_EINVAL, "count is not the length of this slot");
-    HIPCHK(hipSetDevice(l->device));
-    std::vector<float> pad((size_t)l->np, 0.f);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(pad.data(), ddpg_slot_ptr(l, slot), pad.size() * sizeof(float), hipMemcpyDeviceToHost));
-    ddpg_pad(l, l->n_in(which), nullptr, pad, false, values);
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_set_state(stmpc_ddpg *l, const int64_t *counters, const float *beta_pow) {
-    if (!l || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
-    if (counters[DG_CURSOR] < 0 || counters[DG_CURSOR] >= l->cfg.capacity || counters[DG_FILL] < 0 || counters[DG_FILL] > l->cfg.capacity || counters[DG_UPDATES] < 0 ||
-        counters[DG_ACTS] < 0 || counters[DG_FRAMES] < 0) return fail(STMPC_EINVAL, "counters out of range");
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    long long cn[DG_NCNT];
-    for (int i = 0; i < DG_NCNT; ++i) cn[i] = i <= DG_FRAMES ? counters[i] : 0;
-    HIPCHK(hipMemcpy(l->dev.cnt, cn, sizeof cn, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(l->dev.pi.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(l->dev.q.bpow, beta_pow + 2, 2 * sizeof(float), hipMemcpyHostToDevice));
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_get_state(stmpc_ddpg *l, int64_t *counters, float *beta_pow) {
-    if (!l || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    long long cn[DG_NCNT];
-    HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
-    for (int i = 0; i < DG_NCNT; ++i) counters[i] = cn[i];
-    HIPCHK(hipMemcpy(beta_pow, l->dev.pi.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(beta_pow + 2, l->dev.q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_push_device(stmpc_ddpg *l, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_ticks,
-                           const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated,
-                           void *stream) {
-    if (!l) return fail(STMPC_EINVAL, "learner is NULL");
-    if (N < 0 || N > l->cfg.capacity || obs_stride < l->cfg.n_obs) return fail(STMPC_EINVAL, "N exceeds the replay capacity, or obs_stride is shorter than the observation");
-    if (N == 0) return STMPC_OK;
-    if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(l->device));
-    const long long items = (long long)N * DG_ROW;
-    const int blocks = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_replay_push, dim3(blocks), dim3(256), 0, (hipStream_t)stream, l->dev, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks,
-                       d_action, d_reward, d_terminated, d_truncated);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_act_device(stmpc_ddpg *l, int N, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action, uint32_t *d_debug,
-                          void *stream) {
-    if (!l) return fail(STMPC_EINVAL, "learner is NULL");
-    if (N < 0 || obs_stride < l->cfg.n_obs) return fail(STMPC_EINVAL, "N negative, or obs_stride shorter than the observation");
-    if (N == 0) return STMPC_OK;
-    if (!d_obs || !d_ticks || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(l->device));
-    hipLaunchKernelGGL(k_ddpg_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), l->lds, (hipStream_t)stream, l->dev, N, d_obs, obs_stride, d_ticks, noise != 0,
-                       d_action, d_debug);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_update_device(stmpc_ddpg *l, int n_updates, double lr_q, double lr_pi, void *stream) {
-    if (!l) return fail(STMPC_EINVAL, "learner is NULL");
-    if (n_updates < 0 || !(lr_q >= 0) || !(lr_pi >= 0)) return fail(STMPC_EINVAL, "n_updates or a learning rate is negative");
-    HIPCHK(hipSetDevice(l->device));
-    for (int u = 0; u < n_updates; ++u) {
-        ddpg_launch_grads(l, 1, 1, (hipStream_t)stream);
-        ddpg_launch_adam(l, 1, (float)lr_q, 0, 0, (hipStream_t)stream);
-        ddpg_launch_grads(l, 0, 1, (hipStream_t)stream);
-        ddpg_launch_adam(l, 0, (float)lr_pi, 0, 1, (hipStream_t)stream);
-    }
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_grads_device(stmpc_ddpg *l, float *d_grad_actor, float *d_grad_critic, void *stream) {
-    if (!l || !d_grad_actor || !d_grad_critic) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(l->device));
-    hipStream_t st = (hipStream_t)stream;
-    ddpg_launch_grads(l, 1, 0, st);
-    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(1), (const float *)l->dev.q.g, d_grad_critic);
-    ddpg_launch_grads(l, 0, 0, st);
-    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(0), (const float *)l->dev.pi.g, d_grad_actor);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_stats_device(stmpc_ddpg *l, double *d_out, void *stream) {
-    if (!l || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(l->device));
-    hipLaunchKernelGGL(k_ddpg_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, l->dev, l->cfg.batch, d_out);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_replay_read(stmpc_ddpg *l, int64_t first, int64_t count, float *rows) {
-    if (!l || !rows) return fail(STMPC_EINVAL, "NULL argument");
-    if (first < 0 || count < 0 || first + count > l->cfg.capacity) return fail(STMPC_EINVAL, "rows outside the ring");
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    if (count) HIPCHK(hipMemcpy(rows, l->dev.ring + (size_t)first * DG_ROW, (size_t)count * DG_ROW * sizeof(float), hipMemcpyDeviceToHost));
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_gather_device(stmpc_ddpg *l, float *d_rows, void *stream) {
-    if (!l || !d_rows) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(l->device));
-    hipLaunchKernelGGL(k_replay_gather, dim3((l->cfg.batch * DG_ROW + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->dev, l->cfg.batch, d_rows);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-uint64_t stmpc_ddpg_sample_index(uint64_t seed, uint64_t update, uint32_t row, uint64_t fill) {
-    return fill ? (uint64_t)(dg_hash(seed, update, row) % fill) : 0;
-}
-
-double stmpc_ddpg_noise(uint64_t seed, uint64_t call, uint32_t row, uint32_t *draw1, uint32_t *draw2) {
-    const unsigned long long h = dg_hash(seed ^ DG_NOISE_STREAM, call, row);
-    const uint32_t u1 = (uint32_t)(h >> 40), u2 = (uint32_t)((h >> 8) & 0xFFFFFFull);
-    if (draw1) *draw1 = u1;
-    if (draw2) *draw2 = u2;
-    const double f1 = ((double)u1 + 1.0) * 5.9604644775390625e-8;
-    const volatile float theta = 6.2831855f * ((float)u2 * 5.9604644775390625e-8f);      // the float32 product the kernel forms
-    return sqrt(-2.0 * log(f1)) * cos((double)theta);
-}
-
-}  // extern "C"
-
-// ---- DDPG population (stmpc_ddpg_pop_*): P learners of the section above, one launch per kernel; kernels in stmpc_ddpg_pop_kernels.hpp ------------
-struct stmpc_ddpg_pop {
-    int device = 0;
-    std::vector<stmpc_ddpg *> members;      // owned; made by stmpc_ddpg_create, so every single-learner entry works on a borrowed member
-    DevBuf table;                           // DdpgDev [P]: the members' structs (their pointers and constants never change after create)
-    int P() const { return (int)members.size(); }
-    const DdpgDev *dev() const { return table.as<DdpgDev>(); }
-};
-
-static_assert(DG_POP_MAX == STMPC_DDPG_POP_MAX, "DdpgLr holds one learning rate per possible member");
-
-namespace {
-int ddpg_pop_lrs(const stmpc_ddpg_pop *p, const double *lr, DdpgLr &out) {
-    for (int m = 0; m < p->P(); ++m) {
-        if (!(lr[m] >= 0)) return fail(STMPC_EINVAL, "a member's learning rate is negative");
-        out.lr[m] = (float)lr[m];
-    }
-    return STMPC_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int stmpc_ddpg_pop_create(stmpc_ctx *c, const stmpc_ddpg_cfg *cfgs, int P, stmpc_ddpg_pop **out) {
-    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (P < 1 || P > DG_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
-    if (!cfgs) return fail(STMPC_EINVAL, "NULL argument");
-    for (int m = 1; m < P; ++m)
-        if (cfgs[m].n_obs != cfgs[0].n_obs || cfgs[m].h1 != cfgs[0].h1 || cfgs[m].h2 != cfgs[0].h2 || cfgs[m].batch != cfgs[0].batch || cfgs[m].capacity != cfgs[0].capacity)
-            return fail(STMPC_EINVAL, "the members of a population share n_obs, h1, h2, batch and capacity (member " + std::to_string(m) + " differs from member 0)");
-    HIPCHK(hipSetDevice(c->device));
-    stmpc_ddpg_pop *p = new stmpc_ddpg_pop();
-    p->device = c->device;
-    int rc = STMPC_OK;
-    std::vector<DdpgDev> host;
-    for (int m = 0; m < P && !rc; ++m) {
-        stmpc_ddpg *l = nullptr;
-        rc = stmpc_ddpg_create(c, cfgs + m, &l);
-        if (!rc) { p->members.push_back(l); host.push_back(l->dev); }
-    }
-    if (!rc) rc = p->table.ensure(host.size() * sizeof(DdpgDev));
-    if (!rc && hipMemcpy(p->table.p, host.data(), host.size() * sizeof(DdpgDev), hipMemcpyHostToDevice) != hipSuccess) rc = fail(STMPC_EHIP, "hipMemcpy of the member table failed");
-    const size_t lds = rc ? 0 : p->members[0]->lds;
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_critic_fwd_pop, lds);
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_actor_fwd_pop, lds);
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_act_pop, lds);
-    if (rc) { stmpc_ddpg_pop_destroy(p); return rc; }
-    *out = p;
-    return STMPC_OK;
-}
-
-void stmpc_ddpg_pop_destroy(stmpc_ddpg_pop *p) {
-    if (!p) return;
-    for (stmpc_ddpg *l : p->members) stmpc_ddpg_destroy(l);
-    (void)hipSetDevice(p->device);
-    delete p;
-}
-
-int stmpc_ddpg_pop_size(const stmpc_ddpg_pop *p) { return p ? p->P() : 0; }
-
-stmpc_ddpg *stmpc_ddpg_pop_member(stmpc_ddpg_pop *p, int m) {
-    if (!p || m < 0 || m >= p->P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
-    return p->members[m];
-}
-
-int stmpc_ddpg_pop_act_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action,
-                              uint32_t *d_debug, void *stream) {
-    if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    const stmpc_ddpg *l0 = p->members[0];
-    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
-        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
-    if (!d_obs || !d_ticks || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(p->device));
-    hipLaunchKernelGGL(k_ddpg_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, p->P()), dim3(AT_THREADS), l0->lds, (hipStream_t)stream, p->dev(), n_per_member, d_obs,
-                       obs_stride, d_ticks, noise != 0, d_action, d_debug);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_pop_push_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
-                               const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated,
-                               const uint8_t *d_truncated, void *stream) {
-    if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    const stmpc_ddpg *l0 = p->members[0];
-    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
-        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
-    if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(p->device));
-    const long long items = (long long)n_per_member * DG_ROW;       // per member: stmpc_ddpg_push_device's block count
-    const int blocks = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_replay_push_pop, dim3(blocks, p->P()), dim3(256), 0, (hipStream_t)stream, p->dev(), n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride,
-                       d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *p, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream) {
-    if (!p || !lr_q || !lr_pi) return fail(STMPC_EINVAL, "NULL argument");
-    if (n_lr != p->P()) return fail(STMPC_EINVAL, "the learning-rate arrays have " + std::to_string(n_lr) + " entries, the population " + std::to_string(p->P()) + " members");
-    if (n_updates < 0) return fail(STMPC_EINVAL, "n_updates is negative");
-    DdpgLr lq{}, lp{};
-    TRY(ddpg_pop_lrs(p, lr_q, lq));
-    TRY(ddpg_pop_lrs(p, lr_pi, lp));
-    HIPCHK(hipSetDevice(p->device));
-    const stmpc_ddpg *l = p->members[0];
-    const int P = p->P(), tiles = l->Bp / AT_TM, t1 = l->h2p / 16, t0 = l->h1p / 16, jobs = t1 * t0 + 2 * t0 + t1 + t0 + t1 + 1, ablocks = (l->np + 255) / 256;
-    hipStream_t st = (hipStream_t)stream;
-    for (int u = 0; u < n_updates; ++u) {                            // stmpc_ddpg_update_device's six launches, each over the members
-        hipLaunchKernelGGL(k_ddpg_critic_fwd_pop, dim3(tiles, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
-        hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 1, l->Bp, 1);
-        hipLaunchKernelGGL(k_ddpg_adam_pop, dim3(ablocks, P), dim3(256), 0, st, p->dev(), 1, lq, 0, 0, 1);
-        hipLaunchKernelGGL(k_ddpg_actor_fwd_pop, dim3(tiles, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
-        hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 0, l->Bp, 1);
-        hipLaunchKernelGGL(k_ddpg_adam_pop, dim3(ablocks, P), dim3(256), 0, st, p->dev(), 0, lp, 0, 1, 1);
-    }
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *p, double *d_out, void *stream) {
-    if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(p->device));
-    hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->members[0]->cfg.batch, d_out);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-}  // extern "C"
-
-// ---- actors from learners, and a population of actors (stmpc_actor_view_ddpg, stmpc_actor_pop_*); kernel in stmpc_actor_pop_kernels.hpp -----------
-struct stmpc_actor_pop {
-    int device = 0;
-    DevBuf table;                           // ActorDev [P]: the members' structs (a view's pointers are fixed for its learner's lifetime)
-    int P = 0, n_in = 0;
-    size_t lds = 0;
-    const ActorDev *dev() const { return table.as<ActorDev>(); }
-};
-
-extern "C" {
-
-int stmpc_actor_view_ddpg(stmpc_ddpg *l, int target, stmpc_actor **out) {
-    if (!l || !out) return fail(STMPC_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (target != 0 && target != 1) return fail(STMPC_EINVAL, "target must be 0 (online actor) or 1 (target actor)");
-    // k_ddpg_adam keeps both actors packed in actor_layer's lane order; biases and the last layer are read in place in the padded parameter array
-    const DdpgNet &pi = l->dev.pi;
-    const float *w = target ? pi.wt : pi.w;
-    HIPCHK(hipSetDevice(l->device));
-    stmpc_actor *a = new stmpc_actor();     // owns no buffer: destroying it frees nothing of the learner's
-    a->device = l->device; a->lds = actor_lds_bytes(l->h1p, l->h2p);
-    a->dev.p0 = target ? pi.t0 : pi.p0; a->dev.b0 = w + dg_o_b0(l->h1p);
-    a->dev.p1 = target ? pi.t1 : pi.p1; a->dev.b1 = w + dg_o_b1(l->h1p, l->h2p);
-    a->dev.w2 = w + dg_o_w2(l->h1p, l->h2p); a->dev.b2p = w + dg_o_b2(l->h1p, l->h2p);
-    a->dev.scale = l->dev.scale; a->dev.mean = l->dev.mean; a->dev.n_in = pi.n_in; a->dev.h1p = l->h1p; a->dev.h2p = l->h2p;
-    const int rc = actor_raise_lds(0, l->device, a->lds);
-    if (rc) { stmpc_actor_destroy(a); return rc; }
-    *out = a;
-    return STMPC_OK;
-}
-
-int stmpc_actor_pop_create(stmpc_ctx *c, const stmpc_actor *const *actors, int P, stmpc_actor_pop **out) {
-    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (P < 1 || P > STMPC_DDPG_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
-    if (!actors) return fail(STMPC_EINVAL, "NULL argument");
-    std::vector<ActorDev> host;
-    for (int m = 0; m < P; ++m) {
-        const stmpc_actor *a = actors[m];
-        if (!a) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " is NULL");
-        if (a->device != c->device) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " and the context are on different devices");
-        if (a->dev.n_in != actors[0]->dev.n_in || a->dev.h1p != actors[0]->dev.h1p || a->dev.h2p != actors[0]->dev.h2p)
-            return fail(STMPC_EINVAL, "the members of a population share n_in and the padded hidden widths (member " + std::to_string(m) + " differs from member 0)");
-        host.push_back(a->dev);
-    }
-    HIPCHK(hipSetDevice(c->device));
-    stmpc_actor_pop *p = new stmpc_actor_pop();
-    p->device = c->device; p->P = P; p->n_in = host[0].n_in; p->lds = actors[0]->lds;
-    int rc = p->table.ensure(host.size() * sizeof(ActorDev));
-    if (!rc && hipMemcpy(p->table.p, host.data(), host.size() * sizeof(ActorDev), hipMemcpyHostToDevice) != hipSuccess) rc = fail(STMPC_EHIP, "hipMemcpy of the member table failed");
-    if (!rc) rc = actor_raise_lds(1, c->device, p->lds);
-    if (rc) { stmpc_actor_pop_destroy(p); return rc; }
-    *out = p;
-    return STMPC_OK;
-}
-
-void stmpc_actor_pop_destroy(stmpc_actor_pop *p) {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    delete p;
-}
-
-int stmpc_actor_pop_size(const stmpc_actor_pop *p) { return p ? p->P : 0; }
-
-int stmpc_actor_pop_eval_device(stmpc_ctx *c, const stmpc_actor_pop *p, const stmpc_policy_features_cfg *f, int n_per_member, int Kmax, int step,
-                                const double *d_cur_ego4, const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa,
-                                int32_t *d_evals, float *d_feat, int feat_stride, double *d_jerk, void *stream) {
-    if (!c || !p || !f) return fail(STMPC_EINVAL, "NULL argument");
-    if (n_per_member < 0 || (long long)n_per_member * p->P > 0x7fffffffLL) return fail(STMPC_EINVAL, "n_per_member out of range");
-    const int N = n_per_member * p->P;
-    FeatCfg fc;
-    TRY(actor_eval_checks(c, p->device, p->n_in, f, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_evals, d_feat, feat_stride, d_jerk, &fc));
-    if (N == 0) return STMPC_OK;
-    const int *live;
-    TRY(rollout_live(c, N, step, &live));
-    HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_actor_eval_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, p->P), dim3(AT_THREADS), p->lds, (hipStream_t)stream, fc, p->dev(), n_per_member, Kmax,
-                       d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, d_evals, d_feat, feat_stride, d_jerk);
-    HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 

@@ -1,6 +1,10 @@
-// stmpc_host.hpp -- what the host units (stmpc.hip and stmpc_solver.hip) share: the error string and the status macros,
-// device buffers and staging, the argument checks, struct stmpc_ctx, and the few functions one unit calls in another.  Internal to the library:
-// everything declared here has hidden visibility, so none of it joins the C-ABI of include/stmpc.h.
+// stmpc_host.hpp -- what the three host units share: the error string and the status macros, device buffers and staging, the argument checks,
+// struct stmpc_ctx, and the few functions one unit calls in another (the sections "defined in <unit>" at the end).  The units:
+//   stmpc.hip          the context and the host helpers; the controllers on top of the solver (finer fit, st_control, no-jerk grid, combined
+//                      controller, policy features and actor, first-step shield); the episode world, the vector env, the flight recorder
+//   stmpc_solver.hip   the batched ST solver
+//   stmpc_learner.hip  the DDPG learner, its population, and the actor population
+// Internal to the library: everything declared here has hidden visibility, so none of it joins the C-ABI of include/stmpc.h.
 //
 // The kernel headers below are here for the structs the context holds.  Their non-template kernels are compiled only where the unit that launches them
 // has defined its STMPC_UNIT_* macro before this include; a template kernel is compiled where it is instantiated.
@@ -28,6 +32,13 @@
 #include "stmpc.h"
 
 using namespace stmpc;
+
+// The one kernel a unit names without compiling it: stmpc_learner.hip compiles and launches it (stmpc_actor_pop_kernels.hpp), actor_raise_lds in stmpc.hip
+// raises its dynamic LDS.  (Before the visibility push: a kernel keeps the visibility its header gives it.)
+namespace stmpc {
+__global__ void k_actor_eval_pop(FeatCfg f, const ActorDev *members, int n_per_member, int Kmax, const double *ego4, const int *k_count, const double *ox,
+                                 const double *ov, const double *oa, const int *live, int *evals, float *feat_out, int feat_stride, double *jerk_out);
+}
 
 #pragma GCC visibility push(hidden)
 
@@ -315,6 +326,21 @@ struct stmpc_ctx {
 
 // ---- defined in stmpc.hip
 extern double (*volatile host_pow)(double, double);
+// the policy network (stmpc_actor_create, or a view of a learner's weights: stmpc_actor_view_ddpg in stmpc_learner.hip)
+struct stmpc_actor {
+    int device = 0;
+    DevBuf p0, b0, p1, b1, w2, b2;      // empty for a view (stmpc_actor_view_ddpg): dev then points into the learner's arrays
+    ActorDev dev{};
+    size_t lds = 0;
+};
+// for stmpc_learner.hip: the lone actor's argument checks (the actor population makes them too), the rows of a rollout that are still live, an actor's
+// dynamic LDS and the kernel attribute that allows it
+int actor_eval_checks(const stmpc_ctx *c, int device, int n_in, const stmpc_policy_features_cfg *f, int N, int Kmax, int step, const double *d_cur_ego4,
+                      const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov, const int32_t *d_evals, const float *d_feat, int feat_stride,
+                      const double *d_jerk, FeatCfg *fc);
+int rollout_live(const stmpc_ctx *c, int N, int step, const int **live);
+size_t actor_lds_bytes(int h1p, int h2p);
+int actor_raise_lds(int which, int device, size_t lds);
 
 // ---- defined in stmpc_solver.hip
 void host_t_values(const stmpc_params *p, int H, double *t);

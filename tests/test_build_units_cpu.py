@@ -9,7 +9,7 @@ DEPS = {
     "stmpc_solver": ["csrc/stmpc_solver.hip", HOST, KERNELS, STMPC_H],
     "stmpc_env": ["csrc/stmpc_env.hip", HOST, KERNELS, ENV_K, STMPC_H],
     "stmpc_learner": ["csrc/stmpc_learner.hip", DDPG_K, STMPC_H],
-    build.CORE_UNIT: ["csrc/stmpc_core.hip", HOST, STMPC_H],
+    build.CORE_UNIT: ["csrc/stmpc.hip", HOST, STMPC_H],
 }
 BUILT = 100.0                                   # every object's modification time; every source is older
 
