@@ -12,7 +12,7 @@ import numpy as np
 from . import build as _build
 
 STMPC_OK, STMPC_EINVAL, STMPC_ENODEV, STMPC_EHIP, STMPC_ENOMEM, STMPC_EINTERNAL = 0, -1, -2, -3, -4, -5
-KMAX_LIMIT, H_LIMIT, S_LIMIT = 32, 64, 65000
+KMAX_LIMIT, H_LIMIT, S_LIMIT = 32, 64, 65000      # STMPC_KMAX_LIMIT, ...
 
 
 class StmpcError(RuntimeError):
@@ -102,6 +102,11 @@ class CombinedCfg(C.Structure):
                    remember_last_choice=int(bool(getattr(S, "REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED", False))))
 
 
+class CombinedCfgTable(CfgTable):
+    """A contiguous ``stmpc_combined_cfg[C]`` for ``stmpc_combined_groups_set``, from a sequence of ``CombinedCfg``; indexing gives the caller's objects."""
+    ELEM = CombinedCfg
+
+
 class FirstStepCfg(C.Structure):
     """``stmpc_first_step_cfg`` (include/stmpc.h): what st.do_conditional_st_based_on_first_step (st.py:805-814) reads besides the solver's settings."""
     _fields_ = [("tick_length", C.c_double), ("min_crash_distance", C.c_double), ("sparse_control", C.c_int)]
@@ -177,7 +182,6 @@ class SimCfg(C.Structure):
             self._route = None
             self.ego_route_xy, self.ego_route_n = None, 0
         else:
-            import numpy as np
             self._route = np.ascontiguousarray(xy, dtype=np.float64)
             assert self._route.ndim == 2 and self._route.shape[1] == 2
             self.ego_route_xy = self._route.ctypes.data_as(C.POINTER(C.c_double))
@@ -276,7 +280,6 @@ EXPORTS = (
     "stmpc_shield_traffic_mix_env_reset_device", "stmpc_shield_traffic_mix_env_step_device",
 )
 SIM_NACC = 12        # STMPC_SIM_NACC
-KMAX_LIMIT = 32      # STMPC_KMAX_LIMIT
 ENV_CONTINUOUS_JERK, ENV_JERK, ENV_ACCELERATION = 0, 1, 2                                 # STMPC_ENV_*
 REWARD_CONTINUOUS, REWARD_SLOTTED, REWARD_SLOTTED_JERK, REWARD_ST = 0, 1, 2, 3             # STMPC_REWARD_*
 ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
@@ -770,12 +773,9 @@ class Context:
     # -- controller groups (stmpc_combined_groups_*; see include/stmpc.h) --
     def combined_groups_set(self, params, cfgs, n_per_group):
         """``stmpc_combined_groups_set``: ``cfgs`` is a sequence of ``CombinedCfg``, one per controller group."""
-        cfgs = list(cfgs)
-        arr = (CombinedCfg * max(len(cfgs), 1))()
-        for i, c in enumerate(cfgs):
-            C.memmove(C.byref(arr, i * C.sizeof(CombinedCfg)), C.byref(c), C.sizeof(CombinedCfg))
+        t = CombinedCfgTable.of(cfgs)
         self._control_groups_key = None       # (combined.ControlGroups.ensure_set's note of the table the context holds)
-        self._chk(self._lib.stmpc_combined_groups_set(self._h, C.byref(params), arr, len(cfgs), int(n_per_group)))
+        self._chk(self._lib.stmpc_combined_groups_set(self._h, C.byref(params), t.array, len(t), int(n_per_group)))
 
     def combined_groups_clear(self):
         self._control_groups_key = None
@@ -1078,11 +1078,29 @@ class Context:
     # -- first-step shield on traffic groups, reward groups and the traffic mix (stmpc_shield_*groups* / stmpc_shield_traffic_mix_*; see include/stmpc.h) ----
     @staticmethod
     def _penalties(takeover_penalties):
-        """(pointer, P) of a reset's ``takeover_penalties``: None -> (NULL, 0), the shield cfg's penalty for every group."""
+        """(pointer, P, the array kept alive) of a reset's ``takeover_penalties``: None -> (NULL, 0, None), the shield cfg's penalty for every group."""
         if takeover_penalties is None:
             return None, 0, None
         w = np.ascontiguousarray(takeover_penalties, dtype=np.float64).reshape(-1)
         return _dptr(w), int(w.size), w
+
+    @staticmethod
+    def _sims(sim_cfgs):
+        """(pointer, G) of a reward-groups reset's world: one ``SimCfg`` (an ungrouped world: G = 0) or a ``SimCfgTable`` / sequence (the array owns its
+        memory; what its rows point to is the caller's, alive for the call)."""
+        if isinstance(sim_cfgs, SimCfg):
+            return C.byref(sim_cfgs), 0
+        t = SimCfgTable.of(sim_cfgs)
+        return t.array, len(t)
+
+    @staticmethod
+    def _mix(sim_cfgs, weights):
+        """(table, weights as fp64 [T]) of a traffic-mix reset: ValueError unless there is one weight per traffic type."""
+        t = SimCfgTable.of(sim_cfgs)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != len(t):
+            raise ValueError("%d weights for %d traffic types" % (w.size, len(t)))
+        return t, w
 
     def shield_env_reset_groups(self, params, cfgs, n_per_group, env_cfg, shield_cfg, takeover_penalties, d_obs, obs_stride, stream=0):
         """``stmpc_shield_traffic_groups_env_reset_device``; ``takeover_penalties``: None, or 1 or G numbers."""
@@ -1095,21 +1113,14 @@ class Context:
                                        obs_stride, stream=0):
         """``stmpc_shield_reward_groups_env_reset_device``; ``sim_cfgs`` and ``env_cfgs`` as ``env_reset_reward_groups`` takes them."""
         e = EnvCfgTable.of(env_cfgs)
-        if isinstance(sim_cfgs, SimCfg):
-            sims, G = C.byref(sim_cfgs), 0
-        else:
-            t = SimCfgTable.of(sim_cfgs)
-            sims, G = t.array, len(t)
+        sims, G = self._sims(sim_cfgs)
         ptr, P, keep = self._penalties(takeover_penalties)
         self._chk(self._lib.stmpc_shield_reward_groups_env_reset_device(self._h, C.byref(params), sims, G, int(n_per_traffic_group), e.array, len(e),
                                                                         int(n_per_reward_group), C.byref(shield_cfg), ptr, P, d_obs, int(obs_stride), stream))
 
     def shield_traffic_mix_env_reset(self, params, sim_cfgs, weights, mix_seed, env_cfg, shield_cfg, N, d_obs, obs_stride, d_traffic_type=0, stream=0):
         """``stmpc_shield_traffic_mix_env_reset_device``; ``sim_cfgs`` and ``weights`` as ``traffic_mix_env_reset`` takes them."""
-        t = SimCfgTable.of(sim_cfgs)
-        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        if w.size != len(t):
-            raise ValueError("%d weights for %d traffic types" % (w.size, len(t)))
+        t, w = self._mix(sim_cfgs, weights)
         self._chk(self._lib.stmpc_shield_traffic_mix_env_reset_device(self._h, C.byref(params), t.array, len(t), _dptr(w), C.c_uint64(int(mix_seed) & 0xFFFFFFFFFFFFFFFF),
                                                                       C.byref(env_cfg), C.byref(shield_cfg), int(N), d_obs, int(obs_stride), d_traffic_type or None,
                                                                       stream))
@@ -1145,10 +1156,7 @@ class Context:
     def traffic_mix_env_reset(self, params, sim_cfgs, weights, mix_seed, env_cfg, N, d_obs, obs_stride, d_traffic_type=0, stream=0):
         """``stmpc_traffic_mix_env_reset_device``: ``sim_cfgs`` is a ``SimCfgTable`` (or a sequence of ``SimCfg``), one per traffic type, ``weights``
         one number per type."""
-        t = SimCfgTable.of(sim_cfgs)
-        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        if w.size != len(t):
-            raise ValueError("%d weights for %d traffic types" % (w.size, len(t)))
+        t, w = self._mix(sim_cfgs, weights)
         self._chk(self._lib.stmpc_traffic_mix_env_reset_device(self._h, C.byref(params), t.array, len(t), _dptr(w), C.c_uint64(int(mix_seed) & 0xFFFFFFFFFFFFFFFF),
                                                                C.byref(env_cfg), int(N), d_obs, int(obs_stride), d_traffic_type or None, stream))
 
@@ -1165,11 +1173,7 @@ class Context:
         """``stmpc_reward_groups_env_reset_device``: ``env_cfgs`` is an ``EnvCfgTable`` (or a sequence of ``EnvCfg``), one per reward group;
         ``sim_cfgs`` is one ``SimCfg`` (an ungrouped world, ``n_per_traffic_group`` unused) or a ``SimCfgTable`` / sequence (traffic groups)."""
         e = EnvCfgTable.of(env_cfgs)
-        if isinstance(sim_cfgs, SimCfg):
-            sims, G = C.byref(sim_cfgs), 0
-        else:
-            t = SimCfgTable.of(sim_cfgs)
-            sims, G = t.array, len(t)
+        sims, G = self._sims(sim_cfgs)
         self._chk(self._lib.stmpc_reward_groups_env_reset_device(self._h, C.byref(params), sims, G, int(n_per_traffic_group), e.array, len(e),
                                                                  int(n_per_reward_group), d_obs, int(obs_stride), stream))
 

@@ -144,6 +144,99 @@ def observation_bounds(S=Settings):
     return lows, highs
 
 
+#: (shield, group axis) -> the ``_capi.Context`` methods that reset and step that env: the shapes the C entries serve (``env_entries`` reads it)
+_ENTRIES = {
+    (None, "lone"): ("env_reset", "env_step"),
+    (None, "traffic"): ("env_reset_groups", "env_step_groups"),
+    (None, "rewards"): ("env_reset_reward_groups", "env_step_reward_groups"),
+    (None, "mix"): ("traffic_mix_env_reset", "traffic_mix_env_step"),
+    ("first_step", "lone"): ("shield_env_reset", "shield_env_step"),
+    ("first_step", "traffic"): ("shield_env_reset_groups", "shield_env_step_groups"),
+    ("first_step", "rewards"): ("shield_env_reset_reward_groups", "shield_env_step_reward_groups"),
+    ("first_step", "mix"): ("shield_traffic_mix_env_reset", "shield_traffic_mix_env_step"),
+    ("combined", "lone"): ("cshield_env_reset", "cshield_env_step"),
+}
+#: entry -> the env attributes that are its leading arguments, in the method's order: what stands before ``d_obs`` of a reset and ``d_action`` of a step
+_LEAD = {
+    "env_reset": "params sim_cfg cfg n", "env_step": "params sim_cfg cfg n",
+    "env_reset_groups": "params sim_cfgs n_per_group cfg", "env_step_groups": "params cfg n",
+    "env_reset_reward_groups": "params _world n_per_group reward_cfgs n_per_reward_group", "env_step_reward_groups": "params cfg n",
+    "traffic_mix_env_reset": "params mix_cfgs mix_weights mix_seed cfg n", "traffic_mix_env_step": "params cfg n",
+    "shield_env_reset": "params sim_cfg cfg shield_cfg n", "shield_env_step": "params sim_cfg cfg shield_cfg n",
+    "shield_env_reset_groups": "params sim_cfgs n_per_group cfg shield_cfg takeover_penalties", "shield_env_step_groups": "params cfg shield_cfg n",
+    "shield_env_reset_reward_groups": "params _world n_per_group reward_cfgs n_per_reward_group shield_cfg takeover_penalties",
+    "shield_env_step_reward_groups": "params cfg shield_cfg n",
+    "shield_traffic_mix_env_reset": "params mix_cfgs mix_weights mix_seed cfg shield_cfg n", "shield_traffic_mix_env_step": "params cfg shield_cfg n",
+    "cshield_env_reset": "params sim_cfg cfg shield_cfg _actor n", "cshield_env_step": "params sim_cfg cfg shield_cfg _actor n",
+}
+_MIX_ALONE = ("a traffic mix with traffic groups, reward groups or a shield is out of scope: the mixed step serves one ungrouped world "
+              "under one reward, unshielded")
+
+
+def env_entries(shield=None, has_mix=False, R=0, G=0):
+    """(reset, step): the names of the ``_capi.Context`` methods that serve an env behind ``shield`` (None, "first_step" or "combined") with a traffic
+    mix or not, ``R`` reward groups and ``G`` traffic groups (0: none).  A pure table: no device, no torch, no context.  ValueError for the shapes no
+    entry serves: an unknown shield, a mix together with groups, R != G where both are given, anything but the lone world behind the combined shield."""
+    if shield not in (None, "first_step", "combined"):
+        raise ValueError("unknown shield %r (None, 'first_step' or 'combined')" % (shield,))
+    if has_mix and (R or G):
+        raise ValueError(_MIX_ALONE)
+    if R and G and R != G:
+        raise ValueError("the env has %d traffic groups and %d reward groups: cell c pairs traffic c with reward c, so they must coincide" % (G, R))
+    axis = "mix" if has_mix else "rewards" if R else "traffic" if G else "lone"
+    if (shield, axis) not in _ENTRIES:
+        raise ValueError("traffic groups, reward groups and a traffic mix behind the combined shield are out of scope: it serves one ungrouped world")
+    return _ENTRIES[(shield, axis)]
+
+
+def _shield_args(takeover_penalty, shield_kmax, count=None):
+    """The checked ``takeover_penalty`` / ``shield_kmax`` of a shielded env: the penalties as a list of floats.  ``count`` None: one number (a Python or
+    numpy number, a 0-d array or tensor); else one number or one per group of ``count`` groups.  ValueError unless each is finite and >= 0 and
+    ``shield_kmax`` is 1 ... ``KMAX_LIMIT``."""
+    try:
+        penalties = [float(takeover_penalty)] if count is None else [float(x) for x in np.asarray(takeover_penalty, dtype=np.float64).reshape(-1)]
+    except (TypeError, ValueError):
+        raise ValueError("takeover_penalty must be a number%s, not %r" % ("" if count is None else " or one number per group", takeover_penalty))
+    if len(penalties) not in (1, count):
+        raise ValueError("takeover_penalty has %d values for %d groups: one number, or one per group" % (len(penalties), count))
+    if not all(np.isfinite(x) and x >= 0 for x in penalties):
+        raise ValueError("takeover_penalty must be finite and not negative, not %r" % (takeover_penalty,))
+    if not 1 <= int(shield_kmax) <= _capi.KMAX_LIMIT:
+        raise ValueError("shield_kmax must be 1 ... %d (the solver's vehicles per state), not %r" % (_capi.KMAX_LIMIT, shield_kmax))
+    return penalties
+
+
+def _mix_args(seed, traffic_mix, mix_weights, mix_seed, alone):
+    """The checked traffic mix of an env: None without ``traffic_mix``, else (types, their cfgs, weights, cumulative weights, mix seed).  ``alone``:
+    whether the env has nothing the mix does not go with.  Every ValueError of the mix's arguments; touches no device."""
+    if traffic_mix is None:
+        if mix_weights is not None or mix_seed is not None:
+            raise ValueError("mix_weights and mix_seed belong to a traffic_mix: none was given")
+        return None
+    if not alone:
+        raise ValueError(_MIX_ALONE)
+    mix = list(traffic_mix)
+    mix_cfgs = episodes.traffic_mix_cfgs(mix, seed, float(Settings.MAX_EPISODE_LENGTH))
+    weights = [1.0] * len(mix) if mix_weights is None else list(mix_weights)
+    if len(weights) != len(mix):
+        raise ValueError("mix_weights has %d entries for %d traffic types" % (len(weights), len(mix)))
+    cum = traffic_mix_cum(weights)
+    return mix, mix_cfgs, [float(w) for w in weights], cum, episode_seed(seed, 2 ** 31 - 1) if mix_seed is None else int(mix_seed) & _M64
+
+
+def _summary_by(rows, owner, count):
+    """One dict per part p < ``count`` for the drained episodes ``rows`` with ``owner == p``: ``episodes`` (their number), the ``merged``, ``crashed``
+    and ``timed_out`` shares, ``mean_ticks`` and ``mean_return`` (NaN for a part without episodes)."""
+    out = []
+    for p in range(count):
+        m = owner == p
+        k = int(m.sum())
+        mean = lambda col: float(np.mean(np.asarray(rows[col], dtype=np.float64)[m])) if k else float("nan")
+        out.append({"episodes": k, "merged": mean("merged"), "crashed": mean("crashed"), "timed_out": mean("timed_out"), "mean_ticks": mean("ticks"),
+                    "mean_return": mean("episode_return")})
+    return out
+
+
 class MergeVecEnv:
     """``n`` merge environments on the device.  ``env_id``: "sumo-jerk-continuous-v0" (actions: fp64 jerks [n], not clipped to the Box, as the
     reference does not clip them), "sumo-jerk-v0" or "sumo-accel-v0" (actions: int indices [n]); ``reward``: "Continuous", "Slotted",
@@ -151,6 +244,9 @@ class MergeVecEnv:
     ``ctx``: the ``_capi.Context`` that holds the world (default: a context of its own).  A context holds one world: a second env reset on it,
     or an ``EpisodeRunner`` started on it, ends this one -- its next ``step`` raises instead of stepping the other's world.
     Kernels run on the current torch stream of the call.
+
+    Which C entries reset and step an env follows from its shape alone -- its shield, whether it has a traffic mix, its reward and traffic groups --
+    by the table ``env_entries``; every class below checks its own arguments and then hands the shape to ``_setup``, which binds the two entries once.
 
     ``traffic``: None, or a list as ``episodes.sim_cfgs`` takes: ``G = len(traffic)`` traffic groups of ``n / G`` consecutive environments
     (``stmpc_env_reset_groups_device`` / ``stmpc_env_step_groups_device``, the launches of an ungrouped env), group g bit-identical -- through
@@ -193,22 +289,26 @@ class MergeVecEnv:
 
     def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, traffic=None, rewards=None, shield=None,
                  shield_sparse=False, takeover_penalty=0.0, shield_kmax=32):
-        self.shield = shield
-        if shield is not None:                                   # (before any device call)
-            if shield not in self.SHIELDS:
-                raise ValueError("unknown shield %r (None or one of %s)" % (shield, ", ".join(self.SHIELDS)))
-            if traffic is not None or rewards is not None:
-                raise ValueError("a shielded env with traffic or reward groups is out of scope: the shielded step serves one ungrouped world under one reward")
-            try:
-                penalty = float(takeover_penalty)                # (a Python or numpy number, a 0-d array or tensor)
-            except (TypeError, ValueError):
-                raise ValueError("takeover_penalty must be a number, not %r" % (takeover_penalty,))
-            if not (np.isfinite(penalty) and penalty >= 0):
-                raise ValueError("takeover_penalty must be finite and not negative, not %r" % (takeover_penalty,))
-            if not 1 <= int(shield_kmax) <= _capi.KMAX_LIMIT:
-                raise ValueError("shield_kmax must be 1 ... %d (the solver's vehicles per state), not %r" % (_capi.KMAX_LIMIT, shield_kmax))
-        import torch
-        self.torch = torch
+        shield_cfg = self._own_shield_cfg(shield, traffic, rewards, shield_sparse, takeover_penalty, shield_kmax)
+        self._setup(n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic, rewards, None, shield, shield_cfg)
+
+    @classmethod
+    def _own_shield_cfg(cls, shield, traffic, rewards, shield_sparse, takeover_penalty, shield_kmax):
+        """The ``ShieldEnvCfg`` of ``MergeVecEnv(shield=...)`` (None without a shield), after this class's refusals: the lone world only."""
+        if shield is None:
+            return None
+        if shield not in cls.SHIELDS:
+            raise ValueError("unknown shield %r (None or one of %s)" % (shield, ", ".join(cls.SHIELDS)))
+        if traffic is not None or rewards is not None:
+            raise ValueError("a shielded env with traffic or reward groups is out of scope: the shielded step serves one ungrouped world under one reward")
+        penalty, = _shield_args(takeover_penalty, shield_kmax)
+        return _capi.ShieldEnvCfg.from_settings(Settings, shield_sparse, penalty, shield_kmax)
+
+    def _setup(self, n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic=None, rewards=None, mix=None, shield=None, shield_cfg=None, policy=None):
+        """What every constructor ends in, after its own checks: the env's settings and world (the remaining ValueErrors, all before the first device
+        call), its context and tensors, the shield's outputs (``shield``: None, "first_step" or "combined", with its ``shield_cfg``; ``policy``: the
+        combined shield's actor), the mix's (``mix``: what ``_mix_args`` returns) and the env's two entries, bound once."""
+        self.shield, self.shield_cfg = shield, shield_cfg
         self.env_id = Settings.GYM_ENVIRONMENT if env_id is None else env_id
         self.reward_name = Settings.REWARD_FUNCTION if reward is None else reward
         self.cfg = env_cfg(self.env_id, self.reward_name, autoreset, Settings, log_capacity)         # (raises ValueError first)
@@ -224,14 +324,20 @@ class MergeVecEnv:
         if self.R and self.n % self.R:
             raise ValueError("n = %d environments do not divide into %d reward groups of equal size" % (self.n, self.R))
         self.n_per_reward_group = self.n // self.R if self.R else 0
-        if self.R and self.traffic is not None and self.R != self.G:
-            raise ValueError("the env has %d traffic groups and %d reward groups: cell c pairs traffic c with reward c, so they must coincide" % (self.G, self.R))
+        entries = env_entries(shield, mix is not None, self.R, self.G)       # (ValueError unless R and G coincide)
         self.reward_names = [r.get("REWARD_FUNCTION", Settings.REWARD_FUNCTION) for r in self.rewards] if self.R else [self.reward_name]
         if self.R:
             self.cfg = self.reward_cfgs[0]                   # (the shared fields: what the step entry reads of it)
+        self.traffic_mix = None
+        if mix is not None:
+            self.traffic_mix, self.mix_cfgs, self.mix_weights, self.mix_cum, self.mix_seed = mix
+            self.T = len(self.traffic_mix)
+        import torch
+        self.torch = torch
         self.ctx = ctx if ctx is not None else _capi.Context(-1)
         self.params = _capi.Params.from_settings(Settings)
         self.sim_cfg = self.sim_cfgs[0] if self.sim_cfgs is not None else episodes.sim_cfg(seed, float(Settings.MAX_EPISODE_LENGTH))
+        self._world = self.sim_cfgs if self.sim_cfgs is not None else self.sim_cfg       # (what a reward-groups reset takes: the table, or the one cfg)
         self.log_capacity = int(log_capacity) if log_capacity else 16 * self.n
         self.obs_dim = (4 if Settings.USE_ACCELERATION_OF_OTHER_CARS else 3) * (Settings.CARS_AHEAD + Settings.CARS_BEHIND) + 4
         self.observation_low, self.observation_high = observation_bounds(Settings)
@@ -250,34 +356,45 @@ class MergeVecEnv:
         self._cur = 0
         self._ticks = z(self.n, dtype=torch.int32)
         self._reset_done = False
-        self.shield_cfg = None
+        # what a step writes besides the observation, in the entries' order, and what ``info`` shows of it: the same tensors at every step
+        out = [self._reward, self._term, self._trunc, self._final_obs, self._final_stats]
+        self._info = {"final_observation": self._final_obs, "final_stats": self._final_stats, "episode_return": self._final_stats[:, _capi.ENV_NSTAT - 1],
+                      "status": self._final_stats[:, _capi.SIM_NACC]}
+        reset_tail = []
         if shield is not None:
-            self.shield_cfg = _capi.ShieldEnvCfg.from_settings(Settings, shield_sparse, float(takeover_penalty), shield_kmax)
             self._takeover, self._reason = z(self.n, dtype=torch.bool), z(self.n, dtype=torch.int32)
             self._exec_jerk, self._takeover_ticks = z(self.n), z(self.n, dtype=torch.int32)
             self._exec_action = z(self.n) if self.continuous else None
-        # the env's reset and step entry, bound to their leading arguments: reset(d_obs, obs_stride, stream) and step(d_action, d_obs, ..., stream)
-        bind, c = functools.partial, self.ctx
-        if shield is not None:
-            self._reset = bind(c.shield_env_reset, self.params, self.sim_cfg, self.cfg, self.shield_cfg, self.n)
-            self._step = bind(c.shield_env_step, self.params, self.sim_cfg, self.cfg, self.shield_cfg, self.n)
-        elif self.R:
-            self._reset = bind(c.env_reset_reward_groups, self.params, self.sim_cfgs if self.sim_cfgs is not None else self.sim_cfg, self.n_per_group,
-                               self.reward_cfgs, self.n_per_reward_group)
-            self._step = bind(c.env_step_reward_groups, self.params, self.cfg, self.n)
-        elif self.sim_cfgs is not None:
-            self._reset = bind(c.env_reset_groups, self.params, self.sim_cfgs, self.n_per_group, self.cfg)
-            self._step = bind(c.env_step_groups, self.params, self.cfg, self.n)
-        else:
-            self._reset = bind(c.env_reset, self.params, self.sim_cfg, self.cfg, self.n)
-            self._step = bind(c.env_step, self.params, self.sim_cfg, self.cfg, self.n)
+            out += [self._takeover, self._reason, self._exec_jerk, self._exec_action, self._takeover_ticks]
+            self._info.update(takeover=self._takeover, reason=self._reason, executed_jerk=self._exec_jerk, takeover_ticks=self._takeover_ticks)
+            if self._exec_action is not None:
+                self._info["executed_action"] = self._exec_action
+        if mix is not None:
+            self._type, self._final_type = z(self.n, dtype=torch.int32), z(self.n, dtype=torch.int32)
+            out += [self._type, self._final_type]
+            reset_tail = [self._type]
+            self._info.update(traffic_type=self._type, final_traffic_type=self._final_type)
+        self._actor = policy.handle if policy is not None else None
+        self._bind(entries, reset_tail, out)
+
+    def _bind(self, entries, reset_tail, step_out):
+        """The env's reset and step entry, bound once: the ``Context`` method, its leading arguments (``_LEAD``) and the pointers that follow the per-call
+        ones.  ``reset()`` calls ``entry(*lead, d_obs, obs_stride, *tail, stream)`` and ``step()`` ``entry(*lead, d_action, d_obs, obs_stride, *out, stream)``,
+        ``lead`` held by a ``functools.partial`` and ``out`` being the step's outputs from the reward on, then the shield's, then the mix's types (None: a
+        NULL pointer).  ``_setup`` is its only caller, and every constructor calls ``_setup`` once."""
+        if hasattr(self, "_step"):
+            raise RuntimeError("an env binds its entries once")
+        bound = lambda name: functools.partial(getattr(self.ctx, name), *(getattr(self, a) for a in _LEAD[name].split()))
+        ptrs = lambda tensors: tuple(t.data_ptr() if t is not None else 0 for t in tensors)
+        self._reset, self._reset_tail = bound(entries[0]), ptrs(reset_tail)
+        self._step, self._step_out = bound(entries[1]), ptrs(step_out)
 
     def reset(self):
-        """Every environment back to episode 0 (``stmpc_env_reset_device``, or the reset entry of the env's traffic groups, reward groups or shield):
+        """Every environment back to episode 0 (``stmpc_env_reset_device``, or the reset entry of the env's traffic groups, reward groups, mix or shield):
         the observations of the start states [n][obs_dim] float32."""
         self._cur = 0
         obs = self._obs[0]
-        self._reset(obs.data_ptr(), self.obs_dim, self._stream())
+        self._reset(obs.data_ptr(), self.obs_dim, *self._reset_tail, self._stream())
         _owners[self.ctx] = self
         self._reset_done = True
         return obs
@@ -305,7 +422,8 @@ class MergeVecEnv:
         """One tick of every environment; no host synchronisation (but with ``shield_sparse=True``).  Returns (obs, reward, terminated, truncated, info) as device tensors;
         info: final_observation [n][obs_dim], final_stats [n][15] (world statistics as episodes.EpisodeRunner reads them, status, ticks, return),
         episode_return [n] (= final_stats[:, 14]) and status [n] (= final_stats[:, 12]) -- valid where terminated | truncated.  A shielded env adds
-        takeover, reason, executed_jerk, executed_action (continuous env) and takeover_ticks, valid in every row (see the class)."""
+        takeover, reason, executed_jerk, executed_action (continuous env) and takeover_ticks, valid in every row, an env with a traffic mix
+        traffic_type and final_traffic_type (see the classes).  The dict is the call's own; its tensors are the same at every step."""
         if not self._reset_done:
             raise RuntimeError("call reset() before step()")
         if _owners.get(self.ctx) is not self:
@@ -313,20 +431,9 @@ class MergeVecEnv:
         a = self._action_tensor(action)
         self._cur ^= 1
         obs = self._obs[self._cur]
-        shield_out = ()
-        if self.shield_cfg is not None:
-            shield_out = (self._takeover.data_ptr(), self._reason.data_ptr(), self._exec_jerk.data_ptr(),
-                          self._exec_action.data_ptr() if self._exec_action is not None else 0, self._takeover_ticks.data_ptr())
-        self._step(a.data_ptr(), obs.data_ptr(), self.obs_dim, self._reward.data_ptr(), self._term.data_ptr(), self._trunc.data_ptr(), self._final_obs.data_ptr(),
-                   self._final_stats.data_ptr(), *shield_out, self._stream())
+        self._step(a.data_ptr(), obs.data_ptr(), self.obs_dim, *self._step_out, self._stream())
         self._last_action = a                                # (kept alive until the kernels have read it)
-        info = {"final_observation": self._final_obs, "final_stats": self._final_stats, "episode_return": self._final_stats[:, _capi.ENV_NSTAT - 1],
-                "status": self._final_stats[:, _capi.SIM_NACC]}
-        if self.shield_cfg is not None:
-            info.update(takeover=self._takeover, reason=self._reason, executed_jerk=self._exec_jerk, takeover_ticks=self._takeover_ticks)
-            if self._exec_action is not None:
-                info["executed_action"] = self._exec_action
-        return obs, self._reward, self._term, self._trunc, info
+        return obs, self._reward, self._term, self._trunc, dict(self._info)
 
     def shield_counts(self, reset=False):
         """(states decided, states taken over, controller solves) of the shield on this env's context since the last reset of the counts
@@ -378,35 +485,14 @@ class TrafficMixVecEnv(MergeVecEnv):
     episode that ended; elsewhere the current type), device tensors, no host synchronisation.  ``traffic_type`` reads the current types,
     ``drain_episode_stats`` adds a ``traffic_type`` column (``traffic_of_log``), ``summary_by_traffic`` condenses it per type.
     ``learner.train_ddpg`` and ``learner.DDPGPopulation`` train on it as on any env.  Out of scope, refused with a ValueError before any device call:
-    a mix together with ``traffic`` groups, ``rewards`` groups or a ``shield``."""
+    a mix together with ``traffic`` groups, ``rewards`` groups or a ``shield`` (the shielded mix is a ``GroupedShieldVecEnv``).  This class checks the
+    mix's arguments; the mix's tensors, its ``info`` keys and its entries are the base class's (``_setup``)."""
 
     def __init__(self, n, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, traffic=None, rewards=None, shield=None,
                  shield_sparse=False, takeover_penalty=0.0, shield_kmax=32, *, traffic_mix=None, mix_weights=None, mix_seed=None):
-        self.traffic_mix = None
-        if traffic_mix is None:
-            if mix_weights is not None or mix_seed is not None:
-                raise ValueError("mix_weights and mix_seed belong to a traffic_mix: none was given")
-            super().__init__(n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic, rewards, shield, shield_sparse, takeover_penalty, shield_kmax)
-            return
-        if traffic is not None or rewards is not None or shield is not None:         # (before any device call)
-            raise ValueError("a traffic mix with traffic groups, reward groups or a shield is out of scope: the mixed step serves one ungrouped world "
-                             "under one reward, unshielded")
-        mix = list(traffic_mix)
-        mix_cfgs = episodes.traffic_mix_cfgs(mix, seed, float(Settings.MAX_EPISODE_LENGTH))
-        weights = [1.0] * len(mix) if mix_weights is None else list(mix_weights)
-        if len(weights) != len(mix):
-            raise ValueError("mix_weights has %d entries for %d traffic types" % (len(weights), len(mix)))
-        cum = traffic_mix_cum(weights)
-        super().__init__(n, env_id, seed, reward, autoreset, ctx, log_capacity)
-        self.traffic_mix, self.mix_cfgs, self.T = mix, mix_cfgs, len(mix)
-        self.mix_weights, self.mix_cum = [float(w) for w in weights], cum
-        self.mix_seed = episode_seed(seed, 2 ** 31 - 1) if mix_seed is None else int(mix_seed) & _M64
-        self._type = self.torch.zeros(self.n, dtype=self.torch.int32, device=self.device)
-        self._final_type = self.torch.zeros(self.n, dtype=self.torch.int32, device=self.device)
-        c = self.ctx
-        self._reset = lambda d_obs, obs_stride, stream: c.traffic_mix_env_reset(self.params, self.mix_cfgs, self.mix_weights, self.mix_seed, self.cfg, self.n,
-                                                                                d_obs, obs_stride, self._type.data_ptr(), stream)
-        self._step = lambda *a: c.traffic_mix_env_step(self.params, self.cfg, self.n, *a[:-1], self._type.data_ptr(), self._final_type.data_ptr(), a[-1])
+        mix = _mix_args(seed, traffic_mix, mix_weights, mix_seed, alone=traffic is None and rewards is None and shield is None)      # (before any device call)
+        shield_cfg = self._own_shield_cfg(shield, traffic, rewards, shield_sparse, takeover_penalty, shield_kmax)
+        self._setup(n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic, rewards, mix, shield, shield_cfg)
 
     @property
     def traffic_type(self):
@@ -418,12 +504,6 @@ class TrafficMixVecEnv(MergeVecEnv):
         if self.traffic_mix is None:
             raise RuntimeError("this env has no traffic mix")
 
-    def step(self, action):
-        out = super().step(action)
-        if self.traffic_mix is not None:
-            out[4].update(traffic_type=self._type, final_traffic_type=self._final_type)
-        return out
-
     def traffic_of_log(self, rows):
         """The traffic type of each drained episode (``rows``: what ``drain_episode_stats`` returns, or any dict with ``env`` and ``episode``
         columns), int64 [len]: host arithmetic on the two columns through ``traffic_mix_draw`` -- the log has no column for it."""
@@ -433,15 +513,7 @@ class TrafficMixVecEnv(MergeVecEnv):
     def summary_by_traffic(self, rows):
         """One dict per traffic type for drained episodes ``rows``: ``episodes`` (their number), the ``merged``, ``crashed`` and ``timed_out`` shares,
         ``mean_ticks`` and ``mean_return`` (NaN for a type without episodes)."""
-        types = self.traffic_of_log(rows)
-        out = []
-        for t in range(self.T):
-            m = types == t
-            k = int(m.sum())
-            mean = lambda col: float(np.mean(np.asarray(rows[col], dtype=np.float64)[m])) if k else float("nan")
-            out.append({"episodes": k, "merged": mean("merged"), "crashed": mean("crashed"), "timed_out": mean("timed_out"), "mean_ticks": mean("ticks"),
-                        "mean_return": mean("episode_return")})
-        return out
+        return _summary_by(rows, self.traffic_of_log(rows), self.T)
 
     def drain_episode_stats(self):
         out = super().drain_episode_stats()
@@ -472,7 +544,8 @@ class CombinedShieldVecEnv(MergeVecEnv):
 
     Refused with a ValueError before any device call: a discrete env id, ``REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED`` true (the env keeps no
     takeover history), an ``actor.ActorPopulation`` or anything else that is no hip-engine ``DDPGActor``, an actor of another ``n`` or context, and a
-    bad ``rollout_time``, ``takeover_penalty`` or ``shield_kmax``.  Out of scope: traffic groups, reward groups and the traffic mix behind this shield."""
+    bad ``rollout_time``, ``takeover_penalty`` or ``shield_kmax``.  Out of scope: traffic groups, reward groups and the traffic mix behind this shield
+    (``env_entries`` has no entry for them)."""
 
     def __init__(self, n, policy, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, *, rollout_time="env", shield_sparse=False,
                  takeover_penalty=0.0, shield_kmax=32, control=None):
@@ -492,28 +565,15 @@ class CombinedShieldVecEnv(MergeVecEnv):
             raise ValueError("the actor lives on another context than the env's: build it on ctx (or leave ctx=None to take the actor's)")
         if rollout_time not in _capi.CShieldEnvCfg.ROLLOUT_TIMES:
             raise ValueError("rollout_time must be 'env' or 'deployed', not %r" % (rollout_time,))
-        try:
-            penalty = float(takeover_penalty)
-        except (TypeError, ValueError):
-            raise ValueError("takeover_penalty must be a number, not %r" % (takeover_penalty,))
-        if not (np.isfinite(penalty) and penalty >= 0):
-            raise ValueError("takeover_penalty must be finite and not negative, not %r" % (takeover_penalty,))
-        if not 1 <= int(shield_kmax) <= _capi.KMAX_LIMIT:
-            raise ValueError("shield_kmax must be 1 ... %d (the solver's vehicles per state), not %r" % (_capi.KMAX_LIMIT, shield_kmax))
+        penalty, = _shield_args(takeover_penalty, shield_kmax)
         self.control = dict(control) if control is not None else {}
         combined.control_cfgs([self.control])                               # (ValueError for a key that is no setting of do_combined_control)
         cfg = _capi.CShieldEnvCfg.from_settings(combined._Overlay(Settings, self.control), shield_sparse, penalty, shield_kmax, rollout_time, policy.fcfg)
         if cfg.cc.remember_last_choice:
             raise ValueError("REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED is out of scope behind the combined shield: the env keeps no takeover history")
-        super().__init__(n, env_id_, seed, reward, autoreset, policy.ctx, log_capacity)
-        self.shield, self.policy, self.rollout_time, self.shield_cfg = "combined", policy, rollout_time, cfg
-        z = lambda dtype: self.torch.zeros(self.n, dtype=dtype, device=self.device)
-        self._takeover, self._reason = z(self.torch.bool), z(self.torch.int32)
-        self._exec_jerk, self._exec_action, self._takeover_ticks = z(self.torch.float64), z(self.torch.float64), z(self.torch.int32)
-        self._evals = z(self.torch.int32)
-        bind, c = functools.partial, self.ctx
-        self._reset = bind(c.cshield_env_reset, self.params, self.sim_cfg, self.cfg, cfg, policy.handle, self.n)
-        self._step = bind(c.cshield_env_step, self.params, self.sim_cfg, self.cfg, cfg, policy.handle, self.n)
+        self.policy, self.rollout_time = policy, rollout_time
+        self._setup(n, env_id_, seed, reward, autoreset, policy.ctx, log_capacity, shield="combined", shield_cfg=cfg, policy=policy)
+        self._evals = self.torch.zeros(self.n, dtype=self.torch.int32, device=self.device)
 
     @property
     def rollout_evals(self):
@@ -534,6 +594,8 @@ class GroupedShieldVecEnv(TrafficMixVecEnv):
     mixed-traffic policy trained in the closed loop of ``st.do_conditional_st_based_on_first_step`` (st.py:805-814), on the device
     (``stmpc_shield_traffic_groups_env_reset_device``, ``stmpc_shield_reward_groups_env_reset_device``, ``stmpc_shield_traffic_mix_env_reset_device`` and their
     step entries: the launches of the lone shielded step).  A class of its own: ``MergeVecEnv`` keeps refusing a shield together with groups or a mix.
+    It checks its own arguments and hands the shape (the shield with groups or a mix) to the base class's ``_setup``: nothing of it rests on what its
+    parents' constructors do.
 
     ``traffic``, ``rewards``, ``traffic_mix`` / ``mix_weights`` / ``mix_seed``: as ``MergeVecEnv`` and ``TrafficMixVecEnv`` take them; at least one
     of the three must be given, and the mix goes with neither kind of groups (ValueError).  ``takeover_penalty``: one number for every group, or one per
@@ -552,45 +614,15 @@ class GroupedShieldVecEnv(TrafficMixVecEnv):
             raise ValueError("a GroupedShieldVecEnv needs traffic groups, reward groups or a traffic_mix: the lone shielded env is MergeVecEnv(shield='first_step')")
         traffic = list(traffic) if traffic is not None else None
         rewards = list(rewards) if rewards is not None else None
-        count = len(traffic) if traffic is not None else len(rewards) if rewards is not None else 1
-        try:
-            penalties = [float(x) for x in np.asarray(takeover_penalty, dtype=np.float64).reshape(-1)]
-        except (TypeError, ValueError):
-            raise ValueError("takeover_penalty must be a number or one number per group, not %r" % (takeover_penalty,))
-        if len(penalties) not in (1, count):
-            raise ValueError("takeover_penalty has %d values for %d groups: one number, or one per group" % (len(penalties), count))
-        if not all(np.isfinite(x) and x >= 0 for x in penalties):
-            raise ValueError("takeover_penalty must be finite and not negative, not %r" % (takeover_penalty,))
-        if not 1 <= int(shield_kmax) <= _capi.KMAX_LIMIT:
-            raise ValueError("shield_kmax must be 1 ... %d (the solver's vehicles per state), not %r" % (_capi.KMAX_LIMIT, shield_kmax))
-        super().__init__(n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic, rewards, traffic_mix=traffic_mix, mix_weights=mix_weights,
-                         mix_seed=mix_seed)
-        torch = self.torch
-        self.shield, self.takeover_penalties = "first_step", penalties
+        self.takeover_penalties = _shield_args(takeover_penalty, shield_kmax, len(traffic) if traffic is not None else len(rewards) if rewards is not None else 1)
+        mix = _mix_args(seed, traffic_mix, mix_weights, mix_seed, alone=traffic is None and rewards is None)
         # (the cfg's own penalty is what the lone shielded step reads; the grouped step reads the reset's table)
-        self.shield_cfg = _capi.ShieldEnvCfg.from_settings(Settings, shield_sparse, penalties[0], shield_kmax)
-        z = lambda dtype: torch.zeros(self.n, dtype=dtype, device=self.device)
-        self._takeover, self._reason = z(torch.bool), z(torch.int32)
-        self._exec_jerk, self._takeover_ticks = z(torch.float64), z(torch.int32)
-        self._exec_action = z(torch.float64) if self.continuous else None
-        bind, c = functools.partial, self.ctx
-        if self.traffic_mix is not None:
-            self.n_groups = self.T
-            self._group_of_row = None                            # (the type the tick ran under: info["final_traffic_type"])
-            self._reset = lambda d_obs, obs_stride, stream: c.shield_traffic_mix_env_reset(self.params, self.mix_cfgs, self.mix_weights, self.mix_seed, self.cfg,
-                                                                                           self.shield_cfg, self.n, d_obs, obs_stride, self._type.data_ptr(), stream)
-            self._step = lambda *a: c.shield_traffic_mix_env_step(self.params, self.cfg, self.shield_cfg, self.n, *a[:-1], self._type.data_ptr(),
-                                                                  self._final_type.data_ptr(), a[-1])
-        else:
-            self.n_groups = self.R or self.G
-            self._group_of_row = torch.arange(self.n, device=self.device) // (self.n // self.n_groups)
-            if self.R:
-                self._reset = bind(c.shield_env_reset_reward_groups, self.params, self.sim_cfgs if self.sim_cfgs is not None else self.sim_cfg, self.n_per_group,
-                                   self.reward_cfgs, self.n_per_reward_group, self.shield_cfg, penalties)
-                self._step = bind(c.shield_env_step_reward_groups, self.params, self.cfg, self.shield_cfg, self.n)
-            else:
-                self._reset = bind(c.shield_env_reset_groups, self.params, self.sim_cfgs, self.n_per_group, self.cfg, self.shield_cfg, penalties)
-                self._step = bind(c.shield_env_step_groups, self.params, self.cfg, self.shield_cfg, self.n)
+        shield_cfg = _capi.ShieldEnvCfg.from_settings(Settings, shield_sparse, self.takeover_penalties[0], shield_kmax)
+        self._setup(n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic, rewards, mix, "first_step", shield_cfg)
+        torch = self.torch
+        self.n_groups = self.T if mix is not None else self.R or self.G
+        # the group a row's tick counts for: fixed, or (None) the type the tick ran under, info["final_traffic_type"]
+        self._group_of_row = None if mix is not None else torch.arange(self.n, device=self.device) // (self.n // self.n_groups)
         self._taken = torch.zeros(self.n_groups, dtype=torch.int64, device=self.device)
         self._lived = torch.zeros(self.n_groups, dtype=torch.int64, device=self.device)
         self._alive = torch.ones(self.n, dtype=torch.bool, device=self.device)
@@ -622,14 +654,7 @@ class GroupedShieldVecEnv(TrafficMixVecEnv):
         if self.traffic_mix is not None:
             out = self.summary_by_traffic(rows)
         else:
-            owner = np.asarray(rows["env"], dtype=np.int64) // (self.n // self.n_groups)
-            out = []
-            for g in range(self.n_groups):
-                m = owner == g
-                k = int(m.sum())
-                mean = lambda col: float(np.mean(np.asarray(rows[col], dtype=np.float64)[m])) if k else float("nan")
-                out.append({"episodes": k, "merged": mean("merged"), "crashed": mean("crashed"), "timed_out": mean("timed_out"), "mean_ticks": mean("ticks"),
-                            "mean_return": mean("episode_return")})
+            out = _summary_by(rows, np.asarray(rows["env"], dtype=np.int64) // (self.n // self.n_groups), self.n_groups)
         for d, share in zip(out, self.takeover_share()):
             d["takeover_share"] = share
         return out

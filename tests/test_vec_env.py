@@ -474,57 +474,3 @@ def test_gpu_context_holds_one_world(gpu_ctx, restore_settings):
     a.reset(), b.reset()
     a.step(torch.zeros(n, dtype=torch.float64, device="cuda")), b.step(torch.zeros(n, dtype=torch.float64, device="cuda"))
     gpu_ctx.check_error()
-
-
-# Which step entries serve an env made by which reset entry.  Read off the checks of the four step entries as each spelled them on its own (before they
-# shared one body): the plain step refuses traffic groups and reward groups and asks nothing about a shield; the traffic-groups step needs a grouped world
-# and refuses reward groups; the reward-groups step needs reward groups on either world; the shielded step needs its own reset of the same world
-# generation and refuses both kinds of groups.
-STEP_ENTRIES = ("plain", "traffic_groups", "reward_groups", "shield")
-SERVED_BY = {"plain": {"plain"}, "traffic_groups": {"traffic_groups"}, "reward_groups": {"reward_groups"}, "traffic_and_reward_groups": {"reward_groups"},
-             "shield": {"shield", "plain"}}
-OWN_STEP = {"plain": "plain", "traffic_groups": "traffic_groups", "reward_groups": "reward_groups", "traffic_and_reward_groups": "reward_groups", "shield": "shield"}
-
-
-@pytest.mark.gpu
-def test_gpu_step_entries_serve_their_own_reset_shape(gpu_ctx, restore_settings):
-    """Every step entry on every reset shape: the env's own step (and the plain step on a shield-reset context) runs, every other pairing is STMPC_EINVAL
-    and leaves the world as it was -- after which the env's own step still runs and no error is latched."""
-    import torch
-    import rl_mpc_lanemerging_amd as pkg
-    from rl_mpc_lanemerging_amd import _capi, vec_env
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    n, kmax, ctx = 8, 8, gpu_ctx
-    traffic, rewards = ["low", "fast"], [{"REWARD_FUNCTION": "Continuous"}, {"REWARD_FUNCTION": "ST"}]
-    shapes = {"plain": {}, "traffic_groups": {"traffic": traffic}, "reward_groups": {"rewards": rewards},
-              "traffic_and_reward_groups": {"traffic": traffic, "rewards": rewards}, "shield": {"shield": "first_step", "shield_kmax": kmax}}
-    assert set(shapes) == set(SERVED_BY) == set(OWN_STEP)
-    shield_cfg = _capi.ShieldEnvCfg.from_settings(pkg.Settings, False, 0.0, kmax)
-    z = lambda dtype: torch.zeros(n, dtype=dtype, device="cuda")
-    takeover, reason, exec_jerk, exec_action, takeover_ticks = z(torch.bool), z(torch.int32), z(torch.float64), z(torch.float64), z(torch.int32)
-    action = torch.linspace(-1.0, 1.0, n, dtype=torch.float64, device="cuda")
-    for shape, kwargs in shapes.items():
-        env = vec_env.MergeVecEnv(n, env_id="sumo-jerk-continuous-v0", seed=7, ctx=ctx, **kwargs)
-        env.reset()
-        out = (action.data_ptr(), env._obs[1].data_ptr(), env.obs_dim, env._reward.data_ptr(), env._term.data_ptr(), env._trunc.data_ptr(),
-               env._final_obs.data_ptr(), env._final_stats.data_ptr())
-        step = {"plain": lambda: ctx.env_step(env.params, env.sim_cfg, env.cfg, n, *out),
-                "traffic_groups": lambda: ctx.env_step_groups(env.params, env.cfg, n, *out),
-                "reward_groups": lambda: ctx.env_step_reward_groups(env.params, env.cfg, n, *out),
-                "shield": lambda: ctx.shield_env_step(env.params, env.sim_cfg, env.cfg, shield_cfg, n, *out, takeover.data_ptr(), reason.data_ptr(),
-                                                      exec_jerk.data_ptr(), exec_action.data_ptr(), takeover_ticks.data_ptr())}
-        assert set(step) == set(STEP_ENTRIES)
-        for entry in STEP_ENTRIES:
-            before = ctx.sim_read(n)
-            if entry in SERVED_BY[shape]:
-                step[entry]()
-                assert ctx.sim_read(n)[1].sum() > before[1].sum(), (shape, entry)         # (it stepped: the tick counters moved)
-                continue
-            with pytest.raises(_capi.StmpcError) as e:
-                step[entry]()
-            assert e.value.code == _capi.STMPC_EINVAL, (shape, entry)
-            for a, b in zip(before, ctx.sim_read(n)):
-                assert a.tobytes() == b.tobytes(), (shape, entry)
-            step[OWN_STEP[shape]]()
-            ctx.check_error()
-        ctx.check_error()
