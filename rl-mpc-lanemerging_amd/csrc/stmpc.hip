@@ -571,21 +571,23 @@ int upload(DevBuf &b, const std::vector<float> &v) { return upload(b, v.data(), 
 }  // namespace
 
 size_t actor_lds_bytes(int h1p, int h2p) { return ((size_t)AT_TM * AT_KIN + (size_t)AT_TM * (h1p + 4) + (size_t)AT_TM * (h2p + 4)) * sizeof(float); }
-// dynamic LDS of k_actor_eval (which = 0) / k_actor_eval_pop (1)
-// (the attribute belongs to the kernel, not to an actor: only ever raised, so that a narrower actor created later does not take the
-// dynamic LDS away from a wider one that is still in use)
-int actor_raise_lds(int which, int device, size_t lds) {
-    static size_t actor_lds_max[2][16] = {{0}};
-    size_t &lds_max = actor_lds_max[which][(unsigned)device & 15u];
+// (stmpc_host.hpp: the attribute is only ever raised)
+int raise_dynamic_lds(const void *fn, const char *kernel, LdsCeiling &ceiling, int device, size_t lds) {
+    size_t &lds_max = ceiling.max[(unsigned)device & 15u];
     if (lds > 48 * 1024 && lds > lds_max) {
-        const void *fn = which ? (const void *)k_actor_eval_pop : (const void *)k_actor_eval;
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(STMPC_EHIP, which ? "hipFuncSetAttribute(k_actor_eval_pop, dynamic LDS) failed" : "hipFuncSetAttribute(k_actor_eval, dynamic LDS) failed");
+            return fail(STMPC_EHIP, std::string("hipFuncSetAttribute(") + kernel + ", dynamic LDS) failed");
         }
         lds_max = lds;
     }
     return STMPC_OK;
+}
+// dynamic LDS of k_actor_eval (which = 0) / k_actor_eval_pop (1)
+int actor_raise_lds(int which, int device, size_t lds) {
+    static LdsCeiling ceiling[2];
+    return which ? raise_dynamic_lds((const void *)k_actor_eval_pop, "k_actor_eval_pop", ceiling[1], device, lds)
+                 : raise_dynamic_lds((const void *)k_actor_eval, "k_actor_eval", ceiling[0], device, lds);
 }
 // the argument checks stmpc_actor_eval_device and stmpc_actor_pop_eval_device share; N: all rows of the call
 int actor_eval_checks(const stmpc_ctx *c, int device, int n_in, const stmpc_policy_features_cfg *f, int N, int Kmax, int step, const double *d_cur_ego4,

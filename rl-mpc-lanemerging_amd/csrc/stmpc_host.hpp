@@ -341,6 +341,11 @@ int actor_eval_checks(const stmpc_ctx *c, int device, int n_in, const stmpc_poli
 int rollout_live(const stmpc_ctx *c, int N, int step, const int **live);
 size_t actor_lds_bytes(int h1p, int h2p);
 int actor_raise_lds(int which, int device, size_t lds);
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel, not to the actor or learner that launches it: it is only ever raised, so that
+// a narrower network created later does not take the dynamic LDS away from a wider one that is still in use.  One ceiling per kernel (and device),
+// kept by the caller; the current device is `device`.
+struct LdsCeiling { size_t max[16] = {0}; };
+int raise_dynamic_lds(const void *fn, const char *kernel, LdsCeiling &ceiling, int device, size_t lds);
 
 // ---- defined in stmpc_solver.hip
 void host_t_values(const stmpc_params *p, int H, double *t);

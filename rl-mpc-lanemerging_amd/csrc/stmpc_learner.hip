@@ -39,11 +39,13 @@ void ddpg_pad(const stmpc_ddpg *l, int n_in, const float *flat, std::vector<floa
     for (int n = 0; n < h2; ++n) item((size_t)dg_o_w2(h1p, h2p) + n);
     item((size_t)dg_o_b2(h1p, h2p));
 }
-int ddpg_set_lds(const void *fn, size_t lds) {
-    if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(STMPC_EHIP, "hipFuncSetAttribute(dynamic LDS) failed for a DDPG kernel");
-    }
+// dynamic LDS of the three per-tile kernels of a learner (pop = false) or of a population (true): raised, never lowered (raise_dynamic_lds)
+int ddpg_raise_lds(bool pop, int device, size_t lds) {
+    static LdsCeiling ceiling[2][3];
+    static const void *const fn[2][3] = {{(const void *)k_ddpg_critic_fwd, (const void *)k_ddpg_actor_fwd, (const void *)k_ddpg_act},
+                                         {(const void *)k_ddpg_critic_fwd_pop, (const void *)k_ddpg_actor_fwd_pop, (const void *)k_ddpg_act_pop}};
+    static const char *const name[2][3] = {{"k_ddpg_critic_fwd", "k_ddpg_actor_fwd", "k_ddpg_act"}, {"k_ddpg_critic_fwd_pop", "k_ddpg_actor_fwd_pop", "k_ddpg_act_pop"}};
+    for (int i = 0; i < 3; ++i) TRY(raise_dynamic_lds(fn[pop][i], name[pop][i], ceiling[pop][i], device, lds));
     return STMPC_OK;
 }
 void ddpg_launch_grads(stmpc_ddpg *l, int which, int gate, hipStream_t st) {
@@ -90,9 +92,7 @@ int stmpc_ddpg_create(stmpc_ctx *c, const stmpc_ddpg_cfg *g, stmpc_ddpg **out) {
     if (!rc) rc = ddpg_zero(l->ring, (size_t)g->capacity * DG_ROW * sizeof(float));
     if (!rc) rc = ddpg_zero(l->cnt, DG_NCNT * sizeof(long long));
     if (!rc) rc = ddpg_zero(l->tick, DG_NTICK * sizeof(unsigned int));
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_critic_fwd, l->lds);
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_actor_fwd, l->lds);
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_act, l->lds);
+    if (!rc) rc = ddpg_raise_lds(false, l->device, l->lds);
     if (rc) { stmpc_ddpg_destroy(l); return rc; }
     d.ring = l->ring.as<float>(); d.cnt = l->cnt.as<long long>(); d.tick = l->tick.as<unsigned int>();
     d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = g->h2; d.h1p = h1p; d.h2p = h2p; d.capacity = g->capacity; d.replay_start = g->replay_start; d.seed = g->seed;
@@ -306,10 +306,7 @@ int stmpc_ddpg_pop_create(stmpc_ctx *c, const stmpc_ddpg_cfg *cfgs, int P, stmpc
     }
     if (!rc) rc = p->table.ensure(host.size() * sizeof(DdpgDev));
     if (!rc && hipMemcpy(p->table.p, host.data(), host.size() * sizeof(DdpgDev), hipMemcpyHostToDevice) != hipSuccess) rc = fail(STMPC_EHIP, "hipMemcpy of the member table failed");
-    const size_t lds = rc ? 0 : p->members[0]->lds;
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_critic_fwd_pop, lds);
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_actor_fwd_pop, lds);
-    if (!rc) rc = ddpg_set_lds((const void *)k_ddpg_act_pop, lds);
+    if (!rc) rc = ddpg_raise_lds(true, p->device, p->members[0]->lds);
     if (rc) { stmpc_ddpg_pop_destroy(p); return rc; }
     *out = p;
     return STMPC_OK;
