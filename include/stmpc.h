@@ -649,6 +649,57 @@ int  stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *pop, int n_updates, const doub
 int  stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *pop, double *d_out, void *stream);
 
 /*
+ * TD3 learner (Fujimoto et al. 2018) on the device: the DDPG learner above with two critics, clipped noise on the target action, and the actor and all
+ * targets updated only every policy_delay-th update.  (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION
+ * stays 8.)  With u the updates done so far and the minibatch rows of stmpc_ddpg_sample_index(seed, u, r, fill), one update is
+ *   eps_r = clip(target_noise_std * gauss(u, r), -noise_clip, +noise_clip), gauss as stmpc_td3_noise restates it;
+ *   a'_r = clip(pi_target(s'_r) + eps_r, action_low, action_high);  y_r = r_r + gamma * mask_r * min(Q1_target(s'_r, a'_r), Q2_target(s'_r, a'_r));
+ *   each critic: one Adam step on mean((Q_i(s, a) - y)^2) with lr_q, its own moments and beta powers;
+ *   only if (u + 1) % policy_delay == 0: one Adam step of the actor on -mean(Q1(s, pi(s))) with the Q1 just stepped and lr_pi, then the Polyak update
+ *   of the actor's and both critics' targets (the actor's beta powers advance only when it steps);  updates += 1.
+ * Nothing happens until more than replay_start frames were pushed.  Every update queues the same six launches; whether it is gated or its delayed
+ * half is due is decided on the device, so a chain with updates stays free of host synchronisation and capturable.  With target_noise_std = 0,
+ * policy_delay = 1 and critic 2 equal to critic 1, every bit of the actor and of both critics equals stmpc_ddpg_update_device's.
+ *   create          refuses policy_delay < 1, negative or non-finite noise fields and whatever stmpc_ddpg_create refuses, before any device call
+ *   stmpc_td3_base  the BORROWED DDPG learner that owns the actor, critic 1, the ring and the counters, valid until stmpc_td3_destroy (never
+ *                   stmpc_ddpg_destroy it).  act_device, push_device, set / get_params, set / get_state, replay_read, gather_device, stats_device
+ *                   and stmpc_actor_view_ddpg work on it as on any learner; stmpc_ddpg_update_device and stmpc_ddpg_grads_device on it return
+ *                   STMPC_EINVAL and change nothing (they would step critic 1 alone)
+ *   set / get_params    critic 2's four slots, HOST float32 in the critic's slot layout: STMPC_TD3_CRITIC2, _CRITIC2_TARGET, _CRITIC2_M, _CRITIC2_V
+ *   set / get_state     critic 2's running beta powers, HOST float32 [2]
+ *   update_device   n_updates updates with the critics' / the actor's learning rate
+ *   grads_device    debug, no replay_start gate, nothing applied: the actor's gradient against the current critic 1, and both critics' gradients
+ *                   (DEVICE float32, slot layout)
+ *   targets_device  debug: d_out DEVICE float32 [batch][5] = eps, a', Q1_target, Q2_target, y of the minibatch the next update will draw
+ *   stats_device    d_out DEVICE fp64 [6]: loss of critic 1, of critic 2, mean Q1(s, a), mean Q2(s, a) of the last minibatch, fill, updates done
+ *   stmpc_td3_noise host only, no learner: the standard normal in fp64 of (seed, update, row) and its two draws -- stmpc_ddpg_noise on another stream
+ */
+#define STMPC_TD3_CRITIC2 0
+#define STMPC_TD3_CRITIC2_TARGET 1
+#define STMPC_TD3_CRITIC2_M 2
+#define STMPC_TD3_CRITIC2_V 3
+typedef struct stmpc_td3_cfg {
+    stmpc_ddpg_cfg base;             /* everything the DDPG learner takes */
+    double target_noise_std;         /* smoothing noise on the target action, absolute (0.2 * tanh_scale) */
+    double noise_clip;               /* its clip, absolute (0.5 * tanh_scale) */
+    int32_t policy_delay;            /* the actor and the targets step every policy_delay-th update (2); >= 1 */
+    int32_t reserved0;
+} stmpc_td3_cfg;
+typedef struct stmpc_td3 stmpc_td3;
+int  stmpc_td3_create(stmpc_ctx *ctx, const stmpc_td3_cfg *cfg, stmpc_td3 **out);
+void stmpc_td3_destroy(stmpc_td3 *learner);
+stmpc_ddpg *stmpc_td3_base(stmpc_td3 *learner);
+int  stmpc_td3_set_params(stmpc_td3 *learner, int slot, const float *values, int64_t count);
+int  stmpc_td3_get_params(stmpc_td3 *learner, int slot, float *values, int64_t count);
+int  stmpc_td3_set_state(stmpc_td3 *learner, const float *beta_pow2);
+int  stmpc_td3_get_state(stmpc_td3 *learner, float *beta_pow2);
+int  stmpc_td3_update_device(stmpc_td3 *learner, int n_updates, double lr_q, double lr_pi, void *stream);
+int  stmpc_td3_grads_device(stmpc_td3 *learner, float *d_grad_actor, float *d_grad_critic1, float *d_grad_critic2, void *stream);
+int  stmpc_td3_targets_device(stmpc_td3 *learner, float *d_out, void *stream);
+int  stmpc_td3_stats_device(stmpc_td3 *learner, double *d_out, void *stream);
+double stmpc_td3_noise(uint64_t seed, uint64_t update, uint32_t row, uint32_t *draw1, uint32_t *draw2);
+
+/*
  * Actors straight from learners, and a population of actors evaluated in one launch.  The reference's workflow ends a training with an evaluation
  * of the model it trained (ddpg.train_ddpg_all_with_lr_drop's closing `evaluate`, ddpg.py:96-117) and publishes a matrix of EVALUATE_COMBINED_DDPG runs, one per
  * MODEL_NAME (DDPGAgent.load + get_control, ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json, experiment_data/saved_data.csv).  (Additive: new

@@ -241,6 +241,11 @@ class DDPGCfg(C.Structure):
                 ("action_low", C.c_double), ("action_high", C.c_double)]
 
 
+class TD3Cfg(C.Structure):
+    """``stmpc_td3_cfg`` (include/stmpc.h): the DDPG cfg plus the smoothing noise (absolute) and the delay of the actor and the targets."""
+    _fields_ = [("base", DDPGCfg), ("target_noise_std", C.c_double), ("noise_clip", C.c_double), ("policy_delay", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class ProfileTotals(C.Structure):
     _fields_ = [("launches", C.c_int64), ("episodes", C.c_int64), ("solve_ms", C.c_double), ("dp_kernel_ms", C.c_double)]
 
@@ -266,6 +271,8 @@ EXPORTS = (
     "stmpc_ddpg_replay_read", "stmpc_ddpg_gather_device", "stmpc_ddpg_sample_index", "stmpc_ddpg_noise",
     "stmpc_ddpg_pop_create", "stmpc_ddpg_pop_destroy", "stmpc_ddpg_pop_size", "stmpc_ddpg_pop_member", "stmpc_ddpg_pop_act_device",
     "stmpc_ddpg_pop_push_device", "stmpc_ddpg_pop_update_device", "stmpc_ddpg_pop_stats_device",
+    "stmpc_td3_create", "stmpc_td3_destroy", "stmpc_td3_base", "stmpc_td3_set_params", "stmpc_td3_get_params", "stmpc_td3_set_state", "stmpc_td3_get_state",
+    "stmpc_td3_update_device", "stmpc_td3_grads_device", "stmpc_td3_targets_device", "stmpc_td3_stats_device", "stmpc_td3_noise",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
@@ -289,6 +296,7 @@ SIM_GROUPS_MAX = 64                   # STMPC_SIM_GROUPS_MAX
 SOLVER_GROUPS_MAX = 512               # STMPC_SOLVER_GROUPS_MAX
 ENV_REWARD_GROUPS_MAX = 64            # STMPC_ENV_REWARD_GROUPS_MAX
 TRAFFIC_MIX_MAX = 64                  # STMPC_TRAFFIC_MIX_MAX
+TD3_SLOTS = ("critic2", "critic2_target", "critic2_m", "critic2_v")     # STMPC_TD3_CRITIC2 ... STMPC_TD3_CRITIC2_V
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
 REC_HDR, REC_NQ, REC_MAX_DEPTH, REC_MAX_EDGES = 10, 4, 64, 32      # STMPC_REC_HDR, STMPC_REC_NQ, STMPC_REC_MAX_DEPTH, STMPC_REC_MAX_EDGES
 REC_COLUMNS = ("tick", "x", "y", "v", "a", "s", "k", "cmd", "takeover", "jerk")      # the first STMPC_REC_HDR columns of a record
@@ -431,6 +439,21 @@ def load():
     lib.stmpc_ddpg_pop_push_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 6 + [vp]
     lib.stmpc_ddpg_pop_update_device.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, vp]
     lib.stmpc_ddpg_pop_stats_device.argtypes = [vp, vp, vp]
+    lib.stmpc_td3_create.argtypes = [vp, C.POINTER(TD3Cfg), C.POINTER(vp)]
+    lib.stmpc_td3_destroy.argtypes = [vp]
+    lib.stmpc_td3_destroy.restype = None
+    lib.stmpc_td3_base.argtypes = [vp]
+    lib.stmpc_td3_base.restype = vp
+    lib.stmpc_td3_set_params.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_td3_get_params.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_td3_set_state.argtypes = [vp, fp]
+    lib.stmpc_td3_get_state.argtypes = [vp, fp]
+    lib.stmpc_td3_update_device.argtypes = [vp, C.c_int, C.c_double, C.c_double, vp]
+    lib.stmpc_td3_grads_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.stmpc_td3_targets_device.argtypes = [vp, vp, vp]
+    lib.stmpc_td3_stats_device.argtypes = [vp, vp, vp]
+    lib.stmpc_td3_noise.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, u32p, u32p]
+    lib.stmpc_td3_noise.restype = C.c_double
     lib.stmpc_actor_view_ddpg.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_destroy.argtypes = [vp]
@@ -528,6 +551,13 @@ def ddpg_noise(seed, call, row):
     """``stmpc_ddpg_noise``: (standard normal in fp64, draw 1, draw 2) of row ``row`` in noisy acting call ``call`` (host only)."""
     u1, u2 = C.c_uint32(0), C.c_uint32(0)
     g = load().stmpc_ddpg_noise(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(call)), C.c_uint32(int(row)), C.byref(u1), C.byref(u2))
+    return float(g), int(u1.value), int(u2.value)
+
+
+def td3_noise(seed, update, row):
+    """``stmpc_td3_noise``: (standard normal in fp64, draw 1, draw 2) of minibatch row ``row`` of update ``update``'s target smoothing (host only)."""
+    u1, u2 = C.c_uint32(0), C.c_uint32(0)
+    g = load().stmpc_td3_noise(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(update)), C.c_uint32(int(row)), C.byref(u1), C.byref(u2))
     return float(g), int(u1.value), int(u2.value)
 
 
@@ -960,6 +990,54 @@ class Context:
 
     def ddpg_gather(self, handle, d_rows, stream=0):
         self._chk(self._lib.stmpc_ddpg_gather_device(handle, d_rows, stream))
+
+    # -- TD3 learner (stmpc_td3_*): a DDPG learner as base plus critic 2 ------------------------
+    def td3_create(self, cfg):
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_td3_create(self._h, C.byref(cfg), C.byref(h)))
+        return h
+
+    def td3_destroy(self, handle):
+        self._lib.stmpc_td3_destroy(handle)
+
+    def td3_base(self, handle):
+        """The base as a borrowed ``stmpc_ddpg`` handle for the ``ddpg_*`` methods above (never ``ddpg_destroy`` it)."""
+        h = self._lib.stmpc_td3_base(handle)
+        if not h:
+            self._chk(-1)
+        return C.c_void_p(h)
+
+    def td3_set_params(self, handle, slot, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        self._chk(self._lib.stmpc_td3_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+
+    def td3_get_params(self, handle, slot, count):
+        flat = np.empty(int(count), dtype=np.float32)
+        self._chk(self._lib.stmpc_td3_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        return flat
+
+    def td3_set_state(self, handle, beta_pow2):
+        bp = np.ascontiguousarray(beta_pow2, dtype=np.float32)
+        assert bp.size == 2
+        self._chk(self._lib.stmpc_td3_set_state(handle, bp.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def td3_get_state(self, handle):
+        """Critic 2's beta powers float32 [2]; synchronises."""
+        bp = np.zeros(2, dtype=np.float32)
+        self._chk(self._lib.stmpc_td3_get_state(handle, bp.ctypes.data_as(C.POINTER(C.c_float))))
+        return bp
+
+    def td3_update(self, handle, n_updates, lr_q, lr_pi, stream=0):
+        self._chk(self._lib.stmpc_td3_update_device(handle, int(n_updates), float(lr_q), float(lr_pi), stream))
+
+    def td3_grads(self, handle, d_grad_actor, d_grad_critic1, d_grad_critic2, stream=0):
+        self._chk(self._lib.stmpc_td3_grads_device(handle, d_grad_actor, d_grad_critic1, d_grad_critic2, stream))
+
+    def td3_targets(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_td3_targets_device(handle, d_out, stream))
+
+    def td3_stats(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_td3_stats_device(handle, d_out, stream))
 
     # -- DDPG population (stmpc_ddpg_pop_*): P learners, one launch per kernel ------------------------
     def ddpg_pop_create(self, cfgs):

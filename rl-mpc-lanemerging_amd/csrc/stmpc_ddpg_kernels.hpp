@@ -207,40 +207,30 @@ __device__ __forceinline__ bool ddpg_gate(const DdpgDev &L, int gate) {
 }
 
 // ---- critic pass ------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ddpg_critic_fwd_body(const DdpgDev &L, int B, int gate, unsigned char *dg_smem) {
-    if (!ddpg_gate(L, gate)) return;
-    const DdpgTile T = ddpg_tile(dg_smem, L.h1p, L.h2p);
-    const int tid = threadIdx.x, r0 = blockIdx.x * AT_TM, ns = L.n_obs + 1;
-    const long long fill = L.cnt[DG_FILL], upd = L.cnt[DG_UPDATES];
-    {   // gather: 32 lanes per row
-        const int row = tid >> 5, c = tid & 31;
-        const bool valid = r0 + row < B;
-        const long long idx = valid ? (long long)(dg_hash(L.seed, (unsigned long long)upd, (unsigned long long)(r0 + row)) % (unsigned long long)fill) : 0;
-        const float *src = L.ring + (size_t)idx * DG_ROW;
-        T.X[row * AT_KIN + c] = valid ? src[c] : 0.f;
-        T.Xn[row * AT_KIN + c] = valid ? src[32 + c] : 0.f;
-        if (c < 2) T.sc[row * 4 + c] = valid ? src[DG_R + c] : 0.f;
-    }
-    __syncthreads();
+// (its stages are functions of their own because the TD3 critic pass of stmpc_td3_kernels.hpp is made of the same ones)
+// gather: 32 lanes per row; X = (s, a), Xn = s', sc = (reward, mask)
+__device__ __forceinline__ void ddpg_gather_tile(const DdpgDev &L, const DdpgTile &T, int r0, int B, long long fill, long long upd) {
+    const int row = threadIdx.x >> 5, c = threadIdx.x & 31;
+    const bool valid = r0 + row < B;
+    const long long idx = valid ? (long long)(dg_hash(L.seed, (unsigned long long)upd, (unsigned long long)(r0 + row)) % (unsigned long long)fill) : 0;
+    const float *src = L.ring + (size_t)idx * DG_ROW;
+    T.X[row * AT_KIN + c] = valid ? src[c] : 0.f;
+    T.Xn[row * AT_KIN + c] = valid ? src[32 + c] : 0.f;
+    if (c < 2) T.sc[row * 4 + c] = valid ? src[DG_R + c] : 0.f;
+}
+// the target networks on Xn: the output of `net`'s target (pre-tanh for the actor, Q for a critic), in every lane of the row; the caller's barrier comes before H1 / H2 are written again
+__device__ __forceinline__ float ddpg_target_out(const DdpgDev &L, const DdpgNet &net, const DdpgTile &T) {
     const int ob0 = dg_o_b0(L.h1p), ob1 = dg_o_b1(L.h1p, L.h2p), ow2 = dg_o_w2(L.h1p, L.h2p), ob2 = dg_o_b2(L.h1p, L.h2p);
-    const int row = tid >> 5, part = tid & 31;
-    // a' = pi_target(s')
-    ddpg_layer<false>(T.Xn, AT_KIN, AT_KIN, L.pi.t0, L.pi.wt + ob0, T.H1, T.h1_ld, L.h1p);
+    ddpg_layer<false>(T.Xn, AT_KIN, AT_KIN, net.t0, net.wt + ob0, T.H1, T.h1_ld, L.h1p);
     __syncthreads();
-    ddpg_layer<false>(T.H1, T.h1_ld, L.h1p, L.pi.t1, L.pi.wt + ob1, T.H2, T.h2_ld, L.h2p);
+    ddpg_layer<false>(T.H1, T.h1_ld, L.h1p, net.t1, net.wt + ob1, T.H2, T.h2_ld, L.h2p);
     __syncthreads();
-    float z = ddpg_out_dot(T.H2, T.h2_ld, L.h2p, L.pi.wt + ow2, L.pi.wt[ob2]);
-    if (part == 0) T.Xn[row * AT_KIN + ns] = ddpg_tanh(z) * L.scale + L.mean;
-    __syncthreads();
-    // Q_target(s', a')
-    ddpg_layer<false>(T.Xn, AT_KIN, AT_KIN, L.q.t0, L.q.wt + ob0, T.H1, T.h1_ld, L.h1p);
-    __syncthreads();
-    ddpg_layer<false>(T.H1, T.h1_ld, L.h1p, L.q.t1, L.q.wt + ob1, T.H2, T.h2_ld, L.h2p);
-    __syncthreads();
-    const float qn = ddpg_out_dot(T.H2, T.h2_ld, L.h2p, L.q.wt + ow2, L.q.wt[ob2]);
-    const float y = T.sc[row * 4 + 0] + (L.gamma * T.sc[row * 4 + 1]) * qn;
-    __syncthreads();
-    // Q(s, a)
+    return ddpg_out_dot(T.H2, T.h2_ld, L.h2p, net.wt + ow2, net.wt[ob2]);
+}
+// Q(s, a) of the online critic L.q on X against the target y, and the backward pass down to dZ1; everything the weight gradients need goes to L's workspace
+__device__ __forceinline__ void ddpg_critic_online(const DdpgDev &L, const DdpgTile &T, int r0, int B, float y) {
+    const int tid = threadIdx.x, row = tid >> 5, part = tid & 31;
+    const int ob0 = dg_o_b0(L.h1p), ob1 = dg_o_b1(L.h1p, L.h2p), ow2 = dg_o_w2(L.h1p, L.h2p), ob2 = dg_o_b2(L.h1p, L.h2p);
     ddpg_layer<false>(T.X, AT_KIN, AT_KIN, L.q.p0, L.q.w + ob0, T.H1, T.h1_ld, L.h1p);
     __syncthreads();
     ddpg_layer<false>(T.H1, T.h1_ld, L.h1p, L.q.p1, L.q.w + ob1, T.H2, T.h2_ld, L.h2p);
@@ -270,6 +260,24 @@ __device__ __forceinline__ void ddpg_critic_fwd_body(const DdpgDev &L, int B, in
     ddpg_store_tile(T.H2, T.h2_ld, L.aD2 + (size_t)r0 * L.h2p, L.h2p);
     __syncthreads();
     ddpg_store_tile(T.H1, T.h1_ld, L.aD1 + (size_t)r0 * L.h1p, L.h1p);
+}
+__device__ __forceinline__ void ddpg_critic_fwd_body(const DdpgDev &L, int B, int gate, unsigned char *dg_smem) {
+    if (!ddpg_gate(L, gate)) return;
+    const DdpgTile T = ddpg_tile(dg_smem, L.h1p, L.h2p);
+    const int tid = threadIdx.x, r0 = blockIdx.x * AT_TM, ns = L.n_obs + 1;
+    const int row = tid >> 5, part = tid & 31;
+    ddpg_gather_tile(L, T, r0, B, L.cnt[DG_FILL], L.cnt[DG_UPDATES]);
+    __syncthreads();
+    // a' = pi_target(s')
+    const float z = ddpg_target_out(L, L.pi, T);
+    if (part == 0) T.Xn[row * AT_KIN + ns] = ddpg_tanh(z) * L.scale + L.mean;
+    __syncthreads();
+    // Q_target(s', a')
+    const float qn = ddpg_target_out(L, L.q, T);
+    const float y = T.sc[row * 4 + 0] + (L.gamma * T.sc[row * 4 + 1]) * qn;
+    __syncthreads();
+    // Q(s, a)
+    ddpg_critic_online(L, T, r0, B, y);
 }
 __global__ void __launch_bounds__(AT_THREADS) k_ddpg_critic_fwd(DdpgDev L, int B, int gate) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
@@ -399,34 +407,44 @@ __global__ void __launch_bounds__(64 * DG_WG_WAVES) k_ddpg_wgrad(DdpgDev L, int 
 __device__ __forceinline__ size_t dg_packed_index(int n, int k, int kblocks) {
     return ((((size_t)(n >> 4) * kblocks + (k >> 4)) * 64) + (n & 15) + 16 * ((k & 15) >> 2)) * 4 + (k & 3);
 }
+// one element's Adam step (bias-corrected through step = lr / (1 - beta1^t) and bc2s = sqrt(1 - beta2^t)): moments stored, the new weight returned
+__device__ __forceinline__ float ddpg_adam_step(const DdpgDev &L, const DdpgNet &net, int i, float w, float step, float bc2s) {
+    const float g = net.g[i];
+    const float m = L.beta1 * net.m[i] + L.omb1 * g;
+    const float v = L.beta2 * net.v[i] + L.omb2 * (g * g);
+    const float denom = sqrtf(v) / bc2s + L.eps;
+    net.m[i] = m; net.v[i] = v;
+    return w - step * (m / denom);
+}
+// element i of the padded parameter array (online value w, target value wt) into the packed copies the layers consume
+__device__ __forceinline__ void ddpg_repack(const DdpgDev &L, const DdpgNet &net, int i, float w, float wt) {
+    const int ow1 = dg_o_w1(L.h1p), ob1 = dg_o_b1(L.h1p, L.h2p), ob0 = dg_o_b0(L.h1p);
+    if (i < ob0) {
+        const size_t p = dg_packed_index(i / AT_KIN, i % AT_KIN, AT_KIN >> 4);
+        net.p0[p] = w; net.t0[p] = wt;
+    } else if (i >= ow1 && i < ob1) {
+        const int n = (i - ow1) / L.h1p, k = (i - ow1) % L.h1p;
+        const size_t p = dg_packed_index(n, k, L.h1p >> 4);
+        net.p1[p] = w; net.t1[p] = wt;
+        net.p1t[dg_packed_index(k, n, L.h2p >> 4)] = w;
+    }
+}
 // mode 0: Adam step with learning rate lr, Polyak, re-pack; mode 1: re-pack only (after stmpc_ddpg_set_params).  bump: this launch ends an update.
 __device__ __forceinline__ void ddpg_adam_body(const DdpgDev &L, int which, float lr, int mode, int bump, int gate) {
     if (mode == 0 && !ddpg_gate(L, gate)) return;
     const DdpgNet &net = which ? L.q : L.pi;
-    const int np = dg_nparam(L.h1p, L.h2p), ow1 = dg_o_w1(L.h1p), ob1 = dg_o_b1(L.h1p, L.h2p), ob0 = dg_o_b0(L.h1p);
+    const int np = dg_nparam(L.h1p, L.h2p);
     const float pw1 = net.bpow[0] * L.beta1, pw2 = net.bpow[1] * L.beta2;
     const long long upd = L.cnt[DG_UPDATES];
     const float step = lr / (1.0f - pw1), bc2s = sqrtf(1.0f - pw2);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < np; i += gridDim.x * blockDim.x) {
         float w = net.w[i], wt = net.wt[i];
         if (mode == 0) {
-            const float g = net.g[i];
-            const float m = L.beta1 * net.m[i] + L.omb1 * g;
-            const float v = L.beta2 * net.v[i] + L.omb2 * (g * g);
-            const float denom = sqrtf(v) / bc2s + L.eps;
-            w = w - step * (m / denom);
+            w = ddpg_adam_step(L, net, i, w, step, bc2s);
             wt = L.omtau * wt + L.tau * w;
-            net.m[i] = m; net.v[i] = v; net.w[i] = w; net.wt[i] = wt;
+            net.w[i] = w; net.wt[i] = wt;
         }
-        if (i < ob0) {
-            const size_t p = dg_packed_index(i / AT_KIN, i % AT_KIN, AT_KIN >> 4);
-            net.p0[p] = w; net.t0[p] = wt;
-        } else if (i >= ow1 && i < ob1) {
-            const int n = (i - ow1) / L.h1p, k = (i - ow1) % L.h1p;
-            const size_t p = dg_packed_index(n, k, L.h1p >> 4);
-            net.p1[p] = w; net.t1[p] = wt;
-            net.p1t[dg_packed_index(k, n, L.h2p >> 4)] = w;
-        }
+        ddpg_repack(L, net, i, w, wt);
     }
     __syncthreads();
     if (mode == 0 && threadIdx.x == 0 && dg_last_block(L.tick + DG_T_ADAM + which, gridDim.x)) {
@@ -465,6 +483,13 @@ __device__ __forceinline__ void ddpg_stats_body(const DdpgDev &L, int B, double 
 __global__ void __launch_bounds__(64) k_ddpg_stats(DdpgDev L, int B, double *out) { ddpg_stats_body(L, B, out); }
 
 // ---- acting -------------------------------------------------------------------------------------------------------------------------------------
+// a standard normal in float32 from one hash: Box-Muller on its two 24-bit draws, which are returned too
+__device__ __forceinline__ float dg_gauss(unsigned long long h, unsigned int &u1, unsigned int &u2) {
+    u1 = (unsigned int)(h >> 40); u2 = (unsigned int)((h >> 8) & 0xFFFFFFull);
+    const float f1 = (float)(u1 + 1u) * 5.9604644775390625e-8f;      // (0, 1]: multiples of 2^-24, exact in float32
+    const float f2 = (float)u2 * 5.9604644775390625e-8f;             // [0, 1)
+    return sqrtf(-2.0f * logf(f1)) * cosf(6.2831855f * f2);
+}
 // action [N] fp64 = clip(pi(obs, time_scale * ticks) + noise_std * gauss); gauss: Box-Muller on two 24-bit draws of splitmix64(seed ^ stream, acting call, env).
 // dbg (may be null) uint32 [N][4]: the two draws, the bits of the float32 gaussian, the bits of the float32 greedy action.
 __device__ __forceinline__ void ddpg_act_body(const DdpgDev &L, int N, const float *__restrict__ obs, int obs_stride, const int *__restrict__ ticks, int noise,
@@ -491,11 +516,7 @@ __device__ __forceinline__ void ddpg_act_body(const DdpgDev &L, int N, const flo
         float a = greedy, g = 0.f;
         unsigned int u1 = 0, u2 = 0;
         if (noise) {
-            const unsigned long long h = dg_hash(L.seed ^ DG_NOISE_STREAM, (unsigned long long)acts, (unsigned long long)e);
-            u1 = (unsigned int)(h >> 40); u2 = (unsigned int)((h >> 8) & 0xFFFFFFull);
-            const float f1 = (float)(u1 + 1u) * 5.9604644775390625e-8f;      // (0, 1]: multiples of 2^-24, exact in float32
-            const float f2 = (float)u2 * 5.9604644775390625e-8f;             // [0, 1)
-            g = sqrtf(-2.0f * logf(f1)) * cosf(6.2831855f * f2);
+            g = dg_gauss(dg_hash(L.seed ^ DG_NOISE_STREAM, (unsigned long long)acts, (unsigned long long)e), u1, u2);
             a = greedy + L.noise_std * g;
         }
         a = a < L.a_low ? L.a_low : (a > L.a_high ? L.a_high : a);

@@ -1,8 +1,9 @@
-// stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), actors that view a learner's networks
+// stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), the TD3 learner on top of it (stmpc_td3_*), actors that view a learner's networks
 // (stmpc_actor_view_ddpg) and the population of actors (stmpc_actor_pop_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
 #include "stmpc_ddpg_pop_kernels.hpp"
+#include "stmpc_td3_kernels.hpp"
 #include "stmpc_actor_pop_kernels.hpp"
 
 // ---- DDPG learner (stmpc_ddpg_*): replay ring, fused update, acting; kernels in stmpc_ddpg_kernels.hpp -------------------------------------------
@@ -13,6 +14,7 @@ struct stmpc_ddpg {
     DevBuf netbuf[2][13], ring, cnt, tick, ws[7];
     int h1p = 0, h2p = 0, np = 0, Bp = 0;
     size_t lds = 0;
+    bool td3_base = false;          // lent by a stmpc_td3 (stmpc_td3_base): an update or gradients of this handle alone would leave critic 2 behind
     int n_in(int which) const { return cfg.n_obs + 1 + which; }
     int64_t slot_len(int which) const { const int64_t n = n_in(which); return (int64_t)cfg.h1 * n + cfg.h1 + (int64_t)cfg.h2 * cfg.h1 + cfg.h2 + cfg.h2 + 1; }
 };
@@ -47,6 +49,15 @@ int ddpg_raise_lds(bool pop, int device, size_t lds) {
     static const char *const name[2][3] = {{"k_ddpg_critic_fwd", "k_ddpg_actor_fwd", "k_ddpg_act"}, {"k_ddpg_critic_fwd_pop", "k_ddpg_actor_fwd_pop", "k_ddpg_act_pop"}};
     for (int i = 0; i < 3; ++i) TRY(raise_dynamic_lds(fn[pop][i], name[pop][i], ceiling[pop][i], device, lds));
     return STMPC_OK;
+}
+// the host twin of dg_gauss: the standard normal of one hash in fp64, and its two draws
+double ddpg_gauss_host(unsigned long long h, uint32_t *draw1, uint32_t *draw2) {
+    const uint32_t u1 = (uint32_t)(h >> 40), u2 = (uint32_t)((h >> 8) & 0xFFFFFFull);
+    if (draw1) *draw1 = u1;
+    if (draw2) *draw2 = u2;
+    const double f1 = ((double)u1 + 1.0) * 5.9604644775390625e-8;
+    const volatile float theta = 6.2831855f * ((float)u2 * 5.9604644775390625e-8f);      // the float32 product the kernel forms
+    return sqrt(-2.0 * log(f1)) * cos((double)theta);
 }
 void ddpg_launch_grads(stmpc_ddpg *l, int which, int gate, hipStream_t st) {
     const int tiles = l->Bp / AT_TM, t1 = l->h2p / 16, t0 = l->h1p / 16;
@@ -198,6 +209,7 @@ int stmpc_ddpg_act_device(stmpc_ddpg *l, int N, const float *d_obs, int obs_stri
 
 int stmpc_ddpg_update_device(stmpc_ddpg *l, int n_updates, double lr_q, double lr_pi, void *stream) {
     if (!l) return fail(STMPC_EINVAL, "learner is NULL");
+    if (l->td3_base) return fail(STMPC_EINVAL, "this learner is the base of a TD3 learner: update it with stmpc_td3_update_device");
     if (n_updates < 0 || !(lr_q >= 0) || !(lr_pi >= 0)) return fail(STMPC_EINVAL, "n_updates or a learning rate is negative");
     HIPCHK(hipSetDevice(l->device));
     for (int u = 0; u < n_updates; ++u) {
@@ -212,6 +224,7 @@ int stmpc_ddpg_update_device(stmpc_ddpg *l, int n_updates, double lr_q, double l
 
 int stmpc_ddpg_grads_device(stmpc_ddpg *l, float *d_grad_actor, float *d_grad_critic, void *stream) {
     if (!l || !d_grad_actor || !d_grad_critic) return fail(STMPC_EINVAL, "NULL argument");
+    if (l->td3_base) return fail(STMPC_EINVAL, "this learner is the base of a TD3 learner: take its gradients with stmpc_td3_grads_device");
     HIPCHK(hipSetDevice(l->device));
     hipStream_t st = (hipStream_t)stream;
     ddpg_launch_grads(l, 1, 0, st);
@@ -252,13 +265,7 @@ uint64_t stmpc_ddpg_sample_index(uint64_t seed, uint64_t update, uint32_t row, u
 }
 
 double stmpc_ddpg_noise(uint64_t seed, uint64_t call, uint32_t row, uint32_t *draw1, uint32_t *draw2) {
-    const unsigned long long h = dg_hash(seed ^ DG_NOISE_STREAM, call, row);
-    const uint32_t u1 = (uint32_t)(h >> 40), u2 = (uint32_t)((h >> 8) & 0xFFFFFFull);
-    if (draw1) *draw1 = u1;
-    if (draw2) *draw2 = u2;
-    const double f1 = ((double)u1 + 1.0) * 5.9604644775390625e-8;
-    const volatile float theta = 6.2831855f * ((float)u2 * 5.9604644775390625e-8f);      // the float32 product the kernel forms
-    return sqrt(-2.0 * log(f1)) * cos((double)theta);
+    return ddpg_gauss_host(dg_hash(seed ^ DG_NOISE_STREAM, call, row), draw1, draw2);
 }
 
 }  // extern "C"
@@ -386,6 +393,186 @@ int stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *p, double *d_out, void *stream) 
     hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->members[0]->cfg.batch, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- TD3 learner (stmpc_td3_*): a DDPG learner as base (actor, critic 1, ring, counters) plus critic 2; kernels in stmpc_td3_kernels.hpp -----------
+struct stmpc_td3 {
+    stmpc_ddpg *base = nullptr;             // owned; lent out by stmpc_td3_base
+    stmpc_td3_cfg cfg{};
+    Td3Dev dev{};
+    DevBuf net2[11], ws2[7], tick;          // critic 2, its workspace; tickets: [0 ... DG_NTICK) view 1's, [DG_NTICK] k_td3_adam_finish's
+    float *slot_ptr(int slot) { const DdpgNet &n = dev.v[1].q; float *const p[4] = {n.w, n.wt, n.m, n.v}; return p[slot]; }
+};
+
+namespace {
+int td3_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling[2];
+    TRY(raise_dynamic_lds((const void *)k_td3_critic_fwd, "k_td3_critic_fwd", ceiling[0], device, lds));
+    return raise_dynamic_lds((const void *)k_td3_actor_fwd, "k_td3_actor_fwd", ceiling[1], device, lds);
+}
+struct Td3Grid { int tiles, jobs, ablocks; };
+Td3Grid td3_grid(const stmpc_ddpg *l) {
+    const int t1 = l->h2p / 16, t0 = l->h1p / 16;
+    return {l->Bp / AT_TM, t1 * t0 + 2 * t0 + t1 + t0 + t1 + 1, (l->np + 255) / 256};
+}
+// critic pass and weight gradients of both critics, then (if due, or gate = 0) of the actor against critic 1 as it then is
+void td3_launch_critic_grads(stmpc_td3 *t, int gate, hipStream_t st) {
+    const stmpc_ddpg *l = t->base;
+    const Td3Grid g = td3_grid(l);
+    hipLaunchKernelGGL(k_td3_critic_fwd, dim3(g.tiles, 2), dim3(AT_THREADS), l->lds, st, t->dev, l->cfg.batch, gate, (float *)nullptr);
+    hipLaunchKernelGGL(k_td3_wgrad, dim3(g.jobs, 2), dim3(64 * DG_WG_WAVES), 0, st, t->dev, 1, l->Bp, gate);
+}
+void td3_launch_actor_grads(stmpc_td3 *t, int gate, hipStream_t st) {
+    const stmpc_ddpg *l = t->base;
+    const Td3Grid g = td3_grid(l);
+    hipLaunchKernelGGL(k_td3_actor_fwd, dim3(g.tiles), dim3(AT_THREADS), l->lds, st, t->dev, l->cfg.batch, gate);
+    hipLaunchKernelGGL(k_td3_wgrad, dim3(g.jobs, 1), dim3(64 * DG_WG_WAVES), 0, st, t->dev, 0, l->Bp, gate);
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *g, stmpc_td3 **out) {
+    if (!c || !g || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (g->policy_delay < 1) return fail(STMPC_EINVAL, "policy_delay must be at least 1");
+    if (!(g->target_noise_std >= 0) || !std::isfinite(g->target_noise_std) || !(g->noise_clip >= 0) || !std::isfinite(g->noise_clip))
+        return fail(STMPC_EINVAL, "target_noise_std and noise_clip must be finite and not negative");
+    stmpc_td3 *t = new stmpc_td3();
+    t->cfg = *g;
+    int rc = stmpc_ddpg_create(c, &g->base, &t->base);
+    if (rc) { delete t; return rc; }
+    stmpc_ddpg *l = t->base;
+    l->td3_base = true;
+    DdpgDev v1 = l->dev;
+    DdpgNet &n = v1.q;
+    const size_t np = (size_t)l->np, h1p = (size_t)l->h1p, h2p = (size_t)l->h2p, Bp = (size_t)l->Bp;
+    float **ptr[11] = {&n.w, &n.wt, &n.m, &n.v, &n.g, &n.p0, &n.p1, &n.p1t, &n.t0, &n.t1, &n.bpow};
+    const size_t len[11] = {np, np, np, np, np, h1p * AT_KIN, h2p * h1p, h2p * h1p, h1p * AT_KIN, h2p * h1p, 4};
+    for (int i = 0; i < 11 && !rc; ++i) { rc = ddpg_zero(t->net2[i], len[i] * sizeof(float)); *ptr[i] = t->net2[i].as<float>(); }
+    const size_t wlen[7] = {Bp * AT_KIN, Bp * h1p, Bp * h2p, Bp * h2p, Bp * h1p, Bp, Bp * 2};
+    float **wptr[7] = {&v1.aX, &v1.aH1, &v1.aH2, &v1.aD2, &v1.aD1, &v1.adz, &v1.arow};
+    for (int i = 0; i < 7 && !rc; ++i) { rc = ddpg_zero(t->ws2[i], wlen[i] * sizeof(float)); *wptr[i] = t->ws2[i].as<float>(); }
+    if (!rc) rc = ddpg_zero(t->tick, (DG_NTICK + 1) * sizeof(unsigned int));
+    if (!rc) rc = td3_raise_lds(l->device, l->lds);
+    const float one[4] = {1.f, 1.f, 0.f, 0.f};                       // beta^0
+    if (!rc && hipMemcpy(n.bpow, one, sizeof one, hipMemcpyHostToDevice) != hipSuccess) rc = fail(STMPC_EHIP, "hipMemcpy of critic 2's beta powers failed");
+    if (rc) { stmpc_td3_destroy(t); return rc; }
+    v1.tick = t->tick.as<unsigned int>();
+    t->dev.v[0] = l->dev; t->dev.v[1] = v1;
+    t->dev.tick = v1.tick + DG_NTICK;
+    t->dev.sigma = (float)g->target_noise_std; t->dev.clip = (float)g->noise_clip; t->dev.delay = g->policy_delay;
+    *out = t;
+    return STMPC_OK;
+}
+
+void stmpc_td3_destroy(stmpc_td3 *t) {
+    if (!t) return;
+    stmpc_ddpg_destroy(t->base);            // (sets the device)
+    delete t;
+}
+
+stmpc_ddpg *stmpc_td3_base(stmpc_td3 *t) {
+    if (!t) { (void)fail(STMPC_EINVAL, "learner is NULL"); return nullptr; }
+    return t->base;
+}
+
+int stmpc_td3_set_params(stmpc_td3 *t, int slot, const float *values, int64_t count) {
+    if (!t || !values || slot < 0 || slot > 3) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
+    stmpc_ddpg *l = t->base;
+    if (count != l->slot_len(1)) return fail(STMPC_EINVAL, "count is not the length of this slot");
+    HIPCHK(hipSetDevice(l->device));
+    std::vector<float> pad((size_t)l->np, 0.f);
+    ddpg_pad(l, l->n_in(1), values, pad, true, nullptr);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(t->slot_ptr(slot), pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (slot < 2) {                                                  // the packed copies follow the parameters
+        hipLaunchKernelGGL(k_ddpg_adam, dim3((l->np + 255) / 256), dim3(256), 0, (hipStream_t)0, t->dev.v[1], 1, 0.f, 1, 0, 1);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return STMPC_OK;
+}
+
+int stmpc_td3_get_params(stmpc_td3 *t, int slot, float *values, int64_t count) {
+    if (!t || !values || slot < 0 || slot > 3) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
+    stmpc_ddpg *l = t->base;
+    if (count != l->slot_len(1)) return fail(STMPC_EINVAL, "count is not the length of this slot");
+    HIPCHK(hipSetDevice(l->device));
+    std::vector<float> pad((size_t)l->np, 0.f);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(pad.data(), t->slot_ptr(slot), pad.size() * sizeof(float), hipMemcpyDeviceToHost));
+    ddpg_pad(l, l->n_in(1), nullptr, pad, false, values);
+    return STMPC_OK;
+}
+
+int stmpc_td3_set_state(stmpc_td3 *t, const float *beta_pow2) {
+    if (!t || !beta_pow2) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->base->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(t->dev.v[1].q.bpow, beta_pow2, 2 * sizeof(float), hipMemcpyHostToDevice));
+    return STMPC_OK;
+}
+
+int stmpc_td3_get_state(stmpc_td3 *t, float *beta_pow2) {
+    if (!t || !beta_pow2) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->base->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(beta_pow2, t->dev.v[1].q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return STMPC_OK;
+}
+
+int stmpc_td3_update_device(stmpc_td3 *t, int n_updates, double lr_q, double lr_pi, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
+    if (n_updates < 0 || !(lr_q >= 0) || !(lr_pi >= 0)) return fail(STMPC_EINVAL, "n_updates or a learning rate is negative");
+    HIPCHK(hipSetDevice(t->base->device));
+    const Td3Grid g = td3_grid(t->base);
+    hipStream_t st = (hipStream_t)stream;
+    for (int u = 0; u < n_updates; ++u) {                            // the same six launches whatever the counters say
+        td3_launch_critic_grads(t, 1, st);
+        hipLaunchKernelGGL(k_td3_adam_critics, dim3(g.ablocks, 2), dim3(256), 0, st, t->dev, (float)lr_q, 1);
+        td3_launch_actor_grads(t, 1, st);
+        hipLaunchKernelGGL(k_td3_adam_finish, dim3(g.ablocks, 3), dim3(256), 0, st, t->dev, (float)lr_pi, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_td3_grads_device(stmpc_td3 *t, float *d_grad_actor, float *d_grad_critic1, float *d_grad_critic2, void *stream) {
+    if (!t || !d_grad_actor || !d_grad_critic1 || !d_grad_critic2) return fail(STMPC_EINVAL, "NULL argument");
+    stmpc_ddpg *l = t->base;
+    HIPCHK(hipSetDevice(l->device));
+    hipStream_t st = (hipStream_t)stream;
+    td3_launch_critic_grads(t, 0, st);
+    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(1), (const float *)t->dev.v[0].q.g, d_grad_critic1);
+    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(1), (const float *)t->dev.v[1].q.g, d_grad_critic2);
+    td3_launch_actor_grads(t, 0, st);
+    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(0), (const float *)l->dev.pi.g, d_grad_actor);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_td3_targets_device(stmpc_td3 *t, float *d_out, void *stream) {
+    if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    const stmpc_ddpg *l = t->base;
+    HIPCHK(hipSetDevice(l->device));
+    hipLaunchKernelGGL(k_td3_critic_fwd, dim3(l->Bp / AT_TM, 1), dim3(AT_THREADS), l->lds, (hipStream_t)stream, t->dev, l->cfg.batch, 0, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_td3_stats_device(stmpc_td3 *t, double *d_out, void *stream) {
+    if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->base->device));
+    hipLaunchKernelGGL(k_td3_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, t->dev, t->base->cfg.batch, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+double stmpc_td3_noise(uint64_t seed, uint64_t update, uint32_t row, uint32_t *draw1, uint32_t *draw2) {
+    return ddpg_gauss_host(dg_hash(seed ^ TD3_STREAM, update, row), draw1, draw2);
 }
 
 }  // extern "C"

@@ -20,6 +20,10 @@ Per update on a minibatch (s, a, r, s', mask), s including the time feature:
 
 Host twins (the suite's yardsticks, in the style of ``rewards.py``): ``update_host`` (torch autograd, float64 or float32), ``adam_host`` (numpy
 float32 in the kernel's operation order), ``sample_indices_host``, ``noise_host``.
+
+``TD3Learner`` (``TD3Config``, ``csrc/stmpc_td3_kernels.hpp``) is the same learner with TD3's three changes -- two critics and the minimum of their
+targets, clipped noise on the target action, the actor and all targets stepped every ``policy_delay``-th update -- in six launches per update that
+carry both critics in ``blockIdx.y``; twins: ``update_host_td3``, ``smoothing_noise_host``.
 """
 import math
 
@@ -70,12 +74,12 @@ def sample_indices_host(seed, update, batch, fill):
     return np.array([hash3(seed, update, r) % int(fill) for r in range(int(batch))], dtype=np.int64)
 
 
-def noise_host(seed, call, n):
+def noise_host(seed, call, n, stream=NOISE_STREAM):
     """Noisy acting call ``call``, rows 0 .. n-1: (draw1, draw2, gauss) -- the two 24-bit draws (uint32) and Box-Muller on them in float64,
-    cos taken at the float32 product 2 pi x draw2 / 2^24 the kernel forms."""
+    cos taken at the float32 product 2 pi x draw2 / 2^24 the kernel forms.  ``stream``: the constant that keeps this use of the generator apart."""
     u1, u2 = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
     for e in range(n):
-        h = hash3((int(seed) & _M64) ^ NOISE_STREAM, call, e)
+        h = hash3((int(seed) & _M64) ^ stream, call, e)
         u1[e], u2[e] = h >> 40, (h >> 8) & 0xFFFFFF
     f1 = (u1.astype(np.float64) + 1.0) * 2.0 ** -24
     theta = (np.float32(TWO_PI_F32) * (u2.astype(np.float32) * np.float32(2.0 ** -24))).astype(np.float64)
@@ -131,6 +135,22 @@ def _mlp(t, x):
     return (h @ t["w2"].T + t["b2"])[:, 0]
 
 
+def _adam_step(P, name, grads, lr, t, cfg):
+    """Adam step number ``t`` of net ``name`` of the torch parameter dict ``P`` (slots ``name``, ``name_m``, ``name_v``), bias-corrected."""
+    bc1, bc2 = 1.0 - cfg.beta1 ** t, 1.0 - cfg.beta2 ** t
+    for k in TENSORS:
+        g, m, v = grads[k], P[name + "_m"][k], P[name + "_v"][k]
+        m = cfg.beta1 * m + (1 - cfg.beta1) * g
+        v = cfg.beta2 * v + (1 - cfg.beta2) * g * g
+        P[name + "_m"][k], P[name + "_v"][k] = m, v
+        P[name][k] = P[name][k] - (lr / bc1) * m / (v.sqrt() / math.sqrt(bc2) + cfg.eps)
+
+
+def _polyak(P, name, cfg):
+    for k in TENSORS:
+        P[name + "_target"][k] = (1 - cfg.tau) * P[name + "_target"][k] + cfg.tau * P[name][k]
+
+
 def update_host(params, batch, cfg, dtype="float64", lr_q=None, lr_pi=None, grads_only=False):
     """One update (steps 1-4 of the module text) in torch with autograd, every tensor in ``dtype`` ("float64" or "float32").
     ``params``: as ``new_params`` / ``DDPGLearner.state_dict()["params"]``; returns the new one (numpy arrays of ``dtype``) and a dict with
@@ -146,14 +166,8 @@ def update_host(params, batch, cfg, dtype="float64", lr_q=None, lr_pi=None, grad
     t = int(params["updates"]) + 1
 
     def adam(name, grads):
-        bc1, bc2 = 1.0 - cfg.beta1 ** t, 1.0 - cfg.beta2 ** t
-        for k in TENSORS:
-            g, m, v = grads[k], P[name + "_m"][k], P[name + "_v"][k]
-            m = cfg.beta1 * m + (1 - cfg.beta1) * g
-            v = cfg.beta2 * v + (1 - cfg.beta2) * g * g
-            P[name + "_m"][k], P[name + "_v"][k] = m, v
-            P[name][k] = P[name][k] - (lr[name] / bc1) * m / (v.sqrt() / math.sqrt(bc2) + cfg.eps)
-            P[name + "_target"][k] = (1 - cfg.tau) * P[name + "_target"][k] + cfg.tau * P[name][k]
+        _adam_step(P, name, grads, lr[name], t, cfg)
+        _polyak(P, name, cfg)
 
     with torch.no_grad():
         a2 = torch.tanh(_mlp(P["actor_target"], s2)) * scale + mean
@@ -196,6 +210,94 @@ def adam_host(w, g, m, v, wt, beta_pow, lr, cfg):
     return w, m, v, wt, np.array([pw1, pw2], dtype=f)
 
 
+# ---- TD3: configuration and host twins ---------------------------------------------------------------------------------------------------------
+TD3_STREAM = 0x7464336E6F697365
+
+
+class TD3Config(DDPGConfig):
+    """``DDPGConfig`` plus TD3's three constants (Fujimoto et al. 2018, their defaults): ``target_noise`` and ``noise_clip`` are fractions of
+    ``tanh_scale`` as ``noise`` is; the actor and all targets are updated on every ``policy_delay``-th update."""
+
+    def __init__(self, *args, target_noise=0.2, noise_clip=0.5, policy_delay=2, **kw):
+        super().__init__(*args, **kw)
+        self.target_noise_std, self.noise_clip_abs = float(target_noise) * self.tanh_scale, float(noise_clip) * self.tanh_scale
+        self.policy_delay = int(policy_delay)
+
+    def to_c_td3(self, seed):
+        return _capi.TD3Cfg(base=self.to_c(seed), target_noise_std=self.target_noise_std, noise_clip=self.noise_clip_abs, policy_delay=self.policy_delay)
+
+
+def smoothing_noise_host(seed, update, n):
+    """Target smoothing of update ``update``, minibatch rows 0 .. n-1: (draw1, draw2, gauss) as ``noise_host`` forms them, on TD3's own stream."""
+    return noise_host(seed, update, n, stream=TD3_STREAM)
+
+
+def smoothing_eps_host(gauss, cfg, dtype=np.float64):
+    """eps = clip(sigma * gauss, -c, +c) in ``dtype`` (float32: the kernel's statement, given the kernel's float32 gauss)."""
+    f = np.dtype(dtype).type
+    return np.clip(f(cfg.target_noise_std) * np.asarray(gauss, dtype=dtype), -f(cfg.noise_clip_abs), f(cfg.noise_clip_abs))
+
+
+def new_params_td3(actor_net, critic_net, critic2_net):
+    """``new_params`` plus critic 2's four slots; ``beta_pow`` float32 [6]: actor, critic 1, critic 2."""
+    p = new_params(actor_net, critic_net)
+    p2 = new_params(actor_net, critic2_net)
+    for slot in _capi.TD3_SLOTS:
+        p[slot] = p2[slot.replace("critic2", "critic")]
+    p["beta_pow"] = np.ones(6, dtype=np.float32)
+    return p
+
+
+def update_host_td3(params, batch, cfg, dtype="float64", eps=None, lr_q=None, lr_pi=None, grads_only=False):
+    """One TD3 update in torch with autograd, every tensor in ``dtype``: ``update_host`` with the smoothed, clipped target action, the minimum of
+    both target critics, both critics stepped, and -- only if (updates + 1) % cfg.policy_delay == 0 -- the actor stepped against critic 1 and all
+    three targets moved.  ``eps``: the smoothing noise per minibatch row (None: zeros); the twin is handed it, it does not draw.
+    ``params``: as ``new_params_td3`` / ``TD3Learner.state_dict()["params"]``.  ``info`` carries ``critic_loss`` / ``critic2_loss``, ``mean_q`` /
+    ``mean_q2``, ``grad_critic`` / ``grad_critic2`` / ``grad_actor`` (None when the actor did not step) and ``targets`` [B][4] = a', Qt1, Qt2, y.
+    ``grads_only``: nothing is applied and all three gradients are taken against the current critics (``stmpc_td3_grads_device``'s mode)."""
+    import torch
+    td = getattr(torch, dtype)
+    T = lambda a: torch.tensor(np.asarray(a), dtype=td)
+    slots = _capi.DDPG_SLOTS + _capi.TD3_SLOTS
+    P = {slot: {k: T(params[slot][k]) for k in TENSORS} for slot in slots}
+    s, a, r, s2, mask = (T(batch[k]) for k in ("s", "a", "r", "s2", "mask"))
+    e = T(np.zeros(len(batch["r"])) if eps is None else eps)
+    scale, mean = cfg.tanh_scale, cfg.tanh_mean
+    lr_q, lr_pi = cfg.lr_q if lr_q is None else lr_q, cfg.lr_pi if lr_pi is None else lr_pi
+    u = int(params["updates"])
+    due = grads_only or (u + 1) % cfg.policy_delay == 0
+    with torch.no_grad():
+        a2 = torch.clamp((torch.tanh(_mlp(P["actor_target"], s2)) * scale + mean) + e, cfg.action_low, cfg.action_high)
+        x2 = torch.cat([s2, a2[:, None]], 1)
+        qt1, qt2 = _mlp(P["critic_target"], x2), _mlp(P["critic2_target"], x2)
+        y = r + cfg.gamma * mask * torch.minimum(qt1, qt2)
+    info = {"targets": torch.stack([a2, qt1, qt2, y], 1).numpy(), "grad_actor": None}
+    for name, tag in (("critic", ""), ("critic2", "2")):
+        crit = {k: P[name][k].clone().requires_grad_(True) for k in TENSORS}
+        q = _mlp(crit, torch.cat([s, a[:, None]], 1))
+        loss = ((q - y) ** 2).mean()
+        g = dict(zip(TENSORS, torch.autograd.grad(loss, [crit[k] for k in TENSORS])))
+        if not grads_only:
+            _adam_step(P, name, g, lr_q, u + 1, cfg)
+        info["critic%s_loss" % tag], info["mean_q%s" % tag], info["grad_critic%s" % tag] = float(loss.detach()), float(q.detach().mean()), {k: g[k].numpy() for k in TENSORS}
+    if due:
+        act = {k: P["actor"][k].clone().requires_grad_(True) for k in TENSORS}
+        pa = torch.tanh(_mlp(act, s)) * scale + mean
+        aloss = -_mlp(P["critic"], torch.cat([s, pa[:, None]], 1)).mean()
+        gp = dict(zip(TENSORS, torch.autograd.grad(aloss, [act[k] for k in TENSORS])))
+        info["grad_actor"] = {k: gp[k].numpy() for k in TENSORS}
+        if not grads_only:
+            _adam_step(P, "actor", gp, lr_pi, (u + 1) // cfg.policy_delay, cfg)        # the actor's own step count
+            for name in ("actor", "critic", "critic2"):
+                _polyak(P, name, cfg)
+    out = {slot: {k: P[slot][k].detach().numpy() for k in TENSORS} for slot in slots}
+    b = np.array([cfg.beta1, cfg.beta2], dtype=np.float32)
+    one = np.ones(2, dtype=np.float32)
+    out["beta_pow"] = np.array(params["beta_pow"], dtype=np.float32) * (1 if grads_only else np.concatenate([b if due else one, b, b]))
+    out["updates"] = u + (0 if grads_only else 1)
+    return out, info
+
+
 # ---- the learner -------------------------------------------------------------------------------------------------------------------------------
 class DDPGLearner:
     """``env_or_dims``: a ``MergeVecEnv`` (continuous-jerk; its context, observation width and action Box are taken over) or the observation width.
@@ -231,13 +333,17 @@ class DDPGLearner:
         self._lens = {"actor": flatten(a_net).size, "critic": flatten(q_net).size}
         if self._lens["actor"] != (c.n_obs + 2) * c.h1 + (c.h1 + 2) * c.h2 + 1:
             raise ValueError("the actor's tensors do not have the shape %d -> %d -> %d -> 1" % (c.n_obs + 1, c.h1, c.h2))
-        self.load_state_dict({"params": new_params(a_net, q_net), "counters": None})
+        self.load_state_dict({"params": self._initial_params(a_net, q_net, rng), "counters": None})
         z = lambda *sh, dtype=torch.float64: torch.zeros(sh, dtype=dtype, device=self.device)
         self._stats = z(4)
         self._actions = {}
 
     def _make_handle(self):
         return self.ctx.ddpg_create(self.cfg.to_c(self.seed))
+
+    def _initial_params(self, a_net, q_net, rng):
+        """The parameter state a new learner starts from; ``rng`` stands after the draws of the actor and the critic."""
+        return new_params(a_net, q_net)
 
     def __del__(self):
         if getattr(self, "handle", None) is not None:
@@ -333,6 +439,86 @@ class DDPGLearner:
         net = unflatten(self.ctx.ddpg_get_params(self.handle, 0, self._lens["actor"]), c.n_obs + 1, c.h1, c.h2)
         write_actor(path, net, c.tanh_scale, c.tanh_mean)
         return path
+
+
+class TD3Learner(DDPGLearner):
+    """TD3 on the device (``csrc/stmpc_td3_kernels.hpp``, ``stmpc_td3_*``): ``DDPGLearner`` with a second critic, clipped noise on the target action
+    and the actor and all targets updated every ``cfg.policy_delay``-th update (``TD3Config``; module text of ``update_host_td3``).
+
+    ``self.handle`` is the BASE: a DDPG learner handle borrowed from the TD3 handle, which owns the actor, critic 1, the ring and the counters --
+    so ``act`` / ``push`` / ``stats`` / ``export_actor`` / ``minibatch`` are inherited as they are, and ``train_ddpg``, ``actor.DDPGActor.from_learner``
+    and a shielded env's ``policy=`` take a ``TD3Learner`` like any learner.  ``init``: as ``DDPGLearner``'s, or a triple (actor, critic, critic 2)
+    of nets (critic 2 None, or no triple: a fresh draw from the next values of the same rng)."""
+
+    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None):
+        self._critic2_init = None
+        if isinstance(init, (tuple, list)):
+            a_net, q_net, self._critic2_init = init
+            init = {"actor": a_net, "critic": q_net}
+        if cfg is None:
+            cfg = TD3Config(n_obs=env_or_dims if isinstance(env_or_dims, int) else env_or_dims.obs_dim)
+        super().__init__(env_or_dims, cfg, seed=seed, init=init, ctx=ctx)
+        self._stats6 = self.torch.zeros(6, dtype=self.torch.float64, device=self.device)
+
+    def _make_handle(self):
+        self.td3 = self.ctx.td3_create(self.cfg.to_c_td3(self.seed))
+        return self.ctx.td3_base(self.td3)
+
+    def _initial_params(self, a_net, q_net, rng):
+        c = self.cfg
+        q2 = self._critic2_init if self._critic2_init is not None else init_net(c.n_obs + 2, c.h1, c.h2, rng)
+        return new_params_td3(a_net, q_net, q2)
+
+    def __del__(self):
+        self.handle = None                                          # the TD3 handle destroys its base
+        if getattr(self, "td3", None) is not None:
+            try:
+                self.ctx.td3_destroy(self.td3)
+            except Exception:
+                pass
+            self.td3 = None
+
+    def update(self, n=1, lr_q=None, lr_pi=None):
+        """``n`` TD3 updates, six launches each whatever the counters say: both critics step; on every cfg.policy_delay-th update the actor steps and
+        all targets move; nothing happens until more than cfg.replay_start frames were pushed."""
+        self.ctx.td3_update(self.td3, n, self.cfg.lr_q if lr_q is None else lr_q, self.cfg.lr_pi if lr_pi is None else lr_pi, self._stream())
+
+    def grads(self):
+        """Debug: (actor gradient against critic 1, critic 1's gradient, critic 2's gradient) on the current update index's minibatch; nothing applied;
+        synchronises."""
+        torch, c = self.torch, self.cfg
+        ga = torch.empty(self._lens["actor"], dtype=torch.float32, device=self.device)
+        g1, g2 = (torch.empty(self._lens["critic"], dtype=torch.float32, device=self.device) for _ in range(2))
+        self.ctx.td3_grads(self.td3, ga.data_ptr(), g1.data_ptr(), g2.data_ptr(), self._stream())
+        return (unflatten(ga.cpu().numpy(), c.n_obs + 1, c.h1, c.h2),) + tuple(unflatten(g.cpu().numpy(), c.n_obs + 2, c.h1, c.h2) for g in (g1, g2))
+
+    def targets(self):
+        """Debug: float32 [batch][5] = eps, a', Qt1, Qt2, y of the minibatch the next update will draw (numpy); synchronises."""
+        out = self.torch.zeros(self.cfg.batch, 5, dtype=self.torch.float32, device=self.device)
+        self.ctx.td3_targets(self.td3, out.data_ptr(), self._stream())
+        return out.cpu().numpy()
+
+    def stats_td3(self):
+        """Both critics' numbers as a dict; synchronises.  (``stats`` stays critic 1's four.)"""
+        self.ctx.td3_stats(self.td3, self._stats6.data_ptr(), self._stream())
+        s = self._stats6.cpu().numpy()
+        return {"critic_loss": float(s[0]), "critic2_loss": float(s[1]), "mean_q": float(s[2]), "mean_q2": float(s[3]), "fill": int(s[4]), "updates": int(s[5])}
+
+    def state_dict(self):
+        """``DDPGLearner.state_dict`` plus critic 2's four slots; ``beta_pow`` float32 [6]: actor, critic 1, critic 2."""
+        c = self.cfg
+        sd = super().state_dict()
+        for i, slot in enumerate(_capi.TD3_SLOTS):
+            sd["params"][slot] = unflatten(self.ctx.td3_get_params(self.td3, i, self._lens["critic"]), c.n_obs + 2, c.h1, c.h2)
+        sd["params"]["beta_pow"] = np.concatenate([sd["params"]["beta_pow"], self.ctx.td3_get_state(self.td3)])
+        return sd
+
+    def load_state_dict(self, sd):
+        p = sd["params"]
+        super().load_state_dict({"params": dict(p, beta_pow=p["beta_pow"][:4]), "counters": sd.get("counters")})
+        for i, slot in enumerate(_capi.TD3_SLOTS):
+            self.ctx.td3_set_params(self.td3, i, flatten(p[slot]))
+        self.ctx.td3_set_state(self.td3, p["beta_pow"][4:6])
 
 
 class _PopulationMember(DDPGLearner):
