@@ -700,6 +700,40 @@ int  stmpc_td3_stats_device(stmpc_td3 *learner, double *d_out, void *stream);
 double stmpc_td3_noise(uint64_t seed, uint64_t update, uint32_t row, uint32_t *draw1, uint32_t *draw2);
 
 /*
+ * A population of TD3 learners: what the population of DDPG learners above is to stmpc_ddpg, for stmpc_td3.  P independent TD3 learners -- each its
+ * own ring, actor, two critics, Adam state, counters, seed and constants, target_noise_std, noise_clip and policy_delay included -- share one vector
+ * environment and advance with ONE launch per kernel: six launches per update whatever P is and whatever the members' counters say.  Member m owns
+ * rows [m * n_per_member, (m + 1) * n_per_member) of the step tensors and is bit-identical to a lone stmpc_td3 with its cfg given its slice.
+ * (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.)  The entries read stmpc_pop_td3_*: the prefix
+ * stmpc_td3_ is the lone learner's closed set of twelve.
+ *   pop_create      P = 1 ... STMPC_TD3_POP_MAX configs whose bases share n_obs, h1, h2, batch and capacity; everything else may differ per member.
+ *                   Each member is made by stmpc_td3_create, whose refusals (policy_delay, the noise fields, the base's) apply per member
+ *   pop_member      the m-th member as a BORROWED stmpc_td3, valid until pop_destroy (never stmpc_td3_destroy it): stmpc_td3_base, set / get_params,
+ *                   set / get_state, grads_device, targets_device, stats_device -- and, on its base, replay_read, stmpc_actor_view_ddpg and the
+ *                   rest of what stmpc_td3_base lists -- work on it as on a lone learner
+ *   pop_act_device / pop_push_device   stmpc_ddpg_pop_act_device / stmpc_ddpg_pop_push_device on the members' bases: same arguments, same noise keys
+ *   pop_update_device   n_updates updates of every member; lr_q / lr_pi: HOST fp64 [n_lr], n_lr = P (they travel as kernel arguments: no copy, no
+ *                   synchronisation, capturable).  A member whose replay_start gate is shut skips its update, and a member whose delayed half is
+ *                   not due skips that half, while the others proceed; both are decided on the device from the member's own counters
+ *   pop_stats_device    d_out DEVICE fp64 [P][6]: stmpc_td3_stats_device's six numbers per member
+ * Refused with STMPC_EINVAL before any launch: P outside 1 ... 64, members that differ in a shared field, n_lr != P, a negative learning rate or
+ * n_updates, n_per_member outside 1 ... capacity, NULL pointers.
+ */
+#define STMPC_TD3_POP_MAX 64            /* == STMPC_DDPG_POP_MAX */
+typedef struct stmpc_td3_pop stmpc_td3_pop;
+int  stmpc_pop_td3_create(stmpc_ctx *ctx, const stmpc_td3_cfg *cfgs, int P, stmpc_td3_pop **out);
+void stmpc_pop_td3_destroy(stmpc_td3_pop *pop);
+int  stmpc_pop_td3_size(const stmpc_td3_pop *pop);
+stmpc_td3 *stmpc_pop_td3_member(stmpc_td3_pop *pop, int m);
+int  stmpc_pop_td3_act_device(stmpc_td3_pop *pop, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise,
+                              double *d_action, uint32_t *d_debug, void *stream);
+int  stmpc_pop_td3_push_device(stmpc_td3_pop *pop, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs,
+                               int obs_stride, const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward,
+                               const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream);
+int  stmpc_pop_td3_update_device(stmpc_td3_pop *pop, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream);
+int  stmpc_pop_td3_stats_device(stmpc_td3_pop *pop, double *d_out, void *stream);
+
+/*
  * Actors straight from learners, and a population of actors evaluated in one launch.  The reference's workflow ends a training with an evaluation
  * of the model it trained (ddpg.train_ddpg_all_with_lr_drop's closing `evaluate`, ddpg.py:96-117) and publishes a matrix of EVALUATE_COMBINED_DDPG runs, one per
  * MODEL_NAME (DDPGAgent.load + get_control, ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json, experiment_data/saved_data.csv).  (Additive: new

@@ -273,6 +273,8 @@ EXPORTS = (
     "stmpc_ddpg_pop_push_device", "stmpc_ddpg_pop_update_device", "stmpc_ddpg_pop_stats_device",
     "stmpc_td3_create", "stmpc_td3_destroy", "stmpc_td3_base", "stmpc_td3_set_params", "stmpc_td3_get_params", "stmpc_td3_set_state", "stmpc_td3_get_state",
     "stmpc_td3_update_device", "stmpc_td3_grads_device", "stmpc_td3_targets_device", "stmpc_td3_stats_device", "stmpc_td3_noise",
+    "stmpc_pop_td3_create", "stmpc_pop_td3_destroy", "stmpc_pop_td3_size", "stmpc_pop_td3_member", "stmpc_pop_td3_act_device",
+    "stmpc_pop_td3_push_device", "stmpc_pop_td3_update_device", "stmpc_pop_td3_stats_device",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
@@ -292,6 +294,7 @@ REWARD_CONTINUOUS, REWARD_SLOTTED, REWARD_SLOTTED_JERK, REWARD_ST = 0, 1, 2, 3  
 ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
 DDPG_ROW, DDPG_NCOUNTERS = 68, 8      # STMPC_DDPG_ROW, STMPC_DDPG_NCOUNTERS
 DDPG_POP_MAX = 64                     # STMPC_DDPG_POP_MAX
+TD3_POP_MAX = 64                      # STMPC_TD3_POP_MAX
 SIM_GROUPS_MAX = 64                   # STMPC_SIM_GROUPS_MAX
 SOLVER_GROUPS_MAX = 512               # STMPC_SOLVER_GROUPS_MAX
 ENV_REWARD_GROUPS_MAX = 64            # STMPC_ENV_REWARD_GROUPS_MAX
@@ -454,6 +457,16 @@ def load():
     lib.stmpc_td3_stats_device.argtypes = [vp, vp, vp]
     lib.stmpc_td3_noise.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, u32p, u32p]
     lib.stmpc_td3_noise.restype = C.c_double
+    lib.stmpc_pop_td3_create.argtypes = [vp, C.POINTER(TD3Cfg), C.c_int, C.POINTER(vp)]
+    lib.stmpc_pop_td3_destroy.argtypes = [vp]
+    lib.stmpc_pop_td3_destroy.restype = None
+    lib.stmpc_pop_td3_size.argtypes = [vp]
+    lib.stmpc_pop_td3_member.argtypes = [vp, C.c_int]
+    lib.stmpc_pop_td3_member.restype = vp
+    lib.stmpc_pop_td3_act_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    lib.stmpc_pop_td3_push_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 6 + [vp]
+    lib.stmpc_pop_td3_update_device.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, vp]
+    lib.stmpc_pop_td3_stats_device.argtypes = [vp, vp, vp]
     lib.stmpc_actor_view_ddpg.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_destroy.argtypes = [vp]
@@ -1077,6 +1090,45 @@ class Context:
 
     def ddpg_pop_stats(self, handle, d_out, stream=0):
         self._chk(self._lib.stmpc_ddpg_pop_stats_device(handle, d_out, stream))
+
+    # -- TD3 population (stmpc_pop_td3_*): P TD3 learners, one launch per kernel ------------------------
+    def td3_pop_create(self, cfgs):
+        """``cfgs``: a sequence of ``TD3Cfg``; the library checks the member count and that the launch shapes are common."""
+        arr = (TD3Cfg * len(cfgs))(*cfgs)
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_pop_td3_create(self._h, arr, len(cfgs), C.byref(h)))
+        return h
+
+    def td3_pop_destroy(self, handle):
+        self._lib.stmpc_pop_td3_destroy(handle)
+
+    def td3_pop_size(self, handle):
+        return int(self._lib.stmpc_pop_td3_size(handle))
+
+    def td3_pop_member(self, handle, m):
+        """The m-th member as a borrowed ``stmpc_td3`` handle for the ``td3_*`` methods above (never ``td3_destroy`` it)."""
+        h = self._lib.stmpc_pop_td3_member(handle, int(m))
+        if not h:
+            self._chk(STMPC_EINVAL)
+        return C.c_void_p(h)
+
+    def td3_pop_act(self, handle, n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug=0, stream=0):
+        self._chk(self._lib.stmpc_pop_td3_act_device(handle, int(n_per_member), d_obs, int(obs_stride), d_ticks, int(bool(noise)), d_action, d_debug, stream))
+
+    def td3_pop_push(self, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated,
+                     stream=0):
+        self._chk(self._lib.stmpc_pop_td3_push_device(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_ticks, d_next_ticks, d_action,
+                                                      d_reward, d_terminated, d_truncated, stream))
+
+    def td3_pop_update(self, handle, n_updates, lr_q, lr_pi, stream=0):
+        """``lr_q`` / ``lr_pi``: one learning rate per member (the library checks the lengths)."""
+        lq, lp = np.ascontiguousarray(lr_q, dtype=np.float64).reshape(-1), np.ascontiguousarray(lr_pi, dtype=np.float64).reshape(-1)
+        if lq.size != lp.size:
+            raise ValueError("lr_q has %d entries, lr_pi %d" % (lq.size, lp.size))
+        self._chk(self._lib.stmpc_pop_td3_update_device(handle, int(n_updates), _dptr(lq), _dptr(lp), int(lq.size), stream))
+
+    def td3_pop_stats(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_pop_td3_stats_device(handle, d_out, stream))
 
     # -- episode flight recorder (stmpc_rec_*): the handle follows this context's world ------------------------
     def rec_create(self, N, Kmax, depth, tick_length, edges):

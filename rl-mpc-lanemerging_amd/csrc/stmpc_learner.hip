@@ -1,9 +1,10 @@
-// stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), the TD3 learner on top of it (stmpc_td3_*), actors that view a learner's networks
+// stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), the TD3 learner on top of it and its population (stmpc_td3_*, stmpc_pop_td3_*), actors that view a learner's networks
 // (stmpc_actor_view_ddpg) and the population of actors (stmpc_actor_pop_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
 #include "stmpc_ddpg_pop_kernels.hpp"
 #include "stmpc_td3_kernels.hpp"
+#include "stmpc_td3_pop_kernels.hpp"
 #include "stmpc_actor_pop_kernels.hpp"
 
 // ---- DDPG learner (stmpc_ddpg_*): replay ring, fused update, acting; kernels in stmpc_ddpg_kernels.hpp -------------------------------------------
@@ -282,11 +283,37 @@ struct stmpc_ddpg_pop {
 static_assert(DG_POP_MAX == STMPC_DDPG_POP_MAX, "DdpgLr holds one learning rate per possible member");
 
 namespace {
-int ddpg_pop_lrs(const stmpc_ddpg_pop *p, const double *lr, DdpgLr &out) {
-    for (int m = 0; m < p->P(); ++m) {
+int ddpg_pop_lrs(int P, const double *lr, DdpgLr &out) {
+    for (int m = 0; m < P; ++m) {
         if (!(lr[m] >= 0)) return fail(STMPC_EINVAL, "a member's learning rate is negative");
         out.lr[m] = (float)lr[m];
     }
+    return STMPC_OK;
+}
+// acting and pushing of P members whose DdpgDev are table[0 ... P): the DDPG population's own, and a TD3 population's on its members' bases
+int ddpg_pop_act(int device, const DdpgDev *table, int P, const stmpc_ddpg *l0, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise,
+                 double *d_action, uint32_t *d_debug, void *stream) {
+    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
+        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
+    if (!d_obs || !d_ticks || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(device));
+    hipLaunchKernelGGL(k_ddpg_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, P), dim3(AT_THREADS), l0->lds, (hipStream_t)stream, table, n_per_member, d_obs,
+                       obs_stride, d_ticks, noise != 0, d_action, d_debug);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+int ddpg_pop_push(int device, const DdpgDev *table, int P, const stmpc_ddpg *l0, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs,
+                  int obs_stride, const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated,
+                  const uint8_t *d_truncated, void *stream) {
+    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
+        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
+    if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(device));
+    const long long items = (long long)n_per_member * DG_ROW;       // per member: stmpc_ddpg_push_device's block count
+    const int blocks = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_replay_push_pop, dim3(blocks, P), dim3(256), 0, (hipStream_t)stream, table, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride,
+                       d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated);
+    HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 }  // namespace
@@ -336,32 +363,15 @@ stmpc_ddpg *stmpc_ddpg_pop_member(stmpc_ddpg_pop *p, int m) {
 int stmpc_ddpg_pop_act_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action,
                               uint32_t *d_debug, void *stream) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    const stmpc_ddpg *l0 = p->members[0];
-    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
-        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
-    if (!d_obs || !d_ticks || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(p->device));
-    hipLaunchKernelGGL(k_ddpg_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, p->P()), dim3(AT_THREADS), l0->lds, (hipStream_t)stream, p->dev(), n_per_member, d_obs,
-                       obs_stride, d_ticks, noise != 0, d_action, d_debug);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    return ddpg_pop_act(p->device, p->dev(), p->P(), p->members[0], n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug, stream);
 }
 
 int stmpc_ddpg_pop_push_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
                                const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated,
                                const uint8_t *d_truncated, void *stream) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    const stmpc_ddpg *l0 = p->members[0];
-    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
-        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
-    if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(p->device));
-    const long long items = (long long)n_per_member * DG_ROW;       // per member: stmpc_ddpg_push_device's block count
-    const int blocks = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_replay_push_pop, dim3(blocks, p->P()), dim3(256), 0, (hipStream_t)stream, p->dev(), n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride,
-                       d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    return ddpg_pop_push(p->device, p->dev(), p->P(), p->members[0], n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward,
+                         d_terminated, d_truncated, stream);
 }
 
 int stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *p, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream) {
@@ -369,8 +379,8 @@ int stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *p, int n_updates, const double 
     if (n_lr != p->P()) return fail(STMPC_EINVAL, "the learning-rate arrays have " + std::to_string(n_lr) + " entries, the population " + std::to_string(p->P()) + " members");
     if (n_updates < 0) return fail(STMPC_EINVAL, "n_updates is negative");
     DdpgLr lq{}, lp{};
-    TRY(ddpg_pop_lrs(p, lr_q, lq));
-    TRY(ddpg_pop_lrs(p, lr_pi, lp));
+    TRY(ddpg_pop_lrs(p->P(), lr_q, lq));
+    TRY(ddpg_pop_lrs(p->P(), lr_pi, lp));
     HIPCHK(hipSetDevice(p->device));
     const stmpc_ddpg *l = p->members[0];
     const int P = p->P(), tiles = l->Bp / AT_TM, t1 = l->h2p / 16, t0 = l->h1p / 16, jobs = t1 * t0 + 2 * t0 + t1 + t0 + t1 + 1, ablocks = (l->np + 255) / 256;
@@ -573,6 +583,123 @@ int stmpc_td3_stats_device(stmpc_td3 *t, double *d_out, void *stream) {
 
 double stmpc_td3_noise(uint64_t seed, uint64_t update, uint32_t row, uint32_t *draw1, uint32_t *draw2) {
     return ddpg_gauss_host(dg_hash(seed ^ TD3_STREAM, update, row), draw1, draw2);
+}
+
+}  // extern "C"
+
+// ---- TD3 population (stmpc_pop_td3_*): P learners of the section above, one launch per kernel; kernels in stmpc_td3_pop_kernels.hpp ---------------
+struct stmpc_td3_pop {
+    int device = 0;
+    std::vector<stmpc_td3 *> members;       // owned; made by stmpc_td3_create, so every single-learner entry works on a borrowed member (and on its base)
+    DevBuf table, bases;                    // Td3Dev [P]: the members' structs; DdpgDev [P]: their bases' (v[0]), for k_ddpg_act_pop / k_replay_push_pop
+    int P() const { return (int)members.size(); }
+    const Td3Dev *dev() const { return table.as<Td3Dev>(); }
+    const DdpgDev *base_dev() const { return bases.as<DdpgDev>(); }
+};
+
+static_assert(STMPC_TD3_POP_MAX == DG_POP_MAX && STMPC_TD3_POP_MAX == STMPC_DDPG_POP_MAX, "DdpgLr holds one learning rate per possible member");
+
+namespace {
+int td3_pop_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling[2];
+    TRY(raise_dynamic_lds((const void *)k_td3_critic_fwd_pop, "k_td3_critic_fwd_pop", ceiling[0], device, lds));
+    TRY(raise_dynamic_lds((const void *)k_td3_actor_fwd_pop, "k_td3_actor_fwd_pop", ceiling[1], device, lds));
+    return ddpg_raise_lds(true, device, lds);                       // (k_ddpg_act_pop)
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_pop_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *cfgs, int P, stmpc_td3_pop **out) {
+    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (P < 1 || P > STMPC_TD3_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
+    if (!cfgs) return fail(STMPC_EINVAL, "NULL argument");
+    for (int m = 1; m < P; ++m) {
+        const stmpc_ddpg_cfg &a = cfgs[m].base, &b = cfgs[0].base;
+        if (a.n_obs != b.n_obs || a.h1 != b.h1 || a.h2 != b.h2 || a.batch != b.batch || a.capacity != b.capacity)
+            return fail(STMPC_EINVAL, "the members of a population share n_obs, h1, h2, batch and capacity (member " + std::to_string(m) + " differs from member 0)");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_td3_pop *p = new stmpc_td3_pop();
+    p->device = c->device;
+    int rc = STMPC_OK;
+    std::vector<Td3Dev> host;
+    std::vector<DdpgDev> base;
+    for (int m = 0; m < P && !rc; ++m) {
+        stmpc_td3 *t = nullptr;
+        rc = stmpc_td3_create(c, cfgs + m, &t);
+        if (!rc) { p->members.push_back(t); host.push_back(t->dev); base.push_back(t->dev.v[0]); }
+    }
+    if (!rc) rc = p->table.ensure(host.size() * sizeof(Td3Dev));
+    if (!rc) rc = p->bases.ensure(base.size() * sizeof(DdpgDev));
+    if (!rc && (hipMemcpy(p->table.p, host.data(), host.size() * sizeof(Td3Dev), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(p->bases.p, base.data(), base.size() * sizeof(DdpgDev), hipMemcpyHostToDevice) != hipSuccess))
+        rc = fail(STMPC_EHIP, "hipMemcpy of the member tables failed");
+    if (!rc) rc = td3_pop_raise_lds(p->device, p->members[0]->base->lds);
+    if (rc) { stmpc_pop_td3_destroy(p); return rc; }
+    *out = p;
+    return STMPC_OK;
+}
+
+void stmpc_pop_td3_destroy(stmpc_td3_pop *p) {
+    if (!p) return;
+    for (stmpc_td3 *t : p->members) stmpc_td3_destroy(t);
+    (void)hipSetDevice(p->device);
+    delete p;
+}
+
+int stmpc_pop_td3_size(const stmpc_td3_pop *p) { return p ? p->P() : 0; }
+
+stmpc_td3 *stmpc_pop_td3_member(stmpc_td3_pop *p, int m) {
+    if (!p || m < 0 || m >= p->P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
+    return p->members[m];
+}
+
+int stmpc_pop_td3_act_device(stmpc_td3_pop *p, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action,
+                             uint32_t *d_debug, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return ddpg_pop_act(p->device, p->base_dev(), p->P(), p->members[0]->base, n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug, stream);
+}
+
+int stmpc_pop_td3_push_device(stmpc_td3_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                              const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated,
+                              const uint8_t *d_truncated, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return ddpg_pop_push(p->device, p->base_dev(), p->P(), p->members[0]->base, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action,
+                         d_reward, d_terminated, d_truncated, stream);
+}
+
+int stmpc_pop_td3_update_device(stmpc_td3_pop *p, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream) {
+    if (!p || !lr_q || !lr_pi) return fail(STMPC_EINVAL, "NULL argument");
+    if (n_lr != p->P()) return fail(STMPC_EINVAL, "the learning-rate arrays have " + std::to_string(n_lr) + " entries, the population " + std::to_string(p->P()) + " members");
+    if (n_updates < 0) return fail(STMPC_EINVAL, "n_updates is negative");
+    DdpgLr lq{}, lp{};
+    TRY(ddpg_pop_lrs(p->P(), lr_q, lq));
+    TRY(ddpg_pop_lrs(p->P(), lr_pi, lp));
+    HIPCHK(hipSetDevice(p->device));
+    const stmpc_ddpg *l = p->members[0]->base;
+    const Td3Grid g = td3_grid(l);
+    const int P = p->P();
+    hipStream_t st = (hipStream_t)stream;
+    for (int u = 0; u < n_updates; ++u) {                            // stmpc_td3_update_device's six launches, each over the members in gridDim.z
+        hipLaunchKernelGGL(k_td3_critic_fwd_pop, dim3(g.tiles, 2, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
+        hipLaunchKernelGGL(k_td3_wgrad_pop, dim3(g.jobs, 2, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 1, l->Bp, 1);
+        hipLaunchKernelGGL(k_td3_adam_critics_pop, dim3(g.ablocks, 2, P), dim3(256), 0, st, p->dev(), lq, 1);
+        hipLaunchKernelGGL(k_td3_actor_fwd_pop, dim3(g.tiles, 1, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
+        hipLaunchKernelGGL(k_td3_wgrad_pop, dim3(g.jobs, 1, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 0, l->Bp, 1);
+        hipLaunchKernelGGL(k_td3_adam_finish_pop, dim3(g.ablocks, 3, P), dim3(256), 0, st, p->dev(), lp, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_td3_stats_device(stmpc_td3_pop *p, double *d_out, void *stream) {
+    if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(p->device));
+    hipLaunchKernelGGL(k_td3_stats_pop, dim3(1, 1, p->P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->members[0]->base->cfg.batch, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
 }
 
 }  // extern "C"

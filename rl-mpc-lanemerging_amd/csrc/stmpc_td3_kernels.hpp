@@ -12,6 +12,8 @@
 //   k_td3_actor_fwd     (tiles)      } the actor against critic 1 as just stepped: only if (updates + 1) % policy_delay == 0
 //   k_td3_wgrad         (jobs, 1)    }
 //   k_td3_adam_finish   (blocks, 3)  if due: the actor's Adam step and the Polyak update of the actor's and both critics' targets; always: updates += 1
+// Each kernel's text is a __device__ body taking the learner's struct by reference; the __global__ entry passes its by-value argument, and the
+// population's entries (stmpc_td3_pop_kernels.hpp) a row of a device table.  The bodies read blockIdx.x / .y and gridDim.x / .y only.
 // No float atomics, no sums across workgroups: a run is bit-reproducible.  With target noise 0, policy_delay 1 and critic 2 equal to critic 1 every
 // bit equals the DDPG update's (the critic's Polyak reads nothing the actor step writes, so doing it after that step changes nothing).
 #pragma once
@@ -41,8 +43,7 @@ __device__ __forceinline__ float td3_smoothing(const Td3Dev &T3, unsigned long l
 }
 
 // dbg (may be null) float32 [B][5]: eps, a', Qt1, Qt2, y of the minibatch; with it the pass ends there and writes nothing else
-__global__ void __launch_bounds__(AT_THREADS) k_td3_critic_fwd(Td3Dev T3, int B, int gate, float *__restrict__ dbg) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+__device__ __forceinline__ void td3_critic_fwd_body(const Td3Dev &T3, int B, int gate, float *__restrict__ dbg, unsigned char *dg_smem) {
     const DdpgDev &L = T3.v[blockIdx.y];
     if (!ddpg_gate(L, gate)) return;
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, L.h2p);
@@ -75,22 +76,32 @@ __global__ void __launch_bounds__(AT_THREADS) k_td3_critic_fwd(Td3Dev T3, int B,
     __syncthreads();
     ddpg_critic_online(L, T, r0, B, y);
 }
+__global__ void __launch_bounds__(AT_THREADS) k_td3_critic_fwd(Td3Dev T3, int B, int gate, float *__restrict__ dbg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    td3_critic_fwd_body(T3, B, gate, dbg, dg_smem);
+}
 
 // which = 1: both critics (gridDim.y = 2); which = 0: the actor, from view 0's workspace (gridDim.y = 1), if the delayed half is due
-__global__ void __launch_bounds__(64 * DG_WG_WAVES) k_td3_wgrad(Td3Dev T3, int which, int Bp, int gate) {
-    __shared__ double part_s[DG_WG_WAVES][256];
+__device__ __forceinline__ void td3_wgrad_body(const Td3Dev &T3, int which, int Bp, int gate, double (*part_s)[256]) {
     if (!which && !td3_due(T3, gate)) return;
     ddpg_wgrad_body(T3.v[blockIdx.y], which, Bp, gate, part_s);
 }
+__global__ void __launch_bounds__(64 * DG_WG_WAVES) k_td3_wgrad(Td3Dev T3, int which, int Bp, int gate) {
+    __shared__ double part_s[DG_WG_WAVES][256];
+    td3_wgrad_body(T3, which, Bp, gate, part_s);
+}
 
-__global__ void __launch_bounds__(AT_THREADS) k_td3_actor_fwd(Td3Dev T3, int B, int gate) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+__device__ __forceinline__ void td3_actor_fwd_body(const Td3Dev &T3, int B, int gate, unsigned char *dg_smem) {
     if (!td3_due(T3, gate)) return;
     ddpg_actor_fwd_body(T3.v[0], B, gate, dg_smem);
 }
+__global__ void __launch_bounds__(AT_THREADS) k_td3_actor_fwd(Td3Dev T3, int B, int gate) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    td3_actor_fwd_body(T3, B, gate, dg_smem);
+}
 
 // Adam step of critic blockIdx.y with its own moments, beta powers and ticket; the target stays (t0 / t1 are re-packed from the unchanged target)
-__global__ void __launch_bounds__(256) k_td3_adam_critics(Td3Dev T3, float lr, int gate) {
+__device__ __forceinline__ void td3_adam_critics_body(const Td3Dev &T3, float lr, int gate) {
     const DdpgDev &L = T3.v[blockIdx.y];
     if (!ddpg_gate(L, gate)) return;
     const DdpgNet &net = L.q;
@@ -105,10 +116,11 @@ __global__ void __launch_bounds__(256) k_td3_adam_critics(Td3Dev T3, float lr, i
     __syncthreads();
     if (threadIdx.x == 0 && dg_last_block(L.tick + DG_T_ADAM + 1, gridDim.x)) { net.bpow[0] = pw1; net.bpow[1] = pw2; }
 }
+__global__ void __launch_bounds__(256) k_td3_adam_critics(Td3Dev T3, float lr, int gate) { td3_adam_critics_body(T3, lr, gate); }
 
 // blockIdx.y = 0: the actor (Adam step, Polyak), 1 and 2: critic 1 and 2 (Polyak), all with the re-pack and only if the delayed half is due.
 // The last workgroup of the whole grid advances the actor's beta powers (if it stepped) and ends the update.
-__global__ void __launch_bounds__(256) k_td3_adam_finish(Td3Dev T3, float lr, int gate) {
+__device__ __forceinline__ void td3_adam_finish_body(const Td3Dev &T3, float lr, int gate) {
     const DdpgDev &L = T3.v[blockIdx.y == 2];
     if (!ddpg_gate(L, gate)) return;
     const DdpgNet &net = blockIdx.y ? L.q : L.pi;
@@ -131,9 +143,10 @@ __global__ void __launch_bounds__(256) k_td3_adam_finish(Td3Dev T3, float lr, in
         L.cnt[DG_UPDATES] = upd + 1;
     }
 }
+__global__ void __launch_bounds__(256) k_td3_adam_finish(Td3Dev T3, float lr, int gate) { td3_adam_finish_body(T3, lr, gate); }
 
 // loss 1, loss 2, mean Q1, mean Q2 of the last minibatch, fill, updates -> out [6] fp64 (ddpg_stats_body's fixed summation order)
-__global__ void __launch_bounds__(64) k_td3_stats(Td3Dev T3, int B, double *out) {
+__device__ __forceinline__ void td3_stats_body(const Td3Dev &T3, int B, double *out) {
     const int lane = threadIdx.x;
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int r = lane; r < B; r += 64)
@@ -145,5 +158,6 @@ __global__ void __launch_bounds__(64) k_td3_stats(Td3Dev T3, int B, double *out)
         out[4] = (double)T3.v[0].cnt[DG_FILL]; out[5] = (double)T3.v[0].cnt[DG_UPDATES];
     }
 }
+__global__ void __launch_bounds__(64) k_td3_stats(Td3Dev T3, int B, double *out) { td3_stats_body(T3, B, out); }
 
 }  // namespace stmpc

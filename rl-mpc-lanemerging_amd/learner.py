@@ -23,7 +23,8 @@ float32 in the kernel's operation order), ``sample_indices_host``, ``noise_host`
 
 ``TD3Learner`` (``TD3Config``, ``csrc/stmpc_td3_kernels.hpp``) is the same learner with TD3's three changes -- two critics and the minimum of their
 targets, clipped noise on the target action, the actor and all targets stepped every ``policy_delay``-th update -- in six launches per update that
-carry both critics in ``blockIdx.y``; twins: ``update_host_td3``, ``smoothing_noise_host``.
+carry both critics in ``blockIdx.y``; twins: ``update_host_td3``, ``smoothing_noise_host``.  ``TD3Population`` is to it what ``DDPGPopulation`` is
+to ``DDPGLearner`` (``csrc/stmpc_td3_pop_kernels.hpp``: the member axis in ``blockIdx.z``).
 """
 import math
 
@@ -558,6 +559,17 @@ class DDPGPopulation:
     slice of the lone env made under reward m.  Nothing else changes: the population reads the env's reward tensor row by row.
     ``evaluate_members`` / ``episodes.summary_by_member`` then compare the policies the rewards produced on one common report."""
 
+    _api, _nstat = "ddpg_pop", 4                                    # the binding's entries (ctx.<_api>_create, ...) and the width of a stats row
+
+    def _call(self, name):
+        return getattr(self.ctx, "%s_%s" % (self._api, name))
+
+    def _create_handle(self):
+        return self._call("create")([c.to_c(s) for c, s in zip(self.cfgs, self.seeds)])
+
+    def _make_member(self, m, env, init):
+        return _PopulationMember(self, m, env, self.cfgs[m], self.seeds[m], init)
+
     def __init__(self, env, cfgs, seeds=None, init=None, ctx=None):
         if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], DDPGConfig):
             cfgs = [cfgs[0]] * int(cfgs[1])
@@ -586,16 +598,16 @@ class DDPGPopulation:
         self.env_n, self.n_per_member = env.n, (env.n // P if P >= 1 else 0)
         self.ctx = ctx if ctx is not None else env.ctx
         self.device = torch.device("cuda", torch.cuda.current_device())
-        self.handle = self.ctx.ddpg_pop_create([c.to_c(s) for c, s in zip(self.cfgs, self.seeds)])
-        self._members = [_PopulationMember(self, m, env, self.cfgs[m], self.seeds[m], inits[m]) for m in range(P)]
+        self.handle = self._create_handle()
+        self._members = [self._make_member(m, env, inits[m]) for m in range(P)]
         self._lr_q, self._lr_pi = np.array([c.lr_q for c in self.cfgs]), np.array([c.lr_pi for c in self.cfgs])
-        self._stats = torch.zeros(P, 4, dtype=torch.float64, device=self.device)
+        self._stats = torch.zeros(P, self._nstat, dtype=torch.float64, device=self.device)
         self._actions = torch.empty(env.n, dtype=torch.float64, device=self.device)
 
     def __del__(self):
         if getattr(self, "handle", None) is not None:
             try:
-                self.ctx.ddpg_pop_destroy(self.handle)
+                self._call("destroy")(self.handle)
             except Exception:
                 pass
             self.handle = None
@@ -617,8 +629,8 @@ class DDPGPopulation:
         """``DDPGLearner.act`` for all members: row e is acted on by member e // n_per_member.  The returned tensor is reused by the next call."""
         self._rows(obs)
         assert obs.dtype == self.torch.float32 and ticks.dtype == self.torch.int32 and obs.stride(1) == 1
-        self.ctx.ddpg_pop_act(self.handle, self.n_per_member, obs.data_ptr(), obs.stride(0), ticks.data_ptr(), noise, self._actions.data_ptr(),
-                              debug.data_ptr() if debug is not None else 0, self._stream())
+        self._call("act")(self.handle, self.n_per_member, obs.data_ptr(), obs.stride(0), ticks.data_ptr(), noise, self._actions.data_ptr(),
+                          debug.data_ptr() if debug is not None else 0, self._stream())
         return self._actions
 
     def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
@@ -628,9 +640,9 @@ class DDPGPopulation:
         assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == reward.dtype == torch.float64 and ticks.dtype == torch.int32
         assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
         assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
-        self.ctx.ddpg_pop_push(self.handle, self.n_per_member, obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0,
-                               obs.stride(0), ticks.data_ptr(), next_ticks.data_ptr() if next_ticks is not None else 0, action.data_ptr(), reward.data_ptr(),
-                               terminated.data_ptr(), truncated.data_ptr(), self._stream())
+        self._call("push")(self.handle, self.n_per_member, obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0,
+                           obs.stride(0), ticks.data_ptr(), next_ticks.data_ptr() if next_ticks is not None else 0, action.data_ptr(), reward.data_ptr(),
+                           terminated.data_ptr(), truncated.data_ptr(), self._stream())
 
     def _lr(self, lr, default):
         if lr is None:
@@ -641,17 +653,82 @@ class DDPGPopulation:
     def update(self, n=1, lr_q=None, lr_pi=None):
         """``n`` updates of every member, six launches each; a member whose replay_start gate is still shut skips its own.  ``lr_q`` / ``lr_pi``:
         a scalar or one value per member (default: each member's cfg's)."""
-        self.ctx.ddpg_pop_update(self.handle, n, self._lr(lr_q, self._lr_q), self._lr(lr_pi, self._lr_pi), self._stream())
+        self._call("update")(self.handle, n, self._lr(lr_q, self._lr_q), self._lr(lr_pi, self._lr_pi), self._stream())
 
     def stats_device(self):
         """fp64 [P][4] device tensor: per member, critic loss and mean Q of the last minibatch, fill, updates done (asynchronous)."""
-        self.ctx.ddpg_pop_stats(self.handle, self._stats.data_ptr(), self._stream())
+        self._call("stats")(self.handle, self._stats.data_ptr(), self._stream())
         return self._stats
 
     def stats(self):
         """The same as a dict of arrays of length P; synchronises."""
         s = self.stats_device().cpu().numpy()
         return {"critic_loss": s[:, 0].copy(), "mean_q": s[:, 1].copy(), "fill": s[:, 2].astype(np.int64), "updates": s[:, 3].astype(np.int64)}
+
+
+class _TD3PopulationMember(TD3Learner):
+    """One member of a ``TD3Population`` as a ``TD3Learner``: the TD3 handle is borrowed from the population (``stmpc_pop_td3_member``), which outlives
+    it, and so is its base; everything else -- the seeded initialisation, critic 2's draw included -- is the lone learner's code."""
+
+    def __init__(self, population, m, env, cfg, seed, init):
+        self._population, self._borrowed = population, population.ctx.td3_pop_member(population.handle, m)
+        super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
+
+    def _make_handle(self):
+        self.td3 = self._borrowed
+        return self.ctx.td3_base(self.td3)
+
+    def __del__(self):
+        self.handle = self.td3 = None                               # the population destroys its members
+
+
+def _is_net_triple(x):
+    return isinstance(x, (tuple, list)) and len(x) == 3 and isinstance(x[0], dict) and "w0" in x[0]
+
+
+class TD3Population(DDPGPopulation):
+    """P independent TD3 learners on one ``MergeVecEnv``, advanced together: ``DDPGPopulation`` for ``TD3Learner`` (``csrc/stmpc_td3_pop_kernels.hpp``,
+    ``stmpc_pop_td3_*``): six launches per update whatever P is.  The members share n_obs, h1, h2, batch and capacity and may differ in everything
+    else -- ``target_noise``, ``noise_clip``, ``policy_delay``, ``replay_start``, gamma, tau, seed, learning rates: whether a member is gated, or
+    its delayed half due, is decided on the device from its own counters.
+
+    ``cfgs``: a list of ``TD3Config`` or ``(TD3Config, P)`` (a plain ``DDPGConfig`` is refused).  ``init``: as ``TD3Learner``'s -- a dict, or an
+    (actor, critic, critic 2) triple of nets -- for every member, or a list of P of those.  Member m starts exactly as
+    ``TD3Learner(seed=seeds[m], init=...)`` does, critic 2's fresh draw included, and stays bit-identical to that learner driven on its slice alone.
+    ``act`` / ``push`` / ``update`` and what ``DDPGPopulation`` says about traffic and reward groups hold unchanged; ``stats_device`` is fp64 [P][6]
+    and ``stats`` has the keys of ``TD3Learner.stats_td3``; ``member(m)`` is a ``TD3Learner`` view (``grads``, ``targets``, ``stats_td3``,
+    ``state_dict`` / ``load_state_dict`` with all twelve slots and six beta powers, ``export_actor``).  ``train_ddpg``, ``evaluate_members`` and
+    ``actor.ActorPopulation`` take it as they take a ``DDPGPopulation``."""
+
+    _api, _nstat = "td3_pop", 6
+
+    def __init__(self, env, cfgs, seeds=None, init=None, ctx=None):
+        if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], DDPGConfig):
+            cfgs = [cfgs[0]] * int(cfgs[1])
+        cfgs = list(cfgs)
+        for m, c in enumerate(cfgs):
+            if not isinstance(c, TD3Config):
+                raise ValueError("member %d's cfg is a %s, not a TD3Config: a TD3Population takes TD3Configs (a plain DDPGConfig has no target_noise, "
+                                 "noise_clip or policy_delay)" % (m, type(c).__name__))
+        if _is_net_triple(init):                                    # one triple for every member, not a list of three members
+            init = [init] * len(cfgs)
+        super().__init__(env, cfgs, seeds=seeds, init=init, ctx=ctx)
+
+    def _create_handle(self):
+        return self._call("create")([c.to_c_td3(s) for c, s in zip(self.cfgs, self.seeds)])
+
+    def _make_member(self, m, env, init):
+        return _TD3PopulationMember(self, m, env, self.cfgs[m], self.seeds[m], init)
+
+    def stats_device(self):
+        """fp64 [P][6] device tensor: per member, both critics' losses and mean Qs of the last minibatch, fill, updates done (asynchronous)."""
+        return super().stats_device()
+
+    def stats(self):
+        """The same as a dict of arrays of length P with the keys of ``TD3Learner.stats_td3``; synchronises."""
+        s = self.stats_device().cpu().numpy()
+        return {"critic_loss": s[:, 0].copy(), "critic2_loss": s[:, 1].copy(), "mean_q": s[:, 2].copy(), "mean_q2": s[:, 3].copy(),
+                "fill": s[:, 4].astype(np.int64), "updates": s[:, 5].astype(np.int64)}
 
 
 def write_actor(path, net, tanh_scale, tanh_mean):

@@ -1,0 +1,81 @@
+"""A population of TD3 learners (learner.TD3Population, csrc/stmpc_td3_pop_kernels.hpp, stmpc_pop_td3_* of include/stmpc.h): CPU part.
+
+Header, library and binding agree on the eight new entries and on STMPC_TD3_POP_MAX; ``TD3Population`` refuses, with a ValueError and before it
+touches the device, an env it cannot split, traffic or reward groups that are not one per member, a wrong ``n_obs`` and a plain ``DDPGConfig``.
+The GPU part is test_td3_pop.py.
+"""
+import os
+import re
+
+import pytest
+
+from conftest import REPO
+from test_net_shapes_cpu import _capi
+
+ENTRIES = {"stmpc_pop_td3_create", "stmpc_pop_td3_destroy", "stmpc_pop_td3_size", "stmpc_pop_td3_member", "stmpc_pop_td3_act_device",
+           "stmpc_pop_td3_push_device", "stmpc_pop_td3_update_device", "stmpc_pop_td3_stats_device"}
+
+
+def test_header_library_and_binding_agree_on_the_td3_population():
+    import ctypes
+    capi = _capi()
+    lib = capi.load()
+    header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
+    declared = {name: args for name, args in re.findall(r"\b(stmpc_pop_td3_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}
+    assert set(declared) == ENTRIES == {n for n in capi.EXPORTS if n.startswith("stmpc_pop_td3_")}
+    for name, args in declared.items():
+        fn = getattr(lib, name)                                   # (AttributeError: the library does not export it)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(args.split(",")), name
+    # act / push / update / stats have the DDPG population's signatures
+    ddpg = {name: args for name, args in re.findall(r"\b(stmpc_ddpg_pop_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}
+    for tail in ("act_device", "push_device", "update_device", "stats_device"):
+        assert declared["stmpc_pop_td3_" + tail].replace("stmpc_td3_pop", "stmpc_ddpg_pop") == ddpg["stmpc_ddpg_pop_" + tail], tail
+        assert getattr(lib, "stmpc_pop_td3_" + tail).argtypes == getattr(lib, "stmpc_ddpg_pop_" + tail).argtypes, tail
+    assert lib.stmpc_pop_td3_member.restype is ctypes.c_void_p and lib.stmpc_pop_td3_destroy.restype is None
+    assert "#define STMPC_TD3_POP_MAX %d" % capi.TD3_POP_MAX in header and "#define STMPC_DDPG_POP_MAX %d" % capi.DDPG_POP_MAX in header
+    assert capi.TD3_POP_MAX == capi.DDPG_POP_MAX == 64
+    assert capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8 and "#define STMPC_ABI_VERSION 8" in header
+    for name in ("create", "destroy", "size", "member", "act", "push", "update", "stats"):
+        assert callable(getattr(capi.Context, "td3_pop_" + name)), name
+
+
+class _Env:
+    """An env whose context must not be asked for."""
+    n, obs_dim, continuous = 72, 20, True
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def ctx(self):
+        raise AssertionError("the device was touched")
+
+
+def test_td3_population_refuses_before_touching_the_device():
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    assert issubclass(learner.TD3Population, learner.DDPGPopulation)
+    cfg = learner.TD3Config(n_obs=20, batch=16, capacity=200, replay_start=0)
+    # an env it cannot split
+    with pytest.raises(ValueError, match="70 is not a multiple of the population's 3 members"):
+        learner.TD3Population(_Env(n=70), (cfg, 3))
+    with pytest.raises(ValueError, match="70 is not a multiple"):
+        learner.TD3Population(_Env(n=70), [cfg] * 4, seeds=[1, 2, 3, 4])
+    with pytest.raises(ValueError, match="continuous"):
+        learner.TD3Population(_Env(continuous=False), (cfg, 2))
+    # G != P, R != P
+    with pytest.raises(ValueError, match="the env has 2 traffic groups, the population 3 members"):
+        learner.TD3Population(_Env(sim_cfgs=[None, None], G=2), (cfg, 3))
+    with pytest.raises(ValueError, match="the env has 4 reward groups, the population 3 members"):
+        learner.TD3Population(_Env(R=4), (cfg, 3))
+    # a wrong n_obs
+    with pytest.raises(ValueError, match="cfg.n_obs is 19, the observation has 20 entries"):
+        learner.TD3Population(_Env(), [cfg, learner.TD3Config(n_obs=19, batch=16, capacity=200), cfg])
+    # a DDPGConfig among the cfgs, or as the (cfg, P) pair
+    plain = learner.DDPGConfig(n_obs=20, batch=16, capacity=200, replay_start=0)
+    with pytest.raises(ValueError, match="member 1's cfg is a DDPGConfig, not a TD3Config"):
+        learner.TD3Population(_Env(), [cfg, plain, cfg])
+    with pytest.raises(ValueError, match="member 0's cfg is a DDPGConfig, not a TD3Config"):
+        learner.TD3Population(_Env(), (plain, 3))
+    with pytest.raises(ValueError, match="seeds and init"):
+        learner.TD3Population(_Env(), (cfg, 3), seeds=[1, 2])
