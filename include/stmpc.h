@@ -734,6 +734,44 @@ int  stmpc_pop_td3_update_device(stmpc_td3_pop *pop, int n_updates, const double
 int  stmpc_pop_td3_stats_device(stmpc_td3_pop *pop, double *d_out, void *stream);
 
 /*
+ * Prioritised replay for a lone DDPG or TD3 learner: the reference's hand-written trainer samples its minibatches from a sum tree (dqn.py:267-349,
+ * class SumTree dqn.py:727-794; config.py: USE_PRIORITIZED_ER = True, PER_ALPHA 0.5, PER_MIN_PRIORITY 1e-6, PER_MAX_PRIORITY 4.0), restated.
+ * (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.  A learner on which stmpc_per_enable was never
+ * called computes what it computed before, bit for bit.)
+ *   The tree: L = capacity rounded up to a power of two; 2L - 1 fp64 nodes, root 0, children of i at 2i + 1 and 2i + 2; ring row p is leaf p + L - 1;
+ *   unfilled leaves are 0.  An internal node is always recomputed as left + right, so the tree does not depend on the order of the writes.
+ *   push            the rows a push writes get leaf weight max_priority ^ alpha (in the push's own launch)
+ *   sample          row r of update u: roll = uniform01 of a hash of (seed, u, r) times the root, 53 bits; descent: roll <= left goes left, else roll -=
+ *                   left and right.  A leaf at or past fill, or of weight 0, is redrawn up to three times; then the row falls back to
+ *                   stmpc_ddpg_sample_index.  stmpc_per_sample_index is this procedure on a HOST tree (the kernel calls the same function)
+ *   weights         w_r = (fill * p_r / root) ^ -beta over the largest w of the minibatch, fp64, stored float32; the critic's loss is mean(w (Q - y)^2).
+ *                   beta = 0: every w is exactly 1 (the reference applies no correction)
+ *   priorities      after the critic pass: leaf[idx_r] = min(|td_r| + min_priority, max_priority) ^ alpha, td_r the float32 Q - y (TD3: of the critic with
+ *                   the larger |td|, on every update); of rows with the same index the highest row wins (the reference's loop order).
+ *                   alpha = 0.5 is a square root, alpha = 1 the identity, anything else pow
+ * One update is two launches more than without (the sampling step, the priority update); both are gated by replay_start like the update, and every
+ * counter stays on the device.  gather_device, grads_device and stmpc_td3_targets_device run the sampling step first (ungated), so they see the rows
+ * the next update will read.
+ *   stmpc_per_enable    on a learner whose ring is empty (a TD3 learner: on its stmpc_td3_base).  STMPC_EINVAL for min_priority <= 0, max_priority <
+ *                   min_priority, alpha < 0, beta < 0, a non-empty ring, a member of a population, a second call.  Afterwards stmpc_ddpg_set_state
+ *                   refuses counters that would change the ring's cursor or fill
+ *   stmpc_per_tree_read     debug, HOST: `count` nodes from node `first`; synchronises
+ *   stmpc_per_last_device   DEVICE int64 [batch], float32 [batch], float32 [batch]: the ring rows and weights of the last sampling step and the td of
+ *                   the last critic pass
+ *   stmpc_per_sample_index  host only, no learner: `leaves` = L, tree = 2L - 1 nodes; -1 for leaves not a power of two or fill outside 1 ... leaves
+ */
+typedef struct stmpc_per_cfg {
+    double alpha;                    /* exponent of the priorities (0.5) */
+    double beta;                     /* exponent of the importance weights (0: none) */
+    double min_priority;             /* added to |td| (1e-6); > 0 */
+    double max_priority;             /* cap of |td| + min_priority, and what new rows enter with (4.0) */
+} stmpc_per_cfg;
+int  stmpc_per_enable(stmpc_ddpg *learner, const stmpc_per_cfg *cfg);
+int  stmpc_per_tree_read(stmpc_ddpg *learner, int64_t first, int64_t count, double *nodes);
+int  stmpc_per_last_device(stmpc_ddpg *learner, int64_t *d_idx, float *d_td, float *d_weight, void *stream);
+int64_t stmpc_per_sample_index(const double *tree, int64_t leaves, int64_t fill, uint64_t seed, uint64_t update, uint32_t row);
+
+/*
  * Actors straight from learners, and a population of actors evaluated in one launch.  The reference's workflow ends a training with an evaluation
  * of the model it trained (ddpg.train_ddpg_all_with_lr_drop's closing `evaluate`, ddpg.py:96-117) and publishes a matrix of EVALUATE_COMBINED_DDPG runs, one per
  * MODEL_NAME (DDPGAgent.load + get_control, ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json, experiment_data/saved_data.csv).  (Additive: new

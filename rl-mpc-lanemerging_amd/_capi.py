@@ -246,6 +246,11 @@ class TD3Cfg(C.Structure):
     _fields_ = [("base", DDPGCfg), ("target_noise_std", C.c_double), ("noise_clip", C.c_double), ("policy_delay", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class PERCfg(C.Structure):
+    """``stmpc_per_cfg`` (include/stmpc.h): the constants of prioritised replay (defaults: the reference's config.py)."""
+    _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("min_priority", C.c_double), ("max_priority", C.c_double)]
+
+
 class ProfileTotals(C.Structure):
     _fields_ = [("launches", C.c_int64), ("episodes", C.c_int64), ("solve_ms", C.c_double), ("dp_kernel_ms", C.c_double)]
 
@@ -275,6 +280,7 @@ EXPORTS = (
     "stmpc_td3_update_device", "stmpc_td3_grads_device", "stmpc_td3_targets_device", "stmpc_td3_stats_device", "stmpc_td3_noise",
     "stmpc_pop_td3_create", "stmpc_pop_td3_destroy", "stmpc_pop_td3_size", "stmpc_pop_td3_member", "stmpc_pop_td3_act_device",
     "stmpc_pop_td3_push_device", "stmpc_pop_td3_update_device", "stmpc_pop_td3_stats_device",
+    "stmpc_per_enable", "stmpc_per_tree_read", "stmpc_per_last_device", "stmpc_per_sample_index",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
@@ -467,6 +473,11 @@ def load():
     lib.stmpc_pop_td3_push_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 6 + [vp]
     lib.stmpc_pop_td3_update_device.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, vp]
     lib.stmpc_pop_td3_stats_device.argtypes = [vp, vp, vp]
+    lib.stmpc_per_enable.argtypes = [vp, C.POINTER(PERCfg)]
+    lib.stmpc_per_tree_read.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
+    lib.stmpc_per_last_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.stmpc_per_sample_index.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint32]
+    lib.stmpc_per_sample_index.restype = C.c_int64
     lib.stmpc_actor_view_ddpg.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_destroy.argtypes = [vp]
@@ -565,6 +576,14 @@ def ddpg_noise(seed, call, row):
     u1, u2 = C.c_uint32(0), C.c_uint32(0)
     g = load().stmpc_ddpg_noise(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(call)), C.c_uint32(int(row)), C.byref(u1), C.byref(u2))
     return float(g), int(u1.value), int(u2.value)
+
+
+def per_sample_index(tree, leaves, fill, seed, update, row):
+    """``stmpc_per_sample_index``: the ring row minibatch row ``row`` of update ``update`` reads from the sum tree ``tree`` (fp64 [2 * leaves - 1]; host only)."""
+    tree = np.ascontiguousarray(tree, dtype=np.float64)
+    assert tree.size == 2 * int(leaves) - 1
+    return int(load().stmpc_per_sample_index(tree.ctypes.data_as(C.POINTER(C.c_double)), int(leaves), int(fill), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                             C.c_uint64(int(update)), C.c_uint32(int(row))))
 
 
 def td3_noise(seed, update, row):
@@ -1003,6 +1022,18 @@ class Context:
 
     def ddpg_gather(self, handle, d_rows, stream=0):
         self._chk(self._lib.stmpc_ddpg_gather_device(handle, d_rows, stream))
+
+    # -- prioritised replay (stmpc_per_*) on a lone learner's handle (a TD3 learner: its base) ------------------------
+    def per_enable(self, handle, cfg):
+        self._chk(self._lib.stmpc_per_enable(handle, C.byref(cfg)))
+
+    def per_tree_read(self, handle, first, count):
+        nodes = np.empty(int(count), dtype=np.float64)
+        self._chk(self._lib.stmpc_per_tree_read(handle, int(first), int(count), nodes.ctypes.data_as(C.POINTER(C.c_double))))
+        return nodes
+
+    def per_last(self, handle, d_idx, d_td, d_weight, stream=0):
+        self._chk(self._lib.stmpc_per_last_device(handle, d_idx, d_td, d_weight, stream))
 
     # -- TD3 learner (stmpc_td3_*): a DDPG learner as base plus critic 2 ------------------------
     def td3_create(self, cfg):

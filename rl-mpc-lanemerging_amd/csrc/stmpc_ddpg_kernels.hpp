@@ -50,6 +50,12 @@ struct DdpgDev {
     long long replay_start;
     unsigned long long seed;
     float gamma, tau, beta1, beta2, omb1, omb2, omtau, eps, time_scale, scale, mean, noise_std, a_low, a_high;
+    // prioritised replay (stmpc_per_kernels.hpp); all null / 0 on a learner that samples uniformly, whose kernels then do what they did without these
+    double *tree;                   // [2 * per_L - 1] sum tree
+    long long *idx;                 // [Bp] ring rows of the current update's minibatch
+    float *aw, *atd;                // [Bp] importance weights; [Bp] Q - y of the last critic pass
+    double per_alpha, per_beta, per_min, per_max;
+    long long per_L;                // leaves: capacity rounded up to a power of two
 };
 
 __host__ __device__ inline int dg_o_b0(int h1p) { return h1p * AT_KIN; }
@@ -80,6 +86,12 @@ __device__ __forceinline__ bool dg_last_block(unsigned int *ticket, unsigned int
     return true;
 }
 
+// ring row of minibatch row r: the sampling step's (prioritised replay) or the hash's
+__device__ __forceinline__ long long dg_row_index(const DdpgDev &L, long long upd, long long fill, int r) {
+    return L.idx ? L.idx[r] : (long long)(dg_hash(L.seed, (unsigned long long)upd, (unsigned long long)r) % (unsigned long long)fill);
+}
+__device__ __forceinline__ void per_push_tree(const DdpgDev &L, long long cursor, int N);      // stmpc_per_kernels.hpp
+
 // ---- replay ---------------------------------------------------------------------------------------------------------------------------------
 // (every kernel's body is a __device__ function of the learner's struct: the single-learner entry passes its by-value argument, the population
 // entry of stmpc_ddpg_pop_kernels.hpp the member blockIdx.y selects)
@@ -102,11 +114,17 @@ __device__ __forceinline__ void ddpg_push_body(const DdpgDev &L, int N, const fl
         L.ring[(size_t)((cursor + e) % L.capacity) * DG_ROW + c] = v;
     }
     __syncthreads();
-    if (threadIdx.x == 0 && dg_last_block(L.tick + DG_T_PUSH, gridDim.x)) {
+    __shared__ int last_s;
+    const bool last = threadIdx.x == 0 && dg_last_block(L.tick + DG_T_PUSH, gridDim.x);
+    if (last) {
         L.cnt[DG_CURSOR] = (cursor + N) % L.capacity;
         L.cnt[DG_FILL] = fill + N < L.capacity ? fill + N : L.capacity;
         L.cnt[DG_FRAMES] = frames + N;
     }
+    if (!L.tree) return;
+    if (threadIdx.x == 0) last_s = last;
+    __syncthreads();
+    if (last_s) per_push_tree(L, cursor, N);                       // the new rows' priorities, in this one workgroup
 }
 __global__ void __launch_bounds__(256) k_replay_push(DdpgDev L, int N, const float *__restrict__ obs, const float *__restrict__ next_obs, const float *__restrict__ final_obs,
                                                      int obs_stride, const int *__restrict__ ticks, const int *__restrict__ next_ticks, const double *__restrict__ action,
@@ -120,7 +138,7 @@ __global__ void k_replay_gather(DdpgDev L, int B, float *out) {
     if (fill < 1) return;
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < B * DG_ROW; x += gridDim.x * blockDim.x) {
         const int r = x / DG_ROW, c = x % DG_ROW;
-        const long long idx = (long long)(dg_hash(L.seed, (unsigned long long)upd, (unsigned long long)r) % (unsigned long long)fill);
+        const long long idx = dg_row_index(L, upd, fill, r);
         out[x] = L.ring[(size_t)idx * DG_ROW + c];
     }
 }
@@ -212,7 +230,7 @@ __device__ __forceinline__ bool ddpg_gate(const DdpgDev &L, int gate) {
 __device__ __forceinline__ void ddpg_gather_tile(const DdpgDev &L, const DdpgTile &T, int r0, int B, long long fill, long long upd) {
     const int row = threadIdx.x >> 5, c = threadIdx.x & 31;
     const bool valid = r0 + row < B;
-    const long long idx = valid ? (long long)(dg_hash(L.seed, (unsigned long long)upd, (unsigned long long)(r0 + row)) % (unsigned long long)fill) : 0;
+    const long long idx = valid ? dg_row_index(L, upd, fill, r0 + row) : 0;
     const float *src = L.ring + (size_t)idx * DG_ROW;
     T.X[row * AT_KIN + c] = valid ? src[c] : 0.f;
     T.Xn[row * AT_KIN + c] = valid ? src[32 + c] : 0.f;
@@ -238,8 +256,10 @@ __device__ __forceinline__ void ddpg_critic_online(const DdpgDev &L, const DdpgT
     const float qv = ddpg_out_dot(T.H2, T.h2_ld, L.h2p, L.q.w + ow2, L.q.w[ob2]);
     const bool valid = r0 + row < B;
     const float diff = qv - y;
-    const float dz = valid ? (2.0f * diff) / (float)B : 0.f;           // d mean((Q - y)^2) / dQ
+    // d mean((Q - y)^2) / dQ; prioritised replay: d mean(w (Q - y)^2) / dQ
+    const float dz = valid ? (L.aw ? ((2.0f * L.aw[r0 + row]) * diff) / (float)B : (2.0f * diff) / (float)B) : 0.f;
     if (part == 0) {
+        if (L.atd) L.atd[r0 + row] = valid ? diff : 0.f;
         T.sc[row * 4 + 2] = dz;
         L.adz[r0 + row] = dz;
         L.arow[2 * (r0 + row)] = valid ? diff * diff : 0.f;
@@ -293,7 +313,7 @@ __device__ __forceinline__ void ddpg_actor_fwd_body(const DdpgDev &L, int B, int
     const int row = tid >> 5, part = tid & 31;
     const bool valid = r0 + row < B;
     {   // gather s: X = (s, 0) for the actor, Xn = (s, pi(s)) for the critic
-        const long long idx = valid ? (long long)(dg_hash(L.seed, (unsigned long long)upd, (unsigned long long)(r0 + row)) % (unsigned long long)fill) : 0;
+        const long long idx = valid ? dg_row_index(L, upd, fill, r0 + row) : 0;
         const float v = valid && part < ns ? L.ring[(size_t)idx * DG_ROW + part] : 0.f;
         T.X[row * AT_KIN + part] = v;
         T.Xn[row * AT_KIN + part] = v;
@@ -533,3 +553,5 @@ __global__ void __launch_bounds__(AT_THREADS) k_ddpg_act(DdpgDev L, int N, const
 }
 
 }  // namespace stmpc
+
+#include "stmpc_per_kernels.hpp"

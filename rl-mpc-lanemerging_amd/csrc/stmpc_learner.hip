@@ -1,7 +1,8 @@
-// stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), the TD3 learner on top of it and its population (stmpc_td3_*, stmpc_pop_td3_*), actors that view a learner's networks
+// stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), the TD3 learner on top of it and its population (stmpc_td3_*, stmpc_pop_td3_*), prioritised replay for the two lone learners (stmpc_per_*), actors that view a learner's networks
 // (stmpc_actor_view_ddpg) and the population of actors (stmpc_actor_pop_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
+#include "stmpc_per_kernels.hpp"
 #include "stmpc_ddpg_pop_kernels.hpp"
 #include "stmpc_td3_kernels.hpp"
 #include "stmpc_td3_pop_kernels.hpp"
@@ -16,6 +17,10 @@ struct stmpc_ddpg {
     int h1p = 0, h2p = 0, np = 0, Bp = 0;
     size_t lds = 0;
     bool td3_base = false;          // lent by a stmpc_td3 (stmpc_td3_base): an update or gradients of this handle alone would leave critic 2 behind
+    struct stmpc_td3 *td3_owner = nullptr;  // that stmpc_td3: it holds copies of dev (its two views), which stmpc_per_enable has to follow
+    bool pop_member = false;        // owned by a population, whose device table holds a copy of dev
+    bool per = false;               // prioritised replay (stmpc_per_enable): dev.tree ... dev.per_L are set
+    DevBuf per_tree, per_idx, per_aw, per_atd, per_atd2;    // (per_atd2: critic 2's Q - y, when td3_owner)
     int n_in(int which) const { return cfg.n_obs + 1 + which; }
     int64_t slot_len(int which) const { const int64_t n = n_in(which); return (int64_t)cfg.h1 * n + cfg.h1 + (int64_t)cfg.h2 * cfg.h1 + cfg.h2 + cfg.h2 + 1; }
 };
@@ -59,6 +64,14 @@ double ddpg_gauss_host(unsigned long long h, uint32_t *draw1, uint32_t *draw2) {
     const double f1 = ((double)u1 + 1.0) * 5.9604644775390625e-8;
     const volatile float theta = 6.2831855f * ((float)u2 * 5.9604644775390625e-8f);      // the float32 product the kernel forms
     return sqrt(-2.0 * log(f1)) * cos((double)theta);
+}
+// prioritised replay: the sampling step in front of a pass that gathers (nothing on a learner that samples uniformly)
+void per_launch_sample(const stmpc_ddpg *l, int gate, hipStream_t st) {
+    if (l->per) hipLaunchKernelGGL(k_per_sample, dim3(1), dim3(PER_THREADS), 0, st, l->dev, l->cfg.batch, l->Bp, gate);
+}
+// ... and the priority update behind the critic pass
+void per_launch_update(const stmpc_ddpg *l, hipStream_t st) {
+    if (l->per) hipLaunchKernelGGL(k_per_update, dim3(1), dim3(PER_THREADS), 0, st, l->dev, (const float *)l->per_atd2.as<float>(), l->cfg.batch, 1);
 }
 void ddpg_launch_grads(stmpc_ddpg *l, int which, int gate, hipStream_t st) {
     const int tiles = l->Bp / AT_TM, t1 = l->h2p / 16, t0 = l->h1p / 16;
@@ -160,6 +173,11 @@ int stmpc_ddpg_set_state(stmpc_ddpg *l, const int64_t *counters, const float *be
     HIPCHK(hipSetDevice(l->device));
     HIPCHK(hipDeviceSynchronize());
     long long cn[DG_NCNT];
+    if (l->per) {                                                    // the tree's leaves follow the ring's cursor and fill
+        HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
+        if (cn[DG_CURSOR] != counters[DG_CURSOR] || cn[DG_FILL] != counters[DG_FILL])
+            return fail(STMPC_EINVAL, "prioritised replay is enabled: the ring's cursor and fill cannot be set (the priorities belong to the rows pushed)");
+    }
     for (int i = 0; i < DG_NCNT; ++i) cn[i] = i <= DG_FRAMES ? counters[i] : 0;
     HIPCHK(hipMemcpy(l->dev.cnt, cn, sizeof cn, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(l->dev.pi.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
@@ -214,7 +232,9 @@ int stmpc_ddpg_update_device(stmpc_ddpg *l, int n_updates, double lr_q, double l
     if (n_updates < 0 || !(lr_q >= 0) || !(lr_pi >= 0)) return fail(STMPC_EINVAL, "n_updates or a learning rate is negative");
     HIPCHK(hipSetDevice(l->device));
     for (int u = 0; u < n_updates; ++u) {
+        per_launch_sample(l, 1, (hipStream_t)stream);
         ddpg_launch_grads(l, 1, 1, (hipStream_t)stream);
+        per_launch_update(l, (hipStream_t)stream);
         ddpg_launch_adam(l, 1, (float)lr_q, 0, 0, (hipStream_t)stream);
         ddpg_launch_grads(l, 0, 1, (hipStream_t)stream);
         ddpg_launch_adam(l, 0, (float)lr_pi, 0, 1, (hipStream_t)stream);
@@ -228,6 +248,7 @@ int stmpc_ddpg_grads_device(stmpc_ddpg *l, float *d_grad_actor, float *d_grad_cr
     if (l->td3_base) return fail(STMPC_EINVAL, "this learner is the base of a TD3 learner: take its gradients with stmpc_td3_grads_device");
     HIPCHK(hipSetDevice(l->device));
     hipStream_t st = (hipStream_t)stream;
+    per_launch_sample(l, 0, st);
     ddpg_launch_grads(l, 1, 0, st);
     hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(1), (const float *)l->dev.q.g, d_grad_critic);
     ddpg_launch_grads(l, 0, 0, st);
@@ -256,6 +277,7 @@ int stmpc_ddpg_replay_read(stmpc_ddpg *l, int64_t first, int64_t count, float *r
 int stmpc_ddpg_gather_device(stmpc_ddpg *l, float *d_rows, void *stream) {
     if (!l || !d_rows) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(l->device));
+    per_launch_sample(l, 0, (hipStream_t)stream);
     hipLaunchKernelGGL(k_replay_gather, dim3((l->cfg.batch * DG_ROW + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->dev, l->cfg.batch, d_rows);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -336,7 +358,7 @@ int stmpc_ddpg_pop_create(stmpc_ctx *c, const stmpc_ddpg_cfg *cfgs, int P, stmpc
     for (int m = 0; m < P && !rc; ++m) {
         stmpc_ddpg *l = nullptr;
         rc = stmpc_ddpg_create(c, cfgs + m, &l);
-        if (!rc) { p->members.push_back(l); host.push_back(l->dev); }
+        if (!rc) { l->pop_member = true; p->members.push_back(l); host.push_back(l->dev); }
     }
     if (!rc) rc = p->table.ensure(host.size() * sizeof(DdpgDev));
     if (!rc && hipMemcpy(p->table.p, host.data(), host.size() * sizeof(DdpgDev), hipMemcpyHostToDevice) != hipSuccess) rc = fail(STMPC_EHIP, "hipMemcpy of the member table failed");
@@ -456,6 +478,7 @@ int stmpc_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *g, stmpc_td3 **out) {
     if (rc) { delete t; return rc; }
     stmpc_ddpg *l = t->base;
     l->td3_base = true;
+    l->td3_owner = t;
     DdpgDev v1 = l->dev;
     DdpgNet &n = v1.q;
     const size_t np = (size_t)l->np, h1p = (size_t)l->h1p, h2p = (size_t)l->h2p, Bp = (size_t)l->Bp;
@@ -541,7 +564,9 @@ int stmpc_td3_update_device(stmpc_td3 *t, int n_updates, double lr_q, double lr_
     const Td3Grid g = td3_grid(t->base);
     hipStream_t st = (hipStream_t)stream;
     for (int u = 0; u < n_updates; ++u) {                            // the same six launches whatever the counters say
+        per_launch_sample(t->base, 1, st);
         td3_launch_critic_grads(t, 1, st);
+        per_launch_update(t->base, st);
         hipLaunchKernelGGL(k_td3_adam_critics, dim3(g.ablocks, 2), dim3(256), 0, st, t->dev, (float)lr_q, 1);
         td3_launch_actor_grads(t, 1, st);
         hipLaunchKernelGGL(k_td3_adam_finish, dim3(g.ablocks, 3), dim3(256), 0, st, t->dev, (float)lr_pi, 1);
@@ -555,6 +580,7 @@ int stmpc_td3_grads_device(stmpc_td3 *t, float *d_grad_actor, float *d_grad_crit
     stmpc_ddpg *l = t->base;
     HIPCHK(hipSetDevice(l->device));
     hipStream_t st = (hipStream_t)stream;
+    per_launch_sample(l, 0, st);
     td3_launch_critic_grads(t, 0, st);
     hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(1), (const float *)t->dev.v[0].q.g, d_grad_critic1);
     hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(1), (const float *)t->dev.v[1].q.g, d_grad_critic2);
@@ -568,6 +594,7 @@ int stmpc_td3_targets_device(stmpc_td3 *t, float *d_out, void *stream) {
     if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
     const stmpc_ddpg *l = t->base;
     HIPCHK(hipSetDevice(l->device));
+    per_launch_sample(l, 0, (hipStream_t)stream);
     hipLaunchKernelGGL(k_td3_critic_fwd, dim3(l->Bp / AT_TM, 1), dim3(AT_THREADS), l->lds, (hipStream_t)stream, t->dev, l->cfg.batch, 0, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -583,6 +610,69 @@ int stmpc_td3_stats_device(stmpc_td3 *t, double *d_out, void *stream) {
 
 double stmpc_td3_noise(uint64_t seed, uint64_t update, uint32_t row, uint32_t *draw1, uint32_t *draw2) {
     return ddpg_gauss_host(dg_hash(seed ^ TD3_STREAM, update, row), draw1, draw2);
+}
+
+}  // extern "C"
+
+// ---- prioritised replay (stmpc_per_*) for a lone DDPG learner or a lone TD3 learner's base; kernels in stmpc_per_kernels.hpp ----------------------
+extern "C" {
+
+int stmpc_per_enable(stmpc_ddpg *l, const stmpc_per_cfg *g) {
+    if (!l || !g) return fail(STMPC_EINVAL, "NULL argument");
+    if (!(g->min_priority > 0) || !(g->max_priority >= g->min_priority) || !std::isfinite(g->max_priority) || !(g->alpha >= 0) || !std::isfinite(g->alpha) ||
+        !(g->beta >= 0) || !std::isfinite(g->beta))
+        return fail(STMPC_EINVAL, "prioritised replay needs min_priority > 0, max_priority >= min_priority, alpha >= 0 and beta >= 0, all finite");
+    if (l->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: populations sample uniformly");
+    if (l->per) return fail(STMPC_EINVAL, "prioritised replay is already enabled on this learner");
+    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipDeviceSynchronize());
+    long long cn[DG_NCNT];
+    HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
+    if (cn[DG_FILL] != 0 || cn[DG_CURSOR] != 0) return fail(STMPC_EINVAL, "prioritised replay can be enabled on an empty ring only (fill is " + std::to_string(cn[DG_FILL]) + ")");
+    long long leaves = 1;
+    while (leaves < l->cfg.capacity) leaves <<= 1;
+    const size_t Bp = (size_t)l->Bp;
+    TRY(ddpg_zero(l->per_tree, (size_t)(2 * leaves - 1) * sizeof(double)));
+    TRY(ddpg_zero(l->per_idx, Bp * sizeof(long long)));
+    TRY(ddpg_zero(l->per_aw, Bp * sizeof(float)));
+    TRY(ddpg_zero(l->per_atd, Bp * sizeof(float)));
+    if (l->td3_owner) { TRY(ddpg_zero(l->per_atd2, Bp * sizeof(float))); }
+    auto set = [&](DdpgDev &d, DevBuf &atd) {
+        d.tree = l->per_tree.as<double>(); d.idx = l->per_idx.as<long long>(); d.aw = l->per_aw.as<float>(); d.atd = atd.as<float>();
+        d.per_alpha = g->alpha; d.per_beta = g->beta; d.per_min = g->min_priority; d.per_max = g->max_priority; d.per_L = leaves;
+    };
+    set(l->dev, l->per_atd);
+    if (l->td3_owner) {                                             // both views share the tree, idx and the weights; each critic leaves its own Q - y
+        set(l->td3_owner->dev.v[0], l->per_atd);
+        set(l->td3_owner->dev.v[1], l->per_atd2);
+    }
+    l->per = true;
+    return STMPC_OK;
+}
+
+int stmpc_per_tree_read(stmpc_ddpg *l, int64_t first, int64_t count, double *nodes) {
+    if (!l || !nodes) return fail(STMPC_EINVAL, "NULL argument");
+    if (!l->per) return fail(STMPC_EINVAL, "prioritised replay is not enabled on this learner");
+    if (first < 0 || count < 0 || first + count > 2 * l->dev.per_L - 1) return fail(STMPC_EINVAL, "nodes outside the tree");
+    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (count) HIPCHK(hipMemcpy(nodes, l->dev.tree + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    return STMPC_OK;
+}
+
+int stmpc_per_last_device(stmpc_ddpg *l, int64_t *d_idx, float *d_td, float *d_weight, void *stream) {
+    if (!l || !d_idx || !d_td || !d_weight) return fail(STMPC_EINVAL, "NULL argument");
+    if (!l->per) return fail(STMPC_EINVAL, "prioritised replay is not enabled on this learner");
+    HIPCHK(hipSetDevice(l->device));
+    hipLaunchKernelGGL(k_per_last, dim3((l->cfg.batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->dev, (const float *)l->per_atd2.as<float>(), l->cfg.batch,
+                       (long long *)d_idx, d_td, d_weight);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int64_t stmpc_per_sample_index(const double *tree, int64_t leaves, int64_t fill, uint64_t seed, uint64_t update, uint32_t row) {
+    if (!tree || leaves < 1 || (leaves & (leaves - 1)) || fill < 1 || fill > leaves) return -1;
+    return per_sample_index(tree, leaves, fill, seed, update, row);
 }
 
 }  // extern "C"
@@ -629,7 +719,7 @@ int stmpc_pop_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *cfgs, int P, stmpc_t
     for (int m = 0; m < P && !rc; ++m) {
         stmpc_td3 *t = nullptr;
         rc = stmpc_td3_create(c, cfgs + m, &t);
-        if (!rc) { p->members.push_back(t); host.push_back(t->dev); base.push_back(t->dev.v[0]); }
+        if (!rc) { t->base->pop_member = true; p->members.push_back(t); host.push_back(t->dev); base.push_back(t->dev.v[0]); }
     }
     if (!rc) rc = p->table.ensure(host.size() * sizeof(Td3Dev));
     if (!rc) rc = p->bases.ensure(base.size() * sizeof(DdpgDev));

@@ -25,6 +25,13 @@ float32 in the kernel's operation order), ``sample_indices_host``, ``noise_host`
 targets, clipped noise on the target action, the actor and all targets stepped every ``policy_delay``-th update -- in six launches per update that
 carry both critics in ``blockIdx.y``; twins: ``update_host_td3``, ``smoothing_noise_host``.  ``TD3Population`` is to it what ``DDPGPopulation`` is
 to ``DDPGLearner`` (``csrc/stmpc_td3_pop_kernels.hpp``: the member axis in ``blockIdx.z``).
+
+Prioritised replay (``DDPGConfig(per=PERConfig())``, ``csrc/stmpc_per_kernels.hpp``, ``stmpc_per_*``) is the reference's hand-written trainer's way of
+drawing minibatches (dqn.py:267-349, ``SumTree`` dqn.py:727-794; ``USE_PRIORITIZED_ER = True`` in config.py) for ``DDPGLearner`` and ``TD3Learner``:
+rows are drawn from a sum tree in proportion to ``min(|td| + min_priority, max_priority) ** alpha`` of their last critic error, new rows enter at
+``max_priority ** alpha``, and the critic's loss carries the importance weights ``(fill * p / total) ** -beta`` over their largest (``beta`` 0, the
+reference's: none).  Two launches more per update; populations sample uniformly.  Twins: ``SumTreeHost``, ``per_sample_host``, ``per_priority_host``,
+``per_weights_host`` and the ``weights=`` argument of ``update_host`` / ``update_host_td3``.
 """
 import math
 
@@ -41,11 +48,29 @@ NOISE_STREAM = 0x6E6F697365
 TWO_PI_F32 = float(np.float32(6.2831855))
 
 
+class PERConfig:
+    """The constants of prioritised replay; defaults are the reference's (config.py: PER_ALPHA, PER_MIN_PRIORITY, PER_MAX_PRIORITY; no importance
+    weights, so ``beta`` 0).  ``alpha`` 0.5 is a square root and 1 the identity on host and device alike; any other value goes through ``pow``."""
+
+    def __init__(self, alpha=0.5, beta=0.0, min_priority=1e-6, max_priority=4.0):
+        self.alpha, self.beta, self.min_priority, self.max_priority = float(alpha), float(beta), float(min_priority), float(max_priority)
+        if not (self.min_priority > 0 and self.max_priority >= self.min_priority and self.alpha >= 0 and self.beta >= 0 and
+                all(math.isfinite(x) for x in (self.alpha, self.beta, self.max_priority))):
+            raise ValueError("prioritised replay needs min_priority > 0, max_priority >= min_priority, alpha >= 0 and beta >= 0, all finite")
+
+    def to_c(self):
+        return _capi.PERCfg(alpha=self.alpha, beta=self.beta, min_priority=self.min_priority, max_priority=self.max_priority)
+
+
 class DDPGConfig:
-    """The constants of the update; defaults are the ``all`` ddpg preset's as its documentation gives them (``lr``: Settings.LEARNING_RATE)."""
+    """The constants of the update; defaults are the ``all`` ddpg preset's as its documentation gives them (``lr``: Settings.LEARNING_RATE).
+    ``per``: a ``PERConfig`` for prioritised replay (None: uniform minibatches); it is not part of ``to_c`` -- the learner enables it on its handle."""
 
     def __init__(self, n_obs=20, h1=400, h2=300, batch=100, capacity=1000000, replay_start=5000, gamma=0.99, tau=0.005, lr_q=None, lr_pi=None,
-                 beta1=0.9, beta2=0.999, eps=1e-8, time_scale=0.001, tanh_scale=None, tanh_mean=None, noise=0.1, action_low=None, action_high=None):
+                 beta1=0.9, beta2=0.999, eps=1e-8, time_scale=0.001, tanh_scale=None, tanh_mean=None, noise=0.1, action_low=None, action_high=None, per=None):
+        if per is not None and not isinstance(per, PERConfig):
+            raise ValueError("per must be a PERConfig or None")
+        self.per = per
         lo = float(Settings.MINIMUM_NEGATIVE_JERK) if action_low is None else float(action_low)
         hi = float(Settings.MAXIMUM_POSITIVE_JERK) if action_high is None else float(action_high)
         self.n_obs, self.h1, self.h2, self.batch, self.capacity, self.replay_start = int(n_obs), int(h1), int(h2), int(batch), int(capacity), int(replay_start)
@@ -152,11 +177,12 @@ def _polyak(P, name, cfg):
         P[name + "_target"][k] = (1 - cfg.tau) * P[name + "_target"][k] + cfg.tau * P[name][k]
 
 
-def update_host(params, batch, cfg, dtype="float64", lr_q=None, lr_pi=None, grads_only=False):
+def update_host(params, batch, cfg, dtype="float64", lr_q=None, lr_pi=None, grads_only=False, weights=None):
     """One update (steps 1-4 of the module text) in torch with autograd, every tensor in ``dtype`` ("float64" or "float32").
     ``params``: as ``new_params`` / ``DDPGLearner.state_dict()["params"]``; returns the new one (numpy arrays of ``dtype``) and a dict with
     ``critic_loss``, ``mean_q``, ``grad_critic``, ``grad_actor``.  ``grads_only``: nothing is applied and BOTH gradients are taken against the
-    current critic (``stmpc_ddpg_grads_device``'s mode)."""
+    current critic (``stmpc_ddpg_grads_device``'s mode).  ``weights``: prioritised replay's importance weight per minibatch row, which multiplies
+    that row's term of the critic's loss (None: none; ``critic_loss`` stays the unweighted mean, as the device reports it)."""
     import torch
     td = getattr(torch, dtype)
     T = lambda a: torch.tensor(np.asarray(a), dtype=td)
@@ -176,7 +202,7 @@ def update_host(params, batch, cfg, dtype="float64", lr_q=None, lr_pi=None, grad
     crit = {k: P["critic"][k].clone().requires_grad_(True) for k in TENSORS}
     q = _mlp(crit, torch.cat([s, a[:, None]], 1))
     loss = ((q - y) ** 2).mean()
-    gq = dict(zip(TENSORS, torch.autograd.grad(loss, [crit[k] for k in TENSORS])))
+    gq = dict(zip(TENSORS, torch.autograd.grad(loss if weights is None else (T(weights) * (q - y) ** 2).mean(), [crit[k] for k in TENSORS])))
     if not grads_only:
         adam("critic", gq)
     act = {k: P["actor"][k].clone().requires_grad_(True) for k in TENSORS}
@@ -249,13 +275,14 @@ def new_params_td3(actor_net, critic_net, critic2_net):
     return p
 
 
-def update_host_td3(params, batch, cfg, dtype="float64", eps=None, lr_q=None, lr_pi=None, grads_only=False):
+def update_host_td3(params, batch, cfg, dtype="float64", eps=None, lr_q=None, lr_pi=None, grads_only=False, weights=None):
     """One TD3 update in torch with autograd, every tensor in ``dtype``: ``update_host`` with the smoothed, clipped target action, the minimum of
     both target critics, both critics stepped, and -- only if (updates + 1) % cfg.policy_delay == 0 -- the actor stepped against critic 1 and all
     three targets moved.  ``eps``: the smoothing noise per minibatch row (None: zeros); the twin is handed it, it does not draw.
     ``params``: as ``new_params_td3`` / ``TD3Learner.state_dict()["params"]``.  ``info`` carries ``critic_loss`` / ``critic2_loss``, ``mean_q`` /
     ``mean_q2``, ``grad_critic`` / ``grad_critic2`` / ``grad_actor`` (None when the actor did not step) and ``targets`` [B][4] = a', Qt1, Qt2, y.
-    ``grads_only``: nothing is applied and all three gradients are taken against the current critics (``stmpc_td3_grads_device``'s mode)."""
+    ``grads_only``: nothing is applied and all three gradients are taken against the current critics (``stmpc_td3_grads_device``'s mode).
+    ``weights``: as ``update_host``'s, on both critics' losses."""
     import torch
     td = getattr(torch, dtype)
     T = lambda a: torch.tensor(np.asarray(a), dtype=td)
@@ -277,7 +304,7 @@ def update_host_td3(params, batch, cfg, dtype="float64", eps=None, lr_q=None, lr
         crit = {k: P[name][k].clone().requires_grad_(True) for k in TENSORS}
         q = _mlp(crit, torch.cat([s, a[:, None]], 1))
         loss = ((q - y) ** 2).mean()
-        g = dict(zip(TENSORS, torch.autograd.grad(loss, [crit[k] for k in TENSORS])))
+        g = dict(zip(TENSORS, torch.autograd.grad(loss if weights is None else (T(weights) * (q - y) ** 2).mean(), [crit[k] for k in TENSORS])))
         if not grads_only:
             _adam_step(P, name, g, lr_q, u + 1, cfg)
         info["critic%s_loss" % tag], info["mean_q%s" % tag], info["grad_critic%s" % tag] = float(loss.detach()), float(q.detach().mean()), {k: g[k].numpy() for k in TENSORS}
@@ -297,6 +324,97 @@ def update_host_td3(params, batch, cfg, dtype="float64", eps=None, lr_q=None, lr
     out["beta_pow"] = np.array(params["beta_pow"], dtype=np.float32) * (1 if grads_only else np.concatenate([b if due else one, b, b]))
     out["updates"] = u + (0 if grads_only else 1)
     return out, info
+
+
+# ---- prioritised replay: host twins (stmpc_per_kernels.hpp) ------------------------------------------------------------------------------------
+PER_STREAM = 0x70657264726177
+PER_REDRAWS = 3
+
+
+def per_leaves(capacity):
+    """The tree's leaf count: ``capacity`` rounded up to a power of two."""
+    n = 1
+    while n < int(capacity):
+        n *= 2
+    return n
+
+
+def per_pow(p, alpha):
+    """p ** alpha as the library forms it: a square root for 0.5, the identity for 1, pow otherwise (float64)."""
+    p = np.asarray(p, dtype=np.float64)
+    return np.sqrt(p) if alpha == 0.5 else (p.copy() if alpha == 1.0 else np.power(p, np.float64(alpha)))
+
+
+def per_priority_host(td, cfg):
+    """The leaf weights min(|td| + min_priority, max_priority) ** alpha of critic errors ``td`` (float32, as the device reports them); float64."""
+    e = np.abs(np.asarray(td, dtype=np.float32).astype(np.float64)) + np.float64(cfg.min_priority)
+    return per_pow(np.where(e < cfg.max_priority, e, np.float64(cfg.max_priority)), cfg.alpha)
+
+
+class SumTreeHost:
+    """The reference's ``SumTree`` weights (dqn.py:727-794) for a ring of ``capacity`` rows: ``nodes`` float64 [2 * leaves - 1], root 0, children of
+    i at 2i + 1 and 2i + 2, ring row p at leaf p + leaves - 1.  ``push(n)``: the next ``n`` ring rows get ``max_priority ** alpha``; ``set``: one leaf.
+    Every internal node on the way up is recomputed as left + right, as ``_update_sum`` does."""
+
+    def __init__(self, capacity, cfg=None):
+        self.capacity, self.cfg = int(capacity), cfg if cfg is not None else PERConfig()
+        self.leaves = per_leaves(capacity)
+        self.nodes = np.zeros(2 * self.leaves - 1, dtype=np.float64)
+        self.cursor = self.fill = 0
+
+    def set(self, position, weight):
+        i = int(position) + self.leaves - 1
+        self.nodes[i] = weight
+        while i:
+            i = (i - 1) // 2
+            self.nodes[i] = self.nodes[2 * i + 1] + self.nodes[2 * i + 2]
+
+    def push(self, n):
+        w = float(per_pow(self.cfg.max_priority, self.cfg.alpha))
+        for _ in range(int(n)):
+            self.set(self.cursor, w)
+            self.cursor = (self.cursor + 1) % self.capacity
+            self.fill = min(self.fill + 1, self.capacity)
+
+
+def per_sample_host(nodes, seed, update, batch, fill):
+    """Ring rows of the ``batch`` minibatch rows of update ``update`` drawn from the tree ``nodes`` with ``fill`` rows filled (int64 [batch]):
+    ``stmpc_per_sample_index``'s procedure in Python floats (IEEE fp64, one operation per operation)."""
+    nodes = np.asarray(nodes, dtype=np.float64)
+    leaves = (nodes.size + 1) // 2
+    tree, total, fill, s = nodes.tolist(), float(nodes[0]), int(fill), (int(seed) & _M64) ^ PER_STREAM
+    out = np.zeros(int(batch), dtype=np.int64)
+    for r in range(int(batch)):
+        pos = None
+        for a in range(PER_REDRAWS + 1):
+            roll = ((hash3(s, update, r | (a << 32)) >> 11) * 2.0 ** -53) * total
+            i = 0
+            while i < leaves - 1:
+                left = 2 * i + 1
+                if roll <= tree[left]:
+                    i = left
+                else:
+                    roll -= tree[left]
+                    i = left + 1
+            if i - (leaves - 1) < fill and tree[i] > 0.0:
+                pos = i - (leaves - 1)
+                break
+        out[r] = hash3(seed, update, r) % fill if pos is None else pos
+    return out
+
+
+def per_weights_host(nodes, idx, fill, beta):
+    """Importance weights float32 [batch] of the rows ``idx``: (fill * p / total) ** -beta over the largest of them, in float64; exactly 1 for
+    ``beta`` 0 (and for a row of weight 0, which only the uniform fall-back can draw and which does not count for the largest)."""
+    nodes, idx = np.asarray(nodes, dtype=np.float64), np.asarray(idx, dtype=np.int64)
+    if beta == 0:
+        return np.ones(idx.size, dtype=np.float32)
+    p = nodes[idx + (nodes.size + 1) // 2 - 1]
+    ok = p > 0
+    w = np.ones(idx.size, dtype=np.float64)
+    if ok.any():
+        w[ok] = np.power(np.float64(fill) * p[ok] / nodes[0], -np.float64(beta)) / np.power(np.float64(fill) * p[ok].min() / nodes[0], -np.float64(beta))
+    return w.astype(np.float32)
 
 
 # ---- the learner -------------------------------------------------------------------------------------------------------------------------------
@@ -320,6 +438,8 @@ class DDPGLearner:
         self.seed = int(seed)
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.handle = self._make_handle()
+        if self.cfg.per is not None:                                # (a population member's handle refuses: populations sample uniformly)
+            self.ctx.per_enable(self.handle, self.cfg.per.to_c())
         c = self.cfg
         rng = np.random.default_rng(self.seed)
         if isinstance(init, dict):
@@ -400,6 +520,20 @@ class DDPGLearner:
         rows = self.torch.empty(self.cfg.batch, _capi.DDPG_ROW, dtype=self.torch.float32, device=self.device)
         self.ctx.ddpg_gather(self.handle, rows.data_ptr(), self._stream())
         return rows.cpu().numpy()
+
+    def priorities(self):
+        """Debug, prioritised replay: the sum tree, float64 [2 * leaves - 1] (numpy; ``SumTreeHost``'s layout); synchronises."""
+        return self.ctx.per_tree_read(self.handle, 0, 2 * per_leaves(self.cfg.capacity) - 1)
+
+    def last_sample(self):
+        """Debug, prioritised replay: {"idx" int64, "td" float32, "weight" float32}, [batch] each (numpy) -- the ring rows and importance weights of
+        the most recent sampling step (an update's, or ``minibatch`` / ``grads`` / ``targets``') and Q - y of the most recent critic pass (TD3: of
+        the critic with the larger magnitude); synchronises."""
+        torch, B = self.torch, self.cfg.batch
+        idx = torch.zeros(B, dtype=torch.int64, device=self.device)
+        td, w = (torch.zeros(B, dtype=torch.float32, device=self.device) for _ in range(2))
+        self.ctx.per_last(self.handle, idx.data_ptr(), td.data_ptr(), w.data_ptr(), self._stream())
+        return {"idx": idx.cpu().numpy(), "td": td.cpu().numpy(), "weight": w.cpu().numpy()}
 
     def stats_device(self):
         """fp64 [4] device tensor: critic loss and mean Q of the last minibatch, fill, updates done (asynchronous)."""
@@ -575,6 +709,10 @@ class DDPGPopulation:
             cfgs = [cfgs[0]] * int(cfgs[1])
         self.cfgs = list(cfgs)
         P = self.P = len(self.cfgs)
+        for m, c in enumerate(self.cfgs):
+            if getattr(c, "per", None) is not None:
+                raise ValueError("member %d's cfg asks for prioritised replay (per=): a population's members sample uniformly; train that member as a lone "
+                                 "learner" % m)
         if not env.continuous:
             raise ValueError("DDPG needs the continuous action space (sumo-jerk-continuous-v0)")
         # (a member count outside 1 ... DDPG_POP_MAX is the library's to refuse)

@@ -1,0 +1,276 @@
+"""Prioritised replay for the DDPG / TD3 learners (learner.PERConfig, csrc/stmpc_per_kernels.hpp, stmpc_per_* of include/stmpc.h): CPU part.
+
+  * header, library and binding agree on the new entries and on stmpc_per_cfg; the ABI is still 8;
+  * ``per_sample_host`` equals ``stmpc_per_sample_index`` -- the function the kernel calls -- on random and on hand-made trees;
+  * ``SumTreeHost`` against brute force; sampling frequencies; the priority rule on duplicates; ``update_host(weights=)``; refusals.
+The GPU part is test_per.py, which takes its helpers from here.
+"""
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import REPO
+
+ENTRIES = {"stmpc_per_enable", "stmpc_per_tree_read", "stmpc_per_last_device", "stmpc_per_sample_index"}
+
+
+def _capi():
+    import rl_mpc_lanemerging_amd as pkg
+    if pkg.build.needs_build():
+        pkg.build.build()
+    from rl_mpc_lanemerging_amd import _capi
+    return _capi
+
+
+def tree_from_leaves(w):
+    """The sum tree over leaf weights ``w`` (a power of two of them), every level summed from the one below: brute force, no incremental update."""
+    w = np.asarray(w, dtype=np.float64)
+    n = np.zeros(2 * w.size - 1)
+    n[w.size - 1:] = w
+    width = w.size // 2
+    while width >= 1:
+        n[width - 1:2 * width - 1] = n[2 * width - 1:4 * width - 1:2] + n[2 * width:4 * width:2]
+        width //= 2
+    return n
+
+
+def internal_nodes_are_exact(nodes):
+    leaves = (nodes.size + 1) // 2
+    i = np.arange(leaves - 1)
+    return bool(np.array_equal(nodes[i], nodes[2 * i + 1] + nodes[2 * i + 2]))
+
+
+def test_header_library_and_binding_agree_on_prioritised_replay():
+    capi = _capi()
+    from test_host_cpu import _header_struct_fields
+    lib = capi.load()
+    header = open(os.path.join(REPO, "include", "stmpc.h")).read()
+    declared = {n for n in re.findall(r"\b(stmpc_[a-z_0-9]+)\s*\(", header) if n.startswith("stmpc_per_")}
+    assert declared == ENTRIES == {n for n in capi.EXPORTS if n.startswith("stmpc_per_")}
+    for name in declared:
+        assert getattr(lib, name) is not None and getattr(lib, name).argtypes is not None, name
+    want = _header_struct_fields("stmpc_per_cfg")
+    assert [n for n, _ in want] == [n for n, _ in capi.PERCfg._fields_] == ["alpha", "beta", "min_priority", "max_priority"]
+    assert all(t == "double" for _, t in want) and all(t is ctypes.c_double for _, t in capi.PERCfg._fields_)
+    assert lib.stmpc_per_sample_index.restype is ctypes.c_int64
+    assert capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8 and "#define STMPC_ABI_VERSION 8" in " ".join(header.split())
+    # the cfg structs of ABI 8 did not grow: prioritisation is enabled on the handle
+    from rl_mpc_lanemerging_amd import learner
+    assert ctypes.sizeof(capi.DDPGCfg) == 24 + 8 * 13 and ctypes.sizeof(capi.TD3Cfg) == ctypes.sizeof(capi.DDPGCfg) + 24
+    c = learner.TD3Config(per=learner.PERConfig(alpha=1.0, beta=0.4))
+    assert (c.per.alpha, c.per.beta, c.per.min_priority, c.per.max_priority) == (1.0, 0.4, 1e-6, 4.0) and learner.DDPGConfig().per is None
+    d = learner.PERConfig()
+    assert (d.alpha, d.beta, d.min_priority, d.max_priority) == (0.5, 0.0, 1e-6, 4.0)
+
+
+def _c_indices(capi, nodes, fill, seed, update, batch):
+    leaves = (nodes.size + 1) // 2
+    return [capi.per_sample_index(nodes, leaves, fill, seed, update, r) for r in range(batch)]
+
+
+def test_sampling_twin_equals_the_c_twin():
+    capi = _capi()
+    from rl_mpc_lanemerging_amd import learner
+    rng = np.random.default_rng(0)
+    for leaves in (1, 2, 64, 2 ** 20):
+        big = leaves > 64
+        for fill in sorted({1, max(1, leaves // 3), leaves}):
+            w = np.zeros(leaves)
+            w[:fill] = rng.uniform(1e-3, 2.0, fill)
+            nodes = tree_from_leaves(w)
+            for seed in ((5,) if big else (0, 5, 2 ** 63 + 11, 2 ** 64 - 1)):
+                for update in ((7,) if big else (0, 1, 999, 2 ** 40 + 3)):
+                    batch = 8 if big else 24
+                    idx = learner.per_sample_host(nodes, seed, update, batch, fill)
+                    assert idx.min() >= 0 and idx.max() < fill
+                    assert _c_indices(capi, nodes, fill, seed, update, batch) == list(idx), (leaves, fill, seed, update)
+    # hand-made: node 1 claims mass its leaves do not have, so half the rolls end on ring row 1 -- filled, weight 0 -- and are redrawn
+    nodes = np.array([2.0, 1.0, 1.0, 0.0, 0.0, 1.0, 0.0])
+    idx = learner.per_sample_host(nodes, 3, 0, 64, 3)
+    uni = learner.sample_indices_host(3, 0, 64, 3)
+    assert _c_indices(capi, nodes, 3, 3, 0, 64) == list(idx)
+    first = learner.per_sample_host(tree_from_leaves([0.0, 1.0, 1.0, 0.0]), 3, 0, 64, 3)          # the same rolls on a sound tree: rows 1 and 2, no redraw
+    redrawn = first == 1
+    assert redrawn.sum() > 16 and (idx[~redrawn] == 2).all()
+    assert (idx[redrawn] == 2).sum() > 8                           # a redraw that succeeded ...
+    fell = redrawn & (idx != 2)
+    assert fell.any() and np.array_equal(idx[fell], uni[fell])      # ... and four failures in a row: the uniform index (row 2 can be one, so >= these)
+    # all the mass next to unfilled leaves: every draw and redraw ends past fill, every row falls back
+    nodes = tree_from_leaves([0.0, 0.0, 0.0, 0.0, 0.0, 3.0, 1.0, 0.0])
+    for fill in (1, 5):
+        idx = learner.per_sample_host(nodes, 9, 4, 32, fill)
+        assert np.array_equal(idx, learner.sample_indices_host(9, 4, 32, fill)) and _c_indices(capi, nodes, fill, 9, 4, 32) == list(idx)
+    # mass on both sides of fill: in range, and equal to the C twin
+    nodes = tree_from_leaves([0.1, 0.1, 5.0, 5.0])
+    idx = learner.per_sample_host(nodes, 1, 2, 64, 2)
+    assert idx.max() < 2 and _c_indices(capi, nodes, 2, 1, 2, 64) == list(idx)
+    # refused inputs
+    assert capi.per_sample_index(np.zeros(5), 3, 1, 0, 0, 0) == -1 and capi.per_sample_index(np.ones(3), 2, 0, 0, 0, 0) == -1
+    assert capi.per_sample_index(np.ones(3), 2, 3, 0, 0, 0) == -1
+
+
+@pytest.mark.parametrize("capacity", [1, 37, 64])
+def test_sum_tree_host_against_brute_force(capacity):
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    rng = np.random.default_rng(capacity)
+    for alpha in (0.5, 1.0):
+        cfg = learner.PERConfig(alpha=alpha)
+        t = learner.SumTreeHost(capacity, cfg)
+        assert t.leaves == {1: 1, 37: 64, 64: 64}[capacity] and t.nodes.size == 2 * t.leaves - 1 and not t.nodes.any()
+        leaf = np.zeros(t.leaves)
+        cursor = 0
+        w0 = 2.0 if alpha == 0.5 else 4.0                            # max_priority ** alpha, exactly
+        for step in range(12):
+            n = int(rng.integers(1, capacity + 1))
+            t.push(n)
+            leaf[(cursor + np.arange(n)) % capacity] = w0
+            cursor = (cursor + n) % capacity
+            for _ in range(5):
+                p = int(rng.integers(0, t.fill))
+                w = float(rng.uniform(0, 2))
+                t.set(p, w)
+                leaf[p] = w
+            assert t.cursor == cursor and t.fill == min(capacity, t.fill) and np.array_equal(t.nodes[t.leaves - 1:], leaf)
+            assert internal_nodes_are_exact(t.nodes) and np.array_equal(t.nodes, tree_from_leaves(leaf))
+            assert abs(t.nodes[0] - math.fsum(leaf)) <= 1e-12 * math.fsum(leaf)
+            assert not leaf[capacity:].any()
+        assert t.fill == capacity
+
+
+def test_sampling_frequencies_follow_the_priorities():
+    """8 x 2048 draws (updates 0 ... 7 of seed 11) from eight leaves: every leaf's count within 5 binomial standard deviations of N p_i
+    (the twin alone: worst 2.7 on these inputs)."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    w = np.array([1, 2, 3, 4, 0.5, 1.5, 2.5, 3.5])
+    nodes = tree_from_leaves(w)
+    cnt, N = np.zeros(8), 0
+    for u in range(8):
+        cnt += np.bincount(learner.per_sample_host(nodes, 11, u, 2048, 8), minlength=8)
+        N += 2048
+    p = w / w.sum()
+    z = (cnt - N * p) / np.sqrt(N * p * (1 - p))
+    print("z scores", z)
+    assert np.abs(z).max() <= 5
+
+
+def test_priority_rule_and_duplicates():
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    td = np.array([0.25, -9.0, 0.0, 1.0, -0.25, 2.25 - 1e-6], dtype=np.float32)
+    for alpha in (0.5, 1.0):
+        cfg = learner.PERConfig(alpha=alpha)
+        p = learner.per_priority_host(td, cfg)
+        e = np.minimum(np.abs(td.astype(np.float64)) + 1e-6, 4.0)
+        assert p.dtype == np.float64 and np.array_equal(p, np.sqrt(e) if alpha == 0.5 else e) and p[1] == (2.0 if alpha == 0.5 else 4.0)
+        t = learner.SumTreeHost(8, cfg)
+        t.push(8)
+        idx = [3, 5, 3, 7, 5, 3]                                    # rows 0, 2, 5 hit leaf 3; rows 1, 4 leaf 5
+        for r, i in enumerate(idx):
+            t.set(i, p[r])
+        leaf = t.nodes[t.leaves - 1:]
+        assert leaf[3] == p[5] and leaf[5] == p[4] and leaf[7] == p[3] and leaf[0] == (2.0 if alpha == 0.5 else 4.0)
+        assert internal_nodes_are_exact(t.nodes)
+    assert np.allclose(learner.per_priority_host(td, learner.PERConfig(alpha=0.7)), np.minimum(np.abs(td.astype(np.float64)) + 1e-6, 4.0) ** 0.7, rtol=1e-15)
+    nodes = tree_from_leaves([1.0, 4.0, 0.25, 0.0])
+    w = learner.per_weights_host(nodes, [0, 1, 2, 2], 3, 0.4)
+    assert w.dtype == np.float32 and w[2] == w[3] == 1.0 and w.max() == 1.0
+    assert np.allclose(w[:2], [(1.0 / 0.25) ** -0.4, (4.0 / 0.25) ** -0.4], rtol=1e-6)
+    assert np.array_equal(learner.per_weights_host(nodes, [0, 1, 2], 3, 0.0), np.ones(3, dtype=np.float32))
+
+
+def test_update_host_weights():
+    """weights = ones changes no bit; given weights equal an independent restatement: nn.Sequential modules, torch.optim.Adam, loss.backward() on
+    mean(w (Q - y)^2), three updates in a row (test_learner's restatement and tolerances, with the weights)."""
+    _capi()
+    import torch
+    from rl_mpc_lanemerging_amd import learner
+    from test_learner import _random_problem
+    rng = np.random.default_rng(2)
+    cfg, params, batch = _random_problem(rng)
+    B = len(batch["r"])
+    for dtype in ("float64", "float32"):
+        for go in (False, True):
+            a, ia = learner.update_host(params, batch, cfg, dtype, grads_only=go)
+            b, ib = learner.update_host(params, batch, cfg, dtype, grads_only=go, weights=np.ones(B))
+            for slot in ("actor", "critic", "actor_target", "critic_target", "critic_m", "critic_v"):
+                assert all(np.array_equal(a[slot][k], b[slot][k]) for k in learner.TENSORS), (dtype, go, slot)
+            assert all(np.array_equal(ia["grad_critic"][k], ib["grad_critic"][k]) and np.array_equal(ia["grad_actor"][k], ib["grad_actor"][k]) for k in learner.TENSORS)
+            assert ia["critic_loss"] == ib["critic_loss"]
+    from test_td3_cpu import minibatch_host, random_td3_problem
+    cfg3, params3, replay3 = random_td3_problem("padded", 48, seed=3)
+    batch3 = minibatch_host(replay3, cfg3)[1]
+    a, ia = learner.update_host_td3(params3, batch3, cfg3)
+    b, ib = learner.update_host_td3(params3, batch3, cfg3, weights=np.ones(len(batch3["r"])))
+    assert all(np.array_equal(a[s][k], b[s][k]) for s in ("critic", "critic2", "actor") for k in learner.TENSORS)
+    wts = rng.uniform(0.1, 1.0, len(batch3["r"]))
+    _, iw = learner.update_host_td3(params3, batch3, cfg3, weights=wts, grads_only=True)
+    assert not np.array_equal(iw["grad_critic2"]["w1"], ia["grad_critic2"]["w1"])
+
+    weights = rng.uniform(0.05, 1.0, B)
+    weights[3] = 1.0
+    T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
+
+    def module(net):
+        h1, n_in = net["w0"].shape
+        h2 = net["w1"].shape[0]
+        m = torch.nn.Sequential(torch.nn.Linear(n_in, h1), torch.nn.ReLU(), torch.nn.Linear(h1, h2), torch.nn.ReLU(), torch.nn.Linear(h2, 1)).double()
+        with torch.no_grad():
+            for lin, (w, b) in zip((m[0], m[2], m[4]), (("w0", "b0"), ("w1", "b1"), ("w2", "b2"))):
+                lin.weight.copy_(T(net[w])); lin.bias.copy_(T(net[b]))
+        return m
+    pi, pi_t, q, q_t = module(params["actor"]), module(params["actor_target"]), module(params["critic"]), module(params["critic_target"])
+    opt_q = torch.optim.Adam(q.parameters(), lr=cfg.lr_q, betas=(cfg.beta1, cfg.beta2), eps=cfg.eps)
+    opt_pi = torch.optim.Adam(pi.parameters(), lr=cfg.lr_pi, betas=(cfg.beta1, cfg.beta2), eps=cfg.eps)
+    s, a, r, s2, mask, wt = (T(x) for x in (batch["s"], batch["a"], batch["r"], batch["s2"], batch["mask"], weights))
+    squash = lambda z: torch.tanh(z) * cfg.tanh_scale + cfg.tanh_mean
+    plain = params
+    for it in range(3):
+        params, info = learner.update_host(params, batch, cfg, "float64", weights=weights)
+        plain, _ = learner.update_host(plain, batch, cfg, "float64")
+        with torch.no_grad():
+            y = r + cfg.gamma * mask * q_t(torch.cat([s2, squash(pi_t(s2))], 1))[:, 0]
+        qv = q(torch.cat([s, a[:, None]], 1))[:, 0]
+        unweighted = float(((qv - y) ** 2).mean().detach())
+        loss = (wt * (qv - y) ** 2).sum() / B
+        opt_q.zero_grad(); loss.backward(); opt_q.step()
+        aloss = -q(torch.cat([s, squash(pi(s))], 1)).mean()
+        opt_pi.zero_grad(); aloss.backward(); opt_pi.step()
+        with torch.no_grad():
+            for tgt, src in ((pi_t, pi), (q_t, q)):
+                for pt, ps in zip(tgt.parameters(), src.parameters()):
+                    pt.mul_(1 - cfg.tau).add_(cfg.tau * ps)
+        assert abs(info["critic_loss"] - unweighted) <= 1e-12 * abs(unweighted)
+        for slot, mod in (("actor", pi), ("actor_target", pi_t), ("critic", q), ("critic_target", q_t)):
+            for k, p in zip(learner.TENSORS, mod.parameters()):
+                np.testing.assert_allclose(params[slot][k], p.detach().numpy(), rtol=1e-11, atol=1e-14, err_msg="%s.%s after update %d" % (slot, k, it + 1))
+    assert params["updates"] == 3 and np.abs(params["critic"]["w1"] - plain["critic"]["w1"]).max() > 1e-6
+
+
+def test_refusals():
+    capi = _capi()
+    from rl_mpc_lanemerging_amd import learner
+    for kw in ({"min_priority": 0.0}, {"min_priority": -1e-6}, {"max_priority": 1e-7}, {"alpha": -0.1}, {"beta": -0.1}, {"alpha": float("nan")},
+               {"max_priority": float("inf")}):
+        with pytest.raises(ValueError):
+            learner.PERConfig(**kw)
+    with pytest.raises(ValueError):
+        learner.DDPGConfig(per={"alpha": 0.5})
+    # the library refuses before it touches a device: no learner, no cfg
+    lib = capi.load()
+    good = capi.PERCfg(alpha=0.5, beta=0.0, min_priority=1e-6, max_priority=4.0)
+    assert lib.stmpc_per_enable(None, ctypes.byref(good)) == capi.STMPC_EINVAL
+    assert lib.stmpc_per_tree_read(None, 0, 1, (ctypes.c_double * 1)()) == capi.STMPC_EINVAL
+    assert lib.stmpc_per_last_device(None, None, None, None, None) == capi.STMPC_EINVAL
+    # populations sample uniformly: refused before the env is looked at
+    per = learner.PERConfig()
+    for Pop, Cfg in ((learner.DDPGPopulation, learner.DDPGConfig), (learner.TD3Population, learner.TD3Config)):
+        with pytest.raises(ValueError, match="prioritised"):
+            Pop(None, [Cfg(n_obs=20), Cfg(n_obs=20, per=per)])
+        with pytest.raises(ValueError, match="prioritised"):
+            Pop(None, (Cfg(n_obs=20, per=per), 3))
