@@ -772,6 +772,26 @@ int  stmpc_per_last_device(stmpc_ddpg *learner, int64_t *d_idx, float *d_td, flo
 int64_t stmpc_per_sample_index(const double *tree, int64_t leaves, int64_t fill, uint64_t seed, uint64_t update, uint32_t row);
 
 /*
+ * Prioritised replay for the two populations: the section above per member, so that "prioritised against uniform" and "which alpha / beta" are sweeps
+ * a population runs in one launch sequence.  (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8.  A
+ * population on which neither entry was called launches what it launched before and computes the same bits.)  The entries read stmpc_pop_per_*: the
+ * prefixes of the lone entries above and of the two populations are closed sets.
+ *   cfgs HOST [P], enabled HOST uint8 [P], P = the population's size: member m gets a sum tree with cfgs[m] where enabled[m] is not 0 and keeps sampling
+ *   uniformly where it is 0 (cfgs[m] is then not read); the population may mix both.  Every enabled member passes the checks of the lone enable (the
+ *   cfg's ranges, an empty ring) before anything is allocated; then the members' structs change and the population's device table(s) are written anew.
+ *   One call per population: STMPC_EINVAL for a second one, for P other than the population's size, NULL pointers, a cfg out of range, a ring that is
+ *   not empty.  The lone enable on a borrowed member stays refused.
+ * Afterwards a prioritised member is bit-identical to a lone learner with the same cfg and the lone enable, given its slice: pop_push_device sets the
+ * pushed rows' leaves in the push's own launch, pop_update_device runs the sampling step in front of the critic pass and the priority update behind
+ * the critic's weight gradients, one workgroup per member each -- EIGHT launches per update whatever P is, and only if at least one member is
+ * prioritised (else the six of before).  Both steps are gated by the member's own replay_start.  On a borrowed member everything that follows the
+ * lone enable works: the tree_read / last_device entries above, gather_device, grads_device, stmpc_td3_targets_device (each with its ungated sampling
+ * step), and stmpc_ddpg_set_state's refusal to move the cursor or the fill.
+ */
+int  stmpc_pop_per_enable_ddpg(stmpc_ddpg_pop *pop, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P);
+int  stmpc_pop_per_enable_td3(stmpc_td3_pop *pop, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P);
+
+/*
  * Actors straight from learners, and a population of actors evaluated in one launch.  The reference's workflow ends a training with an evaluation
  * of the model it trained (ddpg.train_ddpg_all_with_lr_drop's closing `evaluate`, ddpg.py:96-117) and publishes a matrix of EVALUATE_COMBINED_DDPG runs, one per
  * MODEL_NAME (DDPGAgent.load + get_control, ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json, experiment_data/saved_data.csv).  (Additive: new

@@ -281,6 +281,7 @@ EXPORTS = (
     "stmpc_pop_td3_create", "stmpc_pop_td3_destroy", "stmpc_pop_td3_size", "stmpc_pop_td3_member", "stmpc_pop_td3_act_device",
     "stmpc_pop_td3_push_device", "stmpc_pop_td3_update_device", "stmpc_pop_td3_stats_device",
     "stmpc_per_enable", "stmpc_per_tree_read", "stmpc_per_last_device", "stmpc_per_sample_index",
+    "stmpc_pop_per_enable_ddpg", "stmpc_pop_per_enable_td3",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
@@ -478,6 +479,8 @@ def load():
     lib.stmpc_per_last_device.argtypes = [vp, vp, vp, vp, vp]
     lib.stmpc_per_sample_index.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint32]
     lib.stmpc_per_sample_index.restype = C.c_int64
+    lib.stmpc_pop_per_enable_ddpg.argtypes = [vp, C.POINTER(PERCfg), C.POINTER(C.c_uint8), C.c_int]
+    lib.stmpc_pop_per_enable_td3.argtypes = [vp, C.POINTER(PERCfg), C.POINTER(C.c_uint8), C.c_int]
     lib.stmpc_actor_view_ddpg.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_destroy.argtypes = [vp]
@@ -1034,6 +1037,20 @@ class Context:
 
     def per_last(self, handle, d_idx, d_td, d_weight, stream=0):
         self._chk(self._lib.stmpc_per_last_device(handle, d_idx, d_td, d_weight, stream))
+
+    # -- prioritised replay for the populations (stmpc_pop_per_*): once per population, on empty rings ------------------------
+    @staticmethod
+    def _per_table(cfgs):
+        """``cfgs``: one ``PERCfg`` or None per member -> (PERCfg [P], uint8 [P], P); a None member keeps sampling uniformly."""
+        P = len(cfgs)
+        arr = (PERCfg * P)(*[c if c is not None else PERCfg() for c in cfgs])
+        return arr, (C.c_uint8 * P)(*[int(c is not None) for c in cfgs]), P
+
+    def ddpg_pop_per_enable(self, handle, cfgs):
+        self._chk(self._lib.stmpc_pop_per_enable_ddpg(handle, *self._per_table(cfgs)))
+
+    def td3_pop_per_enable(self, handle, cfgs):
+        self._chk(self._lib.stmpc_pop_per_enable_td3(handle, *self._per_table(cfgs)))
 
     # -- TD3 learner (stmpc_td3_*): a DDPG learner as base plus critic 2 ------------------------
     def td3_create(self, cfg):

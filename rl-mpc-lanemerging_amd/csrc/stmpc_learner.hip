@@ -1,4 +1,4 @@
-// stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), the TD3 learner on top of it and its population (stmpc_td3_*, stmpc_pop_td3_*), prioritised replay for the two lone learners (stmpc_per_*), actors that view a learner's networks
+// stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), the TD3 learner on top of it and its population (stmpc_td3_*, stmpc_pop_td3_*), prioritised replay for the two lone learners (stmpc_per_*) and for the two populations (stmpc_pop_per_*), actors that view a learner's networks
 // (stmpc_actor_view_ddpg) and the population of actors (stmpc_actor_pop_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
@@ -6,6 +6,7 @@
 #include "stmpc_ddpg_pop_kernels.hpp"
 #include "stmpc_td3_kernels.hpp"
 #include "stmpc_td3_pop_kernels.hpp"
+#include "stmpc_per_pop_kernels.hpp"
 #include "stmpc_actor_pop_kernels.hpp"
 
 // ---- DDPG learner (stmpc_ddpg_*): replay ring, fused update, acting; kernels in stmpc_ddpg_kernels.hpp -------------------------------------------
@@ -19,7 +20,7 @@ struct stmpc_ddpg {
     bool td3_base = false;          // lent by a stmpc_td3 (stmpc_td3_base): an update or gradients of this handle alone would leave critic 2 behind
     struct stmpc_td3 *td3_owner = nullptr;  // that stmpc_td3: it holds copies of dev (its two views), which stmpc_per_enable has to follow
     bool pop_member = false;        // owned by a population, whose device table holds a copy of dev
-    bool per = false;               // prioritised replay (stmpc_per_enable): dev.tree ... dev.per_L are set
+    bool per = false;               // prioritised replay (stmpc_per_enable, stmpc_pop_per_enable_*): dev.tree ... dev.per_L are set
     DevBuf per_tree, per_idx, per_aw, per_atd, per_atd2;    // (per_atd2: critic 2's Q - y, when td3_owner)
     int n_in(int which) const { return cfg.n_obs + 1 + which; }
     int64_t slot_len(int which) const { const int64_t n = n_in(which); return (int64_t)cfg.h1 * n + cfg.h1 + (int64_t)cfg.h2 * cfg.h1 + cfg.h2 + cfg.h2 + 1; }
@@ -297,7 +298,8 @@ double stmpc_ddpg_noise(uint64_t seed, uint64_t call, uint32_t row, uint32_t *dr
 struct stmpc_ddpg_pop {
     int device = 0;
     std::vector<stmpc_ddpg *> members;      // owned; made by stmpc_ddpg_create, so every single-learner entry works on a borrowed member
-    DevBuf table;                           // DdpgDev [P]: the members' structs (their pointers and constants never change after create)
+    DevBuf table;                           // DdpgDev [P]: the members' structs (their pointers and constants change once at most: stmpc_pop_per_enable_ddpg)
+    bool per_called = false, per_any = false;   // stmpc_pop_per_enable_ddpg was called; at least one member has a tree
     int P() const { return (int)members.size(); }
     const DdpgDev *dev() const { return table.as<DdpgDev>(); }
 };
@@ -407,9 +409,11 @@ int stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *p, int n_updates, const double 
     const stmpc_ddpg *l = p->members[0];
     const int P = p->P(), tiles = l->Bp / AT_TM, t1 = l->h2p / 16, t0 = l->h1p / 16, jobs = t1 * t0 + 2 * t0 + t1 + t0 + t1 + 1, ablocks = (l->np + 255) / 256;
     hipStream_t st = (hipStream_t)stream;
-    for (int u = 0; u < n_updates; ++u) {                            // stmpc_ddpg_update_device's six launches, each over the members
+    for (int u = 0; u < n_updates; ++u) {                            // stmpc_ddpg_update_device's six launches (eight with prioritised members), each over the members
+        if (p->per_any) hipLaunchKernelGGL(k_per_sample_pop, dim3(1, P), dim3(PER_THREADS), 0, st, p->dev(), l->cfg.batch, l->Bp, 1);
         hipLaunchKernelGGL(k_ddpg_critic_fwd_pop, dim3(tiles, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
         hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 1, l->Bp, 1);
+        if (p->per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, p->dev(), l->cfg.batch, 1);
         hipLaunchKernelGGL(k_ddpg_adam_pop, dim3(ablocks, P), dim3(256), 0, st, p->dev(), 1, lq, 0, 0, 1);
         hipLaunchKernelGGL(k_ddpg_actor_fwd_pop, dim3(tiles, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
         hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 0, l->Bp, 1);
@@ -615,20 +619,25 @@ double stmpc_td3_noise(uint64_t seed, uint64_t update, uint32_t row, uint32_t *d
 }  // extern "C"
 
 // ---- prioritised replay (stmpc_per_*) for a lone DDPG learner or a lone TD3 learner's base; kernels in stmpc_per_kernels.hpp ----------------------
-extern "C" {
-
-int stmpc_per_enable(stmpc_ddpg *l, const stmpc_per_cfg *g) {
-    if (!l || !g) return fail(STMPC_EINVAL, "NULL argument");
+namespace {
+int per_check_cfg(const stmpc_per_cfg *g) {
     if (!(g->min_priority > 0) || !(g->max_priority >= g->min_priority) || !std::isfinite(g->max_priority) || !(g->alpha >= 0) || !std::isfinite(g->alpha) ||
         !(g->beta >= 0) || !std::isfinite(g->beta))
         return fail(STMPC_EINVAL, "prioritised replay needs min_priority > 0, max_priority >= min_priority, alpha >= 0 and beta >= 0, all finite");
-    if (l->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: populations sample uniformly");
+    return STMPC_OK;
+}
+// not enabled yet, and the ring empty (synchronises)
+int per_check_ring(stmpc_ddpg *l) {
     if (l->per) return fail(STMPC_EINVAL, "prioritised replay is already enabled on this learner");
     HIPCHK(hipSetDevice(l->device));
     HIPCHK(hipDeviceSynchronize());
     long long cn[DG_NCNT];
     HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
     if (cn[DG_FILL] != 0 || cn[DG_CURSOR] != 0) return fail(STMPC_EINVAL, "prioritised replay can be enabled on an empty ring only (fill is " + std::to_string(cn[DG_FILL]) + ")");
+    return STMPC_OK;
+}
+// the tree, idx, weights and td buffers of a learner that passed both checks, and the fields of its host structs (a TD3 learner's base: of both views too)
+int per_attach(stmpc_ddpg *l, const stmpc_per_cfg *g) {
     long long leaves = 1;
     while (leaves < l->cfg.capacity) leaves <<= 1;
     const size_t Bp = (size_t)l->Bp;
@@ -648,6 +657,17 @@ int stmpc_per_enable(stmpc_ddpg *l, const stmpc_per_cfg *g) {
     }
     l->per = true;
     return STMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_per_enable(stmpc_ddpg *l, const stmpc_per_cfg *g) {
+    if (!l || !g) return fail(STMPC_EINVAL, "NULL argument");
+    TRY(per_check_cfg(g));
+    if (l->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: prioritised replay is enabled on the population (stmpc_pop_per_enable_ddpg / _td3)");
+    TRY(per_check_ring(l));
+    return per_attach(l, g);
 }
 
 int stmpc_per_tree_read(stmpc_ddpg *l, int64_t first, int64_t count, double *nodes) {
@@ -682,6 +702,7 @@ struct stmpc_td3_pop {
     int device = 0;
     std::vector<stmpc_td3 *> members;       // owned; made by stmpc_td3_create, so every single-learner entry works on a borrowed member (and on its base)
     DevBuf table, bases;                    // Td3Dev [P]: the members' structs; DdpgDev [P]: their bases' (v[0]), for k_ddpg_act_pop / k_replay_push_pop
+    bool per_called = false, per_any = false;   // stmpc_pop_per_enable_td3 was called; at least one member has a tree
     int P() const { return (int)members.size(); }
     const Td3Dev *dev() const { return table.as<Td3Dev>(); }
     const DdpgDev *base_dev() const { return bases.as<DdpgDev>(); }
@@ -772,9 +793,11 @@ int stmpc_pop_td3_update_device(stmpc_td3_pop *p, int n_updates, const double *l
     const Td3Grid g = td3_grid(l);
     const int P = p->P();
     hipStream_t st = (hipStream_t)stream;
-    for (int u = 0; u < n_updates; ++u) {                            // stmpc_td3_update_device's six launches, each over the members in gridDim.z
+    for (int u = 0; u < n_updates; ++u) {                            // stmpc_td3_update_device's six launches (eight with prioritised members), each over the members in gridDim.z
+        if (p->per_any) hipLaunchKernelGGL(k_per_sample_td3_pop, dim3(1, 1, P), dim3(PER_THREADS), 0, st, p->dev(), l->cfg.batch, l->Bp, 1);
         hipLaunchKernelGGL(k_td3_critic_fwd_pop, dim3(g.tiles, 2, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
         hipLaunchKernelGGL(k_td3_wgrad_pop, dim3(g.jobs, 2, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 1, l->Bp, 1);
+        if (p->per_any) hipLaunchKernelGGL(k_per_update_td3_pop, dim3(1, 1, P), dim3(PER_THREADS), 0, st, p->dev(), l->cfg.batch, 1);
         hipLaunchKernelGGL(k_td3_adam_critics_pop, dim3(g.ablocks, 2, P), dim3(256), 0, st, p->dev(), lq, 1);
         hipLaunchKernelGGL(k_td3_actor_fwd_pop, dim3(g.tiles, 1, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
         hipLaunchKernelGGL(k_td3_wgrad_pop, dim3(g.jobs, 1, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 0, l->Bp, 1);
@@ -790,6 +813,63 @@ int stmpc_pop_td3_stats_device(stmpc_td3_pop *p, double *d_out, void *stream) {
     hipLaunchKernelGGL(k_td3_stats_pop, dim3(1, 1, p->P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->members[0]->base->cfg.batch, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- prioritised replay for the populations (stmpc_pop_per_*): stmpc_per_enable's work per member, then the device tables anew; kernels in
+// stmpc_per_pop_kernels.hpp -----------------------------------------------------------------------------------------------------------------------
+namespace {
+// the checks both entries share (bases[m]: member m's stmpc_ddpg): stmpc_per_enable's, on every enabled member, before anything is attached
+int pop_per_check(const std::vector<stmpc_ddpg *> &bases, bool called, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
+    if (!cfgs || !enabled) return fail(STMPC_EINVAL, "NULL argument");
+    if (P != (int)bases.size()) return fail(STMPC_EINVAL, "cfgs and enabled have " + std::to_string(P) + " entries, the population " + std::to_string(bases.size()) + " members");
+    if (called) return fail(STMPC_EINVAL, "prioritised replay was already set up on this population (one call, on empty rings)");
+    for (int m = 0; m < P; ++m)
+        if (enabled[m]) { TRY(per_check_cfg(cfgs + m)); TRY(per_check_ring(bases[m])); }
+    return STMPC_OK;
+}
+// per_attach on every enabled member; an allocation that fails leaves the members before it prioritised, which the tables then say too
+int pop_per_attach(const std::vector<stmpc_ddpg *> &bases, const stmpc_per_cfg *cfgs, const uint8_t *enabled, bool &any) {
+    int rc = STMPC_OK;
+    for (size_t m = 0; m < bases.size() && !rc; ++m)
+        if (enabled[m]) { rc = per_attach(bases[m], cfgs + m); any = any || !rc; }
+    return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_pop_per_enable_ddpg(stmpc_ddpg_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    TRY(pop_per_check(p->members, p->per_called, cfgs, enabled, P));
+    p->per_called = true;
+    const int rc = pop_per_attach(p->members, cfgs, enabled, p->per_any);
+    if (!p->per_any) return rc;                                     // (no member enabled: the table stands)
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<DdpgDev> host;
+    for (const stmpc_ddpg *l : p->members) host.push_back(l->dev);
+    HIPCHK(hipMemcpy(p->table.p, host.data(), host.size() * sizeof(DdpgDev), hipMemcpyHostToDevice));
+    return rc;
+}
+
+int stmpc_pop_per_enable_td3(stmpc_td3_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    std::vector<stmpc_ddpg *> bases_of;
+    for (const stmpc_td3 *t : p->members) bases_of.push_back(t->base);
+    TRY(pop_per_check(bases_of, p->per_called, cfgs, enabled, P));
+    p->per_called = true;
+    const int rc = pop_per_attach(bases_of, cfgs, enabled, p->per_any);
+    if (!p->per_any) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<Td3Dev> host;
+    std::vector<DdpgDev> base;
+    for (const stmpc_td3 *t : p->members) { host.push_back(t->dev); base.push_back(t->dev.v[0]); }
+    HIPCHK(hipMemcpy(p->table.p, host.data(), host.size() * sizeof(Td3Dev), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->bases.p, base.data(), base.size() * sizeof(DdpgDev), hipMemcpyHostToDevice));
+    return rc;
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@
 //                   critic pass left in atd (TD3: the larger of both critics' |td|); of rows with the same index the highest wins (the reference's
 //                   loop order; B^2 / 2 comparisons in LDS); then the B paths' ancestors level by level
 // A descent is about log2(L) dependent fp64 loads; these kernels are latency chains, not throughput kernels.  Both are gated like the update.
+// Each kernel's text is a __device__ body taking the learner's struct by reference (per_sample_body, per_update_body); the __global__ entries here pass
+// their by-value argument, the populations' entries (stmpc_per_pop_kernels.hpp) a row of a device table.
 // The gathers of the update read idx[] instead of hashing (DdpgDev::idx != null), because the priorities change between the critic and the actor pass.
 #pragma once
 #include "stmpc_ddpg_kernels.hpp"
@@ -73,9 +75,10 @@ __device__ __forceinline__ void per_push_tree(const DdpgDev &L, long long cursor
     }
 }
 
-__global__ void __launch_bounds__(PER_THREADS) k_per_sample(DdpgDev L, int B, int Bp, int gate) {
+// (every thread of ONE workgroup calls it; red: PER_THREADS doubles of LDS.  The returns are workgroup-uniform -- the gate reads the learner's counters,
+// beta is a constant of the learner -- and the first of them precedes the first barrier)
+__device__ __forceinline__ void per_sample_body(const DdpgDev &L, int B, int Bp, int gate, double *red) {
     if (!ddpg_gate(L, gate)) return;
-    __shared__ double red[PER_THREADS];
     const int tid = threadIdx.x;
     const long long fill = L.cnt[DG_FILL], upd = L.cnt[DG_UPDATES], nl = L.per_L;
     const double *tree = L.tree;
@@ -109,6 +112,10 @@ __global__ void __launch_bounds__(PER_THREADS) k_per_sample(DdpgDev L, int B, in
         L.aw[r] = w;
     }
 }
+__global__ void __launch_bounds__(PER_THREADS) k_per_sample(DdpgDev L, int B, int Bp, int gate) {
+    __shared__ double red[PER_THREADS];
+    per_sample_body(L, B, Bp, gate, red);
+}
 
 // the td of row r that sets its priority: view 0's, or critic 2's where that is larger in magnitude (atd2 null: DDPG)
 __device__ __forceinline__ float per_td(const DdpgDev &L, const float *atd2, int r) {
@@ -120,9 +127,10 @@ __device__ __forceinline__ float per_td(const DdpgDev &L, const float *atd2, int
 
 constexpr int PER_MAX_B = 8192;     // stmpc_ddpg_create's largest batch
 
-__global__ void __launch_bounds__(PER_THREADS) k_per_update(DdpgDev L, const float *atd2, int B, int gate) {
+// (every thread of ONE workgroup calls it; idx_s: PER_MAX_B ints of LDS; atd2: critic 2's Q - y, null for DDPG.  The return is workgroup-uniform and
+// precedes the first barrier)
+__device__ __forceinline__ void per_update_body(const DdpgDev &L, const float *atd2, int B, int gate, int *idx_s) {
     if (!ddpg_gate(L, gate)) return;
-    __shared__ int idx_s[PER_MAX_B];
     const int tid = threadIdx.x;
     double *tree = L.tree;
     const long long nl = L.per_L;
@@ -143,6 +151,10 @@ __global__ void __launch_bounds__(PER_THREADS) k_per_update(DdpgDev L, const flo
             tree[i] = tree[2 * i + 1] + tree[2 * i + 2];
         }
     }
+}
+__global__ void __launch_bounds__(PER_THREADS) k_per_update(DdpgDev L, const float *atd2, int B, int gate) {
+    __shared__ int idx_s[PER_MAX_B];
+    per_update_body(L, atd2, B, gate, idx_s);
 }
 
 // what the last sampling step and critic pass left: idx int64 [B], td float32 [B] (per_td), weight float32 [B]

@@ -30,8 +30,11 @@ Prioritised replay (``DDPGConfig(per=PERConfig())``, ``csrc/stmpc_per_kernels.hp
 drawing minibatches (dqn.py:267-349, ``SumTree`` dqn.py:727-794; ``USE_PRIORITIZED_ER = True`` in config.py) for ``DDPGLearner`` and ``TD3Learner``:
 rows are drawn from a sum tree in proportion to ``min(|td| + min_priority, max_priority) ** alpha`` of their last critic error, new rows enter at
 ``max_priority ** alpha``, and the critic's loss carries the importance weights ``(fill * p / total) ** -beta`` over their largest (``beta`` 0, the
-reference's: none).  Two launches more per update; populations sample uniformly.  Twins: ``SumTreeHost``, ``per_sample_host``, ``per_priority_host``,
-``per_weights_host`` and the ``weights=`` argument of ``update_host`` / ``update_host_td3``.
+reference's: none).  Two launches more per update.  Twins: ``SumTreeHost``, ``per_sample_host``, ``per_priority_host``, ``per_weights_host`` and the
+``weights=`` argument of ``update_host`` / ``update_host_td3``.  A population takes ``per=`` itself (``DDPGPopulation(..., per=...)``,
+``TD3Population`` likewise; ``csrc/stmpc_per_pop_kernels.hpp``, ``stmpc_pop_per_*``): one ``PERConfig`` for all members or one per member, None for a
+member that samples uniformly -- prioritised against uniform replay, or a sweep of alpha and beta, in one launch sequence of eight launches per update,
+every member bit-identical to the lone learner with that ``cfg.per``.
 """
 import math
 
@@ -438,7 +441,7 @@ class DDPGLearner:
         self.seed = int(seed)
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.handle = self._make_handle()
-        if self.cfg.per is not None:                                # (a population member's handle refuses: populations sample uniformly)
+        if self.cfg.per is not None:                                # (a population member's handle refuses: the population enables its members)
             self.ctx.per_enable(self.handle, self.cfg.per.to_c())
         c = self.cfg
         rng = np.random.default_rng(self.seed)
@@ -691,7 +694,14 @@ class DDPGPopulation:
     ``n_per_member == env.n_per_reward_group``): member m's slice is reward group m, so member m trains under reward m -- the reference's
     reward-shaping comparison, one ``TRAIN_DDPG`` run per config, in one launch sequence -- and stays bit-identical to a lone learner fed that
     slice of the lone env made under reward m.  Nothing else changes: the population reads the env's reward tensor row by row.
-    ``evaluate_members`` / ``episodes.summary_by_member`` then compare the policies the rewards produced on one common report."""
+    ``evaluate_members`` / ``episodes.summary_by_member`` then compare the policies the rewards produced on one common report.
+
+    ``per``: prioritised replay (module text) -- None, one ``PERConfig`` for every member, or a list of P entries, each a ``PERConfig`` or None
+    (that member samples uniformly).  It is the population's argument, not the members' cfgs' (a cfg with ``per=`` is refused): the population
+    enables its members' trees in one call before anything is pushed.  ``self.per`` is the per-member list.  A prioritised member is
+    bit-identical to ``DDPGLearner(cfg with per=...)`` on its slice, a uniform one to the member of a population without ``per``; one update is
+    eight launches whatever P is (six when no member is prioritised).  ``member(m).priorities()`` / ``.last_sample()`` read member m's tree and
+    last minibatch (they raise on a uniform member)."""
 
     _api, _nstat = "ddpg_pop", 4                                    # the binding's entries (ctx.<_api>_create, ...) and the width of a stats row
 
@@ -704,15 +714,25 @@ class DDPGPopulation:
     def _make_member(self, m, env, init):
         return _PopulationMember(self, m, env, self.cfgs[m], self.seeds[m], init)
 
-    def __init__(self, env, cfgs, seeds=None, init=None, ctx=None):
+    def __init__(self, env, cfgs, seeds=None, init=None, ctx=None, per=None):
         if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], DDPGConfig):
             cfgs = [cfgs[0]] * int(cfgs[1])
         self.cfgs = list(cfgs)
         P = self.P = len(self.cfgs)
         for m, c in enumerate(self.cfgs):
             if getattr(c, "per", None) is not None:
-                raise ValueError("member %d's cfg asks for prioritised replay (per=): a population's members sample uniformly; train that member as a lone "
-                                 "learner" % m)
+                raise ValueError("member %d's cfg asks for prioritised replay (per=): a population enables it for its members itself; give the "
+                                 "PERConfig to the population's per= argument (one for all members, or a list with one entry per member)" % m)
+        if per is None or isinstance(per, PERConfig):
+            per = [per] * P
+        elif not isinstance(per, (list, tuple)):
+            raise ValueError("per must be None, a PERConfig, or a list with a PERConfig or None per member")
+        self.per = list(per)
+        if len(self.per) != P:
+            raise ValueError("per has %d entries, the population %d members" % (len(self.per), P))
+        for m, g in enumerate(self.per):
+            if g is not None and not isinstance(g, PERConfig):
+                raise ValueError("per[%d] is a %s, not a PERConfig or None" % (m, type(g).__name__))
         if not env.continuous:
             raise ValueError("DDPG needs the continuous action space (sumo-jerk-continuous-v0)")
         # (a member count outside 1 ... DDPG_POP_MAX is the library's to refuse)
@@ -737,6 +757,8 @@ class DDPGPopulation:
         self.ctx = ctx if ctx is not None else env.ctx
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.handle = self._create_handle()
+        if any(g is not None for g in self.per):                    # (the rings are empty: nothing was pushed yet)
+            self._call("per_enable")(self.handle, [g.to_c() if g is not None else None for g in self.per])
         self._members = [self._make_member(m, env, inits[m]) for m in range(P)]
         self._lr_q, self._lr_pi = np.array([c.lr_q for c in self.cfgs]), np.array([c.lr_pi for c in self.cfgs])
         self._stats = torch.zeros(P, self._nstat, dtype=torch.float64, device=self.device)
@@ -789,7 +811,7 @@ class DDPGPopulation:
         return np.full(self.P, float(lr)) if lr.ndim == 0 else lr       # (the library checks a given array's length)
 
     def update(self, n=1, lr_q=None, lr_pi=None):
-        """``n`` updates of every member, six launches each; a member whose replay_start gate is still shut skips its own.  ``lr_q`` / ``lr_pi``:
+        """``n`` updates of every member, six launches each (eight with prioritised members); a member whose replay_start gate is still shut skips its own.  ``lr_q`` / ``lr_pi``:
         a scalar or one value per member (default: each member's cfg's)."""
         self._call("update")(self.handle, n, self._lr(lr_q, self._lr_q), self._lr(lr_pi, self._lr_pi), self._stream())
 
@@ -836,11 +858,12 @@ class TD3Population(DDPGPopulation):
     ``act`` / ``push`` / ``update`` and what ``DDPGPopulation`` says about traffic and reward groups hold unchanged; ``stats_device`` is fp64 [P][6]
     and ``stats`` has the keys of ``TD3Learner.stats_td3``; ``member(m)`` is a ``TD3Learner`` view (``grads``, ``targets``, ``stats_td3``,
     ``state_dict`` / ``load_state_dict`` with all twelve slots and six beta powers, ``export_actor``).  ``train_ddpg``, ``evaluate_members`` and
-    ``actor.ActorPopulation`` take it as they take a ``DDPGPopulation``."""
+    ``actor.ActorPopulation`` take it as they take a ``DDPGPopulation``.  ``per``: as ``DDPGPopulation``'s; a prioritised member's priorities follow
+    the critic with the larger error, as ``TD3Learner``'s do."""
 
     _api, _nstat = "td3_pop", 6
 
-    def __init__(self, env, cfgs, seeds=None, init=None, ctx=None):
+    def __init__(self, env, cfgs, seeds=None, init=None, ctx=None, per=None):
         if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], DDPGConfig):
             cfgs = [cfgs[0]] * int(cfgs[1])
         cfgs = list(cfgs)
@@ -850,7 +873,7 @@ class TD3Population(DDPGPopulation):
                                  "noise_clip or policy_delay)" % (m, type(c).__name__))
         if _is_net_triple(init):                                    # one triple for every member, not a list of three members
             init = [init] * len(cfgs)
-        super().__init__(env, cfgs, seeds=seeds, init=init, ctx=ctx)
+        super().__init__(env, cfgs, seeds=seeds, init=init, ctx=ctx, per=per)
 
     def _create_handle(self):
         return self._call("create")([c.to_c_td3(s) for c, s in zip(self.cfgs, self.seeds)])
