@@ -792,6 +792,83 @@ int  stmpc_pop_per_enable_ddpg(stmpc_ddpg_pop *pop, const stmpc_per_cfg *cfgs, c
 int  stmpc_pop_per_enable_td3(stmpc_td3_pop *pop, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P);
 
 /*
+ * DQN learner on the device for the discrete-action environments (STMPC_ENV_JERK, STMPC_ENV_ACCELERATION): the reference's hand-written trainer
+ * (TRAIN_DQN: DQNAgent._train dqn.py:257-359, get_targets dqn.py:673-705, the DQN module dqn.py:566-658), restated.  (Additive: new entries only, no
+ * signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8; no entry above changes what it computes.)  The Q-network is n_obs -> h1 ->
+ * ReLU -> n_actions, float32, the one shape the reference trains; there is no time feature.  The replay ring, its counters, the minibatch indices
+ * and prioritised replay are the DDPG learner's (rows of STMPC_DDPG_ROW float32: [0, 32) s, [32, 64) s', [64] reward, [65] mask, [66] the action
+ * index).  Per update, on a minibatch of `batch` rows:
+ *   double_dqn: a* = the first argmax of Q(s') (the online network), t = Q_target(s')[a*]; else t = max_a Q_target(s')[a];
+ *   g = gamma * t, clipped to [clip_min, clip_max] if clip_targets;  y = r + g, and r alone where the episode terminated (mask = 0);
+ *   Adam step on mean_r(w_r * smooth_l1(Q(s_r)[a_r] - y_r)), smooth_l1 with beta 1 (nn.SmoothL1Loss), w = 1 or prioritised replay's weights;
+ *   after the step, if the number of updates done is a multiple of target_period: Q_target <- Q (a hard copy).
+ * Three launches per update (five with prioritised replay) whose shapes depend on (batch, h1, n_actions) alone; every counter lives on the device
+ * and no entry with a `stream` synchronises, so act -> step -> push -> updates may be captured as one single-stream graph.
+ *   create          STMPC_EINVAL for n_actions outside 1 ... STMPC_ENV_MAX_ACTIONS, n_obs outside 1 ... 31, h1 outside 1 ... 1024, batch outside
+ *                   1 ... 8192, target_period < 1, capacity < 1, replay_start outside 0 ... capacity - 1, constants out of range.  Parameters start at zero
+ *   set / get_params  HOST float32, one slot at a time: STMPC_DQN_Q, _Q_TARGET, _Q_M, _Q_V (Adam's moments); a slot is W0 [h1][n_obs] | b0 [h1] |
+ *                   W1 [n_actions][h1] | b1 [n_actions], row-major as torch stores them; `count` must be that length.  Synchronise
+ *   set / get_state   HOST: counters int64 [STMPC_DDPG_NCOUNTERS] (ring cursor, fill, updates done, exploring acting calls, frames pushed, 0, 0, 0)
+ *                   and Adam's running beta powers float32 [2].  Synchronise.  With prioritised replay the cursor and the fill cannot be moved
+ *   push_device     as the DDPG learner's without ticks; d_action int32 [N], the indices given to the environment's step (an index outside
+ *                   0 ... n_actions - 1, which the environment latches as out of range, is stored clamped)
+ *   act_device      d_action int32 [N]: the first maximum of Q(obs) over the n_actions columns.  eps in 0 ... 1 (else STMPC_EINVAL); eps > 0 is an
+ *                   exploring call: one hash per (seed, exploring calls so far, row); its top 24 bits / 2^24 are u, and where u < (float)eps the
+ *                   action is the hash's next 24 bits modulo n_actions.  The call counter advances on the device.  d_debug_q (may be NULL)
+ *                   float32 [N][n_actions]: Q(obs)
+ *   update_device   n_updates updates with learning rate lr; does nothing (on the device) until more than replay_start frames were pushed
+ *   grads_device    debug: the loss's gradient on the minibatch of the current update index (DEVICE float32, slot layout); nothing applied, no gate
+ *   targets_device  debug: DEVICE float32 [batch][4] = a* (without double_dqn: the maximum's index), the target network's Q there, y, Q(s, a)
+ *   gather_device   the minibatch of the current update index, DEVICE [batch][STMPC_DDPG_ROW];  stats_device: DEVICE fp64 [4]: the loss (unweighted
+ *                   mean) and mean Q(s, a) of the last minibatch, fill, updates done
+ *   padded_read     debug, HOST: a slot as the library keeps it -- W0 [h1p][32] | b0 [h1p] | W1 [Ap][h1p] | b1 [Ap], h1p and Ap the next multiples of
+ *                   16 -- so that the pad rows and columns can be seen; slots STMPC_DQN_Q ... _Q_V, and STMPC_DQN_GRAD: the last gradient.
+ *                   `count` must be 33 h1p + (h1p + 1) Ap.  Synchronises
+ *   per_enable, per_tree_read, per_last_device   prioritised replay as stmpc_per_enable and its two readers provide it, on this learner's ring: the
+ *                   sampling step in front of the pass, the weights on the loss, the priorities from this pass's own Q(s, a) - y, new rows at
+ *                   max_priority ^ alpha
+ */
+#define STMPC_DQN_Q 0
+#define STMPC_DQN_Q_TARGET 1
+#define STMPC_DQN_Q_M 2
+#define STMPC_DQN_Q_V 3
+#define STMPC_DQN_GRAD 4                  /* padded_read only */
+typedef struct stmpc_dqn_cfg {
+    int32_t n_obs;                   /* observation entries (20 for the shipped settings; <= 31) */
+    int32_t h1;                      /* hidden width (256; <= 1024) */
+    int32_t n_actions;               /* A: 1 ... STMPC_ENV_MAX_ACTIONS (5: JERK_VALUES_DQN; 20: ACCELERATION_VALUES_DQN) */
+    int32_t batch;                   /* minibatch rows B, 1 ... 8192 (BATCH_SIZE 50) */
+    int32_t capacity;                /* replay rows (REPLAY_BUFFER_SIZE 50000) */
+    int32_t target_period;           /* the target is copied on every target_period-th update (TARGET_NET_FREEZE_PERIOD 500); >= 1 */
+    int32_t double_dqn;              /* DOUBLE_DQN (1) */
+    int32_t clip_targets;            /* CLIP_TARGETS */
+    int64_t replay_start;            /* updates start once MORE than this many frames were pushed; < capacity */
+    uint64_t seed;                   /* of the minibatch indices and the exploration draws */
+    double gamma;                    /* DISCOUNT_FACTOR (0.999) */
+    double beta1, beta2, eps;        /* Adam: 0.9, 0.999, 1e-8 (optim.Adam's defaults) */
+    double clip_min, clip_max;       /* CLIP_MIN_REWARD, CLIP_MAX_REWARD (-20, 10) */
+} stmpc_dqn_cfg;
+typedef struct stmpc_dqn stmpc_dqn;
+int  stmpc_dqn_create(stmpc_ctx *ctx, const stmpc_dqn_cfg *cfg, stmpc_dqn **out);
+void stmpc_dqn_destroy(stmpc_dqn *learner);
+int  stmpc_dqn_set_params(stmpc_dqn *learner, int slot, const float *values, int64_t count);
+int  stmpc_dqn_get_params(stmpc_dqn *learner, int slot, float *values, int64_t count);
+int  stmpc_dqn_set_state(stmpc_dqn *learner, const int64_t *counters, const float *beta_pow);
+int  stmpc_dqn_get_state(stmpc_dqn *learner, int64_t *counters, float *beta_pow);
+int  stmpc_dqn_push_device(stmpc_dqn *learner, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                           const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream);
+int  stmpc_dqn_act_device(stmpc_dqn *learner, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream);
+int  stmpc_dqn_update_device(stmpc_dqn *learner, int n_updates, double lr, void *stream);
+int  stmpc_dqn_grads_device(stmpc_dqn *learner, float *d_grad, void *stream);
+int  stmpc_dqn_targets_device(stmpc_dqn *learner, float *d_out, void *stream);
+int  stmpc_dqn_gather_device(stmpc_dqn *learner, float *d_rows, void *stream);
+int  stmpc_dqn_stats_device(stmpc_dqn *learner, double *d_out, void *stream);
+int  stmpc_dqn_per_enable(stmpc_dqn *learner, const stmpc_per_cfg *cfg);
+int  stmpc_dqn_per_tree_read(stmpc_dqn *learner, int64_t first, int64_t count, double *nodes);
+int  stmpc_dqn_per_last_device(stmpc_dqn *learner, int64_t *d_idx, float *d_td, float *d_weight, void *stream);
+int  stmpc_dqn_padded_read(stmpc_dqn *learner, int slot, float *values, int64_t count);
+
+/*
  * Actors straight from learners, and a population of actors evaluated in one launch.  The reference's workflow ends a training with an evaluation
  * of the model it trained (ddpg.train_ddpg_all_with_lr_drop's closing `evaluate`, ddpg.py:96-117) and publishes a matrix of EVALUATE_COMBINED_DDPG runs, one per
  * MODEL_NAME (DDPGAgent.load + get_control, ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json, experiment_data/saved_data.csv).  (Additive: new

@@ -251,6 +251,13 @@ class PERCfg(C.Structure):
     _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("min_priority", C.c_double), ("max_priority", C.c_double)]
 
 
+class DQNCfg(C.Structure):
+    """``stmpc_dqn_cfg`` (include/stmpc.h): the Q-network's shape, the replay size and the constants of the DQN update (defaults: the reference's config.py)."""
+    _fields_ = [("n_obs", C.c_int32), ("h1", C.c_int32), ("n_actions", C.c_int32), ("batch", C.c_int32), ("capacity", C.c_int32), ("target_period", C.c_int32),
+                ("double_dqn", C.c_int32), ("clip_targets", C.c_int32), ("replay_start", C.c_int64), ("seed", C.c_uint64), ("gamma", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("clip_min", C.c_double), ("clip_max", C.c_double)]
+
+
 class ProfileTotals(C.Structure):
     _fields_ = [("launches", C.c_int64), ("episodes", C.c_int64), ("solve_ms", C.c_double), ("dp_kernel_ms", C.c_double)]
 
@@ -282,6 +289,10 @@ EXPORTS = (
     "stmpc_pop_td3_push_device", "stmpc_pop_td3_update_device", "stmpc_pop_td3_stats_device",
     "stmpc_per_enable", "stmpc_per_tree_read", "stmpc_per_last_device", "stmpc_per_sample_index",
     "stmpc_pop_per_enable_ddpg", "stmpc_pop_per_enable_td3",
+    "stmpc_dqn_create", "stmpc_dqn_destroy", "stmpc_dqn_set_params", "stmpc_dqn_get_params", "stmpc_dqn_set_state", "stmpc_dqn_get_state",
+    "stmpc_dqn_push_device", "stmpc_dqn_act_device", "stmpc_dqn_update_device", "stmpc_dqn_grads_device", "stmpc_dqn_targets_device",
+    "stmpc_dqn_gather_device", "stmpc_dqn_stats_device", "stmpc_dqn_per_enable", "stmpc_dqn_per_tree_read", "stmpc_dqn_per_last_device",
+    "stmpc_dqn_padded_read",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
@@ -307,6 +318,9 @@ SOLVER_GROUPS_MAX = 512               # STMPC_SOLVER_GROUPS_MAX
 ENV_REWARD_GROUPS_MAX = 64            # STMPC_ENV_REWARD_GROUPS_MAX
 TRAFFIC_MIX_MAX = 64                  # STMPC_TRAFFIC_MIX_MAX
 TD3_SLOTS = ("critic2", "critic2_target", "critic2_m", "critic2_v")     # STMPC_TD3_CRITIC2 ... STMPC_TD3_CRITIC2_V
+DQN_SLOTS = ("q", "q_target", "q_m", "q_v")     # STMPC_DQN_Q ... STMPC_DQN_Q_V
+DQN_GRAD = 4                          # STMPC_DQN_GRAD: the gradient, for dqn_padded_read
+DQN_ACTION_COL = 66                   # the replay row's action column of a DQN learner
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
 REC_HDR, REC_NQ, REC_MAX_DEPTH, REC_MAX_EDGES = 10, 4, 64, 32      # STMPC_REC_HDR, STMPC_REC_NQ, STMPC_REC_MAX_DEPTH, STMPC_REC_MAX_EDGES
 REC_COLUMNS = ("tick", "x", "y", "v", "a", "s", "k", "cmd", "takeover", "jerk")      # the first STMPC_REC_HDR columns of a record
@@ -481,6 +495,24 @@ def load():
     lib.stmpc_per_sample_index.restype = C.c_int64
     lib.stmpc_pop_per_enable_ddpg.argtypes = [vp, C.POINTER(PERCfg), C.POINTER(C.c_uint8), C.c_int]
     lib.stmpc_pop_per_enable_td3.argtypes = [vp, C.POINTER(PERCfg), C.POINTER(C.c_uint8), C.c_int]
+    lib.stmpc_dqn_create.argtypes = [vp, C.POINTER(DQNCfg), C.POINTER(vp)]
+    lib.stmpc_dqn_destroy.argtypes = [vp]
+    lib.stmpc_dqn_destroy.restype = None
+    lib.stmpc_dqn_set_params.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_dqn_get_params.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_dqn_set_state.argtypes = [vp, i64p, fp]
+    lib.stmpc_dqn_get_state.argtypes = [vp, i64p, fp]
+    lib.stmpc_dqn_push_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 4 + [vp]
+    lib.stmpc_dqn_act_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, vp, vp, vp]
+    lib.stmpc_dqn_update_device.argtypes = [vp, C.c_int, C.c_double, vp]
+    lib.stmpc_dqn_grads_device.argtypes = [vp, vp, vp]
+    lib.stmpc_dqn_targets_device.argtypes = [vp, vp, vp]
+    lib.stmpc_dqn_gather_device.argtypes = [vp, vp, vp]
+    lib.stmpc_dqn_stats_device.argtypes = [vp, vp, vp]
+    lib.stmpc_dqn_per_enable.argtypes = [vp, C.POINTER(PERCfg)]
+    lib.stmpc_dqn_per_tree_read.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
+    lib.stmpc_dqn_per_last_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.stmpc_dqn_padded_read.argtypes = [vp, C.c_int, fp, C.c_int64]
     lib.stmpc_actor_view_ddpg.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_destroy.argtypes = [vp]
@@ -1051,6 +1083,77 @@ class Context:
 
     def td3_pop_per_enable(self, handle, cfgs):
         self._chk(self._lib.stmpc_pop_per_enable_td3(handle, *self._per_table(cfgs)))
+
+    # -- DQN learner (stmpc_dqn_*): the discrete agent; the handle belongs to this context's device ------------------------
+    def dqn_create(self, cfg):
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_dqn_create(self._h, C.byref(cfg), C.byref(h)))
+        return h
+
+    def dqn_destroy(self, handle):
+        self._lib.stmpc_dqn_destroy(handle)
+
+    def dqn_set_params(self, handle, slot, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        self._chk(self._lib.stmpc_dqn_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+
+    def dqn_get_params(self, handle, slot, count):
+        flat = np.empty(int(count), dtype=np.float32)
+        self._chk(self._lib.stmpc_dqn_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        return flat
+
+    def dqn_set_state(self, handle, counters, beta_pow):
+        cn = np.ascontiguousarray(counters, dtype=np.int64)
+        bp = np.ascontiguousarray(beta_pow, dtype=np.float32)
+        assert cn.size == DDPG_NCOUNTERS and bp.size == 2
+        self._chk(self._lib.stmpc_dqn_set_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def dqn_get_state(self, handle):
+        """(counters int64 [8]: cursor, fill, updates, exploring acting calls, frames, ...; Adam's beta powers float32 [2]); synchronises."""
+        cn, bp = np.zeros(DDPG_NCOUNTERS, dtype=np.int64), np.zeros(2, dtype=np.float32)
+        self._chk(self._lib.stmpc_dqn_get_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
+        return cn, bp
+
+    def dqn_push(self, handle, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
+        self._chk(self._lib.stmpc_dqn_push_device(handle, int(N), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated, d_truncated,
+                                                  stream))
+
+    def dqn_act(self, handle, N, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
+        self._chk(self._lib.stmpc_dqn_act_device(handle, int(N), d_obs, int(obs_stride), float(eps), d_action, d_debug_q, stream))
+
+    def dqn_update(self, handle, n_updates, lr, stream=0):
+        self._chk(self._lib.stmpc_dqn_update_device(handle, int(n_updates), float(lr), stream))
+
+    def dqn_grads(self, handle, d_grad, stream=0):
+        self._chk(self._lib.stmpc_dqn_grads_device(handle, d_grad, stream))
+
+    def dqn_targets(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_dqn_targets_device(handle, d_out, stream))
+
+    def dqn_gather(self, handle, d_rows, stream=0):
+        self._chk(self._lib.stmpc_dqn_gather_device(handle, d_rows, stream))
+
+    def dqn_stats(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_dqn_stats_device(handle, d_out, stream))
+
+    def dqn_per_enable(self, handle, cfg):
+        self._chk(self._lib.stmpc_dqn_per_enable(handle, C.byref(cfg)))
+
+    def dqn_per_tree_read(self, handle, first, count):
+        nodes = np.empty(int(count), dtype=np.float64)
+        self._chk(self._lib.stmpc_dqn_per_tree_read(handle, int(first), int(count), nodes.ctypes.data_as(C.POINTER(C.c_double))))
+        return nodes
+
+    def dqn_per_last(self, handle, d_idx, d_td, d_weight, stream=0):
+        self._chk(self._lib.stmpc_dqn_per_last_device(handle, d_idx, d_td, d_weight, stream))
+
+    def dqn_padded_read(self, handle, slot, h1, n_actions):
+        """Debug: a slot (0 ... 3, or ``DQN_GRAD``) in the library's padded layout as {w0 [h1p][32], b0 [h1p], w1 [Ap][h1p], b1 [Ap]}; synchronises."""
+        h1p, Ap = (int(h1) + 15) & ~15, (int(n_actions) + 15) & ~15
+        flat = np.empty(33 * h1p + (h1p + 1) * Ap, dtype=np.float32)
+        self._chk(self._lib.stmpc_dqn_padded_read(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        o = np.cumsum([0, 32 * h1p, h1p, Ap * h1p, Ap])
+        return {"w0": flat[o[0]:o[1]].reshape(h1p, 32), "b0": flat[o[1]:o[2]], "w1": flat[o[2]:o[3]].reshape(Ap, h1p), "b1": flat[o[3]:o[4]]}
 
     # -- TD3 learner (stmpc_td3_*): a DDPG learner as base plus critic 2 ------------------------
     def td3_create(self, cfg):

@@ -93,6 +93,7 @@ __device__ __forceinline__ long long dg_row_index(const DdpgDev &L, long long up
 __device__ __forceinline__ void per_push_tree(const DdpgDev &L, long long cursor, int N);      // stmpc_per_kernels.hpp
 
 // ---- replay ---------------------------------------------------------------------------------------------------------------------------------
+// (k_dqn_push of stmpc_dqn_kernels.hpp is a sibling of ddpg_push_body with an int32 action column and no time feature: a fix here belongs there too)
 // (every kernel's body is a __device__ function of the learner's struct: the single-learner entry passes its by-value argument, the population
 // entry of stmpc_ddpg_pop_kernels.hpp the member blockIdx.y selects)
 __device__ __forceinline__ void ddpg_push_body(const DdpgDev &L, int N, const float *__restrict__ obs, const float *__restrict__ next_obs, const float *__restrict__ final_obs,
@@ -150,6 +151,7 @@ __global__ void k_replay_gather(DdpgDev L, int B, float *out) {
 // in k order in fp64 (four VALU additions per four MFMAs) and rounded to float32 once, with the bias -- instead of one chain of kp fused multiply-adds.  The replay's rows resemble each other, so a long chain's rounding
 // error repeats from row to row and survives the mean over the minibatch; measured against the float64 twin the short float32 chains are what keeps the
 // gradients within the float32 twin's error (tests/test_learner.py).  Acting keeps actor_layer itself.
+// (dqn_out_layer of stmpc_dqn_kernels.hpp is the BWD = false case without the ReLU, same loops and summation order: a fix here belongs there too)
 template <bool BWD>
 __device__ __forceinline__ void ddpg_layer(const float *in, int in_ld, int kp, const float *packed, const float *bias, float *out, int out_ld, int np) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
@@ -375,6 +377,7 @@ __global__ void __launch_bounds__(AT_THREADS) k_ddpg_actor_fwd(DdpgDev L, int B,
 // ---- weight gradients ---------------------------------------------------------------------------------------------------------------------------
 // One workgroup per 16 x 16 tile of out[i][j] = sum_b Lm[b][i] * Rm[b][j]; an operand with ld = 0 is a vector broadcast over its 16 columns
 // (ones: the bias gradients; dz: the last layer's).  Jobs in blockIdx order: dW1, dW0, db1, db0, dW2, db2.
+// k_dqn_wgrad (stmpc_dqn_kernels.hpp) launches the first four jobs only, its matrix output layer in the place of layer 1: the scalar head's jobs stay LAST.
 __device__ __forceinline__ void ddpg_wgrad_body(const DdpgDev &L, int which, int Bp, int gate, double (*part_s)[256]) {
     if (!ddpg_gate(L, gate)) return;
     const DdpgNet &net = which ? L.q : L.pi;

@@ -1,5 +1,5 @@
 // stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), the TD3 learner on top of it and its population (stmpc_td3_*, stmpc_pop_td3_*), prioritised replay for the two lone learners (stmpc_per_*) and for the two populations (stmpc_pop_per_*), actors that view a learner's networks
-// (stmpc_actor_view_ddpg) and the population of actors (stmpc_actor_pop_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
+// (stmpc_actor_view_ddpg), the population of actors (stmpc_actor_pop_*) and the DQN learner for the discrete envs (stmpc_dqn_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
 #include "stmpc_per_kernels.hpp"
@@ -953,6 +953,277 @@ int stmpc_actor_pop_eval_device(stmpc_ctx *c, const stmpc_actor_pop *p, const st
     hipLaunchKernelGGL(k_actor_eval_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, p->P), dim3(AT_THREADS), p->lds, (hipStream_t)stream, fc, p->dev(), n_per_member, Kmax,
                        d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, d_evals, d_feat, feat_stride, d_jerk);
     HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- DQN learner (stmpc_dqn_*): the discrete agent on the DDPG learner's ring, counters and tree; kernels in stmpc_dqn_kernels.hpp -----------------
+#include "stmpc_dqn_kernels.hpp"
+
+struct stmpc_dqn {
+    stmpc_ddpg base;                        // NOT made by stmpc_ddpg_create and never handed out: its buffers, its dev (ring, counters, tickets, workspace, base.dev.q = the
+                                            // Q-network, h2p = Ap) and the fields the per_ helpers above read (device, cfg.batch, cfg.capacity, Bp, per ...)
+    stmpc_dqn_cfg cfg{};
+    DqnDev dev{};                           // dev.base is a copy of base.dev: made anew after stmpc_dqn_per_enable
+    int Ap = 0, tiles = 0, jobs = 0, ablocks = 0;
+    int64_t slot_len() const { return (int64_t)cfg.h1 * cfg.n_obs + cfg.h1 + (int64_t)cfg.n_actions * cfg.h1 + cfg.n_actions; }
+};
+
+namespace {
+int dqn_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling[2];
+    TRY(raise_dynamic_lds((const void *)k_dqn_fwd, "k_dqn_fwd", ceiling[0], device, lds));
+    return raise_dynamic_lds((const void *)k_dqn_act, "k_dqn_act", ceiling[1], device, lds);
+}
+float *dqn_slot_ptr(stmpc_dqn *t, int slot) {
+    const DdpgNet &n = t->dev.base.q;
+    float *const p[4] = {n.w, n.wt, n.m, n.v};
+    return p[slot];
+}
+// slot layout (unpadded) <-> padded layout, on the host
+void dqn_pad(const stmpc_dqn *t, const float *flat, std::vector<float> &pad, bool to_pad, float *flat_out) {
+    const int h1 = t->cfg.h1, A = t->cfg.n_actions, n_obs = t->cfg.n_obs, h1p = t->base.h1p, Ap = t->Ap;
+    size_t i = 0;
+    auto item = [&](size_t p) { if (to_pad) pad[p] = flat[i]; else flat_out[i] = pad[p]; ++i; };
+    for (int n = 0; n < h1; ++n) for (int k = 0; k < n_obs; ++k) item((size_t)n * AT_KIN + k);
+    for (int n = 0; n < h1; ++n) item((size_t)dg_o_b0(h1p) + n);
+    for (int n = 0; n < A; ++n) for (int k = 0; k < h1; ++k) item((size_t)dg_o_w1(h1p) + (size_t)n * h1p + k);
+    for (int n = 0; n < A; ++n) item((size_t)dg_o_b1(h1p, Ap) + n);
+}
+// the pass and the weight gradients; dbg: stmpc_dqn_targets_device's output
+void dqn_launch_grads(stmpc_dqn *t, int gate, float *dbg, hipStream_t st) {
+    hipLaunchKernelGGL(k_dqn_fwd, dim3(t->tiles), dim3(AT_THREADS), t->base.lds, st, t->dev, t->cfg.batch, gate, dbg);
+    hipLaunchKernelGGL(k_dqn_wgrad, dim3(t->jobs), dim3(64 * DG_WG_WAVES), 0, st, t->dev, t->base.Bp, gate);
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_dqn_create(stmpc_ctx *c, const stmpc_dqn_cfg *g, stmpc_dqn **out) {
+    if (!c || !g || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (g->n_actions < 1 || g->n_actions > STMPC_ENV_MAX_ACTIONS) return fail(STMPC_EINVAL, "n_actions must be in 1 ... " + std::to_string(STMPC_ENV_MAX_ACTIONS));
+    if (g->n_obs < 1 || g->n_obs > AT_KIN - 1 || g->h1 < 1 || g->h1 > 1024) return fail(STMPC_EINVAL, "DQN network shape out of range (n_obs <= 31, hidden width <= 1024)");
+    if (g->batch < 1 || g->batch > PER_MAX_B) return fail(STMPC_EINVAL, "batch must be in 1 ... 8192");
+    if (g->target_period < 1) return fail(STMPC_EINVAL, "target_period must be at least 1");
+    if (g->capacity < 1 || g->replay_start < 0 || g->replay_start >= g->capacity) return fail(STMPC_EINVAL, "capacity must be positive and replay_start below it");
+    if (!(g->gamma >= 0) || !std::isfinite(g->gamma) || !(g->beta1 >= 0 && g->beta1 < 1) || !(g->beta2 >= 0 && g->beta2 < 1) || !(g->eps > 0) ||
+        (g->clip_targets && !(g->clip_min <= g->clip_max))) return fail(STMPC_EINVAL, "DQN constants out of range");
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_dqn *t = new stmpc_dqn();
+    stmpc_ddpg *l = &t->base;
+    t->cfg = *g;
+    l->device = c->device;
+    l->cfg.n_obs = g->n_obs; l->cfg.h1 = g->h1; l->cfg.h2 = g->n_actions; l->cfg.batch = g->batch; l->cfg.capacity = g->capacity;
+    l->cfg.replay_start = g->replay_start; l->cfg.seed = g->seed;
+    const int h1p = l->h1p = (g->h1 + 15) & ~15, Ap = l->h2p = t->Ap = (g->n_actions + 15) & ~15;
+    const int np = l->np = dg_nparam(h1p, Ap), Bp = l->Bp = (g->batch + 15) & ~15;
+    l->lds = ddpg_tile_bytes(h1p, Ap);
+    if (l->lds + 1024 > (size_t)c->lds_per_block) { delete t; return fail(STMPC_EINVAL, "DQN network too wide for one workgroup's LDS"); }
+    t->tiles = Bp / AT_TM;
+    t->jobs = (Ap / 16) * (h1p / 16) + 2 * (h1p / 16) + Ap / 16 + h1p / 16;      // k_ddpg_wgrad's dW1, dW0, db1, db0
+    t->ablocks = (dq_nparam(h1p, Ap) + 255) / 256;
+    DdpgDev &d = l->dev;
+    int rc = 0;
+    {
+        DdpgNet &n = d.q;
+        float **ptr[11] = {&n.w, &n.wt, &n.m, &n.v, &n.g, &n.p0, &n.p1, &n.p1t, &n.t0, &n.t1, &n.bpow};
+        const size_t len[11] = {(size_t)np, (size_t)np, (size_t)np, (size_t)np, (size_t)np, (size_t)h1p * AT_KIN, (size_t)Ap * h1p, (size_t)Ap * h1p,
+                                (size_t)h1p * AT_KIN, (size_t)Ap * h1p, 4};
+        for (int i = 0; i < 11 && !rc; ++i) { rc = ddpg_zero(l->netbuf[1][i], len[i] * sizeof(float)); *ptr[i] = l->netbuf[1][i].as<float>(); }
+        n.n_in = g->n_obs;
+    }
+    const size_t wlen[7] = {(size_t)Bp * AT_KIN, (size_t)Bp * h1p, (size_t)Bp * Ap, (size_t)Bp * Ap, (size_t)Bp * h1p, (size_t)Bp, (size_t)Bp * 2};
+    float **wptr[7] = {&d.aX, &d.aH1, &d.aH2, &d.aD2, &d.aD1, &d.adz, &d.arow};
+    for (int i = 0; i < 7 && !rc; ++i) { rc = ddpg_zero(l->ws[i], wlen[i] * sizeof(float)); *wptr[i] = l->ws[i].as<float>(); }
+    if (!rc) rc = ddpg_zero(l->ring, (size_t)g->capacity * DG_ROW * sizeof(float));
+    if (!rc) rc = ddpg_zero(l->cnt, DG_NCNT * sizeof(long long));
+    if (!rc) rc = ddpg_zero(l->tick, DG_NTICK * sizeof(unsigned int));
+    if (!rc) rc = dqn_raise_lds(l->device, l->lds);
+    if (rc) { stmpc_dqn_destroy(t); return rc; }
+    d.ring = l->ring.as<float>(); d.cnt = l->cnt.as<long long>(); d.tick = l->tick.as<unsigned int>();
+    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = g->n_actions; d.h1p = h1p; d.h2p = Ap; d.capacity = g->capacity; d.replay_start = g->replay_start; d.seed = g->seed;
+    d.gamma = (float)g->gamma; d.beta1 = (float)g->beta1; d.beta2 = (float)g->beta2;
+    d.omb1 = 1.0f - d.beta1; d.omb2 = 1.0f - d.beta2; d.eps = (float)g->eps;       // (tau, the time feature, the squash and the noise: unused, 0)
+    const float one[4] = {1.f, 1.f, 0.f, 0.f};                       // beta^0
+    if (hipMemcpy(d.q.bpow, one, sizeof one, hipMemcpyHostToDevice) != hipSuccess) { stmpc_dqn_destroy(t); return fail(STMPC_EHIP, "hipMemcpy of the beta powers failed"); }
+    t->dev.base = d;
+    t->dev.A = g->n_actions; t->dev.Ap = Ap; t->dev.dbl = g->double_dqn != 0; t->dev.clip = g->clip_targets != 0; t->dev.target_period = g->target_period;
+    t->dev.clip_min = (float)g->clip_min; t->dev.clip_max = (float)g->clip_max;
+    *out = t;
+    return STMPC_OK;
+}
+
+void stmpc_dqn_destroy(stmpc_dqn *t) {
+    if (!t) return;
+    (void)hipSetDevice(t->base.device);
+    delete t;
+}
+
+int stmpc_dqn_set_params(stmpc_dqn *t, int slot, const float *values, int64_t count) {
+    if (!t || !values || slot < 0 || slot > 3) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
+    if (count != t->slot_len()) return fail(STMPC_EINVAL, "count is not the length of this slot");
+    HIPCHK(hipSetDevice(t->base.device));
+    std::vector<float> pad((size_t)t->base.np, 0.f);
+    dqn_pad(t, values, pad, true, nullptr);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(dqn_slot_ptr(t, slot), pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (slot < 2) {                                                  // the packed copies follow the parameters
+        hipLaunchKernelGGL(k_dqn_adam, dim3(t->ablocks), dim3(256), 0, (hipStream_t)0, t->dev, 0.f, 1, 1);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return STMPC_OK;
+}
+
+int stmpc_dqn_get_params(stmpc_dqn *t, int slot, float *values, int64_t count) {
+    if (!t || !values || slot < 0 || slot > 3) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
+    if (count != t->slot_len()) return fail(STMPC_EINVAL, "count is not the length of this slot");
+    HIPCHK(hipSetDevice(t->base.device));
+    std::vector<float> pad((size_t)t->base.np, 0.f);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(pad.data(), dqn_slot_ptr(t, slot), pad.size() * sizeof(float), hipMemcpyDeviceToHost));
+    dqn_pad(t, nullptr, pad, false, values);
+    return STMPC_OK;
+}
+
+int stmpc_dqn_set_state(stmpc_dqn *t, const int64_t *counters, const float *beta_pow) {
+    if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
+    const stmpc_ddpg *l = &t->base;
+    if (counters[DG_CURSOR] < 0 || counters[DG_CURSOR] >= l->cfg.capacity || counters[DG_FILL] < 0 || counters[DG_FILL] > l->cfg.capacity || counters[DG_UPDATES] < 0 ||
+        counters[DG_ACTS] < 0 || counters[DG_FRAMES] < 0) return fail(STMPC_EINVAL, "counters out of range");
+    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipDeviceSynchronize());
+    long long cn[DG_NCNT];
+    if (l->per) {                                                    // the tree's leaves follow the ring's cursor and fill
+        HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
+        if (cn[DG_CURSOR] != counters[DG_CURSOR] || cn[DG_FILL] != counters[DG_FILL])
+            return fail(STMPC_EINVAL, "prioritised replay is enabled: the ring's cursor and fill cannot be set (the priorities belong to the rows pushed)");
+    }
+    for (int i = 0; i < DG_NCNT; ++i) cn[i] = i <= DG_FRAMES ? counters[i] : 0;
+    HIPCHK(hipMemcpy(l->dev.cnt, cn, sizeof cn, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(l->dev.q.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
+    return STMPC_OK;
+}
+
+int stmpc_dqn_get_state(stmpc_dqn *t, int64_t *counters, float *beta_pow) {
+    if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
+    const stmpc_ddpg *l = &t->base;
+    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipDeviceSynchronize());
+    long long cn[DG_NCNT];
+    HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
+    for (int i = 0; i < DG_NCNT; ++i) counters[i] = cn[i];
+    HIPCHK(hipMemcpy(beta_pow, l->dev.q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return STMPC_OK;
+}
+
+int stmpc_dqn_push_device(stmpc_dqn *t, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_action,
+                          const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
+    if (N < 0 || N > t->cfg.capacity || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N exceeds the replay capacity, or obs_stride is shorter than the observation");
+    if (N == 0) return STMPC_OK;
+    if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(t->base.device));
+    const long long items = (long long)N * DG_ROW;
+    const int blocks = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_dqn_push, dim3(blocks), dim3(256), 0, (hipStream_t)stream, t->dev, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward,
+                       d_terminated, d_truncated);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_dqn_act_device(stmpc_dqn *t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
+    if (N < 0 || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N negative, or obs_stride shorter than the observation");
+    if (!(eps >= 0 && eps <= 1)) return fail(STMPC_EINVAL, "eps must be in 0 ... 1");
+    if (N == 0) return STMPC_OK;
+    if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(t->base.device));
+    hipLaunchKernelGGL(k_dqn_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t->base.lds, (hipStream_t)stream, t->dev, N, d_obs, obs_stride, (float)eps,
+                       eps > 0 ? 1 : 0, d_action, d_debug_q);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_dqn_update_device(stmpc_dqn *t, int n_updates, double lr, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
+    if (n_updates < 0 || !(lr >= 0)) return fail(STMPC_EINVAL, "n_updates or the learning rate is negative");
+    HIPCHK(hipSetDevice(t->base.device));
+    hipStream_t st = (hipStream_t)stream;
+    for (int u = 0; u < n_updates; ++u) {                            // three launches, five with prioritised replay, whatever the counters say
+        per_launch_sample(&t->base, 1, st);
+        dqn_launch_grads(t, 1, nullptr, st);
+        per_launch_update(&t->base, st);
+        hipLaunchKernelGGL(k_dqn_adam, dim3(t->ablocks), dim3(256), 0, st, t->dev, (float)lr, 0, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_dqn_grads_device(stmpc_dqn *t, float *d_grad, void *stream) {
+    if (!t || !d_grad) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->base.device));
+    hipStream_t st = (hipStream_t)stream;
+    per_launch_sample(&t->base, 0, st);
+    dqn_launch_grads(t, 0, nullptr, st);
+    hipLaunchKernelGGL(k_dqn_unpad, dim3(128), dim3(256), 0, st, t->dev, (const float *)t->dev.base.q.g, d_grad);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_dqn_targets_device(stmpc_dqn *t, float *d_out, void *stream) {
+    if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->base.device));
+    per_launch_sample(&t->base, 0, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_dqn_fwd, dim3(t->tiles), dim3(AT_THREADS), t->base.lds, (hipStream_t)stream, t->dev, t->cfg.batch, 0, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_dqn_gather_device(stmpc_dqn *t, float *d_rows, void *stream) {
+    if (!t || !d_rows) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->base.device));
+    per_launch_sample(&t->base, 0, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_replay_gather, dim3((t->cfg.batch * DG_ROW + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->dev.base, t->cfg.batch, d_rows);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_dqn_stats_device(stmpc_dqn *t, double *d_out, void *stream) {
+    if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->base.device));
+    hipLaunchKernelGGL(k_dqn_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, t->dev, t->cfg.batch, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_dqn_per_enable(stmpc_dqn *t, const stmpc_per_cfg *g) {
+    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
+    TRY(per_check_cfg(g));
+    TRY(per_check_ring(&t->base));
+    TRY(per_attach(&t->base, g));
+    t->dev.base = t->base.dev;                                       // (the tree, idx, aw, atd and the constants)
+    return STMPC_OK;
+}
+
+int stmpc_dqn_per_tree_read(stmpc_dqn *t, int64_t first, int64_t count, double *nodes) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return stmpc_per_tree_read(&t->base, first, count, nodes);
+}
+
+int stmpc_dqn_per_last_device(stmpc_dqn *t, int64_t *d_idx, float *d_td, float *d_weight, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return stmpc_per_last_device(&t->base, d_idx, d_td, d_weight, stream);
+}
+
+int stmpc_dqn_padded_read(stmpc_dqn *t, int slot, float *values, int64_t count) {
+    if (!t || !values || slot < 0 || slot > STMPC_DQN_GRAD) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
+    if (count != dq_nparam(t->base.h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
+    HIPCHK(hipSetDevice(t->base.device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(values, slot == STMPC_DQN_GRAD ? t->dev.base.q.g : dqn_slot_ptr(t, slot), (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
     return STMPC_OK;
 }
 

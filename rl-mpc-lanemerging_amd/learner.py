@@ -35,6 +35,12 @@ reference's: none).  Two launches more per update.  Twins: ``SumTreeHost``, ``pe
 ``TD3Population`` likewise; ``csrc/stmpc_per_pop_kernels.hpp``, ``stmpc_pop_per_*``): one ``PERConfig`` for all members or one per member, None for a
 member that samples uniformly -- prioritised against uniform replay, or a sweep of alpha and beta, in one launch sequence of eight launches per update,
 every member bit-identical to the lone learner with that ``cfg.per``.
+
+``DQNLearner`` (``DQNConfig``, ``csrc/stmpc_dqn_kernels.hpp``, ``stmpc_dqn_*``) is the reference's other agent, the hand-written DQN trainer
+(TRAIN_DQN: dqn.py:257-359, ``get_targets`` dqn.py:673-705, the ``DQN`` module dqn.py:566-658), for the discrete-action envs ``sumo-jerk-v0`` and
+``sumo-accel-v0``: a Q-network n_obs -> h1 -> ReLU -> A on the same ring, counters and sum tree, double DQN targets, SmoothL1 loss, Adam, a hard
+target copy every ``target_period`` updates -- three launches per update, five with ``per``.  Twins: ``update_host_dqn``, ``dqn_targets_host``,
+``dqn_adam_host``, ``dqn_act_host``, ``dqn_epsilon``; the loop: ``train_dqn``.
 """
 import math
 
@@ -890,6 +896,325 @@ class TD3Population(DDPGPopulation):
         s = self.stats_device().cpu().numpy()
         return {"critic_loss": s[:, 0].copy(), "critic2_loss": s[:, 1].copy(), "mean_q": s[:, 2].copy(), "mean_q2": s[:, 3].copy(),
                 "fill": s[:, 4].astype(np.int64), "updates": s[:, 5].astype(np.int64)}
+
+
+# ---- DQN: the discrete agent (csrc/stmpc_dqn_kernels.hpp, stmpc_dqn_*) ---------------------------------------------------------------------------
+DQN_TENSORS = ("w0", "b0", "w1", "b1")
+DQN_STREAM = 0x64716E657870
+
+
+class DQNConfig:
+    """The constants of the DQN update; defaults are the reference's config.py (hidden_size 256 of ``DQN()``, BATCH_SIZE, REPLAY_BUFFER_SIZE,
+    DISCOUNT_FACTOR, LEARNING_RATE, TARGET_NET_FREEZE_PERIOD -- counted in updates here, in episodes there --, DOUBLE_DQN, CLIP_MIN_REWARD /
+    CLIP_MAX_REWARD; Adam: ``optim.Adam``'s defaults).  ``n_actions`` None: the env's.  ``per``: a ``PERConfig`` for prioritised replay
+    (USE_PRIORITIZED_ER), None: uniform minibatches."""
+
+    def __init__(self, n_obs=20, n_actions=None, h1=256, batch=50, capacity=50000, replay_start=0, gamma=0.999, lr=2e-4, target_period=500, double=True,
+                 clip_targets=False, clip_min=-20.0, clip_max=10.0, beta1=0.9, beta2=0.999, eps=1e-8, per=None):
+        if per is not None and not isinstance(per, PERConfig):
+            raise ValueError("per must be a PERConfig or None")
+        self.per = per
+        self.n_obs, self.n_actions, self.h1, self.batch = int(n_obs), (None if n_actions is None else int(n_actions)), int(h1), int(batch)
+        self.capacity, self.replay_start, self.target_period = int(capacity), int(replay_start), int(target_period)
+        self.gamma, self.lr, self.beta1, self.beta2, self.eps = float(gamma), float(lr), float(beta1), float(beta2), float(eps)
+        self.double, self.clip_targets, self.clip_min, self.clip_max = bool(double), bool(clip_targets), float(clip_min), float(clip_max)
+
+    def to_c(self, seed):
+        return _capi.DQNCfg(n_obs=self.n_obs, h1=self.h1, n_actions=self.n_actions, batch=self.batch, capacity=self.capacity, target_period=self.target_period,
+                            double_dqn=int(self.double), clip_targets=int(self.clip_targets), replay_start=self.replay_start, seed=int(seed) & _M64,
+                            gamma=self.gamma, beta1=self.beta1, beta2=self.beta2, eps=self.eps, clip_min=self.clip_min, clip_max=self.clip_max)
+
+
+def dqn_epsilon(iteration, eps_start=1.0, eps_end=0.1, decay_coefficient=0.25, decay_rate=30000):
+    """The reference's exploration schedule (dqn.py:275-276; EPS_START, EPS_END, EPS_DECAY_COEFFICIENT, EPS_DECAY_RATE of config.py)."""
+    return eps_end + (eps_start - eps_end) * math.exp(-decay_coefficient * math.floor(iteration / decay_rate))
+
+
+def dqn_act_host(seed, call, n, eps, A):
+    """Exploring acting call ``call``, rows 0 .. n-1: (explore bool [n], index int32 [n]) -- ``k_dqn_act``'s draws in integer arithmetic: u = the
+    hash's top 24 bits / 2^24 < float32(eps), the index the hash's next 24 bits modulo ``A``.  ``eps`` 0: no row explores (and the device draws nothing)."""
+    bound = float(np.float32(eps)) * 2.0 ** 24                      # (exact: a float32 times a power of two)
+    explore, idx = np.zeros(n, dtype=bool), np.zeros(n, dtype=np.int32)
+    for e in range(n):
+        h = hash3((int(seed) & _M64) ^ DQN_STREAM, call, e)
+        explore[e] = eps > 0 and (h >> 40) < bound
+        idx[e] = ((h >> 16) & 0xFFFFFF) % int(A)
+    return explore, idx
+
+
+def init_q_net(n_obs, h1, A, rng):
+    """torch's nn.Linear initialisation (uniform +-1/sqrt(fan_in) for weight and bias) of both layers, as the reference's ``DQN()`` has it."""
+    u = lambda fan_in, *sh: rng.uniform(-1.0 / math.sqrt(fan_in), 1.0 / math.sqrt(fan_in), size=sh).astype(np.float32)
+    return {"w0": u(n_obs, h1, n_obs), "b0": u(n_obs, h1), "w1": u(h1, A, h1), "b1": u(h1, A)}
+
+
+def flatten_q(net):
+    return np.concatenate([np.asarray(net[k], dtype=np.float32).reshape(-1) for k in DQN_TENSORS])
+
+
+def unflatten_q(flat, n_obs, h1, A):
+    out, o = {}, 0
+    for k, sh in zip(DQN_TENSORS, ((h1, n_obs), (h1,), (A, h1), (A,))):
+        n = int(np.prod(sh))
+        out[k] = np.array(flat[o:o + n]).reshape(sh)
+        o += n
+    assert o == len(flat)
+    return out
+
+
+def new_params_dqn(q_net):
+    """The learner's whole parameter state for a given online net: the target a copy, Adam's moments zero, beta powers 1, no updates."""
+    cp = lambda: {k: np.array(q_net[k], dtype=np.float32) for k in DQN_TENSORS}
+    zero = lambda: {k: np.zeros_like(np.asarray(q_net[k], dtype=np.float32)) for k in DQN_TENSORS}
+    return {"q": cp(), "q_target": cp(), "q_m": zero(), "q_v": zero(), "beta_pow": np.ones(2, dtype=np.float32), "updates": 0}
+
+
+def dqn_batch_from_rows(rows, n_obs):
+    """Replay rows [B][68] of a DQN learner -> the minibatch dict ``update_host_dqn`` takes."""
+    return {"s": rows[:, :n_obs], "a": rows[:, _capi.DQN_ACTION_COL].astype(np.int64), "s2": rows[:, 32:32 + n_obs], "r": rows[:, 64], "mask": rows[:, 65]}
+
+
+def _q_mlp(t, x):
+    import torch
+    return torch.relu(x @ t["w0"].T + t["b0"]) @ t["w1"].T + t["b1"]
+
+
+def dqn_targets_host(params, batch, cfg, dtype="float64"):
+    """``get_targets`` (dqn.py:673-705) in torch, every tensor in ``dtype``: [B][3] = a* (``cfg.double``: the first argmax of the online net on s';
+    else the target net's), the target net's Q(s') there, y = r + clip(gamma * that), r alone on a terminated row."""
+    import torch
+    td = getattr(torch, dtype)
+    T = lambda a: torch.tensor(np.asarray(a), dtype=td)
+    with torch.no_grad():
+        s2, r, mask = T(batch["s2"]), T(batch["r"]), T(batch["mask"])
+        qt = _q_mlp({k: T(params["q_target"][k]) for k in DQN_TENSORS}, s2)
+        astar = torch.argmax(_q_mlp({k: T(params["q"][k]) for k in DQN_TENSORS}, s2) if cfg.double else qt, dim=1, keepdim=True)
+        qsel = torch.gather(qt, 1, astar).flatten()
+        g = cfg.gamma * qsel
+        if cfg.clip_targets:
+            g = torch.clamp(g, cfg.clip_min, cfg.clip_max)
+        y = torch.where(mask != 0, r + g, r)
+    return torch.stack([astar.flatten().to(td), qsel, y], 1).numpy()
+
+
+def update_host_dqn(params, batch, cfg, dtype="float64", weights=None, grads_only=False, lr=None):
+    """One DQN update in torch with autograd, every tensor in ``dtype`` ("float64" or "float32"): the targets of ``dqn_targets_host``, the
+    SmoothL1 loss (beta 1) of Q(s)[a] against them as a mean over the minibatch -- ``weights``: prioritised replay's importance weight per row,
+    multiplying that row's term --, one bias-corrected Adam step, and the hard copy of the target if the new update count is a multiple of
+    ``cfg.target_period``.  ``params``: as ``new_params_dqn`` / ``DQNLearner.state_dict()["params"]``; returns the new one and a dict with ``loss``
+    (unweighted), ``mean_q``, ``q_values``, ``td`` (Q(s, a) - y), ``targets`` ([B][3]) and ``grad``.  ``grads_only``: nothing is applied."""
+    import torch
+    td = getattr(torch, dtype)
+    T = lambda a: torch.tensor(np.asarray(a), dtype=td)
+    P = {slot: {k: T(params[slot][k]) for k in DQN_TENSORS} for slot in _capi.DQN_SLOTS}
+    tg = dqn_targets_host(params, batch, cfg, dtype)
+    y = T(tg[:, 2])
+    net = {k: P["q"][k].clone().requires_grad_(True) for k in DQN_TENSORS}
+    q = torch.gather(_q_mlp(net, T(batch["s"])), 1, torch.tensor(np.asarray(batch["a"], dtype=np.int64))[:, None]).flatten()
+    terms = torch.nn.functional.smooth_l1_loss(q, y, reduction="none", beta=1.0)
+    loss = terms.mean()
+    grads = dict(zip(DQN_TENSORS, torch.autograd.grad(loss if weights is None else (T(weights) * terms).mean(), [net[k] for k in DQN_TENSORS])))
+    u = int(params["updates"])
+    if not grads_only:
+        t = u + 1
+        bc1, bc2 = 1.0 - cfg.beta1 ** t, 1.0 - cfg.beta2 ** t
+        for k in DQN_TENSORS:
+            m = cfg.beta1 * P["q_m"][k] + (1 - cfg.beta1) * grads[k]
+            v = cfg.beta2 * P["q_v"][k] + (1 - cfg.beta2) * grads[k] * grads[k]
+            P["q_m"][k], P["q_v"][k] = m, v
+            P["q"][k] = P["q"][k] - ((cfg.lr if lr is None else lr) / bc1) * m / (v.sqrt() / math.sqrt(bc2) + cfg.eps)
+            if t % cfg.target_period == 0:
+                P["q_target"][k] = P["q"][k].clone()
+    out = {slot: {k: P[slot][k].detach().numpy() for k in DQN_TENSORS} for slot in _capi.DQN_SLOTS}
+    out["beta_pow"] = np.array(params["beta_pow"], dtype=np.float32) * (1 if grads_only else np.array([cfg.beta1, cfg.beta2], dtype=np.float32))
+    out["updates"] = u + (0 if grads_only else 1)
+    info = {"loss": float(loss.detach()), "mean_q": float(q.detach().mean()), "q_values": q.detach().numpy(), "td": (q.detach() - y).numpy(), "targets": tg,
+            "grad": {k: grads[k].numpy() for k in DQN_TENSORS}}
+    return out, info
+
+
+def dqn_adam_host(w, g, m, v, beta_pow, lr, cfg):
+    """``k_dqn_adam``'s step for one tensor (or one flat slot) in numpy float32, operation for operation: (w, m, v, beta_pow) after it."""
+    f = np.float32
+    w, g, m, v = (np.asarray(x, dtype=f) for x in (w, g, m, v))
+    b1, b2, eps = f(cfg.beta1), f(cfg.beta2), f(cfg.eps)
+    pw1, pw2 = f(beta_pow[0]) * b1, f(beta_pow[1]) * b2
+    step, bc2s = f(lr) / (f(1) - pw1), np.sqrt(f(1) - pw2)
+    m = b1 * m + (f(1) - b1) * g
+    v = b2 * v + (f(1) - b2) * (g * g)
+    return w - step * (m / (np.sqrt(v) / bc2s + eps)), m, v, np.array([pw1, pw2], dtype=f)
+
+
+class DQNLearner:
+    """DQN on the device for the discrete-action envs (``MergeVecEnv("sumo-jerk-v0")``, ``"sumo-accel-v0"``): the reference's TRAIN_DQN
+    (dqn.py:257-359) with ``DDPGLearner``'s interface.  ``env_or_dims``: such an env (its context, observation width, action count and action table
+    are taken over) or ``(n_obs, n_actions)``.  ``init``: None (torch's nn.Linear initialisation) or a net {w0, b0, w1, b1}.
+    One update is three HIP launches (five with ``cfg.per``); acting, pushing and updating never synchronise with the host."""
+
+    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None):
+        env = None if isinstance(env_or_dims, (tuple, list)) else env_or_dims
+        if env is not None and env.continuous:
+            raise ValueError("DQN needs a discrete action space (sumo-jerk-v0 or sumo-accel-v0), not the continuous jerk env")
+        n_obs, A = (env.obs_dim, int(env.action_space["n"])) if env is not None else (int(env_or_dims[0]), int(env_or_dims[1]))
+        self.cfg = cfg if cfg is not None else DQNConfig(n_obs=n_obs)
+        if self.cfg.n_actions is None:
+            self.cfg.n_actions = A
+        if self.cfg.n_obs != n_obs or self.cfg.n_actions != A:
+            raise ValueError("cfg has n_obs %d and %d actions; the observation has %d entries and there are %d actions" % (self.cfg.n_obs, self.cfg.n_actions, n_obs, A))
+        for name, ok in (("n_actions in 1 ... 256", 1 <= A <= 256), ("n_obs in 1 ... 31", 1 <= n_obs <= 31), ("batch >= 1", self.cfg.batch >= 1),
+                         ("target_period >= 1", self.cfg.target_period >= 1)):
+            if not ok:
+                raise ValueError("DQN needs " + name)
+        # the env's table, index -> jerk or acceleration (what its cfg hands the library); without an env the indices stand for themselves
+        self.action_values = np.array(env.cfg._actions, dtype=np.float64) if env is not None else np.arange(A, dtype=np.float64)
+        if self.action_values.shape != (A,):
+            raise ValueError("the env's action table has %d entries, its action space %d" % (self.action_values.size, A))
+        import torch
+        self.torch = torch
+        self.ctx = ctx if ctx is not None else (env.ctx if env is not None else _capi.Context(-1))
+        self.seed = int(seed)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.handle = self.ctx.dqn_create(self.cfg.to_c(self.seed))
+        if self.cfg.per is not None:
+            self.ctx.dqn_per_enable(self.handle, self.cfg.per.to_c())
+        c = self.cfg
+        net = init if init is not None else init_q_net(c.n_obs, c.h1, A, np.random.default_rng(self.seed))
+        self._len = flatten_q(net).size
+        if self._len != (c.n_obs + 1) * c.h1 + (c.h1 + 1) * A:
+            raise ValueError("the net's tensors do not have the shape %d -> %d -> %d" % (c.n_obs, c.h1, A))
+        self.load_state_dict({"params": new_params_dqn(net), "counters": None})
+        self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
+        self._actions = {}
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                self.ctx.dqn_destroy(self.handle)
+            except Exception:
+                pass
+            self.handle = None
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    # -- acting / replay / update: asynchronous ---------------------------------------------------------------------------------------------
+    def act(self, obs, ticks=None, eps=0.0, debug_q=None):
+        """Action indices int32 [n] (what ``MergeVecEnv.step`` takes) for observations float32 [n][n_obs]: the first maximum of Q(obs); with
+        ``eps`` > 0 a row explores with that probability and then takes a uniform index (``dqn_act_host``).  ``ticks`` is accepted for
+        ``DDPGLearner``'s signature and not read: the network has no time feature.  The returned tensor is reused by the next call with the
+        same n.  ``debug_q``: float32 [n][n_actions] device tensor for Q(obs)."""
+        n = obs.shape[0]
+        out = self._actions.get(n)
+        if out is None:
+            out = self._actions[n] = self.torch.empty(n, dtype=self.torch.int32, device=self.device)
+        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
+        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (n, self.cfg.n_actions))
+        self.ctx.dqn_act(self.handle, n, obs.data_ptr(), obs.stride(0), eps, out.data_ptr(), debug_q.data_ptr() if debug_q is not None else 0, self._stream())
+        return out
+
+    def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
+        """One env step into the replay ring: ``obs`` as given to ``act``, ``action`` int32 [n], and what ``env.step`` returned
+        (``final_obs = info["final_observation"]``: s' where an episode ended).  ``ticks`` / ``next_ticks`` are not read."""
+        torch = self.torch
+        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == torch.int32 and reward.dtype == torch.float64 and action.is_contiguous()
+        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
+        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+        self.ctx.dqn_push(self.handle, obs.shape[0], obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0, obs.stride(0),
+                          action.data_ptr(), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self._stream())
+
+    def update(self, n=1, lr=None):
+        """``n`` updates; on the device nothing happens until more than cfg.replay_start frames were pushed.  ``lr``: this call's learning rate."""
+        self.ctx.dqn_update(self.handle, n, self.cfg.lr if lr is None else lr, self._stream())
+
+    def grads(self):
+        """Debug: the loss's gradient on the current update index's minibatch as a dict of numpy tensors; nothing applied; synchronises."""
+        c = self.cfg
+        g = self.torch.empty(self._len, dtype=self.torch.float32, device=self.device)
+        self.ctx.dqn_grads(self.handle, g.data_ptr(), self._stream())
+        return unflatten_q(g.cpu().numpy(), c.n_obs, c.h1, c.n_actions)
+
+    def targets(self):
+        """Debug: float32 [batch][4] = a*, the target net's Q(s') there, y, Q(s, a) of the minibatch the next update will draw; synchronises."""
+        out = self.torch.zeros(self.cfg.batch, 4, dtype=self.torch.float32, device=self.device)
+        self.ctx.dqn_targets(self.handle, out.data_ptr(), self._stream())
+        return out.cpu().numpy()
+
+    def minibatch(self):
+        """Debug: the replay rows [batch][68] the next update will read (numpy; ``dqn_batch_from_rows``); synchronises."""
+        rows = self.torch.empty(self.cfg.batch, _capi.DDPG_ROW, dtype=self.torch.float32, device=self.device)
+        self.ctx.dqn_gather(self.handle, rows.data_ptr(), self._stream())
+        return rows.cpu().numpy()
+
+    def priorities(self):
+        """Debug, prioritised replay: the sum tree, float64 [2 * leaves - 1] (``SumTreeHost``'s layout); synchronises."""
+        return self.ctx.dqn_per_tree_read(self.handle, 0, 2 * per_leaves(self.cfg.capacity) - 1)
+
+    def last_sample(self):
+        """Debug, prioritised replay: {"idx" int64, "td" float32, "weight" float32}, [batch] each, of the most recent sampling step and pass."""
+        torch, B = self.torch, self.cfg.batch
+        idx = torch.zeros(B, dtype=torch.int64, device=self.device)
+        td, w = (torch.zeros(B, dtype=torch.float32, device=self.device) for _ in range(2))
+        self.ctx.dqn_per_last(self.handle, idx.data_ptr(), td.data_ptr(), w.data_ptr(), self._stream())
+        return {"idx": idx.cpu().numpy(), "td": td.cpu().numpy(), "weight": w.cpu().numpy()}
+
+    def stats_device(self):
+        """fp64 [4] device tensor: loss and mean Q(s, a) of the last minibatch, fill, updates done (asynchronous)."""
+        self.ctx.dqn_stats(self.handle, self._stats.data_ptr(), self._stream())
+        return self._stats
+
+    def stats(self):
+        s = self.stats_device().cpu().numpy()
+        return {"loss": float(s[0]), "mean_q": float(s[1]), "fill": int(s[2]), "updates": int(s[3])}
+
+    # -- state ------------------------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """{"params": the four slots as dicts of numpy tensors + beta_pow + updates, "counters": int64 [8]}; the replay ring is not part of it."""
+        c = self.cfg
+        cn, bp = self.ctx.dqn_get_state(self.handle)
+        params = {slot: unflatten_q(self.ctx.dqn_get_params(self.handle, i, self._len), c.n_obs, c.h1, c.n_actions) for i, slot in enumerate(_capi.DQN_SLOTS)}
+        params["beta_pow"], params["updates"] = bp, int(cn[2])
+        return {"params": params, "counters": cn}
+
+    def load_state_dict(self, sd):
+        """The inverse; ``counters`` None: only the update count and Adam's beta powers are set (the replay's cursor and fill stay)."""
+        p = sd["params"]
+        for i, slot in enumerate(_capi.DQN_SLOTS):
+            self.ctx.dqn_set_params(self.handle, i, flatten_q(p[slot]))
+        cn = sd.get("counters")
+        if cn is None:
+            cn, _ = self.ctx.dqn_get_state(self.handle)
+            cn[2] = int(p["updates"])
+        self.ctx.dqn_set_state(self.handle, cn, p["beta_pow"])
+
+    def export_q(self, path):
+        """Write the online Q-network as an ``.npz``: w0, b0, w1, b1 (float32) and ``action_values`` (the env's table, index -> jerk or acceleration)."""
+        c = self.cfg
+        net = unflatten_q(self.ctx.dqn_get_params(self.handle, 0, self._len), c.n_obs, c.h1, c.n_actions)
+        with open(path, "wb") as fh:
+            np.savez_compressed(fh, **net, action_values=self.action_values)
+        return path
+
+
+def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_schedule=None, lr_schedule=None):
+    """The loop of the reference's ``DQNAgent._train`` on the device: act (epsilon-greedy) -> env.step -> push -> ``updates_per_step`` updates,
+    until ``frames`` transitions were collected (rounded up to whole steps of env.n).  ``eps_schedule(step, steps) -> eps`` (None:
+    ``dqn_epsilon(step)``, the reference's decay with the step for the episode number); ``lr_schedule(step, steps) -> lr``.  Synchronises only
+    every ``drain_every`` steps.  The result has ``train_ddpg``'s keys (``takeover_share`` 0.0: no shield)."""
+    steps = -(-int(frames) // env.n)
+    obs = env.reset()
+    returns = []
+    for i in range(steps):
+        action = learner.act(obs, None, eps=eps_schedule(i, steps) if eps_schedule is not None else dqn_epsilon(i))
+        next_obs, reward, term, trunc, info = env.step(action)
+        learner.push(obs, None, action, reward, next_obs, term, trunc, final_obs=info["final_observation"])
+        if updates_per_step:
+            learner.update(updates_per_step, lr_schedule(i, steps) if lr_schedule is not None else None)
+        obs = next_obs
+        if (i + 1) % drain_every == 0 or i + 1 == steps:
+            returns.append(env.drain_episode_stats()["episode_return"])
+    returns = np.concatenate(returns) if returns else np.zeros(0)
+    return {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
+            "returns": returns, "takeover_share": 0.0}
 
 
 def write_actor(path, net, tanh_scale, tanh_mean):

@@ -1,0 +1,522 @@
+"""The DQN learner on the GPU (``learner.DQNLearner``, csrc/stmpc_dqn_kernels.hpp) against its host twins, at the shapes (n_obs, h1, A, B) =
+(20, 16, 5, 7), (20, 48, 20, 33), (20, 256, 5, 50), (12, 32, 17, 16): one and two output tiles, an A that crosses a tile with padding, a B that is
+no multiple of 16 and one that is, the reference's own shape.  Rings have at most 256 rows, envs at most 64 environments.
+
+Parity rule for float32 results (tests/test_learner.py's): per tensor, max-norm error against ``update_host_dqn("float64")`` at most
+max(4 x the error of ``update_host_dqn("float32")``, 8 float32 ulps).
+
+Exactness on dyadic data: the targets, a*, Q(s, a) and the pads are exact at every shape.  A gradient carries the factor 1 / B: for B = 16 the
+gradients equal the float64 twin value for value; 1/7, 1/33 and 1/50 are not float32 numbers, so no float32 gradient can equal the float64 one
+there, and those shapes' gradients are held to the parity rule above (test_gpu_dyadic_targets_are_exact) -- and each of the four networks has its
+gradients checked value for value at a power-of-two B of its own (test_gpu_dyadic_gradients_are_exact: B = 8, 32, 64, 16)."""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import REPO
+
+FLOOR = 8 * 2.0 ** -23
+SHAPES = [(20, 16, 5, 7), (20, 48, 20, 33), (20, 256, 5, 50), (12, 32, 17, 16)]
+NAMES = ("w0", "b0", "w1", "b1")
+RING = 128
+
+
+def _capi():
+    import rl_mpc_lanemerging_amd as pkg
+    if pkg.build.needs_build():
+        pkg.build.build()
+    from rl_mpc_lanemerging_amd import _capi
+    return _capi
+
+
+def _rel_err(x, ref):
+    scale = np.abs(ref).max()
+    return float(np.abs(np.asarray(x, dtype=np.float64) - ref).max() / scale) if scale > 0 else float(np.abs(x).max())
+
+
+def _check_4x(label, dev, f32, f64):
+    e_dev, e_32 = _rel_err(dev, f64), _rel_err(f32, f64)
+    bound = max(4 * e_32, FLOOR)
+    print("%-36s device %.3e  float32 twin %.3e  bound %.3e" % (label, e_dev, e_32, bound))
+    return e_dev <= bound
+
+
+def _fill(L, replay):
+    """Push the replay dict's rows (s, a, r, s2, term), 64 at a time."""
+    import torch
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")
+    R = replay["s"].shape[0]
+    for o in range(0, R, 64):
+        sl = slice(o, min(R, o + 64))
+        term = replay["term"][sl]
+        L.push(dev(replay["s"][sl].astype(np.float32)), None, dev(replay["a"][sl].astype(np.int32)), dev(replay["r"][sl].astype(np.float64)),
+               dev(replay["s2"][sl].astype(np.float32)), dev(term), dev(np.zeros_like(term)))
+
+
+def _rows(replay, n_obs):
+    capi = _capi()
+    R = replay["s"].shape[0]
+    rows = np.zeros((R, capi.DDPG_ROW), dtype=np.float32)
+    rows[:, :n_obs], rows[:, 32:32 + n_obs] = replay["s"], replay["s2"]
+    rows[:, 64], rows[:, 65], rows[:, capi.DQN_ACTION_COL] = replay["r"], np.where(replay["term"], 0, 1), replay["a"]
+    return rows
+
+
+def dyadic_problem(shape, double, clip, seed=0):
+    """Weights, observations and rewards on small dyadic grids and gamma = 0.5: every sum of the forward pass is exact in float32 (|Q| < 2^13 in
+    units of 2^-9).  b1 is shifted down so that on some rows every real Q(s') is negative (the pad columns' 0 would win a careless argmax)."""
+    from rl_mpc_lanemerging_amd import learner
+    n_obs, h1, A, B = shape
+    rng = np.random.default_rng(100 + seed)
+    grid = lambda lo, hi, den, *sh: rng.integers(lo, hi + 1, size=sh).astype(np.float64) / den
+    shift = np.round((1.0 if A <= 5 else 0.7) * 0.45 * np.sqrt(h1) * 8) / 8     # about half of the rows: Q(s') spreads by about 0.45 sqrt(h1)
+    net = lambda: {"w0": grid(-4, 4, 8, h1, n_obs).astype(np.float32), "b0": grid(-4, 4, 8, h1).astype(np.float32),
+                   "w1": grid(-4, 4, 8, A, h1).astype(np.float32), "b1": (grid(-4, 4, 8, A) - shift).astype(np.float32)}
+    params = learner.new_params_dqn(net())
+    params["q_target"] = net()
+    replay = {"s": grid(-4, 4, 4, RING, n_obs), "s2": grid(-4, 4, 4, RING, n_obs), "a": rng.integers(0, A, RING), "r": grid(-8, 8, 4, RING),
+              "term": rng.random(RING) < 0.2}
+    cfg = learner.DQNConfig(n_obs=n_obs, n_actions=A, h1=h1, batch=B, capacity=RING, gamma=0.5, double=double, clip_targets=clip, clip_min=-0.5, clip_max=0.25)
+    return cfg, params, replay
+
+
+def _learner(gpu_ctx, cfg, params, replay=None, seed=11):
+    from rl_mpc_lanemerging_amd import learner
+    L = learner.DQNLearner((cfg.n_obs, cfg.n_actions), cfg, seed=seed, init=params["q"], ctx=gpu_ctx)
+    L.load_state_dict({"params": params, "counters": None})
+    if replay is not None:
+        _fill(L, replay)
+    return L
+
+
+def _minibatch_host(replay, cfg, seed=11, update=0):
+    from rl_mpc_lanemerging_amd import learner
+    rows = _rows(replay, cfg.n_obs)[learner.sample_indices_host(seed, update, cfg.batch, replay["s"].shape[0])]
+    return rows, learner.dqn_batch_from_rows(rows, cfg.n_obs)
+
+
+# ---- 1: targets -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("double,clip", [(True, False), (True, True), (False, False), (False, True)])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_gpu_dyadic_targets_are_exact(shape, double, clip, gpu_ctx, restore_settings):
+    """targets() (a*, Qt(s', a*), y, Q(s, a)) equals update_host_dqn(float64) value for value, on minibatches with rows whose real Q(s') are all
+    negative; the gradient tensors: value for value where B is a power of two (B = 16), else -- 1 / B is no float32 number -- under the parity rule."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    n_obs, h1, A, B = shape
+    cfg, params, replay = dyadic_problem(shape, double, clip)
+    L = _learner(gpu_ctx, cfg, params, replay)
+    rows, batch = _minibatch_host(replay, cfg)
+    assert L.stats()["fill"] == RING and np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
+    _, i64 = learner.update_host_dqn(params, batch, cfg, "float64", grads_only=True)
+    _, i32 = learner.update_host_dqn(params, batch, cfg, "float32", grads_only=True)
+    import torch
+    with torch.no_grad():
+        T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
+        qn = learner._q_mlp({k: T(params["q" if double else "q_target"][k]) for k in NAMES}, T(batch["s2"])).numpy()
+    allneg = (qn < 0).all(1)
+    assert allneg.any() and not allneg.all(), int(allneg.sum())     # rows on which a pad column's 0 would beat every real action
+    t = L.targets()
+    assert t.dtype == np.float32 and t.shape == (B, 4)
+    assert np.array_equal(t[:, :3].astype(np.float64), i64["targets"]), np.count_nonzero(t[:, :3].astype(np.float64) != i64["targets"], axis=0)
+    assert np.array_equal(t[:, 3].astype(np.float64), i64["q_values"])
+    assert t[:, 0].max() < A and (double or (t[allneg, 1] < 0).all())          # (double: the sign seen is the online net's, the value the target's)
+    if clip:
+        g = 0.5 * i64["targets"][:, 1]
+        live = batch["mask"] > 0
+        assert (g[live] > cfg.clip_max).any() or (g[live] < cfg.clip_min).any()
+    grad = L.grads()
+    ok = True
+    for k in NAMES:
+        want = i64["grad"][k]
+        assert grad[k].dtype == np.float32 and grad[k].shape == want.shape and np.abs(want).max() > 0
+        if B & (B - 1) == 0:
+            assert np.array_equal(grad[k].astype(np.float64), want), (k, int(np.count_nonzero(grad[k].astype(np.float64) != want)), want.size)
+        else:
+            ok &= _check_4x("%s grad %s" % (shape, k), grad[k], i32["grad"][k], want)
+    assert ok
+    after = L.state_dict()["params"]
+    assert all(np.array_equal(after[s][k], params[s][k]) for s in ("q", "q_target", "q_m", "q_v") for k in NAMES) and after["updates"] == 0
+    gpu_ctx.check_error()
+
+
+GRAD_SHAPES = [(20, 16, 5, 8), (20, 48, 20, 32), (20, 256, 5, 64), (12, 32, 17, 16)]      # SHAPES' networks at a power-of-two B each
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("double,clip", [(True, False), (True, True), (False, False), (False, True)])
+@pytest.mark.parametrize("shape", GRAD_SHAPES)
+def test_gpu_dyadic_gradients_are_exact(shape, double, clip, gpu_ctx, restore_settings):
+    """Every gradient tensor equals update_host_dqn(float64) value for value, at each of the four networks: B is a power of two here (8: half a
+    tile of padded rows; 32, 64, 16), so that dz = clamp(diff) / B is exact and every product and partial sum of the backward pass is a float32
+    number -- any summation order gives the same bits, and a stray or missing term shows."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    n_obs, h1, A, B = shape
+    cfg, params, replay = dyadic_problem(shape, double, clip, seed=2)
+    L = _learner(gpu_ctx, cfg, params, replay)
+    rows, batch = _minibatch_host(replay, cfg)
+    assert np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
+    _, i64 = learner.update_host_dqn(params, batch, cfg, "float64", grads_only=True)
+    assert (np.abs(i64["td"]) > 1).any() and (batch["mask"] == 0).any()
+    t = L.targets()
+    assert np.array_equal(t[:, :3].astype(np.float64), i64["targets"]) and np.array_equal(t[:, 3].astype(np.float64), i64["q_values"])
+    grad = L.grads()
+    for k in NAMES:
+        want = i64["grad"][k]
+        assert grad[k].dtype == np.float32 and grad[k].shape == want.shape and np.abs(want).max() > 0
+        assert np.array_equal(grad[k].astype(np.float64), want), (k, int(np.count_nonzero(grad[k].astype(np.float64) != want)), want.size)
+    gpu_ctx.check_error()
+
+
+def _pad_mask(n_obs, h1, A):
+    """True at the pad entries of a padded slot {w0 [h1p][32], b0 [h1p], w1 [Ap][h1p], b1 [Ap]}."""
+    h1p, Ap = (h1 + 15) & ~15, (A + 15) & ~15
+    m = {"w0": np.ones((h1p, 32), bool), "b0": np.ones(h1p, bool), "w1": np.ones((Ap, h1p), bool), "b1": np.ones(Ap, bool)}
+    m["w0"][:h1, :n_obs], m["b0"][:h1], m["w1"][:A, :h1], m["b1"][:A] = False, False, False, False
+    return m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", SHAPES)
+def test_gpu_pad_entries_stay_zero(shape, gpu_ctx, restore_settings):
+    """The padded arrays themselves (padded_read): the pad rows and columns of the gradient are exact zeros after grads(), and those of the
+    gradient, the weights, the target and both of Adam's moments are exact zeros after each of four updates (target_period 2: the hard copy
+    included); the entries that are no pads are the slot's, and none of a gradient's is zero by accident of the layout (every real row, column
+    and bias is reached)."""
+    capi = _capi()
+    n_obs, h1, A, B = shape
+    cfg, params, replay = _random_problem(shape, 61, target_period=2)
+    L = _learner(gpu_ctx, cfg, params, replay)
+    pad = _pad_mask(n_obs, h1, A)
+    read = lambda slot: gpu_ctx.dqn_padded_read(L.handle, slot, h1, A)
+
+    def check(slots, tag):
+        for slot in slots:
+            arr = read(slot)
+            for k in NAMES:
+                assert arr[k].shape == pad[k].shape and not arr[k][pad[k]].any(), (tag, slot, k, int(np.count_nonzero(arr[k][pad[k]])))
+                assert np.isfinite(arr[k]).all()
+
+    g = L.grads()
+    check([capi.DQN_GRAD], "grads")
+    have = read(capi.DQN_GRAD)
+    assert all(np.array_equal(have[k][~pad[k]].reshape(g[k].shape), g[k]) for k in NAMES)
+    assert (np.abs(g["w0"]).max(0) > 0).all() and np.abs(g["b0"]).max() > 0 and np.abs(g["b1"]).max() > 0
+    for u in range(4):
+        L.update(1)
+        check(range(5), "update %d" % u)
+    sd = L.state_dict()["params"]
+    for i, slot in enumerate(capi.DQN_SLOTS):
+        arr = read(i)
+        assert all(np.array_equal(arr[k][~pad[k]].reshape(sd[slot][k].shape), sd[slot][k]) for k in NAMES), slot
+    assert sd["updates"] == 4 and all(np.array_equal(sd["q_target"][k], sd["q"][k]) and np.abs(sd["q_m"][k]).max() > 0 for k in NAMES)
+    with pytest.raises(RuntimeError):
+        gpu_ctx.dqn_padded_read(L.handle, 5, h1, A)
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+def test_gpu_act_reads_only_the_observation_columns(gpu_ctx, restore_settings):
+    """Q(obs) and the action do not change when the gap of a strided obs tensor -- where the network's pad inputs would read -- holds 1e30."""
+    _capi()
+    import torch
+    n_obs, h1, A, B = SHAPES[3]
+    cfg, params, replay = _random_problem(SHAPES[3], 62)
+    L = _learner(gpu_ctx, cfg, params)
+    wide = torch.full((40, 32), 1e30, dtype=torch.float32, device="cuda")
+    obs = torch.as_tensor(replay["s"][:40].astype(np.float32), device="cuda")
+    wide[:, :n_obs] = obs
+    q0, q1 = (torch.zeros(40, A, dtype=torch.float32, device="cuda") for _ in range(2))
+    a0 = L.act(obs, None, debug_q=q0).clone()
+    a1 = L.act(wide[:, :n_obs], None, debug_q=q1).clone()
+    assert torch.equal(q0, q1) and torch.equal(a0, a1) and torch.isfinite(q0).all()
+    gpu_ctx.check_error()
+
+
+# ---- 2: gradients on data of real magnitude --------------------------------------------------------------------------------------------------
+def _env_replay(gpu_ctx, A_env_id, n_obs, A, rng, steps=4, n=64):
+    """Observations from a stepped MergeVecEnv (random indices); n * steps <= 256 rows."""
+    import rl_mpc_lanemerging_amd as pkg
+    import torch
+    from rl_mpc_lanemerging_amd import vec_env
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    env = vec_env.MergeVecEnv(n, env_id=A_env_id, seed=4, ctx=gpu_ctx)
+    obs = env.reset()
+    out = {k: [] for k in ("s", "s2", "r", "term")}
+    for i in range(steps):
+        a = torch.as_tensor(rng.integers(0, env.action_space["n"], n).astype(np.int32), device="cuda")
+        nobs, r, term, trunc, info = env.step(a)
+        done = (term | trunc)[:, None]
+        out["s"].append(obs.cpu().numpy()[:, :n_obs].copy()); out["s2"].append(torch.where(done, info["final_observation"], nobs).cpu().numpy()[:, :n_obs].copy())
+        out["r"].append(r.cpu().numpy().copy()); out["term"].append(term.cpu().numpy().copy())
+        obs = nobs
+    env.check_error()
+    rep = {k: np.concatenate(v) for k, v in out.items()}
+    rep["a"] = rng.integers(0, A, rep["r"].size)
+    rep["term"] = rep["term"] | (rng.random(rep["r"].size) < 0.15)      # (the few steps end no episode: some rows are made terminal)
+    return rep
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", SHAPES)
+def test_gpu_gradients_against_the_float64_twin(shape, gpu_ctx, restore_settings):
+    """Normal weights at nn.Linear scale, observations of a stepped sumo-jerk-v0 env: the parity rule, per gradient tensor, and for the targets."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    n_obs, h1, A, B = shape
+    rng = np.random.default_rng(7)
+    rep = _env_replay(gpu_ctx, "sumo-jerk-v0", n_obs, A, rng)
+    cfg = learner.DQNConfig(n_obs=n_obs, n_actions=A, h1=h1, batch=B, capacity=256)
+    nrm = lambda fan, *sh: (rng.normal(size=sh) / np.sqrt(fan)).astype(np.float32)
+    net = lambda: {"w0": nrm(n_obs, h1, n_obs), "b0": nrm(n_obs, h1), "w1": nrm(h1, A, h1), "b1": nrm(h1, A)}
+    params = learner.new_params_dqn(net())
+    params["q_target"] = net()
+    L = _learner(gpu_ctx, cfg, params, rep)
+    rows, batch = _minibatch_host(rep, cfg)
+    assert np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
+    _, i64 = learner.update_host_dqn(params, batch, cfg, "float64", grads_only=True)
+    _, i32 = learner.update_host_dqn(params, batch, cfg, "float32", grads_only=True)
+    t, g = L.targets(), L.grads()
+    assert np.array_equal(t[:, 0].astype(np.int64), i64["targets"][:, 0].astype(np.int64))
+    ok = _check_4x("%s y" % (shape,), t[:, 2], i32["targets"][:, 2], i64["targets"][:, 2])
+    ok &= _check_4x("%s Q(s, a)" % (shape,), t[:, 3], i32["q_values"], i64["q_values"])
+    for k in NAMES:
+        assert np.abs(i64["grad"][k]).max() > 0
+        ok &= _check_4x("%s grad %s" % (shape, k), g[k], i32["grad"][k], i64["grad"][k])
+    assert ok
+    gpu_ctx.check_error()
+
+
+# ---- 3: acting ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[2]])
+def test_gpu_acting(shape, gpu_ctx, restore_settings):
+    _capi()
+    import torch
+    import rl_mpc_lanemerging_amd as pkg
+    from rl_mpc_lanemerging_amd import learner, vec_env
+    n_obs, h1, A, B = shape
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    n = 50                                                          # four tiles, the last one partly filled
+    env = vec_env.MergeVecEnv(n, env_id="sumo-jerk-v0" if A == 5 else "sumo-accel-v0", seed=9, ctx=gpu_ctx)
+    cfg = learner.DQNConfig(n_obs=n_obs, h1=h1, batch=B, capacity=256)
+    L = learner.DQNLearner(env, cfg, seed=23)
+    assert cfg.n_actions == A == L.action_values.size
+    obs = env.reset()
+    q = torch.zeros(n, A, dtype=torch.float32, device="cuda")
+    greedy = L.act(obs, None, eps=0.0, debug_q=q).cpu().numpy().copy()
+    qh = q.cpu().numpy()
+    assert greedy.dtype == np.int32 and np.array_equal(greedy, qh.argmax(1))          # numpy's argmax: the first maximum
+    net = L.state_dict()["params"]["q"]
+    want = np.maximum(obs.cpu().numpy().astype(np.float64) @ net["w0"].astype(np.float64).T + net["b0"], 0) @ net["w1"].astype(np.float64).T + net["b1"]
+    assert np.abs(qh - want).max() < 5e-5                            # tests/test_learner.py's acting rule
+    assert int(gpu_ctx.dqn_get_state(L.handle)[0][3]) == 0           # a greedy call is no exploring call
+    call = 0
+    for eps in (0.25, 1.0, 0.25):
+        a = L.act(obs, None, eps=eps).cpu().numpy().copy()
+        explore, idx = learner.dqn_act_host(23, call, n, eps, A)
+        assert np.array_equal(a, np.where(explore, idx, greedy)) and a.min() >= 0 and a.max() < A, (eps, call)
+        assert explore.all() if eps == 1.0 else (explore.any() and not explore.all())
+        call += 1
+        assert int(gpu_ctx.dqn_get_state(L.handle)[0][3]) == call
+    assert np.array_equal(L.act(obs, None, eps=0.0).cpu().numpy(), greedy)
+    # stepping the env with the returned tensor latches no out-of-range flag
+    for _ in range(3):
+        obs, r, term, trunc, info = env.step(L.act(obs, None, eps=0.5))
+    env.check_error()
+    # ties: an all-zero last layer yields action 0 everywhere
+    p = L.state_dict()
+    p["params"]["q"]["w1"][:] = 0
+    p["params"]["q"]["b1"][:] = 0
+    L.load_state_dict(p)
+    assert (L.act(obs, None).cpu().numpy() == 0).all()
+    with pytest.raises(RuntimeError):
+        L.act(obs, None, eps=1.5)
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+def test_gpu_library_refusals(gpu_ctx):
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    good = dict(n_obs=20, n_actions=5, h1=16, batch=7, capacity=64)
+    for bad in (dict(n_actions=0), dict(n_actions=257), dict(n_obs=32), dict(batch=0), dict(target_period=0), dict(replay_start=64)):
+        with pytest.raises(RuntimeError):
+            gpu_ctx.dqn_create(learner.DQNConfig(**dict(good, **bad)).to_c(0))
+    h = gpu_ctx.dqn_create(learner.DQNConfig(**good).to_c(0))
+    gpu_ctx.dqn_destroy(h)
+
+
+# ---- 4: updates --------------------------------------------------------------------------------------------------------------------------------
+def _random_problem(shape, seed, **kw):
+    from rl_mpc_lanemerging_amd import learner
+    n_obs, h1, A, B = shape
+    rng = np.random.default_rng(seed)
+    params = learner.new_params_dqn(learner.init_q_net(n_obs, h1, A, rng))
+    params["q_target"] = learner.init_q_net(n_obs, h1, A, rng)
+    replay = {"s": rng.normal(size=(RING, n_obs)).astype(np.float32), "s2": rng.normal(size=(RING, n_obs)).astype(np.float32), "a": rng.integers(0, A, RING),
+              "r": rng.normal(size=RING) * 2, "term": rng.random(RING) < 0.2}
+    cfg = learner.DQNConfig(n_obs=n_obs, n_actions=A, h1=h1, batch=B, capacity=RING, lr=1e-3, **kw)
+    return cfg, params, replay
+
+
+def _bits_equal(a, b):
+    return all(np.array_equal(a[s][k].view(np.uint32), b[s][k].view(np.uint32)) for s in ("q", "q_target", "q_m", "q_v") for k in NAMES)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[3]])
+def test_gpu_target_schedule_and_gate(shape, gpu_ctx, restore_settings):
+    """target_period = 3: over 7 updates the target equals the online weights bit for bit after updates 3 and 6 and is unchanged otherwise; nothing
+    moves before replay_start; after each update Adam's state and the weights equal the float32 twin stepped with the device's own gradients."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    cfg, params, replay = _random_problem(shape, 31, target_period=3, replay_start=64)
+    L = _learner(gpu_ctx, cfg, params)
+    _fill(L, {k: v[:64] for k, v in replay.items()})                # 64 frames: not MORE than replay_start
+    L.update(2)
+    sd = L.state_dict()
+    assert _bits_equal(sd["params"], params) and sd["params"]["updates"] == 0 and sd["counters"][1] == 64
+    _fill(L, {k: v[64:] for k, v in replay.items()})
+    for u in range(7):
+        before = L.state_dict()["params"]
+        g = L.grads()
+        L.update(1)
+        after = L.state_dict()["params"]
+        for k in NAMES:
+            w, m, v, bp = learner.dqn_adam_host(before["q"][k], g[k], before["q_m"][k], before["q_v"][k], before["beta_pow"], cfg.lr, cfg)
+            assert np.array_equal(after["q"][k], w) and np.array_equal(after["q_m"][k], m) and np.array_equal(after["q_v"][k], v), (u, k)
+            assert np.array_equal(after["q_target"][k], after["q"][k] if (u + 1) % 3 == 0 else before["q_target"][k]), (u, k)
+            assert not np.array_equal(after["q"][k], before["q"][k])
+        assert np.array_equal(after["beta_pow"], bp) and after["updates"] == u + 1
+    st = L.stats()
+    assert st["updates"] == 7 and st["fill"] == RING and np.isfinite(st["loss"])
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("per", [False, True])
+def test_gpu_updates_are_reproducible(per, gpu_ctx, restore_settings):
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    kw = dict(per=learner.PERConfig(beta=0.4)) if per else {}
+    cfg, params, replay = _random_problem(SHAPES[1], 41, target_period=4, **kw)
+    A_, B_ = _learner(gpu_ctx, cfg, params, replay), _learner(gpu_ctx, cfg, params, replay)
+    A_.update(10)
+    B_.update(4)
+    mid = B_.state_dict()
+    B_.update(6)
+    sa, sb = A_.state_dict(), B_.state_dict()
+    assert _bits_equal(sa["params"], sb["params"]) and np.array_equal(sa["counters"], sb["counters"]) and np.array_equal(sa["params"]["beta_pow"], sb["params"]["beta_pow"])
+    assert A_.stats() == B_.stats() and sa["params"]["updates"] == 10
+    if not per:                                                     # (a tree is not part of a state_dict: a fresh learner's would be the pushes')
+        C_ = _learner(gpu_ctx, cfg, params, replay)
+        C_.load_state_dict(mid)
+        C_.update(6)
+        sc = C_.state_dict()
+        assert _bits_equal(sa["params"], sc["params"]) and np.array_equal(sa["counters"], sc["counters"]) and C_.stats() == A_.stats()
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+def test_gpu_prioritised_replay(gpu_ctx, restore_settings):
+    """idx = per_sample_host on the device's tree; after an update the sampled leaves = per_priority_host of the device's own td and the inner sums
+    recomputed exactly; new rows enter at max_priority ** alpha; the weights reach the loss; a learner without per keeps its bits."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    per = learner.PERConfig(beta=0.5)
+    shape = SHAPES[1]
+    cfg, params, replay = _random_problem(shape, 51, per=per)
+    cfg0, _, _ = _random_problem(shape, 51)
+    L, U = _learner(gpu_ctx, cfg, params, replay), _learner(gpu_ctx, cfg0, params, replay)
+    host = learner.SumTreeHost(RING, per)
+    host.push(RING)
+    tree = L.priorities()
+    leaves = learner.per_leaves(RING)
+    assert np.array_equal(tree, host.nodes) and (tree[leaves - 1:leaves - 1 + RING] == per.max_priority ** per.alpha).all()
+    for u in range(3):
+        tree = L.priorities()
+        idx = learner.per_sample_host(tree, 11, u, cfg.batch, RING)
+        w = learner.per_weights_host(tree, idx, RING, per.beta)
+        rows = _rows(replay, cfg.n_obs)[idx]
+        assert np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
+        before = L.state_dict()["params"]
+        g = L.grads()
+        ls = L.last_sample()
+        ulps = np.abs(ls["weight"].astype(np.float64) - w.astype(np.float64)) / np.spacing(w).astype(np.float64)
+        assert np.array_equal(ls["idx"], idx) and ulps.max() <= 4 and ls["weight"].max() == 1.0       # (tests/test_per.py's bound for two fp64 pows)
+        w = ls["weight"]
+        if u > 0:
+            assert len(set(w.tolist())) > 1                         # the weights differ once priorities do
+        batch = learner.dqn_batch_from_rows(rows, cfg.n_obs)
+        _, i64 = learner.update_host_dqn(before, batch, cfg, "float64", weights=w, grads_only=True)
+        _, i32 = learner.update_host_dqn(before, batch, cfg, "float32", weights=w, grads_only=True)
+        assert all(_check_4x("per u%d grad %s" % (u, k), g[k], i32["grad"][k], i64["grad"][k]) for k in NAMES)
+        L.update(1)
+        ls = L.last_sample()
+        assert np.array_equal(ls["idx"], idx) and _check_4x("per u%d td" % u, ls["td"], i32["td"], i64["td"])
+        pri = learner.per_priority_host(ls["td"], per)
+        for r in range(cfg.batch):                                  # of rows with the same index the highest row wins
+            host.set(idx[r], pri[r])
+        assert np.array_equal(L.priorities(), host.nodes), u
+    # a learner without per draws the uniform rows, and differs
+    assert np.array_equal(U.minibatch().view(np.uint32), _minibatch_host(replay, cfg0)[0].view(np.uint32))
+    U.update(3)
+    assert not _bits_equal(U.state_dict()["params"], L.state_dict()["params"])
+    # pushes after updates: the new rows' leaves, the rest untouched
+    _fill(L, {k: v[:64] for k, v in replay.items()})
+    host.cursor = 0
+    host.push(64)
+    assert np.array_equal(L.priorities(), host.nodes)
+    with pytest.raises(RuntimeError):
+        U.priorities()
+    gpu_ctx.check_error()
+
+
+# ---- 5: the training loop ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_id,A", [("sumo-jerk-v0", 5), ("sumo-accel-v0", 20)])
+def test_gpu_train_dqn(env_id, A, gpu_ctx, restore_settings, tmp_path):
+    _capi()
+    import rl_mpc_lanemerging_amd as pkg
+    from rl_mpc_lanemerging_amd import learner, vec_env
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+
+    def run():
+        env = vec_env.MergeVecEnv(64, env_id=env_id, seed=2, ctx=gpu_ctx)
+        cfg = learner.DQNConfig(n_obs=env.obs_dim, h1=32, batch=50, capacity=256, replay_start=100, target_period=5, per=learner.PERConfig() if A == 5 else None)
+        L = learner.DQNLearner(env, cfg, seed=6)
+        first = L.state_dict()["params"]
+        res = learner.train_dqn(env, L, 640, updates_per_step=2, drain_every=4, eps_schedule=lambda i, n: 0.5)
+        env.check_error()
+        return L, first, res
+
+    L, first, res = run()
+    st, sd = L.stats(), L.state_dict()
+    assert res["steps"] == 10 and res["frames"] == 640 and set(res) == {"steps", "frames", "episodes", "mean_return", "returns", "takeover_share"}
+    assert st["updates"] == 2 * 9 and st["fill"] == 256 and np.isfinite(st["loss"])        # updates start once MORE than 100 frames were pushed: steps 2 ... 10
+    assert all(np.isfinite(sd["params"][s][k]).all() for s in ("q", "q_target", "q_m", "q_v") for k in NAMES)
+    assert not np.array_equal(sd["params"]["q"]["w1"], first["q"]["w1"]) and not np.array_equal(sd["params"]["q"]["b1"], first["q"]["b1"])
+    L2, _, res2 = run()
+    sd2 = L2.state_dict()
+    assert _bits_equal(sd["params"], sd2["params"]) and np.array_equal(sd["counters"], sd2["counters"]) and np.array_equal(res["returns"], res2["returns"])
+    path = L.export_q(str(tmp_path / "q.npz"))
+    with np.load(path) as z:
+        assert all(np.array_equal(z[k], sd["params"]["q"][k]) for k in NAMES) and np.array_equal(z["action_values"], L.action_values) and z["action_values"].size == A
+        table = pkg.Settings.JERK_VALUES_DQN if A == 5 else pkg.Settings.ACCELERATION_VALUES_DQN     # the reference's own tables (config.py:114-115)
+        assert np.array_equal(z["action_values"], np.array([table[i] for i in range(A)], dtype=np.float64)) and len(table) == A
+        assert (z["action_values"][0], z["action_values"][-1]) == ((-5.0, 5.0) if A == 5 else (-6.0, 4.5))
+    M = learner.DQNLearner((L.cfg.n_obs, A), learner.DQNConfig(n_obs=L.cfg.n_obs, h1=32, batch=50, capacity=256), init={k: np.load(path)[k] for k in NAMES}, ctx=gpu_ctx)
+    assert all(np.array_equal(M.state_dict()["params"]["q"][k], sd["params"]["q"][k]) for k in NAMES)
+    gpu_ctx.check_error()
+
+
+def test_smoke_and_benchmark_read_only_the_repository():
+    src = open(os.path.join(REPO, "__graft_entry__.py")).read()
+    smoke = src[src.index("def smoke"):]
+    assert "reference" not in smoke.replace("REFERENCE_DEFAULT", "")
+    bench = open(os.path.join(REPO, "scripts", "dqn_bench.py")).read()
+    assert "/root" not in bench and "reference/" not in bench

@@ -1,0 +1,217 @@
+"""The DQN learner without a GPU: header, library and binding agree on the stmpc_dqn_ entries; the host twins (``learner.update_host_dqn``,
+``dqn_targets_host``, ``dqn_epsilon``, ``dqn_act_host``) against the reference's own numbers (tests/golden/golden_dqn.npz, written by
+make_golden_dqn.py from the reference's ``get_targets`` and its SmoothL1 + Adam step) and against torch autograd; the refusals.
+
+The bound against the golden is the learner tests' rule for a float32 computation against its float64 twin: per tensor, in the max norm,
+|golden - twin64| <= max(4 x |twin32 - twin64|, 8 float32 ulps) -- the reference computed in float32, ``update_host_dqn("float32")`` is the yardstick."""
+import ctypes
+import math
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+
+from conftest import REPO, load_golden
+
+FLOOR = 8 * 2.0 ** -23          # 8 float32 ulps, relative
+NAMES = ("w0", "b0", "w1", "b1")
+
+
+def _capi():
+    import rl_mpc_lanemerging_amd as pkg
+    if pkg.build.needs_build():
+        pkg.build.build()
+    from rl_mpc_lanemerging_amd import _capi
+    return _capi
+
+
+def _rel_err(x, ref):
+    scale = np.abs(ref).max()
+    return float(np.abs(np.asarray(x, dtype=np.float64) - ref).max() / scale) if scale > 0 else float(np.abs(x).max())
+
+
+def _check_4x(label, have, f32, f64):
+    e, e32 = _rel_err(have, f64), _rel_err(f32, f64)
+    bound = max(4 * e32, FLOOR)
+    print("%-28s golden %.3e  float32 twin %.3e  bound %.3e" % (label, e, e32, bound))
+    return e <= bound
+
+
+def test_header_library_and_binding_agree_on_the_dqn_learner():
+    capi = _capi()
+    from test_host_cpu import _header_struct_fields
+    lib = capi.load()
+    header = open(os.path.join(REPO, "include", "stmpc.h")).read()
+    declared = {n for n in re.findall(r"\b(stmpc_[a-z_0-9]+)\s*\(", header) if n.startswith("stmpc_dqn_")}
+    assert declared == {"stmpc_dqn_" + n for n in ("create", "destroy", "set_params", "get_params", "set_state", "get_state", "push_device", "act_device",
+                                                    "update_device", "grads_device", "targets_device", "gather_device", "stats_device", "per_enable",
+                                                    "per_tree_read", "per_last_device", "padded_read")}
+    assert declared == {n for n in capi.EXPORTS if n.startswith("stmpc_dqn_")}
+    all_declared = set(re.findall(r"\b(stmpc_[a-z_0-9]+)\s*\(", header)) - {"stmpc_params", "stmpc_stats", "stmpc_ctx"}
+    assert all_declared == set(capi.EXPORTS)
+    for name in declared:
+        assert getattr(lib, name) is not None and getattr(lib, name).argtypes is not None, name
+    flat = " ".join(header.split())
+    for name, val in (("STMPC_DQN_Q", 0), ("STMPC_DQN_Q_V", len(capi.DQN_SLOTS) - 1), ("STMPC_DQN_GRAD", capi.DQN_GRAD), ("STMPC_DQN_Q_TARGET", capi.DQN_SLOTS.index("q_target")),
+                      ("STMPC_ABI_VERSION", 8)):
+        assert "#define %s %d" % (name, val) in flat, name
+    assert capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8
+
+
+def test_dqn_cfg_struct_layout_matches_header():
+    capi = _capi()
+    from test_host_cpu import _header_struct_fields
+    ctype_of = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double}
+    want = _header_struct_fields("stmpc_dqn_cfg")
+    have = list(capi.DQNCfg._fields_)
+    assert [n for n, _ in want] == [n for n, _ in have]
+    assert [ctype_of[t] for _, t in want] == [t for _, t in have]
+    assert ctypes.sizeof(capi.DQNCfg) == 8 * 4 + 8 + 8 + 6 * 8
+
+
+def _golden_case():
+    from rl_mpc_lanemerging_amd import learner
+    g = load_golden("golden_dqn.npz")
+    net = {k: g["q_" + k] for k in NAMES}
+    params = learner.new_params_dqn(net)
+    params["q_target"] = {k: g["t_" + k] for k in NAMES}
+    batch = {"s": g["s"], "a": g["a"], "r": g["r"], "s2": g["s2"], "mask": g["mask"]}
+    mk = lambda **kw: learner.DQNConfig(n_obs=g["s"].shape[1], n_actions=g["q_b1"].size, h1=g["q_b0"].size, batch=g["s"].shape[0], gamma=float(g["gamma"]),
+                                        lr=float(g["lr"]), clip_min=float(g["clip"][0]), clip_max=float(g["clip"][1]), **kw)
+    return g, params, batch, mk
+
+
+def test_update_host_dqn_against_the_reference_golden():
+    """Targets under DOUBLE_DQN True / False / with CLIP_TARGETS, the double-DQN argmax indices, q_values, the gradients and the weights after one
+    Adam step: the reference's own values against ``update_host_dqn("float64")`` under the module text's bound."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    g, params, batch, mk = _golden_case()
+    assert g["s"].shape == (50, 20) and int((g["mask"] == 0).sum()) >= 8
+    assert learner.DQNConfig().h1 == g["q_b0"].size == 256 and learner.DQNConfig().batch == 50 and learner.DQNConfig().gamma == float(g["gamma"]) == 0.999
+    assert learner.DQNConfig().lr == float(g["lr"]) == 2e-4 and learner.DQNConfig().target_period == 500 and learner.DQNConfig().capacity == 50000
+    assert learner.DQNConfig().double and not learner.DQNConfig().clip_targets and learner.DQNConfig().per is None
+    ok = True
+    for key, kw in (("targets_double", dict(double=True)), ("targets_plain", dict(double=False)), ("targets_clip", dict(double=True, clip_targets=True))):
+        t64, t32 = (learner.dqn_targets_host(params, batch, mk(**kw), d) for d in ("float64", "float32"))
+        ok &= _check_4x(key, g[key], t32[:, 2], t64[:, 2])
+        if key == "targets_double":
+            live = g["mask"] > 0
+            assert np.array_equal(t64[live, 0].astype(np.int64), g["best"][live]) and (g["best"][~live] == -1).all()
+        if key == "targets_clip":                                   # the clip bites, on both sides
+            gq = float(g["gamma"]) * t64[:, 1]
+            assert (gq[g["mask"] > 0] > g["clip"][1]).any() and (gq[g["mask"] > 0] < g["clip"][0]).any()
+    cfg = mk(double=True)
+    (p64, i64), (p32, i32) = (learner.update_host_dqn(params, batch, cfg, d) for d in ("float64", "float32"))
+    assert (np.abs(i64["td"]) > 1).any() and (np.abs(i64["td"]) < 1).any()      # both branches of the Huber loss
+    ok &= _check_4x("q_values", g["q_values"], i32["q_values"], i64["q_values"])
+    ok &= _check_4x("loss", g["loss"].reshape(1), np.array([i32["loss"]]), np.array([i64["loss"]]))
+    for k in NAMES:
+        ok &= _check_4x("grad " + k, g["g_" + k], i32["grad"][k], i64["grad"][k])
+        ok &= _check_4x("after " + k, g["after_" + k], p32["q"][k], p64["q"][k])
+        assert np.abs(g["after_" + k] - g["q_" + k]).max() > 0.5 * float(g["lr"])       # (the first Adam step moves a weight by about lr)
+        assert np.array_equal(p64["q_target"][k], g["t_" + k])      # update 1 of 500: the target stays
+    assert ok and p64["updates"] == 1
+
+
+@pytest.mark.parametrize("double,clip", [(True, False), (False, False), (True, True)])
+def test_update_host_dqn_against_torch_autograd(double, clip):
+    """The twin's gradient against a second statement with nn.Linear modules, nn.SmoothL1Loss and loss.backward(): random data with rows in the linear
+    branch of the Huber loss, importance weights and terminal rows; float64, 1e-12 relative.  Three steps with torch.optim.Adam follow the twin's."""
+    _capi()
+    import torch
+    from torch import nn
+    from rl_mpc_lanemerging_amd import learner
+    rng = np.random.default_rng(5 + 2 * double + clip)
+    n_obs, h1, A, B = 12, 24, 7, 33
+    cfg = learner.DQNConfig(n_obs=n_obs, n_actions=A, h1=h1, batch=B, gamma=0.9, lr=1e-3, target_period=2, double=double, clip_targets=clip, clip_min=-0.3,
+                            clip_max=0.2)
+    params = learner.new_params_dqn(learner.init_q_net(n_obs, h1, A, rng))
+    params["q_target"] = learner.init_q_net(n_obs, h1, A, rng)
+    mods = []
+    for slot in ("q", "q_target"):
+        m = nn.Sequential(nn.Linear(n_obs, h1), nn.ReLU(), nn.Linear(h1, A)).double()
+        with torch.no_grad():
+            for p, k in zip(m.parameters(), NAMES):
+                p.copy_(torch.tensor(params[slot][k], dtype=torch.float64))
+        mods.append(m)
+    q, qt = mods
+    opt = torch.optim.Adam(q.parameters(), lr=cfg.lr, betas=(cfg.beta1, cfg.beta2), eps=cfg.eps)
+    for step in range(3):
+        batch = {"s": rng.normal(size=(B, n_obs)), "s2": rng.normal(size=(B, n_obs)), "a": rng.integers(0, A, B), "r": rng.normal(size=B) * 2,
+                 "mask": (rng.random(B) > 0.25).astype(np.float64)}
+        w = rng.uniform(0.2, 1.0, B) if step != 1 else None
+        assert (batch["mask"] == 0).any()
+        new, info = learner.update_host_dqn(params, batch, cfg, "float64", weights=w)
+        assert (np.abs(info["td"]) > 1).any() and (np.abs(info["td"]) < 1).any()
+        T = lambda a: torch.tensor(a, dtype=torch.float64)
+        with torch.no_grad():
+            s2 = T(batch["s2"])
+            nxt = torch.gather(qt(s2), 1, torch.argmax(q(s2), 1, keepdim=True)).flatten() if double else qt(s2).max(1)[0]
+            gq = cfg.gamma * nxt
+            if clip:
+                gq = gq.clamp(cfg.clip_min, cfg.clip_max)
+            y = T(batch["r"]) + T(batch["mask"]) * gq
+        qv = torch.gather(q(T(batch["s"])), 1, torch.tensor(batch["a"])[:, None]).flatten()
+        loss = nn.SmoothL1Loss()(qv, y) if w is None else (T(w) * nn.SmoothL1Loss(reduction="none")(qv, y)).mean()
+        opt.zero_grad()
+        loss.backward()
+        assert np.abs(info["targets"][:, 2] - y.numpy()).max() <= 1e-12 * np.abs(y.numpy()).max()
+        for p, k in zip(q.parameters(), NAMES):
+            assert np.abs(info["grad"][k] - p.grad.numpy()).max() <= 1e-12 * np.abs(p.grad.numpy()).max(), (step, k)
+        opt.step()
+        if (step + 1) % cfg.target_period == 0:
+            qt.load_state_dict(q.state_dict())
+        for m, slot in ((q, "q"), (qt, "q_target")):
+            for p, k in zip(m.parameters(), NAMES):
+                assert np.abs(new[slot][k] - p.detach().numpy()).max() <= 1e-12 * np.abs(p.detach().numpy()).max(), (step, slot, k)
+        assert np.array_equal(new["q_target"]["w1"], new["q"]["w1"]) == ((step + 1) % 2 == 0)
+        params = new
+    assert params["updates"] == 3 and np.allclose(params["beta_pow"], [0.9 ** 3, 0.999 ** 3])
+
+
+def test_dqn_epsilon_is_the_references_decay():
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    for it in (0, 29999, 30000, 300000):
+        assert learner.dqn_epsilon(it) == 0.1 + (1.0 - 0.1) * np.exp(-0.25 * np.floor(it / 30000))     # dqn.py:275-276 with config.py's constants
+    assert learner.dqn_epsilon(0) == learner.dqn_epsilon(29999) == 1.0 and learner.dqn_epsilon(30000) < 1.0
+    assert abs(learner.dqn_epsilon(300000) - (0.1 + 0.9 * math.exp(-2.5))) < 1e-15
+
+
+def test_dqn_act_host_draws():
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    for A in (5, 20, 17):
+        ex0, _ = learner.dqn_act_host(7, 0, 200, 0.0, A)
+        ex1, idx1 = learner.dqn_act_host(7, 0, 200, 1.0, A)
+        assert not ex0.any() and ex1.all() and idx1.min() >= 0 and idx1.max() == A - 1 and len(set(idx1.tolist())) == A
+        exq, idxq = learner.dqn_act_host(7, 0, 200, 0.25, A)
+        assert 20 < exq.sum() < 80 and np.array_equal(idxq, idx1)   # the index does not depend on eps
+        assert not np.array_equal(learner.dqn_act_host(7, 1, 200, 0.25, A)[0], exq)      # the call number is part of the hash
+    # u < eps in integer arithmetic: the draw's 24 bits against float32(eps) * 2^24
+    h = learner.hash3(7 ^ learner.DQN_STREAM, 0, 3)
+    u = (h >> 40) * 2.0 ** -24
+    assert learner.dqn_act_host(7, 0, 4, float(np.nextafter(np.float32(u), np.float32(2))), 5)[0][3] and not learner.dqn_act_host(7, 0, 4, u, 5)[0][3]
+
+
+def test_dqn_refusals():
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    with pytest.raises(ValueError, match="discrete"):
+        learner.DQNLearner(types.SimpleNamespace(continuous=True, obs_dim=20))
+    with pytest.raises(ValueError, match="n_actions"):
+        learner.DQNLearner((20, 0))
+    with pytest.raises(ValueError, match="n_obs"):
+        learner.DQNLearner((32, 5), learner.DQNConfig(n_obs=32))
+    with pytest.raises(ValueError, match="target_period"):
+        learner.DQNLearner((20, 5), learner.DQNConfig(target_period=0))
+    with pytest.raises(ValueError, match="PERConfig"):
+        learner.DQNConfig(per=0.5)
+    # ... and the library's own, on the host, before any device call
+    capi = _capi()
+    lib, h = capi.load(), ctypes.c_void_p()
+    fake_ctx = ctypes.c_void_p()
+    assert lib.stmpc_dqn_create(fake_ctx, ctypes.byref(learner.DQNConfig(n_actions=5).to_c(0)), ctypes.byref(h)) != 0      # NULL context
