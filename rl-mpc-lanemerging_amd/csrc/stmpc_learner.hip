@@ -1,5 +1,10 @@
-// stmpc_learner.hip -- the DDPG learner and its population (stmpc_ddpg_*, stmpc_ddpg_pop_*), the TD3 learner on top of it and its population (stmpc_td3_*, stmpc_pop_td3_*), prioritised replay for the two lone learners (stmpc_per_*) and for the two populations (stmpc_pop_per_*), actors that view a learner's networks
-// (stmpc_actor_view_ddpg), the population of actors (stmpc_actor_pop_*) and the DQN learner for the discrete envs (stmpc_dqn_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
+// stmpc_learner.hip -- the learners' host code.  What they are made of comes first: a replay store (struct Replay: ring, counters, tickets, sum tree),
+// a network's and a workspace's buffers (net_build, ws_build), the slot layout as a list of segments (slot_layout, slot_set, slot_get) and the launch
+// geometry (struct Grid).  Then the handles, each with ONE function that derives its device structs from what it owns: the DDPG learner (stmpc_ddpg_*,
+// ddpg_refresh), the TD3 learner on a DDPG learner as base plus critic 2 (stmpc_td3_*, td3_refresh), prioritised replay for the two (stmpc_per_*), their
+// populations on one skeleton (struct PopCore; stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_per_*; pop_upload, td3_pop_upload), actors that view a
+// learner's networks and their population (stmpc_actor_view_ddpg, stmpc_actor_pop_*), and the DQN learner for the discrete envs (stmpc_dqn_*), which
+// holds a replay store, one network and one workspace of its own.  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
 #include "stmpc_per_kernels.hpp"
@@ -8,45 +13,241 @@
 #include "stmpc_td3_pop_kernels.hpp"
 #include "stmpc_per_pop_kernels.hpp"
 #include "stmpc_actor_pop_kernels.hpp"
+#include "stmpc_dqn_kernels.hpp"
 
-// ---- DDPG learner (stmpc_ddpg_*): replay ring, fused update, acting; kernels in stmpc_ddpg_kernels.hpp -------------------------------------------
-struct stmpc_ddpg {
-    int device = 0;
-    stmpc_ddpg_cfg cfg{};
-    DdpgDev dev{};
-    DevBuf netbuf[2][13], ring, cnt, tick, ws[7];
-    int h1p = 0, h2p = 0, np = 0, Bp = 0;
-    size_t lds = 0;
-    bool td3_base = false;          // lent by a stmpc_td3 (stmpc_td3_base): an update or gradients of this handle alone would leave critic 2 behind
-    struct stmpc_td3 *td3_owner = nullptr;  // that stmpc_td3: it holds copies of dev (its two views), which stmpc_per_enable has to follow
-    bool pop_member = false;        // owned by a population, whose device table holds a copy of dev
-    bool per = false;               // prioritised replay (stmpc_per_enable, stmpc_pop_per_enable_*): dev.tree ... dev.per_L are set
-    DevBuf per_tree, per_idx, per_aw, per_atd, per_atd2;    // (per_atd2: critic 2's Q - y, when td3_owner)
-    int n_in(int which) const { return cfg.n_obs + 1 + which; }
-    int64_t slot_len(int which) const { const int64_t n = n_in(which); return (int64_t)cfg.h1 * n + cfg.h1 + (int64_t)cfg.h2 * cfg.h1 + cfg.h2 + cfg.h2 + 1; }
-};
-
+// ---- the parts every learner is made of ---------------------------------------------------------------------------------------------------------
 namespace {
 int ddpg_zero(DevBuf &b, size_t bytes) {
     TRY(b.ensure(bytes));
     HIPCHK(hipMemset(b.p, 0, bytes));
     return STMPC_OK;
 }
-float *ddpg_slot_ptr(stmpc_ddpg *l, int slot) {
-    const DdpgNet &n = slot >= 4 ? l->dev.q : l->dev.pi;
-    switch (slot & 3) { case 0: return n.w; case 1: return n.wt; case 2: return n.m; default: return n.v; }
+// device -> host behind everything queued on the device (synchronises)
+int read_back(int device, void *host, const void *dev, size_t bytes) {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());
+    if (bytes) HIPCHK(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+    return STMPC_OK;
 }
-// slot layout (unpadded) <-> padded layout, on the host
-void ddpg_pad(const stmpc_ddpg *l, int n_in, const float *flat, std::vector<float> &pad, bool to_pad, float *flat_out) {
-    const int h1 = l->cfg.h1, h2 = l->cfg.h2, h1p = l->h1p, h2p = l->h2p;
-    size_t i = 0;
-    auto item = [&](size_t p) { if (to_pad) pad[p] = flat[i]; else flat_out[i] = pad[p]; ++i; };
-    for (int n = 0; n < h1; ++n) for (int k = 0; k < n_in; ++k) item((size_t)n * AT_KIN + k);
-    for (int n = 0; n < h1; ++n) item((size_t)dg_o_b0(h1p) + n);
-    for (int n = 0; n < h2; ++n) for (int k = 0; k < h1; ++k) item((size_t)dg_o_w1(h1p) + (size_t)n * h1p + k);
-    for (int n = 0; n < h2; ++n) item((size_t)dg_o_b1(h1p, h2p) + n);
-    for (int n = 0; n < h2; ++n) item((size_t)dg_o_w2(h1p, h2p) + n);
-    item((size_t)dg_o_b2(h1p, h2p));
+int per_check_cfg(const stmpc_per_cfg *g) {
+    if (!(g->min_priority > 0) || !(g->max_priority >= g->min_priority) || !std::isfinite(g->max_priority) || !(g->alpha >= 0) || !std::isfinite(g->alpha) ||
+        !(g->beta >= 0) || !std::isfinite(g->beta))
+        return fail(STMPC_EINVAL, "prioritised replay needs min_priority > 0, max_priority >= min_priority, alpha >= 0 and beta >= 0, all finite");
+    return STMPC_OK;
+}
+
+// The replay store of one learner: the ring, the counters, the tickets, and -- once attach() ran -- prioritised replay's tree, idx, weights and td.
+struct Replay {
+    int device = 0, batch = 0, Bp = 0, capacity = 0;
+    bool per = false;               // prioritised replay (stmpc_per_enable, stmpc_pop_per_enable_*, stmpc_dqn_per_enable)
+    DevBuf ring, cnt, tick, tree, idx, aw, atd, atd2;       // (atd2: critic 2's Q - y, on a TD3 learner's base)
+    stmpc_per_cfg pcfg{};
+    long long leaves = 0;
+
+    int create(int dev, int B, int cap) {
+        device = dev; batch = B; Bp = (B + 15) & ~15; capacity = cap;
+        TRY(ddpg_zero(ring, (size_t)cap * DG_ROW * sizeof(float)));
+        TRY(ddpg_zero(cnt, DG_NCNT * sizeof(long long)));
+        return ddpg_zero(tick, DG_NTICK * sizeof(unsigned int));
+    }
+    // its pointers and constants into a learner's device struct
+    void wire(DdpgDev &d) const {
+        d.ring = ring.as<float>(); d.cnt = cnt.as<long long>(); d.tick = tick.as<unsigned int>(); d.capacity = capacity;
+        if (!per) return;
+        d.tree = tree.as<double>(); d.idx = idx.as<long long>(); d.aw = aw.as<float>(); d.atd = atd.as<float>();
+        d.per_alpha = pcfg.alpha; d.per_beta = pcfg.beta; d.per_min = pcfg.min_priority; d.per_max = pcfg.max_priority; d.per_L = leaves;
+    }
+    int get_counters(int64_t *counters) const {
+        long long cn[DG_NCNT];
+        TRY(read_back(device, cn, cnt.p, sizeof cn));
+        for (int i = 0; i < DG_NCNT; ++i) counters[i] = cn[i];
+        return STMPC_OK;
+    }
+    // (synchronises; the caller's copies of the beta powers follow on the selected device)
+    int set_counters(const int64_t *counters) {
+        if (counters[DG_CURSOR] < 0 || counters[DG_CURSOR] >= capacity || counters[DG_FILL] < 0 || counters[DG_FILL] > capacity || counters[DG_UPDATES] < 0 ||
+            counters[DG_ACTS] < 0 || counters[DG_FRAMES] < 0) return fail(STMPC_EINVAL, "counters out of range");
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipDeviceSynchronize());
+        long long cn[DG_NCNT];
+        if (per) {                                                   // the tree's leaves follow the ring's cursor and fill
+            HIPCHK(hipMemcpy(cn, cnt.p, sizeof cn, hipMemcpyDeviceToHost));
+            if (cn[DG_CURSOR] != counters[DG_CURSOR] || cn[DG_FILL] != counters[DG_FILL])
+                return fail(STMPC_EINVAL, "prioritised replay is enabled: the ring's cursor and fill cannot be set (the priorities belong to the rows pushed)");
+        }
+        for (int i = 0; i < DG_NCNT; ++i) cn[i] = i <= DG_FRAMES ? counters[i] : 0;
+        HIPCHK(hipMemcpy(cnt.p, cn, sizeof cn, hipMemcpyHostToDevice));
+        return STMPC_OK;
+    }
+    int read_rows(int64_t first, int64_t count, float *rows) const {
+        if (!rows) return fail(STMPC_EINVAL, "NULL argument");
+        if (first < 0 || count < 0 || first + count > capacity) return fail(STMPC_EINVAL, "rows outside the ring");
+        return read_back(device, rows, ring.as<float>() + (size_t)first * DG_ROW, (size_t)count * DG_ROW * sizeof(float));
+    }
+    int read_tree(int64_t first, int64_t count, double *nodes) const {
+        if (!nodes) return fail(STMPC_EINVAL, "NULL argument");
+        if (!per) return fail(STMPC_EINVAL, "prioritised replay is not enabled on this learner");
+        if (first < 0 || count < 0 || first + count > 2 * leaves - 1) return fail(STMPC_EINVAL, "nodes outside the tree");
+        return read_back(device, nodes, tree.as<double>() + first, (size_t)count * sizeof(double));
+    }
+    // prioritised replay's two checks on the store: not enabled yet, and the ring empty (synchronises)
+    int check_empty() const {
+        if (per) return fail(STMPC_EINVAL, "prioritised replay is already enabled on this learner");
+        long long cn[DG_NCNT];
+        TRY(read_back(device, cn, cnt.p, sizeof cn));
+        if (cn[DG_FILL] != 0 || cn[DG_CURSOR] != 0) return fail(STMPC_EINVAL, "prioritised replay can be enabled on an empty ring only (fill is " + std::to_string(cn[DG_FILL]) + ")");
+        return STMPC_OK;
+    }
+    // the tree, idx, weights and td buffers of a store that passed both checks (second_td: atd2 too); the owner then wires its device structs anew
+    int attach(const stmpc_per_cfg *g, bool second_td) {
+        long long L = 1;
+        while (L < capacity) L <<= 1;
+        TRY(ddpg_zero(tree, (size_t)(2 * L - 1) * sizeof(double)));
+        TRY(ddpg_zero(idx, (size_t)Bp * sizeof(long long)));
+        TRY(ddpg_zero(aw, (size_t)Bp * sizeof(float)));
+        TRY(ddpg_zero(atd, (size_t)Bp * sizeof(float)));
+        if (second_td) TRY(ddpg_zero(atd2, (size_t)Bp * sizeof(float)));
+        pcfg = *g; leaves = L; per = true;
+        return STMPC_OK;
+    }
+};
+
+// prioritised replay: the sampling step in front of a pass that gathers (nothing on a store that samples uniformly); d: the device struct wired to rp
+void per_launch_sample(const Replay &rp, const DdpgDev &d, int gate, hipStream_t st) {
+    if (rp.per) hipLaunchKernelGGL(k_per_sample, dim3(1), dim3(PER_THREADS), 0, st, d, rp.batch, rp.Bp, gate);
+}
+// ... and the priority update behind the critic pass
+void per_launch_update(const Replay &rp, const DdpgDev &d, hipStream_t st) {
+    if (rp.per) hipLaunchKernelGGL(k_per_update, dim3(1), dim3(PER_THREADS), 0, st, d, (const float *)rp.atd2.as<float>(), rp.batch, 1);
+}
+int per_last(const Replay &rp, const DdpgDev &d, int64_t *d_idx, float *d_td, float *d_weight, void *stream) {
+    if (!d_idx || !d_td || !d_weight) return fail(STMPC_EINVAL, "NULL argument");
+    if (!rp.per) return fail(STMPC_EINVAL, "prioritised replay is not enabled on this learner");
+    HIPCHK(hipSetDevice(rp.device));
+    hipLaunchKernelGGL(k_per_last, dim3((rp.batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, d, (const float *)rp.atd2.as<float>(), rp.batch, (long long *)d_idx,
+                       d_td, d_weight);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+int replay_gather(const Replay &rp, const DdpgDev &d, float *d_rows, void *stream) {
+    HIPCHK(hipSetDevice(rp.device));
+    per_launch_sample(rp, d, 0, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_replay_gather, dim3((rp.batch * DG_ROW + 255) / 256), dim3(256), 0, (hipStream_t)stream, d, rp.batch, d_rows);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+// One network's eleven buffers for the padded widths (h1p, h2p): net_wire points a DdpgNet at them, net_build allocates them first and starts Adam's
+// beta powers at beta^0.
+void net_wire(DdpgNet &n, const DevBuf (&buf)[11], int n_in) {
+    float **ptr[11] = {&n.w, &n.wt, &n.m, &n.v, &n.g, &n.p0, &n.p1, &n.p1t, &n.t0, &n.t1, &n.bpow};
+    for (int i = 0; i < 11; ++i) *ptr[i] = buf[i].as<float>();
+    n.n_in = n_in;
+}
+int net_build(DevBuf (&buf)[11], DdpgNet &n, int n_in, int h1p, int h2p) {
+    const size_t np = (size_t)dg_nparam(h1p, h2p), l0 = (size_t)h1p * AT_KIN, l1 = (size_t)h2p * h1p;
+    const size_t len[11] = {np, np, np, np, np, l0, l1, l1, l0, l1, 4};
+    for (int i = 0; i < 11; ++i) TRY(ddpg_zero(buf[i], len[i] * sizeof(float)));
+    net_wire(n, buf, n_in);
+    const float one[4] = {1.f, 1.f, 0.f, 0.f};                       // beta^0
+    if (hipMemcpy(n.bpow, one, sizeof one, hipMemcpyHostToDevice) != hipSuccess) return fail(STMPC_EHIP, "hipMemcpy of the beta powers failed");
+    return STMPC_OK;
+}
+// ... and one minibatch's seven workspace buffers
+void ws_wire(DdpgDev &d, const DevBuf (&buf)[7]) {
+    float **ptr[7] = {&d.aX, &d.aH1, &d.aH2, &d.aD2, &d.aD1, &d.adz, &d.arow};
+    for (int i = 0; i < 7; ++i) *ptr[i] = buf[i].as<float>();
+}
+int ws_build(DevBuf (&buf)[7], DdpgDev &d, int Bp, int h1p, int h2p) {
+    const size_t B = (size_t)Bp, len[7] = {B * AT_KIN, B * h1p, B * h2p, B * h2p, B * h1p, B, B * 2};
+    for (int i = 0; i < 7; ++i) TRY(ddpg_zero(buf[i], len[i] * sizeof(float)));
+    ws_wire(d, buf);
+    return STMPC_OK;
+}
+
+// The slot layout (unpadded, what the C-ABI hands over) against the padded one as data: rows x cols values, row r at pad[off + r * stride].
+struct Seg { int rows, cols; size_t off, stride; };
+// W0, b0, W1, b1 and -- with a third layer (the DDPG nets; not the Q-network) -- W2, b2
+std::vector<Seg> slot_layout(int n_in, int h1, int h2, int h1p, int h2p, bool third) {
+    std::vector<Seg> lay = {{h1, n_in, 0, AT_KIN}, {1, h1, (size_t)dg_o_b0(h1p), 0}, {h2, h1, (size_t)dg_o_w1(h1p), (size_t)h1p}, {1, h2, (size_t)dg_o_b1(h1p, h2p), 0}};
+    if (third) { lay.push_back({1, h2, (size_t)dg_o_w2(h1p, h2p), 0}); lay.push_back({1, 1, (size_t)dg_o_b2(h1p, h2p), 0}); }
+    return lay;
+}
+int64_t slot_len(const std::vector<Seg> &lay) {
+    int64_t n = 0;
+    for (const Seg &s : lay) n += (int64_t)s.rows * s.cols;
+    return n;
+}
+// one slot between the two layouts, on the host, either way
+void slot_move(const std::vector<Seg> &lay, float *flat, float *pad, bool to_pad) {
+    for (const Seg &s : lay)
+        for (int r = 0; r < s.rows; ++r, flat += s.cols) {
+            float *p = pad + s.off + (size_t)r * s.stride;
+            if (to_pad) memcpy(p, flat, s.cols * sizeof(float)); else memcpy(flat, p, s.cols * sizeof(float));
+        }
+}
+int slot_args(const void *handle, const void *values, int slot, int n_slots) {
+    return !handle || !values || slot < 0 || slot >= n_slots ? fail(STMPC_EINVAL, "NULL argument or slot out of range") : STMPC_OK;
+}
+float *net_slot(const DdpgNet &n, int i) { float *const p[4] = {n.w, n.wt, n.m, n.v}; return p[i]; }
+// a *_set_params entry behind slot_args: d_slot is the slot's padded array of np floats; repack() launches the kernel that makes the packed copies
+// follow the parameters, which slots 0 and 1 of a net (online, target) have
+template <class F> int slot_set(int device, const std::vector<Seg> &lay, size_t np, float *d_slot, const float *values, int64_t count, bool packed, F repack) {
+    if (count != slot_len(lay)) return fail(STMPC_EINVAL, "count is not the length of this slot");
+    HIPCHK(hipSetDevice(device));
+    std::vector<float> pad(np, 0.f);
+    slot_move(lay, const_cast<float *>(values), pad.data(), true);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(d_slot, pad.data(), np * sizeof(float), hipMemcpyHostToDevice));
+    if (packed) {
+        repack();
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return STMPC_OK;
+}
+int slot_get(int device, const std::vector<Seg> &lay, size_t np, const float *d_slot, float *values, int64_t count) {
+    if (count != slot_len(lay)) return fail(STMPC_EINVAL, "count is not the length of this slot");
+    std::vector<float> pad(np, 0.f);
+    TRY(read_back(device, pad.data(), d_slot, np * sizeof(float)));
+    slot_move(lay, values, pad.data(), false);
+    return STMPC_OK;
+}
+
+// The launch geometry of a learner: minibatch tiles, weight-gradient jobs (dW1, dW0, db1, db0 and, with a third layer, dW2, db2) and Adam's blocks.
+struct Grid { int tiles, jobs, ablocks; };
+Grid make_grid(int Bp, int h1p, int h2p, bool third) {
+    const int t1 = h2p / 16, t0 = h1p / 16;
+    return {Bp / AT_TM, t1 * t0 + 2 * t0 + t1 + t0 + (third ? t1 + 1 : 0), ((third ? dg_nparam(h1p, h2p) : dq_nparam(h1p, h2p)) + 255) / 256};
+}
+// blocks of a push of `rows` rows (of one member)
+int push_blocks(int rows) {
+    const long long blocks = ((long long)rows * DG_ROW + 255) / 256;
+    return (int)(blocks < 1024 ? blocks : 1024);
+}
+}  // namespace
+
+// ---- DDPG learner (stmpc_ddpg_*): replay ring, fused update, acting; kernels in stmpc_ddpg_kernels.hpp -------------------------------------------
+struct stmpc_ddpg {
+    stmpc_ddpg_cfg cfg{};
+    DdpgDev dev{};                  // the constants (stmpc_ddpg_create), the nets and the workspace; the replay's part is ddpg_refresh's
+    Replay rp;
+    DevBuf net[2][11], ws[7];       // actor, critic; workspace
+    std::vector<Seg> lay[2];        // the actor's and the critic's slot layout
+    int h1p = 0, h2p = 0, np = 0;
+    size_t lds = 0;
+    Grid grid{};
+    bool td3_base = false;          // lent by a stmpc_td3 (stmpc_td3_base): an update or gradients of this handle alone would leave critic 2 behind
+    struct stmpc_td3 *td3_owner = nullptr;  // that stmpc_td3: its two views derive from dev (td3_refresh)
+    bool pop_member = false;        // owned by a population, whose device table holds a copy of dev
+};
+
+namespace {
+void td3_refresh(struct stmpc_td3 *t);
+// dev's replay part from rp, and what derives from dev
+void ddpg_refresh(stmpc_ddpg *l) {
+    l->rp.wire(l->dev);
+    if (l->td3_owner) td3_refresh(l->td3_owner);
 }
 // dynamic LDS of the three per-tile kernels of a learner (pop = false) or of a population (true): raised, never lowered (raise_dynamic_lds)
 int ddpg_raise_lds(bool pop, int device, size_t lds) {
@@ -66,22 +267,17 @@ double ddpg_gauss_host(unsigned long long h, uint32_t *draw1, uint32_t *draw2) {
     const volatile float theta = 6.2831855f * ((float)u2 * 5.9604644775390625e-8f);      // the float32 product the kernel forms
     return sqrt(-2.0 * log(f1)) * cos((double)theta);
 }
-// prioritised replay: the sampling step in front of a pass that gathers (nothing on a learner that samples uniformly)
-void per_launch_sample(const stmpc_ddpg *l, int gate, hipStream_t st) {
-    if (l->per) hipLaunchKernelGGL(k_per_sample, dim3(1), dim3(PER_THREADS), 0, st, l->dev, l->cfg.batch, l->Bp, gate);
-}
-// ... and the priority update behind the critic pass
-void per_launch_update(const stmpc_ddpg *l, hipStream_t st) {
-    if (l->per) hipLaunchKernelGGL(k_per_update, dim3(1), dim3(PER_THREADS), 0, st, l->dev, (const float *)l->per_atd2.as<float>(), l->cfg.batch, 1);
-}
 void ddpg_launch_grads(stmpc_ddpg *l, int which, int gate, hipStream_t st) {
-    const int tiles = l->Bp / AT_TM, t1 = l->h2p / 16, t0 = l->h1p / 16;
-    if (which) hipLaunchKernelGGL(k_ddpg_critic_fwd, dim3(tiles), dim3(AT_THREADS), l->lds, st, l->dev, l->cfg.batch, gate);
-    else hipLaunchKernelGGL(k_ddpg_actor_fwd, dim3(tiles), dim3(AT_THREADS), l->lds, st, l->dev, l->cfg.batch, gate);
-    hipLaunchKernelGGL(k_ddpg_wgrad, dim3(t1 * t0 + 2 * t0 + t1 + t0 + t1 + 1), dim3(64 * DG_WG_WAVES), 0, st, l->dev, which, l->Bp, gate);
+    if (which) hipLaunchKernelGGL(k_ddpg_critic_fwd, dim3(l->grid.tiles), dim3(AT_THREADS), l->lds, st, l->dev, l->cfg.batch, gate);
+    else hipLaunchKernelGGL(k_ddpg_actor_fwd, dim3(l->grid.tiles), dim3(AT_THREADS), l->lds, st, l->dev, l->cfg.batch, gate);
+    hipLaunchKernelGGL(k_ddpg_wgrad, dim3(l->grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, l->dev, which, l->rp.Bp, gate);
 }
-void ddpg_launch_adam(stmpc_ddpg *l, int which, float lr, int mode, int bump, hipStream_t st) {
-    hipLaunchKernelGGL(k_ddpg_adam, dim3((l->np + 255) / 256), dim3(256), 0, st, l->dev, which, lr, mode, bump, 1);
+// k_ddpg_adam on net `which` of the device struct d of a learner with l's shape (l->dev, or a TD3 learner's second view)
+void ddpg_launch_adam(const stmpc_ddpg *l, const DdpgDev &d, int which, float lr, int mode, int bump, hipStream_t st) {
+    hipLaunchKernelGGL(k_ddpg_adam, dim3(l->grid.ablocks), dim3(256), 0, st, d, which, lr, mode, bump, 1);
+}
+void ddpg_launch_unpad(const stmpc_ddpg *l, int which, const float *d_grad, float *d_out, hipStream_t st) {
+    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, (which ? l->dev.q : l->dev.pi).n_in, d_grad, d_out);
 }
 }  // namespace
 
@@ -96,91 +292,54 @@ int stmpc_ddpg_create(stmpc_ctx *c, const stmpc_ddpg_cfg *g, stmpc_ddpg **out) {
     if (!(g->gamma >= 0) || !(g->tau >= 0 && g->tau <= 1) || !(g->beta1 >= 0 && g->beta1 < 1) || !(g->beta2 >= 0 && g->beta2 < 1) || !(g->eps > 0) ||
         !(g->noise_std >= 0) || !(g->action_low <= g->action_high)) return fail(STMPC_EINVAL, "DDPG constants out of range");
     HIPCHK(hipSetDevice(c->device));
+    const int h1p = (g->h1 + 15) & ~15, h2p = (g->h2 + 15) & ~15;
+    const size_t lds = ddpg_tile_bytes(h1p, h2p);
+    if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, "DDPG networks too wide for one workgroup's LDS");
     stmpc_ddpg *l = new stmpc_ddpg();
-    l->device = c->device; l->cfg = *g;
-    const int h1p = l->h1p = (g->h1 + 15) & ~15, h2p = l->h2p = (g->h2 + 15) & ~15;
-    const int np = l->np = dg_nparam(h1p, h2p), Bp = l->Bp = (g->batch + 15) & ~15;
-    l->lds = ddpg_tile_bytes(h1p, h2p);
-    if (l->lds + 1024 > (size_t)c->lds_per_block) { delete l; return fail(STMPC_EINVAL, "DDPG networks too wide for one workgroup's LDS"); }
+    l->cfg = *g; l->h1p = h1p; l->h2p = h2p; l->np = dg_nparam(h1p, h2p); l->lds = lds;
+    l->rp.device = c->device;                                        // (what destroy selects, should an allocation fail)
     DdpgDev &d = l->dev;
     int rc = 0;
     for (int w = 0; w < 2 && !rc; ++w) {
-        DdpgNet &n = w ? d.q : d.pi;
-        float **ptr[13] = {&n.w, &n.wt, &n.m, &n.v, &n.g, &n.p0, &n.p1, &n.p1t, &n.t0, &n.t1, &n.bpow, nullptr, nullptr};
-        const size_t len[11] = {(size_t)np, (size_t)np, (size_t)np, (size_t)np, (size_t)np, (size_t)h1p * AT_KIN, (size_t)h2p * h1p, (size_t)h2p * h1p,
-                                (size_t)h1p * AT_KIN, (size_t)h2p * h1p, 4};
-        for (int i = 0; i < 11 && !rc; ++i) { rc = ddpg_zero(l->netbuf[w][i], len[i] * sizeof(float)); *ptr[i] = l->netbuf[w][i].as<float>(); }
-        n.n_in = l->n_in(w);
+        l->lay[w] = slot_layout(g->n_obs + 1 + w, g->h1, g->h2, h1p, h2p, true);
+        rc = net_build(l->net[w], w ? d.q : d.pi, g->n_obs + 1 + w, h1p, h2p);
     }
-    const size_t wlen[7] = {(size_t)Bp * AT_KIN, (size_t)Bp * h1p, (size_t)Bp * h2p, (size_t)Bp * h2p, (size_t)Bp * h1p, (size_t)Bp, (size_t)Bp * 2};
-    float **wptr[7] = {&d.aX, &d.aH1, &d.aH2, &d.aD2, &d.aD1, &d.adz, &d.arow};
-    for (int i = 0; i < 7 && !rc; ++i) { rc = ddpg_zero(l->ws[i], wlen[i] * sizeof(float)); *wptr[i] = l->ws[i].as<float>(); }
-    if (!rc) rc = ddpg_zero(l->ring, (size_t)g->capacity * DG_ROW * sizeof(float));
-    if (!rc) rc = ddpg_zero(l->cnt, DG_NCNT * sizeof(long long));
-    if (!rc) rc = ddpg_zero(l->tick, DG_NTICK * sizeof(unsigned int));
-    if (!rc) rc = ddpg_raise_lds(false, l->device, l->lds);
+    if (!rc) rc = ws_build(l->ws, d, (g->batch + 15) & ~15, h1p, h2p);
+    if (!rc) rc = l->rp.create(c->device, g->batch, g->capacity);     // (the ring behind the nets and the workspace: the order the buffers always had)
+    if (!rc) rc = ddpg_raise_lds(false, c->device, lds);
     if (rc) { stmpc_ddpg_destroy(l); return rc; }
-    d.ring = l->ring.as<float>(); d.cnt = l->cnt.as<long long>(); d.tick = l->tick.as<unsigned int>();
-    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = g->h2; d.h1p = h1p; d.h2p = h2p; d.capacity = g->capacity; d.replay_start = g->replay_start; d.seed = g->seed;
+    l->grid = make_grid(l->rp.Bp, h1p, h2p, true);
+    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = g->h2; d.h1p = h1p; d.h2p = h2p; d.replay_start = g->replay_start; d.seed = g->seed;
     d.gamma = (float)g->gamma; d.tau = (float)g->tau; d.beta1 = (float)g->beta1; d.beta2 = (float)g->beta2;
     d.omb1 = 1.0f - d.beta1; d.omb2 = 1.0f - d.beta2; d.omtau = 1.0f - d.tau; d.eps = (float)g->eps; d.time_scale = (float)g->time_scale;
     d.scale = (float)g->tanh_scale; d.mean = (float)g->tanh_mean; d.noise_std = (float)g->noise_std; d.a_low = (float)g->action_low; d.a_high = (float)g->action_high;
-    const float one[4] = {1.f, 1.f, 0.f, 0.f};                       // beta^0
-    HIPCHK(hipMemcpy(d.pi.bpow, one, sizeof one, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d.q.bpow, one, sizeof one, hipMemcpyHostToDevice));
+    ddpg_refresh(l);
     *out = l;
     return STMPC_OK;
 }
 
 void stmpc_ddpg_destroy(stmpc_ddpg *l) {
     if (!l) return;
-    (void)hipSetDevice(l->device);
+    (void)hipSetDevice(l->rp.device);
     delete l;
 }
 
 int stmpc_ddpg_set_params(stmpc_ddpg *l, int slot, const float *values, int64_t count) {
-    if (!l || !values || slot < 0 || slot > 7) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
+    TRY(slot_args(l, values, slot, 8));
     const int which = slot >= 4;
-    if (count != l->slot_len(which)) return fail(STMPC_EINVAL, "count is not the length of this slot");
-    HIPCHK(hipSetDevice(l->device));
-    std::vector<float> pad((size_t)l->np, 0.f);
-    ddpg_pad(l, l->n_in(which), values, pad, true, nullptr);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(ddpg_slot_ptr(l, slot), pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
-    if ((slot & 3) < 2) {                                            // the packed copies follow the parameters
-        ddpg_launch_adam(l, which, 0.f, 1, 0, (hipStream_t)0);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-    }
-    return STMPC_OK;
+    return slot_set(l->rp.device, l->lay[which], l->np, net_slot(which ? l->dev.q : l->dev.pi, slot & 3), values, count, (slot & 3) < 2,
+                    [&] { ddpg_launch_adam(l, l->dev, which, 0.f, 1, 0, (hipStream_t)0); });
 }
 
 int stmpc_ddpg_get_params(stmpc_ddpg *l, int slot, float *values, int64_t count) {
-    if (!l || !values || slot < 0 || slot > 7) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
+    TRY(slot_args(l, values, slot, 8));
     const int which = slot >= 4;
-    if (count != l->slot_len(which)) return fail(STMPC_EINVAL, "count is not the length of this slot");
-    HIPCHK(hipSetDevice(l->device));
-    std::vector<float> pad((size_t)l->np, 0.f);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(pad.data(), ddpg_slot_ptr(l, slot), pad.size() * sizeof(float), hipMemcpyDeviceToHost));
-    ddpg_pad(l, l->n_in(which), nullptr, pad, false, values);
-    return STMPC_OK;
+    return slot_get(l->rp.device, l->lay[which], l->np, net_slot(which ? l->dev.q : l->dev.pi, slot & 3), values, count);
 }
 
 int stmpc_ddpg_set_state(stmpc_ddpg *l, const int64_t *counters, const float *beta_pow) {
     if (!l || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
-    if (counters[DG_CURSOR] < 0 || counters[DG_CURSOR] >= l->cfg.capacity || counters[DG_FILL] < 0 || counters[DG_FILL] > l->cfg.capacity || counters[DG_UPDATES] < 0 ||
-        counters[DG_ACTS] < 0 || counters[DG_FRAMES] < 0) return fail(STMPC_EINVAL, "counters out of range");
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    long long cn[DG_NCNT];
-    if (l->per) {                                                    // the tree's leaves follow the ring's cursor and fill
-        HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
-        if (cn[DG_CURSOR] != counters[DG_CURSOR] || cn[DG_FILL] != counters[DG_FILL])
-            return fail(STMPC_EINVAL, "prioritised replay is enabled: the ring's cursor and fill cannot be set (the priorities belong to the rows pushed)");
-    }
-    for (int i = 0; i < DG_NCNT; ++i) cn[i] = i <= DG_FRAMES ? counters[i] : 0;
-    HIPCHK(hipMemcpy(l->dev.cnt, cn, sizeof cn, hipMemcpyHostToDevice));
+    TRY(l->rp.set_counters(counters));
     HIPCHK(hipMemcpy(l->dev.pi.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(l->dev.q.bpow, beta_pow + 2, 2 * sizeof(float), hipMemcpyHostToDevice));
     return STMPC_OK;
@@ -188,11 +347,7 @@ int stmpc_ddpg_set_state(stmpc_ddpg *l, const int64_t *counters, const float *be
 
 int stmpc_ddpg_get_state(stmpc_ddpg *l, int64_t *counters, float *beta_pow) {
     if (!l || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    long long cn[DG_NCNT];
-    HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
-    for (int i = 0; i < DG_NCNT; ++i) counters[i] = cn[i];
+    TRY(l->rp.get_counters(counters));
     HIPCHK(hipMemcpy(beta_pow, l->dev.pi.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(beta_pow + 2, l->dev.q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
     return STMPC_OK;
@@ -205,10 +360,8 @@ int stmpc_ddpg_push_device(stmpc_ddpg *l, int N, const float *d_obs, const float
     if (N < 0 || N > l->cfg.capacity || obs_stride < l->cfg.n_obs) return fail(STMPC_EINVAL, "N exceeds the replay capacity, or obs_stride is shorter than the observation");
     if (N == 0) return STMPC_OK;
     if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(l->device));
-    const long long items = (long long)N * DG_ROW;
-    const int blocks = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_replay_push, dim3(blocks), dim3(256), 0, (hipStream_t)stream, l->dev, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks,
+    HIPCHK(hipSetDevice(l->rp.device));
+    hipLaunchKernelGGL(k_replay_push, dim3(push_blocks(N)), dim3(256), 0, (hipStream_t)stream, l->dev, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks,
                        d_action, d_reward, d_terminated, d_truncated);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -220,7 +373,7 @@ int stmpc_ddpg_act_device(stmpc_ddpg *l, int N, const float *d_obs, int obs_stri
     if (N < 0 || obs_stride < l->cfg.n_obs) return fail(STMPC_EINVAL, "N negative, or obs_stride shorter than the observation");
     if (N == 0) return STMPC_OK;
     if (!d_obs || !d_ticks || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipSetDevice(l->rp.device));
     hipLaunchKernelGGL(k_ddpg_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), l->lds, (hipStream_t)stream, l->dev, N, d_obs, obs_stride, d_ticks, noise != 0,
                        d_action, d_debug);
     HIPCHK(hipGetLastError());
@@ -231,14 +384,15 @@ int stmpc_ddpg_update_device(stmpc_ddpg *l, int n_updates, double lr_q, double l
     if (!l) return fail(STMPC_EINVAL, "learner is NULL");
     if (l->td3_base) return fail(STMPC_EINVAL, "this learner is the base of a TD3 learner: update it with stmpc_td3_update_device");
     if (n_updates < 0 || !(lr_q >= 0) || !(lr_pi >= 0)) return fail(STMPC_EINVAL, "n_updates or a learning rate is negative");
-    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipSetDevice(l->rp.device));
+    hipStream_t st = (hipStream_t)stream;
     for (int u = 0; u < n_updates; ++u) {
-        per_launch_sample(l, 1, (hipStream_t)stream);
-        ddpg_launch_grads(l, 1, 1, (hipStream_t)stream);
-        per_launch_update(l, (hipStream_t)stream);
-        ddpg_launch_adam(l, 1, (float)lr_q, 0, 0, (hipStream_t)stream);
-        ddpg_launch_grads(l, 0, 1, (hipStream_t)stream);
-        ddpg_launch_adam(l, 0, (float)lr_pi, 0, 1, (hipStream_t)stream);
+        per_launch_sample(l->rp, l->dev, 1, st);
+        ddpg_launch_grads(l, 1, 1, st);
+        per_launch_update(l->rp, l->dev, st);
+        ddpg_launch_adam(l, l->dev, 1, (float)lr_q, 0, 0, st);
+        ddpg_launch_grads(l, 0, 1, st);
+        ddpg_launch_adam(l, l->dev, 0, (float)lr_pi, 0, 1, st);
     }
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -247,41 +401,33 @@ int stmpc_ddpg_update_device(stmpc_ddpg *l, int n_updates, double lr_q, double l
 int stmpc_ddpg_grads_device(stmpc_ddpg *l, float *d_grad_actor, float *d_grad_critic, void *stream) {
     if (!l || !d_grad_actor || !d_grad_critic) return fail(STMPC_EINVAL, "NULL argument");
     if (l->td3_base) return fail(STMPC_EINVAL, "this learner is the base of a TD3 learner: take its gradients with stmpc_td3_grads_device");
-    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipSetDevice(l->rp.device));
     hipStream_t st = (hipStream_t)stream;
-    per_launch_sample(l, 0, st);
+    per_launch_sample(l->rp, l->dev, 0, st);
     ddpg_launch_grads(l, 1, 0, st);
-    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(1), (const float *)l->dev.q.g, d_grad_critic);
+    ddpg_launch_unpad(l, 1, l->dev.q.g, d_grad_critic, st);
     ddpg_launch_grads(l, 0, 0, st);
-    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(0), (const float *)l->dev.pi.g, d_grad_actor);
+    ddpg_launch_unpad(l, 0, l->dev.pi.g, d_grad_actor, st);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
 int stmpc_ddpg_stats_device(stmpc_ddpg *l, double *d_out, void *stream) {
     if (!l || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipSetDevice(l->rp.device));
     hipLaunchKernelGGL(k_ddpg_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, l->dev, l->cfg.batch, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
 int stmpc_ddpg_replay_read(stmpc_ddpg *l, int64_t first, int64_t count, float *rows) {
-    if (!l || !rows) return fail(STMPC_EINVAL, "NULL argument");
-    if (first < 0 || count < 0 || first + count > l->cfg.capacity) return fail(STMPC_EINVAL, "rows outside the ring");
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    if (count) HIPCHK(hipMemcpy(rows, l->dev.ring + (size_t)first * DG_ROW, (size_t)count * DG_ROW * sizeof(float), hipMemcpyDeviceToHost));
-    return STMPC_OK;
+    if (!l) return fail(STMPC_EINVAL, "NULL argument");
+    return l->rp.read_rows(first, count, rows);
 }
 
 int stmpc_ddpg_gather_device(stmpc_ddpg *l, float *d_rows, void *stream) {
     if (!l || !d_rows) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(l->device));
-    per_launch_sample(l, 0, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_replay_gather, dim3((l->cfg.batch * DG_ROW + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->dev, l->cfg.batch, d_rows);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    return replay_gather(l->rp, l->dev, d_rows, stream);
 }
 
 uint64_t stmpc_ddpg_sample_index(uint64_t seed, uint64_t update, uint32_t row, uint64_t fill) {
@@ -294,177 +440,41 @@ double stmpc_ddpg_noise(uint64_t seed, uint64_t call, uint32_t row, uint32_t *dr
 
 }  // extern "C"
 
-// ---- DDPG population (stmpc_ddpg_pop_*): P learners of the section above, one launch per kernel; kernels in stmpc_ddpg_pop_kernels.hpp ------------
-struct stmpc_ddpg_pop {
-    int device = 0;
-    std::vector<stmpc_ddpg *> members;      // owned; made by stmpc_ddpg_create, so every single-learner entry works on a borrowed member
-    DevBuf table;                           // DdpgDev [P]: the members' structs (their pointers and constants change once at most: stmpc_pop_per_enable_ddpg)
-    bool per_called = false, per_any = false;   // stmpc_pop_per_enable_ddpg was called; at least one member has a tree
-    int P() const { return (int)members.size(); }
-    const DdpgDev *dev() const { return table.as<DdpgDev>(); }
-};
-
-static_assert(DG_POP_MAX == STMPC_DDPG_POP_MAX, "DdpgLr holds one learning rate per possible member");
-
-namespace {
-int ddpg_pop_lrs(int P, const double *lr, DdpgLr &out) {
-    for (int m = 0; m < P; ++m) {
-        if (!(lr[m] >= 0)) return fail(STMPC_EINVAL, "a member's learning rate is negative");
-        out.lr[m] = (float)lr[m];
-    }
-    return STMPC_OK;
-}
-// acting and pushing of P members whose DdpgDev are table[0 ... P): the DDPG population's own, and a TD3 population's on its members' bases
-int ddpg_pop_act(int device, const DdpgDev *table, int P, const stmpc_ddpg *l0, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise,
-                 double *d_action, uint32_t *d_debug, void *stream) {
-    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
-        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
-    if (!d_obs || !d_ticks || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(device));
-    hipLaunchKernelGGL(k_ddpg_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, P), dim3(AT_THREADS), l0->lds, (hipStream_t)stream, table, n_per_member, d_obs,
-                       obs_stride, d_ticks, noise != 0, d_action, d_debug);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-int ddpg_pop_push(int device, const DdpgDev *table, int P, const stmpc_ddpg *l0, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs,
-                  int obs_stride, const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated,
-                  const uint8_t *d_truncated, void *stream) {
-    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
-        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
-    if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(device));
-    const long long items = (long long)n_per_member * DG_ROW;       // per member: stmpc_ddpg_push_device's block count
-    const int blocks = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_replay_push_pop, dim3(blocks, P), dim3(256), 0, (hipStream_t)stream, table, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride,
-                       d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int stmpc_ddpg_pop_create(stmpc_ctx *c, const stmpc_ddpg_cfg *cfgs, int P, stmpc_ddpg_pop **out) {
-    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (P < 1 || P > DG_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
-    if (!cfgs) return fail(STMPC_EINVAL, "NULL argument");
-    for (int m = 1; m < P; ++m)
-        if (cfgs[m].n_obs != cfgs[0].n_obs || cfgs[m].h1 != cfgs[0].h1 || cfgs[m].h2 != cfgs[0].h2 || cfgs[m].batch != cfgs[0].batch || cfgs[m].capacity != cfgs[0].capacity)
-            return fail(STMPC_EINVAL, "the members of a population share n_obs, h1, h2, batch and capacity (member " + std::to_string(m) + " differs from member 0)");
-    HIPCHK(hipSetDevice(c->device));
-    stmpc_ddpg_pop *p = new stmpc_ddpg_pop();
-    p->device = c->device;
-    int rc = STMPC_OK;
-    std::vector<DdpgDev> host;
-    for (int m = 0; m < P && !rc; ++m) {
-        stmpc_ddpg *l = nullptr;
-        rc = stmpc_ddpg_create(c, cfgs + m, &l);
-        if (!rc) { l->pop_member = true; p->members.push_back(l); host.push_back(l->dev); }
-    }
-    if (!rc) rc = p->table.ensure(host.size() * sizeof(DdpgDev));
-    if (!rc && hipMemcpy(p->table.p, host.data(), host.size() * sizeof(DdpgDev), hipMemcpyHostToDevice) != hipSuccess) rc = fail(STMPC_EHIP, "hipMemcpy of the member table failed");
-    if (!rc) rc = ddpg_raise_lds(true, p->device, p->members[0]->lds);
-    if (rc) { stmpc_ddpg_pop_destroy(p); return rc; }
-    *out = p;
-    return STMPC_OK;
-}
-
-void stmpc_ddpg_pop_destroy(stmpc_ddpg_pop *p) {
-    if (!p) return;
-    for (stmpc_ddpg *l : p->members) stmpc_ddpg_destroy(l);
-    (void)hipSetDevice(p->device);
-    delete p;
-}
-
-int stmpc_ddpg_pop_size(const stmpc_ddpg_pop *p) { return p ? p->P() : 0; }
-
-stmpc_ddpg *stmpc_ddpg_pop_member(stmpc_ddpg_pop *p, int m) {
-    if (!p || m < 0 || m >= p->P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
-    return p->members[m];
-}
-
-int stmpc_ddpg_pop_act_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action,
-                              uint32_t *d_debug, void *stream) {
-    if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    return ddpg_pop_act(p->device, p->dev(), p->P(), p->members[0], n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug, stream);
-}
-
-int stmpc_ddpg_pop_push_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
-                               const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated,
-                               const uint8_t *d_truncated, void *stream) {
-    if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    return ddpg_pop_push(p->device, p->dev(), p->P(), p->members[0], n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward,
-                         d_terminated, d_truncated, stream);
-}
-
-int stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *p, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream) {
-    if (!p || !lr_q || !lr_pi) return fail(STMPC_EINVAL, "NULL argument");
-    if (n_lr != p->P()) return fail(STMPC_EINVAL, "the learning-rate arrays have " + std::to_string(n_lr) + " entries, the population " + std::to_string(p->P()) + " members");
-    if (n_updates < 0) return fail(STMPC_EINVAL, "n_updates is negative");
-    DdpgLr lq{}, lp{};
-    TRY(ddpg_pop_lrs(p->P(), lr_q, lq));
-    TRY(ddpg_pop_lrs(p->P(), lr_pi, lp));
-    HIPCHK(hipSetDevice(p->device));
-    const stmpc_ddpg *l = p->members[0];
-    const int P = p->P(), tiles = l->Bp / AT_TM, t1 = l->h2p / 16, t0 = l->h1p / 16, jobs = t1 * t0 + 2 * t0 + t1 + t0 + t1 + 1, ablocks = (l->np + 255) / 256;
-    hipStream_t st = (hipStream_t)stream;
-    for (int u = 0; u < n_updates; ++u) {                            // stmpc_ddpg_update_device's six launches (eight with prioritised members), each over the members
-        if (p->per_any) hipLaunchKernelGGL(k_per_sample_pop, dim3(1, P), dim3(PER_THREADS), 0, st, p->dev(), l->cfg.batch, l->Bp, 1);
-        hipLaunchKernelGGL(k_ddpg_critic_fwd_pop, dim3(tiles, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
-        hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 1, l->Bp, 1);
-        if (p->per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, p->dev(), l->cfg.batch, 1);
-        hipLaunchKernelGGL(k_ddpg_adam_pop, dim3(ablocks, P), dim3(256), 0, st, p->dev(), 1, lq, 0, 0, 1);
-        hipLaunchKernelGGL(k_ddpg_actor_fwd_pop, dim3(tiles, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
-        hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 0, l->Bp, 1);
-        hipLaunchKernelGGL(k_ddpg_adam_pop, dim3(ablocks, P), dim3(256), 0, st, p->dev(), 0, lp, 0, 1, 1);
-    }
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *p, double *d_out, void *stream) {
-    if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(p->device));
-    hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->members[0]->cfg.batch, d_out);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-}  // extern "C"
-
 // ---- TD3 learner (stmpc_td3_*): a DDPG learner as base (actor, critic 1, ring, counters) plus critic 2; kernels in stmpc_td3_kernels.hpp -----------
 struct stmpc_td3 {
     stmpc_ddpg *base = nullptr;             // owned; lent out by stmpc_td3_base
     stmpc_td3_cfg cfg{};
-    Td3Dev dev{};
+    Td3Dev dev{};                           // sigma, clip, delay, tick (stmpc_td3_create); the two views are td3_refresh's
     DevBuf net2[11], ws2[7], tick;          // critic 2, its workspace; tickets: [0 ... DG_NTICK) view 1's, [DG_NTICK] k_td3_adam_finish's
-    float *slot_ptr(int slot) { const DdpgNet &n = dev.v[1].q; float *const p[4] = {n.w, n.wt, n.m, n.v}; return p[slot]; }
 };
 
 namespace {
+// the two views from the base's dev and critic 2: both share the ring, the counters, the tree, idx and the weights; view 1 has critic 2 in the critic's
+// place, a workspace and tickets of its own, and leaves its own Q - y
+void td3_refresh(stmpc_td3 *t) {
+    const stmpc_ddpg *l = t->base;
+    DdpgDev &v1 = t->dev.v[1];
+    t->dev.v[0] = v1 = l->dev;
+    net_wire(v1.q, t->net2, l->dev.q.n_in);
+    ws_wire(v1, t->ws2);
+    v1.tick = t->tick.as<unsigned int>();
+    if (l->rp.per) v1.atd = l->rp.atd2.as<float>();
+}
 int td3_raise_lds(int device, size_t lds) {
     static LdsCeiling ceiling[2];
     TRY(raise_dynamic_lds((const void *)k_td3_critic_fwd, "k_td3_critic_fwd", ceiling[0], device, lds));
     return raise_dynamic_lds((const void *)k_td3_actor_fwd, "k_td3_actor_fwd", ceiling[1], device, lds);
 }
-struct Td3Grid { int tiles, jobs, ablocks; };
-Td3Grid td3_grid(const stmpc_ddpg *l) {
-    const int t1 = l->h2p / 16, t0 = l->h1p / 16;
-    return {l->Bp / AT_TM, t1 * t0 + 2 * t0 + t1 + t0 + t1 + 1, (l->np + 255) / 256};
-}
 // critic pass and weight gradients of both critics, then (if due, or gate = 0) of the actor against critic 1 as it then is
 void td3_launch_critic_grads(stmpc_td3 *t, int gate, hipStream_t st) {
     const stmpc_ddpg *l = t->base;
-    const Td3Grid g = td3_grid(l);
-    hipLaunchKernelGGL(k_td3_critic_fwd, dim3(g.tiles, 2), dim3(AT_THREADS), l->lds, st, t->dev, l->cfg.batch, gate, (float *)nullptr);
-    hipLaunchKernelGGL(k_td3_wgrad, dim3(g.jobs, 2), dim3(64 * DG_WG_WAVES), 0, st, t->dev, 1, l->Bp, gate);
+    hipLaunchKernelGGL(k_td3_critic_fwd, dim3(l->grid.tiles, 2), dim3(AT_THREADS), l->lds, st, t->dev, l->cfg.batch, gate, (float *)nullptr);
+    hipLaunchKernelGGL(k_td3_wgrad, dim3(l->grid.jobs, 2), dim3(64 * DG_WG_WAVES), 0, st, t->dev, 1, l->rp.Bp, gate);
 }
 void td3_launch_actor_grads(stmpc_td3 *t, int gate, hipStream_t st) {
     const stmpc_ddpg *l = t->base;
-    const Td3Grid g = td3_grid(l);
-    hipLaunchKernelGGL(k_td3_actor_fwd, dim3(g.tiles), dim3(AT_THREADS), l->lds, st, t->dev, l->cfg.batch, gate);
-    hipLaunchKernelGGL(k_td3_wgrad, dim3(g.jobs, 1), dim3(64 * DG_WG_WAVES), 0, st, t->dev, 0, l->Bp, gate);
+    hipLaunchKernelGGL(k_td3_actor_fwd, dim3(l->grid.tiles), dim3(AT_THREADS), l->lds, st, t->dev, l->cfg.batch, gate);
+    hipLaunchKernelGGL(k_td3_wgrad, dim3(l->grid.jobs, 1), dim3(64 * DG_WG_WAVES), 0, st, t->dev, 0, l->rp.Bp, gate);
 }
 }  // namespace
 
@@ -483,24 +493,14 @@ int stmpc_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *g, stmpc_td3 **out) {
     stmpc_ddpg *l = t->base;
     l->td3_base = true;
     l->td3_owner = t;
-    DdpgDev v1 = l->dev;
-    DdpgNet &n = v1.q;
-    const size_t np = (size_t)l->np, h1p = (size_t)l->h1p, h2p = (size_t)l->h2p, Bp = (size_t)l->Bp;
-    float **ptr[11] = {&n.w, &n.wt, &n.m, &n.v, &n.g, &n.p0, &n.p1, &n.p1t, &n.t0, &n.t1, &n.bpow};
-    const size_t len[11] = {np, np, np, np, np, h1p * AT_KIN, h2p * h1p, h2p * h1p, h1p * AT_KIN, h2p * h1p, 4};
-    for (int i = 0; i < 11 && !rc; ++i) { rc = ddpg_zero(t->net2[i], len[i] * sizeof(float)); *ptr[i] = t->net2[i].as<float>(); }
-    const size_t wlen[7] = {Bp * AT_KIN, Bp * h1p, Bp * h2p, Bp * h2p, Bp * h1p, Bp, Bp * 2};
-    float **wptr[7] = {&v1.aX, &v1.aH1, &v1.aH2, &v1.aD2, &v1.aD1, &v1.adz, &v1.arow};
-    for (int i = 0; i < 7 && !rc; ++i) { rc = ddpg_zero(t->ws2[i], wlen[i] * sizeof(float)); *wptr[i] = t->ws2[i].as<float>(); }
+    rc = net_build(t->net2, t->dev.v[1].q, l->dev.q.n_in, l->h1p, l->h2p);
+    if (!rc) rc = ws_build(t->ws2, t->dev.v[1], l->rp.Bp, l->h1p, l->h2p);
     if (!rc) rc = ddpg_zero(t->tick, (DG_NTICK + 1) * sizeof(unsigned int));
-    if (!rc) rc = td3_raise_lds(l->device, l->lds);
-    const float one[4] = {1.f, 1.f, 0.f, 0.f};                       // beta^0
-    if (!rc && hipMemcpy(n.bpow, one, sizeof one, hipMemcpyHostToDevice) != hipSuccess) rc = fail(STMPC_EHIP, "hipMemcpy of critic 2's beta powers failed");
+    if (!rc) rc = td3_raise_lds(l->rp.device, l->lds);
     if (rc) { stmpc_td3_destroy(t); return rc; }
-    v1.tick = t->tick.as<unsigned int>();
-    t->dev.v[0] = l->dev; t->dev.v[1] = v1;
-    t->dev.tick = v1.tick + DG_NTICK;
+    t->dev.tick = t->tick.as<unsigned int>() + DG_NTICK;
     t->dev.sigma = (float)g->target_noise_std; t->dev.clip = (float)g->noise_clip; t->dev.delay = g->policy_delay;
+    td3_refresh(t);
     *out = t;
     return STMPC_OK;
 }
@@ -517,37 +517,21 @@ stmpc_ddpg *stmpc_td3_base(stmpc_td3 *t) {
 }
 
 int stmpc_td3_set_params(stmpc_td3 *t, int slot, const float *values, int64_t count) {
-    if (!t || !values || slot < 0 || slot > 3) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
-    stmpc_ddpg *l = t->base;
-    if (count != l->slot_len(1)) return fail(STMPC_EINVAL, "count is not the length of this slot");
-    HIPCHK(hipSetDevice(l->device));
-    std::vector<float> pad((size_t)l->np, 0.f);
-    ddpg_pad(l, l->n_in(1), values, pad, true, nullptr);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(t->slot_ptr(slot), pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (slot < 2) {                                                  // the packed copies follow the parameters
-        hipLaunchKernelGGL(k_ddpg_adam, dim3((l->np + 255) / 256), dim3(256), 0, (hipStream_t)0, t->dev.v[1], 1, 0.f, 1, 0, 1);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-    }
-    return STMPC_OK;
+    TRY(slot_args(t, values, slot, 4));
+    const stmpc_ddpg *l = t->base;
+    return slot_set(l->rp.device, l->lay[1], l->np, net_slot(t->dev.v[1].q, slot), values, count, slot < 2,
+                    [&] { ddpg_launch_adam(l, t->dev.v[1], 1, 0.f, 1, 0, (hipStream_t)0); });
 }
 
 int stmpc_td3_get_params(stmpc_td3 *t, int slot, float *values, int64_t count) {
-    if (!t || !values || slot < 0 || slot > 3) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
-    stmpc_ddpg *l = t->base;
-    if (count != l->slot_len(1)) return fail(STMPC_EINVAL, "count is not the length of this slot");
-    HIPCHK(hipSetDevice(l->device));
-    std::vector<float> pad((size_t)l->np, 0.f);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(pad.data(), t->slot_ptr(slot), pad.size() * sizeof(float), hipMemcpyDeviceToHost));
-    ddpg_pad(l, l->n_in(1), nullptr, pad, false, values);
-    return STMPC_OK;
+    TRY(slot_args(t, values, slot, 4));
+    const stmpc_ddpg *l = t->base;
+    return slot_get(l->rp.device, l->lay[1], l->np, net_slot(t->dev.v[1].q, slot), values, count);
 }
 
 int stmpc_td3_set_state(stmpc_td3 *t, const float *beta_pow2) {
     if (!t || !beta_pow2) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->base->device));
+    HIPCHK(hipSetDevice(t->base->rp.device));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(t->dev.v[1].q.bpow, beta_pow2, 2 * sizeof(float), hipMemcpyHostToDevice));
     return STMPC_OK;
@@ -555,25 +539,22 @@ int stmpc_td3_set_state(stmpc_td3 *t, const float *beta_pow2) {
 
 int stmpc_td3_get_state(stmpc_td3 *t, float *beta_pow2) {
     if (!t || !beta_pow2) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->base->device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(beta_pow2, t->dev.v[1].q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
-    return STMPC_OK;
+    return read_back(t->base->rp.device, beta_pow2, t->dev.v[1].q.bpow, 2 * sizeof(float));
 }
 
 int stmpc_td3_update_device(stmpc_td3 *t, int n_updates, double lr_q, double lr_pi, void *stream) {
     if (!t) return fail(STMPC_EINVAL, "learner is NULL");
     if (n_updates < 0 || !(lr_q >= 0) || !(lr_pi >= 0)) return fail(STMPC_EINVAL, "n_updates or a learning rate is negative");
-    HIPCHK(hipSetDevice(t->base->device));
-    const Td3Grid g = td3_grid(t->base);
+    const stmpc_ddpg *l = t->base;
+    HIPCHK(hipSetDevice(l->rp.device));
     hipStream_t st = (hipStream_t)stream;
     for (int u = 0; u < n_updates; ++u) {                            // the same six launches whatever the counters say
-        per_launch_sample(t->base, 1, st);
+        per_launch_sample(l->rp, l->dev, 1, st);
         td3_launch_critic_grads(t, 1, st);
-        per_launch_update(t->base, st);
-        hipLaunchKernelGGL(k_td3_adam_critics, dim3(g.ablocks, 2), dim3(256), 0, st, t->dev, (float)lr_q, 1);
+        per_launch_update(l->rp, l->dev, st);
+        hipLaunchKernelGGL(k_td3_adam_critics, dim3(l->grid.ablocks, 2), dim3(256), 0, st, t->dev, (float)lr_q, 1);
         td3_launch_actor_grads(t, 1, st);
-        hipLaunchKernelGGL(k_td3_adam_finish, dim3(g.ablocks, 3), dim3(256), 0, st, t->dev, (float)lr_pi, 1);
+        hipLaunchKernelGGL(k_td3_adam_finish, dim3(l->grid.ablocks, 3), dim3(256), 0, st, t->dev, (float)lr_pi, 1);
     }
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -582,14 +563,14 @@ int stmpc_td3_update_device(stmpc_td3 *t, int n_updates, double lr_q, double lr_
 int stmpc_td3_grads_device(stmpc_td3 *t, float *d_grad_actor, float *d_grad_critic1, float *d_grad_critic2, void *stream) {
     if (!t || !d_grad_actor || !d_grad_critic1 || !d_grad_critic2) return fail(STMPC_EINVAL, "NULL argument");
     stmpc_ddpg *l = t->base;
-    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipSetDevice(l->rp.device));
     hipStream_t st = (hipStream_t)stream;
-    per_launch_sample(l, 0, st);
+    per_launch_sample(l->rp, l->dev, 0, st);
     td3_launch_critic_grads(t, 0, st);
-    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(1), (const float *)t->dev.v[0].q.g, d_grad_critic1);
-    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(1), (const float *)t->dev.v[1].q.g, d_grad_critic2);
+    ddpg_launch_unpad(l, 1, t->dev.v[0].q.g, d_grad_critic1, st);
+    ddpg_launch_unpad(l, 1, t->dev.v[1].q.g, d_grad_critic2, st);
     td3_launch_actor_grads(t, 0, st);
-    hipLaunchKernelGGL(k_ddpg_unpad, dim3(128), dim3(256), 0, st, l->dev, l->n_in(0), (const float *)l->dev.pi.g, d_grad_actor);
+    ddpg_launch_unpad(l, 0, l->dev.pi.g, d_grad_actor, st);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
@@ -597,16 +578,16 @@ int stmpc_td3_grads_device(stmpc_td3 *t, float *d_grad_actor, float *d_grad_crit
 int stmpc_td3_targets_device(stmpc_td3 *t, float *d_out, void *stream) {
     if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
     const stmpc_ddpg *l = t->base;
-    HIPCHK(hipSetDevice(l->device));
-    per_launch_sample(l, 0, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_td3_critic_fwd, dim3(l->Bp / AT_TM, 1), dim3(AT_THREADS), l->lds, (hipStream_t)stream, t->dev, l->cfg.batch, 0, d_out);
+    HIPCHK(hipSetDevice(l->rp.device));
+    per_launch_sample(l->rp, l->dev, 0, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_td3_critic_fwd, dim3(l->grid.tiles, 1), dim3(AT_THREADS), l->lds, (hipStream_t)stream, t->dev, l->cfg.batch, 0, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
 int stmpc_td3_stats_device(stmpc_td3 *t, double *d_out, void *stream) {
     if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->base->device));
+    HIPCHK(hipSetDevice(t->base->rp.device));
     hipLaunchKernelGGL(k_td3_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, t->dev, t->base->cfg.batch, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -620,42 +601,10 @@ double stmpc_td3_noise(uint64_t seed, uint64_t update, uint32_t row, uint32_t *d
 
 // ---- prioritised replay (stmpc_per_*) for a lone DDPG learner or a lone TD3 learner's base; kernels in stmpc_per_kernels.hpp ----------------------
 namespace {
-int per_check_cfg(const stmpc_per_cfg *g) {
-    if (!(g->min_priority > 0) || !(g->max_priority >= g->min_priority) || !std::isfinite(g->max_priority) || !(g->alpha >= 0) || !std::isfinite(g->alpha) ||
-        !(g->beta >= 0) || !std::isfinite(g->beta))
-        return fail(STMPC_EINVAL, "prioritised replay needs min_priority > 0, max_priority >= min_priority, alpha >= 0 and beta >= 0, all finite");
-    return STMPC_OK;
-}
-// not enabled yet, and the ring empty (synchronises)
-int per_check_ring(stmpc_ddpg *l) {
-    if (l->per) return fail(STMPC_EINVAL, "prioritised replay is already enabled on this learner");
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    long long cn[DG_NCNT];
-    HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
-    if (cn[DG_FILL] != 0 || cn[DG_CURSOR] != 0) return fail(STMPC_EINVAL, "prioritised replay can be enabled on an empty ring only (fill is " + std::to_string(cn[DG_FILL]) + ")");
-    return STMPC_OK;
-}
-// the tree, idx, weights and td buffers of a learner that passed both checks, and the fields of its host structs (a TD3 learner's base: of both views too)
+// the store's buffers on a learner that passed the checks, and its device structs (a TD3 learner's base: both views too) anew
 int per_attach(stmpc_ddpg *l, const stmpc_per_cfg *g) {
-    long long leaves = 1;
-    while (leaves < l->cfg.capacity) leaves <<= 1;
-    const size_t Bp = (size_t)l->Bp;
-    TRY(ddpg_zero(l->per_tree, (size_t)(2 * leaves - 1) * sizeof(double)));
-    TRY(ddpg_zero(l->per_idx, Bp * sizeof(long long)));
-    TRY(ddpg_zero(l->per_aw, Bp * sizeof(float)));
-    TRY(ddpg_zero(l->per_atd, Bp * sizeof(float)));
-    if (l->td3_owner) { TRY(ddpg_zero(l->per_atd2, Bp * sizeof(float))); }
-    auto set = [&](DdpgDev &d, DevBuf &atd) {
-        d.tree = l->per_tree.as<double>(); d.idx = l->per_idx.as<long long>(); d.aw = l->per_aw.as<float>(); d.atd = atd.as<float>();
-        d.per_alpha = g->alpha; d.per_beta = g->beta; d.per_min = g->min_priority; d.per_max = g->max_priority; d.per_L = leaves;
-    };
-    set(l->dev, l->per_atd);
-    if (l->td3_owner) {                                             // both views share the tree, idx and the weights; each critic leaves its own Q - y
-        set(l->td3_owner->dev.v[0], l->per_atd);
-        set(l->td3_owner->dev.v[1], l->per_atd2);
-    }
-    l->per = true;
+    TRY(l->rp.attach(g, l->td3_owner != nullptr));
+    ddpg_refresh(l);
     return STMPC_OK;
 }
 }  // namespace
@@ -666,28 +615,18 @@ int stmpc_per_enable(stmpc_ddpg *l, const stmpc_per_cfg *g) {
     if (!l || !g) return fail(STMPC_EINVAL, "NULL argument");
     TRY(per_check_cfg(g));
     if (l->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: prioritised replay is enabled on the population (stmpc_pop_per_enable_ddpg / _td3)");
-    TRY(per_check_ring(l));
+    TRY(l->rp.check_empty());
     return per_attach(l, g);
 }
 
 int stmpc_per_tree_read(stmpc_ddpg *l, int64_t first, int64_t count, double *nodes) {
-    if (!l || !nodes) return fail(STMPC_EINVAL, "NULL argument");
-    if (!l->per) return fail(STMPC_EINVAL, "prioritised replay is not enabled on this learner");
-    if (first < 0 || count < 0 || first + count > 2 * l->dev.per_L - 1) return fail(STMPC_EINVAL, "nodes outside the tree");
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    if (count) HIPCHK(hipMemcpy(nodes, l->dev.tree + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
-    return STMPC_OK;
+    if (!l) return fail(STMPC_EINVAL, "NULL argument");
+    return l->rp.read_tree(first, count, nodes);
 }
 
 int stmpc_per_last_device(stmpc_ddpg *l, int64_t *d_idx, float *d_td, float *d_weight, void *stream) {
-    if (!l || !d_idx || !d_td || !d_weight) return fail(STMPC_EINVAL, "NULL argument");
-    if (!l->per) return fail(STMPC_EINVAL, "prioritised replay is not enabled on this learner");
-    HIPCHK(hipSetDevice(l->device));
-    hipLaunchKernelGGL(k_per_last, dim3((l->cfg.batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->dev, (const float *)l->per_atd2.as<float>(), l->cfg.batch,
-                       (long long *)d_idx, d_td, d_weight);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    if (!l) return fail(STMPC_EINVAL, "NULL argument");
+    return per_last(l->rp, l->dev, d_idx, d_td, d_weight, stream);
 }
 
 int64_t stmpc_per_sample_index(const double *tree, int64_t leaves, int64_t fill, uint64_t seed, uint64_t update, uint32_t row) {
@@ -697,57 +636,215 @@ int64_t stmpc_per_sample_index(const double *tree, int64_t leaves, int64_t fill,
 
 }  // extern "C"
 
-// ---- TD3 population (stmpc_pop_td3_*): P learners of the section above, one launch per kernel; kernels in stmpc_td3_pop_kernels.hpp ---------------
-struct stmpc_td3_pop {
+// ---- the populations (stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_per_*): P learners of the sections above, one launch per kernel; kernels in
+// stmpc_ddpg_pop_kernels.hpp, stmpc_td3_pop_kernels.hpp and stmpc_per_pop_kernels.hpp -------------------------------------------------------------
+// What both population types hold: the members' stmpc_ddpg (a TD3 member's: its base) and the device table of their structs.
+struct PopCore {
     int device = 0;
+    std::vector<stmpc_ddpg *> bases;
+    DevBuf table;                               // DdpgDev [P]: the bases' dev (pop_upload), for the DDPG kernels, k_ddpg_act_pop and k_replay_push_pop
+    bool per_called = false, per_any = false;   // stmpc_pop_per_enable_* was called; at least one member has a tree
+    int P() const { return (int)bases.size(); }
+    const DdpgDev *dev() const { return table.as<DdpgDev>(); }
+};
+struct stmpc_ddpg_pop {
+    PopCore core;                           // core.bases: the members, owned; made by stmpc_ddpg_create, so every single-learner entry works on a borrowed member
+};
+struct stmpc_td3_pop {
+    PopCore core;
     std::vector<stmpc_td3 *> members;       // owned; made by stmpc_td3_create, so every single-learner entry works on a borrowed member (and on its base)
-    DevBuf table, bases;                    // Td3Dev [P]: the members' structs; DdpgDev [P]: their bases' (v[0]), for k_ddpg_act_pop / k_replay_push_pop
-    bool per_called = false, per_any = false;   // stmpc_pop_per_enable_td3 was called; at least one member has a tree
-    int P() const { return (int)members.size(); }
+    DevBuf table;                           // Td3Dev [P]: the members' structs (td3_pop_upload)
     const Td3Dev *dev() const { return table.as<Td3Dev>(); }
-    const DdpgDev *base_dev() const { return bases.as<DdpgDev>(); }
 };
 
-static_assert(STMPC_TD3_POP_MAX == DG_POP_MAX && STMPC_TD3_POP_MAX == STMPC_DDPG_POP_MAX, "DdpgLr holds one learning rate per possible member");
+static_assert(DG_POP_MAX == STMPC_DDPG_POP_MAX && STMPC_TD3_POP_MAX == DG_POP_MAX, "DdpgLr holds one learning rate per possible member");
 
 namespace {
+// the device tables from the members as they are now: at create, and again once prioritised replay gave members a tree
+int pop_upload(PopCore &c) {
+    std::vector<DdpgDev> host;
+    for (const stmpc_ddpg *l : c.bases) host.push_back(l->dev);
+    return upload(c.table, host.data(), host.size());
+}
+int td3_pop_upload(stmpc_td3_pop *p) {
+    std::vector<Td3Dev> host;
+    for (const stmpc_td3 *t : p->members) host.push_back(t->dev);
+    TRY(upload(p->table, host.data(), host.size()));
+    return pop_upload(p->core);
+}
 int td3_pop_raise_lds(int device, size_t lds) {
     static LdsCeiling ceiling[2];
     TRY(raise_dynamic_lds((const void *)k_td3_critic_fwd_pop, "k_td3_critic_fwd_pop", ceiling[0], device, lds));
     TRY(raise_dynamic_lds((const void *)k_td3_actor_fwd_pop, "k_td3_actor_fwd_pop", ceiling[1], device, lds));
     return ddpg_raise_lds(true, device, lds);                       // (k_ddpg_act_pop)
 }
+// a create entry's checks; base(cfg): the stmpc_ddpg_cfg of a member's cfg
+template <class Cfg, class Pop, class F> int pop_check_create(const stmpc_ctx *c, const Cfg *cfgs, int P, Pop **out, F base) {
+    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (P < 1 || P > DG_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
+    if (!cfgs) return fail(STMPC_EINVAL, "NULL argument");
+    for (int m = 1; m < P; ++m) {
+        const stmpc_ddpg_cfg &a = base(cfgs[m]), &b = base(cfgs[0]);
+        if (a.n_obs != b.n_obs || a.h1 != b.h1 || a.h2 != b.h2 || a.batch != b.batch || a.capacity != b.capacity)
+            return fail(STMPC_EINVAL, "the members of a population share n_obs, h1, h2, batch and capacity (member " + std::to_string(m) + " differs from member 0)");
+    }
+    return STMPC_OK;
+}
+// an update entry's checks behind the population's own, and the learning rates as the kernels take them
+int pop_check_update(const PopCore &c, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, DdpgLr &lq, DdpgLr &lp) {
+    if (!lr_q || !lr_pi) return fail(STMPC_EINVAL, "NULL argument");
+    if (n_lr != c.P()) return fail(STMPC_EINVAL, "the learning-rate arrays have " + std::to_string(n_lr) + " entries, the population " + std::to_string(c.P()) + " members");
+    if (n_updates < 0) return fail(STMPC_EINVAL, "n_updates is negative");
+    for (int i = 0; i < 2; ++i)
+        for (int m = 0; m < c.P(); ++m) {
+            const double lr = (i ? lr_pi : lr_q)[m];
+            if (!(lr >= 0)) return fail(STMPC_EINVAL, "a member's learning rate is negative");
+            (i ? lp : lq).lr[m] = (float)lr;
+        }
+    return STMPC_OK;
+}
+// acting and pushing of the members: the DDPG population's own, and a TD3 population's on its members' bases
+int pop_act(const PopCore &c, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action, uint32_t *d_debug, void *stream) {
+    const stmpc_ddpg *l0 = c.bases[0];
+    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
+        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
+    if (!d_obs || !d_ticks || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c.device));
+    hipLaunchKernelGGL(k_ddpg_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, c.P()), dim3(AT_THREADS), l0->lds, (hipStream_t)stream, c.dev(), n_per_member, d_obs,
+                       obs_stride, d_ticks, noise != 0, d_action, d_debug);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+int pop_push(const PopCore &c, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_ticks,
+             const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+    const stmpc_ddpg *l0 = c.bases[0];
+    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
+        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
+    if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c.device));
+    hipLaunchKernelGGL(k_replay_push_pop, dim3(push_blocks(n_per_member), c.P()), dim3(256), 0, (hipStream_t)stream, c.dev(), n_per_member, d_obs, d_next_obs, d_final_obs,
+                       obs_stride, d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+// stmpc_per_enable's work per enabled member -- every check before anything is attached --, then the device tables anew (upload_tables).  An
+// allocation that fails leaves the members before it prioritised, which the tables then say too.
+template <class F> int pop_per_enable(PopCore &c, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P, F upload_tables) {
+    if (!cfgs || !enabled) return fail(STMPC_EINVAL, "NULL argument");
+    if (P != c.P()) return fail(STMPC_EINVAL, "cfgs and enabled have " + std::to_string(P) + " entries, the population " + std::to_string(c.P()) + " members");
+    if (c.per_called) return fail(STMPC_EINVAL, "prioritised replay was already set up on this population (one call, on empty rings)");
+    for (int m = 0; m < P; ++m)
+        if (enabled[m]) { TRY(per_check_cfg(cfgs + m)); TRY(c.bases[m]->rp.check_empty()); }
+    c.per_called = true;
+    int rc = STMPC_OK;
+    for (int m = 0; m < P && !rc; ++m)
+        if (enabled[m]) { rc = per_attach(c.bases[m], cfgs + m); c.per_any = c.per_any || !rc; }
+    if (!c.per_any) return rc;                                      // (no member enabled: the tables stand)
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(hipDeviceSynchronize());
+    TRY(upload_tables());
+    return rc;
+}
 }  // namespace
 
 extern "C" {
 
-int stmpc_pop_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *cfgs, int P, stmpc_td3_pop **out) {
-    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (P < 1 || P > STMPC_TD3_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
-    if (!cfgs) return fail(STMPC_EINVAL, "NULL argument");
-    for (int m = 1; m < P; ++m) {
-        const stmpc_ddpg_cfg &a = cfgs[m].base, &b = cfgs[0].base;
-        if (a.n_obs != b.n_obs || a.h1 != b.h1 || a.h2 != b.h2 || a.batch != b.batch || a.capacity != b.capacity)
-            return fail(STMPC_EINVAL, "the members of a population share n_obs, h1, h2, batch and capacity (member " + std::to_string(m) + " differs from member 0)");
+int stmpc_ddpg_pop_create(stmpc_ctx *c, const stmpc_ddpg_cfg *cfgs, int P, stmpc_ddpg_pop **out) {
+    TRY(pop_check_create(c, cfgs, P, out, [](const stmpc_ddpg_cfg &g) -> const stmpc_ddpg_cfg & { return g; }));
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_ddpg_pop *p = new stmpc_ddpg_pop();
+    p->core.device = c->device;
+    int rc = STMPC_OK;
+    for (int m = 0; m < P && !rc; ++m) {
+        stmpc_ddpg *l = nullptr;
+        rc = stmpc_ddpg_create(c, cfgs + m, &l);
+        if (!rc) { l->pop_member = true; p->core.bases.push_back(l); }
     }
+    if (!rc) rc = pop_upload(p->core);
+    if (!rc) rc = ddpg_raise_lds(true, c->device, p->core.bases[0]->lds);
+    if (rc) { stmpc_ddpg_pop_destroy(p); return rc; }
+    *out = p;
+    return STMPC_OK;
+}
+
+void stmpc_ddpg_pop_destroy(stmpc_ddpg_pop *p) {
+    if (!p) return;
+    for (stmpc_ddpg *l : p->core.bases) stmpc_ddpg_destroy(l);
+    (void)hipSetDevice(p->core.device);
+    delete p;
+}
+
+int stmpc_ddpg_pop_size(const stmpc_ddpg_pop *p) { return p ? p->core.P() : 0; }
+
+stmpc_ddpg *stmpc_ddpg_pop_member(stmpc_ddpg_pop *p, int m) {
+    if (!p || m < 0 || m >= p->core.P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
+    return p->core.bases[m];
+}
+
+int stmpc_ddpg_pop_act_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action,
+                              uint32_t *d_debug, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return pop_act(p->core, n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug, stream);
+}
+
+int stmpc_ddpg_pop_push_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                               const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated,
+                               const uint8_t *d_truncated, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return pop_push(p->core, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated, stream);
+}
+
+int stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *p, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "NULL argument");
+    DdpgLr lq{}, lp{};
+    TRY(pop_check_update(p->core, n_updates, lr_q, lr_pi, n_lr, lq, lp));
+    HIPCHK(hipSetDevice(p->core.device));
+    const stmpc_ddpg *l = p->core.bases[0];
+    const DdpgDev *tab = p->core.dev();
+    const Grid g = l->grid;
+    const int P = p->core.P(), B = l->cfg.batch, Bp = l->rp.Bp;
+    hipStream_t st = (hipStream_t)stream;
+    for (int u = 0; u < n_updates; ++u) {                            // stmpc_ddpg_update_device's six launches (eight with prioritised members), each over the members
+        if (p->core.per_any) hipLaunchKernelGGL(k_per_sample_pop, dim3(1, P), dim3(PER_THREADS), 0, st, tab, B, Bp, 1);
+        hipLaunchKernelGGL(k_ddpg_critic_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), l->lds, st, tab, B, 1);
+        hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, tab, 1, Bp, 1);
+        if (p->core.per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, tab, B, 1);
+        hipLaunchKernelGGL(k_ddpg_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, tab, 1, lq, 0, 0, 1);
+        hipLaunchKernelGGL(k_ddpg_actor_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), l->lds, st, tab, B, 1);
+        hipLaunchKernelGGL(k_ddpg_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, tab, 0, Bp, 1);
+        hipLaunchKernelGGL(k_ddpg_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, tab, 0, lp, 0, 1, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *p, double *d_out, void *stream) {
+    if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(p->core.device));
+    hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->core.dev(), p->core.bases[0]->cfg.batch, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_per_enable_ddpg(stmpc_ddpg_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return pop_per_enable(p->core, cfgs, enabled, P, [&] { return pop_upload(p->core); });
+}
+
+int stmpc_pop_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *cfgs, int P, stmpc_td3_pop **out) {
+    TRY(pop_check_create(c, cfgs, P, out, [](const stmpc_td3_cfg &g) -> const stmpc_ddpg_cfg & { return g.base; }));
     HIPCHK(hipSetDevice(c->device));
     stmpc_td3_pop *p = new stmpc_td3_pop();
-    p->device = c->device;
+    p->core.device = c->device;
     int rc = STMPC_OK;
-    std::vector<Td3Dev> host;
-    std::vector<DdpgDev> base;
     for (int m = 0; m < P && !rc; ++m) {
         stmpc_td3 *t = nullptr;
         rc = stmpc_td3_create(c, cfgs + m, &t);
-        if (!rc) { t->base->pop_member = true; p->members.push_back(t); host.push_back(t->dev); base.push_back(t->dev.v[0]); }
+        if (!rc) { t->base->pop_member = true; p->members.push_back(t); p->core.bases.push_back(t->base); }
     }
-    if (!rc) rc = p->table.ensure(host.size() * sizeof(Td3Dev));
-    if (!rc) rc = p->bases.ensure(base.size() * sizeof(DdpgDev));
-    if (!rc && (hipMemcpy(p->table.p, host.data(), host.size() * sizeof(Td3Dev), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(p->bases.p, base.data(), base.size() * sizeof(DdpgDev), hipMemcpyHostToDevice) != hipSuccess))
-        rc = fail(STMPC_EHIP, "hipMemcpy of the member tables failed");
-    if (!rc) rc = td3_pop_raise_lds(p->device, p->members[0]->base->lds);
+    if (!rc) rc = td3_pop_upload(p);
+    if (!rc) rc = td3_pop_raise_lds(c->device, p->core.bases[0]->lds);
     if (rc) { stmpc_pop_td3_destroy(p); return rc; }
     *out = p;
     return STMPC_OK;
@@ -756,51 +853,47 @@ int stmpc_pop_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *cfgs, int P, stmpc_t
 void stmpc_pop_td3_destroy(stmpc_td3_pop *p) {
     if (!p) return;
     for (stmpc_td3 *t : p->members) stmpc_td3_destroy(t);
-    (void)hipSetDevice(p->device);
+    (void)hipSetDevice(p->core.device);
     delete p;
 }
 
-int stmpc_pop_td3_size(const stmpc_td3_pop *p) { return p ? p->P() : 0; }
+int stmpc_pop_td3_size(const stmpc_td3_pop *p) { return p ? p->core.P() : 0; }
 
 stmpc_td3 *stmpc_pop_td3_member(stmpc_td3_pop *p, int m) {
-    if (!p || m < 0 || m >= p->P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
+    if (!p || m < 0 || m >= p->core.P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
     return p->members[m];
 }
 
 int stmpc_pop_td3_act_device(stmpc_td3_pop *p, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action,
                              uint32_t *d_debug, void *stream) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    return ddpg_pop_act(p->device, p->base_dev(), p->P(), p->members[0]->base, n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug, stream);
+    return pop_act(p->core, n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug, stream);
 }
 
 int stmpc_pop_td3_push_device(stmpc_td3_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
                               const int32_t *d_ticks, const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated,
                               const uint8_t *d_truncated, void *stream) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    return ddpg_pop_push(p->device, p->base_dev(), p->P(), p->members[0]->base, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action,
-                         d_reward, d_terminated, d_truncated, stream);
+    return pop_push(p->core, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated, stream);
 }
 
 int stmpc_pop_td3_update_device(stmpc_td3_pop *p, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream) {
-    if (!p || !lr_q || !lr_pi) return fail(STMPC_EINVAL, "NULL argument");
-    if (n_lr != p->P()) return fail(STMPC_EINVAL, "the learning-rate arrays have " + std::to_string(n_lr) + " entries, the population " + std::to_string(p->P()) + " members");
-    if (n_updates < 0) return fail(STMPC_EINVAL, "n_updates is negative");
+    if (!p) return fail(STMPC_EINVAL, "NULL argument");
     DdpgLr lq{}, lp{};
-    TRY(ddpg_pop_lrs(p->P(), lr_q, lq));
-    TRY(ddpg_pop_lrs(p->P(), lr_pi, lp));
-    HIPCHK(hipSetDevice(p->device));
-    const stmpc_ddpg *l = p->members[0]->base;
-    const Td3Grid g = td3_grid(l);
-    const int P = p->P();
+    TRY(pop_check_update(p->core, n_updates, lr_q, lr_pi, n_lr, lq, lp));
+    HIPCHK(hipSetDevice(p->core.device));
+    const stmpc_ddpg *l = p->core.bases[0];
+    const Grid g = l->grid;
+    const int P = p->core.P(), B = l->cfg.batch, Bp = l->rp.Bp;
     hipStream_t st = (hipStream_t)stream;
     for (int u = 0; u < n_updates; ++u) {                            // stmpc_td3_update_device's six launches (eight with prioritised members), each over the members in gridDim.z
-        if (p->per_any) hipLaunchKernelGGL(k_per_sample_td3_pop, dim3(1, 1, P), dim3(PER_THREADS), 0, st, p->dev(), l->cfg.batch, l->Bp, 1);
-        hipLaunchKernelGGL(k_td3_critic_fwd_pop, dim3(g.tiles, 2, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
-        hipLaunchKernelGGL(k_td3_wgrad_pop, dim3(g.jobs, 2, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 1, l->Bp, 1);
-        if (p->per_any) hipLaunchKernelGGL(k_per_update_td3_pop, dim3(1, 1, P), dim3(PER_THREADS), 0, st, p->dev(), l->cfg.batch, 1);
+        if (p->core.per_any) hipLaunchKernelGGL(k_per_sample_td3_pop, dim3(1, 1, P), dim3(PER_THREADS), 0, st, p->dev(), B, Bp, 1);
+        hipLaunchKernelGGL(k_td3_critic_fwd_pop, dim3(g.tiles, 2, P), dim3(AT_THREADS), l->lds, st, p->dev(), B, 1);
+        hipLaunchKernelGGL(k_td3_wgrad_pop, dim3(g.jobs, 2, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 1, Bp, 1);
+        if (p->core.per_any) hipLaunchKernelGGL(k_per_update_td3_pop, dim3(1, 1, P), dim3(PER_THREADS), 0, st, p->dev(), B, 1);
         hipLaunchKernelGGL(k_td3_adam_critics_pop, dim3(g.ablocks, 2, P), dim3(256), 0, st, p->dev(), lq, 1);
-        hipLaunchKernelGGL(k_td3_actor_fwd_pop, dim3(g.tiles, 1, P), dim3(AT_THREADS), l->lds, st, p->dev(), l->cfg.batch, 1);
-        hipLaunchKernelGGL(k_td3_wgrad_pop, dim3(g.jobs, 1, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 0, l->Bp, 1);
+        hipLaunchKernelGGL(k_td3_actor_fwd_pop, dim3(g.tiles, 1, P), dim3(AT_THREADS), l->lds, st, p->dev(), B, 1);
+        hipLaunchKernelGGL(k_td3_wgrad_pop, dim3(g.jobs, 1, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), 0, Bp, 1);
         hipLaunchKernelGGL(k_td3_adam_finish_pop, dim3(g.ablocks, 3, P), dim3(256), 0, st, p->dev(), lp, 1);
     }
     HIPCHK(hipGetLastError());
@@ -809,67 +902,15 @@ int stmpc_pop_td3_update_device(stmpc_td3_pop *p, int n_updates, const double *l
 
 int stmpc_pop_td3_stats_device(stmpc_td3_pop *p, double *d_out, void *stream) {
     if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(p->device));
-    hipLaunchKernelGGL(k_td3_stats_pop, dim3(1, 1, p->P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->members[0]->base->cfg.batch, d_out);
+    HIPCHK(hipSetDevice(p->core.device));
+    hipLaunchKernelGGL(k_td3_stats_pop, dim3(1, 1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->core.bases[0]->cfg.batch, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
-}  // extern "C"
-
-// ---- prioritised replay for the populations (stmpc_pop_per_*): stmpc_per_enable's work per member, then the device tables anew; kernels in
-// stmpc_per_pop_kernels.hpp -----------------------------------------------------------------------------------------------------------------------
-namespace {
-// the checks both entries share (bases[m]: member m's stmpc_ddpg): stmpc_per_enable's, on every enabled member, before anything is attached
-int pop_per_check(const std::vector<stmpc_ddpg *> &bases, bool called, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
-    if (!cfgs || !enabled) return fail(STMPC_EINVAL, "NULL argument");
-    if (P != (int)bases.size()) return fail(STMPC_EINVAL, "cfgs and enabled have " + std::to_string(P) + " entries, the population " + std::to_string(bases.size()) + " members");
-    if (called) return fail(STMPC_EINVAL, "prioritised replay was already set up on this population (one call, on empty rings)");
-    for (int m = 0; m < P; ++m)
-        if (enabled[m]) { TRY(per_check_cfg(cfgs + m)); TRY(per_check_ring(bases[m])); }
-    return STMPC_OK;
-}
-// per_attach on every enabled member; an allocation that fails leaves the members before it prioritised, which the tables then say too
-int pop_per_attach(const std::vector<stmpc_ddpg *> &bases, const stmpc_per_cfg *cfgs, const uint8_t *enabled, bool &any) {
-    int rc = STMPC_OK;
-    for (size_t m = 0; m < bases.size() && !rc; ++m)
-        if (enabled[m]) { rc = per_attach(bases[m], cfgs + m); any = any || !rc; }
-    return rc;
-}
-}  // namespace
-
-extern "C" {
-
-int stmpc_pop_per_enable_ddpg(stmpc_ddpg_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
-    if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    TRY(pop_per_check(p->members, p->per_called, cfgs, enabled, P));
-    p->per_called = true;
-    const int rc = pop_per_attach(p->members, cfgs, enabled, p->per_any);
-    if (!p->per_any) return rc;                                     // (no member enabled: the table stands)
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<DdpgDev> host;
-    for (const stmpc_ddpg *l : p->members) host.push_back(l->dev);
-    HIPCHK(hipMemcpy(p->table.p, host.data(), host.size() * sizeof(DdpgDev), hipMemcpyHostToDevice));
-    return rc;
-}
-
 int stmpc_pop_per_enable_td3(stmpc_td3_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    std::vector<stmpc_ddpg *> bases_of;
-    for (const stmpc_td3 *t : p->members) bases_of.push_back(t->base);
-    TRY(pop_per_check(bases_of, p->per_called, cfgs, enabled, P));
-    p->per_called = true;
-    const int rc = pop_per_attach(bases_of, cfgs, enabled, p->per_any);
-    if (!p->per_any) return rc;
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<Td3Dev> host;
-    std::vector<DdpgDev> base;
-    for (const stmpc_td3 *t : p->members) { host.push_back(t->dev); base.push_back(t->dev.v[0]); }
-    HIPCHK(hipMemcpy(p->table.p, host.data(), host.size() * sizeof(Td3Dev), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->bases.p, base.data(), base.size() * sizeof(DdpgDev), hipMemcpyHostToDevice));
-    return rc;
+    return pop_per_enable(p->core, cfgs, enabled, P, [&] { return td3_pop_upload(p); });
 }
 
 }  // extern "C"
@@ -892,14 +933,14 @@ int stmpc_actor_view_ddpg(stmpc_ddpg *l, int target, stmpc_actor **out) {
     // k_ddpg_adam keeps both actors packed in actor_layer's lane order; biases and the last layer are read in place in the padded parameter array
     const DdpgNet &pi = l->dev.pi;
     const float *w = target ? pi.wt : pi.w;
-    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipSetDevice(l->rp.device));
     stmpc_actor *a = new stmpc_actor();     // owns no buffer: destroying it frees nothing of the learner's
-    a->device = l->device; a->lds = actor_lds_bytes(l->h1p, l->h2p);
+    a->device = l->rp.device; a->lds = actor_lds_bytes(l->h1p, l->h2p);
     a->dev.p0 = target ? pi.t0 : pi.p0; a->dev.b0 = w + dg_o_b0(l->h1p);
     a->dev.p1 = target ? pi.t1 : pi.p1; a->dev.b1 = w + dg_o_b1(l->h1p, l->h2p);
     a->dev.w2 = w + dg_o_w2(l->h1p, l->h2p); a->dev.b2p = w + dg_o_b2(l->h1p, l->h2p);
     a->dev.scale = l->dev.scale; a->dev.mean = l->dev.mean; a->dev.n_in = pi.n_in; a->dev.h1p = l->h1p; a->dev.h2p = l->h2p;
-    const int rc = actor_raise_lds(0, l->device, a->lds);
+    const int rc = actor_raise_lds(0, l->rp.device, a->lds);
     if (rc) { stmpc_actor_destroy(a); return rc; }
     *out = a;
     return STMPC_OK;
@@ -958,16 +999,17 @@ int stmpc_actor_pop_eval_device(stmpc_ctx *c, const stmpc_actor_pop *p, const st
 
 }  // extern "C"
 
-// ---- DQN learner (stmpc_dqn_*): the discrete agent on the DDPG learner's ring, counters and tree; kernels in stmpc_dqn_kernels.hpp -----------------
-#include "stmpc_dqn_kernels.hpp"
-
+// ---- DQN learner (stmpc_dqn_*): the discrete agent on a replay store, one network and one workspace of its own; kernels in stmpc_dqn_kernels.hpp --
 struct stmpc_dqn {
-    stmpc_ddpg base;                        // NOT made by stmpc_ddpg_create and never handed out: its buffers, its dev (ring, counters, tickets, workspace, base.dev.q = the
-                                            // Q-network, h2p = Ap) and the fields the per_ helpers above read (device, cfg.batch, cfg.capacity, Bp, per ...)
     stmpc_dqn_cfg cfg{};
-    DqnDev dev{};                           // dev.base is a copy of base.dev: made anew after stmpc_dqn_per_enable
-    int Ap = 0, tiles = 0, jobs = 0, ablocks = 0;
-    int64_t slot_len() const { return (int64_t)cfg.h1 * cfg.n_obs + cfg.h1 + (int64_t)cfg.n_actions * cfg.h1 + cfg.n_actions; }
+    DqnDev dev{};                           // dev.base: the constants (stmpc_dqn_create), base.q the Q-network (base.h2p = Ap; base.pi stays null), the
+                                            // workspace, and the replay's part, which rp.wire writes at create and again in stmpc_dqn_per_enable
+    Replay rp;
+    DevBuf net[11], ws[7];
+    std::vector<Seg> lay;
+    int h1p = 0, Ap = 0, np = 0;
+    size_t lds = 0;
+    Grid grid{};
 };
 
 namespace {
@@ -976,25 +1018,10 @@ int dqn_raise_lds(int device, size_t lds) {
     TRY(raise_dynamic_lds((const void *)k_dqn_fwd, "k_dqn_fwd", ceiling[0], device, lds));
     return raise_dynamic_lds((const void *)k_dqn_act, "k_dqn_act", ceiling[1], device, lds);
 }
-float *dqn_slot_ptr(stmpc_dqn *t, int slot) {
-    const DdpgNet &n = t->dev.base.q;
-    float *const p[4] = {n.w, n.wt, n.m, n.v};
-    return p[slot];
-}
-// slot layout (unpadded) <-> padded layout, on the host
-void dqn_pad(const stmpc_dqn *t, const float *flat, std::vector<float> &pad, bool to_pad, float *flat_out) {
-    const int h1 = t->cfg.h1, A = t->cfg.n_actions, n_obs = t->cfg.n_obs, h1p = t->base.h1p, Ap = t->Ap;
-    size_t i = 0;
-    auto item = [&](size_t p) { if (to_pad) pad[p] = flat[i]; else flat_out[i] = pad[p]; ++i; };
-    for (int n = 0; n < h1; ++n) for (int k = 0; k < n_obs; ++k) item((size_t)n * AT_KIN + k);
-    for (int n = 0; n < h1; ++n) item((size_t)dg_o_b0(h1p) + n);
-    for (int n = 0; n < A; ++n) for (int k = 0; k < h1; ++k) item((size_t)dg_o_w1(h1p) + (size_t)n * h1p + k);
-    for (int n = 0; n < A; ++n) item((size_t)dg_o_b1(h1p, Ap) + n);
-}
 // the pass and the weight gradients; dbg: stmpc_dqn_targets_device's output
 void dqn_launch_grads(stmpc_dqn *t, int gate, float *dbg, hipStream_t st) {
-    hipLaunchKernelGGL(k_dqn_fwd, dim3(t->tiles), dim3(AT_THREADS), t->base.lds, st, t->dev, t->cfg.batch, gate, dbg);
-    hipLaunchKernelGGL(k_dqn_wgrad, dim3(t->jobs), dim3(64 * DG_WG_WAVES), 0, st, t->dev, t->base.Bp, gate);
+    hipLaunchKernelGGL(k_dqn_fwd, dim3(t->grid.tiles), dim3(AT_THREADS), t->lds, st, t->dev, t->cfg.batch, gate, dbg);
+    hipLaunchKernelGGL(k_dqn_wgrad, dim3(t->grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t->dev, t->rp.Bp, gate);
 }
 }  // namespace
 
@@ -1011,44 +1038,24 @@ int stmpc_dqn_create(stmpc_ctx *c, const stmpc_dqn_cfg *g, stmpc_dqn **out) {
     if (!(g->gamma >= 0) || !std::isfinite(g->gamma) || !(g->beta1 >= 0 && g->beta1 < 1) || !(g->beta2 >= 0 && g->beta2 < 1) || !(g->eps > 0) ||
         (g->clip_targets && !(g->clip_min <= g->clip_max))) return fail(STMPC_EINVAL, "DQN constants out of range");
     HIPCHK(hipSetDevice(c->device));
+    const int h1p = (g->h1 + 15) & ~15, Ap = (g->n_actions + 15) & ~15;
+    const size_t lds = ddpg_tile_bytes(h1p, Ap);
+    if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, "DQN network too wide for one workgroup's LDS");
     stmpc_dqn *t = new stmpc_dqn();
-    stmpc_ddpg *l = &t->base;
-    t->cfg = *g;
-    l->device = c->device;
-    l->cfg.n_obs = g->n_obs; l->cfg.h1 = g->h1; l->cfg.h2 = g->n_actions; l->cfg.batch = g->batch; l->cfg.capacity = g->capacity;
-    l->cfg.replay_start = g->replay_start; l->cfg.seed = g->seed;
-    const int h1p = l->h1p = (g->h1 + 15) & ~15, Ap = l->h2p = t->Ap = (g->n_actions + 15) & ~15;
-    const int np = l->np = dg_nparam(h1p, Ap), Bp = l->Bp = (g->batch + 15) & ~15;
-    l->lds = ddpg_tile_bytes(h1p, Ap);
-    if (l->lds + 1024 > (size_t)c->lds_per_block) { delete t; return fail(STMPC_EINVAL, "DQN network too wide for one workgroup's LDS"); }
-    t->tiles = Bp / AT_TM;
-    t->jobs = (Ap / 16) * (h1p / 16) + 2 * (h1p / 16) + Ap / 16 + h1p / 16;      // k_ddpg_wgrad's dW1, dW0, db1, db0
-    t->ablocks = (dq_nparam(h1p, Ap) + 255) / 256;
-    DdpgDev &d = l->dev;
-    int rc = 0;
-    {
-        DdpgNet &n = d.q;
-        float **ptr[11] = {&n.w, &n.wt, &n.m, &n.v, &n.g, &n.p0, &n.p1, &n.p1t, &n.t0, &n.t1, &n.bpow};
-        const size_t len[11] = {(size_t)np, (size_t)np, (size_t)np, (size_t)np, (size_t)np, (size_t)h1p * AT_KIN, (size_t)Ap * h1p, (size_t)Ap * h1p,
-                                (size_t)h1p * AT_KIN, (size_t)Ap * h1p, 4};
-        for (int i = 0; i < 11 && !rc; ++i) { rc = ddpg_zero(l->netbuf[1][i], len[i] * sizeof(float)); *ptr[i] = l->netbuf[1][i].as<float>(); }
-        n.n_in = g->n_obs;
-    }
-    const size_t wlen[7] = {(size_t)Bp * AT_KIN, (size_t)Bp * h1p, (size_t)Bp * Ap, (size_t)Bp * Ap, (size_t)Bp * h1p, (size_t)Bp, (size_t)Bp * 2};
-    float **wptr[7] = {&d.aX, &d.aH1, &d.aH2, &d.aD2, &d.aD1, &d.adz, &d.arow};
-    for (int i = 0; i < 7 && !rc; ++i) { rc = ddpg_zero(l->ws[i], wlen[i] * sizeof(float)); *wptr[i] = l->ws[i].as<float>(); }
-    if (!rc) rc = ddpg_zero(l->ring, (size_t)g->capacity * DG_ROW * sizeof(float));
-    if (!rc) rc = ddpg_zero(l->cnt, DG_NCNT * sizeof(long long));
-    if (!rc) rc = ddpg_zero(l->tick, DG_NTICK * sizeof(unsigned int));
-    if (!rc) rc = dqn_raise_lds(l->device, l->lds);
+    t->cfg = *g; t->h1p = h1p; t->Ap = Ap; t->np = dg_nparam(h1p, Ap); t->lds = lds;
+    t->lay = slot_layout(g->n_obs, g->h1, g->n_actions, h1p, Ap, false);
+    t->rp.device = c->device;                                        // (what destroy selects, should an allocation fail)
+    DdpgDev &d = t->dev.base;
+    int rc = net_build(t->net, d.q, g->n_obs, h1p, Ap);
+    if (!rc) rc = ws_build(t->ws, d, (g->batch + 15) & ~15, h1p, Ap);
+    if (!rc) rc = t->rp.create(c->device, g->batch, g->capacity);     // (the ring behind the net and the workspace: the order the buffers always had)
+    if (!rc) rc = dqn_raise_lds(c->device, lds);
     if (rc) { stmpc_dqn_destroy(t); return rc; }
-    d.ring = l->ring.as<float>(); d.cnt = l->cnt.as<long long>(); d.tick = l->tick.as<unsigned int>();
-    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = g->n_actions; d.h1p = h1p; d.h2p = Ap; d.capacity = g->capacity; d.replay_start = g->replay_start; d.seed = g->seed;
+    t->grid = make_grid(t->rp.Bp, h1p, Ap, false);
+    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = g->n_actions; d.h1p = h1p; d.h2p = Ap; d.replay_start = g->replay_start; d.seed = g->seed;
     d.gamma = (float)g->gamma; d.beta1 = (float)g->beta1; d.beta2 = (float)g->beta2;
     d.omb1 = 1.0f - d.beta1; d.omb2 = 1.0f - d.beta2; d.eps = (float)g->eps;       // (tau, the time feature, the squash and the noise: unused, 0)
-    const float one[4] = {1.f, 1.f, 0.f, 0.f};                       // beta^0
-    if (hipMemcpy(d.q.bpow, one, sizeof one, hipMemcpyHostToDevice) != hipSuccess) { stmpc_dqn_destroy(t); return fail(STMPC_EHIP, "hipMemcpy of the beta powers failed"); }
-    t->dev.base = d;
+    t->rp.wire(d);
     t->dev.A = g->n_actions; t->dev.Ap = Ap; t->dev.dbl = g->double_dqn != 0; t->dev.clip = g->clip_targets != 0; t->dev.target_period = g->target_period;
     t->dev.clip_min = (float)g->clip_min; t->dev.clip_max = (float)g->clip_max;
     *out = t;
@@ -1057,65 +1064,32 @@ int stmpc_dqn_create(stmpc_ctx *c, const stmpc_dqn_cfg *g, stmpc_dqn **out) {
 
 void stmpc_dqn_destroy(stmpc_dqn *t) {
     if (!t) return;
-    (void)hipSetDevice(t->base.device);
+    (void)hipSetDevice(t->rp.device);
     delete t;
 }
 
 int stmpc_dqn_set_params(stmpc_dqn *t, int slot, const float *values, int64_t count) {
-    if (!t || !values || slot < 0 || slot > 3) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
-    if (count != t->slot_len()) return fail(STMPC_EINVAL, "count is not the length of this slot");
-    HIPCHK(hipSetDevice(t->base.device));
-    std::vector<float> pad((size_t)t->base.np, 0.f);
-    dqn_pad(t, values, pad, true, nullptr);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(dqn_slot_ptr(t, slot), pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (slot < 2) {                                                  // the packed copies follow the parameters
-        hipLaunchKernelGGL(k_dqn_adam, dim3(t->ablocks), dim3(256), 0, (hipStream_t)0, t->dev, 0.f, 1, 1);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-    }
-    return STMPC_OK;
+    TRY(slot_args(t, values, slot, 4));
+    return slot_set(t->rp.device, t->lay, t->np, net_slot(t->dev.base.q, slot), values, count, slot < 2,
+                    [&] { hipLaunchKernelGGL(k_dqn_adam, dim3(t->grid.ablocks), dim3(256), 0, (hipStream_t)0, t->dev, 0.f, 1, 1); });
 }
 
 int stmpc_dqn_get_params(stmpc_dqn *t, int slot, float *values, int64_t count) {
-    if (!t || !values || slot < 0 || slot > 3) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
-    if (count != t->slot_len()) return fail(STMPC_EINVAL, "count is not the length of this slot");
-    HIPCHK(hipSetDevice(t->base.device));
-    std::vector<float> pad((size_t)t->base.np, 0.f);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(pad.data(), dqn_slot_ptr(t, slot), pad.size() * sizeof(float), hipMemcpyDeviceToHost));
-    dqn_pad(t, nullptr, pad, false, values);
-    return STMPC_OK;
+    TRY(slot_args(t, values, slot, 4));
+    return slot_get(t->rp.device, t->lay, t->np, net_slot(t->dev.base.q, slot), values, count);
 }
 
 int stmpc_dqn_set_state(stmpc_dqn *t, const int64_t *counters, const float *beta_pow) {
     if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
-    const stmpc_ddpg *l = &t->base;
-    if (counters[DG_CURSOR] < 0 || counters[DG_CURSOR] >= l->cfg.capacity || counters[DG_FILL] < 0 || counters[DG_FILL] > l->cfg.capacity || counters[DG_UPDATES] < 0 ||
-        counters[DG_ACTS] < 0 || counters[DG_FRAMES] < 0) return fail(STMPC_EINVAL, "counters out of range");
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    long long cn[DG_NCNT];
-    if (l->per) {                                                    // the tree's leaves follow the ring's cursor and fill
-        HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
-        if (cn[DG_CURSOR] != counters[DG_CURSOR] || cn[DG_FILL] != counters[DG_FILL])
-            return fail(STMPC_EINVAL, "prioritised replay is enabled: the ring's cursor and fill cannot be set (the priorities belong to the rows pushed)");
-    }
-    for (int i = 0; i < DG_NCNT; ++i) cn[i] = i <= DG_FRAMES ? counters[i] : 0;
-    HIPCHK(hipMemcpy(l->dev.cnt, cn, sizeof cn, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(l->dev.q.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
+    TRY(t->rp.set_counters(counters));
+    HIPCHK(hipMemcpy(t->dev.base.q.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
     return STMPC_OK;
 }
 
 int stmpc_dqn_get_state(stmpc_dqn *t, int64_t *counters, float *beta_pow) {
     if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
-    const stmpc_ddpg *l = &t->base;
-    HIPCHK(hipSetDevice(l->device));
-    HIPCHK(hipDeviceSynchronize());
-    long long cn[DG_NCNT];
-    HIPCHK(hipMemcpy(cn, l->dev.cnt, sizeof cn, hipMemcpyDeviceToHost));
-    for (int i = 0; i < DG_NCNT; ++i) counters[i] = cn[i];
-    HIPCHK(hipMemcpy(beta_pow, l->dev.q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
+    TRY(t->rp.get_counters(counters));
+    HIPCHK(hipMemcpy(beta_pow, t->dev.base.q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
     return STMPC_OK;
 }
 
@@ -1125,10 +1099,8 @@ int stmpc_dqn_push_device(stmpc_dqn *t, int N, const float *d_obs, const float *
     if (N < 0 || N > t->cfg.capacity || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N exceeds the replay capacity, or obs_stride is shorter than the observation");
     if (N == 0) return STMPC_OK;
     if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(t->base.device));
-    const long long items = (long long)N * DG_ROW;
-    const int blocks = (int)((items + 255) / 256 < 1024 ? (items + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_dqn_push, dim3(blocks), dim3(256), 0, (hipStream_t)stream, t->dev, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward,
+    HIPCHK(hipSetDevice(t->rp.device));
+    hipLaunchKernelGGL(k_dqn_push, dim3(push_blocks(N)), dim3(256), 0, (hipStream_t)stream, t->dev, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward,
                        d_terminated, d_truncated);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -1140,8 +1112,8 @@ int stmpc_dqn_act_device(stmpc_dqn *t, int N, const float *d_obs, int obs_stride
     if (!(eps >= 0 && eps <= 1)) return fail(STMPC_EINVAL, "eps must be in 0 ... 1");
     if (N == 0) return STMPC_OK;
     if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(t->base.device));
-    hipLaunchKernelGGL(k_dqn_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t->base.lds, (hipStream_t)stream, t->dev, N, d_obs, obs_stride, (float)eps,
+    HIPCHK(hipSetDevice(t->rp.device));
+    hipLaunchKernelGGL(k_dqn_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t->lds, (hipStream_t)stream, t->dev, N, d_obs, obs_stride, (float)eps,
                        eps > 0 ? 1 : 0, d_action, d_debug_q);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -1150,13 +1122,13 @@ int stmpc_dqn_act_device(stmpc_dqn *t, int N, const float *d_obs, int obs_stride
 int stmpc_dqn_update_device(stmpc_dqn *t, int n_updates, double lr, void *stream) {
     if (!t) return fail(STMPC_EINVAL, "learner is NULL");
     if (n_updates < 0 || !(lr >= 0)) return fail(STMPC_EINVAL, "n_updates or the learning rate is negative");
-    HIPCHK(hipSetDevice(t->base.device));
+    HIPCHK(hipSetDevice(t->rp.device));
     hipStream_t st = (hipStream_t)stream;
     for (int u = 0; u < n_updates; ++u) {                            // three launches, five with prioritised replay, whatever the counters say
-        per_launch_sample(&t->base, 1, st);
+        per_launch_sample(t->rp, t->dev.base, 1, st);
         dqn_launch_grads(t, 1, nullptr, st);
-        per_launch_update(&t->base, st);
-        hipLaunchKernelGGL(k_dqn_adam, dim3(t->ablocks), dim3(256), 0, st, t->dev, (float)lr, 0, 1);
+        per_launch_update(t->rp, t->dev.base, st);
+        hipLaunchKernelGGL(k_dqn_adam, dim3(t->grid.ablocks), dim3(256), 0, st, t->dev, (float)lr, 0, 1);
     }
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -1164,9 +1136,9 @@ int stmpc_dqn_update_device(stmpc_dqn *t, int n_updates, double lr, void *stream
 
 int stmpc_dqn_grads_device(stmpc_dqn *t, float *d_grad, void *stream) {
     if (!t || !d_grad) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->base.device));
+    HIPCHK(hipSetDevice(t->rp.device));
     hipStream_t st = (hipStream_t)stream;
-    per_launch_sample(&t->base, 0, st);
+    per_launch_sample(t->rp, t->dev.base, 0, st);
     dqn_launch_grads(t, 0, nullptr, st);
     hipLaunchKernelGGL(k_dqn_unpad, dim3(128), dim3(256), 0, st, t->dev, (const float *)t->dev.base.q.g, d_grad);
     HIPCHK(hipGetLastError());
@@ -1175,25 +1147,21 @@ int stmpc_dqn_grads_device(stmpc_dqn *t, float *d_grad, void *stream) {
 
 int stmpc_dqn_targets_device(stmpc_dqn *t, float *d_out, void *stream) {
     if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->base.device));
-    per_launch_sample(&t->base, 0, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_dqn_fwd, dim3(t->tiles), dim3(AT_THREADS), t->base.lds, (hipStream_t)stream, t->dev, t->cfg.batch, 0, d_out);
+    HIPCHK(hipSetDevice(t->rp.device));
+    per_launch_sample(t->rp, t->dev.base, 0, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_dqn_fwd, dim3(t->grid.tiles), dim3(AT_THREADS), t->lds, (hipStream_t)stream, t->dev, t->cfg.batch, 0, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
 int stmpc_dqn_gather_device(stmpc_dqn *t, float *d_rows, void *stream) {
     if (!t || !d_rows) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->base.device));
-    per_launch_sample(&t->base, 0, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_replay_gather, dim3((t->cfg.batch * DG_ROW + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->dev.base, t->cfg.batch, d_rows);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    return replay_gather(t->rp, t->dev.base, d_rows, stream);
 }
 
 int stmpc_dqn_stats_device(stmpc_dqn *t, double *d_out, void *stream) {
     if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->base.device));
+    HIPCHK(hipSetDevice(t->rp.device));
     hipLaunchKernelGGL(k_dqn_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, t->dev, t->cfg.batch, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -1202,29 +1170,26 @@ int stmpc_dqn_stats_device(stmpc_dqn *t, double *d_out, void *stream) {
 int stmpc_dqn_per_enable(stmpc_dqn *t, const stmpc_per_cfg *g) {
     if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
     TRY(per_check_cfg(g));
-    TRY(per_check_ring(&t->base));
-    TRY(per_attach(&t->base, g));
-    t->dev.base = t->base.dev;                                       // (the tree, idx, aw, atd and the constants)
+    TRY(t->rp.check_empty());
+    TRY(t->rp.attach(g, false));
+    t->rp.wire(t->dev.base);                                         // (the tree, idx, aw, atd and the constants)
     return STMPC_OK;
 }
 
 int stmpc_dqn_per_tree_read(stmpc_dqn *t, int64_t first, int64_t count, double *nodes) {
     if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return stmpc_per_tree_read(&t->base, first, count, nodes);
+    return t->rp.read_tree(first, count, nodes);
 }
 
 int stmpc_dqn_per_last_device(stmpc_dqn *t, int64_t *d_idx, float *d_td, float *d_weight, void *stream) {
     if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return stmpc_per_last_device(&t->base, d_idx, d_td, d_weight, stream);
+    return per_last(t->rp, t->dev.base, d_idx, d_td, d_weight, stream);
 }
 
 int stmpc_dqn_padded_read(stmpc_dqn *t, int slot, float *values, int64_t count) {
     if (!t || !values || slot < 0 || slot > STMPC_DQN_GRAD) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
-    if (count != dq_nparam(t->base.h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
-    HIPCHK(hipSetDevice(t->base.device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(values, slot == STMPC_DQN_GRAD ? t->dev.base.q.g : dqn_slot_ptr(t, slot), (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-    return STMPC_OK;
+    if (count != dq_nparam(t->h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
+    return read_back(t->rp.device, values, slot == STMPC_DQN_GRAD ? t->dev.base.q.g : net_slot(t->dev.base.q, slot), (size_t)count * sizeof(float));
 }
 
 }  // extern "C"

@@ -427,11 +427,84 @@ def per_weights_host(nodes, idx, fill, beta):
 
 
 # ---- the learner -------------------------------------------------------------------------------------------------------------------------------
-class DDPGLearner:
+class _Learner:
+    """What ``DDPGLearner`` and ``DQNLearner`` share word for word: the handle's lifetime, the stream, the output tensor kept per n, the debug reads
+    of the replay and the statistics, and ``state_dict`` / ``load_state_dict``.  A subclass names its binding's entries (``ctx.<_api>_<name>``, and
+    ``ctx.<_per_api>_<name>`` for prioritised replay), its ``_slots`` and ``_flatten``, and reads one slot in ``_slot``."""
+
+    def _call(self, name):
+        return getattr(self.ctx, "%s_%s" % (self._api, name))
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                self._call("destroy")(self.handle)
+            except Exception:
+                pass
+            self.handle = None
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _out(self, n, dtype):
+        """The tensor [n] ``act`` returns: one per n, reused."""
+        out = self._actions.get(n)
+        if out is None:
+            out = self._actions[n] = self.torch.empty(n, dtype=dtype, device=self.device)
+        return out
+
+    def minibatch(self):
+        """Debug: the replay rows [batch][68] the next update will read (numpy; ``batch_from_rows`` / ``dqn_batch_from_rows``); synchronises."""
+        rows = self.torch.empty(self.cfg.batch, _capi.DDPG_ROW, dtype=self.torch.float32, device=self.device)
+        self._call("gather")(self.handle, rows.data_ptr(), self._stream())
+        return rows.cpu().numpy()
+
+    def priorities(self):
+        """Debug, prioritised replay: the sum tree, float64 [2 * leaves - 1] (numpy; ``SumTreeHost``'s layout); synchronises."""
+        return getattr(self.ctx, self._per_api + "_tree_read")(self.handle, 0, 2 * per_leaves(self.cfg.capacity) - 1)
+
+    def last_sample(self):
+        """Debug, prioritised replay: {"idx" int64, "td" float32, "weight" float32}, [batch] each (numpy) -- the ring rows and importance weights of
+        the most recent sampling step (an update's, or ``minibatch`` / ``grads`` / ``targets``') and Q - y of the most recent critic pass (TD3: of
+        the critic with the larger magnitude); synchronises."""
+        torch, B = self.torch, self.cfg.batch
+        idx = torch.zeros(B, dtype=torch.int64, device=self.device)
+        td, w = (torch.zeros(B, dtype=torch.float32, device=self.device) for _ in range(2))
+        getattr(self.ctx, self._per_api + "_last")(self.handle, idx.data_ptr(), td.data_ptr(), w.data_ptr(), self._stream())
+        return {"idx": idx.cpu().numpy(), "td": td.cpu().numpy(), "weight": w.cpu().numpy()}
+
+    def stats_device(self):
+        """fp64 [4] device tensor: the (critic's) loss and mean Q(s, a) of the last minibatch, fill, updates done (asynchronous)."""
+        self._call("stats")(self.handle, self._stats.data_ptr(), self._stream())
+        return self._stats
+
+    def state_dict(self):
+        """{"params": the slots (eight of DDPG, four of DQN) as dicts of numpy tensors + beta_pow + updates, "counters": int64 [8]}; the replay ring
+        is not part of it."""
+        cn, bp = self._call("get_state")(self.handle)
+        params = {slot: self._slot(i) for i, slot in enumerate(self._slots)}
+        params["beta_pow"], params["updates"] = bp, int(cn[2])
+        return {"params": params, "counters": cn}
+
+    def load_state_dict(self, sd):
+        """The inverse; ``counters`` None: only the update count and Adam's beta powers are set (the replay's cursor and fill stay)."""
+        p = sd["params"]
+        for i, slot in enumerate(self._slots):
+            self._call("set_params")(self.handle, i, self._flatten(p[slot]))
+        cn = sd.get("counters")
+        if cn is None:
+            cn, _ = self._call("get_state")(self.handle)
+            cn[2] = int(p["updates"])
+        self._call("set_state")(self.handle, cn, p["beta_pow"])
+
+
+class DDPGLearner(_Learner):
     """``env_or_dims``: a ``MergeVecEnv`` (continuous-jerk; its context, observation width and action Box are taken over) or the observation width.
     ``cfg``: ``DDPGConfig`` (None: the defaults); ``seed``: of the initialisation, the minibatch indices and the exploration noise;
     ``init``: None (torch's nn.Linear initialisation, last layers zero), the name of a shipped actor ("medium1": that actor, a fresh critic), or a
     dict ``{"actor": net, "critic": net}`` of numpy tensors."""
+
+    _api, _per_api, _slots, _flatten = "ddpg", "per", _capi.DDPG_SLOTS, staticmethod(flatten)
 
     def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None):
         import torch
@@ -475,16 +548,9 @@ class DDPGLearner:
         """The parameter state a new learner starts from; ``rng`` stands after the draws of the actor and the critic."""
         return new_params(a_net, q_net)
 
-    def __del__(self):
-        if getattr(self, "handle", None) is not None:
-            try:
-                self.ctx.ddpg_destroy(self.handle)
-            except Exception:
-                pass
-            self.handle = None
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
+    def _slot(self, i):
+        c, which = self.cfg, "critic" if i >= 4 else "actor"
+        return unflatten(self.ctx.ddpg_get_params(self.handle, i, self._lens[which]), c.n_obs + (2 if i >= 4 else 1), c.h1, c.h2)
 
     # -- acting / replay / update: asynchronous ---------------------------------------------------------------------------------------------
     def act(self, obs, ticks, noise=True, debug=None):
@@ -492,9 +558,7 @@ class DDPGLearner:
         plus N(0, cfg.noise_std) exploration noise if ``noise``, clipped to the action Box.  The returned tensor is reused by the next call
         with the same n.  ``debug``: uint32 [n][4] device tensor for the draws (debugging)."""
         n = obs.shape[0]
-        out = self._actions.get(n)
-        if out is None:
-            out = self._actions[n] = self.torch.empty(n, dtype=self.torch.float64, device=self.device)
+        out = self._out(n, self.torch.float64)
         assert obs.dtype == self.torch.float32 and ticks.dtype == self.torch.int32 and obs.stride(1) == 1
         self.ctx.ddpg_act(self.handle, n, obs.data_ptr(), obs.stride(0), ticks.data_ptr(), noise, out.data_ptr(), debug.data_ptr() if debug is not None else 0,
                           self._stream())
@@ -524,64 +588,14 @@ class DDPGLearner:
         self.ctx.ddpg_grads(self.handle, ga.data_ptr(), gq.data_ptr(), self._stream())
         return unflatten(ga.cpu().numpy(), c.n_obs + 1, c.h1, c.h2), unflatten(gq.cpu().numpy(), c.n_obs + 2, c.h1, c.h2)
 
-    def minibatch(self):
-        """Debug: the replay rows [batch][68] the next update will read (numpy); synchronises."""
-        rows = self.torch.empty(self.cfg.batch, _capi.DDPG_ROW, dtype=self.torch.float32, device=self.device)
-        self.ctx.ddpg_gather(self.handle, rows.data_ptr(), self._stream())
-        return rows.cpu().numpy()
-
-    def priorities(self):
-        """Debug, prioritised replay: the sum tree, float64 [2 * leaves - 1] (numpy; ``SumTreeHost``'s layout); synchronises."""
-        return self.ctx.per_tree_read(self.handle, 0, 2 * per_leaves(self.cfg.capacity) - 1)
-
-    def last_sample(self):
-        """Debug, prioritised replay: {"idx" int64, "td" float32, "weight" float32}, [batch] each (numpy) -- the ring rows and importance weights of
-        the most recent sampling step (an update's, or ``minibatch`` / ``grads`` / ``targets``') and Q - y of the most recent critic pass (TD3: of
-        the critic with the larger magnitude); synchronises."""
-        torch, B = self.torch, self.cfg.batch
-        idx = torch.zeros(B, dtype=torch.int64, device=self.device)
-        td, w = (torch.zeros(B, dtype=torch.float32, device=self.device) for _ in range(2))
-        self.ctx.per_last(self.handle, idx.data_ptr(), td.data_ptr(), w.data_ptr(), self._stream())
-        return {"idx": idx.cpu().numpy(), "td": td.cpu().numpy(), "weight": w.cpu().numpy()}
-
-    def stats_device(self):
-        """fp64 [4] device tensor: critic loss and mean Q of the last minibatch, fill, updates done (asynchronous)."""
-        self.ctx.ddpg_stats(self.handle, self._stats.data_ptr(), self._stream())
-        return self._stats
-
     def stats(self):
-        """The same as a dict; synchronises."""
+        """``stats_device`` as a dict; synchronises."""
         s = self.stats_device().cpu().numpy()
         return {"critic_loss": float(s[0]), "mean_q": float(s[1]), "fill": int(s[2]), "updates": int(s[3])}
 
-    # -- state ------------------------------------------------------------------------------------------------------------------------------
-    def state_dict(self):
-        """{"params": the eight slots as dicts of numpy tensors + beta_pow + updates, "counters": int64 [8]}; the replay ring is not part of it."""
-        c = self.cfg
-        cn, bp = self.ctx.ddpg_get_state(self.handle)
-        params = {}
-        for i, slot in enumerate(_capi.DDPG_SLOTS):
-            which = "critic" if i >= 4 else "actor"
-            params[slot] = unflatten(self.ctx.ddpg_get_params(self.handle, i, self._lens[which]), c.n_obs + (2 if i >= 4 else 1), c.h1, c.h2)
-        params["beta_pow"], params["updates"] = bp, int(cn[2])
-        return {"params": params, "counters": cn}
-
-    def load_state_dict(self, sd):
-        """The inverse; ``counters`` None: only the update count and Adam's beta powers are set (the replay's cursor and fill stay)."""
-        p = sd["params"]
-        for i, slot in enumerate(_capi.DDPG_SLOTS):
-            self.ctx.ddpg_set_params(self.handle, i, flatten(p[slot]))
-        cn = sd.get("counters")
-        if cn is None:
-            cn, _ = self.ctx.ddpg_get_state(self.handle)
-            cn[2] = int(p["updates"])
-        self.ctx.ddpg_set_state(self.handle, cn, p["beta_pow"])
-
     def export_actor(self, path):
         """Write the online actor as the ``.npz`` ``actor.load_weights`` reads (w0 ... b2 float32, tanh_scale, tanh_mean)."""
-        c = self.cfg
-        net = unflatten(self.ctx.ddpg_get_params(self.handle, 0, self._lens["actor"]), c.n_obs + 1, c.h1, c.h2)
-        write_actor(path, net, c.tanh_scale, c.tanh_mean)
+        write_actor(path, self._slot(0), self.cfg.tanh_scale, self.cfg.tanh_mean)
         return path
 
 
@@ -1045,11 +1059,13 @@ def dqn_adam_host(w, g, m, v, beta_pow, lr, cfg):
     return w - step * (m / (np.sqrt(v) / bc2s + eps)), m, v, np.array([pw1, pw2], dtype=f)
 
 
-class DQNLearner:
+class DQNLearner(_Learner):
     """DQN on the device for the discrete-action envs (``MergeVecEnv("sumo-jerk-v0")``, ``"sumo-accel-v0"``): the reference's TRAIN_DQN
     (dqn.py:257-359) with ``DDPGLearner``'s interface.  ``env_or_dims``: such an env (its context, observation width, action count and action table
     are taken over) or ``(n_obs, n_actions)``.  ``init``: None (torch's nn.Linear initialisation) or a net {w0, b0, w1, b1}.
     One update is three HIP launches (five with ``cfg.per``); acting, pushing and updating never synchronise with the host."""
+
+    _api, _per_api, _slots, _flatten = "dqn", "dqn_per", _capi.DQN_SLOTS, staticmethod(flatten_q)
 
     def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None):
         env = None if isinstance(env_or_dims, (tuple, list)) else env_or_dims
@@ -1086,16 +1102,9 @@ class DQNLearner:
         self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self._actions = {}
 
-    def __del__(self):
-        if getattr(self, "handle", None) is not None:
-            try:
-                self.ctx.dqn_destroy(self.handle)
-            except Exception:
-                pass
-            self.handle = None
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
+    def _slot(self, i):
+        c = self.cfg
+        return unflatten_q(self.ctx.dqn_get_params(self.handle, i, self._len), c.n_obs, c.h1, c.n_actions)
 
     # -- acting / replay / update: asynchronous ---------------------------------------------------------------------------------------------
     def act(self, obs, ticks=None, eps=0.0, debug_q=None):
@@ -1104,9 +1113,7 @@ class DQNLearner:
         ``DDPGLearner``'s signature and not read: the network has no time feature.  The returned tensor is reused by the next call with the
         same n.  ``debug_q``: float32 [n][n_actions] device tensor for Q(obs)."""
         n = obs.shape[0]
-        out = self._actions.get(n)
-        if out is None:
-            out = self._actions[n] = self.torch.empty(n, dtype=self.torch.int32, device=self.device)
+        out = self._out(n, self.torch.int32)
         assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
         assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (n, self.cfg.n_actions))
         self.ctx.dqn_act(self.handle, n, obs.data_ptr(), obs.stride(0), eps, out.data_ptr(), debug_q.data_ptr() if debug_q is not None else 0, self._stream())
@@ -1139,59 +1146,15 @@ class DQNLearner:
         self.ctx.dqn_targets(self.handle, out.data_ptr(), self._stream())
         return out.cpu().numpy()
 
-    def minibatch(self):
-        """Debug: the replay rows [batch][68] the next update will read (numpy; ``dqn_batch_from_rows``); synchronises."""
-        rows = self.torch.empty(self.cfg.batch, _capi.DDPG_ROW, dtype=self.torch.float32, device=self.device)
-        self.ctx.dqn_gather(self.handle, rows.data_ptr(), self._stream())
-        return rows.cpu().numpy()
-
-    def priorities(self):
-        """Debug, prioritised replay: the sum tree, float64 [2 * leaves - 1] (``SumTreeHost``'s layout); synchronises."""
-        return self.ctx.dqn_per_tree_read(self.handle, 0, 2 * per_leaves(self.cfg.capacity) - 1)
-
-    def last_sample(self):
-        """Debug, prioritised replay: {"idx" int64, "td" float32, "weight" float32}, [batch] each, of the most recent sampling step and pass."""
-        torch, B = self.torch, self.cfg.batch
-        idx = torch.zeros(B, dtype=torch.int64, device=self.device)
-        td, w = (torch.zeros(B, dtype=torch.float32, device=self.device) for _ in range(2))
-        self.ctx.dqn_per_last(self.handle, idx.data_ptr(), td.data_ptr(), w.data_ptr(), self._stream())
-        return {"idx": idx.cpu().numpy(), "td": td.cpu().numpy(), "weight": w.cpu().numpy()}
-
-    def stats_device(self):
-        """fp64 [4] device tensor: loss and mean Q(s, a) of the last minibatch, fill, updates done (asynchronous)."""
-        self.ctx.dqn_stats(self.handle, self._stats.data_ptr(), self._stream())
-        return self._stats
-
     def stats(self):
+        """``stats_device`` as a dict; synchronises."""
         s = self.stats_device().cpu().numpy()
         return {"loss": float(s[0]), "mean_q": float(s[1]), "fill": int(s[2]), "updates": int(s[3])}
 
-    # -- state ------------------------------------------------------------------------------------------------------------------------------
-    def state_dict(self):
-        """{"params": the four slots as dicts of numpy tensors + beta_pow + updates, "counters": int64 [8]}; the replay ring is not part of it."""
-        c = self.cfg
-        cn, bp = self.ctx.dqn_get_state(self.handle)
-        params = {slot: unflatten_q(self.ctx.dqn_get_params(self.handle, i, self._len), c.n_obs, c.h1, c.n_actions) for i, slot in enumerate(_capi.DQN_SLOTS)}
-        params["beta_pow"], params["updates"] = bp, int(cn[2])
-        return {"params": params, "counters": cn}
-
-    def load_state_dict(self, sd):
-        """The inverse; ``counters`` None: only the update count and Adam's beta powers are set (the replay's cursor and fill stay)."""
-        p = sd["params"]
-        for i, slot in enumerate(_capi.DQN_SLOTS):
-            self.ctx.dqn_set_params(self.handle, i, flatten_q(p[slot]))
-        cn = sd.get("counters")
-        if cn is None:
-            cn, _ = self.ctx.dqn_get_state(self.handle)
-            cn[2] = int(p["updates"])
-        self.ctx.dqn_set_state(self.handle, cn, p["beta_pow"])
-
     def export_q(self, path):
         """Write the online Q-network as an ``.npz``: w0, b0, w1, b1 (float32) and ``action_values`` (the env's table, index -> jerk or acceleration)."""
-        c = self.cfg
-        net = unflatten_q(self.ctx.dqn_get_params(self.handle, 0, self._len), c.n_obs, c.h1, c.n_actions)
         with open(path, "wb") as fh:
-            np.savez_compressed(fh, **net, action_values=self.action_values)
+            np.savez_compressed(fh, **self._slot(0), action_values=self.action_values)
         return path
 
 

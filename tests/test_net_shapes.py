@@ -194,7 +194,7 @@ def test_gpu_fused_actor_kernel_on_exact_weights(shape, gpu_ctx, restore_setting
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", SMALL)
 def test_gpu_parameters_round_trip(shape, gpu_ctx, restore_settings):
-    """load_state_dict -> state_dict over all eight slots with values that are all different: ddpg_pad's and the slot layout's index arithmetic,
+    """load_state_dict -> state_dict over all eight slots with values that are all different: slot_move's and the slot layout's index arithmetic,
     n_obs = 1 and n_obs = 30 (the full 32-wide critic input) included.  Also: the re-packing the upload triggers leaves the parameters alone."""
     from rl_mpc_lanemerging_amd import learner
     n_obs, h1, h2 = SHAPES[shape]
@@ -213,6 +213,50 @@ def test_gpu_parameters_round_trip(shape, gpu_ctx, restore_settings):
     sd = L.state_dict()
     _assert_params_equal(sd["params"], params)
     assert np.array_equal(sd["params"]["beta_pow"], params["beta_pow"]) and sd["params"]["updates"] == 2 and sd["counters"][2] == 2
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["ddpg", "td3-critic2", "dqn"])
+def test_gpu_slot_layout_round_trip_off_the_tile(kind, gpu_ctx, restore_settings):
+    """set_params -> get_params of every slot of every handle kind at widths that are no multiples of 16 (h1 = 20, h2 = 24, 3 actions), with values
+    that are all different within a slot and between slots: the library's segment list against the C-ABI's slot layout.  TD3: critic 2's four
+    slots, which leave critic 1's alone.  DQN: also through padded_read -- the real entries are the slot's, the pad entries exact zeros."""
+    from rl_mpc_lanemerging_amd import learner
+    n_obs, h1, h2, A = 5, 20, 24, 3
+    rng = np.random.default_rng(9)
+    distinct = lambda n, i: (rng.permutation(np.arange(1, n + 1)) + 1000 * i).astype(np.float32) / np.float32(8.0)
+    kw = dict(n_obs=n_obs, h1=h1, batch=16, capacity=64, replay_start=0)
+    len_ddpg = lambda n_in: (n_in + 1) * h1 + (h1 + 2) * h2 + 1
+    if kind == "dqn":
+        L = learner.DQNLearner((n_obs, A), learner.DQNConfig(n_actions=A, **kw), seed=1, ctx=gpu_ctx)
+        n = (n_obs + 1) * h1 + (h1 + 1) * A
+        slots = [(i, n) for i in range(4)]
+        put, get = (lambda i, flat: gpu_ctx.dqn_set_params(L.handle, i, flat)), (lambda i, n: gpu_ctx.dqn_get_params(L.handle, i, n))
+    elif kind == "ddpg":
+        L = learner.DDPGLearner(n_obs, learner.DDPGConfig(h2=h2, **kw), seed=1, ctx=gpu_ctx)
+        slots = [(i, len_ddpg(n_obs + (2 if i >= 4 else 1))) for i in range(8)]
+        put, get = (lambda i, flat: gpu_ctx.ddpg_set_params(L.handle, i, flat)), (lambda i, n: gpu_ctx.ddpg_get_params(L.handle, i, n))
+    else:
+        L = learner.TD3Learner(n_obs, learner.TD3Config(h2=h2, **kw), seed=1, ctx=gpu_ctx)
+        slots = [(i, len_ddpg(n_obs + 2)) for i in range(4)]
+        put, get = (lambda i, flat: gpu_ctx.td3_set_params(L.td3, i, flat)), (lambda i, n: gpu_ctx.td3_get_params(L.td3, i, n))
+        critic1 = [gpu_ctx.ddpg_get_params(L.handle, 4 + i, n) for i, n in slots]
+    want = [distinct(n, i) for i, n in slots]
+    for (i, _), flat in zip(slots, want):
+        put(i, flat)
+    for (i, n), flat in zip(slots, want):                           # (after all were set: no slot's upload or re-packing reaches another)
+        assert np.array_equal(get(i, n).view(np.uint32), flat.view(np.uint32)), (kind, i)
+    if kind == "td3-critic2":
+        assert all(np.array_equal(gpu_ctx.ddpg_get_params(L.handle, 4 + i, n), critic1[i]) for i, n in slots)
+    if kind == "dqn":
+        real = {"w0": (slice(0, h1), slice(0, n_obs)), "b0": (slice(0, h1),), "w1": (slice(0, A), slice(0, h1)), "b1": (slice(0, A),)}
+        for (i, _), flat in zip(slots, want):
+            arr, net = gpu_ctx.dqn_padded_read(L.handle, i, h1, A), learner.unflatten_q(flat, n_obs, h1, A)
+            for k, sl in real.items():
+                pad = np.ones(arr[k].shape, bool)
+                pad[sl] = False
+                assert np.array_equal(arr[k][sl], net[k]) and not arr[k][pad].any(), (i, k)
     gpu_ctx.check_error()
 
 
