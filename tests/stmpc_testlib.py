@@ -1,8 +1,11 @@
-"""Helpers the suite's modules share (plain functions: no fixtures, no hooks).  Import what a module needs, e.g.
-``from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same``."""
+"""Helpers the suite's modules share (plain functions: no fixtures, no hooks, nothing heavy at import time).  Import what a module needs, e.g.
+``from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same``.  What only the learner tests share is in learner_testlib.py; no test
+module imports another (test_testlib_cpu.py)."""
 import contextlib
+import json
 import math
 import os
+import re
 import shutil
 import struct
 import subprocess
@@ -18,6 +21,13 @@ def pkg():
     if pkg.build.needs_build():
         pkg.build.build()
     return pkg
+
+
+def capi():
+    """The binding (rl_mpc_lanemerging_amd._capi), with its library built if it is not."""
+    pkg()
+    from rl_mpc_lanemerging_amd import _capi
+    return _capi
 
 
 def bits(a):
@@ -93,3 +103,141 @@ def fastdiv_proven(dt):
     def fastdiv_ok(d):
         return 1e-100 < d < 1e100 and struct.unpack("<Q", struct.pack("<d", d))[0] & 0xFFFFFFFFFFFFF != 0xFFFFFFFFFFFFF
     return all(fastdiv_ok(d) and _capi.fastdiv2_check(d)[0] for d in (dt, dt * dt, math.pow(dt, 3.0)))
+
+
+def record_json(path, key, value):
+    """Merge one entry into the JSON file ``path`` (evidence under profiles/; the assertions are in the tests)."""
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    data = json.load(open(path)) if os.path.exists(path) else {}
+    data[key] = value
+    with open(path, "w") as fh:
+        json.dump(data, fh, indent=1, sort_keys=True)
+
+
+# ---- include/stmpc.h ---------------------------------------------------------------------------------------------------------------------------
+def header_text(flat=False):
+    """include/stmpc.h; ``flat``: with every run of white space made one blank."""
+    header = open(os.path.join(REPO, "include", "stmpc.h")).read()
+    return " ".join(header.split()) if flat else header
+
+
+def header_entries(prefix):
+    """The names ``prefix``... that the header follows with an opening parenthesis (its functions; a struct named in a cast would count too)."""
+    return {n for n in re.findall(r"\b(stmpc_[a-z_0-9]+)\s*\(", header_text()) if n.startswith(prefix)}
+
+
+def header_prototypes(prefix):
+    """name -> argument list (as text) of the prototypes ``prefix``...(...); of the header.  Stricter than ``header_entries``: only what ends
+    in ");" counts, which is why both exist."""
+    return {name: args for name, args in re.findall(r"\b(%s[a-z_0-9]+)\s*\(([^)]*)\)\s*;" % re.escape(prefix), header_text(flat=True))}
+
+
+def header_struct_fields(name):
+    """Field names and C types of `typedef struct <name> { ... } <name>;` in include/stmpc.h, in order (comments stripped)."""
+    header = header_text()
+    body = header[header.index("typedef struct %s {" % name) + len("typedef struct %s {" % name):header.index("} %s;" % name)]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    out = []
+    for stmt in body.split(";"):
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        if stmt.startswith("const "):
+            stmt = stmt[6:]
+        ctype, rest = stmt.split(" ", 1)
+        for n in rest.split(","):
+            n = n.strip()
+            out.append((n.lstrip("*"), ctype + " *" if n.startswith("*") else ctype))
+    return out
+
+
+# ---- the solver and the combined controller against their goldens ----------------------------------------------------------------------------------
+def check_solve(res, ref, H):
+    """A solve's integer outputs, cost and path distances equal the reference's, bit for bit (NaNs at the same places)."""
+    assert np.array_equal(res["best_t"], ref["best_t"])
+    assert np.array_equal(res["path_idx"], ref["path_idx"])
+    assert np.array_equal(res["cost"], ref["cost"])
+    assert np.array_equal(res["crash"], ref["crash"])
+    assert np.array_equal(np.isnan(res["path_dist"]), np.isnan(ref["path_dist"]))
+    m = ~np.isnan(ref["path_dist"])
+    assert np.array_equal(res["path_dist"][m], ref["path_dist"][m])
+
+
+def apply_settings(g):
+    """The Settings a combined-controller golden ``g`` was generated with; returns the package."""
+    import rl_mpc_lanemerging_amd as pkg
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    for key, val in zip(g["setting_keys"], g["setting_vals"]):
+        setattr(pkg.Settings, str(key), int(val) if str(key) in ("ROLLOUT_LENGTH", "ST_TEST_ROLLOUTS", "STOP_X") else float(val))
+    pkg.Settings.CHECK_ROLLOUT_CRASH, pkg.Settings.LIMIT_DQN_SPEED, pkg.Settings.TEST_ROLLOUT_STATE, \
+        pkg.Settings.TEST_ST_STRICTLY_BETTER = [bool(x) for x in g["flags"]]
+    return pkg
+
+
+# ---- actor populations (test_actor_pop.py; the learner tests evaluate views of their learners' actors through the same steps) ------------------
+ACTOR_P, ACTOR_N_PER, ACTOR_KMAX = 3, 24, 16
+ACTOR_N = ACTOR_P * ACTOR_N_PER
+
+
+def actor_settings():
+    from conftest import load_golden
+    g = load_golden("golden_combined_real.npz")
+    return g, apply_settings(g).Settings
+
+
+def actor_states(g, dev, same=False):
+    """72 states of the golden, vehicle slots padded from 8 to Kmax = 16: per member 18 of its first states and, spread over both tiles of the
+    member's slice, 6 whose rollout the reference ended after the first step (so that step 2 meets rows that are no longer live).
+    ``same``: member 0's 24 states, three times."""
+    import torch
+    P, N_PER, N, KMAX = ACTOR_P, ACTOR_N_PER, ACTOR_N, ACTOR_KMAX
+    short = np.nonzero(g["n_evals"] == 1)[0]
+    assert len(short) >= 6 * P
+    rows = np.arange(N)
+    for m in range(P):
+        rows[m * N_PER + np.array([3, 9, 15, 16, 20, 23])] = short[6 * m:6 * m + 6]
+    if same:
+        rows = np.tile(rows[:N_PER], P)
+    pad = lambda a: np.concatenate([a[rows], np.zeros((N, KMAX - a.shape[1]))], axis=1)
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    return {"ego5": t(g["ego"][rows]), "ego4": t(g["ego"][rows][:, :4]), "k": t(g["k_count"][rows]), "ox": t(pad(g["other_x"])), "ov": t(pad(g["other_v"])),
+            "oa": t(pad(g["other_a"])), "evals0": t(g["evals0"][rows])}
+
+
+def actor_two_steps(ctx, S, policy, st, rows):
+    """Evaluate ``policy`` on ``rows`` of the states at step 1, roll those rows out one step with its jerks, evaluate at step 2 (only the rows whose
+    rollout goes on are evaluated then).  Returns the policy's jerk, input vectors and counters after each step, as numpy."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi
+    params, ccfg = _capi.Params.from_settings(S), _capi.CombinedCfg.from_settings(S)
+    cur = {k: st[k][rows].clone().contiguous() for k in ("ego4", "ox", "ov", "oa")}
+    ego5, k = st["ego5"][rows].contiguous(), st["k"][rows].contiguous()
+    n = ego5.shape[0]
+    policy.keep_features = True
+    policy.evals.copy_(st["evals0"][rows])
+    policy.feat.fill_(-7.0)
+    policy.jerk.fill_(-7.0)
+    out = []
+    for step in (1, 2):
+        jerk = policy(step, cur["ego4"], k, cur["ox"], cur["ov"], cur["oa"])
+        torch.cuda.synchronize()
+        out.append({"jerk": jerk.cpu().numpy().copy(), "feat": policy.feat.cpu().numpy().copy(), "evals": policy.evals.cpu().numpy().copy()})
+        if step == 1:
+            ctx.rollout_step_device(params, ccfg, n, ACTOR_KMAX, 1, ego5.data_ptr(), cur["ego4"].data_ptr(), k.data_ptr(), cur["ox"].data_ptr(), cur["ov"].data_ptr(),
+                                    cur["oa"].data_ptr(), jerk.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    ctx.check_error()
+    return out
+
+
+def actor_eval(ctx, S, policy, st):
+    return actor_two_steps(ctx, S, policy, st, slice(0, ACTOR_N_PER))
+
+
+def assert_steps_equal(got, want, label):
+    for step, (a, b) in enumerate(zip(got, want), 1):
+        for key in ("jerk", "feat", "evals"):
+            assert same(a[key], b[key]), (label, "step", step, key)
+
+
+def slice_steps(steps, sl):
+    return [{k: v[sl] for k, v in s.items()} for s in steps]

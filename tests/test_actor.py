@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from test_combined import _apply_settings
+from stmpc_testlib import apply_settings as _apply_settings
 
 ACC_SLOTS = [0, 4, 8, 12]          # the other vehicles' accelerations in the 21-vector (dqn.py:399-400)
 

@@ -8,46 +8,24 @@ masked tail, and a tile that wrongly spanned two members would mix weights at ro
 on its slice, a view equals the actor loaded from the learner's export, a run under a population equals the runs of its members -- all bit for
 bit: the population runs the lone actor's own arithmetic, so no tolerance appears anywhere.
 """
-import os
-import re
-
 import numpy as np
 import pytest
 
-from conftest import REPO, load_golden
-from test_combined import _apply_settings
+from stmpc_testlib import (ACTOR_KMAX as KMAX, ACTOR_N as N, ACTOR_N_PER as N_PER, ACTOR_P as P, actor_eval as _eval, actor_settings as _settings, actor_states as _states,
+                           actor_two_steps as _two_steps, assert_steps_equal as _assert_steps_equal, capi as _capi, header_prototypes, header_text,
+                           same as _same_bits, slice_steps as _slice_steps)
 
 NAMES = ("low1", "medium1", "fast1")
-P, N_PER, KMAX = 3, 24, 16
-N = P * N_PER
 NEW = ("stmpc_actor_view_ddpg", "stmpc_actor_pop_create", "stmpc_actor_pop_destroy", "stmpc_actor_pop_size", "stmpc_actor_pop_eval_device")
 _cache = {}
-
-
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def _same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_agree_on_the_new_entries():
     capi = _capi()
     lib = capi.load()
-    header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
-    declared = {name: args for name, args in re.findall(r"\b(stmpc_actor_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}
+    header = header_text(flat=True)
+    declared = header_prototypes("stmpc_actor_")
     assert set(declared) == {"stmpc_actor_create", "stmpc_actor_destroy", "stmpc_actor_eval_device"} | set(NEW)
     assert set(NEW) <= set(capi.EXPORTS)
     for name in NEW:
@@ -182,65 +160,6 @@ def test_reduce_rows_host_has_the_recorders_order():
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------------------------
-def _settings():
-    g = load_golden("golden_combined_real.npz")
-    pkg = _apply_settings(g)
-    return g, pkg.Settings
-
-
-def _states(g, dev, same=False):
-    """72 states of the golden, vehicle slots padded from 8 to Kmax = 16: per member 18 of its first states and, spread over both tiles of the
-    member's slice, 6 whose rollout the reference ended after the first step (so that step 2 meets rows that are no longer live).
-    ``same``: member 0's 24 states, three times."""
-    import torch
-    short = np.nonzero(g["n_evals"] == 1)[0]
-    assert len(short) >= 6 * P
-    rows = np.arange(N)
-    for m in range(P):
-        rows[m * N_PER + np.array([3, 9, 15, 16, 20, 23])] = short[6 * m:6 * m + 6]
-    if same:
-        rows = np.tile(rows[:N_PER], P)
-    pad = lambda a: np.concatenate([a[rows], np.zeros((N, KMAX - a.shape[1]))], axis=1)
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    return {"ego5": t(g["ego"][rows]), "ego4": t(g["ego"][rows][:, :4]), "k": t(g["k_count"][rows]), "ox": t(pad(g["other_x"])), "ov": t(pad(g["other_v"])),
-            "oa": t(pad(g["other_a"])), "evals0": t(g["evals0"][rows])}
-
-
-def _two_steps(ctx, S, policy, st, rows):
-    """Evaluate ``policy`` on ``rows`` of the states at step 1, roll those rows out one step with its jerks, evaluate at step 2 (only the rows whose
-    rollout goes on are evaluated then).  Returns the policy's jerk, input vectors and counters after each step, as numpy."""
-    import torch
-    from rl_mpc_lanemerging_amd import _capi as capi
-    params, ccfg = capi.Params.from_settings(S), capi.CombinedCfg.from_settings(S)
-    cur = {k: st[k][rows].clone().contiguous() for k in ("ego4", "ox", "ov", "oa")}
-    ego5, k = st["ego5"][rows].contiguous(), st["k"][rows].contiguous()
-    n = ego5.shape[0]
-    policy.keep_features = True
-    policy.evals.copy_(st["evals0"][rows])
-    policy.feat.fill_(-7.0)
-    policy.jerk.fill_(-7.0)
-    out = []
-    for step in (1, 2):
-        jerk = policy(step, cur["ego4"], k, cur["ox"], cur["ov"], cur["oa"])
-        torch.cuda.synchronize()
-        out.append({"jerk": jerk.cpu().numpy().copy(), "feat": policy.feat.cpu().numpy().copy(), "evals": policy.evals.cpu().numpy().copy()})
-        if step == 1:
-            ctx.rollout_step_device(params, ccfg, n, KMAX, 1, ego5.data_ptr(), cur["ego4"].data_ptr(), k.data_ptr(), cur["ox"].data_ptr(), cur["ov"].data_ptr(),
-                                    cur["oa"].data_ptr(), jerk.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    ctx.check_error()
-    return out
-
-
-def _assert_steps_equal(got, want, label):
-    for step, (a, b) in enumerate(zip(got, want), 1):
-        for key in ("jerk", "feat", "evals"):
-            assert _same_bits(a[key], b[key]), (label, "step", step, key)
-
-
-def _slice_steps(steps, sl):
-    return [{k: v[sl] for k, v in s.items()} for s in steps]
-
-
 @pytest.mark.gpu
 def test_gpu_members_are_lone_actors(gpu_ctx, restore_settings):
     import torch
@@ -285,10 +204,6 @@ def _nonzero_last_layers(L, seed):
         sd["params"][slot]["w2"] = r.normal(0, 0.05, (1, L.cfg.h2)).astype(np.float32)
         sd["params"][slot]["b2"] = r.normal(0, 0.05, 1).astype(np.float32)
     L.load_state_dict({"params": sd["params"], "counters": None})
-
-
-def _eval(ctx, S, policy, st):
-    return _two_steps(ctx, S, policy, st, slice(0, N_PER))
 
 
 @pytest.mark.gpu

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from stmpc_testlib import apply_settings as _apply_settings
 
 
 def stub_policy(state):
@@ -15,16 +16,6 @@ def stub_policy(state):
             gap = d
     j = 0.4 * (18.0 - state.ego_speed) - 0.8 * state.ego_acceleration - 25.0 / (gap + 5.0) + 1.0
     return max(-5.0, min(5.0, j))
-
-
-def _apply_settings(g):
-    import rl_mpc_lanemerging_amd as pkg
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    for key, val in zip(g["setting_keys"], g["setting_vals"]):
-        setattr(pkg.Settings, str(key), int(val) if str(key) in ("ROLLOUT_LENGTH", "ST_TEST_ROLLOUTS", "STOP_X") else float(val))
-    pkg.Settings.CHECK_ROLLOUT_CRASH, pkg.Settings.LIMIT_DQN_SPEED, pkg.Settings.TEST_ROLLOUT_STATE, \
-        pkg.Settings.TEST_ST_STRICTLY_BETTER = [bool(x) for x in g["flags"]]
-    return pkg
 
 
 class _S:      # minimal state for the stand-in policy on oracle structs

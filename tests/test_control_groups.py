@@ -18,8 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from test_combined import _apply_settings
-from stmpc_testlib import bits as _bits, same as _same
+from stmpc_testlib import apply_settings as _apply_settings, bits as _bits, same as _same
 
 NPG, KMAX = 24, 16
 IDX = [90, 128, 131, 165, 241, 101, 108, 144, 187, 202, 123, 167, 291, 297, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9]

@@ -3,7 +3,7 @@ vec_env.CombinedShieldVecEnv): the fused step equals the composition of the pinn
 
 Shape unless stated: n = 100 (a full 64-thread workgroup and a partial one; six full actor tiles of 16 rows and one of 4), "sumo-jerk-continuous-v0",
 the "default" traffic, shield_kmax = 16, world seed 7, the pretrained ddpg_medium1 actor, actions a fixed hash of (environment, episode tick) in the
-Box.  Every run is recorded once (``_record``) and shared by the tests that need it."""
+Box.  Every run is recorded once (``_recorded_run``) and shared by the tests that need it."""
 import numpy as np
 import pytest
 
@@ -47,7 +47,7 @@ def _env(ctx, policy=None, **kw):
     return vec_env.CombinedShieldVecEnv(N, policy, seed=SEED, reward="Continuous", ctx=ctx, **kw)
 
 
-def _record(ticks=TICKS, cell="default", rollout_time="env", sparse=False, autoreset=True, penalty=0.0, shield=True, actions=None):
+def _recorded_run(ticks=TICKS, cell="default", rollout_time="env", sparse=False, autoreset=True, penalty=0.0, shield=True, actions=None):
     """One run of the env on a context of its own: the actions, every output of every tick, the world after every tick, the counter before it, the
     drained log and the combined controller's counts.  Cached: a reference is computed once and never changed."""
     key = (ticks, cell, rollout_time, sparse, autoreset, penalty, shield, None if actions is None else hash(np.ascontiguousarray(actions).tobytes()))
@@ -270,7 +270,7 @@ def test_gpu_step_is_the_composition_bit_for_bit(cell, rollout_time, restore_set
     live rows, reasons, episodes 0 ended / on a takeover tick, autoresets, row-ticks past episode 0): default cell "env" 18576 / 1424, {1, 3}, 73 / 11, 75,
     3516; default "deployed" 18582 / 1418, {1, 3}, 75 / 12, 76, 3434; L3T2 "env" 18209 / 1791, {1, 3}, 74 / 20, 74, 3626; L3T2 "deployed" 18152 / 1848,
     {1, 3}, 75 / 16, 75, 3811."""
-    rec = _record(cell=cell, rollout_time=rollout_time)
+    rec = _recorded_run(cell=cell, rollout_time=rollout_time)
     seen = _compose(rec, cell, rollout_time)
     print("cshield env composition:", cell, rollout_time, {k: v for k, v in seen.items() if k != "rolled"}, "counts", rec["counts"])
     assert rec["shield_name"] == "combined" and rec["info_keys"] >= set(SHIELD_KEYS)
@@ -282,8 +282,8 @@ def test_gpu_step_is_the_composition_bit_for_bit(cell, rollout_time, restore_set
 
 @pytest.mark.gpu
 def test_gpu_sparse_equals_dense(restore_settings):
-    dense = _record()
-    sparse = _record(ticks=60, sparse=True, actions=dense["action"][:60])
+    dense = _recorded_run()
+    sparse = _recorded_run(ticks=60, sparse=True, actions=dense["action"][:60])
     for k in KEYS + WORLD:
         assert _same(sparse[k], dense[k][:60]), k
     decisions, solves = sparse["counts"]
@@ -331,8 +331,8 @@ def test_gpu_env_follows_the_combined_runner(restore_settings):
 
 @pytest.mark.gpu
 def test_gpu_up_to_the_first_takeover_it_is_todays_env(restore_settings):
-    shielded = _record(ticks=60, autoreset=False)
-    plain = _record(ticks=60, autoreset=False, shield=False, actions=shielded["action"])
+    shielded = _recorded_run(ticks=60, autoreset=False)
+    plain = _recorded_run(ticks=60, autoreset=False, shield=False, actions=shielded["action"])
     assert not plain["info_keys"] & set(SHIELD_KEYS)
     taken_before = np.cumsum(shielded["takeover"], axis=0) - shielded["takeover"] > 0          # [t][e]: a takeover on an earlier tick
     clean = ~(taken_before | shielded["takeover"])                                              # the non-takeover ticks up to the row's first takeover

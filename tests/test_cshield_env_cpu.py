@@ -8,21 +8,13 @@ import re
 import pytest
 
 from conftest import REPO
+from stmpc_testlib import capi as _capi, header_struct_fields as _header_struct_fields
 
 ENTRIES = {"stmpc_cshield_env_reset_device": 10, "stmpc_cshield_env_step_device": 21, "stmpc_cshield_env_evals_device": 4}
 
 
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
-
-
 def test_header_declares_the_struct_and_the_entries():
     capi = _capi()
-    from test_host_cpu import _header_struct_fields
     header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
     declared = {name: args for name, args in re.findall(r"\bint (stmpc_cshield_env_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}
     assert set(declared) == set(ENTRIES) <= set(capi.EXPORTS)

@@ -2,7 +2,7 @@
 (20, 16, 5, 7), (20, 48, 20, 33), (20, 256, 5, 50), (12, 32, 17, 16): one and two output tiles, an A that crosses a tile with padding, a B that is
 no multiple of 16 and one that is, the reference's own shape.  Rings have at most 256 rows, envs at most 64 environments.
 
-Parity rule for float32 results (tests/test_learner.py's): per tensor, max-norm error against ``update_host_dqn("float64")`` at most
+Parity rule for float32 results (tests/learner_testlib.py's): per tensor, max-norm error against ``update_host_dqn("float64")`` at most
 max(4 x the error of ``update_host_dqn("float32")``, 8 float32 ulps).
 
 Exactness on dyadic data: the targets, a*, Q(s, a) and the pads are exact at every shape.  A gradient carries the factor 1 / B: for B = 16 the
@@ -15,31 +15,13 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from learner_testlib import bits_equal, check_4x as _check_4x
+from stmpc_testlib import capi as _capi
 
-FLOOR = 8 * 2.0 ** -23
 SHAPES = [(20, 16, 5, 7), (20, 48, 20, 33), (20, 256, 5, 50), (12, 32, 17, 16)]
 NAMES = ("w0", "b0", "w1", "b1")
+Q_SLOTS = ("q", "q_target", "q_m", "q_v")
 RING = 128
-
-
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
-
-
-def _rel_err(x, ref):
-    scale = np.abs(ref).max()
-    return float(np.abs(np.asarray(x, dtype=np.float64) - ref).max() / scale) if scale > 0 else float(np.abs(x).max())
-
-
-def _check_4x(label, dev, f32, f64):
-    e_dev, e_32 = _rel_err(dev, f64), _rel_err(f32, f64)
-    bound = max(4 * e_32, FLOOR)
-    print("%-36s device %.3e  float32 twin %.3e  bound %.3e" % (label, e_dev, e_32, bound))
-    return e_dev <= bound
 
 
 def _fill(L, replay):
@@ -363,10 +345,6 @@ def _random_problem(shape, seed, **kw):
     return cfg, params, replay
 
 
-def _bits_equal(a, b):
-    return all(np.array_equal(a[s][k].view(np.uint32), b[s][k].view(np.uint32)) for s in ("q", "q_target", "q_m", "q_v") for k in NAMES)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[3]])
 def test_gpu_target_schedule_and_gate(shape, gpu_ctx, restore_settings):
@@ -379,7 +357,7 @@ def test_gpu_target_schedule_and_gate(shape, gpu_ctx, restore_settings):
     _fill(L, {k: v[:64] for k, v in replay.items()})                # 64 frames: not MORE than replay_start
     L.update(2)
     sd = L.state_dict()
-    assert _bits_equal(sd["params"], params) and sd["params"]["updates"] == 0 and sd["counters"][1] == 64
+    assert bits_equal(sd["params"], params, Q_SLOTS, NAMES) and sd["params"]["updates"] == 0 and sd["counters"][1] == 64
     _fill(L, {k: v[64:] for k, v in replay.items()})
     for u in range(7):
         before = L.state_dict()["params"]
@@ -410,14 +388,14 @@ def test_gpu_updates_are_reproducible(per, gpu_ctx, restore_settings):
     mid = B_.state_dict()
     B_.update(6)
     sa, sb = A_.state_dict(), B_.state_dict()
-    assert _bits_equal(sa["params"], sb["params"]) and np.array_equal(sa["counters"], sb["counters"]) and np.array_equal(sa["params"]["beta_pow"], sb["params"]["beta_pow"])
+    assert bits_equal(sa["params"], sb["params"], Q_SLOTS, NAMES) and np.array_equal(sa["counters"], sb["counters"]) and np.array_equal(sa["params"]["beta_pow"], sb["params"]["beta_pow"])
     assert A_.stats() == B_.stats() and sa["params"]["updates"] == 10
     if not per:                                                     # (a tree is not part of a state_dict: a fresh learner's would be the pushes')
         C_ = _learner(gpu_ctx, cfg, params, replay)
         C_.load_state_dict(mid)
         C_.update(6)
         sc = C_.state_dict()
-        assert _bits_equal(sa["params"], sc["params"]) and np.array_equal(sa["counters"], sc["counters"]) and C_.stats() == A_.stats()
+        assert bits_equal(sa["params"], sc["params"], Q_SLOTS, NAMES) and np.array_equal(sa["counters"], sc["counters"]) and C_.stats() == A_.stats()
     gpu_ctx.check_error()
 
 
@@ -465,7 +443,7 @@ def test_gpu_prioritised_replay(gpu_ctx, restore_settings):
     # a learner without per draws the uniform rows, and differs
     assert np.array_equal(U.minibatch().view(np.uint32), _minibatch_host(replay, cfg0)[0].view(np.uint32))
     U.update(3)
-    assert not _bits_equal(U.state_dict()["params"], L.state_dict()["params"])
+    assert not bits_equal(U.state_dict()["params"], L.state_dict()["params"], Q_SLOTS, NAMES)
     # pushes after updates: the new rows' leaves, the rest untouched
     _fill(L, {k: v[:64] for k, v in replay.items()})
     host.cursor = 0
@@ -502,7 +480,7 @@ def test_gpu_train_dqn(env_id, A, gpu_ctx, restore_settings, tmp_path):
     assert not np.array_equal(sd["params"]["q"]["w1"], first["q"]["w1"]) and not np.array_equal(sd["params"]["q"]["b1"], first["q"]["b1"])
     L2, _, res2 = run()
     sd2 = L2.state_dict()
-    assert _bits_equal(sd["params"], sd2["params"]) and np.array_equal(sd["counters"], sd2["counters"]) and np.array_equal(res["returns"], res2["returns"])
+    assert bits_equal(sd["params"], sd2["params"], Q_SLOTS, NAMES) and np.array_equal(sd["counters"], sd2["counters"]) and np.array_equal(res["returns"], res2["returns"])
     path = L.export_q(str(tmp_path / "q.npz"))
     with np.load(path) as z:
         assert all(np.array_equal(z[k], sd["params"]["q"][k]) for k in NAMES) and np.array_equal(z["action_values"], L.action_values) and z["action_values"].size == A

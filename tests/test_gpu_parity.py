@@ -7,20 +7,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, settings_from_golden
+from stmpc_testlib import check_solve as _check
 
 pytestmark = pytest.mark.gpu
 
 STATE_FILES = ["golden_default.npz", "golden_uncertainty.npz", "golden_h40a21.npz", "golden_h40a21_unc.npz"]
-
-
-def _check(res, ref, H):
-    assert np.array_equal(res["best_t"], ref["best_t"])
-    assert np.array_equal(res["path_idx"], ref["path_idx"])
-    assert np.array_equal(res["cost"], ref["cost"])
-    assert np.array_equal(res["crash"], ref["crash"])
-    assert np.array_equal(np.isnan(res["path_dist"]), np.isnan(ref["path_dist"]))
-    m = ~np.isnan(ref["path_dist"])
-    assert np.array_equal(res["path_dist"][m], ref["path_dist"][m])
 
 
 def test_device_arithmetic_is_ieee(gpu_ctx):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO, load_golden
+from stmpc_testlib import header_struct_fields as _header_struct_fields
 
 
 def _lib():
@@ -40,26 +41,6 @@ def test_params_struct_layout_matches_header():
             names += [n.strip() for n in line[len("double"):].rstrip(";").split(",")]
     assert names == [n for n, _ in capi.Params._fields_]
     assert ctypes.sizeof(capi.Params) == 8 * len(names)
-
-
-def _header_struct_fields(name):
-    """Field names and C types of `typedef struct <name> { ... } <name>;` in include/stmpc.h, in order (comments stripped)."""
-    import re
-    header = open(os.path.join(REPO, "include", "stmpc.h")).read()
-    body = header[header.index("typedef struct %s {" % name) + len("typedef struct %s {" % name):header.index("} %s;" % name)]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    out = []
-    for stmt in body.split(";"):
-        stmt = " ".join(stmt.split())
-        if not stmt:
-            continue
-        if stmt.startswith("const "):
-            stmt = stmt[6:]
-        ctype, rest = stmt.split(" ", 1)
-        for n in rest.split(","):
-            n = n.strip()
-            out.append((n.lstrip("*"), ctype + " *" if n.startswith("*") else ctype))
-    return out
 
 
 def test_every_other_struct_layout_matches_header():

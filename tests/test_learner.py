@@ -4,29 +4,19 @@ CPU: header / library / binding agree; the generator's Python twins equal the C 
 restatement; ``export_actor`` round-trips.  GPU: replay ring, gradients, Adam + Polyak, padded rows, ten updates, reproducibility, a critic
 regression, acting, the training loop and graph capture -- all through the C-ABI.
 
-The parity rule of the floating-point GPU tests: error = max-abs difference to ``update_host`` in float64 divided by the float64 tensor's max-abs;
+The parity rule of the floating-point GPU tests (learner_testlib.check_4x, its one definition): error = max-abs difference to ``update_host`` in float64 divided by the float64 tensor's max-abs;
 bound = 4 x the same error of ``update_host`` in float32 on the CPU, floor 8 float32 ulps.  The yardstick is the torch float32 twin, never the kernel;
 4 covers two float32 evaluations with different summation orders.  Measured ratios go to profiles/learner/parity.json.
 """
 import ctypes
-import json
 import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REPO
-
-FLOOR = 8 * 2.0 ** -23          # 8 float32 ulps, relative
-
-
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
+from conftest import GOLDEN
+from learner_testlib import bound_4x, capi_slots, check_4x as _check_4x, random_problem as _random_problem, record as _record
+from stmpc_testlib import capi as _capi, header_entries, header_struct_fields as _header_struct_fields, header_text
 
 
 def _critic_fixture():
@@ -34,23 +24,11 @@ def _critic_fixture():
         return {k: np.array(z[k]) for k in ("w0", "b0", "w1", "b1", "w2", "b2")}
 
 
-def _record(key, value):
-    """Merge one entry into profiles/learner/parity.json (evidence; the assertions are in the tests)."""
-    path = os.path.join(REPO, "profiles", "learner", "parity.json")
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    data = json.load(open(path)) if os.path.exists(path) else {}
-    data[key] = value
-    with open(path, "w") as fh:
-        json.dump(data, fh, indent=1, sort_keys=True)
-
-
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_agree_on_the_learner():
     capi = _capi()
-    from test_host_cpu import _header_struct_fields
     lib = capi.load()
-    header = open(os.path.join(REPO, "include", "stmpc.h")).read()
-    declared = {n for n in re.findall(r"\b(stmpc_[a-z_0-9]+)\s*\(", header) if n.startswith("stmpc_ddpg_")}
+    declared = header_entries("stmpc_ddpg_")
     assert declared >= {"stmpc_ddpg_create", "stmpc_ddpg_destroy", "stmpc_ddpg_set_params", "stmpc_ddpg_get_params", "stmpc_ddpg_push_device",
                         "stmpc_ddpg_act_device", "stmpc_ddpg_update_device", "stmpc_ddpg_stats_device", "stmpc_ddpg_grads_device",
                         "stmpc_ddpg_sample_index", "stmpc_ddpg_noise"}
@@ -62,7 +40,7 @@ def test_header_library_and_binding_agree_on_the_learner():
     have = list(capi.DDPGCfg._fields_)
     assert [n for n, _ in want] == [n for n, _ in have]
     assert [ctype_of[t] for _, t in want] == [t for _, t in have]
-    flat = " ".join(header.split())
+    flat = header_text(flat=True)
     for name, val in (("STMPC_DDPG_ROW", capi.DDPG_ROW), ("STMPC_DDPG_NCOUNTERS", capi.DDPG_NCOUNTERS), ("STMPC_ABI_VERSION", capi.ABI_VERSION),
                       ("STMPC_DDPG_CRITIC_V", len(capi.DDPG_SLOTS) - 1), ("STMPC_DDPG_CRITIC", capi.DDPG_SLOTS.index("critic"))):
         assert "#define %s %d" % (name, val) in flat, name
@@ -90,21 +68,6 @@ def test_generator_twins_equal_the_c_twins():
     assert not np.array_equal(idx, learner.sample_indices_host(4, 0, 4096, 64)) and not np.array_equal(idx, learner.sample_indices_host(3, 1, 4096, 64))
     g = np.concatenate([learner.noise_host(5, c, 512)[2] for c in range(8)])
     assert abs(g.mean()) < 0.06 and abs(g.std() - 1) < 0.05
-
-
-def _random_problem(rng, B=48, n_obs=20, h1=40, h2=24):
-    from rl_mpc_lanemerging_amd import learner
-    cfg = learner.DDPGConfig(n_obs=n_obs, h1=h1, h2=h2, batch=B, lr_q=1e-3, lr_pi=5e-4)
-    a_net, q_net = learner.init_net(n_obs + 1, h1, h2, rng), learner.init_net(n_obs + 2, h1, h2, rng)
-    a_net["w2"] = rng.normal(0, 0.1, a_net["w2"].shape).astype(np.float32)
-    q_net["w2"] = rng.normal(0, 0.1, q_net["w2"].shape).astype(np.float32)
-    params = learner.new_params(a_net, q_net)
-    for k in learner.TENSORS:                                     # targets that differ from the online nets
-        params["actor_target"][k] = params["actor_target"][k] + rng.normal(0, 0.01, params["actor_target"][k].shape).astype(np.float32)
-        params["critic_target"][k] = params["critic_target"][k] + rng.normal(0, 0.01, params["critic_target"][k].shape).astype(np.float32)
-    batch = {"s": rng.normal(0, 1, (B, n_obs + 1)), "a": rng.uniform(-5, 5, B), "r": rng.normal(0, 1, B), "s2": rng.normal(0, 1, (B, n_obs + 1)),
-             "mask": (rng.random(B) > 0.2).astype(np.float64)}
-    return cfg, params, batch
 
 
 def test_update_host_equals_an_independent_torch_adam_restatement():
@@ -172,20 +135,6 @@ def test_export_actor_round_trips(tmp_path):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------------------------
-def _rel_err(x, ref):
-    scale = np.abs(ref).max()
-    return float(np.abs(np.asarray(x, dtype=np.float64) - ref).max() / scale) if scale > 0 else float(np.abs(x).max())
-
-
-def _check_4x(label, dev, f32, f64, ratios):
-    """The parity rule of the module text for one tensor; prints and records before it asserts."""
-    e_dev, e_32 = _rel_err(dev, f64), _rel_err(f32, f64)
-    bound = max(4 * e_32, FLOOR)
-    ratios[label] = {"device": e_dev, "float32_twin": e_32, "ratio": e_dev / e_32 if e_32 > 0 else None}
-    print("%-40s device %.3e  float32 twin %.3e  bound %.3e" % (label, e_dev, e_32, bound))
-    return e_dev <= bound
-
-
 def _filled_learner(gpu_ctx, B, seed=3, n_env=256, steps=24, capacity=8192, learner_seed=None, **cfg_kw):
     """medium1 actor + the critic fixture + a replay filled from real MergeVecEnv steps (actions: the actor's with exploration noise)."""
     import torch
@@ -269,10 +218,6 @@ def test_gpu_gradients_against_the_float64_twin(B, gpu_ctx, restore_settings):
     assert ok, ratios
     after = L.state_dict()
     assert all(np.array_equal(after["params"][s][k], sd["params"][s][k]) for s in capi_slots() for k in learner.TENSORS) and after["params"]["updates"] == 0
-
-
-def capi_slots():
-    return _capi().DDPG_SLOTS
 
 
 @pytest.mark.gpu
@@ -396,7 +341,7 @@ def test_gpu_critic_regression(gpu_ctx, restore_settings):
     print("critic regression: loss %.6g -> %.6g; float64 twin %.6g, float32 twin %.6g; errors device %.3e, float32 twin %.3e" % (start, end, l64, l32, e_dev, e_32))
     _record("critic_regression", {"start": start, "device": end, "float64_twin": l64, "float32_twin": l32, "device_err": e_dev, "float32_twin_err": e_32})
     assert end < start
-    assert e_dev <= max(4 * e_32, FLOOR)
+    assert e_dev <= bound_4x(e_32)
 
 
 @pytest.mark.gpu

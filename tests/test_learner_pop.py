@@ -6,15 +6,12 @@ parameters, counters, beta powers, rings and statistics at the end); members do 
 training loop and the export of a member's actor.  Everything at the shipped 400/300 network shape.  No tolerance anywhere except the actor
 export's 5e-5 (test_actor.py's): the members run the single learner's own arithmetic.
 """
-import os
-import re
-
 import numpy as np
 import pytest
 
-from conftest import REPO
+from learner_testlib import CAP, N_PER, STEPS, assert_same as _assert_same, snapshot as _snapshot
+from stmpc_testlib import bits as _bits, capi as _capi, header_prototypes, header_text, linit as _init
 
-N_PER, CAP, STEPS = 24, 200, 12                # 24: an acting tile with masked tail rows; 200: every ring wraps within 9 pushes
 SEEDS = (11, 12, 13)
 GAMMA, TAU, NOISE = (0.99, 0.95, 0.9), (0.005, 0.01, 0.02), (0.1, 0.2, 0.05)
 LR_Q, LR_PI = (2e-4, 1e-3, 5e-4), (2e-4, 3e-4, 1e-4)
@@ -22,20 +19,12 @@ REPLAY_START = (0, 48, 120)                    # member 2 is still gated while m
 _cache = {}
 
 
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
-
-
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_agree_on_the_population():
     capi = _capi()
     lib = capi.load()
-    header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
-    declared = {name: args for name, args in re.findall(r"\b(stmpc_ddpg_pop_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}
+    header = header_text(flat=True)
+    declared = header_prototypes("stmpc_ddpg_pop_")
     assert set(declared) >= {"stmpc_ddpg_pop_create", "stmpc_ddpg_pop_destroy", "stmpc_ddpg_pop_member", "stmpc_ddpg_pop_act_device",
                              "stmpc_ddpg_pop_push_device", "stmpc_ddpg_pop_update_device", "stmpc_ddpg_pop_stats_device"}
     assert set(declared) == {n for n in capi.EXPORTS if n.startswith("stmpc_ddpg_pop_")}
@@ -67,41 +56,10 @@ def test_population_refuses_an_env_it_cannot_split_before_touching_the_device():
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------------------------
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
 def _cfgs(B, P, gamma=GAMMA):
     from rl_mpc_lanemerging_amd import learner
     return [learner.DDPGConfig(n_obs=20, batch=B, capacity=CAP, replay_start=REPLAY_START[m], gamma=gamma[m], tau=TAU[m], noise=NOISE[m], lr_q=LR_Q[m],
                                lr_pi=LR_PI[m]) for m in range(P)]
-
-
-def _init(m):
-    """Member m's starting networks: torch's initialisation with last layers that are not zero, so that every gradient is alive from update 1."""
-    from rl_mpc_lanemerging_amd import learner
-    rng = np.random.default_rng(100 + m)
-    a_net, q_net = learner.init_net(21, 400, 300, rng), learner.init_net(22, 400, 300, rng)
-    a_net["w2"] = rng.normal(0, 0.05, (1, 300)).astype(np.float32)
-    q_net["w2"] = rng.normal(0, 0.05, (1, 300)).astype(np.float32)
-    return {"actor": a_net, "critic": q_net}
-
-
-def _snapshot(gpu_ctx, L, stats):
-    sd = L.state_dict()
-    return {"params": sd["params"], "counters": sd["counters"], "ring": gpu_ctx.ddpg_replay_read(L.handle, 0, CAP), "stats": stats}
-
-
-def _assert_same(a, b, label):
-    from rl_mpc_lanemerging_amd import _capi as capi, learner
-    for slot in capi.DDPG_SLOTS:
-        for k in learner.TENSORS:
-            assert np.array_equal(_bits(a["params"][slot][k]), _bits(b["params"][slot][k])), (label, slot, k)
-    assert np.array_equal(_bits(a["params"]["beta_pow"]), _bits(b["params"]["beta_pow"])), (label, "beta_pow")
-    assert np.array_equal(a["counters"], b["counters"]), (label, a["counters"], b["counters"])
-    assert np.array_equal(_bits(a["ring"]), _bits(b["ring"])), (label, "ring")
-    assert np.array_equal(_bits(np.array(a["stats"])), _bits(np.array(b["stats"]))), (label, a["stats"], b["stats"])
 
 
 def _run(gpu_ctx, B, P, seeds=SEEDS, gamma=GAMMA, alone=True):

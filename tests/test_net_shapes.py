@@ -1,11 +1,11 @@
 """The actor and DDPG kernels (csrc/stmpc_actor_kernels.hpp, csrc/stmpc_ddpg_kernels.hpp and their population entries) at network shapes other than
-the shipped 21-400-300-1, on the GPU.  The shapes and what each reaches are test_net_shapes_cpu.SHAPES.
+the shipped 21-400-300-1, on the GPU.  The shapes and what each reaches are learner_testlib.SHAPES.
 
-1. Bit for bit on the exact-arithmetic problems of test_net_shapes_cpu.py (which asserts, on the CPU, that every partial sum of the critic's passes
+1. Bit for bit on the exact-arithmetic problems of learner_testlib.py (test_net_shapes_cpu.py asserts, on the CPU, that every partial sum of the critic's passes
    is a float32 number whatever the summation order): the critic's six gradient tensors, the gathered minibatch, the parameters' round trip.
    Acting and the fused k_actor_eval on the same weights: the pre-tanh output is exact, tanh is not, so these two carry the one bound each that the
    test states.
-2. The 4 x rule of test_learner.py (imported, not restated) on ordinary random problems, for what cannot be exact: the actor's gradient,
+2. The 4 x rule of learner_testlib.py on ordinary random problems, for what cannot be exact: the actor's gradient,
    gamma = 0.99 with targets, padded minibatch rows; then two updates against adam_host within the same 2 ulps.
 3. Populations bit-equal to their members alone, and wide networks that keep working after narrower ones were created (the dynamic-LDS attribute
    of a kernel is only ever raised).
@@ -14,8 +14,10 @@ No test uses an environment: replays are synthetic pushes, parameters come throu
 import numpy as np
 import pytest
 
-from test_learner import FLOOR, _check_4x, _random_problem, _record
-from test_net_shapes_cpu import EXACT_CASES, SEED, SHAPES, TIME_SCALE, _capi, forward_host, host_minibatch, problem, replay_rows_host
+from learner_testlib import (CAP, EXACT_CASES, FLOOR, SEED, SHAPES, TIME_SCALE, assert_same as _assert_same, check_4x as _check_4x, dev as _dev, forward_host,
+                             host_minibatch, problem, push as _push, random_problem as _random_problem, record as _record, replay_rows_host, snapshot as _snapshot)
+from stmpc_testlib import (ACTOR_N as N, ACTOR_N_PER as N_PER, ACTOR_P as P, actor_settings as _settings, actor_states as _states, actor_two_steps as _two_steps,
+                           assert_steps_equal as _assert_steps_equal, capi as _capi, slice_steps as _slice_steps)
 
 SMALL = ("one-tile", "padded", "mixed-k", "wide-h2")
 # a state vector (FeaturesCfg) as long as the actor's input, per shape: settings overrides, time feature.  one-tile (6 inputs) and wide-h2 (2) have no
@@ -25,16 +27,6 @@ FEATURES = {"one-tile": (dict(CARS_AHEAD=1, CARS_BEHIND=0, USE_ACCELERATION_OF_O
             "mixed-k": (dict(CARS_AHEAD=5, CARS_BEHIND=4, USE_ACCELERATION_OF_OTHER_CARS=False), False, 31),
             "wide-h2": (dict(CARS_AHEAD=0, CARS_BEHIND=0, USE_ACCELERATION_OF_OTHER_CARS=True), False, 4),
             "over-64K": (dict(CARS_AHEAD=2, CARS_BEHIND=2, USE_ACCELERATION_OF_OTHER_CARS=True), True, 21)}
-
-
-def _dev(a):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a), device="cuda")
-
-
-def _push(L, replay, rows=slice(None)):
-    L.push(_dev(replay["obs"][rows]), _dev(replay["ticks"][rows]), _dev(replay["action"][rows]), _dev(replay["reward"][rows]), _dev(replay["next_obs"][rows]),
-           _dev(replay["terminated"][rows]), _dev(replay["truncated"][rows]))
 
 
 def _exact_learner(gpu_ctx, shape, B):
@@ -271,8 +263,8 @@ def _random_replay(rng, n_obs, rows=600):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,B", [pytest.param(s, B, id="%s-B%d" % (s, B)) for s in ("padded", "mixed-k") for B in (48, 100)])
 def test_gpu_random_problem_by_the_4x_rule(shape, B, gpu_ctx, restore_settings):
-    """Random float32 parameters (test_learner._random_problem's), gamma = 0.99, targets that differ, a synthetic replay of 600 rows.  B = 48 leaves
-    five of k_ddpg_wgrad's eight waves without work, B = 100 has 12 padded rows.  Gradients of both networks by test_learner.py's rule, then two
+    """Random float32 parameters (learner_testlib.random_problem's), gamma = 0.99, targets that differ, a synthetic replay of 600 rows.  B = 48 leaves
+    five of k_ddpg_wgrad's eight waves without work, B = 100 has 12 padded rows.  Gradients of both networks by the 4 x rule, then two
     updates against adam_host within its 2 ulps."""
     from rl_mpc_lanemerging_amd import learner
     n_obs, h1, h2 = SHAPES[shape]
@@ -328,10 +320,9 @@ class _Rows:
 @pytest.mark.gpu
 def test_gpu_ddpg_population_at_the_padded_shape(gpu_ctx, restore_settings):
     """Three members at 21-40-24-1 (pads in both widths), B = 48: after three updates every member equals a lone learner with the same seed, pushes and
-    parameters, bit for bit (test_learner_pop.py's snapshot and comparison: parameters, Adam state, counters, ring, statistics)."""
+    parameters, bit for bit (learner_testlib's snapshot and comparison: parameters, Adam state, counters, ring, statistics)."""
     import torch
     from rl_mpc_lanemerging_amd import learner
-    from test_learner_pop import CAP, _assert_same, _snapshot
     n_obs, h1, h2 = SHAPES["padded"]
     P, n_per, seeds = 3, 24, (11, 12, 13)
     cfgs = [learner.DDPGConfig(n_obs=n_obs, h1=h1, h2=h2, batch=48, capacity=CAP, replay_start=0, gamma=(0.99, 0.95, 0.9)[m], tau=(0.005, 0.01, 0.02)[m],
@@ -368,13 +359,12 @@ def test_gpu_ddpg_population_at_the_padded_shape(gpu_ctx, restore_settings):
 @pytest.mark.gpu
 def test_gpu_actor_population_at_the_mixed_k_widths(gpu_ctx, restore_settings, tmp_path):
     """Three actors with mixed-k's hidden widths (96, 48: six k blocks -- the unrolled loop, then a tail of one -- and three tiles for eight waves),
-    24 rows each, two rollout steps: every member equals the lone actor on its slice, bit for bit (test_actor_pop.py's helpers and states).
+    24 rows each, two rollout steps: every member equals the lone actor on its slice, bit for bit (test_actor_pop.py's steps and states, from stmpc_testlib).
     ActorPopulation always feeds the time feature, and no state vector with it has mixed-k's 31 entries; nine vehicles of three entries and the
     five ego entries give 32, the widest input the kernel takes (AT_KIN), which no other test reaches."""
     import torch
     import rl_mpc_lanemerging_amd as pkg
     from rl_mpc_lanemerging_amd import actor, learner
-    from test_actor_pop import N, N_PER, P, _assert_steps_equal, _settings, _slice_steps, _states, _two_steps
     g, S = _settings()
     pkg.apply_overrides(dict(CARS_AHEAD=5, CARS_BEHIND=4, USE_ACCELERATION_OF_OTHER_CARS=False))
     dev = torch.device("cuda", torch.cuda.current_device())

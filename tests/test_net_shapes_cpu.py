@@ -11,170 +11,12 @@ This module asserts the condition the GPU tests rest on, for every (shape, B) th
   * ``update_host`` in float32 and in float64 give the same critic gradients, value for value, and a plain numpy forward pass of both networks
     gives the same hidden activations and pre-tanh outputs in float32 and float64;
   * the problems are not vacuous: at least a third of every gradient tensor is non-zero, and no two rows of W1 are equal.
+The problems themselves (``dyadic_problem``, ``exactness_bits``, the case tables) are in learner_testlib.py, which the GPU part shares.
 """
 import numpy as np
 import pytest
 
-# name -> (n_obs, h1, h2); what each reaches is in DESIGN.md section 12
-SHAPES = {"one-tile": (5, 16, 16), "padded": (20, 40, 24), "mixed-k": (30, 96, 48), "wide-h2": (1, 176, 208), "over-64K": (20, 512, 512)}
-BATCHES = (16, 64, 256)
-EXACT_CASES = [(s, B) for s in ("one-tile", "padded", "mixed-k", "wide-h2") for B in BATCHES] + [("over-64K", 16)]
-SEED = 17                       # the learner's seed: it draws the minibatch rows
-REPLAY_ROWS = 320
-TIME_SCALE = 0.25               # time feature = 0.25 x ticks: a multiple of 1/4 like the observations (the shipped 0.001 is no dyadic number)
-
-
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
-
-
-def _sparse_rows(rng, rows, cols, nnz, values, distinct=False):
-    """[rows][cols] with ``nnz`` entries per row drawn from ``values`` (none of them 0) at random columns; ``distinct``: no two rows equal."""
-    nnz = min(nnz, cols)
-    w = np.zeros((rows, cols), dtype=np.float32)
-    seen = set()
-    for n in range(rows):
-        while True:
-            row = np.zeros(cols, dtype=np.float32)
-            row[rng.choice(cols, nnz, replace=False)] = rng.choice(values, nnz)
-            if not distinct or row.tobytes() not in seen:
-                break
-        seen.add(row.tobytes())
-        w[n] = row
-    return w
-
-
-def _dyadic_net(rng, n_in, h1, h2, out_scale):
-    """One network of the value sets ``dyadic_problem`` documents; ``out_scale`` (a power of two) scales the last layer."""
-    half = np.array([-1.0, -0.5, 0.5, 1.0], dtype=np.float32)
-    w2 = rng.choice(np.array([-1.0, 1.0], dtype=np.float32), (1, h2))
-    w2[0, rng.random(h2) < 0.125] = 0.0
-    return {"w0": _sparse_rows(rng, h1, n_in, 3, half), "b0": rng.choice(np.array([-0.5, 0.0, 0.5], dtype=np.float32), h1),
-            "w1": _sparse_rows(rng, h2, h1, 3, half, distinct=True), "b1": rng.choice(np.array([0.0, 0.5, 1.0], dtype=np.float32), h2),
-            "w2": (w2 * np.float32(out_scale)).astype(np.float32), "b2": np.array([0.5 * out_scale], dtype=np.float32)}
-
-
-def dyadic_problem(shape, B, rng):
-    """(cfg, params, replay) for ``shape`` = (n_obs, h1, h2) (or a name of SHAPES) and minibatch size ``B`` (a power of two).
-
-    Value sets (tuned on the CPU until ``exactness_bits`` stayed below 24 for every case of EXACT_CASES):
-      observations, next observations, actions   multiples of 1/4 in [-1, 1]
-      time feature                               0.25 x ticks, ticks in 0 ... 4 (cfg.time_scale = 0.25)
-      rewards                                    multiples of 1/4 in [-2, 2]
-      W0, W1                                     three entries of {-1, -1/2, 1/2, 1} per row, the rest 0 (sparse rows keep the sums short); the rows of
-                                                 W1 are pairwise different
-      b0 in {-1/2, 0, 1/2}, b1 in {0, 1/2, 1}    (b1 >= 0 keeps most second-layer units alive)
-      W2                                         -1 or +1, one in eight 0; the actor's scaled by a power of two so that tanh is not saturated
-      b2                                         1/2 (times the same power of two)
-      gamma = 0                                  y = r: the critic's gradient does not see the target networks (they get values of the same sets)
-      dz = 2 (Q - r) / B                         exact because B is a power of two
-    The products are then multiples of 2^-3 (layer 0), 2^-5 (layer 1, Q), 2^-(4 + log2 B) (dz) ... 2^-(9 + log2 B) (dW1).  Largest width reached
-    over EXACT_CASES: 20.4 bits, in dW2 of mixed-k at B = 256 (printed by test_every_partial_sum_fits_float32); 24 is float32's.
-    ``replay``: REPLAY_ROWS transitions as ``DDPGLearner.push`` takes them (numpy)."""
-    _capi()
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, h2 = SHAPES[shape] if isinstance(shape, str) else shape
-    assert B & (B - 1) == 0
-    cfg = learner.DDPGConfig(n_obs=n_obs, h1=h1, h2=h2, batch=B, capacity=512, replay_start=0, gamma=0.0, time_scale=TIME_SCALE, lr_q=1e-3, lr_pi=5e-4,
-                             action_low=-5.0, action_high=5.0)
-    a_scale = 2.0 ** -int(round(np.log2(np.sqrt(1.5 * h2))))
-    params = learner.new_params(_dyadic_net(rng, n_obs + 1, h1, h2, a_scale), _dyadic_net(rng, n_obs + 2, h1, h2, 1.0))
-    params["actor_target"] = {k: v.copy() for k, v in _dyadic_net(rng, n_obs + 1, h1, h2, a_scale).items()}
-    params["critic_target"] = {k: v.copy() for k, v in _dyadic_net(rng, n_obs + 2, h1, h2, 1.0).items()}
-    quarter = lambda lo, hi, *sh: (rng.integers(4 * lo, 4 * hi + 1, sh) / 4.0)
-    R = REPLAY_ROWS
-    kind = rng.integers(0, 4, R)                                  # 0, 1: neither; 2: terminated; 3: truncated
-    replay = {"obs": quarter(-1, 1, R, n_obs).astype(np.float32), "next_obs": quarter(-1, 1, R, n_obs).astype(np.float32),
-              "ticks": rng.integers(0, 4, R).astype(np.int32), "action": quarter(-1, 1, R), "reward": quarter(-2, 2, R), "terminated": kind == 2,
-              "truncated": kind == 3}
-    return cfg, params, replay
-
-
-def replay_rows_host(replay, cfg):
-    """The ring rows k_replay_push writes for ``replay`` pushed into an empty ring (test_gpu_replay_ring_equals_a_numpy_ring's twin; no final_obs,
-    no next_ticks: s' is next_obs at ticks + 1)."""
-    capi = _capi()
-    n_obs, R = cfg.n_obs, len(replay["ticks"])
-    ts = np.float32(cfg.time_scale)
-    rows = np.zeros((R, capi.DDPG_ROW), dtype=np.float32)
-    rows[:, :n_obs], rows[:, n_obs], rows[:, n_obs + 1] = replay["obs"], ts * replay["ticks"].astype(np.float32), replay["action"].astype(np.float32)
-    rows[:, 32:32 + n_obs], rows[:, 32 + n_obs] = replay["next_obs"], ts * (replay["ticks"] + 1).astype(np.float32)
-    rows[:, 64], rows[:, 65] = replay["reward"].astype(np.float32), np.where(replay["terminated"], 0, 1)
-    return rows
-
-
-def host_minibatch(replay, cfg, update=0, seed=SEED):
-    """(rows [B][68], the minibatch dict of update_host) the learner with ``seed`` samples at update index ``update``."""
-    from rl_mpc_lanemerging_amd import learner
-    rows = replay_rows_host(replay, cfg)
-    rows = rows[learner.sample_indices_host(seed, update, cfg.batch, rows.shape[0])]
-    return rows, learner.batch_from_rows(rows, cfg.n_obs)
-
-
-def forward_host(net, x, dtype):
-    """A plain numpy forward pass in ``dtype``: (H1, H2, z) -- hidden activations and the pre-tanh output."""
-    f = lambda a: np.asarray(a, dtype=dtype)
-    h1 = np.maximum(f(x) @ f(net["w0"]).T + f(net["b0"]), 0)
-    h2 = np.maximum(h1 @ f(net["w1"]).T + f(net["b1"]), 0)
-    return h1, h2, (h2 @ f(net["w2"]).T + f(net["b2"]))[:, 0]
-
-
-def _frac_bits(a):
-    """Smallest e such that every entry of ``a`` is a multiple of 2^-e."""
-    a = np.asarray(a, dtype=np.float64)
-    for e in range(-8, 64):
-        if np.array_equal(a * 2.0 ** e, np.round(a * 2.0 ** e)):
-            return e
-    raise AssertionError("not dyadic")
-
-
-def exactness_bits(params, batch):
-    """Per stage of the critic's forward pass, backward pass and weight gradients (and of the actor's forward pass): log2 of (the largest sum of
-    |a| |b| over the summed index) / (the unit every product is a multiple of).  Below 24, every partial sum of every summation order is a float32
-    number.  Computed in float64, which is exact as long as the result holds."""
-    q, B = params["critic"], len(batch["r"])
-    d = lambda a: np.asarray(a, dtype=np.float64)
-    bits = {}
-
-    def stage(name, a, b, bias=None):                             # a [m][k] @ b [k][n] (+ bias [n])
-        a, b = d(a), d(b)
-        e = _frac_bits(a) + _frac_bits(b)
-        s = np.abs(a) @ np.abs(b)
-        if bias is not None:
-            e, s = max(e, _frac_bits(bias)), s + np.abs(d(bias))
-        bits[name] = float(np.log2(max(s.max(), 2.0 ** -e) * 2.0 ** e))
-
-    x = np.concatenate([d(batch["s"]), d(batch["a"])[:, None]], 1)
-    h1, h2, qv = forward_host(q, x, np.float64)
-    stage("critic z1", x, d(q["w0"]).T, q["b0"])
-    stage("critic z2", h1, d(q["w1"]).T, q["b1"])
-    stage("critic Q", h2, d(q["w2"]).T, q["b2"])
-    stage("Q - r", np.stack([qv, -d(batch["r"])], 1), np.ones((2, 1)))
-    dz = 2.0 * (qv - d(batch["r"])) / B
-    dz2 = dz[:, None] * d(q["w2"]) * (h2 > 0)
-    stage("dZ2", np.abs(dz2).reshape(-1, 1), np.ones((1, 1)))
-    stage("dZ1", dz2, d(q["w1"]))
-    dz1 = (dz2 @ d(q["w1"])) * (h1 > 0)
-    for name, left, right in (("dW1", dz2, h1), ("db1", dz2, np.ones((B, 1))), ("dW2", dz[:, None], h2), ("db2", dz[:, None], np.ones((B, 1))),
-                              ("dW0", dz1, x), ("db0", dz1, np.ones((B, 1)))):
-        stage(name, left.T, right)
-    for slot in ("actor", "actor_target"):
-        a = params[slot]
-        xs = d(batch["s"] if slot == "actor" else batch["s2"])
-        g1, g2, _ = forward_host(a, xs, np.float64)
-        stage(slot + " z1", xs, d(a["w0"]).T, a["b0"])
-        stage(slot + " z2", g1, d(a["w1"]).T, a["b1"])
-        stage(slot + " z", g2, d(a["w2"]).T, a["b2"])
-    return bits
-
-
-def problem(shape, B):
-    """The problem of one case: the same for the CPU and the GPU tests (one generator seed per case)."""
-    return dyadic_problem(shape, B, np.random.default_rng(1000 + 7 * list(SHAPES).index(shape) + B))
+from learner_testlib import EXACT_CASES, SHAPES, TIME_SCALE, exactness_bits, forward_host, host_minibatch, problem
 
 
 def _cases():

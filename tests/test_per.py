@@ -1,39 +1,20 @@
-"""Prioritised replay on the GPU (learner.PERConfig on DDPGLearner / TD3Learner, csrc/stmpc_per_kernels.hpp, stmpc_per_*).  Twins and helpers:
-test_per_cpu.py; problems: test_td3_cpu.random_td3_problem at the small network 20-40-24, ring rows pushed from its 256 synthetic rows.
+"""Prioritised replay on the GPU (learner.PERConfig on DDPGLearner / TD3Learner, csrc/stmpc_per_kernels.hpp, stmpc_per_*).  Twins: test_per_cpu.py;
+helpers and problems: learner_testlib.py -- random_td3_problem at the small network 20-40-24, ring rows pushed from its 256 synthetic rows.
 
 Bit for bit wherever the arithmetic allows it: the tree after pushes and after priority updates (alpha 0.5 and 1: sqrt and the identity are correctly
 rounded on both sides), the sampled rows for any alpha (the twin descends the device's own tree), weights at beta 0, reproducibility, the gate.
 Elsewhere: the weights within 4 float32 ulps of the float64 twin (both sides compute in fp64 and may differ by a few fp64 ulps of pow, which moves
-the float32 rounding by at most one step); gradients and ten updates under test_learner.py's rule -- error = max-abs difference to the float64 twin
+the float32 rounding by at most one step); gradients and ten updates under the parity rule (learner_testlib.check_4x) -- error = max-abs difference to the float64 twin
 over its max-abs, bound = 4 x the float32 twin's same error, floor 8 float32 ulps -- the twins fed the device's own rows and weights.
 """
 import numpy as np
 import pytest
 
-from test_learner import _record
-from test_net_shapes import _push
-from test_net_shapes_cpu import SEED, _capi
-from test_per_cpu import internal_nodes_are_exact
-from test_td3_cpu import ddpg_view, random_td3_problem
+from learner_testlib import (SEED, bits64 as _bits, bits_equal as _bits_equal, check_4x as _check_4x, ddpg_view, internal_nodes_are_exact, push as _push,
+                             random_td3_problem, record as _record, rel_err as _rel_err)
+from stmpc_testlib import capi as _capi
 
-FLOOR = 8 * 2.0 ** -23          # 8 float32 ulps, relative
 KINDS = ["ddpg", "td3"]
-
-
-def _rel_err(x, ref):
-    scale = np.abs(ref).max()
-    return float(np.abs(np.asarray(x, dtype=np.float64) - ref).max() / scale) if scale > 0 else float(np.abs(x).max())
-
-
-def _check_4x(label, dev, f32, f64, ratios):
-    """The parity rule of the module text for one tensor; prints and records before it asserts."""
-    e_dev, e_32 = _rel_err(dev, f64), _rel_err(f32, f64)
-    bound = max(4 * e_32, FLOOR)
-    ratios[label] = {"device": e_dev, "float32_twin": e_32, "ratio": e_dev / e_32 if e_32 > 0 else None}
-    print("%-40s device %.3e  float32 twin %.3e  bound %.3e" % (label, e_dev, e_32, bound))
-    return e_dev <= bound
-
-
 B2_MIN = 0.05
 
 
@@ -69,11 +50,6 @@ def _slots(kind):
     return capi.DDPG_SLOTS + (capi.TD3_SLOTS if kind == "td3" else ())
 
 
-def _bits_equal(a, b, slots):
-    from rl_mpc_lanemerging_amd import learner
-    return all(np.array_equal(np.asarray(a[s][k], np.float32).view(np.uint32), np.asarray(b[s][k], np.float32).view(np.uint32)) for s in slots for k in learner.TENSORS)
-
-
 def _twin(kind, params, batch, cfg, dtype, weights, eps=None, grads_only=False):
     from rl_mpc_lanemerging_amd import learner
     if kind == "td3":
@@ -84,10 +60,6 @@ def _twin(kind, params, batch, cfg, dtype, weights, eps=None, grads_only=False):
 def _eps(kind, L):
     """The device's smoothing noise of the next update's rows (TD3; it also runs the sampling step, as the update will)."""
     return L.targets()[:, 0].astype(np.float64) if kind == "td3" else None
-
-
-def _bits(a):
-    return np.asarray(a, dtype=np.float64).view(np.uint64)
 
 
 # ---- 1 -----------------------------------------------------------------------------------------------------------------------------------------

@@ -3,53 +3,24 @@
   * header, library and binding agree on the new entries and on stmpc_per_cfg; the ABI is still 8;
   * ``per_sample_host`` equals ``stmpc_per_sample_index`` -- the function the kernel calls -- on random and on hand-made trees;
   * ``SumTreeHost`` against brute force; sampling frequencies; the priority rule on duplicates; ``update_host(weights=)``; refusals.
-The GPU part is test_per.py, which takes its helpers from here.
+The GPU part is test_per.py; the helpers both use are in learner_testlib.py.
 """
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+from learner_testlib import internal_nodes_are_exact, minibatch_host, random_problem as _random_problem, random_td3_problem, tree_from_leaves
+from stmpc_testlib import capi as _capi, header_entries, header_struct_fields as _header_struct_fields, header_text
 
 ENTRIES = {"stmpc_per_enable", "stmpc_per_tree_read", "stmpc_per_last_device", "stmpc_per_sample_index"}
 
 
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
-
-
-def tree_from_leaves(w):
-    """The sum tree over leaf weights ``w`` (a power of two of them), every level summed from the one below: brute force, no incremental update."""
-    w = np.asarray(w, dtype=np.float64)
-    n = np.zeros(2 * w.size - 1)
-    n[w.size - 1:] = w
-    width = w.size // 2
-    while width >= 1:
-        n[width - 1:2 * width - 1] = n[2 * width - 1:4 * width - 1:2] + n[2 * width:4 * width:2]
-        width //= 2
-    return n
-
-
-def internal_nodes_are_exact(nodes):
-    leaves = (nodes.size + 1) // 2
-    i = np.arange(leaves - 1)
-    return bool(np.array_equal(nodes[i], nodes[2 * i + 1] + nodes[2 * i + 2]))
-
-
 def test_header_library_and_binding_agree_on_prioritised_replay():
     capi = _capi()
-    from test_host_cpu import _header_struct_fields
     lib = capi.load()
-    header = open(os.path.join(REPO, "include", "stmpc.h")).read()
-    declared = {n for n in re.findall(r"\b(stmpc_[a-z_0-9]+)\s*\(", header) if n.startswith("stmpc_per_")}
+    declared = header_entries("stmpc_per_")
     assert declared == ENTRIES == {n for n in capi.EXPORTS if n.startswith("stmpc_per_")}
     for name in declared:
         assert getattr(lib, name) is not None and getattr(lib, name).argtypes is not None, name
@@ -57,7 +28,7 @@ def test_header_library_and_binding_agree_on_prioritised_replay():
     assert [n for n, _ in want] == [n for n, _ in capi.PERCfg._fields_] == ["alpha", "beta", "min_priority", "max_priority"]
     assert all(t == "double" for _, t in want) and all(t is ctypes.c_double for _, t in capi.PERCfg._fields_)
     assert lib.stmpc_per_sample_index.restype is ctypes.c_int64
-    assert capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8 and "#define STMPC_ABI_VERSION 8" in " ".join(header.split())
+    assert capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8 and "#define STMPC_ABI_VERSION 8" in header_text(flat=True)
     # the cfg structs of ABI 8 did not grow: prioritisation is enabled on the handle
     from rl_mpc_lanemerging_amd import learner
     assert ctypes.sizeof(capi.DDPGCfg) == 24 + 8 * 13 and ctypes.sizeof(capi.TD3Cfg) == ctypes.sizeof(capi.DDPGCfg) + 24
@@ -190,7 +161,6 @@ def test_update_host_weights():
     _capi()
     import torch
     from rl_mpc_lanemerging_amd import learner
-    from test_learner import _random_problem
     rng = np.random.default_rng(2)
     cfg, params, batch = _random_problem(rng)
     B = len(batch["r"])
@@ -202,7 +172,6 @@ def test_update_host_weights():
                 assert all(np.array_equal(a[slot][k], b[slot][k]) for k in learner.TENSORS), (dtype, go, slot)
             assert all(np.array_equal(ia["grad_critic"][k], ib["grad_critic"][k]) and np.array_equal(ia["grad_actor"][k], ib["grad_actor"][k]) for k in learner.TENSORS)
             assert ia["critic_loss"] == ib["critic_loss"]
-    from test_td3_cpu import minibatch_host, random_td3_problem
     cfg3, params3, replay3 = random_td3_problem("padded", 48, seed=3)
     batch3 = minibatch_host(replay3, cfg3)[1]
     a, ia = learner.update_host_td3(params3, batch3, cfg3)

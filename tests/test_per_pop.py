@@ -5,21 +5,16 @@ Every comparison is bit equality: device against device (a member against the lo
 the same member of another population), or device against the host twin ``SumTreeHost`` where only pushes touched a tree.  No tolerance anywhere: the
 population's kernels are the lone kernels' bodies on the member the grid selects.
 
-Shapes: the "padded" 20-40-24 network of test_net_shapes_cpu.SHAPES (the shipped 400 x 300 once per learner kind, at B = 100), N_PER = 24 environments
+Shapes: the "padded" 20-40-24 network of learner_testlib.SHAPES (the shipped 400 x 300 once per learner kind, at B = 100), N_PER = 24 environments
 per member, 12 steps, capacity 200 -- not a power of two, so the tree has 256 leaves of which 56 stay empty, and every ring wraps.  Member 2's
 ``replay_start`` is 199, the largest a ring of 200 allows (test_td3_pop's module text): its gate is shut during steps 1 ... 8 and opens at step 9.
 """
-import types
-
 import numpy as np
 import pytest
 
-from test_learner_pop import CAP, N_PER, STEPS, _assert_same, _bits, _snapshot
-from test_net_shapes import _dev, _push
-from test_net_shapes_cpu import SHAPES, _capi
-from test_per_cpu import internal_nodes_are_exact
-from test_td3_cpu import SHIPPED, random_td3_problem
-from test_td3_pop import _assert_same_td3, _init, _stats_row
+from learner_testlib import (CAP, N_PER, SHAPES, SHIPPED, STEPS, assert_same as _assert_same, assert_same_td3 as _assert_same_td3, dev as _dev, internal_nodes_are_exact,
+                             push as _push, random_td3_problem, snapshot as _snapshot, stats_row as _stats_row, stub_env as _stub_env, td3_init as _init)
+from stmpc_testlib import bits as _bits, capi as _capi
 
 KINDS = ["ddpg", "td3"]
 SEEDS = (11, 12, 13)
@@ -209,7 +204,7 @@ def test_gpu_mixed_population(kind, gpu_ctx, restore_settings):
     assert not np.array_equal(mixed[0]["params"]["critic"]["w1"], plain[0]["params"]["critic"]["w1"])      # prioritisation changed member 0's run
     # priorities() / last_sample() on a uniform member raise
     Pop, _ = _classes(kind)
-    env = types.SimpleNamespace(n=32, obs_dim=20, continuous=True, ctx=gpu_ctx)
+    env = _stub_env(gpu_ctx, 32)
     pop = Pop(env, [_cfg(kind, "padded", 16, m) for m in range(2)], per=[pers[0], None])
     pop.member(0).priorities()
     for call in (pop.member(1).priorities, pop.member(1).last_sample):
@@ -234,10 +229,6 @@ def test_gpu_members_are_independent(kind, gpu_ctx, restore_settings):
 
 
 # ---- synthetic populations: rings filled by the population's push of rows, no env ---------------------------------------------------------------------
-def _stub_env(gpu_ctx, n, n_obs=20):
-    return types.SimpleNamespace(n=n, obs_dim=n_obs, continuous=True, ctx=gpu_ctx)
-
-
 def _synthetic(gpu_ctx, kind, P, per, B=16, capacity=CAP, n_per=N_PER, replay_start=0):
     """(population, replay): P members at the padded shape with test_td3_pop's starting networks, nothing pushed; ``replay``: 256 synthetic rows."""
     Pop, _ = _classes(kind)

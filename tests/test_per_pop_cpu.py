@@ -7,29 +7,19 @@ include/stmpc.h): CPU part.
 The GPU part is test_per_pop.py.
 """
 import ctypes
-import os
-import re
 
 import pytest
 
-from conftest import REPO
+from stmpc_testlib import capi as _capi, header_prototypes, header_text
 
 ENTRIES = {"stmpc_pop_per_enable_ddpg", "stmpc_pop_per_enable_td3"}
-
-
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
 
 
 def test_header_library_and_binding_agree_on_population_prioritised_replay():
     capi = _capi()
     lib = capi.load()
-    header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
-    declared = {name: args for name, args in re.findall(r"\b(stmpc_pop_per_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}
+    header = header_text(flat=True)
+    declared = header_prototypes("stmpc_pop_per_")
     assert set(declared) == ENTRIES == {n for n in capi.EXPORTS if n.startswith("stmpc_pop_per_")}
     for name, args in declared.items():
         fn = getattr(lib, name)                                   # (AttributeError: the library does not export it)

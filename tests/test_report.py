@@ -18,16 +18,9 @@ import numpy as np
 import pytest
 
 from conftest import REPO, load_golden
+from stmpc_testlib import capi as _capi
 
 ST_TRAFFIC = dict(BASE_TRAFFIC_INTERVAL=2.4, OTHER_CAR_SPEED=7.0)
-
-
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
 
 
 def _bits(a):

@@ -2,7 +2,7 @@
 vec_env.MergeVecEnv; ``executed_actions`` of learner.train_ddpg): the fused step equals the composition of the pinned public pieces, bit for bit.
 
 Shape unless stated: n = 96 (a full 64-thread workgroup and a partial one), "sumo-jerk-continuous-v0", the "default" traffic (1.2 s headway),
-shield_kmax = 32.  Every shielded run is recorded once (``_record``) and shared by the tests that need it."""
+shield_kmax = 32.  Every shielded run is recorded once (``_recorded_run``) and shared by the tests that need it."""
 import numpy as np
 import pytest
 
@@ -30,8 +30,8 @@ def _actions(env, rng, n):
 KEYS = ("obs", "reward", "term", "trunc", "takeover", "reason", "executed_jerk", "executed_action", "takeover_ticks", "final_stats")
 
 
-def _record(env_id="sumo-jerk-continuous-v0", n=N, ticks=150, shield="first_step", sparse=False, penalty=0.0, autoreset=False, world=True, actions=None,
-            expect_error=False):
+def _recorded_run(env_id="sumo-jerk-continuous-v0", n=N, ticks=150, shield="first_step", sparse=False, penalty=0.0, autoreset=False, world=True, actions=None,
+                  expect_error=False):
     """One run of a MergeVecEnv on a context of its own under the seeded actions: every output of every tick (host copies), the world after every tick
     (``world``) and the shield's counts.  Cached: a reference is computed once and never changed."""
     key = (env_id, n, ticks, shield, sparse, penalty, autoreset, world, None if actions is None else hash(np.ascontiguousarray(actions).tobytes()))
@@ -182,7 +182,7 @@ def test_gpu_step_is_the_composition_bit_for_bit(restore_settings):
     """150 ticks of uniform jerks in the Box, world seed 7, action seed 11.  That run, on an MI355X: 1378 takeovers and 12250 accepted proposals on
     live rows, 33 environments end, 17 of them (crash or arrival) on a tick on which they were taken over -- the corrected projected jerk; 772 decisions
     fall on finished rows, and over all rows the composition counts 1852 takeovers, the context's own count."""
-    rec = _record()
+    rec = _recorded_run()
     seen = _compose(rec, "sumo-jerk-continuous-v0")
     print("shield env composition:", seen, "counts", rec["counts"])
     assert seen["takeovers"] >= 1 and seen["accepted"] >= 1, seen
@@ -237,8 +237,8 @@ def test_gpu_env_follows_the_first_step_runner(gpu_ctx, restore_settings):
 
 @pytest.mark.gpu
 def test_gpu_sparse_equals_dense(restore_settings):
-    dense = _record()
-    sparse = _record(ticks=100, sparse=True, actions=dense["action"][:100])
+    dense = _recorded_run()
+    sparse = _recorded_run(ticks=100, sparse=True, actions=dense["action"][:100])
     for k in KEYS + ("status", "sim_ticks", "acc", "ego4"):
         assert _same(sparse[k], dense[k][:100]), k
     d, t, solves = sparse["counts"]
@@ -249,8 +249,8 @@ def test_gpu_sparse_equals_dense(restore_settings):
 @pytest.mark.gpu
 def test_gpu_no_takeover_is_todays_env_and_the_penalty_is_exact(restore_settings):
     S = _settings()
-    shielded = _record()
-    plain = _record(shield=None, actions=shielded["action"])
+    shielded = _recorded_run()
+    plain = _recorded_run(shield=None, actions=shielded["action"])
     assert not plain["info_keys"] & {"takeover", "reason", "executed_jerk", "executed_action", "takeover_ticks"}
     taken_before = np.cumsum(shielded["takeover"], axis=0) - shielded["takeover"] > 0          # [t][e]: a takeover on an earlier tick
     clean = ~(taken_before | shielded["takeover"])                                              # up to the row's first takeover
@@ -261,7 +261,7 @@ def test_gpu_no_takeover_is_todays_env_and_the_penalty_is_exact(restore_settings
     stood = ~shielded["takeover"]
     assert _same(shielded["executed_action"][stood], shielded["action"][stood])
     # the takeover penalty: the world does not read the reward, so the run is the same run and only the reward moves
-    fined = _record(penalty=0.7, actions=shielded["action"])
+    fined = _recorded_run(penalty=0.7, actions=shielded["action"])
     for k in ("status", "sim_ticks", "acc", "ego4", "obs", "term", "trunc", "takeover", "reason", "executed_jerk", "executed_action", "takeover_ticks"):
         assert _same(fined[k], shielded[k]), k
     take = shielded["takeover"]
@@ -277,7 +277,7 @@ def test_gpu_no_takeover_is_todays_env_and_the_penalty_is_exact(restore_settings
 @pytest.mark.gpu
 def test_gpu_autoreset_counters_and_fewer_crashes(restore_settings):
     n, ticks = 1024, 400
-    a = _record(n=n, ticks=ticks, autoreset=True, world=False)
+    a = _recorded_run(n=n, ticks=ticks, autoreset=True, world=False)
     done = a["term"] | a["trunc"]
     count = np.zeros(n, np.int32)
     ends = 0
@@ -289,7 +289,7 @@ def test_gpu_autoreset_counters_and_fewer_crashes(restore_settings):
     assert ends > n and (a["takeover_ticks"][done] > 0).any() and (a["takeover_ticks"][done] == 0).any()
     dr = a["drained"]
     assert len(dr["env"]) == ends and np.isfinite(dr["episode_return"]).all()
-    b = _record(n=n, ticks=ticks, shield=None, autoreset=True, world=False, actions=a["action"])
+    b = _recorded_run(n=n, ticks=ticks, shield=None, autoreset=True, world=False, actions=a["action"])
     crashed_a, crashed_b = int(dr["crashed"].sum()), int(b["drained"]["crashed"].sum())
     print("crashed episodes: shielded %d of %d, unshielded %d of %d; takeover share %.4f"
           % (crashed_a, ends, crashed_b, len(b["drained"]["env"]), a["takeover"].mean()))
@@ -299,7 +299,7 @@ def test_gpu_autoreset_counters_and_fewer_crashes(restore_settings):
 @pytest.mark.gpu
 @pytest.mark.parametrize("env_id", ["sumo-jerk-v0", "sumo-accel-v0"])
 def test_gpu_discrete_envs(env_id, restore_settings):
-    rec = _record(env_id=env_id, ticks=60)
+    rec = _recorded_run(env_id=env_id, ticks=60)
     assert "executed_action" not in rec["info_keys"] and rec["executed_action"] == []
     seen = _compose(rec, env_id, check=("world", "reward", "shield"))
     print("shield env composition,", env_id, seen)
@@ -308,7 +308,7 @@ def test_gpu_discrete_envs(env_id, restore_settings):
     # composition with exactly that proposal pins through the world's state after the step; nothing turns NaN
     act = np.zeros((1, N), np.int32)
     act[0, 70] = 20 if env_id == "sumo-accel-v0" else 5
-    bad = _record(env_id=env_id, ticks=1, actions=act, expect_error=True)
+    bad = _recorded_run(env_id=env_id, ticks=1, actions=act, expect_error=True)
     _compose(bad, env_id, check=("world", "reward", "shield"))
     for k in ("obs", "reward", "executed_jerk", "acc", "ego4"):
         assert np.isfinite(bad[k]).all(), k

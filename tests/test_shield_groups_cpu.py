@@ -9,6 +9,7 @@ import re
 import pytest
 
 from conftest import REPO
+from stmpc_testlib import capi as _capi
 
 # entry -> its number of arguments
 ENTRIES = {"stmpc_shield_traffic_groups_env_reset_device": 12, "stmpc_shield_traffic_groups_env_step_device": 19,
@@ -16,14 +17,6 @@ ENTRIES = {"stmpc_shield_traffic_groups_env_reset_device": 12, "stmpc_shield_tra
            "stmpc_shield_traffic_mix_env_reset_device": 13, "stmpc_shield_traffic_mix_env_step_device": 21}
 METHODS = {"shield_env_step_groups": "stmpc_shield_traffic_groups_env_step_device",
            "shield_env_step_reward_groups": "stmpc_shield_reward_groups_env_step_device", "shield_traffic_mix_env_step": "stmpc_shield_traffic_mix_env_step_device"}
-
-
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
 
 
 def test_header_declares_the_entries_and_the_abi_stays():

@@ -4,7 +4,6 @@ under its STMPC_* settings, bit for bit against the CPU oracle's layered DP -- a
 episode.  tests/test_solver_variants_cpu.py shows, from the launch plan, which kernels each case launches.
 
 The statistics every case showed are kept in profiles/solver/variant_cases_stats.json (evidence; the assertions are here)."""
-import json
 import os
 
 import numpy as np
@@ -12,21 +11,13 @@ import pytest
 
 import solver_variant_cases as svc
 from conftest import REPO, load_golden
-from test_gpu_parity import _check
+from stmpc_testlib import check_solve as _check, record_json
 
 pytestmark = pytest.mark.gpu
 
 STATS = os.path.join(REPO, "profiles", "solver", "variant_cases_stats.json")
 COUNTERS = ("episodes", "fallback", "hbm_tier", "retries", "guided", "pool_exhausted", "resume_refused")
 KEYS = ("path_idx", "best_t", "cost", "crash", "path_dist")
-
-
-def _record(key, value):
-    """Merge one entry into profiles/solver/variant_cases_stats.json."""
-    data = json.load(open(STATS)) if os.path.exists(STATS) else {}
-    data[key] = value
-    with open(STATS, "w") as fh:
-        json.dump(data, fh, indent=1, sort_keys=True)
 
 
 class _World:
@@ -112,7 +103,7 @@ def test_case_equals_the_oracle(case, world, restore_settings, monkeypatch):
                 stats = ctx.stats()
         except _capi.StmpcError as e:
             pytest.exit("the device reported an error in case %s (%s): nothing more is started on it" % (case["name"], e), returncode=3)
-        _record(case["name"], {"knobs": case["knobs"], "N": case["N"], "stats": {k: int(stats[k]) for k in COUNTERS}})
+        record_json(STATS, case["name"], {"knobs": case["knobs"], "N": case["N"], "stats": {k: int(stats[k]) for k in COUNTERS}})
         print(case["name"], {k: int(stats[k]) for k in COUNTERS})
         if case["groups"]:
             differ = False

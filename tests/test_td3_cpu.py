@@ -1,160 +1,28 @@
-"""The TD3 learner (learner.TD3Learner, csrc/stmpc_td3_kernels.hpp, stmpc_td3_* of include/stmpc.h): CPU part, and the problems the GPU part
-(test_td3.py) shares.
+"""The TD3 learner (learner.TD3Learner, csrc/stmpc_td3_kernels.hpp, stmpc_td3_* of include/stmpc.h): CPU part.  The problems it and
+the GPU part (test_td3.py) share are in learner_testlib.py.
 
   * header, library and binding agree on the new entries and on stmpc_td3_cfg;
   * ``smoothing_noise_host`` equals ``stmpc_td3_noise`` and is another stream than the acting noise;
   * degenerate TD3 (no target noise, policy_delay 1, critic 2 = critic 1) is ``update_host`` value for value, float64 and float32, four updates;
   * the delay schedule of ``update_host_td3``;
-  * ``td3_dyadic_problem``: ``dyadic_problem`` of test_net_shapes_cpu.py with a second dyadic critic, dyadic target critics, a target actor whose
+  * ``td3_dyadic_problem`` (learner_testlib.py): ``dyadic_problem`` with a second dyadic critic, dyadic target critics, a target actor whose
     last layer is zero (a' = tanh_mean exactly) and gamma in {0.5, 1}: y = r + gamma * mask * min(Qt1, Qt2) and everything downstream of it stays in
     float32 numbers, so the GPU test compares with np.array_equal.
 """
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import REPO
-from test_net_shapes_cpu import SEED, SHAPES, _capi, _dyadic_net, _frac_bits, dyadic_problem, exactness_bits, forward_host, replay_rows_host
-
-RING = 256                      # the GPU tests' ring capacity; the first RING rows of a problem's replay are pushed
-# (shape, B, gamma) of the exact cases, CPU and GPU
-DYADIC_CASES = [("padded", 16, 0.5), ("padded", 64, 1.0), ("mixed-k", 16, 1.0), ("mixed-k", 64, 0.5)]
-# generator seed per case: the first from 5000 on under which test_dyadic_twin_target_is_exact holds (found on the CPU, with the twin alone)
-DYADIC_SEEDS = {("padded", 16): 5001, ("padded", 64): 5001, ("mixed-k", 16): 5000, ("mixed-k", 64): 5000}
-SHIPPED = (20, 400, 300)
-GRADIENT_CASES = [("padded", 48), (SHIPPED, 100)]                 # (shape, B) of the GPU gradient test
+from learner_testlib import (DYADIC_CASES, GRADIENT_CASES, SEED, SHIPPED, capi_slots, clipped_seed, conditioned_problem, ddpg_view, degenerate, exactness_bits,
+                             forward_host, frac_bits as _frac_bits, minibatch_host, random_td3_problem, td3_dyadic_problem, td_error_cancellation)
+from stmpc_testlib import capi as _capi, header_entries, header_struct_fields as _header_struct_fields, header_text
 
 
-def td3_config(cfg, **kw):
-    """A TD3Config with the fields of a DDPGConfig ``cfg`` (a dyadic problem's), ring capacity RING, and ``kw`` on top."""
-    from rl_mpc_lanemerging_amd import learner
-    base = dict(n_obs=cfg.n_obs, h1=cfg.h1, h2=cfg.h2, batch=cfg.batch, capacity=RING, replay_start=cfg.replay_start, gamma=cfg.gamma, tau=cfg.tau,
-                lr_q=cfg.lr_q, lr_pi=cfg.lr_pi, time_scale=cfg.time_scale, action_low=cfg.action_low, action_high=cfg.action_high)
-    base.update(kw)
-    return learner.TD3Config(**base)
-
-
-def td3_dyadic_problem(shape, B, gamma, seed=None):
-    """(cfg, params, replay): see the module text.  One generator seed per case, chosen so that the minibatch of update 0 has rows with Qt1 < Qt2, rows
-    with Qt2 < Qt1 and both values of mask (asserted below)."""
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, h2 = SHAPES[shape]
-    rng = np.random.default_rng(DYADIC_SEEDS[shape, B] if seed is None else seed)
-    cfg, p, replay = dyadic_problem(shape, B, rng)
-    cfg = td3_config(cfg, gamma=gamma, target_noise=0.0)
-    replay = {k: v[:RING] for k, v in replay.items()}
-    params = learner.new_params_td3(p["actor"], p["critic"], _dyadic_net(rng, n_obs + 2, h1, h2, 1.0))
-    params["actor_target"] = {k: v.copy() for k, v in p["actor_target"].items()}
-    params["actor_target"]["w2"][:] = 0.0
-    params["actor_target"]["b2"][:] = 0.0
-    params["critic_target"] = {k: v.copy() for k, v in p["critic_target"].items()}
-    params["critic2_target"] = {k: v.copy() for k, v in _dyadic_net(rng, n_obs + 2, h1, h2, 1.0).items()}
-    return cfg, params, replay
-
-
-def minibatch_host(replay, cfg, update=0, seed=SEED):
-    """(rows, the minibatch dict) a learner with ``seed`` samples at ``update`` from ``replay`` pushed into an empty ring."""
-    from rl_mpc_lanemerging_amd import learner
-    rows = replay_rows_host(replay, cfg)
-    rows = rows[learner.sample_indices_host(seed, update, cfg.batch, rows.shape[0])]
-    return rows, learner.batch_from_rows(rows, cfg.n_obs)
-
-
-def random_td3_problem(shape, B, seed=0, **kw):
-    """An ordinary floating-point problem: (cfg, params with targets that differ from the online nets and critic 2 != critic 1, RING replay rows).
-    Both tensors of the last layers are drawn away from their zero initialisation (as test_actor_pop._nonzero_last_layers does).  For b2 this matters
-    to the 4 x rule on PARAMETERS: a scalar that starts at zero is nothing but the sum of its Adam steps, so its relative error is the steps' -- and
-    k_ddpg_adam's float32 bias corrections (running products beta^t, 1 - beta2^t formed in float32; the arithmetic TD3 must share with DDPG bit for
-    bit) put 2.6e-6 on such a sum where torch's double-precision corrections put 3e-7 (test_float32_adam_on_a_zero_initialised_scalar)."""
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, h2 = SHAPES[shape] if isinstance(shape, str) else shape
-    rng = np.random.default_rng(seed)
-    base = dict(n_obs=n_obs, h1=h1, h2=h2, batch=B, capacity=RING, replay_start=0, lr_q=1e-3, lr_pi=5e-4, action_low=-5.0, action_high=5.0)
-    base.update(kw)
-    cfg = learner.TD3Config(**base)
-    nets = [learner.init_net(n_obs + 1, h1, h2, rng), learner.init_net(n_obs + 2, h1, h2, rng), learner.init_net(n_obs + 2, h1, h2, rng)]
-    for n in nets:
-        n["w2"] = rng.normal(0, 0.1, n["w2"].shape).astype(np.float32)
-        n["b2"] = rng.normal(0, 0.1, 1).astype(np.float32)
-    params = learner.new_params_td3(*nets)
-    for slot in ("actor_target", "critic_target", "critic2_target"):
-        for k in learner.TENSORS:
-            params[slot][k] = params[slot][k] + rng.normal(0, 0.01, params[slot][k].shape).astype(np.float32)
-    kind = rng.integers(0, 4, RING)
-    replay = {"obs": rng.normal(0, 1, (RING, n_obs)).astype(np.float32), "next_obs": rng.normal(0, 1, (RING, n_obs)).astype(np.float32),
-              "ticks": rng.integers(0, 500, RING).astype(np.int32), "action": rng.uniform(-5, 5, RING), "reward": rng.normal(0, 1, RING),
-              "terminated": kind == 2, "truncated": kind == 3}
-    return cfg, params, replay
-
-
-def td_error_cancellation(cfg, params, replay, seed=SEED):
-    """The smallest |mean| / rms, on the minibatch of update 0 (float64 twin, host noise), of the per-row terms whose mean is the gradient of an output
-    bias: Q_i - y for both critics, and dQ1/da * scale * (1 - tanh^2) for the actor.  Where the terms of a minibatch cancel to a small fraction of
-    their size, that gradient's RELATIVE error is rounding noise magnified by the inverse of this number -- in the float32 twin as much as on the
-    device -- and the 4 x rule would compare two draws of noise."""
-    import torch
-    from rl_mpc_lanemerging_amd import learner
-    T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
-    _, batch = minibatch_host(replay, cfg, 0, seed)
-    eps = learner.smoothing_eps_host(learner.smoothing_noise_host(seed, 0, cfg.batch)[2], cfg)
-    _, i = learner.update_host_td3(params, batch, cfg, "float64", eps=eps, grads_only=True)
-    y = i["targets"][:, 3].mean()
-    s = T(batch["s"])
-    z = learner._mlp({k: T(params["actor"][k]) for k in learner.TENSORS}, s)
-    a = (torch.tanh(z) * cfg.tanh_scale + cfg.tanh_mean).requires_grad_(True)
-    q = learner._mlp({k: T(params["critic"][k]) for k in learner.TENSORS}, torch.cat([s, a[:, None]], 1))
-    term = (torch.autograd.grad(q.sum(), a)[0] * cfg.tanh_scale * (1 - torch.tanh(z) ** 2)).numpy()
-    return min(abs(i["mean_q"] - y) / np.sqrt(i["critic_loss"]), abs(i["mean_q2"] - y) / np.sqrt(i["critic2_loss"]),
-               abs(term.mean()) / np.sqrt((term ** 2).mean()))
-
-
-def conditioned_problem(shape, B, lo, **kw):
-    """``random_td3_problem`` under the first generator seed >= lo whose bias-gradient terms cancel to no less than a tenth of their size (found with
-    the float64 twin alone, on the CPU)."""
-    for seed in range(lo, lo + 64):
-        out = random_td3_problem(shape, B, seed=seed, **kw)
-        if td_error_cancellation(*out) >= 0.1:
-            return out
-    raise AssertionError("no seed found")
-
-
-def ddpg_view(params):
-    """The DDPG learner's part of TD3 parameters (critic 2 dropped, beta_pow [4])."""
-    p = {k: v for k, v in params.items() if not k.startswith("critic2")}
-    p["beta_pow"] = np.array(params["beta_pow"][:4], dtype=np.float32)
-    return p
-
-
-def degenerate(cfg, params):
-    """TD3 that must equal DDPG: no target noise, policy_delay 1, critic 2 a copy of critic 1 in all four slots."""
-    cfg = td3_config(cfg, target_noise=0.0, policy_delay=1)
-    p = dict(params)
-    for slot in ("critic", "critic_target", "critic_m", "critic_v"):
-        p[slot.replace("critic", "critic2")] = {k: np.array(v) for k, v in params[slot].items()}
-    return cfg, p
-
-
-def clipped_seed(cfg, lo=0, n=64):
-    """The first learner seed >= lo whose smoothing noise of update 0 is clipped on some of the cfg.batch rows and not on others (host twin)."""
-    from rl_mpc_lanemerging_amd import learner
-    for seed in range(lo, lo + n):
-        g = learner.smoothing_noise_host(seed, 0, cfg.batch)[2]
-        hit = np.abs(cfg.target_noise_std * g) > cfg.noise_clip_abs
-        if 2 <= hit.sum() <= cfg.batch - 2:
-            return seed
-    raise AssertionError("no seed found")
-
-
-# ---- tests ---------------------------------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_agree_on_td3():
     capi = _capi()
-    from test_host_cpu import _header_struct_fields
     lib = capi.load()
-    header = open(os.path.join(REPO, "include", "stmpc.h")).read()
-    declared = {n for n in re.findall(r"\b(stmpc_[a-z_0-9]+)\s*\(", header) if n.startswith("stmpc_td3_")}
+    declared = header_entries("stmpc_td3_")
     assert declared == {"stmpc_td3_create", "stmpc_td3_destroy", "stmpc_td3_base", "stmpc_td3_set_params", "stmpc_td3_get_params", "stmpc_td3_set_state",
                         "stmpc_td3_get_state", "stmpc_td3_update_device", "stmpc_td3_grads_device", "stmpc_td3_targets_device", "stmpc_td3_stats_device",
                         "stmpc_td3_noise"}
@@ -166,7 +34,7 @@ def test_header_library_and_binding_agree_on_td3():
     have = list(capi.TD3Cfg._fields_)
     assert [n for n, _ in want] == [n for n, _ in have] and [ctype_of[t] for _, t in want] == [t for _, t in have]
     assert ctypes.sizeof(capi.TD3Cfg) == ctypes.sizeof(capi.DDPGCfg) + 24
-    flat = " ".join(header.split())
+    flat = header_text(flat=True)
     for i, slot in enumerate(capi.TD3_SLOTS):
         assert "#define STMPC_TD3_%s %d" % (slot.upper(), i) in flat, slot
     assert "#define STMPC_ABI_VERSION 8" in flat and capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8
@@ -220,10 +88,6 @@ def test_degenerate_td3_twin_is_the_ddpg_twin(dtype):
         for k in learner.TENSORS:
             assert np.array_equal(i3["grad_critic"][k], idd["grad_critic"][k]) and np.array_equal(i3["grad_actor"][k], idd["grad_actor"][k])
     assert np.abs(pd["actor"]["w1"] - params["actor"]["w1"]).max() > 0
-
-
-def capi_slots():
-    return _capi().DDPG_SLOTS
 
 
 def test_delay_schedule_of_the_twin():

@@ -4,22 +4,20 @@ Every comparison is bit equality against the lone ``TD3Learner`` (or, for degene
 are the lone learner's bodies on the member ``blockIdx.z`` selects.  The only tolerance in this file is test_actor.py's 5e-5 between the actor
 kernel and the acting kernel (two float32 evaluations of one network), as test_td3.py uses it.
 
-Shapes: "padded" 20-40-24 of test_net_shapes_cpu.SHAPES, rings of at most 256 rows, B in {16, 48}; the shipped 400 x 300 once, at B = 100.
+Shapes: "padded" 20-40-24 of learner_testlib.SHAPES, rings of at most 256 rows, B in {16, 48}; the shipped 400 x 300 once, at B = 100.
 
 The gate in test 1.  A learner's ``replay_start`` must lie below its capacity (``stmpc_ddpg_create``), and the members of a population share the
 capacity and the frames per step.  With capacity 200 (so that every ring wraps) and 12 steps of 24 frames no legal ``replay_start`` keeps a gate
 shut for the whole run: member 2 has the largest legal one, 199, so its gate is shut during steps 1 ... 8 -- it stays at 0 updates while members
 0 and 1 advance -- and opens at step 9, inside the run.  A gate that stays shut THROUGHOUT is test 2's member 3 (255 frames, replay_start 255).
 """
-import types
-
 import numpy as np
 import pytest
 
-from test_learner_pop import CAP, N_PER, STEPS, _assert_same, _bits, _snapshot
-from test_net_shapes import _dev, _push
-from test_net_shapes_cpu import SHAPES, _capi
-from test_td3_cpu import RING, SHIPPED, degenerate, random_td3_problem, td3_config
+from learner_testlib import (CAP, N_PER, RING, SHAPES, SHIPPED, STEPS, assert_same_td3 as _assert_same_td3, ddpg_view, degenerate, dev as _dev, push as _push,
+                             random_td3_problem, snapshot as _snapshot, stats_row as _stats_row, stub_env as _stub_env, td3_init as _init)
+from stmpc_testlib import (ACTOR_N_PER as VIEW_N, actor_eval as _eval, actor_settings as _settings, actor_states as _states, assert_steps_equal as _assert_steps_equal,
+                           bits as _bits, capi as _capi)
 
 SEEDS = (11, 12, 13)
 GAMMA, TAU, NOISE = (0.99, 0.95, 0.9), (0.005, 0.01, 0.02), (0.1, 0.2, 0.05)
@@ -42,38 +40,12 @@ def _same_slots(a, b, slots):
     return all(np.array_equal(_bits(a[s][k]), _bits(b[s][k])) for s in slots for k in learner.TENSORS)
 
 
-def _assert_same_td3(a, b, label):
-    """test_learner_pop._assert_same (the DDPG slots, all beta powers, counters, ring, statistics) plus critic 2's four slots."""
-    from rl_mpc_lanemerging_amd import learner
-    _assert_same(a, b, label)
-    assert a["params"]["beta_pow"].shape == b["params"]["beta_pow"].shape == (6,)
-    for slot in _capi().TD3_SLOTS:
-        for k in learner.TENSORS:
-            assert np.array_equal(_bits(a["params"][slot][k]), _bits(b["params"][slot][k])), (label, slot, k)
-
-
-def _stats_row(s, m=None):
-    keys = ("critic_loss", "critic2_loss", "mean_q", "mean_q2", "fill", "updates")
-    return [float(s[k] if m is None else s[k][m]) for k in keys]
-
-
 # ---- 1, 4: a population on a real env next to lone learners on its slices ------------------------------------------------------------------------------
 def _cfgs(shape, B, P, seeds_of=None, delay=DELAY, target_noise=TARGET_NOISE):
     from rl_mpc_lanemerging_amd import learner
     n_obs, h1, h2 = SHAPES[shape] if isinstance(shape, str) else shape
     return [learner.TD3Config(n_obs=n_obs, h1=h1, h2=h2, batch=B, capacity=CAP, replay_start=REPLAY_START[m], gamma=GAMMA[m], tau=TAU[m], noise=NOISE[m],
                               lr_q=LR_Q[m], lr_pi=LR_PI[m], target_noise=target_noise[m], noise_clip=NOISE_CLIP[m], policy_delay=delay[m]) for m in range(P)]
-
-
-def _init(shape, m):
-    """Member m's starting networks as an (actor, critic, critic 2) triple: torch's initialisation with last layers that are not zero."""
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, h2 = SHAPES[shape] if isinstance(shape, str) else shape
-    rng = np.random.default_rng(100 + m)
-    nets = (learner.init_net(n_obs + 1, h1, h2, rng), learner.init_net(n_obs + 2, h1, h2, rng), learner.init_net(n_obs + 2, h1, h2, rng))
-    for net in nets:
-        net["w2"] = rng.normal(0, 0.05, (1, h2)).astype(np.float32)
-    return nets
 
 
 def _run(gpu_ctx, shape, B, P, seeds=SEEDS, delay=DELAY, target_noise=TARGET_NOISE, alone=True):
@@ -154,10 +126,6 @@ def test_gpu_members_are_independent(gpu_ctx, restore_settings):
 
 
 # ---- synthetic populations: rings filled by push of rows, no env -------------------------------------------------------------------------------------
-def _stub_env(gpu_ctx, n, n_obs=20):
-    return types.SimpleNamespace(n=n, obs_dim=n_obs, continuous=True, ctx=gpu_ctx)
-
-
 def _triple(params):
     return (params["actor"], params["critic"], params["critic2"])
 
@@ -240,7 +208,7 @@ def test_gpu_population_of_one_equals_a_learner(gpu_ctx, restore_settings):
 
 
 def _snapshot_ring(gpu_ctx, L, stats):
-    """test_learner_pop._snapshot for a ring of RING rows."""
+    """learner_testlib.snapshot for a ring of RING rows."""
     sd = L.state_dict()
     return {"params": sd["params"], "counters": sd["counters"], "ring": gpu_ctx.ddpg_replay_read(L.handle, 0, RING), "stats": stats}
 
@@ -250,7 +218,6 @@ def _snapshot_ring(gpu_ctx, L, stats):
 def test_gpu_degenerate_population_is_a_ddpg_population(gpu_ctx, restore_settings):
     capi = _capi()
     from rl_mpc_lanemerging_amd import learner
-    from test_td3_cpu import ddpg_view
     raw = [random_td3_problem("padded", 48, seed=50 + m, gamma=GAMMA[m], tau=TAU[m], lr_q=LR_Q[m], lr_pi=LR_PI[m]) for m in range(3)]
     deg = [degenerate(c, p) + (r,) for c, p, r in raw]
     T = _synthetic(gpu_ctx, deg, seeds=SEEDS)
@@ -279,7 +246,6 @@ def test_gpu_member_handles(gpu_ctx, restore_settings):
     _capi()
     import torch
     from rl_mpc_lanemerging_amd import actor, learner
-    from test_actor_pop import N_PER as VIEW_N, _assert_steps_equal, _eval, _settings, _states
     problems = [random_td3_problem("padded", 48, seed=60 + m, policy_delay=1 + m) for m in range(3)]
     pop = _synthetic(gpu_ctx, problems, seeds=SEEDS)
     lone = [_lone(gpu_ctx, problems[m], SEEDS[m]) for m in range(3)]

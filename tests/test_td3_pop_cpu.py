@@ -4,13 +4,9 @@ Header, library and binding agree on the eight new entries and on STMPC_TD3_POP_
 touches the device, an env it cannot split, traffic or reward groups that are not one per member, a wrong ``n_obs`` and a plain ``DDPGConfig``.
 The GPU part is test_td3_pop.py.
 """
-import os
-import re
-
 import pytest
 
-from conftest import REPO
-from test_net_shapes_cpu import _capi
+from stmpc_testlib import capi as _capi, header_prototypes, header_text
 
 ENTRIES = {"stmpc_pop_td3_create", "stmpc_pop_td3_destroy", "stmpc_pop_td3_size", "stmpc_pop_td3_member", "stmpc_pop_td3_act_device",
            "stmpc_pop_td3_push_device", "stmpc_pop_td3_update_device", "stmpc_pop_td3_stats_device"}
@@ -20,14 +16,14 @@ def test_header_library_and_binding_agree_on_the_td3_population():
     import ctypes
     capi = _capi()
     lib = capi.load()
-    header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
-    declared = {name: args for name, args in re.findall(r"\b(stmpc_pop_td3_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}
+    header = header_text(flat=True)
+    declared = header_prototypes("stmpc_pop_td3_")
     assert set(declared) == ENTRIES == {n for n in capi.EXPORTS if n.startswith("stmpc_pop_td3_")}
     for name, args in declared.items():
         fn = getattr(lib, name)                                   # (AttributeError: the library does not export it)
         assert fn.argtypes is not None and len(fn.argtypes) == len(args.split(",")), name
     # act / push / update / stats have the DDPG population's signatures
-    ddpg = {name: args for name, args in re.findall(r"\b(stmpc_ddpg_pop_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}
+    ddpg = header_prototypes("stmpc_ddpg_pop_")
     for tail in ("act_device", "push_device", "update_device", "stats_device"):
         assert declared["stmpc_pop_td3_" + tail].replace("stmpc_td3_pop", "stmpc_ddpg_pop") == ddpg["stmpc_ddpg_pop_" + tail], tail
         assert getattr(lib, "stmpc_pop_td3_" + tail).argtypes == getattr(lib, "stmpc_ddpg_pop_" + tail).argtypes, tail

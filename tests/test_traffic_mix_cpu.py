@@ -11,7 +11,7 @@ import re
 import pytest
 
 from conftest import REPO
-from stmpc_testlib import pkg as _pkg
+from stmpc_testlib import header_struct_fields as _header_struct_fields, pkg as _pkg
 
 ENTRIES = {"stmpc_traffic_mix_env_reset_device": 12, "stmpc_traffic_mix_env_step_device": 15, "stmpc_traffic_mix_draw": 5}
 
@@ -127,7 +127,6 @@ def test_the_new_keywords_are_keyword_only_after_the_existing_ones():
 def test_header_library_and_binding_agree_on_the_traffic_mix_entries():
     _pkg()
     from rl_mpc_lanemerging_amd import _capi as capi
-    from test_host_cpu import _header_struct_fields
     lib = capi.load()
     header = " ".join(open(os.path.join(REPO, "include", "stmpc.h")).read().split())
     declared = {name: args for name, args in re.findall(r"\bint (stmpc_traffic_mix_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header)}

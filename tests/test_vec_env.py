@@ -12,16 +12,9 @@ import numpy as np
 import pytest
 
 from conftest import REPO, load_golden
+from stmpc_testlib import capi as _capi, header_struct_fields as _header_struct_fields
 
 ENVS = ("sumo-jerk-continuous-v0", "sumo-jerk-v0", "sumo-accel-v0")
-
-
-def _capi():
-    import rl_mpc_lanemerging_amd as pkg
-    if pkg.build.needs_build():
-        pkg.build.build()
-    from rl_mpc_lanemerging_amd import _capi
-    return _capi
 
 
 def _apply(S, keys, vals):
@@ -77,7 +70,6 @@ def test_action_twins_equal_the_reference(restore_settings):
 
 def test_env_cfg_mirror_and_episode_seed():
     capi = _capi()
-    from test_host_cpu import _header_struct_fields
     from rl_mpc_lanemerging_amd import vec_env
     ctype_of = {"double": ctypes.c_double, "int32_t": ctypes.c_int32, "double *": ctypes.POINTER(ctypes.c_double),
                 "stmpc_policy_features_cfg *": ctypes.POINTER(capi.FeaturesCfg)}
