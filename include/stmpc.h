@@ -21,6 +21,7 @@
  *   stmpc_policy_features_device <- dqn.get_state_vector_from_base_state  dqn.py:389-446 (+ the float32 cast and TimeFeature input of ddpg.py:41,84)
  *   stmpc_actor_eval_device   <- DDPGAgent.get_control                ddpg.py:83-87 (state vector + the pretrained policy network, one launch)
  *   stmpc_actor_view_ddpg     <- the closing `evaluate` of ddpg.train_ddpg_all_with_lr_drop (the model just trained, evaluated where it lies)
+ *   stmpc_qactor_eval_device  <- DQNAgent.get_control                 dqn.py:375-380 (state vector + Q-network + argmax + JERK_VALUES_DQN[a], one launch)
  *   stmpc_actor_pop_*         <- DDPGAgent.load + get_control for several MODEL_NAMEs (ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json), one launch
  *   stmpc_env_*               <- merge_gym.JerkEnv / ContinuousJerkEnv / AccelerationEnv  merge_gym.py:15-221 with the rewards of
  *                                dqn.get_reward_function (dqn.py:449-563, rl.py:168-174), batched on the SUMO-free world (stmpc_sim_*)
@@ -867,6 +868,46 @@ int  stmpc_dqn_per_enable(stmpc_dqn *learner, const stmpc_per_cfg *cfg);
 int  stmpc_dqn_per_tree_read(stmpc_dqn *learner, int64_t first, int64_t count, double *nodes);
 int  stmpc_dqn_per_last_device(stmpc_dqn *learner, int64_t *d_idx, float *d_td, float *d_weight, void *stream);
 int  stmpc_dqn_padded_read(stmpc_dqn *learner, int slot, float *values, int64_t count);
+
+/*
+ * A Q-network as the policy of the combined controller and of the first-step shield: DQNAgent.get_control (dqn.py:375-380) -- state vector -> Q ->
+ * argmax -> JERK_VALUES_DQN[a] -- for N states in ONE launch, behind which RLAgent.do_combined_control runs as it does behind the DDPG actor.
+ * (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8; no entry above changes what it computes.)  The
+ * forward pass and the first-maximum argmax are stmpc_dqn_act_device's own code on the same packed operands: Q, the index and the jerk are the bits
+ * that entry gives (eps = 0) on the input vectors stmpc_policy_features_device writes with time_feature = 0.
+ *   stmpc_qactor_create   (dqn.py:375-380 with DQNAgent.load's network) from HOST row-major tensors as torch stores them: w0 [h1][n_in], b0 [h1],
+ *                   w1 [n_actions][h1], b1 [n_actions], and the action table action_values [n_actions] (index -> what the env executes).  The
+ *                   tensors go through the learner's own network builder and re-packing kernel: bit-identical to a stmpc_dqn loaded with them.
+ *                   STMPC_EINVAL for a NULL argument, n_in outside 1 ... 31, h1 outside 1 ... 1024, n_actions outside 1 ... STMPC_ENV_MAX_ACTIONS,
+ *                   a mode that is neither STMPC_QACTOR_JERK nor STMPC_QACTOR_ACCELERATION, a table entry that is not finite.  Synchronises
+ *   stmpc_qactor_view_dqn (dqn.py:375-380 on the agent being trained) a BORROWED policy whose network ALIASES the learner's online (target = 0) or
+ *                   target (target = 1) Q-network: the learner keeps both packed after every update, so no copy is made, and an evaluation ordered
+ *                   after an update ON THE SAME STREAM sees the update.  It owns its action table alone; stmpc_qactor_destroy frees nothing of the
+ *                   learner's; destroy it before the learner.  Evaluating reads the network only: no counter, ticket or workspace of the learner is
+ *                   touched.  STMPC_EINVAL for a NULL argument, target not 0 or 1, n_actions different from the learner's, a bad mode or table
+ *   stmpc_qactor_set_limits   (merge_gym.py:196-204) acceleration mode's constants: Settings.TICK_LENGTH, MINIMUM_NEGATIVE_JERK, MAXIMUM_POSITIVE_JERK
+ *                   (tick_length > 0, minimum <= maximum, all finite, else STMPC_EINVAL).  Not read in jerk mode
+ *   stmpc_qactor_eval_device  (dqn.py:375-380) d_jerk fp64 [N], required; optional (NULL: not written) d_action int32 [N], d_q float32 [N][n_actions],
+ *                   d_feat float32 [N][feat_stride].  STMPC_QACTOR_JERK: jerk = action_values[a].  STMPC_QACTOR_ACCELERATION: jerk =
+ *                   clip((action_values[a] - the state's ego acceleration) / tick_length, minimum_negative_jerk, maximum_positive_jerk) in fp64 --
+ *                   AccelerationEnv._do_action's projected jerk before its speed clamp, with the state's own acceleration for the env's previous
+ *                   one; the reference has no evaluator for that env, the rule is this library's.  The state arguments, `step` and the rows of
+ *                   finished rollouts are stmpc_actor_eval_device's (step > 1 needs a rollout of N states in the context; without a time feature
+ *                   every row is evaluated alike).  STMPC_EINVAL, before anything is launched, for a NULL ctx / qactor / cfg / required pointer,
+ *                   N < 1, cfg->time_feature set, stmpc_policy_features_len(cfg) != n_in, feat_stride < n_in with d_feat given, a context on another
+ *                   device than the policy's, acceleration mode without stmpc_qactor_set_limits.  Asynchronous
+ */
+#define STMPC_QACTOR_JERK 0
+#define STMPC_QACTOR_ACCELERATION 1
+typedef struct stmpc_qactor stmpc_qactor;
+int  stmpc_qactor_create(stmpc_ctx *ctx, int n_in, int h1, int n_actions, const float *w0, const float *b0, const float *w1, const float *b1,
+                         const double *action_values, int mode, stmpc_qactor **out);
+int  stmpc_qactor_view_dqn(stmpc_dqn *learner, int target, const double *action_values, int n_actions, int mode, stmpc_qactor **out);
+void stmpc_qactor_destroy(stmpc_qactor *qactor);
+int  stmpc_qactor_set_limits(stmpc_qactor *qactor, double tick_length, double minimum_negative_jerk, double maximum_positive_jerk);
+int  stmpc_qactor_eval_device(stmpc_ctx *ctx, const stmpc_qactor *qactor, const stmpc_policy_features_cfg *cfg, int N, int Kmax, int step,
+                              const double *d_cur_ego4, const int32_t *d_k_count, const double *d_cur_other_x, const double *d_cur_other_v,
+                              const double *d_cur_other_a, float *d_feat, int feat_stride, int32_t *d_action, float *d_q, double *d_jerk, void *stream);
 
 /*
  * Actors straight from learners, and a population of actors evaluated in one launch.  The reference's workflow ends a training with an evaluation

@@ -293,6 +293,7 @@ EXPORTS = (
     "stmpc_dqn_push_device", "stmpc_dqn_act_device", "stmpc_dqn_update_device", "stmpc_dqn_grads_device", "stmpc_dqn_targets_device",
     "stmpc_dqn_gather_device", "stmpc_dqn_stats_device", "stmpc_dqn_per_enable", "stmpc_dqn_per_tree_read", "stmpc_dqn_per_last_device",
     "stmpc_dqn_padded_read",
+    "stmpc_qactor_create", "stmpc_qactor_view_dqn", "stmpc_qactor_destroy", "stmpc_qactor_set_limits", "stmpc_qactor_eval_device",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
@@ -321,6 +322,7 @@ TD3_SLOTS = ("critic2", "critic2_target", "critic2_m", "critic2_v")     # STMPC_
 DQN_SLOTS = ("q", "q_target", "q_m", "q_v")     # STMPC_DQN_Q ... STMPC_DQN_Q_V
 DQN_GRAD = 4                          # STMPC_DQN_GRAD: the gradient, for dqn_padded_read
 DQN_ACTION_COL = 66                   # the replay row's action column of a DQN learner
+QACTOR_MODES = {"jerk": 0, "acceleration": 1}      # STMPC_QACTOR_JERK, STMPC_QACTOR_ACCELERATION
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
 REC_HDR, REC_NQ, REC_MAX_DEPTH, REC_MAX_EDGES = 10, 4, 64, 32      # STMPC_REC_HDR, STMPC_REC_NQ, STMPC_REC_MAX_DEPTH, STMPC_REC_MAX_EDGES
 REC_COLUMNS = ("tick", "x", "y", "v", "a", "s", "k", "cmd", "takeover", "jerk")      # the first STMPC_REC_HDR columns of a record
@@ -513,6 +515,12 @@ def load():
     lib.stmpc_dqn_per_tree_read.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
     lib.stmpc_dqn_per_last_device.argtypes = [vp, vp, vp, vp, vp]
     lib.stmpc_dqn_padded_read.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_qactor_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, dp, C.c_int, C.POINTER(vp)]
+    lib.stmpc_qactor_view_dqn.argtypes = [vp, C.c_int, dp, C.c_int, C.c_int, C.POINTER(vp)]
+    lib.stmpc_qactor_destroy.argtypes = [vp]
+    lib.stmpc_qactor_destroy.restype = None
+    lib.stmpc_qactor_set_limits.argtypes = [vp, C.c_double, C.c_double, C.c_double]
+    lib.stmpc_qactor_eval_device.argtypes = [vp, vp, C.POINTER(FeaturesCfg), C.c_int, C.c_int, C.c_int] + [vp] * 6 + [C.c_int, vp, vp, vp, vp]
     lib.stmpc_actor_view_ddpg.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_destroy.argtypes = [vp]
@@ -1154,6 +1162,40 @@ class Context:
         self._chk(self._lib.stmpc_dqn_padded_read(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
         o = np.cumsum([0, 32 * h1p, h1p, Ap * h1p, Ap])
         return {"w0": flat[o[0]:o[1]].reshape(h1p, 32), "b0": flat[o[1]:o[2]], "w1": flat[o[2]:o[3]].reshape(Ap, h1p), "b1": flat[o[3]:o[4]]}
+
+    # -- a Q-network as a policy (stmpc_qactor_*): DQNAgent.get_control, dqn.py:375-380 ------------------------
+    def qactor_create(self, net, action_values, mode=0):
+        """Pack and upload a Q-network (dict of numpy float32 arrays w0, b0, w1, b1 as torch stores them) with its action table (fp64 [A]);
+        ``mode``: a ``QACTOR_MODES`` code.  Returns an opaque handle for ``qactor_eval_device`` / ``qactor_destroy``."""
+        f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+        w0, b0, w1, b1 = f32(net["w0"]), f32(net["b0"]).reshape(-1), f32(net["w1"]), f32(net["b1"]).reshape(-1)
+        if w0.ndim != 2 or w1.ndim != 2 or b0.size != w0.shape[0] or w1.shape[1] != w0.shape[0] or b1.size != w1.shape[0]:
+            raise ValueError("the net's tensors are not w0 [h1][n_in], b0 [h1], w1 [A][h1], b1 [A]")
+        table = np.ascontiguousarray(action_values, dtype=np.float64).reshape(-1)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_qactor_create(self._h, int(w0.shape[1]), int(w0.shape[0]), int(table.size), fp(w0), fp(b0), fp(w1), fp(b1),
+                                                table.ctypes.data_as(C.POINTER(C.c_double)), int(mode), C.byref(h)))
+        return h
+
+    def qactor_view_dqn(self, learner_handle, action_values, target=False, mode=0):
+        """A borrowed policy aliasing the DQN learner's online (or target) network: no copy; ``qactor_destroy`` it before the learner goes."""
+        table = np.ascontiguousarray(action_values, dtype=np.float64).reshape(-1)
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_qactor_view_dqn(learner_handle, int(bool(target)), table.ctypes.data_as(C.POINTER(C.c_double)), int(table.size), int(mode), C.byref(h)))
+        return h
+
+    def qactor_destroy(self, handle):
+        self._lib.stmpc_qactor_destroy(handle)
+
+    def qactor_set_limits(self, handle, tick_length, minimum_negative_jerk, maximum_positive_jerk):
+        """Acceleration mode's constants (Settings.TICK_LENGTH, MINIMUM_NEGATIVE_JERK, MAXIMUM_POSITIVE_JERK)."""
+        self._chk(self._lib.stmpc_qactor_set_limits(handle, float(tick_length), float(minimum_negative_jerk), float(maximum_positive_jerk)))
+
+    def qactor_eval_device(self, handle, fcfg, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_feat, feat_stride, d_action, d_q, d_jerk, stream=0):
+        """One launch: state vectors + Q-network + first argmax + action table -> jerk [N] fp64 (``stmpc_qactor_eval_device``)."""
+        self._chk(self._lib.stmpc_qactor_eval_device(self._h, handle, C.byref(fcfg), int(N), int(Kmax), int(step), d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa,
+                                                     d_feat, int(feat_stride), d_action, d_q, d_jerk, stream))
 
     # -- TD3 learner (stmpc_td3_*): a DDPG learner as base plus critic 2 ------------------------
     def td3_create(self, cfg):

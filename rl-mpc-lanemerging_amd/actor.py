@@ -20,12 +20,16 @@ two interchangeable engines:
 Parity: the 20 state-vector entries and the network's weights are the reference's own (pinned by ``golden_combined_real.npz``); the
 float32 cast and the TimeFeature input restate ``autonomous-learning-library`` 0.5.3 (requirements.txt:10), which is absent from the
 reference checkout -- parity unpinned for those two steps, and the suite's ``test_actor.py`` measures how much the decisions depend on them.
+
+``DQNActor`` is the same for the reference's second agent, ``DQNAgent.get_control`` (dqn.py:375-380): state vector (no time feature) -> Q ->
+``argmax`` -> the action table, one launch (``k_qactor_eval``), from a ``learner.DQNLearner`` where it lies or from its exported file.
 """
 import os
 
 import numpy as np
 
 from . import _capi
+from .config import Settings
 
 ACTOR_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")      # package data: the reference's pretrained_models/*/policy.pt as tensors
 #: MODEL_NAME of the shipped evaluation configs -> exported tensor file (configs/combined_<traffic>_1.json:4)
@@ -284,6 +288,121 @@ class ActorPopulation:
                                        cur_ov.data_ptr(), cur_oa.data_ptr() if cur_oa is not None else 0, self.evals.data_ptr(),
                                        self.feat.data_ptr() if self.keep_features else 0, self.flen, self.jerk.data_ptr(), stream)
         return self.jerk
+
+
+class DQNActor:
+    """The reference's second agent as a policy: ``DQNAgent.get_control`` (dqn.py:375-380) -- state vector -> Q -> ``argmax`` ->
+    ``JERK_VALUES_DQN[a]`` -- for ``n`` states in ONE launch (``k_qactor_eval``, csrc/stmpc_qactor_kernels.hpp), with ``DDPGActor``'s call:
+    ``policy(step, cur_ego4, k, cur_ox, cur_ov, cur_oa) -> jerk[n]`` (fp64, on the device), so ``combined.decide_batch_device`` and
+    ``episodes.EpisodeRunner(controller="combined" | "first_step")`` take it as they are.
+
+    ``source``: a file written by ``learner.DQNLearner.export_q`` (w0, b0, w1, b1, action_values); ``action_values`` replaces the file's table.
+    ``mode``: "jerk" (the table holds jerks: sumo-jerk-v0) or "acceleration" (it holds accelerations: sumo-accel-v0; the jerk is then
+    ``clip((table[a] - ego acceleration) / TICK_LENGTH, MINIMUM_NEGATIVE_JERK, MAXIMUM_POSITIVE_JERK)`` in fp64 -- ``AccelerationEnv._do_action``'s
+    projected jerk before its speed clamp, with the state's own acceleration for the env's previous one.  The reference has no evaluator for that
+    env: the rule is this project's; ``q_policy_host`` is its host twin).  The constants are read from ``S`` when the actor is built.
+
+    The network has no time feature: ``reset`` does nothing.  ``.action`` (int32 [n]) is filled by every call; ``keep_features`` / ``keep_q`` fill
+    ``.feat`` (float32 [n][n_in]) and ``.q`` (float32 [n][A]) too.  Q, the index and the jerk are bit for bit what ``DQNLearner.act`` gives on the
+    same input vectors: the kernel runs the learner's own forward pass and argmax."""
+
+    MODES = tuple(_capi.QACTOR_MODES)
+
+    def __init__(self, source, n, ctx, S, mode="jerk", action_values=None):
+        with np.load(os.fspath(source)) as z:
+            net = {k: np.array(z[k], dtype=np.float32) for k in ("w0", "b0", "w1", "b1")}
+            table = np.array(z["action_values"], dtype=np.float64) if action_values is None else action_values
+        self._setup(n, ctx, S, mode, table, (int(net["w0"].shape[1]), int(net["w0"].shape[0]), int(net["w1"].shape[0])))
+        self.name, self.learner, self.target = os.fspath(source), None, False
+        self.handle = ctx.qactor_create(net, self.action_values, _capi.QACTOR_MODES[self.mode])
+        self._limits(S)
+
+    @classmethod
+    def from_learner(cls, learner, n, ctx, S, target=False, mode=None):
+        """A zero-copy VIEW of a ``learner.DQNLearner``'s online (``target=True``: target) Q-network (``stmpc_qactor_view_dqn``): the learner keeps
+        both packed for the kernel after every update, so nothing is exported or uploaded, and an evaluation queued after an update on the same
+        stream sees the update.  The table is ``learner.action_values``; ``mode`` defaults to the kind of env the learner was built from
+        ("acceleration" for sumo-accel-v0, else -- and without an env -- "jerk").  Evaluating changes nothing of the learner's.  The view holds
+        the learner, so the learner cannot be collected first."""
+        self = cls.__new__(cls)
+        if mode is None:
+            mode = "acceleration" if getattr(learner, "env_id", None) == "sumo-accel-v0" else "jerk"
+        c = learner.cfg
+        self._setup(n, ctx, S, mode, learner.action_values, (c.n_obs, c.h1, c.n_actions))
+        self.learner, self.target = learner, bool(target)
+        self.name = "view of %r (%s network)" % (learner, "target" if target else "online")
+        self.handle = ctx.qactor_view_dqn(learner.handle, self.action_values, self.target, _capi.QACTOR_MODES[self.mode])
+        self._limits(S)
+        return self
+
+    def _setup(self, n, ctx, S, mode, table, shape):
+        import torch
+        self.handle = None
+        self.torch, self.ctx, self.n, self.engine, self.dtype, self.shape = torch, ctx, int(n), "hip", torch.float32, shape
+        if self.n < 1:
+            raise ValueError("n must be positive")
+        if mode not in _capi.QACTOR_MODES:
+            raise ValueError("mode must be one of %s, not %r" % (", ".join(map(repr, _capi.QACTOR_MODES)), mode))
+        self.mode = mode
+        self.action_values = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+        if self.action_values.size != shape[2]:
+            raise ValueError("the action table has %d entries, the network %d actions" % (self.action_values.size, shape[2]))
+        if not np.isfinite(self.action_values).all():
+            raise ValueError("the action table has entries that are not finite")
+        self.fcfg = _capi.FeaturesCfg.from_settings(S, time_feature=False)
+        self.flen = (self.fcfg.cars_ahead + self.fcfg.cars_behind) * (4 if self.fcfg.use_acceleration else 3) + 4
+        if self.flen != shape[0]:
+            raise ValueError("the Q-network takes %d inputs, the state vector of these settings has %d" % (shape[0], self.flen))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.feat = torch.empty(self.n, self.flen, dtype=torch.float32, device=dev)
+        self.q = torch.empty(self.n, shape[2], dtype=torch.float32, device=dev)
+        self.action = torch.empty(self.n, dtype=torch.int32, device=dev)
+        self.jerk = torch.empty(self.n, dtype=torch.float64, device=dev)
+        self.keep_features = self.keep_q = False
+
+    def _limits(self, S):
+        self.limits = (float(S.TICK_LENGTH), float(S.MINIMUM_NEGATIVE_JERK), float(S.MAXIMUM_POSITIVE_JERK))
+        if self.mode == "acceleration":
+            self.ctx.qactor_set_limits(self.handle, *self.limits)
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                self.ctx.qactor_destroy(self.handle)
+            except Exception:
+                pass
+            self.handle = None
+
+    def reset(self, mask=None):
+        """Nothing: there are no per-episode evaluation counters without a time feature."""
+
+    def __call__(self, step, cur_ego4, k, cur_ox, cur_ov, cur_oa):
+        _check_rows(self.n, cur_ego4, k, cur_ox, cur_ov, cur_oa)
+        stream = self.torch.cuda.current_stream().cuda_stream
+        self.ctx.qactor_eval_device(self.handle, self.fcfg, self.n, cur_ox.shape[1], step, cur_ego4.data_ptr(), k.data_ptr(), cur_ox.data_ptr(), cur_ov.data_ptr(),
+                                    cur_oa.data_ptr() if cur_oa is not None else 0, self.feat.data_ptr() if self.keep_features else 0, self.flen,
+                                    self.action.data_ptr(), self.q.data_ptr() if self.keep_q else 0, self.jerk.data_ptr(), stream)
+        return self.jerk
+
+
+def q_policy_host(net, feat, action_values, mode, ego_acc=None, S=Settings, dtype=np.float64):
+    """The host twin of ``DQNActor`` in numpy (CPU suite), for input vectors ``feat`` [n][n_in] and a net {w0, b0, w1, b1}: (Q [n][A] in
+    ``dtype``, the first maximum's index int64 [n], the jerk fp64 [n]).  ``mode`` "acceleration" needs ``ego_acc`` [n] (the states' ego
+    accelerations, fp64) and reads TICK_LENGTH, MINIMUM_NEGATIVE_JERK and MAXIMUM_POSITIVE_JERK of ``S`` (default: the package's Settings)."""
+    if mode not in _capi.QACTOR_MODES:
+        raise ValueError("mode must be one of %s, not %r" % (", ".join(map(repr, _capi.QACTOR_MODES)), mode))
+    f = lambda a: np.asarray(a, dtype=dtype)
+    q = np.maximum(f(feat) @ f(net["w0"]).T + f(net["b0"]), 0) @ f(net["w1"]).T + f(net["b1"])
+    table = np.asarray(action_values, dtype=np.float64).reshape(-1)
+    if table.size != q.shape[1]:
+        raise ValueError("the action table has %d entries, the network %d actions" % (table.size, q.shape[1]))
+    idx = np.argmax(q, axis=1)                                      # (numpy's argmax returns the first maximum, like torch's)
+    jerk = table[idx]
+    if mode == "acceleration":
+        if ego_acc is None:
+            raise ValueError("acceleration mode needs the states' ego accelerations (ego_acc)")
+        jerk = np.clip((jerk - np.asarray(ego_acc, dtype=np.float64)) / float(S.TICK_LENGTH), float(S.MINIMUM_NEGATIVE_JERK), float(S.MAXIMUM_POSITIVE_JERK))
+    return q, idx, jerk
 
 
 def forward_host(w, feat, dtype=np.float32):

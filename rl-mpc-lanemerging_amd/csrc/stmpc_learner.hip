@@ -4,7 +4,7 @@
 // ddpg_refresh), the TD3 learner on a DDPG learner as base plus critic 2 (stmpc_td3_*, td3_refresh), prioritised replay for the two (stmpc_per_*), their
 // populations on one skeleton (struct PopCore; stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_per_*; pop_upload, td3_pop_upload), actors that view a
 // learner's networks and their population (stmpc_actor_view_ddpg, stmpc_actor_pop_*), and the DQN learner for the discrete envs (stmpc_dqn_*), which
-// holds a replay store, one network and one workspace of its own.  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
+// holds a replay store, one network and one workspace of its own, with the Q-network as a policy behind it (stmpc_qactor_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
 #include "stmpc_per_kernels.hpp"
@@ -14,6 +14,7 @@
 #include "stmpc_per_pop_kernels.hpp"
 #include "stmpc_actor_pop_kernels.hpp"
 #include "stmpc_dqn_kernels.hpp"
+#include "stmpc_qactor_kernels.hpp"
 
 // ---- the parts every learner is made of ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -1190,6 +1191,126 @@ int stmpc_dqn_padded_read(stmpc_dqn *t, int slot, float *values, int64_t count) 
     if (!t || !values || slot < 0 || slot > STMPC_DQN_GRAD) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
     if (count != dq_nparam(t->h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
     return read_back(t->rp.device, values, slot == STMPC_DQN_GRAD ? t->dev.base.q.g : net_slot(t->dev.base.q, slot), (size_t)count * sizeof(float));
+}
+
+}  // extern "C"
+
+// ---- a Q-network as a policy (stmpc_qactor_*): DQNAgent.get_control for N states in one launch; kernel in stmpc_qactor_kernels.hpp ------------------
+struct stmpc_qactor {
+    int device = 0;
+    const stmpc_dqn *learner = nullptr;     // a view (stmpc_qactor_view_dqn): the network is the learner's, read through its struct at every evaluation
+    int target = 0, mode = 0, n_in = 0, A = 0;
+    bool limits = false;                    // stmpc_qactor_set_limits was called
+    double tick = 0, jerk_min = 0, jerk_max = 0;
+    DqnDev dev{};                           // a created actor: base.q (its own network), the shape and the counters ddpg_repack's kernel reads
+    DevBuf net[11], cnt, table;             // (net, cnt: empty for a view)
+    size_t lds = 0;
+};
+
+namespace {
+int qactor_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling;
+    return raise_dynamic_lds((const void *)k_qactor_eval, "k_qactor_eval", ceiling, device, lds);
+}
+// what create and view share: the mode, the table (checked, then uploaded into q), the kernel's dynamic LDS
+int qactor_check_table(const double *action_values, int n_actions, int A, int mode) {
+    if (mode != STMPC_QACTOR_JERK && mode != STMPC_QACTOR_ACCELERATION) return fail(STMPC_EINVAL, "mode must be STMPC_QACTOR_JERK or STMPC_QACTOR_ACCELERATION");
+    if (n_actions != A) return fail(STMPC_EINVAL, "the action table has " + std::to_string(n_actions) + " entries, the network " + std::to_string(A) + " actions");
+    for (int i = 0; i < A; ++i)
+        if (!std::isfinite(action_values[i])) return fail(STMPC_EINVAL, "action table entry " + std::to_string(i) + " is not finite");
+    return STMPC_OK;
+}
+int qactor_finish(stmpc_qactor *q, const double *action_values, stmpc_qactor **out) {
+    int rc = upload(q->table, action_values, (size_t)q->A);
+    if (!rc) rc = qactor_raise_lds(q->device, q->lds);
+    if (rc) { stmpc_qactor_destroy(q); return rc; }
+    *out = q;
+    return STMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_qactor_create(stmpc_ctx *c, int n_in, int h1, int n_actions, const float *w0, const float *b0, const float *w1, const float *b1,
+                        const double *action_values, int mode, stmpc_qactor **out) {
+    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (!w0 || !b0 || !w1 || !b1 || !action_values) return fail(STMPC_EINVAL, "NULL weight or table pointer");
+    if (n_actions < 1 || n_actions > STMPC_ENV_MAX_ACTIONS) return fail(STMPC_EINVAL, "n_actions must be in 1 ... " + std::to_string(STMPC_ENV_MAX_ACTIONS));
+    if (n_in < 1 || n_in > AT_KIN - 1 || h1 < 1 || h1 > 1024) return fail(STMPC_EINVAL, "Q-network shape out of range (n_in <= 31, hidden width <= 1024)");
+    TRY(qactor_check_table(action_values, n_actions, n_actions, mode));
+    HIPCHK(hipSetDevice(c->device));
+    const int h1p = (h1 + 15) & ~15, Ap = (n_actions + 15) & ~15;
+    const size_t lds = ddpg_tile_bytes(h1p, Ap);
+    if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, "Q-network too wide for one workgroup's LDS");
+    stmpc_qactor *q = new stmpc_qactor();
+    q->device = c->device; q->mode = mode; q->n_in = n_in; q->A = n_actions; q->lds = lds;
+    // the learner's own path: net_build's buffers, the slot's segments into the padded layout, k_dqn_adam's re-packing
+    DdpgDev &d = q->dev.base;
+    d.n_obs = n_in; d.h1 = h1; d.h2 = n_actions; d.h1p = h1p; d.h2p = Ap;
+    q->dev.A = n_actions; q->dev.Ap = Ap; q->dev.target_period = 1;
+    int rc = net_build(q->net, d.q, n_in, h1p, Ap);
+    if (!rc) rc = ddpg_zero(q->cnt, DG_NCNT * sizeof(long long));
+    if (!rc) {
+        d.cnt = q->cnt.as<long long>();
+        const std::vector<Seg> lay = slot_layout(n_in, h1, n_actions, h1p, Ap, false);
+        std::vector<float> flat;
+        flat.insert(flat.end(), w0, w0 + (size_t)h1 * n_in);
+        flat.insert(flat.end(), b0, b0 + h1);
+        flat.insert(flat.end(), w1, w1 + (size_t)n_actions * h1);
+        flat.insert(flat.end(), b1, b1 + n_actions);
+        const int ablocks = make_grid(16, h1p, Ap, false).ablocks;
+        rc = slot_set(c->device, lay, (size_t)dg_nparam(h1p, Ap), d.q.w, flat.data(), (int64_t)flat.size(), true,
+                      [&] { hipLaunchKernelGGL(k_dqn_adam, dim3(ablocks), dim3(256), 0, (hipStream_t)0, q->dev, 0.f, 1, 1); });
+    }
+    if (rc) { stmpc_qactor_destroy(q); return rc; }
+    return qactor_finish(q, action_values, out);
+}
+
+int stmpc_qactor_view_dqn(stmpc_dqn *t, int target, const double *action_values, int n_actions, int mode, stmpc_qactor **out) {
+    if (!t || !action_values || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (target != 0 && target != 1) return fail(STMPC_EINVAL, "target must be 0 (online network) or 1 (target network)");
+    TRY(qactor_check_table(action_values, n_actions, t->cfg.n_actions, mode));
+    HIPCHK(hipSetDevice(t->rp.device));
+    stmpc_qactor *q = new stmpc_qactor();   // owns its table alone: destroying it frees nothing of the learner's
+    q->device = t->rp.device; q->learner = t; q->target = target; q->mode = mode; q->n_in = t->cfg.n_obs; q->A = t->cfg.n_actions; q->lds = t->lds;
+    return qactor_finish(q, action_values, out);
+}
+
+void stmpc_qactor_destroy(stmpc_qactor *q) {
+    if (!q) return;
+    (void)hipSetDevice(q->device);
+    delete q;
+}
+
+int stmpc_qactor_set_limits(stmpc_qactor *q, double tick_length, double minimum_negative_jerk, double maximum_positive_jerk) {
+    if (!q) return fail(STMPC_EINVAL, "NULL argument");
+    if (!(tick_length > 0) || !std::isfinite(tick_length) || !std::isfinite(minimum_negative_jerk) || !std::isfinite(maximum_positive_jerk) ||
+        !(minimum_negative_jerk <= maximum_positive_jerk))
+        return fail(STMPC_EINVAL, "tick_length must be positive and the jerk limits ordered, all finite");
+    q->tick = tick_length; q->jerk_min = minimum_negative_jerk; q->jerk_max = maximum_positive_jerk; q->limits = true;
+    return STMPC_OK;
+}
+
+int stmpc_qactor_eval_device(stmpc_ctx *c, const stmpc_qactor *q, const stmpc_policy_features_cfg *f, int N, int Kmax, int step, const double *d_cur_ego4,
+                             const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa, float *d_feat, int feat_stride,
+                             int32_t *d_action, float *d_q, double *d_jerk, void *stream) {
+    if (!c || !q || !f) return fail(STMPC_EINVAL, "NULL argument");
+    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
+    if (f->time_feature) return fail(STMPC_EINVAL, "a Q-network has no time feature: the features cfg must have time_feature = 0");
+    if (q->mode == STMPC_QACTOR_ACCELERATION && !q->limits)
+        return fail(STMPC_EINVAL, "acceleration mode needs the tick length and the jerk limits (stmpc_qactor_set_limits)");
+    FeatCfg fc;
+    TRY(actor_eval_checks(c, q->device, q->n_in, f, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, nullptr, d_feat, feat_stride, d_jerk, &fc));
+    const int *live;
+    TRY(rollout_live(c, N, step, &live));
+    HIPCHK(hipSetDevice(c->device));
+    QActorOut o{q->table.as<double>(), q->tick, q->jerk_min, q->jerk_max, q->mode == STMPC_QACTOR_ACCELERATION, feat_stride, d_feat, d_action, d_q, d_jerk};
+    hipLaunchKernelGGL(k_qactor_eval, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), q->lds, (hipStream_t)stream, fc, q->learner ? q->learner->dev : q->dev,
+                       q->learner ? q->target : 0, N, Kmax, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, o);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
 }
 
 }  // extern "C"

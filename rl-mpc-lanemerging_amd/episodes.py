@@ -205,7 +205,7 @@ class EpisodeRunner:
         if self.control is not None and controller != "combined":
             raise ValueError("control groups are settings of the combined controller, not of %r" % (controller,))
         if controller == "first_step" and policy is None:
-            raise ValueError("the first-step controller shields a policy's proposal: give one (an actor.DDPGActor or an actor.ActorPopulation)")
+            raise ValueError("the first-step controller shields a policy's proposal: give one (an actor.DDPGActor, an actor.DQNActor or an actor.ActorPopulation)")
         self.C, self.n_per_cell = _check_control(n, self.control, self.traffic, policy) if self.control is not None else (0, 0)
         self.G, self.n_per_group = (_check_traffic(n, self.traffic, policy, _capi.SOLVER_GROUPS_MAX if self.solver is not None else None)
                                     if self.traffic is not None else (0, 0))

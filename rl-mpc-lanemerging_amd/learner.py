@@ -1083,6 +1083,7 @@ class DQNLearner(_Learner):
                 raise ValueError("DQN needs " + name)
         # the env's table, index -> jerk or acceleration (what its cfg hands the library); without an env the indices stand for themselves
         self.action_values = np.array(env.cfg._actions, dtype=np.float64) if env is not None else np.arange(A, dtype=np.float64)
+        self.env_id = getattr(env, "env_id", None)                    # (what actor.DQNActor.from_learner's default mode reads; None without an env)
         if self.action_values.shape != (A,):
             raise ValueError("the env's action table has %d entries, its action space %d" % (self.action_values.size, A))
         import torch
@@ -1260,3 +1261,25 @@ def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=1
     rep = stats.get("report")
     return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),
             "reports": rep.by_member(pop.P, traffic) if rep is not None else None}
+
+
+def evaluate_dqn(source, n, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):
+    """The reference's evaluation of its DQN agent -- ``DQNAgent.get_control`` (dqn.py:375-380) behind ``RLAgent.do_combined_control`` -- for ``n``
+    merge episodes in one run, with an ``actor.DQNActor`` as the policy.  ``source``: a ``DQNLearner`` (a zero-copy view of its online network as it
+    is on the device), a file written by ``DQNLearner.export_q``, or a ``DQNActor`` built for ``n`` states on ``ctx``.
+    ``ctx``: the evaluation's context; by default a new one (a ``DQNActor``'s own), because a context holds one world and the training env has its
+    own.  ``controller``: "combined", or "first_step" for the one-step shield of ``first_step.py``.  ``traffic``: None, or the traffic groups of
+    ``episodes.EpisodeRunner``.  Returns ``run_episodes``' columns (with ``report`` when ``record`` is given)."""
+    from . import episodes
+    if controller not in ("combined", "first_step"):
+        raise ValueError("a DQN policy is evaluated under 'combined' or 'first_step', not %r" % (controller,))
+    if isinstance(source, _actor.DQNActor):
+        policy = source
+        if policy.n != int(n):
+            raise ValueError("n = %d, the DQNActor was built for %d states" % (n, policy.n))
+        ctx = ctx if ctx is not None else policy.ctx
+    else:
+        ctx = ctx if ctx is not None else _capi.Context(-1)
+        policy = _actor.DQNActor.from_learner(source, n, ctx, Settings) if isinstance(source, DQNLearner) else _actor.DQNActor(source, n, ctx, Settings)
+    return episodes.run_episodes(int(n), seed=seed, controller=controller, policy=policy, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
+                                 traffic=traffic)
