@@ -870,6 +870,55 @@ int  stmpc_dqn_per_last_device(stmpc_dqn *learner, int64_t *d_idx, float *d_td, 
 int  stmpc_dqn_padded_read(stmpc_dqn *learner, int slot, float *values, int64_t count);
 
 /*
+ * A population of DQN learners: what the populations of DDPG and TD3 learners above are to stmpc_ddpg and stmpc_td3, for stmpc_dqn.  P independent
+ * DQN learners -- each its own ring, Q-network, target, Adam state, counters, seed and constants, double_dqn, clip_targets, target_period and
+ * replay_start included -- share one discrete-action vector environment and advance with ONE launch per kernel: three launches per update whatever
+ * P is and whatever the members' counters say, five when at least one member is prioritised; acting, pushing and the statistics are one launch
+ * each.  Member m owns rows [m * n_per_member, (m + 1) * n_per_member) of the step tensors and is bit-identical to a lone stmpc_dqn with its cfg
+ * given its slice.  The comparisons the reference runs its hand-written trainer for (TRAIN_DQN: DQNAgent._train dqn.py:257-359) -- double against
+ * plain targets, clipped against unclipped ones, TARGET_NET_FREEZE_PERIOD, the epsilon schedule, prioritised against uniform replay, seeds, traffic
+ * types, reward settings -- are then one run.  (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8;
+ * no entry above changes what it computes.)  The entries read stmpc_pop_dqn_*: the prefixes stmpc_dqn_ and stmpc_pop_per_ are closed sets.
+ *   pop_create      (dqn.py:257-359) P = 1 ... STMPC_DQN_POP_MAX configs that share n_obs, h1, n_actions, batch and capacity (the launch shapes are
+ *                   common); everything else may differ per member.  Each member is made by the lone create, whose refusals apply per member
+ *   pop_destroy, pop_size   (dqn.py:257-359) the population with its members; the member count (0 for NULL)
+ *   pop_member      (dqn.py:257-359) the m-th member as a BORROWED stmpc_dqn, valid until pop_destroy (never destroy it): set / get_params, set /
+ *                   get_state, grads_device, targets_device, gather_device, stats_device, padded_read, per_tree_read, per_last_device and
+ *                   stmpc_qactor_view_dqn work on it as on a lone learner, as do the lone act, push and update entries.  The lone per_enable refuses
+ *   pop_act_device  (dqn.py:257-359, do_dqn_control dqn.py:661-670) the lone act_device per member: d_action int32 [P * n_per_member]; eps HOST fp64
+ *                   [n_eps], n_eps = P, one value per member (it travels as a kernel argument).  Member m's exploration hash is keyed by its own
+ *                   seed, its own count of exploring calls and the row local to its slice.  A member whose eps is 0 draws nothing and its
+ *                   call counter stays, as a lone learner's does under eps = 0.  d_debug_q (may be NULL) float32 [P * n_per_member][n_actions]
+ *   pop_push_device (dqn.py:257-359) the lone push_device per member, each slice into its member's ring (and tree, where the member has one)
+ *   pop_update_device   (dqn.py:257-359, get_targets dqn.py:673-705) n_updates updates of every member; lr HOST fp64 [n_lr], n_lr = P.  A member
+ *                   whose replay_start gate is shut skips its update while the others proceed, and the hard copy of the target follows the
+ *                   member's own update count and target_period; both are decided on the device
+ *   pop_stats_device    (dqn.py:257-359) d_out DEVICE fp64 [P][4]: the lone stats_device's four numbers per member
+ *   pop_per_enable  (dqn.py:257-359, the sum tree of dqn.py:267-349, 727-794) stmpc_pop_per_enable_ddpg for this population: cfgs HOST [P], enabled
+ *                   HOST uint8 [P]; one call, on empty rings; afterwards a prioritised member is bit-identical to a lone learner with the lone
+ *                   per_enable, a uniform one to the member of a population without the call
+ *   pop_replay_read (dqn.py:257-359) debug, HOST: `count` rows of STMPC_DDPG_ROW float32 from row `first` of a learner's ring -- a borrowed member's,
+ *                   or a lone stmpc_dqn's, so that the two can be compared; synchronises
+ * Refused with STMPC_EINVAL before any launch: P outside 1 ... 64, members that differ in a shared field (the message names the member), n_lr or
+ * n_eps other than P, an eps outside 0 ... 1, a negative learning rate or n_updates, n_per_member outside 1 ... capacity, NULL pointers.
+ */
+#define STMPC_DQN_POP_MAX 64            /* == STMPC_DDPG_POP_MAX */
+typedef struct stmpc_dqn_pop stmpc_dqn_pop;
+int  stmpc_pop_dqn_create(stmpc_ctx *ctx, const stmpc_dqn_cfg *cfgs, int P, stmpc_dqn_pop **out);
+void stmpc_pop_dqn_destroy(stmpc_dqn_pop *pop);
+int  stmpc_pop_dqn_size(const stmpc_dqn_pop *pop);
+stmpc_dqn *stmpc_pop_dqn_member(stmpc_dqn_pop *pop, int m);
+int  stmpc_pop_dqn_act_device(stmpc_dqn_pop *pop, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps,
+                              int32_t *d_action, float *d_debug_q, void *stream);
+int  stmpc_pop_dqn_push_device(stmpc_dqn_pop *pop, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs,
+                               int obs_stride, const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated,
+                               const uint8_t *d_truncated, void *stream);
+int  stmpc_pop_dqn_update_device(stmpc_dqn_pop *pop, int n_updates, const double *lr, int n_lr, void *stream);
+int  stmpc_pop_dqn_stats_device(stmpc_dqn_pop *pop, double *d_out, void *stream);
+int  stmpc_pop_dqn_per_enable(stmpc_dqn_pop *pop, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P);
+int  stmpc_pop_dqn_replay_read(stmpc_dqn *learner, int64_t first, int64_t count, float *rows);
+
+/*
  * A Q-network as the policy of the combined controller and of the first-step shield: DQNAgent.get_control (dqn.py:375-380) -- state vector -> Q ->
  * argmax -> JERK_VALUES_DQN[a] -- for N states in ONE launch, behind which RLAgent.do_combined_control runs as it does behind the DDPG actor.
  * (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8; no entry above changes what it computes.)  The

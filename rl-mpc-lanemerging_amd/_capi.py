@@ -293,6 +293,8 @@ EXPORTS = (
     "stmpc_dqn_push_device", "stmpc_dqn_act_device", "stmpc_dqn_update_device", "stmpc_dqn_grads_device", "stmpc_dqn_targets_device",
     "stmpc_dqn_gather_device", "stmpc_dqn_stats_device", "stmpc_dqn_per_enable", "stmpc_dqn_per_tree_read", "stmpc_dqn_per_last_device",
     "stmpc_dqn_padded_read",
+    "stmpc_pop_dqn_create", "stmpc_pop_dqn_destroy", "stmpc_pop_dqn_size", "stmpc_pop_dqn_member", "stmpc_pop_dqn_act_device",
+    "stmpc_pop_dqn_push_device", "stmpc_pop_dqn_update_device", "stmpc_pop_dqn_stats_device", "stmpc_pop_dqn_per_enable", "stmpc_pop_dqn_replay_read",
     "stmpc_qactor_create", "stmpc_qactor_view_dqn", "stmpc_qactor_destroy", "stmpc_qactor_set_limits", "stmpc_qactor_eval_device",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
@@ -314,6 +316,7 @@ ENV_NSTAT, ENV_LOG_COLS = 15, 17      # STMPC_ENV_NSTAT, STMPC_ENV_LOG_COLS
 DDPG_ROW, DDPG_NCOUNTERS = 68, 8      # STMPC_DDPG_ROW, STMPC_DDPG_NCOUNTERS
 DDPG_POP_MAX = 64                     # STMPC_DDPG_POP_MAX
 TD3_POP_MAX = 64                      # STMPC_TD3_POP_MAX
+DQN_POP_MAX = 64                      # STMPC_DQN_POP_MAX
 SIM_GROUPS_MAX = 64                   # STMPC_SIM_GROUPS_MAX
 SOLVER_GROUPS_MAX = 512               # STMPC_SOLVER_GROUPS_MAX
 ENV_REWARD_GROUPS_MAX = 64            # STMPC_ENV_REWARD_GROUPS_MAX
@@ -515,6 +518,18 @@ def load():
     lib.stmpc_dqn_per_tree_read.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
     lib.stmpc_dqn_per_last_device.argtypes = [vp, vp, vp, vp, vp]
     lib.stmpc_dqn_padded_read.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_pop_dqn_create.argtypes = [vp, C.POINTER(DQNCfg), C.c_int, C.POINTER(vp)]
+    lib.stmpc_pop_dqn_destroy.argtypes = [vp]
+    lib.stmpc_pop_dqn_destroy.restype = None
+    lib.stmpc_pop_dqn_size.argtypes = [vp]
+    lib.stmpc_pop_dqn_member.argtypes = [vp, C.c_int]
+    lib.stmpc_pop_dqn_member.restype = vp
+    lib.stmpc_pop_dqn_act_device.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]
+    lib.stmpc_pop_dqn_push_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 4 + [vp]
+    lib.stmpc_pop_dqn_update_device.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.c_int, vp]
+    lib.stmpc_pop_dqn_stats_device.argtypes = [vp, vp, vp]
+    lib.stmpc_pop_dqn_per_enable.argtypes = [vp, C.POINTER(PERCfg), C.POINTER(C.c_uint8), C.c_int]
+    lib.stmpc_pop_dqn_replay_read.argtypes = [vp, C.c_int64, C.c_int64, fp]
     lib.stmpc_qactor_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, dp, C.c_int, C.POINTER(vp)]
     lib.stmpc_qactor_view_dqn.argtypes = [vp, C.c_int, dp, C.c_int, C.c_int, C.POINTER(vp)]
     lib.stmpc_qactor_destroy.argtypes = [vp]
@@ -1162,6 +1177,53 @@ class Context:
         self._chk(self._lib.stmpc_dqn_padded_read(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
         o = np.cumsum([0, 32 * h1p, h1p, Ap * h1p, Ap])
         return {"w0": flat[o[0]:o[1]].reshape(h1p, 32), "b0": flat[o[1]:o[2]], "w1": flat[o[2]:o[3]].reshape(Ap, h1p), "b1": flat[o[3]:o[4]]}
+
+    # -- DQN population (stmpc_pop_dqn_*): P DQN learners, one launch per kernel (dqn.py:257-359) ------------------------
+    def dqn_pop_create(self, cfgs):
+        """``cfgs``: a sequence of ``DQNCfg``; the library checks the member count and that the launch shapes are common."""
+        arr = (DQNCfg * len(cfgs))(*cfgs)
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_pop_dqn_create(self._h, arr, len(cfgs), C.byref(h)))
+        return h
+
+    def dqn_pop_destroy(self, handle):
+        self._lib.stmpc_pop_dqn_destroy(handle)
+
+    def dqn_pop_size(self, handle):
+        return int(self._lib.stmpc_pop_dqn_size(handle))
+
+    def dqn_pop_member(self, handle, m):
+        """The m-th member as a borrowed ``stmpc_dqn`` handle for the ``dqn_*`` methods above (never ``dqn_destroy`` it)."""
+        h = self._lib.stmpc_pop_dqn_member(handle, int(m))
+        if not h:
+            self._chk(STMPC_EINVAL)
+        return C.c_void_p(h)
+
+    def dqn_pop_act(self, handle, n_per_member, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
+        """``eps``: one value per member (the library checks the length and the range)."""
+        e = np.ascontiguousarray(eps, dtype=np.float64).reshape(-1)
+        self._chk(self._lib.stmpc_pop_dqn_act_device(handle, int(n_per_member), d_obs, int(obs_stride), _dptr(e), int(e.size), d_action, d_debug_q, stream))
+
+    def dqn_pop_push(self, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
+        self._chk(self._lib.stmpc_pop_dqn_push_device(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated,
+                                                      d_truncated, stream))
+
+    def dqn_pop_update(self, handle, n_updates, lr, stream=0):
+        """``lr``: one learning rate per member (the library checks the length)."""
+        lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
+        self._chk(self._lib.stmpc_pop_dqn_update_device(handle, int(n_updates), _dptr(lr), int(lr.size), stream))
+
+    def dqn_pop_stats(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_pop_dqn_stats_device(handle, d_out, stream))
+
+    def dqn_pop_per_enable(self, handle, cfgs):
+        self._chk(self._lib.stmpc_pop_dqn_per_enable(handle, *self._per_table(cfgs)))
+
+    def dqn_pop_replay_read(self, learner_handle, first, count):
+        """Debug: ``count`` rows from row ``first`` of a DQN learner's ring (a borrowed member's or a lone learner's), float32 [count][DDPG_ROW]; synchronises."""
+        rows = np.zeros((int(count), DDPG_ROW), dtype=np.float32)
+        self._chk(self._lib.stmpc_pop_dqn_replay_read(learner_handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
+        return rows
 
     # -- a Q-network as a policy (stmpc_qactor_*): DQNAgent.get_control, dqn.py:375-380 ------------------------
     def qactor_create(self, net, action_values, mode=0):

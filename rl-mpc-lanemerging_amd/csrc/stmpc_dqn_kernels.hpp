@@ -40,9 +40,11 @@ struct DqnDev {
 __host__ __device__ inline int dq_nparam(int h1p, int Ap) { return dg_o_w2(h1p, Ap); }
 
 // ---- replay: k_replay_push's row with an int32 action index in column DQ_ACTION and no time feature ---------------------------------------------
-__global__ void __launch_bounds__(256) k_dqn_push(DqnDev D, int N, const float *__restrict__ obs, const float *__restrict__ next_obs, const float *__restrict__ final_obs,
-                                                  int obs_stride, const int *__restrict__ action, const double *__restrict__ reward,
-                                                  const unsigned char *__restrict__ term, const unsigned char *__restrict__ trunc) {
+// (every kernel's body is a __device__ function of the learner's struct: the lone entry passes its by-value argument, the population entry of
+// stmpc_dqn_pop_kernels.hpp the member blockIdx.y selects)
+__device__ __forceinline__ void dqn_push_body(const DqnDev &D, int N, const float *__restrict__ obs, const float *__restrict__ next_obs, const float *__restrict__ final_obs,
+                                              int obs_stride, const int *__restrict__ action, const double *__restrict__ reward,
+                                              const unsigned char *__restrict__ term, const unsigned char *__restrict__ trunc) {
     const DdpgDev &L = D.base;
     const long long cursor = L.cnt[DG_CURSOR], fill = L.cnt[DG_FILL], frames = L.cnt[DG_FRAMES];
     for (long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x; x < (long long)N * DG_ROW; x += (long long)gridDim.x * blockDim.x) {
@@ -68,6 +70,11 @@ __global__ void __launch_bounds__(256) k_dqn_push(DqnDev D, int N, const float *
     if (threadIdx.x == 0) last_s = last;
     __syncthreads();
     if (last_s) per_push_tree(L, cursor, N);
+}
+__global__ void __launch_bounds__(256) k_dqn_push(DqnDev D, int N, const float *__restrict__ obs, const float *__restrict__ next_obs, const float *__restrict__ final_obs,
+                                                  int obs_stride, const int *__restrict__ action, const double *__restrict__ reward,
+                                                  const unsigned char *__restrict__ term, const unsigned char *__restrict__ trunc) {
+    dqn_push_body(D, N, obs, next_obs, final_obs, obs_stride, action, reward, term, trunc);
 }
 
 // ---- pieces -------------------------------------------------------------------------------------------------------------------------------------
@@ -126,8 +133,7 @@ __device__ __forceinline__ int dqn_argmax(const float *q, int A, float &best) {
 
 // ---- forward / backward -------------------------------------------------------------------------------------------------------------------------
 // dbg (may be null) float32 [B][4]: a* (plain DQN: the maximum's index), the target net's Q there, y, Q(s, a)
-__global__ void __launch_bounds__(AT_THREADS) k_dqn_fwd(DqnDev D, int B, int gate, float *__restrict__ dbg) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+__device__ __forceinline__ void dqn_fwd_body(const DqnDev &D, int B, int gate, float *__restrict__ dbg, unsigned char *dg_smem) {
     const DdpgDev &L = D.base;
     if (!ddpg_gate(L, gate)) return;
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, D.Ap);
@@ -181,6 +187,10 @@ __global__ void __launch_bounds__(AT_THREADS) k_dqn_fwd(DqnDev D, int B, int gat
     for (int k = part; k < L.h1p; k += 32)
         L.aD1[(size_t)(r0 + row) * L.h1p + k] = T.H1[(size_t)row * T.h1_ld + k] > 0.f ? dz * w1a[k] : 0.f;
 }
+__global__ void __launch_bounds__(AT_THREADS) k_dqn_fwd(DqnDev D, int B, int gate, float *__restrict__ dbg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    dqn_fwd_body(D, B, gate, dbg, dg_smem);
+}
 
 // ---- weight gradients: k_ddpg_wgrad's body; the grid covers its jobs dW1, dW0, db1, db0 and stops in front of the scalar head's ------------------
 __global__ void __launch_bounds__(64 * DG_WG_WAVES) k_dqn_wgrad(DqnDev D, int Bp, int gate) {
@@ -190,7 +200,7 @@ __global__ void __launch_bounds__(64 * DG_WG_WAVES) k_dqn_wgrad(DqnDev D, int Bp
 
 // ---- Adam + target sync + re-pack ---------------------------------------------------------------------------------------------------------------
 // mode 0: Adam step, the hard copy of the target if this update's number is a multiple of target_period, re-pack; mode 1: re-pack only
-__global__ void __launch_bounds__(256) k_dqn_adam(DqnDev D, float lr, int mode, int gate) {
+__device__ __forceinline__ void dqn_adam_body(const DqnDev &D, float lr, int mode, int gate) {
     const DdpgDev &L = D.base;
     if (mode == 0 && !ddpg_gate(L, gate)) return;
     const DdpgNet &net = L.q;
@@ -214,6 +224,7 @@ __global__ void __launch_bounds__(256) k_dqn_adam(DqnDev D, float lr, int mode, 
         L.cnt[DG_UPDATES] = upd + 1;
     }
 }
+__global__ void __launch_bounds__(256) k_dqn_adam(DqnDev D, float lr, int mode, int gate) { dqn_adam_body(D, lr, mode, gate); }
 
 // padded parameter layout -> W0 [h1][n_obs] | b0 [h1] | W1 [A][h1] | b1 [A], row-major, unpadded
 __global__ void k_dqn_unpad(DqnDev D, const float *__restrict__ src, float *__restrict__ dst) {
@@ -233,9 +244,8 @@ __global__ void __launch_bounds__(64) k_dqn_stats(DqnDev D, int B, double *out) 
 
 // ---- acting -------------------------------------------------------------------------------------------------------------------------------------
 // action [N] int32: the greedy index, or -- explore != 0 and the row's u < eps -- the second draw modulo A.  dbg_q (may be null) float32 [N][A]
-__global__ void __launch_bounds__(AT_THREADS) k_dqn_act(DqnDev D, int N, const float *__restrict__ obs, int obs_stride, float eps, int explore,
-                                                        int *__restrict__ action, float *__restrict__ dbg_q) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+__device__ __forceinline__ void dqn_act_body(const DqnDev &D, int N, const float *__restrict__ obs, int obs_stride, float eps, int explore,
+                                             int *__restrict__ action, float *__restrict__ dbg_q, unsigned char *dg_smem) {
     const DdpgDev &L = D.base;
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, D.Ap);
     const int tid = threadIdx.x, e0 = blockIdx.x * AT_TM, row = tid >> 5, part = tid & 31, e = e0 + row;
@@ -258,6 +268,11 @@ __global__ void __launch_bounds__(AT_THREADS) k_dqn_act(DqnDev D, int N, const f
     }
     __syncthreads();
     if (explore && tid == 0 && dg_last_block(L.tick + DG_T_ACT, gridDim.x)) L.cnt[DG_ACTS] = acts + 1;
+}
+__global__ void __launch_bounds__(AT_THREADS) k_dqn_act(DqnDev D, int N, const float *__restrict__ obs, int obs_stride, float eps, int explore,
+                                                        int *__restrict__ action, float *__restrict__ dbg_q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    dqn_act_body(D, N, obs, obs_stride, eps, explore, action, dbg_q, dg_smem);
 }
 
 }  // namespace stmpc

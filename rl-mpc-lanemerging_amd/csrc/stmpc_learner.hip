@@ -2,9 +2,10 @@
 // a network's and a workspace's buffers (net_build, ws_build), the slot layout as a list of segments (slot_layout, slot_set, slot_get) and the launch
 // geometry (struct Grid).  Then the handles, each with ONE function that derives its device structs from what it owns: the DDPG learner (stmpc_ddpg_*,
 // ddpg_refresh), the TD3 learner on a DDPG learner as base plus critic 2 (stmpc_td3_*, td3_refresh), prioritised replay for the two (stmpc_per_*), their
-// populations on one skeleton (struct PopCore; stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_per_*; pop_upload, td3_pop_upload), actors that view a
+// populations on one skeleton (struct PopCore over struct PopSlot; stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_per_*; pop_upload, td3_pop_upload), actors that view a
 // learner's networks and their population (stmpc_actor_view_ddpg, stmpc_actor_pop_*), and the DQN learner for the discrete envs (stmpc_dqn_*), which
-// holds a replay store, one network and one workspace of its own, with the Q-network as a policy behind it (stmpc_qactor_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
+// holds a replay store, one network and one workspace of its own, with its population on the same skeleton (stmpc_pop_dqn_*; dqn_pop_upload) and
+// the Q-network as a policy behind it (stmpc_qactor_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
 #include "stmpc_per_kernels.hpp"
@@ -14,7 +15,10 @@
 #include "stmpc_per_pop_kernels.hpp"
 #include "stmpc_actor_pop_kernels.hpp"
 #include "stmpc_dqn_kernels.hpp"
+#include "stmpc_dqn_pop_kernels.hpp"
 #include "stmpc_qactor_kernels.hpp"
+#include <initializer_list>
+#include <utility>
 
 // ---- the parts every learner is made of ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -602,10 +606,12 @@ double stmpc_td3_noise(uint64_t seed, uint64_t update, uint32_t row, uint32_t *d
 
 // ---- prioritised replay (stmpc_per_*) for a lone DDPG learner or a lone TD3 learner's base; kernels in stmpc_per_kernels.hpp ----------------------
 namespace {
-// the store's buffers on a learner that passed the checks, and its device structs (a TD3 learner's base: both views too) anew
-int per_attach(stmpc_ddpg *l, const stmpc_per_cfg *g) {
-    TRY(l->rp.attach(g, l->td3_owner != nullptr));
-    ddpg_refresh(l);
+// the store's buffers on a learner of any type that passed the checks, and the device struct the store is wired into (a TD3 learner's base: both
+// views too) anew
+int per_attach(Replay &rp, DdpgDev &dev, stmpc_td3 *td3_owner, const stmpc_per_cfg *g) {
+    TRY(rp.attach(g, td3_owner != nullptr));
+    rp.wire(dev);
+    if (td3_owner) td3_refresh(td3_owner);
     return STMPC_OK;
 }
 }  // namespace
@@ -617,7 +623,7 @@ int stmpc_per_enable(stmpc_ddpg *l, const stmpc_per_cfg *g) {
     TRY(per_check_cfg(g));
     if (l->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: prioritised replay is enabled on the population (stmpc_pop_per_enable_ddpg / _td3)");
     TRY(l->rp.check_empty());
-    return per_attach(l, g);
+    return per_attach(l->rp, l->dev, l->td3_owner, g);
 }
 
 int stmpc_per_tree_read(stmpc_ddpg *l, int64_t first, int64_t count, double *nodes) {
@@ -639,17 +645,32 @@ int64_t stmpc_per_sample_index(const double *tree, int64_t leaves, int64_t fill,
 
 // ---- the populations (stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_per_*): P learners of the sections above, one launch per kernel; kernels in
 // stmpc_ddpg_pop_kernels.hpp, stmpc_td3_pop_kernels.hpp and stmpc_per_pop_kernels.hpp -------------------------------------------------------------
-// What both population types hold: the members' stmpc_ddpg (a TD3 member's: its base) and the device table of their structs.
+// What a population's shared code uses of a member, whatever its type: the replay store, the DdpgDev that store is wired into (a DDPG learner's
+// dev, a TD3 member's base's, a DQN member's dev.base) and -- a TD3 member's base alone -- the stmpc_td3 whose views derive from it.
+struct PopSlot {
+    Replay *rp = nullptr;
+    DdpgDev *dev = nullptr;
+    stmpc_td3 *td3_owner = nullptr;
+};
+// What every population type holds: its members' slots, the shape they share and the device table of their DdpgDev.
 struct PopCore {
-    int device = 0;
-    std::vector<stmpc_ddpg *> bases;
-    DevBuf table;                               // DdpgDev [P]: the bases' dev (pop_upload), for the DDPG kernels, k_ddpg_act_pop and k_replay_push_pop
-    bool per_called = false, per_any = false;   // stmpc_pop_per_enable_* was called; at least one member has a tree
-    int P() const { return (int)bases.size(); }
+    int device = 0, n_obs = 0, capacity = 0, batch = 0;
+    size_t lds = 0;
+    std::vector<PopSlot> slots;
+    DevBuf table;                               // DdpgDev [P]: the slots' dev (pop_upload), for the DDPG kernels, k_ddpg_act_pop, k_replay_push_pop,
+                                                // k_per_sample_pop, k_per_update_pop and k_ddpg_stats_pop
+    bool per_called = false, per_any = false;   // stmpc_pop_per_enable_* / stmpc_pop_dqn_per_enable was called; at least one member has a tree
+    int P() const { return (int)slots.size(); }
     const DdpgDev *dev() const { return table.as<DdpgDev>(); }
+    void add(stmpc_ddpg *l) {
+        l->pop_member = true;
+        slots.push_back({&l->rp, &l->dev, l->td3_owner});
+        n_obs = l->cfg.n_obs; capacity = l->cfg.capacity; batch = l->cfg.batch; lds = l->lds;
+    }
 };
 struct stmpc_ddpg_pop {
-    PopCore core;                           // core.bases: the members, owned; made by stmpc_ddpg_create, so every single-learner entry works on a borrowed member
+    PopCore core;
+    std::vector<stmpc_ddpg *> bases;        // the members, owned; made by stmpc_ddpg_create, so every single-learner entry works on a borrowed member
 };
 struct stmpc_td3_pop {
     PopCore core;
@@ -664,7 +685,7 @@ namespace {
 // the device tables from the members as they are now: at create, and again once prioritised replay gave members a tree
 int pop_upload(PopCore &c) {
     std::vector<DdpgDev> host;
-    for (const stmpc_ddpg *l : c.bases) host.push_back(l->dev);
+    for (const PopSlot &s : c.slots) host.push_back(*s.dev);
     return upload(c.table, host.data(), host.size());
 }
 int td3_pop_upload(stmpc_td3_pop *p) {
@@ -679,49 +700,54 @@ int td3_pop_raise_lds(int device, size_t lds) {
     TRY(raise_dynamic_lds((const void *)k_td3_actor_fwd_pop, "k_td3_actor_fwd_pop", ceiling[1], device, lds));
     return ddpg_raise_lds(true, device, lds);                       // (k_ddpg_act_pop)
 }
-// a create entry's checks; base(cfg): the stmpc_ddpg_cfg of a member's cfg
-template <class Cfg, class Pop, class F> int pop_check_create(const stmpc_ctx *c, const Cfg *cfgs, int P, Pop **out, F base) {
+// a create entry's checks; same(a, b): two members' cfgs agree in the fields `shared` names
+template <class Cfg, class Pop, class F> int pop_check_create(const stmpc_ctx *c, const Cfg *cfgs, int P, Pop **out, const char *shared, F same) {
     if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
     *out = nullptr;
     if (P < 1 || P > DG_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
     if (!cfgs) return fail(STMPC_EINVAL, "NULL argument");
-    for (int m = 1; m < P; ++m) {
-        const stmpc_ddpg_cfg &a = base(cfgs[m]), &b = base(cfgs[0]);
-        if (a.n_obs != b.n_obs || a.h1 != b.h1 || a.h2 != b.h2 || a.batch != b.batch || a.capacity != b.capacity)
-            return fail(STMPC_EINVAL, "the members of a population share n_obs, h1, h2, batch and capacity (member " + std::to_string(m) + " differs from member 0)");
-    }
+    for (int m = 1; m < P; ++m)
+        if (!same(cfgs[m], cfgs[0]))
+            return fail(STMPC_EINVAL, std::string("the members of a population share ") + shared + " (member " + std::to_string(m) + " differs from member 0)");
     return STMPC_OK;
 }
+const char *const DDPG_SHARED = "n_obs, h1, h2, batch and capacity";
+bool ddpg_same_shape(const stmpc_ddpg_cfg &a, const stmpc_ddpg_cfg &b) {
+    return a.n_obs == b.n_obs && a.h1 == b.h1 && a.h2 == b.h2 && a.batch == b.batch && a.capacity == b.capacity;
+}
 // an update entry's checks behind the population's own, and the learning rates as the kernels take them
-int pop_check_update(const PopCore &c, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, DdpgLr &lq, DdpgLr &lp) {
-    if (!lr_q || !lr_pi) return fail(STMPC_EINVAL, "NULL argument");
+// (rates: each HOST array of n_lr learning rates with the struct it goes into -- two of DDPG and TD3, one of DQN)
+int pop_check_update(const PopCore &c, int n_updates, int n_lr, std::initializer_list<std::pair<const double *, DdpgLr *>> rates) {
+    for (const auto &r : rates)
+        if (!r.first) return fail(STMPC_EINVAL, "NULL argument");
     if (n_lr != c.P()) return fail(STMPC_EINVAL, "the learning-rate arrays have " + std::to_string(n_lr) + " entries, the population " + std::to_string(c.P()) + " members");
     if (n_updates < 0) return fail(STMPC_EINVAL, "n_updates is negative");
-    for (int i = 0; i < 2; ++i)
+    for (const auto &r : rates)
         for (int m = 0; m < c.P(); ++m) {
-            const double lr = (i ? lr_pi : lr_q)[m];
-            if (!(lr >= 0)) return fail(STMPC_EINVAL, "a member's learning rate is negative");
-            (i ? lp : lq).lr[m] = (float)lr;
+            if (!(r.first[m] >= 0)) return fail(STMPC_EINVAL, "a member's learning rate is negative");
+            r.second->lr[m] = (float)r.first[m];
         }
+    return STMPC_OK;
+}
+// what an acting or pushing entry of any population checks of its row count and stride
+int pop_check_rows(const PopCore &c, int n_per_member, int obs_stride) {
+    if (n_per_member < 1 || n_per_member > c.capacity || obs_stride < c.n_obs)
+        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
     return STMPC_OK;
 }
 // acting and pushing of the members: the DDPG population's own, and a TD3 population's on its members' bases
 int pop_act(const PopCore &c, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action, uint32_t *d_debug, void *stream) {
-    const stmpc_ddpg *l0 = c.bases[0];
-    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
-        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
+    TRY(pop_check_rows(c, n_per_member, obs_stride));
     if (!d_obs || !d_ticks || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(c.device));
-    hipLaunchKernelGGL(k_ddpg_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, c.P()), dim3(AT_THREADS), l0->lds, (hipStream_t)stream, c.dev(), n_per_member, d_obs,
+    hipLaunchKernelGGL(k_ddpg_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, c.P()), dim3(AT_THREADS), c.lds, (hipStream_t)stream, c.dev(), n_per_member, d_obs,
                        obs_stride, d_ticks, noise != 0, d_action, d_debug);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 int pop_push(const PopCore &c, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_ticks,
              const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
-    const stmpc_ddpg *l0 = c.bases[0];
-    if (n_per_member < 1 || n_per_member > l0->cfg.capacity || obs_stride < l0->cfg.n_obs)
-        return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
+    TRY(pop_check_rows(c, n_per_member, obs_stride));
     if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(c.device));
     hipLaunchKernelGGL(k_replay_push_pop, dim3(push_blocks(n_per_member), c.P()), dim3(256), 0, (hipStream_t)stream, c.dev(), n_per_member, d_obs, d_next_obs, d_final_obs,
@@ -736,11 +762,11 @@ template <class F> int pop_per_enable(PopCore &c, const stmpc_per_cfg *cfgs, con
     if (P != c.P()) return fail(STMPC_EINVAL, "cfgs and enabled have " + std::to_string(P) + " entries, the population " + std::to_string(c.P()) + " members");
     if (c.per_called) return fail(STMPC_EINVAL, "prioritised replay was already set up on this population (one call, on empty rings)");
     for (int m = 0; m < P; ++m)
-        if (enabled[m]) { TRY(per_check_cfg(cfgs + m)); TRY(c.bases[m]->rp.check_empty()); }
+        if (enabled[m]) { TRY(per_check_cfg(cfgs + m)); TRY(c.slots[m].rp->check_empty()); }
     c.per_called = true;
     int rc = STMPC_OK;
     for (int m = 0; m < P && !rc; ++m)
-        if (enabled[m]) { rc = per_attach(c.bases[m], cfgs + m); c.per_any = c.per_any || !rc; }
+        if (enabled[m]) { rc = per_attach(*c.slots[m].rp, *c.slots[m].dev, c.slots[m].td3_owner, cfgs + m); c.per_any = c.per_any || !rc; }
     if (!c.per_any) return rc;                                      // (no member enabled: the tables stand)
     HIPCHK(hipSetDevice(c.device));
     HIPCHK(hipDeviceSynchronize());
@@ -752,7 +778,7 @@ template <class F> int pop_per_enable(PopCore &c, const stmpc_per_cfg *cfgs, con
 extern "C" {
 
 int stmpc_ddpg_pop_create(stmpc_ctx *c, const stmpc_ddpg_cfg *cfgs, int P, stmpc_ddpg_pop **out) {
-    TRY(pop_check_create(c, cfgs, P, out, [](const stmpc_ddpg_cfg &g) -> const stmpc_ddpg_cfg & { return g; }));
+    TRY(pop_check_create(c, cfgs, P, out, DDPG_SHARED, ddpg_same_shape));
     HIPCHK(hipSetDevice(c->device));
     stmpc_ddpg_pop *p = new stmpc_ddpg_pop();
     p->core.device = c->device;
@@ -760,10 +786,10 @@ int stmpc_ddpg_pop_create(stmpc_ctx *c, const stmpc_ddpg_cfg *cfgs, int P, stmpc
     for (int m = 0; m < P && !rc; ++m) {
         stmpc_ddpg *l = nullptr;
         rc = stmpc_ddpg_create(c, cfgs + m, &l);
-        if (!rc) { l->pop_member = true; p->core.bases.push_back(l); }
+        if (!rc) { p->bases.push_back(l); p->core.add(l); }
     }
     if (!rc) rc = pop_upload(p->core);
-    if (!rc) rc = ddpg_raise_lds(true, c->device, p->core.bases[0]->lds);
+    if (!rc) rc = ddpg_raise_lds(true, c->device, p->core.lds);
     if (rc) { stmpc_ddpg_pop_destroy(p); return rc; }
     *out = p;
     return STMPC_OK;
@@ -771,7 +797,7 @@ int stmpc_ddpg_pop_create(stmpc_ctx *c, const stmpc_ddpg_cfg *cfgs, int P, stmpc
 
 void stmpc_ddpg_pop_destroy(stmpc_ddpg_pop *p) {
     if (!p) return;
-    for (stmpc_ddpg *l : p->core.bases) stmpc_ddpg_destroy(l);
+    for (stmpc_ddpg *l : p->bases) stmpc_ddpg_destroy(l);
     (void)hipSetDevice(p->core.device);
     delete p;
 }
@@ -780,7 +806,7 @@ int stmpc_ddpg_pop_size(const stmpc_ddpg_pop *p) { return p ? p->core.P() : 0; }
 
 stmpc_ddpg *stmpc_ddpg_pop_member(stmpc_ddpg_pop *p, int m) {
     if (!p || m < 0 || m >= p->core.P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
-    return p->core.bases[m];
+    return p->bases[m];
 }
 
 int stmpc_ddpg_pop_act_device(stmpc_ddpg_pop *p, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action,
@@ -799,9 +825,9 @@ int stmpc_ddpg_pop_push_device(stmpc_ddpg_pop *p, int n_per_member, const float 
 int stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *p, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream) {
     if (!p) return fail(STMPC_EINVAL, "NULL argument");
     DdpgLr lq{}, lp{};
-    TRY(pop_check_update(p->core, n_updates, lr_q, lr_pi, n_lr, lq, lp));
+    TRY(pop_check_update(p->core, n_updates, n_lr, {{lr_q, &lq}, {lr_pi, &lp}}));
     HIPCHK(hipSetDevice(p->core.device));
-    const stmpc_ddpg *l = p->core.bases[0];
+    const stmpc_ddpg *l = p->bases[0];
     const DdpgDev *tab = p->core.dev();
     const Grid g = l->grid;
     const int P = p->core.P(), B = l->cfg.batch, Bp = l->rp.Bp;
@@ -823,7 +849,7 @@ int stmpc_ddpg_pop_update_device(stmpc_ddpg_pop *p, int n_updates, const double 
 int stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *p, double *d_out, void *stream) {
     if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(p->core.device));
-    hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->core.dev(), p->core.bases[0]->cfg.batch, d_out);
+    hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->core.dev(), p->core.batch, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
@@ -834,7 +860,7 @@ int stmpc_pop_per_enable_ddpg(stmpc_ddpg_pop *p, const stmpc_per_cfg *cfgs, cons
 }
 
 int stmpc_pop_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *cfgs, int P, stmpc_td3_pop **out) {
-    TRY(pop_check_create(c, cfgs, P, out, [](const stmpc_td3_cfg &g) -> const stmpc_ddpg_cfg & { return g.base; }));
+    TRY(pop_check_create(c, cfgs, P, out, DDPG_SHARED, [](const stmpc_td3_cfg &a, const stmpc_td3_cfg &b) { return ddpg_same_shape(a.base, b.base); }));
     HIPCHK(hipSetDevice(c->device));
     stmpc_td3_pop *p = new stmpc_td3_pop();
     p->core.device = c->device;
@@ -842,10 +868,10 @@ int stmpc_pop_td3_create(stmpc_ctx *c, const stmpc_td3_cfg *cfgs, int P, stmpc_t
     for (int m = 0; m < P && !rc; ++m) {
         stmpc_td3 *t = nullptr;
         rc = stmpc_td3_create(c, cfgs + m, &t);
-        if (!rc) { t->base->pop_member = true; p->members.push_back(t); p->core.bases.push_back(t->base); }
+        if (!rc) { p->members.push_back(t); p->core.add(t->base); }
     }
     if (!rc) rc = td3_pop_upload(p);
-    if (!rc) rc = td3_pop_raise_lds(c->device, p->core.bases[0]->lds);
+    if (!rc) rc = td3_pop_raise_lds(c->device, p->core.lds);
     if (rc) { stmpc_pop_td3_destroy(p); return rc; }
     *out = p;
     return STMPC_OK;
@@ -881,9 +907,9 @@ int stmpc_pop_td3_push_device(stmpc_td3_pop *p, int n_per_member, const float *d
 int stmpc_pop_td3_update_device(stmpc_td3_pop *p, int n_updates, const double *lr_q, const double *lr_pi, int n_lr, void *stream) {
     if (!p) return fail(STMPC_EINVAL, "NULL argument");
     DdpgLr lq{}, lp{};
-    TRY(pop_check_update(p->core, n_updates, lr_q, lr_pi, n_lr, lq, lp));
+    TRY(pop_check_update(p->core, n_updates, n_lr, {{lr_q, &lq}, {lr_pi, &lp}}));
     HIPCHK(hipSetDevice(p->core.device));
-    const stmpc_ddpg *l = p->core.bases[0];
+    const stmpc_ddpg *l = p->members[0]->base;
     const Grid g = l->grid;
     const int P = p->core.P(), B = l->cfg.batch, Bp = l->rp.Bp;
     hipStream_t st = (hipStream_t)stream;
@@ -904,7 +930,7 @@ int stmpc_pop_td3_update_device(stmpc_td3_pop *p, int n_updates, const double *l
 int stmpc_pop_td3_stats_device(stmpc_td3_pop *p, double *d_out, void *stream) {
     if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(p->core.device));
-    hipLaunchKernelGGL(k_td3_stats_pop, dim3(1, 1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->core.bases[0]->cfg.batch, d_out);
+    hipLaunchKernelGGL(k_td3_stats_pop, dim3(1, 1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->core.batch, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
@@ -1011,6 +1037,7 @@ struct stmpc_dqn {
     int h1p = 0, Ap = 0, np = 0;
     size_t lds = 0;
     Grid grid{};
+    bool pop_member = false;                // owned by a population (stmpc_dqn_pop), whose device tables hold copies of dev and dev.base
 };
 
 namespace {
@@ -1171,10 +1198,9 @@ int stmpc_dqn_stats_device(stmpc_dqn *t, double *d_out, void *stream) {
 int stmpc_dqn_per_enable(stmpc_dqn *t, const stmpc_per_cfg *g) {
     if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
     TRY(per_check_cfg(g));
+    if (t->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: prioritised replay is enabled on the population (stmpc_pop_dqn_per_enable)");
     TRY(t->rp.check_empty());
-    TRY(t->rp.attach(g, false));
-    t->rp.wire(t->dev.base);                                         // (the tree, idx, aw, atd and the constants)
-    return STMPC_OK;
+    return per_attach(t->rp, t->dev.base, nullptr, g);               // (the tree, idx, aw, atd and the constants into dev.base)
 }
 
 int stmpc_dqn_per_tree_read(stmpc_dqn *t, int64_t first, int64_t count, double *nodes) {
@@ -1191,6 +1217,151 @@ int stmpc_dqn_padded_read(stmpc_dqn *t, int slot, float *values, int64_t count) 
     if (!t || !values || slot < 0 || slot > STMPC_DQN_GRAD) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
     if (count != dq_nparam(t->h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
     return read_back(t->rp.device, values, slot == STMPC_DQN_GRAD ? t->dev.base.q.g : net_slot(t->dev.base.q, slot), (size_t)count * sizeof(float));
+}
+
+}  // extern "C"
+
+// ---- a population of DQN learners (stmpc_pop_dqn_*): P learners of the section above, one launch per kernel; kernels in stmpc_dqn_pop_kernels.hpp,
+// prioritised replay and the statistics on the core's DdpgDev table with stmpc_per_pop_kernels.hpp's and stmpc_ddpg_pop_kernels.hpp's kernels ---------
+struct stmpc_dqn_pop {
+    PopCore core;                           // core.table: the members' dev.base
+    std::vector<stmpc_dqn *> members;       // owned; made by stmpc_dqn_create, so every lone entry works on a borrowed member
+    DevBuf table;                           // DqnDev [P]: the members' structs (dqn_pop_upload)
+    const DqnDev *dev() const { return table.as<DqnDev>(); }
+};
+
+static_assert(STMPC_DQN_POP_MAX == DG_POP_MAX && DG_POP_MAX <= 64, "DdpgLr and DqnEps hold one value, and DqnEps::explore one bit, per possible member");
+
+namespace {
+// both device tables from the members as they are now: at create, and again once prioritised replay re-wired members
+int dqn_pop_upload(stmpc_dqn_pop *p) {
+    std::vector<DqnDev> host;
+    for (const stmpc_dqn *t : p->members) host.push_back(t->dev);
+    TRY(upload(p->table, host.data(), host.size()));
+    return pop_upload(p->core);
+}
+int dqn_pop_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling[2];
+    TRY(raise_dynamic_lds((const void *)k_dqn_fwd_pop, "k_dqn_fwd_pop", ceiling[0], device, lds));
+    return raise_dynamic_lds((const void *)k_dqn_act_pop, "k_dqn_act_pop", ceiling[1], device, lds);
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_pop_dqn_create(stmpc_ctx *c, const stmpc_dqn_cfg *cfgs, int P, stmpc_dqn_pop **out) {
+    TRY(pop_check_create(c, cfgs, P, out, "n_obs, h1, n_actions, batch and capacity", [](const stmpc_dqn_cfg &a, const stmpc_dqn_cfg &b) {
+        return a.n_obs == b.n_obs && a.h1 == b.h1 && a.n_actions == b.n_actions && a.batch == b.batch && a.capacity == b.capacity;
+    }));
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_dqn_pop *p = new stmpc_dqn_pop();
+    PopCore &core = p->core;
+    core.device = c->device;
+    int rc = STMPC_OK;
+    for (int m = 0; m < P && !rc; ++m) {
+        stmpc_dqn *t = nullptr;
+        rc = stmpc_dqn_create(c, cfgs + m, &t);
+        if (rc) break;
+        t->pop_member = true;
+        p->members.push_back(t);
+    }
+    if (!rc) {
+        for (stmpc_dqn *t : p->members) core.slots.push_back({&t->rp, &t->dev.base, nullptr});     // (members is complete: the pointers stay)
+        const stmpc_dqn *t0 = p->members[0];
+        core.n_obs = t0->cfg.n_obs; core.capacity = t0->cfg.capacity; core.batch = t0->cfg.batch; core.lds = t0->lds;
+        rc = dqn_pop_upload(p);
+    }
+    if (!rc) rc = dqn_pop_raise_lds(c->device, core.lds);
+    if (rc) { stmpc_pop_dqn_destroy(p); return rc; }
+    *out = p;
+    return STMPC_OK;
+}
+
+void stmpc_pop_dqn_destroy(stmpc_dqn_pop *p) {
+    if (!p) return;
+    for (stmpc_dqn *t : p->members) stmpc_dqn_destroy(t);
+    (void)hipSetDevice(p->core.device);
+    delete p;
+}
+
+int stmpc_pop_dqn_size(const stmpc_dqn_pop *p) { return p ? p->core.P() : 0; }
+
+stmpc_dqn *stmpc_pop_dqn_member(stmpc_dqn_pop *p, int m) {
+    if (!p || m < 0 || m >= p->core.P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
+    return p->members[m];
+}
+
+int stmpc_pop_dqn_act_device(stmpc_dqn_pop *p, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps, int32_t *d_action,
+                             float *d_debug_q, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    const PopCore &c = p->core;
+    TRY(pop_check_rows(c, n_per_member, obs_stride));
+    if (!eps) return fail(STMPC_EINVAL, "NULL argument");
+    if (n_eps != c.P()) return fail(STMPC_EINVAL, "the eps array has " + std::to_string(n_eps) + " entries, the population " + std::to_string(c.P()) + " members");
+    DqnEps e{};
+    for (int m = 0; m < c.P(); ++m) {
+        if (!(eps[m] >= 0 && eps[m] <= 1)) return fail(STMPC_EINVAL, "member " + std::to_string(m) + "'s eps must be in 0 ... 1");
+        e.eps[m] = (float)eps[m];
+        if (eps[m] > 0) e.explore |= 1ull << m;                      // (stmpc_dqn_act_device's rule: an exploring call is one with eps > 0)
+    }
+    if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c.device));
+    hipLaunchKernelGGL(k_dqn_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, c.P()), dim3(AT_THREADS), c.lds, (hipStream_t)stream, p->dev(), n_per_member, d_obs,
+                       obs_stride, e, d_action, d_debug_q);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_dqn_push_device(stmpc_dqn_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                              const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    const PopCore &c = p->core;
+    TRY(pop_check_rows(c, n_per_member, obs_stride));
+    if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c.device));
+    hipLaunchKernelGGL(k_dqn_push_pop, dim3(push_blocks(n_per_member), c.P()), dim3(256), 0, (hipStream_t)stream, p->dev(), n_per_member, d_obs, d_next_obs, d_final_obs,
+                       obs_stride, d_action, d_reward, d_terminated, d_truncated);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_dqn_update_device(stmpc_dqn_pop *p, int n_updates, const double *lr, int n_lr, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "NULL argument");
+    const PopCore &c = p->core;
+    DdpgLr lrs{};
+    TRY(pop_check_update(c, n_updates, n_lr, {{lr, &lrs}}));
+    HIPCHK(hipSetDevice(c.device));
+    const stmpc_dqn *t = p->members[0];
+    const Grid g = t->grid;
+    const int P = c.P(), B = c.batch, Bp = t->rp.Bp;
+    hipStream_t st = (hipStream_t)stream;
+    for (int u = 0; u < n_updates; ++u) {                            // stmpc_dqn_update_device's three launches (five with prioritised members), each over the members
+        if (c.per_any) hipLaunchKernelGGL(k_per_sample_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, Bp, 1);
+        hipLaunchKernelGGL(k_dqn_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), c.lds, st, p->dev(), B, 1);
+        hipLaunchKernelGGL(k_dqn_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), Bp, 1);
+        if (c.per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, 1);
+        hipLaunchKernelGGL(k_dqn_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, p->dev(), lrs, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_dqn_stats_device(stmpc_dqn_pop *p, double *d_out, void *stream) {
+    if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(p->core.device));
+    hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->core.dev(), p->core.batch, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_dqn_per_enable(stmpc_dqn_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return pop_per_enable(p->core, cfgs, enabled, P, [&] { return dqn_pop_upload(p); });
+}
+
+int stmpc_pop_dqn_replay_read(stmpc_dqn *t, int64_t first, int64_t count, float *rows) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return t->rp.read_rows(first, count, rows);
 }
 
 }  // extern "C"

@@ -40,7 +40,9 @@ every member bit-identical to the lone learner with that ``cfg.per``.
 (TRAIN_DQN: dqn.py:257-359, ``get_targets`` dqn.py:673-705, the ``DQN`` module dqn.py:566-658), for the discrete-action envs ``sumo-jerk-v0`` and
 ``sumo-accel-v0``: a Q-network n_obs -> h1 -> ReLU -> A on the same ring, counters and sum tree, double DQN targets, SmoothL1 loss, Adam, a hard
 target copy every ``target_period`` updates -- three launches per update, five with ``per``.  Twins: ``update_host_dqn``, ``dqn_targets_host``,
-``dqn_adam_host``, ``dqn_act_host``, ``dqn_epsilon``; the loop: ``train_dqn``.
+``dqn_adam_host``, ``dqn_act_host``, ``dqn_epsilon``; the loop: ``train_dqn``.  ``DQNPopulation`` (``csrc/stmpc_dqn_pop_kernels.hpp``,
+``stmpc_pop_dqn_*``) is to it what ``DDPGPopulation`` is to ``DDPGLearner``: P independent DQN learners on slices of one discrete env, the same
+three (five) launches per update whatever P is, ``eps`` and ``lr`` per member, ``per=`` per member.
 """
 import math
 
@@ -679,6 +681,15 @@ class TD3Learner(DDPGLearner):
         self.ctx.td3_set_state(self.td3, p["beta_pow"][4:6])
 
 
+def per_member(value, P, default=None):
+    """What a population's call takes per member -- a learning rate, an eps -- as a float64 array: ``value`` None gives ``default``, a scalar is
+    repeated ``P`` times, and an array is taken as it is (the library checks a given array's length)."""
+    if value is None:
+        return default
+    value = np.asarray(value, dtype=np.float64)
+    return np.full(P, float(value)) if value.ndim == 0 else value
+
+
 class _PopulationMember(DDPGLearner):
     """One member of a ``DDPGPopulation`` as a ``DDPGLearner``: the handle is borrowed from the population (``stmpc_ddpg_pop_member``), which
     outlives it; everything else -- the seeded initialisation included -- is the lone learner's code."""
@@ -724,9 +735,22 @@ class DDPGPopulation:
     last minibatch (they raise on a uniform member)."""
 
     _api, _nstat = "ddpg_pop", 4                                    # the binding's entries (ctx.<_api>_create, ...) and the width of a stats row
+    _cfg_type, _action_dtype = DDPGConfig, "float64"                # what a (cfg, P) pair holds, and the dtype of the tensor ``act`` returns
 
     def _call(self, name):
         return getattr(self.ctx, "%s_%s" % (self._api, name))
+
+    def _check_env(self, env):
+        if not env.continuous:
+            raise ValueError("DDPG needs the continuous action space (sumo-jerk-continuous-v0)")
+
+    def _check_cfgs(self, env):
+        for c in self.cfgs:
+            if c.n_obs != env.obs_dim:
+                raise ValueError("cfg.n_obs is %d, the observation has %d entries" % (c.n_obs, env.obs_dim))
+
+    def _default_rates(self):
+        self._lr_q, self._lr_pi = np.array([c.lr_q for c in self.cfgs]), np.array([c.lr_pi for c in self.cfgs])
 
     def _create_handle(self):
         return self._call("create")([c.to_c(s) for c, s in zip(self.cfgs, self.seeds)])
@@ -735,7 +759,7 @@ class DDPGPopulation:
         return _PopulationMember(self, m, env, self.cfgs[m], self.seeds[m], init)
 
     def __init__(self, env, cfgs, seeds=None, init=None, ctx=None, per=None):
-        if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], DDPGConfig):
+        if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], self._cfg_type):
             cfgs = [cfgs[0]] * int(cfgs[1])
         self.cfgs = list(cfgs)
         P = self.P = len(self.cfgs)
@@ -753,8 +777,7 @@ class DDPGPopulation:
         for m, g in enumerate(self.per):
             if g is not None and not isinstance(g, PERConfig):
                 raise ValueError("per[%d] is a %s, not a PERConfig or None" % (m, type(g).__name__))
-        if not env.continuous:
-            raise ValueError("DDPG needs the continuous action space (sumo-jerk-continuous-v0)")
+        self._check_env(env)
         # (a member count outside 1 ... DDPG_POP_MAX is the library's to refuse)
         if 1 <= P <= _capi.DDPG_POP_MAX and env.n % P:
             raise ValueError("env.n = %d is not a multiple of the population's %d members" % (env.n, P))
@@ -768,9 +791,7 @@ class DDPGPopulation:
         inits = list(init) if isinstance(init, (list, tuple)) else [init] * P
         if len(self.seeds) != P or len(inits) != P:
             raise ValueError("seeds and init (if a list) have one entry per member")
-        for c in self.cfgs:
-            if c.n_obs != env.obs_dim:
-                raise ValueError("cfg.n_obs is %d, the observation has %d entries" % (c.n_obs, env.obs_dim))
+        self._check_cfgs(env)
         import torch
         self.torch = torch
         self.env_n, self.n_per_member = env.n, (env.n // P if P >= 1 else 0)
@@ -780,9 +801,9 @@ class DDPGPopulation:
         if any(g is not None for g in self.per):                    # (the rings are empty: nothing was pushed yet)
             self._call("per_enable")(self.handle, [g.to_c() if g is not None else None for g in self.per])
         self._members = [self._make_member(m, env, inits[m]) for m in range(P)]
-        self._lr_q, self._lr_pi = np.array([c.lr_q for c in self.cfgs]), np.array([c.lr_pi for c in self.cfgs])
+        self._default_rates()
         self._stats = torch.zeros(P, self._nstat, dtype=torch.float64, device=self.device)
-        self._actions = torch.empty(env.n, dtype=torch.float64, device=self.device)
+        self._actions = torch.empty(env.n, dtype=getattr(torch, self._action_dtype), device=self.device)
 
     def __del__(self):
         if getattr(self, "handle", None) is not None:
@@ -825,10 +846,7 @@ class DDPGPopulation:
                            terminated.data_ptr(), truncated.data_ptr(), self._stream())
 
     def _lr(self, lr, default):
-        if lr is None:
-            return default
-        lr = np.asarray(lr, dtype=np.float64)
-        return np.full(self.P, float(lr)) if lr.ndim == 0 else lr       # (the library checks a given array's length)
+        return per_member(lr, self.P, default)
 
     def update(self, n=1, lr_q=None, lr_pi=None):
         """``n`` updates of every member, six launches each (eight with prioritised members); a member whose replay_start gate is still shut skips its own.  ``lr_q`` / ``lr_pi``:
@@ -1091,8 +1109,8 @@ class DQNLearner(_Learner):
         self.ctx = ctx if ctx is not None else (env.ctx if env is not None else _capi.Context(-1))
         self.seed = int(seed)
         self.device = torch.device("cuda", torch.cuda.current_device())
-        self.handle = self.ctx.dqn_create(self.cfg.to_c(self.seed))
-        if self.cfg.per is not None:
+        self.handle = self._make_handle()
+        if self.cfg.per is not None:                                # (a population member's handle refuses: the population enables its members)
             self.ctx.dqn_per_enable(self.handle, self.cfg.per.to_c())
         c = self.cfg
         net = init if init is not None else init_q_net(c.n_obs, c.h1, A, np.random.default_rng(self.seed))
@@ -1102,6 +1120,9 @@ class DQNLearner(_Learner):
         self.load_state_dict({"params": new_params_dqn(net), "counters": None})
         self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self._actions = {}
+
+    def _make_handle(self):
+        return self.ctx.dqn_create(self.cfg.to_c(self.seed))
 
     def _slot(self, i):
         c = self.cfg
@@ -1159,14 +1180,108 @@ class DQNLearner(_Learner):
         return path
 
 
+class _DQNPopulationMember(DQNLearner):
+    """One member of a ``DQNPopulation`` as a ``DQNLearner``: the handle is borrowed from the population (``stmpc_pop_dqn_member``), which outlives
+    it; everything else -- the seeded initialisation, ``action_values`` and ``env_id`` from the env included -- is the lone learner's code."""
+
+    def __init__(self, population, m, env, cfg, seed, init):
+        self._population, self._borrowed = population, population.ctx.dqn_pop_member(population.handle, m)
+        super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
+
+    def _make_handle(self):
+        return self._borrowed
+
+    def __del__(self):
+        self.handle = None                                          # the population destroys its members
+
+
+class DQNPopulation(DDPGPopulation):
+    """P independent DQN learners on one discrete-action ``MergeVecEnv`` (``sumo-jerk-v0``, ``sumo-accel-v0``), advanced together: three launches
+    per update whatever P is (five when at least one member is prioritised), one each for acting, pushing and the statistics
+    (``csrc/stmpc_dqn_pop_kernels.hpp``, ``stmpc_pop_dqn_*``).  The reference trains its DQN agent one TRAIN_DQN run (dqn.py:257-359) at a time; what
+    it compares between runs -- double against plain targets, clipped against unclipped ones, TARGET_NET_FREEZE_PERIOD, the epsilon schedule,
+    prioritised against uniform replay, seeds, traffic types, reward settings -- is a population's members side by side.
+
+    ``cfgs``: a list of ``DQNConfig`` or ``(cfg, P)``; the members share n_obs, h1, n_actions, batch and capacity and may differ in everything
+    else.  ``env.n`` must be ``P * n_per_member``: member m owns environments [m * n_per_member, (m + 1) * n_per_member).  ``seeds``: one per
+    member (None: 0 .. P-1); ``init``: as ``DQNLearner``'s, for every member, or a list of P.  Member m starts exactly as
+    ``DQNLearner(seed=seeds[m], init=...)`` does and stays bit-identical to that learner driven on its slice alone.  Traffic groups and reward
+    groups: as ``DDPGPopulation``'s (as many as members; member m trains on traffic m, under reward m).  ``per``: as ``DDPGPopulation``'s -- None,
+    one ``PERConfig``, or a list of P entries, each a ``PERConfig`` or None; a cfg that carries ``per=`` is refused.
+
+    ``act`` / ``push`` / ``update`` / ``stats_device`` / ``stats`` are ``DQNLearner``'s on the whole env's tensors, with ``eps`` and ``lr`` a scalar
+    or one value per member.  A member whose eps is 0 draws nothing and its acting counter stays, as the lone learner's under ``eps=0``.
+    ``member(m)`` is a ``DQNLearner`` view: ``state_dict`` / ``load_state_dict``, ``grads``, ``targets``, ``minibatch``, ``priorities``,
+    ``last_sample``, ``export_q``, ``actor.DQNActor.from_learner(pop.member(m), ...)`` and ``evaluate_dqn(pop.member(m), ...)`` work on it.
+    ``train_dqn`` takes a population.  Evaluating all members' Q-networks in one launch (``evaluate_members`` for DQN) is not built yet."""
+
+    _api, _nstat = "dqn_pop", 4
+    _cfg_type, _action_dtype = DQNConfig, "int32"
+
+    def _check_env(self, env):
+        if env.continuous:
+            raise ValueError("DQN needs a discrete action space (sumo-jerk-v0 or sumo-accel-v0), not the continuous jerk env")
+
+    def _check_cfgs(self, env):
+        A = int(env.action_space["n"])
+        for m, c in enumerate(self.cfgs):
+            if c.n_actions is None:
+                c.n_actions = A
+            if c.n_obs != env.obs_dim or c.n_actions != A:
+                raise ValueError("member %d's cfg has n_obs %d and %d actions; the observation has %d entries and there are %d actions"
+                                 % (m, c.n_obs, c.n_actions, env.obs_dim, A))
+
+    def _default_rates(self):
+        self._lr_default = np.array([c.lr for c in self.cfgs])
+
+    def _make_member(self, m, env, init):
+        return _DQNPopulationMember(self, m, env, self.cfgs[m], self.seeds[m], init)
+
+    def act(self, obs, ticks=None, eps=0.0, debug_q=None):
+        """``DQNLearner.act`` for all members: row e is acted on by member e // n_per_member; int32 [env.n], reused by the next call.  ``eps``: a
+        scalar or one value per member.  ``debug_q``: float32 [env.n][n_actions]."""
+        self._rows(obs)
+        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
+        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (self.env_n, self.cfgs[0].n_actions))
+        self._call("act")(self.handle, self.n_per_member, obs.data_ptr(), obs.stride(0), per_member(eps, self.P), self._actions.data_ptr(),
+                          debug_q.data_ptr() if debug_q is not None else 0, self._stream())
+        return self._actions
+
+    def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
+        """``DQNLearner.push`` for all members: each member's slice of the step goes into its own ring."""
+        torch = self.torch
+        self._rows(obs)
+        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == torch.int32 and reward.dtype == torch.float64 and action.is_contiguous()
+        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
+        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+        self._call("push")(self.handle, self.n_per_member, obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0,
+                           obs.stride(0), action.data_ptr(), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self._stream())
+
+    def update(self, n=1, lr=None):
+        """``n`` updates of every member, three launches each (five with prioritised members); a member whose replay_start gate is still shut skips
+        its own.  ``lr``: a scalar or one value per member (default: each member's cfg's)."""
+        self._call("update")(self.handle, n, self._lr(lr, self._lr_default), self._stream())
+
+    def stats_device(self):
+        """fp64 [P][4] device tensor: per member, the loss and mean Q(s, a) of the last minibatch, fill, updates done (asynchronous)."""
+        return super().stats_device()
+
+    def stats(self):
+        """The same as a dict of arrays of length P with the keys of ``DQNLearner.stats``; synchronises."""
+        s = self.stats_device().cpu().numpy()
+        return {"loss": s[:, 0].copy(), "mean_q": s[:, 1].copy(), "fill": s[:, 2].astype(np.int64), "updates": s[:, 3].astype(np.int64)}
+
+
 def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_schedule=None, lr_schedule=None):
     """The loop of the reference's ``DQNAgent._train`` on the device: act (epsilon-greedy) -> env.step -> push -> ``updates_per_step`` updates,
     until ``frames`` transitions were collected (rounded up to whole steps of env.n).  ``eps_schedule(step, steps) -> eps`` (None:
     ``dqn_epsilon(step)``, the reference's decay with the step for the episode number); ``lr_schedule(step, steps) -> lr``.  Synchronises only
-    every ``drain_every`` steps.  The result has ``train_ddpg``'s keys (``takeover_share`` 0.0: no shield)."""
+    every ``drain_every`` steps.  The result has ``train_ddpg``'s keys (``takeover_share`` 0.0: no shield).
+    ``learner`` may be a ``DQNPopulation`` (both schedules may then return per-member arrays); the result then also carries ``member_returns``:
+    the drained returns of each member's environments, a list of P arrays (owner = env index // n_per_member), as ``train_ddpg``'s does."""
     steps = -(-int(frames) // env.n)
     obs = env.reset()
-    returns = []
+    returns, envs = [], []
     for i in range(steps):
         action = learner.act(obs, None, eps=eps_schedule(i, steps) if eps_schedule is not None else dqn_epsilon(i))
         next_obs, reward, term, trunc, info = env.step(action)
@@ -1175,10 +1290,16 @@ def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_sche
             learner.update(updates_per_step, lr_schedule(i, steps) if lr_schedule is not None else None)
         obs = next_obs
         if (i + 1) % drain_every == 0 or i + 1 == steps:
-            returns.append(env.drain_episode_stats()["episode_return"])
+            drained = env.drain_episode_stats()
+            returns.append(drained["episode_return"])
+            envs.append(drained["env"])
     returns = np.concatenate(returns) if returns else np.zeros(0)
-    return {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
-            "returns": returns, "takeover_share": 0.0}
+    out = {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
+           "returns": returns, "takeover_share": 0.0}
+    if isinstance(learner, DQNPopulation):
+        owner = (np.concatenate(envs) if envs else np.zeros(0, dtype=np.int64)) // learner.n_per_member
+        out["member_returns"] = [returns[owner == m] for m in range(learner.P)]
+    return out
 
 
 def write_actor(path, net, tanh_scale, tanh_mean):
@@ -1251,6 +1372,9 @@ def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=1
     from . import episodes
     if controller not in ("combined", "first_step"):
         raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
+    if isinstance(source, DQNPopulation):
+        raise ValueError("a DQNPopulation's members are evaluated one at a time, evaluate_dqn(pop.member(m), ...): a population of Q-networks in one "
+                         "launch is not built yet")
     members = source if isinstance(source, (DDPGPopulation, list, tuple)) else [source]
     if traffic is not None and len(traffic) != len(members):
         raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), len(members)))
