@@ -22,6 +22,7 @@
  *   stmpc_actor_eval_device   <- DDPGAgent.get_control                ddpg.py:83-87 (state vector + the pretrained policy network, one launch)
  *   stmpc_actor_view_ddpg     <- the closing `evaluate` of ddpg.train_ddpg_all_with_lr_drop (the model just trained, evaluated where it lies)
  *   stmpc_qactor_eval_device  <- DQNAgent.get_control                 dqn.py:375-380 (state vector + Q-network + argmax + JERK_VALUES_DQN[a], one launch)
+ *   stmpc_pop_qactor_*        <- DQNAgent.get_control for several models  dqn.py:375-380, one launch
  *   stmpc_actor_pop_*         <- DDPGAgent.load + get_control for several MODEL_NAMEs (ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json), one launch
  *   stmpc_env_*               <- merge_gym.JerkEnv / ContinuousJerkEnv / AccelerationEnv  merge_gym.py:15-221 with the rewards of
  *                                dqn.get_reward_function (dqn.py:449-563, rl.py:168-174), batched on the SUMO-free world (stmpc_sim_*)
@@ -957,6 +958,38 @@ int  stmpc_qactor_set_limits(stmpc_qactor *qactor, double tick_length, double mi
 int  stmpc_qactor_eval_device(stmpc_ctx *ctx, const stmpc_qactor *qactor, const stmpc_policy_features_cfg *cfg, int N, int Kmax, int step,
                               const double *d_cur_ego4, const int32_t *d_k_count, const double *d_cur_other_x, const double *d_cur_other_v,
                               const double *d_cur_other_a, float *d_feat, int feat_stride, int32_t *d_action, float *d_q, double *d_jerk, void *stream);
+
+/*
+ * A population of Q-networks as policies, evaluated in one launch: what stmpc_actor_pop_* is for DDPG actors, for the Q-actors above.  The reference
+ * compares its DQN agents run by run (double against plain targets, clipped against unclipped, the freeze period, prioritised against uniform replay,
+ * seeds, traffic types), one DQNAgent.get_control (dqn.py:375-380) evaluation process per model.  (Additive: new entries only, no signature or struct
+ * of ABI 8 changes, so STMPC_ABI_VERSION stays 8; stmpc_qactor_* above is unchanged.)
+ *   stmpc_pop_qactor_create   (dqn.py:375-380 for P models) P = 1 ... STMPC_DDPG_POP_MAX Q-actors -- created ones or stmpc_qactor_view_dqn views, of the
+ *                   online or the target network, of a lone learner or of a handle lent by stmpc_pop_dqn_member -- on the context's device, which
+ *                   share n_in, the padded hidden width, the padded action width and n_actions itself (one launch shape, one LDS size, one d_q
+ *                   layout), else STMPC_EINVAL; also for P out of range, a NULL member, and an acceleration-mode member without
+ *                   stmpc_qactor_set_limits.  Mode, action table, limits and online / target may differ per member.  The population holds a DEVICE
+ *                   TABLE of the members' descriptions, written once here: a member's table pointer, mode and limits as they are now (a later
+ *                   stmpc_qactor_set_limits on a member does not reach the population), and the network's pointers.  A learner's network buffers
+ *                   and shape are fixed from stmpc_dqn_create to stmpc_dqn_destroy -- stmpc_dqn_per_enable and stmpc_pop_dqn_per_enable re-wire the
+ *                   replay store's part of the learner alone -- so a view's entry stays valid and LIVE: an evaluation ordered after an update on the
+ *                   same stream sees the update, as the lone view does.  The members stay the caller's and must outlive the population.  Synchronises
+ *   stmpc_pop_qactor_destroy  (dqn.py:375-380) frees the table alone; nothing of a member's
+ *   stmpc_pop_qactor_size     (dqn.py:375-380) P; 0 for NULL
+ *   stmpc_pop_qactor_eval_device  (dqn.py:375-380) stmpc_qactor_eval_device on arrays of P * n_per_member rows: member m evaluates rows [m *
+ *                   n_per_member, (m + 1) * n_per_member), bit-identical to stmpc_qactor_eval_device with that member on that slice; d_q is
+ *                   [P * n_per_member][n_actions].  Same argument checks (step > 1 needs a rollout of P * n_per_member states in the context).
+ *                   STMPC_EINVAL, before anything is launched, for a NULL ctx / pop / cfg / required pointer, n_per_member < 0 or P * n_per_member
+ *                   beyond int32, cfg->time_feature set, stmpc_policy_features_len(cfg) != n_in, feat_stride < n_in with d_feat given, a context on
+ *                   another device than the population's.  n_per_member = 0 returns STMPC_OK and launches nothing.  Asynchronous
+ */
+typedef struct stmpc_qactor_pop stmpc_qactor_pop;
+int  stmpc_pop_qactor_create(stmpc_ctx *ctx, const stmpc_qactor *const *qactors, int P, stmpc_qactor_pop **out);
+void stmpc_pop_qactor_destroy(stmpc_qactor_pop *pop);
+int  stmpc_pop_qactor_size(const stmpc_qactor_pop *pop);
+int  stmpc_pop_qactor_eval_device(stmpc_ctx *ctx, const stmpc_qactor_pop *pop, const stmpc_policy_features_cfg *cfg, int n_per_member, int Kmax, int step,
+                                  const double *d_cur_ego4, const int32_t *d_k_count, const double *d_cur_other_x, const double *d_cur_other_v,
+                                  const double *d_cur_other_a, float *d_feat, int feat_stride, int32_t *d_action, float *d_q, double *d_jerk, void *stream);
 
 /*
  * Actors straight from learners, and a population of actors evaluated in one launch.  The reference's workflow ends a training with an evaluation

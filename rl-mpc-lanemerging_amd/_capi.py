@@ -296,6 +296,7 @@ EXPORTS = (
     "stmpc_pop_dqn_create", "stmpc_pop_dqn_destroy", "stmpc_pop_dqn_size", "stmpc_pop_dqn_member", "stmpc_pop_dqn_act_device",
     "stmpc_pop_dqn_push_device", "stmpc_pop_dqn_update_device", "stmpc_pop_dqn_stats_device", "stmpc_pop_dqn_per_enable", "stmpc_pop_dqn_replay_read",
     "stmpc_qactor_create", "stmpc_qactor_view_dqn", "stmpc_qactor_destroy", "stmpc_qactor_set_limits", "stmpc_qactor_eval_device",
+    "stmpc_pop_qactor_create", "stmpc_pop_qactor_destroy", "stmpc_pop_qactor_size", "stmpc_pop_qactor_eval_device",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
@@ -536,6 +537,11 @@ def load():
     lib.stmpc_qactor_destroy.restype = None
     lib.stmpc_qactor_set_limits.argtypes = [vp, C.c_double, C.c_double, C.c_double]
     lib.stmpc_qactor_eval_device.argtypes = [vp, vp, C.POINTER(FeaturesCfg), C.c_int, C.c_int, C.c_int] + [vp] * 6 + [C.c_int, vp, vp, vp, vp]
+    lib.stmpc_pop_qactor_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
+    lib.stmpc_pop_qactor_destroy.argtypes = [vp]
+    lib.stmpc_pop_qactor_destroy.restype = None
+    lib.stmpc_pop_qactor_size.argtypes = [vp]
+    lib.stmpc_pop_qactor_eval_device.argtypes = list(lib.stmpc_qactor_eval_device.argtypes)
     lib.stmpc_actor_view_ddpg.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_destroy.argtypes = [vp]
@@ -1258,6 +1264,27 @@ class Context:
         """One launch: state vectors + Q-network + first argmax + action table -> jerk [N] fp64 (``stmpc_qactor_eval_device``)."""
         self._chk(self._lib.stmpc_qactor_eval_device(self._h, handle, C.byref(fcfg), int(N), int(Kmax), int(step), d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa,
                                                      d_feat, int(feat_stride), d_action, d_q, d_jerk, stream))
+
+    # -- a population of Q-networks as policies (stmpc_pop_qactor_*) ------------------------
+    def qactor_pop_create(self, handles):
+        """``handles``: a sequence of Q-actor handles (created or views); the library checks the member count, the common shape and that every
+        acceleration-mode member has its limits.  The members must outlive the population."""
+        arr = (C.c_void_p * len(handles))(*handles)
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_pop_qactor_create(self._h, arr, len(handles), C.byref(h)))
+        return h
+
+    def qactor_pop_destroy(self, handle):
+        self._lib.stmpc_pop_qactor_destroy(handle)
+
+    def qactor_pop_size(self, handle):
+        return int(self._lib.stmpc_pop_qactor_size(handle))
+
+    def qactor_pop_eval_device(self, handle, fcfg, n_per_member, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_feat, feat_stride, d_action, d_q,
+                               d_jerk, stream=0):
+        """One launch for all members, member m on rows [m * n_per_member, (m + 1) * n_per_member) (``stmpc_pop_qactor_eval_device``)."""
+        self._chk(self._lib.stmpc_pop_qactor_eval_device(self._h, handle, C.byref(fcfg), int(n_per_member), int(Kmax), int(step), d_cur_ego4, d_k, d_cur_ox,
+                                                         d_cur_ov, d_cur_oa, d_feat, int(feat_stride), d_action, d_q, d_jerk, stream))
 
     # -- TD3 learner (stmpc_td3_*): a DDPG learner as base plus critic 2 ------------------------
     def td3_create(self, cfg):

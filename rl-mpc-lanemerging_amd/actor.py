@@ -23,6 +23,8 @@ reference checkout -- parity unpinned for those two steps, and the suite's ``tes
 
 ``DQNActor`` is the same for the reference's second agent, ``DQNAgent.get_control`` (dqn.py:375-380): state vector (no time feature) -> Q ->
 ``argmax`` -> the action table, one launch (``k_qactor_eval``), from a ``learner.DQNLearner`` where it lies or from its exported file.
+``QActorPopulation`` is ``ActorPopulation`` for such policies (``k_qactor_eval_pop``: P Q-networks, one launch), and ``population_of`` picks
+between the two from the members' kind.
 """
 import os
 
@@ -383,6 +385,111 @@ class DQNActor:
                                     cur_oa.data_ptr() if cur_oa is not None else 0, self.feat.data_ptr() if self.keep_features else 0, self.flen,
                                     self.action.data_ptr(), self.q.data_ptr() if self.keep_q else 0, self.jerk.data_ptr(), stream)
         return self.jerk
+
+
+def _is_dqn_learner(item):
+    return hasattr(item, "export_q") and hasattr(item, "handle")      # a learner.DQNLearner (learner.py imports this module)
+
+
+def _is_q_member(item):
+    return isinstance(item, DQNActor) or _is_dqn_learner(item)
+
+
+class QActorPopulation:
+    """P Q-networks, each on its own slice of one batch, evaluated in ONE launch (``k_qactor_eval_pop``, csrc/stmpc_qactor_pop_kernels.hpp):
+    ``ActorPopulation`` for ``DQNActor``s -- the reference's run-by-run comparisons of its DQN agent (double against plain targets, clipped against
+    unclipped, the freeze period, prioritised against uniform replay, seeds, traffic types; ``DQNAgent.get_control``, dqn.py:375-380) side by side.
+
+    ``members``: a list whose items are files written by ``learner.DQNLearner.export_q`` (jerk mode, the file's table), ``learner.DQNLearner``s (a
+    zero-copy view of the online network each, see ``DQNActor.from_learner``) or existing ``DQNActor``s (file actors or views, online or target,
+    either mode); or a ``learner.DQNPopulation`` (one view of ``member(m)`` each).  The members share n_in, the hidden width padded to a multiple of
+    16 and the action count; table, mode, limits and online / target may differ.  Member m evaluates rows [m * n_per_member, (m + 1) *
+    n_per_member) and is bit-identical to a lone ``DQNActor`` on that slice.  A view is live: an evaluation queued after an update on the same
+    stream sees it.  ``DDPGActor``'s call signature: ``combined.decide_batch_device`` and ``episodes.EpisodeRunner`` take it as they are (the
+    runner then reports per member).  ``.jerk`` (fp64 [n]) and ``.action`` (int32 [n]) are filled by every call; ``keep_features`` / ``keep_q`` fill
+    ``.feat`` (float32 [n][n_in]) and ``.q`` (float32 [n][A]) too.  There is no time feature: ``reset`` does nothing."""
+
+    def __init__(self, members, n_per_member, ctx, S):
+        if hasattr(members, "member") and hasattr(members, "P"):                 # a learner.DQNPopulation
+            members = [members.member(m) for m in range(members.P)]
+        members = list(members)
+        if not 1 <= len(members) <= _capi.DDPG_POP_MAX:
+            raise ValueError("a population has 1 ... %d members, not %d" % (_capi.DDPG_POP_MAX, len(members)))
+        self.P, self.n_per_member = len(members), int(n_per_member)
+        if self.n_per_member < 1:
+            raise ValueError("n_per_member must be positive")
+        self.n = self.P * self.n_per_member
+        # kinds and shapes first, from the host's data alone: nothing is built for a list that will be refused
+        shapes = []
+        for item in members:
+            if isinstance(item, DQNActor):
+                shapes.append(tuple(item.shape))
+            elif _is_dqn_learner(item):
+                shapes.append((item.cfg.n_obs, item.cfg.h1, item.cfg.n_actions))
+            elif isinstance(item, (str, os.PathLike)):
+                with np.load(os.fspath(item)) as z:
+                    shapes.append((int(z["w0"].shape[1]), int(z["w0"].shape[0]), int(z["w1"].shape[0])))
+            else:
+                raise ValueError("a member is an export_q file, a DQNLearner or a DQNActor, not %r" % (item,))
+        pad = lambda sh: (sh[0], (sh[1] + 15) & ~15, sh[2])
+        for m, sh in enumerate(shapes):
+            if pad(sh) != pad(shapes[0]):
+                raise ValueError("member %d is %d -> %d -> %d, member 0 is %d -> %d -> %d: one launch needs one shape" % ((m,) + sh + shapes[0]))
+        import torch
+        self.torch, self.ctx, self.engine, self.dtype, self.shape = torch, ctx, "hip", torch.float32, shapes[0]
+        self.members = []
+        for item in members:
+            if isinstance(item, DQNActor):
+                a = item
+            elif _is_dqn_learner(item):
+                a = DQNActor.from_learner(item, 1, ctx, S)              # (its own row buffers stay unused: the population has them)
+            else:
+                a = DQNActor(item, 1, ctx, S)
+            self.members.append(a)
+        self.fcfg, self.flen = self.members[0].fcfg, self.members[0].flen
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.feat = torch.empty(self.n, self.flen, dtype=torch.float32, device=dev)
+        self.q = torch.empty(self.n, self.shape[2], dtype=torch.float32, device=dev)
+        self.action = torch.empty(self.n, dtype=torch.int32, device=dev)
+        self.jerk = torch.empty(self.n, dtype=torch.float64, device=dev)
+        self.keep_features = self.keep_q = False
+        self.handle = ctx.qactor_pop_create([a.handle for a in self.members])
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                self.ctx.qactor_pop_destroy(self.handle)
+            except Exception:
+                pass
+            self.handle = None
+
+    def reset(self, mask=None):
+        """Nothing: there are no per-episode evaluation counters without a time feature."""
+
+    def __call__(self, step, cur_ego4, k, cur_ox, cur_ov, cur_oa):
+        _check_rows(self.n, cur_ego4, k, cur_ox, cur_ov, cur_oa)
+        stream = self.torch.cuda.current_stream().cuda_stream
+        self.ctx.qactor_pop_eval_device(self.handle, self.fcfg, self.n_per_member, cur_ox.shape[1], step, cur_ego4.data_ptr(), k.data_ptr(), cur_ox.data_ptr(),
+                                        cur_ov.data_ptr(), cur_oa.data_ptr() if cur_oa is not None else 0, self.feat.data_ptr() if self.keep_features else 0,
+                                        self.flen, self.action.data_ptr(), self.q.data_ptr() if self.keep_q else 0, self.jerk.data_ptr(), stream)
+        return self.jerk
+
+
+def population_of(members, n_per_member, ctx, S, **kw):
+    """The population for ``members``: a ``QActorPopulation`` when every member is a ``DQNActor`` or a ``learner.DQNLearner`` (a
+    ``learner.DQNPopulation`` counts as its members), an ``ActorPopulation`` (with ``kw``) when none is -- names and paths stay DDPG actors, as they
+    always were -- and a ValueError for a mix: one launch evaluates one kind of network."""
+    items = members
+    if hasattr(members, "member") and hasattr(members, "P"):
+        items = [members.member(m) for m in range(members.P)]
+    items = list(items)
+    q = [_is_q_member(item) for item in items]
+    if items and all(q):
+        return QActorPopulation(items, n_per_member, ctx, S)
+    if any(q):
+        raise ValueError("members %s are Q-networks and the others are not: DDPG and DQN members do not share a population"
+                         % ", ".join(str(m) for m, is_q in enumerate(q) if is_q))
+    return ActorPopulation(members, n_per_member, ctx, S, **kw)
 
 
 def q_policy_host(net, feat, action_values, mode, ego_acc=None, S=Settings, dtype=np.float64):

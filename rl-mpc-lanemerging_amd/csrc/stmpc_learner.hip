@@ -5,7 +5,7 @@
 // populations on one skeleton (struct PopCore over struct PopSlot; stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_per_*; pop_upload, td3_pop_upload), actors that view a
 // learner's networks and their population (stmpc_actor_view_ddpg, stmpc_actor_pop_*), and the DQN learner for the discrete envs (stmpc_dqn_*), which
 // holds a replay store, one network and one workspace of its own, with its population on the same skeleton (stmpc_pop_dqn_*; dqn_pop_upload) and
-// the Q-network as a policy behind it (stmpc_qactor_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
+// the Q-network as a policy behind it (stmpc_qactor_*), lone and as a population (stmpc_pop_qactor_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
 #include "stmpc_per_kernels.hpp"
@@ -17,6 +17,7 @@
 #include "stmpc_dqn_kernels.hpp"
 #include "stmpc_dqn_pop_kernels.hpp"
 #include "stmpc_qactor_kernels.hpp"
+#include "stmpc_qactor_pop_kernels.hpp"
 #include <initializer_list>
 #include <utility>
 
@@ -1480,6 +1481,85 @@ int stmpc_qactor_eval_device(stmpc_ctx *c, const stmpc_qactor *q, const stmpc_po
     QActorOut o{q->table.as<double>(), q->tick, q->jerk_min, q->jerk_max, q->mode == STMPC_QACTOR_ACCELERATION, feat_stride, d_feat, d_action, d_q, d_jerk};
     hipLaunchKernelGGL(k_qactor_eval, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), q->lds, (hipStream_t)stream, fc, q->learner ? q->learner->dev : q->dev,
                        q->learner ? q->target : 0, N, Kmax, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, o);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+}  // extern "C"
+
+// ---- a population of Q-networks as policies (stmpc_pop_qactor_*): P members, one launch per evaluation; kernel in stmpc_qactor_pop_kernels.hpp ------
+struct stmpc_qactor_pop {
+    int device = 0;
+    DevBuf table;                           // QActorMember [P], built once at create.  A view's entry copies its learner's dev.base.q: net_build wires those
+                                            // pointers in stmpc_dqn_create and nothing re-wires them before destroy (stmpc_dqn_per_enable and
+                                            // stmpc_pop_dqn_per_enable go through Replay::wire, which writes the replay's part of dev.base alone)
+    int P = 0, n_in = 0;
+    size_t lds = 0;
+    const QActorMember *dev() const { return table.as<QActorMember>(); }
+};
+
+namespace {
+int qactor_pop_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling;
+    return raise_dynamic_lds((const void *)k_qactor_eval_pop, "k_qactor_eval_pop", ceiling, device, lds);
+}
+// the struct k_qactor_eval gets for this actor
+const DqnDev &qactor_dev(const stmpc_qactor *q) { return q->learner ? q->learner->dev : q->dev; }
+}  // namespace
+
+extern "C" {
+
+int stmpc_pop_qactor_create(stmpc_ctx *c, const stmpc_qactor *const *qactors, int P, stmpc_qactor_pop **out) {
+    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (P < 1 || P > STMPC_DDPG_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
+    if (!qactors) return fail(STMPC_EINVAL, "NULL argument");
+    std::vector<QActorMember> host;
+    for (int m = 0; m < P; ++m) {
+        const stmpc_qactor *q = qactors[m];
+        if (!q) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " is NULL");
+        if (q->device != c->device) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " and the context are on different devices");
+        const DqnDev &d = qactor_dev(q), &d0 = qactor_dev(qactors[0]);
+        if (q->n_in != qactors[0]->n_in || d.base.h1p != d0.base.h1p || d.Ap != d0.Ap || q->A != qactors[0]->A)
+            return fail(STMPC_EINVAL, "the members of a population share n_in, the padded widths and n_actions (member " + std::to_string(m) + " differs from member 0)");
+        if (q->mode == STMPC_QACTOR_ACCELERATION && !q->limits)
+            return fail(STMPC_EINVAL, "member " + std::to_string(m) + " is in acceleration mode and needs the tick length and the jerk limits (stmpc_qactor_set_limits)");
+        host.push_back({d.base.q, q->n_in, d.base.h1p, q->A, d.Ap, q->learner ? q->target : 0, q->mode == STMPC_QACTOR_ACCELERATION, q->table.as<double>(), q->tick,
+                        q->jerk_min, q->jerk_max});
+    }
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_qactor_pop *p = new stmpc_qactor_pop();
+    p->device = c->device; p->P = P; p->n_in = qactors[0]->n_in; p->lds = qactors[0]->lds;
+    int rc = upload(p->table, host.data(), host.size());
+    if (!rc) rc = qactor_pop_raise_lds(c->device, p->lds);
+    if (rc) { stmpc_pop_qactor_destroy(p); return rc; }
+    *out = p;
+    return STMPC_OK;
+}
+
+void stmpc_pop_qactor_destroy(stmpc_qactor_pop *p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    delete p;
+}
+
+int stmpc_pop_qactor_size(const stmpc_qactor_pop *p) { return p ? p->P : 0; }
+
+int stmpc_pop_qactor_eval_device(stmpc_ctx *c, const stmpc_qactor_pop *p, const stmpc_policy_features_cfg *f, int n_per_member, int Kmax, int step,
+                                 const double *d_cur_ego4, const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa,
+                                 float *d_feat, int feat_stride, int32_t *d_action, float *d_q, double *d_jerk, void *stream) {
+    if (!c || !p || !f) return fail(STMPC_EINVAL, "NULL argument");
+    if (n_per_member < 0 || (long long)n_per_member * p->P > 0x7fffffffLL) return fail(STMPC_EINVAL, "n_per_member out of range");
+    if (f->time_feature) return fail(STMPC_EINVAL, "a Q-network has no time feature: the features cfg must have time_feature = 0");
+    const int N = n_per_member * p->P;
+    FeatCfg fc;
+    TRY(actor_eval_checks(c, p->device, p->n_in, f, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, nullptr, d_feat, feat_stride, d_jerk, &fc));
+    if (N == 0) return STMPC_OK;
+    const int *live;
+    TRY(rollout_live(c, N, step, &live));
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_qactor_eval_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, p->P), dim3(AT_THREADS), p->lds, (hipStream_t)stream, fc, p->dev(), n_per_member, Kmax,
+                       d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, d_feat, feat_stride, d_action, d_q, d_jerk);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }

@@ -13,6 +13,9 @@
 // The acceleration rule is AccelerationEnv._do_action's projected jerk (merge_gym.py:194-204) before its speed clamp, with the evaluated state's own
 // acceleration in the place of the env's previous_acceleration.  The reference has no evaluator for a network trained on that env (its get_control
 // reads JERK_VALUES_DQN whatever the env was): the rule is this project's.
+//
+// The arithmetic is one __device__ body, qactor_eval_body, with two entries: k_qactor_eval (a lone actor on N rows) and k_qactor_eval_pop of
+// stmpc_qactor_pop_kernels.hpp (P actors, each on its own slice of one batch).
 #pragma once
 #include "stmpc_dqn_kernels.hpp"
 
@@ -29,25 +32,26 @@ struct QActorOut {                  // what one evaluation writes; rows at or be
     double *jerk;                   // [N]
 };
 
-// D: the learner's struct (a view) or one with base.q, base.n_obs, base.h1p, A and Ap alone (a created actor); neither the counters nor the workspace
-// are read or written.  live (null at step 1) is passed on to dev_policy_features, which reads it for the time feature only: without one, the rows of
-// finished rollouts are evaluated like the others and their jerks ignored by the rollout, as k_actor_eval's are
-__global__ void __launch_bounds__(AT_THREADS) k_qactor_eval(FeatCfg f, DqnDev D, int target, int N, int Kmax, const double *__restrict__ ego4,
-                                                            const int *__restrict__ k_count, const double *__restrict__ ox, const double *__restrict__ ov,
-                                                            const double *__restrict__ oa, const int *__restrict__ live, QActorOut o) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char qa_smem[];
+// The evaluation of rows [row0 + 16 blockIdx.x, + 16) with the network of D, as far as row0 + n_rows: row0 = 0 and n_rows = N for a lone actor; a
+// member of a population has its slice's first row and length here.  The state arrays, live and the outputs of o are indexed by the global row.
+// D: the learner's struct (a view) or one with base.q, base.n_obs, base.h1p, A and Ap alone (a created actor, a population's member); neither the
+// counters nor the workspace are read or written.  live (null at step 1) is passed on to dev_policy_features, which reads it for the time feature
+// only: without one, the rows of finished rollouts are evaluated like the others and their jerks ignored by the rollout, as k_actor_eval's are
+__device__ __forceinline__ void qactor_eval_body(const FeatCfg &f, const DqnDev &D, int target, int row0, int n_rows, int Kmax, const double *__restrict__ ego4,
+                                                 const int *__restrict__ k_count, const double *__restrict__ ox, const double *__restrict__ ov,
+                                                 const double *__restrict__ oa, const int *__restrict__ live, const QActorOut &o, unsigned char *qa_smem) {
     const DdpgDev &L = D.base;
     const DdpgTile T = ddpg_tile(qa_smem, L.h1p, D.Ap);
-    const int tid = threadIdx.x, e0 = blockIdx.x * AT_TM, row = tid >> 5, part = tid & 31, e = e0 + row;
-    for (int x = tid; x < AT_TM * AT_KIN; x += blockDim.x) T.X[x] = 0.f;       // pad columns and the rows beyond N
+    const int tid = threadIdx.x, l0 = blockIdx.x * AT_TM, row = tid >> 5, part = tid & 31, l = l0 + row, e = row0 + l;
+    for (int x = tid; x < AT_TM * AT_KIN; x += blockDim.x) T.X[x] = 0.f;       // pad columns and the rows beyond n_rows
     __syncthreads();
-    if (tid < AT_TM && e0 + tid < N) dev_policy_features(f, e0 + tid, Kmax, ego4, k_count, ox, ov, oa, live, nullptr, T.X + tid * AT_KIN);
+    if (tid < AT_TM && l0 + tid < n_rows) dev_policy_features(f, row0 + l0 + tid, Kmax, ego4, k_count, ox, ov, oa, live, nullptr, T.X + tid * AT_KIN);
     __syncthreads();
-    if (o.feat && e < N && part < L.n_obs) o.feat[(size_t)e * o.feat_stride + part] = T.X[row * AT_KIN + part];
+    if (o.feat && l < n_rows && part < L.n_obs) o.feat[(size_t)e * o.feat_stride + part] = T.X[row * AT_KIN + part];
     dqn_q(D, T, T.X, target != 0);
     float qbest;
     const int a = dqn_argmax(T.H2 + (size_t)row * T.h2_ld, D.A, qbest);
-    if (e >= N) return;
+    if (l >= n_rows) return;
     if (o.q) for (int j = part; j < D.A; j += 32) o.q[(size_t)e * D.A + j] = T.H2[(size_t)row * T.h2_ld + j];
     if (part != 0) return;
     double v = o.table[a];
@@ -57,6 +61,13 @@ __global__ void __launch_bounds__(AT_THREADS) k_qactor_eval(FeatCfg f, DqnDev D,
     }
     o.jerk[e] = v;
     if (o.action) o.action[e] = a;
+}
+
+__global__ void __launch_bounds__(AT_THREADS) k_qactor_eval(FeatCfg f, DqnDev D, int target, int N, int Kmax, const double *__restrict__ ego4,
+                                                            const int *__restrict__ k_count, const double *__restrict__ ox, const double *__restrict__ ov,
+                                                            const double *__restrict__ oa, const int *__restrict__ live, QActorOut o) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char qa_smem[];
+    qactor_eval_body(f, D, target, 0, N, Kmax, ego4, k_count, ox, ov, oa, live, o, qa_smem);
 }
 
 }  // namespace stmpc

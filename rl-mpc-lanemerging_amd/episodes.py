@@ -409,7 +409,7 @@ def grid_search_st(n_per_cell, seed=0, traffic=None, cells=None, common_random_n
 def grid_search_combined(model, traffic, n_per_cell, cells=None, seed=0, common_random_numbers=True, ctx=None, kmax=16, max_episode_length=100.0, record=None,
                          max_ticks=None, check_every=16):
     """The reference's ``main.do_grid_search_combined`` (main.py:62-81: one ``EVALUATE_COMBINED_DDPG`` process per cell) in ONE run: ``model`` (as
-    ``actor.ActorPopulation`` takes a member) under the combined controller on the traffic type ``traffic`` (as ``sim_cfgs`` takes one group), once
+    ``actor.population_of`` takes a member: a DDPG model, or a ``DQNLearner`` / ``DQNActor``) under the combined controller on the traffic type ``traffic`` (as ``sim_cfgs`` takes one group), once
     per cell of ``cells`` (default ``combined.grid_search_cells()``; dicts as ``combined.control_cfgs`` takes them), ``n_per_cell`` episodes each.
     ``common_random_numbers``: every cell's traffic group gets the same seed (``seed``), so all cells face the same traffic draws and start
     speeds and differ by the controller alone -- something one process per cell cannot give; False: cell c's seed is
@@ -426,7 +426,7 @@ def grid_search_combined(model, traffic, n_per_cell, cells=None, seed=0, common_
         t["seed"] = int(seed)
     ctx = ctx if ctx is not None else _capi.default_context()
     one = actor.DDPGActor(os.fspath(model), 1, ctx, Settings) if isinstance(model, (str, os.PathLike)) else model
-    pop = actor.ActorPopulation([one] * C, int(n_per_cell), ctx, Settings)
+    pop = actor.population_of([one] * C, int(n_per_cell), ctx, Settings)     # (a DQNLearner or a DQNActor: a population of Q-networks)
     stats = run_episodes(pop.n, seed=seed, controller="combined", policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, check_every=check_every,
                          max_ticks=max_ticks, record=record, traffic=[dict(t) for _ in range(C)], control=cells)
     by = summary_by_control(stats, C)
@@ -436,7 +436,8 @@ def grid_search_combined(model, traffic, n_per_cell, cells=None, seed=0, common_
 def cross_matrix(models, traffic, n_per_cell, seed=0, ctx=None, kmax=16, max_episode_length=100.0, record=None, max_ticks=None, check_every=16,
                  controller="combined"):
     """The reference's ``combined_{traffic}_{seed}`` diagonal and ``cross_{traffic_1}_network_{traffic_2}_traffic_{seed}`` off-diagonals in ONE run:
-    every model of ``models`` (as ``actor.ActorPopulation`` takes them: shipped names, paths, learners, actors) under the combined controller on
+    every model of ``models`` (as ``actor.population_of`` takes them: shipped names, paths, DDPG learners and actors -- or, all of them,
+    ``DQNLearner``s and ``DQNActor``s, for a matrix of Q-networks) under the combined controller on
     every traffic group of ``traffic`` (as ``sim_cfgs`` takes them), ``n_per_cell`` episodes each.  Cell c = i * len(traffic) + j (row-major) pairs
     model i with traffic j: the population repeats each member len(traffic) times, the traffic list is tiled len(models) times, and the cells are
     the groups of one runner (cell c's default seed is ``vec_env.episode_seed(seed, c)``).  ``controller``: "combined" or "first_step" -- the same
@@ -459,7 +460,7 @@ def cross_matrix(models, traffic, n_per_cell, seed=0, ctx=None, kmax=16, max_epi
     # (a shipped name or a path is loaded once and its actor repeated along its row)
     loaded = [actor.DDPGActor(os.fspath(m), 1, ctx, Settings) if isinstance(m, (str, os.PathLike)) else m for m in models]
     cell_models = [m for m in loaded for _ in range(T)]
-    pop = actor.ActorPopulation(cell_models, int(n_per_cell), ctx, Settings)
+    pop = actor.population_of(cell_models, int(n_per_cell), ctx, Settings)
     stats = run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, check_every=check_every,
                          max_ticks=max_ticks, record=record, traffic=cell_traffic)
     cells = summary_by_group(stats, M * T)

@@ -1213,7 +1213,8 @@ class DQNPopulation(DDPGPopulation):
     or one value per member.  A member whose eps is 0 draws nothing and its acting counter stays, as the lone learner's under ``eps=0``.
     ``member(m)`` is a ``DQNLearner`` view: ``state_dict`` / ``load_state_dict``, ``grads``, ``targets``, ``minibatch``, ``priorities``,
     ``last_sample``, ``export_q``, ``actor.DQNActor.from_learner(pop.member(m), ...)`` and ``evaluate_dqn(pop.member(m), ...)`` work on it.
-    ``train_dqn`` takes a population.  Evaluating all members' Q-networks in one launch (``evaluate_members`` for DQN) is not built yet."""
+    ``train_dqn`` takes a population.  ``evaluate_dqn_members(pop, n_per_member)`` evaluates all members' Q-networks in one launch per tick
+    (``actor.QActorPopulation``)."""
 
     _api, _nstat = "dqn_pop", 4
     _cfg_type, _action_dtype = DQNConfig, "int32"
@@ -1373,13 +1374,36 @@ def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=1
     if controller not in ("combined", "first_step"):
         raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
     if isinstance(source, DQNPopulation):
-        raise ValueError("a DQNPopulation's members are evaluated one at a time, evaluate_dqn(pop.member(m), ...): a population of Q-networks in one "
-                         "launch is not built yet")
+        raise ValueError("a DQNPopulation's members are Q-networks: evaluate them all in one launch with evaluate_dqn_members(pop, n_per_member, ...), or "
+                         "one at a time with evaluate_dqn(pop.member(m), ...); evaluate_members builds a population of DDPG actors")
     members = source if isinstance(source, (DDPGPopulation, list, tuple)) else [source]
     if traffic is not None and len(traffic) != len(members):
         raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), len(members)))
     ctx = ctx if ctx is not None else _capi.Context(-1)
     pop = _actor.ActorPopulation(members, n_per_member, ctx, Settings)
+    stats = episodes.run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
+                                  traffic=traffic)
+    rep = stats.get("report")
+    return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),
+            "reports": rep.by_member(pop.P, traffic) if rep is not None else None}
+
+
+def evaluate_dqn_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):
+    """``evaluate_members`` for Q-networks: ``n_per_member`` merge episodes per member under the combined controller, in ONE run of P *
+    n_per_member environments whose policy is an ``actor.QActorPopulation`` -- one launch per evaluation whatever P is, where
+    ``evaluate_dqn(pop.member(m), ...)`` takes P runners, P worlds and P launch sequences per tick.  ``source``: a ``DQNPopulation`` or a
+    ``DQNLearner`` (zero-copy views of the online networks as they are on the device), or a list as ``QActorPopulation`` takes (``export_q`` files,
+    learners, ``DQNActor``s).  ``ctx``, ``traffic``, ``controller`` and the returned dict -- ``stats`` with ``member``, ``by_member``, ``reports``
+    -- are ``evaluate_members``'."""
+    from . import episodes
+    if controller not in ("combined", "first_step"):
+        raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
+    members = source if isinstance(source, (DQNPopulation, list, tuple)) else [source]
+    P = members.P if isinstance(members, DQNPopulation) else len(members)
+    if traffic is not None and len(traffic) != P:
+        raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), P))
+    ctx = ctx if ctx is not None else _capi.Context(-1)
+    pop = _actor.QActorPopulation(members, n_per_member, ctx, Settings)
     stats = episodes.run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
                                   traffic=traffic)
     rep = stats.get("report")
