@@ -1399,6 +1399,57 @@ int stmpc_cshield_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const s
 int stmpc_cshield_env_evals_device(stmpc_ctx *ctx, int N, int32_t *d_evals, void *stream);
 
 /*
+ * Combined-controller shield for the DISCRETE vector environments (STMPC_ENV_JERK, STMPC_ENV_ACCELERATION): stmpc_env_step_device behind
+ * dqn.RLAgent.do_combined_control (dqn.py:117-200), which DQNAgent inherits, with DQNAgent.get_control (dqn.py:375-380) -- a Q-network, its first argmax
+ * and the action table -- proposing rollout steps 2 ... L on the device, so that a DQN learner trains in the closed loop it is deployed in.  (Additive:
+ * new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8; stmpc_cshield_env_* above keeps every refusal it has.)
+ * The env's action INDEX is the controller's first action.  One step, on `stream`: the env's action handling + the planner's view at row stride kmax
+ * with the other vehicles' accelerations, into the start rows and the rollout's current rows + first_action, in one kernel -> for step = 1 ...
+ * max(rollout_length, 1): from step 2 on the body of stmpc_qactor_eval_device (or of stmpc_pop_qactor_eval_device) on the current rows, then the body
+ * of stmpc_rollout_step_device -> the body of stmpc_combined_decide_device (the context's stmpc_combined_counts advance) -> the takeover branch of
+ * stmpc_shield_env_step_device with d_executed_action NULL (a takeover's speed is no table entry: the index is not rewritten) -> the world step and the
+ * reward / observation / autoreset kernel of stmpc_env_step_device, unchanged.  The step equals, bit for bit, that composition made from the public
+ * entries by a caller.
+ * first_action is the jerk rollout step 1 applies: action_values[index] under STMPC_ENV_JERK; under STMPC_ENV_ACCELERATION
+ * clip((action_values[index] - ego acceleration of the view) / tick_length, minimum_negative_jerk, maximum_positive_jerk) in fp64 -- under both what
+ * stmpc_qactor_eval_device returns as d_jerk for that index on that state.  An index out of range latches the error word (stmpc_check_error) for a
+ * running environment; running or not, the row commands its current speed and its first_action is 0.0.
+ * A Q-network has no time feature, so there is no rollout time counter, no rollout_time and no *_evals_device entry.
+ * The policy is EITHER qactor (created, or a stmpc_qactor_view_dqn view: a step queued after stmpc_dqn_update_device rolls out with the updated
+ * weights) on all N rows with qactor_pop NULL and n_per_member 0, OR qactor_pop with qactor NULL, member m on rows [m * n_per_member, (m + 1) *
+ * n_per_member) and P * n_per_member == N.
+ *   stmpc_qshield_env_reset_device   stmpc_env_reset_device + every buffer of the step, sized here: the step allocates none.  STMPC_EINVAL (before
+ *                       anything changes) for STMPC_ENV_CONTINUOUS_JERK (use stmpc_cshield_env_*), cc.remember_last_choice != 0, kmax outside 1 ...
+ *                       STMPC_KMAX_LIMIT, a takeover_penalty that is negative or not finite, features.time_feature != 0, both or neither policy
+ *                       pointer, a policy on another device, n_in != stmpc_policy_features_len(&features), and for the lone Q-actor or any member:
+ *                       n_actions != env_cfg->n_action_values, a mode that is not the env's action mode, a table that is not byte-identical to
+ *                       env_cfg->action_values, in acceleration mode limits (stmpc_qactor_set_limits) that are not the env's; P * n_per_member != N.
+ *   stmpc_qshield_env_step_device    the arguments of stmpc_env_step_device (d_action int32 [N]), the cfg and the policy, then d_takeover uint8 [N],
+ *                       d_reason int32 [N] (the combined controller's codes 0-4), d_executed_jerk fp64 [N], d_takeover_ticks int32 [N] as
+ *                       stmpc_shield_env_step_device writes them.  Asynchronous with cc.sparse_control = 0; with 1 the one host round trip of
+ *                       stmpc_combined_decide_device.  STMPC_EINVAL -- and nothing changes -- for every refusal of the reset, if the context's
+ *                       environment was not reset through stmpc_qshield_env_reset_device (a stmpc_cshield_env_reset_device context included), if N,
+ *                       kmax, the rollout length, the policy pointer, n_per_member or n_action_values differ from the reset's, or the world has
+ *                       traffic groups, the env reward groups, the first-step shield or a traffic mix.  Every other env step entry and
+ *                       stmpc_sim_step_device return STMPC_EINVAL on such an env: they would execute the proposal unprotected.
+ */
+typedef struct stmpc_qshield_env_cfg {
+    stmpc_combined_cfg cc;               /* as stmpc_combined_decide_device; remember_last_choice must be 0 (the env keeps no takeover history per episode) */
+    stmpc_policy_features_cfg features;  /* the Q-network's input (time_feature must be 0) */
+    double takeover_penalty;             /* added to the tick's reward as takeover_penalty * tick_length where the controller took over (>= 0, finite) */
+    int32_t kmax;                        /* row stride of the planner view, 1 ... STMPC_KMAX_LIMIT */
+    int32_t reserved0;
+} stmpc_qshield_env_cfg;
+int stmpc_qshield_env_reset_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfg, const stmpc_env_cfg *env_cfg,
+                                   const stmpc_qshield_env_cfg *shield_cfg, const stmpc_qactor *qactor, const stmpc_qactor_pop *qactor_pop, int n_per_member,
+                                   int N, float *d_obs, int obs_stride, void *stream);
+int stmpc_qshield_env_step_device(stmpc_ctx *ctx, const stmpc_params *p, const stmpc_sim_cfg *sim_cfg, const stmpc_env_cfg *env_cfg,
+                                  const stmpc_qshield_env_cfg *shield_cfg, const stmpc_qactor *qactor, const stmpc_qactor_pop *qactor_pop, int n_per_member,
+                                  int N, const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
+                                  float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk,
+                                  int32_t *d_takeover_ticks, void *stream);
+
+/*
  * First-step shield for grouped and mixed-traffic vector environments: stmpc_shield_env_step_device in front of the env's group axes -- traffic groups
  * (the reference's traffic types, configs/train_*_*.json, control.py:215-226), reward groups (its per-run reward settings, dqn.py:449-563,
  * merge_gym.py:25) and the traffic mix -- so that the per-traffic-type training matrix, a reward-shaping sweep and a mixed-traffic policy train in

@@ -163,6 +163,20 @@ class CShieldEnvCfg(C.Structure):
                    rollout_time=cls.ROLLOUT_TIMES[rollout_time])
 
 
+class QShieldEnvCfg(C.Structure):
+    """``stmpc_qshield_env_cfg`` (include/stmpc.h): the combined controller behind a discrete vector environment with a Q-network in the rollout -- its
+    flags, the Q-network's input (no time feature), the takeover penalty and the row stride of the planner's view.  ``stmpc_cshield_env_cfg`` without
+    the rollout's time counter."""
+    _fields_ = [("cc", CombinedCfg), ("features", FeaturesCfg), ("takeover_penalty", C.c_double), ("kmax", C.c_int32), ("reserved0", C.c_int32)]
+
+    @classmethod
+    def from_settings(cls, S, sparse_control=False, takeover_penalty=0.0, kmax=32, features=None):
+        """``S``: the ``Settings`` (or an overlay of them) ``do_combined_control`` reads; ``features``: the Q-actor's ``FeaturesCfg`` (default:
+        ``FeaturesCfg.from_settings(S, time_feature=False)``)."""
+        f = FeaturesCfg.from_buffer_copy(features) if features is not None else FeaturesCfg.from_settings(S, time_feature=False)
+        return cls(cc=CombinedCfg.from_settings(S, sparse_control=sparse_control), features=f, takeover_penalty=float(takeover_penalty), kmax=int(kmax))
+
+
 class SimCfg(C.Structure):
     """``stmpc_sim_cfg`` (include/stmpc.h): scenario constants of the batched SUMO-free episode runner."""
     _fields_ = [("tick_length", C.c_double), ("other_car_speed", C.c_double), ("base_traffic_interval", C.c_double), ("spawn_x", C.c_double),
@@ -306,6 +320,7 @@ EXPORTS = (
     "stmpc_shield_env_reset_device", "stmpc_shield_env_step_device",
     "stmpc_traffic_mix_env_reset_device", "stmpc_traffic_mix_env_step_device", "stmpc_traffic_mix_draw",
     "stmpc_cshield_env_reset_device", "stmpc_cshield_env_step_device", "stmpc_cshield_env_evals_device",
+    "stmpc_qshield_env_reset_device", "stmpc_qshield_env_step_device",
     "stmpc_shield_traffic_groups_env_reset_device", "stmpc_shield_traffic_groups_env_step_device",
     "stmpc_shield_reward_groups_env_reset_device", "stmpc_shield_reward_groups_env_step_device",
     "stmpc_shield_traffic_mix_env_reset_device", "stmpc_shield_traffic_mix_env_step_device",
@@ -570,6 +585,9 @@ def load():
     lib.stmpc_cshield_env_reset_device.argtypes = [vp, pp, sp, ep, csp, vp, C.c_int, vp, C.c_int, vp]
     lib.stmpc_cshield_env_step_device.argtypes = [vp, pp, sp, ep, csp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.stmpc_cshield_env_evals_device.argtypes = [vp, C.c_int, vp, vp]
+    qsp = C.POINTER(QShieldEnvCfg)
+    lib.stmpc_qshield_env_reset_device.argtypes = [vp, pp, sp, ep, qsp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
+    lib.stmpc_qshield_env_step_device.argtypes = [vp, pp, sp, ep, qsp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int] + [vp] * 10
     shield_step = [vp, pp, ep, shp, C.c_int, vp, vp, C.c_int] + [vp] * 10         # ctx ... N, d_action, d_obs, obs_stride, the step's and the shield's outputs
     lib.stmpc_shield_traffic_groups_env_reset_device.argtypes = [vp, pp, sp, C.c_int, C.c_int, ep, shp, dp, C.c_int, vp, C.c_int, vp]
     lib.stmpc_shield_traffic_groups_env_step_device.argtypes = shield_step + [vp]
@@ -1482,6 +1500,20 @@ class Context:
         self._chk(self._lib.stmpc_cshield_env_step_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), C.byref(shield_cfg), actor, int(N), d_action,
                                                           d_obs, int(obs_stride), d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, d_takeover,
                                                           d_reason, d_executed_jerk, d_executed_action or None, d_takeover_ticks, stream))
+
+    # -- discrete vector environment behind the combined controller, a Q-network in the rollout (stmpc_qshield_env_*; see include/stmpc.h) --------
+    def qshield_env_reset(self, params, sim_cfg, env_cfg, shield_cfg, qactor, qactor_pop, n_per_member, N, d_obs, obs_stride, stream=0):
+        """``stmpc_qshield_env_reset_device``; exactly one of ``qactor`` (a ``qactor_create`` / ``qactor_view_dqn`` handle, ``n_per_member`` 0) and
+        ``qactor_pop`` (a ``pop_qactor_create`` handle) is given, the other None."""
+        self._chk(self._lib.stmpc_qshield_env_reset_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), C.byref(shield_cfg), qactor, qactor_pop,
+                                                           int(n_per_member), int(N), d_obs, int(obs_stride), stream))
+
+    def qshield_env_step(self, params, sim_cfg, env_cfg, shield_cfg, qactor, qactor_pop, n_per_member, N, d_action, d_obs, obs_stride, d_reward, d_terminated,
+                         d_truncated, d_final_obs, d_final_stats, d_takeover, d_reason, d_executed_jerk, d_takeover_ticks, stream=0):
+        """``stmpc_qshield_env_step_device``: no ``d_executed_action`` (a discrete index is not rewritten)."""
+        self._chk(self._lib.stmpc_qshield_env_step_device(self._h, C.byref(params), C.byref(sim_cfg), C.byref(env_cfg), C.byref(shield_cfg), qactor, qactor_pop,
+                                                          int(n_per_member), int(N), d_action, d_obs, int(obs_stride), d_reward, d_terminated, d_truncated,
+                                                          d_final_obs, d_final_stats, d_takeover, d_reason, d_executed_jerk, d_takeover_ticks, stream))
 
     def cshield_env_evals(self, N, d_evals, stream=0):
         """``stmpc_cshield_env_evals_device``: the count the next step's proposal is evaluated at, int32 [N] on the device."""

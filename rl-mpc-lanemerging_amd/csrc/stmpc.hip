@@ -1091,7 +1091,11 @@ const char *const GROUPED_WORLD = "the world has traffic groups (stmpc_sim_init_
 const char *const MIXED_ENV = "the env has a traffic mix (stmpc_traffic_mix_env_reset_device): one cfg would step every type; use stmpc_traffic_mix_env_step_device";
 const char *const CSHIELD_ENV = "the env runs behind the combined controller (stmpc_cshield_env_reset_device): this entry would execute the proposal unprotected; use stmpc_cshield_env_step_device";
 const char *const SHIELDED_ENV = "the env runs behind the first-step shield (a stmpc_shield_*_reset_device entry): this entry would execute the proposal unprotected; use the shielded step entry of the env's groups";
-bool has_cshield_env(const stmpc_ctx *c) { return c->env.N >= 1 && c->cshield.N == c->env.N && c->cshield.generation == c->sim.generation; }
+const char *const QSHIELD_ENV = "the env runs behind the combined controller with a Q-network (stmpc_qshield_env_reset_device): this entry would execute the proposal unprotected; use stmpc_qshield_env_step_device";
+// (one set of rows serves both envs behind the combined controller: `qpolicy` tells whose they are)
+bool has_combined_env(const stmpc_ctx *c) { return c->env.N >= 1 && c->cshield.N == c->env.N && c->cshield.generation == c->sim.generation; }
+bool has_cshield_env(const stmpc_ctx *c) { return has_combined_env(c) && !c->cshield.qpolicy; }
+bool has_qshield_env(const stmpc_ctx *c) { return has_combined_env(c) && c->cshield.qpolicy; }
 const char *const REWARD_GROUPED_ENV = "the env has reward groups (stmpc_reward_groups_env_reset_device): one cfg would reward every group; use stmpc_reward_groups_env_step_device";
 }  // namespace
 
@@ -1131,6 +1135,7 @@ int stmpc_sim_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_c
     if (c->sim.G) return fail(STMPC_EINVAL, GROUPED_WORLD);
     if (c->env.N >= 1 && c->env.T >= 1) return fail(STMPC_EINVAL, MIXED_ENV);
     if (has_cshield_env(c)) return fail(STMPC_EINVAL, CSHIELD_ENV);
+    if (has_qshield_env(c)) return fail(STMPC_EINVAL, QSHIELD_ENV);
     sim::Cfg sc;
     DevP dp;
     TRY(make_simcfg(g, &sc));
@@ -1429,12 +1434,47 @@ int cshield_cfg_check(const stmpc_ctx *c, const stmpc_params *p, const stmpc_csh
     return actor_eval_checks(c, a->device, a->dev.n_in, &sh->features, 0, sh->kmax, 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, fc);
 }
 
+// what the combined-shield env behind a Q-network takes besides the env's arguments
+struct QShieldStep {
+    const stmpc_qshield_env_cfg *cfg;
+    const stmpc_qactor *q;                   // exactly one of q and pop (qshield_policy_check)
+    const stmpc_qactor_pop *pop;
+    int n_per_member;
+    const void *policy() const { return q ? (const void *)q : (const void *)pop; }
+};
+// its cfg, env cfg and policy (its reset and its step): `cc`, `fc` receive the kernels' forms.  Changes nothing.
+int qshield_cfg_check(const stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, const QShieldStep &qs, int N, CCfg *cc, FeatCfg *fc) {
+    const stmpc_qshield_env_cfg *sh = qs.cfg;
+    if (!sh) return fail(STMPC_EINVAL, "combined shield (Q) cfg is NULL");
+    if (!ec) return fail(STMPC_EINVAL, "env cfg is NULL");
+    if (sh->kmax < 1 || sh->kmax > STMPC_KMAX_LIMIT)
+        return fail(STMPC_EINVAL, "combined shield (Q) cfg: kmax must be 1 ... STMPC_KMAX_LIMIT (32), the solver's vehicles per state");
+    if (!(sh->takeover_penalty >= 0) || !(sh->takeover_penalty <= 1.7976931348623157e308))
+        return fail(STMPC_EINVAL, "combined shield (Q) cfg: takeover_penalty must be finite and not negative");
+    TRY(make_ccfg(p, &sh->cc, cc));
+    if (cc->remember_last) return fail(STMPC_EINVAL, "combined shield (Q) cfg: remember_last_choice must be 0 (the env keeps no takeover history per episode)");
+    TRY(check_batch(N, sh->kmax));
+    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
+    if (ec->action_mode == STMPC_ENV_CONTINUOUS_JERK)
+        return fail(STMPC_EINVAL, "stmpc_qshield_env_* serves STMPC_ENV_JERK and STMPC_ENV_ACCELERATION (the rollout policy is a Q-network): the continuous env "
+                                  "behind the combined controller is stmpc_cshield_env_reset_device / stmpc_cshield_env_step_device");
+    if (ec->action_mode != STMPC_ENV_JERK && ec->action_mode != STMPC_ENV_ACCELERATION) return fail(STMPC_EINVAL, "env cfg: unknown action_mode");
+    if (!ec->action_values || ec->n_action_values < 1 || ec->n_action_values > STMPC_ENV_MAX_ACTIONS)
+        return fail(STMPC_EINVAL, "a discrete env needs 1..STMPC_ENV_MAX_ACTIONS action_values");
+    if (sh->features.time_feature) return fail(STMPC_EINVAL, "a Q-network has no time feature: the features cfg must have time_feature = 0");
+    int n_in = 0;
+    TRY(qshield_policy_check(c, qs.q, qs.pop, qs.n_per_member, N, ec->action_mode == STMPC_ENV_ACCELERATION, ec->action_values, ec->n_action_values,
+                             ec->tick_length, ec->minimum_negative_jerk, ec->maximum_positive_jerk, &n_in));
+    // (the eval entries' checks of an empty batch: the features, the policy's input width; the rows are the context's own)
+    return actor_eval_checks(c, c->device, n_in, &sh->features, 0, sh->kmax, 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, fc);
+}
+
 // ---- one reset, one step and one reward body behind the plain, traffic-groups, reward-groups and shielded entries ----
 // Which env shapes an entry serves: a shape the context has and the entry refuses, or lacks and the entry requires, is STMPC_EINVAL.
 enum Need { REFUSED, EITHER, REQUIRED };
 struct EnvEntry {
     const char *reset_entry;                 // the reset entry that makes this entry's env (for messages)
-    Need traffic_groups, reward_groups, shield, traffic_mix, cshield;
+    Need traffic_groups, reward_groups, shield, traffic_mix, cshield, qshield = REFUSED;
 };
 const EnvEntry PLAIN_ENV{"stmpc_env_reset_device", REFUSED, REFUSED, EITHER, REFUSED, REFUSED};       // (on a shield-reset context: the unshielded step)
 // (the unshielded grouped entries refuse a shielded env: only the lone shielded env, whose world takes one cfg, has an unshielded step)
@@ -1443,6 +1483,7 @@ const EnvEntry REWARD_GROUPS_ENV{"stmpc_reward_groups_env_reset_device", EITHER,
 const EnvEntry SHIELD_ENV{"stmpc_shield_env_reset_device", REFUSED, REFUSED, REQUIRED, REFUSED, REFUSED};
 const EnvEntry TRAFFIC_MIX_ENV{"stmpc_traffic_mix_env_reset_device", REFUSED, REFUSED, REFUSED, REQUIRED, REFUSED};
 const EnvEntry CSHIELD_ENV_ENTRY{"stmpc_cshield_env_reset_device", REFUSED, REFUSED, REFUSED, REFUSED, REQUIRED};
+const EnvEntry QSHIELD_ENV_ENTRY{"stmpc_qshield_env_reset_device", REFUSED, REFUSED, REFUSED, REFUSED, REFUSED, REQUIRED};
 const EnvEntry SHIELD_TRAFFIC_GROUPS_ENV{"stmpc_shield_traffic_groups_env_reset_device", REQUIRED, REFUSED, REQUIRED, REFUSED, REFUSED};
 const EnvEntry SHIELD_REWARD_GROUPS_ENV{"stmpc_shield_reward_groups_env_reset_device", EITHER, REQUIRED, REQUIRED, REFUSED, REFUSED};
 const EnvEntry SHIELD_TRAFFIC_MIX_ENV{"stmpc_shield_traffic_mix_env_reset_device", REFUSED, REFUSED, REQUIRED, REQUIRED, REFUSED};
@@ -1457,6 +1498,7 @@ int env_shape_check(const stmpc_ctx *c, const EnvEntry &who) {
          "the environment in this context was not reset through stmpc_shield_env_reset_device or a shielded reset entry of its groups"},
         {c->env.N >= 1 && c->env.T >= 1, who.traffic_mix, MIXED_ENV, "the environment in this context was not reset through stmpc_traffic_mix_env_reset_device"},
         {has_cshield_env(c), who.cshield, CSHIELD_ENV, "the environment in this context was not reset through stmpc_cshield_env_reset_device"},
+        {has_qshield_env(c), who.qshield, QSHIELD_ENV, "the environment in this context was not reset through stmpc_qshield_env_reset_device"},
     };
     for (const auto &sh : shapes) {
         if (sh.has && sh.need == REFUSED) return fail(STMPC_EINVAL, sh.refused);
@@ -1567,7 +1609,7 @@ void env_world_step(stmpc_ctx *c, const DevP &dp, double crash_min_s, const env:
 
 // Step.  `g`: the cfg of a lone world (NULL: the entry takes none); `sh`: the shielded step's arguments, or NULL.
 int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const EnvEntry &who, const StepOut &o,
-             const ShieldStep *sh = nullptr, const MixStep *mix = nullptr, const CShieldStep *cs = nullptr) {
+             const ShieldStep *sh = nullptr, const MixStep *mix = nullptr, const CShieldStep *cs = nullptr, const QShieldStep *qs = nullptr) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     TRY(env_shape_check(c, who));
     if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, std::string("N does not match ") + who.reset_entry);
@@ -1579,6 +1621,10 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
         TRY(cshield_cfg_check(c, p, cs->cfg, cs->actor, N, &cs_cc, &cs_fc));
         if (cs->cfg->kmax != u.kmax || cs->cfg->rollout_time != u.rollout_time || cs_cc.rollout_length != u.L)
             return fail(STMPC_EINVAL, "combined shield cfg: kmax, rollout_time or the rollout length differs from the one the context was reset with (stmpc_cshield_env_reset_device)");
+    } else if (qs) {
+        TRY(qshield_cfg_check(c, p, ec, *qs, N, &cs_cc, &cs_fc));
+        if (qs->cfg->kmax != u.kmax || cs_cc.rollout_length != u.L || qs->policy() != u.qpolicy || qs->n_per_member != u.n_per_member || ec->n_action_values != c->env.n_actions)
+            return fail(STMPC_EINVAL, "combined shield (Q): kmax, the rollout length, the policy, n_per_member or n_action_values differs from the one the context was reset with (stmpc_qshield_env_reset_device)");
     } else if (sh) {
         TRY(shield_cfg_check(p, sh->cfg, N));
         if (sh->cfg->kmax != v.kmax) return fail(STMPC_EINVAL, std::string("shield cfg: kmax differs from the one the context was reset with (") + who.reset_entry + ")");
@@ -1608,7 +1654,30 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
     const sim::State s = c->sim.state();
     const env::EState es = env_state(c);
     // the action stage: the command of every live environment
-    if (cs) {
+    if (qs) {
+        const env::CShieldView w = u.view();
+        const stmpc_combined_cfg *g = &qs->cfg->cc;
+        // 1. action handling, the planner's view into the start and the current rows, the first action (no time counter: a Q-network has no time feature)
+        hipLaunchKernelGGL(env::k_qshield_env_pre, grid, block, 0, st_, e, sc, N, u.kmax, s, es, o.action, w);
+        HIPCHK(hipGetLastError());
+        // 2. dqn.RLAgent.do_combined_control on that view: the bodies of stmpc_qactor_eval_device or stmpc_pop_qactor_eval_device (steps 2 ... L),
+        //    stmpc_rollout_step_device and stmpc_combined_decide_device
+        for (int step = 1; step <= cs_cc.rollout_length; ++step) {
+            if (step > 1 && qs->q)
+                TRY(qactor_eval_run(c, qs->q, cs_fc, N, u.kmax, step, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, nullptr, 0, nullptr, nullptr, u.jerk.as<double>(), o.stream));
+            else if (step > 1)
+                TRY(qactor_pop_eval_run(c, qs->pop, cs_fc, qs->n_per_member, u.kmax, step, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, nullptr, 0, nullptr, nullptr,
+                                        u.jerk.as<double>(), o.stream));
+            TRY(rollout_step_run(c, p, g, N, u.kmax, step, w.ego5, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, step > 1 ? u.jerk.as<double>() : w.first_action,
+                                 o.stream));
+        }
+        TRY(combined_decide_run(c, p, g, N, u.kmax, w.ego5, w.k, w.ox, w.ov, w.cur_ego4, w.cur_ox, w.cur_ov, w.first_action, nullptr, u.takeover.as<int32_t>(),
+                                u.reason.as<int32_t>(), u.speed.as<double>(), o.stream));
+        // 3. what is executed, and what the learner is told: the first-step shield's rule, unchanged (exec_action NULL: the index is not rewritten)
+        hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, qs->cfg->takeover_penalty, N, s, es, o.action, (const double *)u.speed.as<double>(),
+                           (const int *)u.takeover.as<int>(), (const int *)u.reason.as<int>(), u.count.as<int>(), u.tag.as<int>(), sh->takeover, sh->reason,
+                           sh->executed_jerk, (double *)nullptr, sh->takeover_ticks);
+    } else if (cs) {
         const env::CShieldView w = u.view();
         const stmpc_combined_cfg *g = &cs->cfg->cc;
         // 1. action handling, the planner's view into the start and the current rows, the first action, the rollout's time counter
@@ -1797,6 +1866,7 @@ int stmpc_cshield_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const st
     TRY(combined_ensure(c, N, sh->kmax, dp.H, true));         // (the sparse solve's compact batch too: a step may set cc.sparse_control either way)
     for (DevBuf *b : {&u.evals, &u.evals_tag, &u.count, &u.tag}) HIPCHK(hipMemsetAsync(b->p, 0, (size_t)N * 4, (hipStream_t)stream));
     u.N = N; u.kmax = sh->kmax; u.rollout_time = sh->rollout_time; u.L = cc.rollout_length; u.generation = c->sim.generation;
+    u.qpolicy = nullptr; u.n_per_member = 0;
     return STMPC_OK;
 }
 
@@ -1808,6 +1878,40 @@ int stmpc_cshield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stm
     const CShieldStep cs{sh, actor};
     return env_step(c, p, g, ec, N, CSHIELD_ENV_ENTRY, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, &out,
                     nullptr, &cs);
+}
+
+// The discrete envs behind dqn.RLAgent.do_combined_control (dqn.py:117-200) with DQNAgent.get_control (dqn.py:375-380) in the rollout: the plain reset,
+// then every buffer of the step and zeroed takeover counters.
+int stmpc_qshield_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_qshield_env_cfg *sh,
+                                   const stmpc_qactor *qactor, const stmpc_qactor_pop *qactor_pop, int n_per_member, int N, float *d_obs, int obs_stride,
+                                   void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    CCfg cc;
+    FeatCfg fc;
+    const QShieldStep qs{sh, qactor, qactor_pop, n_per_member};
+    TRY(qshield_cfg_check(c, p, ec, qs, N, &cc, &fc));
+    DevP dp;
+    TRY(make_devp(p, &dp));
+    HIPCHK(hipSetDevice(c->device));
+    auto &u = c->cshield;                        // (a world initialised below outdates an earlier combined-shield env by its generation)
+    TRY(stmpc_env_reset_device(c, p, g, ec, N, d_obs, obs_stride, stream));
+    TRY(u.ensure(N, sh->kmax));
+    TRY(c->cc.ensure(N, sh->kmax, cc.rollout_length));
+    TRY(combined_ensure(c, N, sh->kmax, dp.H, true));         // (the sparse solve's compact batch too: a step may set cc.sparse_control either way)
+    for (DevBuf *b : {&u.count, &u.tag}) HIPCHK(hipMemsetAsync(b->p, 0, (size_t)N * 4, (hipStream_t)stream));
+    u.N = N; u.kmax = sh->kmax; u.rollout_time = 0; u.L = cc.rollout_length; u.generation = c->sim.generation;
+    u.qpolicy = qs.policy(); u.n_per_member = n_per_member;
+    return STMPC_OK;
+}
+
+int stmpc_qshield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_qshield_env_cfg *sh,
+                                  const stmpc_qactor *qactor, const stmpc_qactor_pop *qactor_pop, int n_per_member, int N, const void *d_action, float *d_obs,
+                                  int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats,
+                                  uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk, int32_t *d_takeover_ticks, void *stream) {
+    const ShieldStep out{nullptr, d_takeover, d_reason, d_executed_jerk, nullptr, d_takeover_ticks};
+    const QShieldStep qs{sh, qactor, qactor_pop, n_per_member};
+    return env_step(c, p, g, ec, N, QSHIELD_ENV_ENTRY, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, &out,
+                    nullptr, nullptr, &qs);
 }
 
 int stmpc_cshield_env_evals_device(stmpc_ctx *c, int N, int32_t *d_evals, void *stream) {

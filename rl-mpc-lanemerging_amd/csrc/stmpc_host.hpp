@@ -16,6 +16,7 @@
 #include "stmpc_env_groups_kernels.hpp"
 #include "stmpc_shield_env_kernels.hpp"
 #include "stmpc_cshield_env_kernels.hpp"
+#include "stmpc_qshield_env_kernels.hpp"
 #include "stmpc_traffic_mix_kernels.hpp"
 #include "stmpc_shield_groups_kernels.hpp"
 #include "stmpc_solve_plan.hpp"
@@ -262,10 +263,14 @@ struct stmpc_ctx {
     } shield;
     // vector environment behind the combined controller (stmpc_cshield_env_*): the start and current rows of the rollout, the first action, the rollout
     // actor's time counter with the episode it was counted in, the decision, and the takeovers of each environment's current episode with theirs.  Valid
-    // while `generation` is the world's; kmax, rollout_time and L (the rollout length) are the reset's
+    // while `generation` is the world's; kmax, rollout_time and L (the rollout length) are the reset's.  The discrete env behind a Q-network
+    // (stmpc_qshield_env_*) keeps the same rows here -- a context holds one env -- without the time counter: `qpolicy` is then the reset's stmpc_qactor
+    // or stmpc_qactor_pop (NULL: the continuous env behind an actor), n_per_member the population's rows per member (0: a lone Q-actor)
     struct CShieldEnv {
         DevBuf ego5, k, ox, ov, cur_ego4, cur_ox, cur_ov, cur_oa, first_action, jerk, evals, evals_tag, speed, takeover, reason, count, tag;
         int N = 0, kmax = 0, rollout_time = 0, L = 0;
+        const void *qpolicy = nullptr;
+        int n_per_member = 0;
         int64_t generation = -1;
         int ensure(int n_, int kmax_) {
             const size_t n = (size_t)n_, row = n * kmax_ * 8;
@@ -346,6 +351,20 @@ int actor_raise_lds(int which, int device, size_t lds);
 // kept by the caller; the current device is `device`.
 struct LdsCeiling { size_t max[16] = {0}; };
 int raise_dynamic_lds(const void *fn, const char *kernel, LdsCeiling &ceiling, int device, size_t lds);
+
+// ---- defined in stmpc_learner.hip
+// stmpc_qactor_eval_device / stmpc_pop_qactor_eval_device after their argument checks (N >= 1): the entries' bodies, shared with stmpc_qshield_env_step_device
+int qactor_eval_run(stmpc_ctx *c, const stmpc_qactor *q, const FeatCfg &fc, int N, int Kmax, int step, const double *d_cur_ego4, const int32_t *d_k,
+                    const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa, float *d_feat, int feat_stride, int32_t *d_action, float *d_q,
+                    double *d_jerk, void *stream);
+int qactor_pop_eval_run(stmpc_ctx *c, const stmpc_qactor_pop *p, const FeatCfg &fc, int n_per_member, int Kmax, int step, const double *d_cur_ego4,
+                        const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa, float *d_feat, int feat_stride,
+                        int32_t *d_action, float *d_q, double *d_jerk, void *stream);
+// what stmpc_qshield_env_* requires of its rollout policy -- exactly one of q (a lone Q-actor on all N rows) and pop (P members, P * n_per_member == N):
+// the context's device, n_actions == n_values, the env's action mode, a table byte-identical to `values` and, in acceleration mode, the env's tick and
+// jerk limits.  *n_in receives the policy's input width.
+int qshield_policy_check(const stmpc_ctx *c, const stmpc_qactor *q, const stmpc_qactor_pop *pop, int n_per_member, int N, bool acceleration,
+                         const double *values, int n_values, double tick, double jerk_min, double jerk_max, int *n_in);
 
 // ---- defined in stmpc_solver.hip
 void host_t_values(const stmpc_params *p, int H, double *t);

@@ -1376,6 +1376,7 @@ struct stmpc_qactor {
     double tick = 0, jerk_min = 0, jerk_max = 0;
     DqnDev dev{};                           // a created actor: base.q (its own network), the shape and the counters ddpg_repack's kernel reads
     DevBuf net[11], cnt, table;             // (net, cnt: empty for a view)
+    std::vector<double> table_h;            // the host's copy of `table` (qshield_policy_check compares it with an env's)
     size_t lds = 0;
 };
 
@@ -1393,6 +1394,7 @@ int qactor_check_table(const double *action_values, int n_actions, int A, int mo
     return STMPC_OK;
 }
 int qactor_finish(stmpc_qactor *q, const double *action_values, stmpc_qactor **out) {
+    q->table_h.assign(action_values, action_values + q->A);
     int rc = upload(q->table, action_values, (size_t)q->A);
     if (!rc) rc = qactor_raise_lds(q->device, q->lds);
     if (rc) { stmpc_qactor_destroy(q); return rc; }
@@ -1475,6 +1477,15 @@ int stmpc_qactor_eval_device(stmpc_ctx *c, const stmpc_qactor *q, const stmpc_po
         return fail(STMPC_EINVAL, "acceleration mode needs the tick length and the jerk limits (stmpc_qactor_set_limits)");
     FeatCfg fc;
     TRY(actor_eval_checks(c, q->device, q->n_in, f, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, nullptr, d_feat, feat_stride, d_jerk, &fc));
+    return qactor_eval_run(c, q, fc, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_feat, feat_stride, d_action, d_q, d_jerk, stream);
+}
+
+}  // extern "C"
+
+// (stmpc_host.hpp) stmpc_qactor_eval_device after its argument checks (N >= 1)
+int qactor_eval_run(stmpc_ctx *c, const stmpc_qactor *q, const FeatCfg &fc, int N, int Kmax, int step, const double *d_cur_ego4, const int32_t *d_k,
+                    const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa, float *d_feat, int feat_stride, int32_t *d_action, float *d_q,
+                    double *d_jerk, void *stream) {
     const int *live;
     TRY(rollout_live(c, N, step, &live));
     HIPCHK(hipSetDevice(c->device));
@@ -1485,8 +1496,6 @@ int stmpc_qactor_eval_device(stmpc_ctx *c, const stmpc_qactor *q, const stmpc_po
     return STMPC_OK;
 }
 
-}  // extern "C"
-
 // ---- a population of Q-networks as policies (stmpc_pop_qactor_*): P members, one launch per evaluation; kernel in stmpc_qactor_pop_kernels.hpp ------
 struct stmpc_qactor_pop {
     int device = 0;
@@ -1495,6 +1504,9 @@ struct stmpc_qactor_pop {
                                             // stmpc_pop_dqn_per_enable go through Replay::wire, which writes the replay's part of dev.base alone)
     int P = 0, n_in = 0;
     size_t lds = 0;
+    // what qshield_policy_check compares with an env, per member: the mode, the limits, the host's copy of the action table
+    struct Meta { int mode; double tick, jerk_min, jerk_max; std::vector<double> table; };
+    std::vector<Meta> meta;
     const QActorMember *dev() const { return table.as<QActorMember>(); }
 };
 
@@ -1530,6 +1542,7 @@ int stmpc_pop_qactor_create(stmpc_ctx *c, const stmpc_qactor *const *qactors, in
     HIPCHK(hipSetDevice(c->device));
     stmpc_qactor_pop *p = new stmpc_qactor_pop();
     p->device = c->device; p->P = P; p->n_in = qactors[0]->n_in; p->lds = qactors[0]->lds;
+    for (int m = 0; m < P; ++m) p->meta.push_back({qactors[m]->mode, qactors[m]->tick, qactors[m]->jerk_min, qactors[m]->jerk_max, qactors[m]->table_h});
     int rc = upload(p->table, host.data(), host.size());
     if (!rc) rc = qactor_pop_raise_lds(c->device, p->lds);
     if (rc) { stmpc_pop_qactor_destroy(p); return rc; }
@@ -1555,8 +1568,17 @@ int stmpc_pop_qactor_eval_device(stmpc_ctx *c, const stmpc_qactor_pop *p, const 
     FeatCfg fc;
     TRY(actor_eval_checks(c, p->device, p->n_in, f, N, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, nullptr, d_feat, feat_stride, d_jerk, &fc));
     if (N == 0) return STMPC_OK;
+    return qactor_pop_eval_run(c, p, fc, n_per_member, Kmax, step, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, d_feat, feat_stride, d_action, d_q, d_jerk, stream);
+}
+
+}  // extern "C"
+
+// (stmpc_host.hpp) stmpc_pop_qactor_eval_device after its argument checks (P * n_per_member >= 1)
+int qactor_pop_eval_run(stmpc_ctx *c, const stmpc_qactor_pop *p, const FeatCfg &fc, int n_per_member, int Kmax, int step, const double *d_cur_ego4,
+                        const int32_t *d_k, const double *d_cur_ox, const double *d_cur_ov, const double *d_cur_oa, float *d_feat, int feat_stride,
+                        int32_t *d_action, float *d_q, double *d_jerk, void *stream) {
     const int *live;
-    TRY(rollout_live(c, N, step, &live));
+    TRY(rollout_live(c, n_per_member * p->P, step, &live));
     HIPCHK(hipSetDevice(c->device));
     hipLaunchKernelGGL(k_qactor_eval_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, p->P), dim3(AT_THREADS), p->lds, (hipStream_t)stream, fc, p->dev(), n_per_member, Kmax,
                        d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, d_feat, feat_stride, d_action, d_q, d_jerk);
@@ -1564,4 +1586,33 @@ int stmpc_pop_qactor_eval_device(stmpc_ctx *c, const stmpc_qactor_pop *p, const 
     return STMPC_OK;
 }
 
-}  // extern "C"
+// (stmpc_host.hpp) the rollout policy of stmpc_qshield_env_*: a lone Q-actor, or a population on slices of the env's rows
+int qshield_policy_check(const stmpc_ctx *c, const stmpc_qactor *q, const stmpc_qactor_pop *pop, int n_per_member, int N, bool acceleration,
+                         const double *values, int n_values, double tick, double jerk_min, double jerk_max, int *n_in) {
+    if (!q == !pop) return fail(STMPC_EINVAL, "combined shield (Q): exactly one of the Q-actor and the Q-actor population must be given, the other NULL");
+    if ((q ? q->device : pop->device) != c->device) return fail(STMPC_EINVAL, "combined shield (Q): the policy and the context are on different devices");
+    if (q && n_per_member != 0) return fail(STMPC_EINVAL, "combined shield (Q): n_per_member belongs to a population (0 with a lone Q-actor)");
+    if (pop && (n_per_member < 1 || (long long)n_per_member * pop->P != N))
+        return fail(STMPC_EINVAL, "combined shield (Q): the population's P * n_per_member must be the env's N (" + std::to_string(pop->P) + " * " +
+                                  std::to_string(n_per_member) + " != " + std::to_string(N) + ")");
+    const int members = q ? 1 : pop->P;
+    for (int m = 0; m < members; ++m) {
+        const int mode = q ? q->mode : pop->meta[m].mode;
+        const std::vector<double> &table = q ? q->table_h : pop->meta[m].table;
+        const std::string who = q ? std::string("the Q-actor") : "member " + std::to_string(m);
+        if ((int)table.size() != n_values)
+            return fail(STMPC_EINVAL, "combined shield (Q): " + who + " has " + std::to_string(table.size()) + " actions, the env's table n_action_values = " + std::to_string(n_values));
+        if ((mode == STMPC_QACTOR_ACCELERATION) != acceleration)
+            return fail(STMPC_EINVAL, "combined shield (Q): the mode of " + who + " is not the env's action mode (STMPC_QACTOR_JERK with STMPC_ENV_JERK, STMPC_QACTOR_ACCELERATION with STMPC_ENV_ACCELERATION)");
+        if (memcmp(table.data(), values, (size_t)n_values * 8) != 0)
+            return fail(STMPC_EINVAL, "combined shield (Q): the action table of " + who + " is not byte-identical to the env's action_values");
+        if (acceleration) {
+            const bool has = q ? q->limits : true;          // (a population refuses an acceleration member without limits at create)
+            const double t = q ? q->tick : pop->meta[m].tick, lo = q ? q->jerk_min : pop->meta[m].jerk_min, hi = q ? q->jerk_max : pop->meta[m].jerk_max;
+            if (!has || t != tick || lo != jerk_min || hi != jerk_max)
+                return fail(STMPC_EINVAL, "combined shield (Q): the tick length and jerk limits of " + who + " (stmpc_qactor_set_limits) are not the env's");
+        }
+    }
+    *n_in = q ? q->n_in : pop->n_in;
+    return STMPC_OK;
+}

@@ -1273,20 +1273,68 @@ class DQNPopulation(DDPGPopulation):
         return {"loss": s[:, 0].copy(), "mean_q": s[:, 1].copy(), "fill": s[:, 2].astype(np.int64), "updates": s[:, 3].astype(np.int64)}
 
 
+class _TakeoverShare:
+    """What ``train_ddpg`` and ``train_dqn`` count on a shielded env: the ticks on which the shield overruled the action and the live ticks, summed on
+    the device at every step (no host synchronisation) and read at the drains.  Without autoreset a finished environment idles: not a live tick.
+    ``P`` > 0: per member too, the owner of row e being e // ``n_per_member``."""
+
+    def __init__(self, env, P=0, n_per_member=0):
+        torch = env.torch
+        self.env, self.P = env, int(P)
+        self.taken, self.lived = torch.zeros((), dtype=torch.int64, device=env.device), torch.zeros((), dtype=torch.int64, device=env.device)
+        self.alive = torch.ones(env.n, dtype=torch.bool, device=env.device)
+        self.takeover_ticks = self.live_ticks = 0
+        if self.P:
+            self.owner = torch.arange(env.n, device=env.device) // int(n_per_member)
+            self.member_taken, self.member_lived = (torch.zeros(self.P, dtype=torch.int64, device=env.device) for _ in range(2))
+            self.member_ticks = ([0] * self.P, [0] * self.P)
+
+    def step(self, info, term, trunc):
+        self.taken += info["takeover"].sum()
+        self.lived += self.alive.sum()
+        if self.P:
+            self.member_taken.index_add_(0, self.owner, info["takeover"].to(self.env.torch.int64))
+            self.member_lived.index_add_(0, self.owner, self.alive.to(self.env.torch.int64))
+        if not self.env.autoreset:
+            self.alive &= ~(term | trunc)
+
+    def read(self):
+        """At a drain: the loop has just synchronised."""
+        self.takeover_ticks, self.live_ticks = int(self.taken.item()), int(self.lived.item())
+        if self.P:
+            self.member_ticks = (self.member_taken.tolist(), self.member_lived.tolist())
+
+    @property
+    def share(self):
+        return self.takeover_ticks / self.live_ticks if self.live_ticks else 0.0
+
+    @property
+    def member_share(self):
+        return [t / l if l else 0.0 for t, l in zip(*self.member_ticks)]
+
+
 def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_schedule=None, lr_schedule=None):
     """The loop of the reference's ``DQNAgent._train`` on the device: act (epsilon-greedy) -> env.step -> push -> ``updates_per_step`` updates,
     until ``frames`` transitions were collected (rounded up to whole steps of env.n).  ``eps_schedule(step, steps) -> eps`` (None:
     ``dqn_epsilon(step)``, the reference's decay with the step for the episode number); ``lr_schedule(step, steps) -> lr``.  Synchronises only
-    every ``drain_every`` steps.  The result has ``train_ddpg``'s keys (``takeover_share`` 0.0: no shield).
+    every ``drain_every`` steps.  The result has ``train_ddpg``'s keys.
     ``learner`` may be a ``DQNPopulation`` (both schedules may then return per-member arrays); the result then also carries ``member_returns``:
-    the drained returns of each member's environments, a list of P arrays (owner = env index // n_per_member), as ``train_ddpg``'s does."""
+    the drained returns of each member's environments, a list of P arrays (owner = env index // n_per_member), as ``train_ddpg``'s does.
+    On a shielded env (a discrete ``MergeVecEnv(shield="first_step")``, ``vec_env.GroupedShieldVecEnv`` or ``vec_env.QCombinedShieldVecEnv``) the
+    result's ``takeover_share`` is the share of the live ticks on which the shield overruled the action (summed on the device, read at the drains,
+    as ``train_ddpg`` does it; 0.0 on an env without a ``shield``), and with a ``DQNPopulation`` ``member_takeover_share`` is that share per member,
+    a list of P floats (owner = env index // n_per_member)."""
+    pop = isinstance(learner, DQNPopulation)
     steps = -(-int(frames) // env.n)
     obs = env.reset()
     returns, envs = [], []
+    shield = _TakeoverShare(env, learner.P if pop else 0, learner.n_per_member if pop else 0) if getattr(env, "shield", None) is not None else None
     for i in range(steps):
         action = learner.act(obs, None, eps=eps_schedule(i, steps) if eps_schedule is not None else dqn_epsilon(i))
         next_obs, reward, term, trunc, info = env.step(action)
         learner.push(obs, None, action, reward, next_obs, term, trunc, final_obs=info["final_observation"])
+        if shield is not None:
+            shield.step(info, term, trunc)
         if updates_per_step:
             learner.update(updates_per_step, lr_schedule(i, steps) if lr_schedule is not None else None)
         obs = next_obs
@@ -1294,12 +1342,16 @@ def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_sche
             drained = env.drain_episode_stats()
             returns.append(drained["episode_return"])
             envs.append(drained["env"])
+            if shield is not None:
+                shield.read()
     returns = np.concatenate(returns) if returns else np.zeros(0)
     out = {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
-           "returns": returns, "takeover_share": 0.0}
-    if isinstance(learner, DQNPopulation):
+           "returns": returns, "takeover_share": shield.share if shield is not None else 0.0}
+    if pop:
         owner = (np.concatenate(envs) if envs else np.zeros(0, dtype=np.int64)) // learner.n_per_member
         out["member_returns"] = [returns[owner == m] for m in range(learner.P)]
+        if shield is not None:
+            out["member_takeover_share"] = shield.member_share
     return out
 
 
@@ -1326,21 +1378,14 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
     steps = -(-int(frames) // env.n)
     obs = env.reset()
     returns, envs = [], []
-    if shielded:
-        torch = env.torch
-        taken, lived = torch.zeros((), dtype=torch.int64, device=env.device), torch.zeros((), dtype=torch.int64, device=env.device)
-        alive = torch.ones(env.n, dtype=torch.bool, device=env.device)       # (without autoreset a finished environment idles: not a live tick)
-    takeover_ticks = live_ticks = 0
+    shield = _TakeoverShare(env) if shielded else None
     for i in range(steps):
         ticks = env.episode_ticks.clone()
         action = learner.act(obs, ticks, noise=True)
         next_obs, reward, term, trunc, info = env.step(action)
         learner.push(obs, ticks, info["executed_action"] if executed_actions else action, reward, next_obs, term, trunc, final_obs=info["final_observation"])
         if shielded:
-            taken += info["takeover"].sum()
-            lived += alive.sum()
-            if not env.autoreset:
-                alive &= ~(term | trunc)
+            shield.step(info, term, trunc)
         if updates_per_step:
             lr_q, lr_pi = lr_schedule(i, steps) if lr_schedule is not None else (None, None)
             learner.update(updates_per_step, lr_q, lr_pi)
@@ -1350,10 +1395,10 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
             returns.append(drained["episode_return"])
             envs.append(drained["env"])
             if shielded:
-                takeover_ticks, live_ticks = int(taken.item()), int(lived.item())
+                shield.read()
     returns = np.concatenate(returns) if returns else np.zeros(0)
     out = {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
-           "returns": returns, "takeover_share": takeover_ticks / live_ticks if live_ticks else 0.0}
+           "returns": returns, "takeover_share": shield.share if shielded else 0.0}
     if isinstance(learner, DDPGPopulation):
         owner = (np.concatenate(envs) if envs else np.zeros(0, dtype=np.int64)) // learner.n_per_member
         out["member_returns"] = [returns[owner == m] for m in range(learner.P)]

@@ -169,6 +169,10 @@ _LEAD = {
     "shield_traffic_mix_env_reset": "params mix_cfgs mix_weights mix_seed cfg shield_cfg n", "shield_traffic_mix_env_step": "params cfg shield_cfg n",
     "cshield_env_reset": "params sim_cfg cfg shield_cfg _actor n", "cshield_env_step": "params sim_cfg cfg shield_cfg _actor n",
 }
+#: the discrete env behind the combined shield with a Q-network in the rollout (``QCombinedShieldVecEnv``): a class of its own with entries of its own,
+#: bound by that class -- ``env_entries`` and ``_LEAD`` describe the shapes ``MergeVecEnv``'s arguments can express and stay as they are
+_Q_ENTRIES = ("qshield_env_reset", "qshield_env_step")
+_Q_LEAD = {name: "params sim_cfg cfg shield_cfg _qactor _qpop _n_per_member n" for name in _Q_ENTRIES}
 _MIX_ALONE = ("a traffic mix with traffic groups, reward groups or a shield is out of scope: the mixed step serves one ungrouped world "
               "under one reward, unshielded")
 
@@ -304,10 +308,12 @@ class MergeVecEnv:
         penalty, = _shield_args(takeover_penalty, shield_kmax)
         return _capi.ShieldEnvCfg.from_settings(Settings, shield_sparse, penalty, shield_kmax)
 
-    def _setup(self, n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic=None, rewards=None, mix=None, shield=None, shield_cfg=None, policy=None):
+    def _setup(self, n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic=None, rewards=None, mix=None, shield=None, shield_cfg=None, policy=None,
+               entries=None):
         """What every constructor ends in, after its own checks: the env's settings and world (the remaining ValueErrors, all before the first device
         call), its context and tensors, the shield's outputs (``shield``: None, "first_step" or "combined", with its ``shield_cfg``; ``policy``: the
-        combined shield's actor), the mix's (``mix``: what ``_mix_args`` returns) and the env's two entries, bound once."""
+        combined shield's actor), the mix's (``mix``: what ``_mix_args`` returns) and the env's two entries, bound once (``entries``: a class's own pair
+        instead of ``env_entries``' -- it has then set the attributes of its leading arguments itself)."""
         self.shield, self.shield_cfg = shield, shield_cfg
         self.env_id = Settings.GYM_ENVIRONMENT if env_id is None else env_id
         self.reward_name = Settings.REWARD_FUNCTION if reward is None else reward
@@ -324,7 +330,8 @@ class MergeVecEnv:
         if self.R and self.n % self.R:
             raise ValueError("n = %d environments do not divide into %d reward groups of equal size" % (self.n, self.R))
         self.n_per_reward_group = self.n // self.R if self.R else 0
-        entries = env_entries(shield, mix is not None, self.R, self.G)       # (ValueError unless R and G coincide)
+        table_entries = env_entries(shield, mix is not None, self.R, self.G)       # (ValueError unless R and G coincide)
+        entries = table_entries if entries is None else entries
         self.reward_names = [r.get("REWARD_FUNCTION", Settings.REWARD_FUNCTION) for r in self.rewards] if self.R else [self.reward_name]
         if self.R:
             self.cfg = self.reward_cfgs[0]                   # (the shared fields: what the step entry reads of it)
@@ -365,7 +372,7 @@ class MergeVecEnv:
             self._takeover, self._reason = z(self.n, dtype=torch.bool), z(self.n, dtype=torch.int32)
             self._exec_jerk, self._takeover_ticks = z(self.n), z(self.n, dtype=torch.int32)
             self._exec_action = z(self.n) if self.continuous else None
-            out += [self._takeover, self._reason, self._exec_jerk, self._exec_action, self._takeover_ticks]
+            out += [self._takeover, self._reason, self._exec_jerk] + ([self._exec_action] if entries != _Q_ENTRIES else []) + [self._takeover_ticks]
             self._info.update(takeover=self._takeover, reason=self._reason, executed_jerk=self._exec_jerk, takeover_ticks=self._takeover_ticks)
             if self._exec_action is not None:
                 self._info["executed_action"] = self._exec_action
@@ -374,7 +381,8 @@ class MergeVecEnv:
             out += [self._type, self._final_type]
             reset_tail = [self._type]
             self._info.update(traffic_type=self._type, final_traffic_type=self._final_type)
-        self._actor = policy.handle if policy is not None else None
+        if entries != _Q_ENTRIES:
+            self._actor = policy.handle if policy is not None else None
         self._bind(entries, reset_tail, out)
 
     def _bind(self, entries, reset_tail, step_out):
@@ -384,7 +392,8 @@ class MergeVecEnv:
         NULL pointer).  ``_setup`` is its only caller, and every constructor calls ``_setup`` once."""
         if hasattr(self, "_step"):
             raise RuntimeError("an env binds its entries once")
-        bound = lambda name: functools.partial(getattr(self.ctx, name), *(getattr(self, a) for a in _LEAD[name].split()))
+        lead = lambda name: (_LEAD[name] if name in _LEAD else _Q_LEAD[name]).split()
+        bound = lambda name: functools.partial(getattr(self.ctx, name), *(getattr(self, a) for a in lead(name)))
         ptrs = lambda tensors: tuple(t.data_ptr() if t is not None else 0 for t in tensors)
         self._reset, self._reset_tail = bound(entries[0]), ptrs(reset_tail)
         self._step, self._step_out = bound(entries[1]), ptrs(step_out)
@@ -581,6 +590,98 @@ class CombinedShieldVecEnv(MergeVecEnv):
         ``rollout_time="env"``, the episode's policy evaluations so far under "deployed" -- the ``evals`` to hand to an actor that proposes the action."""
         self.ctx.cshield_env_evals(self.n, self._evals.data_ptr(), self._stream())
         return self._evals
+
+    def shield_counts(self, reset=False):
+        """(states decided, controller solves run for them) on this env's context since the last reset of the counts (``stmpc_combined_counts``:
+        finished environments of a run without autoreset are decided too, and count; equal unless ``shield_sparse``)."""
+        return self.ctx.combined_counts(reset)
+
+
+def q_first_action_host(env_id, index, ego_acc, S=Settings):
+    """The host twin of ``k_qshield_env_pre``'s first action in numpy fp64, operation for operation: the jerk rollout step 1 of
+    ``QCombinedShieldVecEnv`` applies for the action indices ``index`` [n] on states whose view has the ego accelerations ``ego_acc`` [n] -- the
+    table's entry on "sumo-jerk-v0"; ``clip((table[a] - ego_acc) / TICK_LENGTH, MINIMUM_NEGATIVE_JERK, MAXIMUM_POSITIVE_JERK)`` on "sumo-accel-v0"
+    (``actor.q_policy_host``'s rule); 0.0 for an index out of range.  Returns (first_action fp64 [n], out_of_range bool [n])."""
+    if env_id not in QCombinedShieldVecEnv.MODE_OF:
+        raise ValueError("a discrete env id ('sumo-jerk-v0' or 'sumo-accel-v0'), not %r" % (env_id,))
+    values = S.JERK_VALUES_DQN if env_id == "sumo-jerk-v0" else S.ACCELERATION_VALUES_DQN
+    table = np.array([values[i] for i in range(len(values))], dtype=np.float64)              # (index order, as env_cfg reads it)
+    index = np.asarray(index, dtype=np.int64).reshape(-1)
+    bad = (index < 0) | (index >= table.size)
+    value = table[np.where(bad, 0, index)]
+    if env_id == "sumo-accel-v0":
+        value = (value - np.asarray(ego_acc, dtype=np.float64).reshape(-1)) / float(S.TICK_LENGTH)
+        lo, hi = float(S.MINIMUM_NEGATIVE_JERK), float(S.MAXIMUM_POSITIVE_JERK)
+        value = np.where(value < lo, lo, np.where(value > hi, hi, value))
+    return np.where(bad, 0.0, value), bad
+
+
+class QCombinedShieldVecEnv(MergeVecEnv):
+    """A DISCRETE ``MergeVecEnv`` ("sumo-jerk-v0", "sumo-accel-v0") whose every step runs behind the combined RL + ST controller,
+    ``dqn.RLAgent.do_combined_control`` (dqn.py:117-200) as ``DQNAgent`` inherits it, with a Q-network (``DQNAgent.get_control``, dqn.py:375-380)
+    proposing rollout steps 2 ... ROLLOUT_LENGTH on the device (``stmpc_qshield_env_reset_device`` / ``stmpc_qshield_env_step_device``): a DQN learner
+    trains in the closed loop ``evaluate_dqn`` and ``EpisodeRunner(controller="combined")`` deploy it in.  A class of its own:
+    ``CombinedShieldVecEnv`` stays the continuous env's and keeps refusing the discrete ids.
+
+    The action INDEX handed to ``step`` is the controller's first action: its jerk is the table's entry ("sumo-jerk-v0") or, on "sumo-accel-v0",
+    ``clip((table[a] - ego acceleration) / TICK_LENGTH, MINIMUM_NEGATIVE_JERK, MAXIMUM_POSITIVE_JERK)`` -- what ``policy`` itself returns for that index
+    on that state.  ``info`` has ``takeover``, ``reason`` (``combined.REASON_*``), ``executed_jerk`` and ``takeover_ticks``, and no ``executed_action``: a
+    takeover's speed is no table entry, so the index is not rewritten (as on the first-step-shielded discrete env).  ``env.shield == "combined"``:
+    ``learner.train_dqn`` runs on it as on a shielded env.  There is no time feature, hence no ``rollout_time`` and no ``rollout_evals``.
+
+    ``policy``: a hip-engine ``actor.DQNActor`` of ``n`` rows on the env's context (``ctx`` defaults to the policy's) -- an ``export_q`` file, or
+    ``DQNActor.from_learner(learner, n, ctx, S, target=...)``, a zero-copy view, so a step queued after ``learner.update`` on the same stream rolls out
+    with the updated weights -- or an ``actor.QActorPopulation`` with ``P * n_per_member == n``: member m proposes for rows ``[m * n_per_member, (m + 1)
+    * n_per_member)`` of the one world.  Its mode and action table must be the env's ("jerk" with JERK_VALUES_DQN, "acceleration" with
+    ACCELERATION_VALUES_DQN, byte for byte).  The env keeps it alive.
+    ``control``, ``shield_sparse``, ``takeover_penalty``, ``shield_kmax``: as ``CombinedShieldVecEnv`` takes them; ``shield_counts()`` reads
+    ``(decisions, controller solves)``.
+
+    Refused with a ValueError before any device call: a continuous or unknown env id, an ``actor.DDPGActor``, an ``actor.ActorPopulation`` or anything
+    else that is no hip-engine ``DQNActor`` / ``QActorPopulation``, a mode or table that is not the env's, another ``n`` or context,
+    ``REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED`` true, a bad ``takeover_penalty`` or ``shield_kmax``.  Out of scope: traffic groups, reward groups
+    and the traffic mix behind this shield."""
+
+    MODE_OF = {"sumo-jerk-v0": "jerk", "sumo-accel-v0": "acceleration"}
+
+    def __init__(self, n, policy, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, *, shield_sparse=False, takeover_penalty=0.0,
+                 shield_kmax=32, control=None):
+        from . import actor as _actor, combined
+        env_id_ = Settings.GYM_ENVIRONMENT if env_id is None else env_id
+        if env_id_ not in ENV_IDS:
+            raise ValueError("Invalid gym environment {} (one of {})".format(env_id_, ", ".join(ENV_IDS)))
+        if env_id_ not in self.MODE_OF:
+            raise ValueError("the combined shield behind a Q-network serves 'sumo-jerk-v0' and 'sumo-accel-v0', not %r: the continuous env's is "
+                             "CombinedShieldVecEnv" % (env_id_,))
+        if isinstance(policy, (_actor.DDPGActor, _actor.ActorPopulation)):
+            raise ValueError("a DDPGActor or an ActorPopulation proposes continuous jerks: policy is an actor.DQNActor or an actor.QActorPopulation "
+                             "(the continuous env's class is CombinedShieldVecEnv)")
+        pop = isinstance(policy, _actor.QActorPopulation)
+        if not (pop or isinstance(policy, _actor.DQNActor)) or getattr(policy, "engine", None) != "hip" or getattr(policy, "handle", None) is None:
+            raise ValueError("policy must be a hip-engine actor.DQNActor (an export_q file, or DQNActor.from_learner) or an actor.QActorPopulation, not %r"
+                             % (policy,))
+        if int(n) < 1 or policy.n != int(n):
+            raise ValueError("the policy was built for %d rows%s, the env has n = %r"
+                             % (policy.n, " (P = %d members x n_per_member = %d)" % (policy.P, policy.n_per_member) if pop else "", n))
+        if ctx is not None and policy.ctx is not ctx:
+            raise ValueError("the policy lives on another context than the env's: build it on ctx (or leave ctx=None to take the policy's)")
+        table = np.ascontiguousarray(env_cfg(env_id_, reward, autoreset, Settings, log_capacity)._actions, dtype=np.float64)     # (ValueError for an unknown reward)
+        for m, a in enumerate(policy.members if pop else [policy]):
+            who = "member %d" % m if pop else "the policy"
+            if a.mode != self.MODE_OF[env_id_]:
+                raise ValueError("%s is in %r mode, %r needs %r" % (who, a.mode, env_id_, self.MODE_OF[env_id_]))
+            if np.asarray(a.action_values, dtype=np.float64).tobytes() != table.tobytes():
+                raise ValueError("the action table of %s is not the env's (%s of the Settings, byte for byte)"
+                                 % (who, "JERK_VALUES_DQN" if env_id_ == "sumo-jerk-v0" else "ACCELERATION_VALUES_DQN"))
+        penalty, = _shield_args(takeover_penalty, shield_kmax)
+        self.control = dict(control) if control is not None else {}
+        combined.control_cfgs([self.control])                               # (ValueError for a key that is no setting of do_combined_control)
+        cfg = _capi.QShieldEnvCfg.from_settings(combined._Overlay(Settings, self.control), shield_sparse, penalty, shield_kmax, policy.fcfg)
+        if cfg.cc.remember_last_choice:
+            raise ValueError("REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED is out of scope behind the combined shield: the env keeps no takeover history")
+        self.policy = policy
+        self._qactor, self._qpop, self._n_per_member = (None, policy.handle, policy.n_per_member) if pop else (policy.handle, None, 0)
+        self._setup(n, env_id_, seed, reward, autoreset, policy.ctx, log_capacity, shield="combined", shield_cfg=cfg, entries=_Q_ENTRIES)
 
     def shield_counts(self, reset=False):
         """(states decided, controller solves run for them) on this env's context since the last reset of the counts (``stmpc_combined_counts``:

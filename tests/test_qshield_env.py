@@ -1,0 +1,684 @@
+"""The combined-controller shield of the DISCRETE vector environments on the GPU (csrc/stmpc_qshield_env_kernels.hpp; stmpc_qshield_env_* of
+include/stmpc.h; vec_env.QCombinedShieldVecEnv): the fused step equals the composition of the pinned public pieces, bit for bit.
+
+Shape unless stated: n = 100 (a full 64-thread workgroup and a partial one; six full Q-actor tiles of 16 rows and one of 4), the "default" traffic,
+shield_kmax = 8, world seed 7, Q-networks 20 -> 16 -> 5 on "sumo-jerk-v0" and 20 -> 48 -> 20 on "sumo-accel-v0" with seeded random weights, actions:
+for every (environment, episode tick) a fixed hash picks the policy's own step-1 index or a uniform index.  Every run is recorded once
+(``_recorded_run``) and shared by the tests that need it."""
+import os
+
+import numpy as np
+import pytest
+
+from stmpc_testlib import pkg as _pkg, same as _same
+
+N, KMAX, SEED = 100, 8, 7
+TICKS = 200            # (the continuous env needed 200 ticks at this N for episodes to end, on and off takeover ticks, and restart)
+# under L = 3, T = 2 these policies end no episode before the world's time limit (MAX_EPISODE_LENGTH: 500 ticks; measured: the first episode ends at
+# tick 499, and all 100 do), so that cell's run is lengthened past it: every episode is truncated, restarts, and runs ten ticks of its episode 1
+TICKS_OF = {"default": TICKS, "L3T2": 510}
+CELLS = {"default": {}, "L3T2": {"ROLLOUT_LENGTH": 3, "ST_TEST_ROLLOUTS": 2}}
+HIDDEN = {"sumo-jerk-v0": 16, "sumo-accel-v0": 48}
+SHIELD_KEYS = ("takeover", "reason", "executed_jerk", "takeover_ticks")
+KEYS = ("obs", "reward", "term", "trunc", "final_obs", "final_stats") + SHIELD_KEYS
+WORLD = ("status", "sim_ticks", "acc", "ego4")
+_cache = {}
+
+
+def _settings():
+    pkg = _pkg()
+    from rl_mpc_lanemerging_amd import combined_bench, episodes
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
+    pkg.apply_overrides(episodes.TRAFFIC_TYPES["default"])
+    return pkg.Settings
+
+
+def _table(env_id):
+    from rl_mpc_lanemerging_amd import vec_env
+    return np.array(vec_env.env_cfg(env_id, "Continuous")._actions, dtype=np.float64)
+
+
+def _net(env_id, seed=0):
+    """Seeded random weights 20 -> HIDDEN -> A, large enough for the argmax to move with the state."""
+    rng = np.random.default_rng(1000 + seed)
+    h, A = HIDDEN[env_id], _table(env_id).size
+    return {"w0": rng.normal(0, 0.6, (h, 20)).astype(np.float32), "b0": rng.normal(0, 0.3, h).astype(np.float32),
+            "w1": rng.normal(0, 0.6, (A, h)).astype(np.float32), "b1": rng.normal(0, 0.3, A).astype(np.float32)}
+
+
+def _q_file(tmp, env_id, seed=0, net=None):
+    path = os.path.join(str(tmp), "q_%s_%d_%d.npz" % (env_id, seed, len(os.listdir(str(tmp)))))
+    with open(path, "wb") as fh:
+        np.savez(fh, **(net if net is not None else _net(env_id, seed)), action_values=_table(env_id))
+    return path
+
+
+def _mode(env_id):
+    return "jerk" if env_id == "sumo-jerk-v0" else "acceleration"
+
+
+def _file_actor(tmp, env_id, ctx, n=N, seed=0, net=None):
+    from rl_mpc_lanemerging_amd import actor
+    return actor.DQNActor(_q_file(tmp, env_id, seed, net), n, ctx, _settings(), mode=_mode(env_id))
+
+
+def _hash01(ticks, salt):
+    from rl_mpc_lanemerging_amd import groups
+    return np.array([(groups.splitmix64(((e << 32) + int(t) + salt * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF) >> 11) / 9007199254740992.0
+                     for e, t in enumerate(ticks)])
+
+
+def _mixed_actions(ticks, own, A):
+    """The policy's own index where the hash of (environment, episode tick) says so (half of them), else a uniform index from another hash."""
+    return np.where(_hash01(ticks, 1) < 0.5, own, np.minimum((_hash01(ticks, 2) * A).astype(np.int64), A - 1)).astype(np.int32)
+
+
+def _env(ctx, env_id, policy, **kw):
+    from rl_mpc_lanemerging_amd import vec_env
+    _settings()
+    kw.setdefault("shield_kmax", KMAX)
+    return vec_env.QCombinedShieldVecEnv(N, policy, env_id=env_id, seed=SEED, reward="Continuous", ctx=ctx, **kw)
+
+
+class _View:
+    """stmpc_sim_view_device of a context's world into buffers of its own."""
+
+    def __init__(self, ctx, K=KMAX):
+        import torch
+        z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device="cuda")
+        self.ctx, self.K, self.b = ctx, K, (z(N, 5), z(N, dtype=torch.int32), z(N, K), z(N, K), z(N, K))
+
+    def __call__(self, sim_cfg):
+        b = self.b
+        self.ctx.sim_view(sim_cfg, N, self.K, b[0].data_ptr(), b[1].data_ptr(), b[2].data_ptr(), b[3].data_ptr(), b[4].data_ptr())
+        return b
+
+
+def _own_index(pol, b):
+    """The policy's step-1 index on the view ``b``."""
+    pol(1, b[0][:, :4].contiguous(), b[1], b[2], b[3], b[4])
+    return pol.action.cpu().numpy().copy()
+
+
+def _recorded_run(tmp, env_id, ticks=TICKS, cell="default", sparse=False, autoreset=True, penalty=0.0, shield=True, actions=None, policy_of=None, tag=None):
+    """One run of the env on a context of its own: the actions, every output of every tick, the world after every tick, the drained log and the
+    combined controller's counts.  Cached: a reference is computed once and never changed."""
+    key = (env_id, ticks, cell, sparse, autoreset, penalty, shield, None if actions is None else hash(np.ascontiguousarray(actions).tobytes()), tag)
+    if key in _cache:
+        return _cache[key]
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, vec_env
+    _settings()
+    ctx = _capi.Context(-1)
+    if shield:
+        policy = policy_of(ctx) if policy_of is not None else _file_actor(tmp, env_id, ctx)
+        env = _env(ctx, env_id, policy, shield_sparse=sparse, autoreset=autoreset, takeover_penalty=penalty, control=CELLS[cell])
+        env.shield_counts(reset=True)
+        own_pol = policy_of(ctx) if policy_of is not None else _file_actor(tmp, env_id, ctx)
+    else:
+        env = vec_env.MergeVecEnv(N, env_id=env_id, seed=SEED, reward="Continuous", autoreset=autoreset, ctx=ctx)
+    A, view = env.action_space["n"], _View(ctx)
+    out = {k: [] for k in KEYS + WORLD + ("action", "ticks_before")}
+    out["obs0"] = env.reset().cpu().numpy().copy()
+    for t in range(ticks):
+        tb = env.episode_ticks.cpu().numpy().copy()
+        act = actions[t] if actions is not None else _mixed_actions(tb, _own_index(own_pol, view(env.sim_cfg)), A)
+        out["ticks_before"].append(tb)
+        obs, r, term, trunc, info = env.step(torch.as_tensor(act, device="cuda"))
+        out["action"].append(act)
+        for k, v in (("obs", obs), ("reward", r), ("term", term), ("trunc", trunc), ("final_obs", info["final_observation"]), ("final_stats", info["final_stats"])):
+            out[k].append(v.cpu().numpy().copy())
+        for k in SHIELD_KEYS:
+            if k in info:
+                out[k].append(info[k].cpu().numpy().copy())
+        for k, v in zip(WORLD, ctx.sim_read(N)):
+            out[k].append(v.copy())
+    out = {k: (np.stack(v) if isinstance(v, list) and v else v) for k, v in out.items()}
+    out["info_keys"] = set(info)
+    out["counts"] = env.shield_counts() if shield else None
+    out["shield_name"] = env.shield
+    out["drained"] = env.drain_episode_stats()
+    env.check_error()
+    ctx.close()
+    _cache[key] = out
+    return out
+
+
+class _Pieces:
+    """do_combined_control for N states from the public entries, on a context of its own: stmpc_rollout_step_device (step 1 with the first action's
+    jerk), stmpc_qactor_eval_device or stmpc_pop_qactor_eval_device (the policy's call) + stmpc_rollout_step_device (steps 2 ... L),
+    stmpc_combined_decide_device."""
+
+    def __init__(self, ctx, policy, cell, sparse=False):
+        import torch
+        from rl_mpc_lanemerging_amd import _capi, combined
+        self.torch, self.ctx, self.policy = torch, ctx, policy
+        self.S = _settings()
+        self.params = _capi.Params.from_settings(self.S)
+        self.ccfg = combined.control_cfgs([CELLS[cell]], sparse_control=sparse)[0]
+        self.L = max(int(self.ccfg.rollout_length), 1)
+        z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device="cuda")
+        self.take, self.reason, self.speed = z(N, dtype=torch.int32), z(N, dtype=torch.int32), z(N)
+
+    def decide(self, ego5, k, ox, ov, oa, first):
+        """-> takeover, reason, speed (host), the rolled-out ego rows (host)."""
+        c, p, g = self.ctx, self.params, self.ccfg
+        cur4, cox, cov, coa = ego5[:, :4].clone().contiguous(), ox.clone(), ov.clone(), oa.clone()
+        for step in range(1, self.L + 1):
+            a = first if step == 1 else self.policy(step, cur4, k, cox, cov, coa)
+            c.rollout_step_device(p, g, N, KMAX, step, ego5.data_ptr(), cur4.data_ptr(), k.data_ptr(), cox.data_ptr(), cov.data_ptr(), coa.data_ptr(), a.data_ptr())
+        c.combined_decide_device(p, g, N, KMAX, ego5.data_ptr(), k.data_ptr(), ox.data_ptr(), ov.data_ptr(), cur4.data_ptr(), cox.data_ptr(), cov.data_ptr(),
+                                 first.data_ptr(), 0, self.take.data_ptr(), self.reason.data_ptr(), self.speed.data_ptr())
+        return self.take.cpu().numpy() != 0, self.reason.cpu().numpy().copy(), self.speed.cpu().numpy().copy(), cur4.cpu().numpy()
+
+
+def _compose(tmp, rec, env_id, cell, penalty=0.0, policy_of=None, ticks=None):
+    """The recorded run made again from the public pieces (the construction of the continuous env's test with the Q-actor in the rollout and the host
+    twin of the first action in front).  A row in its episode 0 lives in a world of the composition's own (stmpc_sim_init_device ...
+    stmpc_sim_step_device with the decided speeds -- the controller's on a takeover, the action-handling twin's command else --, no autoreset) and everything it returned is compared: the world row, obs, reward, flags, final
+    obs, stats row, log row and the four shield outputs.  No public entry puts one row of a world into a later episode, so from its episode 1 on a
+    row's decision is made by the same pieces on stmpc_sim_view_device of the recorded world before the tick (compared: the four shield outputs, and
+    obs and reward from the view after the tick while the episode goes on); the start state of episode 1 is environment e of a fresh
+    stmpc_sim_init_device seeded episode_seed(seed, 1).  Returns what the run exercised."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, episodes, rewards, vec_env
+    S = _settings()
+    ticks = ticks if ticks is not None else rec["action"].shape[0]
+    make = policy_of if policy_of is not None else (lambda c: _file_actor(tmp, env_id, c))
+    ctx = _capi.Context(-1)
+    pieces = _Pieces(ctx, make(ctx), cell)
+    cfg = episodes.sim_cfg(SEED, float(S.MAX_EPISODE_LENGTH))
+    ecfg = vec_env.env_cfg(env_id, "Continuous", autoreset=False)
+    params = pieces.params
+    fcfg = _capi.FeaturesCfg.from_settings(S, time_feature=False)
+    dev = lambda a, dtype=None: torch.as_tensor(np.ascontiguousarray(a), device="cuda", dtype=dtype)
+    z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device="cuda")
+    WIDE = 32                                             # the env's own view has no cut: obs and reward are made from rows that hold every vehicle
+    feat, rew = z(N, 20, dtype=torch.float32), z(N)
+    tick = float(S.TICK_LENGTH)
+    a_min, a_max = float(S.MAX_NEGATIVE_ACCELERATION), float(S.MAX_POSITIVE_ACCELERATION)
+    j_min, j_max = float(S.MINIMUM_NEGATIVE_JERK), float(S.MAXIMUM_POSITIVE_JERK)
+
+    def features(b):
+        e4 = b[0][:, :4].contiguous()
+        assert int(b[1].max()) < WIDE                     # (the wide rows hold every vehicle in sight)
+        ctx.policy_features_device(fcfg, N, WIDE, 1, e4.data_ptr(), b[1].data_ptr(), b[2].data_ptr(), b[3].data_ptr(), b[4].data_ptr(), 0, feat.data_ptr(), 20)
+        return e4, feat.cpu().numpy().copy()
+
+    def reward_of(b, e4, jerk, crashed, arrived):
+        d_jerk, d_cr, d_ar = dev(jerk), dev(crashed.astype(np.int32)), dev(arrived.astype(np.int32))       # (kept alive until the kernel has read them)
+        ctx.env_reward(ecfg, N, WIDE, e4.data_ptr(), b[1].data_ptr(), b[2].data_ptr(), d_jerk.data_ptr(), d_cr.data_ptr(), d_ar.data_ptr(), rew.data_ptr())
+        return rew.cpu().numpy().copy()
+
+    # the recorded world before every tick, for the rows past their episode 0: a context that replays the recorded run (the env itself) so that
+    # stmpc_sim_view_device can be asked before and after each of its ticks
+    twin_ctx = _capi.Context(-1)
+    twin = _env(twin_ctx, env_id, make(twin_ctx), takeover_penalty=penalty, control=CELLS[cell], autoreset=True)
+    twin.reset()
+    ctx.sim_init(cfg, N)
+    own_v, seen_v, wide_v, after_v = _View(ctx), _View(twin_ctx), _View(ctx, WIDE), _View(twin_ctx, WIDE)
+    own = own_v(cfg)
+    assert _same(rec["obs0"], features(wide_v(cfg))[1])
+    ctx1 = _capi.Context(-1)                               # the start states of episode 1
+    cfg1 = episodes.sim_cfg(vec_env.episode_seed(SEED, 1), float(S.MAX_EPISODE_LENGTH))
+    ctx1.sim_init(cfg1, N)
+    start1 = features(_View(ctx1, WIDE)(cfg1))[1]
+    ep, prev_a, count, ret = np.zeros(N, np.int64), np.zeros(N), np.zeros(N, np.int32), np.zeros(N)
+    seen = {"kept": 0, "takeovers": 0, "reasons": set(), "ended": 0, "ended_taken": 0, "autoresets": 0, "later_rows": 0, "clipped": 0, "unclipped": 0, "rolled": []}
+    ended_rows = {}
+    for t in range(ticks):
+        first = ep == 0                                     # rows the composition's own world holds
+        seen_b = seen_v(twin.sim_cfg)
+        m = dev(first)
+        b = tuple(torch.where(m.reshape(-1, *([1] * (x.dim() - 1))), x, y) for x, y in zip(own, seen_b))
+        e5 = b[0].cpu().numpy()
+        sim_ticks = np.where(first, ctx.sim_read(N)[1], twin_ctx.sim_read(N)[1])
+        assert _same(rec["ticks_before"][t], sim_ticks.astype(np.int32)), t
+        act = rec["action"][t]
+        fa, bad = vec_env.q_first_action_host(env_id, act, e5[:, 3], S)        # the host twin of the first action
+        assert not bad.any()
+        take, reason, speed, rolled = pieces.decide(b[0], b[1], b[2], b[3], b[4], dev(fa, torch.float64))
+        seen["rolled"].append(rolled)
+        handled = [rewards.handle_action(env_id, float(e5[i, 2]), float(e5[i, 3]), float(prev_a[i]), int(act[i])) for i in range(N)]
+        cmd, pj, inv = (np.array([h[i] for h in handled]) for i in range(3))
+        ex_jerk = np.where(take, (np.clip((speed - e5[:, 2]) / tick, a_min, a_max) - prev_a) / tick, pj)
+        inv = np.where(take, inv + penalty * tick, inv)
+        count += take.astype(np.int32)
+        # every row, whatever its episode: the decision and what the learner is told
+        assert _same(rec["takeover"][t], take) and _same(rec["reason"][t], reason), t
+        assert _same(rec["executed_jerk"][t], ex_jerk), t
+        assert _same(rec["takeover_ticks"][t], count), t
+        # the world step: the composition's own world with the decided speeds -- the controller's where it took over, else the command of the env's
+        # action handling (k_shield_env_apply's rule; on "sumo-accel-v0" handle_acceleration's v + a * tick is not, bit for bit, the speed the
+        # decision reports for a kept proposal, which goes through the clipped jerk) --, the replayed env with the recorded action
+        d_speed = dev(np.where(take, speed, cmd))
+        ctx.sim_step(params, cfg, N, d_speed.data_ptr())
+        twin.step(dev(act, torch.int32))
+        status, w_ticks, acc, ego4 = ctx.sim_read(N)
+        t_status, _, _, t_ego4 = twin_ctx.sim_read(N)
+        for name, got, want in (("status", rec["status"][t], status), ("ticks", rec["sim_ticks"][t], w_ticks), ("acc", rec["acc"][t], acc), ("ego", rec["ego4"][t], ego4)):
+            keep = first & (status == 0)                    # (a row that ended was reset in the same step: its final row is in final_stats and the log)
+            assert _same(got[keep], want[keep]), (name, t)
+        own = own_v(cfg)
+        wide = wide_v(cfg)
+        e4, f_own = features(wide)
+        crashed, arrived = status == 2, status == 1
+        ended = crashed | arrived
+        over = first & (status != 0)
+        jerk = np.where(ended, ex_jerk, (ego4[:, 3] - prev_a) / tick)
+        r_own = reward_of(wide, e4, jerk, crashed, arrived) + inv
+        after_b = after_v(twin.sim_cfg)
+        e4b, f_after = features(after_b)
+        r_after = reward_of(after_b, e4b, (t_ego4[:, 3] - prev_a) / tick, np.zeros(N, bool), np.zeros(N, bool)) + inv
+        done = rec["term"][t] | rec["trunc"][t]
+        later = ~first & ~done                              # rows past episode 0 whose episode goes on: obs and reward from the view after the tick
+        assert _same(rec["reward"][t][first], r_own[first]) and _same(rec["reward"][t][later], r_after[later]), t
+        assert _same(rec["term"][t][first], ended[first]) and _same(rec["trunc"][t][first], (status == 3)[first]), t
+        final_obs = np.where(ended[:, None], np.float32(0), f_own)
+        assert _same(rec["obs"][t][first & ~over], f_own[first & ~over]) and _same(rec["obs"][t][later], f_after[later]), t
+        assert _same(rec["obs"][t][over], start1[over]), t                  # the autoreset: the observation of episode 1's start state
+        assert _same(rec["final_obs"][t][over], final_obs[over]), t
+        ret = ret + rec["reward"][t]
+        for e in np.nonzero(over)[0]:
+            want_row = np.concatenate([acc[e], [float(status[e]), float(w_ticks[e]), ret[e]]])
+            assert _same(rec["final_stats"][t][e], want_row), (t, e)
+            ended_rows[int(e)] = want_row
+        seen["kept"] += int((~take).sum())
+        seen["takeovers"] += int(take.sum())
+        seen["reasons"] |= set(int(x) for x in reason[take])
+        seen["ended"] += int(over.sum())
+        seen["ended_taken"] += int((over & ended & take).sum())
+        seen["autoresets"] += int(done.sum())
+        seen["later_rows"] += int((~first).sum())
+        seen["clipped"] += int(((fa == j_min) | (fa == j_max)).sum())
+        seen["unclipped"] += int(((fa > j_min) & (fa < j_max)).sum())
+        moved = done
+        prev_a = np.where(moved, 0.0, np.where(first, ego4[:, 3], t_ego4[:, 3]))
+        count[moved], ret[moved] = 0, 0.0
+        ep += moved
+    # the log rows of the episodes 0 that ended: the composition's final world row, the environment, episode 0
+    dr = rec["drained"]
+    if ticks == rec["action"].shape[0]:
+        for e, row in ended_rows.items():
+            i = np.nonzero((dr["env"] == e) & (dr["episode"] == 0))[0]
+            assert len(i) == 1 and dr["episode_return"][i[0]] == row[-1] and dr["ticks"][i[0]] == row[-2], e
+    for c in (ctx, ctx1, twin_ctx):
+        c.check_error()
+        c.close()
+    seen["rolled"] = np.stack(seen["rolled"])
+    return seen
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cell", ["default", "L3T2"])
+@pytest.mark.parametrize("env_id", ["sumo-jerk-v0", "sumo-accel-v0"])
+def test_gpu_step_is_the_composition_bit_for_bit(env_id, cell, restore_settings, tmp_path_factory):
+    """200 ticks (510 under L3T2: ``TICKS_OF``) with autoreset under the mixed actions; the observed counts are recorded in DESIGN section 35."""
+    tmp = tmp_path_factory.mktemp("q")
+    rec = _recorded_run(tmp, env_id, ticks=TICKS_OF[cell], cell=cell)
+    seen = _compose(tmp, rec, env_id, cell)
+    print("qshield env composition:", env_id, cell, {k: v for k, v in seen.items() if k != "rolled"}, "counts", rec["counts"])
+    assert rec["shield_name"] == "combined" and rec["info_keys"] >= set(SHIELD_KEYS) and "executed_action" not in rec["info_keys"]
+    assert seen["kept"] >= 1 and seen["takeovers"] >= 1, seen
+    assert seen["ended"] >= 1 and seen["autoresets"] >= 1 and seen["later_rows"] >= 1, seen
+    if env_id == "sumo-accel-v0":
+        assert seen["clipped"] >= 1 and seen["unclipped"] >= 1, seen
+    assert rec["counts"] == (TICKS_OF[cell] * N, TICKS_OF[cell] * N)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_id", ["sumo-jerk-v0", "sumo-accel-v0"])
+def test_gpu_sparse_equals_dense(env_id, restore_settings, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("q")
+    dense = _recorded_run(tmp, env_id)
+    sparse = _recorded_run(tmp, env_id, ticks=60, sparse=True, actions=dense["action"][:60])
+    for k in KEYS + WORLD:
+        assert _same(sparse[k], dense[k][:60]), k
+    decisions, solves = sparse["counts"]
+    assert decisions == 60 * N and solves == int(dense["takeover"][:60].sum()) >= 1
+    assert dense["counts"] == (TICKS * N, TICKS * N)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_id", ["sumo-jerk-v0", "sumo-accel-v0"])
+def test_gpu_up_to_the_first_takeover_it_is_todays_env(env_id, restore_settings, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("q")
+    shielded = _recorded_run(tmp, env_id, ticks=60, autoreset=False)
+    plain = _recorded_run(tmp, env_id, ticks=60, autoreset=False, shield=False, actions=shielded["action"])
+    assert not plain["info_keys"] & set(SHIELD_KEYS)
+    taken_before = np.cumsum(shielded["takeover"], axis=0) - shielded["takeover"] > 0          # [t][e]: a takeover on an earlier tick
+    clean = ~(taken_before | shielded["takeover"])                                              # the non-takeover ticks up to the row's first takeover
+    assert clean.sum() >= N and shielded["takeover"].sum() >= 1
+    for k in ("reward", "term", "trunc", "obs"):
+        assert _same(shielded[k][clean], plain[k][clean]), k
+
+
+@pytest.mark.gpu
+def test_gpu_env_follows_the_combined_runner(restore_settings, tmp_path):
+    """Jerk mode only: the same DQNActor's own step-1 indices through the env (no autoreset) end every episode exactly where
+    EpisodeRunner(controller="combined") with that actor ends it, with the runner's counts: both decide every row on every tick, finished rows
+    included.  Under its own actions the policy ends no episode before the time limit, so the run goes past it (505 ticks): every episode is truncated at
+    tick 500 on both sides.  Acceleration mode is left out: there the env executes handle_acceleration's command for the index and the runner its own rule (the
+    speed of the clipped jerk), so the two worlds part although the decisions agree."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, episodes
+    env_id = "sumo-jerk-v0"
+    S = _settings()
+    ticks = 505
+    ctx_r = _capi.Context(-1)
+    runner = episodes.EpisodeRunner(N, seed=SEED, controller="combined", policy=_file_actor(tmp_path, env_id, ctx_r), ctx=ctx_r, kmax=KMAX,
+                                    max_episode_length=float(S.MAX_EPISODE_LENGTH))
+    ctx_r.combined_counts(reset=True)
+    ctx = _capi.Context(-1)
+    env = _env(ctx, env_id, _file_actor(tmp_path, env_id, ctx), autoreset=False, shield_sparse=True)
+    env.shield_counts(reset=True)
+    env.reset()
+    pol, view = _file_actor(tmp_path, env_id, ctx), _View(ctx)
+    for t in range(ticks):
+        runner.tick()
+        b = view(env.sim_cfg)                                                     # the controller's own view
+        pol(1, b[0][:, :4].contiguous(), b[1], b[2], b[3], b[4])
+        env.step(pol.action.clone())
+    want, got = ctx_r.sim_read(N), ctx.sim_read(N)
+    for name_, a, b in zip(WORLD, got, want):
+        assert _same(a, b), name_
+    counts_r, counts_e = ctx_r.combined_counts(), env.shield_counts()
+    print("qshield env vs runner: ticks", ticks, "ended", np.bincount(want[0], minlength=4), "runner counts", counts_r, "env counts", counts_e)
+    assert (want[0] != 0).all()                             # every episode is over
+    assert counts_e == counts_r and counts_e[0] == ticks * N and 1 <= counts_e[1] < counts_e[0]
+    env.check_error()
+    ctx.close()
+    ctx_r.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_id", ["sumo-jerk-v0", "sumo-accel-v0"])
+def test_gpu_populations(env_id, restore_settings, tmp_path_factory):
+    """P = 2 members with different weights on slices of 50 rows of one world (the boundary row 50 lies inside the 16-row tile 48 ... 63 of a lone
+    actor): the run is the composition that calls stmpc_pop_qactor_eval_device.  P identical members: row for row the env behind the lone DQNActor."""
+    from rl_mpc_lanemerging_amd import actor
+    tmp = tmp_path_factory.mktemp("q")
+    S = _settings()
+
+    def pop_of(seeds):
+        return lambda ctx: actor.QActorPopulation([_file_actor(tmp, env_id, ctx, n=1, seed=s) for s in seeds], N // 2, ctx, S)
+    rec = _recorded_run(tmp, env_id, ticks=60, policy_of=pop_of((0, 1)), tag="pop01")
+    seen = _compose(tmp, rec, env_id, "default", policy_of=pop_of((0, 1)))
+    print("qshield env population:", env_id, {k: v for k, v in seen.items() if k != "rolled"})
+    assert seen["kept"] >= 1 and seen["takeovers"] >= 1, seen
+    lone = _recorded_run(tmp, env_id)
+    # the second member's weights matter: its rows' rollouts are not the lone (member 0) actor's everywhere
+    same_pop = _recorded_run(tmp, env_id, ticks=60, policy_of=pop_of((0, 0)), actions=lone["action"][:60], tag="pop00")
+    for k in KEYS + WORLD:
+        assert _same(same_pop[k], lone[k][:60]), k
+
+
+@pytest.mark.gpu
+def test_gpu_a_view_sees_the_learners_update(restore_settings, tmp_path):
+    """The policy is a view of a DQN learner's online network: a step queued after learner.update(3) equals the step of a twin env whose policy is a
+    file actor holding the UPDATED weights, and its rollouts differ from those under the weights before the update.  The three updates learn from
+    one pushed batch of made-up transitions, so that all three envs still stand in the reset's world when they step."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, actor, learner
+    env_id = "sumo-jerk-v0"
+    S = _settings()
+    A = _table(env_id).size
+    ctx = _capi.Context(-1)
+    L = learner.DQNLearner((20, A), learner.DQNConfig(n_obs=20, n_actions=A, h1=16, batch=16, capacity=4 * N, replay_start=N // 2, lr=1.0), seed=3,
+                           init=_net(env_id), ctx=ctx)
+    L.action_values = _table(env_id)                        # (a learner built from dims: the indices stand for the env's table)
+    env = _env(ctx, env_id, actor.DQNActor.from_learner(L, N, ctx, S), autoreset=False)
+    stale_ctx = _capi.Context(-1)
+    stale = _env(stale_ctx, env_id, _file_actor(tmp_path, env_id, stale_ctx), autoreset=False)
+    obs = env.reset()
+    stale.reset()
+    act = torch.as_tensor(_mixed_actions(np.zeros(N), np.zeros(N, np.int64), A), device="cuda")
+    reward = torch.as_tensor(_hash01(np.zeros(N), 3) * 4 - 2, device="cuda")
+    no = torch.zeros(N, dtype=torch.bool, device="cuda")
+    L.push(obs.clone(), None, act, reward, obs.clone(), no, no, final_obs=obs.clone())
+    L.update(3)
+    assert L.stats()["updates"] == 3
+    updated_path = L.export_q(str(tmp_path / "updated.npz"))
+    with np.load(updated_path) as zf:
+        assert not _same(zf["w0"], _net(env_id)["w0"])
+    fresh_ctx = _capi.Context(-1)
+    fresh = _env(fresh_ctx, env_id, actor.DQNActor(updated_path, N, fresh_ctx, S), autoreset=False)
+    fresh.reset()
+    L_ = max(int(env.shield_cfg.cc.rollout_length), 1)
+    out = {}
+    for name, e in (("view", env), ("fresh", fresh), ("stale", stale)):
+        o = e.step(act)
+        out[name] = {k: o[4][k].cpu().numpy().copy() for k in SHIELD_KEYS}
+        out[name].update(obs=o[0].cpu().numpy().copy(), reward=o[1].cpu().numpy().copy(), rollout_s=e.ctx.combined_read_state(N, KMAX, L_)["rollout_s"])
+    for k in SHIELD_KEYS + ("obs", "reward", "rollout_s"):
+        assert _same(out["view"][k], out["fresh"][k]), k
+    differ = (out["view"]["rollout_s"] != out["stale"]["rollout_s"]).any(axis=1)
+    print("a view sees the update: rolled-out rows that differ from the pre-update ones:", int(differ.sum()), "of", N)
+    assert differ.sum() >= 1
+    for c in (ctx, stale_ctx, fresh_ctx):
+        c.check_error()
+        c.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_id", ["sumo-jerk-v0", "sumo-accel-v0"])
+def test_gpu_index_out_of_range(env_id, restore_settings, tmp_path):
+    import torch
+    from rl_mpc_lanemerging_amd import _capi
+    A = _table(env_id).size
+    ctxs = [_capi.Context(-1) for _ in range(2)]
+    bad_env, good_env = (_env(c, env_id, _file_actor(tmp_path, env_id, c), autoreset=False) for c in ctxs)
+    bad_env.reset(), good_env.reset()
+    good = _mixed_actions(np.zeros(N), np.zeros(N, np.int64), A)
+    bad = good.copy()
+    bad[[3, 70]] = (A, -1)                                   # one row in each workgroup
+    speed_before = ctxs[0].sim_read(N)[3][:, 2].copy()
+    a, b = bad_env.step(torch.as_tensor(bad, device="cuda")), good_env.step(torch.as_tensor(good, device="cuda"))
+    rows = np.ones(N, bool)
+    rows[[3, 70]] = False
+    for x, y in zip(a[:4], b[:4]):
+        assert _same(x.cpu().numpy()[rows], y.cpu().numpy()[rows])
+    for k in SHIELD_KEYS:
+        assert _same(a[4][k].cpu().numpy()[rows], b[4][k].cpu().numpy()[rows]), k
+    for x, y in zip(ctxs[0].sim_read(N), ctxs[1].sim_read(N)):
+        assert _same(x[rows], y[rows])
+    assert np.isfinite(a[1].cpu().numpy()).all() and np.isfinite(ctxs[0].sim_read(N)[3]).all()
+    took = a[4]["takeover"].cpu().numpy()
+    kept_speed = ctxs[0].sim_read(N)[3][[3, 70], 2] == speed_before[[3, 70]]
+    assert (kept_speed | took[[3, 70]]).all()               # the row keeps its speed (unless the controller took over and set its own)
+    with pytest.raises(_capi.StmpcError, match="out of range"):
+        bad_env.check_error()
+    good_env.check_error()
+    # on a finished row, without autoreset, nothing is latched
+    for t in range(400):
+        o = good_env.step(torch.as_tensor(good, device="cuda"))
+        finished = ctxs[1].sim_read(N)[0] != 0
+        if finished.any():
+            break
+    assert finished.any()
+    late = good.copy()
+    late[np.nonzero(finished)[0][0]] = A + 7
+    good_env.step(torch.as_tensor(late, device="cuda"))
+    good_env.check_error()
+    for c in ctxs:
+        c.close()
+
+
+@pytest.mark.gpu
+def test_gpu_shape_table(restore_settings, tmp_path):
+    """Every existing step entry and stmpc_sim_step_device refuse the new env; the new entries refuse every other reset shape and every mismatch of
+    the policy and the cfg; after each refusal the next legal step gives the bits of an undisturbed twin."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, actor, vec_env
+    env_id = "sumo-jerk-v0"
+    S = _settings()
+    EINVAL = _capi.STMPC_EINVAL
+    A = _table(env_id).size
+    ctx, ctx_t = _capi.Context(-1), _capi.Context(-1)
+    env, twin = (_env(c, env_id, _file_actor(tmp_path, env_id, c)) for c in (ctx, ctx_t))
+    env.reset(), twin.reset()
+    act = torch.as_tensor(_mixed_actions(np.zeros(N), np.zeros(N, np.int64), A), device="cuda")
+    tail = lambda e: (act.data_ptr(), e._obs[1].data_ptr(), e.obs_dim, e._reward.data_ptr(), e._term.data_ptr(), e._trunc.data_ptr(), e._final_obs.data_ptr(),
+                      e._final_stats.data_ptr())
+    q_out = lambda e: (e._takeover.data_ptr(), e._reason.data_ptr(), e._exec_jerk.data_ptr(), e._takeover_ticks.data_ptr())
+    shield_out = lambda e: (e._takeover.data_ptr(), e._reason.data_ptr(), e._exec_jerk.data_ptr(), 0, e._takeover_ticks.data_ptr())
+    fs_cfg = _capi.ShieldEnvCfg.from_settings(S, kmax=KMAX)
+    cs_cfg = _capi.CShieldEnvCfg.from_settings(S, kmax=KMAX)
+    itype = torch.zeros(N, dtype=torch.int32, device="cuda")
+    ddpg = actor.DDPGActor(__import__("rl_mpc_lanemerging_amd.combined_bench", fromlist=["x"]).COMBINED_MEDIUM_1_ACTOR, N, ctx, S)
+
+    def same_as_twin(label):
+        a, b = env.step(act), twin.step(act)
+        torch.cuda.synchronize()
+        for x, y in zip(a[:4], b[:4]):
+            assert _same(x.cpu().numpy(), y.cpu().numpy()), label
+        for k in SHIELD_KEYS:
+            assert _same(a[4][k].cpu().numpy(), b[4][k].cpu().numpy()), (label, k)
+        for x, y in zip(ctx.sim_read(N), ctx_t.sim_read(N)):
+            assert _same(x, y), label
+
+    def refused(call, label, match=None):
+        with pytest.raises(_capi.StmpcError, match=match) as err:
+            call()
+        assert err.value.code == EINVAL, label
+
+    for i, call in enumerate([
+            lambda: ctx.env_step(env.params, env.sim_cfg, env.cfg, N, *tail(env)),
+            lambda: ctx.env_step_groups(env.params, env.cfg, N, *tail(env)),
+            lambda: ctx.env_step_reward_groups(env.params, env.cfg, N, *tail(env)),
+            lambda: ctx.shield_env_step(env.params, env.sim_cfg, env.cfg, fs_cfg, N, *tail(env), *shield_out(env)),
+            lambda: ctx.traffic_mix_env_step(env.params, env.cfg, N, *tail(env), itype.data_ptr(), itype.data_ptr()),
+            lambda: ctx.cshield_env_step(env.params, env.sim_cfg, env.cfg, cs_cfg, ddpg.handle, N, *tail(env), *shield_out(env)),
+            lambda: ctx.cshield_env_evals(N, itype.data_ptr()),
+            lambda: ctx.sim_step(env.params, env.sim_cfg, N, env._reward.data_ptr())]):
+        refused(call, i)
+        same_as_twin(i)
+    # the new step on every other reset shape, the continuous combined-shield env included
+    q_step = lambda c, e=env, cfg=None, q=None, pop=None, npm=0, ecfg=None: c.qshield_env_step(
+        env.params, env.sim_cfg, ecfg if ecfg is not None else env.cfg, cfg if cfg is not None else env.shield_cfg, q, pop, npm, N, *tail(e), *q_out(e))
+    mk = lambda **kw: vec_env.MergeVecEnv(N, env_id=env_id, seed=SEED, reward="Continuous", ctx=_capi.Context(-1), **kw)
+    others = {"plain": {}, "traffic groups": dict(traffic=["default", "low"]), "reward groups": dict(rewards=[{"REWARD_FUNCTION": "ST"}, {"REWARD_FUNCTION": "Slotted"}]),
+              "first-step shield": dict(shield="first_step", shield_kmax=KMAX), "traffic mix": dict(traffic_mix=["default", "low"])}
+    for name, kw in others.items():
+        other, fresh = mk(**kw), mk(**kw)
+        other.reset(), fresh.reset()
+        pol = _file_actor(tmp_path, env_id, other.ctx)
+        refused(lambda: q_step(other.ctx, q=pol.handle), name, "not reset through stmpc_qshield_env_reset_device|traffic groups|reward groups|first-step shield|traffic mix")
+        x, y = other.step(act), fresh.step(act)             # the refusal changed nothing: the env's own step gives an undisturbed twin's bits
+        for q in range(4):
+            assert _same(x[q].cpu().numpy(), y[q].cpu().numpy()), (name, q)
+        for u, v in zip(other.ctx.sim_read(N), fresh.ctx.sim_read(N)):
+            assert _same(u, v), name
+        other.ctx.close(), fresh.ctx.close()
+    cctx = _capi.Context(-1)
+    cenv = vec_env.CombinedShieldVecEnv(N, actor.DDPGActor(ddpg.name, N, cctx, S), seed=SEED, reward="Continuous", ctx=cctx, shield_kmax=KMAX)
+    cenv.reset()
+    refused(lambda: q_step(cctx, q=_file_actor(tmp_path, env_id, cctx).handle), "cshield context")
+    cctx.close()
+    # the cfg and the policy against the reset's and the env's
+    h = env.policy.handle
+    for field, value, text in (("kmax", 16, "differs"), ("kmax", 33, "kmax must be"), ("takeover_penalty", -1.0, "takeover_penalty")):
+        bad = _capi.QShieldEnvCfg.from_buffer_copy(env.shield_cfg)
+        setattr(bad, field, value)
+        refused(lambda: q_step(ctx, cfg=bad, q=h), field, text)
+    bad = _capi.QShieldEnvCfg.from_buffer_copy(env.shield_cfg)
+    bad.cc.remember_last_choice = 1
+    refused(lambda: q_step(ctx, cfg=bad, q=h), "remember", "remember_last_choice")
+    bad = _capi.QShieldEnvCfg.from_buffer_copy(env.shield_cfg)
+    bad.cc.rollout_length = env.shield_cfg.cc.rollout_length + 1
+    refused(lambda: q_step(ctx, cfg=bad, q=h), "rollout length", "differs")
+    bad = _capi.QShieldEnvCfg.from_buffer_copy(env.shield_cfg)
+    bad.features.time_feature = 1
+    refused(lambda: q_step(ctx, cfg=bad, q=h), "time feature", "time feature")
+    another = _file_actor(tmp_path, env_id, ctx)
+    refused(lambda: q_step(ctx, q=another.handle), "another policy", "differs")
+    refused(lambda: q_step(ctx), "no policy", "exactly one")
+    pop = actor.QActorPopulation([_file_actor(tmp_path, env_id, ctx, n=1, seed=s) for s in (0, 1)], N // 2, ctx, S)
+    refused(lambda: q_step(ctx, q=h, pop=pop.handle, npm=N // 2), "both policies", "exactly one")
+    refused(lambda: q_step(ctx, pop=pop.handle, npm=N // 2 - 1), "P * n_per_member", "n_per_member")
+    refused(lambda: q_step(ctx, pop=pop.handle, npm=N // 2), "a population is not the reset's lone actor", "differs")
+    accel = _file_actor(tmp_path, "sumo-accel-v0", ctx)
+    refused(lambda: q_step(ctx, q=accel.handle), "n_actions", "actions")
+    wrong_mode = actor.DQNActor(_q_file(tmp_path, env_id), N, ctx, S, mode="acceleration")
+    refused(lambda: q_step(ctx, q=wrong_mode.handle), "mode", "mode")
+    table = _table(env_id)
+    table[1] = np.nextafter(table[1], 9.0)
+    wrong_table = actor.DQNActor(_q_file(tmp_path, env_id), N, ctx, S, mode="jerk", action_values=table)
+    refused(lambda: q_step(ctx, q=wrong_table.handle), "table", "byte-identical")
+    reset = lambda ecfg, cfg, q: ctx.qshield_env_reset(env.params, env.sim_cfg, ecfg, cfg, q, None, 0, N, env._obs[0].data_ptr(), env.obs_dim)
+    refused(lambda: reset(vec_env.env_cfg("sumo-jerk-continuous-v0", "Continuous"), env.shield_cfg, h), "continuous", "stmpc_cshield_env_")
+    refused(lambda: reset(env.cfg, env.shield_cfg, wrong_table.handle), "table at reset", "byte-identical")
+    refused(lambda: reset(vec_env.env_cfg("sumo-accel-v0", "Continuous"), env.shield_cfg, h), "another env's table", "actions")
+    same_as_twin("after every refusal")                     # none of it changed anything
+    for c in (ctx, ctx_t):
+        c.check_error()
+        c.close()
+
+
+def _flat(d, prefix=""):
+    out = {}
+    for k, v in d.items():
+        if isinstance(v, dict):
+            out.update(_flat(v, prefix + str(k) + "."))
+        else:
+            out[prefix + str(k)] = np.asarray(v).copy()
+    return out
+
+
+class _Summing:
+    """An env wrapper that sums info["takeover"] and the live ticks by hand, on the host, tick by tick."""
+
+    def __init__(self, env):
+        self.env, self.taken, self.lived = env, 0, 0
+
+    def __getattr__(self, name):
+        return getattr(self.env, name)
+
+    def step(self, action):
+        out = self.env.step(action)
+        self.taken += int(out[4]["takeover"].cpu().numpy().sum())
+        self.lived += self.env.n                            # (autoreset: every row lives on every tick)
+        return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["lone", "population", "first_step"])
+def test_gpu_training_behind_the_shield(kind, restore_settings):
+    """train_dqn for 40 steps at N = 100, twice from the same seeds: behind a fresh DQNLearner's own online view, behind a DQNPopulation of 2's
+    QActorPopulation, and on the first-step-shielded MergeVecEnv("sumo-jerk-v0") (whose takeover_share the parent reported as 0.0)."""
+    from rl_mpc_lanemerging_amd import _capi, actor, learner, vec_env
+    env_id = "sumo-jerk-v0"
+    A = _table(env_id).size
+
+    def run():
+        S = _settings()
+        ctx = _capi.Context(-1)
+        cfg = lambda: learner.DQNConfig(n_obs=20, n_actions=A, h1=16, batch=32, capacity=64 * N, replay_start=4 * N)
+        plain = vec_env.MergeVecEnv(N, env_id=env_id, seed=SEED, reward="Continuous", ctx=ctx, **({"shield": "first_step", "shield_kmax": KMAX} if kind == "first_step" else {}))
+        if kind == "population":
+            L = learner.DQNPopulation(plain, (cfg(), 2), seeds=[3, 4], init=[_net(env_id, 0), _net(env_id, 1)], ctx=ctx)
+            env = _env(ctx, env_id, actor.QActorPopulation(L, N // 2, ctx, S))
+        else:
+            L = learner.DQNLearner(plain, cfg(), seed=3, init=_net(env_id), ctx=ctx)
+            env = plain if kind == "first_step" else _env(ctx, env_id, actor.DQNActor.from_learner(L, N, ctx, S))
+        env = _Summing(env)
+        res = learner.train_dqn(env, L, frames=40 * N, drain_every=8)
+        env.check_error()
+        state = _flat(L.state_dict()) if kind != "population" else {"%d.%s" % (m, k): v for m in range(2) for k, v in _flat(L.member(m).state_dict()).items()}
+        ctx.close()
+        return res, state, env.taken, env.lived
+    r1, s1, taken, lived = run()
+    r2, s2, _, _ = run()
+    print("training behind the shield:", kind, "takeover_share %.4f (%d of %d), episodes %d" % (r1["takeover_share"], taken, lived, r1["episodes"]),
+          r1.get("member_takeover_share"))
+    assert r1["steps"] == 40 and lived == 40 * N and r1["takeover_share"] == taken / lived and 0.0 < r1["takeover_share"] < 1.0
+    assert r1["takeover_share"] == r2["takeover_share"] and _same(r1["returns"], r2["returns"])
+    if kind == "population":
+        m = r1["member_takeover_share"]
+        assert len(m) == 2 and m == r2["member_takeover_share"] and abs(sum(m) / 2 - r1["takeover_share"]) < 1e-12
+    else:
+        assert "member_takeover_share" not in r1
+    assert set(s1) == set(s2)
+    for k in s1:
+        assert _same(s1[k], s2[k]), k
