@@ -145,6 +145,12 @@ class FeaturesCfg(C.Structure):
                    time_feature=int(bool(time_feature)))
 
 
+def _combined_shield_fields(S, sparse_control, takeover_penalty, kmax, features, time_feature):
+    """The fields ``stmpc_cshield_env_cfg`` and ``stmpc_qshield_env_cfg`` share (``features`` None: the Settings' with ``time_feature``)."""
+    f = FeaturesCfg.from_buffer_copy(features) if features is not None else FeaturesCfg.from_settings(S, time_feature=time_feature)
+    return dict(cc=CombinedCfg.from_settings(S, sparse_control=sparse_control), features=f, takeover_penalty=float(takeover_penalty), kmax=int(kmax))
+
+
 class CShieldEnvCfg(C.Structure):
     """``stmpc_cshield_env_cfg`` (include/stmpc.h): the combined controller behind the vector environment -- its flags, the rollout actor's input, the
     takeover penalty, the row stride of the planner's view and the rule of the rollout's time counter."""
@@ -158,9 +164,7 @@ class CShieldEnvCfg(C.Structure):
         ``FeaturesCfg.from_settings(S)``, the time feature on); ``rollout_time``: "env" or "deployed" (ValueError otherwise)."""
         if rollout_time not in cls.ROLLOUT_TIMES:
             raise ValueError("rollout_time must be one of %s, not %r" % (", ".join(map(repr, cls.ROLLOUT_TIMES)), rollout_time))
-        f = FeaturesCfg.from_buffer_copy(features) if features is not None else FeaturesCfg.from_settings(S)
-        return cls(cc=CombinedCfg.from_settings(S, sparse_control=sparse_control), features=f, takeover_penalty=float(takeover_penalty), kmax=int(kmax),
-                   rollout_time=cls.ROLLOUT_TIMES[rollout_time])
+        return cls(rollout_time=cls.ROLLOUT_TIMES[rollout_time], **_combined_shield_fields(S, sparse_control, takeover_penalty, kmax, features, True))
 
 
 class QShieldEnvCfg(C.Structure):
@@ -173,8 +177,7 @@ class QShieldEnvCfg(C.Structure):
     def from_settings(cls, S, sparse_control=False, takeover_penalty=0.0, kmax=32, features=None):
         """``S``: the ``Settings`` (or an overlay of them) ``do_combined_control`` reads; ``features``: the Q-actor's ``FeaturesCfg`` (default:
         ``FeaturesCfg.from_settings(S, time_feature=False)``)."""
-        f = FeaturesCfg.from_buffer_copy(features) if features is not None else FeaturesCfg.from_settings(S, time_feature=False)
-        return cls(cc=CombinedCfg.from_settings(S, sparse_control=sparse_control), features=f, takeover_penalty=float(takeover_penalty), kmax=int(kmax))
+        return cls(**_combined_shield_fields(S, sparse_control, takeover_penalty, kmax, features, False))
 
 
 class SimCfg(C.Structure):

@@ -1418,42 +1418,30 @@ int reward_groups_reset_check(stmpc_ctx *c, const stmpc_params *p, const stmpc_s
     return STMPC_OK;
 }
 
-// the combined-shield env's cfg and actor (its reset and its step): `cc`, `fc` receive the kernels' forms
-int cshield_cfg_check(const stmpc_ctx *c, const stmpc_params *p, const stmpc_cshield_env_cfg *sh, const stmpc_actor *a, int N, CCfg *cc, FeatCfg *fc) {
-    if (!sh) return fail(STMPC_EINVAL, "combined shield cfg is NULL");
-    if (!a) return fail(STMPC_EINVAL, "combined shield: actor is NULL");
-    if (sh->kmax < 1 || sh->kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, "combined shield cfg: kmax must be 1 ... STMPC_KMAX_LIMIT (32), the solver's vehicles per state");
-    if (!(sh->takeover_penalty >= 0) || !(sh->takeover_penalty <= 1.7976931348623157e308))
-        return fail(STMPC_EINVAL, "combined shield cfg: takeover_penalty must be finite and not negative");
-    if (sh->rollout_time != env::ROLLOUT_TIME_ENV && sh->rollout_time != env::ROLLOUT_TIME_DEPLOYED)
-        return fail(STMPC_EINVAL, "combined shield cfg: rollout_time must be 0 (env) or 1 (deployed)");
-    TRY(make_ccfg(p, &sh->cc, cc));
-    if (cc->remember_last) return fail(STMPC_EINVAL, "combined shield cfg: remember_last_choice must be 0 (the env keeps no takeover history per episode)");
-    TRY(check_batch(N, sh->kmax));
-    // (stmpc_actor_eval_device's checks of an empty batch: the device, the features, the actor's input width; the rows are the context's own)
-    return actor_eval_checks(c, a->device, a->dev.n_in, &sh->features, 0, sh->kmax, 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, fc);
-}
-
-// what the combined-shield env behind a Q-network takes besides the env's arguments
-struct QShieldStep {
-    const stmpc_qshield_env_cfg *cfg;
+// The env behind the combined controller, whichever policy proposes in its rollout: what its reset and its step take of the entry's cfg
+// (stmpc_cshield_env_cfg, stmpc_qshield_env_cfg) and the policy.  `cc` is NULL where the entry's cfg was.
+struct CombinedShield {
+    const stmpc_combined_cfg *cc;
+    const stmpc_policy_features_cfg *features;
+    double takeover_penalty;
+    int kmax, rollout_time;                  // (rollout_time: 0 for the Q env, which has no time counter)
+    bool qnet;                               // the Q env (stmpc_qshield_env_*): the policy is q or pop, else actor
+    const stmpc_actor *actor;
     const stmpc_qactor *q;                   // exactly one of q and pop (qshield_policy_check)
     const stmpc_qactor_pop *pop;
     int n_per_member;
-    const void *policy() const { return q ? (const void *)q : (const void *)pop; }
+    const void *qpolicy() const { return q ? (const void *)q : (const void *)pop; }
 };
-// its cfg, env cfg and policy (its reset and its step): `cc`, `fc` receive the kernels' forms.  Changes nothing.
-int qshield_cfg_check(const stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, const QShieldStep &qs, int N, CCfg *cc, FeatCfg *fc) {
-    const stmpc_qshield_env_cfg *sh = qs.cfg;
-    if (!sh) return fail(STMPC_EINVAL, "combined shield (Q) cfg is NULL");
-    if (!ec) return fail(STMPC_EINVAL, "env cfg is NULL");
-    if (sh->kmax < 1 || sh->kmax > STMPC_KMAX_LIMIT)
-        return fail(STMPC_EINVAL, "combined shield (Q) cfg: kmax must be 1 ... STMPC_KMAX_LIMIT (32), the solver's vehicles per state");
-    if (!(sh->takeover_penalty >= 0) || !(sh->takeover_penalty <= 1.7976931348623157e308))
-        return fail(STMPC_EINVAL, "combined shield (Q) cfg: takeover_penalty must be finite and not negative");
-    TRY(make_ccfg(p, &sh->cc, cc));
-    if (cc->remember_last) return fail(STMPC_EINVAL, "combined shield (Q) cfg: remember_last_choice must be 0 (the env keeps no takeover history per episode)");
-    TRY(check_batch(N, sh->kmax));
+CombinedShield combined_shield_of(const stmpc_cshield_env_cfg *sh, const stmpc_actor *a) {
+    if (!sh) return CombinedShield{nullptr, nullptr, 0, 0, 0, false, a, nullptr, nullptr, 0};
+    return CombinedShield{&sh->cc, &sh->features, sh->takeover_penalty, sh->kmax, sh->rollout_time, false, a, nullptr, nullptr, 0};
+}
+CombinedShield combined_shield_of(const stmpc_qshield_env_cfg *sh, const stmpc_qactor *q, const stmpc_qactor_pop *pop, int n_per_member) {
+    if (!sh) return CombinedShield{nullptr, nullptr, 0, 0, 0, true, nullptr, q, pop, n_per_member};
+    return CombinedShield{&sh->cc, &sh->features, sh->takeover_penalty, sh->kmax, 0, true, nullptr, q, pop, n_per_member};
+}
+// the Q env's own checks: a discrete env cfg, no time feature, the policy (*n_in receives its input width)
+int qshield_checks(const stmpc_ctx *c, const stmpc_env_cfg *ec, const CombinedShield &d, int N, int *n_in) {
     if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
     if (ec->action_mode == STMPC_ENV_CONTINUOUS_JERK)
         return fail(STMPC_EINVAL, "stmpc_qshield_env_* serves STMPC_ENV_JERK and STMPC_ENV_ACCELERATION (the rollout policy is a Q-network): the continuous env "
@@ -1461,12 +1449,34 @@ int qshield_cfg_check(const stmpc_ctx *c, const stmpc_params *p, const stmpc_env
     if (ec->action_mode != STMPC_ENV_JERK && ec->action_mode != STMPC_ENV_ACCELERATION) return fail(STMPC_EINVAL, "env cfg: unknown action_mode");
     if (!ec->action_values || ec->n_action_values < 1 || ec->n_action_values > STMPC_ENV_MAX_ACTIONS)
         return fail(STMPC_EINVAL, "a discrete env needs 1..STMPC_ENV_MAX_ACTIONS action_values");
-    if (sh->features.time_feature) return fail(STMPC_EINVAL, "a Q-network has no time feature: the features cfg must have time_feature = 0");
-    int n_in = 0;
-    TRY(qshield_policy_check(c, qs.q, qs.pop, qs.n_per_member, N, ec->action_mode == STMPC_ENV_ACCELERATION, ec->action_values, ec->n_action_values,
-                             ec->tick_length, ec->minimum_negative_jerk, ec->maximum_positive_jerk, &n_in));
-    // (the eval entries' checks of an empty batch: the features, the policy's input width; the rows are the context's own)
-    return actor_eval_checks(c, c->device, n_in, &sh->features, 0, sh->kmax, 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, fc);
+    if (d.features->time_feature) return fail(STMPC_EINVAL, "a Q-network has no time feature: the features cfg must have time_feature = 0");
+    return qshield_policy_check(c, d.q, d.pop, d.n_per_member, N, ec->action_mode == STMPC_ENV_ACCELERATION, ec->action_values, ec->n_action_values,
+                                ec->tick_length, ec->minimum_negative_jerk, ec->maximum_positive_jerk, n_in);
+}
+// its cfg, and with a Q-network its env cfg, and its policy (the reset and the step): `cc`, `fc` receive the kernels' forms.  Changes nothing.
+int combined_shield_check(const stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, const CombinedShield &d, int N, CCfg *cc, FeatCfg *fc) {
+    const std::string cfg = d.qnet ? "combined shield (Q) cfg" : "combined shield cfg";
+    if (!d.cc) return fail(STMPC_EINVAL, cfg + " is NULL");
+    if (d.qnet && !ec) return fail(STMPC_EINVAL, "env cfg is NULL");
+    if (!d.qnet && !d.actor) return fail(STMPC_EINVAL, "combined shield: actor is NULL");
+    if (d.kmax < 1 || d.kmax > STMPC_KMAX_LIMIT) return fail(STMPC_EINVAL, cfg + ": kmax must be 1 ... STMPC_KMAX_LIMIT (32), the solver's vehicles per state");
+    if (!(d.takeover_penalty >= 0) || !(d.takeover_penalty <= 1.7976931348623157e308)) return fail(STMPC_EINVAL, cfg + ": takeover_penalty must be finite and not negative");
+    if (d.rollout_time != env::ROLLOUT_TIME_ENV && d.rollout_time != env::ROLLOUT_TIME_DEPLOYED)
+        return fail(STMPC_EINVAL, "combined shield cfg: rollout_time must be 0 (env) or 1 (deployed)");
+    TRY(make_ccfg(p, d.cc, cc));
+    if (cc->remember_last) return fail(STMPC_EINVAL, cfg + ": remember_last_choice must be 0 (the env keeps no takeover history per episode)");
+    TRY(check_batch(N, d.kmax));
+    int device = c->device, n_in = 0;
+    if (d.qnet) { TRY(qshield_checks(c, ec, d, N, &n_in)); }
+    else { device = d.actor->device; n_in = d.actor->dev.n_in; }
+    // (the eval entries' checks of an empty batch: the device, the features, the policy's input width; the rows are the context's own)
+    return actor_eval_checks(c, device, n_in, d.features, 0, d.kmax, 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, fc);
+}
+// the rollout's "propose step `step`" on the current rows: the bodies of stmpc_actor_eval_device, stmpc_qactor_eval_device or stmpc_pop_qactor_eval_device
+int combined_shield_propose(stmpc_ctx *c, const CombinedShield &d, const FeatCfg &fc, int N, int step, const env::CShieldView &w, double *jerk, void *stream) {
+    if (d.actor) return actor_eval_run(c, d.actor, fc, N, d.kmax, step, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, w.evals, nullptr, 0, jerk, stream);
+    if (d.q) return qactor_eval_run(c, d.q, fc, N, d.kmax, step, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, nullptr, 0, nullptr, nullptr, jerk, stream);
+    return qactor_pop_eval_run(c, d.pop, fc, d.n_per_member, d.kmax, step, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, nullptr, 0, nullptr, nullptr, jerk, stream);
 }
 
 // ---- one reset, one step and one reward body behind the plain, traffic-groups, reward-groups and shielded entries ----
@@ -1567,16 +1577,17 @@ struct StepOut {                             // the tail every step entry takes
 struct MixStep {                             // what the traffic-mix step takes on top
     int32_t *traffic_type, *final_traffic_type;
 };
-struct CShieldStep {                         // what the combined-shield step takes on top of ShieldStep's outputs (ShieldStep::cfg is then NULL)
-    const stmpc_cshield_env_cfg *cfg;
-    const stmpc_actor *actor;
-};
-struct ShieldStep {                          // what the shielded step takes on top
-    const stmpc_shield_env_cfg *cfg;
+struct ShieldOut {                           // what a step behind either shield writes on top (executed_action may be NULL)
     uint8_t *takeover;
     int32_t *reason;
     double *executed_jerk, *executed_action;
     int32_t *takeover_ticks;
+};
+struct StepExtra {                           // what an entry has besides the plain step's arguments: it names those it has
+    const stmpc_shield_env_cfg *shield = nullptr;    // behind the first-step shield ...
+    const CombinedShield *combined = nullptr;        // ... or the combined controller: either writes `out`
+    ShieldOut out{};
+    const MixStep *mix = nullptr;
 };
 
 // the world step and the env's reward / observation / autoreset: `lone` is the cfg of an ungrouped world, NULL for the context's traffic groups
@@ -1607,41 +1618,45 @@ void env_world_step(stmpc_ctx *c, const DevP &dp, double crash_min_s, const env:
 #undef POST
 }
 
-// Step.  `g`: the cfg of a lone world (NULL: the entry takes none); `sh`: the shielded step's arguments, or NULL.
+// Step.  `g`: the cfg of a lone world (NULL: the entry takes none); `x`: what the entry has on top of the plain step.
 int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, int N, const EnvEntry &who, const StepOut &o,
-             const ShieldStep *sh = nullptr, const MixStep *mix = nullptr, const CShieldStep *cs = nullptr, const QShieldStep *qs = nullptr) {
+             const StepExtra &x = {}) {
     if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
     TRY(env_shape_check(c, who));
     if (N != c->env.N || N != c->sim.N || N < 1) return fail(STMPC_EINVAL, std::string("N does not match ") + who.reset_entry);
+    const stmpc_shield_env_cfg *sh = x.shield;
+    const CombinedShield *cs = x.combined;
+    const MixStep *mix = x.mix;
+    const ShieldOut &out = x.out;
     const auto &v = c->shield;
     const auto &u = c->cshield;
     CCfg cs_cc;
     FeatCfg cs_fc;
     if (cs) {
-        TRY(cshield_cfg_check(c, p, cs->cfg, cs->actor, N, &cs_cc, &cs_fc));
-        if (cs->cfg->kmax != u.kmax || cs->cfg->rollout_time != u.rollout_time || cs_cc.rollout_length != u.L)
-            return fail(STMPC_EINVAL, "combined shield cfg: kmax, rollout_time or the rollout length differs from the one the context was reset with (stmpc_cshield_env_reset_device)");
-    } else if (qs) {
-        TRY(qshield_cfg_check(c, p, ec, *qs, N, &cs_cc, &cs_fc));
-        if (qs->cfg->kmax != u.kmax || cs_cc.rollout_length != u.L || qs->policy() != u.qpolicy || qs->n_per_member != u.n_per_member || ec->n_action_values != c->env.n_actions)
-            return fail(STMPC_EINVAL, "combined shield (Q): kmax, the rollout length, the policy, n_per_member or n_action_values differs from the one the context was reset with (stmpc_qshield_env_reset_device)");
+        TRY(combined_shield_check(c, p, ec, *cs, N, &cs_cc, &cs_fc));
+        const bool as_reset = cs->kmax == u.kmax && cs_cc.rollout_length == u.L &&
+                              (cs->qnet ? cs->qpolicy() == u.qpolicy && cs->n_per_member == u.n_per_member && ec->n_action_values == c->env.n_actions
+                                        : cs->rollout_time == u.rollout_time);
+        if (!as_reset)
+            return fail(STMPC_EINVAL, cs->qnet ? "combined shield (Q): kmax, the rollout length, the policy, n_per_member or n_action_values differs from the one the context was reset with (stmpc_qshield_env_reset_device)"
+                                               : "combined shield cfg: kmax, rollout_time or the rollout length differs from the one the context was reset with (stmpc_cshield_env_reset_device)");
     } else if (sh) {
-        TRY(shield_cfg_check(p, sh->cfg, N));
-        if (sh->cfg->kmax != v.kmax) return fail(STMPC_EINVAL, std::string("shield cfg: kmax differs from the one the context was reset with (") + who.reset_entry + ")");
+        TRY(shield_cfg_check(p, sh, N));
+        if (sh->kmax != v.kmax) return fail(STMPC_EINVAL, std::string("shield cfg: kmax differs from the one the context was reset with (") + who.reset_entry + ")");
     }
     if (!o.action || !o.obs || !o.reward || !o.terminated || !o.truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    if (sh && (!sh->takeover || !sh->reason || !sh->executed_jerk || !sh->takeover_ticks)) return fail(STMPC_EINVAL, "NULL device pointer (shield outputs)");
+    if ((sh || cs) && (!out.takeover || !out.reason || !out.executed_jerk || !out.takeover_ticks)) return fail(STMPC_EINVAL, "NULL device pointer (shield outputs)");
     if (mix && (!mix->traffic_type || !mix->final_traffic_type)) return fail(STMPC_EINVAL, "NULL device pointer (traffic type outputs)");
     env::ECfg e;
     sim::Cfg sc;
     DevP dp;
     TRY(env_step_begin(c, ec, o.obs_stride, who.reset_entry, &e));
-    if (sh && sh->executed_action && e.mode != env::ACT_CONTINUOUS_JERK)
+    if (out.executed_action && e.mode != env::ACT_CONTINUOUS_JERK)
         return fail(STMPC_EINVAL, "d_executed_action is the continuous env's (a discrete index is not rewritten): pass NULL");
-    if (cs && e.mode != env::ACT_CONTINUOUS_JERK) return fail(STMPC_EINVAL, "the combined shield serves STMPC_ENV_CONTINUOUS_JERK only (the rollout policy is a continuous actor)");
+    if (cs && !cs->qnet && e.mode != env::ACT_CONTINUOUS_JERK) return fail(STMPC_EINVAL, "the combined shield serves STMPC_ENV_CONTINUOUS_JERK only (the rollout policy is a continuous actor)");
     // the world: one cfg -- the caller's, or the one an ungrouped reward-groups reset kept -- or the context's table of traffic groups
     const bool grouped = c->sim.G > 0, reward_groups = who.reward_groups == REQUIRED;
-    if (sh && !cs && (grouped || reward_groups || mix) && (v.P < 1 || (int64_t)v.P * v.n_per_penalty != N))         // (what k_shield_env_apply_groups indexes)
+    if (sh && (grouped || reward_groups || mix) && (v.P < 1 || (int64_t)v.P * v.n_per_penalty != N))         // (what k_shield_env_apply_groups indexes)
         return fail(STMPC_EINVAL, std::string("the context holds no takeover penalty table for this env (") + who.reset_entry + ")");
     if (!grouped && reward_groups) sc = c->env.rg_sc;
     else if (mix) sc = c->env.mix_sc;
@@ -1654,49 +1669,27 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
     const sim::State s = c->sim.state();
     const env::EState es = env_state(c);
     // the action stage: the command of every live environment
-    if (qs) {
+    if (cs) {
         const env::CShieldView w = u.view();
-        const stmpc_combined_cfg *g = &qs->cfg->cc;
-        // 1. action handling, the planner's view into the start and the current rows, the first action (no time counter: a Q-network has no time feature)
-        hipLaunchKernelGGL(env::k_qshield_env_pre, grid, block, 0, st_, e, sc, N, u.kmax, s, es, o.action, w);
+        // 1. action handling, the planner's view into the start and the current rows, the first action and, in front of an actor, the rollout's time
+        //    counter (a Q-network has no time feature)
+        if (cs->qnet) hipLaunchKernelGGL(env::k_qshield_env_pre, grid, block, 0, st_, e, sc, N, u.kmax, s, es, o.action, w);
+        else hipLaunchKernelGGL(env::k_cshield_env_pre, grid, block, 0, st_, e, sc, N, u.kmax, u.rollout_time, s, es, o.action, w);
         HIPCHK(hipGetLastError());
-        // 2. dqn.RLAgent.do_combined_control on that view: the bodies of stmpc_qactor_eval_device or stmpc_pop_qactor_eval_device (steps 2 ... L),
-        //    stmpc_rollout_step_device and stmpc_combined_decide_device
+        // 2. dqn.RLAgent.do_combined_control on that view: the policy's eval body (steps 2 ... L), stmpc_rollout_step_device's and
+        //    stmpc_combined_decide_device's
         for (int step = 1; step <= cs_cc.rollout_length; ++step) {
-            if (step > 1 && qs->q)
-                TRY(qactor_eval_run(c, qs->q, cs_fc, N, u.kmax, step, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, nullptr, 0, nullptr, nullptr, u.jerk.as<double>(), o.stream));
-            else if (step > 1)
-                TRY(qactor_pop_eval_run(c, qs->pop, cs_fc, qs->n_per_member, u.kmax, step, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, nullptr, 0, nullptr, nullptr,
-                                        u.jerk.as<double>(), o.stream));
-            TRY(rollout_step_run(c, p, g, N, u.kmax, step, w.ego5, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, step > 1 ? u.jerk.as<double>() : w.first_action,
+            if (step > 1) TRY(combined_shield_propose(c, *cs, cs_fc, N, step, w, u.jerk.as<double>(), o.stream));
+            TRY(rollout_step_run(c, p, cs->cc, N, u.kmax, step, w.ego5, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, step > 1 ? u.jerk.as<double>() : w.first_action,
                                  o.stream));
         }
-        TRY(combined_decide_run(c, p, g, N, u.kmax, w.ego5, w.k, w.ox, w.ov, w.cur_ego4, w.cur_ox, w.cur_ov, w.first_action, nullptr, u.takeover.as<int32_t>(),
+        TRY(combined_decide_run(c, p, cs->cc, N, u.kmax, w.ego5, w.k, w.ox, w.ov, w.cur_ego4, w.cur_ox, w.cur_ov, w.first_action, nullptr, u.takeover.as<int32_t>(),
                                 u.reason.as<int32_t>(), u.speed.as<double>(), o.stream));
-        // 3. what is executed, and what the learner is told: the first-step shield's rule, unchanged (exec_action NULL: the index is not rewritten)
-        hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, qs->cfg->takeover_penalty, N, s, es, o.action, (const double *)u.speed.as<double>(),
-                           (const int *)u.takeover.as<int>(), (const int *)u.reason.as<int>(), u.count.as<int>(), u.tag.as<int>(), sh->takeover, sh->reason,
-                           sh->executed_jerk, (double *)nullptr, sh->takeover_ticks);
-    } else if (cs) {
-        const env::CShieldView w = u.view();
-        const stmpc_combined_cfg *g = &cs->cfg->cc;
-        // 1. action handling, the planner's view into the start and the current rows, the first action, the rollout's time counter
-        hipLaunchKernelGGL(env::k_cshield_env_pre, grid, block, 0, st_, e, sc, N, u.kmax, u.rollout_time, s, es, o.action, w);
-        HIPCHK(hipGetLastError());
-        // 2. dqn.RLAgent.do_combined_control on that view: the bodies of stmpc_actor_eval_device (steps 2 ... L), stmpc_rollout_step_device and
-        //    stmpc_combined_decide_device
-        for (int step = 1; step <= cs_cc.rollout_length; ++step) {
-            if (step > 1)
-                TRY(actor_eval_run(c, cs->actor, cs_fc, N, u.kmax, step, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, w.evals, nullptr, 0, u.jerk.as<double>(), o.stream));
-            TRY(rollout_step_run(c, p, g, N, u.kmax, step, w.ego5, w.cur_ego4, w.k, w.cur_ox, w.cur_ov, w.cur_oa, step > 1 ? u.jerk.as<double>() : w.first_action,
-                                 o.stream));
-        }
-        TRY(combined_decide_run(c, p, g, N, u.kmax, w.ego5, w.k, w.ox, w.ov, w.cur_ego4, w.cur_ox, w.cur_ov, w.first_action, nullptr, u.takeover.as<int32_t>(),
-                                u.reason.as<int32_t>(), u.speed.as<double>(), o.stream));
-        // 3. what is executed, and what the learner is told: the first-step shield's rule, unchanged
-        hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, cs->cfg->takeover_penalty, N, s, es, o.action, (const double *)u.speed.as<double>(),
-                           (const int *)u.takeover.as<int>(), (const int *)u.reason.as<int>(), u.count.as<int>(), u.tag.as<int>(), sh->takeover, sh->reason,
-                           sh->executed_jerk, sh->executed_action, sh->takeover_ticks);
+        // 3. what is executed, and what the learner is told: the first-step shield's rule, unchanged (the Q env's executed_action is NULL: the index is
+        //    not rewritten)
+        hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, cs->takeover_penalty, N, s, es, o.action, (const double *)u.speed.as<double>(),
+                           (const int *)u.takeover.as<int>(), (const int *)u.reason.as<int>(), u.count.as<int>(), u.tag.as<int>(), out.takeover, out.reason,
+                           out.executed_jerk, out.executed_action, out.takeover_ticks);
     } else if (sh) {
         const env::ShieldView w = v.view();
         const bool lone = !grouped && !reward_groups && !mix;
@@ -1710,17 +1703,17 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
         else hipLaunchKernelGGL(env::k_shield_env_pre_rg, grid, block, 0, st_, e, c->env.reward_tab(), sc, N, v.kmax, s, es, o.action, w);
         HIPCHK(hipGetLastError());
         // 2. st.do_conditional_st_based_on_first_step on that view and proposal: stmpc_first_step_device's body, on all N rows whatever their group
-        TRY(first_step_run(c, p, &sh->cfg->fs, N, v.kmax, w.ego5, w.k, w.ox, w.ov, w.proposal, v.speed.as<double>(), v.takeover.as<int32_t>(), v.reason.as<int32_t>(),
+        TRY(first_step_run(c, p, &sh->fs, N, v.kmax, w.ego5, w.k, w.ox, w.ov, w.proposal, v.speed.as<double>(), v.takeover.as<int32_t>(), v.reason.as<int32_t>(),
                            o.stream));
         // 3. what is executed, and what the learner is told (with groups: under the penalty of the environment's row of the reset's table)
         if (lone)
-            hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, sh->cfg->takeover_penalty, N, s, es, o.action, (const double *)v.speed.as<double>(),
-                               (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), sh->takeover, sh->reason,
-                               sh->executed_jerk, sh->executed_action, sh->takeover_ticks);
+            hipLaunchKernelGGL(env::k_shield_env_apply, grid, block, 0, st_, e, sh->takeover_penalty, N, s, es, o.action, (const double *)v.speed.as<double>(),
+                               (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), out.takeover, out.reason,
+                               out.executed_jerk, out.executed_action, out.takeover_ticks);
         else
             hipLaunchKernelGGL(env::k_shield_env_apply_groups, grid, block, 0, st_, e, v.penalty_tab(), N, s, es, o.action, (const double *)v.speed.as<double>(),
-                               (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), sh->takeover, sh->reason,
-                               sh->executed_jerk, sh->executed_action, sh->takeover_ticks);
+                               (const int *)v.takeover.as<int>(), (const int *)v.reason.as<int>(), v.count.as<int>(), v.tag.as<int>(), out.takeover, out.reason,
+                               out.executed_jerk, out.executed_action, out.takeover_ticks);
     } else if (reward_groups) {
         hipLaunchKernelGGL(env::k_env_act_rg, grid, block, 0, st_, e, c->env.reward_tab(), N, s, es, o.action);
     } else {
@@ -1728,6 +1721,34 @@ int env_step(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const 
     }
     env_world_step(c, dp, p->crash_min_s, e, grouped ? nullptr : &sc, reward_groups, o, mix);
     HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+// The reset behind both combined-shield reset entries: the plain reset, then every buffer of the step and zeroed counters.
+int combined_shield_reset(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const CombinedShield &d, int N, float *d_obs,
+                          int obs_stride, void *stream) {
+    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
+    CCfg cc;
+    FeatCfg fc;
+    TRY(combined_shield_check(c, p, ec, d, N, &cc, &fc));
+    if (!d.qnet) {                               // (the Q env's checks have looked at N and the env cfg)
+        if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
+        if (!ec) return fail(STMPC_EINVAL, "env cfg is NULL");
+        if (ec->action_mode != STMPC_ENV_CONTINUOUS_JERK)
+            return fail(STMPC_EINVAL, "the combined shield serves STMPC_ENV_CONTINUOUS_JERK only (the rollout policy is a continuous actor)");
+    }
+    DevP dp;
+    TRY(make_devp(p, &dp));
+    HIPCHK(hipSetDevice(c->device));
+    auto &u = c->cshield;                        // (a world initialised below outdates an earlier combined-shield env by its generation)
+    TRY(stmpc_env_reset_device(c, p, g, ec, N, d_obs, obs_stride, stream));
+    TRY(u.ensure(N, d.kmax));
+    TRY(c->cc.ensure(N, d.kmax, cc.rollout_length));
+    TRY(combined_ensure(c, N, d.kmax, dp.H, true));           // (the sparse solve's compact batch too: a step may set cc.sparse_control either way)
+    DevBuf *const zeroed[] = {&u.evals, &u.evals_tag, &u.count, &u.tag};      // (the Q env has no time counter: the takeover counters only)
+    for (int i = d.qnet ? 2 : 0; i < 4; ++i) HIPCHK(hipMemsetAsync(zeroed[i]->p, 0, (size_t)N * 4, (hipStream_t)stream));
+    u.N = N; u.kmax = d.kmax; u.rollout_time = d.rollout_time; u.L = cc.rollout_length; u.generation = c->sim.generation;
+    u.qpolicy = d.qnet ? d.qpolicy() : nullptr; u.n_per_member = d.n_per_member;
     return STMPC_OK;
 }
 
@@ -1841,77 +1862,43 @@ int stmpc_shield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmp
                                  const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
                                  float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk,
                                  double *d_executed_action, int32_t *d_takeover_ticks, void *stream) {
-    const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
-    return env_step(c, p, g, ec, N, SHIELD_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, &shield);
+    StepExtra x;
+    x.shield = sh; x.out = {d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    return env_step(c, p, g, ec, N, SHIELD_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, x);
 }
 
 // The env behind dqn.RLAgent.do_combined_control (dqn.py:117-200): the plain reset, then every buffer of the step and zeroed counters.
 int stmpc_cshield_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_cshield_env_cfg *sh,
                                    const stmpc_actor *actor, int N, float *d_obs, int obs_stride, void *stream) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    CCfg cc;
-    FeatCfg fc;
-    TRY(cshield_cfg_check(c, p, sh, actor, N, &cc, &fc));
-    if (N < 1) return fail(STMPC_EINVAL, "N must be positive");
-    if (!ec) return fail(STMPC_EINVAL, "env cfg is NULL");
-    if (ec->action_mode != STMPC_ENV_CONTINUOUS_JERK)
-        return fail(STMPC_EINVAL, "the combined shield serves STMPC_ENV_CONTINUOUS_JERK only (the rollout policy is a continuous actor)");
-    DevP dp;
-    TRY(make_devp(p, &dp));
-    HIPCHK(hipSetDevice(c->device));
-    auto &u = c->cshield;                        // (a world initialised below outdates an earlier combined-shield env by its generation)
-    TRY(stmpc_env_reset_device(c, p, g, ec, N, d_obs, obs_stride, stream));
-    TRY(u.ensure(N, sh->kmax));
-    TRY(c->cc.ensure(N, sh->kmax, cc.rollout_length));
-    TRY(combined_ensure(c, N, sh->kmax, dp.H, true));         // (the sparse solve's compact batch too: a step may set cc.sparse_control either way)
-    for (DevBuf *b : {&u.evals, &u.evals_tag, &u.count, &u.tag}) HIPCHK(hipMemsetAsync(b->p, 0, (size_t)N * 4, (hipStream_t)stream));
-    u.N = N; u.kmax = sh->kmax; u.rollout_time = sh->rollout_time; u.L = cc.rollout_length; u.generation = c->sim.generation;
-    u.qpolicy = nullptr; u.n_per_member = 0;
-    return STMPC_OK;
+    return combined_shield_reset(c, p, g, ec, combined_shield_of(sh, actor), N, d_obs, obs_stride, stream);
 }
 
 int stmpc_cshield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_cshield_env_cfg *sh,
                                   const stmpc_actor *actor, int N, const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated,
                                   uint8_t *d_truncated, float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason,
                                   double *d_executed_jerk, double *d_executed_action, int32_t *d_takeover_ticks, void *stream) {
-    const ShieldStep out{nullptr, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
-    const CShieldStep cs{sh, actor};
-    return env_step(c, p, g, ec, N, CSHIELD_ENV_ENTRY, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, &out,
-                    nullptr, &cs);
+    const CombinedShield cs = combined_shield_of(sh, actor);
+    StepExtra x;
+    x.combined = &cs; x.out = {d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    return env_step(c, p, g, ec, N, CSHIELD_ENV_ENTRY, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, x);
 }
 
-// The discrete envs behind dqn.RLAgent.do_combined_control (dqn.py:117-200) with DQNAgent.get_control (dqn.py:375-380) in the rollout: the plain reset,
-// then every buffer of the step and zeroed takeover counters.
+// The discrete envs behind dqn.RLAgent.do_combined_control (dqn.py:117-200) with DQNAgent.get_control (dqn.py:375-380) in the rollout: the same reset
+// (no time counter to zero) and the same step (the action index is not rewritten: no d_executed_action).
 int stmpc_qshield_env_reset_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_qshield_env_cfg *sh,
                                    const stmpc_qactor *qactor, const stmpc_qactor_pop *qactor_pop, int n_per_member, int N, float *d_obs, int obs_stride,
                                    void *stream) {
-    if (!c) return fail(STMPC_EINVAL, "ctx is NULL");
-    CCfg cc;
-    FeatCfg fc;
-    const QShieldStep qs{sh, qactor, qactor_pop, n_per_member};
-    TRY(qshield_cfg_check(c, p, ec, qs, N, &cc, &fc));
-    DevP dp;
-    TRY(make_devp(p, &dp));
-    HIPCHK(hipSetDevice(c->device));
-    auto &u = c->cshield;                        // (a world initialised below outdates an earlier combined-shield env by its generation)
-    TRY(stmpc_env_reset_device(c, p, g, ec, N, d_obs, obs_stride, stream));
-    TRY(u.ensure(N, sh->kmax));
-    TRY(c->cc.ensure(N, sh->kmax, cc.rollout_length));
-    TRY(combined_ensure(c, N, sh->kmax, dp.H, true));         // (the sparse solve's compact batch too: a step may set cc.sparse_control either way)
-    for (DevBuf *b : {&u.count, &u.tag}) HIPCHK(hipMemsetAsync(b->p, 0, (size_t)N * 4, (hipStream_t)stream));
-    u.N = N; u.kmax = sh->kmax; u.rollout_time = 0; u.L = cc.rollout_length; u.generation = c->sim.generation;
-    u.qpolicy = qs.policy(); u.n_per_member = n_per_member;
-    return STMPC_OK;
+    return combined_shield_reset(c, p, g, ec, combined_shield_of(sh, qactor, qactor_pop, n_per_member), N, d_obs, obs_stride, stream);
 }
 
 int stmpc_qshield_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_sim_cfg *g, const stmpc_env_cfg *ec, const stmpc_qshield_env_cfg *sh,
                                   const stmpc_qactor *qactor, const stmpc_qactor_pop *qactor_pop, int n_per_member, int N, const void *d_action, float *d_obs,
                                   int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats,
                                   uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk, int32_t *d_takeover_ticks, void *stream) {
-    const ShieldStep out{nullptr, d_takeover, d_reason, d_executed_jerk, nullptr, d_takeover_ticks};
-    const QShieldStep qs{sh, qactor, qactor_pop, n_per_member};
-    return env_step(c, p, g, ec, N, QSHIELD_ENV_ENTRY, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, &out,
-                    nullptr, nullptr, &qs);
+    const CombinedShield cs = combined_shield_of(sh, qactor, qactor_pop, n_per_member);
+    StepExtra x;
+    x.combined = &cs; x.out = {d_takeover, d_reason, d_executed_jerk, nullptr, d_takeover_ticks};
+    return env_step(c, p, g, ec, N, QSHIELD_ENV_ENTRY, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, x);
 }
 
 int stmpc_cshield_env_evals_device(stmpc_ctx *c, int N, int32_t *d_evals, void *stream) {
@@ -1945,8 +1932,9 @@ int stmpc_traffic_mix_env_step_device(stmpc_ctx *c, const stmpc_params *p, const
                                       double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs, double *d_final_stats,
                                       int32_t *d_traffic_type, int32_t *d_final_traffic_type, void *stream) {
     const MixStep mix{d_traffic_type, d_final_traffic_type};
-    return env_step(c, p, nullptr, ec, N, TRAFFIC_MIX_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream},
-                    nullptr, &mix);
+    StepExtra x;
+    x.mix = &mix;
+    return env_step(c, p, nullptr, ec, N, TRAFFIC_MIX_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream}, x);
 }
 
 // ... in front of the traffic mix (one policy across the types of configs/train_*_*.json): the mix's reset, then the shield's part; one takeover penalty,
@@ -1975,18 +1963,20 @@ int stmpc_shield_traffic_groups_env_step_device(stmpc_ctx *c, const stmpc_params
                                         float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated, float *d_final_obs,
                                         double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk, double *d_executed_action,
                                         int32_t *d_takeover_ticks, void *stream) {
-    const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    StepExtra x;
+    x.shield = sh; x.out = {d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
     return env_step(c, p, nullptr, ec, N, SHIELD_TRAFFIC_GROUPS_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream},
-                    &shield);
+                    x);
 }
 
 int stmpc_shield_reward_groups_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N,
                                                const void *d_action, float *d_obs, int obs_stride, double *d_reward, uint8_t *d_terminated, uint8_t *d_truncated,
                                                float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk,
                                                double *d_executed_action, int32_t *d_takeover_ticks, void *stream) {
-    const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    StepExtra x;
+    x.shield = sh; x.out = {d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
     return env_step(c, p, nullptr, ec, N, SHIELD_REWARD_GROUPS_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream},
-                    &shield);
+                    x);
 }
 
 int stmpc_shield_traffic_mix_env_step_device(stmpc_ctx *c, const stmpc_params *p, const stmpc_env_cfg *ec, const stmpc_shield_env_cfg *sh, int N,
@@ -1994,10 +1984,12 @@ int stmpc_shield_traffic_mix_env_step_device(stmpc_ctx *c, const stmpc_params *p
                                              float *d_final_obs, double *d_final_stats, uint8_t *d_takeover, int32_t *d_reason, double *d_executed_jerk,
                                              double *d_executed_action, int32_t *d_takeover_ticks, int32_t *d_traffic_type, int32_t *d_final_traffic_type,
                                              void *stream) {
-    const ShieldStep shield{sh, d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
+    StepExtra x;
+    x.shield = sh; x.out = {d_takeover, d_reason, d_executed_jerk, d_executed_action, d_takeover_ticks};
     const MixStep mix{d_traffic_type, d_final_traffic_type};
+    x.mix = &mix;
     return env_step(c, p, nullptr, ec, N, SHIELD_TRAFFIC_MIX_ENV, {d_action, d_obs, obs_stride, d_reward, d_terminated, d_truncated, d_final_obs, d_final_stats, stream},
-                    &shield, &mix);
+                    x);
 }
 
 int stmpc_traffic_mix_draw(uint64_t mix_seed, int env_index, uint32_t episode, const double *cum, int T) {

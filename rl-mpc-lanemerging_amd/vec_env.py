@@ -308,12 +308,11 @@ class MergeVecEnv:
         penalty, = _shield_args(takeover_penalty, shield_kmax)
         return _capi.ShieldEnvCfg.from_settings(Settings, shield_sparse, penalty, shield_kmax)
 
-    def _setup(self, n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic=None, rewards=None, mix=None, shield=None, shield_cfg=None, policy=None,
-               entries=None):
+    def _setup(self, n, env_id, seed, reward, autoreset, ctx, log_capacity, traffic=None, rewards=None, mix=None, shield=None, shield_cfg=None, entries=None):
         """What every constructor ends in, after its own checks: the env's settings and world (the remaining ValueErrors, all before the first device
-        call), its context and tensors, the shield's outputs (``shield``: None, "first_step" or "combined", with its ``shield_cfg``; ``policy``: the
-        combined shield's actor), the mix's (``mix``: what ``_mix_args`` returns) and the env's two entries, bound once (``entries``: a class's own pair
-        instead of ``env_entries``' -- it has then set the attributes of its leading arguments itself)."""
+        call), its context and tensors, the shield's outputs (``shield``: None, "first_step" or "combined", with its ``shield_cfg``), the mix's (``mix``:
+        what ``_mix_args`` returns) and the env's two entries, bound once (``entries``: a class's own pair instead of ``env_entries``'; a class sets the
+        attributes of ``_LEAD`` that only its entries take, such as the combined shield's policy, before it calls this)."""
         self.shield, self.shield_cfg = shield, shield_cfg
         self.env_id = Settings.GYM_ENVIRONMENT if env_id is None else env_id
         self.reward_name = Settings.REWARD_FUNCTION if reward is None else reward
@@ -381,8 +380,6 @@ class MergeVecEnv:
             out += [self._type, self._final_type]
             reset_tail = [self._type]
             self._info.update(traffic_type=self._type, final_traffic_type=self._final_type)
-        if entries != _Q_ENTRIES:
-            self._actor = policy.handle if policy is not None else None
         self._bind(entries, reset_tail, out)
 
     def _bind(self, entries, reset_tail, step_out):
@@ -531,7 +528,51 @@ class TrafficMixVecEnv(MergeVecEnv):
         return out
 
 
-class CombinedShieldVecEnv(MergeVecEnv):
+class _CombinedShieldEnv(MergeVecEnv):
+    """What the two envs behind the combined controller share, whichever policy proposes in the rollout: the checks of the env id and of where the policy
+    lives, the ``control`` overlay, the shield's cfg and ``shield_counts``.  ``noun`` is what the messages call the policy."""
+
+    @staticmethod
+    def _served_env_id(env_id, served, refusal):
+        """The env id (default: the Settings'), which must be one of ``served``: ``refusal % env_id`` otherwise."""
+        env_id = Settings.GYM_ENVIRONMENT if env_id is None else env_id
+        if env_id not in ENV_IDS:
+            raise ValueError("Invalid gym environment {} (one of {})".format(env_id, ", ".join(ENV_IDS)))
+        if env_id not in served:
+            raise ValueError(refusal % (env_id,))
+        return env_id
+
+    @staticmethod
+    def _placed(n, policy, ctx, kinds, wanted, noun, rows=""):
+        """``policy`` is a live hip-engine instance of ``kinds`` (``wanted`` names them) with the env's ``n`` rows (``rows``: how they split) on ``ctx``."""
+        if not isinstance(policy, kinds) or getattr(policy, "engine", None) != "hip" or getattr(policy, "handle", None) is None:
+            raise ValueError("policy must be a hip-engine %s, not %r" % (wanted, policy))
+        if int(n) < 1 or policy.n != int(n):
+            raise ValueError("%s was built for %d rows%s, the env has n = %r" % (noun, policy.n, rows, n))
+        if ctx is not None and policy.ctx is not ctx:
+            raise ValueError("%s lives on another context than the env's: build it on ctx (or leave ctx=None to take %s's)" % (noun, noun))
+
+    def _combined_setup(self, cfg_cls, n, policy, env_id, seed, reward, autoreset, log_capacity, shield_sparse, takeover_penalty, shield_kmax, control,
+                        entries=None, **cfg_args):
+        """The checked shield arguments and ``control`` overlay, the shield's cfg (``cfg_cls.from_settings`` with the policy's features and ``cfg_args``),
+        then ``_setup`` on the policy's context."""
+        from . import combined
+        penalty, = _shield_args(takeover_penalty, shield_kmax)
+        self.control = dict(control) if control is not None else {}
+        combined.control_cfgs([self.control])                               # (ValueError for a key that is no setting of do_combined_control)
+        cfg = cfg_cls.from_settings(combined._Overlay(Settings, self.control), shield_sparse, penalty, shield_kmax, features=policy.fcfg, **cfg_args)
+        if cfg.cc.remember_last_choice:
+            raise ValueError("REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED is out of scope behind the combined shield: the env keeps no takeover history")
+        self.policy = policy
+        self._setup(n, env_id, seed, reward, autoreset, policy.ctx, log_capacity, shield="combined", shield_cfg=cfg, entries=entries)
+
+    def shield_counts(self, reset=False):
+        """(states decided, controller solves run for them) on this env's context since the last reset of the counts (``stmpc_combined_counts``:
+        finished environments of a run without autoreset are decided too, and count; equal unless ``shield_sparse``)."""
+        return self.ctx.combined_counts(reset)
+
+
+class CombinedShieldVecEnv(_CombinedShieldEnv):
     """``MergeVecEnv`` whose every step runs behind the combined RL + ST controller, ``dqn.RLAgent.do_combined_control`` (dqn.py:117-200) -- the
     controller the reference deploys and evaluates (``EVALUATE_COMBINED_DDPG``, ``episodes.EpisodeRunner(controller="combined")``) -- on the device
     (``stmpc_cshield_env_reset_device`` / ``stmpc_cshield_env_step_device``), so that a policy trains in the closed loop it is deployed in.  A class of
@@ -558,30 +599,17 @@ class CombinedShieldVecEnv(MergeVecEnv):
 
     def __init__(self, n, policy, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, *, rollout_time="env", shield_sparse=False,
                  takeover_penalty=0.0, shield_kmax=32, control=None):
-        from . import actor as _actor, combined
-        env_id_ = Settings.GYM_ENVIRONMENT if env_id is None else env_id
-        if env_id_ not in ENV_IDS:
-            raise ValueError("Invalid gym environment {} (one of {})".format(env_id_, ", ".join(ENV_IDS)))
-        if env_id_ != "sumo-jerk-continuous-v0":
-            raise ValueError("the combined shield serves 'sumo-jerk-continuous-v0' only (the rollout policy is a continuous actor), not %r" % (env_id_,))
+        from . import actor as _actor
+        env_id_ = self._served_env_id(env_id, ("sumo-jerk-continuous-v0",),
+                                      "the combined shield serves 'sumo-jerk-continuous-v0' only (the rollout policy is a continuous actor), not %r")
         if isinstance(policy, _actor.ActorPopulation):
             raise ValueError("an ActorPopulation behind the combined shield is out of scope: policy is one actor.DDPGActor")
-        if not isinstance(policy, _actor.DDPGActor) or getattr(policy, "engine", None) != "hip" or getattr(policy, "handle", None) is None:
-            raise ValueError("policy must be a hip-engine actor.DDPGActor (pretrained, or DDPGActor.from_learner), not %r" % (policy,))
-        if int(n) < 1 or policy.n != int(n):
-            raise ValueError("the actor was built for %d rows, the env has n = %r" % (policy.n, n))
-        if ctx is not None and policy.ctx is not ctx:
-            raise ValueError("the actor lives on another context than the env's: build it on ctx (or leave ctx=None to take the actor's)")
+        self._placed(n, policy, ctx, _actor.DDPGActor, "actor.DDPGActor (pretrained, or DDPGActor.from_learner)", "the actor")
         if rollout_time not in _capi.CShieldEnvCfg.ROLLOUT_TIMES:
             raise ValueError("rollout_time must be 'env' or 'deployed', not %r" % (rollout_time,))
-        penalty, = _shield_args(takeover_penalty, shield_kmax)
-        self.control = dict(control) if control is not None else {}
-        combined.control_cfgs([self.control])                               # (ValueError for a key that is no setting of do_combined_control)
-        cfg = _capi.CShieldEnvCfg.from_settings(combined._Overlay(Settings, self.control), shield_sparse, penalty, shield_kmax, rollout_time, policy.fcfg)
-        if cfg.cc.remember_last_choice:
-            raise ValueError("REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED is out of scope behind the combined shield: the env keeps no takeover history")
-        self.policy, self.rollout_time = policy, rollout_time
-        self._setup(n, env_id_, seed, reward, autoreset, policy.ctx, log_capacity, shield="combined", shield_cfg=cfg, policy=policy)
+        self.rollout_time, self._actor = rollout_time, policy.handle
+        self._combined_setup(_capi.CShieldEnvCfg, n, policy, env_id_, seed, reward, autoreset, log_capacity, shield_sparse, takeover_penalty, shield_kmax,
+                             control, rollout_time=rollout_time)
         self._evals = self.torch.zeros(self.n, dtype=self.torch.int32, device=self.device)
 
     @property
@@ -590,11 +618,6 @@ class CombinedShieldVecEnv(MergeVecEnv):
         ``rollout_time="env"``, the episode's policy evaluations so far under "deployed" -- the ``evals`` to hand to an actor that proposes the action."""
         self.ctx.cshield_env_evals(self.n, self._evals.data_ptr(), self._stream())
         return self._evals
-
-    def shield_counts(self, reset=False):
-        """(states decided, controller solves run for them) on this env's context since the last reset of the counts (``stmpc_combined_counts``:
-        finished environments of a run without autoreset are decided too, and count; equal unless ``shield_sparse``)."""
-        return self.ctx.combined_counts(reset)
 
 
 def q_first_action_host(env_id, index, ego_acc, S=Settings):
@@ -616,7 +639,7 @@ def q_first_action_host(env_id, index, ego_acc, S=Settings):
     return np.where(bad, 0.0, value), bad
 
 
-class QCombinedShieldVecEnv(MergeVecEnv):
+class QCombinedShieldVecEnv(_CombinedShieldEnv):
     """A DISCRETE ``MergeVecEnv`` ("sumo-jerk-v0", "sumo-accel-v0") whose every step runs behind the combined RL + ST controller,
     ``dqn.RLAgent.do_combined_control`` (dqn.py:117-200) as ``DQNAgent`` inherits it, with a Q-network (``DQNAgent.get_control``, dqn.py:375-380)
     proposing rollout steps 2 ... ROLLOUT_LENGTH on the device (``stmpc_qshield_env_reset_device`` / ``stmpc_qshield_env_step_device``): a DQN learner
@@ -646,25 +669,16 @@ class QCombinedShieldVecEnv(MergeVecEnv):
 
     def __init__(self, n, policy, env_id=None, seed=0, reward=None, autoreset=True, ctx=None, log_capacity=0, *, shield_sparse=False, takeover_penalty=0.0,
                  shield_kmax=32, control=None):
-        from . import actor as _actor, combined
-        env_id_ = Settings.GYM_ENVIRONMENT if env_id is None else env_id
-        if env_id_ not in ENV_IDS:
-            raise ValueError("Invalid gym environment {} (one of {})".format(env_id_, ", ".join(ENV_IDS)))
-        if env_id_ not in self.MODE_OF:
-            raise ValueError("the combined shield behind a Q-network serves 'sumo-jerk-v0' and 'sumo-accel-v0', not %r: the continuous env's is "
-                             "CombinedShieldVecEnv" % (env_id_,))
+        from . import actor as _actor
+        env_id_ = self._served_env_id(env_id, self.MODE_OF, "the combined shield behind a Q-network serves 'sumo-jerk-v0' and 'sumo-accel-v0', not %r: the "
+                                                            "continuous env's is CombinedShieldVecEnv")
         if isinstance(policy, (_actor.DDPGActor, _actor.ActorPopulation)):
             raise ValueError("a DDPGActor or an ActorPopulation proposes continuous jerks: policy is an actor.DQNActor or an actor.QActorPopulation "
                              "(the continuous env's class is CombinedShieldVecEnv)")
         pop = isinstance(policy, _actor.QActorPopulation)
-        if not (pop or isinstance(policy, _actor.DQNActor)) or getattr(policy, "engine", None) != "hip" or getattr(policy, "handle", None) is None:
-            raise ValueError("policy must be a hip-engine actor.DQNActor (an export_q file, or DQNActor.from_learner) or an actor.QActorPopulation, not %r"
-                             % (policy,))
-        if int(n) < 1 or policy.n != int(n):
-            raise ValueError("the policy was built for %d rows%s, the env has n = %r"
-                             % (policy.n, " (P = %d members x n_per_member = %d)" % (policy.P, policy.n_per_member) if pop else "", n))
-        if ctx is not None and policy.ctx is not ctx:
-            raise ValueError("the policy lives on another context than the env's: build it on ctx (or leave ctx=None to take the policy's)")
+        self._placed(n, policy, ctx, (_actor.DQNActor, _actor.QActorPopulation),
+                     "actor.DQNActor (an export_q file, or DQNActor.from_learner) or an actor.QActorPopulation", "the policy",
+                     " (P = %d members x n_per_member = %d)" % (policy.P, policy.n_per_member) if pop else "")
         table = np.ascontiguousarray(env_cfg(env_id_, reward, autoreset, Settings, log_capacity)._actions, dtype=np.float64)     # (ValueError for an unknown reward)
         for m, a in enumerate(policy.members if pop else [policy]):
             who = "member %d" % m if pop else "the policy"
@@ -673,20 +687,9 @@ class QCombinedShieldVecEnv(MergeVecEnv):
             if np.asarray(a.action_values, dtype=np.float64).tobytes() != table.tobytes():
                 raise ValueError("the action table of %s is not the env's (%s of the Settings, byte for byte)"
                                  % (who, "JERK_VALUES_DQN" if env_id_ == "sumo-jerk-v0" else "ACCELERATION_VALUES_DQN"))
-        penalty, = _shield_args(takeover_penalty, shield_kmax)
-        self.control = dict(control) if control is not None else {}
-        combined.control_cfgs([self.control])                               # (ValueError for a key that is no setting of do_combined_control)
-        cfg = _capi.QShieldEnvCfg.from_settings(combined._Overlay(Settings, self.control), shield_sparse, penalty, shield_kmax, policy.fcfg)
-        if cfg.cc.remember_last_choice:
-            raise ValueError("REMEMBER_LAST_CHOICE_FOR_SWITCHING_COMBINED is out of scope behind the combined shield: the env keeps no takeover history")
-        self.policy = policy
         self._qactor, self._qpop, self._n_per_member = (None, policy.handle, policy.n_per_member) if pop else (policy.handle, None, 0)
-        self._setup(n, env_id_, seed, reward, autoreset, policy.ctx, log_capacity, shield="combined", shield_cfg=cfg, entries=_Q_ENTRIES)
-
-    def shield_counts(self, reset=False):
-        """(states decided, controller solves run for them) on this env's context since the last reset of the counts (``stmpc_combined_counts``:
-        finished environments of a run without autoreset are decided too, and count; equal unless ``shield_sparse``)."""
-        return self.ctx.combined_counts(reset)
+        self._combined_setup(_capi.QShieldEnvCfg, n, policy, env_id_, seed, reward, autoreset, log_capacity, shield_sparse, takeover_penalty, shield_kmax,
+                             control, entries=_Q_ENTRIES)
 
 
 class GroupedShieldVecEnv(TrafficMixVecEnv):

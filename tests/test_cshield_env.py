@@ -7,6 +7,7 @@ Box.  Every run is recorded once (``_recorded_run``) and shared by the tests tha
 import numpy as np
 import pytest
 
+from env_testlib import settings as _settings, flat as _flat
 from stmpc_testlib import pkg as _pkg, same as _same
 
 N, KMAX, SEED = 100, 16, 7
@@ -16,15 +17,6 @@ SHIELD_KEYS = ("takeover", "reason", "executed_jerk", "executed_action", "takeov
 KEYS = ("obs", "reward", "term", "trunc", "final_obs", "final_stats") + SHIELD_KEYS
 WORLD = ("status", "sim_ticks", "acc", "ego4")
 _cache = {}
-
-
-def _settings():
-    pkg = _pkg()
-    from rl_mpc_lanemerging_amd import combined_bench, episodes
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
-    pkg.apply_overrides(episodes.TRAFFIC_TYPES["default"])
-    return pkg.Settings
 
 
 def _actor_name():
@@ -502,16 +494,6 @@ def test_gpu_shape_table(restore_settings):
     for c in (ctx, ctx_t):
         c.check_error()
         c.close()
-
-
-def _flat(d, prefix=""):
-    out = {}
-    for k, v in d.items():
-        if isinstance(v, dict):
-            out.update(_flat(v, prefix + str(k) + "."))
-        else:
-            out[prefix + str(k)] = np.asarray(v).copy()
-    return out
 
 
 @pytest.mark.gpu

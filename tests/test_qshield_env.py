@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from env_testlib import settings as _settings, flat as _flat
 from stmpc_testlib import pkg as _pkg, same as _same
 
 N, KMAX, SEED = 100, 8, 7
@@ -23,15 +24,6 @@ SHIELD_KEYS = ("takeover", "reason", "executed_jerk", "takeover_ticks")
 KEYS = ("obs", "reward", "term", "trunc", "final_obs", "final_stats") + SHIELD_KEYS
 WORLD = ("status", "sim_ticks", "acc", "ego4")
 _cache = {}
-
-
-def _settings():
-    pkg = _pkg()
-    from rl_mpc_lanemerging_amd import combined_bench, episodes
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
-    pkg.apply_overrides(episodes.TRAFFIC_TYPES["default"])
-    return pkg.Settings
 
 
 def _table(env_id):
@@ -63,7 +55,7 @@ def _file_actor(tmp, env_id, ctx, n=N, seed=0, net=None):
     return actor.DQNActor(_q_file(tmp, env_id, seed, net), n, ctx, _settings(), mode=_mode(env_id))
 
 
-def _hash01(ticks, salt):
+def _salted01(ticks, salt):
     from rl_mpc_lanemerging_amd import groups
     return np.array([(groups.splitmix64(((e << 32) + int(t) + salt * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF) >> 11) / 9007199254740992.0
                      for e, t in enumerate(ticks)])
@@ -71,7 +63,7 @@ def _hash01(ticks, salt):
 
 def _mixed_actions(ticks, own, A):
     """The policy's own index where the hash of (environment, episode tick) says so (half of them), else a uniform index from another hash."""
-    return np.where(_hash01(ticks, 1) < 0.5, own, np.minimum((_hash01(ticks, 2) * A).astype(np.int64), A - 1)).astype(np.int32)
+    return np.where(_salted01(ticks, 1) < 0.5, own, np.minimum((_salted01(ticks, 2) * A).astype(np.int64), A - 1)).astype(np.int32)
 
 
 def _env(ctx, env_id, policy, **kw):
@@ -434,7 +426,7 @@ def test_gpu_a_view_sees_the_learners_update(restore_settings, tmp_path):
     obs = env.reset()
     stale.reset()
     act = torch.as_tensor(_mixed_actions(np.zeros(N), np.zeros(N, np.int64), A), device="cuda")
-    reward = torch.as_tensor(_hash01(np.zeros(N), 3) * 4 - 2, device="cuda")
+    reward = torch.as_tensor(_salted01(np.zeros(N), 3) * 4 - 2, device="cuda")
     no = torch.zeros(N, dtype=torch.bool, device="cuda")
     L.push(obs.clone(), None, act, reward, obs.clone(), no, no, final_obs=obs.clone())
     L.update(3)
@@ -614,16 +606,6 @@ def test_gpu_shape_table(restore_settings, tmp_path):
     for c in (ctx, ctx_t):
         c.check_error()
         c.close()
-
-
-def _flat(d, prefix=""):
-    out = {}
-    for k, v in d.items():
-        if isinstance(v, dict):
-            out.update(_flat(v, prefix + str(k) + "."))
-        else:
-            out[prefix + str(k)] = np.asarray(v).copy()
-    return out
 
 
 class _Summing:

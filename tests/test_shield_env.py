@@ -6,19 +6,11 @@ shield_kmax = 32.  Every shielded run is recorded once (``_recorded_run``) and s
 import numpy as np
 import pytest
 
+from env_testlib import settings as _settings, flat as _flat
 from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same
 
 N, KMAX, SEED, ACT_SEED = 96, 32, 7, 11
 _cache = {}
-
-
-def _settings():
-    pkg = _pkg()
-    from rl_mpc_lanemerging_amd import combined_bench, episodes
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
-    pkg.apply_overrides(episodes.TRAFFIC_TYPES["default"])
-    return pkg.Settings
 
 
 def _actions(env, rng, n):
@@ -367,16 +359,6 @@ def test_gpu_step_entry_refusals_and_the_plain_step_stays_legal(restore_settings
     for e in (shielded, plain, discrete, fresh):
         e.check_error()
         e.ctx.close()
-
-
-def _flat(d, prefix=""):
-    out = {}
-    for k, v in d.items():
-        if isinstance(v, dict):
-            out.update(_flat(v, prefix + str(k) + "."))
-        else:
-            out[prefix + str(k)] = np.asarray(v).copy()
-    return out
 
 
 @pytest.mark.gpu

@@ -13,6 +13,7 @@ finishes an episode and is reset within the STEPS = 60 steps.  Actions: seeded u
 import numpy as np
 import pytest
 
+from env_testlib import flat as _flat, hash01 as _hash01, episodes_of as _episodes_of, log_rows as _log_rows
 from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same, settings_of as _settings_of, linit as _linit
 
 CONT, DISC = "sumo-jerk-continuous-v0", "sumo-jerk-v0"
@@ -214,15 +215,6 @@ def test_gpu_per_group_takeover_penalty_is_exact(restore_settings):
 
 # ---- the traffic mix -----------------------------------------------------------------------------------------------------------------------------
 MIX, MIX_TICKS = ["low", "default", "fast"], 30
-_M64 = (1 << 64) - 1
-
-
-def _hash01(e, tick):
-    z = (0x9E3779B97F4A7C15 * (e * 1000003 + tick + 1)) & _M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    z ^= z >> 31
-    return (z >> 11) / 9007199254740992.0
 
 
 def _mix_run(env, steps):
@@ -248,25 +240,6 @@ def _mix_run(env, steps):
     return out
 
 
-def _episodes(run, n):
-    """{(e, j): the record of finished episode j of row e}, as tests/test_traffic_mix.py cuts a run, with the shield's outputs of every tick of it"""
-    eps = {}
-    for e in range(n):
-        start, s0, j = run["obs0"][e], 0, 0
-        for s in np.flatnonzero(run["done"][:, e]):
-            ep = {"start": start, "obs": run["obs"][s0:s, e], "final_observation": run["final_observation"][s, e], "final_stats": run["final_stats"][s, e],
-                  "ticks": run["ticks"][s0:s, e], "end_step": int(s)}
-            ep.update({k: run[k][s0:s + 1, e] for k in ("reward", "terminated", "truncated") + INFO})
-            eps[(e, j)] = ep
-            start, s0, j = run["obs"][s, e], s + 1, j + 1
-    return eps
-
-
-def _log_rows(log):
-    cols = [k for k in sorted(log) if k not in ("traffic_type", "traffic_group", "reward_group")]
-    return {(int(e), int(j)): np.array([log[k][i] for k in cols], dtype=np.float64).tobytes() for i, (e, j) in enumerate(zip(log["env"], log["episode"]))}
-
-
 @pytest.mark.gpu
 def test_gpu_every_shielded_mixed_episode_is_the_lone_shielded_envs_episode(restore_settings):
     pkg = _pkg()
@@ -283,7 +256,7 @@ def test_gpu_every_shielded_mixed_episode_is_the_lone_shielded_envs_episode(rest
     assert set(mixed) >= set(INFO) | {"traffic_type", "final_traffic_type"}
     share = env.takeover_share()
     ctx.close()
-    mine, mlog = _episodes(mixed, N), _log_rows(mixed["log"])
+    mine, mlog = _episodes_of(mixed, N, INFO), _log_rows(mixed["log"])
     assert len(mine) == mixed["done"].sum() == len(mlog) and set(mine) == set(mlog)
     j_max = max(j for _, j in mine)
     theirs = []
@@ -294,7 +267,7 @@ def test_gpu_every_shielded_mixed_episode_is_the_lone_shielded_envs_episode(rest
             lenv = vec_env.MergeVecEnv(N, env_id=CONT, seed=7, ctx=lctx, log_capacity=64 * N, shield="first_step", takeover_penalty=0.5)
         r = _mix_run(lenv, (j_max + 1) * (MIX_TICKS + 1))
         lctx.close()
-        theirs.append((_episodes(r, N), _log_rows(r["log"])))
+        theirs.append((_episodes_of(r, N, INFO), _log_rows(r["log"])))
     per_type, changes, takeovers = [0] * len(MIX), 0, 0
     for (e, j), ep in sorted(mine.items()):
         t = vec_env.traffic_mix_draw(env.mix_seed, e, j, env.mix_cum)
@@ -477,16 +450,6 @@ def test_gpu_every_step_entry_serves_exactly_its_own_reset_shape(gpu_ctx, restor
 
 # ---- training: a population behind the shield, member m on traffic m -------------------------------------------------------------------------------
 L_SEEDS = (11, 12, 13)
-
-
-def _flat(d, prefix=""):
-    out = {}
-    for k, v in d.items():
-        if isinstance(v, dict):
-            out.update(_flat(v, prefix + str(k) + "."))
-        else:
-            out[prefix + str(k)] = np.asarray(v).copy()
-    return out
 
 
 @pytest.mark.gpu

@@ -1,15 +1,16 @@
-"""The suite's own structure: no test module imports another (what two of them share is in stmpc_testlib.py or learner_testlib.py), the helpers that
-were once copied from module to module are defined in no test module again, and the shared comparators still bite."""
+"""The suite's own structure: no test module imports another (what two of them share is in stmpc_testlib.py, learner_testlib.py or env_testlib.py), the
+helpers that were once copied from module to module are defined in no test module again, and the shared comparators and env helpers still bite."""
 import ast
 import glob
 import os
 
 import numpy as np
 
+from env_testlib import episodes_of, hash01, log_rows
 from learner_testlib import FLOOR, bits64, bits_equal, check_4x
 from stmpc_testlib import REPO, bits, same
 
-SHARED_ONLY = {"_capi", "_rel_err", "_check_4x", "_record"}
+SHARED_ONLY = {"_capi", "_rel_err", "_check_4x", "_record", "_flat", "_hash01", "_log_rows", "_episodes"}
 
 
 def test_no_test_module_imports_another_or_redefines_a_shared_helper():
@@ -49,3 +50,47 @@ def test_check_4x_passes_at_its_bound_and_fails_just_above_it():
     assert FLOOR == 8 * 2.0 ** -23                                 # the floor governs: an exact float32 twin
     assert check_4x("at the floor", at(FLOOR), f64, f64) and not check_4x("above the floor", at(FLOOR + 2.0 ** -40), f64, f64)
     assert check_4x("floor, small twin error", at(FLOOR), at(FLOOR / 8), f64) and not check_4x("floor, small twin error", at(FLOOR * 1.001), at(FLOOR / 8), f64)
+
+
+def test_hash01_at_four_literal_pairs():
+    """The values the env tests' copies of it gave before they became one: exact, every operation is on integers but the last division by 2^53."""
+    want = {(0, 0): "0x1.c4415072f63b9p-1", (1, 0): "0x1.e87d761ce519bp-1", (95, 50): "0x1.4ae3b978a7500p-8", (71, 30): "0x1.de140a44df3c0p-4"}
+    for (e, tick), value in want.items():
+        assert hash01(e, tick) == float.fromhex(value), (e, tick)
+    assert hash01(0, 0) == 0.8833108082136426
+
+
+def test_episodes_of_cuts_a_hand_made_run_with_and_without_extra_keys():
+    """2 rows x 5 ticks: row 0 ends an episode at tick 2 and another at tick 4 (the run's end), row 1 none.  obs[s, e] = 10 e + s + 1, obs0[e] = 10 e."""
+    step, row = np.mgrid[0:5, 0:2]
+    done = np.zeros((5, 2), bool)
+    done[2, 0] = done[4, 0] = True
+    run = {"obs0": np.array([0.0, 10.0]), "obs": 10.0 * row + step + 1, "done": done, "final_observation": 100.0 + step + 0 * row,
+           "final_stats": 200.0 + step + 0 * row, "ticks": step + 0 * row, "reward": -1.0 * step + 0 * row, "terminated": done, "truncated": ~done,
+           "takeover": step % 2 == 0}
+    eps = episodes_of(run, 2)
+    assert sorted(eps) == [(0, 0), (0, 1)]
+    first, second = eps[(0, 0)], eps[(0, 1)]
+    assert set(first) == {"start", "obs", "final_observation", "final_stats", "ticks", "end_step", "reward", "terminated", "truncated"}
+    assert first["start"] == 0.0 and first["obs"].tolist() == [1.0, 2.0] and first["final_observation"] == 102.0 and first["final_stats"] == 202.0
+    assert first["ticks"].tolist() == [0, 1] and first["end_step"] == 2 and first["reward"].tolist() == [0.0, -1.0, -2.0]
+    assert first["terminated"].tolist() == [False, False, True] and first["truncated"].tolist() == [True, True, False]
+    # the next episode starts from the observation the step that ended the first one returned
+    assert second["start"] == 3.0 and second["obs"].tolist() == [4.0] and second["end_step"] == 4 and second["reward"].tolist() == [-3.0, -4.0]
+    assert second["final_observation"] == 104.0 and second["ticks"].tolist() == [3]
+    assert episodes_of(run, 1).keys() == eps.keys()                # (n: the rows looked at)
+    extra = episodes_of(run, 2, ("takeover",))
+    assert set(extra[(0, 0)]) == set(first) | {"takeover"} and extra[(0, 0)]["takeover"].tolist() == [True, False, True]
+    assert extra[(0, 1)]["takeover"].tolist() == [False, True]
+    assert all(np.array_equal(extra[key][k], eps[key][k]) for key in eps for k in eps[key])
+
+
+def test_log_rows_keys_by_env_and_episode_and_ignores_the_traffic_type():
+    log = {"env": np.array([3, 0]), "episode": np.array([1, 0]), "ticks": np.array([40, 45]), "episode_return": np.array([-1.5, 2.25]),
+           "traffic_type": np.array([2, 1])}
+    rows = log_rows(log)
+    assert set(rows) == {(3, 1), (0, 0)}
+    # the columns in sorted order: env, episode, episode_return, ticks
+    assert rows[(3, 1)] == np.array([3, 1, -1.5, 40], np.float64).tobytes() and rows[(0, 0)] == np.array([0, 0, 2.25, 45], np.float64).tobytes()
+    assert log_rows(dict(log, traffic_type=np.array([0, 0]))) == rows and log_rows({k: v for k, v in log.items() if k != "traffic_type"}) == rows
+    assert log_rows(dict(log, ticks=np.array([41, 45])))[(3, 1)] != rows[(3, 1)]

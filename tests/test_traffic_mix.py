@@ -15,6 +15,7 @@ third hold their speed (arrivals), a third brake (out of time).
 import numpy as np
 import pytest
 
+from env_testlib import hash01 as _hash01, episodes_of as _episodes_of, log_rows as _log_rows
 from stmpc_testlib import pkg as _pkg, bits as _bits, same as _same
 
 N, SEED, STEPS = 96, 7, 300
@@ -22,16 +23,7 @@ MIX = ["low", "default", "fast"]
 TICK, EPISODE_S, MAX_TICKS = 0.4, 20.0, 50
 CONT, DISC = "sumo-jerk-continuous-v0", "sumo-jerk-v0"
 KEYS = ("obs", "reward", "terminated", "truncated", "final_observation", "final_stats", "ticks")
-_M64 = (1 << 64) - 1
 _cache = {}
-
-
-def _hash01(e, tick):
-    z = (0x9E3779B97F4A7C15 * (e * 1000003 + tick + 1)) & _M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    z ^= z >> 31
-    return (z >> 11) / 9007199254740992.0
 
 
 def _action_table(env_id):
@@ -93,25 +85,6 @@ def _run(ctx, key, steps, env_id=CONT, autoreset=True, **kwargs):
     return out
 
 
-def _episodes(run):
-    """{(e, j): the record of finished episode j of row e}: the observation it started from, every later observation of it, its final observation,
-    rewards, flags and statistics row."""
-    eps = {}
-    for e in range(N):
-        start, s0, j = run["obs0"][e], 0, 0
-        for s in np.flatnonzero(run["done"][:, e]):
-            eps[(e, j)] = {"start": start, "obs": run["obs"][s0:s, e], "final_observation": run["final_observation"][s, e], "reward": run["reward"][s0:s + 1, e],
-                           "terminated": run["terminated"][s0:s + 1, e], "truncated": run["truncated"][s0:s + 1, e], "final_stats": run["final_stats"][s, e],
-                           "ticks": run["ticks"][s0:s, e], "end_step": int(s)}
-            start, s0, j = run["obs"][s, e], s + 1, j + 1
-    return eps
-
-
-def _log_rows(log):
-    cols = [k for k in sorted(log) if k not in ("traffic_type", "traffic_group", "reward_group")]
-    return {(int(e), int(j)): np.array([log[k][i] for k in cols], dtype=np.float64).tobytes() for i, (e, j) in enumerate(zip(log["env"], log["episode"]))}
-
-
 def _mixed(gpu_ctx):
     return _run(gpu_ctx, "mixed", STEPS, traffic_mix=MIX)
 
@@ -131,7 +104,7 @@ def test_gpu_a_mix_of_one_type_is_the_plain_env(gpu_ctx, restore_settings, env_i
         assert _same(mixed[k], lone[k][:STEPS] if k != "obs0" else lone[k]), (env_id, k)
     assert mixed["done"].sum() > N and (mixed["episode"][-1] >= 2).all()                                  # (every row through autoresets)
     assert (mixed["traffic_type"] == 0).all() and (mixed["final_traffic_type"] == 0).all() and (mixed["type0"] == 0).all()
-    lone_eps = _episodes(lone)                                  # (the lone run may be a longer one another test made: its first STEPS steps)
+    lone_eps = _episodes_of(lone, N)                                  # (the lone run may be a longer one another test made: its first STEPS steps)
     lone_log = {k: v for k, v in _log_rows(lone["log"]).items() if lone_eps[k]["end_step"] < STEPS}
     assert _log_rows(mixed["log"]) == lone_log and len(lone_log) == mixed["done"].sum()
 
@@ -142,12 +115,12 @@ def test_gpu_every_mixed_episode_is_the_lone_envs_episode(gpu_ctx, restore_setti
     from rl_mpc_lanemerging_amd import vec_env
     mixed = _mixed(gpu_ctx)
     env = mixed["env"]
-    mine, mlog = _episodes(mixed), _log_rows(mixed["log"])
+    mine, mlog = _episodes_of(mixed, N), _log_rows(mixed["log"])
     assert len(mine) == mixed["done"].sum() == len(mlog) and set(mine) == set(mlog)
     j_max = max(j for _, j in mine)
     lone_steps = (j_max + 1) * (MAX_TICKS + 1)
     lones = [_run(gpu_ctx, ("lone", t, CONT), lone_steps, traffic=[t]) for t in MIX]
-    theirs = [(_episodes(r), _log_rows(r["log"])) for r in lones]
+    theirs = [(_episodes_of(r, N), _log_rows(r["log"])) for r in lones]
     per_type, status_seen, types_of_row = [0] * len(MIX), set(), [set() for _ in range(N)]
     for (e, j), ep in sorted(mine.items()):
         t = vec_env.traffic_mix_draw(env.mix_seed, e, j, env.mix_cum)
@@ -185,7 +158,7 @@ def test_gpu_the_type_outputs_are_the_twins_draws(gpu_ctx, restore_settings):
         before = after
     assert len(set(mixed["traffic_type"].ravel().tolist())) == len(MIX)
     log = mixed["log"]
-    ends = {(e, j): ep["end_step"] for (e, j), ep in _episodes(mixed).items()}
+    ends = {(e, j): ep["end_step"] for (e, j), ep in _episodes_of(mixed, N).items()}
     recorded = np.array([mixed["final_traffic_type"][ends[(int(e), int(j))], int(e)] for e, j in zip(log["env"], log["episode"])])
     assert np.array_equal(env.traffic_of_log(log), recorded) and np.array_equal(log["traffic_type"], recorded)
     summary = env.summary_by_traffic(log)
