@@ -920,6 +920,46 @@ int  stmpc_pop_dqn_per_enable(stmpc_dqn_pop *pop, const stmpc_per_cfg *cfgs, con
 int  stmpc_pop_dqn_replay_read(stmpc_dqn *learner, int64_t first, int64_t count, float *rows);
 
 /*
+ * Multi-step (n-step) returns for the three learners and their populations: the uncorrected n-step target of Rainbow (Hessel et al. 2018,
+ * "Multi-step learning": R = sum_k gamma^k r_{t+k+1}, bootstrapped with gamma^n) and of D4PG (Barth-Maron et al. 2018, eq. 5), which the reference's
+ * third agent (rainbow.py, the `all` library's rainbow preset with its n_steps) trains with.  (Additive: new entries only, no signature or struct of
+ * ABI 8 changes, so STMPC_ABI_VERSION stays 8; the three cfg structs keep their layout, so a caller written before this section stays valid, and a
+ * learner on which no enable entry was called -- or one enabled with n_step 1 -- computes what it computed before, bit for bit.  The entries read
+ * stmpc_nstep_* / stmpc_pop_nstep_*: the lone learners' prefixes are closed sets.)
+ *   The return is formed at sampling time from the ring itself.  A push writes its N rows at cursor + e, so the transition that follows ring row i
+ *   in the same env is row (i + N) % capacity as long as every push has N rows.  age(i) = (cursor - 1 - i) mod capacity; row_k = (i + k N) % capacity
+ *   exists iff age(i) >= k N.  The window of row i has length m = the smallest k + 1 (k = 0 .. n_step - 1) at which row_k is done (terminated or
+ *   truncated), k + 1 == n_step, or row_{k+1} does not exist (the window ran into the ring's newest rows: a shorter return, not a refusal).
+ *   R = sum_{k<m} gamma^k r(row_k) and disc = gamma^m, accumulated in fp64 from (double)(float)gamma in k order with unfused operations and rounded to
+ *   float32 once; s' and the mask are row_{m-1}'s (a truncated row bootstraps from its final observation with mask 1, a terminated one has mask 0).
+ *   DDPG: y = R + disc * mask * Qt(s', pi_t(s')); TD3: the same with the minimum of both target critics; DQN: g = disc * Qsel, clipped if asked,
+ *   y = R + g (R alone where mask = 0).  Prioritised replay's priorities come from this target's error.  gather_device then returns row i with s'
+ *   and the mask of row_{m-1} and R in the reward's column.
+ *   The push of an enabled learner with n_step > 1 writes terminated || truncated into column 67 of the row (zero otherwise, as before).
+ *   stmpc_nstep_enable_ddpg / _dqn   on a learner whose ring is empty (a TD3 learner: on its stmpc_td3_base).  STMPC_EINVAL for n_step outside
+ *                   1 ... STMPC_NSTEP_MAX, and with n_step > 1 for rows_per_push < 1 or n_step * rows_per_push > capacity, a non-empty ring, a member of
+ *                   a population.  Afterwards a push with N != rows_per_push is refused (n_step 1: any N stays legal)
+ *   stmpc_pop_nstep_enable_ddpg / _td3 / _dqn   cfgs HOST [P], P = the population's size: member m gets cfgs[m], so "which n" is a sweep one population
+ *                   runs; rows_per_push is the population's n_per_member.  Every member passes the lone entry's checks before any changes; then the
+ *                   device tables are written anew.  A member is bit-identical to a lone learner with the same cfgs given its slice
+ *   stmpc_nstep_window_ddpg / _dqn   debug, HOST: out [n_idx][4] fp64 = R, disc, the ring row of the window's last transition, m for the n_idx ring
+ *                   rows idx (each a filled row, else STMPC_EINVAL), so that a test can check every live row and not a sampled subset; synchronises.
+ *                   They work on a borrowed member of a population as on a lone learner
+ */
+#define STMPC_NSTEP_MAX 16
+typedef struct stmpc_nstep_cfg {
+    int32_t n_step;                  /* the window's length, 1 ... STMPC_NSTEP_MAX (1: one-step targets) */
+    int32_t rows_per_push;           /* N of every push: the env's size, a population's n_per_member; read when n_step > 1 */
+} stmpc_nstep_cfg;
+int  stmpc_nstep_enable_ddpg(stmpc_ddpg *learner, const stmpc_nstep_cfg *cfg);
+int  stmpc_nstep_enable_dqn(stmpc_dqn *learner, const stmpc_nstep_cfg *cfg);
+int  stmpc_pop_nstep_enable_ddpg(stmpc_ddpg_pop *pop, const stmpc_nstep_cfg *cfgs, int P);
+int  stmpc_pop_nstep_enable_td3(stmpc_td3_pop *pop, const stmpc_nstep_cfg *cfgs, int P);
+int  stmpc_pop_nstep_enable_dqn(stmpc_dqn_pop *pop, const stmpc_nstep_cfg *cfgs, int P);
+int  stmpc_nstep_window_ddpg(stmpc_ddpg *learner, const int64_t *idx, int n_idx, double *out);
+int  stmpc_nstep_window_dqn(stmpc_dqn *learner, const int64_t *idx, int n_idx, double *out);
+
+/*
  * A Q-network as the policy of the combined controller and of the first-step shield: DQNAgent.get_control (dqn.py:375-380) -- state vector -> Q ->
  * argmax -> JERK_VALUES_DQN[a] -- for N states in ONE launch, behind which RLAgent.do_combined_control runs as it does behind the DDPG actor.
  * (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8; no entry above changes what it computes.)  The

@@ -268,6 +268,11 @@ class PERCfg(C.Structure):
     _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("min_priority", C.c_double), ("max_priority", C.c_double)]
 
 
+class NStepCfg(C.Structure):
+    """``stmpc_nstep_cfg`` (include/stmpc.h): the length of the multi-step return's window and the rows of every push."""
+    _fields_ = [("n_step", C.c_int32), ("rows_per_push", C.c_int32)]
+
+
 class DQNCfg(C.Structure):
     """``stmpc_dqn_cfg`` (include/stmpc.h): the Q-network's shape, the replay size and the constants of the DQN update (defaults: the reference's config.py)."""
     _fields_ = [("n_obs", C.c_int32), ("h1", C.c_int32), ("n_actions", C.c_int32), ("batch", C.c_int32), ("capacity", C.c_int32), ("target_period", C.c_int32),
@@ -312,6 +317,8 @@ EXPORTS = (
     "stmpc_dqn_padded_read",
     "stmpc_pop_dqn_create", "stmpc_pop_dqn_destroy", "stmpc_pop_dqn_size", "stmpc_pop_dqn_member", "stmpc_pop_dqn_act_device",
     "stmpc_pop_dqn_push_device", "stmpc_pop_dqn_update_device", "stmpc_pop_dqn_stats_device", "stmpc_pop_dqn_per_enable", "stmpc_pop_dqn_replay_read",
+    "stmpc_nstep_enable_ddpg", "stmpc_nstep_enable_dqn", "stmpc_pop_nstep_enable_ddpg", "stmpc_pop_nstep_enable_td3", "stmpc_pop_nstep_enable_dqn",
+    "stmpc_nstep_window_ddpg", "stmpc_nstep_window_dqn",
     "stmpc_qactor_create", "stmpc_qactor_view_dqn", "stmpc_qactor_destroy", "stmpc_qactor_set_limits", "stmpc_qactor_eval_device",
     "stmpc_pop_qactor_create", "stmpc_pop_qactor_destroy", "stmpc_pop_qactor_size", "stmpc_pop_qactor_eval_device",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
@@ -343,6 +350,8 @@ TRAFFIC_MIX_MAX = 64                  # STMPC_TRAFFIC_MIX_MAX
 TD3_SLOTS = ("critic2", "critic2_target", "critic2_m", "critic2_v")     # STMPC_TD3_CRITIC2 ... STMPC_TD3_CRITIC2_V
 DQN_SLOTS = ("q", "q_target", "q_m", "q_v")     # STMPC_DQN_Q ... STMPC_DQN_Q_V
 DQN_GRAD = 4                          # STMPC_DQN_GRAD: the gradient, for dqn_padded_read
+NSTEP_MAX = 16                        # STMPC_NSTEP_MAX
+DONE_COL = 67                         # the replay row's done column (terminated || truncated) on a learner with n_step > 1
 DQN_ACTION_COL = 66                   # the replay row's action column of a DQN learner
 QACTOR_MODES = {"jerk": 0, "acceleration": 1}      # STMPC_QACTOR_JERK, STMPC_QACTOR_ACCELERATION
 DDPG_SLOTS = ("actor", "actor_target", "actor_m", "actor_v", "critic", "critic_target", "critic_m", "critic_v")     # STMPC_DDPG_ACTOR ... STMPC_DDPG_CRITIC_V
@@ -549,6 +558,12 @@ def load():
     lib.stmpc_pop_dqn_stats_device.argtypes = [vp, vp, vp]
     lib.stmpc_pop_dqn_per_enable.argtypes = [vp, C.POINTER(PERCfg), C.POINTER(C.c_uint8), C.c_int]
     lib.stmpc_pop_dqn_replay_read.argtypes = [vp, C.c_int64, C.c_int64, fp]
+    for name in ("stmpc_nstep_enable_ddpg", "stmpc_nstep_enable_dqn"):
+        getattr(lib, name).argtypes = [vp, C.POINTER(NStepCfg)]
+    for name in ("stmpc_pop_nstep_enable_ddpg", "stmpc_pop_nstep_enable_td3", "stmpc_pop_nstep_enable_dqn"):
+        getattr(lib, name).argtypes = [vp, C.POINTER(NStepCfg), C.c_int]
+    for name in ("stmpc_nstep_window_ddpg", "stmpc_nstep_window_dqn"):
+        getattr(lib, name).argtypes = [vp, i64p, C.c_int, dp]
     lib.stmpc_qactor_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, dp, C.c_int, C.POINTER(vp)]
     lib.stmpc_qactor_view_dqn.argtypes = [vp, C.c_int, dp, C.c_int, C.c_int, C.POINTER(vp)]
     lib.stmpc_qactor_destroy.argtypes = [vp]
@@ -1245,6 +1260,21 @@ class Context:
 
     def dqn_pop_per_enable(self, handle, cfgs):
         self._chk(self._lib.stmpc_pop_dqn_per_enable(handle, *self._per_table(cfgs)))
+
+    # -- multi-step returns (stmpc_nstep_*, stmpc_pop_nstep_*): once per learner / population, on empty rings; ``kind``: "ddpg" (a TD3 learner's base too), "td3" (populations) or "dqn"
+    def nstep_enable(self, kind, handle, cfg):
+        self._chk(getattr(self._lib, "stmpc_nstep_enable_" + kind)(handle, C.byref(cfg)))
+
+    def pop_nstep_enable(self, kind, handle, cfgs):
+        table = (NStepCfg * len(cfgs))(*cfgs)
+        self._chk(getattr(self._lib, "stmpc_pop_nstep_enable_" + kind)(handle, table, len(cfgs)))
+
+    def nstep_window(self, kind, handle, idx):
+        """Debug: float64 [len(idx)][4] = R, disc, the ring row of the window's last transition, m of the ring rows ``idx``; synchronises."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        out = np.zeros((idx.size, 4), dtype=np.float64)
+        self._chk(getattr(self._lib, "stmpc_nstep_window_" + kind)(handle, idx.ctypes.data_as(C.POINTER(C.c_int64)), int(idx.size), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     def dqn_pop_replay_read(self, learner_handle, first, count):
         """Debug: ``count`` rows from row ``first`` of a DQN learner's ring (a borrowed member's or a lone learner's), float32 [count][DDPG_ROW]; synchronises."""

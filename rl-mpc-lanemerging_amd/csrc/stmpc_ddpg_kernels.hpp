@@ -26,6 +26,7 @@ namespace stmpc {
 
 constexpr int DG_ROW = 68;          // replay row, float32: [0, 32) s, time feature, action, zeros; [32, 64) s', time feature, zeros; 64 reward; 65 mask
 constexpr int DG_R = 64, DG_MASK = 65;
+constexpr int DG_DONE = 67;         // terminated || truncated, written by the push of a learner with n_step > 1 (stmpc_nstep_kernels.hpp); else zero
 constexpr int DG_WG_WAVES = 8;      // waves per weight-gradient tile
 // counters (int64): ring cursor, fill, updates done, acting calls with noise, frames pushed
 enum { DG_CURSOR = 0, DG_FILL = 1, DG_UPDATES = 2, DG_ACTS = 3, DG_FRAMES = 4, DG_NCNT = 8 };
@@ -56,7 +57,10 @@ struct DdpgDev {
     float *aw, *atd;                // [Bp] importance weights; [Bp] Q - y of the last critic pass
     double per_alpha, per_beta, per_min, per_max;
     long long per_L;                // leaves: capacity rounded up to a power of two
+    // multi-step returns (stmpc_nstep_kernels.hpp); n_step <= 1 on a learner with one-step targets, whose kernels then do what they did without these
+    int n_step, rows_push;          // the window's length n (<= 16) and the rows N of every push
 };
+struct NstepWin { float R, disc; long long last; int m; };   // a row's window: return, gamma^m, the ring row of its last transition, its length
 
 __host__ __device__ inline int dg_o_b0(int h1p) { return h1p * AT_KIN; }
 __host__ __device__ inline int dg_o_w1(int h1p) { return h1p * AT_KIN + h1p; }
@@ -91,6 +95,9 @@ __device__ __forceinline__ long long dg_row_index(const DdpgDev &L, long long up
     return L.idx ? L.idx[r] : (long long)(dg_hash(L.seed, (unsigned long long)upd, (unsigned long long)r) % (unsigned long long)fill);
 }
 __device__ __forceinline__ void per_push_tree(const DdpgDev &L, long long cursor, int N);      // stmpc_per_kernels.hpp
+__device__ __forceinline__ NstepWin nstep_window(const DdpgDev &L, long long i, long long cursor);                      // stmpc_nstep_kernels.hpp
+__device__ __forceinline__ void nstep_gather_tile(const DdpgDev &L, float *X, float *Xn, float *sc, long long idx, bool valid);   // stmpc_nstep_kernels.hpp
+__device__ __forceinline__ void nstep_gather_body(const DdpgDev &L, int B, float *out, long long fill, long long upd);  // stmpc_nstep_kernels.hpp
 
 // ---- replay ---------------------------------------------------------------------------------------------------------------------------------
 // (k_dqn_push of stmpc_dqn_kernels.hpp is a sibling of ddpg_push_body with an int32 action column and no time feature: a fix here belongs there too)
@@ -101,6 +108,7 @@ __device__ __forceinline__ void ddpg_push_body(const DdpgDev &L, int N, const fl
                                                const double *__restrict__ reward, const unsigned char *__restrict__ term, const unsigned char *__restrict__ trunc) {
     const long long cursor = L.cnt[DG_CURSOR], fill = L.cnt[DG_FILL], frames = L.cnt[DG_FRAMES];
     const int ns = L.n_obs + 1;
+    const float done_v = L.n_step > 1 ? 1.f : 0.f;                  // what a done row's DG_DONE column gets (hoisted: one test per launch, not per column)
     for (long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x; x < (long long)N * DG_ROW; x += (long long)gridDim.x * blockDim.x) {
         const int e = (int)(x / DG_ROW), c = (int)(x % DG_ROW);
         const bool done = term[e] || trunc[e];
@@ -112,6 +120,7 @@ __device__ __forceinline__ void ddpg_push_body(const DdpgDev &L, int N, const fl
         else if (c == 32 + L.n_obs) v = L.time_scale * (float)((done || !next_ticks) ? ticks[e] + 1 : next_ticks[e]);
         else if (c == DG_R) v = (float)reward[e];
         else if (c == DG_MASK) v = term[e] ? 0.f : 1.f;
+        else if (c == DG_DONE) v = done ? done_v : 0.f;
         L.ring[(size_t)((cursor + e) % L.capacity) * DG_ROW + c] = v;
     }
     __syncthreads();
@@ -137,6 +146,7 @@ __global__ void __launch_bounds__(256) k_replay_push(DdpgDev L, int N, const flo
 __global__ void k_replay_gather(DdpgDev L, int B, float *out) {
     const long long fill = L.cnt[DG_FILL], upd = L.cnt[DG_UPDATES];
     if (fill < 1) return;
+    if (L.n_step > 1) { nstep_gather_body(L, B, out, fill, upd); return; }
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < B * DG_ROW; x += gridDim.x * blockDim.x) {
         const int r = x / DG_ROW, c = x % DG_ROW;
         const long long idx = dg_row_index(L, upd, fill, r);
@@ -228,15 +238,24 @@ __device__ __forceinline__ bool ddpg_gate(const DdpgDev &L, int gate) {
 
 // ---- critic pass ------------------------------------------------------------------------------------------------------------------------------
 // (its stages are functions of their own because the TD3 critic pass of stmpc_td3_kernels.hpp is made of the same ones)
-// gather: 32 lanes per row; X = (s, a), Xn = s', sc = (reward, mask)
+// gather: 32 lanes per row; X = (s, a), Xn = s', sc = (reward, mask); n_step > 1: s' and the mask of the window's last row, sc = (R, mask, gamma^m)
+// (NS: the n-step instance.  The passes that form a target are compiled twice and entered through ONE test of L.n_step, so that the one-step
+// instance is the one-step learner's own instruction stream)
+template <bool NS>
 __device__ __forceinline__ void ddpg_gather_tile(const DdpgDev &L, const DdpgTile &T, int r0, int B, long long fill, long long upd) {
     const int row = threadIdx.x >> 5, c = threadIdx.x & 31;
     const bool valid = r0 + row < B;
     const long long idx = valid ? dg_row_index(L, upd, fill, r0 + row) : 0;
     const float *src = L.ring + (size_t)idx * DG_ROW;
+    if (NS) { nstep_gather_tile(L, T.X, T.Xn, T.sc, idx, valid); return; }
     T.X[row * AT_KIN + c] = valid ? src[c] : 0.f;
     T.Xn[row * AT_KIN + c] = valid ? src[32 + c] : 0.f;
     if (c < 2) T.sc[row * 4 + c] = valid ? src[DG_R + c] : 0.f;
+}
+// the target's discount of this thread's row: gamma, or gamma^m of the row's window (ddpg_gather_tile left it in sc; read before dz takes its place)
+template <bool NS>
+__device__ __forceinline__ float ddpg_discount(const DdpgDev &L, const DdpgTile &T) {
+    return NS ? T.sc[(threadIdx.x >> 5) * 4 + 2] : L.gamma;
 }
 // the target networks on Xn: the output of `net`'s target (pre-tanh for the actor, Q for a critic), in every lane of the row; the caller's barrier comes before H1 / H2 are written again
 __device__ __forceinline__ float ddpg_target_out(const DdpgDev &L, const DdpgNet &net, const DdpgTile &T) {
@@ -283,12 +302,13 @@ __device__ __forceinline__ void ddpg_critic_online(const DdpgDev &L, const DdpgT
     __syncthreads();
     ddpg_store_tile(T.H1, T.h1_ld, L.aD1 + (size_t)r0 * L.h1p, L.h1p);
 }
-__device__ __forceinline__ void ddpg_critic_fwd_body(const DdpgDev &L, int B, int gate, unsigned char *dg_smem) {
+template <bool NS>
+__device__ __forceinline__ void ddpg_critic_fwd_pass(const DdpgDev &L, int B, int gate, unsigned char *dg_smem) {
     if (!ddpg_gate(L, gate)) return;
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, L.h2p);
     const int tid = threadIdx.x, r0 = blockIdx.x * AT_TM, ns = L.n_obs + 1;
     const int row = tid >> 5, part = tid & 31;
-    ddpg_gather_tile(L, T, r0, B, L.cnt[DG_FILL], L.cnt[DG_UPDATES]);
+    ddpg_gather_tile<NS>(L, T, r0, B, L.cnt[DG_FILL], L.cnt[DG_UPDATES]);
     __syncthreads();
     // a' = pi_target(s')
     const float z = ddpg_target_out(L, L.pi, T);
@@ -296,10 +316,14 @@ __device__ __forceinline__ void ddpg_critic_fwd_body(const DdpgDev &L, int B, in
     __syncthreads();
     // Q_target(s', a')
     const float qn = ddpg_target_out(L, L.q, T);
-    const float y = T.sc[row * 4 + 0] + (L.gamma * T.sc[row * 4 + 1]) * qn;
+    const float y = T.sc[row * 4 + 0] + (ddpg_discount<NS>(L, T) * T.sc[row * 4 + 1]) * qn;
     __syncthreads();
     // Q(s, a)
     ddpg_critic_online(L, T, r0, B, y);
+}
+__device__ __forceinline__ void ddpg_critic_fwd_body(const DdpgDev &L, int B, int gate, unsigned char *dg_smem) {
+    if (L.n_step > 1) ddpg_critic_fwd_pass<true>(L, B, gate, dg_smem);
+    else ddpg_critic_fwd_pass<false>(L, B, gate, dg_smem);
 }
 __global__ void __launch_bounds__(AT_THREADS) k_ddpg_critic_fwd(DdpgDev L, int B, int gate) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
@@ -558,3 +582,4 @@ __global__ void __launch_bounds__(AT_THREADS) k_ddpg_act(DdpgDev L, int N, const
 }  // namespace stmpc
 
 #include "stmpc_per_kernels.hpp"
+#include "stmpc_nstep_kernels.hpp"

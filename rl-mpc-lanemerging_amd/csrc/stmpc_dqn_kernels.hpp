@@ -47,6 +47,7 @@ __device__ __forceinline__ void dqn_push_body(const DqnDev &D, int N, const floa
                                               const unsigned char *__restrict__ term, const unsigned char *__restrict__ trunc) {
     const DdpgDev &L = D.base;
     const long long cursor = L.cnt[DG_CURSOR], fill = L.cnt[DG_FILL], frames = L.cnt[DG_FRAMES];
+    const float done_v = L.n_step > 1 ? 1.f : 0.f;                  // (ddpg_push_body's)
     for (long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x; x < (long long)N * DG_ROW; x += (long long)gridDim.x * blockDim.x) {
         const int e = (int)(x / DG_ROW), c = (int)(x % DG_ROW);
         const bool done = term[e] || trunc[e];
@@ -55,6 +56,7 @@ __device__ __forceinline__ void dqn_push_body(const DqnDev &D, int N, const floa
         else if (c >= 32 && c < 32 + L.n_obs) v = (done && final_obs ? final_obs : next_obs)[(size_t)e * obs_stride + (c - 32)];
         else if (c == DG_R) v = (float)reward[e];
         else if (c == DG_MASK) v = term[e] ? 0.f : 1.f;
+        else if (c == DG_DONE) v = done ? done_v : 0.f;
         else if (c == DQ_ACTION) { const int a = action[e]; v = (float)(a < 0 ? 0 : (a >= D.A ? D.A - 1 : a)); }     // (the env latches an index out of range; the ring stays in range)
         L.ring[(size_t)((cursor + e) % L.capacity) * DG_ROW + c] = v;
     }
@@ -133,7 +135,9 @@ __device__ __forceinline__ int dqn_argmax(const float *q, int A, float &best) {
 
 // ---- forward / backward -------------------------------------------------------------------------------------------------------------------------
 // dbg (may be null) float32 [B][4]: a* (plain DQN: the maximum's index), the target net's Q there, y, Q(s, a)
-__device__ __forceinline__ void dqn_fwd_body(const DqnDev &D, int B, int gate, float *__restrict__ dbg, unsigned char *dg_smem) {
+// (NS: the n-step instance, as ddpg_critic_fwd_pass's)
+template <bool NS>
+__device__ __forceinline__ void dqn_fwd_pass(const DqnDev &D, int B, int gate, float *__restrict__ dbg, unsigned char *dg_smem) {
     const DdpgDev &L = D.base;
     if (!ddpg_gate(L, gate)) return;
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, D.Ap);
@@ -144,9 +148,12 @@ __device__ __forceinline__ void dqn_fwd_body(const DqnDev &D, int B, int gate, f
     {   // gather: X = s, Xn = s' (columns >= n_obs are zero in the ring), sc = (reward, mask)
         const long long idx = valid ? dg_row_index(L, upd, fill, r0 + row) : 0;
         const float *src = L.ring + (size_t)idx * DG_ROW;
-        T.X[row * AT_KIN + part] = valid ? src[part] : 0.f;
-        T.Xn[row * AT_KIN + part] = valid ? src[32 + part] : 0.f;
-        if (part < 2) T.sc[row * 4 + part] = valid ? src[DG_R + part] : 0.f;
+        if (NS) nstep_gather_tile(L, T.X, T.Xn, T.sc, idx, valid);      // s' and the mask of the window's last row, sc = (R, mask, gamma^m)
+        else {
+            T.X[row * AT_KIN + part] = valid ? src[part] : 0.f;
+            T.Xn[row * AT_KIN + part] = valid ? src[32 + part] : 0.f;
+            if (part < 2) T.sc[row * 4 + part] = valid ? src[DG_R + part] : 0.f;
+        }
         act = valid ? (int)src[DQ_ACTION] : 0;
     }
     __syncthreads();
@@ -160,7 +167,7 @@ __device__ __forceinline__ void dqn_fwd_body(const DqnDev &D, int B, int gate, f
     dqn_q(D, T, T.Xn, true);
     if (D.dbl) qsel = T.H2[(size_t)row * T.h2_ld + astar];
     else astar = dqn_argmax(T.H2 + (size_t)row * T.h2_ld, D.A, qsel);
-    float g = L.gamma * qsel;
+    float g = ddpg_discount<NS>(L, T) * qsel;
     if (D.clip) g = g < D.clip_min ? D.clip_min : (g > D.clip_max ? D.clip_max : g);
     const float y = T.sc[row * 4 + 1] != 0.f ? T.sc[row * 4 + 0] + g : T.sc[row * 4 + 0];      // a terminated row is its reward alone (next_state is None), whatever g is
     __syncthreads();
@@ -186,6 +193,10 @@ __device__ __forceinline__ void dqn_fwd_body(const DqnDev &D, int B, int gate, f
     const float *w1a = L.q.w + dg_o_w1(L.h1p) + (size_t)act * L.h1p;
     for (int k = part; k < L.h1p; k += 32)
         L.aD1[(size_t)(r0 + row) * L.h1p + k] = T.H1[(size_t)row * T.h1_ld + k] > 0.f ? dz * w1a[k] : 0.f;
+}
+__device__ __forceinline__ void dqn_fwd_body(const DqnDev &D, int B, int gate, float *__restrict__ dbg, unsigned char *dg_smem) {
+    if (D.base.n_step > 1) dqn_fwd_pass<true>(D, B, gate, dbg, dg_smem);
+    else dqn_fwd_pass<false>(D, B, gate, dbg, dg_smem);
 }
 __global__ void __launch_bounds__(AT_THREADS) k_dqn_fwd(DqnDev D, int B, int gate, float *__restrict__ dbg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];

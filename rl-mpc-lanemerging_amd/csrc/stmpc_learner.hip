@@ -118,6 +118,43 @@ struct Replay {
     }
 };
 
+// multi-step returns: the checks of a stmpc_nstep_cfg against the store it goes onto (an empty ring; synchronises), then the two fields into dev
+int nstep_attach(const Replay &rp, DdpgDev &dev, const stmpc_nstep_cfg *g) {
+    if (g->n_step < 1 || g->n_step > STMPC_NSTEP_MAX) return fail(STMPC_EINVAL, "n_step must be in 1 ... " + std::to_string(STMPC_NSTEP_MAX));
+    if (g->n_step > 1 && (g->rows_per_push < 1 || (long long)g->n_step * g->rows_per_push > rp.capacity))
+        return fail(STMPC_EINVAL, "n_step > 1 needs rows_per_push >= 1 and n_step * rows_per_push <= capacity (" + std::to_string(g->n_step) + " * " +
+                                      std::to_string(g->rows_per_push) + " against " + std::to_string(rp.capacity) + ")");
+    long long cn[DG_NCNT];
+    TRY(read_back(rp.device, cn, rp.cnt.p, sizeof cn));
+    if (cn[DG_FILL] != 0 || cn[DG_CURSOR] != 0) return fail(STMPC_EINVAL, "n_step can be set on an empty ring only (fill is " + std::to_string(cn[DG_FILL]) + ")");
+    dev.n_step = g->n_step; dev.rows_push = g->n_step > 1 ? g->rows_per_push : 0;
+    return STMPC_OK;
+}
+// a push of N rows onto a learner with n_step > 1: the ring's successor rule (stmpc_nstep_kernels.hpp) needs every push to have rows_push rows
+int nstep_check_push(const DdpgDev &dev, int N) {
+    if (dev.n_step > 1 && N != dev.rows_push)
+        return fail(STMPC_EINVAL, "this learner forms " + std::to_string(dev.n_step) + "-step returns from pushes of " + std::to_string(dev.rows_push) + " rows: a push of " +
+                                      std::to_string(N) + " rows is refused");
+    return STMPC_OK;
+}
+// the windows of n_idx ring rows of a store (HOST idx, HOST out [n_idx][4]); synchronises
+int nstep_window_read(const Replay &rp, const DdpgDev &dev, const int64_t *idx, int n_idx, double *out) {
+    if (!idx || !out || n_idx < 0) return fail(STMPC_EINVAL, "NULL argument or n_idx negative");
+    long long cn[DG_NCNT];
+    TRY(read_back(rp.device, cn, rp.cnt.p, sizeof cn));
+    for (int i = 0; i < n_idx; ++i)
+        if (idx[i] < 0 || idx[i] >= cn[DG_FILL]) return fail(STMPC_EINVAL, "index " + std::to_string(i) + " is not a filled ring row (fill is " + std::to_string(cn[DG_FILL]) + ")");
+    if (n_idx == 0) return STMPC_OK;
+    static_assert(sizeof(long long) == sizeof(int64_t), "ring indices travel as int64");
+    DevBuf d_idx, d_out;
+    TRY(upload(d_idx, (const long long *)idx, (size_t)n_idx));
+    TRY(d_out.ensure((size_t)n_idx * 4 * sizeof(double)));
+    const int blocks = (n_idx + 7) / 8 < 256 ? (n_idx + 7) / 8 : 256;      // (two rows per wave, four waves per block)
+    hipLaunchKernelGGL(k_nstep_window, dim3(blocks), dim3(256), 0, (hipStream_t)0, dev, (const long long *)d_idx.as<long long>(), n_idx, d_out.as<double>());
+    HIPCHK(hipGetLastError());
+    return read_back(rp.device, out, d_out.p, (size_t)n_idx * 4 * sizeof(double));
+}
+
 // prioritised replay: the sampling step in front of a pass that gathers (nothing on a store that samples uniformly); d: the device struct wired to rp
 void per_launch_sample(const Replay &rp, const DdpgDev &d, int gate, hipStream_t st) {
     if (rp.per) hipLaunchKernelGGL(k_per_sample, dim3(1), dim3(PER_THREADS), 0, st, d, rp.batch, rp.Bp, gate);
@@ -365,6 +402,7 @@ int stmpc_ddpg_push_device(stmpc_ddpg *l, int N, const float *d_obs, const float
     if (!l) return fail(STMPC_EINVAL, "learner is NULL");
     if (N < 0 || N > l->cfg.capacity || obs_stride < l->cfg.n_obs) return fail(STMPC_EINVAL, "N exceeds the replay capacity, or obs_stride is shorter than the observation");
     if (N == 0) return STMPC_OK;
+    TRY(nstep_check_push(l->dev, N));
     if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(l->rp.device));
     hipLaunchKernelGGL(k_replay_push, dim3(push_blocks(N)), dim3(256), 0, (hipStream_t)stream, l->dev, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks,
@@ -627,6 +665,19 @@ int stmpc_per_enable(stmpc_ddpg *l, const stmpc_per_cfg *g) {
     return per_attach(l->rp, l->dev, l->td3_owner, g);
 }
 
+int stmpc_nstep_enable_ddpg(stmpc_ddpg *l, const stmpc_nstep_cfg *g) {
+    if (!l || !g) return fail(STMPC_EINVAL, "NULL argument");
+    if (l->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: n_step is set on the population (stmpc_pop_nstep_enable_ddpg / _td3)");
+    TRY(nstep_attach(l->rp, l->dev, g));
+    ddpg_refresh(l);
+    return STMPC_OK;
+}
+
+int stmpc_nstep_window_ddpg(stmpc_ddpg *l, const int64_t *idx, int n_idx, double *out) {
+    if (!l) return fail(STMPC_EINVAL, "NULL argument");
+    return nstep_window_read(l->rp, l->dev, idx, n_idx, out);
+}
+
 int stmpc_per_tree_read(stmpc_ddpg *l, int64_t first, int64_t count, double *nodes) {
     if (!l) return fail(STMPC_EINVAL, "NULL argument");
     return l->rp.read_tree(first, count, nodes);
@@ -736,6 +787,25 @@ int pop_check_rows(const PopCore &c, int n_per_member, int obs_stride) {
         return fail(STMPC_EINVAL, "n_per_member must be in 1 ... capacity, and obs_stride at least the observation's width");
     return STMPC_OK;
 }
+// ... and a pushing entry of the members' n-step windows
+int pop_check_push(const PopCore &c, int n_per_member) {
+    for (const PopSlot &s : c.slots) TRY(nstep_check_push(*s.dev, n_per_member));
+    return STMPC_OK;
+}
+// stmpc_nstep_enable_* per member -- every check before any member changes --, then the device tables anew (upload_tables)
+template <class F> int pop_nstep_enable(PopCore &c, const stmpc_nstep_cfg *cfgs, int P, F upload_tables) {
+    if (!cfgs) return fail(STMPC_EINVAL, "NULL argument");
+    if (P != c.P()) return fail(STMPC_EINVAL, "cfgs has " + std::to_string(P) + " entries, the population " + std::to_string(c.P()) + " members");
+    std::vector<DdpgDev> probe;
+    for (int m = 0; m < P; ++m) { probe.push_back(*c.slots[m].dev); TRY(nstep_attach(*c.slots[m].rp, probe[m], cfgs + m)); }
+    for (int m = 0; m < P; ++m) {
+        c.slots[m].dev->n_step = probe[m].n_step; c.slots[m].dev->rows_push = probe[m].rows_push;
+        if (c.slots[m].td3_owner) td3_refresh(c.slots[m].td3_owner);
+    }
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(hipDeviceSynchronize());
+    return upload_tables();
+}
 // acting and pushing of the members: the DDPG population's own, and a TD3 population's on its members' bases
 int pop_act(const PopCore &c, int n_per_member, const float *d_obs, int obs_stride, const int32_t *d_ticks, int noise, double *d_action, uint32_t *d_debug, void *stream) {
     TRY(pop_check_rows(c, n_per_member, obs_stride));
@@ -749,6 +819,7 @@ int pop_act(const PopCore &c, int n_per_member, const float *d_obs, int obs_stri
 int pop_push(const PopCore &c, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_ticks,
              const int32_t *d_next_ticks, const double *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
     TRY(pop_check_rows(c, n_per_member, obs_stride));
+    TRY(pop_check_push(c, n_per_member));
     if (!d_obs || !d_next_obs || !d_ticks || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(c.device));
     hipLaunchKernelGGL(k_replay_push_pop, dim3(push_blocks(n_per_member), c.P()), dim3(256), 0, (hipStream_t)stream, c.dev(), n_per_member, d_obs, d_next_obs, d_final_obs,
@@ -855,6 +926,11 @@ int stmpc_ddpg_pop_stats_device(stmpc_ddpg_pop *p, double *d_out, void *stream) 
     return STMPC_OK;
 }
 
+int stmpc_pop_nstep_enable_ddpg(stmpc_ddpg_pop *p, const stmpc_nstep_cfg *cfgs, int P) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return pop_nstep_enable(p->core, cfgs, P, [&] { return pop_upload(p->core); });
+}
+
 int stmpc_pop_per_enable_ddpg(stmpc_ddpg_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
     return pop_per_enable(p->core, cfgs, enabled, P, [&] { return pop_upload(p->core); });
@@ -934,6 +1010,11 @@ int stmpc_pop_td3_stats_device(stmpc_td3_pop *p, double *d_out, void *stream) {
     hipLaunchKernelGGL(k_td3_stats_pop, dim3(1, 1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->dev(), p->core.batch, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
+}
+
+int stmpc_pop_nstep_enable_td3(stmpc_td3_pop *p, const stmpc_nstep_cfg *cfgs, int P) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return pop_nstep_enable(p->core, cfgs, P, [&] { return td3_pop_upload(p); });
 }
 
 int stmpc_pop_per_enable_td3(stmpc_td3_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
@@ -1127,6 +1208,7 @@ int stmpc_dqn_push_device(stmpc_dqn *t, int N, const float *d_obs, const float *
     if (!t) return fail(STMPC_EINVAL, "learner is NULL");
     if (N < 0 || N > t->cfg.capacity || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N exceeds the replay capacity, or obs_stride is shorter than the observation");
     if (N == 0) return STMPC_OK;
+    TRY(nstep_check_push(t->dev.base, N));
     if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(t->rp.device));
     hipLaunchKernelGGL(k_dqn_push, dim3(push_blocks(N)), dim3(256), 0, (hipStream_t)stream, t->dev, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward,
@@ -1202,6 +1284,17 @@ int stmpc_dqn_per_enable(stmpc_dqn *t, const stmpc_per_cfg *g) {
     if (t->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: prioritised replay is enabled on the population (stmpc_pop_dqn_per_enable)");
     TRY(t->rp.check_empty());
     return per_attach(t->rp, t->dev.base, nullptr, g);               // (the tree, idx, aw, atd and the constants into dev.base)
+}
+
+int stmpc_nstep_enable_dqn(stmpc_dqn *t, const stmpc_nstep_cfg *g) {
+    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
+    if (t->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: n_step is set on the population (stmpc_pop_nstep_enable_dqn)");
+    return nstep_attach(t->rp, t->dev.base, g);
+}
+
+int stmpc_nstep_window_dqn(stmpc_dqn *t, const int64_t *idx, int n_idx, double *out) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return nstep_window_read(t->rp, t->dev.base, idx, n_idx, out);
 }
 
 int stmpc_dqn_per_tree_read(stmpc_dqn *t, int64_t first, int64_t count, double *nodes) {
@@ -1318,6 +1411,7 @@ int stmpc_pop_dqn_push_device(stmpc_dqn_pop *p, int n_per_member, const float *d
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
     const PopCore &c = p->core;
     TRY(pop_check_rows(c, n_per_member, obs_stride));
+    TRY(pop_check_push(c, n_per_member));
     if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(c.device));
     hipLaunchKernelGGL(k_dqn_push_pop, dim3(push_blocks(n_per_member), c.P()), dim3(256), 0, (hipStream_t)stream, p->dev(), n_per_member, d_obs, d_next_obs, d_final_obs,
@@ -1358,6 +1452,11 @@ int stmpc_pop_dqn_stats_device(stmpc_dqn_pop *p, double *d_out, void *stream) {
 int stmpc_pop_dqn_per_enable(stmpc_dqn_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
     return pop_per_enable(p->core, cfgs, enabled, P, [&] { return dqn_pop_upload(p); });
+}
+
+int stmpc_pop_nstep_enable_dqn(stmpc_dqn_pop *p, const stmpc_nstep_cfg *cfgs, int P) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return pop_nstep_enable(p->core, cfgs, P, [&] { return dqn_pop_upload(p); });
 }
 
 int stmpc_pop_dqn_replay_read(stmpc_dqn *t, int64_t first, int64_t count, float *rows) {

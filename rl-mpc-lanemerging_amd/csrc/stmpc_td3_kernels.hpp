@@ -43,14 +43,15 @@ __device__ __forceinline__ float td3_smoothing(const Td3Dev &T3, unsigned long l
 }
 
 // dbg (may be null) float32 [B][5]: eps, a', Qt1, Qt2, y of the minibatch; with it the pass ends there and writes nothing else
-__device__ __forceinline__ void td3_critic_fwd_body(const Td3Dev &T3, int B, int gate, float *__restrict__ dbg, unsigned char *dg_smem) {
+template <bool NS>
+__device__ __forceinline__ void td3_critic_fwd_pass(const Td3Dev &T3, int B, int gate, float *__restrict__ dbg, unsigned char *dg_smem) {
     const DdpgDev &L = T3.v[blockIdx.y];
     if (!ddpg_gate(L, gate)) return;
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, L.h2p);
     const int tid = threadIdx.x, r0 = blockIdx.x * AT_TM, ns = L.n_obs + 1;
     const int row = tid >> 5, part = tid & 31;
     const long long upd = L.cnt[DG_UPDATES];
-    ddpg_gather_tile(L, T, r0, B, L.cnt[DG_FILL], upd);
+    ddpg_gather_tile<NS>(L, T, r0, B, L.cnt[DG_FILL], upd);
     __syncthreads();
     // a' = clip(pi_target(s') + eps, Box)
     const float z = ddpg_target_out(L, L.pi, T);
@@ -65,7 +66,7 @@ __device__ __forceinline__ void td3_critic_fwd_body(const Td3Dev &T3, int B, int
     const float q1 = ddpg_target_out(L, T3.v[0].q, T);
     __syncthreads();
     const float q2 = ddpg_target_out(L, T3.v[1].q, T);
-    const float y = T.sc[row * 4 + 0] + (L.gamma * T.sc[row * 4 + 1]) * (q2 < q1 ? q2 : q1);
+    const float y = T.sc[row * 4 + 0] + (ddpg_discount<NS>(L, T) * T.sc[row * 4 + 1]) * (q2 < q1 ? q2 : q1);
     if (dbg) {
         if (blockIdx.y == 0 && part == 0 && r0 + row < B) {
             float *o = dbg + 5 * (size_t)(r0 + row);
@@ -75,6 +76,11 @@ __device__ __forceinline__ void td3_critic_fwd_body(const Td3Dev &T3, int B, int
     }
     __syncthreads();
     ddpg_critic_online(L, T, r0, B, y);
+}
+// (ddpg_critic_fwd_body's two instances)
+__device__ __forceinline__ void td3_critic_fwd_body(const Td3Dev &T3, int B, int gate, float *__restrict__ dbg, unsigned char *dg_smem) {
+    if (T3.v[0].n_step > 1) td3_critic_fwd_pass<true>(T3, B, gate, dbg, dg_smem);
+    else td3_critic_fwd_pass<false>(T3, B, gate, dbg, dg_smem);
 }
 __global__ void __launch_bounds__(AT_THREADS) k_td3_critic_fwd(Td3Dev T3, int B, int gate, float *__restrict__ dbg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];

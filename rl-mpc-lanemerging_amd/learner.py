@@ -73,15 +73,34 @@ class PERConfig:
         return _capi.PERCfg(alpha=self.alpha, beta=self.beta, min_priority=self.min_priority, max_priority=self.max_priority)
 
 
+def _check_n_step(n_step):
+    n = int(n_step)
+    if not 1 <= n <= _capi.NSTEP_MAX:
+        raise ValueError("n_step must be in 1 ... %d, not %r" % (_capi.NSTEP_MAX, n_step))
+    return n
+
+
+def nstep_to_c(cfg, rows_per_push):
+    """``stmpc_nstep_cfg`` of a learner's cfg and the rows N of every push; with ``cfg.n_step`` > 1 the window of n pushes must fit the ring."""
+    N = int(rows_per_push or 0)
+    if cfg.n_step > 1 and N < 1:
+        raise ValueError("n_step = %d needs the rows of every push: an env, a population's n_per_member, or rows_per_push=" % cfg.n_step)
+    if cfg.n_step > 1 and cfg.n_step * N > cfg.capacity:
+        raise ValueError("n_step * rows_per_push = %d * %d does not fit the replay's capacity %d" % (cfg.n_step, N, cfg.capacity))
+    return _capi.NStepCfg(n_step=cfg.n_step, rows_per_push=N if cfg.n_step > 1 else 0)
+
+
 class DDPGConfig:
     """The constants of the update; defaults are the ``all`` ddpg preset's as its documentation gives them (``lr``: Settings.LEARNING_RATE).
     ``per``: a ``PERConfig`` for prioritised replay (None: uniform minibatches); it is not part of ``to_c`` -- the learner enables it on its handle."""
 
     def __init__(self, n_obs=20, h1=400, h2=300, batch=100, capacity=1000000, replay_start=5000, gamma=0.99, tau=0.005, lr_q=None, lr_pi=None,
-                 beta1=0.9, beta2=0.999, eps=1e-8, time_scale=0.001, tanh_scale=None, tanh_mean=None, noise=0.1, action_low=None, action_high=None, per=None):
+                 beta1=0.9, beta2=0.999, eps=1e-8, time_scale=0.001, tanh_scale=None, tanh_mean=None, noise=0.1, action_low=None, action_high=None, per=None,
+                 n_step=1):
         if per is not None and not isinstance(per, PERConfig):
             raise ValueError("per must be a PERConfig or None")
         self.per = per
+        self.n_step = _check_n_step(n_step)                         # multi-step returns (``nstep_window_host``); like ``per`` it travels beside ``to_c``: ``to_c_nstep``
         lo = float(Settings.MINIMUM_NEGATIVE_JERK) if action_low is None else float(action_low)
         hi = float(Settings.MAXIMUM_POSITIVE_JERK) if action_high is None else float(action_high)
         self.n_obs, self.h1, self.h2, self.batch, self.capacity, self.replay_start = int(n_obs), int(h1), int(h2), int(batch), int(capacity), int(replay_start)
@@ -98,6 +117,9 @@ class DDPGConfig:
                              seed=int(seed) & _M64, gamma=self.gamma, tau=self.tau, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
                              time_scale=self.time_scale, tanh_scale=self.tanh_scale, tanh_mean=self.tanh_mean, noise_std=self.noise_std,
                              action_low=self.action_low, action_high=self.action_high)
+
+    def to_c_nstep(self, rows_per_push):
+        return nstep_to_c(self, rows_per_push)
 
 
 # ---- the generator (host twins of dg_hash / stmpc_ddpg_sample_index / stmpc_ddpg_noise) ------------------------------------------------------
@@ -188,12 +210,13 @@ def _polyak(P, name, cfg):
         P[name + "_target"][k] = (1 - cfg.tau) * P[name + "_target"][k] + cfg.tau * P[name][k]
 
 
-def update_host(params, batch, cfg, dtype="float64", lr_q=None, lr_pi=None, grads_only=False, weights=None):
+def update_host(params, batch, cfg, dtype="float64", lr_q=None, lr_pi=None, grads_only=False, weights=None, disc=None):
     """One update (steps 1-4 of the module text) in torch with autograd, every tensor in ``dtype`` ("float64" or "float32").
     ``params``: as ``new_params`` / ``DDPGLearner.state_dict()["params"]``; returns the new one (numpy arrays of ``dtype``) and a dict with
     ``critic_loss``, ``mean_q``, ``grad_critic``, ``grad_actor``.  ``grads_only``: nothing is applied and BOTH gradients are taken against the
     current critic (``stmpc_ddpg_grads_device``'s mode).  ``weights``: prioritised replay's importance weight per minibatch row, which multiplies
-    that row's term of the critic's loss (None: none; ``critic_loss`` stays the unweighted mean, as the device reports it)."""
+    that row's term of the critic's loss (None: none; ``critic_loss`` stays the unweighted mean, as the device reports it).  ``disc``: the
+    target's discount per minibatch row in ``cfg.gamma``'s place (``nstep_batch_host``'s gamma^m; None: ``cfg.gamma``)."""
     import torch
     td = getattr(torch, dtype)
     T = lambda a: torch.tensor(np.asarray(a), dtype=td)
@@ -209,7 +232,7 @@ def update_host(params, batch, cfg, dtype="float64", lr_q=None, lr_pi=None, grad
 
     with torch.no_grad():
         a2 = torch.tanh(_mlp(P["actor_target"], s2)) * scale + mean
-        y = r + cfg.gamma * mask * _mlp(P["critic_target"], torch.cat([s2, a2[:, None]], 1))
+        y = r + (cfg.gamma if disc is None else T(disc)) * mask * _mlp(P["critic_target"], torch.cat([s2, a2[:, None]], 1))
     crit = {k: P["critic"][k].clone().requires_grad_(True) for k in TENSORS}
     q = _mlp(crit, torch.cat([s, a[:, None]], 1))
     loss = ((q - y) ** 2).mean()
@@ -286,14 +309,14 @@ def new_params_td3(actor_net, critic_net, critic2_net):
     return p
 
 
-def update_host_td3(params, batch, cfg, dtype="float64", eps=None, lr_q=None, lr_pi=None, grads_only=False, weights=None):
+def update_host_td3(params, batch, cfg, dtype="float64", eps=None, lr_q=None, lr_pi=None, grads_only=False, weights=None, disc=None):
     """One TD3 update in torch with autograd, every tensor in ``dtype``: ``update_host`` with the smoothed, clipped target action, the minimum of
     both target critics, both critics stepped, and -- only if (updates + 1) % cfg.policy_delay == 0 -- the actor stepped against critic 1 and all
     three targets moved.  ``eps``: the smoothing noise per minibatch row (None: zeros); the twin is handed it, it does not draw.
     ``params``: as ``new_params_td3`` / ``TD3Learner.state_dict()["params"]``.  ``info`` carries ``critic_loss`` / ``critic2_loss``, ``mean_q`` /
     ``mean_q2``, ``grad_critic`` / ``grad_critic2`` / ``grad_actor`` (None when the actor did not step) and ``targets`` [B][4] = a', Qt1, Qt2, y.
     ``grads_only``: nothing is applied and all three gradients are taken against the current critics (``stmpc_td3_grads_device``'s mode).
-    ``weights``: as ``update_host``'s, on both critics' losses."""
+    ``weights``: as ``update_host``'s, on both critics' losses; ``disc``: as ``update_host``'s."""
     import torch
     td = getattr(torch, dtype)
     T = lambda a: torch.tensor(np.asarray(a), dtype=td)
@@ -309,7 +332,7 @@ def update_host_td3(params, batch, cfg, dtype="float64", eps=None, lr_q=None, lr
         a2 = torch.clamp((torch.tanh(_mlp(P["actor_target"], s2)) * scale + mean) + e, cfg.action_low, cfg.action_high)
         x2 = torch.cat([s2, a2[:, None]], 1)
         qt1, qt2 = _mlp(P["critic_target"], x2), _mlp(P["critic2_target"], x2)
-        y = r + cfg.gamma * mask * torch.minimum(qt1, qt2)
+        y = r + (cfg.gamma if disc is None else T(disc)) * mask * torch.minimum(qt1, qt2)
     info = {"targets": torch.stack([a2, qt1, qt2, y], 1).numpy(), "grad_actor": None}
     for name, tag in (("critic", ""), ("critic2", "2")):
         crit = {k: P[name][k].clone().requires_grad_(True) for k in TENSORS}
@@ -428,14 +451,71 @@ def per_weights_host(nodes, idx, fill, beta):
     return w.astype(np.float32)
 
 
+# ---- multi-step returns: host twins (stmpc_nstep_kernels.hpp) ------------------------------------------------------------------------------------
+def nstep_window_host(rows, i, cursor, fill, N, n, gamma):
+    """The window of ring row ``i`` as ``nstep_window`` of csrc/stmpc_nstep_kernels.hpp forms it, operation for operation: (R float32, disc
+    float32, the ring row of the window's last transition, m).  ``rows``: the whole ring [capacity][68] (column 67: done); ``cursor`` / ``fill``:
+    the ring's counters; ``N``: the rows of every push; ``n``: the window's length.  row_k = (i + k N) % capacity exists iff age(i) =
+    (cursor - 1 - i) mod capacity >= k N; the window ends with the first k at which row_k is done, k + 1 == n or row_{k+1} does not exist.
+    R and disc accumulate in float64 from float64(float32(gamma)) in k order and are rounded to float32 once."""
+    cap, i, N, n = len(rows), int(i), int(N), int(n)
+    if not 0 <= i < int(fill):
+        raise ValueError("row %d is not a filled ring row (fill is %d)" % (i, fill))
+    age = (int(cursor) - 1 - i) % cap
+    g = float(np.float32(gamma))
+    R, gk, k = 0.0, 1.0, 0
+    while True:
+        row = rows[(i + k * N) % cap]
+        term = gk * float(row[64])
+        R = term if k == 0 else R + term
+        gk = gk * g
+        if row[_capi.DONE_COL] != 0 or k + 1 == n or age < (k + 1) * N:
+            return np.float32(R), np.float32(gk), (i + k * N) % cap, k + 1
+        k += 1
+
+
+def nstep_batch_host(rows, idx, cursor, fill, N, n, gamma, n_obs, dqn=False):
+    """The minibatch dict ``update_host`` / ``update_host_td3`` (``dqn``: ``update_host_dqn`` / ``dqn_targets_host``) take for the ring rows ``idx``
+    under n-step returns: s and a of row i, s' and the mask of its window's last row, r = R, plus ``disc`` (gamma^m, for the twins' ``disc=``),
+    ``last`` and ``m``."""
+    rows = np.asarray(rows)
+    win = [nstep_window_host(rows, i, cursor, fill, N, n, gamma) for i in idx]
+    g = np.array(rows[np.asarray(idx, dtype=np.int64)])
+    last = np.array([w[2] for w in win], dtype=np.int64)
+    g[:, 32:64], g[:, 65], g[:, 64] = rows[last, 32:64], rows[last, 65], np.array([w[0] for w in win], dtype=np.float32)
+    b = dqn_batch_from_rows(g, n_obs) if dqn else batch_from_rows(g, n_obs)
+    b.update(disc=np.array([w[1] for w in win], dtype=np.float32), last=last, m=np.array([w[3] for w in win], dtype=np.int64), rows=g)
+    return b
+
+
 # ---- the learner -------------------------------------------------------------------------------------------------------------------------------
 class _Learner:
     """What ``DDPGLearner`` and ``DQNLearner`` share word for word: the handle's lifetime, the stream, the output tensor kept per n, the debug reads
     of the replay and the statistics, and ``state_dict`` / ``load_state_dict``.  A subclass names its binding's entries (``ctx.<_api>_<name>``, and
     ``ctx.<_per_api>_<name>`` for prioritised replay), its ``_slots`` and ``_flatten``, and reads one slot in ``_slot``."""
 
+    _owns_handle = True                                             # (False: a population's member, whose population sets up what it shares)
+
     def _call(self, name):
         return getattr(self.ctx, "%s_%s" % (self._api, name))
+
+    def _enable_nstep(self, env, rows_per_push):
+        """``cfg.n_step`` onto the new handle (the ring is empty); ``self.rows_per_push``: the N every push must have when n_step > 1."""
+        owner = getattr(self, "_population", None)
+        self.rows_per_push = owner.n_per_member if owner is not None else (getattr(env, "n", None) if env is not None else rows_per_push)
+        if self._owns_handle and self.cfg.n_step > 1:
+            self.ctx.nstep_enable(self._api, self.handle, self.cfg.to_c_nstep(self.rows_per_push))
+
+    def nstep_window(self, idx):
+        """Debug: float64 [len(idx)][4] = R, disc, the ring row of the window's last transition, m for the filled ring rows ``idx``
+        (``nstep_window_host``'s four); synchronises."""
+        return self.ctx.nstep_window(self._api, self.handle, idx)
+
+    def _check_nstep(self, sd):
+        if "n_step" in sd and int(sd["n_step"]) != self.cfg.n_step:
+            raise ValueError("the state was saved with n_step = %d, this learner has n_step = %d: the rows' done column and the targets differ" % (int(sd["n_step"]), self.cfg.n_step))
+        if self.cfg.n_step > 1 and "rows_per_push" in sd and int(sd["rows_per_push"] or 0) != int(self.rows_per_push or 0):
+            raise ValueError("the state was saved with %r rows per push, this learner has %r" % (sd["rows_per_push"], self.rows_per_push))
 
     def __del__(self):
         if getattr(self, "handle", None) is not None:
@@ -482,14 +562,16 @@ class _Learner:
 
     def state_dict(self):
         """{"params": the slots (eight of DDPG, four of DQN) as dicts of numpy tensors + beta_pow + updates, "counters": int64 [8]}; the replay ring
-        is not part of it."""
+        is not part of it; ``n_step`` and ``rows_per_push`` say how its rows were written and are read."""
         cn, bp = self._call("get_state")(self.handle)
         params = {slot: self._slot(i) for i, slot in enumerate(self._slots)}
         params["beta_pow"], params["updates"] = bp, int(cn[2])
-        return {"params": params, "counters": cn}
+        return {"params": params, "counters": cn, "n_step": self.cfg.n_step, "rows_per_push": self.rows_per_push}
 
     def load_state_dict(self, sd):
-        """The inverse; ``counters`` None: only the update count and Adam's beta powers are set (the replay's cursor and fill stay)."""
+        """The inverse; ``counters`` None: only the update count and Adam's beta powers are set (the replay's cursor and fill stay).  A state
+        saved under another ``n_step`` is refused (one without the key is taken as it is)."""
+        self._check_nstep(sd)
         p = sd["params"]
         for i, slot in enumerate(self._slots):
             self._call("set_params")(self.handle, i, self._flatten(p[slot]))
@@ -504,11 +586,12 @@ class DDPGLearner(_Learner):
     """``env_or_dims``: a ``MergeVecEnv`` (continuous-jerk; its context, observation width and action Box are taken over) or the observation width.
     ``cfg``: ``DDPGConfig`` (None: the defaults); ``seed``: of the initialisation, the minibatch indices and the exploration noise;
     ``init``: None (torch's nn.Linear initialisation, last layers zero), the name of a shipped actor ("medium1": that actor, a fresh critic), or a
-    dict ``{"actor": net, "critic": net}`` of numpy tensors."""
+    dict ``{"actor": net, "critic": net}`` of numpy tensors.  ``rows_per_push``: with ``cfg.n_step`` > 1 and no env, the rows N every push
+    will have (an env's ``n`` otherwise); a push with another N is then refused."""
 
     _api, _per_api, _slots, _flatten = "ddpg", "per", _capi.DDPG_SLOTS, staticmethod(flatten)
 
-    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None):
+    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None, rows_per_push=None):
         import torch
         self.torch = torch
         env = None if isinstance(env_or_dims, int) else env_or_dims
@@ -522,6 +605,7 @@ class DDPGLearner(_Learner):
         self.seed = int(seed)
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.handle = self._make_handle()
+        self._enable_nstep(env, rows_per_push)
         if self.cfg.per is not None:                                # (a population member's handle refuses: the population enables its members)
             self.ctx.per_enable(self.handle, self.cfg.per.to_c())
         c = self.cfg
@@ -610,14 +694,14 @@ class TD3Learner(DDPGLearner):
     and a shielded env's ``policy=`` take a ``TD3Learner`` like any learner.  ``init``: as ``DDPGLearner``'s, or a triple (actor, critic, critic 2)
     of nets (critic 2 None, or no triple: a fresh draw from the next values of the same rng)."""
 
-    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None):
+    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None, rows_per_push=None):
         self._critic2_init = None
         if isinstance(init, (tuple, list)):
             a_net, q_net, self._critic2_init = init
             init = {"actor": a_net, "critic": q_net}
         if cfg is None:
             cfg = TD3Config(n_obs=env_or_dims if isinstance(env_or_dims, int) else env_or_dims.obs_dim)
-        super().__init__(env_or_dims, cfg, seed=seed, init=init, ctx=ctx)
+        super().__init__(env_or_dims, cfg, seed=seed, init=init, ctx=ctx, rows_per_push=rows_per_push)
         self._stats6 = self.torch.zeros(6, dtype=self.torch.float64, device=self.device)
 
     def _make_handle(self):
@@ -674,6 +758,7 @@ class TD3Learner(DDPGLearner):
         return sd
 
     def load_state_dict(self, sd):
+        self._check_nstep(sd)
         p = sd["params"]
         super().load_state_dict({"params": dict(p, beta_pow=p["beta_pow"][:4]), "counters": sd.get("counters")})
         for i, slot in enumerate(_capi.TD3_SLOTS):
@@ -693,6 +778,8 @@ def per_member(value, P, default=None):
 class _PopulationMember(DDPGLearner):
     """One member of a ``DDPGPopulation`` as a ``DDPGLearner``: the handle is borrowed from the population (``stmpc_ddpg_pop_member``), which
     outlives it; everything else -- the seeded initialisation included -- is the lone learner's code."""
+
+    _owns_handle = False
 
     def __init__(self, population, m, env, cfg, seed, init):
         self._population, self._borrowed = population, population.ctx.ddpg_pop_member(population.handle, m)
@@ -732,9 +819,13 @@ class DDPGPopulation:
     enables its members' trees in one call before anything is pushed.  ``self.per`` is the per-member list.  A prioritised member is
     bit-identical to ``DDPGLearner(cfg with per=...)`` on its slice, a uniform one to the member of a population without ``per``; one update is
     eight launches whatever P is (six when no member is prioritised).  ``member(m).priorities()`` / ``.last_sample()`` read member m's tree and
-    last minibatch (they raise on a uniform member)."""
+    last minibatch (they raise on a uniform member).
+
+    ``n_step`` is a member's cfg's like any other constant, so "which n" is a sweep: member m forms ``cfgs[m].n_step``-step returns from pushes
+    of ``n_per_member`` rows and stays bit-identical to the lone learner with that cfg; ``member(m).nstep_window(idx)`` reads its windows."""
 
     _api, _nstat = "ddpg_pop", 4                                    # the binding's entries (ctx.<_api>_create, ...) and the width of a stats row
+    _nstep_kind = "ddpg"                                            # which stmpc_pop_nstep_enable_* entry sets the members' n_step
     _cfg_type, _action_dtype = DDPGConfig, "float64"                # what a (cfg, P) pair holds, and the dtype of the tensor ``act`` returns
 
     def _call(self, name):
@@ -798,6 +889,8 @@ class DDPGPopulation:
         self.ctx = ctx if ctx is not None else env.ctx
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.handle = self._create_handle()
+        if any(c.n_step > 1 for c in self.cfgs):                    # (the rings are empty; member m forms cfgs[m].n_step-step returns from pushes of n_per_member rows)
+            self.ctx.pop_nstep_enable(self._nstep_kind, self.handle, [c.to_c_nstep(self.n_per_member) for c in self.cfgs])
         if any(g is not None for g in self.per):                    # (the rings are empty: nothing was pushed yet)
             self._call("per_enable")(self.handle, [g.to_c() if g is not None else None for g in self.per])
         self._members = [self._make_member(m, env, inits[m]) for m in range(P)]
@@ -868,6 +961,8 @@ class _TD3PopulationMember(TD3Learner):
     """One member of a ``TD3Population`` as a ``TD3Learner``: the TD3 handle is borrowed from the population (``stmpc_pop_td3_member``), which outlives
     it, and so is its base; everything else -- the seeded initialisation, critic 2's draw included -- is the lone learner's code."""
 
+    _owns_handle = False
+
     def __init__(self, population, m, env, cfg, seed, init):
         self._population, self._borrowed = population, population.ctx.td3_pop_member(population.handle, m)
         super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
@@ -900,6 +995,7 @@ class TD3Population(DDPGPopulation):
     the critic with the larger error, as ``TD3Learner``'s do."""
 
     _api, _nstat = "td3_pop", 6
+    _nstep_kind = "td3"
 
     def __init__(self, env, cfgs, seeds=None, init=None, ctx=None, per=None):
         if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], DDPGConfig):
@@ -942,10 +1038,11 @@ class DQNConfig:
     (USE_PRIORITIZED_ER), None: uniform minibatches."""
 
     def __init__(self, n_obs=20, n_actions=None, h1=256, batch=50, capacity=50000, replay_start=0, gamma=0.999, lr=2e-4, target_period=500, double=True,
-                 clip_targets=False, clip_min=-20.0, clip_max=10.0, beta1=0.9, beta2=0.999, eps=1e-8, per=None):
+                 clip_targets=False, clip_min=-20.0, clip_max=10.0, beta1=0.9, beta2=0.999, eps=1e-8, per=None, n_step=1):
         if per is not None and not isinstance(per, PERConfig):
             raise ValueError("per must be a PERConfig or None")
         self.per = per
+        self.n_step = _check_n_step(n_step)                         # multi-step returns; travels beside ``to_c``: ``to_c_nstep``
         self.n_obs, self.n_actions, self.h1, self.batch = int(n_obs), (None if n_actions is None else int(n_actions)), int(h1), int(batch)
         self.capacity, self.replay_start, self.target_period = int(capacity), int(replay_start), int(target_period)
         self.gamma, self.lr, self.beta1, self.beta2, self.eps = float(gamma), float(lr), float(beta1), float(beta2), float(eps)
@@ -955,6 +1052,9 @@ class DQNConfig:
         return _capi.DQNCfg(n_obs=self.n_obs, h1=self.h1, n_actions=self.n_actions, batch=self.batch, capacity=self.capacity, target_period=self.target_period,
                             double_dqn=int(self.double), clip_targets=int(self.clip_targets), replay_start=self.replay_start, seed=int(seed) & _M64,
                             gamma=self.gamma, beta1=self.beta1, beta2=self.beta2, eps=self.eps, clip_min=self.clip_min, clip_max=self.clip_max)
+
+    def to_c_nstep(self, rows_per_push):
+        return nstep_to_c(self, rows_per_push)
 
 
 def dqn_epsilon(iteration, eps_start=1.0, eps_end=0.1, decay_coefficient=0.25, decay_rate=30000):
@@ -1011,9 +1111,10 @@ def _q_mlp(t, x):
     return torch.relu(x @ t["w0"].T + t["b0"]) @ t["w1"].T + t["b1"]
 
 
-def dqn_targets_host(params, batch, cfg, dtype="float64"):
+def dqn_targets_host(params, batch, cfg, dtype="float64", disc=None):
     """``get_targets`` (dqn.py:673-705) in torch, every tensor in ``dtype``: [B][3] = a* (``cfg.double``: the first argmax of the online net on s';
-    else the target net's), the target net's Q(s') there, y = r + clip(gamma * that), r alone on a terminated row."""
+    else the target net's), the target net's Q(s') there, y = r + clip(gamma * that), r alone on a terminated row.  ``disc``: the discount per
+    row in ``cfg.gamma``'s place (``nstep_batch_host``'s gamma^m; None: ``cfg.gamma``)."""
     import torch
     td = getattr(torch, dtype)
     T = lambda a: torch.tensor(np.asarray(a), dtype=td)
@@ -1022,24 +1123,25 @@ def dqn_targets_host(params, batch, cfg, dtype="float64"):
         qt = _q_mlp({k: T(params["q_target"][k]) for k in DQN_TENSORS}, s2)
         astar = torch.argmax(_q_mlp({k: T(params["q"][k]) for k in DQN_TENSORS}, s2) if cfg.double else qt, dim=1, keepdim=True)
         qsel = torch.gather(qt, 1, astar).flatten()
-        g = cfg.gamma * qsel
+        g = (cfg.gamma if disc is None else T(disc)) * qsel
         if cfg.clip_targets:
             g = torch.clamp(g, cfg.clip_min, cfg.clip_max)
         y = torch.where(mask != 0, r + g, r)
     return torch.stack([astar.flatten().to(td), qsel, y], 1).numpy()
 
 
-def update_host_dqn(params, batch, cfg, dtype="float64", weights=None, grads_only=False, lr=None):
+def update_host_dqn(params, batch, cfg, dtype="float64", weights=None, grads_only=False, lr=None, disc=None):
     """One DQN update in torch with autograd, every tensor in ``dtype`` ("float64" or "float32"): the targets of ``dqn_targets_host``, the
     SmoothL1 loss (beta 1) of Q(s)[a] against them as a mean over the minibatch -- ``weights``: prioritised replay's importance weight per row,
     multiplying that row's term --, one bias-corrected Adam step, and the hard copy of the target if the new update count is a multiple of
     ``cfg.target_period``.  ``params``: as ``new_params_dqn`` / ``DQNLearner.state_dict()["params"]``; returns the new one and a dict with ``loss``
-    (unweighted), ``mean_q``, ``q_values``, ``td`` (Q(s, a) - y), ``targets`` ([B][3]) and ``grad``.  ``grads_only``: nothing is applied."""
+    (unweighted), ``mean_q``, ``q_values``, ``td`` (Q(s, a) - y), ``targets`` ([B][3]) and ``grad``.  ``grads_only``: nothing is applied.
+    ``disc``: as ``dqn_targets_host``'s."""
     import torch
     td = getattr(torch, dtype)
     T = lambda a: torch.tensor(np.asarray(a), dtype=td)
     P = {slot: {k: T(params[slot][k]) for k in DQN_TENSORS} for slot in _capi.DQN_SLOTS}
-    tg = dqn_targets_host(params, batch, cfg, dtype)
+    tg = dqn_targets_host(params, batch, cfg, dtype, disc=disc)
     y = T(tg[:, 2])
     net = {k: P["q"][k].clone().requires_grad_(True) for k in DQN_TENSORS}
     q = torch.gather(_q_mlp(net, T(batch["s"])), 1, torch.tensor(np.asarray(batch["a"], dtype=np.int64))[:, None]).flatten()
@@ -1081,11 +1183,12 @@ class DQNLearner(_Learner):
     """DQN on the device for the discrete-action envs (``MergeVecEnv("sumo-jerk-v0")``, ``"sumo-accel-v0"``): the reference's TRAIN_DQN
     (dqn.py:257-359) with ``DDPGLearner``'s interface.  ``env_or_dims``: such an env (its context, observation width, action count and action table
     are taken over) or ``(n_obs, n_actions)``.  ``init``: None (torch's nn.Linear initialisation) or a net {w0, b0, w1, b1}.
-    One update is three HIP launches (five with ``cfg.per``); acting, pushing and updating never synchronise with the host."""
+    One update is three HIP launches (five with ``cfg.per``); acting, pushing and updating never synchronise with the host.
+    ``rows_per_push``: as ``DDPGLearner``'s."""
 
     _api, _per_api, _slots, _flatten = "dqn", "dqn_per", _capi.DQN_SLOTS, staticmethod(flatten_q)
 
-    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None):
+    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None, rows_per_push=None):
         env = None if isinstance(env_or_dims, (tuple, list)) else env_or_dims
         if env is not None and env.continuous:
             raise ValueError("DQN needs a discrete action space (sumo-jerk-v0 or sumo-accel-v0), not the continuous jerk env")
@@ -1110,6 +1213,7 @@ class DQNLearner(_Learner):
         self.seed = int(seed)
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.handle = self._make_handle()
+        self._enable_nstep(env, rows_per_push)
         if self.cfg.per is not None:                                # (a population member's handle refuses: the population enables its members)
             self.ctx.dqn_per_enable(self.handle, self.cfg.per.to_c())
         c = self.cfg
@@ -1184,6 +1288,8 @@ class _DQNPopulationMember(DQNLearner):
     """One member of a ``DQNPopulation`` as a ``DQNLearner``: the handle is borrowed from the population (``stmpc_pop_dqn_member``), which outlives
     it; everything else -- the seeded initialisation, ``action_values`` and ``env_id`` from the env included -- is the lone learner's code."""
 
+    _owns_handle = False
+
     def __init__(self, population, m, env, cfg, seed, init):
         self._population, self._borrowed = population, population.ctx.dqn_pop_member(population.handle, m)
         super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
@@ -1217,6 +1323,7 @@ class DQNPopulation(DDPGPopulation):
     (``actor.QActorPopulation``)."""
 
     _api, _nstat = "dqn_pop", 4
+    _nstep_kind = "dqn"
     _cfg_type, _action_dtype = DQNConfig, "int32"
 
     def _check_env(self, env):
