@@ -36,6 +36,24 @@ def stub_policy(state):
     return max(-5.0, min(5.0, j))
 
 
+def agent_class(dqn):
+    """The reference's RLAgent with the stand-in policy in place of its network (``dqn``: the reference's module)."""
+    class Agent(dqn.RLAgent):
+        @classmethod
+        def load(cls, path): pass
+        @classmethod
+        def train(cls, num_frames): pass
+        @classmethod
+        def resume_training(cls, path, num_frames): pass
+        def get_control(self, state):
+            return stub_policy(state)
+    return Agent
+
+
+#: the takeover messages of dqn.py:145,149,153 as reason codes
+CODES = {"Crash predicted": 1, "DDPG going too fast": 2, "ST solver not happy with rollout state": 3}
+
+
 def main():
     tb = types.ModuleType("torch.utils.tensorboard")
     tb.SummaryWriter = object
@@ -48,15 +66,7 @@ def main():
     for k_, v_ in pkg.REFERENCE_DEFAULT.items():
         setattr(S, k_, v_)
 
-    class Agent(dqn.RLAgent):
-        @classmethod
-        def load(cls, path): pass
-        @classmethod
-        def train(cls, num_frames): pass
-        @classmethod
-        def resume_training(cls, path, num_frames): pass
-        def get_control(self, state):
-            return stub_policy(state)
+    Agent = agent_class(dqn)
 
     calls = {}
     msgs = []
@@ -71,7 +81,7 @@ def main():
     ego[:, 1] = synth.road_y(ego[:, 0])
     takeover = np.zeros(len(k), dtype=np.int32)
     reason = np.zeros(len(k), dtype=np.int32)
-    codes = {"Crash predicted": 1, "DDPG going too fast": 2, "ST solver not happy with rollout state": 3}
+    codes = dict(CODES)
     for i in range(len(k)):
         kk = int(k[i])
         state = prediction.HighwayState((float(ego[i, 0]), float(ego[i, 1])), float(ego[i, 2]), float(ego[i, 3]),

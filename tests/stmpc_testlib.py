@@ -174,6 +174,111 @@ def apply_settings(g):
     return pkg
 
 
+def combined_cells(g):
+    """The cell table of golden_combined_cells.npz as one dict per cell: ``base`` (0: A, 1: B) and the settings of the cell under their names."""
+    kinds = {"ROLLOUT_LENGTH": int, "ST_TEST_ROLLOUTS": int, "DESIRED_SPEED": float}
+    return [dict({str(key): kinds.get(str(key), bool)(val) for key, val in zip(g["cell_keys"], row)}, base=int(base))
+            for row, base in zip(g["cell_vals"], g["cell_base"])]
+
+
+def apply_cell(g, cell):
+    """The Settings of one cell of golden_combined_cells.npz (or one part of golden_combined_cells_b.npz: any dict of settings; ``base`` is no
+    setting): the fixture's own, then the cell's.  Returns the package."""
+    pkg = apply_settings(g)
+    pkg.apply_overrides({key: val for key, val in cell.items() if key != "base"})
+    return pkg
+
+
+def golden_states(g, n=None):
+    """The first ``n`` start states of a combined-controller golden as HighwayStates (vehicles cruising: accelerations 0)."""
+    from rl_mpc_lanemerging_amd.prediction import HighwayState
+    out = []
+    for i in range(g["ego"].shape[0] if n is None else n):
+        k = int(g["k_count"][i])
+        out.append(HighwayState((float(g["ego"][i, 0]), float(g["ego"][i, 1])), float(g["ego"][i, 2]), float(g["ego"][i, 3]),
+                                [float(x) for x in g["other_x"][i, :k]], [float(x) for x in g["other_v"][i, :k]], [0.0] * k))
+    return out
+
+
+def stub_policy(state):
+    """The stand-in policy of the combined-controller goldens: the arithmetic of tests/golden/make_golden_combined.py::stub_policy, operation for operation."""
+    gap = 100.0
+    for x in state.other_xs:
+        d = x - state.ego_position[0]
+        if 0.0 <= d < gap:
+            gap = d
+    j = 0.4 * (18.0 - state.ego_speed) - 0.8 * state.ego_acceleration - 25.0 / (gap + 5.0) + 1.0
+    return max(-5.0, min(5.0, j))
+
+
+class TwinState:
+    """An oracle state under the attribute names a policy reads (``other_accelerations``: the oracle's predictor does not return them)."""
+
+    def __init__(self, st_, xs, vs):
+        self.ego_position = (st_.ego_x, st_.ego_y); self.ego_speed = st_.ego_v; self.ego_acceleration = st_.ego_a
+        self.other_xs = xs; self.other_speeds = vs
+
+
+def combined_twin(S, states, policy, nthreads=8):
+    """The decision tree of dqn.RLAgent.do_combined_control (dqn.py:117-155) restated on the CPU oracle: its predictor rolls the policy's
+    jerks out, its solver probes the rolled-out state.  This is the layer between the reference's recorded decisions and the GPU's: a mismatch
+    of the GPU that this twin does not share is the kernels' or the host path's.
+
+    ``S``: the settings (ROLLOUT_LENGTH, ST_TEST_ROLLOUTS, TICK_LENGTH, COMBINATION_MIN_DISTANCE, STOP_X, CHECK_ROLLOUT_CRASH, LIMIT_DQN_SPEED with
+    DESIRED_SPEED, TEST_ROLLOUT_STATE, and what the solver reads).  ``states``: (ego[n, >= 4], k_count[n], other_x[n, K], other_v[n, K]).
+    ``policy(i, step, state) -> jerk``: asked once per rollout step of state i (step from 1), on a ``TwinState``.
+
+    Returns ``reason`` (0 policy, 1 crash predicted, 2 too fast, 3 probe), ``takeover``, ``crash_predicted``, ``rollout_steps``,
+    ``selected_speed`` (of the last step), ``rollout_s`` (one list per state, the start state's s first), ``test_states`` (oracle states: after
+    step ST_TEST_ROLLOUTS, else the last rolled-out one) and ``test_fallback`` (which of the two)."""
+    from rl_mpc_lanemerging_amd import _capi
+    from rl_mpc_lanemerging_amd.combined import get_ego_speed_from_jerk
+    from oracle import st_oracle as orc
+    ego, k_count, other_x, other_v = states
+    op = orc.OrcParams.from_dict(_capi.Params.from_settings(S).as_dict())
+    n, K = ego.shape[0], other_x.shape[1]
+    reason, crash_predicted, steps = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    selected, fallback = np.zeros(n), np.zeros(n, np.int32)
+    rollout_s, test_states, probe = [], [], []
+    for i in range(n):
+        k = int(k_count[i])
+        st_ = orc.make_state(*ego[i, :4], other_x[i, :k], other_v[i, :k])
+        hist = [orc.ego_s(st_.ego_x, st_.ego_y)]
+        crash, test_state, j, sel = False, None, 0, 0.0
+        while not (crash or j >= max(S.ROLLOUT_LENGTH, 1)):                    # dqn.py:129-141
+            j += 1
+            xs, vs = orc.state_lists(st_)
+            sel = get_ego_speed_from_jerk(st_.ego_v, st_.ego_a, policy(i, j, TwinState(st_, xs, vs)))
+            st_, crash = orc.predict_with_ego(op, st_, sel, S.TICK_LENGTH, S.COMBINATION_MIN_DISTANCE)
+            if j == S.ST_TEST_ROLLOUTS:
+                test_state = st_
+            hist.append(orc.ego_s(st_.ego_x, st_.ego_y))
+            if st_.ego_x > S.STOP_X:
+                break
+        if test_state is None:                                                 # dqn.py:142-143
+            test_state, fallback[i] = st_, 1
+        crash_predicted[i], steps[i], selected[i] = crash, j, sel
+        rollout_s.append(hist)
+        test_states.append(test_state)
+        if S.CHECK_ROLLOUT_CRASH and crash:                                    # dqn.py:144-155: the first that holds
+            reason[i] = 1
+        elif S.LIMIT_DQN_SPEED and sel > S.DESIRED_SPEED:
+            reason[i] = 2
+        elif S.TEST_ROLLOUT_STATE:
+            probe.append(i)
+    if probe:
+        ts = [test_states[i] for i in probe]
+        p_ego = np.array([[t.ego_x, t.ego_y, t.ego_v, t.ego_a, orc.ego_s(t.ego_x, t.ego_y)] for t in ts])
+        p_k = np.array([t.k for t in ts], dtype=np.int32)
+        p_ox, p_ov = np.zeros((len(ts), K)), np.zeros((len(ts), K))
+        for r, t in enumerate(ts):
+            p_ox[r, :t.k], p_ov[r, :t.k] = orc.state_lists(t)
+        res = orc.solve_batch(op, p_ego, p_k, p_ox, p_ov, solver="layered", nthreads=nthreads)
+        reason[np.array(probe)[res["crash"] != 0]] = 3
+    return {"reason": reason, "takeover": (reason != 0).astype(np.int32), "crash_predicted": crash_predicted, "rollout_steps": steps,
+            "selected_speed": selected, "rollout_s": rollout_s, "test_states": test_states, "test_fallback": fallback}
+
+
 # ---- actor populations (test_actor_pop.py; the learner tests evaluate views of their learners' actors through the same steps) ------------------
 ACTOR_P, ACTOR_N_PER, ACTOR_KMAX = 3, 24, 16
 ACTOR_N = ACTOR_P * ACTOR_N_PER

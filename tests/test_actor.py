@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from stmpc_testlib import apply_settings as _apply_settings
+from stmpc_testlib import apply_settings as _apply_settings, combined_twin as _combined_twin
 
 ACC_SLOTS = [0, 4, 8, 12]          # the other vehicles' accelerations in the 21-vector (dqn.py:399-400)
 
@@ -69,45 +69,10 @@ def test_host_state_vector_and_network_reproduce_the_reference(restore_settings)
 def test_reference_decisions_follow_from_the_recorded_jerks(restore_settings):
     """CPU: the decision tree on the oracle's predictor + solver, fed the recorded jerks, gives the reference's decisions (the same check as
     test_combined's, on the states and actions of the real actor)."""
-    from rl_mpc_lanemerging_amd import _capi
-    from rl_mpc_lanemerging_amd.combined import get_ego_speed_from_jerk
-    from oracle import st_oracle as orc
     g, pkg = _golden()
-    S = pkg.Settings
-    p = _capi.Params.from_settings(S)
-    op = orc.OrcParams.from_dict(p.as_dict())
-    n = g["ego"].shape[0]
-    reason = np.zeros(n, dtype=np.int32)
-    probe = []
-    for i in range(n):
-        k = int(g["k_count"][i])
-        st_ = orc.make_state(*g["ego"][i, :4], g["other_x"][i, :k], g["other_v"][i, :k])
-        crash, test_state, j = False, None, 0
-        while not (crash or j >= max(S.ROLLOUT_LENGTH, 1)):
-            j += 1
-            sel = get_ego_speed_from_jerk(st_.ego_v, st_.ego_a, float(g["jerks"][i, j - 1]))
-            st_, crash = orc.predict_with_ego(op, st_, sel, S.TICK_LENGTH, S.COMBINATION_MIN_DISTANCE)
-            if j == S.ST_TEST_ROLLOUTS:
-                test_state = st_
-            if st_.ego_x > S.STOP_X:
-                break
-        assert j == g["n_evals"][i]
-        if test_state is None:
-            test_state = st_
-        if crash:
-            reason[i] = 1
-        else:
-            probe.append((i, test_state))
-    ego = np.array([[t.ego_x, t.ego_y, t.ego_v, t.ego_a, orc.ego_s(t.ego_x, t.ego_y)] for _, t in probe])
-    kc = np.array([t.k for _, t in probe], dtype=np.int32)
-    ox = np.zeros((len(probe), 8)); ov = np.zeros((len(probe), 8))
-    for r, (_, t) in enumerate(probe):
-        xs, vs = orc.state_lists(t)
-        ox[r, :t.k] = xs; ov[r, :t.k] = vs
-    res = orc.solve_batch(op, ego, kc, ox, ov, solver="layered", nthreads=8)
-    for r, (i, _) in enumerate(probe):
-        if res["crash"][r]:
-            reason[i] = 3
+    twin = _combined_twin(pkg.Settings, (g["ego"], g["k_count"], g["other_x"], g["other_v"]), lambda i, step, state: float(g["jerks"][i, step - 1]))
+    assert np.array_equal(twin["rollout_steps"], g["n_evals"])
+    reason = twin["reason"]
     assert np.array_equal(reason, g["reason"])
     assert (g["reason"] == 1).sum() > 40 and (g["reason"] == 3).sum() > 20 and (g["reason"] == 0).sum() > 1000
 
