@@ -960,6 +960,92 @@ int  stmpc_nstep_window_ddpg(stmpc_ddpg *learner, const int64_t *idx, int n_idx,
 int  stmpc_nstep_window_dqn(stmpc_dqn *learner, const int64_t *idx, int n_idx, double *out);
 
 /*
+ * Categorical (C51) DQN learner on the device for the discrete-action environments: the distributional head of the reference's third agent
+ * (rainbow.py: RainbowAgent, the `all` library's rainbow preset; TRAIN_DQN / EVALUATE_DQN reach it too), after Bellemare, Dabney and Munos 2017,
+ * "A Distributional Perspective on Reinforcement Learning", Algorithm 1.  (Additive: new entries only, no signature or struct of ABI 8 changes, so
+ * STMPC_ABI_VERSION stays 8; no entry above changes what it computes.)  The network is n_obs -> h1 -> ReLU -> n_actions * n_atoms, float32: action
+ * a's n_atoms logits are the contiguous outputs a * n_atoms ... (a + 1) * n_atoms - 1, their softmax is a distribution over the support
+ * z_k = v_min + k * dz, dz = (v_max - v_min) / (n_atoms - 1), and Q(s, a) is its mean.  The replay ring, its counters, the minibatch indices,
+ * prioritised replay and the multi-step window are the DQN learner's.  Per update, on a minibatch of `batch` rows:
+ *   a* = the first maximum over the actions of the expected values of the online network (double_dqn) or the target network on s';
+ *   p' = the target network's distribution of a* on s';  b_j = (clamp(R + disc * z_j, v_min, v_max) - v_min) / dz, R alone where the episode
+ *   terminated (mask = 0); disc = gamma, or gamma^m of the multi-step window;  m_i = sum_j p'_j * max(0, 1 - |b_j - i|), j in order, in fp64;
+ *   row loss l = -sum_i m_i log p_i(s, a) with the stored action a;  Adam step on mean_r(w_r * l_r), w = 1 or prioritised replay's weights;
+ *   after the step, if the number of updates done is a multiple of target_period: target <- online (a hard copy).
+ * The softmax is formed in fp64 from the float32 logits and rounded once.  Three launches per update (five with prioritised replay); every counter
+ * lives on the device and no entry with a `stream` synchronises.  The entries mirror the DQN learner's one for one:
+ *   create          STMPC_EINVAL for what the DQN learner's create refuses, and for n_atoms < 2, n_actions * n_atoms > STMPC_C51_MAX_LOGITS, v_max <=
+ *                   v_min or a support that is not finite.  clip_targets, clip_min and clip_max are not read: the support's clamp is the clip
+ *   set / get_params, set / get_state, push_device, gather_device, per_enable, per_tree_read, per_last_device   as the DQN learner's; a slot is W0
+ *                   [h1][n_obs] | b0 [h1] | W1 [n_actions * n_atoms][h1] | b1 [n_actions * n_atoms]; slots STMPC_C51_Q ... STMPC_C51_Q_V.  The
+ *                   priority of a row is its loss l (per_last_device's td is l)
+ *   act_device      as the DQN learner's on the expected values: the greedy index is their first maximum; the exploration draws have the DQN
+ *                   learner's stream and counter rule.  d_debug_q (may be NULL) float32 [N][n_actions]: the expected values
+ *   update_device, grads_device   as the DQN learner's
+ *   targets_device  debug: DEVICE float32 [batch][4] = a*, the target network's expected value there, l, Q(s, a)
+ *   dist_device     debug: d_dist (may be NULL) DEVICE float32 [batch][2][n_atoms] = m and the online distribution p(s, a) of the minibatch of the
+ *                   current update index; d_out (may be NULL) as targets_device's; not both NULL
+ *   project_device  debug: d_m [n][n_atoms] = the projection of n caller-given distributions d_p [n][n_atoms] under d_reward, d_mask, d_disc
+ *                   (float32 [n] each), by the device function the update calls
+ *   stats_device    DEVICE fp64 [4]: the loss (unweighted mean of l) and mean Q(s, a) of the last minibatch, fill, updates done
+ *   multi_step_enable   stmpc_nstep_enable_dqn for this learner (the stmpc_nstep_ prefix is a closed set): on an empty ring, with its refusals
+ *   replay_read     debug, HOST: `count` rows of STMPC_DDPG_ROW float32 from row `first` of the ring; synchronises
+ *   dzout_read      debug, HOST: the output layer's gradient of the last pass as the weight gradients read it, float32 [Bp][Ap], Bp = batch rounded up
+ *                   to 16: (w / batch) (p - m) in the stored action's block, exact zeros elsewhere.  `count` must be Bp * Ap.  Synchronises
+ *   padded_read     debug, HOST: a slot as the library keeps it -- W0 [h1p][32] | b0 [h1p] | W1 [Ap][h1p] | b1 [Ap], h1p and Ap the next multiples of
+ *                   16 of h1 and n_actions * n_atoms; slots STMPC_C51_Q ... _Q_V, and STMPC_C51_GRAD: the last gradient.  Synchronises
+ */
+#define STMPC_C51_Q 0
+#define STMPC_C51_Q_TARGET 1
+#define STMPC_C51_Q_M 2
+#define STMPC_C51_Q_V 3
+#define STMPC_C51_GRAD 4                  /* padded_read only */
+#define STMPC_C51_MAX_LOGITS 1024         /* n_actions * n_atoms: the widest layer of the parameter layout */
+typedef struct stmpc_c51_cfg {
+    int32_t n_obs;                   /* the first sixteen fields are stmpc_dqn_cfg's, in its order */
+    int32_t h1;
+    int32_t n_actions;
+    int32_t batch;
+    int32_t capacity;
+    int32_t target_period;
+    int32_t double_dqn;
+    int32_t clip_targets;            /* not read */
+    int64_t replay_start;
+    uint64_t seed;
+    double gamma;
+    double beta1, beta2, eps;
+    double clip_min, clip_max;       /* not read */
+    double v_min, v_max;             /* the support's ends (-10, 10: the C51 paper's) */
+    int32_t n_atoms;                 /* K >= 2 (51) */
+    int32_t reserved;                /* 0 */
+} stmpc_c51_cfg;
+typedef struct stmpc_c51 stmpc_c51;
+int  stmpc_c51_create(stmpc_ctx *ctx, const stmpc_c51_cfg *cfg, stmpc_c51 **out);
+void stmpc_c51_destroy(stmpc_c51 *learner);
+int  stmpc_c51_set_params(stmpc_c51 *learner, int slot, const float *values, int64_t count);
+int  stmpc_c51_get_params(stmpc_c51 *learner, int slot, float *values, int64_t count);
+int  stmpc_c51_set_state(stmpc_c51 *learner, const int64_t *counters, const float *beta_pow);
+int  stmpc_c51_get_state(stmpc_c51 *learner, int64_t *counters, float *beta_pow);
+int  stmpc_c51_push_device(stmpc_c51 *learner, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                           const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream);
+int  stmpc_c51_act_device(stmpc_c51 *learner, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream);
+int  stmpc_c51_update_device(stmpc_c51 *learner, int n_updates, double lr, void *stream);
+int  stmpc_c51_grads_device(stmpc_c51 *learner, float *d_grad, void *stream);
+int  stmpc_c51_targets_device(stmpc_c51 *learner, float *d_out, void *stream);
+int  stmpc_c51_dist_device(stmpc_c51 *learner, float *d_dist, float *d_out, void *stream);
+int  stmpc_c51_project_device(stmpc_c51 *learner, int n, const float *d_p, const float *d_reward, const float *d_mask, const float *d_disc, float *d_m,
+                              void *stream);
+int  stmpc_c51_gather_device(stmpc_c51 *learner, float *d_rows, void *stream);
+int  stmpc_c51_stats_device(stmpc_c51 *learner, double *d_out, void *stream);
+int  stmpc_c51_per_enable(stmpc_c51 *learner, const stmpc_per_cfg *cfg);
+int  stmpc_c51_per_tree_read(stmpc_c51 *learner, int64_t first, int64_t count, double *nodes);
+int  stmpc_c51_per_last_device(stmpc_c51 *learner, int64_t *d_idx, float *d_td, float *d_weight, void *stream);
+int  stmpc_c51_multi_step_enable(stmpc_c51 *learner, const stmpc_nstep_cfg *cfg);
+int  stmpc_c51_replay_read(stmpc_c51 *learner, int64_t first, int64_t count, float *rows);
+int  stmpc_c51_dzout_read(stmpc_c51 *learner, float *values, int64_t count);
+int  stmpc_c51_padded_read(stmpc_c51 *learner, int slot, float *values, int64_t count);
+
+/*
  * A Q-network as the policy of the combined controller and of the first-step shield: DQNAgent.get_control (dqn.py:375-380) -- state vector -> Q ->
  * argmax -> JERK_VALUES_DQN[a] -- for N states in ONE launch, behind which RLAgent.do_combined_control runs as it does behind the DDPG actor.
  * (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8; no entry above changes what it computes.)  The

@@ -280,6 +280,11 @@ class DQNCfg(C.Structure):
                 ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("clip_min", C.c_double), ("clip_max", C.c_double)]
 
 
+class C51Cfg(C.Structure):
+    """``stmpc_c51_cfg`` (include/stmpc.h): ``stmpc_dqn_cfg``'s fields, then the support's ends and the atom count of the categorical head."""
+    _fields_ = list(DQNCfg._fields_) + [("v_min", C.c_double), ("v_max", C.c_double), ("n_atoms", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ProfileTotals(C.Structure):
     _fields_ = [("launches", C.c_int64), ("episodes", C.c_int64), ("solve_ms", C.c_double), ("dp_kernel_ms", C.c_double)]
 
@@ -315,6 +320,10 @@ EXPORTS = (
     "stmpc_dqn_push_device", "stmpc_dqn_act_device", "stmpc_dqn_update_device", "stmpc_dqn_grads_device", "stmpc_dqn_targets_device",
     "stmpc_dqn_gather_device", "stmpc_dqn_stats_device", "stmpc_dqn_per_enable", "stmpc_dqn_per_tree_read", "stmpc_dqn_per_last_device",
     "stmpc_dqn_padded_read",
+    "stmpc_c51_create", "stmpc_c51_destroy", "stmpc_c51_set_params", "stmpc_c51_get_params", "stmpc_c51_set_state", "stmpc_c51_get_state",
+    "stmpc_c51_push_device", "stmpc_c51_act_device", "stmpc_c51_update_device", "stmpc_c51_grads_device", "stmpc_c51_targets_device",
+    "stmpc_c51_dist_device", "stmpc_c51_project_device", "stmpc_c51_gather_device", "stmpc_c51_stats_device", "stmpc_c51_per_enable",
+    "stmpc_c51_per_tree_read", "stmpc_c51_per_last_device", "stmpc_c51_multi_step_enable", "stmpc_c51_replay_read", "stmpc_c51_dzout_read", "stmpc_c51_padded_read",
     "stmpc_pop_dqn_create", "stmpc_pop_dqn_destroy", "stmpc_pop_dqn_size", "stmpc_pop_dqn_member", "stmpc_pop_dqn_act_device",
     "stmpc_pop_dqn_push_device", "stmpc_pop_dqn_update_device", "stmpc_pop_dqn_stats_device", "stmpc_pop_dqn_per_enable", "stmpc_pop_dqn_replay_read",
     "stmpc_nstep_enable_ddpg", "stmpc_nstep_enable_dqn", "stmpc_pop_nstep_enable_ddpg", "stmpc_pop_nstep_enable_td3", "stmpc_pop_nstep_enable_dqn",
@@ -350,6 +359,9 @@ TRAFFIC_MIX_MAX = 64                  # STMPC_TRAFFIC_MIX_MAX
 TD3_SLOTS = ("critic2", "critic2_target", "critic2_m", "critic2_v")     # STMPC_TD3_CRITIC2 ... STMPC_TD3_CRITIC2_V
 DQN_SLOTS = ("q", "q_target", "q_m", "q_v")     # STMPC_DQN_Q ... STMPC_DQN_Q_V
 DQN_GRAD = 4                          # STMPC_DQN_GRAD: the gradient, for dqn_padded_read
+C51_SLOTS = DQN_SLOTS                 # STMPC_C51_Q ... STMPC_C51_Q_V
+C51_GRAD = 4                          # STMPC_C51_GRAD: the gradient, for c51_padded_read
+C51_MAX_LOGITS = 1024                 # STMPC_C51_MAX_LOGITS
 NSTEP_MAX = 16                        # STMPC_NSTEP_MAX
 DONE_COL = 67                         # the replay row's done column (terminated || truncated) on a learner with n_step > 1
 DQN_ACTION_COL = 66                   # the replay row's action column of a DQN learner
@@ -546,6 +558,17 @@ def load():
     lib.stmpc_dqn_per_tree_read.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.c_double)]
     lib.stmpc_dqn_per_last_device.argtypes = [vp, vp, vp, vp, vp]
     lib.stmpc_dqn_padded_read.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_c51_create.argtypes = [vp, C.POINTER(C51Cfg), C.POINTER(vp)]
+    lib.stmpc_c51_destroy.argtypes = [vp]
+    lib.stmpc_c51_destroy.restype = None
+    for name in ("set_params", "get_params", "set_state", "get_state", "push_device", "act_device", "update_device", "grads_device", "targets_device",
+                 "gather_device", "stats_device", "per_enable", "per_tree_read", "per_last_device", "padded_read"):       # the DQN learner's signatures
+        getattr(lib, "stmpc_c51_" + name).argtypes = list(getattr(lib, "stmpc_dqn_" + name).argtypes)
+    lib.stmpc_c51_dist_device.argtypes = [vp, vp, vp, vp]
+    lib.stmpc_c51_project_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.stmpc_c51_multi_step_enable.argtypes = [vp, C.POINTER(NStepCfg)]
+    lib.stmpc_c51_replay_read.argtypes = [vp, C.c_int64, C.c_int64, fp]
+    lib.stmpc_c51_dzout_read.argtypes = [vp, fp, C.c_int64]
     lib.stmpc_pop_dqn_create.argtypes = [vp, C.POINTER(DQNCfg), C.c_int, C.POINTER(vp)]
     lib.stmpc_pop_dqn_destroy.argtypes = [vp]
     lib.stmpc_pop_dqn_destroy.restype = None
@@ -1220,6 +1243,95 @@ class Context:
         o = np.cumsum([0, 32 * h1p, h1p, Ap * h1p, Ap])
         return {"w0": flat[o[0]:o[1]].reshape(h1p, 32), "b0": flat[o[1]:o[2]], "w1": flat[o[2]:o[3]].reshape(Ap, h1p), "b1": flat[o[3]:o[4]]}
 
+    # -- C51 learner (stmpc_c51_*): the categorical DQN agent; the DQN learner's methods on its own handle, plus the distribution's debug entries ----
+    def c51_create(self, cfg):
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_c51_create(self._h, C.byref(cfg), C.byref(h)))
+        return h
+
+    def c51_destroy(self, handle):
+        self._lib.stmpc_c51_destroy(handle)
+
+    def c51_set_params(self, handle, slot, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        self._chk(self._lib.stmpc_c51_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+
+    def c51_get_params(self, handle, slot, count):
+        flat = np.empty(int(count), dtype=np.float32)
+        self._chk(self._lib.stmpc_c51_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        return flat
+
+    def c51_set_state(self, handle, counters, beta_pow):
+        cn = np.ascontiguousarray(counters, dtype=np.int64)
+        bp = np.ascontiguousarray(beta_pow, dtype=np.float32)
+        assert cn.size == DDPG_NCOUNTERS and bp.size == 2
+        self._chk(self._lib.stmpc_c51_set_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def c51_get_state(self, handle):
+        cn, bp = np.zeros(DDPG_NCOUNTERS, dtype=np.int64), np.zeros(2, dtype=np.float32)
+        self._chk(self._lib.stmpc_c51_get_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
+        return cn, bp
+
+    def c51_push(self, handle, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
+        self._chk(self._lib.stmpc_c51_push_device(handle, int(N), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated, d_truncated,
+                                                  stream))
+
+    def c51_act(self, handle, N, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
+        self._chk(self._lib.stmpc_c51_act_device(handle, int(N), d_obs, int(obs_stride), float(eps), d_action, d_debug_q, stream))
+
+    def c51_update(self, handle, n_updates, lr, stream=0):
+        self._chk(self._lib.stmpc_c51_update_device(handle, int(n_updates), float(lr), stream))
+
+    def c51_grads(self, handle, d_grad, stream=0):
+        self._chk(self._lib.stmpc_c51_grads_device(handle, d_grad, stream))
+
+    def c51_targets(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_c51_targets_device(handle, d_out, stream))
+
+    def c51_dist(self, handle, d_dist, d_out=0, stream=0):
+        self._chk(self._lib.stmpc_c51_dist_device(handle, d_dist, d_out, stream))
+
+    def c51_project(self, handle, n, d_p, d_reward, d_mask, d_disc, d_m, stream=0):
+        self._chk(self._lib.stmpc_c51_project_device(handle, int(n), d_p, d_reward, d_mask, d_disc, d_m, stream))
+
+    def c51_gather(self, handle, d_rows, stream=0):
+        self._chk(self._lib.stmpc_c51_gather_device(handle, d_rows, stream))
+
+    def c51_stats(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_c51_stats_device(handle, d_out, stream))
+
+    def c51_per_enable(self, handle, cfg):
+        self._chk(self._lib.stmpc_c51_per_enable(handle, C.byref(cfg)))
+
+    def c51_per_tree_read(self, handle, first, count):
+        nodes = np.empty(int(count), dtype=np.float64)
+        self._chk(self._lib.stmpc_c51_per_tree_read(handle, int(first), int(count), nodes.ctypes.data_as(C.POINTER(C.c_double))))
+        return nodes
+
+    def c51_per_last(self, handle, d_idx, d_td, d_weight, stream=0):
+        self._chk(self._lib.stmpc_c51_per_last_device(handle, d_idx, d_td, d_weight, stream))
+
+    def c51_replay_read(self, handle, first, count):
+        """Debug: ``count`` rows from row ``first`` of a C51 learner's ring, float32 [count][DDPG_ROW]; synchronises."""
+        rows = np.zeros((int(count), DDPG_ROW), dtype=np.float32)
+        self._chk(self._lib.stmpc_c51_replay_read(handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
+        return rows
+
+    def c51_dzout_read(self, handle, batch, n_logits):
+        """Debug: the output layer's gradient of the last pass, float32 [Bp][Ap] (``batch`` rounded up to 16, ``n_logits`` to 16); synchronises."""
+        out = np.zeros((((int(batch) + 15) & ~15), ((int(n_logits) + 15) & ~15)), dtype=np.float32)
+        self._chk(self._lib.stmpc_c51_dzout_read(handle, out.ctypes.data_as(C.POINTER(C.c_float)), int(out.size)))
+        return out
+
+    def c51_padded_read(self, handle, slot, h1, n_logits):
+        """Debug: a slot (0 ... 3, or ``C51_GRAD``) in the library's padded layout as {w0 [h1p][32], b0 [h1p], w1 [Ap][h1p], b1 [Ap]}, ``n_logits`` =
+        n_actions * n_atoms; synchronises."""
+        h1p, Ap = (int(h1) + 15) & ~15, (int(n_logits) + 15) & ~15
+        flat = np.empty(33 * h1p + (h1p + 1) * Ap, dtype=np.float32)
+        self._chk(self._lib.stmpc_c51_padded_read(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        o = np.cumsum([0, 32 * h1p, h1p, Ap * h1p, Ap])
+        return {"w0": flat[o[0]:o[1]].reshape(h1p, 32), "b0": flat[o[1]:o[2]], "w1": flat[o[2]:o[3]].reshape(Ap, h1p), "b1": flat[o[3]:o[4]]}
+
     # -- DQN population (stmpc_pop_dqn_*): P DQN learners, one launch per kernel (dqn.py:257-359) ------------------------
     def dqn_pop_create(self, cfgs):
         """``cfgs``: a sequence of ``DQNCfg``; the library checks the member count and that the launch shapes are common."""
@@ -1263,7 +1375,8 @@ class Context:
 
     # -- multi-step returns (stmpc_nstep_*, stmpc_pop_nstep_*): once per learner / population, on empty rings; ``kind``: "ddpg" (a TD3 learner's base too), "td3" (populations) or "dqn"
     def nstep_enable(self, kind, handle, cfg):
-        self._chk(getattr(self._lib, "stmpc_nstep_enable_" + kind)(handle, C.byref(cfg)))
+        name = "stmpc_c51_multi_step_enable" if kind == "c51" else "stmpc_nstep_enable_" + kind      # (the stmpc_nstep_ prefix is a closed set)
+        self._chk(getattr(self._lib, name)(handle, C.byref(cfg)))
 
     def pop_nstep_enable(self, kind, handle, cfgs):
         table = (NStepCfg * len(cfgs))(*cfgs)

@@ -16,6 +16,7 @@
 #include "stmpc_actor_pop_kernels.hpp"
 #include "stmpc_dqn_kernels.hpp"
 #include "stmpc_dqn_pop_kernels.hpp"
+#include "stmpc_c51_kernels.hpp"
 #include "stmpc_qactor_kernels.hpp"
 #include "stmpc_qactor_pop_kernels.hpp"
 #include <initializer_list>
@@ -1311,6 +1312,235 @@ int stmpc_dqn_padded_read(stmpc_dqn *t, int slot, float *values, int64_t count) 
     if (!t || !values || slot < 0 || slot > STMPC_DQN_GRAD) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
     if (count != dq_nparam(t->h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
     return read_back(t->rp.device, values, slot == STMPC_DQN_GRAD ? t->dev.base.q.g : net_slot(t->dev.base.q, slot), (size_t)count * sizeof(float));
+}
+
+}  // extern "C"
+
+// ---- C51 learner (stmpc_c51_*): the categorical DQN agent on a replay store, one network and one workspace of its own, as stmpc_dqn holds them (it is
+// not a stmpc_dqn: its device struct is a C51Dev and its network's output width is n_actions * n_atoms); kernels in stmpc_c51_kernels.hpp ----------
+struct stmpc_c51 {
+    stmpc_c51_cfg cfg{};
+    C51Dev dev{};                           // dev.dq.base: the constants, base.q the logits network (base.h2 = A K, base.h2p = Ap), the workspace and the
+                                            // replay's part (rp.wire at create and again in stmpc_c51_per_enable)
+    Replay rp;
+    DevBuf net[11], ws[7];
+    std::vector<Seg> lay;
+    int h1p = 0, Ap = 0, np = 0;
+    size_t lds = 0;
+    Grid grid{};
+};
+
+namespace {
+int c51_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling[2];
+    TRY(raise_dynamic_lds((const void *)k_c51_fwd, "k_c51_fwd", ceiling[0], device, lds));
+    return raise_dynamic_lds((const void *)k_c51_act, "k_c51_act", ceiling[1], device, lds);
+}
+// the pass and the weight gradients; dbg4, dist: the two debug entries' outputs
+void c51_launch_grads(stmpc_c51 *t, int gate, float *dbg4, float *dist, hipStream_t st) {
+    hipLaunchKernelGGL(k_c51_fwd, dim3(t->grid.tiles), dim3(AT_THREADS), t->lds, st, t->dev, t->cfg.batch, gate, dbg4, dist);
+    hipLaunchKernelGGL(k_c51_wgrad, dim3(t->grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t->dev, t->rp.Bp, gate);
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_c51_create(stmpc_ctx *c, const stmpc_c51_cfg *g, stmpc_c51 **out) {
+    if (!c || !g || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (g->n_actions < 1 || g->n_actions > STMPC_ENV_MAX_ACTIONS) return fail(STMPC_EINVAL, "n_actions must be in 1 ... " + std::to_string(STMPC_ENV_MAX_ACTIONS));
+    if (g->n_atoms < 2) return fail(STMPC_EINVAL, "n_atoms must be at least 2");
+    if ((long long)g->n_actions * g->n_atoms > STMPC_C51_MAX_LOGITS)
+        return fail(STMPC_EINVAL, "n_actions * n_atoms = " + std::to_string((long long)g->n_actions * g->n_atoms) + " exceeds " + std::to_string(STMPC_C51_MAX_LOGITS));
+    if (!std::isfinite(g->v_min) || !std::isfinite(g->v_max) || !(g->v_max > g->v_min)) return fail(STMPC_EINVAL, "the support needs finite v_min < v_max");
+    if (g->n_obs < 1 || g->n_obs > AT_KIN - 1 || g->h1 < 1 || g->h1 > 1024) return fail(STMPC_EINVAL, "C51 network shape out of range (n_obs <= 31, hidden width <= 1024)");
+    if (g->batch < 1 || g->batch > PER_MAX_B) return fail(STMPC_EINVAL, "batch must be in 1 ... 8192");
+    if (g->target_period < 1) return fail(STMPC_EINVAL, "target_period must be at least 1");
+    if (g->capacity < 1 || g->replay_start < 0 || g->replay_start >= g->capacity) return fail(STMPC_EINVAL, "capacity must be positive and replay_start below it");
+    if (!(g->gamma >= 0) || !std::isfinite(g->gamma) || !(g->beta1 >= 0 && g->beta1 < 1) || !(g->beta2 >= 0 && g->beta2 < 1) || !(g->eps > 0))
+        return fail(STMPC_EINVAL, "C51 constants out of range");
+    HIPCHK(hipSetDevice(c->device));
+    const int AK = g->n_actions * g->n_atoms, h1p = (g->h1 + 15) & ~15, Ap = (AK + 15) & ~15;
+    const size_t lds = c51_tile_bytes(h1p, Ap, g->n_atoms);
+    if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, "C51 network too wide for one workgroup's LDS");
+    stmpc_c51 *t = new stmpc_c51();
+    t->cfg = *g; t->h1p = h1p; t->Ap = Ap; t->np = dg_nparam(h1p, Ap); t->lds = lds;
+    t->lay = slot_layout(g->n_obs, g->h1, AK, h1p, Ap, false);
+    t->rp.device = c->device;                                        // (what destroy selects, should an allocation fail)
+    DdpgDev &d = t->dev.dq.base;
+    int rc = net_build(t->net, d.q, g->n_obs, h1p, Ap);
+    if (!rc) rc = ws_build(t->ws, d, (g->batch + 15) & ~15, h1p, Ap);
+    if (!rc) rc = t->rp.create(c->device, g->batch, g->capacity);
+    if (!rc) rc = c51_raise_lds(c->device, lds);
+    if (rc) { stmpc_c51_destroy(t); return rc; }
+    t->grid = make_grid(t->rp.Bp, h1p, Ap, false);
+    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = AK; d.h1p = h1p; d.h2p = Ap; d.replay_start = g->replay_start; d.seed = g->seed;
+    d.gamma = (float)g->gamma; d.beta1 = (float)g->beta1; d.beta2 = (float)g->beta2;
+    d.omb1 = 1.0f - d.beta1; d.omb2 = 1.0f - d.beta2; d.eps = (float)g->eps;
+    t->rp.wire(d);
+    DqnDev &q = t->dev.dq;
+    q.A = g->n_actions; q.Ap = Ap; q.dbl = g->double_dqn != 0; q.clip = 0; q.target_period = g->target_period;     // (clip_targets: the support's clamp is the clip)
+    t->dev.K = g->n_atoms; t->dev.v_min = g->v_min; t->dev.v_max = g->v_max; t->dev.dz = (g->v_max - g->v_min) / (double)(g->n_atoms - 1);
+    *out = t;
+    return STMPC_OK;
+}
+
+void stmpc_c51_destroy(stmpc_c51 *t) {
+    if (!t) return;
+    (void)hipSetDevice(t->rp.device);
+    delete t;
+}
+
+int stmpc_c51_set_params(stmpc_c51 *t, int slot, const float *values, int64_t count) {
+    TRY(slot_args(t, values, slot, 4));
+    return slot_set(t->rp.device, t->lay, t->np, net_slot(t->dev.dq.base.q, slot), values, count, slot < 2,
+                    [&] { hipLaunchKernelGGL(k_c51_adam, dim3(t->grid.ablocks), dim3(256), 0, (hipStream_t)0, t->dev, 0.f, 1, 1); });
+}
+
+int stmpc_c51_get_params(stmpc_c51 *t, int slot, float *values, int64_t count) {
+    TRY(slot_args(t, values, slot, 4));
+    return slot_get(t->rp.device, t->lay, t->np, net_slot(t->dev.dq.base.q, slot), values, count);
+}
+
+int stmpc_c51_set_state(stmpc_c51 *t, const int64_t *counters, const float *beta_pow) {
+    if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
+    TRY(t->rp.set_counters(counters));
+    HIPCHK(hipMemcpy(t->dev.dq.base.q.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
+    return STMPC_OK;
+}
+
+int stmpc_c51_get_state(stmpc_c51 *t, int64_t *counters, float *beta_pow) {
+    if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
+    TRY(t->rp.get_counters(counters));
+    HIPCHK(hipMemcpy(beta_pow, t->dev.dq.base.q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return STMPC_OK;
+}
+
+int stmpc_c51_push_device(stmpc_c51 *t, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_action,
+                          const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
+    if (N < 0 || N > t->cfg.capacity || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N exceeds the replay capacity, or obs_stride is shorter than the observation");
+    if (N == 0) return STMPC_OK;
+    TRY(nstep_check_push(t->dev.dq.base, N));
+    if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(t->rp.device));
+    hipLaunchKernelGGL(k_dqn_push, dim3(push_blocks(N)), dim3(256), 0, (hipStream_t)stream, t->dev.dq, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward,
+                       d_terminated, d_truncated);                  // (the DQN learner's own push kernel on the embedded struct: the row has the same columns)
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_c51_act_device(stmpc_c51 *t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
+    if (N < 0 || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N negative, or obs_stride shorter than the observation");
+    if (!(eps >= 0 && eps <= 1)) return fail(STMPC_EINVAL, "eps must be in 0 ... 1");
+    if (N == 0) return STMPC_OK;
+    if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(t->rp.device));
+    hipLaunchKernelGGL(k_c51_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t->lds, (hipStream_t)stream, t->dev, N, d_obs, obs_stride, (float)eps,
+                       eps > 0 ? 1 : 0, d_action, d_debug_q);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_c51_update_device(stmpc_c51 *t, int n_updates, double lr, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
+    if (n_updates < 0 || !(lr >= 0)) return fail(STMPC_EINVAL, "n_updates or the learning rate is negative");
+    HIPCHK(hipSetDevice(t->rp.device));
+    hipStream_t st = (hipStream_t)stream;
+    for (int u = 0; u < n_updates; ++u) {                            // three launches, five with prioritised replay, whatever the counters say
+        per_launch_sample(t->rp, t->dev.dq.base, 1, st);
+        c51_launch_grads(t, 1, nullptr, nullptr, st);
+        per_launch_update(t->rp, t->dev.dq.base, st);
+        hipLaunchKernelGGL(k_c51_adam, dim3(t->grid.ablocks), dim3(256), 0, st, t->dev, (float)lr, 0, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_c51_grads_device(stmpc_c51 *t, float *d_grad, void *stream) {
+    if (!t || !d_grad) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->rp.device));
+    hipStream_t st = (hipStream_t)stream;
+    per_launch_sample(t->rp, t->dev.dq.base, 0, st);
+    c51_launch_grads(t, 0, nullptr, nullptr, st);
+    hipLaunchKernelGGL(k_c51_unpad, dim3(128), dim3(256), 0, st, t->dev, (const float *)t->dev.dq.base.q.g, d_grad);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_c51_targets_device(stmpc_c51 *t, float *d_out, void *stream) { return stmpc_c51_dist_device(t, nullptr, d_out, stream); }
+
+int stmpc_c51_dist_device(stmpc_c51 *t, float *d_dist, float *d_out, void *stream) {
+    if (!t || (!d_dist && !d_out)) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->rp.device));
+    per_launch_sample(t->rp, t->dev.dq.base, 0, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_c51_fwd, dim3(t->grid.tiles), dim3(AT_THREADS), t->lds, (hipStream_t)stream, t->dev, t->cfg.batch, 0, d_out, d_dist);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_c51_project_device(stmpc_c51 *t, int n, const float *d_p, const float *d_reward, const float *d_mask, const float *d_disc, float *d_m, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
+    if (n < 0) return fail(STMPC_EINVAL, "n is negative");
+    if (n == 0) return STMPC_OK;
+    if (!d_p || !d_reward || !d_mask || !d_disc || !d_m) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(t->rp.device));
+    hipLaunchKernelGGL(k_c51_project, dim3((n + AT_TM - 1) / AT_TM), dim3(AT_THREADS), 0, (hipStream_t)stream, t->dev, n, d_p, d_reward, d_mask, d_disc, d_m);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_c51_gather_device(stmpc_c51 *t, float *d_rows, void *stream) {
+    if (!t || !d_rows) return fail(STMPC_EINVAL, "NULL argument");
+    return replay_gather(t->rp, t->dev.dq.base, d_rows, stream);
+}
+
+int stmpc_c51_stats_device(stmpc_c51 *t, double *d_out, void *stream) {
+    if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->rp.device));
+    hipLaunchKernelGGL(k_c51_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, t->dev, t->cfg.batch, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_c51_per_enable(stmpc_c51 *t, const stmpc_per_cfg *g) {
+    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
+    TRY(per_check_cfg(g));
+    TRY(t->rp.check_empty());
+    return per_attach(t->rp, t->dev.dq.base, nullptr, g);
+}
+
+int stmpc_c51_per_tree_read(stmpc_c51 *t, int64_t first, int64_t count, double *nodes) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return t->rp.read_tree(first, count, nodes);
+}
+
+int stmpc_c51_per_last_device(stmpc_c51 *t, int64_t *d_idx, float *d_td, float *d_weight, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return per_last(t->rp, t->dev.dq.base, d_idx, d_td, d_weight, stream);
+}
+
+int stmpc_c51_multi_step_enable(stmpc_c51 *t, const stmpc_nstep_cfg *g) {
+    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
+    return nstep_attach(t->rp, t->dev.dq.base, g);
+}
+
+int stmpc_c51_replay_read(stmpc_c51 *t, int64_t first, int64_t count, float *rows) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return t->rp.read_rows(first, count, rows);
+}
+
+int stmpc_c51_dzout_read(stmpc_c51 *t, float *values, int64_t count) {
+    if (!t || !values) return fail(STMPC_EINVAL, "NULL argument");
+    if (count != (int64_t)t->rp.Bp * t->Ap) return fail(STMPC_EINVAL, "count is not batch rounded up to 16 times the padded logit count");
+    return read_back(t->rp.device, values, t->dev.dq.base.aD2, (size_t)count * sizeof(float));
+}
+
+int stmpc_c51_padded_read(stmpc_c51 *t, int slot, float *values, int64_t count) {
+    if (!t || !values || slot < 0 || slot > STMPC_C51_GRAD) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
+    if (count != dq_nparam(t->h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
+    return read_back(t->rp.device, values, slot == STMPC_C51_GRAD ? t->dev.dq.base.q.g : net_slot(t->dev.dq.base.q, slot), (size_t)count * sizeof(float));
 }
 
 }  // extern "C"

@@ -43,6 +43,12 @@ target copy every ``target_period`` updates -- three launches per update, five w
 ``dqn_adam_host``, ``dqn_act_host``, ``dqn_epsilon``; the loop: ``train_dqn``.  ``DQNPopulation`` (``csrc/stmpc_dqn_pop_kernels.hpp``,
 ``stmpc_pop_dqn_*``) is to it what ``DDPGPopulation`` is to ``DDPGLearner``: P independent DQN learners on slices of one discrete env, the same
 three (five) launches per update whatever P is, ``eps`` and ``lr`` per member, ``per=`` per member.
+
+``C51Learner`` (``C51Config``, ``csrc/stmpc_c51_kernels.hpp``, ``stmpc_c51_*``) is the categorical head of the reference's third agent (rainbow.py, the
+``all`` library's rainbow preset) on the DQN learner's ring: the network emits ``n_atoms`` logits per action, Q(s, a) is the mean of their softmax over
+a fixed support, and the update minimises the cross-entropy against the projected Bellman-shifted target distribution (Bellemare et al. 2017,
+Algorithm 1) -- three launches per update, five with ``per``; ``n_step`` as the DQN learner's.  Twins: ``c51_support``, ``c51_project_host``,
+``c51_project_scatter_host``, ``c51_targets_host``, ``update_host_c51``; ``train_dqn`` takes it as it takes a ``DQNLearner``.
 """
 import math
 
@@ -1378,6 +1384,269 @@ class DQNPopulation(DDPGPopulation):
         """The same as a dict of arrays of length P with the keys of ``DQNLearner.stats``; synchronises."""
         s = self.stats_device().cpu().numpy()
         return {"loss": s[:, 0].copy(), "mean_q": s[:, 1].copy(), "fill": s[:, 2].astype(np.int64), "updates": s[:, 3].astype(np.int64)}
+
+
+# ---- C51: the categorical DQN agent (csrc/stmpc_c51_kernels.hpp, stmpc_c51_*) ---------------------------------------------------------------------
+class C51Config(DQNConfig):
+    """``DQNConfig`` plus the categorical head's support: ``n_atoms`` atoms z_k = v_min + k (v_max - v_min) / (n_atoms - 1).  The defaults 51, -10, 10 are
+    the C51 paper's (Bellemare et al. 2017); the ``all`` rainbow preset's own values could not be read (the library is absent from the reference
+    checkout).  ``clip_targets`` / ``clip_min`` / ``clip_max`` are not read: the support's clamp is the clip."""
+
+    def __init__(self, *args, n_atoms=51, v_min=-10.0, v_max=10.0, **kw):
+        super().__init__(*args, **kw)
+        self.n_atoms, self.v_min, self.v_max = int(n_atoms), float(v_min), float(v_max)
+        if self.n_atoms < 2:
+            raise ValueError("C51 needs n_atoms >= 2, not %d" % self.n_atoms)
+        if not (math.isfinite(self.v_min) and math.isfinite(self.v_max) and self.v_max > self.v_min):
+            raise ValueError("C51 needs a finite support with v_max > v_min, not [%r, %r]" % (self.v_min, self.v_max))
+        self.check_width()
+
+    def check_width(self):
+        if self.n_actions is not None and self.n_actions * self.n_atoms > _capi.C51_MAX_LOGITS:
+            raise ValueError("n_actions * n_atoms = %d * %d exceeds the widest layer, %d" % (self.n_actions, self.n_atoms, _capi.C51_MAX_LOGITS))
+
+    def to_c(self, seed):
+        base = super().to_c(seed)
+        return _capi.C51Cfg(v_min=self.v_min, v_max=self.v_max, n_atoms=self.n_atoms, reserved=0, **{n: getattr(base, n) for n, _ in _capi.DQNCfg._fields_})
+
+
+def c51_support(cfg, dtype=np.float64):
+    """The atoms z_k = v_min + k dz [n_atoms], formed in float64 as the kernels form them, then cast to ``dtype``."""
+    dz = (cfg.v_max - cfg.v_min) / (cfg.n_atoms - 1)
+    return (np.float64(cfg.v_min) + np.arange(cfg.n_atoms, dtype=np.float64) * np.float64(dz)).astype(dtype)
+
+
+def _c51_positions(r, mask, disc, cfg, dtype):
+    """b [n][K]: the positions on the support of the shifted atoms clamp(r + disc z_j, v_min, v_max); r alone where mask == 0 (a select)."""
+    f = np.dtype(dtype).type
+    r, mask, disc = (np.asarray(x, dtype=dtype).reshape(-1) for x in (r, mask, disc))
+    z = c51_support(cfg, dtype)
+    t = np.where(mask[:, None] != 0, r[:, None] + disc[:, None] * z[None, :], np.broadcast_to(r[:, None], (r.size, z.size)))
+    t = np.clip(t, f(cfg.v_min), f(cfg.v_max))
+    return (t - f(cfg.v_min)) / f((cfg.v_max - cfg.v_min) / (cfg.n_atoms - 1))
+
+
+def c51_project_host(p, r, mask, disc, cfg, dtype="float64"):
+    """The categorical projection in gather form, ``c51_project_row`` of csrc/stmpc_c51_kernels.hpp in numpy, every number in ``dtype``:
+    m_i = sum_j p_j max(0, 1 - |b_j - i|), the terms added in j order.  ``p`` [n][K]; ``r``, ``mask``, ``disc`` [n].  Right where b_j is an integer."""
+    p = np.asarray(p, dtype=dtype)
+    b = _c51_positions(r, mask, disc, cfg, dtype)
+    i = np.arange(cfg.n_atoms).astype(dtype)
+    m = np.zeros_like(p)
+    for j in range(cfg.n_atoms):
+        m = m + p[:, j:j + 1] * np.maximum(0, 1 - np.abs(b[:, j:j + 1] - i[None, :]))
+    return m
+
+
+def c51_project_scatter_host(p, r, mask, disc, cfg):
+    """The textbook statement (Bellemare et al. 2017, Algorithm 1) in float64, one atom at a time: l = floor(b_j), u = ceil(b_j), m_l += p_j (u - b_j),
+    m_u += p_j (b_j - l) -- with the customary correction where b_j is an integer (l == u: both weights vanish and the plain loop loses p_j):
+    m_l += p_j.  For the suite's comparison only."""
+    p = np.asarray(p, dtype=np.float64)
+    b = _c51_positions(r, mask, disc, cfg, "float64")
+    m = np.zeros_like(p)
+    for n in range(p.shape[0]):
+        for j in range(cfg.n_atoms):
+            lo, up = int(math.floor(b[n, j])), int(math.ceil(b[n, j]))
+            if lo == up:
+                m[n, lo] += p[n, j]
+            else:
+                m[n, lo] += p[n, j] * (up - b[n, j])
+                m[n, up] += p[n, j] * (b[n, j] - lo)
+    return m
+
+
+def init_c51_net(n_obs, h1, A, n_atoms, rng):
+    """``init_q_net`` with A * n_atoms outputs: action a's logits are rows a * n_atoms ... (a + 1) * n_atoms - 1 of w1 and b1."""
+    return init_q_net(n_obs, h1, A * n_atoms, rng)
+
+
+def _c51_logits(t, x, A, K):
+    return _q_mlp(t, x).reshape(x.shape[0], A, K)
+
+
+def c51_targets_host(params, batch, cfg, dtype="float64", disc=None):
+    """The target side of one update in ``dtype``: {"ev_next" [B][A]: the expected values on s' of the net that picks a* (``cfg.double``: the online
+    one), "astar" int64 [B]: their first maximum, "q_next" [B]: the target net's expected value at a*, "p_next" [B][K]: its distribution there,
+    "m" [B][K]: ``c51_project_host`` of it under (r, mask, disc)}.  ``disc``: the discount per row (``nstep_batch_host``'s; None: ``cfg.gamma``)."""
+    import torch
+    td = getattr(torch, dtype)
+    T = lambda a: torch.tensor(np.asarray(a), dtype=td)
+    A, K, B = cfg.n_actions, cfg.n_atoms, len(batch["r"])
+    z = T(c51_support(cfg))
+    with torch.no_grad():
+        s2 = T(batch["s2"])
+        pt = torch.softmax(_c51_logits({k: T(params["q_target"][k]) for k in DQN_TENSORS}, s2, A, K), -1)
+        ps = torch.softmax(_c51_logits({k: T(params["q"][k]) for k in DQN_TENSORS}, s2, A, K), -1) if cfg.double else pt
+        ev = (ps * z).sum(-1)
+        astar = torch.argmax(ev, dim=1)
+        p_next = pt[torch.arange(B), astar]
+        q_next = (p_next * z).sum(-1)
+    d = np.full(B, cfg.gamma) if disc is None else np.asarray(disc)
+    m = c51_project_host(p_next.numpy(), np.asarray(batch["r"]), np.asarray(batch["mask"]), d, cfg, dtype)
+    return {"ev_next": ev.numpy(), "astar": astar.numpy(), "q_next": q_next.numpy(), "p_next": p_next.numpy(), "m": m}
+
+
+def update_host_c51(params, batch, cfg, dtype="float64", weights=None, grads_only=False, lr=None, disc=None):
+    """One C51 update in torch with autograd, every tensor in ``dtype``: the projected target distribution of ``c51_targets_host``, the row loss
+    l = -sum_i m_i log_softmax(logits(s)[a])_i, its mean over the minibatch -- ``weights``: prioritised replay's importance weight per row --, one
+    bias-corrected Adam step and the hard copy of the target as ``update_host_dqn`` has them.  Returns the new params and a dict with
+    ``update_host_dqn``'s keys -- ``loss`` (unweighted), ``mean_q``, ``q_values`` (the expected value of the stored action), ``td`` (the row loss: the
+    priority), ``targets`` ([B][3]: a*, the target net's expected value there, l), ``grad`` -- plus ``dist`` ([B][2][K]: m and p(s, a)), ``row_loss``
+    and ``ev_next``."""
+    import torch
+    td = getattr(torch, dtype)
+    T = lambda a: torch.tensor(np.asarray(a), dtype=td)
+    A, K, B = cfg.n_actions, cfg.n_atoms, len(batch["r"])
+    P = {slot: {k: T(params[slot][k]) for k in DQN_TENSORS} for slot in _capi.C51_SLOTS}
+    tg = c51_targets_host(params, batch, cfg, dtype, disc=disc)
+    m = T(tg["m"])
+    net = {k: P["q"][k].clone().requires_grad_(True) for k in DQN_TENSORS}
+    a = torch.tensor(np.asarray(batch["a"], dtype=np.int64))
+    logp = torch.log_softmax(_c51_logits(net, T(batch["s"]), A, K), -1)[torch.arange(B), a]
+    terms = -(m * logp).sum(-1)
+    loss = terms.mean()
+    grads = dict(zip(DQN_TENSORS, torch.autograd.grad(loss if weights is None else (T(weights) * terms).mean(), [net[k] for k in DQN_TENSORS])))
+    u = int(params["updates"])
+    if not grads_only:
+        t = u + 1
+        bc1, bc2 = 1.0 - cfg.beta1 ** t, 1.0 - cfg.beta2 ** t
+        for k in DQN_TENSORS:
+            mm = cfg.beta1 * P["q_m"][k] + (1 - cfg.beta1) * grads[k]
+            vv = cfg.beta2 * P["q_v"][k] + (1 - cfg.beta2) * grads[k] * grads[k]
+            P["q_m"][k], P["q_v"][k] = mm, vv
+            P["q"][k] = P["q"][k] - ((cfg.lr if lr is None else lr) / bc1) * mm / (vv.sqrt() / math.sqrt(bc2) + cfg.eps)
+            if t % cfg.target_period == 0:
+                P["q_target"][k] = P["q"][k].clone()
+    out = {slot: {k: P[slot][k].detach().numpy() for k in DQN_TENSORS} for slot in _capi.C51_SLOTS}
+    out["beta_pow"] = np.array(params["beta_pow"], dtype=np.float32) * (1 if grads_only else np.array([cfg.beta1, cfg.beta2], dtype=np.float32))
+    out["updates"] = u + (0 if grads_only else 1)
+    p = logp.detach().exp()
+    q = (p * T(c51_support(cfg))).sum(-1)
+    row_loss = terms.detach().numpy()
+    info = {"loss": float(loss.detach()), "mean_q": float(q.mean()), "q_values": q.numpy(), "td": row_loss, "row_loss": row_loss,
+            "targets": np.stack([tg["astar"].astype(row_loss.dtype), tg["q_next"], row_loss], 1), "dist": np.stack([tg["m"], p.numpy()], 1),
+            "ev_next": tg["ev_next"], "grad": {k: grads[k].numpy() for k in DQN_TENSORS}}
+    return out, info
+
+
+class C51Learner(_Learner):
+    """Categorical DQN on the device for the discrete-action envs, with ``DQNLearner``'s interface (``train_dqn`` takes either).  ``env_or_dims``: a
+    discrete env or ``(n_obs, n_actions)``; ``cfg``: ``C51Config``; ``init``: None (torch's nn.Linear initialisation, ``init_c51_net``) or a net
+    {w0, b0, w1 [A * n_atoms][h1], b1 [A * n_atoms]}.  One update is three HIP launches (five with ``cfg.per``)."""
+
+    _api, _per_api, _slots, _flatten = "c51", "c51_per", _capi.C51_SLOTS, staticmethod(flatten_q)
+
+    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None, rows_per_push=None):
+        env = None if isinstance(env_or_dims, (tuple, list)) else env_or_dims
+        if env is not None and env.continuous:
+            raise ValueError("C51 needs a discrete action space (sumo-jerk-v0 or sumo-accel-v0), not the continuous jerk env")
+        n_obs, A = (env.obs_dim, int(env.action_space["n"])) if env is not None else (int(env_or_dims[0]), int(env_or_dims[1]))
+        self.cfg = cfg if cfg is not None else C51Config(n_obs=n_obs)
+        if not isinstance(self.cfg, C51Config):
+            raise ValueError("cfg must be a C51Config")
+        if self.cfg.n_actions is None:
+            self.cfg.n_actions = A
+        if self.cfg.n_obs != n_obs or self.cfg.n_actions != A:
+            raise ValueError("cfg has n_obs %d and %d actions; the observation has %d entries and there are %d actions" % (self.cfg.n_obs, self.cfg.n_actions, n_obs, A))
+        for name, ok in (("n_actions in 1 ... 256", 1 <= A <= 256), ("n_obs in 1 ... 31", 1 <= n_obs <= 31), ("batch >= 1", self.cfg.batch >= 1),
+                         ("target_period >= 1", self.cfg.target_period >= 1)):
+            if not ok:
+                raise ValueError("C51 needs " + name)
+        self.cfg.check_width()
+        self.action_values = np.array(env.cfg._actions, dtype=np.float64) if env is not None else np.arange(A, dtype=np.float64)
+        self.env_id = getattr(env, "env_id", None)
+        if self.action_values.shape != (A,):
+            raise ValueError("the env's action table has %d entries, its action space %d" % (self.action_values.size, A))
+        import torch
+        self.torch = torch
+        self.ctx = ctx if ctx is not None else (env.ctx if env is not None else _capi.Context(-1))
+        self.seed = int(seed)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.handle = self.ctx.c51_create(self.cfg.to_c(self.seed))
+        self._enable_nstep(env, rows_per_push)
+        if self.cfg.per is not None:
+            self.ctx.c51_per_enable(self.handle, self.cfg.per.to_c())
+        c = self.cfg
+        self._n_out = A * c.n_atoms
+        net = init if init is not None else init_c51_net(c.n_obs, c.h1, A, c.n_atoms, np.random.default_rng(self.seed))
+        self._len = flatten_q(net).size
+        if self._len != (c.n_obs + 1) * c.h1 + (c.h1 + 1) * self._n_out:
+            raise ValueError("the net's tensors do not have the shape %d -> %d -> %d * %d" % (c.n_obs, c.h1, A, c.n_atoms))
+        self.load_state_dict({"params": new_params_dqn(net), "counters": None})
+        self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
+        self._actions = {}
+
+    def _slot(self, i):
+        return unflatten_q(self.ctx.c51_get_params(self.handle, i, self._len), self.cfg.n_obs, self.cfg.h1, self._n_out)
+
+    # -- acting / replay / update: asynchronous ---------------------------------------------------------------------------------------------
+    def act(self, obs, ticks=None, eps=0.0, debug_q=None):
+        """``DQNLearner.act`` on the expected values: int32 [n], the first maximum of E[Z(obs, a)]; ``eps`` > 0 explores as ``dqn_act_host`` says.
+        ``debug_q``: float32 [n][n_actions] device tensor for the expected values."""
+        n = obs.shape[0]
+        out = self._out(n, self.torch.int32)
+        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
+        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (n, self.cfg.n_actions))
+        self.ctx.c51_act(self.handle, n, obs.data_ptr(), obs.stride(0), eps, out.data_ptr(), debug_q.data_ptr() if debug_q is not None else 0, self._stream())
+        return out
+
+    def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
+        """``DQNLearner.push``: one env step into the replay ring."""
+        torch = self.torch
+        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == torch.int32 and reward.dtype == torch.float64 and action.is_contiguous()
+        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
+        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+        self.ctx.c51_push(self.handle, obs.shape[0], obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0, obs.stride(0),
+                          action.data_ptr(), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self._stream())
+
+    def update(self, n=1, lr=None):
+        """``n`` updates; on the device nothing happens until more than cfg.replay_start frames were pushed.  ``lr``: this call's learning rate."""
+        self.ctx.c51_update(self.handle, n, self.cfg.lr if lr is None else lr, self._stream())
+
+    def grads(self):
+        """Debug: the loss's gradient on the current update index's minibatch as a dict of numpy tensors; nothing applied; synchronises."""
+        g = self.torch.empty(self._len, dtype=self.torch.float32, device=self.device)
+        self.ctx.c51_grads(self.handle, g.data_ptr(), self._stream())
+        return unflatten_q(g.cpu().numpy(), self.cfg.n_obs, self.cfg.h1, self._n_out)
+
+    def targets(self):
+        """Debug: float32 [batch][4] = a*, the target net's expected value there, the row loss l, Q(s, a) of the minibatch the next update will
+        draw; synchronises."""
+        out = self.torch.zeros(self.cfg.batch, 4, dtype=self.torch.float32, device=self.device)
+        self.ctx.c51_targets(self.handle, out.data_ptr(), self._stream())
+        return out.cpu().numpy()
+
+    def dist(self):
+        """Debug: (float32 [batch][2][n_atoms] = the projected target distribution m and the online distribution p(s, a); ``targets()``'s array) of
+        the minibatch the next update will draw, from one pass; synchronises."""
+        d = self.torch.zeros(self.cfg.batch, 2, self.cfg.n_atoms, dtype=self.torch.float32, device=self.device)
+        out = self.torch.zeros(self.cfg.batch, 4, dtype=self.torch.float32, device=self.device)
+        self.ctx.c51_dist(self.handle, d.data_ptr(), out.data_ptr(), self._stream())
+        return d.cpu().numpy(), out.cpu().numpy()
+
+    def project(self, p, reward, mask, disc):
+        """Debug: the device's projection of caller-given distributions ``p`` [n][n_atoms] under ``reward``, ``mask``, ``disc`` [n] (numpy in, float32
+        numpy out): the device function the update calls; synchronises."""
+        torch = self.torch
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=self.device)
+        p, reward, mask, disc = t(p), t(reward), t(mask), t(disc)
+        assert p.shape == (reward.numel(), self.cfg.n_atoms) and mask.numel() == disc.numel() == reward.numel()
+        m = torch.zeros_like(p)
+        self.ctx.c51_project(self.handle, p.shape[0], p.data_ptr(), reward.data_ptr(), mask.data_ptr(), disc.data_ptr(), m.data_ptr(), self._stream())
+        return m.cpu().numpy()
+
+    def stats(self):
+        """``stats_device`` as a dict; synchronises."""
+        s = self.stats_device().cpu().numpy()
+        return {"loss": float(s[0]), "mean_q": float(s[1]), "fill": int(s[2]), "updates": int(s[3])}
+
+    def export_q(self, path):
+        """Write the online logits network as an ``.npz``: w0, b0, w1, b1 (float32), ``action_values`` and the head's ``n_atoms``, ``v_min``, ``v_max``."""
+        with open(path, "wb") as fh:
+            np.savez_compressed(fh, **self._slot(0), action_values=self.action_values, n_atoms=np.int64(self.cfg.n_atoms), v_min=np.float64(self.cfg.v_min),
+                                v_max=np.float64(self.cfg.v_max))
+        return path
 
 
 class _TakeoverShare:

@@ -1,0 +1,390 @@
+"""The C51 learner on the GPU (``learner.C51Learner``, csrc/stmpc_c51_kernels.hpp) against its host twins at the shapes of tests/c51_testlib.py,
+(n_obs, h1, A, K, B) = (20, 16, 5, 17, 7), (12, 32, 3, 33, 16), (20, 48, 20, 51, 33), (20, 256, 5, 51, 64).  Rings have at most 256 rows, envs at
+most 64 environments.
+
+Parity rule for float32 results (tests/learner_testlib.py's): per tensor, max-norm error against ``update_host_c51("float64")`` fed the device's own
+minibatch rows at most max(4 x the error of ``update_host_c51("float32")``, 8 float32 ulps).  The projection on dyadic data is exact."""
+import numpy as np
+import pytest
+
+from c51_testlib import (LEARNER_SEED, NAMES, PROBLEM_SEEDS, Q_SLOTS, RING, SHAPES, all_negative_rows, astar_rows, dyadic_projection_case, minibatch_host,
+                         projection_edge_cases, random_problem, rows_of)
+from learner_testlib import FLOOR, bits_equal, check_4x as _check_4x, record as _record
+from stmpc_testlib import capi as _capi
+
+
+def _fill(L, replay, rows=slice(None), chunk=64):
+    import torch
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")
+    rep = {k: v[rows] for k, v in replay.items()}
+    R = rep["s"].shape[0]
+    for o in range(0, R, chunk):
+        sl = slice(o, min(R, o + chunk))
+        term = rep["term"][sl]
+        trunc = rep["trunc"][sl] if "trunc" in rep else np.zeros_like(term)
+        L.push(dev(rep["s"][sl].astype(np.float32)), None, dev(rep["a"][sl].astype(np.int32)), dev(rep["r"][sl].astype(np.float64)),
+               dev(rep["s2"][sl].astype(np.float32)), dev(term), dev(trunc))
+
+
+def _learner(gpu_ctx, cfg, params, replay=None, seed=LEARNER_SEED, **kw):
+    from rl_mpc_lanemerging_amd import learner
+    L = learner.C51Learner((cfg.n_obs, cfg.n_actions), cfg, seed=seed, init=params["q"], ctx=gpu_ctx, **kw)
+    L.load_state_dict({"params": params, "counters": None})
+    if replay is not None:
+        _fill(L, replay)
+    return L
+
+
+def _twins(params, batch, cfg, **kw):
+    from rl_mpc_lanemerging_amd import learner
+    return tuple(learner.update_host_c51(params, batch, cfg, d, grads_only=True, **kw)[1] for d in ("float64", "float32"))
+
+
+# ---- 1: the projection, exact --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [17, 33])
+def test_gpu_projection_is_exact_on_dyadic_data(K, gpu_ctx, restore_settings):
+    """stmpc_c51_project_device on p' in multiples of 2^-10, dyadic rewards and discounts, v_min = -8, v_max = 8 (dz = 1 and 1/2): m equals
+    c51_project_host(float64) value for value and every row sums to exactly 1; the edge cases are present (48 rows: three tiles)."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    cfg, p, r, mask, disc = dyadic_projection_case(K)
+    cases = projection_edge_cases(cfg, r, mask, disc)
+    assert all(cases.values()), cases
+    L = learner.C51Learner((cfg.n_obs, cfg.n_actions), cfg, ctx=gpu_ctx)
+    m = L.project(p, r, mask, disc)
+    want = learner.c51_project_host(p, r, mask, disc, cfg)
+    assert m.dtype == np.float32 and m.shape == want.shape
+    assert np.array_equal(m.astype(np.float64), want), int(np.count_nonzero(m.astype(np.float64) != want))
+    assert (m.astype(np.float64).sum(1) == 1.0).all()
+    # a part of a tile: rows past n are not written
+    m7 = L.project(p[:7], r[:7], mask[:7], disc[:7])
+    assert np.array_equal(m7, m[:7])
+    gpu_ctx.check_error()
+
+
+# ---- 2: distributions, loss, targets ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("double", [True, False])
+@pytest.mark.parametrize("si", range(len(SHAPES)))
+def test_gpu_distributions_loss_and_targets(si, double, gpu_ctx, restore_settings):
+    """dist() (m and p(s, a)) and targets() (a*, Qt(s', a*), l, Q(s, a)) against update_host_c51 fed the device's own minibatch rows, on minibatches
+    where some rows have only negative real expected values at s' (a pad column's would win a careless argmax).  a* is compared where the float64
+    twin's two best expected values differ by more than the parity bound; at most 10 % of the rows are left out."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    shape = SHAPES[si]
+    n_obs, h1, A, K, B = shape
+    cfg, params, replay = random_problem(shape, PROBLEM_SEEDS[si, double], neg_shift=True, double=double)
+    L = _learner(gpu_ctx, cfg, params, replay)
+    rows = L.minibatch()
+    assert L.stats()["fill"] == RING and np.array_equal(rows.view(np.uint32), minibatch_host(replay, cfg)[0].view(np.uint32))
+    batch = learner.dqn_batch_from_rows(rows, n_obs)
+    i64, i32 = _twins(params, batch, cfg)
+    neg = all_negative_rows(i64)
+    assert neg.any() and not neg.all(), int(neg.sum())
+    d, t = L.dist()
+    assert d.dtype == t.dtype == np.float32 and d.shape == (B, 2, K) and t.shape == (B, 4) and np.array_equal(t, L.targets())
+    ratios, tag = {}, "c51 %s %s " % (shape, "double" if double else "plain")
+    ok = _check_4x(tag + "m", d[:, 0], i32["dist"][:, 0], i64["dist"][:, 0], ratios)
+    ok &= _check_4x(tag + "p(s, a)", d[:, 1], i32["dist"][:, 1], i64["dist"][:, 1], ratios)
+    ok &= _check_4x(tag + "Qt(s', a*)", t[:, 1], i32["targets"][:, 1], i64["targets"][:, 1], ratios)
+    ok &= _check_4x(tag + "row loss", t[:, 2], i32["row_loss"], i64["row_loss"], ratios)
+    ok &= _check_4x(tag + "Q(s, a)", t[:, 3], i32["q_values"], i64["q_values"], ratios)
+    keep, left_out = astar_rows(i64, i32)
+    assert left_out <= 0.10
+    assert np.array_equal(t[keep, 0].astype(np.int64), i64["targets"][keep, 0].astype(np.int64)) and t[:, 0].min() >= 0 and t[:, 0].max() < A
+    assert (t[neg, 1] < 0).all() or double                          # (double: the sign seen is the online net's, the value the target's)
+    assert np.abs(d[:, 0].astype(np.float64).sum(1) - 1).max() <= 8 * FLOOR and np.abs(d[:, 1].astype(np.float64).sum(1) - 1).max() <= 8 * FLOOR
+    _record("c51 dist %s %s" % (shape, "double" if double else "plain"), ratios)
+    assert ok
+    st = L.stats()                                                  # the pass left its statistics: the unweighted mean loss and mean Q(s, a)
+    assert abs(st["loss"] - i64["loss"]) <= 1e-5 * abs(i64["loss"]) and abs(st["mean_q"] - i64["mean_q"]) <= 1e-5 * np.abs(i64["q_values"]).max()
+    after = L.state_dict()["params"]
+    assert bits_equal(after, params, Q_SLOTS, NAMES) and after["updates"] == 0
+    gpu_ctx.check_error()
+
+
+# ---- 3: gradients ----------------------------------------------------------------------------------------------------------------------------------
+def _pad_mask(n_obs, h1, n_out):
+    h1p, Ap = (h1 + 15) & ~15, (n_out + 15) & ~15
+    m = {"w0": np.ones((h1p, 32), bool), "b0": np.ones(h1p, bool), "w1": np.ones((Ap, h1p), bool), "b1": np.ones(Ap, bool)}
+    m["w0"][:h1, :n_obs], m["b0"][:h1], m["w1"][:n_out, :h1], m["b1"][:n_out] = False, False, False, False
+    return m
+
+
+def _pads_are_zero(gpu_ctx, L, slots, pad, tag):
+    for slot in slots:
+        arr = gpu_ctx.c51_padded_read(L.handle, slot, L.cfg.h1, L.cfg.n_actions * L.cfg.n_atoms)
+        for k in NAMES:
+            assert arr[k].shape == pad[k].shape and not arr[k][pad[k]].any(), (tag, slot, k, int(np.count_nonzero(arr[k][pad[k]])))
+            assert np.isfinite(arr[k]).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("si", range(len(SHAPES)))
+def test_gpu_gradients(si, gpu_ctx, restore_settings):
+    """All four gradient tensors under the parity rule; the padded gradient's pad rows and columns are exact zeros; dZout is an exact zero outside
+    the stored action's block and on the padded minibatch rows, equals (p - m) / B inside it under the rule, and every row of it sums to zero as
+    well as the float32 twin's does."""
+    capi = _capi()
+    from rl_mpc_lanemerging_amd import learner
+    shape = SHAPES[si]
+    n_obs, h1, A, K, B = shape
+    cfg, params, replay = random_problem(shape, 320 + si)
+    L = _learner(gpu_ctx, cfg, params, replay)
+    rows = L.minibatch()
+    batch = learner.dqn_batch_from_rows(rows, n_obs)
+    i64, i32 = _twins(params, batch, cfg)
+    g = L.grads()
+    ratios, ok = {}, True
+    for k in NAMES:
+        assert g[k].dtype == np.float32 and g[k].shape == i64["grad"][k].shape and np.abs(i64["grad"][k]).max() > 0
+        ok &= _check_4x("c51 %s grad %s" % (shape, k), g[k], i32["grad"][k], i64["grad"][k], ratios)
+    _record("c51 grad %s" % (shape,), ratios)
+    pad = _pad_mask(n_obs, h1, A * K)
+    _pads_are_zero(gpu_ctx, L, [capi.C51_GRAD], pad, "grads")
+    have = gpu_ctx.c51_padded_read(L.handle, capi.C51_GRAD, h1, A * K)
+    assert all(np.array_equal(have[k][~pad[k]].reshape(g[k].shape), g[k]) for k in NAMES)
+    dz = gpu_ctx.c51_dzout_read(L.handle, B, A * K)
+    inside = np.zeros(dz.shape, bool)
+    for r in range(B):
+        inside[r, batch["a"][r] * K:(batch["a"][r] + 1) * K] = True
+    assert not dz[~inside].any() and (np.abs(dz[inside].reshape(B, K)).max(1) > 0).all()
+    blocks = dz[inside].reshape(B, K)
+    want = lambda i: (i["dist"][:, 1] - i["dist"][:, 0]) / i["dist"].dtype.type(B)
+    ok &= _check_4x("c51 %s dZout" % (shape,), blocks, want(i32), want(i64))
+    tol = max(4 * np.abs(want(i32).astype(np.float64).sum(1)).max(), FLOOR * np.abs(want(i64)).max())
+    assert np.abs(blocks.astype(np.float64).sum(1)).max() <= tol, (np.abs(blocks.astype(np.float64).sum(1)).max(), tol)
+    assert ok
+    gpu_ctx.check_error()
+
+
+# ---- 4: Adam and the target copy ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("si", range(len(SHAPES)))
+def test_gpu_adam_and_target_copy(si, gpu_ctx, restore_settings):
+    """Four updates across target_period = 3: after each, weights and moments equal dqn_adam_host fed the device's own gradient, bit for bit, the
+    target is the online net after update 3 and unchanged otherwise, and every pad of the five padded arrays is an exact zero."""
+    capi = _capi()
+    from rl_mpc_lanemerging_amd import learner
+    shape = SHAPES[si]
+    n_obs, h1, A, K, B = shape
+    cfg, params, replay = random_problem(shape, 340 + si, target_period=3)
+    L = _learner(gpu_ctx, cfg, params, replay)
+    pad = _pad_mask(n_obs, h1, A * K)
+    for u in range(4):
+        before = L.state_dict()["params"]
+        g = L.grads()
+        L.update(1)
+        after = L.state_dict()["params"]
+        for k in NAMES:
+            w, m, v, bp = learner.dqn_adam_host(before["q"][k], g[k], before["q_m"][k], before["q_v"][k], before["beta_pow"], cfg.lr, cfg)
+            assert np.array_equal(after["q"][k], w) and np.array_equal(after["q_m"][k], m) and np.array_equal(after["q_v"][k], v), (u, k)
+            assert np.array_equal(after["q_target"][k], after["q"][k] if (u + 1) % 3 == 0 else before["q_target"][k]), (u, k)
+            assert not np.array_equal(after["q"][k], before["q"][k])
+        assert np.array_equal(after["beta_pow"], bp) and after["updates"] == u + 1
+        _pads_are_zero(gpu_ctx, L, range(5), pad, "update %d" % u)
+    st = L.stats()
+    assert st["updates"] == 4 and st["fill"] == RING and np.isfinite(st["loss"]) and st["loss"] > 0
+    gpu_ctx.check_error()
+
+
+# ---- 5: acting -----------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("si", [0, 2, 3])
+def test_gpu_acting(si, gpu_ctx, restore_settings):
+    _capi()
+    import torch
+    from rl_mpc_lanemerging_amd import learner
+    shape = SHAPES[si]
+    n_obs, h1, A, K, B = shape
+    cfg, params, replay = random_problem(shape, 360 + si)
+    L = _learner(gpu_ctx, cfg, params, seed=23)
+    n = 50                                                          # four tiles, the last one partly filled
+    obs = torch.as_tensor(replay["s"][:n].astype(np.float32), device="cuda")
+    q = torch.zeros(n, A, dtype=torch.float32, device="cuda")
+    greedy = L.act(obs, None, eps=0.0, debug_q=q).cpu().numpy().copy()
+    qh = q.cpu().numpy()
+    assert greedy.dtype == np.int32 and np.array_equal(greedy, qh.argmax(1))      # numpy's argmax: the first maximum
+    ev = {}
+    for d in ("float64", "float32"):
+        T = lambda a: torch.tensor(np.asarray(a), dtype=getattr(torch, d))
+        with torch.no_grad():
+            p = torch.softmax(learner._c51_logits({k: T(params["q"][k]) for k in NAMES}, T(replay["s"][:n]), A, K), -1)
+            ev[d] = (p * T(learner.c51_support(cfg))).sum(-1).numpy()
+    assert _check_4x("c51 %s acting E[Z]" % (shape,), qh, ev["float32"], ev["float64"])
+    assert int(gpu_ctx.c51_get_state(L.handle)[0][3]) == 0          # a greedy call is no exploring call
+    call = 0
+    for eps in (0.25, 1.0, 0.25):
+        a = L.act(obs, None, eps=eps).cpu().numpy().copy()
+        explore, idx = learner.dqn_act_host(23, call, n, eps, A)
+        assert np.array_equal(a, np.where(explore, idx, greedy)) and a.min() >= 0 and a.max() < A, (eps, call)
+        assert explore.all() if eps == 1.0 else (explore.any() and not explore.all())
+        call += 1
+        assert int(gpu_ctx.c51_get_state(L.handle)[0][3]) == call
+    assert np.array_equal(L.act(obs, None, eps=0.0).cpu().numpy(), greedy) and int(gpu_ctx.c51_get_state(L.handle)[0][3]) == call
+    # ties: an all-zero last layer makes every distribution uniform and every expected value the same: action 0 everywhere
+    sd = L.state_dict()
+    sd["params"]["q"]["w1"][:] = 0
+    sd["params"]["q"]["b1"][:] = 0
+    L.load_state_dict(sd)
+    assert (L.act(obs, None).cpu().numpy() == 0).all()
+    with pytest.raises(RuntimeError):
+        L.act(obs, None, eps=1.5)
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+def test_gpu_library_refusals(gpu_ctx):
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    good = dict(n_obs=20, n_actions=5, h1=16, batch=7, capacity=64, n_atoms=17)
+    for bad in (dict(n_actions=0), dict(n_actions=257, n_atoms=2), dict(n_obs=32), dict(batch=0), dict(target_period=0), dict(replay_start=64)):
+        with pytest.raises(RuntimeError):
+            gpu_ctx.c51_create(learner.C51Config(**dict(good, **bad)).to_c(0))
+    for field, value in (("n_atoms", 1), ("n_atoms", 205), ("v_max", -10.0), ("reserved", 0)):      # (the library's own checks: the struct set by hand)
+        c = learner.C51Config(**good).to_c(0)
+        setattr(c, field, value)
+        if field == "reserved":
+            gpu_ctx.c51_destroy(gpu_ctx.c51_create(c))
+        else:
+            with pytest.raises(RuntimeError):
+                gpu_ctx.c51_create(c)
+    gpu_ctx.check_error()
+
+
+# ---- 6: combinations -----------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_prioritised_replay(gpu_ctx, restore_settings):
+    """The priorities are per_priority_host of the device's own row losses, the tree equals SumTreeHost's, the importance weights reach the
+    gradient."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    per = learner.PERConfig(beta=0.5, max_priority=16.0)            # (a cross-entropy over 51 atoms is about log 51: the reference's cap of 4 would level them)
+    shape = SHAPES[2]
+    cfg, params, replay = random_problem(shape, 371, per=per)
+    L = _learner(gpu_ctx, cfg, params, replay)
+    host = learner.SumTreeHost(RING, per)
+    host.push(RING)
+    assert np.array_equal(L.priorities(), host.nodes)
+    seen, mixed = set(), 0
+    for u in range(3):
+        tree = L.priorities()
+        idx = learner.per_sample_host(tree, LEARNER_SEED, u, cfg.batch, RING)
+        rows = rows_of(replay, cfg.n_obs)[idx]
+        assert np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
+        before = L.state_dict()["params"]
+        g = L.grads()
+        ls = L.last_sample()
+        assert np.array_equal(ls["idx"], idx) and ls["weight"].max() == 1.0
+        w = ls["weight"]
+        if seen & set(idx.tolist()) and not seen >= set(idx.tolist()):      # rows with a priority of their own next to new ones: the weights differ
+            mixed += 1
+            assert len(set(w.tolist())) > 1
+        seen |= set(idx.tolist())
+        batch = learner.dqn_batch_from_rows(rows, cfg.n_obs)
+        i64, i32 = _twins(before, batch, cfg, weights=w)
+        assert all(_check_4x("c51 per u%d grad %s" % (u, k), g[k], i32["grad"][k], i64["grad"][k]) for k in NAMES)
+        L.update(1)
+        ls = L.last_sample()
+        assert np.array_equal(ls["idx"], idx) and _check_4x("c51 per u%d row loss" % u, ls["td"], i32["row_loss"], i64["row_loss"]) and (ls["td"] > 0).all()
+        pri = learner.per_priority_host(ls["td"], per)
+        for r in range(cfg.batch):
+            host.set(idx[r], pri[r])
+        assert np.array_equal(L.priorities(), host.nodes), u
+    assert mixed >= 1
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("double", [True, False])
+def test_gpu_three_step_returns(double, gpu_ctx, restore_settings):
+    """n_step = 3 on pushes of 8 rows with terminated and truncated rows: the twins are fed nstep_batch_host's window (R, gamma^m, s' and the mask
+    of the window's last row) of the device's own ring; dist(), targets() and the gradients under the parity rule."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    shape = SHAPES[1]
+    n_obs, h1, A, K, B = shape
+    N = 8
+    cfg, params, replay = random_problem(shape, 380, double=double, n_step=3, gamma=0.9)
+    rng = np.random.default_rng(5)
+    replay["trunc"] = (rng.random(RING) < 0.15) & ~replay["term"]
+    L = _learner(gpu_ctx, cfg, params, rows_per_push=N)
+    _fill(L, replay, slice(0, 96), chunk=N)                         # 96 of 128 rows: the newest rows' windows are cut short
+    cn = L.state_dict()["counters"]
+    ring = gpu_ctx.c51_replay_read(L.handle, 0, RING)
+    assert cn[0] == 96 and cn[1] == 96 and ring[:96, 67].any()
+    idx = learner.sample_indices_host(LEARNER_SEED, 0, B, 96)
+    b = learner.nstep_batch_host(ring, idx, cn[0], cn[1], N, 3, cfg.gamma, n_obs, dqn=True)
+    assert len(set(b["m"].tolist())) >= 2 and set(b["m"].tolist()) <= {1, 2, 3} and np.array_equal(L.minibatch().view(np.uint32), b["rows"].view(np.uint32))
+    i64, i32 = _twins(params, b, cfg, disc=b["disc"])
+    d, t = L.dist()
+    g = L.grads()
+    tag = "c51 n=3 %s " % ("double" if double else "plain")
+    ok = _check_4x(tag + "m", d[:, 0], i32["dist"][:, 0], i64["dist"][:, 0]) and _check_4x(tag + "p(s, a)", d[:, 1], i32["dist"][:, 1], i64["dist"][:, 1])
+    ok &= _check_4x(tag + "row loss", t[:, 2], i32["row_loss"], i64["row_loss"])
+    keep, left_out = astar_rows(i64, i32)
+    assert left_out <= 0.10 and np.array_equal(t[keep, 0].astype(np.int64), i64["targets"][keep, 0].astype(np.int64))
+    for k in NAMES:
+        ok &= _check_4x(tag + "grad " + k, g[k], i32["grad"][k], i64["grad"][k])
+    assert ok
+    with pytest.raises(RuntimeError):
+        _fill(L, replay, slice(96, 100), chunk=4)                  # a push of another size is refused
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("per", [False, True])
+def test_gpu_updates_are_reproducible_and_state_round_trips(per, gpu_ctx, restore_settings):
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    kw = dict(per=learner.PERConfig(beta=0.4)) if per else {}
+    cfg, params, replay = random_problem(SHAPES[2], 390, target_period=4, **kw)
+    A_, B_ = _learner(gpu_ctx, cfg, params, replay), _learner(gpu_ctx, cfg, params, replay)
+    A_.update(10)
+    B_.update(4)
+    mid = B_.state_dict()
+    B_.update(6)
+    sa, sb = A_.state_dict(), B_.state_dict()
+    assert bits_equal(sa["params"], sb["params"], Q_SLOTS, NAMES) and np.array_equal(sa["counters"], sb["counters"]) and np.array_equal(sa["params"]["beta_pow"], sb["params"]["beta_pow"])
+    assert A_.stats() == B_.stats() and sa["params"]["updates"] == 10 and not bits_equal(sa["params"], params, ("q",), NAMES)
+    if not per:                                                     # (a tree is not part of a state_dict)
+        C_ = _learner(gpu_ctx, cfg, params, replay)
+        C_.load_state_dict(mid)
+        back = C_.state_dict()
+        assert bits_equal(back["params"], mid["params"], Q_SLOTS, NAMES) and np.array_equal(back["counters"], mid["counters"])
+        C_.update(6)
+        sc = C_.state_dict()
+        assert bits_equal(sa["params"], sc["params"], Q_SLOTS, NAMES) and np.array_equal(sa["counters"], sc["counters"]) and C_.stats() == A_.stats()
+    gpu_ctx.check_error()
+
+
+# ---- 7: the training loop ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_id,A,shield", [("sumo-jerk-v0", 5, None), ("sumo-accel-v0", 20, None), ("sumo-jerk-v0", 5, "first_step")])
+def test_gpu_train_dqn_takes_a_c51_learner(env_id, A, shield, gpu_ctx, restore_settings, tmp_path):
+    _capi()
+    import rl_mpc_lanemerging_amd as pkg
+    from rl_mpc_lanemerging_amd import learner, vec_env
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    kw = dict(shield=shield) if shield else {}
+    env = vec_env.MergeVecEnv(64, env_id=env_id, seed=2, ctx=gpu_ctx, **kw)
+    cfg = learner.C51Config(n_obs=env.obs_dim, h1=32, batch=50, capacity=256, replay_start=100, target_period=5, n_atoms=51 if A == 5 else 21,
+                            per=learner.PERConfig() if A == 5 else None)
+    L = learner.C51Learner(env, cfg, seed=6)
+    first = L.state_dict()["params"]
+    res = learner.train_dqn(env, L, 640, updates_per_step=2, drain_every=4, eps_schedule=lambda i, n: 0.5)
+    env.check_error()
+    st, sd = L.stats(), L.state_dict()
+    assert res["steps"] == 10 and res["frames"] == 640 and set(res) == {"steps", "frames", "episodes", "mean_return", "returns", "takeover_share"}
+    assert st["updates"] == 2 * 9 and st["fill"] == 256 and np.isfinite(st["loss"]) and st["loss"] > 0      # updates start once MORE than 100 frames were pushed
+    assert sd["counters"][4] == 640 and sd["counters"][3] == 10 and sd["params"]["updates"] == 18
+    assert all(np.isfinite(sd["params"][s][k]).all() for s in Q_SLOTS for k in NAMES)
+    assert not np.array_equal(sd["params"]["q"]["w1"], first["q"]["w1"]) and not np.array_equal(sd["params"]["q"]["b1"], first["q"]["b1"])
+    assert (res["takeover_share"] >= 0.0) if shield else (res["takeover_share"] == 0.0)
+    path = L.export_q(str(tmp_path / "c51.npz"))
+    with np.load(path) as z:
+        assert all(np.array_equal(z[k], sd["params"]["q"][k]) for k in NAMES) and np.array_equal(z["action_values"], L.action_values)
+        assert (int(z["n_atoms"]), float(z["v_min"]), float(z["v_max"])) == (cfg.n_atoms, -10.0, 10.0) and z["w1"].shape == (A * cfg.n_atoms, 32)
+    gpu_ctx.check_error()
