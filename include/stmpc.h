@@ -23,6 +23,7 @@
  *   stmpc_actor_view_ddpg     <- the closing `evaluate` of ddpg.train_ddpg_all_with_lr_drop (the model just trained, evaluated where it lies)
  *   stmpc_qactor_eval_device  <- DQNAgent.get_control                 dqn.py:375-380 (state vector + Q-network + argmax + JERK_VALUES_DQN[a], one launch)
  *   stmpc_pop_qactor_*        <- DQNAgent.get_control for several models  dqn.py:375-380, one launch
+ *   stmpc_c51actor_*          <- DQNAgent.get_control's job for RainbowAgent's categorical head  dqn.py:375-380, rainbow.py, one launch
  *   stmpc_actor_pop_*         <- DDPGAgent.load + get_control for several MODEL_NAMEs (ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json), one launch
  *   stmpc_env_*               <- merge_gym.JerkEnv / ContinuousJerkEnv / AccelerationEnv  merge_gym.py:15-221 with the rewards of
  *                                dqn.get_reward_function (dqn.py:449-563, rl.py:168-174), batched on the SUMO-free world (stmpc_sim_*)
@@ -1086,6 +1087,32 @@ int  stmpc_qactor_eval_device(stmpc_ctx *ctx, const stmpc_qactor *qactor, const 
                               const double *d_cur_other_a, float *d_feat, int feat_stride, int32_t *d_action, float *d_q, double *d_jerk, void *stream);
 
 /*
+ * A categorical (C51) network as such a policy: DQNAgent.get_control's job (dqn.py:375-380) for the distributional head of the reference's third
+ * agent (rainbow.py: RainbowAgent) -- state vector -> logits -> E[Z(s, a)] of every action -> first maximum -> the action table -- for N states in
+ * ONE launch.  (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8; no entry above changes what it
+ * computes.)  A C51 policy IS a stmpc_qactor, with a categorical head: stmpc_qactor_eval_device, stmpc_qactor_set_limits, stmpc_qactor_destroy and
+ * the lone policy of stmpc_qshield_env_reset_device / _step_device take it as they take a Q-network's, and d_q is then the expected values,
+ * float32 [N][n_actions].  The forward pass and the argmax are stmpc_c51_act_device's own code on the same packed operands: the expected values,
+ * the index and the jerk are the bits that entry gives (eps = 0, d_debug_q) on the input vectors stmpc_policy_features_device writes with
+ * time_feature = 0.  (The two entries are not named stmpc_qactor_...: that prefix and stmpc_c51_... are closed sets.)
+ *   stmpc_c51actor_create   (dqn.py:375-380 with RainbowAgent.load's network, rainbow.py) from HOST row-major tensors as C51Learner.export_q writes
+ *                   them: w0 [h1][n_in], b0 [h1], w1 [n_actions * n_atoms][h1], b1 [n_actions * n_atoms] (action a's logits are rows a * n_atoms
+ *                   ...), the support's n_atoms, v_min, v_max, and the action table.  The tensors go through the C51 learner's own network
+ *                   builder, slot layout and re-packing kernel: bit-identical to a stmpc_c51 loaded with them; dz = (v_max - v_min) / (n_atoms - 1)
+ *                   in fp64 as that learner forms it.  STMPC_EINVAL for everything stmpc_qactor_create refuses, n_atoms < 2, n_actions * n_atoms >
+ *                   STMPC_C51_MAX_LOGITS, a support that is not finite or v_max <= v_min, a network too wide for one workgroup's LDS.  Synchronises
+ *   stmpc_c51actor_view     (dqn.py:375-380 on the agent being trained, rainbow.py) a BORROWED policy whose network ALIASES the C51 learner's online
+ *                   (target = 0) or target (target = 1) logits network, with stmpc_qactor_view_dqn's rules: no copy, an evaluation ordered after
+ *                   an update on the same stream sees the update, it owns its action table alone, destroy it before the learner.  Evaluating reads
+ *                   the network, the shape and the support only: no counter, ticket or workspace of the learner is touched.  STMPC_EINVAL for a
+ *                   NULL argument, target not 0 or 1, n_actions different from the learner's, a bad mode or table
+ * stmpc_pop_qactor_create refuses a categorical member (STMPC_EINVAL): a population of C51 policies does not exist, one launch needs one head.
+ */
+int  stmpc_c51actor_create(stmpc_ctx *ctx, int n_in, int h1, int n_actions, int n_atoms, double v_min, double v_max, const float *w0, const float *b0,
+                           const float *w1, const float *b1, const double *action_values, int mode, stmpc_qactor **out);
+int  stmpc_c51actor_view(stmpc_c51 *learner, int target, const double *action_values, int n_actions, int mode, stmpc_qactor **out);
+
+/*
  * A population of Q-networks as policies, evaluated in one launch: what stmpc_actor_pop_* is for DDPG actors, for the Q-actors above.  The reference
  * compares its DQN agents run by run (double against plain targets, clipped against unclipped, the freeze period, prioritised against uniform replay,
  * seeds, traffic types), one DQNAgent.get_control (dqn.py:375-380) evaluation process per model.  (Additive: new entries only, no signature or struct
@@ -1542,7 +1569,7 @@ int stmpc_cshield_env_evals_device(stmpc_ctx *ctx, int N, int32_t *d_evals, void
  * running environment; running or not, the row commands its current speed and its first_action is 0.0.
  * A Q-network has no time feature, so there is no rollout time counter, no rollout_time and no *_evals_device entry.
  * The policy is EITHER qactor (created, or a stmpc_qactor_view_dqn view: a step queued after stmpc_dqn_update_device rolls out with the updated
- * weights) on all N rows with qactor_pop NULL and n_per_member 0, OR qactor_pop with qactor NULL, member m on rows [m * n_per_member, (m + 1) *
+ * weights; or a categorical one, stmpc_c51actor_create / stmpc_c51actor_view, likewise after stmpc_c51_update_device) on all N rows with qactor_pop NULL and n_per_member 0, OR qactor_pop with qactor NULL, member m on rows [m * n_per_member, (m + 1) *
  * n_per_member) and P * n_per_member == N.
  *   stmpc_qshield_env_reset_device   stmpc_env_reset_device + every buffer of the step, sized here: the step allocates none.  STMPC_EINVAL (before
  *                       anything changes) for STMPC_ENV_CONTINUOUS_JERK (use stmpc_cshield_env_*), cc.remember_last_choice != 0, kmax outside 1 ...

@@ -24,7 +24,8 @@ reference checkout -- parity unpinned for those two steps, and the suite's ``tes
 ``DQNActor`` is the same for the reference's second agent, ``DQNAgent.get_control`` (dqn.py:375-380): state vector (no time feature) -> Q ->
 ``argmax`` -> the action table, one launch (``k_qactor_eval``), from a ``learner.DQNLearner`` where it lies or from its exported file.
 ``QActorPopulation`` is ``ActorPopulation`` for such policies (``k_qactor_eval_pop``: P Q-networks, one launch), and ``population_of`` picks
-between the two from the members' kind.
+between the two from the members' kind.  ``C51Actor`` is ``DQNActor`` for a ``learner.C51Learner``'s categorical network (``k_c51actor_eval``: the
+expected values of the return distributions in Q's place); it is evaluated alone, no population takes it.
 """
 import os
 
@@ -312,6 +313,8 @@ class DQNActor:
 
     def __init__(self, source, n, ctx, S, mode="jerk", action_values=None):
         with np.load(os.fspath(source)) as z:
+            if "n_atoms" in z.files:
+                raise ValueError("%s holds a categorical (C51) network (it has n_atoms): load it with C51Actor" % os.fspath(source))
             net = {k: np.array(z[k], dtype=np.float32) for k in ("w0", "b0", "w1", "b1")}
             table = np.array(z["action_values"], dtype=np.float64) if action_values is None else action_values
         self._setup(n, ctx, S, mode, table, (int(net["w0"].shape[1]), int(net["w0"].shape[0]), int(net["w1"].shape[0])))
@@ -326,6 +329,12 @@ class DQNActor:
         stream sees the update.  The table is ``learner.action_values``; ``mode`` defaults to the kind of env the learner was built from
         ("acceleration" for sumo-accel-v0, else -- and without an env -- "jerk").  Evaluating changes nothing of the learner's.  The view holds
         the learner, so the learner cannot be collected first."""
+        if _is_c51_learner(learner):
+            raise ValueError("%r is a C51Learner: its handle is no DQN learner's; build the view with C51Actor.from_learner" % (learner,))
+        return cls._view(learner, n, ctx, S, target, mode, lambda self: ctx.qactor_view_dqn(learner.handle, self.action_values, self.target, _capi.QACTOR_MODES[self.mode]))
+
+    @classmethod
+    def _view(cls, learner, n, ctx, S, target, mode, make_handle):
         self = cls.__new__(cls)
         if mode is None:
             mode = "acceleration" if getattr(learner, "env_id", None) == "sumo-accel-v0" else "jerk"
@@ -333,7 +342,7 @@ class DQNActor:
         self._setup(n, ctx, S, mode, learner.action_values, (c.n_obs, c.h1, c.n_actions))
         self.learner, self.target = learner, bool(target)
         self.name = "view of %r (%s network)" % (learner, "target" if target else "online")
-        self.handle = ctx.qactor_view_dqn(learner.handle, self.action_values, self.target, _capi.QACTOR_MODES[self.mode])
+        self.handle = make_handle(self)
         self._limits(S)
         return self
 
@@ -387,8 +396,73 @@ class DQNActor:
         return self.jerk
 
 
+class C51Actor(DQNActor):
+    """``DQNActor`` for a categorical (C51) network -- the distributional head of the reference's third agent (rainbow.py) doing
+    ``DQNAgent.get_control``'s job (dqn.py:375-380): state vector -> logits -> E[Z(s, a)] of every action -> first maximum -> the action table, for
+    ``n`` states in ONE launch (``k_c51actor_eval``, csrc/stmpc_c51actor_kernels.hpp).  A subclass: whatever takes a ``DQNActor`` --
+    ``combined.decide_batch_device``, ``episodes.EpisodeRunner``, ``learner.evaluate_dqn``, ``vec_env.QCombinedShieldVecEnv`` -- takes it.
+
+    ``source``: a file written by ``learner.C51Learner.export_q`` (w0, b0, w1 [A * n_atoms][h1], b1, action_values, n_atoms, v_min, v_max).
+    ``.shape`` is (n_in, h1, A); ``.n_atoms``, ``.v_min``, ``.v_max`` the head's support; ``.q`` (with ``keep_q``) holds the expected values,
+    float32 [n][A].  ``mode``, the call, ``reset``, ``keep_features`` and ``keep_q`` are ``DQNActor``'s.  The expected values, the index and the jerk
+    are bit for bit what ``C51Learner.act`` gives on the same input vectors; ``c51_policy_host`` is the host twin.  There is no population of C51
+    policies: ``QActorPopulation`` refuses one."""
+
+    def __init__(self, source, n, ctx, S, mode="jerk", action_values=None):
+        with np.load(os.fspath(source)) as z:
+            if "n_atoms" not in z.files:
+                raise ValueError("%s has no n_atoms: it is not a C51Learner.export_q file (a DQNLearner's file goes to DQNActor)" % os.fspath(source))
+            net = {k: np.array(z[k], dtype=np.float32) for k in ("w0", "b0", "w1", "b1")}
+            table = np.array(z["action_values"], dtype=np.float64) if action_values is None else action_values
+            self.n_atoms, self.v_min, self.v_max = int(z["n_atoms"]), float(z["v_min"]), float(z["v_max"])
+        A, rest = divmod(int(net["w1"].shape[0]), self.n_atoms) if self.n_atoms >= 1 else (0, 1)
+        if rest or A < 1:
+            raise ValueError("the last layer has %d rows, no multiple of n_atoms = %d" % (net["w1"].shape[0], self.n_atoms))
+        self._setup(n, ctx, S, mode, table, (int(net["w0"].shape[1]), int(net["w0"].shape[0]), A))
+        self.name, self.learner, self.target = os.fspath(source), None, False
+        self.handle = ctx.c51actor_create(net, self.action_values, self.n_atoms, self.v_min, self.v_max, _capi.QACTOR_MODES[self.mode])
+        self._limits(S)
+
+    @classmethod
+    def from_learner(cls, learner, n, ctx, S, target=False, mode=None):
+        """``DQNActor.from_learner`` for a ``learner.C51Learner``: a zero-copy VIEW of its online (``target=True``: target) logits network
+        (``stmpc_c51actor_view``), live across updates on the same stream; evaluating changes nothing of the learner's."""
+        if not _is_c51_learner(learner):
+            raise ValueError("%r is no C51Learner (DQNActor.from_learner views a DQNLearner)" % (learner,))
+        c = learner.cfg
+
+        def make_handle(self):
+            self.n_atoms, self.v_min, self.v_max = int(c.n_atoms), float(c.v_min), float(c.v_max)
+            return ctx.c51actor_view(learner.handle, self.action_values, self.target, _capi.QACTOR_MODES[self.mode])
+        return cls._view(learner, n, ctx, S, target, mode, make_handle)
+
+
+def _is_c51_learner(item):
+    return hasattr(item, "handle") and hasattr(getattr(item, "cfg", None), "n_atoms")      # a learner.C51Learner: its handle is a stmpc_c51's
+
+
 def _is_dqn_learner(item):
-    return hasattr(item, "export_q") and hasattr(item, "handle")      # a learner.DQNLearner (learner.py imports this module)
+    # a learner.DQNLearner (learner.py imports this module); a C51Learner has the same methods, and a handle of another type
+    return hasattr(item, "export_q") and hasattr(item, "handle") and not _is_c51_learner(item)
+
+
+def _is_c51_file(item):
+    if not isinstance(item, (str, os.PathLike)) or not os.path.isfile(os.fspath(item)):
+        return False
+    try:
+        with np.load(os.fspath(item)) as z:
+            return "n_atoms" in getattr(z, "files", ())
+    except Exception:
+        return False
+
+
+def refuse_c51_members(items, who):
+    """ValueError if a member of ``items`` is a C51 policy (a ``C51Actor``, a ``learner.C51Learner``, a ``C51Learner.export_q`` file): one launch of a
+    population needs one head.  Reads the items alone: nothing is built and the library is not called."""
+    bad = [m for m, item in enumerate(items) if isinstance(item, C51Actor) or _is_c51_learner(item) or _is_c51_file(item)]
+    if bad:
+        raise ValueError("%s: members %s are categorical (C51) policies, and a population of C51 policies does not exist (one launch needs one head); "
+                         "evaluate a C51 policy alone, with learner.evaluate_dqn or a C51Actor" % (who, ", ".join(map(str, bad))))
 
 
 def _is_q_member(item):
@@ -413,6 +487,7 @@ class QActorPopulation:
         if hasattr(members, "member") and hasattr(members, "P"):                 # a learner.DQNPopulation
             members = [members.member(m) for m in range(members.P)]
         members = list(members)
+        refuse_c51_members(members, "QActorPopulation")
         if not 1 <= len(members) <= _capi.DDPG_POP_MAX:
             raise ValueError("a population has 1 ... %d members, not %d" % (_capi.DDPG_POP_MAX, len(members)))
         self.P, self.n_per_member = len(members), int(n_per_member)
@@ -483,6 +558,7 @@ def population_of(members, n_per_member, ctx, S, **kw):
     if hasattr(members, "member") and hasattr(members, "P"):
         items = [members.member(m) for m in range(members.P)]
     items = list(items)
+    refuse_c51_members(items, "population_of")
     q = [_is_q_member(item) for item in items]
     if items and all(q):
         return QActorPopulation(items, n_per_member, ctx, S)
@@ -503,12 +579,43 @@ def q_policy_host(net, feat, action_values, mode, ego_acc=None, S=Settings, dtyp
     table = np.asarray(action_values, dtype=np.float64).reshape(-1)
     if table.size != q.shape[1]:
         raise ValueError("the action table has %d entries, the network %d actions" % (table.size, q.shape[1]))
+    idx, jerk = _first_maximum_jerk(q, table, mode, ego_acc, S)
+    return q, idx, jerk
+
+
+def _first_maximum_jerk(q, table, mode, ego_acc, S):
+    """What ``q_policy_host`` and ``c51_policy_host`` share: the first maximum's index of every row of ``q`` and the jerk it stands for."""
     idx = np.argmax(q, axis=1)                                      # (numpy's argmax returns the first maximum, like torch's)
     jerk = table[idx]
     if mode == "acceleration":
         if ego_acc is None:
             raise ValueError("acceleration mode needs the states' ego accelerations (ego_acc)")
         jerk = np.clip((jerk - np.asarray(ego_acc, dtype=np.float64)) / float(S.TICK_LENGTH), float(S.MINIMUM_NEGATIVE_JERK), float(S.MAXIMUM_POSITIVE_JERK))
+    return idx, jerk
+
+
+def c51_policy_host(net, feat, action_values, mode, n_atoms, v_min, v_max, ego_acc=None, S=Settings, dtype=np.float64):
+    """The host twin of ``C51Actor`` in numpy (CPU suite), for input vectors ``feat`` [n][n_in] and a net {w0, b0, w1 [A * n_atoms][h1], b1}: (the
+    expected values E[Z(s, a)] [n][A] in ``dtype``, the first maximum's index int64 [n], the jerk fp64 [n]).  Action a's logits are the outputs
+    a * n_atoms ... (a + 1) * n_atoms - 1; their softmax (the maximum subtracted) weights the support ``learner.c51_support`` forms.  ``mode``,
+    ``ego_acc`` and ``S`` are ``q_policy_host``'s, and so is the acceleration rule."""
+    import types
+    from .learner import c51_support                                # (learner.py imports this module)
+    if mode not in _capi.QACTOR_MODES:
+        raise ValueError("mode must be one of %s, not %r" % (", ".join(map(repr, _capi.QACTOR_MODES)), mode))
+    n_atoms = int(n_atoms)
+    if n_atoms < 2 or not (np.isfinite(v_min) and np.isfinite(v_max) and v_max > v_min):
+        raise ValueError("C51 needs n_atoms >= 2 and a finite support with v_max > v_min")
+    f = lambda a: np.asarray(a, dtype=dtype)
+    logits = np.maximum(f(feat) @ f(net["w0"]).T + f(net["b0"]), 0) @ f(net["w1"]).T + f(net["b1"])
+    table = np.asarray(action_values, dtype=np.float64).reshape(-1)
+    if table.size * n_atoms != logits.shape[1]:
+        raise ValueError("the action table has %d entries, the network %d outputs = %g actions of %d atoms" % (table.size, logits.shape[1], logits.shape[1] / n_atoms, n_atoms))
+    z = c51_support(types.SimpleNamespace(n_atoms=n_atoms, v_min=float(v_min), v_max=float(v_max)), dtype)
+    x = logits.reshape(logits.shape[0], table.size, n_atoms)
+    w = np.exp(x - x.max(axis=2, keepdims=True))
+    q = (w * z).sum(axis=2) / w.sum(axis=2)
+    idx, jerk = _first_maximum_jerk(q, table, mode, ego_acc, S)
     return q, idx, jerk
 
 

@@ -18,6 +18,7 @@
 #include "stmpc_dqn_pop_kernels.hpp"
 #include "stmpc_c51_kernels.hpp"
 #include "stmpc_qactor_kernels.hpp"
+#include "stmpc_c51actor_kernels.hpp"
 #include "stmpc_qactor_pop_kernels.hpp"
 #include <initializer_list>
 #include <utility>
@@ -1700,6 +1701,10 @@ int stmpc_pop_dqn_replay_read(stmpc_dqn *t, int64_t first, int64_t count, float 
 struct stmpc_qactor {
     int device = 0;
     const stmpc_dqn *learner = nullptr;     // a view (stmpc_qactor_view_dqn): the network is the learner's, read through its struct at every evaluation
+    const stmpc_c51 *c51 = nullptr;         // a view of a categorical learner (stmpc_c51actor_view): likewise, through its C51Dev
+    bool categorical = false;               // a categorical head (stmpc_c51actor_create / _view): k_c51actor_eval evaluates it; `dev`'s output width is A * K
+    int K = 0;                              // a created categorical actor's head: atoms and support (a view reads its learner's)
+    double v_min = 0, v_max = 0, dz = 0;
     int target = 0, mode = 0, n_in = 0, A = 0;
     bool limits = false;                    // stmpc_qactor_set_limits was called
     double tick = 0, jerk_min = 0, jerk_max = 0;
@@ -1714,6 +1719,17 @@ int qactor_raise_lds(int device, size_t lds) {
     static LdsCeiling ceiling;
     return raise_dynamic_lds((const void *)k_qactor_eval, "k_qactor_eval", ceiling, device, lds);
 }
+int c51actor_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling;
+    return raise_dynamic_lds((const void *)k_c51actor_eval, "k_c51actor_eval", ceiling, device, lds);
+}
+// the struct k_c51actor_eval gets for a categorical actor
+C51Dev c51actor_dev(const stmpc_qactor *q) {
+    if (q->c51) return q->c51->dev;
+    C51Dev D{};
+    D.dq = q->dev; D.K = q->K; D.v_min = q->v_min; D.v_max = q->v_max; D.dz = q->dz;
+    return D;
+}
 // what create and view share: the mode, the table (checked, then uploaded into q), the kernel's dynamic LDS
 int qactor_check_table(const double *action_values, int n_actions, int A, int mode) {
     if (mode != STMPC_QACTOR_JERK && mode != STMPC_QACTOR_ACCELERATION) return fail(STMPC_EINVAL, "mode must be STMPC_QACTOR_JERK or STMPC_QACTOR_ACCELERATION");
@@ -1725,7 +1741,7 @@ int qactor_check_table(const double *action_values, int n_actions, int A, int mo
 int qactor_finish(stmpc_qactor *q, const double *action_values, stmpc_qactor **out) {
     q->table_h.assign(action_values, action_values + q->A);
     int rc = upload(q->table, action_values, (size_t)q->A);
-    if (!rc) rc = qactor_raise_lds(q->device, q->lds);
+    if (!rc) rc = q->categorical ? c51actor_raise_lds(q->device, q->lds) : qactor_raise_lds(q->device, q->lds);
     if (rc) { stmpc_qactor_destroy(q); return rc; }
     *out = q;
     return STMPC_OK;
@@ -1781,6 +1797,60 @@ int stmpc_qactor_view_dqn(stmpc_dqn *t, int target, const double *action_values,
     return qactor_finish(q, action_values, out);
 }
 
+int stmpc_c51actor_create(stmpc_ctx *c, int n_in, int h1, int n_actions, int n_atoms, double v_min, double v_max, const float *w0, const float *b0,
+                          const float *w1, const float *b1, const double *action_values, int mode, stmpc_qactor **out) {
+    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (!w0 || !b0 || !w1 || !b1 || !action_values) return fail(STMPC_EINVAL, "NULL weight or table pointer");
+    if (n_actions < 1 || n_actions > STMPC_ENV_MAX_ACTIONS) return fail(STMPC_EINVAL, "n_actions must be in 1 ... " + std::to_string(STMPC_ENV_MAX_ACTIONS));
+    if (n_in < 1 || n_in > AT_KIN - 1 || h1 < 1 || h1 > 1024) return fail(STMPC_EINVAL, "C51 network shape out of range (n_in <= 31, hidden width <= 1024)");
+    if (n_atoms < 2) return fail(STMPC_EINVAL, "n_atoms must be at least 2");
+    if ((long long)n_actions * n_atoms > STMPC_C51_MAX_LOGITS)
+        return fail(STMPC_EINVAL, "n_actions * n_atoms = " + std::to_string((long long)n_actions * n_atoms) + " exceeds " + std::to_string(STMPC_C51_MAX_LOGITS));
+    if (!std::isfinite(v_min) || !std::isfinite(v_max) || !(v_max > v_min)) return fail(STMPC_EINVAL, "the support needs finite v_min < v_max");
+    TRY(qactor_check_table(action_values, n_actions, n_actions, mode));
+    HIPCHK(hipSetDevice(c->device));
+    const int AK = n_actions * n_atoms, h1p = (h1 + 15) & ~15, Ap = (AK + 15) & ~15;
+    const size_t lds = ddpg_tile_bytes(h1p, Ap);
+    if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, "C51 network too wide for one workgroup's LDS");
+    stmpc_qactor *q = new stmpc_qactor();
+    q->device = c->device; q->mode = mode; q->n_in = n_in; q->A = n_actions; q->lds = lds; q->categorical = true;
+    q->K = n_atoms; q->v_min = v_min; q->v_max = v_max; q->dz = (v_max - v_min) / (double)(n_atoms - 1);
+    // the C51 learner's own path: net_build's buffers, the slot's segments into the padded layout with A K output rows, k_c51_adam's re-packing
+    DdpgDev &d = q->dev.base;
+    d.n_obs = n_in; d.h1 = h1; d.h2 = AK; d.h1p = h1p; d.h2p = Ap;
+    q->dev.A = n_actions; q->dev.Ap = Ap; q->dev.target_period = 1;
+    int rc = net_build(q->net, d.q, n_in, h1p, Ap);
+    if (!rc) rc = ddpg_zero(q->cnt, DG_NCNT * sizeof(long long));
+    if (!rc) {
+        d.cnt = q->cnt.as<long long>();
+        const std::vector<Seg> lay = slot_layout(n_in, h1, AK, h1p, Ap, false);
+        std::vector<float> flat;
+        flat.insert(flat.end(), w0, w0 + (size_t)h1 * n_in);
+        flat.insert(flat.end(), b0, b0 + h1);
+        flat.insert(flat.end(), w1, w1 + (size_t)AK * h1);
+        flat.insert(flat.end(), b1, b1 + AK);
+        const int ablocks = make_grid(16, h1p, Ap, false).ablocks;
+        const C51Dev D = c51actor_dev(q);
+        rc = slot_set(c->device, lay, (size_t)dg_nparam(h1p, Ap), d.q.w, flat.data(), (int64_t)flat.size(), true,
+                      [&] { hipLaunchKernelGGL(k_c51_adam, dim3(ablocks), dim3(256), 0, (hipStream_t)0, D, 0.f, 1, 1); });
+    }
+    if (rc) { stmpc_qactor_destroy(q); return rc; }
+    return qactor_finish(q, action_values, out);
+}
+
+int stmpc_c51actor_view(stmpc_c51 *t, int target, const double *action_values, int n_actions, int mode, stmpc_qactor **out) {
+    if (!t || !action_values || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (target != 0 && target != 1) return fail(STMPC_EINVAL, "target must be 0 (online network) or 1 (target network)");
+    TRY(qactor_check_table(action_values, n_actions, t->cfg.n_actions, mode));
+    HIPCHK(hipSetDevice(t->rp.device));
+    stmpc_qactor *q = new stmpc_qactor();   // owns its table alone: destroying it frees nothing of the learner's
+    q->device = t->rp.device; q->c51 = t; q->categorical = true; q->target = target; q->mode = mode; q->n_in = t->cfg.n_obs; q->A = t->cfg.n_actions;
+    q->lds = ddpg_tile_bytes(t->h1p, t->Ap);     // (the learner's own LDS has the m tile behind it, which an evaluation does not need)
+    return qactor_finish(q, action_values, out);
+}
+
 void stmpc_qactor_destroy(stmpc_qactor *q) {
     if (!q) return;
     (void)hipSetDevice(q->device);
@@ -1819,8 +1889,12 @@ int qactor_eval_run(stmpc_ctx *c, const stmpc_qactor *q, const FeatCfg &fc, int 
     TRY(rollout_live(c, N, step, &live));
     HIPCHK(hipSetDevice(c->device));
     QActorOut o{q->table.as<double>(), q->tick, q->jerk_min, q->jerk_max, q->mode == STMPC_QACTOR_ACCELERATION, feat_stride, d_feat, d_action, d_q, d_jerk};
-    hipLaunchKernelGGL(k_qactor_eval, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), q->lds, (hipStream_t)stream, fc, q->learner ? q->learner->dev : q->dev,
-                       q->learner ? q->target : 0, N, Kmax, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, o);
+    if (q->categorical)
+        hipLaunchKernelGGL(k_c51actor_eval, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), q->lds, (hipStream_t)stream, fc, c51actor_dev(q), q->c51 ? q->target : 0, N,
+                           Kmax, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, o);
+    else
+        hipLaunchKernelGGL(k_qactor_eval, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), q->lds, (hipStream_t)stream, fc, q->learner ? q->learner->dev : q->dev,
+                           q->learner ? q->target : 0, N, Kmax, d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, o);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
@@ -1860,6 +1934,9 @@ int stmpc_pop_qactor_create(stmpc_ctx *c, const stmpc_qactor *const *qactors, in
         const stmpc_qactor *q = qactors[m];
         if (!q) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " is NULL");
         if (q->device != c->device) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " and the context are on different devices");
+        if (q->categorical)
+            return fail(STMPC_EINVAL, "member " + std::to_string(m) + " has a categorical (C51) head: a population evaluates Q-networks, one launch needs one head; "
+                                      "evaluate a C51 policy alone (stmpc_qactor_eval_device)");
         const DqnDev &d = qactor_dev(q), &d0 = qactor_dev(qactors[0]);
         if (q->n_in != qactors[0]->n_in || d.base.h1p != d0.base.h1p || d.Ap != d0.Ap || q->A != qactors[0]->A)
             return fail(STMPC_EINVAL, "the members of a population share n_in, the padded widths and n_actions (member " + std::to_string(m) + " differs from member 0)");

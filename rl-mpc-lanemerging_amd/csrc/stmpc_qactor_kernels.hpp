@@ -32,6 +32,17 @@ struct QActorOut {                  // what one evaluation writes; rows at or be
     double *jerk;                   // [N]
 };
 
+// The jerk that index a stands for on the state of global row e: the table's entry, or acceleration mode's rule on it (fp64).  Shared with
+// k_c51actor_eval (stmpc_c51actor_kernels.hpp)
+__device__ __forceinline__ double qactor_jerk(const QActorOut &o, int a, const double *__restrict__ ego4, int e) {
+    double v = o.table[a];
+    if (o.accel) {
+        v = (v - ego4[(size_t)e * 4 + 3]) / o.tick;
+        v = v < o.jerk_min ? o.jerk_min : (v > o.jerk_max ? o.jerk_max : v);
+    }
+    return v;
+}
+
 // The evaluation of rows [row0 + 16 blockIdx.x, + 16) with the network of D, as far as row0 + n_rows: row0 = 0 and n_rows = N for a lone actor; a
 // member of a population has its slice's first row and length here.  The state arrays, live and the outputs of o are indexed by the global row.
 // D: the learner's struct (a view) or one with base.q, base.n_obs, base.h1p, A and Ap alone (a created actor, a population's member); neither the
@@ -54,12 +65,7 @@ __device__ __forceinline__ void qactor_eval_body(const FeatCfg &f, const DqnDev 
     if (l >= n_rows) return;
     if (o.q) for (int j = part; j < D.A; j += 32) o.q[(size_t)e * D.A + j] = T.H2[(size_t)row * T.h2_ld + j];
     if (part != 0) return;
-    double v = o.table[a];
-    if (o.accel) {
-        v = (v - ego4[(size_t)e * 4 + 3]) / o.tick;
-        v = v < o.jerk_min ? o.jerk_min : (v > o.jerk_max ? o.jerk_max : v);
-    }
-    o.jerk[e] = v;
+    o.jerk[e] = qactor_jerk(o, a, ego4, e);
     if (o.action) o.action[e] = a;
 }
 

@@ -1820,6 +1820,8 @@ def evaluate_dqn_members(source, n_per_member, seed=0, kmax=16, max_episode_leng
     if controller not in ("combined", "first_step"):
         raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
     members = source if isinstance(source, (DQNPopulation, list, tuple)) else [source]
+    if not isinstance(members, DQNPopulation):
+        _actor.refuse_c51_members(members, "evaluate_dqn_members")      # (before a context exists: a C51 policy is evaluated alone, by evaluate_dqn)
     P = members.P if isinstance(members, DQNPopulation) else len(members)
     if traffic is not None and len(traffic) != P:
         raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), P))
@@ -1835,7 +1837,9 @@ def evaluate_dqn_members(source, n_per_member, seed=0, kmax=16, max_episode_leng
 def evaluate_dqn(source, n, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):
     """The reference's evaluation of its DQN agent -- ``DQNAgent.get_control`` (dqn.py:375-380) behind ``RLAgent.do_combined_control`` -- for ``n``
     merge episodes in one run, with an ``actor.DQNActor`` as the policy.  ``source``: a ``DQNLearner`` (a zero-copy view of its online network as it
-    is on the device), a file written by ``DQNLearner.export_q``, or a ``DQNActor`` built for ``n`` states on ``ctx``.
+    is on the device), a file written by ``DQNLearner.export_q``, or a ``DQNActor`` built for ``n`` states on ``ctx``.  A categorical policy is
+    evaluated the same way, with an ``actor.C51Actor``: ``source`` is then a ``C51Learner`` (a view of its online network), a file written by
+    ``C51Learner.export_q`` (recognised by its ``n_atoms``), or a ``C51Actor``.
     ``ctx``: the evaluation's context; by default a new one (a ``DQNActor``'s own), because a context holds one world and the training env has its
     own.  ``controller``: "combined", or "first_step" for the one-step shield of ``first_step.py``.  ``traffic``: None, or the traffic groups of
     ``episodes.EpisodeRunner``.  Returns ``run_episodes``' columns (with ``report`` when ``record`` is given)."""
@@ -1849,6 +1853,11 @@ def evaluate_dqn(source, n, seed=0, kmax=16, max_episode_length=100.0, record=No
         ctx = ctx if ctx is not None else policy.ctx
     else:
         ctx = ctx if ctx is not None else _capi.Context(-1)
-        policy = _actor.DQNActor.from_learner(source, n, ctx, Settings) if isinstance(source, DQNLearner) else _actor.DQNActor(source, n, ctx, Settings)
+        if isinstance(source, C51Learner):
+            policy = _actor.C51Actor.from_learner(source, n, ctx, Settings)
+        elif isinstance(source, DQNLearner):
+            policy = _actor.DQNActor.from_learner(source, n, ctx, Settings)
+        else:
+            policy = (_actor.C51Actor if _actor._is_c51_file(source) else _actor.DQNActor)(source, n, ctx, Settings)
     return episodes.run_episodes(int(n), seed=seed, controller=controller, policy=policy, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
                                  traffic=traffic)

@@ -654,7 +654,8 @@ class QCombinedShieldVecEnv(_CombinedShieldEnv):
 
     ``policy``: a hip-engine ``actor.DQNActor`` of ``n`` rows on the env's context (``ctx`` defaults to the policy's) -- an ``export_q`` file, or
     ``DQNActor.from_learner(learner, n, ctx, S, target=...)``, a zero-copy view, so a step queued after ``learner.update`` on the same stream rolls out
-    with the updated weights -- or an ``actor.QActorPopulation`` with ``P * n_per_member == n``: member m proposes for rows ``[m * n_per_member, (m + 1)
+    with the updated weights; or an ``actor.C51Actor``, its subclass for a categorical network (a ``C51Learner.export_q`` file, or
+    ``C51Actor.from_learner``, which sees ``C51Learner.update`` the same way) -- or an ``actor.QActorPopulation`` with ``P * n_per_member == n``: member m proposes for rows ``[m * n_per_member, (m + 1)
     * n_per_member)`` of the one world.  Its mode and action table must be the env's ("jerk" with JERK_VALUES_DQN, "acceleration" with
     ACCELERATION_VALUES_DQN, byte for byte).  The env keeps it alive.
     ``control``, ``shield_sparse``, ``takeover_penalty``, ``shield_kmax``: as ``CombinedShieldVecEnv`` takes them; ``shield_counts()`` reads
@@ -673,11 +674,11 @@ class QCombinedShieldVecEnv(_CombinedShieldEnv):
         env_id_ = self._served_env_id(env_id, self.MODE_OF, "the combined shield behind a Q-network serves 'sumo-jerk-v0' and 'sumo-accel-v0', not %r: the "
                                                             "continuous env's is CombinedShieldVecEnv")
         if isinstance(policy, (_actor.DDPGActor, _actor.ActorPopulation)):
-            raise ValueError("a DDPGActor or an ActorPopulation proposes continuous jerks: policy is an actor.DQNActor or an actor.QActorPopulation "
+            raise ValueError("a DDPGActor or an ActorPopulation proposes continuous jerks: policy is an actor.DQNActor, an actor.C51Actor or an actor.QActorPopulation "
                              "(the continuous env's class is CombinedShieldVecEnv)")
         pop = isinstance(policy, _actor.QActorPopulation)
         self._placed(n, policy, ctx, (_actor.DQNActor, _actor.QActorPopulation),
-                     "actor.DQNActor (an export_q file, or DQNActor.from_learner) or an actor.QActorPopulation", "the policy",
+                     "actor.DQNActor (an export_q file, or DQNActor.from_learner), actor.C51Actor (likewise, of a C51Learner) or an actor.QActorPopulation", "the policy",
                      " (P = %d members x n_per_member = %d)" % (policy.P, policy.n_per_member) if pop else "")
         table = np.ascontiguousarray(env_cfg(env_id_, reward, autoreset, Settings, log_capacity)._actions, dtype=np.float64)     # (ValueError for an unknown reward)
         for m, a in enumerate(policy.members if pop else [policy]):

@@ -1,0 +1,498 @@
+"""The categorical (C51) policy on the GPU (``actor.C51Actor``, ``k_c51actor_eval`` of csrc/stmpc_c51actor_kernels.hpp): the fused launch against the
+public entries it replaces -- ``stmpc_policy_features_device`` (no time feature), ``C51Learner.act`` (eps = 0, debug_q), the action table -- bit for
+bit; against ``actor.c51_policy_host`` by the learner tests' parity rule; the all-negative support, exact ties and sentinel rows at every shape;
+acceleration mode; the view's liveness and that it leaves the learner alone; the drop-in uses; ``QCombinedShieldVecEnv`` behind a view.
+Networks (n_in, h1, A, K) = (20, 16, 5, 17), (20, 32, 3, 33), (20, 48, 20, 51), (20, 256, 5, 51); row counts 1, 16, 17, 33.
+
+Not covered: the refusal of a context on another device than the policy's (one device here)."""
+import ctypes
+import types
+
+import numpy as np
+import pytest
+
+from c51actor_testlib import NAMES, NEGATIVE_SUPPORT, ROWS, SHAPES, SUPPORT, compose_first_step, config as _config, net as _net, table as _table, zero_head
+from env_testlib import settings as _env_settings
+from learner_testlib import bound_4x, check_4x, record, rel_err
+from stmpc_testlib import ACTOR_KMAX, actor_settings, actor_states, capi as _capi, same
+
+SENTINEL, TAIL = -7.0, 3          # every output buffer has TAIL rows beyond N, filled with the sentinel
+
+
+def _dev():
+    import torch
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _states(n):
+    g, S = actor_settings()
+    st = actor_states(g, _dev())
+    return S, {k: v[:n].contiguous() for k, v in st.items()}
+
+
+def _learner(gpu_ctx, shape, seed=5, support=SUPPORT, init=None, target_period=4, updates=1, env=None):
+    """A C51 learner whose online and target networks differ: 32 random transitions, then ``updates`` updates (< target_period: no hard copy)."""
+    from rl_mpc_lanemerging_amd import learner
+    import torch
+    n_in, h1, A, K = shape
+    L = learner.C51Learner(env if env is not None else (n_in, A), _config(shape, support, target_period=target_period), seed=seed,
+                           init=init if init is not None else _net(shape, seed), ctx=gpu_ctx)
+    if env is None:
+        L.action_values = _table(A)
+    rng = np.random.default_rng(seed)
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=_dev())
+    L.push(t(rng.normal(0, 1, (32, n_in)).astype(np.float32)), None, t(rng.integers(0, A, 32).astype(np.int32)), t(rng.normal(0, 1, 32)),
+           t(rng.normal(0, 1, (32, n_in)).astype(np.float32)), t(rng.random(32) < 0.2), t(np.zeros(32, bool)))
+    if updates:
+        L.update(updates)
+    return L
+
+
+def _widen(P):
+    import torch
+    rows = P.n + TAIL
+    P.feat = torch.full((rows, P.flen), SENTINEL, dtype=torch.float32, device=_dev())
+    P.q = torch.full((rows, P.shape[2]), SENTINEL, dtype=torch.float32, device=_dev())
+    P.action = torch.full((rows,), int(SENTINEL), dtype=torch.int32, device=_dev())
+    P.jerk = torch.full((rows,), SENTINEL, dtype=torch.float64, device=_dev())
+    P.keep_features = P.keep_q = True
+    return P
+
+
+def _run(P, st, step=1):
+    """One evaluation; numpy copies of the n evaluated rows, after the check that the rows beyond them kept the sentinel in every output."""
+    import torch
+    P(step, st["ego4"], st["k"], st["ox"], st["ov"], st["oa"])
+    torch.cuda.synchronize()
+    out = {k: getattr(P, k).cpu().numpy().copy() for k in ("feat", "q", "action", "jerk")}
+    for k, v in out.items():
+        assert v.shape[0] == P.n + TAIL and (v[P.n:] == SENTINEL).all(), k
+    return {k: v[:P.n] for k, v in out.items()}
+
+
+def _features(gpu_ctx, fcfg, st, n, flen):
+    import torch
+    feat = torch.full((n, flen), SENTINEL, dtype=torch.float32, device=_dev())
+    gpu_ctx.policy_features_device(fcfg, n, st["ox"].shape[1], 1, st["ego4"].data_ptr(), st["k"].data_ptr(), st["ox"].data_ptr(), st["ov"].data_ptr(),
+                                   st["oa"].data_ptr(), 0, feat.data_ptr(), flen, _stream())
+    return feat
+
+
+def _act(L, feat):
+    """(index int32 [n], expected values float32 [n][A]) of ``C51Learner.act`` on input vectors, as numpy."""
+    import torch
+    q = torch.full((feat.shape[0], L.cfg.n_actions), SENTINEL, dtype=torch.float32, device=_dev())
+    a = L.act(feat, eps=0.0, debug_q=q)
+    torch.cuda.synchronize()
+    return a.cpu().numpy().copy(), q.cpu().numpy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", ROWS)
+@pytest.mark.parametrize("shape", SHAPES)
+def test_gpu_fused_launch_equals_features_act_and_table(shape, n, gpu_ctx, restore_settings, tmp_path):
+    """A view of the online network, a view of the target network (against a second learner loaded with the target slot, after an update with
+    target_period > 1) and a file actor of the exported online network: .feat is stmpc_policy_features_device's output, .action and .q are
+    C51Learner.act's on those rows, jerk = action_values[action]; the rows beyond n keep their sentinel.  Bit for bit."""
+    capi = _capi()
+    from rl_mpc_lanemerging_amd import actor, learner
+    S, st = _states(n)
+    L = _learner(gpu_ctx, shape)
+    params = L.state_dict()["params"]
+    assert params["updates"] == 1 and not np.array_equal(params["q"]["w1"], params["q_target"]["w1"])
+    L_target = learner.C51Learner((shape[0], shape[2]), _config(shape), seed=1, init=params["q_target"], ctx=gpu_ctx)
+    path = L.export_q(str(tmp_path / "c51.npz"))
+    table = L.action_values
+    fcfg = capi.FeaturesCfg.from_settings(S, time_feature=False)
+    feat = _features(gpu_ctx, fcfg, st, n, shape[0])
+    want_feat = feat.cpu().numpy()
+    assert not (want_feat == SENTINEL).any()
+    for label, P, ref in (("online view", actor.C51Actor.from_learner(L, n, gpu_ctx, S), L), ("target view", actor.C51Actor.from_learner(L, n, gpu_ctx, S, target=True), L_target),
+                          ("file", actor.C51Actor(path, n, gpu_ctx, S), L)):
+        assert isinstance(P, actor.DQNActor) and P.mode == "jerk" and P.shape == shape[:3] and np.array_equal(P.action_values, table), label
+        assert (P.n_atoms, P.v_min, P.v_max) == (shape[3],) + SUPPORT, label
+        got = _run(_widen(P), st)
+        a, q = _act(ref, feat)
+        assert same(got["feat"], want_feat), label
+        assert same(got["q"], q), (label, int((got["q"] != q).sum()))
+        assert same(got["action"], a) and a.min() >= 0 and a.max() < shape[2], label
+        assert same(got["jerk"], table[a]), label
+        P.reset()
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", SHAPES)
+def test_gpu_expected_values_against_the_twins(shape, gpu_ctx, restore_settings):
+    """.q against c51_policy_host in float64 by the parity rule (error at most max(4 x the float32 twin's, 8 float32 ulps)) on random weights; .action
+    equals the float64 twin's index on the rows whose top-two gap exceeds the float32 error bound observed for .q; recorded in parity.json."""
+    _capi()
+    from rl_mpc_lanemerging_amd import actor
+    n, (n_in, h1, A, K) = 33, shape
+    S, st = _states(n)
+    net = _net(shape, 21)
+    L = _learner(gpu_ctx, shape, init=net, updates=0)
+    got = _run(_widen(actor.C51Actor.from_learner(L, n, gpu_ctx, S)), st)
+    q64, i64, j64 = actor.c51_policy_host(net, got["feat"], L.action_values, "jerk", K, *SUPPORT)
+    q32 = actor.c51_policy_host(net, got["feat"], L.action_values, "jerk", K, *SUPPORT, dtype=np.float32)[0]
+    ratios = {}
+    ok = check_4x("c51 actor q %dx%dx%dx%d" % shape, got["q"], q32, q64, ratios)
+    top = np.sort(q64, axis=1)
+    keep = top[:, -1] - top[:, -2] > bound_4x(rel_err(q32, q64)) * np.abs(q64).max()
+    print("rows compared:", int(keep.sum()), "of", n)
+    record("c51 actor %dx%dx%dx%d" % shape, {**ratios, "rows_compared": int(keep.sum()), "rows": n})
+    assert ok
+    assert keep.sum() >= n // 2 and np.array_equal(got["action"][keep], i64[keep]) and same(got["jerk"][keep], j64[keep])
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", SHAPES)
+def test_gpu_negative_support_and_ties(shape, gpu_ctx, restore_settings, tmp_path):
+    """A support wholly below zero: every expected value is negative and the index is a real action's, the learner's own (a pad column's logits of 0
+    would mean an expected value above them all).  A zero last layer: every expected value is the same float32 number and the action is 0.  For
+    a view and for a file actor; the rows beyond n keep their sentinel."""
+    _capi()
+    from rl_mpc_lanemerging_amd import actor
+    n, (n_in, h1, A, K) = 33, shape
+    S, st = _states(n)
+    L = _learner(gpu_ctx, shape, seed=8, support=NEGATIVE_SUPPORT, updates=0)
+    path = L.export_q(str(tmp_path / "neg.npz"))
+    for label, P in (("view", actor.C51Actor.from_learner(L, n, gpu_ctx, S)), ("file", actor.C51Actor(path, n, gpu_ctx, S))):
+        got = _run(_widen(P), st)
+        a, q = _act(L, P.feat[:n])
+        assert (got["q"] < 0).all() and (got["q"] >= -10).all() and got["action"].min() >= 0 and got["action"].max() < A, label
+        assert same(got["q"], q) and same(got["action"], a) and same(got["jerk"], L.action_values[a]), label
+        assert np.array_equal(got["q"][np.arange(n), got["action"]], got["q"].max(1)), label
+    Z = _learner(gpu_ctx, shape, seed=8, support=(-10.0, 6.0), init=zero_head(_net(shape, 8)), updates=0)
+    zpath = Z.export_q(str(tmp_path / "zero.npz"))
+    for label, P in (("view", actor.C51Actor.from_learner(Z, n, gpu_ctx, S)), ("file", actor.C51Actor(zpath, n, gpu_ctx, S))):
+        got = _run(_widen(P), st)
+        assert (got["q"] == got["q"][0, 0]).all() and abs(float(got["q"][0, 0]) + 2.0) < 1e-5, label
+        assert (got["action"] == 0).all() and (got["jerk"] == Z.action_values[0]).all(), label
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", ROWS)
+def test_gpu_acceleration_mode_equals_the_numpy_formula(n, gpu_ctx, restore_settings):
+    """(20, 48, 20, 51) behind an env of sumo-accel-v0: the default mode is "acceleration" and the jerk is clip((table[a] - ego acceleration) /
+    TICK_LENGTH, MINIMUM_NEGATIVE_JERK, MAXIMUM_POSITIVE_JERK) of the same fp64 inputs, exactly: accelerations cycle through -20, 0, +20 and the
+    table stays within +-0.1, so rows are clipped at either edge and rows are not.  Without set_limits the evaluation is refused, outputs untouched."""
+    capi = _capi()
+    import torch
+    from rl_mpc_lanemerging_amd import actor
+    S, st = _states(n)
+    st["ego4"][:, 3] = st["ego4"].new_tensor([-20.0, 0.0, 20.0]).repeat(n // 3 + 1)[:n]
+    shape = SHAPES[2]
+    n_in, h1, A, K = shape
+    table = np.linspace(-0.1, 0.1, A)
+    env = types.SimpleNamespace(continuous=False, obs_dim=n_in, action_space={"n": A}, cfg=types.SimpleNamespace(_actions=table), ctx=gpu_ctx, env_id="sumo-accel-v0")
+    L = _learner(gpu_ctx, shape, seed=9, updates=0, env=env)
+    assert L.env_id == "sumo-accel-v0" and np.array_equal(L.action_values, table)
+    P = actor.C51Actor.from_learner(L, n, gpu_ctx, S)
+    assert P.mode == "acceleration"
+    got = _run(_widen(P), st)
+    acc = st["ego4"][:, 3].cpu().numpy()
+    want = np.clip((table[got["action"]] - acc) / S.TICK_LENGTH, S.MINIMUM_NEGATIVE_JERK, S.MAXIMUM_POSITIVE_JERK)
+    assert same(got["jerk"], want)
+    assert same(got["jerk"], actor._first_maximum_jerk(got["q"], table, "acceleration", acc, S)[1])     # the twins' own rule on the device's values
+    assert (got["jerk"] == S.MAXIMUM_POSITIVE_JERK).any()
+    if n >= 3:
+        assert (got["jerk"] == S.MINIMUM_NEGATIVE_JERK).any() and (np.abs(got["jerk"]) <= 0.5).any()
+    J = actor.C51Actor.from_learner(L, n, gpu_ctx, S, mode="jerk")
+    gotj = _run(_widen(J), st)
+    assert same(gotj["action"], got["action"]) and same(gotj["jerk"], table[got["action"]])
+    # a raw handle in acceleration mode on which set_limits was not called
+    raw = gpu_ctx.c51actor_view(L.handle, table, mode=capi.QACTOR_MODES["acceleration"])
+    _widen(P)
+    with pytest.raises(capi.StmpcError, match="set_limits"):
+        gpu_ctx.qactor_eval_device(raw, P.fcfg, n, ACTOR_KMAX, 1, st["ego4"].data_ptr(), st["k"].data_ptr(), st["ox"].data_ptr(), st["ov"].data_ptr(), st["oa"].data_ptr(),
+                                   P.feat.data_ptr(), P.flen, P.action.data_ptr(), P.q.data_ptr(), P.jerk.data_ptr(), _stream())
+    torch.cuda.synchronize()
+    for t in (P.feat, P.q, P.action, P.jerk):
+        assert (t == SENTINEL).all()
+    gpu_ctx.qactor_destroy(raw)
+    gpu_ctx.check_error()
+
+
+@pytest.mark.gpu
+def test_gpu_view_is_live_and_leaves_the_learner_alone(gpu_ctx, restore_settings):
+    """Evaluate, update(3), evaluate again on the same object: the second result is C51Learner.act's of the updated network, and the learner's state
+    (all four slots, Adam's beta powers, every counter -- the exploring-call counter among them) and its next minibatch equal, bit for bit, those
+    of a twin with the same pushes and updates and no evaluation."""
+    capi = _capi()
+    import torch
+    from rl_mpc_lanemerging_amd import actor
+    shape, n = SHAPES[3], 17
+    S, st = _states(n)
+    L, twin = (_learner(gpu_ctx, shape, seed=3, target_period=2, updates=0) for _ in range(2))
+    obs = torch.zeros(8, shape[0], dtype=torch.float32, device=_dev())
+    for x in (L, twin):
+        x.act(obs, eps=1.0)                                         # one exploring call: the counter the evaluations must not advance
+    P = _widen(actor.C51Actor.from_learner(L, n, gpu_ctx, S))
+    first = _run(P, st)
+    L.update(3)
+    twin.update(3)
+    second = _run(P, st)
+    _run(_widen(actor.C51Actor.from_learner(L, n, gpu_ctx, S, target=True)), st)
+    a, b = L.state_dict(), twin.state_dict()
+    assert a["params"]["updates"] == 3 and a["counters"][3] == 1 and np.array_equal(a["counters"], b["counters"])
+    assert same(a["params"]["beta_pow"], b["params"]["beta_pow"])
+    for slot in capi.C51_SLOTS:
+        for k in NAMES:
+            assert same(a["params"][slot][k], b["params"][slot][k]), (slot, k)
+    assert same(L.minibatch(), twin.minibatch())
+    act, q = _act(twin, P.feat[:n])
+    assert same(second["q"], q) and same(second["action"], act) and same(second["jerk"], L.action_values[act])
+    assert same(second["feat"], first["feat"]) and not np.array_equal(second["q"], first["q"])
+    gpu_ctx.check_error()
+
+
+def _episode_settings():
+    import rl_mpc_lanemerging_amd as pkg
+    from rl_mpc_lanemerging_amd import combined_bench
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
+    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1_TRAFFIC)
+    return pkg.Settings
+
+
+def _plain_policy(gpu_ctx, L, S, n):
+    """A plain callable with the policy signature from the public entries: features, C51Learner.act, the table."""
+    import torch
+    capi = _capi()
+    fcfg = capi.FeaturesCfg.from_settings(S, time_feature=False)
+    flen = L.cfg.n_obs
+    table = torch.as_tensor(L.action_values, device=_dev())
+    feat = torch.empty(n, flen, dtype=torch.float32, device=_dev())
+
+    def policy(step, cur_ego4, k, cur_ox, cur_ov, cur_oa):
+        gpu_ctx.policy_features_device(fcfg, n, cur_ox.shape[1], step, cur_ego4.data_ptr(), k.data_ptr(), cur_ox.data_ptr(), cur_ov.data_ptr(), cur_oa.data_ptr(), 0,
+                                       feat.data_ptr(), flen, _stream())
+        return table[L.act(feat, eps=0.0).long()]
+    return policy
+
+
+@pytest.mark.gpu
+def test_gpu_drop_in_for_the_combined_controller(gpu_ctx, restore_settings):
+    """combined.decide_batch_device with a C51Actor returns what it returns with the plain callable, bit for bit."""
+    capi = _capi()
+    import torch
+    from rl_mpc_lanemerging_amd import actor, combined
+    n = 33
+    S, st = _states(n)
+    L = _learner(gpu_ctx, SHAPES[3])
+    params, cfg = capi.Params.from_settings(S), capi.CombinedCfg.from_settings(S)
+    assert cfg.rollout_length > 1
+    out = []
+    for policy in (actor.C51Actor.from_learner(L, n, gpu_ctx, S), _plain_policy(gpu_ctx, L, S, n)):
+        d = combined.decide_batch_device(gpu_ctx, params, cfg, st["ego5"], st["k"], st["ox"], st["ov"], policy, None, _stream(), d_oa=st["oa"])
+        torch.cuda.synchronize()
+        gpu_ctx.check_error()
+        out.append({k: v.cpu().numpy().copy() for k, v in d.items()})
+    assert set(out[0]) == set(out[1]) and len(out[0]) == 8
+    for k in out[0]:
+        assert same(out[0][k], out[1][k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("controller", ["combined", "first_step"])
+def test_gpu_drop_in_for_the_episode_runner(controller, gpu_ctx, restore_settings):
+    """EpisodeRunner(32, controller, policy) gives identical result() columns after 8 ticks with a C51Actor and with the plain callable."""
+    _capi()
+    from rl_mpc_lanemerging_amd import actor, episodes
+    S = _episode_settings()
+    n = 32
+    L = _learner(gpu_ctx, SHAPES[3])
+    res = []
+    for policy in (actor.C51Actor.from_learner(L, n, gpu_ctx, S), _plain_policy(gpu_ctx, L, S, n)):
+        r = episodes.EpisodeRunner(n, seed=4, controller=controller, policy=policy, ctx=gpu_ctx, kmax=ACTOR_KMAX)
+        for _ in range(8):
+            r.tick()
+        res.append(r.result())
+    assert set(res[0]) == set(res[1]) and "percent_st" in res[0]
+    for k in res[0]:
+        assert same(res[0][k], res[1][k]), k
+    assert r.ticks_done == 8 and res[0]["ticks"].max() >= 1
+
+
+@pytest.mark.gpu
+def test_gpu_evaluate_dqn(gpu_ctx, restore_settings, tmp_path):
+    """32 episodes of 2 s behind a C51Learner (a view, a context of the evaluation's own), behind its exported file under the first-step shield, and
+    behind a C51Actor: run_episodes' columns; the file and the actor give the learner's columns where the controller is the same."""
+    _capi()
+    from rl_mpc_lanemerging_amd import _capi as capi, actor, learner
+    S = _episode_settings()
+    L = _learner(gpu_ctx, SHAPES[0], updates=0)
+    out = learner.evaluate_dqn(L, 32, seed=1, kmax=ACTOR_KMAX, max_episode_length=2.0)
+    assert out["ticks"].shape == (32,) and out["ticks"].max() <= 10 and (out["status"] != 0).all() and "percent_st" in out
+    path = L.export_q(str(tmp_path / "c51.npz"))
+    shielded = learner.evaluate_dqn(path, 32, seed=1, kmax=ACTOR_KMAX, max_episode_length=2.0, controller="first_step")
+    assert set(shielded) == set(out) and (shielded["status"] != 0).all()
+    ctx = capi.Context(-1)
+    again = learner.evaluate_dqn(actor.C51Actor(path, 32, ctx, S), 32, seed=1, kmax=ACTOR_KMAX, max_episode_length=2.0)
+    for k in out:
+        assert same(out[k], again[k]), k
+    with pytest.raises(ValueError, match="built for 16"):
+        learner.evaluate_dqn(actor.C51Actor.from_learner(L, 16, gpu_ctx, S), 32)
+    ctx.close()
+
+
+# ---- QCombinedShieldVecEnv behind a view of the learner being trained ------------------------------------------------------------------------------
+ENV_N, ENV_SEED, ENV_KMAX = 24, 11, 16
+ENV_SHAPE = {"sumo-jerk-v0": 16, "sumo-accel-v0": 48}
+
+
+def _env_case(env_id, ctx, seed=0):
+    """(learner on ``ctx`` whose table is the env's, its shape)."""
+    from rl_mpc_lanemerging_amd import learner, vec_env
+    tab = np.array(vec_env.env_cfg(env_id, "Continuous")._actions, dtype=np.float64)
+    shape = (20, ENV_SHAPE[env_id], tab.size, 17)
+    net = _net(shape, 1000 + seed, spread=6.0)
+    net["w0"] = (net["w0"] * 3).astype(np.float32)                  # large enough for the argmax to move with the state
+    env = types.SimpleNamespace(continuous=False, obs_dim=20, action_space={"n": tab.size}, cfg=types.SimpleNamespace(_actions=tab), ctx=ctx, env_id=env_id)
+    L = learner.C51Learner(env, _config(shape, capacity=4 * ENV_N, replay_start=ENV_N // 2, lr=1.0), seed=3, init=net, ctx=ctx)
+    return L, shape
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_id", ["sumo-jerk-v0", "sumo-accel-v0"])
+def test_gpu_shield_env_step_is_the_composition(env_id, restore_settings):
+    """One step of QCombinedShieldVecEnv(C51Actor.from_learner(L, n, ...)) from the reset's world equals the composition of the public view /
+    rollout / policy / decide / world-step / reward entries, bit for bit."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, actor, vec_env
+    S = _env_settings()
+    ctx = _capi.Context(-1)
+    L, shape = _env_case(env_id, ctx)
+    P = actor.C51Actor.from_learner(L, ENV_N, ctx, S)
+    assert P.mode == ("jerk" if env_id == "sumo-jerk-v0" else "acceleration")
+    env = vec_env.QCombinedShieldVecEnv(ENV_N, P, env_id=env_id, seed=ENV_SEED, reward="Continuous", ctx=ctx, shield_kmax=ENV_KMAX, autoreset=False)
+    assert env.shield == "combined"
+    obs0 = env.reset().cpu().numpy().copy()
+    A = shape[2]
+    act = (np.arange(ENV_N) * 7 % A).astype(np.int32)
+    obs, r, term, trunc, info = env.step(torch.as_tensor(act, device="cuda"))
+    got = {"obs": obs, "reward": r, "term": term, "trunc": trunc, "takeover": info["takeover"], "reason": info["reason"], "executed_jerk": info["executed_jerk"]}
+    got = {k: v.cpu().numpy().copy() for k, v in got.items()}
+    L_ = max(int(env.shield_cfg.cc.rollout_length), 1)
+    assert L_ > 1                                                   # (the policy is called in the rollout)
+    env.check_error()
+
+    def policy_of(c):
+        L2, _ = _env_case(env_id, c)
+        return actor.C51Actor.from_learner(L2, ENV_N, c, S)
+    want = compose_first_step(env_id, policy_of, act, ENV_N, ENV_SEED, ENV_KMAX, _env_settings)
+    assert same(obs0, want["obs0"])
+    on = want["status"] == 0
+    assert on.any()
+    for k in ("takeover", "reason", "executed_jerk", "reward", "term", "trunc"):
+        assert same(got[k], want[k].astype(got[k].dtype) if k == "takeover" else want[k]), k
+    assert same(got["obs"][on], want["obs"][on])
+    print("takeovers:", int(want["takeover"].sum()), "of", ENV_N)
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_shield_env_view_sees_the_update_and_trains(restore_settings, tmp_path):
+    """The env's policy is a view of a C51 learner's online network: a step queued after L.update(3) equals the step of a twin env whose policy is
+    a file actor holding the UPDATED weights and differs in its rollouts from an env under the weights before the update.  Then
+    train_dqn(env, C51Learner) runs for a few hundred frames and reports takeover_share."""
+    import torch
+    from rl_mpc_lanemerging_amd import _capi, actor, learner, vec_env
+    env_id = "sumo-jerk-v0"
+    S = _env_settings()
+    mk = lambda c, pol, **kw: vec_env.QCombinedShieldVecEnv(ENV_N, pol, env_id=env_id, seed=ENV_SEED, reward="Continuous", ctx=c, shield_kmax=ENV_KMAX, **kw)
+    ctx, stale_ctx, fresh_ctx = (_capi.Context(-1) for _ in range(3))
+    L, shape = _env_case(env_id, ctx)
+    stale_path = L.export_q(str(tmp_path / "stale.npz"))
+    env = mk(ctx, actor.C51Actor.from_learner(L, ENV_N, ctx, S), autoreset=False)
+    stale = mk(stale_ctx, actor.C51Actor(stale_path, ENV_N, stale_ctx, S), autoreset=False)
+    obs = env.reset()
+    stale.reset()
+    A = shape[2]
+    act = torch.as_tensor((np.arange(ENV_N) * 7 % A).astype(np.int32), device="cuda")
+    reward = torch.as_tensor(np.linspace(-2, 2, ENV_N), device="cuda")
+    no = torch.zeros(ENV_N, dtype=torch.bool, device="cuda")
+    L.push(obs.clone(), None, act, reward, obs.clone(), no, no, final_obs=obs.clone())
+    L.update(3)
+    assert L.stats()["updates"] == 3
+    fresh_path = L.export_q(str(tmp_path / "fresh.npz"))
+    fresh = mk(fresh_ctx, actor.C51Actor(fresh_path, ENV_N, fresh_ctx, S), autoreset=False)
+    fresh.reset()
+    L_ = max(int(env.shield_cfg.cc.rollout_length), 1)
+    out = {}
+    for name, e in (("view", env), ("fresh", fresh), ("stale", stale)):
+        o = e.step(act)
+        out[name] = {k: o[4][k].cpu().numpy().copy() for k in ("takeover", "reason", "executed_jerk", "takeover_ticks")}
+        out[name].update(obs=o[0].cpu().numpy().copy(), reward=o[1].cpu().numpy().copy(), rollout_s=e.ctx.combined_read_state(ENV_N, ENV_KMAX, L_)["rollout_s"])
+    for k in out["view"]:
+        assert same(out["view"][k], out["fresh"][k]), k
+    differ = (out["view"]["rollout_s"] != out["stale"]["rollout_s"]).any(axis=1)
+    print("a view sees the update: rolled-out rows that differ from the pre-update ones:", int(differ.sum()), "of", ENV_N)
+    assert differ.sum() >= 1
+    for c in (ctx, stale_ctx, fresh_ctx):
+        c.check_error()
+        c.close()
+    # training behind the shield
+    tctx = _capi.Context(-1)
+    T, _ = _env_case(env_id, tctx, seed=1)
+    T.cfg.lr = 2e-4
+    tenv = mk(tctx, actor.C51Actor.from_learner(T, ENV_N, tctx, S))
+    res = learner.train_dqn(tenv, T, frames=12 * ENV_N, drain_every=4)
+    tenv.check_error()
+    print("training behind the shield: takeover_share %.4f, episodes %d" % (res["takeover_share"], res["episodes"]))
+    assert res["steps"] == 12 and res["frames"] == 12 * ENV_N and 0.0 <= res["takeover_share"] <= 1.0 and T.stats()["updates"] >= 1
+    tctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_library_refusals(gpu_ctx, restore_settings):
+    """stmpc_pop_qactor_create with a categorical member, a context on the same device with a wrong n_in, a time-feature cfg, and the create / view
+    refusals that need a live context: STMPC_EINVAL with a message, before anything is launched -- the outputs keep their sentinel."""
+    capi = _capi()
+    import torch
+    from rl_mpc_lanemerging_amd import actor
+    lib = capi.load()
+    n, shape = 17, SHAPES[0]
+    S, st = _states(n)
+    L = _learner(gpu_ctx, shape, updates=0)
+    P = _widen(actor.C51Actor.from_learner(L, n, gpu_ctx, S))
+    with pytest.raises(capi.StmpcError, match="categorical") as err:
+        gpu_ctx.qactor_pop_create([P.handle])
+    assert err.value.code == capi.STMPC_EINVAL
+    args = lambda **kw: {**dict(handle=P.handle, fcfg=P.fcfg, N=n, Kmax=ACTOR_KMAX, step=1, d_cur_ego4=st["ego4"].data_ptr(), d_k=st["k"].data_ptr(),
+                                d_cur_ox=st["ox"].data_ptr(), d_cur_ov=st["ov"].data_ptr(), d_cur_oa=st["oa"].data_ptr(), d_feat=P.feat.data_ptr(), feat_stride=P.flen,
+                                d_action=P.action.data_ptr(), d_q=P.q.data_ptr(), d_jerk=P.jerk.data_ptr(), stream=_stream()), **kw}
+    timed = capi.FeaturesCfg.from_settings(S, time_feature=True)
+    wide = capi.FeaturesCfg.from_settings(S, time_feature=False)
+    wide.cars_ahead += 1
+    for kw, word in ((dict(fcfg=timed), "time feature"), (dict(fcfg=wide), "input width"), (dict(N=0), "positive"), (dict(d_jerk=0), "NULL"),
+                     (dict(feat_stride=P.flen - 1), "feat_stride")):
+        with pytest.raises(capi.StmpcError) as err:
+            gpu_ctx.qactor_eval_device(**args(**kw))
+        assert err.value.code == capi.STMPC_EINVAL and word in str(err.value), (kw, str(err.value))
+    h = ctypes.c_void_p()
+    dp = lambda a: np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    for kw, word in ((dict(target=2), "target"), (dict(mode=-1), "mode"), (dict(tab=L.action_values[:4], A=4), "4 entries")):
+        kw = {**dict(target=0, mode=0, tab=L.action_values, A=5), **kw}
+        tab = np.ascontiguousarray(kw["tab"], dtype=np.float64)
+        rc = lib.stmpc_c51actor_view(L.handle, kw["target"], dp(tab), kw["A"], kw["mode"], ctypes.byref(h))
+        assert rc == capi.STMPC_EINVAL and word in lib.stmpc_last_error().decode() and not h.value, kw
+    net = L.state_dict()["params"]["q"]
+    # (the LDS refusal cannot be reached here: the widest shape the other checks let through, 1024 -> 1024 logits, needs 133 KB of the 160 KB)
+    with pytest.raises(ValueError, match="tensors"):
+        gpu_ctx.c51actor_create(net, np.arange(4.0), 17, -10.0, 10.0)
+    torch.cuda.synchronize()
+    for t in (P.feat, P.q, P.action, P.jerk):
+        assert (t == SENTINEL).all()                                # nothing ran
+    gpu_ctx.qactor_eval_device(**args())                            # ... and the same arguments unchanged are accepted
+    torch.cuda.synchronize()
+    assert not (P.jerk[:n] == SENTINEL).any() and (P.jerk[n:] == SENTINEL).all()
+    gpu_ctx.check_error()

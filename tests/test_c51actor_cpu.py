@@ -1,0 +1,199 @@
+"""The categorical (C51) policy (``actor.C51Actor``, ``actor.c51_policy_host``, the stmpc_c51actor_ entries) without a GPU: header, library and binding
+agree; the host twin against ``torch.softmax`` over the (A, K) logits times the support in float64; first-maximum ties from a zero last layer; a
+support wholly below zero; acceleration mode's formula at both clip edges and inside; the Python-side refusals -- among them every way a C51
+learner, file or actor could reach a population, refused before any library call; the library refusals that need no device."""
+import ctypes
+import types
+
+import numpy as np
+import pytest
+
+from c51actor_testlib import (NEGATIVE_SUPPORT, SHAPES, SUPPORT, TWIN_ROWS, TWIN_SEED, NoLibrary, c51_actor_stub, c51_learner_stub, export_file, net as _net,
+                              table as _table, zero_head)
+from stmpc_testlib import capi as _capi, header_entries, header_prototypes, header_text
+
+ENTRIES = {"stmpc_c51actor_create", "stmpc_c51actor_view"}
+
+
+def test_header_library_and_binding_agree_on_the_c51_actor():
+    capi = _capi()
+    lib = capi.load()
+    assert header_entries("stmpc_c51actor_") == ENTRIES == {n for n in capi.EXPORTS if n.startswith("stmpc_c51actor_")}
+    assert header_entries("stmpc_") - {"stmpc_params", "stmpc_stats", "stmpc_ctx"} == set(capi.EXPORTS)
+    protos = header_prototypes("stmpc_c51actor_")
+    assert set(protos) == ENTRIES
+    for name in ENTRIES:
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == protos[name].count(",") + 1, name
+    assert protos["stmpc_c51actor_create"].count(",") + 1 == 14 and "stmpc_qactor **out" in protos["stmpc_c51actor_create"]
+    assert "stmpc_c51 *learner" in protos["stmpc_c51actor_view"] and "stmpc_qactor **out" in protos["stmpc_c51actor_view"]
+    flat = header_text(flat=True)
+    doc = flat[flat.index("A categorical (C51) network as such a policy"):flat.index("int stmpc_c51actor_create(")]
+    for name in ENTRIES:                                            # every entry names the reference's function it stands for
+        at = doc.index(name + " ")
+        assert "dqn.py:375-380" in doc[at:at + 120] and "rainbow.py" in doc[at:at + 160], name
+    assert "stmpc_pop_qactor_create refuses a categorical member" in doc
+    assert "#define STMPC_ABI_VERSION 8" in flat and capi.ABI_VERSION == 8 and lib.stmpc_abi_version() == 8
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_c51_policy_host_against_torch_softmax(shape):
+    """The expected values equal softmax(logits.view(A, K)) @ support of nn.Sequential(Linear, ReLU, Linear) in float64 to 1e-12 relative; the index
+    equals torch.argmax on every row whose top-two gap exceeds 1e-9 (at least 99 % of the rows); the jerk is the table's entry."""
+    _capi()
+    import torch
+    from torch import nn
+    from rl_mpc_lanemerging_amd import actor, learner
+    n_in, h1, A, K = shape
+    net = _net(shape, TWIN_SEED)
+    feat = np.random.default_rng(TWIN_SEED).normal(0, 1, (TWIN_ROWS, n_in)).astype(np.float32)
+    table = _table(A)
+    m = nn.Sequential(nn.Linear(n_in, h1), nn.ReLU(), nn.Linear(h1, A * K)).double()
+    with torch.no_grad():
+        for p, k in zip(m.parameters(), ("w0", "b0", "w1", "b1")):
+            p.copy_(torch.tensor(net[k], dtype=torch.float64))
+        z = torch.tensor(learner.c51_support(types.SimpleNamespace(n_atoms=K, v_min=SUPPORT[0], v_max=SUPPORT[1])))
+        want = (torch.softmax(m(torch.tensor(feat, dtype=torch.float64)).view(TWIN_ROWS, A, K), dim=2) * z).sum(2)
+        want_idx = torch.argmax(want, 1).numpy()
+    want = want.numpy()
+    q, idx, jerk = actor.c51_policy_host(net, feat, table, "jerk", K, *SUPPORT)
+    assert q.dtype == np.float64 and q.shape == (TWIN_ROWS, A) and idx.shape == (TWIN_ROWS,) and jerk.dtype == np.float64
+    assert np.abs(q - want).max() <= 1e-12 * np.abs(want).max()
+    top = np.sort(want, 1)
+    clear = top[:, -1] - top[:, -2] > 1e-9
+    assert clear.mean() >= 0.99, clear.mean()
+    assert np.array_equal(idx[clear], want_idx[clear])
+    assert np.array_equal(jerk, table[idx]) and len(set(idx.tolist())) > 1
+    q32, idx32, _ = actor.c51_policy_host(net, feat, table, "jerk", K, *SUPPORT, dtype=np.float32)
+    assert q32.dtype == np.float32 and (idx32 == idx).mean() > 0.9
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_a_zero_last_layer_ties_and_takes_action_0(shape):
+    _capi()
+    from rl_mpc_lanemerging_amd import actor
+    A, K = shape[2:]
+    feat = np.random.default_rng(1).normal(0, 1, (33, shape[0])).astype(np.float32)
+    for dtype in (np.float64, np.float32):
+        q, idx, jerk = actor.c51_policy_host(zero_head(_net(shape, 1)), feat, _table(A), "jerk", K, -10.0, 6.0, dtype=dtype)
+        assert (q == q[:, :1]).all() and np.array_equal(idx, np.zeros(33, np.int64)) and np.array_equal(jerk, np.full(33, _table(A)[0]))
+        assert np.abs(q + 2.0).max() < 1e-5                         # the support's centre
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_a_negative_support_never_returns_a_pad_index(shape):
+    """The support lies wholly below zero: every real expected value is negative, a pad column's 0 would beat them all.  The twin has no pad."""
+    _capi()
+    from rl_mpc_lanemerging_amd import actor
+    A, K = shape[2:]
+    feat = np.random.default_rng(2).normal(0, 1, (64, shape[0])).astype(np.float32)
+    q, idx, jerk = actor.c51_policy_host(_net(shape, 2), feat, np.arange(A, dtype=np.float64), "jerk", K, *NEGATIVE_SUPPORT)
+    assert (q < -1.0 + 1e-12).all() and (q > -10.0 - 1e-12).all() and idx.min() >= 0 and idx.max() < A and np.array_equal(jerk, idx.astype(np.float64))
+    assert np.array_equal(q[np.arange(64), idx], q.max(1))
+
+
+def test_acceleration_mode_formula():
+    """jerk = clip((table[a] - ego acceleration) / TICK_LENGTH, MINIMUM_NEGATIVE_JERK, MAXIMUM_POSITIVE_JERK): inside, at and beyond both edges; the
+    rule is q_policy_host's own function."""
+    _capi()
+    from rl_mpc_lanemerging_amd import actor
+    S = types.SimpleNamespace(TICK_LENGTH=0.25, MINIMUM_NEGATIVE_JERK=-4.0, MAXIMUM_POSITIVE_JERK=2.0)
+    A, K = 6, 3
+    net = {"w0": np.zeros((2, 3), np.float32), "b0": np.zeros(2, np.float32), "w1": np.zeros((A * K, 2), np.float32), "b1": np.zeros(A * K, np.float32)}
+    table = np.array([-1.5, -1.0, 0.0, 0.25, 0.5, 1.0])
+    for a in range(A):
+        net["b1"][:] = 0
+        net["b1"][a * K + K - 1] = 4                               # action a's mass moves to its top atom: the largest expected value
+        acc = np.array([table[a], table[a] - 0.25, table[a] + 0.5, table[a] - 0.5, table[a] + 1.0, table[a] - 0.75, table[a] + 1.25, 3.0, -3.0])
+        q, idx, jerk = actor.c51_policy_host(net, np.zeros((acc.size, 3), np.float32), table, "acceleration", K, -1.0, 1.0, ego_acc=acc, S=S)
+        assert (idx == a).all()
+        raw = (table[a] - acc) / 0.25
+        assert np.array_equal(jerk, np.minimum(np.maximum(raw, -4.0), 2.0))
+        assert jerk[3] == 2.0 and raw[3] == 2.0 and jerk[4] == -4.0 and raw[4] == -4.0        # exactly at the edges
+        assert jerk[5] == 2.0 and raw[5] == 3.0 and jerk[6] == -4.0 and raw[6] == -5.0        # beyond them
+        inside = (raw > -4.0) & (raw < 2.0)
+        assert inside[:3].all() and np.array_equal(jerk[:3], [0.0, 1.0, -2.0]) and np.array_equal(jerk[inside], raw[inside])
+        qn = {"w0": net["w0"], "b0": net["b0"], "w1": np.zeros((A, 2), np.float32), "b1": np.eye(A, dtype=np.float32)[a]}
+        assert np.array_equal(jerk, actor.q_policy_host(qn, np.zeros((acc.size, 3), np.float32), table, "acceleration", ego_acc=acc, S=S)[2])
+    assert np.array_equal(actor.c51_policy_host(net, np.zeros((2, 3), np.float32), table, "jerk", K, -1.0, 1.0, ego_acc=np.array([9.0, -9.0]))[2], table[[A - 1, A - 1]])
+    with pytest.raises(ValueError, match="ego_acc"):
+        actor.c51_policy_host(net, np.zeros((2, 3), np.float32), table, "acceleration", K, -1.0, 1.0)
+
+
+def test_python_side_refusals(tmp_path):
+    _capi()
+    from rl_mpc_lanemerging_amd import Settings, actor, learner
+    shape = SHAPES[0]
+    net, feat = _net(shape, 0), np.zeros((3, 20), np.float32)
+    with pytest.raises(ValueError, match="mode"):
+        actor.c51_policy_host(net, feat, _table(5), "speed", 17, *SUPPORT)
+    with pytest.raises(ValueError, match="action table"):
+        actor.c51_policy_host(net, feat, np.arange(4.0), "jerk", 17, *SUPPORT)
+    with pytest.raises(ValueError, match="n_atoms"):
+        actor.c51_policy_host(net, feat, _table(5), "jerk", 1, *SUPPORT)
+    with pytest.raises(ValueError, match="v_max > v_min"):
+        actor.c51_policy_host(net, feat, _table(5), "jerk", 17, 1.0, 1.0)
+    c51_file = export_file(tmp_path / "c51.npz", net, shape)
+    with pytest.raises(ValueError, match="action table"):          # a table of the wrong size
+        actor.C51Actor(c51_file, 4, NoLibrary(), Settings, action_values=np.arange(6.0))
+    with pytest.raises(ValueError, match="mode"):
+        actor.C51Actor(c51_file, 4, NoLibrary(), Settings, mode="accel")
+    dqn_file = tmp_path / "q.npz"
+    np.savez(dqn_file, **learner.init_q_net(20, 16, 5, np.random.default_rng(0)), action_values=_table(5))
+    with pytest.raises(ValueError, match="no n_atoms"):
+        actor.C51Actor(dqn_file, 4, NoLibrary(), Settings)
+    with pytest.raises(ValueError, match="C51Actor"):               # and the other way round: no more the table-size message
+        actor.DQNActor(c51_file, 4, NoLibrary(), Settings)
+    stub = c51_learner_stub(shape)
+    with pytest.raises(ValueError, match="action table"):
+        stub.action_values = np.arange(4.0)
+        actor.C51Actor.from_learner(stub, 4, NoLibrary(), Settings)
+    with pytest.raises(ValueError, match="no C51Learner"):
+        actor.C51Actor.from_learner(types.SimpleNamespace(cfg=learner.DQNConfig(n_obs=20, n_actions=5, h1=16), action_values=_table(5), handle=None), 4, NoLibrary(), Settings)
+    assert issubclass(actor.C51Actor, actor.DQNActor) and actor.C51Actor.MODES == ("jerk", "acceleration")
+
+
+@pytest.mark.parametrize("kind", ["file", "learner", "actor"])
+def test_no_c51_policy_reaches_a_population(kind, tmp_path, monkeypatch):
+    """A C51 file, a C51Learner stand-in (export_q, handle and a C51Config: what the parent commit took for a DQN learner and handed to
+    stmpc_qactor_view_dqn) and a C51Actor stand-in are refused by QActorPopulation, population_of and evaluate_dqn_members with a ValueError that
+    names the lone route, before anything is built: every context here fails the test when touched, and so does a new one."""
+    capi = _capi()
+    from rl_mpc_lanemerging_amd import Settings, actor, learner
+    shape = SHAPES[0]
+    member = {"file": lambda: export_file(tmp_path / "c51.npz", _net(shape, 0), shape), "learner": lambda: c51_learner_stub(shape), "actor": lambda: c51_actor_stub(shape)}[kind]()
+    assert not actor._is_dqn_learner(member)
+    monkeypatch.setattr(capi, "Context", lambda *a, **k: NoLibrary())
+    dqn_file = tmp_path / "q.npz"
+    np.savez(dqn_file, **learner.init_q_net(20, 16, 5, np.random.default_rng(0)), action_values=_table(5))
+    for members in ([member], [str(dqn_file), member]):
+        for call in (lambda: actor.QActorPopulation(members, 2, NoLibrary(), Settings), lambda: actor.population_of(members, 2, NoLibrary(), Settings),
+                     lambda: learner.evaluate_dqn_members(members, 2), lambda: learner.evaluate_dqn_members(members, 2, ctx=NoLibrary())):
+            with pytest.raises(ValueError, match="evaluate_dqn or a C51Actor") as err:
+                call()
+            assert "member" in str(err.value) and str(len(members) - 1) in str(err.value)
+    if kind == "learner":
+        with pytest.raises(ValueError, match="C51Actor.from_learner"):
+            actor.DQNActor.from_learner(member, 4, NoLibrary(), Settings)
+        with pytest.raises(ValueError, match="evaluate_dqn or a C51Actor"):
+            learner.evaluate_dqn_members(member, 2)
+
+
+def test_library_refusals_that_need_no_device():
+    capi = _capi()
+    lib, h = capi.load(), ctypes.c_void_p()
+    null = ctypes.c_void_p()
+    bogus = ctypes.c_void_p(8)                                      # a context the checks in front of the device never read
+    fp, dp = ctypes.POINTER(ctypes.c_float)(), ctypes.POINTER(ctypes.c_double)()
+    w = np.zeros(4096, np.float32)
+    wp = w.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    tab = np.arange(5.0)
+    tp = tab.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    create = lambda ctx=bogus, A=5, K=17, lo=-10.0, hi=10.0, w0=wp, t=tp, mode=0: lib.stmpc_c51actor_create(ctx, 20, 16, A, K, lo, hi, w0, wp, wp, wp, t, mode, ctypes.byref(h))
+    for kw, word in ((dict(ctx=null), "NULL"), (dict(w0=fp), "NULL"), (dict(t=dp), "NULL"), (dict(mode=2), "mode"), (dict(K=1), "n_atoms"),
+                     (dict(A=21, K=51), "exceeds 1024"), (dict(lo=1.0, hi=1.0), "support"), (dict(lo=2.0, hi=1.0), "support"),
+                     (dict(hi=float("inf")), "support"), (dict(lo=float("nan")), "support"), (dict(A=0), "n_actions"), (None, "NULL")):
+        rc = create(**kw) if kw is not None else lib.stmpc_c51actor_view(null, 0, tp, 5, 0, ctypes.byref(h))
+        assert rc == capi.STMPC_EINVAL and word in lib.stmpc_last_error().decode(), (word, lib.stmpc_last_error())
+        assert not h.value
+    assert lib.stmpc_c51actor_create(bogus, 20, 16, 5, 17, -10.0, 10.0, wp, wp, wp, wp, tp, 0, None) == capi.STMPC_EINVAL
