@@ -1047,6 +1047,67 @@ int  stmpc_c51_dzout_read(stmpc_c51 *learner, float *values, int64_t count);
 int  stmpc_c51_padded_read(stmpc_c51 *learner, int slot, float *values, int64_t count);
 
 /*
+ * A population of C51 learners: the population axis of stmpc_ddpg_pop_* / stmpc_pop_td3_* / stmpc_pop_dqn_* for the categorical learner above.  P
+ * independent C51 learners -- each its own ring, logits network, target, Adam state, counters, seed and constants, the support [v_min, v_max],
+ * double_dqn, target_period, replay_start and n_step included -- share one discrete-action vector environment and advance with ONE launch per
+ * kernel: three launches per update whatever P is and whatever the members' counters say, five when at least one member is prioritised; acting,
+ * pushing and the statistics are one launch each.  Member m owns rows [m * n_per_member, (m + 1) * n_per_member) of the step tensors and is
+ * bit-identical to a lone stmpc_c51 with its cfg given its slice.  What a user compares between runs of the categorical agent (rainbow.py: the
+ * `all` library's rainbow preset) -- which support fits the env's returns, double against plain action selection, target_period, gamma, n_step,
+ * seeds, prioritised against uniform replay, traffic types, reward settings -- is then one run.  (Additive: new entries only, no signature or struct
+ * of ABI 8 changes, so STMPC_ABI_VERSION stays 8; no entry above changes what it computes.)  The entries read stmpc_pop_c51_*: the prefixes
+ * stmpc_c51_, stmpc_pop_dqn_, stmpc_pop_per_ and stmpc_pop_nstep_ are closed sets, which is why prioritised replay and n_step are enabled here.
+ *   pop_create      (rainbow.py) P = 1 ... STMPC_C51_POP_MAX configs that share n_obs, h1, n_actions, n_atoms, batch and capacity (one network
+ *                   shape, one LDS size, one grid); everything else may differ per member -- v_min, v_max and dz travel in the member's own device
+ *                   struct.  Each member is made by the lone create, whose refusals apply per member
+ *   pop_destroy, pop_size   (rainbow.py) the population with its members; the member count (0 for NULL)
+ *   pop_member      (rainbow.py) the m-th member as a BORROWED stmpc_c51, valid until pop_destroy (never destroy it): every lone entry works on it
+ *                   as on a lone learner -- set / get_params, set / get_state, grads, targets, dist, project, gather, stats, per_tree_read,
+ *                   per_last_device, padded_read, dzout_read, stmpc_c51actor_view, and the lone act, push and update -- but the lone per_enable and
+ *                   multi_step_enable, which refuse: both are the population's to set
+ *   pop_act_device  (rainbow.py) the lone act_device per member: d_action int32 [P * n_per_member]; eps HOST fp64 [n_eps], n_eps = P, one value per
+ *                   member (it travels as a kernel argument).  Member m's exploration hash is keyed by its own seed, its own count of exploring
+ *                   calls and the row local to its slice.  A member whose eps is 0 draws nothing and its call counter stays, as a lone learner's
+ *                   does under eps = 0.  d_debug_q (may be NULL) float32 [P * n_per_member][n_actions]: the expected values
+ *   pop_push_device (rainbow.py) the lone push_device per member, each slice into its member's ring (and tree, where the member has one)
+ *   pop_update_device   (rainbow.py) n_updates updates of every member; lr HOST fp64 [n_lr], n_lr = P.  A member whose replay_start gate is shut
+ *                   skips its update while the others proceed, and the hard copy of the target follows the member's own update count and
+ *                   target_period; both are decided on the device
+ *   pop_stats_device    (rainbow.py) d_out DEVICE fp64 [P][4]: the lone stats_device's four numbers per member
+ *   pop_per_enable  (rainbow.py) stmpc_pop_dqn_per_enable for this population: cfgs HOST [P], enabled HOST uint8 [P]; one call, on empty rings;
+ *                   afterwards a prioritised member is bit-identical to a lone learner with the lone per_enable, a uniform one to the member of a
+ *                   population without the call
+ *   pop_multi_step_enable   (rainbow.py) stmpc_pop_nstep_enable_dqn for this population: cfgs HOST [P], member m gets cfgs[m]; rows_per_push is the
+ *                   population's n_per_member.  Every member passes the lone entry's checks before any changes; then the device tables are
+ *                   written anew
+ *   pop_replay_read (rainbow.py) debug, HOST: `count` rows of STMPC_DDPG_ROW float32 from row `first` of a learner's ring -- a borrowed member's,
+ *                   or a lone stmpc_c51's, so that the two can be compared; synchronises
+ *   pop_multi_step_window   (rainbow.py) debug, HOST: stmpc_nstep_window_dqn for a stmpc_c51, borrowed or lone (the stmpc_nstep_ and stmpc_c51_
+ *                   prefixes are closed sets, and no other exported name holds "nstep"): out [n_idx][4] fp64 = R, disc, the ring row of the window's last transition, m for the n_idx ring rows idx (each
+ *                   a filled row, else STMPC_EINVAL), by the device function the update's gather calls; synchronises
+ * Refused with STMPC_EINVAL before any launch: P outside 1 ... 64, members that differ in a shared field (the message names the member and lists
+ * the shared fields), n_lr or n_eps other than P, an eps outside 0 ... 1, a negative learning rate or n_updates, n_per_member outside
+ * 1 ... capacity, NULL pointers.
+ */
+#define STMPC_C51_POP_MAX 64            /* == STMPC_DDPG_POP_MAX */
+typedef struct stmpc_c51_pop stmpc_c51_pop;
+int  stmpc_pop_c51_create(stmpc_ctx *ctx, const stmpc_c51_cfg *cfgs, int P, stmpc_c51_pop **out);
+void stmpc_pop_c51_destroy(stmpc_c51_pop *pop);
+int  stmpc_pop_c51_size(const stmpc_c51_pop *pop);
+stmpc_c51 *stmpc_pop_c51_member(stmpc_c51_pop *pop, int m);
+int  stmpc_pop_c51_act_device(stmpc_c51_pop *pop, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps,
+                              int32_t *d_action, float *d_debug_q, void *stream);
+int  stmpc_pop_c51_push_device(stmpc_c51_pop *pop, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs,
+                               int obs_stride, const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated,
+                               const uint8_t *d_truncated, void *stream);
+int  stmpc_pop_c51_update_device(stmpc_c51_pop *pop, int n_updates, const double *lr, int n_lr, void *stream);
+int  stmpc_pop_c51_stats_device(stmpc_c51_pop *pop, double *d_out, void *stream);
+int  stmpc_pop_c51_per_enable(stmpc_c51_pop *pop, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P);
+int  stmpc_pop_c51_multi_step_enable(stmpc_c51_pop *pop, const stmpc_nstep_cfg *cfgs, int P);
+int  stmpc_pop_c51_replay_read(stmpc_c51 *learner, int64_t first, int64_t count, float *rows);
+int  stmpc_pop_c51_multi_step_window(stmpc_c51 *learner, const int64_t *idx, int n_idx, double *out);
+
+/*
  * A Q-network as the policy of the combined controller and of the first-step shield: DQNAgent.get_control (dqn.py:375-380) -- state vector -> Q ->
  * argmax -> JERK_VALUES_DQN[a] -- for N states in ONE launch, behind which RLAgent.do_combined_control runs as it does behind the DDPG actor.
  * (Additive: new entries only, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8; no entry above changes what it computes.)  The

@@ -326,6 +326,9 @@ EXPORTS = (
     "stmpc_c51_per_tree_read", "stmpc_c51_per_last_device", "stmpc_c51_multi_step_enable", "stmpc_c51_replay_read", "stmpc_c51_dzout_read", "stmpc_c51_padded_read",
     "stmpc_pop_dqn_create", "stmpc_pop_dqn_destroy", "stmpc_pop_dqn_size", "stmpc_pop_dqn_member", "stmpc_pop_dqn_act_device",
     "stmpc_pop_dqn_push_device", "stmpc_pop_dqn_update_device", "stmpc_pop_dqn_stats_device", "stmpc_pop_dqn_per_enable", "stmpc_pop_dqn_replay_read",
+    "stmpc_pop_c51_create", "stmpc_pop_c51_destroy", "stmpc_pop_c51_size", "stmpc_pop_c51_member", "stmpc_pop_c51_act_device",
+    "stmpc_pop_c51_push_device", "stmpc_pop_c51_update_device", "stmpc_pop_c51_stats_device", "stmpc_pop_c51_per_enable",
+    "stmpc_pop_c51_multi_step_enable", "stmpc_pop_c51_replay_read", "stmpc_pop_c51_multi_step_window",
     "stmpc_nstep_enable_ddpg", "stmpc_nstep_enable_dqn", "stmpc_pop_nstep_enable_ddpg", "stmpc_pop_nstep_enable_td3", "stmpc_pop_nstep_enable_dqn",
     "stmpc_nstep_window_ddpg", "stmpc_nstep_window_dqn",
     "stmpc_qactor_create", "stmpc_qactor_view_dqn", "stmpc_qactor_destroy", "stmpc_qactor_set_limits", "stmpc_qactor_eval_device",
@@ -353,6 +356,7 @@ DDPG_ROW, DDPG_NCOUNTERS = 68, 8      # STMPC_DDPG_ROW, STMPC_DDPG_NCOUNTERS
 DDPG_POP_MAX = 64                     # STMPC_DDPG_POP_MAX
 TD3_POP_MAX = 64                      # STMPC_TD3_POP_MAX
 DQN_POP_MAX = 64                      # STMPC_DQN_POP_MAX
+C51_POP_MAX = 64                      # STMPC_C51_POP_MAX
 SIM_GROUPS_MAX = 64                   # STMPC_SIM_GROUPS_MAX
 SOLVER_GROUPS_MAX = 512               # STMPC_SOLVER_GROUPS_MAX
 ENV_REWARD_GROUPS_MAX = 64            # STMPC_ENV_REWARD_GROUPS_MAX
@@ -582,6 +586,20 @@ def load():
     lib.stmpc_pop_dqn_stats_device.argtypes = [vp, vp, vp]
     lib.stmpc_pop_dqn_per_enable.argtypes = [vp, C.POINTER(PERCfg), C.POINTER(C.c_uint8), C.c_int]
     lib.stmpc_pop_dqn_replay_read.argtypes = [vp, C.c_int64, C.c_int64, fp]
+    lib.stmpc_pop_c51_create.argtypes = [vp, C.POINTER(C51Cfg), C.c_int, C.POINTER(vp)]
+    lib.stmpc_pop_c51_destroy.argtypes = [vp]
+    lib.stmpc_pop_c51_destroy.restype = None
+    lib.stmpc_pop_c51_size.argtypes = [vp]
+    lib.stmpc_pop_c51_member.argtypes = [vp, C.c_int]
+    lib.stmpc_pop_c51_member.restype = vp
+    lib.stmpc_pop_c51_act_device.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]
+    lib.stmpc_pop_c51_push_device.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int] + [vp] * 4 + [vp]
+    lib.stmpc_pop_c51_update_device.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.c_int, vp]
+    lib.stmpc_pop_c51_stats_device.argtypes = [vp, vp, vp]
+    lib.stmpc_pop_c51_per_enable.argtypes = [vp, C.POINTER(PERCfg), C.POINTER(C.c_uint8), C.c_int]
+    lib.stmpc_pop_c51_multi_step_enable.argtypes = [vp, C.POINTER(NStepCfg), C.c_int]
+    lib.stmpc_pop_c51_replay_read.argtypes = [vp, C.c_int64, C.c_int64, fp]
+    lib.stmpc_pop_c51_multi_step_window.argtypes = [vp, i64p, C.c_int, dp]
     for name in ("stmpc_nstep_enable_ddpg", "stmpc_nstep_enable_dqn"):
         getattr(lib, name).argtypes = [vp, C.POINTER(NStepCfg)]
     for name in ("stmpc_pop_nstep_enable_ddpg", "stmpc_pop_nstep_enable_td3", "stmpc_pop_nstep_enable_dqn"):
@@ -1376,12 +1394,70 @@ class Context:
     def dqn_pop_per_enable(self, handle, cfgs):
         self._chk(self._lib.stmpc_pop_dqn_per_enable(handle, *self._per_table(cfgs)))
 
+    # -- C51 population (stmpc_pop_c51_*): P C51 learners, one launch per kernel; the DQN population's methods on its own handle --------------
+    def c51_pop_create(self, cfgs):
+        """``cfgs``: a sequence of ``C51Cfg``; the library checks the member count and that the launch shapes (n_atoms included) are common."""
+        arr = (C51Cfg * len(cfgs))(*cfgs)
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_pop_c51_create(self._h, arr, len(cfgs), C.byref(h)))
+        return h
+
+    def c51_pop_destroy(self, handle):
+        self._lib.stmpc_pop_c51_destroy(handle)
+
+    def c51_pop_size(self, handle):
+        return int(self._lib.stmpc_pop_c51_size(handle))
+
+    def c51_pop_member(self, handle, m):
+        """The m-th member as a borrowed ``stmpc_c51`` handle for the ``c51_*`` methods above (never ``c51_destroy`` it)."""
+        h = self._lib.stmpc_pop_c51_member(handle, int(m))
+        if not h:
+            self._chk(STMPC_EINVAL)
+        return C.c_void_p(h)
+
+    def c51_pop_act(self, handle, n_per_member, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
+        """``eps``: one value per member (the library checks the length and the range)."""
+        e = np.ascontiguousarray(eps, dtype=np.float64).reshape(-1)
+        self._chk(self._lib.stmpc_pop_c51_act_device(handle, int(n_per_member), d_obs, int(obs_stride), _dptr(e), int(e.size), d_action, d_debug_q, stream))
+
+    def c51_pop_push(self, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
+        self._chk(self._lib.stmpc_pop_c51_push_device(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated,
+                                                      d_truncated, stream))
+
+    def c51_pop_update(self, handle, n_updates, lr, stream=0):
+        """``lr``: one learning rate per member (the library checks the length)."""
+        lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
+        self._chk(self._lib.stmpc_pop_c51_update_device(handle, int(n_updates), _dptr(lr), int(lr.size), stream))
+
+    def c51_pop_stats(self, handle, d_out, stream=0):
+        self._chk(self._lib.stmpc_pop_c51_stats_device(handle, d_out, stream))
+
+    def c51_pop_per_enable(self, handle, cfgs):
+        self._chk(self._lib.stmpc_pop_c51_per_enable(handle, *self._per_table(cfgs)))
+
+    def c51_pop_multi_step_enable(self, handle, cfgs):
+        """``cfgs``: one ``NStepCfg`` per member (the stmpc_pop_nstep_ prefix is a closed set: ``pop_nstep_enable`` routes the kind "c51" here)."""
+        table = (NStepCfg * len(cfgs))(*cfgs)
+        self._chk(self._lib.stmpc_pop_c51_multi_step_enable(handle, table, len(cfgs)))
+
+    def c51_pop_replay_read(self, learner_handle, first, count):
+        """Debug: ``count`` rows from row ``first`` of a C51 learner's ring (a borrowed member's or a lone learner's), float32 [count][DDPG_ROW]; synchronises."""
+        rows = np.zeros((int(count), DDPG_ROW), dtype=np.float32)
+        self._chk(self._lib.stmpc_pop_c51_replay_read(learner_handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
+        return rows
+
+    def c51_pop_multi_step_window(self, learner_handle, idx):
+        """Debug: ``nstep_window`` for a C51 learner's handle (a borrowed member's or a lone learner's): float64 [len(idx)][4]; synchronises."""
+        return self.nstep_window("c51", learner_handle, idx)
+
     # -- multi-step returns (stmpc_nstep_*, stmpc_pop_nstep_*): once per learner / population, on empty rings; ``kind``: "ddpg" (a TD3 learner's base too), "td3" (populations) or "dqn"
     def nstep_enable(self, kind, handle, cfg):
         name = "stmpc_c51_multi_step_enable" if kind == "c51" else "stmpc_nstep_enable_" + kind      # (the stmpc_nstep_ prefix is a closed set)
         self._chk(getattr(self._lib, name)(handle, C.byref(cfg)))
 
     def pop_nstep_enable(self, kind, handle, cfgs):
+        if kind == "c51":                                           # (the stmpc_pop_nstep_ prefix is a closed set)
+            return self.c51_pop_multi_step_enable(handle, cfgs)
         table = (NStepCfg * len(cfgs))(*cfgs)
         self._chk(getattr(self._lib, "stmpc_pop_nstep_enable_" + kind)(handle, table, len(cfgs)))
 
@@ -1389,7 +1465,8 @@ class Context:
         """Debug: float64 [len(idx)][4] = R, disc, the ring row of the window's last transition, m of the ring rows ``idx``; synchronises."""
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         out = np.zeros((idx.size, 4), dtype=np.float64)
-        self._chk(getattr(self._lib, "stmpc_nstep_window_" + kind)(handle, idx.ctypes.data_as(C.POINTER(C.c_int64)), int(idx.size), out.ctypes.data_as(C.POINTER(C.c_double))))
+        name = "stmpc_pop_c51_multi_step_window" if kind == "c51" else "stmpc_nstep_window_" + kind      # (the stmpc_nstep_ prefix is a closed set)
+        self._chk(getattr(self._lib, name)(handle, idx.ctypes.data_as(C.POINTER(C.c_int64)), int(idx.size), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def dqn_pop_replay_read(self, learner_handle, first, count):

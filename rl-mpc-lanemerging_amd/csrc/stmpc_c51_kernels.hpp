@@ -238,10 +238,10 @@ __global__ void __launch_bounds__(AT_THREADS) k_c51_project(C51Dev D, int n, con
 
 // ---- acting -------------------------------------------------------------------------------------------------------------------------------------
 // k_dqn_act with the expected values in Q's place: the greedy index is their first maximum; the epsilon draw has k_dqn_act's stream constant and
-// counter rule.  dbg_q (may be null) float32 [N][A]: the expected values
-__global__ void __launch_bounds__(AT_THREADS) k_c51_act(C51Dev D, int N, const float *__restrict__ obs, int obs_stride, float eps, int explore,
-                                                        int *__restrict__ action, float *__restrict__ dbg_q) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+// counter rule.  dbg_q (may be null) float32 [N][A]: the expected values.  (A __device__ body like the others: k_c51_act_pop of
+// stmpc_c51_pop_kernels.hpp runs it on the member blockIdx.y selects)
+__device__ __forceinline__ void c51_act_body(const C51Dev &D, int N, const float *__restrict__ obs, int obs_stride, float eps, int explore,
+                                             int *__restrict__ action, float *__restrict__ dbg_q, unsigned char *dg_smem) {
     const DdpgDev &L = D.dq.base;
     const DdpgTile T = ddpg_tile(dg_smem, L.h1p, D.dq.Ap);
     const int tid = threadIdx.x, e0 = blockIdx.x * AT_TM, row = tid >> 5, part = tid & 31, e = e0 + row;
@@ -261,6 +261,11 @@ __global__ void __launch_bounds__(AT_THREADS) k_c51_act(C51Dev D, int N, const f
     }
     __syncthreads();
     if (explore && tid == 0 && dg_last_block(L.tick + DG_T_ACT, gridDim.x)) L.cnt[DG_ACTS] = acts + 1;
+}
+__global__ void __launch_bounds__(AT_THREADS) k_c51_act(C51Dev D, int N, const float *__restrict__ obs, int obs_stride, float eps, int explore,
+                                                        int *__restrict__ action, float *__restrict__ dbg_q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    c51_act_body(D, N, obs, obs_stride, eps, explore, action, dbg_q, dg_smem);
 }
 
 }  // namespace stmpc

@@ -4,7 +4,8 @@
 // ddpg_refresh), the TD3 learner on a DDPG learner as base plus critic 2 (stmpc_td3_*, td3_refresh), prioritised replay for the two (stmpc_per_*), their
 // populations on one skeleton (struct PopCore over struct PopSlot; stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_per_*; pop_upload, td3_pop_upload), actors that view a
 // learner's networks and their population (stmpc_actor_view_ddpg, stmpc_actor_pop_*), and the DQN learner for the discrete envs (stmpc_dqn_*), which
-// holds a replay store, one network and one workspace of its own, with its population on the same skeleton (stmpc_pop_dqn_*; dqn_pop_upload) and
+// holds a replay store, one network and one workspace of its own, with its population on the same skeleton (stmpc_pop_dqn_*; dqn_pop_upload), the
+// categorical learner built the same way (stmpc_c51_*) with its population (stmpc_pop_c51_*; c51_pop_upload), and
 // the Q-network as a policy behind it (stmpc_qactor_*), lone and as a population (stmpc_pop_qactor_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
@@ -17,6 +18,7 @@
 #include "stmpc_dqn_kernels.hpp"
 #include "stmpc_dqn_pop_kernels.hpp"
 #include "stmpc_c51_kernels.hpp"
+#include "stmpc_c51_pop_kernels.hpp"
 #include "stmpc_qactor_kernels.hpp"
 #include "stmpc_c51actor_kernels.hpp"
 #include "stmpc_qactor_pop_kernels.hpp"
@@ -1329,6 +1331,7 @@ struct stmpc_c51 {
     int h1p = 0, Ap = 0, np = 0;
     size_t lds = 0;
     Grid grid{};
+    bool pop_member = false;                // owned by a population (stmpc_c51_pop), whose device tables hold copies of dev and dev.dq.base
 };
 
 namespace {
@@ -1508,6 +1511,7 @@ int stmpc_c51_stats_device(stmpc_c51 *t, double *d_out, void *stream) {
 int stmpc_c51_per_enable(stmpc_c51 *t, const stmpc_per_cfg *g) {
     if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
     TRY(per_check_cfg(g));
+    if (t->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: prioritised replay is enabled on the population (stmpc_pop_c51_per_enable)");
     TRY(t->rp.check_empty());
     return per_attach(t->rp, t->dev.dq.base, nullptr, g);
 }
@@ -1524,6 +1528,7 @@ int stmpc_c51_per_last_device(stmpc_c51 *t, int64_t *d_idx, float *d_td, float *
 
 int stmpc_c51_multi_step_enable(stmpc_c51 *t, const stmpc_nstep_cfg *g) {
     if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
+    if (t->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: n_step is set on the population (stmpc_pop_c51_multi_step_enable)");
     return nstep_attach(t->rp, t->dev.dq.base, g);
 }
 
@@ -1693,6 +1698,163 @@ int stmpc_pop_nstep_enable_dqn(stmpc_dqn_pop *p, const stmpc_nstep_cfg *cfgs, in
 int stmpc_pop_dqn_replay_read(stmpc_dqn *t, int64_t first, int64_t count, float *rows) {
     if (!t) return fail(STMPC_EINVAL, "NULL argument");
     return t->rp.read_rows(first, count, rows);
+}
+
+}  // extern "C"
+
+// ---- a population of C51 learners (stmpc_pop_c51_*): P learners of the C51 section above, one launch per kernel; kernels in
+// stmpc_c51_pop_kernels.hpp, prioritised replay and the statistics on the core's DdpgDev table with stmpc_per_pop_kernels.hpp's and
+// stmpc_ddpg_pop_kernels.hpp's kernels ------------------------------------------------------------------------------------------------------------
+struct stmpc_c51_pop {
+    PopCore core;                           // core.table: the members' dev.dq.base
+    std::vector<stmpc_c51 *> members;       // owned; made by stmpc_c51_create, so every lone entry works on a borrowed member
+    DevBuf table;                           // C51Dev [P]: the members' structs (c51_pop_upload); v_min, v_max and dz travel in each member's own
+    const C51Dev *dev() const { return table.as<C51Dev>(); }
+};
+
+static_assert(STMPC_C51_POP_MAX == DG_POP_MAX && DG_POP_MAX <= 64, "DdpgLr and DqnEps hold one value, and DqnEps::explore one bit, per possible member");
+
+namespace {
+// both device tables from the members as they are now: at create, and again once prioritised replay or n_step re-wired members
+int c51_pop_upload(stmpc_c51_pop *p) {
+    std::vector<C51Dev> host;
+    for (const stmpc_c51 *t : p->members) host.push_back(t->dev);
+    TRY(upload(p->table, host.data(), host.size()));
+    return pop_upload(p->core);
+}
+int c51_pop_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling[2];
+    TRY(raise_dynamic_lds((const void *)k_c51_fwd_pop, "k_c51_fwd_pop", ceiling[0], device, lds));
+    return raise_dynamic_lds((const void *)k_c51_act_pop, "k_c51_act_pop", ceiling[1], device, lds);
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_pop_c51_create(stmpc_ctx *c, const stmpc_c51_cfg *cfgs, int P, stmpc_c51_pop **out) {
+    TRY(pop_check_create(c, cfgs, P, out, "n_obs, h1, n_actions, n_atoms, batch and capacity", [](const stmpc_c51_cfg &a, const stmpc_c51_cfg &b) {
+        return a.n_obs == b.n_obs && a.h1 == b.h1 && a.n_actions == b.n_actions && a.n_atoms == b.n_atoms && a.batch == b.batch && a.capacity == b.capacity;
+    }));
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_c51_pop *p = new stmpc_c51_pop();
+    PopCore &core = p->core;
+    core.device = c->device;
+    int rc = STMPC_OK;
+    for (int m = 0; m < P && !rc; ++m) {
+        stmpc_c51 *t = nullptr;
+        rc = stmpc_c51_create(c, cfgs + m, &t);
+        if (rc) break;
+        t->pop_member = true;
+        p->members.push_back(t);
+    }
+    if (!rc) {
+        for (stmpc_c51 *t : p->members) core.slots.push_back({&t->rp, &t->dev.dq.base, nullptr});     // (members is complete: the pointers stay)
+        const stmpc_c51 *t0 = p->members[0];
+        core.n_obs = t0->cfg.n_obs; core.capacity = t0->cfg.capacity; core.batch = t0->cfg.batch; core.lds = t0->lds;
+        rc = c51_pop_upload(p);
+    }
+    if (!rc) rc = c51_pop_raise_lds(c->device, core.lds);
+    if (rc) { stmpc_pop_c51_destroy(p); return rc; }
+    *out = p;
+    return STMPC_OK;
+}
+
+void stmpc_pop_c51_destroy(stmpc_c51_pop *p) {
+    if (!p) return;
+    for (stmpc_c51 *t : p->members) stmpc_c51_destroy(t);
+    (void)hipSetDevice(p->core.device);
+    delete p;
+}
+
+int stmpc_pop_c51_size(const stmpc_c51_pop *p) { return p ? p->core.P() : 0; }
+
+stmpc_c51 *stmpc_pop_c51_member(stmpc_c51_pop *p, int m) {
+    if (!p || m < 0 || m >= p->core.P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
+    return p->members[m];
+}
+
+int stmpc_pop_c51_act_device(stmpc_c51_pop *p, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps, int32_t *d_action,
+                             float *d_debug_q, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    const PopCore &c = p->core;
+    TRY(pop_check_rows(c, n_per_member, obs_stride));
+    if (!eps) return fail(STMPC_EINVAL, "NULL argument");
+    if (n_eps != c.P()) return fail(STMPC_EINVAL, "the eps array has " + std::to_string(n_eps) + " entries, the population " + std::to_string(c.P()) + " members");
+    DqnEps e{};
+    for (int m = 0; m < c.P(); ++m) {
+        if (!(eps[m] >= 0 && eps[m] <= 1)) return fail(STMPC_EINVAL, "member " + std::to_string(m) + "'s eps must be in 0 ... 1");
+        e.eps[m] = (float)eps[m];
+        if (eps[m] > 0) e.explore |= 1ull << m;                      // (stmpc_c51_act_device's rule: an exploring call is one with eps > 0)
+    }
+    if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c.device));
+    hipLaunchKernelGGL(k_c51_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, c.P()), dim3(AT_THREADS), c.lds, (hipStream_t)stream, p->dev(), n_per_member, d_obs,
+                       obs_stride, e, d_action, d_debug_q);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_c51_push_device(stmpc_c51_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                              const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    const PopCore &c = p->core;
+    TRY(pop_check_rows(c, n_per_member, obs_stride));
+    TRY(pop_check_push(c, n_per_member));
+    if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c.device));
+    hipLaunchKernelGGL(k_c51_push_pop, dim3(push_blocks(n_per_member), c.P()), dim3(256), 0, (hipStream_t)stream, p->dev(), n_per_member, d_obs, d_next_obs, d_final_obs,
+                       obs_stride, d_action, d_reward, d_terminated, d_truncated);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_c51_update_device(stmpc_c51_pop *p, int n_updates, const double *lr, int n_lr, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "NULL argument");
+    const PopCore &c = p->core;
+    DdpgLr lrs{};
+    TRY(pop_check_update(c, n_updates, n_lr, {{lr, &lrs}}));
+    HIPCHK(hipSetDevice(c.device));
+    const stmpc_c51 *t = p->members[0];
+    const Grid g = t->grid;
+    const int P = c.P(), B = c.batch, Bp = t->rp.Bp;
+    hipStream_t st = (hipStream_t)stream;
+    for (int u = 0; u < n_updates; ++u) {                            // stmpc_c51_update_device's three launches (five with prioritised members), each over the members
+        if (c.per_any) hipLaunchKernelGGL(k_per_sample_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, Bp, 1);
+        hipLaunchKernelGGL(k_c51_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), c.lds, st, p->dev(), B, 1);
+        hipLaunchKernelGGL(k_c51_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), Bp, 1);
+        if (c.per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, 1);
+        hipLaunchKernelGGL(k_c51_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, p->dev(), lrs, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_c51_stats_device(stmpc_c51_pop *p, double *d_out, void *stream) {
+    if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(p->core.device));
+    hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->core.dev(), p->core.batch, d_out);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_pop_c51_per_enable(stmpc_c51_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return pop_per_enable(p->core, cfgs, enabled, P, [&] { return c51_pop_upload(p); });
+}
+
+int stmpc_pop_c51_multi_step_enable(stmpc_c51_pop *p, const stmpc_nstep_cfg *cfgs, int P) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    return pop_nstep_enable(p->core, cfgs, P, [&] { return c51_pop_upload(p); });
+}
+
+int stmpc_pop_c51_replay_read(stmpc_c51 *t, int64_t first, int64_t count, float *rows) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return t->rp.read_rows(first, count, rows);
+}
+
+int stmpc_pop_c51_multi_step_window(stmpc_c51 *t, const int64_t *idx, int n_idx, double *out) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return nstep_window_read(t->rp, t->dev.dq.base, idx, n_idx, out);     // (stmpc_nstep_window_dqn's, on a borrowed member's or a lone learner's ring)
 }
 
 }  // extern "C"

@@ -48,7 +48,9 @@ three (five) launches per update whatever P is, ``eps`` and ``lr`` per member, `
 ``all`` library's rainbow preset) on the DQN learner's ring: the network emits ``n_atoms`` logits per action, Q(s, a) is the mean of their softmax over
 a fixed support, and the update minimises the cross-entropy against the projected Bellman-shifted target distribution (Bellemare et al. 2017,
 Algorithm 1) -- three launches per update, five with ``per``; ``n_step`` as the DQN learner's.  Twins: ``c51_support``, ``c51_project_host``,
-``c51_project_scatter_host``, ``c51_targets_host``, ``update_host_c51``; ``train_dqn`` takes it as it takes a ``DQNLearner``.
+``c51_project_scatter_host``, ``c51_targets_host``, ``update_host_c51``; ``train_dqn`` takes it as it takes a ``DQNLearner``.  ``C51Population``
+(``csrc/stmpc_c51_pop_kernels.hpp``, ``stmpc_pop_c51_*``) is to it what ``DQNPopulation`` is to ``DQNLearner``: P independent C51 learners -- the
+support, ``double``, ``target_period``, ``gamma``, ``n_step``, the seed and ``per=`` per member -- for the launch count of one.
 """
 import math
 
@@ -1563,9 +1565,9 @@ class C51Learner(_Learner):
         self.ctx = ctx if ctx is not None else (env.ctx if env is not None else _capi.Context(-1))
         self.seed = int(seed)
         self.device = torch.device("cuda", torch.cuda.current_device())
-        self.handle = self.ctx.c51_create(self.cfg.to_c(self.seed))
+        self.handle = self._make_handle()
         self._enable_nstep(env, rows_per_push)
-        if self.cfg.per is not None:
+        if self.cfg.per is not None:                                # (a population member's handle refuses: the population enables its members)
             self.ctx.c51_per_enable(self.handle, self.cfg.per.to_c())
         c = self.cfg
         self._n_out = A * c.n_atoms
@@ -1576,6 +1578,9 @@ class C51Learner(_Learner):
         self.load_state_dict({"params": new_params_dqn(net), "counters": None})
         self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self._actions = {}
+
+    def _make_handle(self):
+        return self.ctx.c51_create(self.cfg.to_c(self.seed))
 
     def _slot(self, i):
         return unflatten_q(self.ctx.c51_get_params(self.handle, i, self._len), self.cfg.n_obs, self.cfg.h1, self._n_out)
@@ -1647,6 +1652,62 @@ class C51Learner(_Learner):
             np.savez_compressed(fh, **self._slot(0), action_values=self.action_values, n_atoms=np.int64(self.cfg.n_atoms), v_min=np.float64(self.cfg.v_min),
                                 v_max=np.float64(self.cfg.v_max))
         return path
+
+
+class _C51PopulationMember(C51Learner):
+    """One member of a ``C51Population`` as a ``C51Learner``: the handle is borrowed from the population (``stmpc_pop_c51_member``), which outlives
+    it; everything else -- the seeded initialisation, ``action_values`` and ``env_id`` from the env included -- is the lone learner's code."""
+
+    _owns_handle = False
+
+    def __init__(self, population, m, env, cfg, seed, init):
+        self._population, self._borrowed = population, population.ctx.c51_pop_member(population.handle, m)
+        super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
+
+    def _make_handle(self):
+        return self._borrowed
+
+    def __del__(self):
+        self.handle = None                                          # the population destroys its members
+
+
+class C51Population(DQNPopulation):
+    """P independent C51 learners on one discrete-action ``MergeVecEnv``, advanced together: three launches per update whatever P is (five when at
+    least one member is prioritised), one each for acting, pushing and the statistics (``csrc/stmpc_c51_pop_kernels.hpp``, ``stmpc_pop_c51_*``).
+    The questions a user has about the categorical agent -- which support ``[v_min, v_max]`` fits this env's returns, double against plain action
+    selection, which ``target_period``, ``gamma``, ``n_step`` and seed, prioritised against uniform replay -- are a population's members side by side.
+
+    ``cfgs``: a list of ``C51Config`` or ``(cfg, P)``; the members share n_obs, h1, n_actions, n_atoms, batch and capacity and may differ in
+    everything else, the support included.  ``env``, ``seeds``, ``init``, ``per``, traffic groups and reward groups: as ``DQNPopulation``'s.  Member
+    m starts exactly as ``C51Learner(seed=seeds[m], init=...)`` does and stays bit-identical to that learner driven on its slice alone.
+
+    ``act`` / ``push`` / ``update`` / ``stats_device`` / ``stats`` are ``DQNPopulation``'s; ``act(..., debug_q=)`` gives the expected values
+    float32 [env.n][n_actions].  ``member(m)`` is a ``C51Learner`` view: ``state_dict`` / ``load_state_dict``, ``grads``, ``targets``, ``dist``,
+    ``project``, ``minibatch``, ``priorities``, ``last_sample``, ``nstep_window``, ``export_q``, ``actor.C51Actor.from_learner(pop.member(m), ...)`` and
+    ``evaluate_dqn(pop.member(m), ...)`` work on it.  ``train_dqn`` takes a population.  A population of C51 POLICIES does not exist:
+    ``evaluate_dqn_members``, ``actor.QActorPopulation`` and ``actor.population_of`` refuse a ``C51Population`` as they refuse C51 members."""
+
+    _api, _nstat = "c51_pop", 4
+    _nstep_kind = "c51"                                             # (``ctx.pop_nstep_enable`` routes it to stmpc_pop_c51_multi_step_enable)
+    _cfg_type, _action_dtype = C51Config, "int32"
+
+    def _check_env(self, env):
+        if env.continuous:
+            raise ValueError("C51 needs a discrete action space (sumo-jerk-v0 or sumo-accel-v0), not the continuous jerk env")
+
+    def _check_cfgs(self, env):
+        for m, c in enumerate(self.cfgs):
+            if not isinstance(c, C51Config):
+                raise ValueError("member %d's cfg is a %s, not a C51Config" % (m, type(c).__name__))
+        super()._check_cfgs(env)
+        for m, c in enumerate(self.cfgs):
+            c.check_width()
+            if c.n_atoms != self.cfgs[0].n_atoms:
+                raise ValueError("member %d has n_atoms %d, member 0 has %d: the members share n_obs, h1, n_actions, n_atoms, batch and capacity"
+                                 % (m, c.n_atoms, self.cfgs[0].n_atoms))
+
+    def _make_member(self, m, env, init):
+        return _C51PopulationMember(self, m, env, self.cfgs[m], self.seeds[m], init)
 
 
 class _TakeoverShare:
@@ -1820,6 +1881,8 @@ def evaluate_dqn_members(source, n_per_member, seed=0, kmax=16, max_episode_leng
     if controller not in ("combined", "first_step"):
         raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
     members = source if isinstance(source, (DQNPopulation, list, tuple)) else [source]
+    if isinstance(members, C51Population):
+        _actor.refuse_c51_members([members.member(m) for m in range(members.P)], "evaluate_dqn_members")
     if not isinstance(members, DQNPopulation):
         _actor.refuse_c51_members(members, "evaluate_dqn_members")      # (before a context exists: a C51 policy is evaluated alone, by evaluate_dqn)
     P = members.P if isinstance(members, DQNPopulation) else len(members)
