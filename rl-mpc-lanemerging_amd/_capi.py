@@ -5,6 +5,7 @@ fallback -- if ``libstmpc.so`` is missing the import of this module raises, and 
 is visible ``Context()`` raises ``StmpcError(STMPC_ENODEV)``.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -1193,144 +1194,87 @@ class Context:
     def td3_pop_per_enable(self, handle, cfgs):
         self._chk(self._lib.stmpc_pop_per_enable_td3(handle, *self._per_table(cfgs)))
 
-    # -- DQN learner (stmpc_dqn_*): the discrete agent; the handle belongs to this context's device ------------------------
-    def dqn_create(self, cfg):
+    # -- the discrete learners (stmpc_dqn_*, stmpc_c51_*): the DQN agent and the categorical one; the handle belongs to this context's device.  The
+    # entries both have are written once with the ``kind`` ("dqn" or "c51") in front and bound as ``dqn_<name>`` and ``c51_<name>`` below the class
+    def _q(self, kind, name):
+        return getattr(self._lib, "stmpc_%s_%s" % (kind, name))
+
+    def _q_create(self, kind, cfg):
         h = C.c_void_p()
-        self._chk(self._lib.stmpc_dqn_create(self._h, C.byref(cfg), C.byref(h)))
+        self._chk(self._q(kind, "create")(self._h, C.byref(cfg), C.byref(h)))
         return h
 
-    def dqn_destroy(self, handle):
-        self._lib.stmpc_dqn_destroy(handle)
+    def _q_destroy(self, kind, handle):
+        self._q(kind, "destroy")(handle)
 
-    def dqn_set_params(self, handle, slot, flat):
+    def _q_set_params(self, kind, handle, slot, flat):
         flat = np.ascontiguousarray(flat, dtype=np.float32)
-        self._chk(self._lib.stmpc_dqn_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        self._chk(self._q(kind, "set_params")(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
 
-    def dqn_get_params(self, handle, slot, count):
+    def _q_get_params(self, kind, handle, slot, count):
         flat = np.empty(int(count), dtype=np.float32)
-        self._chk(self._lib.stmpc_dqn_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        self._chk(self._q(kind, "get_params")(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
         return flat
 
-    def dqn_set_state(self, handle, counters, beta_pow):
+    def _q_set_state(self, kind, handle, counters, beta_pow):
         cn = np.ascontiguousarray(counters, dtype=np.int64)
         bp = np.ascontiguousarray(beta_pow, dtype=np.float32)
         assert cn.size == DDPG_NCOUNTERS and bp.size == 2
-        self._chk(self._lib.stmpc_dqn_set_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
+        self._chk(self._q(kind, "set_state")(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
 
-    def dqn_get_state(self, handle):
+    def _q_get_state(self, kind, handle):
         """(counters int64 [8]: cursor, fill, updates, exploring acting calls, frames, ...; Adam's beta powers float32 [2]); synchronises."""
         cn, bp = np.zeros(DDPG_NCOUNTERS, dtype=np.int64), np.zeros(2, dtype=np.float32)
-        self._chk(self._lib.stmpc_dqn_get_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
+        self._chk(self._q(kind, "get_state")(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
         return cn, bp
 
-    def dqn_push(self, handle, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
-        self._chk(self._lib.stmpc_dqn_push_device(handle, int(N), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated, d_truncated,
-                                                  stream))
+    def _q_push(self, kind, handle, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
+        self._chk(self._q(kind, "push_device")(handle, int(N), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated, d_truncated, stream))
 
-    def dqn_act(self, handle, N, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
-        self._chk(self._lib.stmpc_dqn_act_device(handle, int(N), d_obs, int(obs_stride), float(eps), d_action, d_debug_q, stream))
+    def _q_act(self, kind, handle, N, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
+        self._chk(self._q(kind, "act_device")(handle, int(N), d_obs, int(obs_stride), float(eps), d_action, d_debug_q, stream))
 
-    def dqn_update(self, handle, n_updates, lr, stream=0):
-        self._chk(self._lib.stmpc_dqn_update_device(handle, int(n_updates), float(lr), stream))
+    def _q_update(self, kind, handle, n_updates, lr, stream=0):
+        self._chk(self._q(kind, "update_device")(handle, int(n_updates), float(lr), stream))
 
-    def dqn_grads(self, handle, d_grad, stream=0):
-        self._chk(self._lib.stmpc_dqn_grads_device(handle, d_grad, stream))
+    def _q_grads(self, kind, handle, d_grad, stream=0):
+        self._chk(self._q(kind, "grads_device")(handle, d_grad, stream))
 
-    def dqn_targets(self, handle, d_out, stream=0):
-        self._chk(self._lib.stmpc_dqn_targets_device(handle, d_out, stream))
+    def _q_targets(self, kind, handle, d_out, stream=0):
+        self._chk(self._q(kind, "targets_device")(handle, d_out, stream))
 
-    def dqn_gather(self, handle, d_rows, stream=0):
-        self._chk(self._lib.stmpc_dqn_gather_device(handle, d_rows, stream))
+    def _q_gather(self, kind, handle, d_rows, stream=0):
+        self._chk(self._q(kind, "gather_device")(handle, d_rows, stream))
 
-    def dqn_stats(self, handle, d_out, stream=0):
-        self._chk(self._lib.stmpc_dqn_stats_device(handle, d_out, stream))
+    def _q_stats(self, kind, handle, d_out, stream=0):
+        self._chk(self._q(kind, "stats_device")(handle, d_out, stream))
 
-    def dqn_per_enable(self, handle, cfg):
-        self._chk(self._lib.stmpc_dqn_per_enable(handle, C.byref(cfg)))
+    def _q_per_enable(self, kind, handle, cfg):
+        self._chk(self._q(kind, "per_enable")(handle, C.byref(cfg)))
 
-    def dqn_per_tree_read(self, handle, first, count):
+    def _q_per_tree_read(self, kind, handle, first, count):
         nodes = np.empty(int(count), dtype=np.float64)
-        self._chk(self._lib.stmpc_dqn_per_tree_read(handle, int(first), int(count), nodes.ctypes.data_as(C.POINTER(C.c_double))))
+        self._chk(self._q(kind, "per_tree_read")(handle, int(first), int(count), nodes.ctypes.data_as(C.POINTER(C.c_double))))
         return nodes
 
-    def dqn_per_last(self, handle, d_idx, d_td, d_weight, stream=0):
-        self._chk(self._lib.stmpc_dqn_per_last_device(handle, d_idx, d_td, d_weight, stream))
+    def _q_per_last(self, kind, handle, d_idx, d_td, d_weight, stream=0):
+        self._chk(self._q(kind, "per_last_device")(handle, d_idx, d_td, d_weight, stream))
 
-    def dqn_padded_read(self, handle, slot, h1, n_actions):
-        """Debug: a slot (0 ... 3, or ``DQN_GRAD``) in the library's padded layout as {w0 [h1p][32], b0 [h1p], w1 [Ap][h1p], b1 [Ap]}; synchronises."""
-        h1p, Ap = (int(h1) + 15) & ~15, (int(n_actions) + 15) & ~15
+    def _q_padded_read(self, kind, handle, slot, h1, n_out):
+        """Debug: a slot (0 ... 3, or ``DQN_GRAD`` / ``C51_GRAD``) in the library's padded layout as {w0 [h1p][32], b0 [h1p], w1 [Ap][h1p], b1 [Ap]};
+        ``n_out``: the network's output width, n_actions of DQN and n_actions * n_atoms of C51; synchronises."""
+        h1p, Ap = (int(h1) + 15) & ~15, (int(n_out) + 15) & ~15
         flat = np.empty(33 * h1p + (h1p + 1) * Ap, dtype=np.float32)
-        self._chk(self._lib.stmpc_dqn_padded_read(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        self._chk(self._q(kind, "padded_read")(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
         o = np.cumsum([0, 32 * h1p, h1p, Ap * h1p, Ap])
         return {"w0": flat[o[0]:o[1]].reshape(h1p, 32), "b0": flat[o[1]:o[2]], "w1": flat[o[2]:o[3]].reshape(Ap, h1p), "b1": flat[o[3]:o[4]]}
 
-    # -- C51 learner (stmpc_c51_*): the categorical DQN agent; the DQN learner's methods on its own handle, plus the distribution's debug entries ----
-    def c51_create(self, cfg):
-        h = C.c_void_p()
-        self._chk(self._lib.stmpc_c51_create(self._h, C.byref(cfg), C.byref(h)))
-        return h
-
-    def c51_destroy(self, handle):
-        self._lib.stmpc_c51_destroy(handle)
-
-    def c51_set_params(self, handle, slot, flat):
-        flat = np.ascontiguousarray(flat, dtype=np.float32)
-        self._chk(self._lib.stmpc_c51_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
-
-    def c51_get_params(self, handle, slot, count):
-        flat = np.empty(int(count), dtype=np.float32)
-        self._chk(self._lib.stmpc_c51_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
-        return flat
-
-    def c51_set_state(self, handle, counters, beta_pow):
-        cn = np.ascontiguousarray(counters, dtype=np.int64)
-        bp = np.ascontiguousarray(beta_pow, dtype=np.float32)
-        assert cn.size == DDPG_NCOUNTERS and bp.size == 2
-        self._chk(self._lib.stmpc_c51_set_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
-
-    def c51_get_state(self, handle):
-        cn, bp = np.zeros(DDPG_NCOUNTERS, dtype=np.int64), np.zeros(2, dtype=np.float32)
-        self._chk(self._lib.stmpc_c51_get_state(handle, cn.ctypes.data_as(C.POINTER(C.c_int64)), bp.ctypes.data_as(C.POINTER(C.c_float))))
-        return cn, bp
-
-    def c51_push(self, handle, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
-        self._chk(self._lib.stmpc_c51_push_device(handle, int(N), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated, d_truncated,
-                                                  stream))
-
-    def c51_act(self, handle, N, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
-        self._chk(self._lib.stmpc_c51_act_device(handle, int(N), d_obs, int(obs_stride), float(eps), d_action, d_debug_q, stream))
-
-    def c51_update(self, handle, n_updates, lr, stream=0):
-        self._chk(self._lib.stmpc_c51_update_device(handle, int(n_updates), float(lr), stream))
-
-    def c51_grads(self, handle, d_grad, stream=0):
-        self._chk(self._lib.stmpc_c51_grads_device(handle, d_grad, stream))
-
-    def c51_targets(self, handle, d_out, stream=0):
-        self._chk(self._lib.stmpc_c51_targets_device(handle, d_out, stream))
-
+    # -- what the C51 learner has on top: the distribution's debug entries ----
     def c51_dist(self, handle, d_dist, d_out=0, stream=0):
         self._chk(self._lib.stmpc_c51_dist_device(handle, d_dist, d_out, stream))
 
     def c51_project(self, handle, n, d_p, d_reward, d_mask, d_disc, d_m, stream=0):
         self._chk(self._lib.stmpc_c51_project_device(handle, int(n), d_p, d_reward, d_mask, d_disc, d_m, stream))
-
-    def c51_gather(self, handle, d_rows, stream=0):
-        self._chk(self._lib.stmpc_c51_gather_device(handle, d_rows, stream))
-
-    def c51_stats(self, handle, d_out, stream=0):
-        self._chk(self._lib.stmpc_c51_stats_device(handle, d_out, stream))
-
-    def c51_per_enable(self, handle, cfg):
-        self._chk(self._lib.stmpc_c51_per_enable(handle, C.byref(cfg)))
-
-    def c51_per_tree_read(self, handle, first, count):
-        nodes = np.empty(int(count), dtype=np.float64)
-        self._chk(self._lib.stmpc_c51_per_tree_read(handle, int(first), int(count), nodes.ctypes.data_as(C.POINTER(C.c_double))))
-        return nodes
-
-    def c51_per_last(self, handle, d_idx, d_td, d_weight, stream=0):
-        self._chk(self._lib.stmpc_c51_per_last_device(handle, d_idx, d_td, d_weight, stream))
 
     def c51_replay_read(self, handle, first, count):
         """Debug: ``count`` rows from row ``first`` of a C51 learner's ring, float32 [count][DDPG_ROW]; synchronises."""
@@ -1344,107 +1288,62 @@ class Context:
         self._chk(self._lib.stmpc_c51_dzout_read(handle, out.ctypes.data_as(C.POINTER(C.c_float)), int(out.size)))
         return out
 
-    def c51_padded_read(self, handle, slot, h1, n_logits):
-        """Debug: a slot (0 ... 3, or ``C51_GRAD``) in the library's padded layout as {w0 [h1p][32], b0 [h1p], w1 [Ap][h1p], b1 [Ap]}, ``n_logits`` =
-        n_actions * n_atoms; synchronises."""
-        h1p, Ap = (int(h1) + 15) & ~15, (int(n_logits) + 15) & ~15
-        flat = np.empty(33 * h1p + (h1p + 1) * Ap, dtype=np.float32)
-        self._chk(self._lib.stmpc_c51_padded_read(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
-        o = np.cumsum([0, 32 * h1p, h1p, Ap * h1p, Ap])
-        return {"w0": flat[o[0]:o[1]].reshape(h1p, 32), "b0": flat[o[1]:o[2]], "w1": flat[o[2]:o[3]].reshape(Ap, h1p), "b1": flat[o[3]:o[4]]}
+    # -- populations of discrete learners (stmpc_pop_dqn_*, stmpc_pop_c51_*): P learners, one launch per kernel (dqn.py:257-359); written once as the
+    # lone learners' are, and bound as ``dqn_pop_<name>`` and ``c51_pop_<name>`` below the class
+    def _q_pop(self, kind, name):
+        return getattr(self._lib, "stmpc_pop_%s_%s" % (kind, name))
 
-    # -- DQN population (stmpc_pop_dqn_*): P DQN learners, one launch per kernel (dqn.py:257-359) ------------------------
-    def dqn_pop_create(self, cfgs):
-        """``cfgs``: a sequence of ``DQNCfg``; the library checks the member count and that the launch shapes are common."""
-        arr = (DQNCfg * len(cfgs))(*cfgs)
+    def _q_pop_create(self, kind, cfgs):
+        """``cfgs``: a sequence of ``DQNCfg`` / ``C51Cfg``; the library checks the member count and that the launch shapes (a C51 population's n_atoms
+        included) are common."""
+        arr = ({"dqn": DQNCfg, "c51": C51Cfg}[kind] * len(cfgs))(*cfgs)
         h = C.c_void_p()
-        self._chk(self._lib.stmpc_pop_dqn_create(self._h, arr, len(cfgs), C.byref(h)))
+        self._chk(self._q_pop(kind, "create")(self._h, arr, len(cfgs), C.byref(h)))
         return h
 
-    def dqn_pop_destroy(self, handle):
-        self._lib.stmpc_pop_dqn_destroy(handle)
+    def _q_pop_destroy(self, kind, handle):
+        self._q_pop(kind, "destroy")(handle)
 
-    def dqn_pop_size(self, handle):
-        return int(self._lib.stmpc_pop_dqn_size(handle))
+    def _q_pop_size(self, kind, handle):
+        return int(self._q_pop(kind, "size")(handle))
 
-    def dqn_pop_member(self, handle, m):
-        """The m-th member as a borrowed ``stmpc_dqn`` handle for the ``dqn_*`` methods above (never ``dqn_destroy`` it)."""
-        h = self._lib.stmpc_pop_dqn_member(handle, int(m))
+    def _q_pop_member(self, kind, handle, m):
+        """The m-th member as a borrowed ``stmpc_dqn`` / ``stmpc_c51`` handle for the lone learner's methods above (never destroy it)."""
+        h = self._q_pop(kind, "member")(handle, int(m))
         if not h:
             self._chk(STMPC_EINVAL)
         return C.c_void_p(h)
 
-    def dqn_pop_act(self, handle, n_per_member, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
+    def _q_pop_act(self, kind, handle, n_per_member, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
         """``eps``: one value per member (the library checks the length and the range)."""
         e = np.ascontiguousarray(eps, dtype=np.float64).reshape(-1)
-        self._chk(self._lib.stmpc_pop_dqn_act_device(handle, int(n_per_member), d_obs, int(obs_stride), _dptr(e), int(e.size), d_action, d_debug_q, stream))
+        self._chk(self._q_pop(kind, "act_device")(handle, int(n_per_member), d_obs, int(obs_stride), _dptr(e), int(e.size), d_action, d_debug_q, stream))
 
-    def dqn_pop_push(self, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
-        self._chk(self._lib.stmpc_pop_dqn_push_device(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated,
-                                                      d_truncated, stream))
+    def _q_pop_push(self, kind, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
+        self._chk(self._q_pop(kind, "push_device")(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated,
+                                                   d_truncated, stream))
 
-    def dqn_pop_update(self, handle, n_updates, lr, stream=0):
+    def _q_pop_update(self, kind, handle, n_updates, lr, stream=0):
         """``lr``: one learning rate per member (the library checks the length)."""
         lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
-        self._chk(self._lib.stmpc_pop_dqn_update_device(handle, int(n_updates), _dptr(lr), int(lr.size), stream))
+        self._chk(self._q_pop(kind, "update_device")(handle, int(n_updates), _dptr(lr), int(lr.size), stream))
 
-    def dqn_pop_stats(self, handle, d_out, stream=0):
-        self._chk(self._lib.stmpc_pop_dqn_stats_device(handle, d_out, stream))
+    def _q_pop_stats(self, kind, handle, d_out, stream=0):
+        self._chk(self._q_pop(kind, "stats_device")(handle, d_out, stream))
 
-    def dqn_pop_per_enable(self, handle, cfgs):
-        self._chk(self._lib.stmpc_pop_dqn_per_enable(handle, *self._per_table(cfgs)))
+    def _q_pop_per_enable(self, kind, handle, cfgs):
+        self._chk(self._q_pop(kind, "per_enable")(handle, *self._per_table(cfgs)))
 
-    # -- C51 population (stmpc_pop_c51_*): P C51 learners, one launch per kernel; the DQN population's methods on its own handle --------------
-    def c51_pop_create(self, cfgs):
-        """``cfgs``: a sequence of ``C51Cfg``; the library checks the member count and that the launch shapes (n_atoms included) are common."""
-        arr = (C51Cfg * len(cfgs))(*cfgs)
-        h = C.c_void_p()
-        self._chk(self._lib.stmpc_pop_c51_create(self._h, arr, len(cfgs), C.byref(h)))
-        return h
-
-    def c51_pop_destroy(self, handle):
-        self._lib.stmpc_pop_c51_destroy(handle)
-
-    def c51_pop_size(self, handle):
-        return int(self._lib.stmpc_pop_c51_size(handle))
-
-    def c51_pop_member(self, handle, m):
-        """The m-th member as a borrowed ``stmpc_c51`` handle for the ``c51_*`` methods above (never ``c51_destroy`` it)."""
-        h = self._lib.stmpc_pop_c51_member(handle, int(m))
-        if not h:
-            self._chk(STMPC_EINVAL)
-        return C.c_void_p(h)
-
-    def c51_pop_act(self, handle, n_per_member, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
-        """``eps``: one value per member (the library checks the length and the range)."""
-        e = np.ascontiguousarray(eps, dtype=np.float64).reshape(-1)
-        self._chk(self._lib.stmpc_pop_c51_act_device(handle, int(n_per_member), d_obs, int(obs_stride), _dptr(e), int(e.size), d_action, d_debug_q, stream))
-
-    def c51_pop_push(self, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
-        self._chk(self._lib.stmpc_pop_c51_push_device(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated,
-                                                      d_truncated, stream))
-
-    def c51_pop_update(self, handle, n_updates, lr, stream=0):
-        """``lr``: one learning rate per member (the library checks the length)."""
-        lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
-        self._chk(self._lib.stmpc_pop_c51_update_device(handle, int(n_updates), _dptr(lr), int(lr.size), stream))
-
-    def c51_pop_stats(self, handle, d_out, stream=0):
-        self._chk(self._lib.stmpc_pop_c51_stats_device(handle, d_out, stream))
-
-    def c51_pop_per_enable(self, handle, cfgs):
-        self._chk(self._lib.stmpc_pop_c51_per_enable(handle, *self._per_table(cfgs)))
+    def _q_pop_replay_read(self, kind, learner_handle, first, count):
+        """Debug: ``count`` rows from row ``first`` of a learner's ring (a borrowed member's or a lone learner's), float32 [count][DDPG_ROW]; synchronises."""
+        rows = np.zeros((int(count), DDPG_ROW), dtype=np.float32)
+        self._chk(self._q_pop(kind, "replay_read")(learner_handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
+        return rows
 
     def c51_pop_multi_step_enable(self, handle, cfgs):
         """``cfgs``: one ``NStepCfg`` per member (the stmpc_pop_nstep_ prefix is a closed set: ``pop_nstep_enable`` routes the kind "c51" here)."""
         table = (NStepCfg * len(cfgs))(*cfgs)
         self._chk(self._lib.stmpc_pop_c51_multi_step_enable(handle, table, len(cfgs)))
-
-    def c51_pop_replay_read(self, learner_handle, first, count):
-        """Debug: ``count`` rows from row ``first`` of a C51 learner's ring (a borrowed member's or a lone learner's), float32 [count][DDPG_ROW]; synchronises."""
-        rows = np.zeros((int(count), DDPG_ROW), dtype=np.float32)
-        self._chk(self._lib.stmpc_pop_c51_replay_read(learner_handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
-        return rows
 
     def c51_pop_multi_step_window(self, learner_handle, idx):
         """Debug: ``nstep_window`` for a C51 learner's handle (a borrowed member's or a lone learner's): float64 [len(idx)][4]; synchronises."""
@@ -1468,12 +1367,6 @@ class Context:
         name = "stmpc_pop_c51_multi_step_window" if kind == "c51" else "stmpc_nstep_window_" + kind      # (the stmpc_nstep_ prefix is a closed set)
         self._chk(getattr(self._lib, name)(handle, idx.ctypes.data_as(C.POINTER(C.c_int64)), int(idx.size), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
-
-    def dqn_pop_replay_read(self, learner_handle, first, count):
-        """Debug: ``count`` rows from row ``first`` of a DQN learner's ring (a borrowed member's or a lone learner's), float32 [count][DDPG_ROW]; synchronises."""
-        rows = np.zeros((int(count), DDPG_ROW), dtype=np.float32)
-        self._chk(self._lib.stmpc_pop_dqn_replay_read(learner_handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
-        return rows
 
     # -- a Q-network as a policy (stmpc_qactor_*): DQNAgent.get_control, dqn.py:375-380 ------------------------
     def qactor_create(self, net, action_values, mode=0):
@@ -1928,6 +1821,14 @@ class Context:
         self._chk(self._lib.stmpc_probe_arith(self._h, int(op), _dptr(a), _dptr(b), _dptr(out), a.size))
         return out
 
+
+# Context.dqn_<name> / c51_<name> and dqn_pop_<name> / c51_pop_<name>: the discrete learners' shared methods with their kind
+for _kind in ("dqn", "c51"):
+    for _name in ("create", "destroy", "set_params", "get_params", "set_state", "get_state", "push", "act", "update", "grads", "targets", "gather", "stats",
+                  "per_enable", "per_tree_read", "per_last", "padded_read"):
+        setattr(Context, "%s_%s" % (_kind, _name), functools.partialmethod(getattr(Context, "_q_" + _name), _kind))
+    for _name in ("create", "destroy", "size", "member", "act", "push", "update", "stats", "per_enable", "replay_read"):
+        setattr(Context, "%s_pop_%s" % (_kind, _name), functools.partialmethod(getattr(Context, "_q_pop_" + _name), _kind))
 
 _default_ctx = None
 

@@ -3,10 +3,11 @@
 // geometry (struct Grid).  Then the handles, each with ONE function that derives its device structs from what it owns: the DDPG learner (stmpc_ddpg_*,
 // ddpg_refresh), the TD3 learner on a DDPG learner as base plus critic 2 (stmpc_td3_*, td3_refresh), prioritised replay for the two (stmpc_per_*), their
 // populations on one skeleton (struct PopCore over struct PopSlot; stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_per_*; pop_upload, td3_pop_upload), actors that view a
-// learner's networks and their population (stmpc_actor_view_ddpg, stmpc_actor_pop_*), and the DQN learner for the discrete envs (stmpc_dqn_*), which
-// holds a replay store, one network and one workspace of its own, with its population on the same skeleton (stmpc_pop_dqn_*; dqn_pop_upload), the
-// categorical learner built the same way (stmpc_c51_*) with its population (stmpc_pop_c51_*; c51_pop_upload), and
-// the Q-network as a policy behind it (stmpc_qactor_*), lone and as a population (stmpc_pop_qactor_*).  struct stmpc_actor and the actor's checks are stmpc.hip's (stmpc_host.hpp).
+// learner's networks and their population (stmpc_actor_view_ddpg, stmpc_actor_pop_*), and the learners for the discrete envs, DQN and categorical
+// (stmpc_dqn_*, stmpc_c51_*): one struct (QLearner) that holds a replay store, one network and one workspace of its own, and one set of entries (q_*)
+// for both, with what differs in a Head (DqnHead, C51Head); their populations likewise on the same skeleton (QPop; stmpc_pop_dqn_*, stmpc_pop_c51_*;
+// q_pop_upload), and the Q-network as a policy behind it (stmpc_qactor_*), lone and as a population (stmpc_pop_qactor_*).  struct stmpc_actor and the
+// actor's checks are stmpc.hip's (stmpc_host.hpp).
 #include "stmpc_host.hpp"      // (the context, the shared helpers, the kernel headers the context needs)
 #include "stmpc_ddpg_kernels.hpp"
 #include "stmpc_per_kernels.hpp"
@@ -1112,373 +1113,376 @@ int stmpc_actor_pop_eval_device(stmpc_ctx *c, const stmpc_actor_pop *p, const st
 
 }  // extern "C"
 
-// ---- DQN learner (stmpc_dqn_*): the discrete agent on a replay store, one network and one workspace of its own; kernels in stmpc_dqn_kernels.hpp --
-struct stmpc_dqn {
-    stmpc_dqn_cfg cfg{};
-    DqnDev dev{};                           // dev.base: the constants (stmpc_dqn_create), base.q the Q-network (base.h2p = Ap; base.pi stays null), the
-                                            // workspace, and the replay's part, which rp.wire writes at create and again in stmpc_dqn_per_enable
+// ---- the discrete learners (stmpc_dqn_*, stmpc_c51_*): a discrete agent on a replay store, one network and one workspace of its own, written once
+// for both heads; kernels in stmpc_dqn_kernels.hpp and stmpc_c51_kernels.hpp ----------------------------------------------------------------------
+// What the DQN learner and the categorical one differ in is their Head (DqnHead, C51Head below): the cfg and device structs, the network's output
+// width, the LDS size, the head's own cfg checks and device fields, and the kernels.  A C51 learner is not a DQN learner: its device struct is a
+// C51Dev and its network's output width is n_actions * n_atoms.
+template <class H> struct QLearner {
+    using Head = H;
+    typename H::Cfg cfg{};
+    typename H::Dev dev{};                  // base(): the constants (q_create), base().q the network (base().h2: its output width, base().h2p = Ap;
+                                            // base().pi stays null), the workspace, and the replay's part, which rp.wire writes at create and again
+                                            // in q_per_enable
     Replay rp;
     DevBuf net[11], ws[7];
     std::vector<Seg> lay;
     int h1p = 0, Ap = 0, np = 0;
     size_t lds = 0;
     Grid grid{};
-    bool pop_member = false;                // owned by a population (stmpc_dqn_pop), whose device tables hold copies of dev and dev.base
+    bool pop_member = false;                // owned by a population (QPop), whose device tables hold copies of dev and base()
+    DdpgDev &base() { return H::base(dev); }        // dev.base of a DqnDev, dev.dq.base of a C51Dev
 };
 
+struct DqnHead {
+    using Cfg = stmpc_dqn_cfg;
+    using Dev = DqnDev;
+    using L = QLearner<DqnHead>;
+    static constexpr const char *name = "DQN", *shared = "n_obs, h1, n_actions, batch and capacity";
+    static constexpr const char *pop_per_enable = "stmpc_pop_dqn_per_enable", *pop_nstep_enable = "stmpc_pop_nstep_enable_dqn";      // (what a member's refusals name)
+    static DdpgDev &base(Dev &d) { return d.base; }
+    static DqnDev &dq(Dev &d) { return d; }
+    static int n_out(const Cfg &g) { return g.n_actions; }
+    static size_t tile_bytes(const Cfg &, int h1p, int Ap) { return ddpg_tile_bytes(h1p, Ap); }
+    static int check(const Cfg &) { return STMPC_OK; }
+    static bool constants_ok(const Cfg &g) { return !g.clip_targets || g.clip_min <= g.clip_max; }
+    static bool same_shape(const Cfg &a, const Cfg &b) { return a.n_obs == b.n_obs && a.h1 == b.h1 && a.n_actions == b.n_actions && a.batch == b.batch && a.capacity == b.capacity; }
+    static void wire(Dev &d, const Cfg &g) { d.clip = g.clip_targets != 0; d.clip_min = (float)g.clip_min; d.clip_max = (float)g.clip_max; }
+    static int raise_lds(bool pop, int device, size_t lds) {
+        static LdsCeiling ceiling[2][2];
+        static const void *const fn[2][2] = {{(const void *)k_dqn_fwd, (const void *)k_dqn_act}, {(const void *)k_dqn_fwd_pop, (const void *)k_dqn_act_pop}};
+        static const char *const kernel[2][2] = {{"k_dqn_fwd", "k_dqn_act"}, {"k_dqn_fwd_pop", "k_dqn_act_pop"}};
+        TRY(raise_dynamic_lds(fn[pop][0], kernel[pop][0], ceiling[pop][0], device, lds));
+        return raise_dynamic_lds(fn[pop][1], kernel[pop][1], ceiling[pop][1], device, lds);
+    }
+    // the launches of a lone learner ...
+    static void fwd(const L &t, int gate, hipStream_t st) { hipLaunchKernelGGL(k_dqn_fwd, dim3(t.grid.tiles), dim3(AT_THREADS), t.lds, st, t.dev, t.cfg.batch, gate, (float *)nullptr); }
+    static void wgrad(const L &t, int gate, hipStream_t st) { hipLaunchKernelGGL(k_dqn_wgrad, dim3(t.grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t.dev, t.rp.Bp, gate); }
+    static void adam(const L &t, float lr, int mode, hipStream_t st) { hipLaunchKernelGGL(k_dqn_adam, dim3(t.grid.ablocks), dim3(256), 0, st, t.dev, lr, mode, 1); }
+    static void unpad(const L &t, float *d_grad, hipStream_t st) { hipLaunchKernelGGL(k_dqn_unpad, dim3(128), dim3(256), 0, st, t.dev, (const float *)t.dev.base.q.g, d_grad); }
+    static void stats(const L &t, double *d_out, hipStream_t st) { hipLaunchKernelGGL(k_dqn_stats, dim3(1), dim3(64), 0, st, t.dev, t.cfg.batch, d_out); }
+    static void act(const L &t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, hipStream_t st) {
+        hipLaunchKernelGGL(k_dqn_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t.lds, st, t.dev, N, d_obs, obs_stride, (float)eps, eps > 0 ? 1 : 0, d_action, d_debug_q);
+    }
+    // ... and of a population of P, on its table of device structs
+    static void fwd_pop(const Dev *tab, const Grid &g, int P, size_t lds, int B, hipStream_t st) { hipLaunchKernelGGL(k_dqn_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), lds, st, tab, B, 1); }
+    static void wgrad_pop(const Dev *tab, const Grid &g, int P, int Bp, hipStream_t st) { hipLaunchKernelGGL(k_dqn_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, tab, Bp, 1); }
+    static void adam_pop(const Dev *tab, const Grid &g, int P, const DdpgLr &lrs, hipStream_t st) { hipLaunchKernelGGL(k_dqn_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, tab, lrs, 1); }
+    static void act_pop(const Dev *tab, int P, size_t lds, int n, const float *d_obs, int obs_stride, const DqnEps &e, int32_t *d_action, float *d_debug_q, hipStream_t st) {
+        hipLaunchKernelGGL(k_dqn_act_pop, dim3((n + AT_TM - 1) / AT_TM, P), dim3(AT_THREADS), lds, st, tab, n, d_obs, obs_stride, e, d_action, d_debug_q);
+    }
+    static void push_pop(const Dev *tab, int P, int n, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_action,
+                         const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, hipStream_t st) {
+        hipLaunchKernelGGL(k_dqn_push_pop, dim3(push_blocks(n), P), dim3(256), 0, st, tab, n, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated,
+                           d_truncated);
+    }
+};
+
+struct C51Head {
+    using Cfg = stmpc_c51_cfg;
+    using Dev = C51Dev;
+    using L = QLearner<C51Head>;
+    static constexpr const char *name = "C51", *shared = "n_obs, h1, n_actions, n_atoms, batch and capacity";
+    static constexpr const char *pop_per_enable = "stmpc_pop_c51_per_enable", *pop_nstep_enable = "stmpc_pop_c51_multi_step_enable";
+    static DdpgDev &base(Dev &d) { return d.dq.base; }
+    static DqnDev &dq(Dev &d) { return d.dq; }
+    static int n_out(const Cfg &g) { return g.n_actions * g.n_atoms; }
+    static size_t tile_bytes(const Cfg &g, int h1p, int Ap) { return c51_tile_bytes(h1p, Ap, g.n_atoms); }
+    static int check(const Cfg &g) {
+        if (g.n_atoms < 2) return fail(STMPC_EINVAL, "n_atoms must be at least 2");
+        if ((long long)g.n_actions * g.n_atoms > STMPC_C51_MAX_LOGITS)
+            return fail(STMPC_EINVAL, "n_actions * n_atoms = " + std::to_string((long long)g.n_actions * g.n_atoms) + " exceeds " + std::to_string(STMPC_C51_MAX_LOGITS));
+        if (!std::isfinite(g.v_min) || !std::isfinite(g.v_max) || !(g.v_max > g.v_min)) return fail(STMPC_EINVAL, "the support needs finite v_min < v_max");
+        return STMPC_OK;
+    }
+    static bool constants_ok(const Cfg &) { return true; }          // (clip_targets is not read: the support's clamp is the clip)
+    static bool same_shape(const Cfg &a, const Cfg &b) {
+        return a.n_obs == b.n_obs && a.h1 == b.h1 && a.n_actions == b.n_actions && a.n_atoms == b.n_atoms && a.batch == b.batch && a.capacity == b.capacity;
+    }
+    static void wire(Dev &d, const Cfg &g) { d.dq.clip = 0; d.K = g.n_atoms; d.v_min = g.v_min; d.v_max = g.v_max; d.dz = (g.v_max - g.v_min) / (double)(g.n_atoms - 1); }
+    static int raise_lds(bool pop, int device, size_t lds) {
+        static LdsCeiling ceiling[2][2];
+        static const void *const fn[2][2] = {{(const void *)k_c51_fwd, (const void *)k_c51_act}, {(const void *)k_c51_fwd_pop, (const void *)k_c51_act_pop}};
+        static const char *const kernel[2][2] = {{"k_c51_fwd", "k_c51_act"}, {"k_c51_fwd_pop", "k_c51_act_pop"}};
+        TRY(raise_dynamic_lds(fn[pop][0], kernel[pop][0], ceiling[pop][0], device, lds));
+        return raise_dynamic_lds(fn[pop][1], kernel[pop][1], ceiling[pop][1], device, lds);
+    }
+    static void fwd(const L &t, int gate, hipStream_t st) {
+        hipLaunchKernelGGL(k_c51_fwd, dim3(t.grid.tiles), dim3(AT_THREADS), t.lds, st, t.dev, t.cfg.batch, gate, (float *)nullptr, (float *)nullptr);
+    }
+    static void wgrad(const L &t, int gate, hipStream_t st) { hipLaunchKernelGGL(k_c51_wgrad, dim3(t.grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t.dev, t.rp.Bp, gate); }
+    static void adam(const L &t, float lr, int mode, hipStream_t st) { hipLaunchKernelGGL(k_c51_adam, dim3(t.grid.ablocks), dim3(256), 0, st, t.dev, lr, mode, 1); }
+    static void unpad(const L &t, float *d_grad, hipStream_t st) { hipLaunchKernelGGL(k_c51_unpad, dim3(128), dim3(256), 0, st, t.dev, (const float *)t.dev.dq.base.q.g, d_grad); }
+    static void stats(const L &t, double *d_out, hipStream_t st) { hipLaunchKernelGGL(k_c51_stats, dim3(1), dim3(64), 0, st, t.dev, t.cfg.batch, d_out); }
+    static void act(const L &t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, hipStream_t st) {
+        hipLaunchKernelGGL(k_c51_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t.lds, st, t.dev, N, d_obs, obs_stride, (float)eps, eps > 0 ? 1 : 0, d_action, d_debug_q);
+    }
+    static void fwd_pop(const Dev *tab, const Grid &g, int P, size_t lds, int B, hipStream_t st) { hipLaunchKernelGGL(k_c51_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), lds, st, tab, B, 1); }
+    static void wgrad_pop(const Dev *tab, const Grid &g, int P, int Bp, hipStream_t st) { hipLaunchKernelGGL(k_c51_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, tab, Bp, 1); }
+    static void adam_pop(const Dev *tab, const Grid &g, int P, const DdpgLr &lrs, hipStream_t st) { hipLaunchKernelGGL(k_c51_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, tab, lrs, 1); }
+    static void act_pop(const Dev *tab, int P, size_t lds, int n, const float *d_obs, int obs_stride, const DqnEps &e, int32_t *d_action, float *d_debug_q, hipStream_t st) {
+        hipLaunchKernelGGL(k_c51_act_pop, dim3((n + AT_TM - 1) / AT_TM, P), dim3(AT_THREADS), lds, st, tab, n, d_obs, obs_stride, e, d_action, d_debug_q);
+    }
+    static void push_pop(const Dev *tab, int P, int n, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_action,
+                         const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, hipStream_t st) {
+        hipLaunchKernelGGL(k_c51_push_pop, dim3(push_blocks(n), P), dim3(256), 0, st, tab, n, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated,
+                           d_truncated);
+    }
+};
+
+struct stmpc_dqn : QLearner<DqnHead> {};
+struct stmpc_c51 : QLearner<C51Head> {};
+static_assert(STMPC_DQN_GRAD == STMPC_C51_GRAD, "q_padded_read takes either head's gradient slot");
+
 namespace {
-int dqn_raise_lds(int device, size_t lds) {
-    static LdsCeiling ceiling[2];
-    TRY(raise_dynamic_lds((const void *)k_dqn_fwd, "k_dqn_fwd", ceiling[0], device, lds));
-    return raise_dynamic_lds((const void *)k_dqn_act, "k_dqn_act", ceiling[1], device, lds);
-}
-// the pass and the weight gradients; dbg: stmpc_dqn_targets_device's output
-void dqn_launch_grads(stmpc_dqn *t, int gate, float *dbg, hipStream_t st) {
-    hipLaunchKernelGGL(k_dqn_fwd, dim3(t->grid.tiles), dim3(AT_THREADS), t->lds, st, t->dev, t->cfg.batch, gate, dbg);
-    hipLaunchKernelGGL(k_dqn_wgrad, dim3(t->grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t->dev, t->rp.Bp, gate);
-}
-}  // namespace
-
-extern "C" {
-
-int stmpc_dqn_create(stmpc_ctx *c, const stmpc_dqn_cfg *g, stmpc_dqn **out) {
-    if (!c || !g || !out) return fail(STMPC_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (g->n_actions < 1 || g->n_actions > STMPC_ENV_MAX_ACTIONS) return fail(STMPC_EINVAL, "n_actions must be in 1 ... " + std::to_string(STMPC_ENV_MAX_ACTIONS));
-    if (g->n_obs < 1 || g->n_obs > AT_KIN - 1 || g->h1 < 1 || g->h1 > 1024) return fail(STMPC_EINVAL, "DQN network shape out of range (n_obs <= 31, hidden width <= 1024)");
-    if (g->batch < 1 || g->batch > PER_MAX_B) return fail(STMPC_EINVAL, "batch must be in 1 ... 8192");
-    if (g->target_period < 1) return fail(STMPC_EINVAL, "target_period must be at least 1");
-    if (g->capacity < 1 || g->replay_start < 0 || g->replay_start >= g->capacity) return fail(STMPC_EINVAL, "capacity must be positive and replay_start below it");
-    if (!(g->gamma >= 0) || !std::isfinite(g->gamma) || !(g->beta1 >= 0 && g->beta1 < 1) || !(g->beta2 >= 0 && g->beta2 < 1) || !(g->eps > 0) ||
-        (g->clip_targets && !(g->clip_min <= g->clip_max))) return fail(STMPC_EINVAL, "DQN constants out of range");
-    HIPCHK(hipSetDevice(c->device));
-    const int h1p = (g->h1 + 15) & ~15, Ap = (g->n_actions + 15) & ~15;
-    const size_t lds = ddpg_tile_bytes(h1p, Ap);
-    if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, "DQN network too wide for one workgroup's LDS");
-    stmpc_dqn *t = new stmpc_dqn();
-    t->cfg = *g; t->h1p = h1p; t->Ap = Ap; t->np = dg_nparam(h1p, Ap); t->lds = lds;
-    t->lay = slot_layout(g->n_obs, g->h1, g->n_actions, h1p, Ap, false);
-    t->rp.device = c->device;                                        // (what destroy selects, should an allocation fail)
-    DdpgDev &d = t->dev.base;
-    int rc = net_build(t->net, d.q, g->n_obs, h1p, Ap);
-    if (!rc) rc = ws_build(t->ws, d, (g->batch + 15) & ~15, h1p, Ap);
-    if (!rc) rc = t->rp.create(c->device, g->batch, g->capacity);     // (the ring behind the net and the workspace: the order the buffers always had)
-    if (!rc) rc = dqn_raise_lds(c->device, lds);
-    if (rc) { stmpc_dqn_destroy(t); return rc; }
-    t->grid = make_grid(t->rp.Bp, h1p, Ap, false);
-    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = g->n_actions; d.h1p = h1p; d.h2p = Ap; d.replay_start = g->replay_start; d.seed = g->seed;
-    d.gamma = (float)g->gamma; d.beta1 = (float)g->beta1; d.beta2 = (float)g->beta2;
-    d.omb1 = 1.0f - d.beta1; d.omb2 = 1.0f - d.beta2; d.eps = (float)g->eps;       // (tau, the time feature, the squash and the noise: unused, 0)
-    t->rp.wire(d);
-    t->dev.A = g->n_actions; t->dev.Ap = Ap; t->dev.dbl = g->double_dqn != 0; t->dev.clip = g->clip_targets != 0; t->dev.target_period = g->target_period;
-    t->dev.clip_min = (float)g->clip_min; t->dev.clip_max = (float)g->clip_max;
-    *out = t;
-    return STMPC_OK;
-}
-
-void stmpc_dqn_destroy(stmpc_dqn *t) {
+// the entries both heads have, each behind a one-line extern "C" forward; L: stmpc_dqn or stmpc_c51
+template <class L> void q_destroy(L *t) {
     if (!t) return;
     (void)hipSetDevice(t->rp.device);
     delete t;
 }
 
-int stmpc_dqn_set_params(stmpc_dqn *t, int slot, const float *values, int64_t count) {
-    TRY(slot_args(t, values, slot, 4));
-    return slot_set(t->rp.device, t->lay, t->np, net_slot(t->dev.base.q, slot), values, count, slot < 2,
-                    [&] { hipLaunchKernelGGL(k_dqn_adam, dim3(t->grid.ablocks), dim3(256), 0, (hipStream_t)0, t->dev, 0.f, 1, 1); });
+template <class L> int q_create(stmpc_ctx *c, const typename L::Head::Cfg *g, L **out) {
+    using H = typename L::Head;
+    if (!c || !g || !out) return fail(STMPC_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (g->n_actions < 1 || g->n_actions > STMPC_ENV_MAX_ACTIONS) return fail(STMPC_EINVAL, "n_actions must be in 1 ... " + std::to_string(STMPC_ENV_MAX_ACTIONS));
+    TRY(H::check(*g));
+    if (g->n_obs < 1 || g->n_obs > AT_KIN - 1 || g->h1 < 1 || g->h1 > 1024)
+        return fail(STMPC_EINVAL, std::string(H::name) + " network shape out of range (n_obs <= 31, hidden width <= 1024)");
+    if (g->batch < 1 || g->batch > PER_MAX_B) return fail(STMPC_EINVAL, "batch must be in 1 ... 8192");
+    if (g->target_period < 1) return fail(STMPC_EINVAL, "target_period must be at least 1");
+    if (g->capacity < 1 || g->replay_start < 0 || g->replay_start >= g->capacity) return fail(STMPC_EINVAL, "capacity must be positive and replay_start below it");
+    if (!(g->gamma >= 0) || !std::isfinite(g->gamma) || !(g->beta1 >= 0 && g->beta1 < 1) || !(g->beta2 >= 0 && g->beta2 < 1) || !(g->eps > 0) || !H::constants_ok(*g))
+        return fail(STMPC_EINVAL, std::string(H::name) + " constants out of range");
+    HIPCHK(hipSetDevice(c->device));
+    const int W = H::n_out(*g), h1p = (g->h1 + 15) & ~15, Ap = (W + 15) & ~15;
+    const size_t lds = H::tile_bytes(*g, h1p, Ap);
+    if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, std::string(H::name) + " network too wide for one workgroup's LDS");
+    L *t = new L();
+    t->cfg = *g; t->h1p = h1p; t->Ap = Ap; t->np = dg_nparam(h1p, Ap); t->lds = lds;
+    t->lay = slot_layout(g->n_obs, g->h1, W, h1p, Ap, false);
+    t->rp.device = c->device;                                        // (what destroy selects, should an allocation fail)
+    DdpgDev &d = t->base();
+    int rc = net_build(t->net, d.q, g->n_obs, h1p, Ap);
+    if (!rc) rc = ws_build(t->ws, d, (g->batch + 15) & ~15, h1p, Ap);
+    if (!rc) rc = t->rp.create(c->device, g->batch, g->capacity);     // (the ring behind the net and the workspace: the order the buffers always had)
+    if (!rc) rc = H::raise_lds(false, c->device, lds);
+    if (rc) { q_destroy(t); return rc; }
+    t->grid = make_grid(t->rp.Bp, h1p, Ap, false);
+    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = W; d.h1p = h1p; d.h2p = Ap; d.replay_start = g->replay_start; d.seed = g->seed;
+    d.gamma = (float)g->gamma; d.beta1 = (float)g->beta1; d.beta2 = (float)g->beta2;
+    d.omb1 = 1.0f - d.beta1; d.omb2 = 1.0f - d.beta2; d.eps = (float)g->eps;       // (tau, the time feature, the squash and the noise: unused, 0)
+    t->rp.wire(d);
+    DqnDev &q = H::dq(t->dev);
+    q.A = g->n_actions; q.Ap = Ap; q.dbl = g->double_dqn != 0; q.target_period = g->target_period;
+    H::wire(t->dev, *g);                                             // (the clip range, or the support)
+    *out = t;
+    return STMPC_OK;
 }
 
-int stmpc_dqn_get_params(stmpc_dqn *t, int slot, float *values, int64_t count) {
+template <class L> int q_set_params(L *t, int slot, const float *values, int64_t count) {
     TRY(slot_args(t, values, slot, 4));
-    return slot_get(t->rp.device, t->lay, t->np, net_slot(t->dev.base.q, slot), values, count);
+    return slot_set(t->rp.device, t->lay, t->np, net_slot(t->base().q, slot), values, count, slot < 2, [&] { L::Head::adam(*t, 0.f, 1, (hipStream_t)0); });
 }
 
-int stmpc_dqn_set_state(stmpc_dqn *t, const int64_t *counters, const float *beta_pow) {
+template <class L> int q_get_params(L *t, int slot, float *values, int64_t count) {
+    TRY(slot_args(t, values, slot, 4));
+    return slot_get(t->rp.device, t->lay, t->np, net_slot(t->base().q, slot), values, count);
+}
+
+template <class L> int q_set_state(L *t, const int64_t *counters, const float *beta_pow) {
     if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
     TRY(t->rp.set_counters(counters));
-    HIPCHK(hipMemcpy(t->dev.base.q.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t->base().q.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
     return STMPC_OK;
 }
 
-int stmpc_dqn_get_state(stmpc_dqn *t, int64_t *counters, float *beta_pow) {
+template <class L> int q_get_state(L *t, int64_t *counters, float *beta_pow) {
     if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
     TRY(t->rp.get_counters(counters));
-    HIPCHK(hipMemcpy(beta_pow, t->dev.base.q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(beta_pow, t->base().q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
     return STMPC_OK;
 }
 
-int stmpc_dqn_push_device(stmpc_dqn *t, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_action,
-                          const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+// (both heads push with the DQN learner's own kernel on the embedded DqnDev: the row has the same columns)
+template <class L> int q_push(L *t, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_action,
+                              const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
     if (!t) return fail(STMPC_EINVAL, "learner is NULL");
     if (N < 0 || N > t->cfg.capacity || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N exceeds the replay capacity, or obs_stride is shorter than the observation");
     if (N == 0) return STMPC_OK;
-    TRY(nstep_check_push(t->dev.base, N));
+    TRY(nstep_check_push(t->base(), N));
     if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(t->rp.device));
-    hipLaunchKernelGGL(k_dqn_push, dim3(push_blocks(N)), dim3(256), 0, (hipStream_t)stream, t->dev, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward,
-                       d_terminated, d_truncated);
+    hipLaunchKernelGGL(k_dqn_push, dim3(push_blocks(N)), dim3(256), 0, (hipStream_t)stream, L::Head::dq(t->dev), N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action,
+                       d_reward, d_terminated, d_truncated);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
-int stmpc_dqn_act_device(stmpc_dqn *t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream) {
+template <class L> int q_act(L *t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream) {
     if (!t) return fail(STMPC_EINVAL, "learner is NULL");
     if (N < 0 || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N negative, or obs_stride shorter than the observation");
     if (!(eps >= 0 && eps <= 1)) return fail(STMPC_EINVAL, "eps must be in 0 ... 1");
     if (N == 0) return STMPC_OK;
     if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(t->rp.device));
-    hipLaunchKernelGGL(k_dqn_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t->lds, (hipStream_t)stream, t->dev, N, d_obs, obs_stride, (float)eps,
-                       eps > 0 ? 1 : 0, d_action, d_debug_q);
+    L::Head::act(*t, N, d_obs, obs_stride, eps, d_action, d_debug_q, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
-int stmpc_dqn_update_device(stmpc_dqn *t, int n_updates, double lr, void *stream) {
+template <class L> int q_update(L *t, int n_updates, double lr, void *stream) {
     if (!t) return fail(STMPC_EINVAL, "learner is NULL");
     if (n_updates < 0 || !(lr >= 0)) return fail(STMPC_EINVAL, "n_updates or the learning rate is negative");
     HIPCHK(hipSetDevice(t->rp.device));
     hipStream_t st = (hipStream_t)stream;
     for (int u = 0; u < n_updates; ++u) {                            // three launches, five with prioritised replay, whatever the counters say
-        per_launch_sample(t->rp, t->dev.base, 1, st);
-        dqn_launch_grads(t, 1, nullptr, st);
-        per_launch_update(t->rp, t->dev.base, st);
-        hipLaunchKernelGGL(k_dqn_adam, dim3(t->grid.ablocks), dim3(256), 0, st, t->dev, (float)lr, 0, 1);
+        per_launch_sample(t->rp, t->base(), 1, st);
+        L::Head::fwd(*t, 1, st);
+        L::Head::wgrad(*t, 1, st);
+        per_launch_update(t->rp, t->base(), st);
+        L::Head::adam(*t, (float)lr, 0, st);
     }
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
-int stmpc_dqn_grads_device(stmpc_dqn *t, float *d_grad, void *stream) {
+template <class L> int q_grads(L *t, float *d_grad, void *stream) {
     if (!t || !d_grad) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(t->rp.device));
     hipStream_t st = (hipStream_t)stream;
-    per_launch_sample(t->rp, t->dev.base, 0, st);
-    dqn_launch_grads(t, 0, nullptr, st);
-    hipLaunchKernelGGL(k_dqn_unpad, dim3(128), dim3(256), 0, st, t->dev, (const float *)t->dev.base.q.g, d_grad);
+    per_launch_sample(t->rp, t->base(), 0, st);
+    L::Head::fwd(*t, 0, st);
+    L::Head::wgrad(*t, 0, st);
+    L::Head::unpad(*t, d_grad, st);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
+template <class L> int q_gather(L *t, float *d_rows, void *stream) {
+    if (!t || !d_rows) return fail(STMPC_EINVAL, "NULL argument");
+    return replay_gather(t->rp, t->base(), d_rows, stream);
+}
+
+template <class L> int q_stats(L *t, double *d_out, void *stream) {
+    if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
+    HIPCHK(hipSetDevice(t->rp.device));
+    L::Head::stats(*t, d_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+template <class L> int q_per_enable(L *t, const stmpc_per_cfg *g) {
+    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
+    TRY(per_check_cfg(g));
+    if (t->pop_member)
+        return fail(STMPC_EINVAL, std::string("this learner is a member of a population: prioritised replay is enabled on the population (") + L::Head::pop_per_enable + ")");
+    TRY(t->rp.check_empty());
+    return per_attach(t->rp, t->base(), nullptr, g);                 // (the tree, idx, aw, atd and the constants into base())
+}
+
+template <class L> int q_nstep_enable(L *t, const stmpc_nstep_cfg *g) {
+    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
+    if (t->pop_member) return fail(STMPC_EINVAL, std::string("this learner is a member of a population: n_step is set on the population (") + L::Head::pop_nstep_enable + ")");
+    return nstep_attach(t->rp, t->base(), g);
+}
+
+// (a lone learner's ring, or a borrowed member's)
+template <class L> int q_nstep_window(L *t, const int64_t *idx, int n_idx, double *out) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return nstep_window_read(t->rp, t->base(), idx, n_idx, out);
+}
+
+template <class L> int q_replay_read(L *t, int64_t first, int64_t count, float *rows) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return t->rp.read_rows(first, count, rows);
+}
+
+template <class L> int q_per_tree_read(L *t, int64_t first, int64_t count, double *nodes) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return t->rp.read_tree(first, count, nodes);
+}
+
+template <class L> int q_per_last(L *t, int64_t *d_idx, float *d_td, float *d_weight, void *stream) {
+    if (!t) return fail(STMPC_EINVAL, "NULL argument");
+    return per_last(t->rp, t->base(), d_idx, d_td, d_weight, stream);
+}
+
+template <class L> int q_padded_read(L *t, int slot, float *values, int64_t count) {
+    if (!t || !values || slot < 0 || slot > STMPC_DQN_GRAD) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
+    if (count != dq_nparam(t->h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
+    return read_back(t->rp.device, values, slot == STMPC_DQN_GRAD ? t->base().q.g : net_slot(t->base().q, slot), (size_t)count * sizeof(float));
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_dqn_create(stmpc_ctx *c, const stmpc_dqn_cfg *g, stmpc_dqn **out) { return q_create(c, g, out); }
+void stmpc_dqn_destroy(stmpc_dqn *t) { q_destroy(t); }
+int stmpc_dqn_set_params(stmpc_dqn *t, int slot, const float *values, int64_t count) { return q_set_params(t, slot, values, count); }
+int stmpc_dqn_get_params(stmpc_dqn *t, int slot, float *values, int64_t count) { return q_get_params(t, slot, values, count); }
+int stmpc_dqn_set_state(stmpc_dqn *t, const int64_t *counters, const float *beta_pow) { return q_set_state(t, counters, beta_pow); }
+int stmpc_dqn_get_state(stmpc_dqn *t, int64_t *counters, float *beta_pow) { return q_get_state(t, counters, beta_pow); }
+int stmpc_dqn_push_device(stmpc_dqn *t, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_action,
+                          const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+    return q_push(t, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream);
+}
+int stmpc_dqn_act_device(stmpc_dqn *t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream) {
+    return q_act(t, N, d_obs, obs_stride, eps, d_action, d_debug_q, stream);
+}
+int stmpc_dqn_update_device(stmpc_dqn *t, int n_updates, double lr, void *stream) { return q_update(t, n_updates, lr, stream); }
+int stmpc_dqn_grads_device(stmpc_dqn *t, float *d_grad, void *stream) { return q_grads(t, d_grad, stream); }
+int stmpc_dqn_gather_device(stmpc_dqn *t, float *d_rows, void *stream) { return q_gather(t, d_rows, stream); }
+int stmpc_dqn_stats_device(stmpc_dqn *t, double *d_out, void *stream) { return q_stats(t, d_out, stream); }
+int stmpc_dqn_per_enable(stmpc_dqn *t, const stmpc_per_cfg *g) { return q_per_enable(t, g); }
+int stmpc_nstep_enable_dqn(stmpc_dqn *t, const stmpc_nstep_cfg *g) { return q_nstep_enable(t, g); }
+int stmpc_nstep_window_dqn(stmpc_dqn *t, const int64_t *idx, int n_idx, double *out) { return q_nstep_window(t, idx, n_idx, out); }
+int stmpc_dqn_per_tree_read(stmpc_dqn *t, int64_t first, int64_t count, double *nodes) { return q_per_tree_read(t, first, count, nodes); }
+int stmpc_dqn_per_last_device(stmpc_dqn *t, int64_t *d_idx, float *d_td, float *d_weight, void *stream) { return q_per_last(t, d_idx, d_td, d_weight, stream); }
+int stmpc_dqn_padded_read(stmpc_dqn *t, int slot, float *values, int64_t count) { return q_padded_read(t, slot, values, count); }
+
+// dbg: float32 [batch][4]
 int stmpc_dqn_targets_device(stmpc_dqn *t, float *d_out, void *stream) {
     if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(t->rp.device));
-    per_launch_sample(t->rp, t->dev.base, 0, (hipStream_t)stream);
+    per_launch_sample(t->rp, t->base(), 0, (hipStream_t)stream);
     hipLaunchKernelGGL(k_dqn_fwd, dim3(t->grid.tiles), dim3(AT_THREADS), t->lds, (hipStream_t)stream, t->dev, t->cfg.batch, 0, d_out);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
-int stmpc_dqn_gather_device(stmpc_dqn *t, float *d_rows, void *stream) {
-    if (!t || !d_rows) return fail(STMPC_EINVAL, "NULL argument");
-    return replay_gather(t->rp, t->dev.base, d_rows, stream);
-}
-
-int stmpc_dqn_stats_device(stmpc_dqn *t, double *d_out, void *stream) {
-    if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->rp.device));
-    hipLaunchKernelGGL(k_dqn_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, t->dev, t->cfg.batch, d_out);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_dqn_per_enable(stmpc_dqn *t, const stmpc_per_cfg *g) {
-    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
-    TRY(per_check_cfg(g));
-    if (t->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: prioritised replay is enabled on the population (stmpc_pop_dqn_per_enable)");
-    TRY(t->rp.check_empty());
-    return per_attach(t->rp, t->dev.base, nullptr, g);               // (the tree, idx, aw, atd and the constants into dev.base)
-}
-
-int stmpc_nstep_enable_dqn(stmpc_dqn *t, const stmpc_nstep_cfg *g) {
-    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
-    if (t->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: n_step is set on the population (stmpc_pop_nstep_enable_dqn)");
-    return nstep_attach(t->rp, t->dev.base, g);
-}
-
-int stmpc_nstep_window_dqn(stmpc_dqn *t, const int64_t *idx, int n_idx, double *out) {
-    if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return nstep_window_read(t->rp, t->dev.base, idx, n_idx, out);
-}
-
-int stmpc_dqn_per_tree_read(stmpc_dqn *t, int64_t first, int64_t count, double *nodes) {
-    if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return t->rp.read_tree(first, count, nodes);
-}
-
-int stmpc_dqn_per_last_device(stmpc_dqn *t, int64_t *d_idx, float *d_td, float *d_weight, void *stream) {
-    if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return per_last(t->rp, t->dev.base, d_idx, d_td, d_weight, stream);
-}
-
-int stmpc_dqn_padded_read(stmpc_dqn *t, int slot, float *values, int64_t count) {
-    if (!t || !values || slot < 0 || slot > STMPC_DQN_GRAD) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
-    if (count != dq_nparam(t->h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
-    return read_back(t->rp.device, values, slot == STMPC_DQN_GRAD ? t->dev.base.q.g : net_slot(t->dev.base.q, slot), (size_t)count * sizeof(float));
-}
-
-}  // extern "C"
-
-// ---- C51 learner (stmpc_c51_*): the categorical DQN agent on a replay store, one network and one workspace of its own, as stmpc_dqn holds them (it is
-// not a stmpc_dqn: its device struct is a C51Dev and its network's output width is n_actions * n_atoms); kernels in stmpc_c51_kernels.hpp ----------
-struct stmpc_c51 {
-    stmpc_c51_cfg cfg{};
-    C51Dev dev{};                           // dev.dq.base: the constants, base.q the logits network (base.h2 = A K, base.h2p = Ap), the workspace and the
-                                            // replay's part (rp.wire at create and again in stmpc_c51_per_enable)
-    Replay rp;
-    DevBuf net[11], ws[7];
-    std::vector<Seg> lay;
-    int h1p = 0, Ap = 0, np = 0;
-    size_t lds = 0;
-    Grid grid{};
-    bool pop_member = false;                // owned by a population (stmpc_c51_pop), whose device tables hold copies of dev and dev.dq.base
-};
-
-namespace {
-int c51_raise_lds(int device, size_t lds) {
-    static LdsCeiling ceiling[2];
-    TRY(raise_dynamic_lds((const void *)k_c51_fwd, "k_c51_fwd", ceiling[0], device, lds));
-    return raise_dynamic_lds((const void *)k_c51_act, "k_c51_act", ceiling[1], device, lds);
-}
-// the pass and the weight gradients; dbg4, dist: the two debug entries' outputs
-void c51_launch_grads(stmpc_c51 *t, int gate, float *dbg4, float *dist, hipStream_t st) {
-    hipLaunchKernelGGL(k_c51_fwd, dim3(t->grid.tiles), dim3(AT_THREADS), t->lds, st, t->dev, t->cfg.batch, gate, dbg4, dist);
-    hipLaunchKernelGGL(k_c51_wgrad, dim3(t->grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t->dev, t->rp.Bp, gate);
-}
-}  // namespace
-
-extern "C" {
-
-int stmpc_c51_create(stmpc_ctx *c, const stmpc_c51_cfg *g, stmpc_c51 **out) {
-    if (!c || !g || !out) return fail(STMPC_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (g->n_actions < 1 || g->n_actions > STMPC_ENV_MAX_ACTIONS) return fail(STMPC_EINVAL, "n_actions must be in 1 ... " + std::to_string(STMPC_ENV_MAX_ACTIONS));
-    if (g->n_atoms < 2) return fail(STMPC_EINVAL, "n_atoms must be at least 2");
-    if ((long long)g->n_actions * g->n_atoms > STMPC_C51_MAX_LOGITS)
-        return fail(STMPC_EINVAL, "n_actions * n_atoms = " + std::to_string((long long)g->n_actions * g->n_atoms) + " exceeds " + std::to_string(STMPC_C51_MAX_LOGITS));
-    if (!std::isfinite(g->v_min) || !std::isfinite(g->v_max) || !(g->v_max > g->v_min)) return fail(STMPC_EINVAL, "the support needs finite v_min < v_max");
-    if (g->n_obs < 1 || g->n_obs > AT_KIN - 1 || g->h1 < 1 || g->h1 > 1024) return fail(STMPC_EINVAL, "C51 network shape out of range (n_obs <= 31, hidden width <= 1024)");
-    if (g->batch < 1 || g->batch > PER_MAX_B) return fail(STMPC_EINVAL, "batch must be in 1 ... 8192");
-    if (g->target_period < 1) return fail(STMPC_EINVAL, "target_period must be at least 1");
-    if (g->capacity < 1 || g->replay_start < 0 || g->replay_start >= g->capacity) return fail(STMPC_EINVAL, "capacity must be positive and replay_start below it");
-    if (!(g->gamma >= 0) || !std::isfinite(g->gamma) || !(g->beta1 >= 0 && g->beta1 < 1) || !(g->beta2 >= 0 && g->beta2 < 1) || !(g->eps > 0))
-        return fail(STMPC_EINVAL, "C51 constants out of range");
-    HIPCHK(hipSetDevice(c->device));
-    const int AK = g->n_actions * g->n_atoms, h1p = (g->h1 + 15) & ~15, Ap = (AK + 15) & ~15;
-    const size_t lds = c51_tile_bytes(h1p, Ap, g->n_atoms);
-    if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, "C51 network too wide for one workgroup's LDS");
-    stmpc_c51 *t = new stmpc_c51();
-    t->cfg = *g; t->h1p = h1p; t->Ap = Ap; t->np = dg_nparam(h1p, Ap); t->lds = lds;
-    t->lay = slot_layout(g->n_obs, g->h1, AK, h1p, Ap, false);
-    t->rp.device = c->device;                                        // (what destroy selects, should an allocation fail)
-    DdpgDev &d = t->dev.dq.base;
-    int rc = net_build(t->net, d.q, g->n_obs, h1p, Ap);
-    if (!rc) rc = ws_build(t->ws, d, (g->batch + 15) & ~15, h1p, Ap);
-    if (!rc) rc = t->rp.create(c->device, g->batch, g->capacity);
-    if (!rc) rc = c51_raise_lds(c->device, lds);
-    if (rc) { stmpc_c51_destroy(t); return rc; }
-    t->grid = make_grid(t->rp.Bp, h1p, Ap, false);
-    d.n_obs = g->n_obs; d.h1 = g->h1; d.h2 = AK; d.h1p = h1p; d.h2p = Ap; d.replay_start = g->replay_start; d.seed = g->seed;
-    d.gamma = (float)g->gamma; d.beta1 = (float)g->beta1; d.beta2 = (float)g->beta2;
-    d.omb1 = 1.0f - d.beta1; d.omb2 = 1.0f - d.beta2; d.eps = (float)g->eps;
-    t->rp.wire(d);
-    DqnDev &q = t->dev.dq;
-    q.A = g->n_actions; q.Ap = Ap; q.dbl = g->double_dqn != 0; q.clip = 0; q.target_period = g->target_period;     // (clip_targets: the support's clamp is the clip)
-    t->dev.K = g->n_atoms; t->dev.v_min = g->v_min; t->dev.v_max = g->v_max; t->dev.dz = (g->v_max - g->v_min) / (double)(g->n_atoms - 1);
-    *out = t;
-    return STMPC_OK;
-}
-
-void stmpc_c51_destroy(stmpc_c51 *t) {
-    if (!t) return;
-    (void)hipSetDevice(t->rp.device);
-    delete t;
-}
-
-int stmpc_c51_set_params(stmpc_c51 *t, int slot, const float *values, int64_t count) {
-    TRY(slot_args(t, values, slot, 4));
-    return slot_set(t->rp.device, t->lay, t->np, net_slot(t->dev.dq.base.q, slot), values, count, slot < 2,
-                    [&] { hipLaunchKernelGGL(k_c51_adam, dim3(t->grid.ablocks), dim3(256), 0, (hipStream_t)0, t->dev, 0.f, 1, 1); });
-}
-
-int stmpc_c51_get_params(stmpc_c51 *t, int slot, float *values, int64_t count) {
-    TRY(slot_args(t, values, slot, 4));
-    return slot_get(t->rp.device, t->lay, t->np, net_slot(t->dev.dq.base.q, slot), values, count);
-}
-
-int stmpc_c51_set_state(stmpc_c51 *t, const int64_t *counters, const float *beta_pow) {
-    if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
-    TRY(t->rp.set_counters(counters));
-    HIPCHK(hipMemcpy(t->dev.dq.base.q.bpow, beta_pow, 2 * sizeof(float), hipMemcpyHostToDevice));
-    return STMPC_OK;
-}
-
-int stmpc_c51_get_state(stmpc_c51 *t, int64_t *counters, float *beta_pow) {
-    if (!t || !counters || !beta_pow) return fail(STMPC_EINVAL, "NULL argument");
-    TRY(t->rp.get_counters(counters));
-    HIPCHK(hipMemcpy(beta_pow, t->dev.dq.base.q.bpow, 2 * sizeof(float), hipMemcpyDeviceToHost));
-    return STMPC_OK;
-}
-
+int stmpc_c51_create(stmpc_ctx *c, const stmpc_c51_cfg *g, stmpc_c51 **out) { return q_create(c, g, out); }
+void stmpc_c51_destroy(stmpc_c51 *t) { q_destroy(t); }
+int stmpc_c51_set_params(stmpc_c51 *t, int slot, const float *values, int64_t count) { return q_set_params(t, slot, values, count); }
+int stmpc_c51_get_params(stmpc_c51 *t, int slot, float *values, int64_t count) { return q_get_params(t, slot, values, count); }
+int stmpc_c51_set_state(stmpc_c51 *t, const int64_t *counters, const float *beta_pow) { return q_set_state(t, counters, beta_pow); }
+int stmpc_c51_get_state(stmpc_c51 *t, int64_t *counters, float *beta_pow) { return q_get_state(t, counters, beta_pow); }
 int stmpc_c51_push_device(stmpc_c51 *t, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_action,
                           const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
-    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
-    if (N < 0 || N > t->cfg.capacity || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N exceeds the replay capacity, or obs_stride is shorter than the observation");
-    if (N == 0) return STMPC_OK;
-    TRY(nstep_check_push(t->dev.dq.base, N));
-    if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(t->rp.device));
-    hipLaunchKernelGGL(k_dqn_push, dim3(push_blocks(N)), dim3(256), 0, (hipStream_t)stream, t->dev.dq, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward,
-                       d_terminated, d_truncated);                  // (the DQN learner's own push kernel on the embedded struct: the row has the same columns)
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    return q_push(t, N, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream);
 }
-
 int stmpc_c51_act_device(stmpc_c51 *t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream) {
-    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
-    if (N < 0 || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N negative, or obs_stride shorter than the observation");
-    if (!(eps >= 0 && eps <= 1)) return fail(STMPC_EINVAL, "eps must be in 0 ... 1");
-    if (N == 0) return STMPC_OK;
-    if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(t->rp.device));
-    hipLaunchKernelGGL(k_c51_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t->lds, (hipStream_t)stream, t->dev, N, d_obs, obs_stride, (float)eps,
-                       eps > 0 ? 1 : 0, d_action, d_debug_q);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
+    return q_act(t, N, d_obs, obs_stride, eps, d_action, d_debug_q, stream);
 }
-
-int stmpc_c51_update_device(stmpc_c51 *t, int n_updates, double lr, void *stream) {
-    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
-    if (n_updates < 0 || !(lr >= 0)) return fail(STMPC_EINVAL, "n_updates or the learning rate is negative");
-    HIPCHK(hipSetDevice(t->rp.device));
-    hipStream_t st = (hipStream_t)stream;
-    for (int u = 0; u < n_updates; ++u) {                            // three launches, five with prioritised replay, whatever the counters say
-        per_launch_sample(t->rp, t->dev.dq.base, 1, st);
-        c51_launch_grads(t, 1, nullptr, nullptr, st);
-        per_launch_update(t->rp, t->dev.dq.base, st);
-        hipLaunchKernelGGL(k_c51_adam, dim3(t->grid.ablocks), dim3(256), 0, st, t->dev, (float)lr, 0, 1);
-    }
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_c51_grads_device(stmpc_c51 *t, float *d_grad, void *stream) {
-    if (!t || !d_grad) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->rp.device));
-    hipStream_t st = (hipStream_t)stream;
-    per_launch_sample(t->rp, t->dev.dq.base, 0, st);
-    c51_launch_grads(t, 0, nullptr, nullptr, st);
-    hipLaunchKernelGGL(k_c51_unpad, dim3(128), dim3(256), 0, st, t->dev, (const float *)t->dev.dq.base.q.g, d_grad);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
+int stmpc_c51_update_device(stmpc_c51 *t, int n_updates, double lr, void *stream) { return q_update(t, n_updates, lr, stream); }
+int stmpc_c51_grads_device(stmpc_c51 *t, float *d_grad, void *stream) { return q_grads(t, d_grad, stream); }
+int stmpc_c51_gather_device(stmpc_c51 *t, float *d_rows, void *stream) { return q_gather(t, d_rows, stream); }
+int stmpc_c51_stats_device(stmpc_c51 *t, double *d_out, void *stream) { return q_stats(t, d_out, stream); }
+int stmpc_c51_per_enable(stmpc_c51 *t, const stmpc_per_cfg *g) { return q_per_enable(t, g); }
+int stmpc_c51_multi_step_enable(stmpc_c51 *t, const stmpc_nstep_cfg *g) { return q_nstep_enable(t, g); }
+int stmpc_c51_per_tree_read(stmpc_c51 *t, int64_t first, int64_t count, double *nodes) { return q_per_tree_read(t, first, count, nodes); }
+int stmpc_c51_per_last_device(stmpc_c51 *t, int64_t *d_idx, float *d_td, float *d_weight, void *stream) { return q_per_last(t, d_idx, d_td, d_weight, stream); }
+int stmpc_c51_padded_read(stmpc_c51 *t, int slot, float *values, int64_t count) { return q_padded_read(t, slot, values, count); }
+int stmpc_c51_replay_read(stmpc_c51 *t, int64_t first, int64_t count, float *rows) { return q_replay_read(t, first, count, rows); }
 
 int stmpc_c51_targets_device(stmpc_c51 *t, float *d_out, void *stream) { return stmpc_c51_dist_device(t, nullptr, d_out, stream); }
 
+// d_dist: float32 [batch][2][K], d_out: float32 [batch][4]; either may be null
 int stmpc_c51_dist_device(stmpc_c51 *t, float *d_dist, float *d_out, void *stream) {
     if (!t || (!d_dist && !d_out)) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(t->rp.device));
-    per_launch_sample(t->rp, t->dev.dq.base, 0, (hipStream_t)stream);
+    per_launch_sample(t->rp, t->base(), 0, (hipStream_t)stream);
     hipLaunchKernelGGL(k_c51_fwd, dim3(t->grid.tiles), dim3(AT_THREADS), t->lds, (hipStream_t)stream, t->dev, t->cfg.batch, 0, d_out, d_dist);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -1495,286 +1499,83 @@ int stmpc_c51_project_device(stmpc_c51 *t, int n, const float *d_p, const float 
     return STMPC_OK;
 }
 
-int stmpc_c51_gather_device(stmpc_c51 *t, float *d_rows, void *stream) {
-    if (!t || !d_rows) return fail(STMPC_EINVAL, "NULL argument");
-    return replay_gather(t->rp, t->dev.dq.base, d_rows, stream);
-}
-
-int stmpc_c51_stats_device(stmpc_c51 *t, double *d_out, void *stream) {
-    if (!t || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(t->rp.device));
-    hipLaunchKernelGGL(k_c51_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, t->dev, t->cfg.batch, d_out);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_c51_per_enable(stmpc_c51 *t, const stmpc_per_cfg *g) {
-    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
-    TRY(per_check_cfg(g));
-    if (t->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: prioritised replay is enabled on the population (stmpc_pop_c51_per_enable)");
-    TRY(t->rp.check_empty());
-    return per_attach(t->rp, t->dev.dq.base, nullptr, g);
-}
-
-int stmpc_c51_per_tree_read(stmpc_c51 *t, int64_t first, int64_t count, double *nodes) {
-    if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return t->rp.read_tree(first, count, nodes);
-}
-
-int stmpc_c51_per_last_device(stmpc_c51 *t, int64_t *d_idx, float *d_td, float *d_weight, void *stream) {
-    if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return per_last(t->rp, t->dev.dq.base, d_idx, d_td, d_weight, stream);
-}
-
-int stmpc_c51_multi_step_enable(stmpc_c51 *t, const stmpc_nstep_cfg *g) {
-    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
-    if (t->pop_member) return fail(STMPC_EINVAL, "this learner is a member of a population: n_step is set on the population (stmpc_pop_c51_multi_step_enable)");
-    return nstep_attach(t->rp, t->dev.dq.base, g);
-}
-
-int stmpc_c51_replay_read(stmpc_c51 *t, int64_t first, int64_t count, float *rows) {
-    if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return t->rp.read_rows(first, count, rows);
-}
-
 int stmpc_c51_dzout_read(stmpc_c51 *t, float *values, int64_t count) {
     if (!t || !values) return fail(STMPC_EINVAL, "NULL argument");
     if (count != (int64_t)t->rp.Bp * t->Ap) return fail(STMPC_EINVAL, "count is not batch rounded up to 16 times the padded logit count");
-    return read_back(t->rp.device, values, t->dev.dq.base.aD2, (size_t)count * sizeof(float));
-}
-
-int stmpc_c51_padded_read(stmpc_c51 *t, int slot, float *values, int64_t count) {
-    if (!t || !values || slot < 0 || slot > STMPC_C51_GRAD) return fail(STMPC_EINVAL, "NULL argument or slot out of range");
-    if (count != dq_nparam(t->h1p, t->Ap)) return fail(STMPC_EINVAL, "count is not the length of a padded slot");
-    return read_back(t->rp.device, values, slot == STMPC_C51_GRAD ? t->dev.dq.base.q.g : net_slot(t->dev.dq.base.q, slot), (size_t)count * sizeof(float));
+    return read_back(t->rp.device, values, t->base().aD2, (size_t)count * sizeof(float));
 }
 
 }  // extern "C"
 
-// ---- a population of DQN learners (stmpc_pop_dqn_*): P learners of the section above, one launch per kernel; kernels in stmpc_dqn_pop_kernels.hpp,
-// prioritised replay and the statistics on the core's DdpgDev table with stmpc_per_pop_kernels.hpp's and stmpc_ddpg_pop_kernels.hpp's kernels ---------
-struct stmpc_dqn_pop {
-    PopCore core;                           // core.table: the members' dev.base
-    std::vector<stmpc_dqn *> members;       // owned; made by stmpc_dqn_create, so every lone entry works on a borrowed member
-    DevBuf table;                           // DqnDev [P]: the members' structs (dqn_pop_upload)
-    const DqnDev *dev() const { return table.as<DqnDev>(); }
+// ---- populations of discrete learners (stmpc_pop_dqn_*, stmpc_pop_c51_*): P learners of the section above, one launch per kernel, written once for
+// both heads; kernels in stmpc_dqn_pop_kernels.hpp and stmpc_c51_pop_kernels.hpp, prioritised replay and the statistics on the core's DdpgDev table
+// with stmpc_per_pop_kernels.hpp's and stmpc_ddpg_pop_kernels.hpp's kernels -------------------------------------------------------------------------
+template <class L> struct QPop {
+    using Member = L;
+    using Head = typename L::Head;
+    using Dev = typename Head::Dev;
+    PopCore core;                         // core.table: the members' base()
+    std::vector<L *> members;               // owned; made by q_create, so every lone entry works on a borrowed member
+    DevBuf table;                           // Dev [P]: the members' structs (q_pop_upload); a C51 member's v_min, v_max and dz travel in its own
+    const Dev *dev() const { return table.as<Dev>(); }
 };
+struct stmpc_dqn_pop : QPop<stmpc_dqn> {};
+struct stmpc_c51_pop : QPop<stmpc_c51> {};
 
 static_assert(STMPC_DQN_POP_MAX == DG_POP_MAX && DG_POP_MAX <= 64, "DdpgLr and DqnEps hold one value, and DqnEps::explore one bit, per possible member");
-
-namespace {
-// both device tables from the members as they are now: at create, and again once prioritised replay re-wired members
-int dqn_pop_upload(stmpc_dqn_pop *p) {
-    std::vector<DqnDev> host;
-    for (const stmpc_dqn *t : p->members) host.push_back(t->dev);
-    TRY(upload(p->table, host.data(), host.size()));
-    return pop_upload(p->core);
-}
-int dqn_pop_raise_lds(int device, size_t lds) {
-    static LdsCeiling ceiling[2];
-    TRY(raise_dynamic_lds((const void *)k_dqn_fwd_pop, "k_dqn_fwd_pop", ceiling[0], device, lds));
-    return raise_dynamic_lds((const void *)k_dqn_act_pop, "k_dqn_act_pop", ceiling[1], device, lds);
-}
-}  // namespace
-
-extern "C" {
-
-int stmpc_pop_dqn_create(stmpc_ctx *c, const stmpc_dqn_cfg *cfgs, int P, stmpc_dqn_pop **out) {
-    TRY(pop_check_create(c, cfgs, P, out, "n_obs, h1, n_actions, batch and capacity", [](const stmpc_dqn_cfg &a, const stmpc_dqn_cfg &b) {
-        return a.n_obs == b.n_obs && a.h1 == b.h1 && a.n_actions == b.n_actions && a.batch == b.batch && a.capacity == b.capacity;
-    }));
-    HIPCHK(hipSetDevice(c->device));
-    stmpc_dqn_pop *p = new stmpc_dqn_pop();
-    PopCore &core = p->core;
-    core.device = c->device;
-    int rc = STMPC_OK;
-    for (int m = 0; m < P && !rc; ++m) {
-        stmpc_dqn *t = nullptr;
-        rc = stmpc_dqn_create(c, cfgs + m, &t);
-        if (rc) break;
-        t->pop_member = true;
-        p->members.push_back(t);
-    }
-    if (!rc) {
-        for (stmpc_dqn *t : p->members) core.slots.push_back({&t->rp, &t->dev.base, nullptr});     // (members is complete: the pointers stay)
-        const stmpc_dqn *t0 = p->members[0];
-        core.n_obs = t0->cfg.n_obs; core.capacity = t0->cfg.capacity; core.batch = t0->cfg.batch; core.lds = t0->lds;
-        rc = dqn_pop_upload(p);
-    }
-    if (!rc) rc = dqn_pop_raise_lds(c->device, core.lds);
-    if (rc) { stmpc_pop_dqn_destroy(p); return rc; }
-    *out = p;
-    return STMPC_OK;
-}
-
-void stmpc_pop_dqn_destroy(stmpc_dqn_pop *p) {
-    if (!p) return;
-    for (stmpc_dqn *t : p->members) stmpc_dqn_destroy(t);
-    (void)hipSetDevice(p->core.device);
-    delete p;
-}
-
-int stmpc_pop_dqn_size(const stmpc_dqn_pop *p) { return p ? p->core.P() : 0; }
-
-stmpc_dqn *stmpc_pop_dqn_member(stmpc_dqn_pop *p, int m) {
-    if (!p || m < 0 || m >= p->core.P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
-    return p->members[m];
-}
-
-int stmpc_pop_dqn_act_device(stmpc_dqn_pop *p, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps, int32_t *d_action,
-                             float *d_debug_q, void *stream) {
-    if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    const PopCore &c = p->core;
-    TRY(pop_check_rows(c, n_per_member, obs_stride));
-    if (!eps) return fail(STMPC_EINVAL, "NULL argument");
-    if (n_eps != c.P()) return fail(STMPC_EINVAL, "the eps array has " + std::to_string(n_eps) + " entries, the population " + std::to_string(c.P()) + " members");
-    DqnEps e{};
-    for (int m = 0; m < c.P(); ++m) {
-        if (!(eps[m] >= 0 && eps[m] <= 1)) return fail(STMPC_EINVAL, "member " + std::to_string(m) + "'s eps must be in 0 ... 1");
-        e.eps[m] = (float)eps[m];
-        if (eps[m] > 0) e.explore |= 1ull << m;                      // (stmpc_dqn_act_device's rule: an exploring call is one with eps > 0)
-    }
-    if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(c.device));
-    hipLaunchKernelGGL(k_dqn_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, c.P()), dim3(AT_THREADS), c.lds, (hipStream_t)stream, p->dev(), n_per_member, d_obs,
-                       obs_stride, e, d_action, d_debug_q);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_pop_dqn_push_device(stmpc_dqn_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
-                              const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
-    if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    const PopCore &c = p->core;
-    TRY(pop_check_rows(c, n_per_member, obs_stride));
-    TRY(pop_check_push(c, n_per_member));
-    if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
-    HIPCHK(hipSetDevice(c.device));
-    hipLaunchKernelGGL(k_dqn_push_pop, dim3(push_blocks(n_per_member), c.P()), dim3(256), 0, (hipStream_t)stream, p->dev(), n_per_member, d_obs, d_next_obs, d_final_obs,
-                       obs_stride, d_action, d_reward, d_terminated, d_truncated);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_pop_dqn_update_device(stmpc_dqn_pop *p, int n_updates, const double *lr, int n_lr, void *stream) {
-    if (!p) return fail(STMPC_EINVAL, "NULL argument");
-    const PopCore &c = p->core;
-    DdpgLr lrs{};
-    TRY(pop_check_update(c, n_updates, n_lr, {{lr, &lrs}}));
-    HIPCHK(hipSetDevice(c.device));
-    const stmpc_dqn *t = p->members[0];
-    const Grid g = t->grid;
-    const int P = c.P(), B = c.batch, Bp = t->rp.Bp;
-    hipStream_t st = (hipStream_t)stream;
-    for (int u = 0; u < n_updates; ++u) {                            // stmpc_dqn_update_device's three launches (five with prioritised members), each over the members
-        if (c.per_any) hipLaunchKernelGGL(k_per_sample_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, Bp, 1);
-        hipLaunchKernelGGL(k_dqn_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), c.lds, st, p->dev(), B, 1);
-        hipLaunchKernelGGL(k_dqn_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), Bp, 1);
-        if (c.per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, 1);
-        hipLaunchKernelGGL(k_dqn_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, p->dev(), lrs, 1);
-    }
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_pop_dqn_stats_device(stmpc_dqn_pop *p, double *d_out, void *stream) {
-    if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
-    HIPCHK(hipSetDevice(p->core.device));
-    hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->core.dev(), p->core.batch, d_out);
-    HIPCHK(hipGetLastError());
-    return STMPC_OK;
-}
-
-int stmpc_pop_dqn_per_enable(stmpc_dqn_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
-    if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    return pop_per_enable(p->core, cfgs, enabled, P, [&] { return dqn_pop_upload(p); });
-}
-
-int stmpc_pop_nstep_enable_dqn(stmpc_dqn_pop *p, const stmpc_nstep_cfg *cfgs, int P) {
-    if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    return pop_nstep_enable(p->core, cfgs, P, [&] { return dqn_pop_upload(p); });
-}
-
-int stmpc_pop_dqn_replay_read(stmpc_dqn *t, int64_t first, int64_t count, float *rows) {
-    if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return t->rp.read_rows(first, count, rows);
-}
-
-}  // extern "C"
-
-// ---- a population of C51 learners (stmpc_pop_c51_*): P learners of the C51 section above, one launch per kernel; kernels in
-// stmpc_c51_pop_kernels.hpp, prioritised replay and the statistics on the core's DdpgDev table with stmpc_per_pop_kernels.hpp's and
-// stmpc_ddpg_pop_kernels.hpp's kernels ------------------------------------------------------------------------------------------------------------
-struct stmpc_c51_pop {
-    PopCore core;                           // core.table: the members' dev.dq.base
-    std::vector<stmpc_c51 *> members;       // owned; made by stmpc_c51_create, so every lone entry works on a borrowed member
-    DevBuf table;                           // C51Dev [P]: the members' structs (c51_pop_upload); v_min, v_max and dz travel in each member's own
-    const C51Dev *dev() const { return table.as<C51Dev>(); }
-};
-
 static_assert(STMPC_C51_POP_MAX == DG_POP_MAX && DG_POP_MAX <= 64, "DdpgLr and DqnEps hold one value, and DqnEps::explore one bit, per possible member");
 
 namespace {
 // both device tables from the members as they are now: at create, and again once prioritised replay or n_step re-wired members
-int c51_pop_upload(stmpc_c51_pop *p) {
-    std::vector<C51Dev> host;
-    for (const stmpc_c51 *t : p->members) host.push_back(t->dev);
+// (Pop: stmpc_dqn_pop or stmpc_c51_pop)
+template <class Pop> int q_pop_upload(Pop *p) {
+    std::vector<typename Pop::Dev> host;
+    for (const typename Pop::Member *t : p->members) host.push_back(t->dev);
     TRY(upload(p->table, host.data(), host.size()));
     return pop_upload(p->core);
 }
-int c51_pop_raise_lds(int device, size_t lds) {
-    static LdsCeiling ceiling[2];
-    TRY(raise_dynamic_lds((const void *)k_c51_fwd_pop, "k_c51_fwd_pop", ceiling[0], device, lds));
-    return raise_dynamic_lds((const void *)k_c51_act_pop, "k_c51_act_pop", ceiling[1], device, lds);
+
+template <class Pop> void q_pop_destroy(Pop *p) {
+    if (!p) return;
+    for (typename Pop::Member *t : p->members) q_destroy(t);
+    (void)hipSetDevice(p->core.device);
+    delete p;
 }
-}  // namespace
 
-extern "C" {
-
-int stmpc_pop_c51_create(stmpc_ctx *c, const stmpc_c51_cfg *cfgs, int P, stmpc_c51_pop **out) {
-    TRY(pop_check_create(c, cfgs, P, out, "n_obs, h1, n_actions, n_atoms, batch and capacity", [](const stmpc_c51_cfg &a, const stmpc_c51_cfg &b) {
-        return a.n_obs == b.n_obs && a.h1 == b.h1 && a.n_actions == b.n_actions && a.n_atoms == b.n_atoms && a.batch == b.batch && a.capacity == b.capacity;
-    }));
+template <class Pop> int q_pop_create(stmpc_ctx *c, const typename Pop::Head::Cfg *cfgs, int P, Pop **out) {
+    using H = typename Pop::Head;
+    TRY(pop_check_create(c, cfgs, P, out, H::shared, H::same_shape));
     HIPCHK(hipSetDevice(c->device));
-    stmpc_c51_pop *p = new stmpc_c51_pop();
+    Pop *p = new Pop();
     PopCore &core = p->core;
     core.device = c->device;
     int rc = STMPC_OK;
     for (int m = 0; m < P && !rc; ++m) {
-        stmpc_c51 *t = nullptr;
-        rc = stmpc_c51_create(c, cfgs + m, &t);
+        typename Pop::Member *t = nullptr;
+        rc = q_create(c, cfgs + m, &t);
         if (rc) break;
         t->pop_member = true;
         p->members.push_back(t);
     }
     if (!rc) {
-        for (stmpc_c51 *t : p->members) core.slots.push_back({&t->rp, &t->dev.dq.base, nullptr});     // (members is complete: the pointers stay)
-        const stmpc_c51 *t0 = p->members[0];
+        for (typename Pop::Member *t : p->members) core.slots.push_back({&t->rp, &t->base(), nullptr});     // (members is complete: the pointers stay)
+        const typename Pop::Member *t0 = p->members[0];
         core.n_obs = t0->cfg.n_obs; core.capacity = t0->cfg.capacity; core.batch = t0->cfg.batch; core.lds = t0->lds;
-        rc = c51_pop_upload(p);
+        rc = q_pop_upload(p);
     }
-    if (!rc) rc = c51_pop_raise_lds(c->device, core.lds);
-    if (rc) { stmpc_pop_c51_destroy(p); return rc; }
+    if (!rc) rc = H::raise_lds(true, c->device, core.lds);
+    if (rc) { q_pop_destroy(p); return rc; }
     *out = p;
     return STMPC_OK;
 }
 
-void stmpc_pop_c51_destroy(stmpc_c51_pop *p) {
-    if (!p) return;
-    for (stmpc_c51 *t : p->members) stmpc_c51_destroy(t);
-    (void)hipSetDevice(p->core.device);
-    delete p;
-}
-
-int stmpc_pop_c51_size(const stmpc_c51_pop *p) { return p ? p->core.P() : 0; }
-
-stmpc_c51 *stmpc_pop_c51_member(stmpc_c51_pop *p, int m) {
+template <class Pop> typename Pop::Member *q_pop_member(Pop *p, int m) {
     if (!p || m < 0 || m >= p->core.P()) { (void)fail(STMPC_EINVAL, "population is NULL, or no such member"); return nullptr; }
     return p->members[m];
 }
 
-int stmpc_pop_c51_act_device(stmpc_c51_pop *p, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps, int32_t *d_action,
-                             float *d_debug_q, void *stream) {
+template <class Pop> int q_pop_act(Pop *p, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps, int32_t *d_action, float *d_debug_q,
+                                   void *stream) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
     const PopCore &c = p->core;
     TRY(pop_check_rows(c, n_per_member, obs_stride));
@@ -1784,52 +1585,51 @@ int stmpc_pop_c51_act_device(stmpc_c51_pop *p, int n_per_member, const float *d_
     for (int m = 0; m < c.P(); ++m) {
         if (!(eps[m] >= 0 && eps[m] <= 1)) return fail(STMPC_EINVAL, "member " + std::to_string(m) + "'s eps must be in 0 ... 1");
         e.eps[m] = (float)eps[m];
-        if (eps[m] > 0) e.explore |= 1ull << m;                      // (stmpc_c51_act_device's rule: an exploring call is one with eps > 0)
+        if (eps[m] > 0) e.explore |= 1ull << m;                      // (q_act's rule: an exploring call is one with eps > 0)
     }
     if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(c.device));
-    hipLaunchKernelGGL(k_c51_act_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, c.P()), dim3(AT_THREADS), c.lds, (hipStream_t)stream, p->dev(), n_per_member, d_obs,
-                       obs_stride, e, d_action, d_debug_q);
+    Pop::Head::act_pop(p->dev(), c.P(), c.lds, n_per_member, d_obs, obs_stride, e, d_action, d_debug_q, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
-int stmpc_pop_c51_push_device(stmpc_c51_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
-                              const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+template <class Pop> int q_pop_push(Pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                                    const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
     const PopCore &c = p->core;
     TRY(pop_check_rows(c, n_per_member, obs_stride));
     TRY(pop_check_push(c, n_per_member));
     if (!d_obs || !d_next_obs || !d_action || !d_reward || !d_terminated || !d_truncated) return fail(STMPC_EINVAL, "NULL device pointer");
     HIPCHK(hipSetDevice(c.device));
-    hipLaunchKernelGGL(k_c51_push_pop, dim3(push_blocks(n_per_member), c.P()), dim3(256), 0, (hipStream_t)stream, p->dev(), n_per_member, d_obs, d_next_obs, d_final_obs,
-                       obs_stride, d_action, d_reward, d_terminated, d_truncated);
+    Pop::Head::push_pop(p->dev(), c.P(), n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
-int stmpc_pop_c51_update_device(stmpc_c51_pop *p, int n_updates, const double *lr, int n_lr, void *stream) {
+template <class Pop> int q_pop_update(Pop *p, int n_updates, const double *lr, int n_lr, void *stream) {
+    using H = typename Pop::Head;
     if (!p) return fail(STMPC_EINVAL, "NULL argument");
     const PopCore &c = p->core;
     DdpgLr lrs{};
     TRY(pop_check_update(c, n_updates, n_lr, {{lr, &lrs}}));
     HIPCHK(hipSetDevice(c.device));
-    const stmpc_c51 *t = p->members[0];
+    const typename Pop::Member *t = p->members[0];
     const Grid g = t->grid;
     const int P = c.P(), B = c.batch, Bp = t->rp.Bp;
     hipStream_t st = (hipStream_t)stream;
-    for (int u = 0; u < n_updates; ++u) {                            // stmpc_c51_update_device's three launches (five with prioritised members), each over the members
+    for (int u = 0; u < n_updates; ++u) {                            // q_update's three launches (five with prioritised members), each over the members
         if (c.per_any) hipLaunchKernelGGL(k_per_sample_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, Bp, 1);
-        hipLaunchKernelGGL(k_c51_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), c.lds, st, p->dev(), B, 1);
-        hipLaunchKernelGGL(k_c51_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, p->dev(), Bp, 1);
+        H::fwd_pop(p->dev(), g, P, c.lds, B, st);
+        H::wgrad_pop(p->dev(), g, P, Bp, st);
         if (c.per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, 1);
-        hipLaunchKernelGGL(k_c51_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, p->dev(), lrs, 1);
+        H::adam_pop(p->dev(), g, P, lrs, st);
     }
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
 
-int stmpc_pop_c51_stats_device(stmpc_c51_pop *p, double *d_out, void *stream) {
+template <class Pop> int q_pop_stats(Pop *p, double *d_out, void *stream) {
     if (!p || !d_out) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(p->core.device));
     hipLaunchKernelGGL(k_ddpg_stats_pop, dim3(1, p->core.P()), dim3(64), 0, (hipStream_t)stream, p->core.dev(), p->core.batch, d_out);
@@ -1837,25 +1637,55 @@ int stmpc_pop_c51_stats_device(stmpc_c51_pop *p, double *d_out, void *stream) {
     return STMPC_OK;
 }
 
-int stmpc_pop_c51_per_enable(stmpc_c51_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
+template <class Pop> int q_pop_per_enable(Pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    return pop_per_enable(p->core, cfgs, enabled, P, [&] { return c51_pop_upload(p); });
+    return pop_per_enable(p->core, cfgs, enabled, P, [&] { return q_pop_upload(p); });
 }
 
-int stmpc_pop_c51_multi_step_enable(stmpc_c51_pop *p, const stmpc_nstep_cfg *cfgs, int P) {
+template <class Pop> int q_pop_nstep_enable(Pop *p, const stmpc_nstep_cfg *cfgs, int P) {
     if (!p) return fail(STMPC_EINVAL, "population is NULL");
-    return pop_nstep_enable(p->core, cfgs, P, [&] { return c51_pop_upload(p); });
+    return pop_nstep_enable(p->core, cfgs, P, [&] { return q_pop_upload(p); });
 }
+}  // namespace
 
-int stmpc_pop_c51_replay_read(stmpc_c51 *t, int64_t first, int64_t count, float *rows) {
-    if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return t->rp.read_rows(first, count, rows);
-}
+extern "C" {
 
-int stmpc_pop_c51_multi_step_window(stmpc_c51 *t, const int64_t *idx, int n_idx, double *out) {
-    if (!t) return fail(STMPC_EINVAL, "NULL argument");
-    return nstep_window_read(t->rp, t->dev.dq.base, idx, n_idx, out);     // (stmpc_nstep_window_dqn's, on a borrowed member's or a lone learner's ring)
+int stmpc_pop_dqn_create(stmpc_ctx *c, const stmpc_dqn_cfg *cfgs, int P, stmpc_dqn_pop **out) { return q_pop_create(c, cfgs, P, out); }
+void stmpc_pop_dqn_destroy(stmpc_dqn_pop *p) { q_pop_destroy(p); }
+int stmpc_pop_dqn_size(const stmpc_dqn_pop *p) { return p ? p->core.P() : 0; }
+stmpc_dqn *stmpc_pop_dqn_member(stmpc_dqn_pop *p, int m) { return q_pop_member(p, m); }
+int stmpc_pop_dqn_act_device(stmpc_dqn_pop *p, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps, int32_t *d_action,
+                             float *d_debug_q, void *stream) {
+    return q_pop_act(p, n_per_member, d_obs, obs_stride, eps, n_eps, d_action, d_debug_q, stream);
 }
+int stmpc_pop_dqn_push_device(stmpc_dqn_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                              const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+    return q_pop_push(p, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream);
+}
+int stmpc_pop_dqn_update_device(stmpc_dqn_pop *p, int n_updates, const double *lr, int n_lr, void *stream) { return q_pop_update(p, n_updates, lr, n_lr, stream); }
+int stmpc_pop_dqn_stats_device(stmpc_dqn_pop *p, double *d_out, void *stream) { return q_pop_stats(p, d_out, stream); }
+int stmpc_pop_dqn_per_enable(stmpc_dqn_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) { return q_pop_per_enable(p, cfgs, enabled, P); }
+int stmpc_pop_nstep_enable_dqn(stmpc_dqn_pop *p, const stmpc_nstep_cfg *cfgs, int P) { return q_pop_nstep_enable(p, cfgs, P); }
+int stmpc_pop_dqn_replay_read(stmpc_dqn *t, int64_t first, int64_t count, float *rows) { return q_replay_read(t, first, count, rows); }
+
+int stmpc_pop_c51_create(stmpc_ctx *c, const stmpc_c51_cfg *cfgs, int P, stmpc_c51_pop **out) { return q_pop_create(c, cfgs, P, out); }
+void stmpc_pop_c51_destroy(stmpc_c51_pop *p) { q_pop_destroy(p); }
+int stmpc_pop_c51_size(const stmpc_c51_pop *p) { return p ? p->core.P() : 0; }
+stmpc_c51 *stmpc_pop_c51_member(stmpc_c51_pop *p, int m) { return q_pop_member(p, m); }
+int stmpc_pop_c51_act_device(stmpc_c51_pop *p, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps, int32_t *d_action,
+                             float *d_debug_q, void *stream) {
+    return q_pop_act(p, n_per_member, d_obs, obs_stride, eps, n_eps, d_action, d_debug_q, stream);
+}
+int stmpc_pop_c51_push_device(stmpc_c51_pop *p, int n_per_member, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride,
+                              const int32_t *d_action, const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
+    return q_pop_push(p, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream);
+}
+int stmpc_pop_c51_update_device(stmpc_c51_pop *p, int n_updates, const double *lr, int n_lr, void *stream) { return q_pop_update(p, n_updates, lr, n_lr, stream); }
+int stmpc_pop_c51_stats_device(stmpc_c51_pop *p, double *d_out, void *stream) { return q_pop_stats(p, d_out, stream); }
+int stmpc_pop_c51_per_enable(stmpc_c51_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) { return q_pop_per_enable(p, cfgs, enabled, P); }
+int stmpc_pop_c51_multi_step_enable(stmpc_c51_pop *p, const stmpc_nstep_cfg *cfgs, int P) { return q_pop_nstep_enable(p, cfgs, P); }
+int stmpc_pop_c51_replay_read(stmpc_c51 *t, int64_t first, int64_t count, float *rows) { return q_replay_read(t, first, count, rows); }
+int stmpc_pop_c51_multi_step_window(stmpc_c51 *t, const int64_t *idx, int n_idx, double *out) { return q_nstep_window(t, idx, n_idx, out); }
 
 }  // extern "C"
 

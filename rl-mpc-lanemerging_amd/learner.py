@@ -783,14 +783,15 @@ def per_member(value, P, default=None):
     return np.full(P, float(value)) if value.ndim == 0 else value
 
 
-class _PopulationMember(DDPGLearner):
-    """One member of a ``DDPGPopulation`` as a ``DDPGLearner``: the handle is borrowed from the population (``stmpc_ddpg_pop_member``), which
-    outlives it; everything else -- the seeded initialisation included -- is the lone learner's code."""
+class _Borrowed:
+    """In front of a lone learner's class, one member of a population as that learner: the handle is borrowed from the population (its binding's
+    ``member`` entry), which outlives it; everything else -- the seeded initialisation, and what a discrete learner takes from the env, included -- is
+    the lone learner's code."""
 
     _owns_handle = False
 
     def __init__(self, population, m, env, cfg, seed, init):
-        self._population, self._borrowed = population, population.ctx.ddpg_pop_member(population.handle, m)
+        self._population, self._borrowed = population, population._call("member")(population.handle, m)
         super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
 
     def _make_handle(self):
@@ -798,6 +799,10 @@ class _PopulationMember(DDPGLearner):
 
     def __del__(self):
         self.handle = None                                          # the population destroys its members
+
+
+class _PopulationMember(_Borrowed, DDPGLearner):
+    """One member of a ``DDPGPopulation`` as a ``DDPGLearner`` (``stmpc_ddpg_pop_member``)."""
 
 
 class DDPGPopulation:
@@ -1187,21 +1192,26 @@ def dqn_adam_host(w, g, m, v, beta_pow, lr, cfg):
     return w - step * (m / (np.sqrt(v) / bc2s + eps)), m, v, np.array([pw1, pw2], dtype=f)
 
 
-class DQNLearner(_Learner):
-    """DQN on the device for the discrete-action envs (``MergeVecEnv("sumo-jerk-v0")``, ``"sumo-accel-v0"``): the reference's TRAIN_DQN
-    (dqn.py:257-359) with ``DDPGLearner``'s interface.  ``env_or_dims``: such an env (its context, observation width, action count and action table
-    are taken over) or ``(n_obs, n_actions)``.  ``init``: None (torch's nn.Linear initialisation) or a net {w0, b0, w1, b1}.
-    One update is three HIP launches (five with ``cfg.per``); acting, pushing and updating never synchronise with the host.
-    ``rows_per_push``: as ``DDPGLearner``'s."""
+class _QLearner(_Learner):
+    """What ``DQNLearner`` and ``C51Learner`` share: everything but the head.  A subclass names itself for the refusals (``_name``), the cfg a learner
+    made without one gets (``_cfg_type``), the network's output width as its factors (``_out_shape``) and the net a learner made without one starts
+    from (``_init_net``); ``_check_cfg_type`` and ``_check_width`` are the two halves of a head's own cfg check, each where its refusal always came."""
 
-    _api, _per_api, _slots, _flatten = "dqn", "dqn_per", _capi.DQN_SLOTS, staticmethod(flatten_q)
+    _cfg_type = None
+
+    def _check_cfg_type(self):
+        pass
+
+    def _check_width(self):
+        pass
 
     def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None, rows_per_push=None):
         env = None if isinstance(env_or_dims, (tuple, list)) else env_or_dims
         if env is not None and env.continuous:
-            raise ValueError("DQN needs a discrete action space (sumo-jerk-v0 or sumo-accel-v0), not the continuous jerk env")
+            raise ValueError(self._name + " needs a discrete action space (sumo-jerk-v0 or sumo-accel-v0), not the continuous jerk env")
         n_obs, A = (env.obs_dim, int(env.action_space["n"])) if env is not None else (int(env_or_dims[0]), int(env_or_dims[1]))
-        self.cfg = cfg if cfg is not None else DQNConfig(n_obs=n_obs)
+        self.cfg = cfg if cfg is not None else self._cfg_type(n_obs=n_obs)
+        self._check_cfg_type()
         if self.cfg.n_actions is None:
             self.cfg.n_actions = A
         if self.cfg.n_obs != n_obs or self.cfg.n_actions != A:
@@ -1209,7 +1219,8 @@ class DQNLearner(_Learner):
         for name, ok in (("n_actions in 1 ... 256", 1 <= A <= 256), ("n_obs in 1 ... 31", 1 <= n_obs <= 31), ("batch >= 1", self.cfg.batch >= 1),
                          ("target_period >= 1", self.cfg.target_period >= 1)):
             if not ok:
-                raise ValueError("DQN needs " + name)
+                raise ValueError(self._name + " needs " + name)
+        self._check_width()
         # the env's table, index -> jerk or acceleration (what its cfg hands the library); without an env the indices stand for themselves
         self.action_values = np.array(env.cfg._actions, dtype=np.float64) if env is not None else np.arange(A, dtype=np.float64)
         self.env_id = getattr(env, "env_id", None)                    # (what actor.DQNActor.from_learner's default mode reads; None without an env)
@@ -1223,34 +1234,35 @@ class DQNLearner(_Learner):
         self.handle = self._make_handle()
         self._enable_nstep(env, rows_per_push)
         if self.cfg.per is not None:                                # (a population member's handle refuses: the population enables its members)
-            self.ctx.dqn_per_enable(self.handle, self.cfg.per.to_c())
-        c = self.cfg
-        net = init if init is not None else init_q_net(c.n_obs, c.h1, A, np.random.default_rng(self.seed))
+            self._call("per_enable")(self.handle, self.cfg.per.to_c())
+        c, out = self.cfg, self._out_shape()
+        self._n_out = int(np.prod(out))
+        net = init if init is not None else self._init_net(np.random.default_rng(self.seed))
         self._len = flatten_q(net).size
-        if self._len != (c.n_obs + 1) * c.h1 + (c.h1 + 1) * A:
-            raise ValueError("the net's tensors do not have the shape %d -> %d -> %d" % (c.n_obs, c.h1, A))
+        if self._len != (c.n_obs + 1) * c.h1 + (c.h1 + 1) * self._n_out:
+            raise ValueError("the net's tensors do not have the shape %d -> %d -> %s" % (c.n_obs, c.h1, " * ".join("%d" % f for f in out)))
         self.load_state_dict({"params": new_params_dqn(net), "counters": None})
         self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self._actions = {}
 
     def _make_handle(self):
-        return self.ctx.dqn_create(self.cfg.to_c(self.seed))
+        return self._call("create")(self.cfg.to_c(self.seed))
 
     def _slot(self, i):
-        c = self.cfg
-        return unflatten_q(self.ctx.dqn_get_params(self.handle, i, self._len), c.n_obs, c.h1, c.n_actions)
+        return unflatten_q(self._call("get_params")(self.handle, i, self._len), self.cfg.n_obs, self.cfg.h1, self._n_out)
 
     # -- acting / replay / update: asynchronous ---------------------------------------------------------------------------------------------
     def act(self, obs, ticks=None, eps=0.0, debug_q=None):
-        """Action indices int32 [n] (what ``MergeVecEnv.step`` takes) for observations float32 [n][n_obs]: the first maximum of Q(obs); with
-        ``eps`` > 0 a row explores with that probability and then takes a uniform index (``dqn_act_host``).  ``ticks`` is accepted for
-        ``DDPGLearner``'s signature and not read: the network has no time feature.  The returned tensor is reused by the next call with the
-        same n.  ``debug_q``: float32 [n][n_actions] device tensor for Q(obs)."""
+        """Action indices int32 [n] (what ``MergeVecEnv.step`` takes) for observations float32 [n][n_obs]: the first maximum of Q(obs) -- of a
+        categorical learner, of the expected values E[Z(obs, a)] --; with ``eps`` > 0 a row explores with that probability and then takes a uniform
+        index (``dqn_act_host``).  ``ticks`` is accepted for ``DDPGLearner``'s signature and not read: the network has no time feature.  The
+        returned tensor is reused by the next call with the same n.  ``debug_q``: float32 [n][n_actions] device tensor for Q(obs) (the expected
+        values)."""
         n = obs.shape[0]
         out = self._out(n, self.torch.int32)
         assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
         assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (n, self.cfg.n_actions))
-        self.ctx.dqn_act(self.handle, n, obs.data_ptr(), obs.stride(0), eps, out.data_ptr(), debug_q.data_ptr() if debug_q is not None else 0, self._stream())
+        self._call("act")(self.handle, n, obs.data_ptr(), obs.stride(0), eps, out.data_ptr(), debug_q.data_ptr() if debug_q is not None else 0, self._stream())
         return out
 
     def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
@@ -1260,30 +1272,47 @@ class DQNLearner(_Learner):
         assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == torch.int32 and reward.dtype == torch.float64 and action.is_contiguous()
         assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
         assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
-        self.ctx.dqn_push(self.handle, obs.shape[0], obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0, obs.stride(0),
-                          action.data_ptr(), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self._stream())
+        self._call("push")(self.handle, obs.shape[0], obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0, obs.stride(0),
+                           action.data_ptr(), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self._stream())
 
     def update(self, n=1, lr=None):
         """``n`` updates; on the device nothing happens until more than cfg.replay_start frames were pushed.  ``lr``: this call's learning rate."""
-        self.ctx.dqn_update(self.handle, n, self.cfg.lr if lr is None else lr, self._stream())
+        self._call("update")(self.handle, n, self.cfg.lr if lr is None else lr, self._stream())
 
     def grads(self):
         """Debug: the loss's gradient on the current update index's minibatch as a dict of numpy tensors; nothing applied; synchronises."""
-        c = self.cfg
         g = self.torch.empty(self._len, dtype=self.torch.float32, device=self.device)
-        self.ctx.dqn_grads(self.handle, g.data_ptr(), self._stream())
-        return unflatten_q(g.cpu().numpy(), c.n_obs, c.h1, c.n_actions)
+        self._call("grads")(self.handle, g.data_ptr(), self._stream())
+        return unflatten_q(g.cpu().numpy(), self.cfg.n_obs, self.cfg.h1, self._n_out)
 
     def targets(self):
-        """Debug: float32 [batch][4] = a*, the target net's Q(s') there, y, Q(s, a) of the minibatch the next update will draw; synchronises."""
+        """Debug: float32 [batch][4] of the minibatch the next update will draw -- DQN: a*, the target net's Q(s') there, y, Q(s, a); C51: a*, the
+        target net's expected value there, the row loss l, Q(s, a) --; synchronises."""
         out = self.torch.zeros(self.cfg.batch, 4, dtype=self.torch.float32, device=self.device)
-        self.ctx.dqn_targets(self.handle, out.data_ptr(), self._stream())
+        self._call("targets")(self.handle, out.data_ptr(), self._stream())
         return out.cpu().numpy()
 
     def stats(self):
         """``stats_device`` as a dict; synchronises."""
         s = self.stats_device().cpu().numpy()
         return {"loss": float(s[0]), "mean_q": float(s[1]), "fill": int(s[2]), "updates": int(s[3])}
+
+
+class DQNLearner(_QLearner):
+    """DQN on the device for the discrete-action envs (``MergeVecEnv("sumo-jerk-v0")``, ``"sumo-accel-v0"``): the reference's TRAIN_DQN
+    (dqn.py:257-359) with ``DDPGLearner``'s interface.  ``env_or_dims``: such an env (its context, observation width, action count and action table
+    are taken over) or ``(n_obs, n_actions)``.  ``init``: None (torch's nn.Linear initialisation) or a net {w0, b0, w1, b1}.
+    One update is three HIP launches (five with ``cfg.per``); acting, pushing and updating never synchronise with the host.
+    ``rows_per_push``: as ``DDPGLearner``'s."""
+
+    _api, _per_api, _slots, _flatten = "dqn", "dqn_per", _capi.DQN_SLOTS, staticmethod(flatten_q)
+    _name, _cfg_type = "DQN", DQNConfig
+
+    def _out_shape(self):
+        return (self.cfg.n_actions,)
+
+    def _init_net(self, rng):
+        return init_q_net(self.cfg.n_obs, self.cfg.h1, self.cfg.n_actions, rng)
 
     def export_q(self, path):
         """Write the online Q-network as an ``.npz``: w0, b0, w1, b1 (float32) and ``action_values`` (the env's table, index -> jerk or acceleration)."""
@@ -1292,21 +1321,8 @@ class DQNLearner(_Learner):
         return path
 
 
-class _DQNPopulationMember(DQNLearner):
-    """One member of a ``DQNPopulation`` as a ``DQNLearner``: the handle is borrowed from the population (``stmpc_pop_dqn_member``), which outlives
-    it; everything else -- the seeded initialisation, ``action_values`` and ``env_id`` from the env included -- is the lone learner's code."""
-
-    _owns_handle = False
-
-    def __init__(self, population, m, env, cfg, seed, init):
-        self._population, self._borrowed = population, population.ctx.dqn_pop_member(population.handle, m)
-        super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
-
-    def _make_handle(self):
-        return self._borrowed
-
-    def __del__(self):
-        self.handle = None                                          # the population destroys its members
+class _DQNPopulationMember(_Borrowed, DQNLearner):
+    """One member of a ``DQNPopulation`` as a ``DQNLearner`` (``stmpc_pop_dqn_member``)."""
 
 
 class DQNPopulation(DDPGPopulation):
@@ -1532,95 +1548,26 @@ def update_host_c51(params, batch, cfg, dtype="float64", weights=None, grads_onl
     return out, info
 
 
-class C51Learner(_Learner):
+class C51Learner(_QLearner):
     """Categorical DQN on the device for the discrete-action envs, with ``DQNLearner``'s interface (``train_dqn`` takes either).  ``env_or_dims``: a
     discrete env or ``(n_obs, n_actions)``; ``cfg``: ``C51Config``; ``init``: None (torch's nn.Linear initialisation, ``init_c51_net``) or a net
     {w0, b0, w1 [A * n_atoms][h1], b1 [A * n_atoms]}.  One update is three HIP launches (five with ``cfg.per``)."""
 
     _api, _per_api, _slots, _flatten = "c51", "c51_per", _capi.C51_SLOTS, staticmethod(flatten_q)
+    _name, _cfg_type = "C51", C51Config
 
-    def __init__(self, env_or_dims, cfg=None, seed=0, init=None, ctx=None, rows_per_push=None):
-        env = None if isinstance(env_or_dims, (tuple, list)) else env_or_dims
-        if env is not None and env.continuous:
-            raise ValueError("C51 needs a discrete action space (sumo-jerk-v0 or sumo-accel-v0), not the continuous jerk env")
-        n_obs, A = (env.obs_dim, int(env.action_space["n"])) if env is not None else (int(env_or_dims[0]), int(env_or_dims[1]))
-        self.cfg = cfg if cfg is not None else C51Config(n_obs=n_obs)
+    def _check_cfg_type(self):
         if not isinstance(self.cfg, C51Config):
             raise ValueError("cfg must be a C51Config")
-        if self.cfg.n_actions is None:
-            self.cfg.n_actions = A
-        if self.cfg.n_obs != n_obs or self.cfg.n_actions != A:
-            raise ValueError("cfg has n_obs %d and %d actions; the observation has %d entries and there are %d actions" % (self.cfg.n_obs, self.cfg.n_actions, n_obs, A))
-        for name, ok in (("n_actions in 1 ... 256", 1 <= A <= 256), ("n_obs in 1 ... 31", 1 <= n_obs <= 31), ("batch >= 1", self.cfg.batch >= 1),
-                         ("target_period >= 1", self.cfg.target_period >= 1)):
-            if not ok:
-                raise ValueError("C51 needs " + name)
+
+    def _check_width(self):
         self.cfg.check_width()
-        self.action_values = np.array(env.cfg._actions, dtype=np.float64) if env is not None else np.arange(A, dtype=np.float64)
-        self.env_id = getattr(env, "env_id", None)
-        if self.action_values.shape != (A,):
-            raise ValueError("the env's action table has %d entries, its action space %d" % (self.action_values.size, A))
-        import torch
-        self.torch = torch
-        self.ctx = ctx if ctx is not None else (env.ctx if env is not None else _capi.Context(-1))
-        self.seed = int(seed)
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self.handle = self._make_handle()
-        self._enable_nstep(env, rows_per_push)
-        if self.cfg.per is not None:                                # (a population member's handle refuses: the population enables its members)
-            self.ctx.c51_per_enable(self.handle, self.cfg.per.to_c())
-        c = self.cfg
-        self._n_out = A * c.n_atoms
-        net = init if init is not None else init_c51_net(c.n_obs, c.h1, A, c.n_atoms, np.random.default_rng(self.seed))
-        self._len = flatten_q(net).size
-        if self._len != (c.n_obs + 1) * c.h1 + (c.h1 + 1) * self._n_out:
-            raise ValueError("the net's tensors do not have the shape %d -> %d -> %d * %d" % (c.n_obs, c.h1, A, c.n_atoms))
-        self.load_state_dict({"params": new_params_dqn(net), "counters": None})
-        self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
-        self._actions = {}
 
-    def _make_handle(self):
-        return self.ctx.c51_create(self.cfg.to_c(self.seed))
+    def _out_shape(self):
+        return (self.cfg.n_actions, self.cfg.n_atoms)
 
-    def _slot(self, i):
-        return unflatten_q(self.ctx.c51_get_params(self.handle, i, self._len), self.cfg.n_obs, self.cfg.h1, self._n_out)
-
-    # -- acting / replay / update: asynchronous ---------------------------------------------------------------------------------------------
-    def act(self, obs, ticks=None, eps=0.0, debug_q=None):
-        """``DQNLearner.act`` on the expected values: int32 [n], the first maximum of E[Z(obs, a)]; ``eps`` > 0 explores as ``dqn_act_host`` says.
-        ``debug_q``: float32 [n][n_actions] device tensor for the expected values."""
-        n = obs.shape[0]
-        out = self._out(n, self.torch.int32)
-        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
-        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (n, self.cfg.n_actions))
-        self.ctx.c51_act(self.handle, n, obs.data_ptr(), obs.stride(0), eps, out.data_ptr(), debug_q.data_ptr() if debug_q is not None else 0, self._stream())
-        return out
-
-    def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
-        """``DQNLearner.push``: one env step into the replay ring."""
-        torch = self.torch
-        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == torch.int32 and reward.dtype == torch.float64 and action.is_contiguous()
-        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
-        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
-        self.ctx.c51_push(self.handle, obs.shape[0], obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0, obs.stride(0),
-                          action.data_ptr(), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self._stream())
-
-    def update(self, n=1, lr=None):
-        """``n`` updates; on the device nothing happens until more than cfg.replay_start frames were pushed.  ``lr``: this call's learning rate."""
-        self.ctx.c51_update(self.handle, n, self.cfg.lr if lr is None else lr, self._stream())
-
-    def grads(self):
-        """Debug: the loss's gradient on the current update index's minibatch as a dict of numpy tensors; nothing applied; synchronises."""
-        g = self.torch.empty(self._len, dtype=self.torch.float32, device=self.device)
-        self.ctx.c51_grads(self.handle, g.data_ptr(), self._stream())
-        return unflatten_q(g.cpu().numpy(), self.cfg.n_obs, self.cfg.h1, self._n_out)
-
-    def targets(self):
-        """Debug: float32 [batch][4] = a*, the target net's expected value there, the row loss l, Q(s, a) of the minibatch the next update will
-        draw; synchronises."""
-        out = self.torch.zeros(self.cfg.batch, 4, dtype=self.torch.float32, device=self.device)
-        self.ctx.c51_targets(self.handle, out.data_ptr(), self._stream())
-        return out.cpu().numpy()
+    def _init_net(self, rng):
+        return init_c51_net(self.cfg.n_obs, self.cfg.h1, self.cfg.n_actions, self.cfg.n_atoms, rng)
 
     def dist(self):
         """Debug: (float32 [batch][2][n_atoms] = the projected target distribution m and the online distribution p(s, a); ``targets()``'s array) of
@@ -1641,11 +1588,6 @@ class C51Learner(_Learner):
         self.ctx.c51_project(self.handle, p.shape[0], p.data_ptr(), reward.data_ptr(), mask.data_ptr(), disc.data_ptr(), m.data_ptr(), self._stream())
         return m.cpu().numpy()
 
-    def stats(self):
-        """``stats_device`` as a dict; synchronises."""
-        s = self.stats_device().cpu().numpy()
-        return {"loss": float(s[0]), "mean_q": float(s[1]), "fill": int(s[2]), "updates": int(s[3])}
-
     def export_q(self, path):
         """Write the online logits network as an ``.npz``: w0, b0, w1, b1 (float32), ``action_values`` and the head's ``n_atoms``, ``v_min``, ``v_max``."""
         with open(path, "wb") as fh:
@@ -1654,21 +1596,8 @@ class C51Learner(_Learner):
         return path
 
 
-class _C51PopulationMember(C51Learner):
-    """One member of a ``C51Population`` as a ``C51Learner``: the handle is borrowed from the population (``stmpc_pop_c51_member``), which outlives
-    it; everything else -- the seeded initialisation, ``action_values`` and ``env_id`` from the env included -- is the lone learner's code."""
-
-    _owns_handle = False
-
-    def __init__(self, population, m, env, cfg, seed, init):
-        self._population, self._borrowed = population, population.ctx.c51_pop_member(population.handle, m)
-        super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
-
-    def _make_handle(self):
-        return self._borrowed
-
-    def __del__(self):
-        self.handle = None                                          # the population destroys its members
+class _C51PopulationMember(_Borrowed, C51Learner):
+    """One member of a ``C51Population`` as a ``C51Learner`` (``stmpc_pop_c51_member``)."""
 
 
 class C51Population(DQNPopulation):
