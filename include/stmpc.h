@@ -996,12 +996,36 @@ int  stmpc_nstep_window_dqn(stmpc_dqn *learner, const int64_t *idx, int n_idx, d
  *   padded_read     debug, HOST: a slot as the library keeps it -- W0 [h1p][32] | b0 [h1p] | W1 [Ap][h1p] | b1 [Ap], h1p and Ap the next multiples of
  *                   16 of h1 and n_actions * n_atoms; slots STMPC_C51_Q ... _Q_V, and STMPC_C51_GRAD: the last gradient.  Synchronises
  */
+/*
+ * The dueling head (stmpc_c51_cfg.dueling = 1): Wang et al. 2016, "Dueling Network Architectures for Deep Reinforcement Learning", in the categorical
+ * form of Hessel et al. 2018, "Rainbow: Combining Improvements in Deep Reinforcement Learning", section "Dueling networks" -- the fifth of the six
+ * pieces of the reference's third agent (rainbow.py: the `all` library's rainbow preset).  The head restates the published one; the library is not
+ * available, so parity with its own network stays unpinned.  (`dueling` is the field ABI 8 called `reserved`, at the same offset and size, and 0
+ * keeps its meaning: no signature or struct layout changes, STMPC_ABI_VERSION stays 8, and with dueling = 0 every entry computes what it computed.)
+ *   network         n_obs -> h1 -> ReLU -> (n_actions + 1) * n_atoms.  The output layer holds the n_actions ADVANTAGE blocks first, where the plain
+ *                   head's action blocks sit (outputs a * n_atoms ... (a + 1) * n_atoms - 1), and the VALUE block last (outputs n_actions * n_atoms
+ *                   ... (n_actions + 1) * n_atoms - 1).  Ap is the next multiple of 16 of (n_actions + 1) * n_atoms
+ *   logits          l[a][k] = V[k] + Adv[a][k] - (1 / n_actions) * sum_b Adv[b][k]: the float32 outputs go to fp64, the sum runs in b order, the
+ *                   division and the two additions are fp64, one rounding to float32.  Everything behind the logits -- softmax, expected values,
+ *                   the first maximum a*, the projection, the cross-entropy, the priorities -- is the plain head's, unchanged
+ *   backward        with g[k] = (w / batch) (p[k] - m[k]) of the stored action a: advantage block b receives g[k] * ((b == a) - 1 / n_actions),
+ *                   formed in fp64 and rounded once, the value block g[k]; dzout_read is then DENSE over the (n_actions + 1) * n_atoms outputs, and
+ *                   its pad columns and the rows at or beyond batch are exact zeros
+ *   slots           W0 [h1][n_obs] | b0 [h1] | W1 [(n_actions + 1) * n_atoms][h1] | b1 [(n_actions + 1) * n_atoms] in set / get_params and
+ *                   grads_device; padded_read and dzout_read follow the padded width
+ *   create          refuses (STMPC_EINVAL) a `dueling` other than 0 or 1, and with dueling = 1 (n_actions + 1) * n_atoms > STMPC_C51_MAX_LOGITS (the
+ *                   message names the product and the limit).  sumo-accel-v0 has 20 actions: with a dueling head it takes at most 48 atoms (21 * 48 =
+ *                   1008; 21 * 49 = 1029), where the plain head takes 51
+ *   populations     the members of a stmpc_pop_c51_create share `dueling` (it sets the network's shape): a mix is refused
+ *   policies        stmpc_c51actor_view of a dueling learner evaluates through the learner's own struct, head included; a policy from plain tensors
+ *                   with (n_actions + 1) * n_atoms output rows is created by stmpc_dueling_c51actor_create (below the C51 policy's entries)
+ */
 #define STMPC_C51_Q 0
 #define STMPC_C51_Q_TARGET 1
 #define STMPC_C51_Q_M 2
 #define STMPC_C51_Q_V 3
 #define STMPC_C51_GRAD 4                  /* padded_read only */
-#define STMPC_C51_MAX_LOGITS 1024         /* n_actions * n_atoms: the widest layer of the parameter layout */
+#define STMPC_C51_MAX_LOGITS 1024         /* n_actions * n_atoms, with a dueling head (n_actions + 1) * n_atoms: the widest layer of the parameter layout */
 typedef struct stmpc_c51_cfg {
     int32_t n_obs;                   /* the first sixteen fields are stmpc_dqn_cfg's, in its order */
     int32_t h1;
@@ -1018,7 +1042,7 @@ typedef struct stmpc_c51_cfg {
     double clip_min, clip_max;       /* not read */
     double v_min, v_max;             /* the support's ends (-10, 10: the C51 paper's) */
     int32_t n_atoms;                 /* K >= 2 (51) */
-    int32_t reserved;                /* 0 */
+    int32_t dueling;                 /* 0: the plain head; 1: the dueling head (below).  The field ABI 8 called `reserved` and wanted 0 */
 } stmpc_c51_cfg;
 typedef struct stmpc_c51 stmpc_c51;
 int  stmpc_c51_create(stmpc_ctx *ctx, const stmpc_c51_cfg *cfg, stmpc_c51 **out);
@@ -1172,6 +1196,17 @@ int  stmpc_qactor_eval_device(stmpc_ctx *ctx, const stmpc_qactor *qactor, const 
 int  stmpc_c51actor_create(stmpc_ctx *ctx, int n_in, int h1, int n_actions, int n_atoms, double v_min, double v_max, const float *w0, const float *b0,
                            const float *w1, const float *b1, const double *action_values, int mode, stmpc_qactor **out);
 int  stmpc_c51actor_view(stmpc_c51 *learner, int target, const double *action_values, int n_actions, int mode, stmpc_qactor **out);
+
+/*
+ * A categorical policy with a DUELING head from plain tensors: stmpc_c51actor_create with its arguments, for a network as a dueling C51Learner's
+ * export_q writes it -- w1 [(n_actions + 1) * n_atoms][h1], b1 [(n_actions + 1) * n_atoms], the n_actions advantage blocks first and the value block
+ * last (the layout of stmpc_c51_cfg.dueling above).  The result is a stmpc_qactor like that entry's, bit-identical to stmpc_c51actor_view of a dueling
+ * stmpc_c51 loaded with the same tensors.  STMPC_EINVAL for what stmpc_c51actor_create refuses, with (n_actions + 1) * n_atoms >
+ * STMPC_C51_MAX_LOGITS in the width's place.  (Additive: a new entry, STMPC_ABI_VERSION stays 8.  It is not named stmpc_c51actor_...: that prefix is
+ * a closed set of two entries.)  Synchronises
+ */
+int  stmpc_dueling_c51actor_create(stmpc_ctx *ctx, int n_in, int h1, int n_actions, int n_atoms, double v_min, double v_max, const float *w0,
+                                   const float *b0, const float *w1, const float *b1, const double *action_values, int mode, stmpc_qactor **out);
 
 /*
  * A population of Q-networks as policies, evaluated in one launch: what stmpc_actor_pop_* is for DDPG actors, for the Q-actors above.  The reference

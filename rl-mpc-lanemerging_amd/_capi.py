@@ -282,8 +282,10 @@ class DQNCfg(C.Structure):
 
 
 class C51Cfg(C.Structure):
-    """``stmpc_c51_cfg`` (include/stmpc.h): ``stmpc_dqn_cfg``'s fields, then the support's ends and the atom count of the categorical head."""
-    _fields_ = list(DQNCfg._fields_) + [("v_min", C.c_double), ("v_max", C.c_double), ("n_atoms", C.c_int32), ("reserved", C.c_int32)]
+    """``stmpc_c51_cfg`` (include/stmpc.h): ``stmpc_dqn_cfg``'s fields, then the support's ends, the atom count of the categorical head and
+    ``dueling`` (0 / 1: the dueling head).  ``reserved`` is that field under the name it had while it had to be 0."""
+    _fields_ = list(DQNCfg._fields_) + [("v_min", C.c_double), ("v_max", C.c_double), ("n_atoms", C.c_int32), ("dueling", C.c_int32)]
+    reserved = property(lambda self: self.dueling, lambda self, value: setattr(self, "dueling", value))
 
 
 class ProfileTotals(C.Structure):
@@ -334,7 +336,7 @@ EXPORTS = (
     "stmpc_nstep_window_ddpg", "stmpc_nstep_window_dqn",
     "stmpc_qactor_create", "stmpc_qactor_view_dqn", "stmpc_qactor_destroy", "stmpc_qactor_set_limits", "stmpc_qactor_eval_device",
     "stmpc_pop_qactor_create", "stmpc_pop_qactor_destroy", "stmpc_pop_qactor_size", "stmpc_pop_qactor_eval_device",
-    "stmpc_c51actor_create", "stmpc_c51actor_view",
+    "stmpc_c51actor_create", "stmpc_c51actor_view", "stmpc_dueling_c51actor_create",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
@@ -610,6 +612,7 @@ def load():
     lib.stmpc_qactor_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, dp, C.c_int, C.POINTER(vp)]
     lib.stmpc_qactor_view_dqn.argtypes = [vp, C.c_int, dp, C.c_int, C.c_int, C.POINTER(vp)]
     lib.stmpc_c51actor_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, fp, fp, fp, fp, dp, C.c_int, C.POINTER(vp)]
+    lib.stmpc_dueling_c51actor_create.argtypes = list(lib.stmpc_c51actor_create.argtypes)
     lib.stmpc_c51actor_view.argtypes = [vp, C.c_int, dp, C.c_int, C.c_int, C.POINTER(vp)]
     lib.stmpc_qactor_destroy.argtypes = [vp]
     lib.stmpc_qactor_destroy.restype = None
@@ -1390,20 +1393,22 @@ class Context:
         self._chk(self._lib.stmpc_qactor_view_dqn(learner_handle, int(bool(target)), table.ctypes.data_as(C.POINTER(C.c_double)), int(table.size), int(mode), C.byref(h)))
         return h
 
-    def c51actor_create(self, net, action_values, n_atoms, v_min, v_max, mode=0):
+    def c51actor_create(self, net, action_values, n_atoms, v_min, v_max, mode=0, dueling=False):
         """``qactor_create`` for a categorical (C51) network: w1 [A * n_atoms][h1], b1 [A * n_atoms] as ``C51Learner.export_q`` writes them, with the
-        support's ``n_atoms``, ``v_min``, ``v_max`` (``stmpc_c51actor_create``).  The handle is a Q-actor's: ``qactor_eval_device``, ``qactor_set_limits``
-        and ``qactor_destroy`` take it."""
+        support's ``n_atoms``, ``v_min``, ``v_max`` (``stmpc_c51actor_create``).  ``dueling``: the net has (A + 1) * n_atoms output rows, the value
+        block last (``stmpc_dueling_c51actor_create``).  The handle is a Q-actor's: ``qactor_eval_device``, ``qactor_set_limits`` and
+        ``qactor_destroy`` take it."""
         f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
         w0, b0, w1, b1 = f32(net["w0"]), f32(net["b0"]).reshape(-1), f32(net["w1"]), f32(net["b1"]).reshape(-1)
         table = np.ascontiguousarray(action_values, dtype=np.float64).reshape(-1)
         if (w0.ndim != 2 or w1.ndim != 2 or b0.size != w0.shape[0] or w1.shape[1] != w0.shape[0] or b1.size != w1.shape[0]
-                or w1.shape[0] != table.size * int(n_atoms)):
-            raise ValueError("the net's tensors are not w0 [h1][n_in], b0 [h1], w1 [A * n_atoms][h1], b1 [A * n_atoms]")
+                or w1.shape[0] != (table.size + (1 if dueling else 0)) * int(n_atoms)):
+            raise ValueError("the net's tensors are not w0 [h1][n_in], b0 [h1], w1 [%s * n_atoms][h1], b1 [%s * n_atoms]" % (("(A + 1)",) * 2 if dueling else ("A",) * 2))
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
         h = C.c_void_p()
-        self._chk(self._lib.stmpc_c51actor_create(self._h, int(w0.shape[1]), int(w0.shape[0]), int(table.size), int(n_atoms), float(v_min), float(v_max), fp(w0),
-                                                  fp(b0), fp(w1), fp(b1), table.ctypes.data_as(C.POINTER(C.c_double)), int(mode), C.byref(h)))
+        create = self._lib.stmpc_dueling_c51actor_create if dueling else self._lib.stmpc_c51actor_create
+        self._chk(create(self._h, int(w0.shape[1]), int(w0.shape[0]), int(table.size), int(n_atoms), float(v_min), float(v_max), fp(w0), fp(b0), fp(w1), fp(b1),
+                         table.ctypes.data_as(C.POINTER(C.c_double)), int(mode), C.byref(h)))
         return h
 
     def c51actor_view(self, learner_handle, action_values, target=False, mode=0):

@@ -402,7 +402,9 @@ class C51Actor(DQNActor):
     ``n`` states in ONE launch (``k_c51actor_eval``, csrc/stmpc_c51actor_kernels.hpp).  A subclass: whatever takes a ``DQNActor`` --
     ``combined.decide_batch_device``, ``episodes.EpisodeRunner``, ``learner.evaluate_dqn``, ``vec_env.QCombinedShieldVecEnv`` -- takes it.
 
-    ``source``: a file written by ``learner.C51Learner.export_q`` (w0, b0, w1 [A * n_atoms][h1], b1, action_values, n_atoms, v_min, v_max).
+    ``source``: a file written by ``learner.C51Learner.export_q`` (w0, b0, w1 [A * n_atoms][h1], b1, action_values, n_atoms, v_min, v_max, dueling).
+    ``dueling`` = 1: w1 and b1 have (A + 1) * n_atoms rows, the value block last, and the logits are the dueling head's
+    (``stmpc_dueling_c51actor_create``); a file without the key has the plain head.  ``.dueling`` says which.
     ``.shape`` is (n_in, h1, A); ``.n_atoms``, ``.v_min``, ``.v_max`` the head's support; ``.q`` (with ``keep_q``) holds the expected values,
     float32 [n][A].  ``mode``, the call, ``reset``, ``keep_features`` and ``keep_q`` are ``DQNActor``'s.  The expected values, the index and the jerk
     are bit for bit what ``C51Learner.act`` gives on the same input vectors; ``c51_policy_host`` is the host twin.  There is no population of C51
@@ -415,12 +417,17 @@ class C51Actor(DQNActor):
             net = {k: np.array(z[k], dtype=np.float32) for k in ("w0", "b0", "w1", "b1")}
             table = np.array(z["action_values"], dtype=np.float64) if action_values is None else action_values
             self.n_atoms, self.v_min, self.v_max = int(z["n_atoms"]), float(z["v_min"]), float(z["v_max"])
+            self.dueling = bool(int(z["dueling"])) if "dueling" in z.files else False
         A, rest = divmod(int(net["w1"].shape[0]), self.n_atoms) if self.n_atoms >= 1 else (0, 1)
         if rest or A < 1:
             raise ValueError("the last layer has %d rows, no multiple of n_atoms = %d" % (net["w1"].shape[0], self.n_atoms))
+        if self.dueling:
+            A -= 1                                                  # (the value block)
+            if A < 1:
+                raise ValueError("a dueling head has the value block and at least one advantage block; the last layer has %d rows" % net["w1"].shape[0])
         self._setup(n, ctx, S, mode, table, (int(net["w0"].shape[1]), int(net["w0"].shape[0]), A))
         self.name, self.learner, self.target = os.fspath(source), None, False
-        self.handle = ctx.c51actor_create(net, self.action_values, self.n_atoms, self.v_min, self.v_max, _capi.QACTOR_MODES[self.mode])
+        self.handle = ctx.c51actor_create(net, self.action_values, self.n_atoms, self.v_min, self.v_max, _capi.QACTOR_MODES[self.mode], dueling=self.dueling)
         self._limits(S)
 
     @classmethod
@@ -432,7 +439,7 @@ class C51Actor(DQNActor):
         c = learner.cfg
 
         def make_handle(self):
-            self.n_atoms, self.v_min, self.v_max = int(c.n_atoms), float(c.v_min), float(c.v_max)
+            self.n_atoms, self.v_min, self.v_max, self.dueling = int(c.n_atoms), float(c.v_min), float(c.v_max), bool(getattr(c, "dueling", False))
             return ctx.c51actor_view(learner.handle, self.action_values, self.target, _capi.QACTOR_MODES[self.mode])
         return cls._view(learner, n, ctx, S, target, mode, make_handle)
 

@@ -20,6 +20,18 @@
 // run lane-strided with a butterfly behind them (a fixed order), and every result is rounded to float32 once.  The projection accumulates in fp64 in
 // j order: no float atomics, no scatter adds.  It is the gather form: it stays right where b_j is an integer, where the textbook l / u scatter
 // loses the mass.
+//
+// The dueling head (C51Dev::dueling; Wang et al. 2016, "Dueling Network Architectures for Deep Reinforcement Learning", in the categorical form of
+// Hessel et al. 2018, "Rainbow", section "Dueling networks"; a restatement of the published head: parity with the `all` library's own is not pinned,
+// the library is absent).  The network is n_obs -> h1 -> ReLU -> (A + 1) * K: the A advantage blocks sit where the action blocks sit, columns a K ...
+// a K + K - 1, the value block comes last, columns A K ... A K + K - 1, and Ap = pad16((A + 1) K).  The logits of action a are
+//   l[a][k] = V[k] + Adv[a][k] - (1 / A) sum_b Adv[b][k]
+// formed by c51_dueling_combine behind every dqn_q, in place over the advantage blocks; from there on the first A blocks of a row are ordinary C51
+// logits and everything above holds as it stands.  Backward, with g[k] = (w / B)(p[k] - m[k]) of the stored action a: dZout is dense -- advantage
+// block b gets g[k] ((b == a) - 1 / A), the value block g[k], pad columns and the rows at or beyond B exact zeros -- and dZ1 sums over all (A + 1) K
+// rows of W1 in row order.  In the acting and evaluation kernels the head is a branch on D.dueling, uniform across the grid; the forward / backward pass
+// takes it as a template argument and has a kernel per head (k_c51_fwd, k_c51_fwd_duel), because with both heads in one kernel the plain head's pass
+// lost its register budget.  With dueling == 0 every kernel computes what it computed without it.
 #pragma once
 #include "stmpc_dqn_kernels.hpp"
 
@@ -28,6 +40,7 @@ namespace stmpc {
 struct C51Dev {
     DqnDev dq;                      // dq.A: the real actions; dq.Ap = pad16(A * K) = dq.base.h2p; dq.base.h2 = A * K; dq.clip unused (0)
     int K;                          // atoms
+    int dueling;                    // 1: the dueling head -- dq.base.h2 = (A + 1) K, dq.Ap = pad16 of it, the value block behind the A advantage blocks
     double v_min, v_max, dz;        // the support, in fp64: dz = (v_max - v_min) / (K - 1) is no float32 number at the shipped K = 51
 };
 
@@ -74,6 +87,22 @@ __device__ __forceinline__ int c51_greedy(const C51Dev &D, const float *q, float
     return bi;
 }
 
+// The dueling head's combine of one row of outputs q[(A + 1) K], in place, by the row's 32 lanes: l[a][k] = (V[k] + Adv[a][k]) - (sum_b Adv[b][k]) / A.
+// The float32 outputs go to fp64, the sum runs in b order, the division and the two additions are fp64, and the result is rounded to float32 once and
+// stored over Adv[a][k].  A lane owns the columns k = part, part + 32, ... of its row in every block: no lane reads what another writes.  The value
+// block stays.  Ends with a barrier (every thread of the workgroup calls it: the branch that leads here is uniform)
+__device__ __forceinline__ void c51_dueling_combine(const C51Dev &D, float *q) {
+    const int part = threadIdx.x & 31, A = D.dq.A, K = D.K;
+    const float *v = q + (size_t)A * K;
+    for (int k = part; k < K; k += 32) {
+        double s = 0.0;
+        for (int b = 0; b < A; ++b) s += (double)q[(size_t)b * K + k];
+        const double mean = s / (double)A, vk = (double)v[k];
+        for (int a = 0; a < A; ++a) q[(size_t)a * K + k] = (float)((vk + (double)q[(size_t)a * K + k]) - mean);
+    }
+    __syncthreads();
+}
+
 // The categorical projection of one row, by its 32 lanes (all 64 lanes of the wave call it): the atoms z_j move to t_j = clamp(R + disc z_j, v_min,
 // v_max) -- R alone where mask == 0: a select, not a product --, b_j = (t_j - v_min) / dz is t_j's position on the support, and atom i receives
 //   m_i = sum_j p_j max(0, 1 - |b_j - i|),  j = 0 ... K - 1 in this order, in fp64, rounded to float32 once.
@@ -107,7 +136,8 @@ __device__ __forceinline__ void c51_project_row(const C51Dev &D, const float *p,
 
 // ---- forward / backward -------------------------------------------------------------------------------------------------------------------------
 // dbg4 (may be null) float32 [B][4]: a*, the target net's expected value there, l, Q(s, a); dist (may be null) float32 [B][2][K]: m and softmax p(s, a)
-template <bool NS>
+// (DUEL: the dueling head, a template argument as NS is -- the plain head's kernel then holds the code it held without the dueling head, at its registers)
+template <bool NS, bool DUEL>
 __device__ __forceinline__ void c51_fwd_pass(const C51Dev &D, int B, int gate, float *__restrict__ dbg4, float *__restrict__ dist, unsigned char *dg_smem) {
     const DdpgDev &L = D.dq.base;
     if (!ddpg_gate(L, gate)) return;
@@ -135,10 +165,12 @@ __device__ __forceinline__ void c51_fwd_pass(const C51Dev &D, int B, int gate, f
     float qsel;
     if (D.dq.dbl) {                                                 // a* from the online net's expected values on s'
         dqn_q(D.dq, T, T.Xn, false);
+        if (DUEL) c51_dueling_combine(D, h2);
         astar = c51_greedy(D, h2, qsel, nullptr);
         __syncthreads();
     }
     dqn_q(D.dq, T, T.Xn, true);
+    if (DUEL) c51_dueling_combine(D, h2);
     if (!D.dq.dbl) astar = c51_greedy(D, h2, qsel, nullptr);
     {   // p' = softmax of the target net's block a*, in place over its logits (each lane its own columns), and its mean
         float *blk = h2 + (size_t)astar * K;
@@ -157,6 +189,8 @@ __device__ __forceinline__ void c51_fwd_pass(const C51Dev &D, int B, int gate, f
     __syncthreads();
     // logits of the online net on s; log-softmax of the stored action's block
     dqn_q(D.dq, T, T.X, false);
+    constexpr bool duel = DUEL;
+    if (duel) c51_dueling_combine(D, h2);
     const float *blk = h2 + (size_t)act * K;
     double mx, se;
     c51_block_stats(blk, K, mx, se);
@@ -164,15 +198,28 @@ __device__ __forceinline__ void c51_fwd_pass(const C51Dev &D, int B, int gate, f
     const double wB = valid ? (L.aw ? (double)L.aw[r0 + row] : 1.0) / (double)B : 0.0;
     double sl = 0.0, sq = 0.0;
     float *dout = L.aD2 + (size_t)(r0 + row) * Ap;
-    for (int j = part; j < Ap; j += 32) if (j < act * K || j >= (act + 1) * K) dout[j] = 0.f;
+    const int A = D.dq.A;
+    if (duel) { for (int j = (A + 1) * K + part; j < Ap; j += 32) dout[j] = 0.f; }                  // (the pad columns; the rest is dense, below)
+    else for (int j = part; j < Ap; j += 32) if (j < act * K || j >= (act + 1) * K) dout[j] = 0.f;
     for (int k = part; k < K; k += 32) {
         const double xs = (double)blk[k] - mx, pk = exp(xs) / se, mk = (double)mrow[k];
         sl += mk * (xs - lse);
         sq += (D.v_min + (double)k * D.dz) * pk;
         const float dzk = valid ? (float)(wB * (pk - mk)) : 0.f;
         if (dist && valid) { float *o = dist + (size_t)(r0 + row) * 2 * K; o[k] = mrow[k]; o[K + k] = (float)pk; }
-        dout[act * K + k] = dzk;
-        mrow[k] = dzk;                                              // (this lane's own atom: m is read no more)
+        if (duel) {                                                 // dense: over this lane's own column of every block of h2, whose logits are read no more
+            const double g = valid ? wB * (pk - mk) : 0.0, invA = 1.0 / (double)A;
+            for (int b = 0; b < A; ++b) {
+                const float db = valid ? (float)(g * ((b == act ? 1.0 : 0.0) - invA)) : 0.f;
+                dout[b * K + k] = db;
+                h2[b * K + k] = db;
+            }
+            dout[A * K + k] = dzk;
+            h2[A * K + k] = dzk;
+        } else {
+            dout[act * K + k] = dzk;
+            mrow[k] = dzk;                                          // (this lane's own atom: m is read no more)
+        }
     }
     const float loss = (float)(-c51_row_sum(sl)), qv = (float)c51_row_sum(sq);
     if (part == 0) {
@@ -185,7 +232,18 @@ __device__ __forceinline__ void c51_fwd_pass(const C51Dev &D, int B, int gate, f
     ddpg_store_tile(T.X, AT_KIN, L.aX + (size_t)r0 * AT_KIN, AT_KIN);
     ddpg_store_tile(T.H1, T.h1_ld, L.aH1 + (size_t)r0 * L.h1p, L.h1p);
     __syncthreads();
-    // dZ1[row][k] = sum_i dZout[a K + i] W1[a K + i][k] where H1 > 0: the K rows of the action's block, in i order, in fp64 (the products are exact there)
+    // dZ1[row][k] = sum_i dZout[a K + i] W1[a K + i][k] where H1 > 0: the K rows of the action's block, in i order, in fp64 (the products are exact there);
+    // the dueling head's dZout is dense: all (A + 1) K rows, in row order, read from the row's own h2
+    if (duel) {
+        const float *w1 = L.q.w + dg_o_w1(L.h1p);
+        const int nr = (A + 1) * K;
+        for (int k = part; k < L.h1p; k += 32) {
+            double s = 0.0;
+            for (int i = 0; i < nr; ++i) s += (double)h2[i] * (double)w1[(size_t)i * L.h1p + k];
+            L.aD1[(size_t)(r0 + row) * L.h1p + k] = T.H1[(size_t)row * T.h1_ld + k] > 0.f ? (float)s : 0.f;
+        }
+        return;
+    }
     const float *w1a = L.q.w + dg_o_w1(L.h1p) + (size_t)act * K * L.h1p;
     for (int k = part; k < L.h1p; k += 32) {
         double s = 0.0;
@@ -193,13 +251,19 @@ __device__ __forceinline__ void c51_fwd_pass(const C51Dev &D, int B, int gate, f
         L.aD1[(size_t)(r0 + row) * L.h1p + k] = T.H1[(size_t)row * T.h1_ld + k] > 0.f ? (float)s : 0.f;
     }
 }
+template <bool DUEL>
 __device__ __forceinline__ void c51_fwd_body(const C51Dev &D, int B, int gate, float *__restrict__ dbg4, float *__restrict__ dist, unsigned char *dg_smem) {
-    if (D.dq.base.n_step > 1) c51_fwd_pass<true>(D, B, gate, dbg4, dist, dg_smem);
-    else c51_fwd_pass<false>(D, B, gate, dbg4, dist, dg_smem);
+    if (D.dq.base.n_step > 1) c51_fwd_pass<true, DUEL>(D, B, gate, dbg4, dist, dg_smem);
+    else c51_fwd_pass<false, DUEL>(D, B, gate, dbg4, dist, dg_smem);
 }
 __global__ void __launch_bounds__(AT_THREADS) k_c51_fwd(C51Dev D, int B, int gate, float *__restrict__ dbg4, float *__restrict__ dist) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
-    c51_fwd_body(D, B, gate, dbg4, dist, dg_smem);
+    c51_fwd_body<false>(D, B, gate, dbg4, dist, dg_smem);
+}
+// the dueling head's: the host launches it for a learner whose D.dueling is set (one head per learner and per population: the choice is uniform)
+__global__ void __launch_bounds__(AT_THREADS) k_c51_fwd_duel(C51Dev D, int B, int gate, float *__restrict__ dbg4, float *__restrict__ dist) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    c51_fwd_body<true>(D, B, gate, dbg4, dist, dg_smem);
 }
 
 __global__ void __launch_bounds__(64 * DG_WG_WAVES) k_c51_wgrad(C51Dev D, int Bp, int gate) {
@@ -209,10 +273,11 @@ __global__ void __launch_bounds__(64 * DG_WG_WAVES) k_c51_wgrad(C51Dev D, int Bp
 
 __global__ void __launch_bounds__(256) k_c51_adam(C51Dev D, float lr, int mode, int gate) { dqn_adam_body(D.dq, lr, mode, gate); }
 
-// padded parameter layout -> W0 [h1][n_obs] | b0 [h1] | W1 [A K][h1] | b1 [A K], row-major, unpadded (k_dqn_unpad with A K output rows)
+// padded parameter layout -> W0 [h1][n_obs] | b0 [h1] | W1 [W][h1] | b1 [W], row-major, unpadded (k_dqn_unpad with W = dq.base.h2 output rows: A K,
+// or (A + 1) K of a dueling head)
 __global__ void k_c51_unpad(C51Dev D, const float *__restrict__ src, float *__restrict__ dst) {
     const DdpgDev &L = D.dq.base;
-    const int AK = D.dq.A * D.K;
+    const int AK = L.h2;
     const int n0 = L.h1 * L.n_obs, n1 = n0 + L.h1, n2 = n1 + AK * L.h1, total = n2 + AK;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         int s;
@@ -249,6 +314,7 @@ __device__ __forceinline__ void c51_act_body(const C51Dev &D, int N, const float
     T.X[row * AT_KIN + part] = e < N && part < L.n_obs ? obs[(size_t)e * obs_stride + part] : 0.f;
     __syncthreads();
     dqn_q(D.dq, T, T.X, false);
+    if (D.dueling) c51_dueling_combine(D, T.H2 + (size_t)row * T.h2_ld);
     float qbest;
     int a = c51_greedy(D, T.H2 + (size_t)row * T.h2_ld, qbest, dbg_q && e < N ? dbg_q + (size_t)e * D.dq.A : nullptr);
     if (e < N && part == 0) {

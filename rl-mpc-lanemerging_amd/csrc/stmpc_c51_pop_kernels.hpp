@@ -47,7 +47,13 @@ __global__ void __launch_bounds__(AT_THREADS) k_c51_act_pop(const C51Dev *__rest
 __global__ void __launch_bounds__(AT_THREADS) k_c51_fwd_pop(const C51Dev *__restrict__ members, int B, int gate) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
     const C51Dev D = members[blockIdx.y];
-    c51_fwd_body(D, B, gate, nullptr, nullptr, dg_smem);
+    c51_fwd_body<false>(D, B, gate, nullptr, nullptr, dg_smem);
+}
+// (a population of dueling members: they share the head)
+__global__ void __launch_bounds__(AT_THREADS) k_c51_fwd_duel_pop(const C51Dev *__restrict__ members, int B, int gate) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dg_smem[];
+    const C51Dev D = members[blockIdx.y];
+    c51_fwd_body<true>(D, B, gate, nullptr, nullptr, dg_smem);
 }
 
 __global__ void __launch_bounds__(64 * DG_WG_WAVES) k_c51_wgrad_pop(const C51Dev *__restrict__ members, int Bp, int gate) {

@@ -11,7 +11,7 @@
 // gfx950 mapping: k_c51_act's -- one workgroup of AT_THREADS per AT_TM = 16 states, 32 lanes per row, X 16 x 32, the hidden activations and the
 // A K logits in LDS (DdpgTile: ddpg_tile_bytes(h1p, Ap), no m tile), both layers v_mfma_f32_16x16x4_f32 loops.
 //
-// The kernel takes the C51Dev by value and reads dq.base.q, the shape (dq.base.n_obs, h1p, dq.A, dq.Ap), K, v_min and dz, and nothing else: no
+// The kernel takes the C51Dev by value and reads dq.base.q, the shape (dq.base.n_obs, h1p, dq.A, dq.Ap), K, dueling, v_min and dz, and nothing else: no
 // counter, no ticket, no workspace.  An evaluation in the middle of a training leaves the run's bits alone.
 #pragma once
 #include "stmpc_c51_kernels.hpp"
@@ -33,6 +33,7 @@ __global__ void __launch_bounds__(AT_THREADS) k_c51actor_eval(FeatCfg f, C51Dev 
     __syncthreads();
     if (o.feat && e < N && part < L.n_obs) o.feat[(size_t)e * o.feat_stride + part] = T.X[row * AT_KIN + part];
     dqn_q(D.dq, T, T.X, target != 0);
+    if (D.dueling) c51_dueling_combine(D, T.H2 + (size_t)row * T.h2_ld);    // (a dueling head: the advantage blocks become the actions' logits)
     float best;
     const int a = c51_greedy(D, T.H2 + (size_t)row * T.h2_ld, best, o.q && e < N ? o.q + (size_t)e * D.dq.A : nullptr);      // (every lane runs its shuffles)
     if (e >= N || part != 0) return;

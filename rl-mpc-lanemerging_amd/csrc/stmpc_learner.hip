@@ -1117,7 +1117,7 @@ int stmpc_actor_pop_eval_device(stmpc_ctx *c, const stmpc_actor_pop *p, const st
 // for both heads; kernels in stmpc_dqn_kernels.hpp and stmpc_c51_kernels.hpp ----------------------------------------------------------------------
 // What the DQN learner and the categorical one differ in is their Head (DqnHead, C51Head below): the cfg and device structs, the network's output
 // width, the LDS size, the head's own cfg checks and device fields, and the kernels.  A C51 learner is not a DQN learner: its device struct is a
-// C51Dev and its network's output width is n_actions * n_atoms.
+// C51Dev and its network's output width is n_actions * n_atoms, or (n_actions + 1) * n_atoms with a dueling head (cfg.dueling).
 template <class H> struct QLearner {
     using Head = H;
     typename H::Cfg cfg{};
@@ -1165,7 +1165,7 @@ struct DqnHead {
         hipLaunchKernelGGL(k_dqn_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t.lds, st, t.dev, N, d_obs, obs_stride, (float)eps, eps > 0 ? 1 : 0, d_action, d_debug_q);
     }
     // ... and of a population of P, on its table of device structs
-    static void fwd_pop(const Dev *tab, const Grid &g, int P, size_t lds, int B, hipStream_t st) { hipLaunchKernelGGL(k_dqn_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), lds, st, tab, B, 1); }
+    static void fwd_pop(const L &, const Dev *tab, const Grid &g, int P, size_t lds, int B, hipStream_t st) { hipLaunchKernelGGL(k_dqn_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), lds, st, tab, B, 1); }
     static void wgrad_pop(const Dev *tab, const Grid &g, int P, int Bp, hipStream_t st) { hipLaunchKernelGGL(k_dqn_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, tab, Bp, 1); }
     static void adam_pop(const Dev *tab, const Grid &g, int P, const DdpgLr &lrs, hipStream_t st) { hipLaunchKernelGGL(k_dqn_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, tab, lrs, 1); }
     static void act_pop(const Dev *tab, int P, size_t lds, int n, const float *d_obs, int obs_stride, const DqnEps &e, int32_t *d_action, float *d_debug_q, hipStream_t st) {
@@ -1178,38 +1178,51 @@ struct DqnHead {
     }
 };
 
+// the widest layer: n_actions * n_atoms logits, (n_actions + 1) * n_atoms with a dueling head's value block (stmpc_c51_create and the actors' creates)
+static int c51_check_width(int n_actions, int n_atoms, int dueling) {
+    const long long W = (long long)(n_actions + (dueling ? 1 : 0)) * n_atoms;
+    if (W <= STMPC_C51_MAX_LOGITS) return STMPC_OK;
+    if (dueling) return fail(STMPC_EINVAL, "(n_actions + 1) * n_atoms = " + std::to_string(W) + " (a dueling head) exceeds " + std::to_string(STMPC_C51_MAX_LOGITS));
+    return fail(STMPC_EINVAL, "n_actions * n_atoms = " + std::to_string(W) + " exceeds " + std::to_string(STMPC_C51_MAX_LOGITS));
+}
+
 struct C51Head {
     using Cfg = stmpc_c51_cfg;
     using Dev = C51Dev;
     using L = QLearner<C51Head>;
-    static constexpr const char *name = "C51", *shared = "n_obs, h1, n_actions, n_atoms, batch and capacity";
+    static constexpr const char *name = "C51", *shared = "n_obs, h1, n_actions, n_atoms, batch and capacity";      // (and the head: dueling or not)
     static constexpr const char *pop_per_enable = "stmpc_pop_c51_per_enable", *pop_nstep_enable = "stmpc_pop_c51_multi_step_enable";
     static DdpgDev &base(Dev &d) { return d.dq.base; }
     static DqnDev &dq(Dev &d) { return d.dq; }
-    static int n_out(const Cfg &g) { return g.n_actions * g.n_atoms; }
+    static int n_out(const Cfg &g) { return (g.n_actions + (g.dueling ? 1 : 0)) * g.n_atoms; }       // (a dueling head: the value block behind the advantage blocks)
     static size_t tile_bytes(const Cfg &g, int h1p, int Ap) { return c51_tile_bytes(h1p, Ap, g.n_atoms); }
     static int check(const Cfg &g) {
         if (g.n_atoms < 2) return fail(STMPC_EINVAL, "n_atoms must be at least 2");
-        if ((long long)g.n_actions * g.n_atoms > STMPC_C51_MAX_LOGITS)
-            return fail(STMPC_EINVAL, "n_actions * n_atoms = " + std::to_string((long long)g.n_actions * g.n_atoms) + " exceeds " + std::to_string(STMPC_C51_MAX_LOGITS));
+        if (g.dueling != 0 && g.dueling != 1) return fail(STMPC_EINVAL, "dueling must be 0 or 1, not " + std::to_string(g.dueling));
+        TRY(c51_check_width(g.n_actions, g.n_atoms, g.dueling));
         if (!std::isfinite(g.v_min) || !std::isfinite(g.v_max) || !(g.v_max > g.v_min)) return fail(STMPC_EINVAL, "the support needs finite v_min < v_max");
         return STMPC_OK;
     }
     static bool constants_ok(const Cfg &) { return true; }          // (clip_targets is not read: the support's clamp is the clip)
     static bool same_shape(const Cfg &a, const Cfg &b) {
-        return a.n_obs == b.n_obs && a.h1 == b.h1 && a.n_actions == b.n_actions && a.n_atoms == b.n_atoms && a.batch == b.batch && a.capacity == b.capacity;
+        return a.n_obs == b.n_obs && a.h1 == b.h1 && a.n_actions == b.n_actions && a.n_atoms == b.n_atoms && a.dueling == b.dueling && a.batch == b.batch &&
+               a.capacity == b.capacity;
     }
-    static void wire(Dev &d, const Cfg &g) { d.dq.clip = 0; d.K = g.n_atoms; d.v_min = g.v_min; d.v_max = g.v_max; d.dz = (g.v_max - g.v_min) / (double)(g.n_atoms - 1); }
+    static void wire(Dev &d, const Cfg &g) { d.dq.clip = 0; d.K = g.n_atoms; d.dueling = g.dueling; d.v_min = g.v_min; d.v_max = g.v_max; d.dz = (g.v_max - g.v_min) / (double)(g.n_atoms - 1); }
     static int raise_lds(bool pop, int device, size_t lds) {
-        static LdsCeiling ceiling[2][2];
-        static const void *const fn[2][2] = {{(const void *)k_c51_fwd, (const void *)k_c51_act}, {(const void *)k_c51_fwd_pop, (const void *)k_c51_act_pop}};
-        static const char *const kernel[2][2] = {{"k_c51_fwd", "k_c51_act"}, {"k_c51_fwd_pop", "k_c51_act_pop"}};
-        TRY(raise_dynamic_lds(fn[pop][0], kernel[pop][0], ceiling[pop][0], device, lds));
-        return raise_dynamic_lds(fn[pop][1], kernel[pop][1], ceiling[pop][1], device, lds);
+        static LdsCeiling ceiling[2][3];
+        static const void *const fn[2][3] = {{(const void *)k_c51_fwd, (const void *)k_c51_act, (const void *)k_c51_fwd_duel},
+                                             {(const void *)k_c51_fwd_pop, (const void *)k_c51_act_pop, (const void *)k_c51_fwd_duel_pop}};
+        static const char *const kernel[2][3] = {{"k_c51_fwd", "k_c51_act", "k_c51_fwd_duel"}, {"k_c51_fwd_pop", "k_c51_act_pop", "k_c51_fwd_duel_pop"}};
+        for (int k = 0; k < 3; ++k) TRY(raise_dynamic_lds(fn[pop][k], kernel[pop][k], ceiling[pop][k], device, lds));      // (both heads' passes: the LDS size is one)
+        return STMPC_OK;
     }
-    static void fwd(const L &t, int gate, hipStream_t st) {
-        hipLaunchKernelGGL(k_c51_fwd, dim3(t.grid.tiles), dim3(AT_THREADS), t.lds, st, t.dev, t.cfg.batch, gate, (float *)nullptr, (float *)nullptr);
+    // the forward / backward pass has a kernel per head (d_out, d_dist: the debug outputs of stmpc_c51_dist_device, null in an update)
+    static void fwd_launch(const L &t, int gate, float *d_out, float *d_dist, hipStream_t st) {
+        if (t.dev.dueling) hipLaunchKernelGGL(k_c51_fwd_duel, dim3(t.grid.tiles), dim3(AT_THREADS), t.lds, st, t.dev, t.cfg.batch, gate, d_out, d_dist);
+        else hipLaunchKernelGGL(k_c51_fwd, dim3(t.grid.tiles), dim3(AT_THREADS), t.lds, st, t.dev, t.cfg.batch, gate, d_out, d_dist);
     }
+    static void fwd(const L &t, int gate, hipStream_t st) { fwd_launch(t, gate, nullptr, nullptr, st); }
     static void wgrad(const L &t, int gate, hipStream_t st) { hipLaunchKernelGGL(k_c51_wgrad, dim3(t.grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t.dev, t.rp.Bp, gate); }
     static void adam(const L &t, float lr, int mode, hipStream_t st) { hipLaunchKernelGGL(k_c51_adam, dim3(t.grid.ablocks), dim3(256), 0, st, t.dev, lr, mode, 1); }
     static void unpad(const L &t, float *d_grad, hipStream_t st) { hipLaunchKernelGGL(k_c51_unpad, dim3(128), dim3(256), 0, st, t.dev, (const float *)t.dev.dq.base.q.g, d_grad); }
@@ -1217,7 +1230,10 @@ struct C51Head {
     static void act(const L &t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, hipStream_t st) {
         hipLaunchKernelGGL(k_c51_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t.lds, st, t.dev, N, d_obs, obs_stride, (float)eps, eps > 0 ? 1 : 0, d_action, d_debug_q);
     }
-    static void fwd_pop(const Dev *tab, const Grid &g, int P, size_t lds, int B, hipStream_t st) { hipLaunchKernelGGL(k_c51_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), lds, st, tab, B, 1); }
+    static void fwd_pop(const L &t0, const Dev *tab, const Grid &g, int P, size_t lds, int B, hipStream_t st) {      // (t0: member 0; the members share the head)
+        if (t0.dev.dueling) hipLaunchKernelGGL(k_c51_fwd_duel_pop, dim3(g.tiles, P), dim3(AT_THREADS), lds, st, tab, B, 1);
+        else hipLaunchKernelGGL(k_c51_fwd_pop, dim3(g.tiles, P), dim3(AT_THREADS), lds, st, tab, B, 1);
+    }
     static void wgrad_pop(const Dev *tab, const Grid &g, int P, int Bp, hipStream_t st) { hipLaunchKernelGGL(k_c51_wgrad_pop, dim3(g.jobs, P), dim3(64 * DG_WG_WAVES), 0, st, tab, Bp, 1); }
     static void adam_pop(const Dev *tab, const Grid &g, int P, const DdpgLr &lrs, hipStream_t st) { hipLaunchKernelGGL(k_c51_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, tab, lrs, 1); }
     static void act_pop(const Dev *tab, int P, size_t lds, int n, const float *d_obs, int obs_stride, const DqnEps &e, int32_t *d_action, float *d_debug_q, hipStream_t st) {
@@ -1483,7 +1499,7 @@ int stmpc_c51_dist_device(stmpc_c51 *t, float *d_dist, float *d_out, void *strea
     if (!t || (!d_dist && !d_out)) return fail(STMPC_EINVAL, "NULL argument");
     HIPCHK(hipSetDevice(t->rp.device));
     per_launch_sample(t->rp, t->base(), 0, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_c51_fwd, dim3(t->grid.tiles), dim3(AT_THREADS), t->lds, (hipStream_t)stream, t->dev, t->cfg.batch, 0, d_out, d_dist);
+    C51Head::fwd_launch(*t, 0, d_out, d_dist, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }
@@ -1620,7 +1636,7 @@ template <class Pop> int q_pop_update(Pop *p, int n_updates, const double *lr, i
     hipStream_t st = (hipStream_t)stream;
     for (int u = 0; u < n_updates; ++u) {                            // q_update's three launches (five with prioritised members), each over the members
         if (c.per_any) hipLaunchKernelGGL(k_per_sample_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, Bp, 1);
-        H::fwd_pop(p->dev(), g, P, c.lds, B, st);
+        H::fwd_pop(*t, p->dev(), g, P, c.lds, B, st);
         H::wgrad_pop(p->dev(), g, P, Bp, st);
         if (c.per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, 1);
         H::adam_pop(p->dev(), g, P, lrs, st);
@@ -1694,7 +1710,9 @@ struct stmpc_qactor {
     int device = 0;
     const stmpc_dqn *learner = nullptr;     // a view (stmpc_qactor_view_dqn): the network is the learner's, read through its struct at every evaluation
     const stmpc_c51 *c51 = nullptr;         // a view of a categorical learner (stmpc_c51actor_view): likewise, through its C51Dev
-    bool categorical = false;               // a categorical head (stmpc_c51actor_create / _view): k_c51actor_eval evaluates it; `dev`'s output width is A * K
+    bool categorical = false;             // a categorical head (stmpc_c51actor_create / _view): k_c51actor_eval evaluates it; `dev`'s output width is A * K,
+                                            // (A + 1) * K of a created dueling one (stmpc_dueling_c51actor_create)
+    int dueling = 0;
     int K = 0;                              // a created categorical actor's head: atoms and support (a view reads its learner's)
     double v_min = 0, v_max = 0, dz = 0;
     int target = 0, mode = 0, n_in = 0, A = 0;
@@ -1719,7 +1737,7 @@ int c51actor_raise_lds(int device, size_t lds) {
 C51Dev c51actor_dev(const stmpc_qactor *q) {
     if (q->c51) return q->c51->dev;
     C51Dev D{};
-    D.dq = q->dev; D.K = q->K; D.v_min = q->v_min; D.v_max = q->v_max; D.dz = q->dz;
+    D.dq = q->dev; D.K = q->K; D.dueling = q->dueling; D.v_min = q->v_min; D.v_max = q->v_max; D.dz = q->dz;
     return D;
 }
 // what create and view share: the mode, the table (checked, then uploaded into q), the kernel's dynamic LDS
@@ -1789,25 +1807,28 @@ int stmpc_qactor_view_dqn(stmpc_dqn *t, int target, const double *action_values,
     return qactor_finish(q, action_values, out);
 }
 
-int stmpc_c51actor_create(stmpc_ctx *c, int n_in, int h1, int n_actions, int n_atoms, double v_min, double v_max, const float *w0, const float *b0,
-                          const float *w1, const float *b1, const double *action_values, int mode, stmpc_qactor **out) {
+}  // extern "C"
+
+namespace {
+// stmpc_c51actor_create and stmpc_dueling_c51actor_create: w1 and b1 have (n_actions + dueling) * n_atoms rows
+int c51actor_create(stmpc_ctx *c, int n_in, int h1, int n_actions, int n_atoms, int dueling, double v_min, double v_max, const float *w0, const float *b0,
+                    const float *w1, const float *b1, const double *action_values, int mode, stmpc_qactor **out) {
     if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
     *out = nullptr;
     if (!w0 || !b0 || !w1 || !b1 || !action_values) return fail(STMPC_EINVAL, "NULL weight or table pointer");
     if (n_actions < 1 || n_actions > STMPC_ENV_MAX_ACTIONS) return fail(STMPC_EINVAL, "n_actions must be in 1 ... " + std::to_string(STMPC_ENV_MAX_ACTIONS));
     if (n_in < 1 || n_in > AT_KIN - 1 || h1 < 1 || h1 > 1024) return fail(STMPC_EINVAL, "C51 network shape out of range (n_in <= 31, hidden width <= 1024)");
     if (n_atoms < 2) return fail(STMPC_EINVAL, "n_atoms must be at least 2");
-    if ((long long)n_actions * n_atoms > STMPC_C51_MAX_LOGITS)
-        return fail(STMPC_EINVAL, "n_actions * n_atoms = " + std::to_string((long long)n_actions * n_atoms) + " exceeds " + std::to_string(STMPC_C51_MAX_LOGITS));
+    TRY(c51_check_width(n_actions, n_atoms, dueling));
     if (!std::isfinite(v_min) || !std::isfinite(v_max) || !(v_max > v_min)) return fail(STMPC_EINVAL, "the support needs finite v_min < v_max");
     TRY(qactor_check_table(action_values, n_actions, n_actions, mode));
     HIPCHK(hipSetDevice(c->device));
-    const int AK = n_actions * n_atoms, h1p = (h1 + 15) & ~15, Ap = (AK + 15) & ~15;
+    const int AK = (n_actions + dueling) * n_atoms, h1p = (h1 + 15) & ~15, Ap = (AK + 15) & ~15;
     const size_t lds = ddpg_tile_bytes(h1p, Ap);
     if (lds + 1024 > (size_t)c->lds_per_block) return fail(STMPC_EINVAL, "C51 network too wide for one workgroup's LDS");
     stmpc_qactor *q = new stmpc_qactor();
     q->device = c->device; q->mode = mode; q->n_in = n_in; q->A = n_actions; q->lds = lds; q->categorical = true;
-    q->K = n_atoms; q->v_min = v_min; q->v_max = v_max; q->dz = (v_max - v_min) / (double)(n_atoms - 1);
+    q->dueling = dueling; q->K = n_atoms; q->v_min = v_min; q->v_max = v_max; q->dz = (v_max - v_min) / (double)(n_atoms - 1);
     // the C51 learner's own path: net_build's buffers, the slot's segments into the padded layout with A K output rows, k_c51_adam's re-packing
     DdpgDev &d = q->dev.base;
     d.n_obs = n_in; d.h1 = h1; d.h2 = AK; d.h1p = h1p; d.h2p = Ap;
@@ -1829,6 +1850,19 @@ int stmpc_c51actor_create(stmpc_ctx *c, int n_in, int h1, int n_actions, int n_a
     }
     if (rc) { stmpc_qactor_destroy(q); return rc; }
     return qactor_finish(q, action_values, out);
+}
+}  // namespace
+
+extern "C" {
+
+int stmpc_c51actor_create(stmpc_ctx *c, int n_in, int h1, int n_actions, int n_atoms, double v_min, double v_max, const float *w0, const float *b0,
+                          const float *w1, const float *b1, const double *action_values, int mode, stmpc_qactor **out) {
+    return c51actor_create(c, n_in, h1, n_actions, n_atoms, 0, v_min, v_max, w0, b0, w1, b1, action_values, mode, out);
+}
+
+int stmpc_dueling_c51actor_create(stmpc_ctx *c, int n_in, int h1, int n_actions, int n_atoms, double v_min, double v_max, const float *w0, const float *b0,
+                                  const float *w1, const float *b1, const double *action_values, int mode, stmpc_qactor **out) {
+    return c51actor_create(c, n_in, h1, n_actions, n_atoms, 1, v_min, v_max, w0, b0, w1, b1, action_values, mode, out);
 }
 
 int stmpc_c51actor_view(stmpc_c51 *t, int target, const double *action_values, int n_actions, int mode, stmpc_qactor **out) {

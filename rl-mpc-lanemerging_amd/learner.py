@@ -51,6 +51,11 @@ Algorithm 1) -- three launches per update, five with ``per``; ``n_step`` as the 
 ``c51_project_scatter_host``, ``c51_targets_host``, ``update_host_c51``; ``train_dqn`` takes it as it takes a ``DQNLearner``.  ``C51Population``
 (``csrc/stmpc_c51_pop_kernels.hpp``, ``stmpc_pop_c51_*``) is to it what ``DQNPopulation`` is to ``DQNLearner``: P independent C51 learners -- the
 support, ``double``, ``target_period``, ``gamma``, ``n_step``, the seed and ``per=`` per member -- for the launch count of one.
+``C51Config(dueling=True)`` gives the learner, its population and ``actor.C51Actor`` the dueling head (Wang et al. 2016, in the categorical form of
+Hessel et al. 2018): (A + 1) * n_atoms outputs, the value block last, logits V + Adv - mean Adv formed on the device behind every forward pass, a
+dense backward, the same launch count.  It restates the published head; parity with the ``all`` library's own is not pinned.  Twins:
+``_c51_logits(dueling=True)``, ``c51_dueling_combine_host`` (the device's operation order), ``c51_fold_dueling_host`` (the plain network with the same
+logits).  Noisy layers, the sixth piece of the rainbow preset, are not built.
 """
 import math
 
@@ -1408,11 +1413,16 @@ class DQNPopulation(DDPGPopulation):
 class C51Config(DQNConfig):
     """``DQNConfig`` plus the categorical head's support: ``n_atoms`` atoms z_k = v_min + k (v_max - v_min) / (n_atoms - 1).  The defaults 51, -10, 10 are
     the C51 paper's (Bellemare et al. 2017); the ``all`` rainbow preset's own values could not be read (the library is absent from the reference
-    checkout).  ``clip_targets`` / ``clip_min`` / ``clip_max`` are not read: the support's clamp is the clip."""
+    checkout).  ``clip_targets`` / ``clip_min`` / ``clip_max`` are not read: the support's clamp is the clip.
 
-    def __init__(self, *args, n_atoms=51, v_min=-10.0, v_max=10.0, **kw):
+    ``dueling``: the dueling head (Wang et al. 2016, in the categorical form of Hessel et al. 2018, section "Dueling networks").  The network is then
+    n_obs -> h1 -> ReLU -> (A + 1) * n_atoms -- the A advantage blocks first, rows a * n_atoms ... of w1 and b1, the value block last -- and the
+    logits of action a are l[a][k] = V[k] + Adv[a][k] - mean_b Adv[b][k].  It restates the published head; parity with the ``all`` library's own
+    stays unpinned, for the same reason.  The widest layer holds 1024 outputs: ``sumo-accel-v0`` (20 actions) takes at most 48 atoms with it."""
+
+    def __init__(self, *args, n_atoms=51, v_min=-10.0, v_max=10.0, dueling=False, **kw):
         super().__init__(*args, **kw)
-        self.n_atoms, self.v_min, self.v_max = int(n_atoms), float(v_min), float(v_max)
+        self.n_atoms, self.v_min, self.v_max, self.dueling = int(n_atoms), float(v_min), float(v_max), bool(dueling)
         if self.n_atoms < 2:
             raise ValueError("C51 needs n_atoms >= 2, not %d" % self.n_atoms)
         if not (math.isfinite(self.v_min) and math.isfinite(self.v_max) and self.v_max > self.v_min):
@@ -1420,12 +1430,18 @@ class C51Config(DQNConfig):
         self.check_width()
 
     def check_width(self):
-        if self.n_actions is not None and self.n_actions * self.n_atoms > _capi.C51_MAX_LOGITS:
-            raise ValueError("n_actions * n_atoms = %d * %d exceeds the widest layer, %d" % (self.n_actions, self.n_atoms, _capi.C51_MAX_LOGITS))
+        if self.n_actions is not None and (self.n_actions + self.dueling) * self.n_atoms > _capi.C51_MAX_LOGITS:
+            raise ValueError("%s * n_atoms = %d * %d exceeds the widest layer, %d"
+                             % ("(n_actions + 1)" if self.dueling else "n_actions", self.n_actions + self.dueling, self.n_atoms, _capi.C51_MAX_LOGITS))
+
+    @property
+    def n_blocks(self):
+        """The output layer's blocks of n_atoms rows: n_actions, and the value block of a dueling head."""
+        return self.n_actions + int(self.dueling)
 
     def to_c(self, seed):
         base = super().to_c(seed)
-        return _capi.C51Cfg(v_min=self.v_min, v_max=self.v_max, n_atoms=self.n_atoms, reserved=0, **{n: getattr(base, n) for n, _ in _capi.DQNCfg._fields_})
+        return _capi.C51Cfg(v_min=self.v_min, v_max=self.v_max, n_atoms=self.n_atoms, dueling=int(self.dueling), **{n: getattr(base, n) for n, _ in _capi.DQNCfg._fields_})
 
 
 def c51_support(cfg, dtype=np.float64):
@@ -1474,13 +1490,41 @@ def c51_project_scatter_host(p, r, mask, disc, cfg):
     return m
 
 
-def init_c51_net(n_obs, h1, A, n_atoms, rng):
-    """``init_q_net`` with A * n_atoms outputs: action a's logits are rows a * n_atoms ... (a + 1) * n_atoms - 1 of w1 and b1."""
-    return init_q_net(n_obs, h1, A * n_atoms, rng)
+def init_c51_net(n_obs, h1, A, n_atoms, rng, dueling=False):
+    """``init_q_net`` with A * n_atoms outputs: action a's logits are rows a * n_atoms ... (a + 1) * n_atoms - 1 of w1 and b1.  ``dueling``:
+    (A + 1) * n_atoms outputs, the A advantage blocks in those rows and the value block behind them."""
+    return init_q_net(n_obs, h1, (A + bool(dueling)) * n_atoms, rng)
 
 
-def _c51_logits(t, x, A, K):
-    return _q_mlp(t, x).reshape(x.shape[0], A, K)
+def _c51_logits(t, x, A, K, dueling=False):
+    """Logits [n][A][K] of a net of torch tensors.  ``dueling``: l[a][k] = V[k] + Adv[a][k] - mean_b Adv[b][k] of the (A + 1) * K outputs, the
+    mathematical statement in the tensors' dtype (float64: the yardstick; the device's own operation order is ``c51_dueling_combine_host``)."""
+    if not dueling:
+        return _q_mlp(t, x).reshape(x.shape[0], A, K)
+    out = _q_mlp(t, x).reshape(x.shape[0], A + 1, K)
+    adv, val = out[:, :A], out[:, A:]
+    return val + adv - adv.mean(1, keepdim=True)
+
+
+def c51_dueling_combine_host(out, A, K):
+    """``c51_dueling_combine`` of csrc/stmpc_c51_kernels.hpp in numpy, operation for operation: float32 outputs ``out`` [n][(A + 1) * K] (the output
+    layer's: advantage blocks, then the value block) -> float32 logits [n][A][K].  The inputs go to float64, the sum over b runs in b order, the
+    division by A and the two additions are float64, (V + Adv) first, and the result is rounded to float32 once."""
+    o = np.asarray(out, dtype=np.float32).astype(np.float64).reshape(-1, A + 1, K)
+    s = np.zeros((o.shape[0], K), dtype=np.float64)
+    for b in range(A):
+        s = s + o[:, b]
+    return ((o[:, A:A + 1] + o[:, :A]) - (s / np.float64(A))[:, None, :]).astype(np.float32)
+
+
+def c51_fold_dueling_host(net, A, K):
+    """The PLAIN C51 network {w0, b0, w1 [A * K][h1], b1 [A * K]} (float64) with the logits of the dueling network ``net`` {w0, b0, w1 [(A + 1) * K][h1],
+    b1}: W'[a K + k] = W_V[k] + W_A[a][k] - mean_b W_A[b][k], the biases likewise -- the combine is linear in the output layer.  For users who want a
+    plain ``.npz`` (``C51Actor`` takes it without the ``dueling`` key), and an independent check of the head."""
+    w1, b1 = np.asarray(net["w1"], dtype=np.float64).reshape(A + 1, K, -1), np.asarray(net["b1"], dtype=np.float64).reshape(A + 1, K)
+    fw = w1[A:] + w1[:A] - w1[:A].mean(0, keepdims=True)
+    fb = b1[A:] + b1[:A] - b1[:A].mean(0, keepdims=True)
+    return {"w0": np.asarray(net["w0"], dtype=np.float64), "b0": np.asarray(net["b0"], dtype=np.float64), "w1": fw.reshape(A * K, -1), "b1": fb.reshape(A * K)}
 
 
 def c51_targets_host(params, batch, cfg, dtype="float64", disc=None):
@@ -1491,11 +1535,12 @@ def c51_targets_host(params, batch, cfg, dtype="float64", disc=None):
     td = getattr(torch, dtype)
     T = lambda a: torch.tensor(np.asarray(a), dtype=td)
     A, K, B = cfg.n_actions, cfg.n_atoms, len(batch["r"])
+    duel = bool(getattr(cfg, "dueling", False))
     z = T(c51_support(cfg))
     with torch.no_grad():
         s2 = T(batch["s2"])
-        pt = torch.softmax(_c51_logits({k: T(params["q_target"][k]) for k in DQN_TENSORS}, s2, A, K), -1)
-        ps = torch.softmax(_c51_logits({k: T(params["q"][k]) for k in DQN_TENSORS}, s2, A, K), -1) if cfg.double else pt
+        pt = torch.softmax(_c51_logits({k: T(params["q_target"][k]) for k in DQN_TENSORS}, s2, A, K, duel), -1)
+        ps = torch.softmax(_c51_logits({k: T(params["q"][k]) for k in DQN_TENSORS}, s2, A, K, duel), -1) if cfg.double else pt
         ev = (ps * z).sum(-1)
         astar = torch.argmax(ev, dim=1)
         p_next = pt[torch.arange(B), astar]
@@ -1511,7 +1556,7 @@ def update_host_c51(params, batch, cfg, dtype="float64", weights=None, grads_onl
     bias-corrected Adam step and the hard copy of the target as ``update_host_dqn`` has them.  Returns the new params and a dict with
     ``update_host_dqn``'s keys -- ``loss`` (unweighted), ``mean_q``, ``q_values`` (the expected value of the stored action), ``td`` (the row loss: the
     priority), ``targets`` ([B][3]: a*, the target net's expected value there, l), ``grad`` -- plus ``dist`` ([B][2][K]: m and p(s, a)), ``row_loss``
-    and ``ev_next``."""
+    and ``ev_next``.  With ``cfg.dueling`` the nets have (A + 1) * K output rows and the logits are the dueling head's (``_c51_logits``)."""
     import torch
     td = getattr(torch, dtype)
     T = lambda a: torch.tensor(np.asarray(a), dtype=td)
@@ -1521,7 +1566,7 @@ def update_host_c51(params, batch, cfg, dtype="float64", weights=None, grads_onl
     m = T(tg["m"])
     net = {k: P["q"][k].clone().requires_grad_(True) for k in DQN_TENSORS}
     a = torch.tensor(np.asarray(batch["a"], dtype=np.int64))
-    logp = torch.log_softmax(_c51_logits(net, T(batch["s"]), A, K), -1)[torch.arange(B), a]
+    logp = torch.log_softmax(_c51_logits(net, T(batch["s"]), A, K, bool(getattr(cfg, "dueling", False))), -1)[torch.arange(B), a]
     terms = -(m * logp).sum(-1)
     loss = terms.mean()
     grads = dict(zip(DQN_TENSORS, torch.autograd.grad(loss if weights is None else (T(weights) * terms).mean(), [net[k] for k in DQN_TENSORS])))
@@ -1551,7 +1596,8 @@ def update_host_c51(params, batch, cfg, dtype="float64", weights=None, grads_onl
 class C51Learner(_QLearner):
     """Categorical DQN on the device for the discrete-action envs, with ``DQNLearner``'s interface (``train_dqn`` takes either).  ``env_or_dims``: a
     discrete env or ``(n_obs, n_actions)``; ``cfg``: ``C51Config``; ``init``: None (torch's nn.Linear initialisation, ``init_c51_net``) or a net
-    {w0, b0, w1 [A * n_atoms][h1], b1 [A * n_atoms]}.  One update is three HIP launches (five with ``cfg.per``)."""
+    {w0, b0, w1 [A * n_atoms][h1], b1 [A * n_atoms]} ((A + 1) * n_atoms rows with ``cfg.dueling``: the value block last).  One update is three HIP
+    launches (five with ``cfg.per``), with either head."""
 
     _api, _per_api, _slots, _flatten = "c51", "c51_per", _capi.C51_SLOTS, staticmethod(flatten_q)
     _name, _cfg_type = "C51", C51Config
@@ -1564,10 +1610,24 @@ class C51Learner(_QLearner):
         self.cfg.check_width()
 
     def _out_shape(self):
-        return (self.cfg.n_actions, self.cfg.n_atoms)
+        return (self.cfg.n_blocks, self.cfg.n_atoms)
 
     def _init_net(self, rng):
-        return init_c51_net(self.cfg.n_obs, self.cfg.h1, self.cfg.n_actions, self.cfg.n_atoms, rng)
+        return init_c51_net(self.cfg.n_obs, self.cfg.h1, self.cfg.n_actions, self.cfg.n_atoms, rng, self.cfg.dueling)
+
+    def state_dict(self):
+        """``_Learner.state_dict`` with the head's flag (``dueling``), which ``load_state_dict`` compares."""
+        sd = super().state_dict()
+        sd["dueling"] = bool(self.cfg.dueling)
+        return sd
+
+    def load_state_dict(self, sd):
+        """``_Learner.load_state_dict``; a state written by the other head is refused (one without the ``dueling`` key is taken as it is, as one
+        without ``n_step`` is)."""
+        if "dueling" in sd and bool(sd["dueling"]) != bool(self.cfg.dueling):
+            raise ValueError("the state is a %s C51 learner's, this learner has a %s head (cfg.dueling = %r)"
+                             % ("dueling" if sd.get("dueling", False) else "plain", "dueling" if self.cfg.dueling else "plain", self.cfg.dueling))
+        super().load_state_dict({k: v for k, v in sd.items() if k != "dueling"})
 
     def dist(self):
         """Debug: (float32 [batch][2][n_atoms] = the projected target distribution m and the online distribution p(s, a); ``targets()``'s array) of
@@ -1589,10 +1649,11 @@ class C51Learner(_QLearner):
         return m.cpu().numpy()
 
     def export_q(self, path):
-        """Write the online logits network as an ``.npz``: w0, b0, w1, b1 (float32), ``action_values`` and the head's ``n_atoms``, ``v_min``, ``v_max``."""
+        """Write the online logits network as an ``.npz``: w0, b0, w1, b1 (float32), ``action_values`` and the head's ``n_atoms``, ``v_min``, ``v_max``
+        and ``dueling`` (0 / 1; a reader takes a file without the key as 0)."""
         with open(path, "wb") as fh:
             np.savez_compressed(fh, **self._slot(0), action_values=self.action_values, n_atoms=np.int64(self.cfg.n_atoms), v_min=np.float64(self.cfg.v_min),
-                                v_max=np.float64(self.cfg.v_max))
+                                v_max=np.float64(self.cfg.v_max), dueling=np.int64(self.cfg.dueling))
         return path
 
 
@@ -1606,8 +1667,8 @@ class C51Population(DQNPopulation):
     The questions a user has about the categorical agent -- which support ``[v_min, v_max]`` fits this env's returns, double against plain action
     selection, which ``target_period``, ``gamma``, ``n_step`` and seed, prioritised against uniform replay -- are a population's members side by side.
 
-    ``cfgs``: a list of ``C51Config`` or ``(cfg, P)``; the members share n_obs, h1, n_actions, n_atoms, batch and capacity and may differ in
-    everything else, the support included.  ``env``, ``seeds``, ``init``, ``per``, traffic groups and reward groups: as ``DQNPopulation``'s.  Member
+    ``cfgs``: a list of ``C51Config`` or ``(cfg, P)``; the members share n_obs, h1, n_actions, n_atoms, ``dueling``, batch and capacity and may differ
+    in everything else, the support included.  ``env``, ``seeds``, ``init``, ``per``, traffic groups and reward groups: as ``DQNPopulation``'s.  Member
     m starts exactly as ``C51Learner(seed=seeds[m], init=...)`` does and stays bit-identical to that learner driven on its slice alone.
 
     ``act`` / ``push`` / ``update`` / ``stats_device`` / ``stats`` are ``DQNPopulation``'s; ``act(..., debug_q=)`` gives the expected values
@@ -1634,6 +1695,9 @@ class C51Population(DQNPopulation):
             if c.n_atoms != self.cfgs[0].n_atoms:
                 raise ValueError("member %d has n_atoms %d, member 0 has %d: the members share n_obs, h1, n_actions, n_atoms, batch and capacity"
                                  % (m, c.n_atoms, self.cfgs[0].n_atoms))
+            if bool(c.dueling) != bool(self.cfgs[0].dueling):
+                raise ValueError("member %d has dueling = %r, member 0 has %r: the members share the head (it sets the network's shape)"
+                                 % (m, c.dueling, self.cfgs[0].dueling))
 
     def _make_member(self, m, env, init):
         return _C51PopulationMember(self, m, env, self.cfgs[m], self.seeds[m], init)
