@@ -290,6 +290,16 @@ def actor_settings():
     return g, apply_settings(g).Settings
 
 
+def episode_settings():
+    """The settings of the episode tests: the reference's defaults under the combined controller's medium-1 overrides and traffic."""
+    import rl_mpc_lanemerging_amd as pkg
+    from rl_mpc_lanemerging_amd import combined_bench
+    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
+    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
+    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1_TRAFFIC)
+    return pkg.Settings
+
+
 def actor_states(g, dev, same=False):
     """72 states of the golden, vehicle slots padded from 8 to Kmax = 16: per member 18 of its first states and, spread over both tiles of the
     member's slice, 6 whose rollout the reference ended after the first step (so that step 2 meets rows that are no longer live).

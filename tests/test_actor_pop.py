@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from stmpc_testlib import (ACTOR_KMAX as KMAX, ACTOR_N as N, ACTOR_N_PER as N_PER, ACTOR_P as P, actor_eval as _eval, actor_settings as _settings, actor_states as _states,
-                           actor_two_steps as _two_steps, assert_steps_equal as _assert_steps_equal, capi as _capi, header_prototypes, header_text,
+                           actor_two_steps as _two_steps, assert_steps_equal as _assert_steps_equal, capi as _capi, episode_settings as _episode_settings, header_prototypes, header_text,
                            same as _same_bits, slice_steps as _slice_steps)
 
 NAMES = ("low1", "medium1", "fast1")
@@ -288,15 +288,6 @@ def test_gpu_views_of_a_learner_population(gpu_ctx, restore_settings, tmp_path):
     views.evals.copy_(same["evals0"])
     j = views(1, same["ego4"], same["k"], same["ox"], same["ov"], same["oa"]).cpu().numpy().reshape(P, N_PER)
     assert (j[0] != j[1]).any() and (j[1] != j[2]).any()
-
-
-def _episode_settings():
-    import rl_mpc_lanemerging_amd as pkg
-    from rl_mpc_lanemerging_amd import combined_bench
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
-    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1_TRAFFIC)
-    return pkg.Settings
 
 
 def _episode_runs(gpu_ctx):

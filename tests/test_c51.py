@@ -1,4 +1,4 @@
-"""The C51 learner on the GPU (``learner.C51Learner``, csrc/stmpc_c51_kernels.hpp) against its host twins at the shapes of tests/c51_testlib.py,
+"""The C51 learner on the GPU (``learner.C51Learner``, csrc/stmpc_c51_kernels.hpp) against its host twins at the shapes of tests/discrete_testlib.py,
 (n_obs, h1, A, K, B) = (20, 16, 5, 17, 7), (12, 32, 3, 33, 16), (20, 48, 20, 51, 33), (20, 256, 5, 51, 64).  Rings have at most 256 rows, envs at
 most 64 environments.
 
@@ -7,38 +7,13 @@ minibatch rows at most max(4 x the error of ``update_host_c51("float32")``, 8 fl
 import numpy as np
 import pytest
 
-from c51_testlib import (LEARNER_SEED, NAMES, PROBLEM_SEEDS, Q_SLOTS, RING, SHAPES, all_negative_rows, astar_rows, dyadic_projection_case, minibatch_host,
-                         projection_edge_cases, random_problem, rows_of)
+from discrete_testlib import (C51 as HEAD, LEARNER_SEED, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, Q_SLOTS, RING, SHAPES as _SHAPES, all_negative_rows, astar_rows,
+                              dyadic_projection_case, expected_values_host, fill as _fill, make_learner as _learner, minibatch_host, pad_mask as _pad_mask,
+                              pads_are_zero as _pads_are_zero, projection_edge_cases, random_problem, rows_of, twins as _twins)
 from learner_testlib import FLOOR, bits_equal, check_4x as _check_4x, record as _record
 from stmpc_testlib import capi as _capi
 
-
-def _fill(L, replay, rows=slice(None), chunk=64):
-    import torch
-    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")
-    rep = {k: v[rows] for k, v in replay.items()}
-    R = rep["s"].shape[0]
-    for o in range(0, R, chunk):
-        sl = slice(o, min(R, o + chunk))
-        term = rep["term"][sl]
-        trunc = rep["trunc"][sl] if "trunc" in rep else np.zeros_like(term)
-        L.push(dev(rep["s"][sl].astype(np.float32)), None, dev(rep["a"][sl].astype(np.int32)), dev(rep["r"][sl].astype(np.float64)),
-               dev(rep["s2"][sl].astype(np.float32)), dev(term), dev(trunc))
-
-
-def _learner(gpu_ctx, cfg, params, replay=None, seed=LEARNER_SEED, **kw):
-    from rl_mpc_lanemerging_amd import learner
-    L = learner.C51Learner((cfg.n_obs, cfg.n_actions), cfg, seed=seed, init=params["q"], ctx=gpu_ctx, **kw)
-    L.load_state_dict({"params": params, "counters": None})
-    if replay is not None:
-        _fill(L, replay)
-    return L
-
-
-def _twins(params, batch, cfg, **kw):
-    from rl_mpc_lanemerging_amd import learner
-    return tuple(learner.update_host_c51(params, batch, cfg, d, grads_only=True, **kw)[1] for d in ("float64", "float32"))
-
+SHAPES, PROBLEM_SEEDS = _SHAPES["c51"], _PROBLEM_SEEDS["c51"]      # tests/discrete_testlib.py's tables
 
 # ---- 1: the projection, exact --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
@@ -75,12 +50,12 @@ def test_gpu_distributions_loss_and_targets(si, double, gpu_ctx, restore_setting
     from rl_mpc_lanemerging_amd import learner
     shape = SHAPES[si]
     n_obs, h1, A, K, B = shape
-    cfg, params, replay = random_problem(shape, PROBLEM_SEEDS[si, double], neg_shift=True, double=double)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = random_problem(HEAD, shape, PROBLEM_SEEDS[si, double], neg_shift=True, double=double)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     rows = L.minibatch()
     assert L.stats()["fill"] == RING and np.array_equal(rows.view(np.uint32), minibatch_host(replay, cfg)[0].view(np.uint32))
     batch = learner.dqn_batch_from_rows(rows, n_obs)
-    i64, i32 = _twins(params, batch, cfg)
+    i64, i32 = _twins(HEAD, params, batch, cfg)
     neg = all_negative_rows(i64)
     assert neg.any() and not neg.all(), int(neg.sum())
     d, t = L.dist()
@@ -106,21 +81,6 @@ def test_gpu_distributions_loss_and_targets(si, double, gpu_ctx, restore_setting
 
 
 # ---- 3: gradients ----------------------------------------------------------------------------------------------------------------------------------
-def _pad_mask(n_obs, h1, n_out):
-    h1p, Ap = (h1 + 15) & ~15, (n_out + 15) & ~15
-    m = {"w0": np.ones((h1p, 32), bool), "b0": np.ones(h1p, bool), "w1": np.ones((Ap, h1p), bool), "b1": np.ones(Ap, bool)}
-    m["w0"][:h1, :n_obs], m["b0"][:h1], m["w1"][:n_out, :h1], m["b1"][:n_out] = False, False, False, False
-    return m
-
-
-def _pads_are_zero(gpu_ctx, L, slots, pad, tag):
-    for slot in slots:
-        arr = gpu_ctx.c51_padded_read(L.handle, slot, L.cfg.h1, L.cfg.n_actions * L.cfg.n_atoms)
-        for k in NAMES:
-            assert arr[k].shape == pad[k].shape and not arr[k][pad[k]].any(), (tag, slot, k, int(np.count_nonzero(arr[k][pad[k]])))
-            assert np.isfinite(arr[k]).all()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("si", range(len(SHAPES)))
 def test_gpu_gradients(si, gpu_ctx, restore_settings):
@@ -131,11 +91,11 @@ def test_gpu_gradients(si, gpu_ctx, restore_settings):
     from rl_mpc_lanemerging_amd import learner
     shape = SHAPES[si]
     n_obs, h1, A, K, B = shape
-    cfg, params, replay = random_problem(shape, 320 + si)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = random_problem(HEAD, shape, 320 + si)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     rows = L.minibatch()
     batch = learner.dqn_batch_from_rows(rows, n_obs)
-    i64, i32 = _twins(params, batch, cfg)
+    i64, i32 = _twins(HEAD, params, batch, cfg)
     g = L.grads()
     ratios, ok = {}, True
     for k in NAMES:
@@ -143,7 +103,7 @@ def test_gpu_gradients(si, gpu_ctx, restore_settings):
         ok &= _check_4x("c51 %s grad %s" % (shape, k), g[k], i32["grad"][k], i64["grad"][k], ratios)
     _record("c51 grad %s" % (shape,), ratios)
     pad = _pad_mask(n_obs, h1, A * K)
-    _pads_are_zero(gpu_ctx, L, [capi.C51_GRAD], pad, "grads")
+    _pads_are_zero(gpu_ctx, HEAD, L, [capi.C51_GRAD], pad, "grads")
     have = gpu_ctx.c51_padded_read(L.handle, capi.C51_GRAD, h1, A * K)
     assert all(np.array_equal(have[k][~pad[k]].reshape(g[k].shape), g[k]) for k in NAMES)
     dz = gpu_ctx.c51_dzout_read(L.handle, B, A * K)
@@ -170,8 +130,8 @@ def test_gpu_adam_and_target_copy(si, gpu_ctx, restore_settings):
     from rl_mpc_lanemerging_amd import learner
     shape = SHAPES[si]
     n_obs, h1, A, K, B = shape
-    cfg, params, replay = random_problem(shape, 340 + si, target_period=3)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = random_problem(HEAD, shape, 340 + si, target_period=3)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     pad = _pad_mask(n_obs, h1, A * K)
     for u in range(4):
         before = L.state_dict()["params"]
@@ -184,7 +144,7 @@ def test_gpu_adam_and_target_copy(si, gpu_ctx, restore_settings):
             assert np.array_equal(after["q_target"][k], after["q"][k] if (u + 1) % 3 == 0 else before["q_target"][k]), (u, k)
             assert not np.array_equal(after["q"][k], before["q"][k])
         assert np.array_equal(after["beta_pow"], bp) and after["updates"] == u + 1
-        _pads_are_zero(gpu_ctx, L, range(5), pad, "update %d" % u)
+        _pads_are_zero(gpu_ctx, HEAD, L, range(5), pad, "update %d" % u)
     st = L.stats()
     assert st["updates"] == 4 and st["fill"] == RING and np.isfinite(st["loss"]) and st["loss"] > 0
     gpu_ctx.check_error()
@@ -199,20 +159,15 @@ def test_gpu_acting(si, gpu_ctx, restore_settings):
     from rl_mpc_lanemerging_amd import learner
     shape = SHAPES[si]
     n_obs, h1, A, K, B = shape
-    cfg, params, replay = random_problem(shape, 360 + si)
-    L = _learner(gpu_ctx, cfg, params, seed=23)
+    cfg, params, replay = random_problem(HEAD, shape, 360 + si)
+    L = _learner(gpu_ctx, HEAD, cfg, params, seed=23)
     n = 50                                                          # four tiles, the last one partly filled
     obs = torch.as_tensor(replay["s"][:n].astype(np.float32), device="cuda")
     q = torch.zeros(n, A, dtype=torch.float32, device="cuda")
     greedy = L.act(obs, None, eps=0.0, debug_q=q).cpu().numpy().copy()
     qh = q.cpu().numpy()
     assert greedy.dtype == np.int32 and np.array_equal(greedy, qh.argmax(1))      # numpy's argmax: the first maximum
-    ev = {}
-    for d in ("float64", "float32"):
-        T = lambda a: torch.tensor(np.asarray(a), dtype=getattr(torch, d))
-        with torch.no_grad():
-            p = torch.softmax(learner._c51_logits({k: T(params["q"][k]) for k in NAMES}, T(replay["s"][:n]), A, K), -1)
-            ev[d] = (p * T(learner.c51_support(cfg))).sum(-1).numpy()
+    ev = expected_values_host(params["q"], replay["s"][:n], cfg)
     assert _check_4x("c51 %s acting E[Z]" % (shape,), qh, ev["float32"], ev["float64"])
     assert int(gpu_ctx.c51_get_state(L.handle)[0][3]) == 0          # a greedy call is no exploring call
     call = 0
@@ -263,8 +218,8 @@ def test_gpu_prioritised_replay(gpu_ctx, restore_settings):
     from rl_mpc_lanemerging_amd import learner
     per = learner.PERConfig(beta=0.5, max_priority=16.0)            # (a cross-entropy over 51 atoms is about log 51: the reference's cap of 4 would level them)
     shape = SHAPES[2]
-    cfg, params, replay = random_problem(shape, 371, per=per)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = random_problem(HEAD, shape, 371, per=per)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     host = learner.SumTreeHost(RING, per)
     host.push(RING)
     assert np.array_equal(L.priorities(), host.nodes)
@@ -284,7 +239,7 @@ def test_gpu_prioritised_replay(gpu_ctx, restore_settings):
             assert len(set(w.tolist())) > 1
         seen |= set(idx.tolist())
         batch = learner.dqn_batch_from_rows(rows, cfg.n_obs)
-        i64, i32 = _twins(before, batch, cfg, weights=w)
+        i64, i32 = _twins(HEAD, before, batch, cfg, weights=w)
         assert all(_check_4x("c51 per u%d grad %s" % (u, k), g[k], i32["grad"][k], i64["grad"][k]) for k in NAMES)
         L.update(1)
         ls = L.last_sample()
@@ -307,10 +262,10 @@ def test_gpu_three_step_returns(double, gpu_ctx, restore_settings):
     shape = SHAPES[1]
     n_obs, h1, A, K, B = shape
     N = 8
-    cfg, params, replay = random_problem(shape, 380, double=double, n_step=3, gamma=0.9)
+    cfg, params, replay = random_problem(HEAD, shape, 380, double=double, n_step=3, gamma=0.9)
     rng = np.random.default_rng(5)
     replay["trunc"] = (rng.random(RING) < 0.15) & ~replay["term"]
-    L = _learner(gpu_ctx, cfg, params, rows_per_push=N)
+    L = _learner(gpu_ctx, HEAD, cfg, params, rows_per_push=N)
     _fill(L, replay, slice(0, 96), chunk=N)                         # 96 of 128 rows: the newest rows' windows are cut short
     cn = L.state_dict()["counters"]
     ring = gpu_ctx.c51_replay_read(L.handle, 0, RING)
@@ -318,7 +273,7 @@ def test_gpu_three_step_returns(double, gpu_ctx, restore_settings):
     idx = learner.sample_indices_host(LEARNER_SEED, 0, B, 96)
     b = learner.nstep_batch_host(ring, idx, cn[0], cn[1], N, 3, cfg.gamma, n_obs, dqn=True)
     assert len(set(b["m"].tolist())) >= 2 and set(b["m"].tolist()) <= {1, 2, 3} and np.array_equal(L.minibatch().view(np.uint32), b["rows"].view(np.uint32))
-    i64, i32 = _twins(params, b, cfg, disc=b["disc"])
+    i64, i32 = _twins(HEAD, params, b, cfg, disc=b["disc"])
     d, t = L.dist()
     g = L.grads()
     tag = "c51 n=3 %s " % ("double" if double else "plain")
@@ -340,8 +295,8 @@ def test_gpu_updates_are_reproducible_and_state_round_trips(per, gpu_ctx, restor
     _capi()
     from rl_mpc_lanemerging_amd import learner
     kw = dict(per=learner.PERConfig(beta=0.4)) if per else {}
-    cfg, params, replay = random_problem(SHAPES[2], 390, target_period=4, **kw)
-    A_, B_ = _learner(gpu_ctx, cfg, params, replay), _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = random_problem(HEAD, SHAPES[2], 390, target_period=4, **kw)
+    A_, B_ = _learner(gpu_ctx, HEAD, cfg, params, replay), _learner(gpu_ctx, HEAD, cfg, params, replay)
     A_.update(10)
     B_.update(4)
     mid = B_.state_dict()
@@ -350,7 +305,7 @@ def test_gpu_updates_are_reproducible_and_state_round_trips(per, gpu_ctx, restor
     assert bits_equal(sa["params"], sb["params"], Q_SLOTS, NAMES) and np.array_equal(sa["counters"], sb["counters"]) and np.array_equal(sa["params"]["beta_pow"], sb["params"]["beta_pow"])
     assert A_.stats() == B_.stats() and sa["params"]["updates"] == 10 and not bits_equal(sa["params"], params, ("q",), NAMES)
     if not per:                                                     # (a tree is not part of a state_dict)
-        C_ = _learner(gpu_ctx, cfg, params, replay)
+        C_ = _learner(gpu_ctx, HEAD, cfg, params, replay)
         C_.load_state_dict(mid)
         back = C_.state_dict()
         assert bits_equal(back["params"], mid["params"], Q_SLOTS, NAMES) and np.array_equal(back["counters"], mid["counters"])

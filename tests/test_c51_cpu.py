@@ -1,18 +1,18 @@
 """The C51 learner without a GPU: header, library and binding agree on the stmpc_c51_ entries and on the config struct; ``update_host_c51`` against a
 second statement with nn.Linear modules, log_softmax, loss.backward() and optim.Adam (float64, 1e-12: test_dqn_cpu.py's bar); the gather-form
 projection ``c51_project_host`` against the textbook scatter loop on random inputs with the edge cases forced in; mass and mean preservation; the
-refusals; and the properties of the GPU tests' problems that the float64 twin alone decides (tests/c51_testlib.py)."""
+refusals; and the properties of the GPU tests' problems that the float64 twin alone decides (tests/discrete_testlib.py)."""
 import ctypes
 import types
 
 import numpy as np
 import pytest
 
-from c51_testlib import (PROBLEM_SEEDS, SHAPES, all_negative_rows, astar_rows, dyadic_projection_case, minibatch_host, projection_edge_cases,
-                         random_problem)
+from discrete_testlib import (C51 as HEAD, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, SHAPES as _SHAPES, all_negative_rows, astar_rows, dyadic_projection_case, minibatch_host,
+                              projection_edge_cases, random_problem, twins)
 from stmpc_testlib import capi as _capi, header_entries, header_prototypes, header_struct_fields as _header_struct_fields, header_text
 
-NAMES = ("w0", "b0", "w1", "b1")
+SHAPES, PROBLEM_SEEDS = _SHAPES["c51"], _PROBLEM_SEEDS["c51"]      # tests/discrete_testlib.py's tables
 ENTRIES = {"stmpc_c51_" + n for n in ("create", "destroy", "set_params", "get_params", "set_state", "get_state", "push_device", "act_device", "update_device",
                                       "grads_device", "targets_device", "dist_device", "project_device", "gather_device", "stats_device", "per_enable",
                                       "per_tree_read", "per_last_device", "multi_step_enable", "replay_read", "dzout_read", "padded_read")}
@@ -227,10 +227,9 @@ def test_gpu_problems_have_the_rows_the_gpu_tests_need(si, double):
     negative and rows on which one is not; at most 10 % of the rows left out of the a* comparison."""
     _capi()
     from rl_mpc_lanemerging_amd import learner
-    cfg, params, replay = random_problem(SHAPES[si], PROBLEM_SEEDS[si, double], neg_shift=True, double=double)
+    cfg, params, replay = random_problem(HEAD, SHAPES[si], PROBLEM_SEEDS[si, double], neg_shift=True, double=double)
     _, batch = minibatch_host(replay, cfg)
-    _, i64 = learner.update_host_c51(params, batch, cfg, "float64", grads_only=True)
-    _, i32 = learner.update_host_c51(params, batch, cfg, "float32", grads_only=True)
+    i64, i32 = twins(HEAD, params, batch, cfg)
     neg = all_negative_rows(i64)
     assert neg.any() and not neg.all(), int(neg.sum())
     keep, left_out = astar_rows(i64, i32)

@@ -1,5 +1,5 @@
 """The dueling head of the C51 learner on the GPU (``learner.C51Config(dueling=True)``, c51_dueling_combine and the dense backward of
-csrc/stmpc_c51_kernels.hpp, k_c51actor_eval) against its host twins at the shapes of tests/c51_dueling_testlib.py, (n_obs, h1, A, K, B) =
+csrc/stmpc_c51_kernels.hpp, k_c51actor_eval) against its host twins at the shapes of tests/discrete_testlib.py, (n_obs, h1, A, K, B) =
 (20, 16, 2, 16, 5), (20, 16, 5, 17, 7), (12, 32, 3, 33, 16), (20, 48, 19, 51, 33), (20, 256, 5, 51, 64).  Rings have 128 rows, the learner's seed is 11.
 
 Parity rule for float32 results (tests/learner_testlib.py's): per tensor, max-norm error against ``update_host_c51("float64")`` fed the device's own
@@ -9,53 +9,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from c51_dueling_testlib import NAMES, PROBLEM_SEEDS, Q_SLOTS, SHAPES, duel_problem, minibatch_host, pad_mask, twins as _twins, width
-from c51_testlib import LEARNER_SEED, RING, all_negative_rows, astar_rows, rows_of
+from discrete_testlib import (C51_DUELING as HEAD, LEARNER_SEED, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, Q_SLOTS, RING, SHAPES as _SHAPES, all_negative_rows, astar_rows,
+                              expected_values_host as _expected_values_host, fill as _fill, make_learner as _learner, minibatch_host, pad_mask,
+                              pads_are_zero as _pads_are_zero, random_problem, rows_of, stub_env as _stub_env, twins as _twins)
 from learner_testlib import FLOOR, bits_equal, bound_4x, check_4x as _check_4x, rel_err
 from stmpc_testlib import capi as _capi
 
-
-def _fill(L, replay, rows=slice(None), chunk=64):
-    import torch
-    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")
-    rep = {k: v[rows] for k, v in replay.items()}
-    R = rep["s"].shape[0]
-    for o in range(0, R, chunk):
-        sl = slice(o, min(R, o + chunk))
-        term = rep["term"][sl]
-        trunc = rep["trunc"][sl] if "trunc" in rep else np.zeros_like(term)
-        L.push(dev(rep["s"][sl].astype(np.float32)), None, dev(rep["a"][sl].astype(np.int32)), dev(rep["r"][sl].astype(np.float64)),
-               dev(rep["s2"][sl].astype(np.float32)), dev(term), dev(trunc))
-
-
-def _learner(gpu_ctx, cfg, params, replay=None, seed=LEARNER_SEED, **kw):
-    from rl_mpc_lanemerging_amd import learner
-    L = learner.C51Learner((cfg.n_obs, cfg.n_actions), cfg, seed=seed, init=params["q"], ctx=gpu_ctx, **kw)
-    L.load_state_dict({"params": params, "counters": None})
-    if replay is not None:
-        _fill(L, replay)
-    return L
-
-
-def _pads_are_zero(gpu_ctx, L, slots, pad, tag):
-    for slot in slots:
-        arr = gpu_ctx.c51_padded_read(L.handle, slot, L.cfg.h1, L.cfg.n_blocks * L.cfg.n_atoms)
-        for k in NAMES:
-            assert arr[k].shape == pad[k].shape and not arr[k][pad[k]].any(), (tag, slot, k, int(np.count_nonzero(arr[k][pad[k]])))
-            assert np.isfinite(arr[k]).all()
-
-
-def _expected_values_host(net, obs, cfg):
-    import torch
-    from rl_mpc_lanemerging_amd import learner
-    ev = {}
-    for d in ("float64", "float32"):
-        T = lambda a: torch.tensor(np.asarray(a), dtype=getattr(torch, d))
-        with torch.no_grad():
-            p = torch.softmax(learner._c51_logits({k: T(net[k]) for k in NAMES}, T(obs), cfg.n_actions, cfg.n_atoms, dueling=True), -1)
-            ev[d] = (p * T(learner.c51_support(cfg))).sum(-1).numpy()
-    return ev
-
+SHAPES, PROBLEM_SEEDS = _SHAPES["c51_dueling"], _PROBLEM_SEEDS["c51_dueling"]      # tests/discrete_testlib.py's tables
 
 # ---- 1: distributions, loss, targets ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
@@ -68,12 +28,12 @@ def test_gpu_distributions_loss_and_targets(si, double, gpu_ctx, restore_setting
     from rl_mpc_lanemerging_amd import learner
     shape = SHAPES[si]
     n_obs, h1, A, K, B = shape
-    cfg, params, replay = duel_problem(shape, PROBLEM_SEEDS[si, double], neg_shift=True, double=double)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = random_problem(HEAD, shape, PROBLEM_SEEDS[si, double], neg_shift=True, double=double)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     rows = L.minibatch()
     assert L.stats()["fill"] == RING and np.array_equal(rows.view(np.uint32), minibatch_host(replay, cfg)[0].view(np.uint32))
     batch = learner.dqn_batch_from_rows(rows, n_obs)
-    i64, i32 = _twins(params, batch, cfg)
+    i64, i32 = _twins(HEAD, params, batch, cfg)
     neg = all_negative_rows(i64)
     assert neg.any() and not neg.all(), int(neg.sum())
     d, t = L.dist()
@@ -107,18 +67,18 @@ def test_gpu_gradients(si, gpu_ctx, restore_settings):
     from rl_mpc_lanemerging_amd import learner
     shape = SHAPES[si]
     n_obs, h1, A, K, B = shape
-    W = width(shape)
-    cfg, params, replay = duel_problem(shape, 320 + si)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    W = HEAD.width(shape)
+    cfg, params, replay = random_problem(HEAD, shape, 320 + si)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     batch = learner.dqn_batch_from_rows(L.minibatch(), n_obs)
-    i64, i32 = _twins(params, batch, cfg)
+    i64, i32 = _twins(HEAD, params, batch, cfg)
     g = L.grads()
     ok = True
     for k in NAMES:
         assert g[k].dtype == np.float32 and g[k].shape == i64["grad"][k].shape == params["q"][k].shape and np.abs(i64["grad"][k]).max() > 0
         ok &= _check_4x("c51 dueling %s grad %s" % (shape, k), g[k], i32["grad"][k], i64["grad"][k])
     pad = pad_mask(n_obs, h1, W)
-    _pads_are_zero(gpu_ctx, L, [capi.C51_GRAD], pad, "grads")
+    _pads_are_zero(gpu_ctx, HEAD, L, [capi.C51_GRAD], pad, "grads")
     have = gpu_ctx.c51_padded_read(L.handle, capi.C51_GRAD, h1, W)
     assert all(np.array_equal(have[k][~pad[k]].reshape(g[k].shape), g[k]) for k in NAMES)
     dz = gpu_ctx.c51_dzout_read(L.handle, B, W)
@@ -150,9 +110,9 @@ def test_gpu_adam_and_target_copy(si, gpu_ctx, restore_settings):
     from rl_mpc_lanemerging_amd import learner
     shape = SHAPES[si]
     n_obs, h1, A, K, B = shape
-    cfg, params, replay = duel_problem(shape, 340 + si, target_period=3)
-    L = _learner(gpu_ctx, cfg, params, replay)
-    pad = pad_mask(n_obs, h1, width(shape))
+    cfg, params, replay = random_problem(HEAD, shape, 340 + si, target_period=3)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
+    pad = pad_mask(n_obs, h1, HEAD.width(shape))
     for u in range(4):
         before = L.state_dict()["params"]
         g = L.grads()
@@ -164,7 +124,7 @@ def test_gpu_adam_and_target_copy(si, gpu_ctx, restore_settings):
             assert np.array_equal(after["q_target"][k], after["q"][k] if (u + 1) % 3 == 0 else before["q_target"][k]), (u, k)
             assert not np.array_equal(after["q"][k], before["q"][k])
         assert np.array_equal(after["beta_pow"], bp) and after["updates"] == u + 1
-        _pads_are_zero(gpu_ctx, L, range(5), pad, "update %d" % u)
+        _pads_are_zero(gpu_ctx, HEAD, L, range(5), pad, "update %d" % u)
     st = L.stats()
     assert st["updates"] == 4 and st["fill"] == RING and np.isfinite(st["loss"]) and st["loss"] > 0
     gpu_ctx.check_error()
@@ -180,8 +140,8 @@ def test_gpu_acting(si, gpu_ctx, restore_settings):
     from rl_mpc_lanemerging_amd import learner
     shape = SHAPES[si]
     n_obs, h1, A, K, B = shape
-    cfg, params, replay = duel_problem(shape, 360 + si)
-    L = _learner(gpu_ctx, cfg, params, seed=23)
+    cfg, params, replay = random_problem(HEAD, shape, 360 + si)
+    L = _learner(gpu_ctx, HEAD, cfg, params, seed=23)
     n = 50                                                          # four tiles, the last one partly filled
     obs = torch.as_tensor(replay["s"][:n].astype(np.float32), device="cuda")
     q = torch.zeros(n, A, dtype=torch.float32, device="cuda")
@@ -211,8 +171,8 @@ def test_gpu_actors_give_the_bits_of_act(si, gpu_ctx, restore_settings, tmp_path
     g, S = actor_settings()
     st = actor_states(g, "cuda")
     n = st["ego5"].shape[0]
-    cfg, params, _ = duel_problem(shape, 400 + si)
-    L = _learner(gpu_ctx, cfg, params)
+    cfg, params, _ = random_problem(HEAD, shape, 400 + si)
+    L = _learner(gpu_ctx, HEAD, cfg, params)
     table = np.linspace(-2.0, 2.0, A)
     L.action_values = table
 
@@ -258,8 +218,8 @@ def test_gpu_prioritised_replay(gpu_ctx, restore_settings):
     from rl_mpc_lanemerging_amd import learner
     per = learner.PERConfig(beta=0.5, max_priority=16.0)
     shape = SHAPES[2]
-    cfg, params, replay = duel_problem(shape, 371, per=per)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = random_problem(HEAD, shape, 371, per=per)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     host = learner.SumTreeHost(RING, per)
     host.push(RING)
     assert np.array_equal(L.priorities(), host.nodes)
@@ -270,7 +230,7 @@ def test_gpu_prioritised_replay(gpu_ctx, restore_settings):
         before = L.state_dict()["params"]
         g = L.grads()
         w = L.last_sample()["weight"]
-        i64, i32 = _twins(before, learner.dqn_batch_from_rows(rows, cfg.n_obs), cfg, weights=w)
+        i64, i32 = _twins(HEAD, before, learner.dqn_batch_from_rows(rows, cfg.n_obs), cfg, weights=w)
         assert all(_check_4x("c51 dueling per u%d grad %s" % (u, k), g[k], i32["grad"][k], i64["grad"][k]) for k in NAMES)
         L.update(1)
         ls = L.last_sample()
@@ -290,16 +250,16 @@ def test_gpu_three_step_returns(gpu_ctx, restore_settings):
     shape = SHAPES[2]
     n_obs, h1, A, K, B = shape
     N = 8
-    cfg, params, replay = duel_problem(shape, 380, n_step=3, gamma=0.9)
+    cfg, params, replay = random_problem(HEAD, shape, 380, n_step=3, gamma=0.9)
     replay["trunc"] = (np.random.default_rng(5).random(RING) < 0.15) & ~replay["term"]
-    L = _learner(gpu_ctx, cfg, params, rows_per_push=N)
+    L = _learner(gpu_ctx, HEAD, cfg, params, rows_per_push=N)
     _fill(L, replay, slice(0, 96), chunk=N)
     cn = L.state_dict()["counters"]
     ring = gpu_ctx.c51_replay_read(L.handle, 0, RING)
     idx = learner.sample_indices_host(LEARNER_SEED, 0, B, 96)
     b = learner.nstep_batch_host(ring, idx, cn[0], cn[1], N, 3, cfg.gamma, n_obs, dqn=True)
     assert len(set(b["m"].tolist())) >= 2 and np.array_equal(L.minibatch().view(np.uint32), b["rows"].view(np.uint32))
-    i64, i32 = _twins(params, b, cfg, disc=b["disc"])
+    i64, i32 = _twins(HEAD, params, b, cfg, disc=b["disc"])
     d, t = L.dist()
     g = L.grads()
     tag = "c51 dueling n=3 "
@@ -314,8 +274,8 @@ def test_gpu_three_step_returns(gpu_ctx, restore_settings):
 @pytest.mark.gpu
 def test_gpu_updates_are_reproducible_and_state_round_trips(gpu_ctx, restore_settings):
     _capi()
-    cfg, params, replay = duel_problem(SHAPES[3], 390, target_period=4)
-    A_, B_ = _learner(gpu_ctx, cfg, params, replay), _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = random_problem(HEAD, SHAPES[3], 390, target_period=4)
+    A_, B_ = _learner(gpu_ctx, HEAD, cfg, params, replay), _learner(gpu_ctx, HEAD, cfg, params, replay)
     A_.update(10)
     B_.update(4)
     mid = B_.state_dict()
@@ -323,7 +283,7 @@ def test_gpu_updates_are_reproducible_and_state_round_trips(gpu_ctx, restore_set
     sa, sb = A_.state_dict(), B_.state_dict()
     assert bits_equal(sa["params"], sb["params"], Q_SLOTS, NAMES) and np.array_equal(sa["counters"], sb["counters"]) and np.array_equal(sa["params"]["beta_pow"], sb["params"]["beta_pow"])
     assert A_.stats() == B_.stats() and sa["params"]["updates"] == 10 and not bits_equal(sa["params"], params, ("q",), NAMES)
-    C_ = _learner(gpu_ctx, cfg, params, replay)
+    C_ = _learner(gpu_ctx, HEAD, cfg, params, replay)
     C_.load_state_dict(mid)
     back = C_.state_dict()
     assert bits_equal(back["params"], mid["params"], Q_SLOTS, NAMES) and np.array_equal(back["counters"], mid["counters"]) and back["dueling"] is True
@@ -341,14 +301,12 @@ def test_gpu_population_members_equal_lone_learners(gpu_ctx, restore_settings):
     capi = _capi()
     import torch
     from rl_mpc_lanemerging_amd import learner
-    import types
     shape = SHAPES[1]
     n_obs, h1, A, K, B = shape
     P, n_per = 3, 16
     sups = [(-10.0, 10.0), (-4.0, 4.0), (-2.0, 6.0)]
-    probs = [duel_problem(shape, 500 + m, v_min=sups[m][0], v_max=sups[m][1], double=bool(m % 2)) for m in range(P)]
-    env = types.SimpleNamespace(n=P * n_per, obs_dim=n_obs, continuous=False, ctx=gpu_ctx, action_space={"n": A}, env_id="sumo-jerk-v0",
-                                cfg=types.SimpleNamespace(_actions=list(np.linspace(-4.75, 4.75, A))))
+    probs = [random_problem(HEAD, shape, 500 + m, v_min=sups[m][0], v_max=sups[m][1], double=bool(m % 2)) for m in range(P)]
+    env = _stub_env(gpu_ctx, P * n_per, n_obs, A)
     seeds = [11, 12, 13]
     pop = learner.C51Population(env, [p[0] for p in probs], seeds=seeds, init=[p[1]["q"] for p in probs])
     lone = [learner.C51Learner((n_obs, A), probs[m][0], seed=seeds[m], init=probs[m][1]["q"], ctx=gpu_ctx) for m in range(P)]
@@ -376,8 +334,8 @@ def test_gpu_population_members_equal_lone_learners(gpu_ctx, restore_settings):
         assert np.array_equal(lone[m].act(obs[ms], None, eps=0.0, debug_q=qb[ms]).cpu().numpy(), act[ms])
     assert torch.equal(qa.view(torch.int32), qb.view(torch.int32))
     with pytest.raises(ValueError, match="member 1 has dueling = False"):
-        learner.C51Population(env, [probs[0][0], duel_problem(shape, 1, dueling=False)[0], probs[2][0]])
-    cfgs = (capi.C51Cfg * 2)(probs[0][0].to_c(0), duel_problem(shape, 1, dueling=False)[0].to_c(0))
+        learner.C51Population(env, [probs[0][0], random_problem(HEAD, shape, 1, dueling=False)[0], probs[2][0]])
+    cfgs = (capi.C51Cfg * 2)(probs[0][0].to_c(0), random_problem(HEAD, shape, 1, dueling=False)[0].to_c(0))
     h = C.c_void_p()
     assert capi.load().stmpc_pop_c51_create(gpu_ctx._h, cfgs, 2, C.byref(h)) == capi.STMPC_EINVAL and not h.value
     assert "member 1 differs from member 0" in capi.load().stmpc_last_error().decode()
@@ -412,9 +370,9 @@ def test_gpu_library_refusals(gpu_ctx):
         gpu_ctx.c51actor_create(net(5, 17), np.arange(6.0), 17, -10.0, 10.0, dueling=True)
     # load_state_dict across the flag, both ways
     shape = SHAPES[1]
-    cfg_d, params_d, _ = duel_problem(shape, 3)
+    cfg_d, params_d, _ = random_problem(HEAD, shape, 3)
     cfg_p = learner.C51Config(n_obs=shape[0], n_actions=shape[2], h1=shape[1], batch=shape[4], capacity=RING, n_atoms=shape[3])
-    Ld, Lp = _learner(gpu_ctx, cfg_d, params_d), learner.C51Learner((shape[0], shape[2]), cfg_p, ctx=gpu_ctx)
+    Ld, Lp = _learner(gpu_ctx, HEAD, cfg_d, params_d), learner.C51Learner((shape[0], shape[2]), cfg_p, ctx=gpu_ctx)
     with pytest.raises(ValueError, match="the state is a dueling C51 learner's, this learner has a plain head"):
         Lp.load_state_dict(Ld.state_dict())
     with pytest.raises(ValueError, match="the state is a plain C51 learner's, this learner has a dueling head"):

@@ -1,25 +1,26 @@
 """The dueling head of the C51 learner without a GPU (``learner.C51Config(dueling=True)``): the float64 twin against an independent torch module
 with separate value and advantage heads; ``c51_fold_dueling_host``; the head's invariance under a shift of every advantage block; the float32
 restatement of the device's combine; the config, the struct and the ``export_q`` key; and the properties of the GPU tests' problems that the twins
-alone decide (tests/c51_dueling_testlib.py).  Every test here needs ``C51Config`` to take ``dueling``."""
+alone decide (tests/discrete_testlib.py).  Every test here needs ``C51Config`` to take ``dueling``."""
 import ctypes
 import types
 
 import numpy as np
 import pytest
 
-from c51_dueling_testlib import NAMES, PROBLEM_SEEDS, SHAPES, duel_net, duel_problem, dueling_module, minibatch_host, split_heads, twins
-from c51_testlib import all_negative_rows, astar_rows
+from discrete_testlib import (C51_DUELING as HEAD, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, SHAPES as _SHAPES, all_negative_rows, astar_rows, dueling_module, minibatch_host,
+                              problem_net, random_problem, twins)
 from stmpc_testlib import capi as _capi
 
+SHAPES, PROBLEM_SEEDS = _SHAPES["c51_dueling"], _PROBLEM_SEEDS["c51_dueling"]      # tests/discrete_testlib.py's tables
 
 def _problem(seed, double=True, shape=(12, 24, 4, 11, 33)):
     from rl_mpc_lanemerging_amd import learner
     n_obs, h1, A, K, B = shape
     rng = np.random.default_rng(seed)
     cfg = learner.C51Config(n_obs=n_obs, n_actions=A, h1=h1, batch=B, gamma=0.9, lr=1e-3, double=double, n_atoms=K, v_min=-4.0, v_max=3.0, dueling=True)
-    params = learner.new_params_dqn(duel_net(shape, rng))
-    params["q_target"] = duel_net(shape, rng)
+    params = learner.new_params_dqn(problem_net(HEAD, shape, rng))
+    params["q_target"] = problem_net(HEAD, shape, rng)
     batch = {"s": rng.normal(size=(B, n_obs)), "s2": rng.normal(size=(B, n_obs)), "a": rng.integers(0, A, B), "r": rng.normal(size=B) * 2,
              "mask": (rng.random(B) > 0.25).astype(np.float64)}
     return cfg, params, batch
@@ -153,7 +154,7 @@ def test_config_struct_and_export_key(tmp_path):
     assert (c.dueling, c.reserved, c.n_atoms, c.seed) == (1, 1, 17, 3)
     assert "stmpc_dueling_c51actor_create" in capi.EXPORTS and capi.load().stmpc_dueling_c51actor_create.argtypes == capi.load().stmpc_c51actor_create.argtypes
     # export_q writes the key (the learner's own method on a stand-in: no device), and a reader takes a missing key as 0
-    net = duel_net((20, 16, 5, 17, 7), np.random.default_rng(0))
+    net = problem_net(HEAD, (20, 16, 5, 17, 7), np.random.default_rng(0))
     for flag in (True, False):
         stub = types.SimpleNamespace(cfg=learner.C51Config(n_obs=20, n_actions=5, h1=16, n_atoms=17, dueling=flag), action_values=np.arange(5.0), _slot=lambda i: net)
         path = learner.C51Learner.export_q(stub, str(tmp_path / ("q%d.npz" % flag)))
@@ -172,9 +173,9 @@ def test_gpu_problems_have_the_rows_the_gpu_tests_need(si, double):
     """The problems of tests/test_c51_dueling.py's distribution test, decided by the twins alone: rows on which every expected value at s' is
     negative and rows on which one is not; at most 10 % of the rows left out of the a* comparison."""
     _capi()
-    cfg, params, replay = duel_problem(SHAPES[si], PROBLEM_SEEDS[si, double], neg_shift=True, double=double)
+    cfg, params, replay = random_problem(HEAD, SHAPES[si], PROBLEM_SEEDS[si, double], neg_shift=True, double=double)
     _, batch = minibatch_host(replay, cfg)
-    i64, i32 = twins(params, batch, cfg)
+    i64, i32 = twins(HEAD, params, batch, cfg)
     neg = all_negative_rows(i64)
     assert neg.any() and not neg.all(), int(neg.sum())
     keep, left_out = astar_rows(i64, i32)

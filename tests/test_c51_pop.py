@@ -3,7 +3,7 @@
 Every comparison is bit equality against the lone ``C51Learner`` (or, for the projection and the multi-step windows, against the host twin on exact
 data): the population's kernels are the lone learner's bodies on the member ``blockIdx.y`` selects.  This file contains no tolerance.
 
-Shapes (n_obs, h1, A, K, B) of tests/c51_testlib.py's list: (20, 16, 5, 17, 7) on sumo-jerk-v0 -- pad columns inside the last tile, K below the lane
+Shapes (n_obs, h1, A, K, B) of tests/discrete_testlib.py's list: (20, 16, 5, 17, 7) on sumo-jerk-v0 -- pad columns inside the last tile, K below the lane
 count, padded minibatch rows --, (20, 48, 20, 51, 33) on sumo-accel-v0 -- A K = 1020 pads to 1024, the widest layer allowed, every action block
 straddles 16-column tiles --, and the shipped (20, 256, 5, 51, 50) in test 1 only.  Rings of at most 256 rows.
 
@@ -13,127 +13,30 @@ Tests 2 ... 7 run at both small shapes.  Multi-step windows (test 5): ``member(m
 the last row, m) through stmpc_pop_c51_multi_step_window and is compared with ``nstep_window_host`` on the member's own ring; the gathered minibatch
 is compared with ``nstep_batch_host`` alongside, before each of the four updates.
 """
-import types
-
 import numpy as np
 import pytest
 
-from c51_testlib import dyadic_projection_case
-from learner_testlib import CAP, N_PER, STEPS, bits64, dev as _dev
+from discrete_testlib import (C51 as HEAD, C51_SUPPORTS as SUPPORT, DOUBLE, NAMES, PERIOD, Q_SLOTS, assert_population_run, assert_same as _assert_same,
+                              dyadic_projection_case, feed as _feed, run_population, same_slots as _same_slots, snapshot as _snapshot, stats_row as _stats_row,
+                              stub_env as _stub_env, syn_steps)
+from learner_testlib import CAP, bits64, dev as _dev
 from stmpc_testlib import actor_settings, actor_states, bits as _bits, capi as _capi
 
-NAMES = ("w0", "b0", "w1", "b1")
-Q_SLOTS = ("q", "q_target", "q_m", "q_v")
 SEEDS = (11, 12, 13)
-GAMMA, LR = (0.999, 0.95, 0.9), (2e-4, 1e-3, 5e-4)
-DOUBLE, PERIOD = (True, False, True), (1, 3, 5)
-SUPPORT = ((-10.0, 10.0), (-4.0, 4.0), (-2.0, 6.0))
 REPLAY_START = (0, 48, CAP - 1)                # (199 is the largest a ring of 200 allows)
 EPS = (0.0, 0.3, 1.0)
 CASES = [pytest.param((20, 16, 5, 17, 7), id="20-16-5-K17-B7"), pytest.param((20, 48, 20, 51, 33), id="20-48-20-K51-B33-accel"),
          pytest.param((20, 256, 5, 51, 50), id="20-256-5-K51-B50")]
-_cache = {}
-
-
-def _snapshot(gpu_ctx, L, stats):
-    sd = L.state_dict()
-    return {"params": sd["params"], "counters": sd["counters"], "ring": gpu_ctx.c51_pop_replay_read(L.handle, 0, L.cfg.capacity), "stats": stats}
-
-
-def _stats_row(s, m=None):
-    return [float(s[k] if m is None else s[k][m]) for k in ("loss", "mean_q", "fill", "updates")]
-
-
-def _same_slots(a, b, slots=Q_SLOTS):
-    return all(np.array_equal(_bits(a[s][k]), _bits(b[s][k])) for s in slots for k in NAMES)
-
-
-def _assert_same(a, b, label):
-    """Two snapshots: all four slots, the beta powers, the counters, the ring and the statistics row, bit for bit."""
-    for slot in Q_SLOTS:
-        for k in NAMES:
-            assert np.array_equal(_bits(a["params"][slot][k]), _bits(b["params"][slot][k])), (label, slot, k)
-    assert np.array_equal(_bits(a["params"]["beta_pow"]), _bits(b["params"]["beta_pow"])) and a["params"]["beta_pow"].shape == (2,), (label, "beta_pow")
-    assert np.array_equal(a["counters"], b["counters"]), (label, a["counters"], b["counters"])
-    assert np.array_equal(_bits(a["ring"]), _bits(b["ring"])), (label, "ring")
-    assert np.array_equal(bits64(a["stats"]), bits64(b["stats"])), (label, a["stats"], b["stats"])
 
 
 # ---- 1: a population on a real env next to lone learners on its slices ----------------------------------------------------------------------------
-def _cfgs(shape, P, replay_start=REPLAY_START):
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, A, K, B = shape
-    return [learner.C51Config(n_obs=n_obs, h1=h1, batch=B, capacity=CAP, replay_start=replay_start[m], gamma=GAMMA[m], lr=LR[m], target_period=PERIOD[m],
-                              double=DOUBLE[m], n_atoms=K, v_min=SUPPORT[m][0], v_max=SUPPORT[m][1]) for m in range(P)]
-
-
-def _run(gpu_ctx, shape, P, steps=STEPS):
-    """``steps`` steps of act -> env.step -> push -> update(1) of a population of P on one env of P * N_PER and of the same learners as lone
-    C51Learners on their slices, fed the same transitions.  Returns the members' snapshots (the population's)."""
-    import torch
-    import rl_mpc_lanemerging_amd as pkg
-    from rl_mpc_lanemerging_amd import learner, vec_env
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    n, A = N_PER, shape[2]
-    env = vec_env.MergeVecEnv(P * n, env_id="sumo-jerk-v0" if A == 5 else "sumo-accel-v0", seed=7, ctx=gpu_ctx)
-    pop = learner.C51Population(env, _cfgs(shape, P), seeds=list(SEEDS[:P]))
-    assert gpu_ctx.c51_pop_size(pop.handle) == P == len(pop) and all(c.n_actions == A for c in pop.cfgs)
-    assert all(isinstance(pop.member(m), learner.C51Learner) and pop.member(m).env_id == env.env_id for m in range(P))
-    assert all(np.array_equal(pop.member(m).action_values, np.array(env.cfg._actions, dtype=np.float64)) for m in range(P))
-    lone = [learner.C51Learner(env, c, seed=SEEDS[m]) for m, c in enumerate(_cfgs(shape, P))]
-    sl = [slice(m * n, (m + 1) * n) for m in range(P)]
-    lr, eps = list(LR[:P]), list(EPS[:P])
-    obs = env.reset()
-    for i in range(steps):
-        action = pop.act(obs, None, eps=eps).clone()
-        assert action.dtype == torch.int32 and action.shape == (P * n,)
-        a_lone = torch.cat([lone[m].act(obs[sl[m]], None, eps=eps[m]) for m in range(P)])
-        assert torch.equal(action, a_lone), "actions of step %d" % i                  # before the env sees them
-        nobs, r, term, trunc, info = env.step(action)
-        fin = info["final_observation"]
-        pop.push(obs, None, action, r, nobs, term, trunc, final_obs=fin)
-        pop.update(1, lr=lr)
-        for m, L in enumerate(lone):
-            L.push(obs[sl[m]], None, action[sl[m]].contiguous(), r[sl[m]], nobs[sl[m]], term[sl[m]], trunc[sl[m]], final_obs=fin[sl[m]])
-            L.update(1, lr=lr[m])
-        obs = nobs
-        # the gate is per member: updates done so far = the pushes after which MORE than replay_start frames were in
-        want = [sum(1 for j in range(1, i + 2) if n * j > REPLAY_START[m]) for m in range(P)]
-        have = pop.stats()["updates"]
-        assert list(have) == want, (i, list(have), want)
-    torch.cuda.synchronize()
-    env.check_error()
-    ps = pop.stats()
-    assert set(ps) == {"loss", "mean_q", "fill", "updates"} and all(len(v) == P for v in ps.values())
-    assert pop.stats_device().shape == (P, 4) and pop.stats_device().dtype == torch.float64
-    snaps = [_snapshot(gpu_ctx, pop.member(m), _stats_row(ps, m)) for m in range(P)]
-    for m, L in enumerate(lone):
-        _assert_same(snaps[m], _snapshot(gpu_ctx, L, _stats_row(L.stats())), "member %d vs alone" % m)
-    gpu_ctx.check_error()
-    return snaps
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", CASES)
 def test_gpu_population_equals_its_members_run_alone(shape, gpu_ctx, restore_settings):
     """P = 3, n = 24 (no multiple of the 16-row acting tile), capacity 200 (every ring wraps), members that differ in seed, gamma, lr, double
     (True, False, True), target_period (1, 3, 5), replay_start (0, 48, 199), support ([-10, 10], [-4, 4], [-2, 6]) and eps (0.0, 0.3, 1.0)."""
     _capi()
-    snaps = _run(gpu_ctx, shape, 3)
-    n = N_PER
-    for m in range(3):
-        c = snaps[m]["counters"]
-        assert (c[0], c[1], c[4]) == ((n * STEPS) % CAP, CAP, n * STEPS)              # every ring wrapped
-    assert [int(s["counters"][2]) for s in snaps] == [12, 10, 4] == [int(s["params"]["updates"]) for s in snaps]
-    assert [int(s["counters"][3]) for s in snaps] == [0, 12, 12]                      # eps = 0 is no exploring call: member 0's acting counter stays
-    for m, s in enumerate(snaps):                                   # the hard copy follows the member's own count and period
-        synced = all(np.array_equal(_bits(s["params"]["q_target"][k]), _bits(s["params"]["q"][k])) for k in NAMES)
-        assert synced == (int(s["counters"][2]) % PERIOD[m] == 0), (m, synced)
-        assert np.isfinite(s["stats"]).all() and all(np.isfinite(s["params"][slot][k]).all() for slot in Q_SLOTS for k in NAMES)
-        assert all(np.abs(s["params"]["q_m"][k]).max() > 0 for k in NAMES), m
-    assert not np.array_equal(snaps[0]["ring"], snaps[1]["ring"]) and not np.array_equal(snaps[0]["params"]["q"]["w1"], snaps[2]["params"]["q"]["w1"])
-    # Adam stepped once per update: the beta powers, float32 running products of 0.9, say so
-    assert [round(float(np.log(s["params"]["beta_pow"][0]) / np.log(np.float32(0.9)))) for s in snaps] == [12, 10, 4]
+    assert_population_run(run_population(gpu_ctx, HEAD, shape, 3, seeds=SEEDS, eps=EPS, replay_start=REPLAY_START), PERIOD)
 
 
 # ---- 2 ... 7: synthetic rings: rows pushed through a stub env ----------------------------------------------------------------------------------------
@@ -142,36 +45,13 @@ BOTH = [pytest.param(SMALL, id="20-16-5-K17-B7"), pytest.param(WIDE, id="20-48-2
 SYN_RING, SYN_N, SYN_PUSHES = 128, 24, 6       # 144 rows into 128: the rings (and the trees' leaves) wrap; 5 * 24 <= 128: n_step = 5 is legal
 
 
-def _stub_env(gpu_ctx, n, n_obs, A):
-    """What a C51 population asks of an env, without one."""
-    return types.SimpleNamespace(n=n, obs_dim=n_obs, continuous=False, ctx=gpu_ctx, action_space={"n": A}, env_id="sumo-jerk-v0",
-                                 cfg=types.SimpleNamespace(_actions=list(np.linspace(-4.75, 4.75, A))))
-
-
 def _syn_cfg(shape, m, **kw):
     """Member m's cfg of the synthetic populations (its own gamma, period, double and support); ``kw`` overrides."""
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, A, K, B = shape
-    base = dict(n_obs=n_obs, n_actions=A, h1=h1, batch=B, capacity=SYN_RING, gamma=GAMMA[m], lr=1e-3, target_period=PERIOD[m], double=DOUBLE[m], n_atoms=K,
-                v_min=SUPPORT[m][0], v_max=SUPPORT[m][1])
-    return learner.C51Config(**dict(base, **kw))
+    return HEAD.cfg(shape, m, **dict(dict(n_actions=shape[2], capacity=SYN_RING, lr=1e-3), **kw))
 
 
 def _syn_steps(shape, P=3, pushes=SYN_PUSHES):
-    """``pushes`` whole-env steps of random transitions (numpy), the same for every caller: the first P * SYN_N rows of a draw of 3 * SYN_N, so that
-    member 0's slice does not depend on P."""
-    n_obs, h1, A, K, B = shape
-    rng = np.random.default_rng(77)
-    N = 3 * SYN_N
-    steps = [{"obs": rng.normal(size=(N, n_obs)).astype(np.float32), "next_obs": rng.normal(size=(N, n_obs)).astype(np.float32),
-              "action": rng.integers(0, A, N).astype(np.int32), "reward": rng.normal(size=N) * 2, "terminated": rng.random(N) < 0.2,
-              "truncated": rng.random(N) < 0.1} for _ in range(pushes)]
-    return [{k: v[:P * SYN_N] for k, v in s.items()} for s in steps]
-
-
-def _feed(L, step, rows=slice(None)):
-    L.push(_dev(step["obs"][rows]), None, _dev(step["action"][rows]), _dev(step["reward"][rows]), _dev(step["next_obs"][rows]), _dev(step["terminated"][rows]),
-           _dev(step["truncated"][rows]))
+    return syn_steps(HEAD, shape, P, pushes, SYN_N, draw_all=True)
 
 
 def _syn_pop(gpu_ctx, shape, cfgs, steps, per=None, seeds=SEEDS):
@@ -216,7 +96,7 @@ def test_gpu_a_members_bits_do_not_depend_on_the_others(shape, gpu_ctx, restore_
         steps = _syn_steps(shape, P)
         pop = _syn_pop(gpu_ctx, shape, [subject()] + others, [], seeds=seeds)
         acts = _act_push_update(pop, steps, eps)
-        runs.append(([a[:SYN_N] for a in acts], _snapshot(gpu_ctx, pop.member(0), _stats_row(pop.stats(), 0)),
+        runs.append(([a[:SYN_N] for a in acts], _snapshot(gpu_ctx, HEAD, pop.member(0), _stats_row(pop.stats(), 0)),
                      pop.member(1).state_dict()["params"]["q"]["w1"] if P > 1 else None))
     (a0, s0, o0), (a1, s1, o1), (a2, s2, _) = runs
     assert int(s0["counters"][2]) == 4 and int(s0["counters"][3]) == SYN_PUSHES       # 24 j > 48 from the third push on; every call explored
@@ -287,10 +167,10 @@ def test_gpu_prioritised_members(shape, gpu_ctx, restore_settings):
                 assert (len(set(a["weight"].tolist())) > 1) == (len(set(leaf.tolist())) > 1) and a["weight"].max() == 1.0, (u, leaf, a["weight"])
                 mixed += len(set(leaf.tolist())) > 1
             assert np.array_equal(a["idx"], b["idx"]) and np.array_equal(_bits(a["td"]), _bits(b["td"])) and np.array_equal(_bits(a["weight"]), _bits(b["weight"])), (m, u)
-            _assert_same(_snapshot(gpu_ctx, M, _stats_row(pop.stats(), m)), _snapshot(gpu_ctx, L, _stats_row(L.stats())), "prioritised member %d, update %d" % (m, u))
+            _assert_same(_snapshot(gpu_ctx, HEAD, M, _stats_row(pop.stats(), m)), _snapshot(gpu_ctx, HEAD, L, _stats_row(L.stats())), "prioritised member %d, update %d" % (m, u))
     # a minibatch that mixes rows with a priority of their own and fresh ones: certain in practice once 33 of 128 rows were visited, not with 7
     assert mixed >= 1 or shape[4] < 33, mixed
-    _assert_same(_snapshot(gpu_ctx, pop.member(1), _stats_row(pop.stats(), 1)), _snapshot(gpu_ctx, plain.member(1), _stats_row(plain.stats(), 1)), "the uniform member")
+    _assert_same(_snapshot(gpu_ctx, HEAD, pop.member(1), _stats_row(pop.stats(), 1)), _snapshot(gpu_ctx, HEAD, plain.member(1), _stats_row(plain.stats(), 1)), "the uniform member")
     assert not _same_slots(pop.member(0).state_dict()["params"], plain.member(0).state_dict()["params"])      # prioritised sampling draws other rows
     assert list(pop.stats()["updates"]) == [4, 4, 4]
     with pytest.raises(RuntimeError, match="not enabled"):
@@ -350,7 +230,7 @@ def test_gpu_n_step_per_member(shape, gpu_ctx, restore_settings):
         pop.update(1)
         for m, L in enumerate(lone):
             L.update(1)
-            _assert_same(_snapshot(gpu_ctx, pop.member(m), _stats_row(pop.stats(), m)), _snapshot(gpu_ctx, L, _stats_row(L.stats())), "n_step %d, update %d" % (NS[m], u))
+            _assert_same(_snapshot(gpu_ctx, HEAD, pop.member(m), _stats_row(pop.stats(), m)), _snapshot(gpu_ctx, HEAD, L, _stats_row(L.stats())), "n_step %d, update %d" % (NS[m], u))
     assert {k for mm, k in seen_m if mm == 0} == {1} and max(k for mm, k in seen_m if mm == 1) <= 3 and len({k for mm, k in seen_m if mm == 2}) >= 2
     with pytest.raises(capi.StmpcError, match="member of a population.*stmpc_pop_c51_multi_step_enable"):
         gpu_ctx.nstep_enable("c51", pop.member(0).handle, mk(2).to_c_nstep(SYN_N))

@@ -11,85 +11,27 @@ import types
 import numpy as np
 import pytest
 
-from c51actor_testlib import NAMES, NEGATIVE_SUPPORT, ROWS, SHAPES, SUPPORT, compose_first_step, config as _config, net as _net, table as _table, zero_head
+from discrete_testlib import (C51_ACTOR_SHAPES as SHAPES, NAMES, NEGATIVE_SUPPORT, ROWS, SENTINEL, SUPPORT, act_on_features as _act, actor_table as _table,
+                              c51_actor_config as _config, c51_actor_net as _net, compose_first_step, dev as _dev, episode_settings as _episode_settings,
+                              plain_policy as _plain_policy, policy_features as _features, policy_states as _states, run_policy as _run, stream as _stream,
+                              transitions as _transitions, widen as _widen, zero_head)
 from env_testlib import settings as _env_settings
 from learner_testlib import bound_4x, check_4x, record, rel_err
-from stmpc_testlib import ACTOR_KMAX, actor_settings, actor_states, capi as _capi, same
-
-SENTINEL, TAIL = -7.0, 3          # every output buffer has TAIL rows beyond N, filled with the sentinel
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _states(n):
-    g, S = actor_settings()
-    st = actor_states(g, _dev())
-    return S, {k: v[:n].contiguous() for k, v in st.items()}
+from stmpc_testlib import ACTOR_KMAX, capi as _capi, same
 
 
 def _learner(gpu_ctx, shape, seed=5, support=SUPPORT, init=None, target_period=4, updates=1, env=None):
     """A C51 learner whose online and target networks differ: 32 random transitions, then ``updates`` updates (< target_period: no hard copy)."""
     from rl_mpc_lanemerging_amd import learner
-    import torch
     n_in, h1, A, K = shape
     L = learner.C51Learner(env if env is not None else (n_in, A), _config(shape, support, target_period=target_period), seed=seed,
                            init=init if init is not None else _net(shape, seed), ctx=gpu_ctx)
     if env is None:
         L.action_values = _table(A)
-    rng = np.random.default_rng(seed)
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=_dev())
-    L.push(t(rng.normal(0, 1, (32, n_in)).astype(np.float32)), None, t(rng.integers(0, A, 32).astype(np.int32)), t(rng.normal(0, 1, 32)),
-           t(rng.normal(0, 1, (32, n_in)).astype(np.float32)), t(rng.random(32) < 0.2), t(np.zeros(32, bool)))
+    L.push(*_transitions(np.random.default_rng(seed), 32, n_in, A))
     if updates:
         L.update(updates)
     return L
-
-
-def _widen(P):
-    import torch
-    rows = P.n + TAIL
-    P.feat = torch.full((rows, P.flen), SENTINEL, dtype=torch.float32, device=_dev())
-    P.q = torch.full((rows, P.shape[2]), SENTINEL, dtype=torch.float32, device=_dev())
-    P.action = torch.full((rows,), int(SENTINEL), dtype=torch.int32, device=_dev())
-    P.jerk = torch.full((rows,), SENTINEL, dtype=torch.float64, device=_dev())
-    P.keep_features = P.keep_q = True
-    return P
-
-
-def _run(P, st, step=1):
-    """One evaluation; numpy copies of the n evaluated rows, after the check that the rows beyond them kept the sentinel in every output."""
-    import torch
-    P(step, st["ego4"], st["k"], st["ox"], st["ov"], st["oa"])
-    torch.cuda.synchronize()
-    out = {k: getattr(P, k).cpu().numpy().copy() for k in ("feat", "q", "action", "jerk")}
-    for k, v in out.items():
-        assert v.shape[0] == P.n + TAIL and (v[P.n:] == SENTINEL).all(), k
-    return {k: v[:P.n] for k, v in out.items()}
-
-
-def _features(gpu_ctx, fcfg, st, n, flen):
-    import torch
-    feat = torch.full((n, flen), SENTINEL, dtype=torch.float32, device=_dev())
-    gpu_ctx.policy_features_device(fcfg, n, st["ox"].shape[1], 1, st["ego4"].data_ptr(), st["k"].data_ptr(), st["ox"].data_ptr(), st["ov"].data_ptr(),
-                                   st["oa"].data_ptr(), 0, feat.data_ptr(), flen, _stream())
-    return feat
-
-
-def _act(L, feat):
-    """(index int32 [n], expected values float32 [n][A]) of ``C51Learner.act`` on input vectors, as numpy."""
-    import torch
-    q = torch.full((feat.shape[0], L.cfg.n_actions), SENTINEL, dtype=torch.float32, device=_dev())
-    a = L.act(feat, eps=0.0, debug_q=q)
-    torch.cuda.synchronize()
-    return a.cpu().numpy().copy(), q.cpu().numpy()
 
 
 @pytest.mark.gpu
@@ -252,31 +194,6 @@ def test_gpu_view_is_live_and_leaves_the_learner_alone(gpu_ctx, restore_settings
     assert same(second["q"], q) and same(second["action"], act) and same(second["jerk"], L.action_values[act])
     assert same(second["feat"], first["feat"]) and not np.array_equal(second["q"], first["q"])
     gpu_ctx.check_error()
-
-
-def _episode_settings():
-    import rl_mpc_lanemerging_amd as pkg
-    from rl_mpc_lanemerging_amd import combined_bench
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
-    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1_TRAFFIC)
-    return pkg.Settings
-
-
-def _plain_policy(gpu_ctx, L, S, n):
-    """A plain callable with the policy signature from the public entries: features, C51Learner.act, the table."""
-    import torch
-    capi = _capi()
-    fcfg = capi.FeaturesCfg.from_settings(S, time_feature=False)
-    flen = L.cfg.n_obs
-    table = torch.as_tensor(L.action_values, device=_dev())
-    feat = torch.empty(n, flen, dtype=torch.float32, device=_dev())
-
-    def policy(step, cur_ego4, k, cur_ox, cur_ov, cur_oa):
-        gpu_ctx.policy_features_device(fcfg, n, cur_ox.shape[1], step, cur_ego4.data_ptr(), k.data_ptr(), cur_ox.data_ptr(), cur_ov.data_ptr(), cur_oa.data_ptr(), 0,
-                                       feat.data_ptr(), flen, _stream())
-        return table[L.act(feat, eps=0.0).long()]
-    return policy
 
 
 @pytest.mark.gpu

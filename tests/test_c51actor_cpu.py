@@ -8,8 +8,8 @@ import types
 import numpy as np
 import pytest
 
-from c51actor_testlib import (NEGATIVE_SUPPORT, SHAPES, SUPPORT, TWIN_ROWS, TWIN_SEED, NoLibrary, c51_actor_stub, c51_learner_stub, export_file, net as _net,
-                              table as _table, zero_head)
+from discrete_testlib import (C51_ACTOR_SHAPES as SHAPES, NEGATIVE_SUPPORT, SUPPORT, TWIN_ROWS, TWIN_SEED, NoLibrary, actor_table as _table, c51_actor_net as _net,
+                              c51_actor_stub, c51_learner_stub, export_file, zero_head)
 from stmpc_testlib import capi as _capi, header_entries, header_prototypes, header_text
 
 ENTRIES = {"stmpc_c51actor_create", "stmpc_c51actor_view"}

@@ -15,34 +15,13 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from discrete_testlib import (DQN as HEAD, GRAD_SHAPES as _GRAD_SHAPES, NAMES, Q_SLOTS, RING, SHAPES as _SHAPES, fill as _fill, make_learner as _learner,
+                              minibatch_host as _minibatch_host, pad_mask as _pad_mask, pads_are_zero as _pads_are_zero, random_problem as _random_problem, rows_of as _rows,
+                              twins as _twins)
 from learner_testlib import bits_equal, check_4x as _check_4x
 from stmpc_testlib import capi as _capi
 
-SHAPES = [(20, 16, 5, 7), (20, 48, 20, 33), (20, 256, 5, 50), (12, 32, 17, 16)]
-NAMES = ("w0", "b0", "w1", "b1")
-Q_SLOTS = ("q", "q_target", "q_m", "q_v")
-RING = 128
-
-
-def _fill(L, replay):
-    """Push the replay dict's rows (s, a, r, s2, term), 64 at a time."""
-    import torch
-    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")
-    R = replay["s"].shape[0]
-    for o in range(0, R, 64):
-        sl = slice(o, min(R, o + 64))
-        term = replay["term"][sl]
-        L.push(dev(replay["s"][sl].astype(np.float32)), None, dev(replay["a"][sl].astype(np.int32)), dev(replay["r"][sl].astype(np.float64)),
-               dev(replay["s2"][sl].astype(np.float32)), dev(term), dev(np.zeros_like(term)))
-
-
-def _rows(replay, n_obs):
-    capi = _capi()
-    R = replay["s"].shape[0]
-    rows = np.zeros((R, capi.DDPG_ROW), dtype=np.float32)
-    rows[:, :n_obs], rows[:, 32:32 + n_obs] = replay["s"], replay["s2"]
-    rows[:, 64], rows[:, 65], rows[:, capi.DQN_ACTION_COL] = replay["r"], np.where(replay["term"], 0, 1), replay["a"]
-    return rows
+SHAPES, GRAD_SHAPES = _SHAPES["dqn"], _GRAD_SHAPES["dqn"]      # tests/discrete_testlib.py's tables
 
 
 def dyadic_problem(shape, double, clip, seed=0):
@@ -63,21 +42,6 @@ def dyadic_problem(shape, double, clip, seed=0):
     return cfg, params, replay
 
 
-def _learner(gpu_ctx, cfg, params, replay=None, seed=11):
-    from rl_mpc_lanemerging_amd import learner
-    L = learner.DQNLearner((cfg.n_obs, cfg.n_actions), cfg, seed=seed, init=params["q"], ctx=gpu_ctx)
-    L.load_state_dict({"params": params, "counters": None})
-    if replay is not None:
-        _fill(L, replay)
-    return L
-
-
-def _minibatch_host(replay, cfg, seed=11, update=0):
-    from rl_mpc_lanemerging_amd import learner
-    rows = _rows(replay, cfg.n_obs)[learner.sample_indices_host(seed, update, cfg.batch, replay["s"].shape[0])]
-    return rows, learner.dqn_batch_from_rows(rows, cfg.n_obs)
-
-
 # ---- 1: targets -----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("double,clip", [(True, False), (True, True), (False, False), (False, True)])
@@ -89,11 +53,10 @@ def test_gpu_dyadic_targets_are_exact(shape, double, clip, gpu_ctx, restore_sett
     from rl_mpc_lanemerging_amd import learner
     n_obs, h1, A, B = shape
     cfg, params, replay = dyadic_problem(shape, double, clip)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     rows, batch = _minibatch_host(replay, cfg)
     assert L.stats()["fill"] == RING and np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
-    _, i64 = learner.update_host_dqn(params, batch, cfg, "float64", grads_only=True)
-    _, i32 = learner.update_host_dqn(params, batch, cfg, "float32", grads_only=True)
+    i64, i32 = _twins(HEAD, params, batch, cfg)
     import torch
     with torch.no_grad():
         T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
@@ -124,9 +87,6 @@ def test_gpu_dyadic_targets_are_exact(shape, double, clip, gpu_ctx, restore_sett
     gpu_ctx.check_error()
 
 
-GRAD_SHAPES = [(20, 16, 5, 8), (20, 48, 20, 32), (20, 256, 5, 64), (12, 32, 17, 16)]      # SHAPES' networks at a power-of-two B each
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("double,clip", [(True, False), (True, True), (False, False), (False, True)])
 @pytest.mark.parametrize("shape", GRAD_SHAPES)
@@ -138,7 +98,7 @@ def test_gpu_dyadic_gradients_are_exact(shape, double, clip, gpu_ctx, restore_se
     from rl_mpc_lanemerging_amd import learner
     n_obs, h1, A, B = shape
     cfg, params, replay = dyadic_problem(shape, double, clip, seed=2)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     rows, batch = _minibatch_host(replay, cfg)
     assert np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
     _, i64 = learner.update_host_dqn(params, batch, cfg, "float64", grads_only=True)
@@ -153,14 +113,6 @@ def test_gpu_dyadic_gradients_are_exact(shape, double, clip, gpu_ctx, restore_se
     gpu_ctx.check_error()
 
 
-def _pad_mask(n_obs, h1, A):
-    """True at the pad entries of a padded slot {w0 [h1p][32], b0 [h1p], w1 [Ap][h1p], b1 [Ap]}."""
-    h1p, Ap = (h1 + 15) & ~15, (A + 15) & ~15
-    m = {"w0": np.ones((h1p, 32), bool), "b0": np.ones(h1p, bool), "w1": np.ones((Ap, h1p), bool), "b1": np.ones(Ap, bool)}
-    m["w0"][:h1, :n_obs], m["b0"][:h1], m["w1"][:A, :h1], m["b1"][:A] = False, False, False, False
-    return m
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", SHAPES)
 def test_gpu_pad_entries_stay_zero(shape, gpu_ctx, restore_settings):
@@ -170,26 +122,18 @@ def test_gpu_pad_entries_stay_zero(shape, gpu_ctx, restore_settings):
     and bias is reached)."""
     capi = _capi()
     n_obs, h1, A, B = shape
-    cfg, params, replay = _random_problem(shape, 61, target_period=2)
-    L = _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = _random_problem(HEAD, shape, 61, target_period=2)
+    L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     pad = _pad_mask(n_obs, h1, A)
     read = lambda slot: gpu_ctx.dqn_padded_read(L.handle, slot, h1, A)
-
-    def check(slots, tag):
-        for slot in slots:
-            arr = read(slot)
-            for k in NAMES:
-                assert arr[k].shape == pad[k].shape and not arr[k][pad[k]].any(), (tag, slot, k, int(np.count_nonzero(arr[k][pad[k]])))
-                assert np.isfinite(arr[k]).all()
-
     g = L.grads()
-    check([capi.DQN_GRAD], "grads")
+    _pads_are_zero(gpu_ctx, HEAD, L, [capi.DQN_GRAD], pad, "grads")
     have = read(capi.DQN_GRAD)
     assert all(np.array_equal(have[k][~pad[k]].reshape(g[k].shape), g[k]) for k in NAMES)
     assert (np.abs(g["w0"]).max(0) > 0).all() and np.abs(g["b0"]).max() > 0 and np.abs(g["b1"]).max() > 0
     for u in range(4):
         L.update(1)
-        check(range(5), "update %d" % u)
+        _pads_are_zero(gpu_ctx, HEAD, L, range(5), pad, "update %d" % u)
     sd = L.state_dict()["params"]
     for i, slot in enumerate(capi.DQN_SLOTS):
         arr = read(i)
@@ -206,8 +150,8 @@ def test_gpu_act_reads_only_the_observation_columns(gpu_ctx, restore_settings):
     _capi()
     import torch
     n_obs, h1, A, B = SHAPES[3]
-    cfg, params, replay = _random_problem(SHAPES[3], 62)
-    L = _learner(gpu_ctx, cfg, params)
+    cfg, params, replay = _random_problem(HEAD, SHAPES[3], 62)
+    L = _learner(gpu_ctx, HEAD, cfg, params)
     wide = torch.full((40, 32), 1e30, dtype=torch.float32, device="cuda")
     obs = torch.as_tensor(replay["s"][:40].astype(np.float32), device="cuda")
     wide[:, :n_obs] = obs
@@ -256,11 +200,10 @@ def test_gpu_gradients_against_the_float64_twin(shape, gpu_ctx, restore_settings
     net = lambda: {"w0": nrm(n_obs, h1, n_obs), "b0": nrm(n_obs, h1), "w1": nrm(h1, A, h1), "b1": nrm(h1, A)}
     params = learner.new_params_dqn(net())
     params["q_target"] = net()
-    L = _learner(gpu_ctx, cfg, params, rep)
+    L = _learner(gpu_ctx, HEAD, cfg, params, rep)
     rows, batch = _minibatch_host(rep, cfg)
     assert np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
-    _, i64 = learner.update_host_dqn(params, batch, cfg, "float64", grads_only=True)
-    _, i32 = learner.update_host_dqn(params, batch, cfg, "float32", grads_only=True)
+    i64, i32 = _twins(HEAD, params, batch, cfg)
     t, g = L.targets(), L.grads()
     assert np.array_equal(t[:, 0].astype(np.int64), i64["targets"][:, 0].astype(np.int64))
     ok = _check_4x("%s y" % (shape,), t[:, 2], i32["targets"][:, 2], i64["targets"][:, 2])
@@ -333,18 +276,6 @@ def test_gpu_library_refusals(gpu_ctx):
 
 
 # ---- 4: updates --------------------------------------------------------------------------------------------------------------------------------
-def _random_problem(shape, seed, **kw):
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, A, B = shape
-    rng = np.random.default_rng(seed)
-    params = learner.new_params_dqn(learner.init_q_net(n_obs, h1, A, rng))
-    params["q_target"] = learner.init_q_net(n_obs, h1, A, rng)
-    replay = {"s": rng.normal(size=(RING, n_obs)).astype(np.float32), "s2": rng.normal(size=(RING, n_obs)).astype(np.float32), "a": rng.integers(0, A, RING),
-              "r": rng.normal(size=RING) * 2, "term": rng.random(RING) < 0.2}
-    cfg = learner.DQNConfig(n_obs=n_obs, n_actions=A, h1=h1, batch=B, capacity=RING, lr=1e-3, **kw)
-    return cfg, params, replay
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[3]])
 def test_gpu_target_schedule_and_gate(shape, gpu_ctx, restore_settings):
@@ -352,8 +283,8 @@ def test_gpu_target_schedule_and_gate(shape, gpu_ctx, restore_settings):
     moves before replay_start; after each update Adam's state and the weights equal the float32 twin stepped with the device's own gradients."""
     _capi()
     from rl_mpc_lanemerging_amd import learner
-    cfg, params, replay = _random_problem(shape, 31, target_period=3, replay_start=64)
-    L = _learner(gpu_ctx, cfg, params)
+    cfg, params, replay = _random_problem(HEAD, shape, 31, target_period=3, replay_start=64)
+    L = _learner(gpu_ctx, HEAD, cfg, params)
     _fill(L, {k: v[:64] for k, v in replay.items()})                # 64 frames: not MORE than replay_start
     L.update(2)
     sd = L.state_dict()
@@ -381,8 +312,8 @@ def test_gpu_updates_are_reproducible(per, gpu_ctx, restore_settings):
     _capi()
     from rl_mpc_lanemerging_amd import learner
     kw = dict(per=learner.PERConfig(beta=0.4)) if per else {}
-    cfg, params, replay = _random_problem(SHAPES[1], 41, target_period=4, **kw)
-    A_, B_ = _learner(gpu_ctx, cfg, params, replay), _learner(gpu_ctx, cfg, params, replay)
+    cfg, params, replay = _random_problem(HEAD, SHAPES[1], 41, target_period=4, **kw)
+    A_, B_ = _learner(gpu_ctx, HEAD, cfg, params, replay), _learner(gpu_ctx, HEAD, cfg, params, replay)
     A_.update(10)
     B_.update(4)
     mid = B_.state_dict()
@@ -391,7 +322,7 @@ def test_gpu_updates_are_reproducible(per, gpu_ctx, restore_settings):
     assert bits_equal(sa["params"], sb["params"], Q_SLOTS, NAMES) and np.array_equal(sa["counters"], sb["counters"]) and np.array_equal(sa["params"]["beta_pow"], sb["params"]["beta_pow"])
     assert A_.stats() == B_.stats() and sa["params"]["updates"] == 10
     if not per:                                                     # (a tree is not part of a state_dict: a fresh learner's would be the pushes')
-        C_ = _learner(gpu_ctx, cfg, params, replay)
+        C_ = _learner(gpu_ctx, HEAD, cfg, params, replay)
         C_.load_state_dict(mid)
         C_.update(6)
         sc = C_.state_dict()
@@ -407,9 +338,9 @@ def test_gpu_prioritised_replay(gpu_ctx, restore_settings):
     from rl_mpc_lanemerging_amd import learner
     per = learner.PERConfig(beta=0.5)
     shape = SHAPES[1]
-    cfg, params, replay = _random_problem(shape, 51, per=per)
-    cfg0, _, _ = _random_problem(shape, 51)
-    L, U = _learner(gpu_ctx, cfg, params, replay), _learner(gpu_ctx, cfg0, params, replay)
+    cfg, params, replay = _random_problem(HEAD, shape, 51, per=per)
+    cfg0, _, _ = _random_problem(HEAD, shape, 51)
+    L, U = _learner(gpu_ctx, HEAD, cfg, params, replay), _learner(gpu_ctx, HEAD, cfg0, params, replay)
     host = learner.SumTreeHost(RING, per)
     host.push(RING)
     tree = L.priorities()

@@ -10,102 +10,25 @@ The gate in test 1.  A learner's ``replay_start`` must lie below its capacity, a
 step.  With capacity 200 (so that every ring wraps) and 12 steps of 24 frames member 2 has the largest legal one, 199: its gate is shut during steps
 1 ... 8 and opens at step 9, so the update counts are 12, 10 and 4.  A gate that stays shut THROUGHOUT is test 3's.
 """
-import types
-
 import numpy as np
 import pytest
 
+from discrete_testlib import (DQN as HEAD, LR, NAMES, PERIOD, Q_SLOTS, assert_population_run, assert_same as _assert_same, feed as _feed, run_population,
+                              same_slots as _same_slots, snapshot as _snapshot, stats_row as _stats_row, stub_env as _stub_env, syn_steps)
 from learner_testlib import CAP, N_PER, STEPS, bits64, dev as _dev
 from stmpc_testlib import actor_settings, actor_states, bits as _bits, capi as _capi
 
-NAMES = ("w0", "b0", "w1", "b1")
-Q_SLOTS = ("q", "q_target", "q_m", "q_v")
 SEEDS = (11, 12, 13)
-GAMMA, LR = (0.999, 0.95, 0.9), (2e-4, 1e-3, 5e-4)
-DOUBLE, CLIP, PERIOD = (True, False, True), (False, True, False), (1, 3, 5)
 REPLAY_START = (0, 48, CAP - 1)                # (module text: 199 is the largest a ring of 200 allows)
 EPS = (0.0, 0.3, 1.0)
 CASES = [pytest.param((20, 16, 5, 7), id="20-16-5-B7"), pytest.param((20, 48, 20, 33), id="20-48-20-B33-accel"), pytest.param((20, 256, 5, 50), id="20-256-5-B50")]
 _cache = {}
 
 
-def _snapshot(gpu_ctx, L, stats):
-    sd = L.state_dict()
-    return {"params": sd["params"], "counters": sd["counters"], "ring": gpu_ctx.dqn_pop_replay_read(L.handle, 0, L.cfg.capacity), "stats": stats}
-
-
-def _stats_row(s, m=None):
-    return [float(s[k] if m is None else s[k][m]) for k in ("loss", "mean_q", "fill", "updates")]
-
-
-def _same_slots(a, b, slots=Q_SLOTS):
-    return all(np.array_equal(_bits(a[s][k]), _bits(b[s][k])) for s in slots for k in NAMES)
-
-
-def _assert_same(a, b, label):
-    """Two snapshots: all four slots, the beta powers, the counters, the ring and the statistics row, bit for bit."""
-    for slot in Q_SLOTS:
-        for k in NAMES:
-            assert np.array_equal(_bits(a["params"][slot][k]), _bits(b["params"][slot][k])), (label, slot, k)
-    assert np.array_equal(_bits(a["params"]["beta_pow"]), _bits(b["params"]["beta_pow"])) and a["params"]["beta_pow"].shape == (2,), (label, "beta_pow")
-    assert np.array_equal(a["counters"], b["counters"]), (label, a["counters"], b["counters"])
-    assert np.array_equal(_bits(a["ring"]), _bits(b["ring"])), (label, "ring")
-    assert np.array_equal(bits64(a["stats"]), bits64(b["stats"])), (label, a["stats"], b["stats"])
-
-
 # ---- 1, 2, 3: a population on a real env next to lone learners on its slices -----------------------------------------------------------------------------
-def _cfgs(shape, P, period=PERIOD, replay_start=REPLAY_START):
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, A, B = shape
-    return [learner.DQNConfig(n_obs=n_obs, h1=h1, batch=B, capacity=CAP, replay_start=replay_start[m], gamma=GAMMA[m], lr=LR[m], target_period=period[m],
-                              double=DOUBLE[m], clip_targets=CLIP[m], clip_min=-2.0, clip_max=1.0) for m in range(P)]
-
-
-def _run(gpu_ctx, shape, P, seeds=SEEDS, period=PERIOD, eps=EPS, replay_start=REPLAY_START, alone=True, steps=STEPS):
-    """``steps`` steps of act -> env.step -> push -> update(1) of a population of P on one env of P * N_PER and, if ``alone``, of the same learners as
-    lone DQNLearners on their slices, fed the same transitions.  Returns the members' snapshots (the population's)."""
-    import torch
-    import rl_mpc_lanemerging_amd as pkg
-    from rl_mpc_lanemerging_amd import learner, vec_env
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    n, A = N_PER, shape[2]
-    env = vec_env.MergeVecEnv(P * n, env_id="sumo-jerk-v0" if A == 5 else "sumo-accel-v0", seed=7, ctx=gpu_ctx)
-    cfgs = _cfgs(shape, P, period, replay_start)
-    pop = learner.DQNPopulation(env, cfgs, seeds=list(seeds[:P]))
-    assert gpu_ctx.dqn_pop_size(pop.handle) == P == len(pop) and all(c.n_actions == A for c in cfgs)
-    assert all(np.array_equal(pop.member(m).action_values, np.array(env.cfg._actions, dtype=np.float64)) and pop.member(m).env_id == env.env_id for m in range(P))
-    lone = [learner.DQNLearner(env, cfgs[m], seed=seeds[m]) for m in range(P)] if alone else []
-    sl = [slice(m * n, (m + 1) * n) for m in range(P)]
-    lr, eps = list(LR[:P]), list(eps[:P])
-    obs = env.reset()
-    for i in range(steps):
-        action = pop.act(obs, None, eps=eps).clone()
-        assert action.dtype == torch.int32 and action.shape == (P * n,)
-        if alone:
-            a_lone = torch.cat([lone[m].act(obs[sl[m]], None, eps=eps[m]) for m in range(P)])
-            assert torch.equal(action, a_lone), "actions of step %d" % i              # before the env sees them
-        nobs, r, term, trunc, info = env.step(action)
-        fin = info["final_observation"]
-        pop.push(obs, None, action, r, nobs, term, trunc, final_obs=fin)
-        pop.update(1, lr=lr)
-        for m, L in enumerate(lone):
-            L.push(obs[sl[m]], None, action[sl[m]].contiguous(), r[sl[m]], nobs[sl[m]], term[sl[m]], trunc[sl[m]], final_obs=fin[sl[m]])
-            L.update(1, lr=lr[m])
-        obs = nobs
-        # the gate is per member: updates done so far = the pushes after which MORE than replay_start frames were in
-        want = [sum(1 for j in range(1, i + 2) if n * j > replay_start[m]) for m in range(P)]
-        have = pop.stats()["updates"]
-        assert list(have) == want, (i, list(have), want)
-    torch.cuda.synchronize()
-    env.check_error()
-    ps = pop.stats()
-    assert set(ps) == {"loss", "mean_q", "fill", "updates"} and all(len(v) == P for v in ps.values())
-    assert pop.stats_device().shape == (P, 4) and pop.stats_device().dtype == torch.float64
-    snaps = [_snapshot(gpu_ctx, pop.member(m), _stats_row(ps, m)) for m in range(P)]
-    for m, L in enumerate(lone):
-        _assert_same(snaps[m], _snapshot(gpu_ctx, L, _stats_row(L.stats())), "member %d vs alone" % m)
-    gpu_ctx.check_error()
-    return snaps
+def _run(gpu_ctx, shape, P, seeds=SEEDS, eps=EPS, replay_start=REPLAY_START, **kw):
+    """discrete_testlib.run_population under this module's seeds, eps and replay_start."""
+    return run_population(gpu_ctx, HEAD, shape, P, seeds=seeds, eps=eps, replay_start=replay_start, **kw)
 
 
 @pytest.mark.gpu
@@ -115,20 +38,7 @@ def test_gpu_population_equals_its_members_run_alone(shape, gpu_ctx, restore_set
     (True, False, True), clip_targets (False, True, False), target_period (1, 3, 5), replay_start (0, 48, 199) and eps (0.0, 0.3, 1.0)."""
     _capi()
     snaps = _cache[shape] = _run(gpu_ctx, shape, 3)
-    n = N_PER
-    for m in range(3):
-        c = snaps[m]["counters"]
-        assert (c[0], c[1], c[4]) == ((n * STEPS) % CAP, CAP, n * STEPS)              # every ring wrapped
-    assert [int(s["counters"][2]) for s in snaps] == [12, 10, 4] == [int(s["params"]["updates"]) for s in snaps]
-    assert [int(s["counters"][3]) for s in snaps] == [0, 12, 12]                      # eps = 0 is no exploring call: member 0's acting counter stays
-    for m, s in enumerate(snaps):                                   # the hard copy follows the member's own count and period
-        synced = all(np.array_equal(_bits(s["params"]["q_target"][k]), _bits(s["params"]["q"][k])) for k in NAMES)
-        assert synced == (int(s["counters"][2]) % PERIOD[m] == 0), (m, synced)
-        assert np.isfinite(s["stats"]).all() and all(np.isfinite(s["params"][slot][k]).all() for slot in Q_SLOTS for k in NAMES)
-        assert all(np.abs(s["params"]["q_m"][k]).max() > 0 for k in NAMES), m
-    assert not np.array_equal(snaps[0]["ring"], snaps[1]["ring"]) and not np.array_equal(snaps[0]["params"]["q"]["w1"], snaps[2]["params"]["q"]["w1"])
-    # Adam stepped once per update: the beta powers, float32 running products of 0.9, say so
-    assert [round(float(np.log(s["params"]["beta_pow"][0]) / np.log(np.float32(0.9)))) for s in snaps] == [12, 10, 4]
+    assert_population_run(snaps, PERIOD)
 
 
 @pytest.mark.gpu
@@ -137,7 +47,7 @@ def test_gpu_members_are_independent(gpu_ctx, restore_settings):
     _capi()
     shape = (20, 16, 5, 7)
     before = _cache.get(shape) or _run(gpu_ctx, shape, 3, alone=False)
-    after = _run(gpu_ctx, shape, 3, seeds=(SEEDS[0], 99, SEEDS[2]), period=(PERIOD[0], 2, PERIOD[2]), eps=(EPS[0], 0.6, EPS[2]), alone=False)
+    after = _run(gpu_ctx, shape, 3, seeds=(SEEDS[0], 99, SEEDS[2]), target_period=(PERIOD[0], 2, PERIOD[2]), eps=(EPS[0], 0.6, EPS[2]), alone=False)
     _assert_same(before[0], after[0], "member 0")
     _assert_same(before[2], after[2], "member 2")
     assert not np.array_equal(before[1]["ring"], after[1]["ring"])
@@ -158,7 +68,7 @@ def test_gpu_population_of_one_and_shut_gates(gpu_ctx, restore_settings):
     # before any push: nothing to sample, so nothing moves
     pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
     env = vec_env.MergeVecEnv(N_PER, env_id="sumo-jerk-v0", seed=7, ctx=gpu_ctx)
-    pop = learner.DQNPopulation(env, _cfgs(shape, 1), seeds=[5])
+    pop = learner.DQNPopulation(env, [HEAD.cfg(shape, 0, capacity=CAP, replay_start=REPLAY_START[0], lr=LR[0])], seeds=[5])
     first = pop.member(0).state_dict()
     pop.update(3)
     sd, st = pop.member(0).state_dict(), pop.stats()
@@ -176,32 +86,13 @@ SYN = (20, 48, 20, 16)                         # (n_obs, h1, A, B): two hidden k
 SYN_RING, SYN_N, SYN_PUSHES = 128, 32, 5       # 160 rows into 128: the rings (and the trees' leaves) wrap
 
 
-def _stub_env(gpu_ctx, n, n_obs, A):
-    """What a DQN population asks of an env, without one."""
-    return types.SimpleNamespace(n=n, obs_dim=n_obs, continuous=False, ctx=gpu_ctx, action_space={"n": A}, env_id="sumo-jerk-v0",
-                                 cfg=types.SimpleNamespace(_actions=list(np.linspace(-4.75, 4.75, A))))
-
-
 def _syn_cfgs(per=(None, None, None), **kw):
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, A, B = SYN
-    return [learner.DQNConfig(n_obs=n_obs, n_actions=A, h1=h1, batch=B, capacity=SYN_RING, gamma=GAMMA[m], lr=1e-3, target_period=PERIOD[m], double=DOUBLE[m],
-                              clip_targets=CLIP[m], clip_min=-2.0, clip_max=1.0, per=per[m], **kw) for m in range(3)]
+    A = SYN[2]
+    return [HEAD.cfg(SYN, m, n_actions=A, capacity=SYN_RING, lr=1e-3, per=per[m], **kw) for m in range(3)]
 
 
 def _syn_steps(P=3):
-    """SYN_PUSHES whole-env steps of random transitions (numpy), the same for every caller."""
-    n_obs, h1, A, B = SYN
-    rng = np.random.default_rng(77)
-    N = P * SYN_N
-    return [{"obs": rng.normal(size=(N, n_obs)).astype(np.float32), "next_obs": rng.normal(size=(N, n_obs)).astype(np.float32),
-             "action": rng.integers(0, A, N).astype(np.int32), "reward": rng.normal(size=N) * 2, "terminated": rng.random(N) < 0.2,
-             "truncated": rng.random(N) < 0.1} for _ in range(SYN_PUSHES)]
-
-
-def _feed(L, step, rows=slice(None)):
-    L.push(_dev(step["obs"][rows]), None, _dev(step["action"][rows]), _dev(step["reward"][rows]), _dev(step["next_obs"][rows]), _dev(step["terminated"][rows]),
-           _dev(step["truncated"][rows]))
+    return syn_steps(HEAD, SYN, P, SYN_PUSHES, SYN_N)
 
 
 def _syn_pop(gpu_ctx, per=None, steps=None):
@@ -245,10 +136,10 @@ def test_gpu_prioritised_members(gpu_ctx, restore_settings):
             assert np.array_equal(bits64(M.priorities()), bits64(L.priorities())), (m, u, "tree")
             a, b = M.last_sample(), L.last_sample()
             assert np.array_equal(a["idx"], b["idx"]) and np.array_equal(_bits(a["td"]), _bits(b["td"])) and np.array_equal(_bits(a["weight"]), _bits(b["weight"])), (m, u)
-            _assert_same(_snapshot(gpu_ctx, M, _stats_row(pop.stats(), m)), _snapshot(gpu_ctx, L, _stats_row(L.stats())), "prioritised member %d, update %d" % (m, u))
+            _assert_same(_snapshot(gpu_ctx, HEAD, M, _stats_row(pop.stats(), m)), _snapshot(gpu_ctx, HEAD, L, _stats_row(L.stats())), "prioritised member %d, update %d" % (m, u))
     w = pop.member(2).last_sample()["weight"]
     assert len(set(w.tolist())) > 1 and w.max() == 1.0              # beta = 0.4: the importance weights reached the loss
-    _assert_same(_snapshot(gpu_ctx, pop.member(1), _stats_row(pop.stats(), 1)), _snapshot(gpu_ctx, plain.member(1), _stats_row(plain.stats(), 1)), "the uniform member")
+    _assert_same(_snapshot(gpu_ctx, HEAD, pop.member(1), _stats_row(pop.stats(), 1)), _snapshot(gpu_ctx, HEAD, plain.member(1), _stats_row(plain.stats(), 1)), "the uniform member")
     assert not _same_slots(pop.member(0).state_dict()["params"], plain.member(0).state_dict()["params"])      # prioritised sampling draws other rows
     assert list(pop.stats()["updates"]) == [4, 4, 4]
     with pytest.raises(RuntimeError, match="not enabled"):

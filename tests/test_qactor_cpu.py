@@ -7,9 +7,9 @@ import types
 import numpy as np
 import pytest
 
+from discrete_testlib import NETS
 from stmpc_testlib import capi as _capi, header_entries, header_prototypes, header_text
 
-NETS = [(20, 16, 5), (20, 48, 20), (20, 256, 5)]
 ROWS = 400
 SEED = 3                        # test_q_policy_host_against_torch_modules asserts that at least 99 % of this seed's rows have a top-two gap above 1e-9
 

@@ -12,51 +12,17 @@ import types
 import numpy as np
 import pytest
 
-from stmpc_testlib import ACTOR_KMAX, actor_settings, actor_states, capi as _capi, same
+from discrete_testlib import (JERKS, NAMES, NETS, OUT, SENTINEL, actor_table as _table, dev as _dev, episode_settings as _episode_settings, policy_states as _states,
+                              run_policy as _run, stream as _stream, stub_env as _stub_env, transitions as _transitions, widen as _widen)
+from stmpc_testlib import ACTOR_KMAX, capi as _capi, same
 
-NETS = [(20, 16, 5), (20, 48, 20), (20, 256, 5)]
 PS = [1, 3, 4]
 N_PER = [1, 16, 17, 33]
-NAMES = ("w0", "b0", "w1", "b1")
-OUT = ("feat", "q", "action", "jerk")
-SENTINEL, TAIL = -7.0, 3          # every output buffer has TAIL rows beyond P * n_per_member, filled with the sentinel
-JERKS = np.array([-5.0, -2.5, 0.0, 2.5, 5.0])     # JERK_VALUES_DQN
 KINDS = ("file", "online", "target", "member")
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _t(a):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a), device=_dev())
-
-
-def _states(n):
-    """(S, n states as contiguous device tensors: the golden's 72, repeated as often as n needs)."""
-    import torch
-    g, S = actor_settings()
-    st = actor_states(g, _dev())
-    rows = torch.arange(n, device=_dev()) % st["k"].shape[0]
-    return S, {k: v[rows].contiguous() for k, v in st.items()}
 
 
 def _slice(st, sl):
     return {k: v[sl].contiguous() for k, v in st.items()}
-
-
-def _table(A, m=0, accel=False):
-    """Member m's action table: every member has its own; an acceleration-mode table stays within +-0.1 (see ``_accel_states``)."""
-    if accel:
-        return np.linspace(-0.1, 0.1, A) + 0.001 * m
-    return (JERKS.copy() if A == 5 else np.linspace(-4.75, 4.75, A)) + 0.125 * m
 
 
 def _accel_states(st):
@@ -65,11 +31,6 @@ def _accel_states(st):
     n = st["ego4"].shape[0]
     st["ego4"][:, 3] = st["ego4"].new_tensor([-20.0, 0.0, 20.0]).repeat(n // 3 + 1)[:n]
     return st
-
-
-def _transitions(rng, n, n_obs, A):
-    return (_t(rng.normal(0, 1, (n, n_obs)).astype(np.float32)), None, _t(rng.integers(0, A, n).astype(np.int32)), _t(rng.normal(0, 1, n)),
-            _t(rng.normal(0, 1, (n, n_obs)).astype(np.float32)), _t(rng.random(n) < 0.2), _t(np.zeros(n, bool)))
 
 
 def _learner(gpu_ctx, shape, seed=5, target_period=4, updates=1, push=True):
@@ -89,8 +50,7 @@ def _dqn_pop(gpu_ctx, shape, seeds=(11, 12), updates=1, push=True, per=None):
     """A DQNPopulation of two members on a stub env of 2 x 16 rows, fed one step of random transitions."""
     from rl_mpc_lanemerging_amd import learner
     n_obs, h1, A = shape
-    env = types.SimpleNamespace(n=32, obs_dim=n_obs, continuous=False, ctx=gpu_ctx, action_space={"n": A}, env_id="sumo-jerk-v0",
-                                cfg=types.SimpleNamespace(_actions=list(_table(A))))
+    env = _stub_env(gpu_ctx, 32, n_obs, A, _table(A))
     cfgs = [learner.DQNConfig(n_obs=n_obs, n_actions=A, h1=h1, batch=16, capacity=64, target_period=4, lr=1e-2, double=bool(m)) for m in range(2)]
     pop = learner.DQNPopulation(env, cfgs, seeds=list(seeds), per=per)
     if push:
@@ -126,29 +86,6 @@ def _make(src, kind, n, ctx, S, table, mode):
         return actor.DQNActor.from_learner(L, n, ctx, S, target=kind == "target", mode=mode)
     finally:
         L.action_values = keep
-
-
-def _widen(P, rows=None):
-    """Output buffers with TAIL rows more than the policy evaluates, all sentinel; every output kept."""
-    import torch
-    rows = (P.n if rows is None else rows) + TAIL
-    P.feat = torch.full((rows, P.flen), SENTINEL, dtype=torch.float32, device=_dev())
-    P.q = torch.full((rows, P.shape[2]), SENTINEL, dtype=torch.float32, device=_dev())
-    P.action = torch.full((rows,), int(SENTINEL), dtype=torch.int32, device=_dev())
-    P.jerk = torch.full((rows,), SENTINEL, dtype=torch.float64, device=_dev())
-    P.keep_features = P.keep_q = True
-    return P
-
-
-def _run(P, st, step=1):
-    """One evaluation through the policy's call; numpy copies of the n evaluated rows, after the check that the rows beyond them kept the sentinel."""
-    import torch
-    P(step, st["ego4"], st["k"], st["ox"], st["ov"], st["oa"])
-    torch.cuda.synchronize()
-    out = {k: getattr(P, k).cpu().numpy().copy() for k in OUT}
-    for k, v in out.items():
-        assert v.shape[0] == P.n + TAIL and (v[P.n:] == SENTINEL).all(), k
-    return {k: v[:P.n] for k, v in out.items()}
 
 
 def _assert_members(got, lone, n_per, label):
@@ -362,15 +299,6 @@ def test_gpu_rollout_steps(gpu_ctx, restore_settings, tmp_path_factory):
 
 
 # ---- 4: the controllers and the episode runner -----------------------------------------------------------------------------------------------------
-def _episode_settings():
-    import rl_mpc_lanemerging_amd as pkg
-    from rl_mpc_lanemerging_amd import combined_bench
-    pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
-    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1)
-    pkg.apply_overrides(combined_bench.COMBINED_MEDIUM_1_TRAFFIC)
-    return pkg.Settings
-
-
 def _jerk_learner(gpu_ctx, seed=2):
     from rl_mpc_lanemerging_amd import learner
     L = learner.DQNLearner((20, 5), learner.DQNConfig(batch=16, capacity=64), seed=seed, ctx=gpu_ctx)

@@ -1,16 +1,23 @@
-"""The suite's own structure: no test module imports another (what two of them share is in stmpc_testlib.py, learner_testlib.py or env_testlib.py), the
-helpers that were once copied from module to module are defined in no test module again, and the shared comparators and env helpers still bite."""
+"""The suite's own structure: no test module imports another (what two of them share is in stmpc_testlib.py, learner_testlib.py, discrete_testlib.py,
+nstep_testlib.py or env_testlib.py), the helpers that were once copied from module to module are defined in no test module again, and the shared
+comparators and env helpers still bite."""
 import ast
 import glob
 import os
 
 import numpy as np
 
+from discrete_testlib import NAMES, Q_SLOTS, assert_same as discrete_assert_same
 from env_testlib import episodes_of, hash01, log_rows
 from learner_testlib import FLOOR, bits64, bits_equal, check_4x
 from stmpc_testlib import REPO, bits, same
 
-SHARED_ONLY = {"_capi", "_rel_err", "_check_4x", "_record", "_flat", "_hash01", "_log_rows", "_episodes"}
+SHARED_ONLY = {"_capi", "_rel_err", "_check_4x", "_record", "_flat", "_hash01", "_log_rows", "_episodes",
+               # the discrete agents' helpers (discrete_testlib.py, and episode_settings of stmpc_testlib.py).  Not listed: _same_slots -- test_td3_pop.py has
+               # one of its own over the continuous learners' tensors, with another signature; _rows and _dev -- test_reward_groups.py and test_vec_env.py
+               # use the names for other things
+               "_snapshot", "_stats_row", "_assert_same", "_stub_env", "_feed", "_fill", "_pad_mask", "_pads_are_zero", "_twins", "_minibatch_host", "_widen",
+               "_plain_policy", "_episode_settings", "_stream", "_states", "_features", "_act", "_transitions", "_expected_values_host"}
 
 
 def test_no_test_module_imports_another_or_redefines_a_shared_helper():
@@ -36,6 +43,42 @@ def test_bit_comparisons_tell_signed_zeros_apart_and_accept_equal_nans():
     a = {"q": {"w": np.array([0.0, nan], np.float32)}}
     assert bits_equal(a, {"q": {"w": np.array([0.0, nan], np.float32)}}, ("q",), ("w",))
     assert not bits_equal(a, {"q": {"w": np.array([-0.0, nan], np.float32)}}, ("q",), ("w",))
+
+
+def test_discrete_assert_same_passes_on_equal_snapshots_and_fails_on_any_single_difference():
+    """Two hand-made discrete snapshots (four slots x four tensors, beta_pow float32 [2], counters int64 [8], a ring, a four-entry statistics row): equal
+    ones pass; one bit of one tensor, beta_pow, one counter, one ring entry, one statistics entry or the sign of a zero in a tensor fails."""
+    import copy
+
+    import pytest
+
+    def snap():
+        rng = np.random.default_rng(3)
+        t = lambda *sh: rng.normal(size=sh).astype(np.float32)
+        params = {slot: {"w0": t(4, 3), "b0": t(4), "w1": t(2, 4), "b1": t(2)} for slot in Q_SLOTS}
+        params["q_m"]["b1"][0] = 0.0
+        params["beta_pow"] = np.array([0.81, 0.998], np.float32)
+        return {"params": params, "counters": np.arange(8, dtype=np.int64), "ring": t(5, 6), "stats": [0.5, -1.25, 5.0, 2.0]}
+
+    def one_bit(a, i):
+        a.view(np.uint32).reshape(-1)[i] ^= 1
+
+    a = snap()
+    assert set(a["params"]) == set(Q_SLOTS) | {"beta_pow"} and all(tuple(a["params"][s]) == NAMES for s in Q_SLOTS)
+    discrete_assert_same(a, snap(), "equal")
+    discrete_assert_same(a, copy.deepcopy(a), "a copy")
+    changes = {"one bit of one tensor": lambda b: one_bit(b["params"]["q_v"]["w1"], 5), "beta_pow": lambda b: one_bit(b["params"]["beta_pow"], 1),
+               "one counter": lambda b: b["counters"].__setitem__(6, 7), "one ring entry": lambda b: one_bit(b["ring"], 29),
+               "one stats entry": lambda b: b["stats"].__setitem__(1, float(np.nextafter(-1.25, 0))),
+               "+0.0 vs -0.0": lambda b: b["params"]["q_m"]["b1"].__setitem__(0, -0.0)}
+    for what, change in changes.items():
+        b = snap()
+        change(b)
+        with pytest.raises(AssertionError):
+            discrete_assert_same(a, b, what)
+        with pytest.raises(AssertionError):
+            discrete_assert_same(b, a, what)
+    assert a["params"]["q_m"]["b1"][0] == -0.0                      # (equal as numbers: only a comparison of bits tells the two zeros apart)
 
 
 def test_check_4x_passes_at_its_bound_and_fails_just_above_it():
