@@ -121,6 +121,7 @@ __device__ __forceinline__ void dqn_q(const DqnDev &D, const DdpgTile &T, const 
 }
 
 // the first maximum of q[0 ... A) as torch.argmax returns it, by the 32 lanes of a row; every lane of the row gets (index, value)
+// (ties across strides: a lane keeps the first of its own columns part, part + 32, ... that holds its maximum, the merge the lower index of two equal values)
 __device__ __forceinline__ int dqn_argmax(const float *q, int A, float &best) {
     const int part = threadIdx.x & 31;
     float bv = -INFINITY; int bi = A;                               // (bi = A: a lane without a column, which never wins)

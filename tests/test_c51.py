@@ -7,13 +7,13 @@ minibatch rows at most max(4 x the error of ``update_host_c51("float32")``, 8 fl
 import numpy as np
 import pytest
 
-from discrete_testlib import (C51 as HEAD, LEARNER_SEED, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, Q_SLOTS, RING, SHAPES as _SHAPES, all_negative_rows, astar_rows,
+from discrete_testlib import (C51 as HEAD, LEARNER_SEED, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, Q_SLOTS, RING, SHAPES as _SHAPES, WIDE_A as _WIDE_A, all_negative_rows, astar_rows,
                               dyadic_projection_case, expected_values_host, fill as _fill, make_learner as _learner, minibatch_host, pad_mask as _pad_mask,
                               pads_are_zero as _pads_are_zero, projection_edge_cases, random_problem, rows_of, twins as _twins)
 from learner_testlib import FLOOR, bits_equal, check_4x as _check_4x, record as _record
 from stmpc_testlib import capi as _capi
 
-SHAPES, PROBLEM_SEEDS = _SHAPES["c51"], _PROBLEM_SEEDS["c51"]      # tests/discrete_testlib.py's tables
+SHAPES, PROBLEM_SEEDS = _SHAPES["c51"] + _WIDE_A["c51"], _PROBLEM_SEEDS["c51"]      # tests/discrete_testlib.py's tables; the last index is the head's shape of WIDE_A
 
 # ---- 1: the projection, exact --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
@@ -152,7 +152,7 @@ def test_gpu_adam_and_target_copy(si, gpu_ctx, restore_settings):
 
 # ---- 5: acting -----------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("si", [0, 2, 3])
+@pytest.mark.parametrize("si", [0, 2, 3, 4])
 def test_gpu_acting(si, gpu_ctx, restore_settings):
     _capi()
     import torch

@@ -8,11 +8,11 @@ import types
 import numpy as np
 import pytest
 
-from discrete_testlib import (C51 as HEAD, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, SHAPES as _SHAPES, all_negative_rows, astar_rows, dyadic_projection_case, minibatch_host,
+from discrete_testlib import (C51 as HEAD, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, SHAPES as _SHAPES, WIDE_A as _WIDE_A, all_negative_rows, astar_rows, dyadic_projection_case, minibatch_host,
                               projection_edge_cases, random_problem, twins)
 from stmpc_testlib import capi as _capi, header_entries, header_prototypes, header_struct_fields as _header_struct_fields, header_text
 
-SHAPES, PROBLEM_SEEDS = _SHAPES["c51"], _PROBLEM_SEEDS["c51"]      # tests/discrete_testlib.py's tables
+SHAPES, PROBLEM_SEEDS = _SHAPES["c51"] + _WIDE_A["c51"], _PROBLEM_SEEDS["c51"]      # tests/discrete_testlib.py's tables; the last index is the head's shape of WIDE_A
 ENTRIES = {"stmpc_c51_" + n for n in ("create", "destroy", "set_params", "get_params", "set_state", "get_state", "push_device", "act_device", "update_device",
                                       "grads_device", "targets_device", "dist_device", "project_device", "gather_device", "stats_device", "per_enable",
                                       "per_tree_read", "per_last_device", "multi_step_enable", "replay_read", "dzout_read", "padded_read")}
@@ -63,6 +63,16 @@ def test_c51_cfg_struct_layout_matches_header():
 
 @pytest.mark.parametrize("double", [True, False])
 def test_update_host_c51_against_torch_autograd(double):
+    _against_torch_autograd(double, (12, 24, 4, 11, 33))
+
+
+@pytest.mark.parametrize("double", [True, False])
+def test_update_host_c51_against_torch_autograd_at_64_actions(double):
+    """The same statement at WIDE_A's shape: 64 blocks of 16 atoms, A K = 1024."""
+    _against_torch_autograd(double, _WIDE_A["c51"][0])
+
+
+def _against_torch_autograd(double, shape):
     """The twin against nn.Linear modules, log_softmax, loss.backward() and torch.optim.Adam with the projection written the textbook way: float64,
     1e-12 relative; importance weights on two of the three steps, terminal rows, a target copy after step 2."""
     _capi()
@@ -70,7 +80,7 @@ def test_update_host_c51_against_torch_autograd(double):
     from torch import nn
     from rl_mpc_lanemerging_amd import learner
     rng = np.random.default_rng(9 + double)
-    n_obs, h1, A, K, B = 12, 24, 4, 11, 33
+    n_obs, h1, A, K, B = shape
     cfg = learner.C51Config(n_obs=n_obs, n_actions=A, h1=h1, batch=B, gamma=0.9, lr=1e-3, target_period=2, double=double, n_atoms=K, v_min=-4.0, v_max=3.0)
     params = learner.new_params_dqn(learner.init_c51_net(n_obs, h1, A, K, rng))
     params["q_target"] = learner.init_c51_net(n_obs, h1, A, K, rng)

@@ -9,13 +9,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from discrete_testlib import (C51_DUELING as HEAD, LEARNER_SEED, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, Q_SLOTS, RING, SHAPES as _SHAPES, all_negative_rows, astar_rows,
+from discrete_testlib import (C51_DUELING as HEAD, LEARNER_SEED, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, Q_SLOTS, RING, SHAPES as _SHAPES, WIDE_A as _WIDE_A, all_negative_rows, astar_rows,
                               expected_values_host as _expected_values_host, fill as _fill, make_learner as _learner, minibatch_host, pad_mask,
                               pads_are_zero as _pads_are_zero, random_problem, rows_of, stub_env as _stub_env, twins as _twins)
 from learner_testlib import FLOOR, bits_equal, bound_4x, check_4x as _check_4x, rel_err
 from stmpc_testlib import capi as _capi
 
-SHAPES, PROBLEM_SEEDS = _SHAPES["c51_dueling"], _PROBLEM_SEEDS["c51_dueling"]      # tests/discrete_testlib.py's tables
+SHAPES, PROBLEM_SEEDS = _SHAPES["c51_dueling"] + _WIDE_A["c51_dueling"], _PROBLEM_SEEDS["c51_dueling"]      # tests/discrete_testlib.py's tables; the last index is the head's shape of WIDE_A
 
 # ---- 1: distributions, loss, targets ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
@@ -132,7 +132,7 @@ def test_gpu_adam_and_target_copy(si, gpu_ctx, restore_settings):
 
 # ---- 4: acting and evaluation -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("si", [0, 3, 4])
+@pytest.mark.parametrize("si", [0, 3, 4, 5])
 def test_gpu_acting(si, gpu_ctx, restore_settings):
     """act with eps = 0: the expected values against the twin under the rule, the index their first maximum; exploring draws are the plain head's."""
     _capi()
@@ -153,6 +153,12 @@ def test_gpu_acting(si, gpu_ctx, restore_settings):
     a = L.act(obs, None, eps=0.25).cpu().numpy().copy()
     explore, idx = learner.dqn_act_host(23, 0, n, 0.25, A)
     assert np.array_equal(a, np.where(explore, idx, greedy)) and explore.any() and not explore.all()
+    # ties: an all-zero last layer makes every distribution uniform and every expected value the same: action 0 everywhere
+    sd = L.state_dict()
+    sd["params"]["q"]["w1"][:] = 0
+    sd["params"]["q"]["b1"][:] = 0
+    L.load_state_dict(sd)
+    assert (L.act(obs, None).cpu().numpy() == 0).all()
     gpu_ctx.check_error()
 
 

@@ -8,11 +8,11 @@ import types
 import numpy as np
 import pytest
 
-from discrete_testlib import (C51_DUELING as HEAD, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, SHAPES as _SHAPES, all_negative_rows, astar_rows, dueling_module, minibatch_host,
+from discrete_testlib import (C51_DUELING as HEAD, NAMES, PROBLEM_SEEDS as _PROBLEM_SEEDS, SHAPES as _SHAPES, WIDE_A as _WIDE_A, all_negative_rows, astar_rows, dueling_module, minibatch_host,
                               problem_net, random_problem, twins)
 from stmpc_testlib import capi as _capi
 
-SHAPES, PROBLEM_SEEDS = _SHAPES["c51_dueling"], _PROBLEM_SEEDS["c51_dueling"]      # tests/discrete_testlib.py's tables
+SHAPES, PROBLEM_SEEDS = _SHAPES["c51_dueling"] + _WIDE_A["c51_dueling"], _PROBLEM_SEEDS["c51_dueling"]      # tests/discrete_testlib.py's tables; the last index is the head's shape of WIDE_A
 
 def _problem(seed, double=True, shape=(12, 24, 4, 11, 33)):
     from rl_mpc_lanemerging_amd import learner
@@ -28,12 +28,22 @@ def _problem(seed, double=True, shape=(12, 24, 4, 11, 33)):
 
 @pytest.mark.parametrize("double", [True, False])
 def test_twin_against_separate_value_and_advantage_heads(double):
+    _against_separate_heads(double, (12, 24, 4, 11, 33))
+
+
+@pytest.mark.parametrize("double", [True, False])
+def test_twin_against_separate_value_and_advantage_heads_at_63_actions(double):
+    """The same statement at WIDE_A's shape: (A + 1) K = 1024, an odd A in the mean's division."""
+    _against_separate_heads(double, _WIDE_A["c51_dueling"][0])
+
+
+def _against_separate_heads(double, shape):
     """update_host_c51(dueling=True) in float64 against a torch module with a value nn.Linear and an advantage nn.Linear carrying the same weights,
     the projection written the textbook way: loss, row losses, m, p and all four gradients to 1e-12 relative; importance weights on one pass."""
     _capi()
     import torch
     from rl_mpc_lanemerging_amd import learner
-    cfg, params, batch = _problem(21 + double, double)
+    cfg, params, batch = _problem(21 + double, double, shape)
     A, K, B = cfg.n_actions, cfg.n_atoms, cfg.batch
     q, qt = dueling_module(params["q"], A, K), dueling_module(params["q_target"], A, K)
     z = torch.tensor(np.linspace(cfg.v_min, cfg.v_max, K))

@@ -8,51 +8,77 @@ max(4 x the error of ``update_host_dqn("float32")``, 8 float32 ulps).
 Exactness on dyadic data: the targets, a*, Q(s, a) and the pads are exact at every shape.  A gradient carries the factor 1 / B: for B = 16 the
 gradients equal the float64 twin value for value; 1/7, 1/33 and 1/50 are not float32 numbers, so no float32 gradient can equal the float64 one
 there, and those shapes' gradients are held to the parity rule above (test_gpu_dyadic_targets_are_exact) -- and each of the four networks has its
-gradients checked value for value at a power-of-two B of its own (test_gpu_dyadic_gradients_are_exact: B = 8, 32, 64, 16)."""
+gradients checked value for value at a power-of-two B of its own (test_gpu_dyadic_gradients_are_exact: B = 8, 32, 64, 16).
+
+More than 32 actions (discrete_testlib.WIDE_A: (20, 32, 40, 16), (12, 16, 64, 8), (20, 48, 256, 32)): the same two tests, the acting test and the
+prioritised-replay body on ``dqn_wide_problem`` -- exact ties across the argmax's strides that hold the row's maximum, stored actions in every
+output tile, clip bounds met exactly; test_dqn_cpu.py asserts from the twins alone that none of it is vacuous."""
 import os
 
 import numpy as np
 import pytest
 
 from conftest import REPO
-from discrete_testlib import (DQN as HEAD, GRAD_SHAPES as _GRAD_SHAPES, NAMES, Q_SLOTS, RING, SHAPES as _SHAPES, fill as _fill, make_learner as _learner,
+from discrete_testlib import (DQN as HEAD, GRAD_SHAPES as _GRAD_SHAPES, NAMES, Q_SLOTS, RING, SHAPES as _SHAPES, WIDE_A as _WIDE_A, WIDE_ACT_ROWS, _q64,
+                              dqn_dyadic_problem as _dyadic_problem, dqn_wide_problem as _wide_problem, fill as _fill, make_learner as _learner,
                               minibatch_host as _minibatch_host, pad_mask as _pad_mask, pads_are_zero as _pads_are_zero, random_problem as _random_problem, rows_of as _rows,
-                              twins as _twins)
+                              tied_rows as _tied_rows, twins as _twins)
 from learner_testlib import bits_equal, check_4x as _check_4x
 from stmpc_testlib import capi as _capi
 
-SHAPES, GRAD_SHAPES = _SHAPES["dqn"], _GRAD_SHAPES["dqn"]      # tests/discrete_testlib.py's tables
+SHAPES, GRAD_SHAPES, WIDE = _SHAPES["dqn"], _GRAD_SHAPES["dqn"], _WIDE_A["dqn"]      # tests/discrete_testlib.py's tables
 
 
 def dyadic_problem(shape, double, clip, seed=0):
-    """Weights, observations and rewards on small dyadic grids and gamma = 0.5: every sum of the forward pass is exact in float32 (|Q| < 2^13 in
-    units of 2^-9).  b1 is shifted down so that on some rows every real Q(s') is negative (the pad columns' 0 would win a careless argmax)."""
-    from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, A, B = shape
-    rng = np.random.default_rng(100 + seed)
-    grid = lambda lo, hi, den, *sh: rng.integers(lo, hi + 1, size=sh).astype(np.float64) / den
-    shift = np.round((1.0 if A <= 5 else 0.7) * 0.45 * np.sqrt(h1) * 8) / 8     # about half of the rows: Q(s') spreads by about 0.45 sqrt(h1)
-    net = lambda: {"w0": grid(-4, 4, 8, h1, n_obs).astype(np.float32), "b0": grid(-4, 4, 8, h1).astype(np.float32),
-                   "w1": grid(-4, 4, 8, A, h1).astype(np.float32), "b1": (grid(-4, 4, 8, A) - shift).astype(np.float32)}
-    params = learner.new_params_dqn(net())
-    params["q_target"] = net()
-    replay = {"s": grid(-4, 4, 4, RING, n_obs), "s2": grid(-4, 4, 4, RING, n_obs), "a": rng.integers(0, A, RING), "r": grid(-8, 8, 4, RING),
-              "term": rng.random(RING) < 0.2}
-    cfg = learner.DQNConfig(n_obs=n_obs, n_actions=A, h1=h1, batch=B, capacity=RING, gamma=0.5, double=double, clip_targets=clip, clip_min=-0.5, clip_max=0.25)
-    return cfg, params, replay
+    """(cfg, params, replay, extra): tests/discrete_testlib.py's exact problem for ``shape`` -- ``dqn_wide_problem`` at a shape of WIDE (ties at
+    s' that hold the row's maximum, hand-set stored actions, clip bounds that rows meet exactly; ``extra`` names them), else
+    ``dqn_dyadic_problem`` (``extra`` None).  ``seed`` is ``dqn_dyadic_problem``'s alone: a WIDE problem's generator seed is the one
+    WIDE_DQN_SEEDS holds for (shape, double), found on the CPU, so the targets test and the gradients test run the same WIDE problem (the second
+    goes on to the update)."""
+    if shape in WIDE:
+        return _wide_problem(shape, double, clip)
+    return _dyadic_problem(shape, double, clip, seed) + (None,)
+
+
+def _wide_checks(gpu_ctx, L, cfg, params, replay, extra, batch, i64, t):
+    """What only a WIDE problem has: the ring after the push holds A - 1 and 0 where A + 3 and -2 were pushed; the stored actions reach every output
+    tile, column 31, column 32 and column A - 1; on every row where a tie group holds the maximum at s', a* is the group's lowest column, group by
+    group; with clip_targets, y sits exactly on each bound on the rows the twin names."""
+    A, B = cfg.n_actions, cfg.batch
+    ring = gpu_ctx.dqn_pop_replay_read(L.handle, 0, cfg.capacity)
+    assert np.array_equal(ring.view(np.uint32), _rows(replay, cfg.n_obs, A).view(np.uint32))
+    col = _capi().DQN_ACTION_COL
+    for r, pushed, stored in extra["hand"]:
+        assert replay["a"][r] == pushed and ring[r, col] == stored, (r, pushed, stored, ring[r, col])
+    assert (extra["hand"][0][1], extra["hand"][0][2], extra["hand"][1][1], extra["hand"][1][2]) == (A + 3, A - 1, -2, 0)
+    stored = set(batch["a"].tolist())
+    assert {31, 32, A - 1} <= stored and {a // 16 for a in stored} == set(range((A + 15) // 16)), sorted(stored)
+    qn = _q64(params["q" if cfg.double else "q_target"], batch["s2"])
+    for name, rows in _tied_rows(qn, extra["groups"]).items():
+        low = extra["groups"][name][0]
+        print("%s: tie %s on %d rows" % ((cfg.n_obs, cfg.h1, A, B), name, rows.size))
+        assert rows.size >= 4 and (i64["targets"][rows, 0] == low).all(), name
+        assert (t[rows, 0] == low).all(), ("a* on the rows tied in " + name, t[rows, 0].tolist(), low)
+    if cfg.clip_targets:
+        live = batch["mask"] > 0
+        g = 0.5 * i64["targets"][:, 1]
+        for bound, beyond in ((cfg.clip_min, g < cfg.clip_min), (cfg.clip_max, g > cfg.clip_max)):
+            on = live & (g == bound)
+            assert on.any() and (live & beyond).any()
+            assert (t[on | (live & beyond), 2].astype(np.float64) == batch["r"][on | (live & beyond)] + bound).all()
 
 
 # ---- 1: targets -----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("double,clip", [(True, False), (True, True), (False, False), (False, True)])
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", SHAPES + WIDE)
 def test_gpu_dyadic_targets_are_exact(shape, double, clip, gpu_ctx, restore_settings):
     """targets() (a*, Qt(s', a*), y, Q(s, a)) equals update_host_dqn(float64) value for value, on minibatches with rows whose real Q(s') are all
     negative; the gradient tensors: value for value where B is a power of two (B = 16), else -- 1 / B is no float32 number -- under the parity rule."""
     _capi()
     from rl_mpc_lanemerging_amd import learner
     n_obs, h1, A, B = shape
-    cfg, params, replay = dyadic_problem(shape, double, clip)
+    cfg, params, replay, extra = dyadic_problem(shape, double, clip)
     L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     rows, batch = _minibatch_host(replay, cfg)
     assert L.stats()["fill"] == RING and np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
@@ -63,6 +89,7 @@ def test_gpu_dyadic_targets_are_exact(shape, double, clip, gpu_ctx, restore_sett
         qn = learner._q_mlp({k: T(params["q" if double else "q_target"][k]) for k in NAMES}, T(batch["s2"])).numpy()
     allneg = (qn < 0).all(1)
     assert allneg.any() and not allneg.all(), int(allneg.sum())     # rows on which a pad column's 0 would beat every real action
+    assert shape != WIDE[0] or 4 <= allneg.sum() <= B - 4
     t = L.targets()
     assert t.dtype == np.float32 and t.shape == (B, 4)
     assert np.array_equal(t[:, :3].astype(np.float64), i64["targets"]), np.count_nonzero(t[:, :3].astype(np.float64) != i64["targets"], axis=0)
@@ -72,6 +99,10 @@ def test_gpu_dyadic_targets_are_exact(shape, double, clip, gpu_ctx, restore_sett
         g = 0.5 * i64["targets"][:, 1]
         live = batch["mask"] > 0
         assert (g[live] > cfg.clip_max).any() or (g[live] < cfg.clip_min).any()
+    if extra is not None:
+        _wide_checks(gpu_ctx, L, cfg, params, replay, extra, batch, i64, t)
+        if double:
+            assert (_q64(params["q"], batch["s2"]).argmax(1) != _q64(params["q_target"], batch["s2"]).argmax(1)).sum() >= 4
     grad = L.grads()
     ok = True
     for k in NAMES:
@@ -89,7 +120,7 @@ def test_gpu_dyadic_targets_are_exact(shape, double, clip, gpu_ctx, restore_sett
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("double,clip", [(True, False), (True, True), (False, False), (False, True)])
-@pytest.mark.parametrize("shape", GRAD_SHAPES)
+@pytest.mark.parametrize("shape", GRAD_SHAPES + WIDE)
 def test_gpu_dyadic_gradients_are_exact(shape, double, clip, gpu_ctx, restore_settings):
     """Every gradient tensor equals update_host_dqn(float64) value for value, at each of the four networks: B is a power of two here (8: half a
     tile of padded rows; 32, 64, 16), so that dz = clamp(diff) / B is exact and every product and partial sum of the backward pass is a float32
@@ -97,7 +128,9 @@ def test_gpu_dyadic_gradients_are_exact(shape, double, clip, gpu_ctx, restore_se
     _capi()
     from rl_mpc_lanemerging_amd import learner
     n_obs, h1, A, B = shape
-    cfg, params, replay = dyadic_problem(shape, double, clip, seed=2)
+    cfg, params, replay, extra = dyadic_problem(shape, double, clip, seed=2)
+    if extra is not None:
+        cfg.target_period, cfg.lr = 1, 1e-3
     L = _learner(gpu_ctx, HEAD, cfg, params, replay)
     rows, batch = _minibatch_host(replay, cfg)
     assert np.array_equal(L.minibatch().view(np.uint32), rows.view(np.uint32))
@@ -110,7 +143,36 @@ def test_gpu_dyadic_gradients_are_exact(shape, double, clip, gpu_ctx, restore_se
         want = i64["grad"][k]
         assert grad[k].dtype == np.float32 and grad[k].shape == want.shape and np.abs(want).max() > 0
         assert np.array_equal(grad[k].astype(np.float64), want), (k, int(np.count_nonzero(grad[k].astype(np.float64) != want)), want.size)
+    if extra is not None:
+        _wide_gradient_checks(gpu_ctx, L, cfg, params, batch, i64)
     gpu_ctx.check_error()
+
+
+def _wide_gradient_checks(gpu_ctx, L, cfg, params, batch, i64):
+    """At a WIDE shape, on top of the exact gradients: dZout is an exact zero outside the stored actions' columns -- read as the padded gradient's
+    rows of dW1 = dZout^T H1 and entries of db1 of every column no minibatch row stores, +0.0 by their bits.  (The DQN learner has no read of
+    dZout itself, as the C51 learner has.  A stray entry of dZout in a column that ANOTHER row stores is not seen here; it changes that column's
+    db1 and row of dW1, which the value-for-value comparison with the float64 twin above holds.)  The pads of the gradient are exact
+    zeros after grads() and those of all five padded arrays after one update(1); that update (target_period 1: the hard copy is in it) leaves the
+    weights, both moments, the beta powers and the target that ``dqn_adam_host`` gives on the float64 twin's gradient, bit for bit."""
+    capi = _capi()
+    from rl_mpc_lanemerging_amd import learner
+    n_obs, h1, A = cfg.n_obs, cfg.h1, cfg.n_actions
+    pad = _pad_mask(n_obs, h1, A)
+    _pads_are_zero(gpu_ctx, HEAD, L, [capi.DQN_GRAD], pad, "grads")
+    g = gpu_ctx.dqn_padded_read(L.handle, capi.DQN_GRAD, h1, A)
+    unstored = np.setdiff1d(np.arange(g["b1"].size), batch["a"])
+    assert unstored.size >= g["b1"].size - cfg.batch and not g["w1"][unstored].view(np.uint32).any() and not g["b1"][unstored].view(np.uint32).any()
+    assert all(np.abs(g["w1"][a]).max() > 0 for a in set(batch["a"].tolist()))
+    L.update(1)
+    _pads_are_zero(gpu_ctx, HEAD, L, range(5), pad, "update")
+    after = L.state_dict()["params"]
+    for k in NAMES:
+        w, m, v, bp = learner.dqn_adam_host(params["q"][k], i64["grad"][k], params["q_m"][k], params["q_v"][k], params["beta_pow"], cfg.lr, cfg)
+        for slot, want in (("q", w), ("q_m", m), ("q_v", v), ("q_target", w)):
+            assert np.array_equal(after[slot][k].view(np.uint32), want.view(np.uint32)), (slot, k)
+        assert not np.array_equal(after["q"][k], params["q"][k])
+    assert np.array_equal(after["beta_pow"].view(np.uint32), bp.view(np.uint32)) and after["updates"] == 1
 
 
 @pytest.mark.gpu
@@ -217,8 +279,11 @@ def test_gpu_gradients_against_the_float64_twin(shape, gpu_ctx, restore_settings
 
 # ---- 3: acting ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[2]])
+@pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[2]] + WIDE)
 def test_gpu_acting(shape, gpu_ctx, restore_settings):
+    """Behind an env at the two shipped action counts.  At a WIDE shape, without one: the acting net and observations of ``dqn_wide_problem`` -- Q
+    equals the float64 forward pass value for value, and on every observation where a tie group holds the maximum the greedy index is the group's
+    lowest column, group by group; rows with only negative Q among them."""
     _capi()
     import torch
     import rl_mpc_lanemerging_amd as pkg
@@ -226,11 +291,18 @@ def test_gpu_acting(shape, gpu_ctx, restore_settings):
     n_obs, h1, A, B = shape
     pkg.apply_overrides(pkg.REFERENCE_DEFAULT)
     n = 50                                                          # four tiles, the last one partly filled
-    env = vec_env.MergeVecEnv(n, env_id="sumo-jerk-v0" if A == 5 else "sumo-accel-v0", seed=9, ctx=gpu_ctx)
-    cfg = learner.DQNConfig(n_obs=n_obs, h1=h1, batch=B, capacity=256)
-    L = learner.DQNLearner(env, cfg, seed=23)
+    if shape in WIDE:
+        env, extra = None, dyadic_problem(shape, True, False)[3]
+        cfg = learner.DQNConfig(n_obs=n_obs, n_actions=A, h1=h1, batch=B, capacity=256)
+        L = learner.DQNLearner((n_obs, A), cfg, seed=23, init=extra["acting_net"], ctx=gpu_ctx)
+        obs = torch.as_tensor(extra["act_obs"], device="cuda")
+        assert obs.shape == (n, n_obs) and n == WIDE_ACT_ROWS
+    else:
+        env = vec_env.MergeVecEnv(n, env_id="sumo-jerk-v0" if A == 5 else "sumo-accel-v0", seed=9, ctx=gpu_ctx)
+        cfg = learner.DQNConfig(n_obs=n_obs, h1=h1, batch=B, capacity=256)
+        L = learner.DQNLearner(env, cfg, seed=23)
+        obs = env.reset()
     assert cfg.n_actions == A == L.action_values.size
-    obs = env.reset()
     q = torch.zeros(n, A, dtype=torch.float32, device="cuda")
     greedy = L.act(obs, None, eps=0.0, debug_q=q).cpu().numpy().copy()
     qh = q.cpu().numpy()
@@ -238,6 +310,13 @@ def test_gpu_acting(shape, gpu_ctx, restore_settings):
     net = L.state_dict()["params"]["q"]
     want = np.maximum(obs.cpu().numpy().astype(np.float64) @ net["w0"].astype(np.float64).T + net["b0"], 0) @ net["w1"].astype(np.float64).T + net["b1"]
     assert np.abs(qh - want).max() < 5e-5                            # tests/test_learner.py's acting rule
+    if env is None:
+        assert np.array_equal(qh.astype(np.float64), want) and np.array_equal(greedy, want.argmax(1))
+        allneg = (want < 0).all(1)
+        assert allneg.any() and not allneg.all()
+        for name, rows in _tied_rows(want, extra["act_groups"]).items():
+            print("%s: acting tie %s on %d rows" % (shape, name, rows.size))
+            assert rows.size >= 2 and (greedy[rows] == extra["act_groups"][name][0]).all(), ("greedy index on the rows tied in " + name, greedy[rows].tolist())
     assert int(gpu_ctx.dqn_get_state(L.handle)[0][3]) == 0           # a greedy call is no exploring call
     call = 0
     for eps in (0.25, 1.0, 0.25):
@@ -249,9 +328,10 @@ def test_gpu_acting(shape, gpu_ctx, restore_settings):
         assert int(gpu_ctx.dqn_get_state(L.handle)[0][3]) == call
     assert np.array_equal(L.act(obs, None, eps=0.0).cpu().numpy(), greedy)
     # stepping the env with the returned tensor latches no out-of-range flag
-    for _ in range(3):
+    for _ in range(3 if env is not None else 0):
         obs, r, term, trunc, info = env.step(L.act(obs, None, eps=0.5))
-    env.check_error()
+    if env is not None:
+        env.check_error()
     # ties: an all-zero last layer yields action 0 everywhere
     p = L.state_dict()
     p["params"]["q"]["w1"][:] = 0
@@ -332,12 +412,21 @@ def test_gpu_updates_are_reproducible(per, gpu_ctx, restore_settings):
 
 @pytest.mark.gpu
 def test_gpu_prioritised_replay(gpu_ctx, restore_settings):
+    _prioritised_replay(gpu_ctx, SHAPES[1])
+
+
+@pytest.mark.gpu
+def test_gpu_prioritised_replay_beyond_one_stride(gpu_ctx, restore_settings):
+    """The same three updates at (20, 32, 40, 16): three output tiles, stored actions of 32 and more."""
+    _prioritised_replay(gpu_ctx, WIDE[0])
+
+
+def _prioritised_replay(gpu_ctx, shape):
     """idx = per_sample_host on the device's tree; after an update the sampled leaves = per_priority_host of the device's own td and the inner sums
     recomputed exactly; new rows enter at max_priority ** alpha; the weights reach the loss; a learner without per keeps its bits."""
     _capi()
     from rl_mpc_lanemerging_amd import learner
     per = learner.PERConfig(beta=0.5)
-    shape = SHAPES[1]
     cfg, params, replay = _random_problem(HEAD, shape, 51, per=per)
     cfg0, _, _ = _random_problem(HEAD, shape, 51)
     L, U = _learner(gpu_ctx, HEAD, cfg, params, replay), _learner(gpu_ctx, HEAD, cfg0, params, replay)

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from discrete_testlib import (WIDE_A, WIDE_DQN_SEEDS, _q64, dqn_exactness_bits, dqn_wide_counts, dqn_wide_counts_ok, dqn_wide_problem, minibatch_host, tie_groups,
+                              tied_rows)
 from learner_testlib import check_4x as _check_4x
 from stmpc_testlib import capi as _capi, header_entries, header_struct_fields as _header_struct_fields, header_text
 
@@ -146,6 +148,86 @@ def test_update_host_dqn_against_torch_autograd(double, clip):
         assert np.array_equal(new["q_target"]["w1"], new["q"]["w1"]) == ((step + 1) % 2 == 0)
         params = new
     assert params["updates"] == 3 and np.allclose(params["beta_pow"], [0.9 ** 3, 0.999 ** 3])
+
+
+@pytest.mark.parametrize("double", [True, False])
+@pytest.mark.parametrize("shape", WIDE_A["dqn"])
+def test_wide_problems_cannot_pass_vacuously(shape, double):
+    """``dqn_wide_problem`` at more than 32 actions, from the host twins alone: the counts the GPU tests rest on (``dqn_wide_counts_ok``: rows per tie
+    group, all-negative rows, online != target rows, the clip bounds met and passed), every partial sum below 24 bits, the float32 and the float64
+    twin equal value for value (targets, Q(s, a), every gradient), with and without clipping, and ``dqn_targets_host``'s a* the lowest column of
+    each tie group."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    c = dqn_wide_counts(shape, double)
+    print(shape, "double" if double else "plain", "seed", WIDE_DQN_SEEDS[shape, double], c)
+    assert dqn_wide_counts_ok(shape, double, c), c
+    n_obs, h1, A, B = shape
+    assert B & (B - 1) == 0
+    for clip in (True, False):
+        cfg, params, replay, extra = dqn_wide_problem(shape, double, clip)
+        _, batch = minibatch_host(replay, cfg)
+        bits = dqn_exactness_bits(params, batch, cfg)
+        assert max(bits.values()) < 24, bits
+        (_, i64), (_, i32) = (learner.update_host_dqn(params, batch, cfg, d, grads_only=True) for d in ("float64", "float32"))
+        assert i32["targets"].dtype == np.float32 and np.array_equal(i32["targets"].astype(np.float64), i64["targets"])
+        assert np.array_equal(i32["q_values"].astype(np.float64), i64["q_values"]) and (np.abs(i64["td"]) > 1).any() and (batch["mask"] == 0).any()
+        for k in NAMES:
+            assert i32["grad"][k].dtype == np.float32 and np.array_equal(i32["grad"][k].astype(np.float64), i64["grad"][k]) and np.abs(i64["grad"][k]).max() > 0, k
+        t = learner.dqn_targets_host(params, batch, cfg)
+        for name, rows in tied_rows(_q64(params["q" if double else "q_target"], batch["s2"]), extra["groups"]).items():
+            assert rows.size >= 4 and (t[rows, 0] == extra["groups"][name][0]).all(), (name, t[rows, 0])
+        stored = set(int(a) for a in batch["a"])
+        assert {31, 32, A - 1} <= stored and {a // 16 for a in stored} == set(range((A + 15) // 16))
+        assert replay["a"].max() == A + 3 and replay["a"].min() == -2 and 0 <= batch["a"].min() and batch["a"].max() == A - 1
+    assert set(tie_groups(A)) >= {"ends", "lanes", "strides"} and tie_groups(A)["strides"][1] - tie_groups(A)["strides"][0] == 32 and (A != 256 or len(tie_groups(A)["triple"]) == 3)
+
+
+def test_wide_twin_gradient_against_torch_autograd():
+    """The twin's gradient at (20, 32, 40, 16) against the second statement with nn.Linear modules, nn.SmoothL1Loss and loss.backward(): float64,
+    1e-12 relative, double DQN with and without clipping and plain DQN."""
+    _capi()
+    import torch
+    from torch import nn
+    from rl_mpc_lanemerging_amd import learner
+    shape = WIDE_A["dqn"][0]
+    for double, clip in ((True, False), (False, False), (True, True)):
+        cfg, params, replay, _ = dqn_wide_problem(shape, double, clip)
+        _, batch = minibatch_host(replay, cfg)
+        mods = []
+        for slot in ("q", "q_target"):
+            m = nn.Sequential(nn.Linear(shape[0], shape[1]), nn.ReLU(), nn.Linear(shape[1], shape[2])).double()
+            with torch.no_grad():
+                for p, k in zip(m.parameters(), NAMES):
+                    p.copy_(torch.tensor(params[slot][k], dtype=torch.float64))
+            mods.append(m)
+        q, qt = mods
+        T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
+        with torch.no_grad():
+            s2 = T(batch["s2"])
+            nxt = torch.gather(qt(s2), 1, torch.argmax(q(s2), 1, keepdim=True)).flatten() if double else qt(s2).max(1)[0]
+            gq = cfg.gamma * nxt
+            if clip:
+                gq = gq.clamp(cfg.clip_min, cfg.clip_max)
+            y = T(batch["r"]) + T(batch["mask"]) * gq
+        qv = torch.gather(q(T(batch["s"])), 1, torch.tensor(batch["a"])[:, None]).flatten()
+        nn.SmoothL1Loss()(qv, y).backward()
+        _, info = learner.update_host_dqn(params, batch, cfg, "float64", grads_only=True)
+        assert np.abs(info["targets"][:, 2] - y.numpy()).max() <= 1e-12 * np.abs(y.numpy()).max()
+        for p, k in zip(q.parameters(), NAMES):
+            assert np.abs(info["grad"][k] - p.grad.numpy()).max() <= 1e-12 * np.abs(p.grad.numpy()).max(), (double, clip, k)
+
+
+def test_dqn_act_host_draws_beyond_one_stride():
+    """A = 40, 64, 256: every index in range; at A = 40 every action is drawn over 4096 envs at eps = 1."""
+    _capi()
+    from rl_mpc_lanemerging_amd import learner
+    for A in (40, 64, 256):
+        ex, idx = learner.dqn_act_host(7, 0, 4096, 1.0, A)
+        assert ex.all() and idx.min() >= 0 and idx.max() < A and idx.dtype == np.int32
+        assert A != 40 or len(set(idx.tolist())) == 40
+        exq, idxq = learner.dqn_act_host(7, 0, 256, 0.25, A)
+        assert np.array_equal(idxq, idx[:256]) and 0 < exq.sum() < 256
 
 
 def test_dqn_epsilon_is_the_references_decay():

@@ -13,7 +13,7 @@ step.  With capacity 200 (so that every ring wraps) and 12 steps of 24 frames me
 import numpy as np
 import pytest
 
-from discrete_testlib import (DQN as HEAD, LR, NAMES, PERIOD, Q_SLOTS, assert_population_run, assert_same as _assert_same, feed as _feed, run_population,
+from discrete_testlib import (DQN as HEAD, LR, NAMES, PERIOD, Q_SLOTS, WIDE_A, assert_population_run, assert_same as _assert_same, feed as _feed, run_population,
                               same_slots as _same_slots, snapshot as _snapshot, stats_row as _stats_row, stub_env as _stub_env, syn_steps)
 from learner_testlib import CAP, N_PER, STEPS, bits64, dev as _dev
 from stmpc_testlib import actor_settings, actor_states, bits as _bits, capi as _capi
@@ -86,31 +86,63 @@ SYN = (20, 48, 20, 16)                         # (n_obs, h1, A, B): two hidden k
 SYN_RING, SYN_N, SYN_PUSHES = 128, 32, 5       # 160 rows into 128: the rings (and the trees' leaves) wrap
 
 
-def _syn_cfgs(per=(None, None, None), **kw):
-    A = SYN[2]
-    return [HEAD.cfg(SYN, m, n_actions=A, capacity=SYN_RING, lr=1e-3, per=per[m], **kw) for m in range(3)]
+def _syn_cfgs(per=(None, None, None), shape=SYN, **kw):
+    A = shape[2]
+    return [HEAD.cfg(shape, m, n_actions=A, capacity=SYN_RING, lr=1e-3, per=per[m], **kw) for m in range(3)]
 
 
-def _syn_steps(P=3):
-    return syn_steps(HEAD, SYN, P, SYN_PUSHES, SYN_N)
+def _syn_steps(P=3, shape=SYN):
+    return syn_steps(HEAD, shape, P, SYN_PUSHES, SYN_N)
 
 
-def _syn_pop(gpu_ctx, per=None, steps=None):
+def _syn_pop(gpu_ctx, per=None, steps=None, shape=SYN, P=3):
     from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, A, B = SYN
-    pop = learner.DQNPopulation(_stub_env(gpu_ctx, 3 * SYN_N, n_obs, A), _syn_cfgs(), seeds=list(SEEDS), per=per)
-    for step in steps if steps is not None else _syn_steps():
+    n_obs, h1, A, B = shape
+    pop = learner.DQNPopulation(_stub_env(gpu_ctx, P * SYN_N, n_obs, A), _syn_cfgs(shape=shape)[:P], seeds=list(SEEDS[:P]), per=per)
+    for step in steps if steps is not None else _syn_steps(P, shape):
         _feed(pop, step)
     return pop
 
 
-def _syn_lone(gpu_ctx, m, per=None, steps=None):
+def _syn_lone(gpu_ctx, m, per=None, steps=None, shape=SYN):
     from rl_mpc_lanemerging_amd import learner
-    n_obs, h1, A, B = SYN
-    L = learner.DQNLearner((n_obs, A), _syn_cfgs(per=[per] * 3)[m], seed=SEEDS[m], ctx=gpu_ctx)
-    for step in steps if steps is not None else _syn_steps():
+    n_obs, h1, A, B = shape
+    L = learner.DQNLearner((n_obs, A), _syn_cfgs(per=[per] * 3, shape=shape)[m], seed=SEEDS[m], ctx=gpu_ctx)
+    for step in steps if steps is not None else _syn_steps(shape=shape):
         _feed(L, step, slice(m * SYN_N, (m + 1) * SYN_N))
     return L
+
+
+@pytest.mark.gpu
+def test_gpu_two_members_beyond_one_stride(gpu_ctx, restore_settings):
+    """(20, 32, 40, 16) of WIDE_A -- three output tiles, stored actions of 32 and more, a lane of the argmax with two columns --: two members with
+    different seeds, gamma, double (True, False), clip_targets and target_period (1, 3) equal the lone learners bit for bit after the pushes and after
+    each of four updates (member 1's hard copy is update 3's); the acting entry on the pushed observations too, greedy and exploring."""
+    _capi()
+    import torch
+    shape = WIDE_A["dqn"][0]
+    steps = _syn_steps(2, shape)
+    assert max(int(s["action"].max()) for s in steps) >= 32
+    pop = _syn_pop(gpu_ctx, None, steps, shape=shape, P=2)
+    lone = [_syn_lone(gpu_ctx, m, None, steps, shape=shape) for m in range(2)]
+    obs = _dev(steps[0]["obs"])
+    for eps in (0.0, 0.5):
+        a = pop.act(obs, None, eps=eps).clone()
+        assert torch.equal(a, torch.cat([lone[m].act(obs[m * SYN_N:(m + 1) * SYN_N], None, eps=eps) for m in range(2)])) and int(a.max()) < shape[2]
+    for u in range(5):
+        for m, L in enumerate(lone):
+            _assert_same(_snapshot(gpu_ctx, HEAD, pop.member(m), _stats_row(pop.stats(), m)), _snapshot(gpu_ctx, HEAD, L, _stats_row(L.stats())), "member %d after %d updates" % (m, u))
+            assert u == 0 or not _same_slots(pop.member(m).state_dict()["params"], first[m])
+        if u == 0:
+            first = [pop.member(m).state_dict()["params"] for m in range(2)]
+        if u < 4:
+            pop.update(1)
+            for L in lone:
+                L.update(1)
+    sd = pop.member(1).state_dict()["params"]
+    assert list(pop.stats()["updates"]) == [4, 4] and not all(np.array_equal(sd["q_target"][k], sd["q"][k]) for k in NAMES)      # copied at update 3, stepped at 4
+    assert not _same_slots(pop.member(0).state_dict()["params"], sd)
+    gpu_ctx.check_error()
 
 
 @pytest.mark.gpu

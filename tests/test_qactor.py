@@ -11,10 +11,9 @@ import types
 import numpy as np
 import pytest
 
-from discrete_testlib import (JERKS, NAMES, NETS, ROWS, SENTINEL, act_on_features as _act, actor_table as _table, dev as _dev, episode_settings as _episode_settings,
+from discrete_testlib import (JERKS, NAMES, NETS, NETS_WIDE, Q_WIDE_VARIANTS, ROWS, SENTINEL, q_dyadic_policy as _dyadic_policy, tied_rows as _tied_rows, act_on_features as _act, actor_table as _table, dev as _dev, episode_settings as _episode_settings,
                               plain_policy as _plain_policy, policy_features as _features, policy_states as _states, run_policy as _run, stream as _stream,
                               transitions as _transitions, widen as _widen)
-from learner_testlib import dyadic_net
 from stmpc_testlib import ACTOR_KMAX, capi as _capi, same
 
 
@@ -101,72 +100,54 @@ def test_gpu_acceleration_mode_equals_the_numpy_formula(n, gpu_ctx, restore_sett
 
 
 # ---- dyadic data: Q against the float64 twin, value for value ------------------------------------------------------------------------------------------
-def dyadic_case(shape, n, seed=0):
-    """(net, table, states as numpy, settings) whose every product and partial sum is a float32 number.  Weights: ``dyadic_net``'s value sets (three
-    entries of {-1, -1/2, 1/2, 1} per row, biases multiples of 1/2), b1 shifted down until about half of the rows have only negative Q; the state
-    vector is not normalised (NORMALIZE_VECTOR_INPUT False) and every state entry is a multiple of 1/4 in [-4, 4].  The action that wins most
-    often is copied into a second column, so the rows it wins hold an exact tie, which the first of the two must take."""
-    n_obs, h1, A = shape
-    rng = np.random.default_rng(40 + seed)
-    S = types.SimpleNamespace(MAX_SPEED=8.0, SENSOR_RADIUS=16.0, CARS_AHEAD=2, CARS_BEHIND=2, USE_ACCELERATION_OF_OTHER_CARS=True, USE_SPEED_DIFFERENCE=True,
-                              NORMALIZE_VECTOR_INPUT=False, TICK_LENGTH=0.25, MINIMUM_NEGATIVE_JERK=-4.0, MAXIMUM_POSITIVE_JERK=2.0)
-    net = {k: v for k, v in dyadic_net(rng, n_obs, h1, A, 1.0).items() if k in NAMES}
-    quarter = lambda lo, hi, *sh: rng.integers(4 * lo, 4 * hi + 1, sh) / 4.0
-    K = 4
-    ox = quarter(-4, 4, n, K)
-    ox[ox == 0] = 0.25
-    states = {"ego4": np.concatenate([np.zeros((n, 1)), quarter(-4, 4, n, 3)], 1),     # (x = 0, y, v, a)
-              "k": np.full(n, K, np.int32), "ox": ox, "ov": quarter(-2, 2, n, K),
-              "oa": quarter(-2, 2, n, K)}
-    return net, S, states
-
-
-def dyadic_features(S, states):
-    from rl_mpc_lanemerging_amd import actor
-    return np.stack([actor.state_vector_host(S, states["ego4"][i], states["ox"][i], states["ov"][i], states["oa"][i]) for i in range(len(states["k"]))])
-
-
-def dyadic_finish(net, feat):
-    """The shift of b1 and the tie column, from the float64 twin alone: (net, j1 < j2 the tied columns)."""
-    from rl_mpc_lanemerging_amd import actor
-    A = net["b1"].size
-    q = actor.q_policy_host(net, feat, np.arange(A), "jerk")[0]
-    net["b1"] = (net["b1"] - np.float32(np.round(np.median(q.max(1)) * 2) / 2 + 0.25)).astype(np.float32)      # (a multiple of 1/4: no row's maximum is 0)
-    idx = actor.q_policy_host(net, feat, np.arange(A), "jerk")[1]
-    win = int(np.bincount(idx, minlength=A).argmax())
-    other = (win + 2) % A
-    j1, j2 = min(win, other), max(win, other)
-    net["w1"][other], net["b1"][other] = net["w1"][win], net["b1"][win]
-    return net, j1, j2
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", NETS)
+@pytest.mark.parametrize("shape", NETS + NETS_WIDE)
 def test_gpu_dyadic_q_equals_the_float64_twin(shape, gpu_ctx, restore_settings, tmp_path):
     """.q equals q_policy_host in float64 value for value, .action its first-maximum index and .jerk the table's entry, for a view and for a file
-    actor, on 33 rows of which some have only negative Q (a pad column's 0 must not win) and some hold an exact tie (the first column wins)."""
+    actor, on rows of which some have only negative Q (a pad column's 0 must not win) and some hold an exact tie (the first column wins).  The
+    problems are discrete_testlib.q_dyadic_policy's.  Up to 32 actions: 33 rows, one tied pair.  Beyond (NETS_WIDE; a lane of the argmax owns
+    several columns), 50 rows, an action table of A distinct values and two problems: "ties" -- (5, 37), (31, 32), (0, A - 1), at A = 256
+    (9, 41, 233) each hold the maximum on rows, and there the index is the group's lowest column, group by group --, and "lone" -- columns 32 and
+    A - 1 win rows alone, and the jerk there is the table's entry, or in acceleration mode the clipped difference quotient of the table's entry."""
     _capi()
     import torch
     from rl_mpc_lanemerging_amd import actor, learner
-    n = 33
-    net, S, states = dyadic_case(shape, n)
-    feat = dyadic_features(S, states)
-    net, j1, j2 = dyadic_finish(net, feat)
-    table = _table(shape[2])
-    q, idx, jerk = actor.q_policy_host(net, feat, table, "jerk")
-    allneg = (q < 0).all(1)
-    tie = (q[:, j1] == q.max(1)) & (q[:, j2] == q.max(1))
-    assert allneg.any() and not allneg.all() and tie.any() and not tie.all() and (idx[tie] == j1).all()
-    assert np.array_equal(q.astype(np.float32).astype(np.float64), q)
-    L = learner.DQNLearner((shape[0], shape[2]), learner.DQNConfig(n_obs=shape[0], n_actions=shape[2], h1=shape[1], batch=16, capacity=64), init=net, ctx=gpu_ctx)
-    L.action_values = table
-    st = {k: torch.as_tensor(np.ascontiguousarray(v), device=_dev()) for k, v in states.items()}
-    path = L.export_q(str(tmp_path / "q.npz"))
-    for label, P in (("view", actor.DQNActor.from_learner(L, n, gpu_ctx, S)), ("file", actor.DQNActor(path, n, gpu_ctx, S))):
-        got = _run(_widen(P), st)
-        assert same(got["feat"], feat), label
-        assert np.array_equal(got["q"].astype(np.float64), q), (label, int((got["q"].astype(np.float64) != q).sum()))
-        assert np.array_equal(got["action"], idx) and same(got["jerk"], jerk), label
+    A, wide = shape[2], shape in NETS_WIDE
+    for variant in Q_WIDE_VARIANTS if wide else (None,):
+        net, S, states, feat, groups, named = _dyadic_policy(shape, variant)
+        n = feat.shape[0]
+        table = _table(A)
+        q, idx, jerk = actor.q_policy_host(net, feat, table, "jerk")
+        allneg = (q < 0).all(1)
+        assert allneg.any() and not allneg.all() and len(set(table.tolist())) == A
+        assert np.array_equal(q.astype(np.float32).astype(np.float64), q)
+        for name, rows in _tied_rows(q, groups).items():
+            print("%s %s: %s holds the maximum on %d rows, %d of them named" % (shape, variant, name, rows.size, named[name].size))
+            assert named[name].size >= 1 and (idx[rows] <= groups[name][0]).all(), name
+        if not wide:                                                # (the one pair: the rows it wins, not every row, and its first column on all of them)
+            tie = _tied_rows(q, groups)["tie"]
+            assert 0 < tie.size < n and (idx[tie] == groups["tie"][0]).all()
+        L = learner.DQNLearner((shape[0], A), learner.DQNConfig(n_obs=shape[0], n_actions=A, h1=shape[1], batch=16, capacity=64), init=net, ctx=gpu_ctx)
+        L.action_values = table
+        st = {k: torch.as_tensor(np.ascontiguousarray(v), device=_dev()) for k, v in states.items()}
+        path = L.export_q(str(tmp_path / ("q%s.npz" % (variant or ""))))
+        for label, P in (("view", actor.DQNActor.from_learner(L, n, gpu_ctx, S)), ("file", actor.DQNActor(path, n, gpu_ctx, S))):
+            got = _run(_widen(P), st)
+            assert same(got["feat"], feat), label
+            assert np.array_equal(got["q"].astype(np.float64), q), (label, int((got["q"].astype(np.float64) != q).sum()))
+            for name, rows in named.items():
+                assert (got["action"][rows] == groups[name][0]).all(), (label, variant, "index on the rows where %s holds the maximum" % name, got["action"][rows].tolist())
+            assert np.array_equal(got["action"], idx) and same(got["jerk"], jerk), label
+        if variant == "lone":
+            small = np.linspace(-0.1, 0.1, A)
+            L.action_values = small
+            acc = states["ego4"][:, 3]
+            want = actor.q_policy_host(net, feat, small, "acceleration", ego_acc=acc, S=S)
+            got = _run(_widen(actor.DQNActor.from_learner(L, n, gpu_ctx, S, mode="acceleration")), st)
+            assert np.array_equal(got["action"], want[1]) and same(got["jerk"], want[2])
+            assert same(got["jerk"], np.clip((small[idx] - acc) / S.TICK_LENGTH, S.MINIMUM_NEGATIVE_JERK, S.MAXIMUM_POSITIVE_JERK))
+            for c in (32, A - 1):
+                assert (idx == c).any() and np.array_equal(got["action"] == c, idx == c)
     gpu_ctx.check_error()
 
 

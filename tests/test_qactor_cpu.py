@@ -7,7 +7,7 @@ import types
 import numpy as np
 import pytest
 
-from discrete_testlib import NETS
+from discrete_testlib import NETS, NETS_WIDE, Q_WIDE_ROWS, Q_WIDE_VARIANTS, actor_table, q_dyadic_policy, tie_groups, tied_rows
 from stmpc_testlib import capi as _capi, header_entries, header_prototypes, header_text
 
 ROWS = 400
@@ -96,6 +96,33 @@ def test_all_negative_rows_never_return_a_pad_index():
         q, idx, jerk = actor.q_policy_host(net, rng.normal(0, 1, (64, n_obs)).astype(np.float32), np.arange(A, dtype=np.float64), "jerk")
         assert (q < 0).all() and idx.min() >= 0 and idx.max() < A and np.array_equal(jerk, idx.astype(np.float64))
         assert np.array_equal(q[np.arange(64), idx], q.max(1))
+
+
+@pytest.mark.parametrize("variant", Q_WIDE_VARIANTS)
+@pytest.mark.parametrize("shape", NETS_WIDE)
+def test_wide_dyadic_policies_cannot_pass_vacuously(shape, variant):
+    """``q_dyadic_policy`` beyond 32 actions, from the float64 twin alone: Q is exact in float32 (the float32 twin equals the float64 one value for
+    value), rows with only negative Q and rows without; "ties": every group of ``tie_groups`` holds the maximum on rows where no lower column ties,
+    and the twin's index there is the group's lowest column; "lone": columns 32 and A - 1 are the twin's index on rows; the table has A distinct
+    values."""
+    _capi()
+    from rl_mpc_lanemerging_amd import actor
+    A = shape[2]
+    net, S, states, feat, groups, named = q_dyadic_policy(shape, variant)
+    table = actor_table(A)
+    q, idx, jerk = actor.q_policy_host(net, feat, table, "jerk")
+    q32, idx32, _ = actor.q_policy_host(net, feat, table, "jerk", dtype=np.float32)
+    assert feat.shape == (Q_WIDE_ROWS, shape[0]) and np.array_equal(q32.astype(np.float64), q) and np.array_equal(idx32, idx) and np.array_equal(jerk, table[idx])
+    allneg = (q < 0).all(1)
+    assert allneg.any() and not allneg.all() and len(set(table.tolist())) == A and idx.max() < A
+    assert set(groups) == (set(tie_groups(A)) if variant == "ties" else {"32", "A - 1"})
+    tied = tied_rows(q, groups)
+    print(shape, variant, {k: (tied[k].size, named[k].size) for k in groups}, "all negative", int(allneg.sum()))
+    for name, cols in groups.items():
+        assert named[name].size >= 1 and (idx[named[name]] == cols[0]).all() and (idx[tied[name]] <= cols[0]).all(), name
+        assert all(np.array_equal(net["w1"][c], net["w1"][cols[0]]) and net["b1"][c] == net["b1"][cols[0]] for c in cols)
+    if variant == "lone":
+        assert (idx == 32).any() and (idx == A - 1).any()
 
 
 def test_acceleration_mode_formula():

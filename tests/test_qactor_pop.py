@@ -12,7 +12,7 @@ import types
 import numpy as np
 import pytest
 
-from discrete_testlib import (JERKS, NAMES, NETS, OUT, SENTINEL, actor_table as _table, dev as _dev, episode_settings as _episode_settings, policy_states as _states,
+from discrete_testlib import (JERKS, NAMES, NETS, NETS_WIDE, OUT, SENTINEL, q_dyadic_policy, actor_table as _table, dev as _dev, episode_settings as _episode_settings, policy_states as _states,
                               run_policy as _run, stream as _stream, stub_env as _stub_env, transitions as _transitions, widen as _widen)
 from stmpc_testlib import ACTOR_KMAX, capi as _capi, same
 
@@ -100,8 +100,39 @@ def _assert_members(got, lone, n_per, label):
 @pytest.mark.parametrize("P", PS)
 @pytest.mark.parametrize("shape", NETS)
 def test_gpu_members_equal_lone_actors(shape, P, n_per, gpu_ctx, restore_settings, tmp_path_factory):
+    _members_equal_lone_actors(shape, P, n_per, gpu_ctx, tmp_path_factory)
+
+
+@pytest.mark.gpu
+def test_gpu_two_members_beyond_one_stride(gpu_ctx, restore_settings, tmp_path_factory):
+    """The same comparison for two members of (20, 32, 40) -- a lane of k_qactor_eval_pop's argmax owns two columns, three output tiles --, 17 rows
+    each, the second in acceleration mode; then two file members of discrete_testlib.q_dyadic_policy's "ties" net, whose copied columns (5, 37),
+    (31, 32), (0, 39) hold the maximum on rows: the population's index there is the group's lowest column, and every output equals the lone
+    actor's, bit for bit."""
+    _capi()
+    import torch
+    from rl_mpc_lanemerging_amd import actor
+    shape = NETS_WIDE[0]
+    _members_equal_lone_actors(shape, 2, 17, gpu_ctx, tmp_path_factory)
+    net, S, states, feat, groups, named = q_dyadic_policy(shape, "ties")
+    n_per, A = feat.shape[0], shape[2]
+    path = str(tmp_path_factory.mktemp("qties") / "q.npz")
+    np.savez(path, **net, action_values=_table(A))
+    st = {k: torch.as_tensor(np.ascontiguousarray(np.concatenate([v, v[::-1]])), device=_dev()) for k, v in states.items()}
+    tables = [_table(A, m) for m in range(2)]
+    pop = _widen(actor.QActorPopulation([actor.DQNActor(path, 1, gpu_ctx, S, action_values=tables[m]) for m in range(2)], n_per, gpu_ctx, S))
+    got = _run(pop, st)
+    lone = [_run(_widen(actor.DQNActor(path, n_per, gpu_ctx, S, action_values=tables[m])), _slice(st, slice(m * n_per, (m + 1) * n_per))) for m in range(2)]
+    _assert_members(got, lone, n_per, "ties")
+    for name, rows in named.items():
+        assert rows.size >= 1 and (got["action"][rows] == groups[name][0]).all() and (got["action"][2 * n_per - 1 - rows] == groups[name][0]).all(), name
+    assert same(got["feat"][:n_per], feat) and same(got["jerk"][n_per:], tables[1][got["action"][n_per:]])
+    gpu_ctx.check_error()
+
+
+def _members_equal_lone_actors(shape, P, n_per, gpu_ctx, tmp_path_factory):
     """jerk, action, q and feat of every member equal a lone DQNActor's on that slice.  The members mix a file actor, an online view, a target view
-    (after an update with target_period 4: it differs from online) and a view of a DQNPopulation's member, each with its own table; at A = 20 the
+    (after an update with target_period 4: it differs from online) and a view of a DQNPopulation's member, each with its own table; at A = 20 (and 40) the
     odd members are in acceleration mode, on states that clip at either edge and states inside.  The population is evaluated through the raw
     entry on sentinel-filled outputs with spare rows beyond P * n_per_member, which keep the sentinel."""
     _capi()
@@ -109,12 +140,12 @@ def test_gpu_members_equal_lone_actors(shape, P, n_per, gpu_ctx, restore_setting
     from rl_mpc_lanemerging_amd import actor
     n, A = P * n_per, shape[2]
     S, st = _states(n)
-    if A == 20:
+    if A in (20, 40):
         _accel_states(st)
     src = _sources(gpu_ctx, shape, tmp_path_factory)
     off = N_PER.index(n_per)
     kinds = [KINDS[(m + off) % 4] for m in range(P)]
-    modes = ["acceleration" if A == 20 and m % 2 else "jerk" for m in range(P)]
+    modes = ["acceleration" if A in (20, 40) and m % 2 else "jerk" for m in range(P)]
     tables = [_table(A, m, modes[m] == "acceleration") for m in range(P)]
     members = [_make(src, kinds[m], 1, gpu_ctx, S, tables[m], modes[m]) for m in range(P)]
     pop = actor.QActorPopulation(members, n_per, gpu_ctx, S)
