@@ -1071,6 +1071,54 @@ int  stmpc_c51_dzout_read(stmpc_c51 *learner, float *values, int64_t count);
 int  stmpc_c51_padded_read(stmpc_c51 *learner, int slot, float *values, int64_t count);
 
 /*
+ * The noisy output layer of the C51 learner: factorised-Gaussian noise (Fortunato et al. 2018, "Noisy Networks for Exploration"; Hessel et al. 2018,
+ * "Rainbow", section "Noisy Nets") on the layer h1 -> n_out, n_out = (n_actions + dueling) * n_atoms -- the sixth piece of the reference's third
+ * agent (rainbow.py: the `all` library's rainbow preset), which explores through it instead of epsilon-greedy.  It restates the published layer;
+ * the library is not available, so parity with its own (its sigma0 included) stays unpinned.
+ *   W_eff[n][k] = mu_W[n][k] + sigma_W[n][k] * f(e_out[n]) * f(e_in[k]),  b_eff[n] = mu_b[n] + sigma_b[n] * f(e_out[n]),  f(x) = sign(x) sqrt|x|
+ * with e ~ N(0, 1), h1 + n_out of them per draw.  The learner's existing parameters ARE mu: the slots, stmpc_c51actor_view, the greedy
+ * stmpc_c51_act_device and everything else that evaluates the mean network keep their meaning and their bits.  (Additive: new entries only, under a
+ * prefix of their own because stmpc_c51_ is a closed set; no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8; a learner on which
+ * enable never ran computes what it computed.)  Once enabled, stmpc_c51_update_device, _grads_device, _targets_device and _dist_device run the
+ * noisy sequence: one update is four launches (six with prioritised replay) -- the draw and the effective parameters of the online and the target
+ * net (independent draws, keyed by seed, update index and net), the pass and the weight gradients on them, then Adam on sigma (g_sigma_W = g_W *
+ * f_out * f_in, g_sigma_b = g_b * f_out, moments of its own, the target's sigma copied where the hard copy runs) and on mu.  The gradient slot
+ * holds the gradient with respect to the effective parameters, which is mu's.
+ *   enable          (rainbow.py) on a FRESH learner: STMPC_EINVAL after a push or an update, for a second enable, for a population's member (the
+ *                   message names stmpc_pop_noisy_c51_enable, behind the population's entries), and for a sigma0 that is negative or not finite.  sigma starts at sigma0 / sqrt(h1)
+ *                   everywhere (0.5: the paper's).  Synchronises
+ *   set / get_params    (rainbow.py) HOST float32 [n_out * h1 + n_out]: W1-shaped [n_out][h1] | [n_out], unpadded; slots STMPC_NOISY_SIGMA (the online
+ *                   net's sigma), _SIGMA_TARGET, _SIGMA_M, _SIGMA_V (Adam's moments).  Synchronise
+ *   act_device      (rainbow.py) stmpc_c51_act_device on a fresh ACTING draw (a stream and a counter of their own: counters[5] of get / set_state,
+ *                   advanced by every call; the learning draws and the exploring-call counter do not move unless eps > 0, which is honoured)
+ *   debug_read      (rainbow.py) debug, HOST: f(e_in) [h1] | f(e_out) [n_out] of the last learning draw of the online net, of the target net, and of the
+ *                   last acting draw (STMPC_NOISY_F_ONLINE, _F_TARGET, _F_ACT; count h1 + n_out); their effective W1 [n_out][h1] | b1 [n_out]
+ *                   (STMPC_NOISY_WEFF_ONLINE ...; count n_out * h1 + n_out); the same in the padded layout [Ap][h1p] | [Ap], pad rows and columns exact
+ *                   zeros (STMPC_NOISY_WEFF_PADDED_ONLINE ...; count Ap * h1p + Ap).  Synchronises
+ */
+#define STMPC_NOISY_SIGMA 0
+#define STMPC_NOISY_SIGMA_TARGET 1
+#define STMPC_NOISY_SIGMA_M 2
+#define STMPC_NOISY_SIGMA_V 3
+#define STMPC_NOISY_F_ONLINE 0
+#define STMPC_NOISY_F_TARGET 1
+#define STMPC_NOISY_F_ACT 2
+#define STMPC_NOISY_WEFF_ONLINE 3
+#define STMPC_NOISY_WEFF_TARGET 4
+#define STMPC_NOISY_WEFF_ACT 5
+#define STMPC_NOISY_WEFF_PADDED_ONLINE 6
+#define STMPC_NOISY_WEFF_PADDED_TARGET 7
+#define STMPC_NOISY_WEFF_PADDED_ACT 8
+typedef struct stmpc_noisy_cfg {
+    double sigma0;                   /* sigma starts at sigma0 / sqrt(h1) (0.5: Fortunato et al. 2018, section 3.2) */
+} stmpc_noisy_cfg;
+int  stmpc_noisy_c51_enable(stmpc_c51 *learner, const stmpc_noisy_cfg *cfg);
+int  stmpc_noisy_c51_set_params(stmpc_c51 *learner, int slot, const float *values, int64_t count);
+int  stmpc_noisy_c51_get_params(stmpc_c51 *learner, int slot, float *values, int64_t count);
+int  stmpc_noisy_c51_act_device(stmpc_c51 *learner, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream);
+int  stmpc_noisy_c51_debug_read(stmpc_c51 *learner, int what, float *out, int64_t count);
+
+/*
  * A population of C51 learners: the population axis of stmpc_ddpg_pop_* / stmpc_pop_td3_* / stmpc_pop_dqn_* for the categorical learner above.  P
  * independent C51 learners -- each its own ring, logits network, target, Adam state, counters, seed and constants, the support [v_min, v_max],
  * double_dqn, target_period, replay_start and n_step included -- share one discrete-action vector environment and advance with ONE launch per
@@ -1130,6 +1178,23 @@ int  stmpc_pop_c51_per_enable(stmpc_c51_pop *pop, const stmpc_per_cfg *cfgs, con
 int  stmpc_pop_c51_multi_step_enable(stmpc_c51_pop *pop, const stmpc_nstep_cfg *cfgs, int P);
 int  stmpc_pop_c51_replay_read(stmpc_c51 *learner, int64_t first, int64_t count, float *rows);
 int  stmpc_pop_c51_multi_step_window(stmpc_c51 *learner, const int64_t *idx, int n_idx, double *out);
+
+/*
+ * The noisy output layer for a population of C51 learners (rainbow.py: the noisy layers of the `all` library's rainbow preset, one run per member).
+ * (Additive: two new entries under a prefix of their own -- stmpc_pop_c51_ is a closed set --, STMPC_ABI_VERSION stays 8.)  The members share on /
+ * off; sigma0 is a member's own.  Member m stays bit-identical to a lone noisy stmpc_c51 with its cfg, seed and sigma0 driven on its slice: the draws
+ * are keyed by the member's seed and its own counters, and nothing crosses members.  stmpc_pop_c51_update_device then runs the noisy sequence, four
+ * launches per update whatever P is (six with prioritised members); stmpc_pop_c51_act_device stays the mean networks'.  The lone set / get_params,
+ * debug_read, act_device and stmpc_c51_set / get_state work on a borrowed member.
+ *   pop_enable      (rainbow.py) cfgs HOST [P], member m gets cfgs[m]; one call, on fresh members (before per_enable or multi_step_enable, or after:
+ *                   both orders work).  STMPC_EINVAL for P other than the member count, a second call, a sigma0 that is negative or not finite, and
+ *                   members that have pushed or updated.  Synchronises
+ *   pop_act_device  (rainbow.py) stmpc_noisy_c51_act_device per member with stmpc_pop_c51_act_device's arguments: every member takes an acting draw
+ *                   of its own (its counters[5] advances); eps HOST fp64 [n_eps], n_eps = P, honoured per member
+ */
+int  stmpc_pop_noisy_c51_enable(stmpc_c51_pop *pop, const stmpc_noisy_cfg *cfgs, int P);
+int  stmpc_pop_noisy_c51_act_device(stmpc_c51_pop *pop, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps,
+                                    int32_t *d_action, float *d_debug_q, void *stream);
 
 /*
  * A Q-network as the policy of the combined controller and of the first-step shield: DQNAgent.get_control (dqn.py:375-380) -- state vector -> Q ->

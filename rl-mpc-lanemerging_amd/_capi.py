@@ -288,6 +288,11 @@ class C51Cfg(C.Structure):
     reserved = property(lambda self: self.dueling, lambda self, value: setattr(self, "dueling", value))
 
 
+class NoisyCfg(C.Structure):
+    """``stmpc_noisy_cfg`` (include/stmpc.h): the noisy output layer's initial sigma is ``sigma0 / sqrt(h1)``."""
+    _fields_ = [("sigma0", C.c_double)]
+
+
 class ProfileTotals(C.Structure):
     _fields_ = [("launches", C.c_int64), ("episodes", C.c_int64), ("solve_ms", C.c_double), ("dp_kernel_ms", C.c_double)]
 
@@ -327,6 +332,8 @@ EXPORTS = (
     "stmpc_c51_push_device", "stmpc_c51_act_device", "stmpc_c51_update_device", "stmpc_c51_grads_device", "stmpc_c51_targets_device",
     "stmpc_c51_dist_device", "stmpc_c51_project_device", "stmpc_c51_gather_device", "stmpc_c51_stats_device", "stmpc_c51_per_enable",
     "stmpc_c51_per_tree_read", "stmpc_c51_per_last_device", "stmpc_c51_multi_step_enable", "stmpc_c51_replay_read", "stmpc_c51_dzout_read", "stmpc_c51_padded_read",
+    "stmpc_noisy_c51_enable", "stmpc_noisy_c51_set_params", "stmpc_noisy_c51_get_params", "stmpc_noisy_c51_act_device", "stmpc_noisy_c51_debug_read",
+    "stmpc_pop_noisy_c51_enable", "stmpc_pop_noisy_c51_act_device",
     "stmpc_pop_dqn_create", "stmpc_pop_dqn_destroy", "stmpc_pop_dqn_size", "stmpc_pop_dqn_member", "stmpc_pop_dqn_act_device",
     "stmpc_pop_dqn_push_device", "stmpc_pop_dqn_update_device", "stmpc_pop_dqn_stats_device", "stmpc_pop_dqn_per_enable", "stmpc_pop_dqn_replay_read",
     "stmpc_pop_c51_create", "stmpc_pop_c51_destroy", "stmpc_pop_c51_size", "stmpc_pop_c51_member", "stmpc_pop_c51_act_device",
@@ -370,6 +377,9 @@ DQN_GRAD = 4                          # STMPC_DQN_GRAD: the gradient, for dqn_pa
 C51_SLOTS = DQN_SLOTS                 # STMPC_C51_Q ... STMPC_C51_Q_V
 C51_GRAD = 4                          # STMPC_C51_GRAD: the gradient, for c51_padded_read
 C51_MAX_LOGITS = 1024                 # STMPC_C51_MAX_LOGITS
+NOISY_SLOTS = ("sigma", "sigma_target", "sigma_m", "sigma_v")      # STMPC_NOISY_SIGMA ... STMPC_NOISY_SIGMA_V
+NOISY_F = {"online": 0, "target": 1, "act": 2}                      # STMPC_NOISY_F_ONLINE ...; + 3: STMPC_NOISY_WEFF_*, + 6: STMPC_NOISY_WEFF_PADDED_*
+NOISY_DRAWS = 5                       # the counters' slot of a noisy C51 learner's acting draws
 NSTEP_MAX = 16                        # STMPC_NSTEP_MAX
 DONE_COL = 67                         # the replay row's done column (terminated || truncated) on a learner with n_step > 1
 DQN_ACTION_COL = 66                   # the replay row's action column of a DQN learner
@@ -577,6 +587,13 @@ def load():
     lib.stmpc_c51_multi_step_enable.argtypes = [vp, C.POINTER(NStepCfg)]
     lib.stmpc_c51_replay_read.argtypes = [vp, C.c_int64, C.c_int64, fp]
     lib.stmpc_c51_dzout_read.argtypes = [vp, fp, C.c_int64]
+    lib.stmpc_noisy_c51_enable.argtypes = [vp, C.POINTER(NoisyCfg)]
+    lib.stmpc_noisy_c51_set_params.argtypes = list(lib.stmpc_c51_set_params.argtypes)
+    lib.stmpc_noisy_c51_get_params.argtypes = list(lib.stmpc_c51_get_params.argtypes)
+    lib.stmpc_noisy_c51_act_device.argtypes = list(lib.stmpc_c51_act_device.argtypes)
+    lib.stmpc_noisy_c51_debug_read.argtypes = [vp, C.c_int, fp, C.c_int64]
+    lib.stmpc_pop_noisy_c51_enable.argtypes = [vp, C.POINTER(NoisyCfg), C.c_int]
+    lib.stmpc_pop_noisy_c51_act_device.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_double), C.c_int, vp, vp, vp]
     lib.stmpc_pop_dqn_create.argtypes = [vp, C.POINTER(DQNCfg), C.c_int, C.POINTER(vp)]
     lib.stmpc_pop_dqn_destroy.argtypes = [vp]
     lib.stmpc_pop_dqn_destroy.restype = None
@@ -1290,6 +1307,38 @@ class Context:
         out = np.zeros((((int(batch) + 15) & ~15), ((int(n_logits) + 15) & ~15)), dtype=np.float32)
         self._chk(self._lib.stmpc_c51_dzout_read(handle, out.ctypes.data_as(C.POINTER(C.c_float)), int(out.size)))
         return out
+
+    # -- the noisy output layer of a C51 learner (stmpc_noisy_c51_*) ----
+    def noisy_c51_enable(self, handle, sigma0):
+        self._chk(self._lib.stmpc_noisy_c51_enable(handle, C.byref(NoisyCfg(sigma0=float(sigma0)))))
+
+    def noisy_c51_set_params(self, handle, slot, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        self._chk(self._lib.stmpc_noisy_c51_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+
+    def noisy_c51_get_params(self, handle, slot, count):
+        flat = np.empty(int(count), dtype=np.float32)
+        self._chk(self._lib.stmpc_noisy_c51_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        return flat
+
+    def noisy_c51_act(self, handle, N, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
+        self._chk(self._lib.stmpc_noisy_c51_act_device(handle, int(N), d_obs, int(obs_stride), float(eps), d_action, d_debug_q, stream))
+
+    def noisy_c51_debug_read(self, handle, what, count):
+        """Debug: quantity ``what`` (STMPC_NOISY_F_* / _WEFF_* / _WEFF_PADDED_*) as float32 [count]; synchronises."""
+        out = np.empty(int(count), dtype=np.float32)
+        self._chk(self._lib.stmpc_noisy_c51_debug_read(handle, int(what), out.ctypes.data_as(C.POINTER(C.c_float)), int(out.size)))
+        return out
+
+    def c51_pop_noisy_enable(self, handle, sigma0s):
+        """``sigma0s``: one value per member (``stmpc_pop_noisy_c51_enable``)."""
+        table = (NoisyCfg * len(sigma0s))(*[NoisyCfg(sigma0=float(s)) for s in sigma0s])
+        self._chk(self._lib.stmpc_pop_noisy_c51_enable(handle, table, len(sigma0s)))
+
+    def c51_pop_noisy_act(self, handle, n_per_member, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
+        eps = np.ascontiguousarray(eps, dtype=np.float64)
+        self._chk(self._lib.stmpc_pop_noisy_c51_act_device(handle, int(n_per_member), d_obs, int(obs_stride), eps.ctypes.data_as(C.POINTER(C.c_double)), int(eps.size),
+                                                           d_action, d_debug_q, stream))
 
     # -- populations of discrete learners (stmpc_pop_dqn_*, stmpc_pop_c51_*): P learners, one launch per kernel (dqn.py:257-359); written once as the
     # lone learners' are, and bound as ``dqn_pop_<name>`` and ``c51_pop_<name>`` below the class

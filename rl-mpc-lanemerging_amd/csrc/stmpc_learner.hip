@@ -20,6 +20,7 @@
 #include "stmpc_dqn_pop_kernels.hpp"
 #include "stmpc_c51_kernels.hpp"
 #include "stmpc_c51_pop_kernels.hpp"
+#include "stmpc_c51_noisy_kernels.hpp"
 #include "stmpc_qactor_kernels.hpp"
 #include "stmpc_c51actor_kernels.hpp"
 #include "stmpc_qactor_pop_kernels.hpp"
@@ -1131,6 +1132,7 @@ template <class H> struct QLearner {
     size_t lds = 0;
     Grid grid{};
     bool pop_member = false;                // owned by a population (QPop), whose device tables hold copies of dev and base()
+    typename H::Extra ex;                   // what one head has on top (C51Head: the noisy output layer's buffers; stmpc_noisy_c51_enable)
     DdpgDev &base() { return H::base(dev); }        // dev.base of a DqnDev, dev.dq.base of a C51Dev
 };
 
@@ -1138,7 +1140,11 @@ struct DqnHead {
     using Cfg = stmpc_dqn_cfg;
     using Dev = DqnDev;
     using L = QLearner<DqnHead>;
+    struct Extra {};
     static constexpr const char *name = "DQN", *shared = "n_obs, h1, n_actions, batch and capacity";
+    static bool noisy(const L &) { return false; }
+    static void noisy_update(const L &, float, hipStream_t) {}
+    static void noisy_grads(const L &, hipStream_t) {}
     static constexpr const char *pop_per_enable = "stmpc_pop_dqn_per_enable", *pop_nstep_enable = "stmpc_pop_nstep_enable_dqn";      // (what a member's refusals name)
     static DdpgDev &base(Dev &d) { return d.base; }
     static DqnDev &dq(Dev &d) { return d; }
@@ -1186,10 +1192,28 @@ static int c51_check_width(int n_actions, int n_atoms, int dueling) {
     return fail(STMPC_EINVAL, "n_actions * n_atoms = " + std::to_string(W) + " exceeds " + std::to_string(STMPC_C51_MAX_LOGITS));
 }
 
+// The noisy output layer of a C51 learner (stmpc_noisy_c51_enable; kernels in stmpc_c51_noisy_kernels.hpp): sigma, its target and Adam moments, the f
+// vectors, and per draw (online, target, acting) the effective parameter array and its packed W1, which a shadow of the learner's struct points at.
+struct C51Noisy {
+    bool on = false;
+    double sigma0 = 0;
+    DevBuf sig, sigt, sm, sv, f, we[C51_NZ_SETS], pe[C51_NZ_SETS];
+    C51NoisyDev dev{};
+    // the learner's struct as it is now with the network's effective copies in the online (and target) network's place
+    C51Dev shadow(const C51Dev &own, bool acting) const {
+        C51Dev s = own;
+        DdpgNet &n = s.dq.base.q;
+        if (acting) { n.w = dev.we2; n.p1 = dev.pe2; }
+        else { n.w = dev.we0; n.p1 = dev.pe0; n.wt = dev.we1; n.t1 = dev.pe1; }
+        return s;
+    }
+};
+
 struct C51Head {
     using Cfg = stmpc_c51_cfg;
     using Dev = C51Dev;
     using L = QLearner<C51Head>;
+    using Extra = C51Noisy;
     static constexpr const char *name = "C51", *shared = "n_obs, h1, n_actions, n_atoms, batch and capacity";      // (and the head: dueling or not)
     static constexpr const char *pop_per_enable = "stmpc_pop_c51_per_enable", *pop_nstep_enable = "stmpc_pop_c51_multi_step_enable";
     static DdpgDev &base(Dev &d) { return d.dq.base; }
@@ -1218,9 +1242,32 @@ struct C51Head {
         return STMPC_OK;
     }
     // the forward / backward pass has a kernel per head (d_out, d_dist: the debug outputs of stmpc_c51_dist_device, null in an update)
+    // (a noisy learner's pass runs on the shadow struct behind the draw's compose: noisy_fwd)
+    static void fwd_on(const Dev &dev, const L &t, int gate, float *d_out, float *d_dist, hipStream_t st) {
+        if (dev.dueling) hipLaunchKernelGGL(k_c51_fwd_duel, dim3(t.grid.tiles), dim3(AT_THREADS), t.lds, st, dev, t.cfg.batch, gate, d_out, d_dist);
+        else hipLaunchKernelGGL(k_c51_fwd, dim3(t.grid.tiles), dim3(AT_THREADS), t.lds, st, dev, t.cfg.batch, gate, d_out, d_dist);
+    }
     static void fwd_launch(const L &t, int gate, float *d_out, float *d_dist, hipStream_t st) {
-        if (t.dev.dueling) hipLaunchKernelGGL(k_c51_fwd_duel, dim3(t.grid.tiles), dim3(AT_THREADS), t.lds, st, t.dev, t.cfg.batch, gate, d_out, d_dist);
-        else hipLaunchKernelGGL(k_c51_fwd, dim3(t.grid.tiles), dim3(AT_THREADS), t.lds, st, t.dev, t.cfg.batch, gate, d_out, d_dist);
+        if (t.ex.on) noisy_fwd(t, gate, d_out, d_dist, st);
+        else fwd_on(t.dev, t, gate, d_out, d_dist, st);
+    }
+    // the noisy learner's launches: the learning draw of the current update index, the pass and the weight gradients on the shadow struct ...
+    static bool noisy(const L &t) { return t.ex.on; }
+    static int compose_blocks(const L &t) { return (t.h1p + (t.h1p + 1) * t.Ap + 255) / 256; }
+    static void noisy_fwd(const L &t, int gate, float *d_out, float *d_dist, hipStream_t st) {
+        hipLaunchKernelGGL(k_c51_noisy_compose, dim3(compose_blocks(t)), dim3(256), 0, st, t.dev, t.ex.dev, 0, gate);
+        fwd_on(t.ex.shadow(t.dev, false), t, gate, d_out, d_dist, st);
+    }
+    static void noisy_grads(const L &t, hipStream_t st) {
+        noisy_fwd(t, 0, nullptr, nullptr, st);
+        hipLaunchKernelGGL(k_c51_wgrad, dim3(t.grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t.ex.shadow(t.dev, false), t.rp.Bp, 0);
+    }
+    // ... and one update behind the sampling step: compose, fwd, wgrad, (the priority update,) sigma's and mu's Adam
+    static void noisy_update(const L &t, float lr, hipStream_t st) {
+        noisy_fwd(t, 1, nullptr, nullptr, st);
+        hipLaunchKernelGGL(k_c51_wgrad, dim3(t.grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t.ex.shadow(t.dev, false), t.rp.Bp, 1);
+        per_launch_update(t.rp, t.dev.dq.base, st);
+        hipLaunchKernelGGL(k_c51_noisy_adam, dim3(t.grid.ablocks), dim3(256), 0, st, t.dev, t.ex.dev, lr, 1);
     }
     static void fwd(const L &t, int gate, hipStream_t st) { fwd_launch(t, gate, nullptr, nullptr, st); }
     static void wgrad(const L &t, int gate, hipStream_t st) { hipLaunchKernelGGL(k_c51_wgrad, dim3(t.grid.jobs), dim3(64 * DG_WG_WAVES), 0, st, t.dev, t.rp.Bp, gate); }
@@ -1355,6 +1402,7 @@ template <class L> int q_update(L *t, int n_updates, double lr, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     for (int u = 0; u < n_updates; ++u) {                            // three launches, five with prioritised replay, whatever the counters say
         per_launch_sample(t->rp, t->base(), 1, st);
+        if (L::Head::noisy(*t)) { L::Head::noisy_update(*t, (float)lr, st); continue; }      // (four launches, six with prioritised replay)
         L::Head::fwd(*t, 1, st);
         L::Head::wgrad(*t, 1, st);
         per_launch_update(t->rp, t->base(), st);
@@ -1369,8 +1417,11 @@ template <class L> int q_grads(L *t, float *d_grad, void *stream) {
     HIPCHK(hipSetDevice(t->rp.device));
     hipStream_t st = (hipStream_t)stream;
     per_launch_sample(t->rp, t->base(), 0, st);
-    L::Head::fwd(*t, 0, st);
-    L::Head::wgrad(*t, 0, st);
+    if (L::Head::noisy(*t)) L::Head::noisy_grads(*t, st);            // (the gradient with respect to the effective parameters: mu's)
+    else {
+        L::Head::fwd(*t, 0, st);
+        L::Head::wgrad(*t, 0, st);
+    }
     L::Head::unpad(*t, d_grad, st);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
@@ -1472,7 +1523,15 @@ int stmpc_c51_create(stmpc_ctx *c, const stmpc_c51_cfg *g, stmpc_c51 **out) { re
 void stmpc_c51_destroy(stmpc_c51 *t) { q_destroy(t); }
 int stmpc_c51_set_params(stmpc_c51 *t, int slot, const float *values, int64_t count) { return q_set_params(t, slot, values, count); }
 int stmpc_c51_get_params(stmpc_c51 *t, int slot, float *values, int64_t count) { return q_get_params(t, slot, values, count); }
-int stmpc_c51_set_state(stmpc_c51 *t, const int64_t *counters, const float *beta_pow) { return q_set_state(t, counters, beta_pow); }
+int stmpc_c51_set_state(stmpc_c51 *t, const int64_t *counters, const float *beta_pow) {
+    // a noisy learner's acting-draw counter travels in the counters' slot C51_NOISY_DRAWS (get_state reads all of them); checked before anything is written
+    if (t && counters && t->ex.on && counters[C51_NOISY_DRAWS] < 0) return fail(STMPC_EINVAL, "counters out of range");
+    TRY(q_set_state(t, counters, beta_pow));
+    if (!t->ex.on) return STMPC_OK;
+    const long long draws = counters[C51_NOISY_DRAWS];
+    HIPCHK(hipMemcpy(t->rp.cnt.as<long long>() + C51_NOISY_DRAWS, &draws, sizeof draws, hipMemcpyHostToDevice));
+    return STMPC_OK;
+}
 int stmpc_c51_get_state(stmpc_c51 *t, int64_t *counters, float *beta_pow) { return q_get_state(t, counters, beta_pow); }
 int stmpc_c51_push_device(stmpc_c51 *t, int N, const float *d_obs, const float *d_next_obs, const float *d_final_obs, int obs_stride, const int32_t *d_action,
                           const double *d_reward, const uint8_t *d_terminated, const uint8_t *d_truncated, void *stream) {
@@ -1523,6 +1582,113 @@ int stmpc_c51_dzout_read(stmpc_c51 *t, float *values, int64_t count) {
 
 }  // extern "C"
 
+// ---- the noisy output layer of a C51 learner (stmpc_noisy_c51_*; kernels in stmpc_c51_noisy_kernels.hpp) -------------------------------------------
+namespace {
+// a sigma slot between the C-ABI's layout (W1-shaped [n_out][h1] | [n_out]) and the padded one ([Ap][h1p] | [Ap])
+std::vector<Seg> noisy_layout(const stmpc_c51 *t) {
+    return {{C51Head::n_out(t->cfg), t->cfg.h1, 0, (size_t)t->h1p}, {1, C51Head::n_out(t->cfg), (size_t)t->Ap * t->h1p, 0}};
+}
+size_t noisy_len(const stmpc_c51 *t) { return (size_t)t->Ap * t->h1p + t->Ap; }
+float *noisy_slot(const C51Noisy &z, int slot) { float *const p[4] = {z.dev.sig, z.dev.sigt, z.dev.sm, z.dev.sv}; return p[slot]; }
+int noisy_check(const stmpc_c51 *t) {
+    if (!t) return fail(STMPC_EINVAL, "learner is NULL");
+    if (!t->ex.on) return fail(STMPC_EINVAL, "the noisy output layer is not enabled on this learner (stmpc_noisy_c51_enable)");
+    return STMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// the checks of a stmpc_noisy_cfg and of the learner it goes onto (fresh; synchronises), then the buffers and sigma's start
+static int noisy_attach(stmpc_c51 *t, const stmpc_noisy_cfg *g) {
+    if (!(g->sigma0 >= 0) || !std::isfinite(g->sigma0)) return fail(STMPC_EINVAL, "sigma0 must be finite and not negative");
+    if (t->ex.on) return fail(STMPC_EINVAL, "the noisy output layer is already enabled on this learner");
+    long long cn[DG_NCNT];
+    TRY(read_back(t->rp.device, cn, t->rp.cnt.p, sizeof cn));
+    if (cn[DG_FILL] != 0 || cn[DG_CURSOR] != 0 || cn[DG_FRAMES] != 0 || cn[DG_UPDATES] != 0)
+        return fail(STMPC_EINVAL, "the noisy output layer can be enabled on a fresh learner only (fill is " + std::to_string(cn[DG_FILL]) + ", updates " +
+                                      std::to_string(cn[DG_UPDATES]) + ")");
+    C51Noisy &z = t->ex;
+    const size_t ns = noisy_len(t), nf = (size_t)C51_NZ_SETS * (t->h1p + t->Ap);
+    TRY(ddpg_zero(z.sig, ns * sizeof(float)));
+    TRY(ddpg_zero(z.sigt, ns * sizeof(float)));
+    TRY(ddpg_zero(z.sm, ns * sizeof(float)));
+    TRY(ddpg_zero(z.sv, ns * sizeof(float)));
+    TRY(ddpg_zero(z.f, nf * sizeof(float)));
+    for (int s = 0; s < C51_NZ_SETS; ++s) {
+        TRY(ddpg_zero(z.we[s], (size_t)t->np * sizeof(float)));
+        TRY(ddpg_zero(z.pe[s], (size_t)t->Ap * t->h1p * sizeof(float)));
+    }
+    z.dev.sig = z.sig.as<float>(); z.dev.sigt = z.sigt.as<float>(); z.dev.sm = z.sm.as<float>(); z.dev.sv = z.sv.as<float>(); z.dev.f = z.f.as<float>();
+    z.dev.we0 = z.we[0].as<float>(); z.dev.we1 = z.we[1].as<float>(); z.dev.we2 = z.we[2].as<float>();
+    z.dev.pe0 = z.pe[0].as<float>(); z.dev.pe1 = z.pe[1].as<float>(); z.dev.pe2 = z.pe[2].as<float>();
+    // sigma = sigma0 / sqrt(h1) everywhere, the target's too (float32 of the fp64 quotient); pad rows and columns stay zero
+    std::vector<float> flat((size_t)C51Head::n_out(t->cfg) * (t->cfg.h1 + 1), (float)(g->sigma0 / std::sqrt((double)t->cfg.h1))), pad(ns, 0.f);
+    slot_move(noisy_layout(t), flat.data(), pad.data(), true);
+    HIPCHK(hipMemcpy(z.dev.sig, pad.data(), ns * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(z.dev.sigt, pad.data(), ns * sizeof(float), hipMemcpyHostToDevice));
+    z.sigma0 = g->sigma0;
+    z.on = true;
+    return STMPC_OK;
+}
+
+int stmpc_noisy_c51_enable(stmpc_c51 *t, const stmpc_noisy_cfg *g) {
+    if (!t || !g) return fail(STMPC_EINVAL, "NULL argument");
+    if (t->pop_member)
+        return fail(STMPC_EINVAL, "this learner is a member of a population: the noisy output layer is enabled on the population (stmpc_pop_noisy_c51_enable)");
+    return noisy_attach(t, g);
+}
+
+int stmpc_noisy_c51_set_params(stmpc_c51 *t, int slot, const float *values, int64_t count) {
+    TRY(noisy_check(t));
+    TRY(slot_args(t, values, slot, 4));
+    return slot_set(t->rp.device, noisy_layout(t), noisy_len(t), noisy_slot(t->ex, slot), values, count, false, [] {});
+}
+
+int stmpc_noisy_c51_get_params(stmpc_c51 *t, int slot, float *values, int64_t count) {
+    TRY(noisy_check(t));
+    TRY(slot_args(t, values, slot, 4));
+    return slot_get(t->rp.device, noisy_layout(t), noisy_len(t), noisy_slot(t->ex, slot), values, count);
+}
+
+int stmpc_noisy_c51_act_device(stmpc_c51 *t, int N, const float *d_obs, int obs_stride, double eps, int32_t *d_action, float *d_debug_q, void *stream) {
+    TRY(noisy_check(t));
+    if (N < 0 || obs_stride < t->cfg.n_obs) return fail(STMPC_EINVAL, "N negative, or obs_stride shorter than the observation");
+    if (!(eps >= 0 && eps <= 1)) return fail(STMPC_EINVAL, "eps must be in 0 ... 1");
+    if (N == 0) return STMPC_OK;
+    if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(t->rp.device));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_c51_noisy_compose, dim3(C51Head::compose_blocks(*t)), dim3(256), 0, st, t->dev, t->ex.dev, 1, 0);
+    hipLaunchKernelGGL(k_c51_act, dim3((N + AT_TM - 1) / AT_TM), dim3(AT_THREADS), t->lds, st, t->ex.shadow(t->dev, true), N, d_obs, obs_stride, (float)eps,
+                       eps > 0 ? 1 : 0, d_action, d_debug_q);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
+int stmpc_noisy_c51_debug_read(stmpc_c51 *t, int what, float *out, int64_t count) {
+    TRY(noisy_check(t));
+    if (!out || what < 0 || what >= 3 * C51_NZ_SETS) return fail(STMPC_EINVAL, "NULL argument, or no such quantity");
+    const int set = what % C51_NZ_SETS, h1 = t->cfg.h1, W = C51Head::n_out(t->cfg);
+    const size_t ns = noisy_len(t);
+    if (what < STMPC_NOISY_WEFF_ONLINE) {                            // f(e_in) [h1] | f(e_out) [n_out]
+        if (count != (int64_t)h1 + W) return fail(STMPC_EINVAL, "count is not h1 + the output rows");
+        std::vector<float> pad((size_t)t->h1p + t->Ap);
+        TRY(read_back(t->rp.device, pad.data(), t->ex.dev.f + (size_t)set * pad.size(), pad.size() * sizeof(float)));
+        memcpy(out, pad.data(), h1 * sizeof(float));
+        memcpy(out + h1, pad.data() + t->h1p, W * sizeof(float));
+        return STMPC_OK;
+    }
+    const float *we = t->ex.we[set].as<float>() + dg_o_w1(t->h1p);    // (W1 | b1 are contiguous in the parameter layout)
+    if (what >= STMPC_NOISY_WEFF_PADDED_ONLINE) {
+        if (count != (int64_t)ns) return fail(STMPC_EINVAL, "count is not the length of the padded W1 | b1");
+        return read_back(t->rp.device, out, we, ns * sizeof(float));
+    }
+    return slot_get(t->rp.device, noisy_layout(t), ns, we, out, count);
+}
+
+}  // extern "C"
+
 // ---- populations of discrete learners (stmpc_pop_dqn_*, stmpc_pop_c51_*): P learners of the section above, one launch per kernel, written once for
 // both heads; kernels in stmpc_dqn_pop_kernels.hpp and stmpc_c51_pop_kernels.hpp, prioritised replay and the statistics on the core's DdpgDev table
 // with stmpc_per_pop_kernels.hpp's and stmpc_ddpg_pop_kernels.hpp's kernels -------------------------------------------------------------------------
@@ -1534,9 +1700,36 @@ template <class L> struct QPop {
     std::vector<L *> members;               // owned; made by q_create, so every lone entry works on a borrowed member
     DevBuf table;                           // Dev [P]: the members' structs (q_pop_upload); a C51 member's v_min, v_max and dz travel in its own
     const Dev *dev() const { return table.as<Dev>(); }
+    // one update's launches behind the sampling step, where the population has a sequence of its own (a noisy C51 population): false -- none
+    bool own_update(const Grid &, int, int, const DdpgLr &, hipStream_t) const { return false; }
 };
 struct stmpc_dqn_pop : QPop<stmpc_dqn> {};
-struct stmpc_c51_pop : QPop<stmpc_c51> {};
+// (noisy: stmpc_pop_noisy_c51_enable ran -- every member's C51Noisy is on, and three more tables follow the members: their noise structs and their
+// shadow structs for learning and for acting)
+struct stmpc_c51_pop : QPop<stmpc_c51> {
+    bool noisy = false;
+    DevBuf ztab, shadow, shadow_act;
+    int noisy_upload() {
+        std::vector<C51NoisyDev> z;
+        std::vector<C51Dev> s, a;
+        for (const stmpc_c51 *t : members) { z.push_back(t->ex.dev); s.push_back(t->ex.shadow(t->dev, false)); a.push_back(t->ex.shadow(t->dev, true)); }
+        TRY(upload(ztab, z.data(), z.size()));
+        TRY(upload(shadow, s.data(), s.size()));
+        return upload(shadow_act, a.data(), a.size());
+    }
+    // compose, fwd, wgrad, (the priority update,) sigma's and mu's Adam, each over the members: C51Head::noisy_update's launches
+    bool own_update(const Grid &g, int B, int Bp, const DdpgLr &lrs, hipStream_t st) const {
+        if (!noisy) return false;
+        const stmpc_c51 *t = members[0];
+        const int P = core.P();
+        hipLaunchKernelGGL(k_c51_noisy_compose_pop, dim3(C51Head::compose_blocks(*t), P), dim3(256), 0, st, dev(), ztab.as<C51NoisyDev>(), 0, 1);
+        C51Head::fwd_pop(*t, shadow.as<C51Dev>(), g, P, core.lds, B, st);
+        C51Head::wgrad_pop(shadow.as<C51Dev>(), g, P, Bp, st);
+        if (core.per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, core.dev(), B, 1);
+        hipLaunchKernelGGL(k_c51_noisy_adam_pop, dim3(g.ablocks, P), dim3(256), 0, st, dev(), ztab.as<C51NoisyDev>(), lrs, 1);
+        return true;
+    }
+};
 
 static_assert(STMPC_DQN_POP_MAX == DG_POP_MAX && DG_POP_MAX <= 64, "DdpgLr and DqnEps hold one value, and DqnEps::explore one bit, per possible member");
 static_assert(STMPC_C51_POP_MAX == DG_POP_MAX && DG_POP_MAX <= 64, "DdpgLr and DqnEps hold one value, and DqnEps::explore one bit, per possible member");
@@ -1636,6 +1829,7 @@ template <class Pop> int q_pop_update(Pop *p, int n_updates, const double *lr, i
     hipStream_t st = (hipStream_t)stream;
     for (int u = 0; u < n_updates; ++u) {                            // q_update's three launches (five with prioritised members), each over the members
         if (c.per_any) hipLaunchKernelGGL(k_per_sample_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, Bp, 1);
+        if (p->own_update(g, B, Bp, lrs, st)) continue;              // (a noisy C51 population: four launches, six with prioritised members)
         H::fwd_pop(*t, p->dev(), g, P, c.lds, B, st);
         H::wgrad_pop(p->dev(), g, P, Bp, st);
         if (c.per_any) hipLaunchKernelGGL(k_per_update_pop, dim3(1, P), dim3(PER_THREADS), 0, st, c.dev(), B, 1);
@@ -1698,10 +1892,57 @@ int stmpc_pop_c51_push_device(stmpc_c51_pop *p, int n_per_member, const float *d
 }
 int stmpc_pop_c51_update_device(stmpc_c51_pop *p, int n_updates, const double *lr, int n_lr, void *stream) { return q_pop_update(p, n_updates, lr, n_lr, stream); }
 int stmpc_pop_c51_stats_device(stmpc_c51_pop *p, double *d_out, void *stream) { return q_pop_stats(p, d_out, stream); }
-int stmpc_pop_c51_per_enable(stmpc_c51_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) { return q_pop_per_enable(p, cfgs, enabled, P); }
-int stmpc_pop_c51_multi_step_enable(stmpc_c51_pop *p, const stmpc_nstep_cfg *cfgs, int P) { return q_pop_nstep_enable(p, cfgs, P); }
+// (both re-wire the members' structs: a noisy population's shadow tables follow)
+int stmpc_pop_c51_per_enable(stmpc_c51_pop *p, const stmpc_per_cfg *cfgs, const uint8_t *enabled, int P) {
+    TRY(q_pop_per_enable(p, cfgs, enabled, P));
+    return p->noisy ? p->noisy_upload() : STMPC_OK;
+}
+int stmpc_pop_c51_multi_step_enable(stmpc_c51_pop *p, const stmpc_nstep_cfg *cfgs, int P) {
+    TRY(q_pop_nstep_enable(p, cfgs, P));
+    return p->noisy ? p->noisy_upload() : STMPC_OK;
+}
 int stmpc_pop_c51_replay_read(stmpc_c51 *t, int64_t first, int64_t count, float *rows) { return q_replay_read(t, first, count, rows); }
 int stmpc_pop_c51_multi_step_window(stmpc_c51 *t, const int64_t *idx, int n_idx, double *out) { return q_nstep_window(t, idx, n_idx, out); }
+
+// ---- the noisy output layer of a population of C51 learners (stmpc_pop_noisy_c51_*) ----
+// one call on fresh members: all of them get the layer, member m with cfgs[m]'s sigma0
+int stmpc_pop_noisy_c51_enable(stmpc_c51_pop *p, const stmpc_noisy_cfg *cfgs, int P) {
+    if (!p || !cfgs) return fail(STMPC_EINVAL, "NULL argument");
+    if (P != p->core.P()) return fail(STMPC_EINVAL, "the cfg array has " + std::to_string(P) + " entries, the population " + std::to_string(p->core.P()) + " members");
+    if (p->noisy) return fail(STMPC_EINVAL, "the noisy output layer is already enabled on this population");
+    for (int m = 0; m < P; ++m)
+        if (!(cfgs[m].sigma0 >= 0) || !std::isfinite(cfgs[m].sigma0)) return fail(STMPC_EINVAL, "member " + std::to_string(m) + "'s sigma0 must be finite and not negative");
+    HIPCHK(hipSetDevice(p->core.device));
+    for (int m = 0; m < P; ++m) TRY(noisy_attach(p->members[m], cfgs + m));
+    TRY(p->noisy_upload());
+    p->noisy = true;
+    return STMPC_OK;
+}
+
+// stmpc_noisy_c51_act_device per member: every member takes an acting draw of its own, then stmpc_pop_c51_act_device's launch on the shadow structs
+int stmpc_pop_noisy_c51_act_device(stmpc_c51_pop *p, int n_per_member, const float *d_obs, int obs_stride, const double *eps, int n_eps, int32_t *d_action,
+                                   float *d_debug_q, void *stream) {
+    if (!p) return fail(STMPC_EINVAL, "population is NULL");
+    if (!p->noisy) return fail(STMPC_EINVAL, "the noisy output layer is not enabled on this population (stmpc_pop_noisy_c51_enable)");
+    const PopCore &c = p->core;
+    TRY(pop_check_rows(c, n_per_member, obs_stride));
+    if (!eps) return fail(STMPC_EINVAL, "NULL argument");
+    if (n_eps != c.P()) return fail(STMPC_EINVAL, "the eps array has " + std::to_string(n_eps) + " entries, the population " + std::to_string(c.P()) + " members");
+    DqnEps e{};
+    for (int m = 0; m < c.P(); ++m) {
+        if (!(eps[m] >= 0 && eps[m] <= 1)) return fail(STMPC_EINVAL, "member " + std::to_string(m) + "'s eps must be in 0 ... 1");
+        e.eps[m] = (float)eps[m];
+        if (eps[m] > 0) e.explore |= 1ull << m;
+    }
+    if (!d_obs || !d_action) return fail(STMPC_EINVAL, "NULL device pointer");
+    HIPCHK(hipSetDevice(c.device));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_c51_noisy_compose_pop, dim3(C51Head::compose_blocks(*p->members[0]), c.P()), dim3(256), 0, st, p->dev(), p->ztab.as<C51NoisyDev>(), 1, 0);
+    C51Head::act_pop(p->shadow_act.as<C51Dev>(), c.P(), c.lds, n_per_member, d_obs, obs_stride, e, d_action, d_debug_q, st);
+    HIPCHK(hipGetLastError());
+    return STMPC_OK;
+}
+
 
 }  // extern "C"
 

@@ -55,7 +55,14 @@ support, ``double``, ``target_period``, ``gamma``, ``n_step``, the seed and ``pe
 Hessel et al. 2018): (A + 1) * n_atoms outputs, the value block last, logits V + Adv - mean Adv formed on the device behind every forward pass, a
 dense backward, the same launch count.  It restates the published head; parity with the ``all`` library's own is not pinned.  Twins:
 ``_c51_logits(dueling=True)``, ``c51_dueling_combine_host`` (the device's operation order), ``c51_fold_dueling_host`` (the plain network with the same
-logits).  Noisy layers, the sixth piece of the rainbow preset, are not built.
+logits).
+``C51Config(noisy=NoisyConfig())`` gives the learner the sixth piece of the rainbow preset, the noisy output layer (Fortunato et al. 2018;
+``csrc/stmpc_c51_noisy_kernels.hpp``, ``stmpc_noisy_c51_*``): W_eff = mu + sigma * outer(f(e_out), f(e_in)) on the layer h1 -> (A + dueling) * n_atoms,
+the existing parameters being mu, a fresh draw per update and net and per acting call, Adam on sigma next to mu -- four launches per update, six with
+``per``; ``train_dqn`` then explores through the noise (epsilon 0).  Twins: ``c51_noisy_f_host``, ``c51_noisy_compose_host``,
+``update_host_c51_noisy``.  ``C51Population(..., noisy=)`` takes it as it takes ``per=`` -- one ``NoisyConfig`` for all members or one per member
+(``sigma0`` may differ), all members on or all off (``stmpc_pop_noisy_c51_*``): four launches per update whatever P is, every member bit-identical
+to the lone noisy learner.
 """
 import math
 
@@ -1410,6 +1417,98 @@ class DQNPopulation(DDPGPopulation):
 
 
 # ---- C51: the categorical DQN agent (csrc/stmpc_c51_kernels.hpp, stmpc_c51_*) ---------------------------------------------------------------------
+class NoisyConfig:
+    """The noisy output layer of a C51 learner (``C51Config(noisy=...)``): sigma starts at ``sigma0 / sqrt(h1)`` everywhere.  0.5 is the paper's
+    (Fortunato et al. 2018, section 3.2); the ``all`` rainbow preset's own value could not be read (the library is absent from the reference
+    checkout).  ``sigma0 = 0`` starts from the mean network (sigma still learns)."""
+
+    def __init__(self, sigma0=0.5):
+        self.sigma0 = float(sigma0)
+        if not (math.isfinite(self.sigma0) and self.sigma0 >= 0):
+            raise ValueError("NoisyConfig needs a finite sigma0 >= 0, not %r" % (sigma0,))
+
+
+NOISY_LEARN_STREAM, NOISY_ACT_STREAM = 0x6E7A6C726E, 0x6E7A616374     # C51_NOISY_LEARN_STREAM, C51_NOISY_ACT_STREAM of csrc/stmpc_c51_noisy_kernels.hpp
+NOISY_TENSORS = ("w1", "b1")                                          # what a sigma slot holds
+
+
+def c51_noisy_f_host(seed, draw, h1, n_out, stream=NOISY_LEARN_STREAM):
+    """(f_in float32 [h1], f_out float32 [n_out]) of noise draw ``draw``: f(e) = sign(e) sqrt|e| of ``noise_host``'s Gaussians, variate k < h1 for
+    e_in and h1 + n for e_out -- the Gaussian rounded to float32 as the kernel holds it, f formed in float64 and rounded to float32 once.  The learning
+    stream's draw is 2 * update + net (0 online, 1 target); the acting stream's (``NOISY_ACT_STREAM``) the learner's acting-draw counter."""
+    e = noise_host(seed, draw, int(h1) + int(n_out), stream=stream)[2].astype(np.float32).astype(np.float64)
+    f = (np.sign(e) * np.sqrt(np.abs(e))).astype(np.float32)
+    return f[:h1], f[h1:]
+
+
+def c51_noisy_compose_host(mu, sigma, f_in, f_out):
+    """``k_c51_noisy_compose``'s effective output layer in numpy, operation for operation: {w1, b1} float32 from float32 ``mu`` {w1 [n_out][h1], b1},
+    ``sigma`` likewise and the float32 f vectors -- W_eff = float32(mu + sigma * (f_out * f_in)) in float64 (the inner product is exact there, the
+    other two operations round), b_eff = float32(mu_b + sigma_b * f_out)."""
+    d = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
+    fo, fi = d(f_out), d(f_in)
+    return {"w1": (d(mu["w1"]) + d(sigma["w1"]) * (fo[:, None] * fi[None, :])).astype(np.float32), "b1": (d(mu["b1"]) + d(sigma["b1"]) * fo).astype(np.float32)}
+
+
+def _c51_noisy_effective(net, sigma, f_in, f_out):
+    """The effective net of torch tensors: the mathematical statement in the tensors' dtype."""
+    return {"w0": net["w0"], "b0": net["b0"], "w1": net["w1"] + sigma["w1"] * (f_out[:, None] * f_in[None, :]), "b1": net["b1"] + sigma["b1"] * f_out}
+
+
+def update_host_c51_noisy(params, batch, cfg, f, dtype="float64", weights=None, grads_only=False, lr=None, disc=None):
+    """``update_host_c51`` for a learner with the noisy output layer, every tensor in ``dtype``.  ``params``: the four slots and ``sigma``,
+    ``sigma_target``, ``sigma_m``, ``sigma_v`` ({w1, b1} each); ``f``: {"online": (f_in, f_out), "target": (f_in, f_out)}, the draws' f vectors
+    (inputs: ``c51_noisy_f_host``'s or the device's).  The target side runs on the effective target net (and, ``cfg.double``, the effective online
+    one); the loss on the effective online net with mu and sigma as autograd's leaves; Adam steps both and the hard copy copies both.  Returns the
+    new params and ``update_host_c51``'s info with ``grad`` = g_mu and ``grad_sigma`` = g_sigma."""
+    import torch
+    td = getattr(torch, dtype)
+    T = lambda a: torch.tensor(np.asarray(a), dtype=td)
+    A, K, B = cfg.n_actions, cfg.n_atoms, len(batch["r"])
+    duel = bool(getattr(cfg, "dueling", False))
+    slots = tuple(_capi.C51_SLOTS)
+    P = {slot: {k: T(params[slot][k]) for k in DQN_TENSORS} for slot in slots}
+    S = {slot: {k: T(params[slot][k]) for k in NOISY_TENSORS} for slot in _capi.NOISY_SLOTS}
+    fo = {net: (T(f[net][0]), T(f[net][1])) for net in ("online", "target")}
+    with torch.no_grad():
+        eff = {"q": {k: v.numpy() for k, v in _c51_noisy_effective(P["q"], S["sigma"], *fo["online"]).items()},
+               "q_target": {k: v.numpy() for k, v in _c51_noisy_effective(P["q_target"], S["sigma_target"], *fo["target"]).items()}}
+    tg = c51_targets_host(eff, batch, cfg, dtype, disc=disc)
+    m = T(tg["m"])
+    mu = {k: P["q"][k].clone().requires_grad_(True) for k in DQN_TENSORS}
+    sg = {k: S["sigma"][k].clone().requires_grad_(True) for k in NOISY_TENSORS}
+    a = torch.tensor(np.asarray(batch["a"], dtype=np.int64))
+    logp = torch.log_softmax(_c51_logits(_c51_noisy_effective(mu, sg, *fo["online"]), T(batch["s"]), A, K, duel), -1)[torch.arange(B), a]
+    terms = -(m * logp).sum(-1)
+    loss = terms.mean()
+    leaves = [mu[k] for k in DQN_TENSORS] + [sg[k] for k in NOISY_TENSORS]
+    gl = torch.autograd.grad(loss if weights is None else (T(weights) * terms).mean(), leaves)
+    grads, gsig = dict(zip(DQN_TENSORS, gl[:4])), dict(zip(NOISY_TENSORS, gl[4:]))
+    u = int(params["updates"])
+    if not grads_only:
+        t = u + 1
+        bc1, bc2 = 1.0 - cfg.beta1 ** t, 1.0 - cfg.beta2 ** t
+        for W, M, V, Wt, G, names in ((P["q"], P["q_m"], P["q_v"], P["q_target"], grads, DQN_TENSORS),
+                                      (S["sigma"], S["sigma_m"], S["sigma_v"], S["sigma_target"], gsig, NOISY_TENSORS)):
+            for k in names:
+                M[k] = cfg.beta1 * M[k] + (1 - cfg.beta1) * G[k]
+                V[k] = cfg.beta2 * V[k] + (1 - cfg.beta2) * G[k] * G[k]
+                W[k] = W[k] - ((cfg.lr if lr is None else lr) / bc1) * M[k] / (V[k].sqrt() / math.sqrt(bc2) + cfg.eps)
+                if t % cfg.target_period == 0:
+                    Wt[k] = W[k].clone()
+    out = {slot: {k: P[slot][k].detach().numpy() for k in DQN_TENSORS} for slot in slots}
+    out.update({slot: {k: S[slot][k].detach().numpy() for k in NOISY_TENSORS} for slot in _capi.NOISY_SLOTS})
+    out["beta_pow"] = np.array(params["beta_pow"], dtype=np.float32) * (1 if grads_only else np.array([cfg.beta1, cfg.beta2], dtype=np.float32))
+    out["updates"] = u + (0 if grads_only else 1)
+    p = logp.detach().exp()
+    q = (p * T(c51_support(cfg))).sum(-1)
+    row_loss = terms.detach().numpy()
+    info = {"loss": float(loss.detach()), "mean_q": float(q.mean()), "q_values": q.numpy(), "td": row_loss, "row_loss": row_loss,
+            "targets": np.stack([tg["astar"].astype(row_loss.dtype), tg["q_next"], row_loss], 1), "dist": np.stack([tg["m"], p.numpy()], 1),
+            "ev_next": tg["ev_next"], "grad": {k: grads[k].numpy() for k in DQN_TENSORS}, "grad_sigma": {k: gsig[k].numpy() for k in NOISY_TENSORS}}
+    return out, info
+
+
 class C51Config(DQNConfig):
     """``DQNConfig`` plus the categorical head's support: ``n_atoms`` atoms z_k = v_min + k (v_max - v_min) / (n_atoms - 1).  The defaults 51, -10, 10 are
     the C51 paper's (Bellemare et al. 2017); the ``all`` rainbow preset's own values could not be read (the library is absent from the reference
@@ -1418,11 +1517,16 @@ class C51Config(DQNConfig):
     ``dueling``: the dueling head (Wang et al. 2016, in the categorical form of Hessel et al. 2018, section "Dueling networks").  The network is then
     n_obs -> h1 -> ReLU -> (A + 1) * n_atoms -- the A advantage blocks first, rows a * n_atoms ... of w1 and b1, the value block last -- and the
     logits of action a are l[a][k] = V[k] + Adv[a][k] - mean_b Adv[b][k].  It restates the published head; parity with the ``all`` library's own
-    stays unpinned, for the same reason.  The widest layer holds 1024 outputs: ``sumo-accel-v0`` (20 actions) takes at most 48 atoms with it."""
+    stays unpinned, for the same reason.  The widest layer holds 1024 outputs: ``sumo-accel-v0`` (20 actions) takes at most 48 atoms with it.
 
-    def __init__(self, *args, n_atoms=51, v_min=-10.0, v_max=10.0, dueling=False, **kw):
+    ``noisy``: None, or a ``NoisyConfig`` for factorised-Gaussian noise on the output layer (Fortunato et al. 2018), plain or dueling."""
+
+    def __init__(self, *args, n_atoms=51, v_min=-10.0, v_max=10.0, dueling=False, noisy=None, **kw):
         super().__init__(*args, **kw)
         self.n_atoms, self.v_min, self.v_max, self.dueling = int(n_atoms), float(v_min), float(v_max), bool(dueling)
+        if noisy is not None and not isinstance(noisy, NoisyConfig):
+            raise ValueError("noisy must be None or a NoisyConfig, not %r" % (noisy,))
+        self.noisy = noisy
         if self.n_atoms < 2:
             raise ValueError("C51 needs n_atoms >= 2, not %d" % self.n_atoms)
         if not (math.isfinite(self.v_min) and math.isfinite(self.v_max) and self.v_max > self.v_min):
@@ -1597,10 +1701,59 @@ class C51Learner(_QLearner):
     """Categorical DQN on the device for the discrete-action envs, with ``DQNLearner``'s interface (``train_dqn`` takes either).  ``env_or_dims``: a
     discrete env or ``(n_obs, n_actions)``; ``cfg``: ``C51Config``; ``init``: None (torch's nn.Linear initialisation, ``init_c51_net``) or a net
     {w0, b0, w1 [A * n_atoms][h1], b1 [A * n_atoms]} ((A + 1) * n_atoms rows with ``cfg.dueling``: the value block last).  One update is three HIP
-    launches (five with ``cfg.per``), with either head."""
+    launches (five with ``cfg.per``), with either head; four (six) with ``cfg.noisy``, whose parameters these tensors are the mean of."""
 
     _api, _per_api, _slots, _flatten = "c51", "c51_per", _capi.C51_SLOTS, staticmethod(flatten_q)
     _name, _cfg_type = "C51", C51Config
+
+    @property
+    def noisy(self):
+        return getattr(self.cfg, "noisy", None) is not None
+
+    def _make_handle(self):
+        """The new handle, with the noisy output layer enabled on it while it is fresh (a population's member never gets here: ``_Borrowed``)."""
+        h = super()._make_handle()
+        if self.noisy:
+            self.ctx.noisy_c51_enable(h, self.cfg.noisy.sigma0)
+        return h
+
+    def _sigma_len(self):
+        return self._n_out * (self.cfg.h1 + 1)
+
+    def _sigma_slot(self, i):
+        flat = self.ctx.noisy_c51_get_params(self.handle, i, self._sigma_len())
+        n = self._n_out * self.cfg.h1
+        return {"w1": flat[:n].reshape(self._n_out, self.cfg.h1).copy(), "b1": flat[n:].copy()}
+
+    def act(self, obs, ticks=None, eps=0.0, debug_q=None, noisy=None):
+        """``_QLearner.act``.  ``noisy``: None -- noisy iff the learner is --; False: the mean network (bit-identical to ``actor.C51Actor.from_learner``;
+        draws nothing, advances nothing); True: a fresh acting draw of the output layer's noise (a plain learner refuses).  ``eps`` is honoured either
+        way."""
+        if noisy is None:
+            noisy = self.noisy
+        if not noisy:
+            return super().act(obs, ticks, eps=eps, debug_q=debug_q)
+        if not self.noisy:
+            raise ValueError("noisy=True needs a learner with the noisy output layer (C51Config(noisy=NoisyConfig())); this one is plain")
+        n = obs.shape[0]
+        out = self._out(n, self.torch.int32)
+        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
+        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (n, self.cfg.n_actions))
+        self.ctx.noisy_c51_act(self.handle, n, obs.data_ptr(), obs.stride(0), eps, out.data_ptr(), debug_q.data_ptr() if debug_q is not None else 0, self._stream())
+        return out
+
+    def noise(self, which="online"):
+        """Debug: (f_in float32 [h1], f_out float32 [n_out]) of the last learning draw of the ``"online"`` or the ``"target"`` net, or of the last
+        ``"act"`` draw; synchronises."""
+        f = self.ctx.noisy_c51_debug_read(self.handle, _capi.NOISY_F[which], self.cfg.h1 + self._n_out)
+        return f[:self.cfg.h1].copy(), f[self.cfg.h1:].copy()
+
+    def effective(self, which="online", padded=False):
+        """Debug: the effective output layer {w1, b1} of that draw as the kernels read it; ``padded``: in the library's layout [Ap][h1p], [Ap];
+        synchronises."""
+        rows, cols = ((self._n_out + 15) & ~15, (self.cfg.h1 + 15) & ~15) if padded else (self._n_out, self.cfg.h1)
+        flat = self.ctx.noisy_c51_debug_read(self.handle, _capi.NOISY_F[which] + (6 if padded else 3), rows * cols + rows)
+        return {"w1": flat[:rows * cols].reshape(rows, cols).copy(), "b1": flat[rows * cols:].copy()}
 
     def _check_cfg_type(self):
         if not isinstance(self.cfg, C51Config):
@@ -1616,9 +1769,14 @@ class C51Learner(_QLearner):
         return init_c51_net(self.cfg.n_obs, self.cfg.h1, self.cfg.n_actions, self.cfg.n_atoms, rng, self.cfg.dueling)
 
     def state_dict(self):
-        """``_Learner.state_dict`` with the head's flag (``dueling``), which ``load_state_dict`` compares."""
+        """``_Learner.state_dict`` with the head's flag (``dueling``) and ``noisy``, which ``load_state_dict`` compares; a noisy learner's params
+        carry the four sigma slots ({w1, b1} each) and its counters the acting draws (``counters[5]``)."""
         sd = super().state_dict()
         sd["dueling"] = bool(self.cfg.dueling)
+        sd["noisy"] = self.noisy
+        if self.noisy:
+            for i, slot in enumerate(_capi.NOISY_SLOTS):
+                sd["params"][slot] = self._sigma_slot(i)
         return sd
 
     def load_state_dict(self, sd):
@@ -1627,7 +1785,15 @@ class C51Learner(_QLearner):
         if "dueling" in sd and bool(sd["dueling"]) != bool(self.cfg.dueling):
             raise ValueError("the state is a %s C51 learner's, this learner has a %s head (cfg.dueling = %r)"
                              % ("dueling" if sd.get("dueling", False) else "plain", "dueling" if self.cfg.dueling else "plain", self.cfg.dueling))
-        super().load_state_dict({k: v for k, v in sd.items() if k != "dueling"})
+        if "noisy" in sd and bool(sd["noisy"]) != self.noisy:
+            raise ValueError("the state is a %s C51 learner's, this learner has a %s output layer (cfg.noisy = %r)"
+                             % ("noisy" if sd["noisy"] else "plain", "noisy" if self.noisy else "plain", getattr(self.cfg, "noisy", None)))
+        super().load_state_dict({k: v for k, v in sd.items() if k not in ("dueling", "noisy")})
+        if self.noisy:
+            for i, slot in enumerate(_capi.NOISY_SLOTS):
+                if slot in sd["params"]:
+                    t = sd["params"][slot]
+                    self.ctx.noisy_c51_set_params(self.handle, i, np.concatenate([np.asarray(t["w1"], dtype=np.float32).ravel(), np.asarray(t["b1"], dtype=np.float32).ravel()]))
 
     def dist(self):
         """Debug: (float32 [batch][2][n_atoms] = the projected target distribution m and the online distribution p(s, a); ``targets()``'s array) of
@@ -1650,10 +1816,11 @@ class C51Learner(_QLearner):
 
     def export_q(self, path):
         """Write the online logits network as an ``.npz``: w0, b0, w1, b1 (float32), ``action_values`` and the head's ``n_atoms``, ``v_min``, ``v_max``
-        and ``dueling`` (0 / 1; a reader takes a file without the key as 0)."""
+        and ``dueling`` (0 / 1; a reader takes a file without the key as 0).  Of a noisy learner it is the MEAN network; ``noisy`` (0 / 1) says so
+        and readers ignore it."""
         with open(path, "wb") as fh:
             np.savez_compressed(fh, **self._slot(0), action_values=self.action_values, n_atoms=np.int64(self.cfg.n_atoms), v_min=np.float64(self.cfg.v_min),
-                                v_max=np.float64(self.cfg.v_max), dueling=np.int64(self.cfg.dueling))
+                                v_max=np.float64(self.cfg.v_max), dueling=np.int64(self.cfg.dueling), noisy=np.int64(getattr(self.cfg, "noisy", None) is not None))
         return path
 
 
@@ -1680,6 +1847,71 @@ class C51Population(DQNPopulation):
     _api, _nstat = "c51_pop", 4
     _nstep_kind = "c51"                                             # (``ctx.pop_nstep_enable`` routes it to stmpc_pop_c51_multi_step_enable)
     _cfg_type, _action_dtype = C51Config, "int32"
+
+    def __init__(self, env, cfgs, seeds=None, init=None, ctx=None, per=None, noisy=None):
+        """``noisy``: the noisy output layer (``NoisyConfig``) -- None, one for every member, or a list of P (``sigma0`` may differ per member; the
+        members are all noisy or all plain).  Like ``per`` it is the population's argument: a cfg that carries ``noisy=`` is refused.  Member m is then
+        bit-identical to ``C51Learner(cfg with noisy=noisy[m], seed=seeds[m])`` on its slice; ``act`` draws per member (``act(noisy=False)``: the mean
+        networks), ``train_dqn`` with ``eps_schedule=None`` uses epsilon 0, one update is four launches (six with prioritised members)."""
+        import copy
+        if isinstance(cfgs, tuple) and len(cfgs) == 2 and isinstance(cfgs[0], self._cfg_type):
+            cfgs = [cfgs[0]] * int(cfgs[1])
+        cfgs = list(cfgs)
+        for m, c in enumerate(cfgs):
+            if getattr(c, "noisy", None) is not None:
+                raise ValueError("member %d's cfg asks for the noisy output layer (noisy=): a population enables it for its members itself; give the "
+                                 "NoisyConfig to the population's noisy= argument (one for all members, or a list with one entry per member)" % m)
+        if noisy is None or isinstance(noisy, NoisyConfig):
+            noisy = [noisy] * len(cfgs)
+        elif not isinstance(noisy, (list, tuple)):
+            raise ValueError("noisy must be None, a NoisyConfig, or a list with one NoisyConfig per member")
+        noisy = list(noisy)
+        if len(noisy) != len(cfgs):
+            raise ValueError("noisy has %d entries, the population %d members" % (len(noisy), len(cfgs)))
+        for m, g in enumerate(noisy):
+            if g is not None and not isinstance(g, NoisyConfig):
+                raise ValueError("noisy[%d] is a %s, not a NoisyConfig" % (m, type(g).__name__))
+            if (g is None) != (noisy[0] is None):
+                raise ValueError("member %d is %s, member 0 is %s: the members of a population are all noisy or all plain (one launch sequence)"
+                                 % (m, "plain" if g is None else "noisy", "plain" if noisy[0] is None else "noisy"))
+        self.noisy_cfgs = noisy
+        if self.noisy:                                              # (the members' views read their cfg: each gets a copy that carries its own)
+            cfgs = [copy.copy(c) for c in cfgs]
+            for c, g in zip(cfgs, noisy):
+                if isinstance(c, C51Config):
+                    c.noisy = g
+        super().__init__(env, cfgs, seeds=seeds, init=init, ctx=ctx, per=per)
+
+    @property
+    def noisy(self):
+        return bool(self.noisy_cfgs) and self.noisy_cfgs[0] is not None
+
+    def _create_handle(self):
+        """The new population, with the noisy output layer enabled on its members while they are fresh."""
+        h = super()._create_handle()
+        if self.noisy:
+            try:
+                self.ctx.c51_pop_noisy_enable(h, [g.sigma0 for g in self.noisy_cfgs])
+            except Exception:
+                self._call("destroy")(h)
+                raise
+        return h
+
+    def act(self, obs, ticks=None, eps=0.0, debug_q=None, noisy=None):
+        """``DQNPopulation.act``.  ``noisy``: None -- noisy iff the population is --; False: the mean networks (nothing drawn, nothing advanced); True:
+        every member takes a fresh acting draw (a plain population refuses).  ``eps`` is honoured either way."""
+        if noisy is None:
+            noisy = self.noisy
+        if not noisy:
+            return super().act(obs, ticks, eps=eps, debug_q=debug_q)
+        if not self.noisy:
+            raise ValueError("noisy=True needs a population with the noisy output layer (C51Population(..., noisy=NoisyConfig())); this one is plain")
+        self._rows(obs)
+        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
+        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (self.env_n, self.cfgs[0].n_actions))
+        self.ctx.c51_pop_noisy_act(self.handle, self.n_per_member, obs.data_ptr(), obs.stride(0), per_member(eps, self.P), self._actions.data_ptr(),
+                                   debug_q.data_ptr() if debug_q is not None else 0, self._stream())
+        return self._actions
 
     def _check_env(self, env):
         if env.continuous:
@@ -1750,6 +1982,8 @@ def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_sche
     every ``drain_every`` steps.  The result has ``train_ddpg``'s keys.
     ``learner`` may be a ``DQNPopulation`` (both schedules may then return per-member arrays); the result then also carries ``member_returns``:
     the drained returns of each member's environments, a list of P arrays (owner = env index // n_per_member), as ``train_ddpg``'s does.
+    A learner with the noisy output layer (``C51Config(noisy=...)``) explores through its noise: with ``eps_schedule=None`` its epsilon is 0 (an
+    explicit schedule is honoured).
     On a shielded env (a discrete ``MergeVecEnv(shield="first_step")``, ``vec_env.GroupedShieldVecEnv`` or ``vec_env.QCombinedShieldVecEnv``) the
     result's ``takeover_share`` is the share of the live ticks on which the shield overruled the action (summed on the device, read at the drains,
     as ``train_ddpg`` does it; 0.0 on an env without a ``shield``), and with a ``DQNPopulation`` ``member_takeover_share`` is that share per member,
@@ -1759,8 +1993,9 @@ def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_sche
     obs = env.reset()
     returns, envs = [], []
     shield = _TakeoverShare(env, learner.P if pop else 0, learner.n_per_member if pop else 0) if getattr(env, "shield", None) is not None else None
+    default_eps = (lambda i: 0.0) if getattr(learner, "noisy", False) else dqn_epsilon
     for i in range(steps):
-        action = learner.act(obs, None, eps=eps_schedule(i, steps) if eps_schedule is not None else dqn_epsilon(i))
+        action = learner.act(obs, None, eps=eps_schedule(i, steps) if eps_schedule is not None else default_eps(i))
         next_obs, reward, term, trunc, info = env.step(action)
         learner.push(obs, None, action, reward, next_obs, term, trunc, final_obs=info["final_observation"])
         if shield is not None:
