@@ -1306,6 +1306,35 @@ int  stmpc_pop_qactor_eval_device(stmpc_ctx *ctx, const stmpc_qactor_pop *pop, c
                                   const double *d_cur_other_a, float *d_feat, int feat_stride, int32_t *d_action, float *d_q, double *d_jerk, void *stream);
 
 /*
+ * A population of categorical (C51) policies, evaluated in one launch: the population above for the distributional head of the reference's third
+ * agent (rainbow.py: RainbowAgent) doing DQNAgent.get_control's job (dqn.py:375-380).  What a C51 population's sweeps train -- support, double,
+ * target period, gamma, multi-step, seed, prioritised replay, sigma0 -- is evaluated side by side, and trained behind the combined controller's
+ * shield, instead of one member at a time.  (Additive: one new entry, no signature or struct of ABI 8 changes, so STMPC_ABI_VERSION stays 8;
+ * stmpc_pop_qactor_create keeps refusing a categorical member.  The entry is not named stmpc_pop_qactor_..., stmpc_c51actor_..., stmpc_pop_c51_... or
+ * stmpc_c51_...: those prefixes are closed sets.)
+ *   stmpc_pop_c51actor_create (dqn.py:375-380 for P models, rainbow.py) P = 1 ... STMPC_DDPG_POP_MAX categorical Q-actors -- stmpc_c51actor_create or
+ *                   stmpc_dueling_c51actor_create actors, or stmpc_c51actor_view views, of the online or the target network, of a lone learner or
+ *                   of a handle lent by stmpc_pop_c51_member -- on the context's device, which share n_in, the padded hidden width, n_actions,
+ *                   n_atoms and the head (dueling or not: one launch shape, one LDS size, one d_q layout).  The support (v_min, v_max), the action
+ *                   table, mode, limits and online / target may differ per member.  STMPC_EINVAL, naming the member, with *out NULL and nothing
+ *                   launched, for P out of range, a NULL member, a member on another device, a member that is no categorical policy (a Q-network
+ *                   goes to stmpc_pop_qactor_create), a shape that differs from member 0's, an acceleration-mode member without
+ *                   stmpc_qactor_set_limits.  The result is a stmpc_qactor_pop: stmpc_pop_qactor_destroy, stmpc_pop_qactor_size,
+ *                   stmpc_pop_qactor_eval_device and the population of stmpc_qshield_env_reset_device / _step_device take it as they take a
+ *                   population of Q-networks, and d_q is then the expected values, float32 [P * n_per_member][n_actions]; member m's rows are
+ *                   bit-identical to stmpc_qactor_eval_device with that member on that slice.  The population holds a DEVICE TABLE of the members'
+ *                   descriptions, written once here: table pointer, mode and limits as they are now, the network's pointers, the shape and the
+ *                   support (dz in fp64 as the owner formed it).  A C51 learner's network buffers, shape and support are fixed from stmpc_c51_create
+ *                   to stmpc_c51_destroy -- stmpc_c51_per_enable, stmpc_pop_c51_per_enable, stmpc_c51_multi_step_enable and
+ *                   stmpc_pop_c51_multi_step_enable re-wire the replay store's part of the learner alone; a population of learners re-uploads its
+ *                   members' structs as they are; stmpc_noisy_c51_enable and stmpc_pop_noisy_c51_enable work on copies of the struct and leave the
+ *                   learner's own on the mean weights mu -- so a view's entry stays valid and LIVE: an evaluation ordered after an update on the same
+ *                   stream sees the update, as the lone view does.  A view of a noisy learner evaluates mu, as the lone view does.  The members stay
+ *                   the caller's and must outlive the population.  Synchronises
+ */
+int  stmpc_pop_c51actor_create(stmpc_ctx *ctx, const stmpc_qactor *const *members, int P, stmpc_qactor_pop **out);
+
+/*
  * Actors straight from learners, and a population of actors evaluated in one launch.  The reference's workflow ends a training with an evaluation
  * of the model it trained (ddpg.train_ddpg_all_with_lr_drop's closing `evaluate`, ddpg.py:96-117) and publishes a matrix of EVALUATE_COMBINED_DDPG runs, one per
  * MODEL_NAME (DDPGAgent.load + get_control, ddpg.py:38-44, 83-87; configs/combined_<traffic>_{1,2,3}.json, experiment_data/saved_data.csv).  (Additive: new

@@ -343,7 +343,7 @@ EXPORTS = (
     "stmpc_nstep_window_ddpg", "stmpc_nstep_window_dqn",
     "stmpc_qactor_create", "stmpc_qactor_view_dqn", "stmpc_qactor_destroy", "stmpc_qactor_set_limits", "stmpc_qactor_eval_device",
     "stmpc_pop_qactor_create", "stmpc_pop_qactor_destroy", "stmpc_pop_qactor_size", "stmpc_pop_qactor_eval_device",
-    "stmpc_c51actor_create", "stmpc_c51actor_view", "stmpc_dueling_c51actor_create",
+    "stmpc_c51actor_create", "stmpc_c51actor_view", "stmpc_dueling_c51actor_create", "stmpc_pop_c51actor_create",
     "stmpc_combined_groups_set", "stmpc_combined_groups_clear", "stmpc_rollout_step_groups_device", "stmpc_combined_decide_groups_device",
     "stmpc_rec_create", "stmpc_rec_destroy", "stmpc_rec_reset", "stmpc_rec_tick_device", "stmpc_rec_reduce_device", "stmpc_rec_read",
     "stmpc_first_step_device", "stmpc_first_step", "stmpc_first_step_counts", "stmpc_speed_from_jerk_device",
@@ -640,6 +640,7 @@ def load():
     lib.stmpc_pop_qactor_destroy.restype = None
     lib.stmpc_pop_qactor_size.argtypes = [vp]
     lib.stmpc_pop_qactor_eval_device.argtypes = list(lib.stmpc_qactor_eval_device.argtypes)
+    lib.stmpc_pop_c51actor_create.argtypes = list(lib.stmpc_pop_qactor_create.argtypes)
     lib.stmpc_actor_view_ddpg.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_create.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]
     lib.stmpc_actor_pop_destroy.argtypes = [vp]
@@ -1486,6 +1487,15 @@ class Context:
         arr = (C.c_void_p * len(handles))(*handles)
         h = C.c_void_p()
         self._chk(self._lib.stmpc_pop_qactor_create(self._h, arr, len(handles), C.byref(h)))
+        return h
+
+    def c51actor_pop_create(self, handles):
+        """``qactor_pop_create`` for categorical (C51) Q-actor handles (``c51actor_create`` or ``c51actor_view``; ``stmpc_pop_c51actor_create``): they
+        share n_in, the padded hidden width, n_actions, n_atoms and the head; the support may differ.  The handle is a Q-actor population's:
+        ``qactor_pop_destroy``, ``qactor_pop_size``, ``qactor_pop_eval_device`` and the ``qshield_env_*`` entries take it."""
+        arr = (C.c_void_p * len(handles))(*handles)
+        h = C.c_void_p()
+        self._chk(self._lib.stmpc_pop_c51actor_create(self._h, arr, len(handles), C.byref(h)))
         return h
 
     def qactor_pop_destroy(self, handle):

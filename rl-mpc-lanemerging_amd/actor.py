@@ -23,9 +23,10 @@ reference checkout -- parity unpinned for those two steps, and the suite's ``tes
 
 ``DQNActor`` is the same for the reference's second agent, ``DQNAgent.get_control`` (dqn.py:375-380): state vector (no time feature) -> Q ->
 ``argmax`` -> the action table, one launch (``k_qactor_eval``), from a ``learner.DQNLearner`` where it lies or from its exported file.
-``QActorPopulation`` is ``ActorPopulation`` for such policies (``k_qactor_eval_pop``: P Q-networks, one launch), and ``population_of`` picks
+``QActorPopulation`` is ``ActorPopulation`` for such policies (``k_qactor_eval_pop``: P Q-networks, one launch; ``C51ActorPopulation`` is its
+subclass for categorical policies, ``k_c51actor_eval_pop``), and ``population_of`` picks
 between the two from the members' kind.  ``C51Actor`` is ``DQNActor`` for a ``learner.C51Learner``'s categorical network (``k_c51actor_eval``: the
-expected values of the return distributions in Q's place); it is evaluated alone, no population takes it.
+expected values of the return distributions in Q's place); ``C51ActorPopulation`` is the population that takes it.
 """
 import os
 
@@ -407,8 +408,8 @@ class C51Actor(DQNActor):
     (``stmpc_dueling_c51actor_create``); a file without the key has the plain head.  ``.dueling`` says which.
     ``.shape`` is (n_in, h1, A); ``.n_atoms``, ``.v_min``, ``.v_max`` the head's support; ``.q`` (with ``keep_q``) holds the expected values,
     float32 [n][A].  ``mode``, the call, ``reset``, ``keep_features`` and ``keep_q`` are ``DQNActor``'s.  The expected values, the index and the jerk
-    are bit for bit what ``C51Learner.act`` gives on the same input vectors; ``c51_policy_host`` is the host twin.  There is no population of C51
-    policies: ``QActorPopulation`` refuses one."""
+    are bit for bit what ``C51Learner.act`` gives on the same input vectors; ``c51_policy_host`` is the host twin.  ``QActorPopulation`` refuses a
+    C51 policy: C51 policies share a population of their own, ``C51ActorPopulation``."""
 
     def __init__(self, source, n, ctx, S, mode="jerk", action_values=None):
         with np.load(os.fspath(source)) as z:
@@ -469,7 +470,8 @@ def refuse_c51_members(items, who):
     bad = [m for m, item in enumerate(items) if isinstance(item, C51Actor) or _is_c51_learner(item) or _is_c51_file(item)]
     if bad:
         raise ValueError("%s: members %s are categorical (C51) policies, and a population of C51 policies does not exist (one launch needs one head); "
-                         "evaluate a C51 policy alone, with learner.evaluate_dqn or a C51Actor" % (who, ", ".join(map(str, bad))))
+                         "evaluate a C51 policy alone, with learner.evaluate_dqn or a C51Actor -- or C51 policies together, in a population of their own: "
+                         "actor.C51ActorPopulation, learner.evaluate_c51_members" % (who, ", ".join(map(str, bad))))
 
 
 def _is_q_member(item):
@@ -490,17 +492,47 @@ class QActorPopulation:
     runner then reports per member).  ``.jerk`` (fp64 [n]) and ``.action`` (int32 [n]) are filled by every call; ``keep_features`` / ``keep_q`` fill
     ``.feat`` (float32 [n][n_in]) and ``.q`` (float32 [n][A]) too.  There is no time feature: ``reset`` does nothing."""
 
-    def __init__(self, members, n_per_member, ctx, S):
-        if hasattr(members, "member") and hasattr(members, "P"):                 # a learner.DQNPopulation
+    def _take(self, members, n_per_member, refuse=None):
+        """What both kinds of population begin with: a learner population as its members, ``refuse`` on the list, the counts (``P``,
+        ``n_per_member``, ``n``).  Returns the list."""
+        if hasattr(members, "member") and hasattr(members, "P"):                 # a learner.DQNPopulation (C51Population)
             members = [members.member(m) for m in range(members.P)]
         members = list(members)
-        refuse_c51_members(members, "QActorPopulation")
+        if refuse is not None:
+            refuse(members)
         if not 1 <= len(members) <= _capi.DDPG_POP_MAX:
             raise ValueError("a population has 1 ... %d members, not %d" % (_capi.DDPG_POP_MAX, len(members)))
         self.P, self.n_per_member = len(members), int(n_per_member)
         if self.n_per_member < 1:
             raise ValueError("n_per_member must be positive")
         self.n = self.P * self.n_per_member
+        return members
+
+    def _build(self, members, ctx, S, shape, actor_cls, is_learner, create):
+        """... and end with, once kinds and shapes were checked: a one-row ``actor_cls`` per member that is not one yet, the row buffers, the handle
+        ``create`` makes of the members' handles."""
+        import torch
+        self.torch, self.ctx, self.engine, self.dtype, self.shape = torch, ctx, "hip", torch.float32, shape
+        self.members = []
+        for item in members:
+            if isinstance(item, actor_cls):
+                a = item
+            elif is_learner(item):
+                a = actor_cls.from_learner(item, 1, ctx, S)             # (its own row buffers stay unused: the population has them)
+            else:
+                a = actor_cls(item, 1, ctx, S)
+            self.members.append(a)
+        self.fcfg, self.flen = self.members[0].fcfg, self.members[0].flen
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.feat = torch.empty(self.n, self.flen, dtype=torch.float32, device=dev)
+        self.q = torch.empty(self.n, self.shape[2], dtype=torch.float32, device=dev)
+        self.action = torch.empty(self.n, dtype=torch.int32, device=dev)
+        self.jerk = torch.empty(self.n, dtype=torch.float64, device=dev)
+        self.keep_features = self.keep_q = False
+        self.handle = create([a.handle for a in self.members])
+
+    def __init__(self, members, n_per_member, ctx, S):
+        members = self._take(members, n_per_member, lambda items: refuse_c51_members(items, "QActorPopulation"))
         # kinds and shapes first, from the host's data alone: nothing is built for a list that will be refused
         shapes = []
         for item in members:
@@ -517,25 +549,7 @@ class QActorPopulation:
         for m, sh in enumerate(shapes):
             if pad(sh) != pad(shapes[0]):
                 raise ValueError("member %d is %d -> %d -> %d, member 0 is %d -> %d -> %d: one launch needs one shape" % ((m,) + sh + shapes[0]))
-        import torch
-        self.torch, self.ctx, self.engine, self.dtype, self.shape = torch, ctx, "hip", torch.float32, shapes[0]
-        self.members = []
-        for item in members:
-            if isinstance(item, DQNActor):
-                a = item
-            elif _is_dqn_learner(item):
-                a = DQNActor.from_learner(item, 1, ctx, S)              # (its own row buffers stay unused: the population has them)
-            else:
-                a = DQNActor(item, 1, ctx, S)
-            self.members.append(a)
-        self.fcfg, self.flen = self.members[0].fcfg, self.members[0].flen
-        dev = torch.device("cuda", torch.cuda.current_device())
-        self.feat = torch.empty(self.n, self.flen, dtype=torch.float32, device=dev)
-        self.q = torch.empty(self.n, self.shape[2], dtype=torch.float32, device=dev)
-        self.action = torch.empty(self.n, dtype=torch.int32, device=dev)
-        self.jerk = torch.empty(self.n, dtype=torch.float64, device=dev)
-        self.keep_features = self.keep_q = False
-        self.handle = ctx.qactor_pop_create([a.handle for a in self.members])
+        self._build(members, ctx, S, shapes[0], DQNActor, _is_dqn_learner, lambda handles: ctx.qactor_pop_create(handles))
 
     def __del__(self):
         if getattr(self, "handle", None) is not None:
@@ -555,6 +569,64 @@ class QActorPopulation:
                                         cur_ov.data_ptr(), cur_oa.data_ptr() if cur_oa is not None else 0, self.feat.data_ptr() if self.keep_features else 0,
                                         self.flen, self.action.data_ptr(), self.q.data_ptr() if self.keep_q else 0, self.jerk.data_ptr(), stream)
         return self.jerk
+
+
+def _is_c51_member(item):
+    return isinstance(item, C51Actor) or _is_c51_learner(item) or _is_c51_file(item)
+
+
+def all_c51(items):
+    """True when ``items`` is not empty and every item is a C51 policy (a ``C51Actor``, a ``learner.C51Learner``, a ``C51Learner.export_q`` file):
+    what ``C51ActorPopulation`` takes.  Reads the items alone."""
+    items = list(items)
+    return bool(items) and all(_is_c51_member(item) for item in items)
+
+
+class C51ActorPopulation(QActorPopulation):
+    """``QActorPopulation`` for categorical (C51) policies: P logits networks, each with its own support and on its own slice of one batch,
+    evaluated in ONE launch (``k_c51actor_eval_pop``, csrc/stmpc_c51actor_pop_kernels.hpp; ``stmpc_pop_c51actor_create``).  A subclass: whatever
+    takes a ``QActorPopulation`` -- ``combined.decide_batch_device``, ``episodes.EpisodeRunner``, ``vec_env.QCombinedShieldVecEnv`` -- takes it, and
+    ``__call__``, ``reset``, ``keep_features`` / ``keep_q``, ``P``, ``n_per_member`` and ``n`` are the parent's.
+
+    ``members``: a list whose items are files written by ``learner.C51Learner.export_q`` (jerk mode, the file's table), ``learner.C51Learner``s (a
+    zero-copy view of the online network each, see ``C51Actor.from_learner``) or existing ``C51Actor``s (file actors or views, online or target,
+    either mode); or a ``learner.C51Population`` (one view of ``member(m)`` each).  The members share n_in, the hidden width padded to a multiple of
+    16, the action count, ``n_atoms`` and the head (dueling or not); support, table, mode, limits and online / target may differ.  Kinds and shapes
+    are checked from host data before anything is built or the library is called; a DQN member is refused (``QActorPopulation`` is theirs).
+    Member m evaluates rows [m * n_per_member, (m + 1) * n_per_member) and is bit-identical to a lone ``C51Actor`` on that slice; its arithmetic
+    on the host is ``c51_policy_host`` on that slice.  A view is live, and a view of a noisy learner evaluates the mean weights, as ``C51Actor``
+    does.  ``.q`` (with ``keep_q``) holds the expected values, float32 [n][A]; ``.shape`` is (n_in, h1, A) of member 0, ``.n_atoms`` and
+    ``.dueling`` the common head."""
+
+    def __init__(self, members, n_per_member, ctx, S):
+        members = self._take(members, n_per_member)
+        # kinds and shapes first, from the host's data alone: nothing is built for a list that will be refused.  (n_in, h1, A, n_atoms, dueling)
+        shapes = []
+        for m, item in enumerate(members):
+            if isinstance(item, C51Actor):
+                shapes.append(tuple(item.shape) + (int(item.n_atoms), bool(item.dueling)))
+            elif _is_c51_learner(item):
+                c = item.cfg
+                shapes.append((c.n_obs, c.h1, c.n_actions, int(c.n_atoms), bool(getattr(c, "dueling", False))))
+            elif _is_c51_file(item):
+                with np.load(os.fspath(item)) as z:
+                    K, duel = int(z["n_atoms"]), bool(int(z["dueling"])) if "dueling" in z.files else False
+                    rows = int(z["w1"].shape[0])
+                    if K < 1 or rows % K or rows // K - duel < 1:
+                        raise ValueError("member %d: the last layer has %d rows, not %s blocks of n_atoms = %d" % (m, rows, "a value block and advantage" if duel else "whole", K))
+                    shapes.append((int(z["w0"].shape[1]), int(z["w0"].shape[0]), rows // K - duel, K, duel))
+            elif _is_q_member(item) or (isinstance(item, (str, os.PathLike)) and os.path.isfile(os.fspath(item))):
+                raise ValueError("member %d is a Q-network (a DQNActor, a DQNLearner or a DQNLearner.export_q file), not a categorical (C51) policy: one launch needs "
+                                 "one head; Q-networks share a population of their own, actor.QActorPopulation" % m)
+            else:
+                raise ValueError("a member is a C51Learner.export_q file, a C51Learner or a C51Actor, not %r" % (item,))
+        pad = lambda sh: (sh[0], (sh[1] + 15) & ~15) + sh[2:]
+        text = lambda sh: "%d -> %d -> %d x %d atoms%s" % (sh[:4] + (" (dueling)" if sh[4] else "",))
+        for m, sh in enumerate(shapes):
+            if pad(sh) != pad(shapes[0]):
+                raise ValueError("member %d is %s, member 0 is %s: one launch needs one shape and one head" % (m, text(sh), text(shapes[0])))
+        self.n_atoms, self.dueling = shapes[0][3], shapes[0][4]
+        self._build(members, ctx, S, shapes[0][:3], C51Actor, _is_c51_learner, lambda handles: ctx.c51actor_pop_create(handles))
 
 
 def population_of(members, n_per_member, ctx, S, **kw):

@@ -24,6 +24,7 @@
 #include "stmpc_qactor_kernels.hpp"
 #include "stmpc_c51actor_kernels.hpp"
 #include "stmpc_qactor_pop_kernels.hpp"
+#include "stmpc_c51actor_pop_kernels.hpp"
 #include <initializer_list>
 #include <utility>
 
@@ -2172,12 +2173,18 @@ struct stmpc_qactor_pop {
     DevBuf table;                           // QActorMember [P], built once at create.  A view's entry copies its learner's dev.base.q: net_build wires those
                                             // pointers in stmpc_dqn_create and nothing re-wires them before destroy (stmpc_dqn_per_enable and
                                             // stmpc_pop_dqn_per_enable go through Replay::wire, which writes the replay's part of dev.base alone)
+    bool categorical = false;               // stmpc_pop_c51actor_create made it: the table is C51ActorMember [P] and k_c51actor_eval_pop evaluates it.  A view's
+                                            // entry copies its learner's dev.dq.base.q, shape and support (K, dueling, v_min, v_max, dz): q_create wires them
+                                            // (net_build, C51Head::wire) and nothing re-wires them before destroy -- stmpc_c51_per_enable, stmpc_pop_c51_per_enable
+                                            // and the multi-step enables go through Replay::wire (the replay's part of dev.dq.base alone), q_pop_upload copies the
+                                            // members' structs as they are, and a noisy learner's shadow structs are copies that leave t->dev on mu
     int P = 0, n_in = 0;
     size_t lds = 0;
     // what qshield_policy_check compares with an env, per member: the mode, the limits, the host's copy of the action table
     struct Meta { int mode; double tick, jerk_min, jerk_max; std::vector<double> table; };
     std::vector<Meta> meta;
     const QActorMember *dev() const { return table.as<QActorMember>(); }
+    const C51ActorMember *dev_c51() const { return table.as<C51ActorMember>(); }
 };
 
 namespace {
@@ -2185,8 +2192,25 @@ int qactor_pop_raise_lds(int device, size_t lds) {
     static LdsCeiling ceiling;
     return raise_dynamic_lds((const void *)k_qactor_eval_pop, "k_qactor_eval_pop", ceiling, device, lds);
 }
+int c51actor_pop_raise_lds(int device, size_t lds) {
+    static LdsCeiling ceiling;
+    return raise_dynamic_lds((const void *)k_c51actor_eval_pop, "k_c51actor_eval_pop", ceiling, device, lds);
+}
 // the struct k_qactor_eval gets for this actor
 const DqnDev &qactor_dev(const stmpc_qactor *q) { return q->learner ? q->learner->dev : q->dev; }
+// what both kinds of population end their create with: the handle around an uploaded member table, the members' meta, the kernel's dynamic LDS
+template <class Member> int qactor_pop_finish(stmpc_ctx *c, const stmpc_qactor *const *qactors, const std::vector<Member> &host, bool categorical, stmpc_qactor_pop **out) {
+    const int P = (int)host.size();
+    HIPCHK(hipSetDevice(c->device));
+    stmpc_qactor_pop *p = new stmpc_qactor_pop();
+    p->device = c->device; p->categorical = categorical; p->P = P; p->n_in = qactors[0]->n_in; p->lds = qactors[0]->lds;
+    for (int m = 0; m < P; ++m) p->meta.push_back({qactors[m]->mode, qactors[m]->tick, qactors[m]->jerk_min, qactors[m]->jerk_max, qactors[m]->table_h});
+    int rc = upload(p->table, host.data(), host.size());
+    if (!rc) rc = categorical ? c51actor_pop_raise_lds(c->device, p->lds) : qactor_pop_raise_lds(c->device, p->lds);
+    if (rc) { stmpc_pop_qactor_destroy(p); return rc; }
+    *out = p;
+    return STMPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2203,7 +2227,7 @@ int stmpc_pop_qactor_create(stmpc_ctx *c, const stmpc_qactor *const *qactors, in
         if (q->device != c->device) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " and the context are on different devices");
         if (q->categorical)
             return fail(STMPC_EINVAL, "member " + std::to_string(m) + " has a categorical (C51) head: a population evaluates Q-networks, one launch needs one head; "
-                                      "evaluate a C51 policy alone (stmpc_qactor_eval_device)");
+                                      "evaluate a C51 policy alone (stmpc_qactor_eval_device), or C51 policies together (stmpc_pop_c51actor_create)");
         const DqnDev &d = qactor_dev(q), &d0 = qactor_dev(qactors[0]);
         if (q->n_in != qactors[0]->n_in || d.base.h1p != d0.base.h1p || d.Ap != d0.Ap || q->A != qactors[0]->A)
             return fail(STMPC_EINVAL, "the members of a population share n_in, the padded widths and n_actions (member " + std::to_string(m) + " differs from member 0)");
@@ -2212,15 +2236,34 @@ int stmpc_pop_qactor_create(stmpc_ctx *c, const stmpc_qactor *const *qactors, in
         host.push_back({d.base.q, q->n_in, d.base.h1p, q->A, d.Ap, q->learner ? q->target : 0, q->mode == STMPC_QACTOR_ACCELERATION, q->table.as<double>(), q->tick,
                         q->jerk_min, q->jerk_max});
     }
-    HIPCHK(hipSetDevice(c->device));
-    stmpc_qactor_pop *p = new stmpc_qactor_pop();
-    p->device = c->device; p->P = P; p->n_in = qactors[0]->n_in; p->lds = qactors[0]->lds;
-    for (int m = 0; m < P; ++m) p->meta.push_back({qactors[m]->mode, qactors[m]->tick, qactors[m]->jerk_min, qactors[m]->jerk_max, qactors[m]->table_h});
-    int rc = upload(p->table, host.data(), host.size());
-    if (!rc) rc = qactor_pop_raise_lds(c->device, p->lds);
-    if (rc) { stmpc_pop_qactor_destroy(p); return rc; }
-    *out = p;
-    return STMPC_OK;
+    return qactor_pop_finish(c, qactors, host, false, out);
+}
+
+int stmpc_pop_c51actor_create(stmpc_ctx *c, const stmpc_qactor *const *members, int P, stmpc_qactor_pop **out) {
+    if (out) *out = nullptr;                // (every refusal leaves *out NULL, a NULL context's too)
+    if (!c || !out) return fail(STMPC_EINVAL, "NULL argument");
+    if (P < 1 || P > STMPC_DDPG_POP_MAX) return fail(STMPC_EINVAL, "a population has 1 ... 64 members, not " + std::to_string(P));
+    if (!members) return fail(STMPC_EINVAL, "NULL argument");
+    std::vector<C51ActorMember> host;
+    C51Dev d0{};
+    for (int m = 0; m < P; ++m) {
+        const stmpc_qactor *q = members[m];
+        if (!q) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " is NULL");
+        if (q->device != c->device) return fail(STMPC_EINVAL, "member " + std::to_string(m) + " and the context are on different devices");
+        if (!q->categorical)
+            return fail(STMPC_EINVAL, "member " + std::to_string(m) + " is a Q-network, not a categorical (C51) policy: one launch needs one head; Q-networks "
+                                      "share a population of their own (stmpc_pop_qactor_create)");
+        const C51Dev d = c51actor_dev(q);
+        if (m == 0) d0 = d;
+        if (q->n_in != members[0]->n_in || d.dq.base.h1p != d0.dq.base.h1p || d.dq.Ap != d0.dq.Ap || q->A != members[0]->A || d.K != d0.K || d.dueling != d0.dueling)
+            return fail(STMPC_EINVAL, "the members of a population share n_in, the padded hidden width, n_actions, n_atoms and the head, dueling or not (member " +
+                                      std::to_string(m) + " differs from member 0)");
+        if (q->mode == STMPC_QACTOR_ACCELERATION && !q->limits)
+            return fail(STMPC_EINVAL, "member " + std::to_string(m) + " is in acceleration mode and needs the tick length and the jerk limits (stmpc_qactor_set_limits)");
+        host.push_back({d.dq.base.q, q->n_in, d.dq.base.h1p, q->A, d.dq.Ap, d.K, d.dueling, d.v_min, d.v_max, d.dz, q->c51 ? q->target : 0,
+                        q->mode == STMPC_QACTOR_ACCELERATION, q->table.as<double>(), q->tick, q->jerk_min, q->jerk_max});
+    }
+    return qactor_pop_finish(c, members, host, true, out);
 }
 
 void stmpc_pop_qactor_destroy(stmpc_qactor_pop *p) {
@@ -2253,8 +2296,13 @@ int qactor_pop_eval_run(stmpc_ctx *c, const stmpc_qactor_pop *p, const FeatCfg &
     const int *live;
     TRY(rollout_live(c, n_per_member * p->P, step, &live));
     HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_qactor_eval_pop, dim3((n_per_member + AT_TM - 1) / AT_TM, p->P), dim3(AT_THREADS), p->lds, (hipStream_t)stream, fc, p->dev(), n_per_member, Kmax,
-                       d_cur_ego4, d_k, d_cur_ox, d_cur_ov, d_cur_oa, live, d_feat, feat_stride, d_action, d_q, d_jerk);
+    const dim3 grid((n_per_member + AT_TM - 1) / AT_TM, p->P);
+    if (p->categorical)
+        hipLaunchKernelGGL(k_c51actor_eval_pop, grid, dim3(AT_THREADS), p->lds, (hipStream_t)stream, fc, p->dev_c51(), n_per_member, Kmax, d_cur_ego4, d_k, d_cur_ox,
+                           d_cur_ov, d_cur_oa, live, d_feat, feat_stride, d_action, d_q, d_jerk);
+    else
+        hipLaunchKernelGGL(k_qactor_eval_pop, grid, dim3(AT_THREADS), p->lds, (hipStream_t)stream, fc, p->dev(), n_per_member, Kmax, d_cur_ego4, d_k, d_cur_ox,
+                           d_cur_ov, d_cur_oa, live, d_feat, feat_stride, d_action, d_q, d_jerk);
     HIPCHK(hipGetLastError());
     return STMPC_OK;
 }

@@ -409,7 +409,7 @@ def grid_search_st(n_per_cell, seed=0, traffic=None, cells=None, common_random_n
 def grid_search_combined(model, traffic, n_per_cell, cells=None, seed=0, common_random_numbers=True, ctx=None, kmax=16, max_episode_length=100.0, record=None,
                          max_ticks=None, check_every=16):
     """The reference's ``main.do_grid_search_combined`` (main.py:62-81: one ``EVALUATE_COMBINED_DDPG`` process per cell) in ONE run: ``model`` (as
-    ``actor.population_of`` takes a member: a DDPG model, or a ``DQNLearner`` / ``DQNActor``) under the combined controller on the traffic type ``traffic`` (as ``sim_cfgs`` takes one group), once
+    ``actor.population_of`` takes a member: a DDPG model, or a ``DQNLearner`` / ``DQNActor``; or a C51 policy, as ``actor.C51ActorPopulation`` takes one) under the combined controller on the traffic type ``traffic`` (as ``sim_cfgs`` takes one group), once
     per cell of ``cells`` (default ``combined.grid_search_cells()``; dicts as ``combined.control_cfgs`` takes them), ``n_per_cell`` episodes each.
     ``common_random_numbers``: every cell's traffic group gets the same seed (``seed``), so all cells face the same traffic draws and start
     speeds and differ by the controller alone -- something one process per cell cannot give; False: cell c's seed is
@@ -425,8 +425,10 @@ def grid_search_combined(model, traffic, n_per_cell, cells=None, seed=0, common_
     if common_random_numbers:
         t["seed"] = int(seed)
     ctx = ctx if ctx is not None else _capi.default_context()
-    one = actor.DDPGActor(os.fspath(model), 1, ctx, Settings) if isinstance(model, (str, os.PathLike)) else model
-    pop = actor.population_of([one] * C, int(n_per_cell), ctx, Settings)     # (a DQNLearner or a DQNActor: a population of Q-networks)
+    # (a shipped name or a path is a DDPG model, loaded once; a C51Learner.export_q file, likewise, as a one-row C51Actor)
+    one = (actor.C51Actor if actor.all_c51([model]) else actor.DDPGActor)(os.fspath(model), 1, ctx, Settings) if isinstance(model, (str, os.PathLike)) else model
+    # (a DQNLearner or a DQNActor: a population of Q-networks; a C51 policy: a population of categorical policies)
+    pop = (actor.C51ActorPopulation if actor.all_c51([one]) else actor.population_of)([one] * C, int(n_per_cell), ctx, Settings)
     stats = run_episodes(pop.n, seed=seed, controller="combined", policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, check_every=check_every,
                          max_ticks=max_ticks, record=record, traffic=[dict(t) for _ in range(C)], control=cells)
     by = summary_by_control(stats, C)
@@ -437,7 +439,7 @@ def cross_matrix(models, traffic, n_per_cell, seed=0, ctx=None, kmax=16, max_epi
                  controller="combined"):
     """The reference's ``combined_{traffic}_{seed}`` diagonal and ``cross_{traffic_1}_network_{traffic_2}_traffic_{seed}`` off-diagonals in ONE run:
     every model of ``models`` (as ``actor.population_of`` takes them: shipped names, paths, DDPG learners and actors -- or, all of them,
-    ``DQNLearner``s and ``DQNActor``s, for a matrix of Q-networks) under the combined controller on
+    ``DQNLearner``s and ``DQNActor``s, for a matrix of Q-networks; or, all of them, C51 policies as ``actor.C51ActorPopulation`` takes them) under the combined controller on
     every traffic group of ``traffic`` (as ``sim_cfgs`` takes them), ``n_per_cell`` episodes each.  Cell c = i * len(traffic) + j (row-major) pairs
     model i with traffic j: the population repeats each member len(traffic) times, the traffic list is tiled len(models) times, and the cells are
     the groups of one runner (cell c's default seed is ``vec_env.episode_seed(seed, c)``).  ``controller``: "combined" or "first_step" -- the same
@@ -457,10 +459,11 @@ def cross_matrix(models, traffic, n_per_cell, seed=0, ctx=None, kmax=16, max_epi
         raise ValueError("%d models x %d traffic groups = %d cells, at most %d fit one run" % (M, T, M * T, _capi.SIM_GROUPS_MAX))
     cell_traffic = [traffic_settings(t) for t in traffic] * M          # (validates the names before anything is built)
     ctx = ctx if ctx is not None else _capi.default_context()
-    # (a shipped name or a path is loaded once and its actor repeated along its row)
-    loaded = [actor.DDPGActor(os.fspath(m), 1, ctx, Settings) if isinstance(m, (str, os.PathLike)) else m for m in models]
+    # (a shipped name or a path is loaded once and its actor repeated along its row; a C51Learner.export_q file, likewise, as a one-row C51Actor)
+    loaded = [(actor.C51Actor if actor.all_c51([m]) else actor.DDPGActor)(os.fspath(m), 1, ctx, Settings) if isinstance(m, (str, os.PathLike)) else m for m in models]
     cell_models = [m for m in loaded for _ in range(T)]
-    pop = actor.population_of(cell_models, int(n_per_cell), ctx, Settings)
+    # (every model a C51 policy: a population of categorical policies; a mix of C51 and others is refused by population_of)
+    pop = (actor.C51ActorPopulation if actor.all_c51(cell_models) else actor.population_of)(cell_models, int(n_per_cell), ctx, Settings)
     stats = run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, check_every=check_every,
                          max_ticks=max_ticks, record=record, traffic=cell_traffic)
     cells = summary_by_group(stats, M * T)

@@ -1842,7 +1842,8 @@ class C51Population(DQNPopulation):
     float32 [env.n][n_actions].  ``member(m)`` is a ``C51Learner`` view: ``state_dict`` / ``load_state_dict``, ``grads``, ``targets``, ``dist``,
     ``project``, ``minibatch``, ``priorities``, ``last_sample``, ``nstep_window``, ``export_q``, ``actor.C51Actor.from_learner(pop.member(m), ...)`` and
     ``evaluate_dqn(pop.member(m), ...)`` work on it.  ``train_dqn`` takes a population.  A population of C51 POLICIES does not exist:
-    ``evaluate_dqn_members``, ``actor.QActorPopulation`` and ``actor.population_of`` refuse a ``C51Population`` as they refuse C51 members."""
+    ``evaluate_dqn_members``, ``actor.QActorPopulation`` and ``actor.population_of`` refuse a ``C51Population`` as they refuse C51 members: its
+    policies are evaluated together by ``evaluate_c51_members`` and ``actor.C51ActorPopulation``."""
 
     _api, _nstat = "c51_pop", 4
     _nstep_kind = "c51"                                             # (``ctx.pop_nstep_enable`` routes it to stmpc_pop_c51_multi_step_enable)
@@ -2123,6 +2124,37 @@ def evaluate_dqn_members(source, n_per_member, seed=0, kmax=16, max_episode_leng
     rep = stats.get("report")
     return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),
             "reports": rep.by_member(pop.P, traffic) if rep is not None else None}
+
+
+def evaluate_c51_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):
+    """``evaluate_dqn_members`` for categorical (C51) policies: ``n_per_member`` merge episodes per member under the combined controller, in ONE
+    run of P * n_per_member environments whose policy is an ``actor.C51ActorPopulation`` -- one launch per evaluation whatever P is, where
+    ``evaluate_dqn(pop.member(m), ...)`` takes P runners, P worlds and P launch sequences per tick.  ``source``: a ``C51Population`` or a
+    ``C51Learner`` (zero-copy views of the online networks as they are on the device; a noisy learner's view evaluates its mean weights), or a list
+    as ``C51ActorPopulation`` takes (``C51Learner.export_q`` files, learners, ``C51Actor``s).  The keywords, the refusals and the returned dict --
+    ``stats`` with ``member``, ``by_member``, ``reports`` -- are ``evaluate_dqn_members``'; a DQN member is refused (``evaluate_dqn_members`` is
+    theirs) before a context exists."""
+    from . import episodes
+    if controller not in ("combined", "first_step"):
+        raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
+    if isinstance(source, DQNPopulation) and not isinstance(source, C51Population):
+        raise ValueError("a DQNPopulation's members are Q-networks, not categorical (C51) policies: evaluate them with evaluate_dqn_members(pop, n_per_member, ...)")
+    members = source if isinstance(source, (C51Population, list, tuple)) else [source]
+    P = members.P if isinstance(members, C51Population) else len(members)
+    if not isinstance(members, C51Population):
+        q = [m for m, item in enumerate(members) if _actor._is_q_member(item) and not isinstance(item, _actor.C51Actor)]      # (a C51Actor is a DQNActor's subclass)
+        if q:
+            raise ValueError("evaluate_c51_members: members %s are Q-networks, not categorical (C51) policies (one launch needs one head); evaluate them with "
+                             "evaluate_dqn_members" % ", ".join(map(str, q)))
+    if traffic is not None and len(traffic) != P:
+        raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), P))
+    ctx = ctx if ctx is not None else _capi.Context(-1)
+    pop = _actor.C51ActorPopulation(members, n_per_member, ctx, Settings)
+    stats = episodes.run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
+                                  traffic=traffic)
+    rep_ = stats.get("report")
+    return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),
+            "reports": rep_.by_member(pop.P, traffic) if rep_ is not None else None}
 
 
 def evaluate_dqn(source, n, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):

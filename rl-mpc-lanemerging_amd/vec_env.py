@@ -655,7 +655,7 @@ class QCombinedShieldVecEnv(_CombinedShieldEnv):
     ``policy``: a hip-engine ``actor.DQNActor`` of ``n`` rows on the env's context (``ctx`` defaults to the policy's) -- an ``export_q`` file, or
     ``DQNActor.from_learner(learner, n, ctx, S, target=...)``, a zero-copy view, so a step queued after ``learner.update`` on the same stream rolls out
     with the updated weights; or an ``actor.C51Actor``, its subclass for a categorical network (a ``C51Learner.export_q`` file, or
-    ``C51Actor.from_learner``, which sees ``C51Learner.update`` the same way) -- or an ``actor.QActorPopulation`` with ``P * n_per_member == n``: member m proposes for rows ``[m * n_per_member, (m + 1)
+    ``C51Actor.from_learner``, which sees ``C51Learner.update`` the same way) -- or an ``actor.QActorPopulation`` (or its subclass for categorical policies, ``actor.C51ActorPopulation``) with ``P * n_per_member == n``: member m proposes for rows ``[m * n_per_member, (m + 1)
     * n_per_member)`` of the one world.  Its mode and action table must be the env's ("jerk" with JERK_VALUES_DQN, "acceleration" with
     ACCELERATION_VALUES_DQN, byte for byte).  The env keeps it alive.
     ``control``, ``shield_sparse``, ``takeover_penalty``, ``shield_kmax``: as ``CombinedShieldVecEnv`` takes them; ``shield_counts()`` reads
