@@ -1135,23 +1135,57 @@ class Context:
         """Environment status words into a device int32 array (asynchronous): 0 running, 1 arrived, 2 crashed, 3 out of time."""
         self._chk(self._lib.stmpc_sim_status_device(self._h, int(N), d_status, stream))
 
+    # -- what the learner families' methods below share: each piece of marshalling once ------------------------
+    def _new_handle(self, entry, *args):
+        """``entry(ctx, *args, &handle)``: the new handle."""
+        h = C.c_void_p()
+        self._chk(entry(self._h, *args, C.byref(h)))
+        return h
+
+    def _borrowed(self, h):
+        """A handle another object owns (a population's member, a TD3 learner's base) as a ``c_void_p``; NULL is ``STMPC_EINVAL``."""
+        if not h:
+            self._chk(STMPC_EINVAL)
+        return C.c_void_p(h)
+
+    def _slot_in(self, entry, handle, slot, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        self._chk(entry(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+
+    def _slot_out(self, entry, handle, slot, count):
+        flat = np.empty(int(count), dtype=np.float32)
+        self._chk(entry(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        return flat
+
+    def _rows_out(self, entry, handle, first, count):
+        """``count`` rows from row ``first`` of a learner's ring, float32 [count][DDPG_ROW]; synchronises."""
+        rows = np.zeros((int(count), DDPG_ROW), dtype=np.float32)
+        self._chk(entry(handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
+        return rows
+
+    def _tree_out(self, entry, handle, first, count):
+        """``count`` nodes from node ``first`` of a learner's sum tree, float64; synchronises."""
+        nodes = np.empty(int(count), dtype=np.float64)
+        self._chk(entry(handle, int(first), int(count), nodes.ctypes.data_as(C.POINTER(C.c_double))))
+        return nodes
+
+    @staticmethod
+    def _table(elem, cfgs):
+        """The contiguous ``elem[len(cfgs)]`` a population's entry takes, from a sequence of ``elem``."""
+        return (elem * len(cfgs))(*cfgs)
+
     # -- DDPG learner (stmpc_ddpg_*): the handle belongs to this context's device ------------------------
     def ddpg_create(self, cfg):
-        h = C.c_void_p()
-        self._chk(self._lib.stmpc_ddpg_create(self._h, C.byref(cfg), C.byref(h)))
-        return h
+        return self._new_handle(self._lib.stmpc_ddpg_create, C.byref(cfg))
 
     def ddpg_destroy(self, handle):
         self._lib.stmpc_ddpg_destroy(handle)
 
     def ddpg_set_params(self, handle, slot, flat):
-        flat = np.ascontiguousarray(flat, dtype=np.float32)
-        self._chk(self._lib.stmpc_ddpg_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        self._slot_in(self._lib.stmpc_ddpg_set_params, handle, slot, flat)
 
     def ddpg_get_params(self, handle, slot, count):
-        flat = np.empty(int(count), dtype=np.float32)
-        self._chk(self._lib.stmpc_ddpg_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
-        return flat
+        return self._slot_out(self._lib.stmpc_ddpg_get_params, handle, slot, count)
 
     def ddpg_set_state(self, handle, counters, beta_pow):
         cn = np.ascontiguousarray(counters, dtype=np.int64)
@@ -1182,9 +1216,7 @@ class Context:
         self._chk(self._lib.stmpc_ddpg_stats_device(handle, d_out, stream))
 
     def ddpg_replay_read(self, handle, first, count):
-        rows = np.empty((int(count), DDPG_ROW), dtype=np.float32)
-        self._chk(self._lib.stmpc_ddpg_replay_read(handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
-        return rows
+        return self._rows_out(self._lib.stmpc_ddpg_replay_read, handle, first, count)
 
     def ddpg_gather(self, handle, d_rows, stream=0):
         self._chk(self._lib.stmpc_ddpg_gather_device(handle, d_rows, stream))
@@ -1194,26 +1226,10 @@ class Context:
         self._chk(self._lib.stmpc_per_enable(handle, C.byref(cfg)))
 
     def per_tree_read(self, handle, first, count):
-        nodes = np.empty(int(count), dtype=np.float64)
-        self._chk(self._lib.stmpc_per_tree_read(handle, int(first), int(count), nodes.ctypes.data_as(C.POINTER(C.c_double))))
-        return nodes
+        return self._tree_out(self._lib.stmpc_per_tree_read, handle, first, count)
 
     def per_last(self, handle, d_idx, d_td, d_weight, stream=0):
         self._chk(self._lib.stmpc_per_last_device(handle, d_idx, d_td, d_weight, stream))
-
-    # -- prioritised replay for the populations (stmpc_pop_per_*): once per population, on empty rings ------------------------
-    @staticmethod
-    def _per_table(cfgs):
-        """``cfgs``: one ``PERCfg`` or None per member -> (PERCfg [P], uint8 [P], P); a None member keeps sampling uniformly."""
-        P = len(cfgs)
-        arr = (PERCfg * P)(*[c if c is not None else PERCfg() for c in cfgs])
-        return arr, (C.c_uint8 * P)(*[int(c is not None) for c in cfgs]), P
-
-    def ddpg_pop_per_enable(self, handle, cfgs):
-        self._chk(self._lib.stmpc_pop_per_enable_ddpg(handle, *self._per_table(cfgs)))
-
-    def td3_pop_per_enable(self, handle, cfgs):
-        self._chk(self._lib.stmpc_pop_per_enable_td3(handle, *self._per_table(cfgs)))
 
     # -- the discrete learners (stmpc_dqn_*, stmpc_c51_*): the DQN agent and the categorical one; the handle belongs to this context's device.  The
     # entries both have are written once with the ``kind`` ("dqn" or "c51") in front and bound as ``dqn_<name>`` and ``c51_<name>`` below the class
@@ -1221,21 +1237,16 @@ class Context:
         return getattr(self._lib, "stmpc_%s_%s" % (kind, name))
 
     def _q_create(self, kind, cfg):
-        h = C.c_void_p()
-        self._chk(self._q(kind, "create")(self._h, C.byref(cfg), C.byref(h)))
-        return h
+        return self._new_handle(self._q(kind, "create"), C.byref(cfg))
 
     def _q_destroy(self, kind, handle):
         self._q(kind, "destroy")(handle)
 
     def _q_set_params(self, kind, handle, slot, flat):
-        flat = np.ascontiguousarray(flat, dtype=np.float32)
-        self._chk(self._q(kind, "set_params")(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        self._slot_in(self._q(kind, "set_params"), handle, slot, flat)
 
     def _q_get_params(self, kind, handle, slot, count):
-        flat = np.empty(int(count), dtype=np.float32)
-        self._chk(self._q(kind, "get_params")(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
-        return flat
+        return self._slot_out(self._q(kind, "get_params"), handle, slot, count)
 
     def _q_set_state(self, kind, handle, counters, beta_pow):
         cn = np.ascontiguousarray(counters, dtype=np.int64)
@@ -1274,9 +1285,7 @@ class Context:
         self._chk(self._q(kind, "per_enable")(handle, C.byref(cfg)))
 
     def _q_per_tree_read(self, kind, handle, first, count):
-        nodes = np.empty(int(count), dtype=np.float64)
-        self._chk(self._q(kind, "per_tree_read")(handle, int(first), int(count), nodes.ctypes.data_as(C.POINTER(C.c_double))))
-        return nodes
+        return self._tree_out(self._q(kind, "per_tree_read"), handle, first, count)
 
     def _q_per_last(self, kind, handle, d_idx, d_td, d_weight, stream=0):
         self._chk(self._q(kind, "per_last_device")(handle, d_idx, d_td, d_weight, stream))
@@ -1285,8 +1294,7 @@ class Context:
         """Debug: a slot (0 ... 3, or ``DQN_GRAD`` / ``C51_GRAD``) in the library's padded layout as {w0 [h1p][32], b0 [h1p], w1 [Ap][h1p], b1 [Ap]};
         ``n_out``: the network's output width, n_actions of DQN and n_actions * n_atoms of C51; synchronises."""
         h1p, Ap = (int(h1) + 15) & ~15, (int(n_out) + 15) & ~15
-        flat = np.empty(33 * h1p + (h1p + 1) * Ap, dtype=np.float32)
-        self._chk(self._q(kind, "padded_read")(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        flat = self._slot_out(self._q(kind, "padded_read"), handle, slot, 33 * h1p + (h1p + 1) * Ap)
         o = np.cumsum([0, 32 * h1p, h1p, Ap * h1p, Ap])
         return {"w0": flat[o[0]:o[1]].reshape(h1p, 32), "b0": flat[o[1]:o[2]], "w1": flat[o[2]:o[3]].reshape(Ap, h1p), "b1": flat[o[3]:o[4]]}
 
@@ -1299,9 +1307,7 @@ class Context:
 
     def c51_replay_read(self, handle, first, count):
         """Debug: ``count`` rows from row ``first`` of a C51 learner's ring, float32 [count][DDPG_ROW]; synchronises."""
-        rows = np.zeros((int(count), DDPG_ROW), dtype=np.float32)
-        self._chk(self._lib.stmpc_c51_replay_read(handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
-        return rows
+        return self._rows_out(self._lib.stmpc_c51_replay_read, handle, first, count)
 
     def c51_dzout_read(self, handle, batch, n_logits):
         """Debug: the output layer's gradient of the last pass, float32 [Bp][Ap] (``batch`` rounded up to 16, ``n_logits`` to 16); synchronises."""
@@ -1314,112 +1320,112 @@ class Context:
         self._chk(self._lib.stmpc_noisy_c51_enable(handle, C.byref(NoisyCfg(sigma0=float(sigma0)))))
 
     def noisy_c51_set_params(self, handle, slot, flat):
-        flat = np.ascontiguousarray(flat, dtype=np.float32)
-        self._chk(self._lib.stmpc_noisy_c51_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        self._slot_in(self._lib.stmpc_noisy_c51_set_params, handle, slot, flat)
 
     def noisy_c51_get_params(self, handle, slot, count):
-        flat = np.empty(int(count), dtype=np.float32)
-        self._chk(self._lib.stmpc_noisy_c51_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
-        return flat
+        return self._slot_out(self._lib.stmpc_noisy_c51_get_params, handle, slot, count)
 
     def noisy_c51_act(self, handle, N, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
         self._chk(self._lib.stmpc_noisy_c51_act_device(handle, int(N), d_obs, int(obs_stride), float(eps), d_action, d_debug_q, stream))
 
     def noisy_c51_debug_read(self, handle, what, count):
         """Debug: quantity ``what`` (STMPC_NOISY_F_* / _WEFF_* / _WEFF_PADDED_*) as float32 [count]; synchronises."""
-        out = np.empty(int(count), dtype=np.float32)
-        self._chk(self._lib.stmpc_noisy_c51_debug_read(handle, int(what), out.ctypes.data_as(C.POINTER(C.c_float)), int(out.size)))
-        return out
+        return self._slot_out(self._lib.stmpc_noisy_c51_debug_read, handle, what, count)
 
     def c51_pop_noisy_enable(self, handle, sigma0s):
         """``sigma0s``: one value per member (``stmpc_pop_noisy_c51_enable``)."""
-        table = (NoisyCfg * len(sigma0s))(*[NoisyCfg(sigma0=float(s)) for s in sigma0s])
-        self._chk(self._lib.stmpc_pop_noisy_c51_enable(handle, table, len(sigma0s)))
+        self._chk(self._lib.stmpc_pop_noisy_c51_enable(handle, self._table(NoisyCfg, [NoisyCfg(sigma0=float(s)) for s in sigma0s]), len(sigma0s)))
 
     def c51_pop_noisy_act(self, handle, n_per_member, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
         eps = np.ascontiguousarray(eps, dtype=np.float64)
         self._chk(self._lib.stmpc_pop_noisy_c51_act_device(handle, int(n_per_member), d_obs, int(obs_stride), eps.ctypes.data_as(C.POINTER(C.c_double)), int(eps.size),
                                                            d_action, d_debug_q, stream))
 
-    # -- populations of discrete learners (stmpc_pop_dqn_*, stmpc_pop_c51_*): P learners, one launch per kernel (dqn.py:257-359); written once as the
-    # lone learners' are, and bound as ``dqn_pop_<name>`` and ``c51_pop_<name>`` below the class
-    def _q_pop(self, kind, name):
-        return getattr(self._lib, "stmpc_pop_%s_%s" % (kind, name))
+    # -- populations (stmpc_ddpg_pop_*, stmpc_pop_td3_*, stmpc_pop_dqn_*, stmpc_pop_c51_*): P learners, one launch per kernel.  Written once with the
+    # ``kind`` in front, as the discrete learners' are, and bound as ``<kind>_pop_<name>`` below the class: the six methods every population has, then
+    # what only the discrete kinds have in this form (``_q_pop_*``); ``act`` / ``push`` / ``update`` of the continuous kinds: ``_continuous_pop_steps``.
+    _POPS = {       # kind: (the entries' prefix, the entry of per_enable, the cfg struct)
+        "ddpg": ("stmpc_ddpg_pop_", "stmpc_pop_per_enable_ddpg", DDPGCfg), "td3": ("stmpc_pop_td3_", "stmpc_pop_per_enable_td3", TD3Cfg),
+        "dqn": ("stmpc_pop_dqn_", "stmpc_pop_dqn_per_enable", DQNCfg), "c51": ("stmpc_pop_c51_", "stmpc_pop_c51_per_enable", C51Cfg)}
 
-    def _q_pop_create(self, kind, cfgs):
-        """``cfgs``: a sequence of ``DQNCfg`` / ``C51Cfg``; the library checks the member count and that the launch shapes (a C51 population's n_atoms
+    def _pop(self, kind, name):
+        return getattr(self._lib, self._POPS[kind][0] + name)
+
+    def _pop_create(self, kind, cfgs):
+        """``cfgs``: a sequence of the kind's cfg struct; the library checks the member count and that the launch shapes (a C51 population's n_atoms
         included) are common."""
-        arr = ({"dqn": DQNCfg, "c51": C51Cfg}[kind] * len(cfgs))(*cfgs)
-        h = C.c_void_p()
-        self._chk(self._q_pop(kind, "create")(self._h, arr, len(cfgs), C.byref(h)))
-        return h
+        return self._new_handle(self._pop(kind, "create"), self._table(self._POPS[kind][2], cfgs), len(cfgs))
 
-    def _q_pop_destroy(self, kind, handle):
-        self._q_pop(kind, "destroy")(handle)
+    def _pop_destroy(self, kind, handle):
+        self._pop(kind, "destroy")(handle)
 
-    def _q_pop_size(self, kind, handle):
-        return int(self._q_pop(kind, "size")(handle))
+    def _pop_size(self, kind, handle):
+        return int(self._pop(kind, "size")(handle))
 
-    def _q_pop_member(self, kind, handle, m):
-        """The m-th member as a borrowed ``stmpc_dqn`` / ``stmpc_c51`` handle for the lone learner's methods above (never destroy it)."""
-        h = self._q_pop(kind, "member")(handle, int(m))
-        if not h:
-            self._chk(STMPC_EINVAL)
-        return C.c_void_p(h)
+    def _pop_member(self, kind, handle, m):
+        """The m-th member as a borrowed handle of the lone learner's kind (``stmpc_ddpg``, ``stmpc_td3``, ...) for its methods above (never destroy it)."""
+        return self._borrowed(self._pop(kind, "member")(handle, int(m)))
+
+    def _pop_stats(self, kind, handle, d_out, stream=0):
+        self._chk(self._pop(kind, "stats_device")(handle, d_out, stream))
+
+    def _pop_per_enable(self, kind, handle, cfgs):
+        """Prioritised replay, once per population, on empty rings.  ``cfgs``: one ``PERCfg`` or None per member; a None member keeps sampling uniformly."""
+        on = (C.c_uint8 * len(cfgs))(*[int(c is not None) for c in cfgs])
+        self._chk(getattr(self._lib, self._POPS[kind][1])(handle, self._table(PERCfg, [c if c is not None else PERCfg() for c in cfgs]), on, len(cfgs)))
 
     def _q_pop_act(self, kind, handle, n_per_member, d_obs, obs_stride, eps, d_action, d_debug_q=0, stream=0):
         """``eps``: one value per member (the library checks the length and the range)."""
         e = np.ascontiguousarray(eps, dtype=np.float64).reshape(-1)
-        self._chk(self._q_pop(kind, "act_device")(handle, int(n_per_member), d_obs, int(obs_stride), _dptr(e), int(e.size), d_action, d_debug_q, stream))
+        self._chk(self._pop(kind, "act_device")(handle, int(n_per_member), d_obs, int(obs_stride), _dptr(e), int(e.size), d_action, d_debug_q, stream))
 
     def _q_pop_push(self, kind, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_action, d_reward, d_terminated, d_truncated, stream=0):
-        self._chk(self._q_pop(kind, "push_device")(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated,
-                                                   d_truncated, stream))
+        self._chk(self._pop(kind, "push_device")(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_action, d_reward, d_terminated,
+                                                 d_truncated, stream))
 
     def _q_pop_update(self, kind, handle, n_updates, lr, stream=0):
         """``lr``: one learning rate per member (the library checks the length)."""
         lr = np.ascontiguousarray(lr, dtype=np.float64).reshape(-1)
-        self._chk(self._q_pop(kind, "update_device")(handle, int(n_updates), _dptr(lr), int(lr.size), stream))
-
-    def _q_pop_stats(self, kind, handle, d_out, stream=0):
-        self._chk(self._q_pop(kind, "stats_device")(handle, d_out, stream))
-
-    def _q_pop_per_enable(self, kind, handle, cfgs):
-        self._chk(self._q_pop(kind, "per_enable")(handle, *self._per_table(cfgs)))
+        self._chk(self._pop(kind, "update_device")(handle, int(n_updates), _dptr(lr), int(lr.size), stream))
 
     def _q_pop_replay_read(self, kind, learner_handle, first, count):
         """Debug: ``count`` rows from row ``first`` of a learner's ring (a borrowed member's or a lone learner's), float32 [count][DDPG_ROW]; synchronises."""
-        rows = np.zeros((int(count), DDPG_ROW), dtype=np.float32)
-        self._chk(self._q_pop(kind, "replay_read")(learner_handle, int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_float))))
-        return rows
+        return self._rows_out(self._pop(kind, "replay_read"), learner_handle, first, count)
 
-    def c51_pop_multi_step_enable(self, handle, cfgs):
-        """``cfgs``: one ``NStepCfg`` per member (the stmpc_pop_nstep_ prefix is a closed set: ``pop_nstep_enable`` routes the kind "c51" here)."""
-        table = (NStepCfg * len(cfgs))(*cfgs)
-        self._chk(self._lib.stmpc_pop_c51_multi_step_enable(handle, table, len(cfgs)))
+    # -- multi-step returns: once per learner / population, on empty rings.  The stmpc_nstep_ and stmpc_pop_nstep_ prefixes are closed sets, so the
+    # C51 learner's entries carry ``multi_step`` in their own prefixes; a lone TD3 learner is its base, kind "ddpg"
+    _NSTEP = {      # kind: the entries of (nstep_enable, pop_nstep_enable, nstep_window)
+        "ddpg": ("stmpc_nstep_enable_ddpg", "stmpc_pop_nstep_enable_ddpg", "stmpc_nstep_window_ddpg"),
+        "td3": (None, "stmpc_pop_nstep_enable_td3", None),
+        "dqn": ("stmpc_nstep_enable_dqn", "stmpc_pop_nstep_enable_dqn", "stmpc_nstep_window_dqn"),
+        "c51": ("stmpc_c51_multi_step_enable", "stmpc_pop_c51_multi_step_enable", "stmpc_pop_c51_multi_step_window")}
 
-    def c51_pop_multi_step_window(self, learner_handle, idx):
-        """Debug: ``nstep_window`` for a C51 learner's handle (a borrowed member's or a lone learner's): float64 [len(idx)][4]; synchronises."""
-        return self.nstep_window("c51", learner_handle, idx)
+    def _nstep(self, kind, which):
+        name = self._NSTEP[kind][which]
+        if name is None:
+            raise ValueError("a lone TD3 learner's ring is its base's: its multi-step entries are the kind \"ddpg\"'s, on the base handle")
+        return getattr(self._lib, name)
 
-    # -- multi-step returns (stmpc_nstep_*, stmpc_pop_nstep_*): once per learner / population, on empty rings; ``kind``: "ddpg" (a TD3 learner's base too), "td3" (populations) or "dqn"
     def nstep_enable(self, kind, handle, cfg):
-        name = "stmpc_c51_multi_step_enable" if kind == "c51" else "stmpc_nstep_enable_" + kind      # (the stmpc_nstep_ prefix is a closed set)
-        self._chk(getattr(self._lib, name)(handle, C.byref(cfg)))
+        self._chk(self._nstep(kind, 0)(handle, C.byref(cfg)))
 
     def pop_nstep_enable(self, kind, handle, cfgs):
-        if kind == "c51":                                           # (the stmpc_pop_nstep_ prefix is a closed set)
-            return self.c51_pop_multi_step_enable(handle, cfgs)
-        table = (NStepCfg * len(cfgs))(*cfgs)
-        self._chk(getattr(self._lib, "stmpc_pop_nstep_enable_" + kind)(handle, table, len(cfgs)))
+        """``cfgs``: one ``NStepCfg`` per member."""
+        self._chk(self._nstep(kind, 1)(handle, self._table(NStepCfg, cfgs), len(cfgs)))
 
     def nstep_window(self, kind, handle, idx):
-        """Debug: float64 [len(idx)][4] = R, disc, the ring row of the window's last transition, m of the ring rows ``idx``; synchronises."""
+        """Debug: float64 [len(idx)][4] = R, disc, the ring row of the window's last transition, m of the ring rows ``idx`` of a learner's handle (a
+        borrowed member's or a lone learner's); synchronises."""
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         out = np.zeros((idx.size, 4), dtype=np.float64)
-        name = "stmpc_pop_c51_multi_step_window" if kind == "c51" else "stmpc_nstep_window_" + kind      # (the stmpc_nstep_ prefix is a closed set)
-        self._chk(getattr(self._lib, name)(handle, idx.ctypes.data_as(C.POINTER(C.c_int64)), int(idx.size), out.ctypes.data_as(C.POINTER(C.c_double))))
+        self._chk(self._nstep(kind, 2)(handle, idx.ctypes.data_as(C.POINTER(C.c_int64)), int(idx.size), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    def c51_pop_multi_step_enable(self, handle, cfgs):
+        return self.pop_nstep_enable("c51", handle, cfgs)
+
+    def c51_pop_multi_step_window(self, learner_handle, idx):
+        return self.nstep_window("c51", learner_handle, idx)
 
     # -- a Q-network as a policy (stmpc_qactor_*): DQNAgent.get_control, dqn.py:375-380 ------------------------
     def qactor_create(self, net, action_values, mode=0):
@@ -1512,28 +1518,20 @@ class Context:
 
     # -- TD3 learner (stmpc_td3_*): a DDPG learner as base plus critic 2 ------------------------
     def td3_create(self, cfg):
-        h = C.c_void_p()
-        self._chk(self._lib.stmpc_td3_create(self._h, C.byref(cfg), C.byref(h)))
-        return h
+        return self._new_handle(self._lib.stmpc_td3_create, C.byref(cfg))
 
     def td3_destroy(self, handle):
         self._lib.stmpc_td3_destroy(handle)
 
     def td3_base(self, handle):
         """The base as a borrowed ``stmpc_ddpg`` handle for the ``ddpg_*`` methods above (never ``ddpg_destroy`` it)."""
-        h = self._lib.stmpc_td3_base(handle)
-        if not h:
-            self._chk(-1)
-        return C.c_void_p(h)
+        return self._borrowed(self._lib.stmpc_td3_base(handle))
 
     def td3_set_params(self, handle, slot, flat):
-        flat = np.ascontiguousarray(flat, dtype=np.float32)
-        self._chk(self._lib.stmpc_td3_set_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
+        self._slot_in(self._lib.stmpc_td3_set_params, handle, slot, flat)
 
     def td3_get_params(self, handle, slot, count):
-        flat = np.empty(int(count), dtype=np.float32)
-        self._chk(self._lib.stmpc_td3_get_params(handle, int(slot), flat.ctypes.data_as(C.POINTER(C.c_float)), int(flat.size)))
-        return flat
+        return self._slot_out(self._lib.stmpc_td3_get_params, handle, slot, count)
 
     def td3_set_state(self, handle, beta_pow2):
         bp = np.ascontiguousarray(beta_pow2, dtype=np.float32)
@@ -1557,84 +1555,6 @@ class Context:
 
     def td3_stats(self, handle, d_out, stream=0):
         self._chk(self._lib.stmpc_td3_stats_device(handle, d_out, stream))
-
-    # -- DDPG population (stmpc_ddpg_pop_*): P learners, one launch per kernel ------------------------
-    def ddpg_pop_create(self, cfgs):
-        """``cfgs``: a sequence of ``DDPGCfg``; the library checks the member count and that the launch shapes are common."""
-        arr = (DDPGCfg * len(cfgs))(*cfgs)
-        h = C.c_void_p()
-        self._chk(self._lib.stmpc_ddpg_pop_create(self._h, arr, len(cfgs), C.byref(h)))
-        return h
-
-    def ddpg_pop_destroy(self, handle):
-        self._lib.stmpc_ddpg_pop_destroy(handle)
-
-    def ddpg_pop_size(self, handle):
-        return int(self._lib.stmpc_ddpg_pop_size(handle))
-
-    def ddpg_pop_member(self, handle, m):
-        """The m-th member as a borrowed ``stmpc_ddpg`` handle for the ``ddpg_*`` methods above (never ``ddpg_destroy`` it)."""
-        h = self._lib.stmpc_ddpg_pop_member(handle, int(m))
-        if not h:
-            self._chk(STMPC_EINVAL)
-        return C.c_void_p(h)
-
-    def ddpg_pop_act(self, handle, n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug=0, stream=0):
-        self._chk(self._lib.stmpc_ddpg_pop_act_device(handle, int(n_per_member), d_obs, int(obs_stride), d_ticks, int(bool(noise)), d_action, d_debug, stream))
-
-    def ddpg_pop_push(self, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated,
-                      stream=0):
-        self._chk(self._lib.stmpc_ddpg_pop_push_device(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_ticks, d_next_ticks, d_action,
-                                                       d_reward, d_terminated, d_truncated, stream))
-
-    def ddpg_pop_update(self, handle, n_updates, lr_q, lr_pi, stream=0):
-        """``lr_q`` / ``lr_pi``: one learning rate per member (the library checks the lengths)."""
-        lq, lp = np.ascontiguousarray(lr_q, dtype=np.float64).reshape(-1), np.ascontiguousarray(lr_pi, dtype=np.float64).reshape(-1)
-        if lq.size != lp.size:
-            raise ValueError("lr_q has %d entries, lr_pi %d" % (lq.size, lp.size))
-        self._chk(self._lib.stmpc_ddpg_pop_update_device(handle, int(n_updates), _dptr(lq), _dptr(lp), int(lq.size), stream))
-
-    def ddpg_pop_stats(self, handle, d_out, stream=0):
-        self._chk(self._lib.stmpc_ddpg_pop_stats_device(handle, d_out, stream))
-
-    # -- TD3 population (stmpc_pop_td3_*): P TD3 learners, one launch per kernel ------------------------
-    def td3_pop_create(self, cfgs):
-        """``cfgs``: a sequence of ``TD3Cfg``; the library checks the member count and that the launch shapes are common."""
-        arr = (TD3Cfg * len(cfgs))(*cfgs)
-        h = C.c_void_p()
-        self._chk(self._lib.stmpc_pop_td3_create(self._h, arr, len(cfgs), C.byref(h)))
-        return h
-
-    def td3_pop_destroy(self, handle):
-        self._lib.stmpc_pop_td3_destroy(handle)
-
-    def td3_pop_size(self, handle):
-        return int(self._lib.stmpc_pop_td3_size(handle))
-
-    def td3_pop_member(self, handle, m):
-        """The m-th member as a borrowed ``stmpc_td3`` handle for the ``td3_*`` methods above (never ``td3_destroy`` it)."""
-        h = self._lib.stmpc_pop_td3_member(handle, int(m))
-        if not h:
-            self._chk(STMPC_EINVAL)
-        return C.c_void_p(h)
-
-    def td3_pop_act(self, handle, n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug=0, stream=0):
-        self._chk(self._lib.stmpc_pop_td3_act_device(handle, int(n_per_member), d_obs, int(obs_stride), d_ticks, int(bool(noise)), d_action, d_debug, stream))
-
-    def td3_pop_push(self, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated,
-                     stream=0):
-        self._chk(self._lib.stmpc_pop_td3_push_device(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_ticks, d_next_ticks, d_action,
-                                                      d_reward, d_terminated, d_truncated, stream))
-
-    def td3_pop_update(self, handle, n_updates, lr_q, lr_pi, stream=0):
-        """``lr_q`` / ``lr_pi``: one learning rate per member (the library checks the lengths)."""
-        lq, lp = np.ascontiguousarray(lr_q, dtype=np.float64).reshape(-1), np.ascontiguousarray(lr_pi, dtype=np.float64).reshape(-1)
-        if lq.size != lp.size:
-            raise ValueError("lr_q has %d entries, lr_pi %d" % (lq.size, lp.size))
-        self._chk(self._lib.stmpc_pop_td3_update_device(handle, int(n_updates), _dptr(lq), _dptr(lp), int(lq.size), stream))
-
-    def td3_pop_stats(self, handle, d_out, stream=0):
-        self._chk(self._lib.stmpc_pop_td3_stats_device(handle, d_out, stream))
 
     # -- episode flight recorder (stmpc_rec_*): the handle follows this context's world ------------------------
     def rec_create(self, N, Kmax, depth, tick_length, edges):
@@ -1886,13 +1806,45 @@ class Context:
         return out
 
 
-# Context.dqn_<name> / c51_<name> and dqn_pop_<name> / c51_pop_<name>: the discrete learners' shared methods with their kind
+# Context.dqn_<name> / c51_<name>: the discrete learners' shared methods with their kind; Context.<kind>_pop_<name>: the populations' likewise
 for _kind in ("dqn", "c51"):
     for _name in ("create", "destroy", "set_params", "get_params", "set_state", "get_state", "push", "act", "update", "grads", "targets", "gather", "stats",
                   "per_enable", "per_tree_read", "per_last", "padded_read"):
         setattr(Context, "%s_%s" % (_kind, _name), functools.partialmethod(getattr(Context, "_q_" + _name), _kind))
-    for _name in ("create", "destroy", "size", "member", "act", "push", "update", "stats", "per_enable", "replay_read"):
+for _kind in Context._POPS:
+    for _name in ("create", "destroy", "size", "member", "stats", "per_enable"):
+        setattr(Context, "%s_pop_%s" % (_kind, _name), functools.partialmethod(getattr(Context, "_pop_" + _name), _kind))
+for _kind in ("dqn", "c51"):
+    for _name in ("act", "push", "update", "replay_read"):
         setattr(Context, "%s_pop_%s" % (_kind, _name), functools.partialmethod(getattr(Context, "_q_pop_" + _name), _kind))
+
+
+def _continuous_pop_steps(prefix):
+    """``act``, ``push`` and ``update`` of a continuous population whose entries begin with ``prefix``.  They are the three calls of every training
+    step, so each is a plain method that knows its entry, with no ``partialmethod`` hop and no table lookup per call: bound through the table like the
+    other six, the population's loop step at P = 4 fell outside the parent's spread (profiles/learner/python_layer_refactor_bench.json, ``first_binding``)."""
+    act_entry, push_entry, update_entry = prefix + "act_device", prefix + "push_device", prefix + "update_device"
+
+    def act(self, handle, n_per_member, d_obs, obs_stride, d_ticks, noise, d_action, d_debug=0, stream=0):
+        self._chk(getattr(self._lib, act_entry)(handle, int(n_per_member), d_obs, int(obs_stride), d_ticks, int(bool(noise)), d_action, d_debug, stream))
+
+    def push(self, handle, n_per_member, d_obs, d_next_obs, d_final_obs, obs_stride, d_ticks, d_next_ticks, d_action, d_reward, d_terminated, d_truncated,
+             stream=0):
+        self._chk(getattr(self._lib, push_entry)(handle, int(n_per_member), d_obs, d_next_obs, d_final_obs, int(obs_stride), d_ticks, d_next_ticks, d_action,
+                                                 d_reward, d_terminated, d_truncated, stream))
+
+    def update(self, handle, n_updates, lr_q, lr_pi, stream=0):
+        """``lr_q`` / ``lr_pi``: one learning rate per member (the library checks the lengths)."""
+        lq, lp = np.ascontiguousarray(lr_q, dtype=np.float64).reshape(-1), np.ascontiguousarray(lr_pi, dtype=np.float64).reshape(-1)
+        if lq.size != lp.size:
+            raise ValueError("lr_q has %d entries, lr_pi %d" % (lq.size, lp.size))
+        self._chk(getattr(self._lib, update_entry)(handle, int(n_updates), _dptr(lq), _dptr(lp), int(lq.size), stream))
+    return {"act": act, "push": push, "update": update}
+
+
+for _kind in ("ddpg", "td3"):
+    for _name, _method in _continuous_pop_steps(Context._POPS[_kind][0]).items():
+        setattr(Context, "%s_pop_%s" % (_kind, _name), _method)
 
 _default_ctx = None
 

@@ -509,15 +509,62 @@ def nstep_batch_host(rows, idx, cursor, fill, N, n, gamma, n_obs, dqn=False):
 
 
 # ---- the learner -------------------------------------------------------------------------------------------------------------------------------
+# the columns of ``stats_device``: a DDPG learner's, a TD3 learner's (``stats_td3``) and a discrete learner's; a population's table has one such row per member
+_DDPG_STATS = ("critic_loss", "mean_q", "fill", "updates")
+_TD3_STATS = ("critic_loss", "critic2_loss", "mean_q", "mean_q2", "fill", "updates")
+_DQN_STATS = ("loss", "mean_q", "fill", "updates")
+
+
+def _stats_dict(keys, s):
+    """``stats_device`` on the host as a dict: scalars from a lone learner's row [len(keys)], arrays of length P from a population's table
+    [P][len(keys)]; ``fill`` and ``updates`` are integers."""
+    out = {}
+    for i, k in enumerate(keys):
+        col, integer = s[..., i], k in ("fill", "updates")
+        out[k] = (int(col) if integer else float(col)) if s.ndim == 1 else (col.astype(np.int64) if integer else col.copy())
+    return out
+
+
+def _check_push(torch, obs, reward, next_obs, terminated, truncated, final_obs):
+    """What ``push`` asks of an env step's tensors, whatever the learner."""
+    assert obs.dtype == next_obs.dtype == torch.float32 and reward.dtype == torch.float64
+    assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
+    assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+
+
+def _check_ddpg_act(torch, obs, ticks):
+    assert obs.dtype == torch.float32 and ticks.dtype == torch.int32 and obs.stride(1) == 1
+
+
+def _check_ddpg_push(torch, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs):
+    assert action.dtype == torch.float64 and ticks.dtype == torch.int32
+    _check_push(torch, obs, reward, next_obs, terminated, truncated, final_obs)
+
+
+def _check_q_act(torch, obs, debug_q, n_actions):
+    assert obs.dtype == torch.float32 and obs.stride(1) == 1
+    assert debug_q is None or (debug_q.dtype == torch.float32 and debug_q.is_contiguous() and debug_q.shape == (obs.shape[0], n_actions))
+
+
+def _check_q_push(torch, obs, action, reward, next_obs, terminated, truncated, final_obs):
+    assert action.dtype == torch.int32 and action.is_contiguous()
+    _check_push(torch, obs, reward, next_obs, terminated, truncated, final_obs)
+
+
 class _Learner:
     """What ``DDPGLearner`` and ``DQNLearner`` share word for word: the handle's lifetime, the stream, the output tensor kept per n, the debug reads
     of the replay and the statistics, and ``state_dict`` / ``load_state_dict``.  A subclass names its binding's entries (``ctx.<_api>_<name>``, and
-    ``ctx.<_per_api>_<name>`` for prioritised replay), its ``_slots`` and ``_flatten``, and reads one slot in ``_slot``."""
+    ``ctx.<_per_api>_<name>`` for prioritised replay), its ``_slots`` and ``_flatten``, reads one slot in ``_slot`` and makes the handle it owns in
+    ``_create`` (a population's member borrows that one instead: ``_Borrowed``)."""
 
     _owns_handle = True                                             # (False: a population's member, whose population sets up what it shares)
 
     def _call(self, name):
         return getattr(self.ctx, "%s_%s" % (self._api, name))
+
+    def _make_handle(self):
+        """What becomes ``self.handle``: the handle the learner's own entries take."""
+        return self._create()
 
     def _enable_nstep(self, env, rows_per_push):
         """``cfg.n_step`` onto the new handle (the ring is empty); ``self.rows_per_push``: the N every push must have when n_step > 1."""
@@ -647,7 +694,7 @@ class DDPGLearner(_Learner):
         self._stats = z(4)
         self._actions = {}
 
-    def _make_handle(self):
+    def _create(self):
         return self.ctx.ddpg_create(self.cfg.to_c(self.seed))
 
     def _initial_params(self, a_net, q_net, rng):
@@ -665,7 +712,7 @@ class DDPGLearner(_Learner):
         with the same n.  ``debug``: uint32 [n][4] device tensor for the draws (debugging)."""
         n = obs.shape[0]
         out = self._out(n, self.torch.float64)
-        assert obs.dtype == self.torch.float32 and ticks.dtype == self.torch.int32 and obs.stride(1) == 1
+        _check_ddpg_act(self.torch, obs, ticks)
         self.ctx.ddpg_act(self.handle, n, obs.data_ptr(), obs.stride(0), ticks.data_ptr(), noise, out.data_ptr(), debug.data_ptr() if debug is not None else 0,
                           self._stream())
         return out
@@ -673,10 +720,7 @@ class DDPGLearner(_Learner):
     def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
         """One env step into the replay ring: ``obs`` / ``ticks`` as given to ``act``, ``action`` fp64 [n], and what ``env.step`` returned
         (``final_obs = info["final_observation"]``).  Where an episode ended, s' is the final observation at ticks + 1."""
-        torch = self.torch
-        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == reward.dtype == torch.float64 and ticks.dtype == torch.int32
-        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
-        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+        _check_ddpg_push(self.torch, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs)
         self.ctx.ddpg_push(self.handle, obs.shape[0], obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0, obs.stride(0),
                            ticks.data_ptr(), next_ticks.data_ptr() if next_ticks is not None else 0, action.data_ptr(), reward.data_ptr(),
                            terminated.data_ptr(), truncated.data_ptr(), self._stream())
@@ -696,8 +740,7 @@ class DDPGLearner(_Learner):
 
     def stats(self):
         """``stats_device`` as a dict; synchronises."""
-        s = self.stats_device().cpu().numpy()
-        return {"critic_loss": float(s[0]), "mean_q": float(s[1]), "fill": int(s[2]), "updates": int(s[3])}
+        return _stats_dict(_DDPG_STATS, self.stats_device().cpu().numpy())
 
     def export_actor(self, path):
         """Write the online actor as the ``.npz`` ``actor.load_weights`` reads (w0 ... b2 float32, tanh_scale, tanh_mean)."""
@@ -724,8 +767,11 @@ class TD3Learner(DDPGLearner):
         super().__init__(env_or_dims, cfg, seed=seed, init=init, ctx=ctx, rows_per_push=rows_per_push)
         self._stats6 = self.torch.zeros(6, dtype=self.torch.float64, device=self.device)
 
+    def _create(self):
+        return self.ctx.td3_create(self.cfg.to_c_td3(self.seed))
+
     def _make_handle(self):
-        self.td3 = self.ctx.td3_create(self.cfg.to_c_td3(self.seed))
+        self.td3 = self._create()
         return self.ctx.td3_base(self.td3)
 
     def _initial_params(self, a_net, q_net, rng):
@@ -765,8 +811,7 @@ class TD3Learner(DDPGLearner):
     def stats_td3(self):
         """Both critics' numbers as a dict; synchronises.  (``stats`` stays critic 1's four.)"""
         self.ctx.td3_stats(self.td3, self._stats6.data_ptr(), self._stream())
-        s = self._stats6.cpu().numpy()
-        return {"critic_loss": float(s[0]), "critic2_loss": float(s[1]), "mean_q": float(s[2]), "mean_q2": float(s[3]), "fill": int(s[4]), "updates": int(s[5])}
+        return _stats_dict(_TD3_STATS, self._stats6.cpu().numpy())
 
     def state_dict(self):
         """``DDPGLearner.state_dict`` plus critic 2's four slots; ``beta_pow`` float32 [6]: actor, critic 1, critic 2."""
@@ -796,9 +841,9 @@ def per_member(value, P, default=None):
 
 
 class _Borrowed:
-    """In front of a lone learner's class, one member of a population as that learner: the handle is borrowed from the population (its binding's
-    ``member`` entry), which outlives it; everything else -- the seeded initialisation, and what a discrete learner takes from the env, included -- is
-    the lone learner's code."""
+    """In front of a lone learner's class, one member of a population as that learner: where the lone learner creates the handle it owns, the
+    member's is borrowed from the population (its binding's ``member`` entry), which outlives it; everything else -- the seeded initialisation,
+    what a TD3 learner takes from its handle and a discrete learner from the env, included -- is the lone learner's code."""
 
     _owns_handle = False
 
@@ -806,11 +851,11 @@ class _Borrowed:
         self._population, self._borrowed = population, population._call("member")(population.handle, m)
         super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
 
-    def _make_handle(self):
+    def _create(self):
         return self._borrowed
 
     def __del__(self):
-        self.handle = None                                          # the population destroys its members
+        self.handle = None                                          # the population destroys its members (no lone learner's ``__del__`` runs)
 
 
 class _PopulationMember(_Borrowed, DDPGLearner):
@@ -849,7 +894,7 @@ class DDPGPopulation:
     ``n_step`` is a member's cfg's like any other constant, so "which n" is a sweep: member m forms ``cfgs[m].n_step``-step returns from pushes
     of ``n_per_member`` rows and stays bit-identical to the lone learner with that cfg; ``member(m).nstep_window(idx)`` reads its windows."""
 
-    _api, _nstat = "ddpg_pop", 4                                    # the binding's entries (ctx.<_api>_create, ...) and the width of a stats row
+    _api, _stat_keys = "ddpg_pop", _DDPG_STATS                      # the binding's entries (ctx.<_api>_create, ...) and the columns of a stats row
     _nstep_kind = "ddpg"                                            # which stmpc_pop_nstep_enable_* entry sets the members' n_step
     _cfg_type, _action_dtype = DDPGConfig, "float64"                # what a (cfg, P) pair holds, and the dtype of the tensor ``act`` returns
 
@@ -920,7 +965,7 @@ class DDPGPopulation:
             self._call("per_enable")(self.handle, [g.to_c() if g is not None else None for g in self.per])
         self._members = [self._make_member(m, env, inits[m]) for m in range(P)]
         self._default_rates()
-        self._stats = torch.zeros(P, self._nstat, dtype=torch.float64, device=self.device)
+        self._stats = torch.zeros(P, len(self._stat_keys), dtype=torch.float64, device=self.device)
         self._actions = torch.empty(env.n, dtype=getattr(torch, self._action_dtype), device=self.device)
 
     def __del__(self):
@@ -947,18 +992,15 @@ class DDPGPopulation:
     def act(self, obs, ticks, noise=True, debug=None):
         """``DDPGLearner.act`` for all members: row e is acted on by member e // n_per_member.  The returned tensor is reused by the next call."""
         self._rows(obs)
-        assert obs.dtype == self.torch.float32 and ticks.dtype == self.torch.int32 and obs.stride(1) == 1
+        _check_ddpg_act(self.torch, obs, ticks)
         self._call("act")(self.handle, self.n_per_member, obs.data_ptr(), obs.stride(0), ticks.data_ptr(), noise, self._actions.data_ptr(),
                           debug.data_ptr() if debug is not None else 0, self._stream())
         return self._actions
 
     def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
         """``DDPGLearner.push`` for all members: each member's slice of the step goes into its own ring."""
-        torch = self.torch
         self._rows(obs)
-        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == reward.dtype == torch.float64 and ticks.dtype == torch.int32
-        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
-        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+        _check_ddpg_push(self.torch, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs)
         self._call("push")(self.handle, self.n_per_member, obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0,
                            obs.stride(0), ticks.data_ptr(), next_ticks.data_ptr() if next_ticks is not None else 0, action.data_ptr(), reward.data_ptr(),
                            terminated.data_ptr(), truncated.data_ptr(), self._stream())
@@ -972,32 +1014,18 @@ class DDPGPopulation:
         self._call("update")(self.handle, n, self._lr(lr_q, self._lr_q), self._lr(lr_pi, self._lr_pi), self._stream())
 
     def stats_device(self):
-        """fp64 [P][4] device tensor: per member, critic loss and mean Q of the last minibatch, fill, updates done (asynchronous)."""
+        """fp64 [P][4] device tensor ([P][6] of a ``TD3Population``): per member, the lone learner's row -- the loss(es) and mean Q(s, a) of the last
+        minibatch, fill, updates done (asynchronous)."""
         self._call("stats")(self.handle, self._stats.data_ptr(), self._stream())
         return self._stats
 
     def stats(self):
-        """The same as a dict of arrays of length P; synchronises."""
-        s = self.stats_device().cpu().numpy()
-        return {"critic_loss": s[:, 0].copy(), "mean_q": s[:, 1].copy(), "fill": s[:, 2].astype(np.int64), "updates": s[:, 3].astype(np.int64)}
+        """The same as a dict of arrays of length P with the lone learner's keys (``TD3Learner.stats_td3``'s of a ``TD3Population``); synchronises."""
+        return _stats_dict(self._stat_keys, self.stats_device().cpu().numpy())
 
 
-class _TD3PopulationMember(TD3Learner):
-    """One member of a ``TD3Population`` as a ``TD3Learner``: the TD3 handle is borrowed from the population (``stmpc_pop_td3_member``), which outlives
-    it, and so is its base; everything else -- the seeded initialisation, critic 2's draw included -- is the lone learner's code."""
-
-    _owns_handle = False
-
-    def __init__(self, population, m, env, cfg, seed, init):
-        self._population, self._borrowed = population, population.ctx.td3_pop_member(population.handle, m)
-        super().__init__(env, cfg, seed=seed, init=init, ctx=population.ctx)
-
-    def _make_handle(self):
-        self.td3 = self._borrowed
-        return self.ctx.td3_base(self.td3)
-
-    def __del__(self):
-        self.handle = self.td3 = None                               # the population destroys its members
+class _TD3PopulationMember(_Borrowed, TD3Learner):
+    """One member of a ``TD3Population`` as a ``TD3Learner`` (``stmpc_pop_td3_member``): the TD3 handle is borrowed, and so is its base."""
 
 
 def _is_net_triple(x):
@@ -1019,7 +1047,7 @@ class TD3Population(DDPGPopulation):
     ``actor.ActorPopulation`` take it as they take a ``DDPGPopulation``.  ``per``: as ``DDPGPopulation``'s; a prioritised member's priorities follow
     the critic with the larger error, as ``TD3Learner``'s do."""
 
-    _api, _nstat = "td3_pop", 6
+    _api, _stat_keys = "td3_pop", _TD3_STATS
     _nstep_kind = "td3"
 
     def __init__(self, env, cfgs, seeds=None, init=None, ctx=None, per=None):
@@ -1039,16 +1067,6 @@ class TD3Population(DDPGPopulation):
 
     def _make_member(self, m, env, init):
         return _TD3PopulationMember(self, m, env, self.cfgs[m], self.seeds[m], init)
-
-    def stats_device(self):
-        """fp64 [P][6] device tensor: per member, both critics' losses and mean Qs of the last minibatch, fill, updates done (asynchronous)."""
-        return super().stats_device()
-
-    def stats(self):
-        """The same as a dict of arrays of length P with the keys of ``TD3Learner.stats_td3``; synchronises."""
-        s = self.stats_device().cpu().numpy()
-        return {"critic_loss": s[:, 0].copy(), "critic2_loss": s[:, 1].copy(), "mean_q": s[:, 2].copy(), "mean_q2": s[:, 3].copy(),
-                "fill": s[:, 4].astype(np.int64), "updates": s[:, 5].astype(np.int64)}
 
 
 # ---- DQN: the discrete agent (csrc/stmpc_dqn_kernels.hpp, stmpc_dqn_*) ---------------------------------------------------------------------------
@@ -1257,7 +1275,7 @@ class _QLearner(_Learner):
         self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self._actions = {}
 
-    def _make_handle(self):
+    def _create(self):
         return self._call("create")(self.cfg.to_c(self.seed))
 
     def _slot(self, i):
@@ -1272,18 +1290,14 @@ class _QLearner(_Learner):
         values)."""
         n = obs.shape[0]
         out = self._out(n, self.torch.int32)
-        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
-        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (n, self.cfg.n_actions))
+        _check_q_act(self.torch, obs, debug_q, self.cfg.n_actions)
         self._call("act")(self.handle, n, obs.data_ptr(), obs.stride(0), eps, out.data_ptr(), debug_q.data_ptr() if debug_q is not None else 0, self._stream())
         return out
 
     def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
         """One env step into the replay ring: ``obs`` as given to ``act``, ``action`` int32 [n], and what ``env.step`` returned
         (``final_obs = info["final_observation"]``: s' where an episode ended).  ``ticks`` / ``next_ticks`` are not read."""
-        torch = self.torch
-        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == torch.int32 and reward.dtype == torch.float64 and action.is_contiguous()
-        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
-        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+        _check_q_push(self.torch, obs, action, reward, next_obs, terminated, truncated, final_obs)
         self._call("push")(self.handle, obs.shape[0], obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0, obs.stride(0),
                            action.data_ptr(), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self._stream())
 
@@ -1306,8 +1320,7 @@ class _QLearner(_Learner):
 
     def stats(self):
         """``stats_device`` as a dict; synchronises."""
-        s = self.stats_device().cpu().numpy()
-        return {"loss": float(s[0]), "mean_q": float(s[1]), "fill": int(s[2]), "updates": int(s[3])}
+        return _stats_dict(_DQN_STATS, self.stats_device().cpu().numpy())
 
 
 class DQNLearner(_QLearner):
@@ -1358,7 +1371,7 @@ class DQNPopulation(DDPGPopulation):
     ``train_dqn`` takes a population.  ``evaluate_dqn_members(pop, n_per_member)`` evaluates all members' Q-networks in one launch per tick
     (``actor.QActorPopulation``)."""
 
-    _api, _nstat = "dqn_pop", 4
+    _api, _stat_keys = "dqn_pop", _DQN_STATS
     _nstep_kind = "dqn"
     _cfg_type, _action_dtype = DQNConfig, "int32"
 
@@ -1385,19 +1398,15 @@ class DQNPopulation(DDPGPopulation):
         """``DQNLearner.act`` for all members: row e is acted on by member e // n_per_member; int32 [env.n], reused by the next call.  ``eps``: a
         scalar or one value per member.  ``debug_q``: float32 [env.n][n_actions]."""
         self._rows(obs)
-        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
-        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (self.env_n, self.cfgs[0].n_actions))
+        _check_q_act(self.torch, obs, debug_q, self.cfgs[0].n_actions)
         self._call("act")(self.handle, self.n_per_member, obs.data_ptr(), obs.stride(0), per_member(eps, self.P), self._actions.data_ptr(),
                           debug_q.data_ptr() if debug_q is not None else 0, self._stream())
         return self._actions
 
     def push(self, obs, ticks, action, reward, next_obs, terminated, truncated, final_obs=None, next_ticks=None):
         """``DQNLearner.push`` for all members: each member's slice of the step goes into its own ring."""
-        torch = self.torch
         self._rows(obs)
-        assert obs.dtype == next_obs.dtype == torch.float32 and action.dtype == torch.int32 and reward.dtype == torch.float64 and action.is_contiguous()
-        assert terminated.dtype == truncated.dtype == torch.bool and obs.stride(1) == 1 and obs.stride(0) == next_obs.stride(0)
-        assert final_obs is None or (final_obs.dtype == torch.float32 and final_obs.stride(0) == obs.stride(0))
+        _check_q_push(self.torch, obs, action, reward, next_obs, terminated, truncated, final_obs)
         self._call("push")(self.handle, self.n_per_member, obs.data_ptr(), next_obs.data_ptr(), final_obs.data_ptr() if final_obs is not None else 0,
                            obs.stride(0), action.data_ptr(), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self._stream())
 
@@ -1405,15 +1414,6 @@ class DQNPopulation(DDPGPopulation):
         """``n`` updates of every member, three launches each (five with prioritised members); a member whose replay_start gate is still shut skips
         its own.  ``lr``: a scalar or one value per member (default: each member's cfg's)."""
         self._call("update")(self.handle, n, self._lr(lr, self._lr_default), self._stream())
-
-    def stats_device(self):
-        """fp64 [P][4] device tensor: per member, the loss and mean Q(s, a) of the last minibatch, fill, updates done (asynchronous)."""
-        return super().stats_device()
-
-    def stats(self):
-        """The same as a dict of arrays of length P with the keys of ``DQNLearner.stats``; synchronises."""
-        s = self.stats_device().cpu().numpy()
-        return {"loss": s[:, 0].copy(), "mean_q": s[:, 1].copy(), "fill": s[:, 2].astype(np.int64), "updates": s[:, 3].astype(np.int64)}
 
 
 # ---- C51: the categorical DQN agent (csrc/stmpc_c51_kernels.hpp, stmpc_c51_*) ---------------------------------------------------------------------
@@ -1710,9 +1710,9 @@ class C51Learner(_QLearner):
     def noisy(self):
         return getattr(self.cfg, "noisy", None) is not None
 
-    def _make_handle(self):
+    def _create(self):
         """The new handle, with the noisy output layer enabled on it while it is fresh (a population's member never gets here: ``_Borrowed``)."""
-        h = super()._make_handle()
+        h = super()._create()
         if self.noisy:
             self.ctx.noisy_c51_enable(h, self.cfg.noisy.sigma0)
         return h
@@ -1737,8 +1737,7 @@ class C51Learner(_QLearner):
             raise ValueError("noisy=True needs a learner with the noisy output layer (C51Config(noisy=NoisyConfig())); this one is plain")
         n = obs.shape[0]
         out = self._out(n, self.torch.int32)
-        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
-        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (n, self.cfg.n_actions))
+        _check_q_act(self.torch, obs, debug_q, self.cfg.n_actions)
         self.ctx.noisy_c51_act(self.handle, n, obs.data_ptr(), obs.stride(0), eps, out.data_ptr(), debug_q.data_ptr() if debug_q is not None else 0, self._stream())
         return out
 
@@ -1845,7 +1844,7 @@ class C51Population(DQNPopulation):
     ``evaluate_dqn_members``, ``actor.QActorPopulation`` and ``actor.population_of`` refuse a ``C51Population`` as they refuse C51 members: its
     policies are evaluated together by ``evaluate_c51_members`` and ``actor.C51ActorPopulation``."""
 
-    _api, _nstat = "c51_pop", 4
+    _api = "c51_pop"
     _nstep_kind = "c51"                                             # (``ctx.pop_nstep_enable`` routes it to stmpc_pop_c51_multi_step_enable)
     _cfg_type, _action_dtype = C51Config, "int32"
 
@@ -1908,8 +1907,7 @@ class C51Population(DQNPopulation):
         if not self.noisy:
             raise ValueError("noisy=True needs a population with the noisy output layer (C51Population(..., noisy=NoisyConfig())); this one is plain")
         self._rows(obs)
-        assert obs.dtype == self.torch.float32 and obs.stride(1) == 1
-        assert debug_q is None or (debug_q.dtype == self.torch.float32 and debug_q.is_contiguous() and debug_q.shape == (self.env_n, self.cfgs[0].n_actions))
+        _check_q_act(self.torch, obs, debug_q, self.cfgs[0].n_actions)
         self.ctx.c51_pop_noisy_act(self.handle, self.n_per_member, obs.data_ptr(), obs.stride(0), per_member(eps, self.P), self._actions.data_ptr(),
                                    debug_q.data_ptr() if debug_q is not None else 0, self._stream())
         return self._actions
@@ -1937,9 +1935,9 @@ class C51Population(DQNPopulation):
 
 
 class _TakeoverShare:
-    """What ``train_ddpg`` and ``train_dqn`` count on a shielded env: the ticks on which the shield overruled the action and the live ticks, summed on
-    the device at every step (no host synchronisation) and read at the drains.  Without autoreset a finished environment idles: not a live tick.
-    ``P`` > 0: per member too, the owner of row e being e // ``n_per_member``."""
+    """What ``train_ddpg`` and ``train_dqn`` (their loop, ``_train``) count on a shielded env: the ticks on which the shield overruled the action and
+    the live ticks, summed on the device at every step (no host synchronisation) and read at the drains.  Without autoreset a finished environment
+    idles: not a live tick.  ``P`` > 0: per member too, the owner of row e being e // ``n_per_member``."""
 
     def __init__(self, env, P=0, n_per_member=0):
         torch = env.torch
@@ -1976,33 +1974,25 @@ class _TakeoverShare:
         return [t / l if l else 0.0 for t, l in zip(*self.member_ticks)]
 
 
-def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_schedule=None, lr_schedule=None):
-    """The loop of the reference's ``DQNAgent._train`` on the device: act (epsilon-greedy) -> env.step -> push -> ``updates_per_step`` updates,
-    until ``frames`` transitions were collected (rounded up to whole steps of env.n).  ``eps_schedule(step, steps) -> eps`` (None:
-    ``dqn_epsilon(step)``, the reference's decay with the step for the episode number); ``lr_schedule(step, steps) -> lr``.  Synchronises only
-    every ``drain_every`` steps.  The result has ``train_ddpg``'s keys.
-    ``learner`` may be a ``DQNPopulation`` (both schedules may then return per-member arrays); the result then also carries ``member_returns``:
-    the drained returns of each member's environments, a list of P arrays (owner = env index // n_per_member), as ``train_ddpg``'s does.
-    A learner with the noisy output layer (``C51Config(noisy=...)``) explores through its noise: with ``eps_schedule=None`` its epsilon is 0 (an
-    explicit schedule is honoured).
-    On a shielded env (a discrete ``MergeVecEnv(shield="first_step")``, ``vec_env.GroupedShieldVecEnv`` or ``vec_env.QCombinedShieldVecEnv``) the
-    result's ``takeover_share`` is the share of the live ticks on which the shield overruled the action (summed on the device, read at the drains,
-    as ``train_ddpg`` does it; 0.0 on an env without a ``shield``), and with a ``DQNPopulation`` ``member_takeover_share`` is that share per member,
-    a list of P floats (owner = env index // n_per_member)."""
-    pop = isinstance(learner, DQNPopulation)
+def _train(env, learner, frames, updates_per_step, drain_every, act, pushed_action, update):
+    """The loop of ``train_ddpg`` and ``train_dqn``: act -> env.step -> push -> update, ``-(-frames // env.n)`` times, with a drain of the finished
+    episodes' statistics (the only synchronisation) every ``drain_every`` steps and after the last, a shielded env's takeovers counted by
+    ``_TakeoverShare``, and the result dict -- with ``member_returns`` (and behind a shield ``member_takeover_share``) when ``learner`` is a
+    population.  The callers supply what differs: ``act(i, steps, obs) -> (ticks, action)``, ``pushed_action(action, info)`` and ``update(i, steps)``,
+    this step's ``updates_per_step`` updates under the schedule's value."""
+    pop = isinstance(learner, DDPGPopulation)
     steps = -(-int(frames) // env.n)
     obs = env.reset()
     returns, envs = [], []
     shield = _TakeoverShare(env, learner.P if pop else 0, learner.n_per_member if pop else 0) if getattr(env, "shield", None) is not None else None
-    default_eps = (lambda i: 0.0) if getattr(learner, "noisy", False) else dqn_epsilon
     for i in range(steps):
-        action = learner.act(obs, None, eps=eps_schedule(i, steps) if eps_schedule is not None else default_eps(i))
+        ticks, action = act(i, steps, obs)
         next_obs, reward, term, trunc, info = env.step(action)
-        learner.push(obs, None, action, reward, next_obs, term, trunc, final_obs=info["final_observation"])
+        learner.push(obs, ticks, pushed_action(action, info), reward, next_obs, term, trunc, final_obs=info["final_observation"])
         if shield is not None:
             shield.step(info, term, trunc)
         if updates_per_step:
-            learner.update(updates_per_step, lr_schedule(i, steps) if lr_schedule is not None else None)
+            update(i, steps)
         obs = next_obs
         if (i + 1) % drain_every == 0 or i + 1 == steps:
             drained = env.drain_episode_stats()
@@ -2021,6 +2011,29 @@ def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_sche
     return out
 
 
+def train_dqn(env, learner, frames, updates_per_step=1, drain_every=64, eps_schedule=None, lr_schedule=None):
+    """The loop of the reference's ``DQNAgent._train`` on the device: act (epsilon-greedy) -> env.step -> push -> ``updates_per_step`` updates,
+    until ``frames`` transitions were collected (rounded up to whole steps of env.n).  ``eps_schedule(step, steps) -> eps`` (None:
+    ``dqn_epsilon(step)``, the reference's decay with the step for the episode number); ``lr_schedule(step, steps) -> lr``.  Synchronises only
+    every ``drain_every`` steps.  The result has ``train_ddpg``'s keys.
+    ``learner`` may be a ``DQNPopulation`` (both schedules may then return per-member arrays); the result then also carries ``member_returns``:
+    the drained returns of each member's environments, a list of P arrays (owner = env index // n_per_member), as ``train_ddpg``'s does.
+    A learner with the noisy output layer (``C51Config(noisy=...)``) explores through its noise: with ``eps_schedule=None`` its epsilon is 0 (an
+    explicit schedule is honoured).
+    On a shielded env (a discrete ``MergeVecEnv(shield="first_step")``, ``vec_env.GroupedShieldVecEnv`` or ``vec_env.QCombinedShieldVecEnv``) the
+    result's ``takeover_share`` is the share of the live ticks on which the shield overruled the action (summed on the device, read at the drains,
+    by ``_train``'s ``_TakeoverShare`` as for ``train_ddpg``; 0.0 on an env without a ``shield``), and with a ``DQNPopulation`` ``member_takeover_share`` is that share per member,
+    a list of P floats (owner = env index // n_per_member)."""
+    default_eps = (lambda i: 0.0) if getattr(learner, "noisy", False) else dqn_epsilon
+
+    def act(i, steps, obs):
+        return None, learner.act(obs, None, eps=eps_schedule(i, steps) if eps_schedule is not None else default_eps(i))
+
+    def update(i, steps):
+        learner.update(updates_per_step, lr_schedule(i, steps) if lr_schedule is not None else None)
+    return _train(env, learner, frames, updates_per_step, drain_every, act, lambda action, info: action, update)
+
+
 def write_actor(path, net, tanh_scale, tanh_mean):
     """The file format of ``actor.load_weights`` for a net {w0, b0, w1, b1, w2, b2}."""
     with open(path, "wb") as fh:
@@ -2035,40 +2048,43 @@ def train_ddpg(env, learner, frames, updates_per_step=1, drain_every=64, lr_sche
     ``learner`` may be a ``DDPGPopulation`` (the schedule may then return per-member arrays); the result then also carries
     ``member_returns``: the drained returns of each member's environments, a list of P arrays.
     On a shielded env (``MergeVecEnv(shield="first_step")``, ``vec_env.CombinedShieldVecEnv``) the result's ``takeover_share`` is the share of the live ticks on which the shield
-    overruled the action (summed on the device, read at the drains; 0.0 on an unshielded env), and ``executed_actions=True`` (continuous env only,
+    overruled the action (summed on the device, read at the drains, by ``_train``'s ``_TakeoverShare``; 0.0 on an unshielded env) -- with a population ``member_takeover_share`` is that
+    share per member, as ``train_dqn``'s --, and ``executed_actions=True`` (continuous env only,
     else ValueError) pushes ``info["executed_action"]`` -- what the shield let through or put in the action's place -- instead of the action."""
     shielded = getattr(env, "shield", None) is not None
     if executed_actions and not (shielded and env.continuous):
         raise ValueError("executed_actions=True needs a shielded continuous env (MergeVecEnv(env_id='sumo-jerk-continuous-v0', shield='first_step') or a "
                          "CombinedShieldVecEnv)")
-    steps = -(-int(frames) // env.n)
-    obs = env.reset()
-    returns, envs = [], []
-    shield = _TakeoverShare(env) if shielded else None
-    for i in range(steps):
+
+    def act(i, steps, obs):
         ticks = env.episode_ticks.clone()
-        action = learner.act(obs, ticks, noise=True)
-        next_obs, reward, term, trunc, info = env.step(action)
-        learner.push(obs, ticks, info["executed_action"] if executed_actions else action, reward, next_obs, term, trunc, final_obs=info["final_observation"])
-        if shielded:
-            shield.step(info, term, trunc)
-        if updates_per_step:
-            lr_q, lr_pi = lr_schedule(i, steps) if lr_schedule is not None else (None, None)
-            learner.update(updates_per_step, lr_q, lr_pi)
-        obs = next_obs
-        if (i + 1) % drain_every == 0 or i + 1 == steps:
-            drained = env.drain_episode_stats()
-            returns.append(drained["episode_return"])
-            envs.append(drained["env"])
-            if shielded:
-                shield.read()
-    returns = np.concatenate(returns) if returns else np.zeros(0)
-    out = {"steps": steps, "frames": steps * env.n, "episodes": int(returns.size), "mean_return": float(returns.mean()) if returns.size else float("nan"),
-           "returns": returns, "takeover_share": shield.share if shielded else 0.0}
-    if isinstance(learner, DDPGPopulation):
-        owner = (np.concatenate(envs) if envs else np.zeros(0, dtype=np.int64)) // learner.n_per_member
-        out["member_returns"] = [returns[owner == m] for m in range(learner.P)]
-    return out
+        return ticks, learner.act(obs, ticks, noise=True)
+
+    def update(i, steps):
+        lr_q, lr_pi = lr_schedule(i, steps) if lr_schedule is not None else (None, None)
+        learner.update(updates_per_step, lr_q, lr_pi)
+    pushed_action = (lambda action, info: info["executed_action"]) if executed_actions else (lambda action, info: action)
+    return _train(env, learner, frames, updates_per_step, drain_every, act, pushed_action, update)
+
+
+def _check_members_controller(controller):
+    if controller not in ("combined", "first_step"):
+        raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
+
+
+def _evaluate_population(members, P, population_cls, n_per_member, seed, kmax, max_episode_length, record, ctx, traffic, controller):
+    """What ``evaluate_members``, ``evaluate_dqn_members`` and ``evaluate_c51_members`` do once they have refused what is not theirs: one run of
+    ``P * n_per_member`` episodes whose policy is ``population_cls(members, ...)``, on a new context unless one is given, summarised per member."""
+    from . import episodes
+    if traffic is not None and len(traffic) != P:
+        raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), P))
+    ctx = ctx if ctx is not None else _capi.Context(-1)
+    pop = population_cls(members, n_per_member, ctx, Settings)
+    stats = episodes.run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
+                                  traffic=traffic)
+    rep = stats.get("report")
+    return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),
+            "reports": rep.by_member(pop.P, traffic) if rep is not None else None}
 
 
 def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):
@@ -2081,22 +2097,12 @@ def evaluate_members(source, n_per_member, seed=0, kmax=16, max_episode_length=1
     The members' episodes are different draws of one world (identically distributed, not common random numbers).
     ``traffic``: None, or one traffic group per member (as ``episodes.sim_cfgs`` takes them): member m is evaluated on traffic m, and its report
     row carries that traffic's TRAFFIC_DESCRIPTION.  ``controller``: "combined", or "first_step" for the one-step shield of ``first_step.py``."""
-    from . import episodes
-    if controller not in ("combined", "first_step"):
-        raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
+    _check_members_controller(controller)
     if isinstance(source, DQNPopulation):
         raise ValueError("a DQNPopulation's members are Q-networks: evaluate them all in one launch with evaluate_dqn_members(pop, n_per_member, ...), or "
                          "one at a time with evaluate_dqn(pop.member(m), ...); evaluate_members builds a population of DDPG actors")
     members = source if isinstance(source, (DDPGPopulation, list, tuple)) else [source]
-    if traffic is not None and len(traffic) != len(members):
-        raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), len(members)))
-    ctx = ctx if ctx is not None else _capi.Context(-1)
-    pop = _actor.ActorPopulation(members, n_per_member, ctx, Settings)
-    stats = episodes.run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
-                                  traffic=traffic)
-    rep = stats.get("report")
-    return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),
-            "reports": rep.by_member(pop.P, traffic) if rep is not None else None}
+    return _evaluate_population(members, len(members), _actor.ActorPopulation, n_per_member, seed, kmax, max_episode_length, record, ctx, traffic, controller)
 
 
 def evaluate_dqn_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):
@@ -2106,24 +2112,14 @@ def evaluate_dqn_members(source, n_per_member, seed=0, kmax=16, max_episode_leng
     ``DQNLearner`` (zero-copy views of the online networks as they are on the device), or a list as ``QActorPopulation`` takes (``export_q`` files,
     learners, ``DQNActor``s).  ``ctx``, ``traffic``, ``controller`` and the returned dict -- ``stats`` with ``member``, ``by_member``, ``reports``
     -- are ``evaluate_members``'."""
-    from . import episodes
-    if controller not in ("combined", "first_step"):
-        raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
+    _check_members_controller(controller)
     members = source if isinstance(source, (DQNPopulation, list, tuple)) else [source]
     if isinstance(members, C51Population):
         _actor.refuse_c51_members([members.member(m) for m in range(members.P)], "evaluate_dqn_members")
     if not isinstance(members, DQNPopulation):
         _actor.refuse_c51_members(members, "evaluate_dqn_members")      # (before a context exists: a C51 policy is evaluated alone, by evaluate_dqn)
     P = members.P if isinstance(members, DQNPopulation) else len(members)
-    if traffic is not None and len(traffic) != P:
-        raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), P))
-    ctx = ctx if ctx is not None else _capi.Context(-1)
-    pop = _actor.QActorPopulation(members, n_per_member, ctx, Settings)
-    stats = episodes.run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
-                                  traffic=traffic)
-    rep = stats.get("report")
-    return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),
-            "reports": rep.by_member(pop.P, traffic) if rep is not None else None}
+    return _evaluate_population(members, P, _actor.QActorPopulation, n_per_member, seed, kmax, max_episode_length, record, ctx, traffic, controller)
 
 
 def evaluate_c51_members(source, n_per_member, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):
@@ -2134,9 +2130,7 @@ def evaluate_c51_members(source, n_per_member, seed=0, kmax=16, max_episode_leng
     as ``C51ActorPopulation`` takes (``C51Learner.export_q`` files, learners, ``C51Actor``s).  The keywords, the refusals and the returned dict --
     ``stats`` with ``member``, ``by_member``, ``reports`` -- are ``evaluate_dqn_members``'; a DQN member is refused (``evaluate_dqn_members`` is
     theirs) before a context exists."""
-    from . import episodes
-    if controller not in ("combined", "first_step"):
-        raise ValueError("members are evaluated under 'combined' or 'first_step', not %r" % (controller,))
+    _check_members_controller(controller)
     if isinstance(source, DQNPopulation) and not isinstance(source, C51Population):
         raise ValueError("a DQNPopulation's members are Q-networks, not categorical (C51) policies: evaluate them with evaluate_dqn_members(pop, n_per_member, ...)")
     members = source if isinstance(source, (C51Population, list, tuple)) else [source]
@@ -2146,15 +2140,7 @@ def evaluate_c51_members(source, n_per_member, seed=0, kmax=16, max_episode_leng
         if q:
             raise ValueError("evaluate_c51_members: members %s are Q-networks, not categorical (C51) policies (one launch needs one head); evaluate them with "
                              "evaluate_dqn_members" % ", ".join(map(str, q)))
-    if traffic is not None and len(traffic) != P:
-        raise ValueError("%d traffic groups for %d members: member m is evaluated on traffic m" % (len(traffic), P))
-    ctx = ctx if ctx is not None else _capi.Context(-1)
-    pop = _actor.C51ActorPopulation(members, n_per_member, ctx, Settings)
-    stats = episodes.run_episodes(pop.n, seed=seed, controller=controller, policy=pop, ctx=ctx, kmax=kmax, max_episode_length=max_episode_length, record=record,
-                                  traffic=traffic)
-    rep_ = stats.get("report")
-    return {"stats": stats, "by_member": episodes.summary_by_member(stats, pop.P),
-            "reports": rep_.by_member(pop.P, traffic) if rep_ is not None else None}
+    return _evaluate_population(members, P, _actor.C51ActorPopulation, n_per_member, seed, kmax, max_episode_length, record, ctx, traffic, controller)
 
 
 def evaluate_dqn(source, n, seed=0, kmax=16, max_episode_length=100.0, record=None, ctx=None, traffic=None, controller="combined"):

@@ -258,6 +258,9 @@ def test_train_dqn_counts_takeovers_on_a_shielded_env():
     none = [[0] * 6] * 3
     assert learner.train_dqn(_FakeShieldedEnv(none, done, True), _fake_learner(learner.DQNLearner, []), 18)["takeover_share"] == 0.0
     assert "_TakeoverShare" in inspect.getsource(learner.train_ddpg) and "_TakeoverShare" in inspect.getsource(learner.train_dqn)
+    # (both name it, and both run the one loop that makes it)
+    assert "_train(" in inspect.getsource(learner.train_ddpg) and "_train(" in inspect.getsource(learner.train_dqn)
+    assert "_TakeoverShare(" in inspect.getsource(learner._train)
 
 
 class _FakePlainEnv:
